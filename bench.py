@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the tile-render hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-in-flight F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-in-flight F] [--dump-outputs DIR] [--full]
 
 A *step* is one render of the BASELINE.json north-star frame (configs[1]: 1920x1080, 4 bounces,
 4 samples/pixel, one light, synthetic 64x64 skin with inner+outer layer, `RayTracer::Config`
 defaults otherwise) with the flattened scene already resident in HBM; the output is the float4
-framebuffer in HBM.  Three figures describe it, all in the line:
+framebuffer in HBM.  A plain run sets up, warms up, times the K steps and prints `value` / `ms_per_step`;
+`--full` adds the other figures below (and `roofline`, `cpu_baseline`), each measured in runs of its own
+after the timed steps.  `--dump-outputs DIR` writes the frame of the last timed step to DIR/frame.npy
+(float32, H x W x 4; frames above 64 MB as a seeded sample of pixels, DIR/frame_sample.npy with the
+pixel indices in DIR/frame_sample_pixels.npy).  Three figures describe the path:
 
   value / ms_per_step   DEVICE THROUGHPUT with F frames (default 4) in flight: step k uses scene handle / stream /
                         output buffer k mod F, every frame is rendered completely (`--check` compares each buffer
@@ -25,7 +29,7 @@ rows (rank r renders tile rows r, r+N, ...), each rank renders into a packed buf
 xGMI assembles the frame on rank 0 (strong scaling: the total work is fixed); gathers overlap the renders of
 the following steps.
 
-Rank 0 prints ONE JSON line: metric/value per BASELINE.json plus `roofline` — algorithmic bytes (16 B per
+Rank 0 prints ONE JSON line: metric/value per BASELINE.json plus, with `--full`, `roofline` — algorithmic bytes (16 B per
 output pixel) over the hipEvent-measured duration of one frame's pipeline against the HBM peak, the HBM
 traffic and the VALU wave-instructions per frame from the committed PMC passes (profiles/pmc_traffic.json),
 and from those the VALU fraction against 78.6 T lane-ops/s: this path is VALU-bound, see DESIGN.md — and, at
@@ -201,6 +205,26 @@ def cpp_dropin(cfg) -> dict:
         return {"error": repr(exc)}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_PIXELS = 1 << 21  # 32 MB of float4 pixels + 16 MB of float64 indices
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, frame) -> None:
+    """Writes what the timed path hands its caller, the float4 framebuffer of the last timed step, as float32 .npy.
+    A frame above DUMP_LIMIT_BYTES is written as a fixed sample of pixels drawn with DUMP_SAMPLE_SEED (the same for
+    every run of the same workload), with the flat pixel indices beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = frame.cpu().numpy().astype(np.float32, copy=False)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), img)
+        return
+    n_px = img.shape[0] * img.shape[1]
+    pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_px, size=min(DUMP_SAMPLE_PIXELS, n_px), replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), img.reshape(n_px, 4)[pick])
+    np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), pick.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -215,6 +239,10 @@ def main() -> None:
     ap.add_argument("--check", action="store_true", help="rank 0 also renders the whole frame alone and compares bit-for-bit")
     ap.add_argument("--frames-in-flight", type=int, default=4,
                     help="frames rendered concurrently (round-robin scene handles/streams/buffers); 1 = one frame at a time")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure latency_ms, kernel.pipeline_ms, render_call, roofline and cpu_baseline after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32; a seeded sample above 64 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -342,78 +370,82 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # one frame at a time (rank-local render only): enqueue, wait, repeat — on a handle of its own with the
-    # library's defaults (a lone frame spreads itself over internal streams, mcrt_scene_set_lanes(0))
-    lat_n = max(5, min(args.steps, 30))
-    lat_target = frames[0] if world == 1 else packed[0]
+    if args.dump_outputs and rank == 0:  # before the figures below reuse frames[0]
+        dump_outputs(args.dump_outputs, frames[(args.steps - 1) % F])
+
     first, stepn = (0, 1) if world == 1 else (rank, world)
     layout = abi.LAYOUT_FRAME if world == 1 else abi.LAYOUT_PACKED
     stream = streams[0].cuda_stream
-    lone = M.DeviceScene(sd, device=local_rank)
-    for _ in range(6):  # workspace allocation, launch recording (4th render of a parameter set)
-        lone.render_device(cfg, lat_target.data_ptr(), first, stepn, layout, stream)
-    torch.cuda.synchronize()
-    t_lat = time.perf_counter()
-    for _ in range(lat_n):
-        lone.render_device(cfg, lat_target.data_ptr(), first, stepn, layout, stream)
+    latency_ms = pipeline_ms = render_call = None
+    if args.full:
+        # one frame at a time (rank-local render only): enqueue, wait, repeat — on a handle of its own with the
+        # library's defaults (a lone frame spreads itself over internal streams, mcrt_scene_set_lanes(0))
+        lat_n = max(5, min(args.steps, 30))
+        lat_target = frames[0] if world == 1 else packed[0]
+        lone = M.DeviceScene(sd, device=local_rank)
+        for _ in range(6):  # workspace allocation, launch recording (4th render of a parameter set)
+            lone.render_device(cfg, lat_target.data_ptr(), first, stepn, layout, stream)
         torch.cuda.synchronize()
-    latency_ms = (time.perf_counter() - t_lat) / lat_n * 1e3
-    lone.check()
-    lone.close()
+        t_lat = time.perf_counter()
+        for _ in range(lat_n):
+            lone.render_device(cfg, lat_target.data_ptr(), first, stepn, layout, stream)
+            torch.cuda.synchronize()
+        latency_ms = (time.perf_counter() - t_lat) / lat_n * 1e3
+        lone.check()
+        lone.close()
 
-    # device-only duration of one frame's pipeline on ONE stream: hipEvents on the launch stream
-    target = frame if world == 1 else packed[0]
-    pipeline_ms = scene.time_render_device(cfg, target.data_ptr(), max(5, min(args.steps, 50)), first, stepn, layout, stream)
-    torch.cuda.synchronize()
+        # device-only duration of one frame's pipeline on ONE stream: hipEvents on the launch stream
+        target = frame if world == 1 else packed[0]
+        pipeline_ms = scene.time_render_device(cfg, target.data_ptr(), max(5, min(args.steps, 50)), first, stepn, layout, stream)
+        torch.cuda.synchronize()
 
-    # wall time of one TileRenderer::render() call — host scene in, a fresh host Image out
-    render_call = None
-    if world == 1 and rank == 0:
-        def timed(calls: int, **kw):
-            walls, splits = [], []
-            for i in range(2 + calls):
+        # wall time of one TileRenderer::render() call — host scene in, a fresh host Image out
+        if world == 1 and rank == 0:
+            def timed(calls: int, **kw):
+                walls, splits = [], []
+                for i in range(2 + calls):
+                    t0 = time.perf_counter()
+                    M.TileRenderer.render(sd, cfg, **kw)
+                    dt = (time.perf_counter() - t0) * 1e3
+                    if M.TileRenderer.lastErrors():
+                        raise SystemExit(f"render failed: {M.TileRenderer.lastErrors()}")
+                    if i >= 2:
+                        walls.append(dt)
+                        splits.append(M.TileRenderer.lastTimings())
+                return walls, splits
+
+            n_calls = max(10, min(args.steps, 20))
+            walls, splits = timed(n_calls)  # out=None: a new Image(W, H) = (0,0,0,1) per call, inside the timed region
+            host = np.zeros((h, w, 4), np.float32)
+            reused, _ = timed(n_calls, out=host)
+            untouched = []
+            import mmap
+            for _ in range(5):  # a destination whose pages were never touched (a fresh anonymous mapping): the runtime's pinning faults them in
+                mm = mmap.mmap(-1, h * w * 16)
+                fresh = np.frombuffer(mm, np.float32).reshape(h, w, 4)
                 t0 = time.perf_counter()
-                M.TileRenderer.render(sd, cfg, **kw)
-                dt = (time.perf_counter() - t0) * 1e3
-                if M.TileRenderer.lastErrors():
-                    raise SystemExit(f"render failed: {M.TileRenderer.lastErrors()}")
-                if i >= 2:
-                    walls.append(dt)
-                    splits.append(M.TileRenderer.lastTimings())
-            return walls, splits
-
-        n_calls = max(10, min(args.steps, 20))
-        walls, splits = timed(n_calls)  # out=None: a new Image(W, H) = (0,0,0,1) per call, inside the timed region
-        host = np.zeros((h, w, 4), np.float32)
-        reused, _ = timed(n_calls, out=host)
-        untouched = []
-        import mmap
-        for _ in range(5):  # a destination whose pages were never touched (a fresh anonymous mapping): the runtime's pinning faults them in
-            mm = mmap.mmap(-1, h * w * 16)
-            fresh = np.frombuffer(mm, np.float32).reshape(h, w, 4)
-            t0 = time.perf_counter()
-            M.TileRenderer.render(sd, cfg, out=fresh)
-            untouched.append((time.perf_counter() - t0) * 1e3)
-            del fresh
-            mm.close()
-        med = statistics.median(walls)
-        render_call = {
-            "ms": round(med, 4),
-            "mpixels_per_s": round(w * h / med / 1e3, 2),
-            "calls": len(walls),
-            "min_ms": round(min(walls), 4),
-            "split_ms": {k: round(statistics.median(t[k] for t in splits), 4) for k in splits[0]},
-            "reused_buffer_ms": round(statistics.median(reused), 4),
-            "untouched_buffer_ms": round(statistics.median(untouched), 4),
-            "what": "median wall time of TileRenderer.render (mcrt_render behind it) returning a FRESH Image per call, as the reference's call "
-                    "site gets one: Image(W,H) allocation and (0,0,0,1) fill + scene flatten + upload + kernels + row-group downloads "
-                    "overlapping the render + progress bookkeeping; reused_buffer_ms = the same call into one caller-owned buffer; "
-                    "untouched_buffer_ms = into never-touched pages (a fresh anonymous mapping, what a bare malloc behind the C ABI is); split_ms = the "
-                    "library's own split of the C call (mcrt_last_timings)",
-        }
-        if not args.quick_host:
-            render_call["cold_process"] = cold_call(args.workload)
-            render_call["cpp_dropin"] = cpp_dropin(cfg)
+                M.TileRenderer.render(sd, cfg, out=fresh)
+                untouched.append((time.perf_counter() - t0) * 1e3)
+                del fresh
+                mm.close()
+            med = statistics.median(walls)
+            render_call = {
+                "ms": round(med, 4),
+                "mpixels_per_s": round(w * h / med / 1e3, 2),
+                "calls": len(walls),
+                "min_ms": round(min(walls), 4),
+                "split_ms": {k: round(statistics.median(t[k] for t in splits), 4) for k in splits[0]},
+                "reused_buffer_ms": round(statistics.median(reused), 4),
+                "untouched_buffer_ms": round(statistics.median(untouched), 4),
+                "what": "median wall time of TileRenderer.render (mcrt_render behind it) returning a FRESH Image per call, as the reference's call "
+                        "site gets one: Image(W,H) allocation and (0,0,0,1) fill + scene flatten + upload + kernels + row-group downloads "
+                        "overlapping the render + progress bookkeeping; reused_buffer_ms = the same call into one caller-owned buffer; "
+                        "untouched_buffer_ms = into never-touched pages (a fresh anonymous mapping, what a bare malloc behind the C ABI is); split_ms = the "
+                        "library's own split of the C call (mcrt_last_timings)",
+            }
+            if not args.quick_host:
+                render_call["cold_process"] = cold_call(args.workload)
+                render_call["cpp_dropin"] = cpp_dropin(cfg)
 
     check = None
     if args.check and rank == 0:
@@ -425,54 +457,6 @@ def main() -> None:
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         mpix = w * h * args.steps / elapsed / 1e6
-        owned_rows = scene.owned_pixel_rows(cfg, first, stepn)
-        owned_px = min(owned_rows, h) * w if world > 1 else w * h
-        algo_bytes = 16.0 * owned_px  # 16 B written per output pixel, ~0 read
-        achieved = algo_bytes / (pipeline_ms * 1e-3) / 1e9
-        # counters of one frame of this workload from the committed rocprofv3 --pmc passes (tools/pmc_run.sh)
-        pmc = {}
-        prof = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(prof):
-            try:
-                pmc = json.load(open(prof)).get(args.workload) or {}
-                if not isinstance(pmc, dict):  # older files held the traffic alone
-                    pmc = {"hbm_bytes": pmc}
-            except Exception:
-                pmc = {}
-        traffic = pmc.get("hbm_bytes")
-        valu = pmc.get("valu_wave_instructions")
-        src_hash = kernel_source_hash()
-        pmc_stale = bool(pmc) and pmc.get("source_hash") != src_hash  # the counters were taken on other kernel sources
-        roof = {
-            "bound": "hbm",
-            "achieved": round(achieved, 2),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 5),
-            "traffic": traffic,
-            "kernel": "one frame's whole pipeline on one stream (kernel.pipeline_ms; the per-kernel split is in " + str(pmc.get("profile", "profiles/")) + ")",
-            "algorithmic_bytes": algo_bytes,
-            "counters": {"from": pmc.get("profile"), "source_hash": pmc.get("source_hash"), "this_build": src_hash, "stale": pmc_stale} if pmc else None,
-            "note": "algorithmic bytes = 16 B x output pixels of the frame; the path is VALU/latency-bound by construction (DESIGN.md), "
-                    "so the HBM fraction is << 1 %: the VALU figures are the ones that describe kernel quality",
-        }
-        # frames that share the device are launched in other shapes (fewer workgroups, one wave per tile stream): their own
-        # counters when the PMC passes took them (tools/collect_profiles.sh), else the lone frame's
-        piped = pmc.get("pipelined") if isinstance(pmc.get("pipelined"), dict) and pmc["pipelined"].get("source_hash") == pmc.get("source_hash") else None
-        traffic_p = (piped or {}).get("hbm_bytes", traffic)
-        valu_p = (piped or {}).get("valu_wave_instructions", valu)
-        if traffic and world == 1:
-            roof["traffic_over_algorithmic"] = round(traffic / algo_bytes, 2)
-            roof["hbm_traffic_gbs_pipelined"] = round(traffic_p / (ms_per_step * 1e-3) / 1e9, 1)
-        if valu and world == 1:
-            lane_ops = valu * 64.0  # a wave-instruction = 64 lane-ops
-            roof["valu_wave_instructions"] = valu
-            roof["valu_peak_tlaneops"] = VALU_PEAK_TLOPS
-            roof["valu_frac"] = round(lane_ops / (pipeline_ms * 1e-3) / (VALU_PEAK_TLOPS * 1e12), 4)  # one frame at a time
-            roof["valu_frac_pipelined"] = round(valu_p * 64.0 / (ms_per_step * 1e-3) / (VALU_PEAK_TLOPS * 1e12), 4)  # at `value`
-            if piped:
-                roof["pipelined_counters"] = {"traffic": traffic_p, "valu_wave_instructions": valu_p,
-                                              "note": "one frame launched as `value`'s frames are (MCRT_SHARED_GRIDS=1)"}
         line = {
             "metric": "Mpixels/s",
             "value": round(mpix, 2),
@@ -497,18 +481,67 @@ def main() -> None:
                 "frames_in_flight": F,
                 "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
             },
-            "latency_ms": round(latency_ms, 4),
-            "latency_mpixels_per_s": round(w * h / latency_ms / 1e3, 2),
-            "kernel": {"pipeline_ms": round(pipeline_ms, 4),
-                       "note": "hipEvents on the launch stream around one frame's whole pipeline on one stream (plan_tiles, "
-                               "primary, [ao,] lit, resolve)"},
-            "roofline": roof,
         }
+        if args.full:
+            owned_rows = scene.owned_pixel_rows(cfg, first, stepn)
+            owned_px = min(owned_rows, h) * w if world > 1 else w * h
+            algo_bytes = 16.0 * owned_px  # 16 B written per output pixel, ~0 read
+            achieved = algo_bytes / (pipeline_ms * 1e-3) / 1e9
+            # counters of one frame of this workload from the committed rocprofv3 --pmc passes (tools/pmc_run.sh)
+            pmc = {}
+            prof = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(prof):
+                try:
+                    pmc = json.load(open(prof)).get(args.workload) or {}
+                    if not isinstance(pmc, dict):  # older files held the traffic alone
+                        pmc = {"hbm_bytes": pmc}
+                except Exception:
+                    pmc = {}
+            traffic = pmc.get("hbm_bytes")
+            valu = pmc.get("valu_wave_instructions")
+            src_hash = kernel_source_hash()
+            pmc_stale = bool(pmc) and pmc.get("source_hash") != src_hash  # the counters were taken on other kernel sources
+            roof = {
+                "bound": "hbm",
+                "achieved": round(achieved, 2),
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5),
+                "traffic": traffic,
+                "kernel": "one frame's whole pipeline on one stream (kernel.pipeline_ms; the per-kernel split is in " + str(pmc.get("profile", "profiles/")) + ")",
+                "algorithmic_bytes": algo_bytes,
+                "counters": {"from": pmc.get("profile"), "source_hash": pmc.get("source_hash"), "this_build": src_hash, "stale": pmc_stale} if pmc else None,
+                "note": "algorithmic bytes = 16 B x output pixels of the frame; the path is VALU/latency-bound by construction (DESIGN.md), "
+                        "so the HBM fraction is << 1 %: the VALU figures are the ones that describe kernel quality",
+            }
+            # frames that share the device are launched in other shapes (fewer workgroups, one wave per tile stream): their own
+            # counters when the PMC passes took them (tools/collect_profiles.sh), else the lone frame's
+            piped = pmc.get("pipelined") if isinstance(pmc.get("pipelined"), dict) and pmc["pipelined"].get("source_hash") == pmc.get("source_hash") else None
+            traffic_p = (piped or {}).get("hbm_bytes", traffic)
+            valu_p = (piped or {}).get("valu_wave_instructions", valu)
+            if traffic and world == 1:
+                roof["traffic_over_algorithmic"] = round(traffic / algo_bytes, 2)
+                roof["hbm_traffic_gbs_pipelined"] = round(traffic_p / (ms_per_step * 1e-3) / 1e9, 1)
+            if valu and world == 1:
+                lane_ops = valu * 64.0  # a wave-instruction = 64 lane-ops
+                roof["valu_wave_instructions"] = valu
+                roof["valu_peak_tlaneops"] = VALU_PEAK_TLOPS
+                roof["valu_frac"] = round(lane_ops / (pipeline_ms * 1e-3) / (VALU_PEAK_TLOPS * 1e12), 4)  # one frame at a time
+                roof["valu_frac_pipelined"] = round(valu_p * 64.0 / (ms_per_step * 1e-3) / (VALU_PEAK_TLOPS * 1e12), 4)  # at `value`
+                if piped:
+                    roof["pipelined_counters"] = {"traffic": traffic_p, "valu_wave_instructions": valu_p,
+                                                  "note": "one frame launched as `value`'s frames are (MCRT_SHARED_GRIDS=1)"}
+            line["latency_ms"] = round(latency_ms, 4)
+            line["latency_mpixels_per_s"] = round(w * h / latency_ms / 1e3, 2)
+            line["kernel"] = {"pipeline_ms": round(pipeline_ms, 4),
+                              "note": "hipEvents on the launch stream around one frame's whole pipeline on one stream (plan_tiles, "
+                                      "primary, [ao,] lit, resolve)"}
+            line["roofline"] = roof
         if render_call is not None:
             line["render_call"] = render_call
         if check is not None:
             line["check_assembled_frame_equals_single_gpu_render"] = check
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.workload, gpu_frame=frames[0].cpu().numpy())
             except Exception as exc:  # the baseline is a report, never a reason to lose the GPU number

@@ -20,13 +20,36 @@ def oracle():
     return oraclelib.Oracle()
 
 
+_REFERENCE_LOGS = {}
+
+
 @pytest.fixture(scope="session")
-def reference():
+def live_reference():
     import oraclelib
 
-    if not oraclelib.Reference.available():
-        pytest.skip("compiled reference (oracle/_ref/libmcref.so) not built here")
-    return oraclelib.Reference()
+    return oraclelib.Reference() if oraclelib.Reference.available() else None
+
+
+@pytest.fixture
+def reference(request, live_reference):
+    """The compiled reference (oracle/_ref/libmcref.so) where it was built; elsewhere its recorded answers to the
+    same calls (tests/golden/reference_outputs.npz).  MCRT_RECORD_REFERENCE=1 records them anew from the former."""
+    import oraclelib
+
+    if os.environ.get("MCRT_RECORD_REFERENCE") == "1":
+        if live_reference is None:
+            pytest.fail("MCRT_RECORD_REFERENCE=1 needs the compiled reference (oracle/_ref/libmcref.so)")
+        return oraclelib.RecordingReference(live_reference, _REFERENCE_LOGS.setdefault(request.node.name, []))
+    if live_reference is not None:
+        return live_reference
+    return oraclelib.ReplayReference(request.node.name)
+
+
+def pytest_sessionfinish(session, exitstatus):
+    if _REFERENCE_LOGS and exitstatus == 0:
+        import oraclelib
+
+        oraclelib.write_reference_outputs(_REFERENCE_LOGS)
 
 
 @pytest.fixture(scope="session")

@@ -3,6 +3,8 @@ been built in the dev container, the compiled reference (oracle/_ref/libmcref.so
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -193,3 +195,148 @@ class Reference(CpuLib):
         if self._f("builtin_pose")(index, abi.fptr(out)) != 0:
             raise IndexError(index)
         return out
+
+
+# ---- the compiled reference's answers, stored: the oracle-vs-reference tests where oracle/_ref cannot be built ----
+REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "reference_outputs.npz")
+_REPLAYED = ("builtin_pose", "build_skin_scene", "build_default_scene", "render", "intersect", "seed_cast")
+
+
+STORED_IN_FULL_BYTES = 256  # larger answers (and structured ones) are stored as digests (RecordedArray)
+
+
+def _canonical_floats(a) -> np.ndarray:
+    """The bits scenes.assert_bit_equal compares: float32, with every NaN alike (NaN payloads may differ)."""
+    f = np.array(a, np.float32, order="C")
+    f[np.isnan(f)] = np.float32("nan")
+    return f
+
+
+def digest(a, kind: str) -> str:
+    """SHA-256 of what one comparison of the tests looks at: "bytes" = the raw bytes (scene data), "floats" = the
+    canonical float32 bits (renders), "hits" = hit flags, then t / point / normal / texture_color / outer flag of the
+    rows that hit (what scenes.assert_hits_equal compares)."""
+    h = hashlib.sha256()
+    if kind == "bytes":
+        h.update(np.ascontiguousarray(a).tobytes())
+    elif kind == "floats":
+        h.update(_canonical_floats(a).tobytes())
+    elif kind == "hits":
+        m = a["hit"] != 0
+        h.update(np.ascontiguousarray(a["hit"]).tobytes())
+        for f in ("t", "point", "normal", "texture_color"):
+            h.update(_canonical_floats(a[f][m]).tobytes())
+        h.update(np.ascontiguousarray(a["is_outer_layer"][m]).tobytes())
+    else:
+        raise ValueError(kind)
+    return h.hexdigest()
+
+
+class RecordedArray:
+    """A large reference answer as stored: its shape, dtype and the digest of what its comparison looks at.
+    matches(a, kind) holds exactly when that comparison between `a` and the answer itself would pass."""
+
+    def __init__(self, shape, dtype: str, kind: str, sha256: str):
+        self.shape, self.dtype, self.kind, self.sha256 = tuple(shape), dtype, kind, sha256
+
+    def matches(self, a, kind: str) -> bool:
+        if kind != self.kind:
+            raise ValueError(f"a {self.kind} digest was recorded for this answer, not a {kind} one")
+        if kind == "bytes":
+            return digest(a, kind) == self.sha256
+        a = np.asarray(a)
+        if kind == "hits" and str(a.dtype) != self.dtype:
+            return False
+        return a.shape == self.shape and digest(a, kind) == self.sha256
+
+
+# which comparison each method's answers meet in the tests (scenes.assert_bit_equal / assert_hits_equal / same_bytes)
+_DIGEST_KIND = {"render": "floats", "intersect": "hits"}
+
+
+def _to_spec(value, blob: bytearray, kind: str):
+    """A reference return value as JSON-able structure: small numpy leaves are packed into `blob`, larger ones are
+    stored as a RecordedArray digest of `kind`."""
+    if isinstance(value, np.ndarray) and (value.nbytes > STORED_IN_FULL_BYTES or value.dtype.fields):
+        return {"recorded": {"shape": list(value.shape), "dtype": str(value.dtype), "kind": kind, "sha256": digest(value, kind)}}
+    if isinstance(value, (np.ndarray, np.generic)):
+        arr = np.ascontiguousarray(value)
+        spec = {"array" if isinstance(value, np.ndarray) else "scalar": [len(blob), arr.dtype.str, list(arr.shape)]}
+        blob += arr.tobytes()
+        return spec
+    if isinstance(value, dict):
+        return {"dict": {k: _to_spec(v, blob, kind) for k, v in value.items()}}
+    if isinstance(value, (list, tuple)):
+        return {"list": [_to_spec(v, blob, kind) for v in value]}
+    if value is None or isinstance(value, (bool, int, float)):
+        return {"value": value}
+    raise TypeError(f"cannot store a {type(value).__name__}")
+
+
+def _from_spec(spec, blob: np.ndarray):
+    if "recorded" in spec:
+        return RecordedArray(**spec["recorded"])
+    for key in ("array", "scalar"):
+        if key in spec:
+            off, dtype, shape = spec[key]
+            arr = np.frombuffer(blob, np.dtype(dtype), count=int(np.prod(shape, dtype=np.int64)), offset=off).reshape(shape).copy()
+            return arr if key == "array" else arr[()]
+    if "dict" in spec:
+        return {k: _from_spec(v, blob) for k, v in spec["dict"].items()}
+    if "list" in spec:
+        return [_from_spec(v, blob) for v in spec["list"]]
+    return spec["value"]
+
+
+class RecordingReference:
+    """The live reference, logging every answer of one test (conftest writes the log to REF_OUTPUTS)."""
+
+    def __init__(self, live: Reference, log: list):
+        self._live, self._log = live, log
+
+    def __getattr__(self, name):
+        if name not in _REPLAYED:
+            raise AttributeError(f"{name} is not recorded (add it to oraclelib._REPLAYED)")
+        fn = getattr(self._live, name)
+
+        def call(*args, **kw):
+            out = fn(*args, **kw)
+            self._log.append((name, out))
+            return out
+        return call
+
+
+def write_reference_outputs(logs: dict, path: str = REF_OUTPUTS) -> None:
+    blob, index = bytearray(), {}
+    for test, calls in sorted(logs.items()):
+        index[test] = [[name, _to_spec(out, blob, _DIGEST_KIND.get(name, "bytes"))] for name, out in calls]
+    np.savez_compressed(path, index=np.frombuffer(json.dumps(index, separators=(",", ":")).encode(), np.uint8),
+                        blob=np.frombuffer(bytes(blob), np.uint8))
+
+
+class ReplayReference:
+    """Answers one test's reference calls, in order, from REF_OUTPUTS (recorded from the compiled reference by
+    running the same test with MCRT_RECORD_REFERENCE=1 where oracle/_ref is built)."""
+
+    _store = None
+
+    def __init__(self, test: str):
+        if ReplayReference._store is None:
+            z = np.load(REF_OUTPUTS)
+            ReplayReference._store = (json.loads(z["index"].tobytes()), z["blob"])
+        index, self._blob = ReplayReference._store
+        if test not in index:
+            raise KeyError(f"{os.path.relpath(REF_OUTPUTS, ROOT)} holds no reference answers for {test}: record them again")
+        self._calls, self._test, self._n = index[test], test, 0
+
+    def __getattr__(self, name):
+        if name not in _REPLAYED:
+            raise AttributeError(name)
+
+        def call(*args, **kw):
+            assert self._n < len(self._calls), f"{self._test}: more reference calls than were recorded"
+            recorded, spec = self._calls[self._n]
+            assert recorded == name, f"{self._test}: call {self._n} is {name}, recorded {recorded}: record the answers again"
+            self._n += 1
+            return _from_spec(spec, self._blob)
+        return call

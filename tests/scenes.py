@@ -7,6 +7,7 @@ import numpy as np
 
 import minecraftskin_raytracer_amd as M
 from minecraftskin_raytracer_amd import abi
+from oraclelib import RecordedArray
 
 f32 = np.float32
 
@@ -69,7 +70,22 @@ def bits(a) -> np.ndarray:
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def _recorded_mismatch(what, a, b) -> str:
+    return (f"{what}: differs from the reference's recorded answer (shape {np.shape(a)} vs {b.shape}); the live "
+            "reference (oracle/_ref) shows where")
+
+
+def same_bytes(a, b) -> bool:
+    """np.asarray(a).tobytes() == np.asarray(b).tobytes(), `b` also a RecordedArray."""
+    if isinstance(b, RecordedArray):
+        return b.matches(a, "bytes")
+    return np.asarray(a).tobytes() == np.asarray(b).tobytes()
+
+
 def assert_bit_equal(a, b, what=""):
+    if isinstance(b, RecordedArray):  # a reference answer stored as its digest (oraclelib.ReplayReference)
+        assert b.matches(a, "floats"), _recorded_mismatch(what, a, b)
+        return
     a = np.ascontiguousarray(a, np.float32)
     b = np.ascontiguousarray(b, np.float32)
     assert a.shape == b.shape, (what, a.shape, b.shape)
@@ -83,6 +99,9 @@ def assert_bit_equal(a, b, what=""):
 
 
 def assert_hits_equal(a, b, what=""):
+    if isinstance(b, RecordedArray):
+        assert b.matches(a, "hits"), _recorded_mismatch(what, a, b)
+        return
     assert a.dtype == b.dtype and a.shape == b.shape
     assert np.array_equal(a["hit"], b["hit"]), what + " hit flags"
     m = a["hit"] != 0

@@ -1,6 +1,10 @@
-"""Dev-container only (skipped where oracle/_ref/libmcref.so was not built): the oracle restatement
-against the compiled reference itself, bit for bit, over a randomised sweep of scenes, poses,
-configs and hand-built edge cases the fixtures do not enumerate."""
+"""The oracle restatement against the compiled reference itself, bit for bit, over a randomised sweep of
+scenes, poses, configs and hand-built edge cases the fixtures do not enumerate.  Where oracle/_ref/libmcref.so
+was not built, the `reference` fixture answers with the reference's recorded answers to the same calls
+(tests/golden/reference_outputs.npz); after a change to these tests, record them again where it was built:
+
+    MCRT_RECORD_REFERENCE=1 python -m pytest tests/test_oracle_vs_ref.py
+"""
 import numpy as np
 import pytest
 
@@ -18,9 +22,9 @@ def test_scene_builder_equals_reference_mesh_builder(mcrt, reference):
             assert len(mine["meshes"]) == len(ref["meshes"])
             for a, b in zip(mine["meshes"], ref["meshes"]):
                 for k in a:
-                    assert np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), (kind, i, k)
+                    assert scenes.same_bytes(a[k], b[k]), (kind, i, k)
             for a, b in zip(mine["textures"], ref["textures"]):
-                assert (a["width"], a["height"]) == (b["width"], b["height"]) and a["pixels"].tobytes() == b["pixels"].tobytes()
+                assert (a["width"], a["height"]) == (b["width"], b["height"]) and scenes.same_bytes(a["pixels"], b["pixels"])
     a, b = mcrt.MeshBuilder.buildDefaultScene().to_numpy(), reference.build_default_scene()
     assert len(a["meshes"]) == len(b["meshes"]) == 6
 

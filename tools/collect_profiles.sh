@@ -31,16 +31,16 @@ for PAIR in gui_defaults:gui 4k_b4_spp4_S64:4k_b4 4k_b8_spp16_S64:4k 8k_b8_spp64
   echo "pmc $W done"
 done
 cp $R/profiles/pmc_traffic.json $O/pmc_traffic.json
-timeout -k 10 500 python3 bench.py --steps 50 --warmup 5 --check > $O/bench.json 2> $O/bench.err || echo "bench failed"
-timeout -k 10 400 python3 bench.py --steps 50 --warmup 5 --frames-in-flight 1 --no-cpu-baseline --quick-host > $O/bench_one_frame_at_a_time.json 2>> $O/bench.err || echo "bench F=1 failed"
+timeout -k 10 500 python3 bench.py --full --steps 50 --warmup 5 --check > $O/bench.json 2> $O/bench.err || echo "bench failed"
+timeout -k 10 400 python3 bench.py --full --steps 50 --warmup 5 --frames-in-flight 1 --no-cpu-baseline --quick-host > $O/bench_one_frame_at_a_time.json 2>> $O/bench.err || echo "bench F=1 failed"
 : > $O/other_workloads.jsonl
 for W in gui_defaults 256_b1_spp1_S64 4k_b4_spp4_S64 4k_b8_spp16_S64 8k_b8_spp64_S32; do
-  timeout -k 10 600 python3 bench.py --workload $W --steps 10 --warmup 2 --quick-host --check >> $O/other_workloads.jsonl 2>> $O/bench.err || echo "bench $W failed"
+  timeout -k 10 600 python3 bench.py --full --workload $W --steps 10 --warmup 2 --quick-host --check >> $O/other_workloads.jsonl 2>> $O/bench.err || echo "bench $W failed"
   echo "bench $W done"
 done
 cd /tmp
 # the same bench command under the kernel tracer (four frames in flight: kernels of different frames overlap)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --quick-host > $O/trace_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --quick-host > $O/trace_bench.log 2>&1
 python3 $R/tools/trace_summary.py $O/trace_bench 40 > $O/kernel_timeline_bench.txt 2>&1
 # one lane: the plain dependency chain of a frame, kernel by kernel
 MCRT_LANES=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_1lane -- python3 $R/tools/gpu_case.py base 10 > $O/trace_1lane.log 2>&1
