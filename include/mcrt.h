@@ -220,6 +220,28 @@ int mcrt_scene_set_lanes(mcrt_scene* scene, int lanes);
 int mcrt_render_device_ex(mcrt_scene* scene, const mcrt_config* cfg, int tile_row_first, int tile_row_step,
                           int layout, float* d_out_f32, uint8_t* d_out_rgba8, void* stream);
 
+/* ---- batches: many small frames in one launch sequence -------------------------------------------------------------
+ * Frame i = exactly what mcrt_render_device_ex(scenes[i], cfg, 0, 1, MCRT_LAYOUT_FRAME, ...) would write, bit for bit.  All
+ * frames share cfg and the device of scenes[0].  Frame i lives at d_out_f32 + i*frame_stride_pixels*4 floats and/or
+ * d_out_rgba8 + i*frame_stride_pixels*4 bytes (either output may be NULL, not both; frame_stride_pixels >= width*height);
+ * the pixels between frames are not written.  Asynchronous on `stream` (not into a graph being recorded on it).
+ * Every frame that takes one pass on the flat pipeline goes through batched kernels, blockIdx.y = frame: one launch per
+ * stage for up to 256 frames (larger batches take several launch sequences); any other frame (one that needs several
+ * passes, or a config of the general variants such as max_bounces > 8) is enqueued on its own, one after the other.
+ * Each handle's earlier renders are waited for and its next render waits for the batch, as for mcrt_render_device.
+ * MCRT_ERR_INVALID, before any device work: n_frames < 0, a NULL entry, both outputs NULL, a stride below width*height,
+ * a handle listed twice (each handle owns one workspace), handles on different devices, max_bounces above 4000.
+ * Zero-size frames (width, height or tile_size <= 0) and n_frames = 0: MCRT_OK, nothing written. */
+int mcrt_render_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, float* d_out_f32, uint8_t* d_out_rgba8,
+                             size_t frame_stride_pixels, void* stream);
+/* One-shot host form: n_frames scene descriptions -> n_frames*width*height*4 floats (out_rgba) and/or bytes (out_rgba8),
+ * frame after frame, rendered on `device` with pooled handles, like mcrt_render. */
+int mcrt_render_batch(const mcrt_scene_desc* const* scenes, int n_frames, const mcrt_config* cfg, float* out_rgba,
+                      uint8_t* out_rgba8, int device);
+/* How the last batch call on this thread ran: frames taken by the batched kernels, and launch sequences enqueued (1 when
+ * the whole batch went through the batched kernels in one; each frame enqueued on its own counts one). */
+int mcrt_last_batch_info(int* batched_frames, int* launch_sequences);
+
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);
 

@@ -11,11 +11,13 @@ from .api import (  # noqa: F401
     device_count,
     flatten,
     getBuiltinPoses,
+    last_batch_info,
     probe_detmath,
     probe_detmath_range,
     probe_mt_uniform,
     quantize_rgba8,
     quantize_rgba8_device,
+    render_batch_device,
     render_png,
     trim,
     unpack_rows_device,
@@ -25,4 +27,5 @@ __all__ = [
     "Config", "Mesh", "Scene", "Texture", "synthetic_skin", "DeviceScene", "MeshBuilder", "SceneDesc",
     "TileRenderer", "device_count", "flatten", "getBuiltinPoses", "probe_detmath", "probe_detmath_range",
     "probe_mt_uniform", "quantize_rgba8", "quantize_rgba8_device", "unpack_rows_device", "ImageWriter", "render_png", "assemble_frame_device", "trim",
+    "render_batch_device", "last_batch_info",
 ]

@@ -221,6 +221,32 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderBatch(scenes, config: Config, device: int = 0, rgba8: bool = False) -> np.ndarray:
+        """N frames of one config in one call (mcrt_render_batch): frame i equals ``render(scenes[i], config)`` bit for bit
+        (or ``renderRGBA8`` with ``rgba8``).  Returns (N, H, W, 4) float32, or uint8 with ``rgba8``.  Small frames go
+        through batched kernels, one launch sequence for the whole batch; ``lastBatchInfo()`` tells how it ran.
+        Unlike ``render``, failures raise ``McrtError``."""
+        descs = [_as_desc(s) for s in scenes]
+        n = len(descs)
+        w, h = max(config.width, 0), max(config.height, 0)
+        dtype = np.uint8 if rgba8 else np.float32
+        out = np.zeros((n, h, w, 4), dtype)
+        out[..., 3] = 255 if rgba8 else 1.0  # Image(w,h): default Color() = (0,0,0,1)
+        c = config.to_c()
+        ptrs = [d.ptr for d in descs]
+        arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*ptrs)
+        f = None if rgba8 else abi.fptr(out)
+        b = out.ctypes.data_as(C.POINTER(C.c_uint8)) if rgba8 else None
+        check(load().mcrt_render_batch(arr, n, C.byref(c), f, b, int(device)))
+        return out
+
+    @staticmethod
+    def lastBatchInfo() -> dict:
+        """How the last batch call on this thread ran (mcrt_last_batch_info): ``batched_frames`` taken by the batched
+        kernels and ``launch_sequences`` enqueued (1 when the whole batch went through them at once)."""
+        return last_batch_info()
+
+    @staticmethod
     def lastErrors() -> List[Tuple[int, str]]:
         return list(TileRenderer._errors)
 
@@ -344,6 +370,36 @@ class DeviceScene:
         c = config.to_c()
         check(load().mcrt_probe_trace(self._h, C.byref(c), abi.fptr(rays), len(rays), depth, abi.fptr(out)))
         return out
+
+
+def render_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, out_f32_ptr: int = 0, out_rgba8_ptr: int = 0,
+                        frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
+    """N frames of one config from resident scenes into device memory, one launch sequence (mcrt_render_batch_device).
+    Frame i is written at ``out_f32_ptr + i * frame_stride_pixels * 16`` bytes and/or ``out_rgba8_ptr + i *
+    frame_stride_pixels * 4``; ``frame_stride_pixels`` defaults to width * height.  Asynchronous on ``stream``."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    if not out_f32_ptr and not out_rgba8_ptr:
+        raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
+    if stride < px:
+        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    c = config.to_c()
+    check(load().mcrt_render_batch_device(arr, n, C.byref(c), C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None),
+                                          stride, C.c_void_p(stream)))
+
+
+def last_batch_info() -> dict:
+    """mcrt_last_batch_info: ``{"batched_frames": ..., "launch_sequences": ...}`` of the last batch call on this thread."""
+    f, q = C.c_int(), C.c_int()
+    load().mcrt_last_batch_info(C.byref(f), C.byref(q))
+    return {"batched_frames": int(f.value), "launch_sequences": int(q.value)}
 
 
 def unpack_rows_device(config: Config, first: int, step: int, packed_ptr: int, frame_ptr: int, stream: int = 0) -> None:

@@ -1695,3 +1695,258 @@ int mcrt_probe_detmath_range(int device, int op, uint32_t lo_bits, uint32_t hi_b
 }
 
 }  // extern "C"
+
+// ---- batches: N frames of one config in one launch sequence (mcrt_render_batch_device) -----------------------------
+namespace {
+thread_local int g_batch_frames = 0, g_batch_sequences = 0;
+
+// The parameter tables of the batched launches, per device: a ring of slots, each a device buffer, its pinned host
+// staging and an event recorded behind the launches that read it.  A slot is refilled only after that event: a table
+// is never overwritten while an earlier batch — on any stream — may still read it.
+struct TableSlot {
+    DeviceBuffer dev;
+    void* host = nullptr;
+    size_t host_bytes = 0;
+    hipEvent_t done = nullptr;
+    bool used = false;  // `done` has been recorded
+    bool busy = false;  // being filled by a thread
+};
+constexpr int kTableSlots = 8;
+struct DeviceTables {
+    TableSlot slot[kTableSlots];
+    int next = 0;
+};
+std::mutex g_table_mutex;
+std::vector<DeviceTables*> g_tables;  // by device; a few hundred KB each, kept for the process
+
+TableSlot* acquire_table_slot(int device) {
+    std::lock_guard<std::mutex> lock(g_table_mutex);
+    if (g_tables.size() <= static_cast<size_t>(device)) g_tables.resize(static_cast<size_t>(device) + 1, nullptr);
+    if (!g_tables[static_cast<size_t>(device)]) g_tables[static_cast<size_t>(device)] = new DeviceTables();
+    DeviceTables& t = *g_tables[static_cast<size_t>(device)];
+    for (int k = 0; k < kTableSlots; ++k) {
+        const int i = (t.next + k) % kTableSlots;
+        if (t.slot[i].busy) continue;
+        t.slot[i].busy = true;
+        t.next = (i + 1) % kTableSlots;
+        return &t.slot[i];
+    }
+    return nullptr;
+}
+void release_table_slot(TableSlot* s) {
+    std::lock_guard<std::mutex> lock(g_table_mutex);
+    s->busy = false;
+}
+
+// one launch sequence for the frames p[0..m) of the handles sc[0..m), all eligible (batch_eligible) and prepared on lane 0
+int launch_batch_sequence(mcrt_scene* const* sc, RenderParams* p, int m, int device, hipStream_t stream) {
+    BatchPlan plan;
+    {
+        const bool others = device_shared(sc[0]);
+        if (plan_batch(p, m, others, plan) != hipSuccess) return fail(MCRT_ERR_HIP, "internal error: the frames of a batch do not share their launch shapes");
+    }
+    // tile seeds: kept per lane with the key they were made for, re-made only for the frames whose key changed
+    std::vector<int> stale;
+    for (int i = 0; i < m; ++i)
+        if (p[i].tile_rng && !(rng_key_of(p[i]) == sc[i]->lanes[0].rng_key)) stale.push_back(i);
+    const size_t n_rows = static_cast<size_t>(m) + stale.size();
+    const size_t bytes = n_rows * sizeof(RenderParams);
+    TableSlot* slot = acquire_table_slot(device);
+    if (!slot) return fail(MCRT_ERR_HIP, "too many batch calls filling parameter tables at once");
+    struct Release {
+        TableSlot* s;
+        ~Release() { release_table_slot(s); }
+    } release{slot};
+    if (slot->used) HIP_TRY(hipEventSynchronize(slot->done));  // the last batch that read this slot has finished
+    if (!slot->done) HIP_TRY(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    if (slot->host_bytes < bytes) {
+        if (slot->host) (void)hipHostFree(slot->host);
+        slot->host = nullptr;
+        slot->host_bytes = 0;
+        HIP_TRY(hipHostMalloc(&slot->host, bytes, hipHostMallocDefault));
+        slot->host_bytes = bytes;
+    }
+    HIP_TRY(slot->dev.reserve(bytes));
+    RenderParams* host = static_cast<RenderParams*>(slot->host);
+    std::memcpy(host, p, sizeof(RenderParams) * static_cast<size_t>(m));
+    for (size_t k = 0; k < stale.size(); ++k) host[static_cast<size_t>(m) + k] = p[stale[k]];
+    // every handle's earlier renders first (one handle = one workspace), then the pass counters of a failed render
+    for (int i = 0; i < m; ++i) {
+        mcrt_scene* s = sc[i];
+        if (s->have_last && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->last_done, 0));
+        if (!s->last_done) {
+            HIP_TRY(hipEventCreateWithFlags(&s->last_done, hipEventDisableTiming));
+            s->busy_probe.store(s->last_done, std::memory_order_release);
+        }
+        s->flags_checked = false;
+        Lane& ln = s->lanes[0];
+        if (ln.counters_dirty && ln.counters.ptr) {
+            uint32_t* c = static_cast<uint32_t*>(ln.counters.ptr);
+            HIP_TRY(hipMemsetAsync(c, 0, static_cast<size_t>(kCounterWords - 4) * 4, stream));
+            HIP_TRY(hipMemsetAsync(c + kCounterWords, 0, (static_cast<size_t>(kCounterWords) + 4) * 4, stream));
+            ln.counters_dirty = false;
+        }
+    }
+    const RenderParams* d_table = static_cast<const RenderParams*>(slot->dev.ptr);
+    hipError_t e = hipMemcpyAsync(slot->dev.ptr, host, bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && !stale.empty()) e = launch_seed_tiles_batch(p[stale[0]], d_table + m, static_cast<int>(stale.size()), stream);
+    if (e == hipSuccess) e = launch_render_batch(p[0], plan, d_table, m, stream);
+    if (e == hipSuccess) e = hipEventRecord(slot->done, stream);
+    if (e != hipSuccess) {
+        for (int i = 0; i < m; ++i) sc[i]->lanes[0].counters_dirty = true;
+        return hip_fail(e, "batched launches");
+    }
+    slot->used = true;
+    for (int k : stale) sc[k]->lanes[0].rng_key = rng_key_of(p[k]);
+    for (int i = 0; i < m; ++i) {
+        mcrt_scene* s = sc[i];
+        HIP_TRY(hipEventRecord(s->last_done, stream));
+        s->last_stream = stream;
+        s->have_last = true;
+    }
+    return MCRT_OK;
+}
+
+int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream) {
+    g_batch_frames = 0;
+    g_batch_sequences = 0;
+    // argument checks, before any device work (the first ones do not look inside the handles)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    {
+        std::vector<mcrt_scene*> sorted(scenes, scenes + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (each handle owns one workspace: one frame in flight)");
+    }
+    if (!d_f32 && !d_u8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
+    if (cfg->max_bounces > kMaxBounces) return fail(MCRT_ERR_INVALID, "max_bounces above 4000 is not supported (one stack slot per level and sample)");
+    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    if (stride < static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height))
+        return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
+    const int device = scenes[0]->device;
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    HIP_TRY(hipSetDevice(device));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(MCRT_ERR_INVALID, "a batch cannot be recorded into a caller's graph (its parameter table is uploaded per call)");
+    (void)hipGetLastError();
+    // every frame on lane 0 of its handle, one lane: the batched kernels take it when it fits their envelope
+    std::vector<RenderParams> p(static_cast<size_t>(n));
+    std::vector<mcrt_scene*> in_batch;
+    std::vector<RenderParams> batch_p;
+    std::vector<int> alone;
+    for (int i = 0; i < n; ++i) {
+        mcrt_scene* s = scenes[i];
+        if (cfg->ao_enabled && cfg->ao_samples > 0 && !s->full_table_tried) {  // as the handle's first AO render would
+            s->full_table_tried = true;
+            s->seed_table_full = acquire_full_seed_table(s->device);
+            s->holds_full_table = s->seed_table_full != nullptr;
+        }
+        float* f = d_f32 ? d_f32 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        uint8_t* b = d_u8 ? d_u8 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        const int rc = prepare(s, 0, 1, cfg, 0, 1, MCRT_LAYOUT_FRAME, f, b, p[static_cast<size_t>(i)]);
+        if (rc != MCRT_OK) return rc;
+        if (batch_eligible(p[static_cast<size_t>(i)])) {
+            in_batch.push_back(s);
+            batch_p.push_back(p[static_cast<size_t>(i)]);
+        } else {
+            alone.push_back(i);
+        }
+    }
+    const int nb = static_cast<int>(in_batch.size());
+    for (int c0 = 0; c0 < nb; c0 += kBatchMaxFrames) {  // one launch sequence per kBatchMaxFrames frames
+        const int m = std::min(kBatchMaxFrames, nb - c0);
+        const int rc = launch_batch_sequence(in_batch.data() + c0, batch_p.data() + c0, m, device, stream);
+        if (rc != MCRT_OK) return rc;
+        g_batch_frames += m;
+        ++g_batch_sequences;
+    }
+    // the rest (more than one pass, or the general variants) one after the other through the single-frame path
+    for (int i : alone) {
+        float* f = d_f32 ? d_f32 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        uint8_t* b = d_u8 ? d_u8 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        const int rc = enqueue_render(scenes[i], cfg, 0, 1, MCRT_LAYOUT_FRAME, f, b, stream);
+        if (rc != MCRT_OK) return rc;
+        ++g_batch_sequences;
+    }
+    return MCRT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mcrt_render_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, float* d_out_f32, uint8_t* d_out_rgba8,
+                             size_t frame_stride_pixels, void* stream) {
+    return render_batch_device(scenes, n_frames, cfg, d_out_f32, d_out_rgba8, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_batch(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, float* out_rgba, uint8_t* out_rgba8, int device) {
+    g_batch_frames = 0;
+    g_batch_sequences = 0;
+    if (n_frames < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || (n_frames > 0 && !descs)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n_frames; ++i)
+        if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
+    if (!out_rgba && !out_rgba8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
+    if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
+    if (n_frames == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    std::vector<std::vector<uint8_t>> blobs(static_cast<size_t>(n_frames));
+    for (int i = 0; i < n_frames; ++i) {
+        std::string err;
+        if (!flatten_scene(descs[i], blobs[static_cast<size_t>(i)], err)) return fail(MCRT_ERR_INVALID, err);
+    }
+    const int visible = mcrt_device_count();
+    if (visible <= 0) return fail(MCRT_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= visible) return fail(MCRT_ERR_NO_DEVICE, "device index out of range");
+    std::vector<mcrt_scene*> h(static_cast<size_t>(n_frames), nullptr);
+    auto cleanup = [&](int code) {
+        for (mcrt_scene* s : h)
+            if (s) mcrt_scene_destroy(s);  // synchronises, checks, pools a workspace
+        return code;
+    };
+    for (int i = 0; i < n_frames; ++i) {
+        const int rc = create_scene_from_blob(blobs[static_cast<size_t>(i)], device, &h[static_cast<size_t>(i)]);
+        if (rc != MCRT_OK) return cleanup(rc);
+    }
+    mcrt_scene* s0 = h[0];
+    if (one_shot_streams(s0) != MCRT_OK) return cleanup(MCRT_ERR_HIP);
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    const size_t f32_bytes = out_rgba ? px * 16 * static_cast<size_t>(n_frames) : 0;
+    const size_t u8_bytes = out_rgba8 ? px * 4 * static_cast<size_t>(n_frames) : 0;
+    hipError_t e = s0->frame.reserve(f32_bytes + u8_bytes);
+    if (e != hipSuccess) return cleanup(hip_fail(e, "frame buffer"));
+    char* base = static_cast<char*>(s0->frame.ptr);
+    float* d_f32 = out_rgba ? reinterpret_cast<float*>(base) : nullptr;
+    uint8_t* d_u8 = out_rgba8 ? reinterpret_cast<uint8_t*>(base + f32_bytes) : nullptr;
+    int rc = render_batch_device(h.data(), n_frames, cfg, d_f32, d_u8, px, s0->main_stream);
+    const int frames = g_batch_frames, sequences = g_batch_sequences;
+    if (rc == MCRT_OK && out_rgba) {
+        e = hipMemcpyAsync(out_rgba, d_f32, f32_bytes, hipMemcpyDeviceToHost, s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "download");
+    }
+    if (rc == MCRT_OK && out_rgba8) {
+        e = hipMemcpyAsync(out_rgba8, d_u8, u8_bytes, hipMemcpyDeviceToHost, s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "download");
+    }
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "batch render");
+    }
+    for (int i = 0; i < n_frames && rc == MCRT_OK; ++i) rc = mcrt_scene_check(h[static_cast<size_t>(i)]);
+    rc = cleanup(rc);
+    g_batch_frames = frames;
+    g_batch_sequences = sequences;
+    return rc;
+}
+
+int mcrt_last_batch_info(int* batched_frames, int* launch_sequences) {
+    if (batched_frames) *batched_frames = g_batch_frames;
+    if (launch_sequences) *launch_sequences = g_batch_sequences;
+    return MCRT_OK;
+}
+
+}  // extern "C"

@@ -163,6 +163,25 @@ struct LaunchMarks {
 };
 hipError_t launch_render(const RenderParams& p, hipStream_t stream, const LaunchMarks* marks = nullptr);
 
+// ---- batches (mcrt_render_batch_device): N frames of one config in ONE launch sequence, blockIdx.y = frame; each
+// frame's RenderParams (its own scene, workspace, counters and output) are read from a device-resident table
+// whether the batched kernels can take a frame: flat pipeline, a whole-frame shard, one pass (rows_per_batch >= owned rows)
+bool batch_eligible(const RenderParams& p);
+struct BatchPlan {
+    int view = 0;        // the kernel variant of the whole batch (the most general any frame needs)
+    size_t dyn = 0;      // dynamic LDS of primary / ao: the largest frame's scene tables
+    size_t lit_dyn = 0;  // dynamic LDS of lit: the largest frame's lit_lds_offset + lit_lds_bytes
+};
+constexpr int kBatchMaxFrames = 256;  // frames per launch sequence (larger batches are split: render_kernels.hip, batch_grid)
+// Makes frames[0..n) one batch: picks the variant (rewriting the frames' LDS fields where it reads HBM), checks the
+// lit_lds_offset invariant per frame and sets the grids (choose_grids with company, then the batch rule).
+// hipErrorInvalidValue when a frame is not eligible or the frames do not share the config's launch shapes.
+hipError_t plan_batch(RenderParams* frames, int n, bool others_running, BatchPlan& plan);
+// seeds the tile streams of the frames in d_table (launch_seed_tiles for each); p0: any one of them (host copy)
+hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d_table, int n_frames, hipStream_t stream);
+// plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
+hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
+
 hipError_t launch_unpack_rows(const mcrt_config& cfg, const Shard& sh, const float* packed, float* frame,
                               hipStream_t stream);
 hipError_t launch_unpack_rows8(const mcrt_config& cfg, const Shard& sh, const uint8_t* packed, uint8_t* frame, hipStream_t stream);  // RGBA8 plane

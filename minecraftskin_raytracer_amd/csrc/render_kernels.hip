@@ -44,6 +44,8 @@
 // A frame is cut into batches of tile rows so that the worst case (every sample of a touched tile hits) fits.
 // No MFMA: there is no dense contraction anywhere on this path.
 #include "kernels.h"
+
+#include <cstring>
 #include "rt_core.h"
 
 // Verification hooks.  tools/decide_check.sh builds a variant of the library with -DMCRT_KERNEL_HOOKS='"decide_check_hooks.h"'
@@ -124,7 +126,7 @@ __device__ __forceinline__ TileGeom tile_of(const RenderParams& p, int owned_til
 // pre-pass: seed one std::mt19937 per owned tile (tile_renderer.cpp:78).  The seeding
 // recurrence is strictly sequential, so it is spread over lanes (one tile per lane).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void seed_tiles_kernel(RenderParams p, int n_tiles) {
+__device__ __forceinline__ void seed_tiles_body(const RenderParams& __restrict__ p, int n_tiles) {
     int tile = blockIdx.x * 64 + threadIdx.x;
     if (tile >= n_tiles) return;
     TileGeom t = tile_of(p, tile);
@@ -136,6 +138,7 @@ __global__ __launch_bounds__(64) void seed_tiles_kernel(RenderParams p, int n_ti
         dst[j] = x;
     }
 }
+__global__ __launch_bounds__(64) void seed_tiles_kernel(RenderParams p, int n_tiles) { seed_tiles_body(p, n_tiles); }
 
 // ---------------------------------------------------------------------------------------------
 // pixel store: the float4 frame and/or its RGBA8 quantisation `(u8)(clamp(c,0,1)*255+0.5)`
@@ -604,11 +607,9 @@ __device__ __forceinline__ uint32_t plan_touched_tile(const RenderParams& p, con
     return ord;
 }
 
-__global__ __launch_bounds__(64 * kStreamWaves) void plan_tiles_kernel(const uint8_t* __restrict__ scene_blob,
-                                                                       const uint32_t* __restrict__ tile_rng,
-                                                                       float* __restrict__ tile_draws, float4* __restrict__ out_frame,
-                                                                       uchar4* __restrict__ out8, const RenderParams p,
-                                                                       const int tile_base, const int n_tiles) {
+__device__ __forceinline__ void plan_tiles_body(const uint8_t* __restrict__ scene_blob, const uint32_t* __restrict__ tile_rng,
+                                                float* __restrict__ tile_draws, float4* __restrict__ out_frame, uchar4* __restrict__ out8,
+                                                const RenderParams& __restrict__ p, const int tile_base, const int n_tiles) {
     __shared__ __align__(16) uint32_t s_state[kStreamWaves][2 * 624];
     __shared__ uint32_t s_ord[kStreamWaves];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -653,11 +654,18 @@ __global__ __launch_bounds__(64 * kStreamWaves) void plan_tiles_kernel(const uin
                           [](unsigned, float&, float&) __attribute__((always_inline)) {});
     }
 }
+__global__ __launch_bounds__(64 * kStreamWaves) void plan_tiles_kernel(const uint8_t* __restrict__ scene_blob,
+                                                                       const uint32_t* __restrict__ tile_rng,
+                                                                       float* __restrict__ tile_draws, float4* __restrict__ out_frame,
+                                                                       uchar4* __restrict__ out8, const RenderParams p,
+                                                                       const int tile_base, const int n_tiles) {
+    plan_tiles_body(scene_blob, tile_rng, tile_draws, out_frame, out8, p, tile_base, n_tiles);
+}
 
 // The engine states at the starts of a tile's parts 1 .. parts-1 (tile_stream_wave): one wave per tile twists the seeded
 // state part_twists times per part, in LDS, and stores where it stands.  A function of the seeds and of part_twists only:
 // run with the tile seeds, kept across renders with them.
-__global__ __launch_bounds__(64 * kStreamWaves) void advance_tiles_kernel(RenderParams p, int n_tiles) {
+__device__ __forceinline__ void advance_tiles_body(const RenderParams& __restrict__ p, int n_tiles) {
     __shared__ __align__(16) uint32_t s_state[kStreamWaves][2 * 624];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tile = static_cast<int>(blockIdx.x) * kStreamWaves + wave;
@@ -699,6 +707,7 @@ __global__ __launch_bounds__(64 * kStreamWaves) void advance_tiles_kernel(Render
         for (int e = lane; e < 624; e += 64) states[static_cast<size_t>(part) * 624 + e] = now[e];
     }
 }
+__global__ __launch_bounds__(64 * kStreamWaves) void advance_tiles_kernel(RenderParams p, int n_tiles) { advance_tiles_body(p, n_tiles); }
 
 // ---------------------------------------------------------------------------------------------
 // primary: persistent workgroups; touched units first, then the background tiles.  A sample's draws
@@ -710,10 +719,9 @@ __global__ __launch_bounds__(64 * kStreamWaves) void advance_tiles_kernel(Render
 #define MCRT_PRIMARY_WAVES 5
 #endif
 template <int kView>
-__global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_kernel(const uint8_t* __restrict__ scene_blob,
-                                                         const float* __restrict__ tile_draws,
-                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
-                                                         const int tile_base, const int n_tiles) {
+__device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
+                                             float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams& __restrict__ p,
+                                             const int tile_base, const int n_tiles) {
     __shared__ int s_wcnt[kBlock / 64];
     __shared__ float4 s_bd[kBlock], s_bp[kBlock], s_bn[kBlock];  // the chunk's primary hits, packed, for their reflection rays
     __shared__ uint32_t s_out_base;
@@ -884,6 +892,13 @@ __global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_kernel(con
         }
     }
 }
+template <int kView>
+__global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_kernel(const uint8_t* __restrict__ scene_blob,
+                                                         const float* __restrict__ tile_draws,
+                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
+                                                         const int tile_base, const int n_tiles) {
+    primary_body<kView>(scene_blob, tile_draws, out_frame, out8, p, tile_base, n_tiles);
+}
 
 // ---------------------------------------------------------------------------------------------
 // background: the tiles no mesh can touch at HIGH sample counts (kSlabMinSpp samples per pixel and more; below that the
@@ -901,9 +916,9 @@ constexpr int kSlabMinSpp = 33;  // `background_kernel` from this many samples p
 #ifndef MCRT_BG_WAVES
 #define MCRT_BG_WAVES 3
 #endif
-__global__ __launch_bounds__(kBlock, MCRT_BG_WAVES) void background_kernel(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
-                                                            float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
-                                                            const int tile_base, const int n_tiles) {
+__device__ __forceinline__ void background_body(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
+                                                float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams& __restrict__ p,
+                                                const int tile_base, const int n_tiles) {
     __shared__ __align__(16) float2 s_slab[kBlock / 64][64][kSlabSamples + 1];
     const SceneView sc = view_of(scene_blob);
     const mcrt_config& cfg = p.cfg;
@@ -983,6 +998,11 @@ __global__ __launch_bounds__(kBlock, MCRT_BG_WAVES) void background_kernel(const
             }
         }
     }
+}
+__global__ __launch_bounds__(kBlock, MCRT_BG_WAVES) void background_kernel(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
+                                                            float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
+                                                            const int tile_base, const int n_tiles) {
+    background_body(scene_blob, tile_draws, out_frame, out8, p, tile_base, n_tiles);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1242,7 +1262,7 @@ __global__ __launch_bounds__(kBlock, MCRT_SHADOW_WAVES) void shadow_kernel(const
 #define MCRT_LIT_WAVES 4
 #endif
 template <int kView>
-__global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p) {
+__device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob, const RenderParams& __restrict__ p) {
     extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks: lit_round][inside masks: lit_round][positions: lit_pass x S x 3 floats][lit counts: lit_round][undecided list: lit_round]
     __shared__ int s_wcnt[kBlock / 64];
     MCRT_HOOK_LIT_SHARED
@@ -1466,6 +1486,10 @@ __global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_kernel(const uint8
         }
     }
 }
+template <int kView>
+__global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p) {
+    lit_body<kView>(scene_blob, p);
+}
 
 // ambient occlusion (raytracer.cpp:38-78, depth 0 only) as one stage over the primary hits, a lane per hit:
 //   1. the meshes any of its rays can meet: within the radius (rt::ball_candidates) and not behind the hit's own
@@ -1482,7 +1506,7 @@ __global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_kernel(const uint8
 #define MCRT_AO_WAVES 4
 #endif
 template <int kView>
-__global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p) {
+__device__ __forceinline__ void ao_body(const uint8_t* __restrict__ scene_blob, const RenderParams& __restrict__ p) {
     __shared__ int s_wcnt[kBlock / 64];
     __shared__ uint32_t s_list[kBlock];
     __shared__ unsigned long long s_mask[kBlock];
@@ -1545,6 +1569,10 @@ __global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_kernel(const uint8_t
         }
         __syncthreads();  // s_list, s_mask are reused by the next block of hits
     });
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p) {
+    ao_body<kView>(scene_blob, p);
 }
 
 // level_shade (general variants): colour of the level, reflection ray, closest hit of the next level →
@@ -1660,9 +1688,9 @@ __device__ __forceinline__ float4 sample_colour(const WaveSpace& ws, uint32_t sl
     }
     return make_float4(tail.r, tail.g, tail.b, tail.a);
 }
-__global__ __launch_bounds__(kBlock) void resolve_kernel(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
-                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
-                                                         const int tile_base) {
+__device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
+                                             float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams& __restrict__ p,
+                                             const int tile_base) {
     __shared__ float4 s_col[kBlock];
     const WaveSpace& ws = p.ws;
     const mcrt_config& cfg = p.cfg;
@@ -1734,6 +1762,57 @@ __global__ __launch_bounds__(kBlock) void resolve_kernel(const uint8_t* __restri
             __syncthreads();
         }
     }
+}
+__global__ __launch_bounds__(kBlock) void resolve_kernel(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
+                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
+                                                         const int tile_base) {
+    resolve_body(scene_blob, tile_draws, out_frame, out8, p, tile_base);
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched entry points (mcrt_render_batch_device): one launch per stage for N frames, blockIdx.y = frame.  The entry
+// reads its frame's RenderParams from a device-resident table — a wave-uniform address, so the fields come in with scalar
+// loads — and runs the single-frame body.  Everything per frame stays per frame because it comes from those parameters:
+// the workspace, the pass counters and their base, frame_info, the blockIdx.x == 0 duties and the grid-stride loops over
+// gridDim.x.  A batch holds frames of one config that take one pass each (tile_base 0), so the tile count is common.
+// ---------------------------------------------------------------------------------------------
+// The table is declared in the constant address space (4), as the single-frame entries' kernel arguments are: memory the
+// kernel cannot write, so the pointers read from it are known to be global ones (global_load / global_store with scalar
+// bases, as in the single-frame kernels) instead of generic flat accesses.
+using ParamTable = const __attribute__((address_space(4))) RenderParams*;
+__device__ __forceinline__ const RenderParams& frame_params(ParamTable table) { return *(const RenderParams*)(table + blockIdx.y); }
+__global__ __launch_bounds__(64) void seed_tiles_batch_kernel(ParamTable table, int n_tiles) {
+    seed_tiles_body(frame_params(table), n_tiles);
+}
+__global__ __launch_bounds__(64 * kStreamWaves) void advance_tiles_batch_kernel(ParamTable table, int n_tiles) {
+    advance_tiles_body(frame_params(table), n_tiles);
+}
+__global__ __launch_bounds__(64 * kStreamWaves) void plan_tiles_batch_kernel(ParamTable table, const int n_tiles) {
+    const RenderParams& p = frame_params(table);
+    plan_tiles_body(p.scene, p.tile_rng, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0, n_tiles);
+}
+__global__ __launch_bounds__(kBlock, MCRT_BG_WAVES) void background_batch_kernel(ParamTable table, const int n_tiles) {
+    const RenderParams& p = frame_params(table);
+    background_body(p.scene, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0, n_tiles);
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_batch_kernel(ParamTable table, const int n_tiles) {
+    const RenderParams& p = frame_params(table);
+    primary_body<kView>(p.scene, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0, n_tiles);
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_batch_kernel(ParamTable table) {
+    const RenderParams& p = frame_params(table);
+    ao_body<kView>(p.scene, p);
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_batch_kernel(ParamTable table) {
+    const RenderParams& p = frame_params(table);
+    lit_body<kView>(p.scene, p);
+}
+__global__ __launch_bounds__(kBlock) void resolve_batch_kernel(ParamTable table) {
+    const RenderParams& p = frame_params(table);
+    resolve_body(p.scene, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2184,6 +2263,110 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
             if (e != hipSuccess) return e;
         }
     }
+    return hipGetLastError();
+}
+
+// ---- batches ----------------------------------------------------------------------------------
+bool batch_eligible(const RenderParams& p) {
+    return p.flat && p.rect_w <= 0 && p.shard.owned_rows > 0 && p.rows_per_batch >= p.shard.owned_rows;
+}
+
+// Workgroups per frame of a batched launch.  Every kernel strides over its frame's device-side work, so the grid only
+// shapes the schedule: a batch aims at kBatchTarget workgroups per launch (8 per CU of the 256 — twice what the largest
+// stage keeps resident, enough to balance frames of unequal cost) spread evenly over its frames, never fewer than
+// kBatchMinGrid per frame (a frame's share of the work never waits on a handful of workgroups) and never more than the
+// frame would get on its own (choose_grids).  From 256 frames on the floor alone fills the target: kBatchMaxFrames.
+constexpr int kBatchTarget = 2048;
+constexpr int kBatchMinGrid = 8;
+static int batch_grid(int single, int n_frames) {
+    if (n_frames <= 1) return single;
+    int g = (kBatchTarget + n_frames - 1) / n_frames;
+    if (g < kBatchMinGrid) g = kBatchMinGrid;
+    return g < single ? g : single;
+}
+
+hipError_t plan_batch(RenderParams* f, int n, bool others_running, BatchPlan& plan) {
+    plan = BatchPlan{};
+    if (n < 1) return hipErrorInvalidValue;
+    const RenderParams& a = f[0];
+    bool any_hbm = false, any_posed = false;
+    for (int i = 0; i < n; ++i) {
+        const RenderParams& q = f[i];
+        // the launch shapes are functions of the config: frames that disagree cannot share a launch
+        if (!batch_eligible(q) || std::memcmp(&q.cfg, &a.cfg, sizeof(mcrt_config)) != 0 || std::memcmp(&q.shard, &a.shard, sizeof(Shard)) != 0 ||
+            q.parts_per_tile != a.parts_per_tile || q.stream_parts != a.stream_parts || q.stream_part_twists != a.stream_part_twists ||
+            q.draws_per_sample != a.draws_per_sample || q.bg_in_plan != a.bg_in_plan || q.bg_kernel != a.bg_kernel || q.lit_lds_bytes != a.lit_lds_bytes)
+            return hipErrorInvalidValue;
+        any_hbm = any_hbm || !q.scene_in_lds;
+        any_posed = any_posed || q.scene_posed;
+    }
+    // one variant for the whole batch, the most general any frame needs: kViewHbm > kViewLds > kViewLdsUnposed.  The
+    // kernels decide the record layout from p.scene_posed, not from the variant, so a frame under a more general variant
+    // renders exactly as alone; under kViewHbm its tables are read from HBM and lit's area starts at offset 0.
+    plan.view = any_hbm ? kViewHbm : (any_posed ? kViewLds : kViewLdsUnposed);
+    for (int i = 0; i < n; ++i) {
+        RenderParams& q = f[i];
+        if (any_hbm) {
+            q.scene_in_lds = 0, q.lds_alpha_words = 0, q.lds_face_entries = 0;
+            q.lit_lds_offset = 0;
+        }
+        const size_t tables = scene_table_bytes(q);
+        if (static_cast<size_t>(q.lit_lds_offset) != ((tables + 15) & ~static_cast<size_t>(15))) return hipErrorInvalidValue;
+        plan.dyn = tables > plan.dyn ? tables : plan.dyn;
+        const size_t lit = static_cast<size_t>(q.lit_lds_offset) + static_cast<size_t>(q.lit_lds_bytes);
+        plan.lit_dyn = lit > plan.lit_dyn ? lit : plan.lit_dyn;
+    }
+    // grids: what a frame would get with company (the other frames of the batch), then the batch rule above
+    const int spp = a.cfg.samples_per_pixel > 1 ? a.cfg.samples_per_pixel : 1;
+    const double samples = static_cast<double>(a.shard.owned_rows) * a.cfg.tile_size * a.cfg.width * spp;
+    const bool company = n > 1 || others_running;
+    for (int i = 0; i < n; ++i) {
+        RenderParams& q = f[i];
+        choose_grids(q, company && samples < 6.4e7, company);
+        q.grid_primary = batch_grid(q.grid_primary, n);
+        q.grid_ao = batch_grid(q.grid_ao, n);
+        q.grid_lit = batch_grid(q.grid_lit, n);
+        q.grid_resolve = batch_grid(q.grid_resolve, n);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d_table, int n_frames, hipStream_t stream) {
+    const int n = owned_tiles(p0);
+    if (n <= 0 || n_frames <= 0 || p0.draws_per_sample <= 0 || !p0.tile_rng) return hipSuccess;
+    const unsigned F = static_cast<unsigned>(n_frames);
+    hipLaunchKernelGGL(seed_tiles_batch_kernel, dim3((n + 63) / 64, F), dim3(64), 0, stream, ParamTable(d_table), n);
+    if (p0.stream_parts > 1)
+        hipLaunchKernelGGL(advance_tiles_batch_kernel, dim3((n + kStreamWaves - 1) / kStreamWaves, F), dim3(64 * kStreamWaves), 0, stream, ParamTable(d_table), n);
+    return hipGetLastError();
+}
+
+template <int kView>
+static void launch_batch_stages(const RenderParams& p0, const BatchPlan& b, const RenderParams* d_table, unsigned F, int n, hipStream_t stream) {
+    const int pgrid = n * p0.parts_per_tile < p0.grid_primary ? n * p0.parts_per_tile : p0.grid_primary;
+    hipLaunchKernelGGL(primary_batch_kernel<kView>, dim3(pgrid, F), dim3(kBlock), b.dyn, stream, ParamTable(d_table), n);
+    if (p0.cfg.ao_enabled && p0.cfg.ao_samples > 0)  // ahead of `lit`, whose last phase applies the AO factor
+        hipLaunchKernelGGL(ao_batch_kernel<kView>, dim3(p0.grid_ao, F), dim3(kBlock), b.dyn, stream, ParamTable(d_table));
+    hipLaunchKernelGGL(lit_batch_kernel<kView>, dim3(p0.grid_lit, F), dim3(kBlock), b.lit_dyn, stream, ParamTable(d_table));
+}
+
+hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& b, const RenderParams* d_table, int n_frames, hipStream_t stream) {
+    const int n = owned_tiles(p0);
+    if (n <= 0 || n_frames <= 0) return hipSuccess;
+    if (!batch_eligible(p0) || n_frames > kBatchMaxFrames || p0.grid_primary <= 0 || p0.grid_ao <= 0 || p0.grid_lit <= 0 || p0.grid_resolve <= 0)
+        return hipErrorInvalidValue;  // (plan_batch sets the grids)
+    const unsigned F = static_cast<unsigned>(n_frames);
+    const int waves = p0.stream_waves > 0 ? p0.stream_waves : 1;
+    hipLaunchKernelGGL(plan_tiles_batch_kernel, dim3((n * waves + kStreamWaves - 1) / kStreamWaves, F), dim3(64 * kStreamWaves), 0, stream, ParamTable(d_table), n);
+    if (p0.bg_kernel) hipLaunchKernelGGL(background_batch_kernel, dim3(n < kQueueGrid ? n : kQueueGrid, F), dim3(kBlock), 0, stream, ParamTable(d_table), n);
+    if (b.view == kViewLdsUnposed)
+        launch_batch_stages<kViewLdsUnposed>(p0, b, d_table, F, n, stream);
+    else if (b.view == kViewLds)
+        launch_batch_stages<kViewLds>(p0, b, d_table, F, n, stream);
+    else
+        launch_batch_stages<kViewHbm>(p0, b, d_table, F, n, stream);
+    const int rgrid = n * p0.parts_per_tile < p0.grid_resolve ? n * p0.parts_per_tile : p0.grid_resolve;
+    hipLaunchKernelGGL(resolve_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
     return hipGetLastError();
 }
 
