@@ -239,8 +239,38 @@ int mcrt_render_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt
 int mcrt_render_batch(const mcrt_scene_desc* const* scenes, int n_frames, const mcrt_config* cfg, float* out_rgba,
                       uint8_t* out_rgba8, int device);
 /* How the last batch call on this thread ran: frames taken by the batched kernels, and launch sequences enqueued (1 when
- * the whole batch went through the batched kernels in one; each frame enqueued on its own counts one). */
+ * the whole batch went through the batched kernels in one; each frame enqueued on its own counts one).  The frames of a
+ * launch sequence share their background mode (mcrt_scene_set_background): a batch that mixes modes takes one sequence
+ * per mode. */
 int mcrt_last_batch_info(int* batched_frames, int* launch_sequences);
+
+/* ---- background modes: the figure alone, on a transparent background -------------------------------------------------
+ * MCRT_BACKGROUND_REFERENCE (the default everywhere): every pixel as the reference renders it (tile_renderer.cpp:89-124).
+ * MCRT_BACKGROUND_TRANSPARENT: the same rays, the same mt19937 draws (jitter and lens draws are taken for samples that
+ * miss too) and the same colour c_s for every sample s that hits — reflections still see the configured background, so
+ * the figure looks exactly as in a reference render.  Of the S = max(1, spp) samples of a pixel, let A be the per-channel
+ * float sum, in sample order, of c_s over the n samples whose primary ray hits (intersectScene(ray_s).hit, :111); the
+ * samples that miss add nothing.  The pixel is (0, 0, 0, 0) when n = 0, else rgb = A.rgb * (1.0f / n) and
+ * a = A.a * (1.0f / S), both reciprocals correctly rounded.  So a pixel whose samples all hit equals the reference pixel
+ * bit for bit, a pixel without a hit is (0,0,0,0), and an edge pixel holds the mean colour of the figure's samples with
+ * alpha = coverage x mean texel alpha: straight alpha, as PNG stores it (the RGBA8 plane is quantised as usual).
+ * A `background` other than these two constants → MCRT_ERR_INVALID, checked right after the NULL-argument checks (before
+ * the early return of a zero-size frame and before any device query).  Not available for mcrt_render_rect /
+ * mcrt_render_tile. */
+#define MCRT_BACKGROUND_REFERENCE 0
+#define MCRT_BACKGROUND_TRANSPARENT 1
+/* Per handle, like mcrt_scene_set_lanes: every later mcrt_render_device[_ex], mcrt_time_render_device and the handle's frame
+ * in mcrt_render_batch_device use it.  A NULL handle → MCRT_ERR_INVALID. */
+int mcrt_scene_set_background(mcrt_scene* scene, int background);
+/* mcrt_render_multi (out_rgba) / mcrt_render_rgba8 (out_rgba8) with a background mode: exactly one of the two outputs
+ * non-NULL, else MCRT_ERR_INVALID.  devices / n_devices / gather / progress as there. */
+int mcrt_render_ex(const mcrt_scene_desc* scene, const mcrt_config* cfg, int background, float* out_rgba, uint8_t* out_rgba8,
+                   mcrt_progress_fn progress, void* user, const int* devices, int n_devices, int gather);
+/* mcrt_render_batch with a background mode for every frame */
+int mcrt_render_batch_ex(const mcrt_scene_desc* const* scenes, int n_frames, const mcrt_config* cfg, int background, float* out_rgba,
+                         uint8_t* out_rgba8, int device);
+/* mcrt_render_png with a background mode (the transparent PNG: colour type 6, straight alpha) */
+int mcrt_render_png_ex(const mcrt_scene_desc* scene, const mcrt_config* cfg, int background, const char* path, int device);
 
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);

@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_device_ex", "mcrt_write_png_rgba8", "mcrt_encode_png_rgba8", "mcrt_write_png_f32", "mcrt_render_png",
     "mcrt_assemble_frame_device", "mcrt_scene_set_lanes", "mcrt_trim", "mcrt_scene_check", "mcrt_render_multi",
     "mcrt_render_rgba8", "mcrt_render_rect", "mcrt_render_batch_device", "mcrt_render_batch", "mcrt_last_batch_info",
+    "mcrt_scene_set_background", "mcrt_render_ex", "mcrt_render_batch_ex", "mcrt_render_png_ex",
 ]
 
 
@@ -60,6 +61,10 @@ def load():
         "mcrt_render_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, vp, vp, C.c_size_t, vp]),
         "mcrt_render_batch": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, f_p, u8_p, C.c_int]),
         "mcrt_last_batch_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mcrt_scene_set_background": (C.c_int, [vp, C.c_int]),
+        "mcrt_render_ex": (C.c_int, [desc_p, cfg_p, C.c_int, f_p, u8_p, abi.PROGRESS_FN, vp, C.POINTER(C.c_int), C.c_int, C.c_int]),
+        "mcrt_render_batch_ex": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, C.c_int, f_p, u8_p, C.c_int]),
+        "mcrt_render_png_ex": (C.c_int, [desc_p, cfg_p, C.c_int, C.c_char_p, C.c_int]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),
         "mcrt_encode_png_rgba8": (C.c_size_t, [u8_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
         "mcrt_write_png_f32": (C.c_int, [C.c_char_p, f_p, C.c_int, C.c_int]),

@@ -21,6 +21,16 @@ MCRT_ERR_HIP = 3
 MCRT_ERR_NOMEM = 4
 LAYOUT_FRAME = 0
 LAYOUT_PACKED = 1
+BACKGROUND_REFERENCE = 0  # MCRT_BACKGROUND_*: every pixel as the reference renders it (the default)
+BACKGROUND_TRANSPARENT = 1  # the figure alone: misses add nothing, straight alpha (include/mcrt.h)
+BACKGROUNDS = {"reference": BACKGROUND_REFERENCE, "transparent": BACKGROUND_TRANSPARENT}
+
+
+def background_mode(name) -> int:
+    """``"reference"`` / ``"transparent"`` → MCRT_BACKGROUND_*; anything else raises ``ValueError``."""
+    if not isinstance(name, str) or name not in BACKGROUNDS:
+        raise ValueError(f"background must be 'reference' or 'transparent', not {name!r}")
+    return BACKGROUNDS[name]
 
 
 class McrtConfig(C.Structure):

@@ -149,7 +149,7 @@ class TileRenderer:
 
     @staticmethod
     def render(scene, config: Config, progressCallback: Optional[Callable[[int, int], None]] = None,
-               device=0, gather: bool = False, out: Optional[np.ndarray] = None) -> Image:
+               device=0, gather: bool = False, out: Optional[np.ndarray] = None, background: str = "reference") -> Image:
         """TileRenderer::render.  Per-frame failures never raise (tile_renderer.cpp:158-166): they are
         recorded as one ``(-1, message)`` entry in ``lastErrors()`` and the image keeps Color() =
         (0,0,0,1) pixels.
@@ -157,7 +157,10 @@ class TileRenderer:
         ``device``: an index, ``"all"`` / ``-1`` (every visible device) or a sequence of indices — one rank per
         entry, cyclic tile rows (mcrt_render_multi; ``gather`` selects the peer-copy assembly on the first
         device instead of per-device downloads).  ``out``: a (H, W, 4) float32 C-contiguous array to render
-        into (the reference returns a fresh Image per call; a caller that renders repeatedly can keep one)."""
+        into (the reference returns a fresh Image per call; a caller that renders repeatedly can keep one).
+        ``background``: ``"reference"`` (the default) or ``"transparent"`` — the figure alone, straight alpha, pixels
+        without a hit (0,0,0,0) (MCRT_BACKGROUND_TRANSPARENT, include/mcrt.h)."""
+        mode = abi.background_mode(background)
         lib = load()
         d = _as_desc(scene)
         c = config.to_c()
@@ -172,7 +175,12 @@ class TileRenderer:
             return out
         cb = abi.PROGRESS_FN((lambda done, total, _u: progressCallback(done, total))) if progressCallback else C.cast(None, abi.PROGRESS_FN)
         one, devs = _devices(device)
-        if one is not None:
+        if mode != abi.BACKGROUND_REFERENCE:
+            if one is not None:
+                devs = [one]
+            arr = (C.c_int * max(len(devs), 1))(*devs)
+            rc = lib.mcrt_render_ex(d.ptr, C.byref(c), mode, abi.fptr(out), None, cb, None, arr if devs else None, len(devs), 1 if gather else 0)
+        elif one is not None:
             rc = lib.mcrt_render(d.ptr, C.byref(c), abi.fptr(out), cb, None, one)
         else:
             arr = (C.c_int * max(len(devs), 1))(*devs)
@@ -197,9 +205,11 @@ class TileRenderer:
             TileRenderer._errors.append((-1, lib.mcrt_last_error().decode("utf-8", "replace")))
 
     @staticmethod
-    def renderRGBA8(scene, config: Config, device=0, gather: bool = False) -> np.ndarray:
+    def renderRGBA8(scene, config: Config, device=0, gather: bool = False, background: str = "reference") -> np.ndarray:
         """The frame as the RGBA8 plane ImageWriter::writePNG would encode ((H, W, 4) uint8), quantised in the kernels'
-        epilogue: 4 B per pixel over PCIe / xGMI instead of 16 (mcrt_render_rgba8).  ``device`` as for ``render``."""
+        epilogue: 4 B per pixel over PCIe / xGMI instead of 16 (mcrt_render_rgba8).  ``device`` and ``background`` as for
+        ``render``."""
+        mode = abi.background_mode(background)
         lib = load()
         c = config.to_c()
         w, h = max(config.width, 0), max(config.height, 0)
@@ -212,8 +222,12 @@ class TileRenderer:
         if one is not None:
             devs = [one]
         arr = (C.c_int * max(len(devs), 1))(*devs)
-        rc = lib.mcrt_render_rgba8(_as_desc(scene).ptr, C.byref(c), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.cast(None, abi.PROGRESS_FN), None,
-                                   arr if devs else None, len(devs), 1 if gather else 0)
+        if mode != abi.BACKGROUND_REFERENCE:
+            rc = lib.mcrt_render_ex(_as_desc(scene).ptr, C.byref(c), mode, None, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    C.cast(None, abi.PROGRESS_FN), None, arr if devs else None, len(devs), 1 if gather else 0)
+        else:
+            rc = lib.mcrt_render_rgba8(_as_desc(scene).ptr, C.byref(c), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.cast(None, abi.PROGRESS_FN), None,
+                                       arr if devs else None, len(devs), 1 if gather else 0)
         if rc != 0:
             TileRenderer._errors = [(-1, lib.mcrt_last_error().decode("utf-8", "replace"))]
             out[...] = 0
@@ -221,11 +235,12 @@ class TileRenderer:
         return out
 
     @staticmethod
-    def renderBatch(scenes, config: Config, device: int = 0, rgba8: bool = False) -> np.ndarray:
+    def renderBatch(scenes, config: Config, device: int = 0, rgba8: bool = False, background: str = "reference") -> np.ndarray:
         """N frames of one config in one call (mcrt_render_batch): frame i equals ``render(scenes[i], config)`` bit for bit
         (or ``renderRGBA8`` with ``rgba8``).  Returns (N, H, W, 4) float32, or uint8 with ``rgba8``.  Small frames go
         through batched kernels, one launch sequence for the whole batch; ``lastBatchInfo()`` tells how it ran.
-        Unlike ``render``, failures raise ``McrtError``."""
+        ``background`` as for ``render``, for every frame.  Unlike ``render``, failures raise ``McrtError``."""
+        mode = abi.background_mode(background)
         descs = [_as_desc(s) for s in scenes]
         n = len(descs)
         w, h = max(config.width, 0), max(config.height, 0)
@@ -237,7 +252,10 @@ class TileRenderer:
         arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*ptrs)
         f = None if rgba8 else abi.fptr(out)
         b = out.ctypes.data_as(C.POINTER(C.c_uint8)) if rgba8 else None
-        check(load().mcrt_render_batch(arr, n, C.byref(c), f, b, int(device)))
+        if mode != abi.BACKGROUND_REFERENCE:
+            check(load().mcrt_render_batch_ex(arr, n, C.byref(c), mode, f, b, int(device)))
+        else:
+            check(load().mcrt_render_batch(arr, n, C.byref(c), f, b, int(device)))
         return out
 
     @staticmethod
@@ -296,10 +314,13 @@ class ImageWriter:
         return bytes(buf[:got])
 
 
-def render_png(scene, config: Config, path: str, device: int = 0) -> bool:
+def render_png(scene, config: Config, path: str, device: int = 0, background: str = "reference") -> bool:
     """TileRenderer::render + ImageWriter::writePNG in one call (RGBA8 quantised in the kernel epilogue,
-    4 B/pixel copied back)."""
+    4 B/pixel copied back).  ``background="transparent"``: the figure alone on a transparent background (straight alpha)."""
+    mode = abi.background_mode(background)
     c = config.to_c()
+    if mode != abi.BACKGROUND_REFERENCE:
+        return load().mcrt_render_png_ex(_as_desc(scene).ptr, C.byref(c), mode, os.fsencode(path), device) == 0
     return load().mcrt_render_png(_as_desc(scene).ptr, C.byref(c), os.fsencode(path), device) == 0
 
 
@@ -331,6 +352,12 @@ class DeviceScene:
     def set_lanes(self, lanes: int) -> None:
         """0 = automatic split of a render over internal streams, n >= 1 = exactly n (mcrt_scene_set_lanes)."""
         check(load().mcrt_scene_set_lanes(self._h, int(lanes)))
+
+    def set_background(self, mode: str) -> None:
+        """``"reference"`` or ``"transparent"`` for every later render of this handle, batches included
+        (mcrt_scene_set_background)."""
+        m = abi.background_mode(mode)
+        check(load().mcrt_scene_set_background(self._h, m))
 
     def owned_pixel_rows(self, config: Config, first: int = 0, step: int = 1) -> int:
         c = config.to_c()

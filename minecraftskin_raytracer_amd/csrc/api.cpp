@@ -78,6 +78,8 @@ struct DeviceBuffer {
 };
 
 bool valid_frame(const mcrt_config* c) { return c->width > 0 && c->height > 0 && c->tile_size > 0; }
+bool valid_background(int b) { return b == MCRT_BACKGROUND_REFERENCE || b == MCRT_BACKGROUND_TRANSPARENT; }
+int bad_background() { return fail(MCRT_ERR_INVALID, "background must be MCRT_BACKGROUND_REFERENCE or MCRT_BACKGROUND_TRANSPARENT"); }
 
 int draws_per_sample(const mcrt_config& c) {
     int spp = c.samples_per_pixel > 1 ? c.samples_per_pixel : 1;
@@ -122,6 +124,7 @@ struct mcrt_scene {
     DeviceBuffer blob;
     Lane lanes[kMaxLanes];
     int forced_lanes = 0;  // mcrt_scene_set_lanes: 0 = automatic
+    int background = MCRT_BACKGROUND_REFERENCE;  // mcrt_scene_set_background
     size_t budget = 0;     // current workspace budget (0 = workspace_budget()); halved when the device is short of memory
     // recorded launch sequences of recent renders (hipGraph), replayed when the parameters repeat
     struct Recorded {
@@ -319,6 +322,7 @@ int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int fir
     p.layout = layout;
     p.out = d_out;
     p.out8 = d_out8;
+    p.background = rect ? MCRT_BACKGROUND_REFERENCE : sc->background;  // (plan_workspace picks the draws layout by it)
     p.draws_per_sample = draws_per_sample(*cfg);
     const bool fits = sc->alpha_words <= static_cast<uint32_t>(kAlphaLdsWordsMax) && sc->n_meshes * 6 <= static_cast<uint32_t>(kFaceLdsEntriesMax);
     p.scene_in_lds = fits ? 1 : 0;
@@ -934,6 +938,7 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
         register_live(s);
     }
     s->forced_lanes = 0;
+    s->background = MCRT_BACKGROUND_REFERENCE;
     s->budget = 0;  // a budget halved under memory pressure is not inherited
     s->have_last = false;  // a pooled shell was synchronised when its previous owner let go of it
     s->last_stream = nullptr;
@@ -1062,6 +1067,13 @@ int mcrt_scene_check(mcrt_scene* s) {
 int mcrt_scene_set_lanes(mcrt_scene* s, int lanes) {
     if (!s || lanes < 0) return fail(MCRT_ERR_INVALID, "bad argument");
     s->forced_lanes = lanes;
+    return MCRT_OK;
+}
+
+int mcrt_scene_set_background(mcrt_scene* s, int background) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (!valid_background(background)) return bad_background();
+    s->background = background;
     return MCRT_OK;
 }
 
@@ -1206,7 +1218,7 @@ bool peer_access(int root, int other) {
 //               frame on the root and downloaded, so progress follows the ranks as they land.
 // Progress callbacks (exactly totalTiles, done = 1..total) fire on the calling thread as rows land in `out`.
 int render_to_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, void* out, int px_bytes, mcrt_progress_fn progress, void* user,
-                   const int* devices, int n_ranks, int gather) {
+                   const int* devices, int n_ranks, int gather, int background) {
     const double t0 = now_ms();
     std::vector<uint8_t> blob;
     std::string err;
@@ -1241,6 +1253,7 @@ int render_to_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, void* ou
         // path (1 MB chunks, ~15 GB/s: 2.3 ms per 1080p call instead of 0.8, tools/micro/hostpath.cpp), and
         // for a host-buffer render the download, not the chain of kernels, is the longer part.
         s->forced_lanes = 1;
+        s->background = background;
         rc = one_shot_streams(s);
         if (rc != MCRT_OK) break;
         const Shard mine = make_shard(*cfg, r, n_ranks);
@@ -1422,12 +1435,9 @@ int render_to_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, void* ou
     return MCRT_OK;
 }
 
-}  // namespace
-extern "C" {
-
-int mcrt_render_multi(const mcrt_scene_desc* desc, const mcrt_config* cfg, float* out_rgba, mcrt_progress_fn progress,
-                      void* user, const int* devices, int n_devices, int gather) {
-    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+// The bodies of mcrt_render_multi / mcrt_render_rgba8 behind their NULL-argument checks, with a background mode (mcrt_render_ex)
+int render_multi_impl(const mcrt_scene_desc* desc, const mcrt_config* cfg, float* out_rgba, mcrt_progress_fn progress, void* user,
+                      const int* devices, int n_devices, int gather, int background) {
     if (!valid_frame(cfg)) return MCRT_OK;  // generateTiles → empty → untouched Image (tile_renderer.cpp:144-146)
     if (!out_rgba) return fail(MCRT_ERR_INVALID, "out_rgba is NULL");
     if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
@@ -1441,23 +1451,11 @@ int mcrt_render_multi(const mcrt_scene_desc* desc, const mcrt_config* cfg, float
     }
     for (int i = 0; i < n_devices; ++i)
         if (devices[i] < 0 || devices[i] >= visible) return fail(MCRT_ERR_NO_DEVICE, "device index out of range");
-    return render_to_host(desc, cfg, out_rgba, 16, progress, user, devices, n_devices, gather ? 1 : 0);
+    return render_to_host(desc, cfg, out_rgba, 16, progress, user, devices, n_devices, gather ? 1 : 0, background);
 }
 
-int mcrt_render(const mcrt_scene_desc* desc, const mcrt_config* cfg, float* out_rgba, mcrt_progress_fn progress,
-                void* user, int device) {
-    if (device == MCRT_DEVICE_ALL) return mcrt_render_multi(desc, cfg, out_rgba, progress, user, nullptr, 0, 0);
-    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
-    if (!valid_frame(cfg)) return MCRT_OK;  // generateTiles → empty → untouched Image (tile_renderer.cpp:144-146)
-    if (!out_rgba) return fail(MCRT_ERR_INVALID, "out_rgba is NULL");
-    if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
-    if (mcrt_device_count() <= 0) return fail(MCRT_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    return render_to_host(desc, cfg, out_rgba, 16, progress, user, &device, 1, 0);
-}
-
-int mcrt_render_rgba8(const mcrt_scene_desc* desc, const mcrt_config* cfg, uint8_t* out_rgba8, mcrt_progress_fn progress, void* user,
-                      const int* devices, int n_devices, int gather) {
-    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+int render_rgba8_impl(const mcrt_scene_desc* desc, const mcrt_config* cfg, uint8_t* out_rgba8, mcrt_progress_fn progress, void* user,
+                      const int* devices, int n_devices, int gather, int background) {
     if (!valid_frame(cfg)) return MCRT_OK;
     if (!out_rgba8) return fail(MCRT_ERR_INVALID, "out_rgba8 is NULL");
     if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
@@ -1471,7 +1469,54 @@ int mcrt_render_rgba8(const mcrt_scene_desc* desc, const mcrt_config* cfg, uint8
     }
     for (int i = 0; i < n_devices; ++i)
         if (devices[i] < 0 || devices[i] >= visible) return fail(MCRT_ERR_NO_DEVICE, "device index out of range");
-    return render_to_host(desc, cfg, out_rgba8, 4, progress, user, devices, n_devices, gather ? 1 : 0);
+    return render_to_host(desc, cfg, out_rgba8, 4, progress, user, devices, n_devices, gather ? 1 : 0, background);
+}
+
+// mcrt_render_png behind its NULL-argument checks
+int render_png_impl(const mcrt_scene_desc* desc, const mcrt_config* cfg, const char* path, int device, int background) {
+    if (!valid_frame(cfg)) return fail(MCRT_ERR_INVALID, "empty image");
+    const size_t npix = static_cast<size_t>(cfg->width) * cfg->height;
+    std::vector<uint8_t> host(npix * 4);
+    // the RGBA8 plane straight from the kernels' epilogue: 4 B per pixel over PCIe (and xGMI) instead of 16
+    const int rc = device == MCRT_DEVICE_ALL ? render_rgba8_impl(desc, cfg, host.data(), nullptr, nullptr, nullptr, 0, 0, background)
+                                             : render_rgba8_impl(desc, cfg, host.data(), nullptr, nullptr, &device, 1, 0, background);
+    if (rc != MCRT_OK) return rc;
+    return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
+}
+
+}  // namespace
+extern "C" {
+
+int mcrt_render_multi(const mcrt_scene_desc* desc, const mcrt_config* cfg, float* out_rgba, mcrt_progress_fn progress,
+                      void* user, const int* devices, int n_devices, int gather) {
+    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+    return render_multi_impl(desc, cfg, out_rgba, progress, user, devices, n_devices, gather, MCRT_BACKGROUND_REFERENCE);
+}
+
+int mcrt_render(const mcrt_scene_desc* desc, const mcrt_config* cfg, float* out_rgba, mcrt_progress_fn progress,
+                void* user, int device) {
+    if (device == MCRT_DEVICE_ALL) return mcrt_render_multi(desc, cfg, out_rgba, progress, user, nullptr, 0, 0);
+    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (!valid_frame(cfg)) return MCRT_OK;  // generateTiles → empty → untouched Image (tile_renderer.cpp:144-146)
+    if (!out_rgba) return fail(MCRT_ERR_INVALID, "out_rgba is NULL");
+    if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
+    if (mcrt_device_count() <= 0) return fail(MCRT_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+    return render_to_host(desc, cfg, out_rgba, 16, progress, user, &device, 1, 0, MCRT_BACKGROUND_REFERENCE);
+}
+
+int mcrt_render_rgba8(const mcrt_scene_desc* desc, const mcrt_config* cfg, uint8_t* out_rgba8, mcrt_progress_fn progress, void* user,
+                      const int* devices, int n_devices, int gather) {
+    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+    return render_rgba8_impl(desc, cfg, out_rgba8, progress, user, devices, n_devices, gather, MCRT_BACKGROUND_REFERENCE);
+}
+
+int mcrt_render_ex(const mcrt_scene_desc* desc, const mcrt_config* cfg, int background, float* out_rgba, uint8_t* out_rgba8,
+                   mcrt_progress_fn progress, void* user, const int* devices, int n_devices, int gather) {
+    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (!valid_background(background)) return bad_background();
+    if ((out_rgba != nullptr) == (out_rgba8 != nullptr)) return fail(MCRT_ERR_INVALID, "exactly one of out_rgba / out_rgba8 must be given");
+    return out_rgba ? render_multi_impl(desc, cfg, out_rgba, progress, user, devices, n_devices, gather, background)
+                    : render_rgba8_impl(desc, cfg, out_rgba8, progress, user, devices, n_devices, gather, background);
 }
 
 int mcrt_render_rect(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_tile* tile, float* frame_rgba, int device) {
@@ -1520,14 +1565,13 @@ int mcrt_render_tile(const mcrt_scene_desc* desc, const mcrt_config* cfg, int ti
 // ---- PNG hand-off: the encoder and the file writers live in png_writer.cpp -------------------------
 int mcrt_render_png(const mcrt_scene_desc* desc, const mcrt_config* cfg, const char* path, int device) {
     if (!desc || !cfg || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
-    if (!valid_frame(cfg)) return fail(MCRT_ERR_INVALID, "empty image");
-    const size_t npix = static_cast<size_t>(cfg->width) * cfg->height;
-    std::vector<uint8_t> host(npix * 4);
-    // the RGBA8 plane straight from the kernels' epilogue: 4 B per pixel over PCIe (and xGMI) instead of 16
-    const int rc = device == MCRT_DEVICE_ALL ? mcrt_render_rgba8(desc, cfg, host.data(), nullptr, nullptr, nullptr, 0, 0)
-                                             : mcrt_render_rgba8(desc, cfg, host.data(), nullptr, nullptr, &device, 1, 0);
-    if (rc != MCRT_OK) return rc;
-    return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
+    return render_png_impl(desc, cfg, path, device, MCRT_BACKGROUND_REFERENCE);
+}
+
+int mcrt_render_png_ex(const mcrt_scene_desc* desc, const mcrt_config* cfg, int background, const char* path, int device) {
+    if (!desc || !cfg || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (!valid_background(background)) return bad_background();
+    return render_png_impl(desc, cfg, path, device, background);
 }
 
 int mcrt_last_timings(mcrt_timings* out) {
@@ -1834,10 +1878,11 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
     if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
         return fail(MCRT_ERR_INVALID, "a batch cannot be recorded into a caller's graph (its parameter table is uploaded per call)");
     (void)hipGetLastError();
-    // every frame on lane 0 of its handle, one lane: the batched kernels take it when it fits their envelope
+    // every frame on lane 0 of its handle, one lane: the batched kernels take it when it fits their envelope.  The frames
+    // of a launch sequence share their background mode (it selects the `resolve` kernel): one group per mode.
     std::vector<RenderParams> p(static_cast<size_t>(n));
-    std::vector<mcrt_scene*> in_batch;
-    std::vector<RenderParams> batch_p;
+    std::vector<mcrt_scene*> in_batch[2];
+    std::vector<RenderParams> batch_p[2];
     std::vector<int> alone;
     for (int i = 0; i < n; ++i) {
         mcrt_scene* s = scenes[i];
@@ -1851,19 +1896,22 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
         const int rc = prepare(s, 0, 1, cfg, 0, 1, MCRT_LAYOUT_FRAME, f, b, p[static_cast<size_t>(i)]);
         if (rc != MCRT_OK) return rc;
         if (batch_eligible(p[static_cast<size_t>(i)])) {
-            in_batch.push_back(s);
-            batch_p.push_back(p[static_cast<size_t>(i)]);
+            const int mode = p[static_cast<size_t>(i)].background == MCRT_BACKGROUND_TRANSPARENT ? 1 : 0;
+            in_batch[mode].push_back(s);
+            batch_p[mode].push_back(p[static_cast<size_t>(i)]);
         } else {
             alone.push_back(i);
         }
     }
-    const int nb = static_cast<int>(in_batch.size());
-    for (int c0 = 0; c0 < nb; c0 += kBatchMaxFrames) {  // one launch sequence per kBatchMaxFrames frames
-        const int m = std::min(kBatchMaxFrames, nb - c0);
-        const int rc = launch_batch_sequence(in_batch.data() + c0, batch_p.data() + c0, m, device, stream);
-        if (rc != MCRT_OK) return rc;
-        g_batch_frames += m;
-        ++g_batch_sequences;
+    for (int mode = 0; mode < 2; ++mode) {
+        const int nb = static_cast<int>(in_batch[mode].size());
+        for (int c0 = 0; c0 < nb; c0 += kBatchMaxFrames) {  // one launch sequence per kBatchMaxFrames frames
+            const int m = std::min(kBatchMaxFrames, nb - c0);
+            const int rc = launch_batch_sequence(in_batch[mode].data() + c0, batch_p[mode].data() + c0, m, device, stream);
+            if (rc != MCRT_OK) return rc;
+            g_batch_frames += m;
+            ++g_batch_sequences;
+        }
     }
     // the rest (more than one pass, or the general variants) one after the other through the single-frame path
     for (int i : alone) {
@@ -1885,6 +1933,11 @@ int mcrt_render_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt
 }
 
 int mcrt_render_batch(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, float* out_rgba, uint8_t* out_rgba8, int device) {
+    return mcrt_render_batch_ex(descs, n_frames, cfg, MCRT_BACKGROUND_REFERENCE, out_rgba, out_rgba8, device);
+}
+
+int mcrt_render_batch_ex(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, int background, float* out_rgba,
+                         uint8_t* out_rgba8, int device) {
     g_batch_frames = 0;
     g_batch_sequences = 0;
     if (n_frames < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
@@ -1892,6 +1945,7 @@ int mcrt_render_batch(const mcrt_scene_desc* const* descs, int n_frames, const m
     for (int i = 0; i < n_frames; ++i)
         if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
     if (!out_rgba && !out_rgba8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
+    if (!valid_background(background)) return bad_background();
     if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
     if (n_frames == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
     std::vector<std::vector<uint8_t>> blobs(static_cast<size_t>(n_frames));
@@ -1911,6 +1965,7 @@ int mcrt_render_batch(const mcrt_scene_desc* const* descs, int n_frames, const m
     for (int i = 0; i < n_frames; ++i) {
         const int rc = create_scene_from_blob(blobs[static_cast<size_t>(i)], device, &h[static_cast<size_t>(i)]);
         if (rc != MCRT_OK) return cleanup(rc);
+        h[static_cast<size_t>(i)]->background = background;
     }
     mcrt_scene* s0 = h[0];
     if (one_shot_streams(s0) != MCRT_OK) return cleanup(MCRT_ERR_HIP);

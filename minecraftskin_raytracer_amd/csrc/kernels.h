@@ -111,6 +111,8 @@ struct RenderParams {
                            //    go to HBM; 0 (more than 24 draws per pixel): all streams to HBM, `primary` renders them
     int bg_kernel;         // 1 (bg_in_plan == 0 and many samples per pixel): `background_kernel` renders the background tiles from their
                            //    streams, slab by slab through LDS; 0: `primary`'s tail does, a lane per pixel straight from HBM
+    int background;        // MCRT_BACKGROUND_*.  TRANSPARENT: background tiles are (0,0,0,0) without draws (`plan_tiles`; bg_in_plan
+                           //    is then 1 and bg_kernel 0 at every sample count) and `resolve_transparent` sums the samples that hit only
     int lit_round;         // `lit`: records per round (a block of 256)
     int lit_pass;          // `lit`: traced records per pass (their light samples live in LDS between two phases)
     int lit_lds_offset;    // `lit`: byte offset of that area in dynamic LDS (behind the scene tables, 16-aligned)
@@ -167,6 +169,7 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
 // frame's RenderParams (its own scene, workspace, counters and output) are read from a device-resident table
 // whether the batched kernels can take a frame: flat pipeline, a whole-frame shard, one pass (rows_per_batch >= owned rows)
 bool batch_eligible(const RenderParams& p);
+// frames of one launch sequence share the background mode (it selects the `resolve` kernel)
 struct BatchPlan {
     int view = 0;        // the kernel variant of the whole batch (the most general any frame needs)
     size_t dyn = 0;      // dynamic LDS of primary / ao: the largest frame's scene tables

@@ -34,6 +34,8 @@
 //                   1 lane / record   Blinn-Phong (+AO) → the chain's stack of level colours
 //   resolve         1 lane / pixel    folds each sample's chain back to front, ordered sum of the pixel's sample
 //                                     colours (float addition order is part of the result), coalesced float4 / RGBA8 store
+//                                     (transparent background: `plan_tiles` fills background tiles with (0,0,0,0), and
+//                                     `resolve_transparent` sums the samples that hit only — mcrt.h)
 //   (general variants — per-hit RNG streams longer than 227 draws, or more than kFlatMaxBounces bounces — run
 //   light_samples / shadow / level_shade once per recursion level instead of lit, and `primary` traces no
 //   reflection rays)
@@ -644,6 +646,8 @@ __device__ __forceinline__ void plan_tiles_body(const uint8_t* __restrict__ scen
     } else if (mask != 0ull) {  // a tile meshes can touch: its draws, at its touched-tile number
         if (p.draws_per_sample > 0 && ord != ~0u)
             tile_stream_wave(sc, tile_rng, tile_draws + static_cast<size_t>(ord) * stride, nullptr, nullptr, p, tg, tile, part * per_wave, per_wave, s_state[wave], lane);
+    } else if (p.background == MCRT_BACKGROUND_TRANSPARENT) {  // no sample of the tile can hit: (0,0,0,0), no draws (bg_in_plan is 1)
+        fill_tile(p, tg, out_frame, out8, make_float4(0.0f, 0.0f, 0.0f, 0.0f), static_cast<unsigned>(part * 64 + lane), static_cast<unsigned>(parts) * 64u);
     } else if (float4 pixel; constant_background(sc, p, tg, pixel)) {  // background tile of one colour: no draws, no samples
         fill_tile(p, tg, out_frame, out8, pixel, static_cast<unsigned>(part * 64 + lane), static_cast<unsigned>(parts) * 64u);
     } else if (p.cfg.samples_per_pixel > 1) {  // background tile, jittered samples
@@ -1671,6 +1675,20 @@ __global__ __launch_bounds__(kBlock, 2) void level_shade_kernel(const uint8_t* _
 // missed (:94-102), the clamped last level colour when it stopped at maxBounces (:146-147).
 // A thread per SAMPLE fetches / folds the colour; the pixel's samples meet in LDS and one thread per
 // pixel adds them in order (float addition order is part of the result).
+// kTransparent (MCRT_BACKGROUND_TRANSPARENT, mcrt.h): a sample whose primary ray missed (kEndMiss) adds nothing and is not
+// counted — its colour is never formed, so the tile's draws are not read here at all — and the pixel is (0,0,0,0) without a
+// hit, else rgb · (1.0f / hits) and alpha · (1.0f / spp).  Both reciprocals are IEEE divisions (hipcc's default correctly
+// rounded fp32 divide, like inv_spp).  A template parameter, not a field test: the reference instantiation is the kernel
+// as it was, registers and LDS included.
+template <bool kTransparent>
+struct ResolveLds {
+    float4 col[kBlock];
+};
+template <>
+struct ResolveLds<true> {
+    float4 col[kBlock];
+    uint8_t hit[kBlock];  // the sample's primary ray hit
+};
 __device__ __forceinline__ float4 sample_colour(const WaveSpace& ws, uint32_t slot, uint32_t code, const C4& flat_bg) {
     if (code == 0u) return ws.scol[slot];
     const float4* lv = ws.stack + slot;  // level d of the chain: lv[d * cap]
@@ -1688,10 +1706,12 @@ __device__ __forceinline__ float4 sample_colour(const WaveSpace& ws, uint32_t sl
     }
     return make_float4(tail.r, tail.g, tail.b, tail.a);
 }
+template <bool kTransparent>
 __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
                                              float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams& __restrict__ p,
                                              const int tile_base) {
-    __shared__ float4 s_col[kBlock];
+    __shared__ ResolveLds<kTransparent> s_lds;
+    float4* s_col = s_lds.col;
     const WaveSpace& ws = p.ws;
     const mcrt_config& cfg = p.cfg;
     const SceneView scg = view_of(scene_blob);
@@ -1726,6 +1746,27 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
         store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx),
                     make_float4(acc.x * inv_spp, acc.y * inv_spp, acc.z * inv_spp, acc.w * inv_spp));
     };
+    // transparent: the colour of a sample whose primary ray hit (else `hit` = false and nothing is formed)
+    auto hit_sample = [&](const uint4& d, uint32_t sidx, bool& hit) __attribute__((always_inline)) -> float4 {
+        const uint32_t slot = d.w + sidx;
+        const uint32_t code = ws.end[slot];
+        hit = code != kEndMiss;
+        if (!hit) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return sample_colour(ws, slot, code, C4{scg.hdr->background[0], scg.hdr->background[1], scg.hdr->background[2], scg.hdr->background[3]});
+    };
+    // transparent: the sum of the n samples that hit
+    auto put_pixel_transparent = [&](const TileGeom& tg, uint32_t i, float4 acc, uint32_t n) __attribute__((always_inline)) {
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (n > 0u) {
+            const float inv_n = 1.0f / static_cast<float>(n);
+            v = make_float4(acc.x * inv_n, acc.y * inv_n, acc.z * inv_n, acc.w * inv_spp);
+        }
+        const uint32_t uly = i / static_cast<uint32_t>(tg.w);
+        const int ly = static_cast<int>(uly);
+        const int lx = static_cast<int>(i - uly * static_cast<uint32_t>(tg.w));
+        const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
+        store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx), v);
+    };
     MCRT_HOOK_RESOLVE_BEGIN()
     if (blockIdx.x == 0) {  // the pass has counted everything: where the counters stand is the next pass's base
         for (int i = threadIdx.x; i < kCounterWords - 4; i += kBlock) ws.counter_base[i] = ws.counters[i];
@@ -1739,25 +1780,56 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
         if (chunk_px == 0u) {
             for (uint32_t i = pp0 + threadIdx.x; i < pp1; i += kBlock) {
                 float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                for (uint32_t s = 0; s < spp; ++s) {
-                    const float4 c = unit_sample(d, tg, draws, (i - pp0) * spp + s, spp);
-                    acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
+                if constexpr (kTransparent) {
+                    uint32_t n = 0;
+                    for (uint32_t s = 0; s < spp; ++s) {
+                        bool hit;
+                        const float4 c = hit_sample(d, (i - pp0) * spp + s, hit);
+                        if (!hit) continue;
+                        acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
+                        ++n;
+                    }
+                    put_pixel_transparent(tg, i, acc, n);
+                } else {
+                    for (uint32_t s = 0; s < spp; ++s) {
+                        const float4 c = unit_sample(d, tg, draws, (i - pp0) * spp + s, spp);
+                        acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
+                    }
+                    put_pixel(tg, i, acc);
                 }
-                put_pixel(tg, i, acc);
             }
             continue;
         }
         for (uint32_t p0 = pp0; p0 < pp1; p0 += chunk_px) {  // uniform
             const uint32_t npx = min(chunk_px, pp1 - p0);
-            if (threadIdx.x < npx * spp) s_col[threadIdx.x] = unit_sample(d, tg, draws, (p0 - pp0) * spp + threadIdx.x, spp);
+            if constexpr (kTransparent) {
+                if (threadIdx.x < npx * spp) {
+                    bool hit;
+                    s_col[threadIdx.x] = hit_sample(d, (p0 - pp0) * spp + threadIdx.x, hit);
+                    s_lds.hit[threadIdx.x] = hit ? 1 : 0;
+                }
+            } else {
+                if (threadIdx.x < npx * spp) s_col[threadIdx.x] = unit_sample(d, tg, draws, (p0 - pp0) * spp + threadIdx.x, spp);
+            }
             __syncthreads();
             if (threadIdx.x < npx) {
                 float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                for (uint32_t s = 0; s < spp; ++s) {
-                    const float4 c = s_col[threadIdx.x * spp + s];
-                    acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
+                if constexpr (kTransparent) {
+                    uint32_t n = 0;
+                    for (uint32_t s = 0; s < spp; ++s) {
+                        if (!s_lds.hit[threadIdx.x * spp + s]) continue;
+                        const float4 c = s_col[threadIdx.x * spp + s];
+                        acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
+                        ++n;
+                    }
+                    put_pixel_transparent(tg, p0 + threadIdx.x, acc, n);
+                } else {
+                    for (uint32_t s = 0; s < spp; ++s) {
+                        const float4 c = s_col[threadIdx.x * spp + s];
+                        acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
+                    }
+                    put_pixel(tg, p0 + threadIdx.x, acc);
                 }
-                put_pixel(tg, p0 + threadIdx.x, acc);
             }
             __syncthreads();
         }
@@ -1766,7 +1838,11 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
 __global__ __launch_bounds__(kBlock) void resolve_kernel(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
                                                          float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
                                                          const int tile_base) {
-    resolve_body(scene_blob, tile_draws, out_frame, out8, p, tile_base);
+    resolve_body<false>(scene_blob, tile_draws, out_frame, out8, p, tile_base);
+}
+__global__ __launch_bounds__(kBlock) void resolve_transparent_kernel(const uint8_t* __restrict__ scene_blob, float4* __restrict__ out_frame,
+                                                                     uchar4* __restrict__ out8, const RenderParams p, const int tile_base) {
+    resolve_body<true>(scene_blob, nullptr, out_frame, out8, p, tile_base);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1812,7 +1888,11 @@ __global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_batch_kernel(Param
 }
 __global__ __launch_bounds__(kBlock) void resolve_batch_kernel(ParamTable table) {
     const RenderParams& p = frame_params(table);
-    resolve_body(p.scene, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
+    resolve_body<false>(p.scene, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
+}
+__global__ __launch_bounds__(kBlock) void resolve_transparent_batch_kernel(ParamTable table) {
+    const RenderParams& p = frame_params(table);
+    resolve_body<true>(p.scene, nullptr, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2085,7 +2165,9 @@ WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* r
     // itself (few draws per pixel: a 624-word twist then completes >= 26 pixels, enough for whole rounds of
     // the wave's 64 lanes), of every tile of the batch otherwise
     const size_t draws_stride = tile_slots * static_cast<size_t>(p.draws_per_sample);
-    p.bg_in_plan = spp * static_cast<size_t>(p.draws_per_sample) <= 24 ? 1 : 0;
+    // A transparent frame takes the touched-tiles layout at every sample count: its background tiles are (0,0,0,0) and need
+    // no stream at all, so only the touched tiles' draws exist (no `background_kernel`, no background work in `primary`).
+    p.bg_in_plan = (p.background == MCRT_BACKGROUND_TRANSPARENT || spp * static_cast<size_t>(p.draws_per_sample) <= 24) ? 1 : 0;
     static const size_t slab_min_spp = [] {  // development knob (the parity sweeps run the slab kernel at every sample count with it)
         const char* e = getenv("MCRT_SLAB_MIN_SPP");
         const int v = e ? atoi(e) : 0;
@@ -2256,7 +2338,10 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
             launch_levels<kViewHbm>(p, stream, 0);
         }
         const int rgrid = batch_tiles * p.parts_per_tile < resolve_grid ? batch_tiles * p.parts_per_tile : resolve_grid;
-        hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, p.ws.tile_draws, out, out8, p, tile_base);
+        if (p.background == MCRT_BACKGROUND_TRANSPARENT)
+            hipLaunchKernelGGL(resolve_transparent_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, out, out8, p, tile_base);
+        else
+            hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, p.ws.tile_draws, out, out8, p, tile_base);
         const int batch = r0 / p.rows_per_batch;
         if (marks && batch < marks->n_batch_done) {
             e = hipEventRecord(marks->batch_done[batch], stream);
@@ -2295,7 +2380,8 @@ hipError_t plan_batch(RenderParams* f, int n, bool others_running, BatchPlan& pl
         // the launch shapes are functions of the config: frames that disagree cannot share a launch
         if (!batch_eligible(q) || std::memcmp(&q.cfg, &a.cfg, sizeof(mcrt_config)) != 0 || std::memcmp(&q.shard, &a.shard, sizeof(Shard)) != 0 ||
             q.parts_per_tile != a.parts_per_tile || q.stream_parts != a.stream_parts || q.stream_part_twists != a.stream_part_twists ||
-            q.draws_per_sample != a.draws_per_sample || q.bg_in_plan != a.bg_in_plan || q.bg_kernel != a.bg_kernel || q.lit_lds_bytes != a.lit_lds_bytes)
+            q.draws_per_sample != a.draws_per_sample || q.bg_in_plan != a.bg_in_plan || q.bg_kernel != a.bg_kernel || q.lit_lds_bytes != a.lit_lds_bytes ||
+            q.background != a.background)
             return hipErrorInvalidValue;
         any_hbm = any_hbm || !q.scene_in_lds;
         any_posed = any_posed || q.scene_posed;
@@ -2366,7 +2452,10 @@ hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& b, const
     else
         launch_batch_stages<kViewHbm>(p0, b, d_table, F, n, stream);
     const int rgrid = n * p0.parts_per_tile < p0.grid_resolve ? n * p0.parts_per_tile : p0.grid_resolve;
-    hipLaunchKernelGGL(resolve_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
+    if (p0.background == MCRT_BACKGROUND_TRANSPARENT)
+        hipLaunchKernelGGL(resolve_transparent_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
+    else
+        hipLaunchKernelGGL(resolve_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
     return hipGetLastError();
 }
 
