@@ -196,6 +196,27 @@ void mcrt_trim(void);
  * reference's scale lie): built once in ~2 ms, it replaces a 397-step recurrence per hit by one load, with
  * identical results.  MCRT_SEED_TABLE=0 turns it off; mcrt_trim() frees it when no scene handle is left. */
 
+/* Background plates.  The gradient background tiles of a frame (three quarters of the tiles of a 1080p frame of the
+ * character) do not depend on the scene: their pixels are a function of width, height, tile_size, samples_per_pixel,
+ * depth of field on / off, gradient_scale and the two gradient colours alone (the jitter comes from the tile's own
+ * mt19937 stream).  The second time such a configuration is rendered on a device — every render call counts, a whole
+ * frame, one rank's shard (a frame rendered as N shard calls is N renders) or a whole batch call alike; opaque gradient
+ * background, 2 to 12 samples per pixel (6 under depth of field) — the library renders those tiles once
+ * more into a plate kept on the device, tile by tile, and every later render of the configuration copies them from it:
+ * identical pixels, a fifth fewer instructions per 1080p / 4 spp frame.  Building a plate costs about one render's first
+ * kernel plus two allocations, synchronously inside that render call (never inside a caller's graph capture: such renders
+ * take no plate).  Memory: ceil(width / tile_size) * ceil(height / tile_size) * tile_size^2 * 16 bytes per plate (1080p at
+ * tile 32: 33.4 MB, 4K: 133.7 MB); at most 8 plates and MCRT_BG_PLATE_BUDGET_MB MiB per device — a configuration whose plate
+ * does not fit gets none and renders as before — plates no scene handle uses make way for new ones, and mcrt_trim() frees
+ * them.  A scene handle holds the plates of the four configurations it rendered last: a handle that goes through more
+ * (a sweep of the gradient colour, say) waits, at each change to a configuration it does not hold, for its own previous
+ * render — not for other handles' frames — and records its launch graphs for that plate anew; a render that builds a
+ * plate, or frees one to make room, waits for the device as any allocation does.  A build that fails (memory refused) is
+ * tried again 16 renders of the configuration later.  MCRT_BG_PLATE=0 turns plates off, MCRT_BG_PLATE=2 builds at a configuration's first render (development knobs). */
+#define MCRT_BG_PLATE_BUDGET_MB 256
+/* plates currently kept on `device`, their bytes, and how many were built there since the process began (any may be NULL) */
+int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds);
+
 /* Waits for the scene's device work and reports an internal inconsistency of the last renders (the
  * workspace is sized for the tiles the host expects meshes to touch; the device flags a tile beyond
  * that bound instead of writing past it).  MCRT_OK in every correct run; the one-shot entry points

@@ -4,6 +4,7 @@ from .skins import synthetic_skin  # noqa: F401
 from .api import (  # noqa: F401
     DeviceScene,
     assemble_frame_device,
+    bg_plate_info,
     ImageWriter,
     MeshBuilder,
     SceneDesc,
@@ -27,5 +28,5 @@ __all__ = [
     "Config", "Mesh", "Scene", "Texture", "synthetic_skin", "DeviceScene", "MeshBuilder", "SceneDesc",
     "TileRenderer", "device_count", "flatten", "getBuiltinPoses", "probe_detmath", "probe_detmath_range",
     "probe_mt_uniform", "quantize_rgba8", "quantize_rgba8_device", "unpack_rows_device", "ImageWriter", "render_png", "assemble_frame_device", "trim",
-    "render_batch_device", "last_batch_info",
+    "render_batch_device", "last_batch_info", "bg_plate_info",
 ]

@@ -115,6 +115,21 @@ struct Lane {
     bool counters_dirty = false;  // a render's launches failed half way: counters and their base no longer fit (cleared before the next render)
 };
 
+// One background plate of a device (kernels.h) and the frame settings its pixels are a function of — nothing else enters
+// (RngKey above says the same of the tile seeds).  Entries live in the per-device store further down.
+struct BgPlateKey {
+    int width, height, tile_size, spp, draws_per_sample, gradient_bg, div_frame;
+    float gradient_scale, bg_center[3], bg_edge[3];
+};
+struct BgPlate {
+    BgPlateKey key;
+    float4* ptr = nullptr;  // NULL: the key has been sighted, no plate built (yet)
+    size_t bytes = 0;
+    int users = 0;          // scene shells (live or pooled) that hold the pointer — in prepared parameters, recorded launch graphs, launches in flight
+    int sightings = 0;      // render calls with this key while it had no plate (negative after a failed build: see build_plate)
+    unsigned long long last_use = 0;
+};
+
 struct mcrt_scene {
     int device = 0;
     uint32_t alpha_words = 0;
@@ -162,6 +177,9 @@ struct mcrt_scene {
     bool holds_seed_table = false;
     const uint32_t* seed_table_full = nullptr;  // the device's table for every 32-bit seed (ambient occlusion), or NULL
     bool holds_full_table = false, full_table_tried = false;
+    // background plates this shell holds a `users` count of, least recently used first: its recorded launch graphs and its
+    // launches in flight may read them, so one is let go of only behind a device synchronisation (acquire_bg_plate)
+    std::vector<BgPlate*> plates;
 };
 
 namespace {
@@ -279,6 +297,8 @@ void touched_tiles_per_row(const mcrt_scene* sc, const mcrt_config& cfg, const S
 }
 
 const uint32_t* acquire_full_seed_table(int device);  // below, with the per-device tables
+// the device's background plate for the frame prepared as `p`, or nullptr (below, with the per-device tables)
+const float4* acquire_bg_plate(mcrt_scene* s, const RenderParams& p, bool capturing, bool count_sighting);
 
 // fill RenderParams for lane `li` of `n_lanes` over the shard (first, step) + make sure its
 // workspace exists (allocation only when it has to grow)
@@ -611,6 +631,11 @@ int enqueue_render(mcrt_scene* s, const mcrt_config* cfg, int first, int step, i
         for (int li = 0; li < n_lanes; ++li) choose_grids(p[li], shared, company);
     }
     if (capturing && groups) return fail(MCRT_ERR_INVALID, "row-group events cannot be recorded into a caller's graph");
+    {  // the gradient background tiles: copied from the device's plate of this frame configuration when it has one (built, if
+       // at all, before anything of this render is enqueued; every lane and shard reads the same plate)
+        const float4* plate = acquire_bg_plate(s, p[0], capturing, true);
+        for (int li = 0; li < n_lanes; ++li) p[li].bg_plate = plate;
+    }
     // all renders of a handle share its workspace: they run one after the other whatever streams they are given
     if (!capturing && s->have_last && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->last_done, 0));
     s->flags_checked = false;
@@ -826,6 +851,190 @@ void free_unused_seed_tables() {  // mcrt_trim
     }
 }
 
+// ---- per-device background plates (kernels.h; mcrt.h states the memory cost and the knobs) -------------------------
+// A store per device, under one mutex, entries with a `users` count like the seed tables.  An entry starts as a sighting
+// record (no memory); the plate is built at the key's second render call on the device — one-shot calls and sweeps over
+// thousands of sizes never allocate — synchronously, on the store's own non-blocking stream, never on the null stream and
+// never while the caller records a graph.  Once built a plate is immutable: no validity flags, nothing published or
+// tested on the device, no writer beside a reader.  Plates nobody holds make way, least recently used first, when a
+// new one needs the room; one that does not fit gets no plate and the frame renders as it always did.
+constexpr size_t kBgPlateBudget = static_cast<size_t>(MCRT_BG_PLATE_BUDGET_MB) << 20;  // built plates of a device, together
+constexpr int kBgPlateBuilt = 8;     // built plates per device
+constexpr int kBgPlateKeys = 32;     // entries per device, sighting records included
+constexpr int kBgPlateRetryAfter = 16;  // sightings a key waits after a failed build before the next try
+constexpr size_t kHeldPlates = 4;    // plates one scene shell holds at a time (as many as it records launch graphs)
+struct DevicePlates {
+    std::vector<BgPlate*> entries;
+    unsigned long long clock = 0;
+    hipStream_t stream = nullptr;  // the builds
+    size_t bytes = 0;              // of the built plates
+    int built = 0;
+    int builds = 0;                // plates built so far (mcrt_bg_plate_info)
+};
+std::mutex g_plate_mutex;
+std::vector<DevicePlates> g_plates;  // by device
+
+int bg_plate_mode() {  // development knob MCRT_BG_PLATE: 0 no plates, 2 build at a key's first render (tests); else at the second
+    static const int mode = [] {
+        const char* e = std::getenv("MCRT_BG_PLATE");
+        const int v = e ? std::atoi(e) : 1;
+        return v == 0 ? 0 : (v == 2 ? 2 : 1);
+    }();
+    return mode;
+}
+BgPlateKey bg_plate_key_of(const RenderParams& p) {
+    BgPlateKey k;
+    std::memset(&k, 0, sizeof k);
+    k.width = p.cfg.width, k.height = p.cfg.height, k.tile_size = p.cfg.tile_size;
+    k.spp = p.cfg.samples_per_pixel > 1 ? p.cfg.samples_per_pixel : 1;
+    k.draws_per_sample = p.draws_per_sample;
+    k.gradient_bg = p.cfg.gradient_bg ? 1 : 0;
+    k.div_frame = p.div_frame;
+    k.gradient_scale = p.cfg.gradient_scale;
+    for (int i = 0; i < 3; ++i) k.bg_center[i] = p.cfg.bg_center[i], k.bg_edge[i] = p.cfg.bg_edge[i];
+    return k;
+}
+bool same_key(const BgPlateKey& a, const BgPlateKey& b) { return std::memcmp(&a, &b, sizeof a) == 0; }  // (floats by their bits)
+
+// g_plate_mutex held.  Frees a built plate nobody holds: every holder synchronised the device before it let go.
+void free_plate(DevicePlates& d, BgPlate* e) {
+    if (!e->ptr) return;
+    (void)hipFree(e->ptr);
+    e->ptr = nullptr;
+    d.bytes -= e->bytes;
+    e->bytes = 0;
+    --d.built;
+}
+// g_plate_mutex held, the device current.  Builds e's plate for the frame prepared as `p`; leaves e->ptr NULL when there is no room
+// (asked again at the key's next render) or the build fails (an allocation refused, for one: asked again kBgPlateRetryAfter sightings later).
+void build_plate(DevicePlates& d, BgPlate* e, const RenderParams& p, size_t bytes) {
+    while (d.built >= kBgPlateBuilt || d.bytes + bytes > kBgPlateBudget) {
+        BgPlate* victim = nullptr;
+        for (BgPlate* q : d.entries)
+            if (q != e && q->ptr && q->users == 0 && (!victim || q->last_use < victim->last_use)) victim = q;
+        if (!victim) return;
+        free_plate(d, victim);
+        victim->sightings = 0;
+    }
+    float4* plate = nullptr;
+    uint32_t* rng = nullptr;
+    hipError_t err = d.stream ? hipSuccess : hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipMalloc(&plate, bytes);
+    if (err == hipSuccess) err = hipMalloc(&rng, bg_plate_rng_bytes(p));
+    if (err == hipSuccess) err = launch_fill_bg_plate(p, plate, rng, d.stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(d.stream);
+    if (rng) (void)hipFree(rng);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        if (plate) (void)hipFree(plate);
+        e->sightings = -kBgPlateRetryAfter;
+        return;
+    }
+    e->ptr = plate;
+    e->bytes = bytes;
+    d.bytes += bytes;
+    ++d.built;
+    ++d.builds;
+}
+// The shell lets go of the plate it has held longest.  Its launches in flight and its recorded launch graphs may read the
+// plate: its last render is waited for — every render of a handle ends in `last_done`, lanes joined, and a handle's renders
+// run one after the other, so nothing of this handle reads the plate after it; other handles' frames are not waited
+// for — and those graphs are dropped first.
+void drop_held_plate(mcrt_scene* s) {
+    BgPlate* e = s->plates.front();
+    if (s->have_last && s->last_done) (void)hipEventSynchronize(s->last_done);
+    for (auto& r : s->recorded) {
+        bool reads = false;
+        for (int li = 0; li < kMaxLanes; ++li) reads = reads || (r.p[li].bg_plate != nullptr && r.p[li].bg_plate == e->ptr);
+        if (!reads) continue;
+        if (r.exec) (void)hipGraphExecDestroy(r.exec);
+        if (r.graph) (void)hipGraphDestroy(r.graph);
+        r.exec = nullptr;
+        r.graph = nullptr;
+        r.n_lanes = 0;
+        r.sightings = 0;
+    }
+    s->plates.erase(s->plates.begin());
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    --e->users;
+}
+void release_bg_plates(mcrt_scene* s) {  // the shell goes (its device work has been waited for)
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    for (BgPlate* e : s->plates) --e->users;
+    s->plates.clear();
+}
+
+const float4* acquire_bg_plate(mcrt_scene* s, const RenderParams& p, bool capturing, bool count_sighting) {
+    const int mode = bg_plate_mode();
+    // (a caller's graph outlives this call in ways the library cannot see: a render recorded into it takes no plate)
+    if (mode == 0 || capturing || !bg_plate_eligible(p)) return nullptr;
+    const BgPlateKey key = bg_plate_key_of(p);
+    for (size_t i = 0; i < s->plates.size(); ++i)
+        if (same_key(s->plates[i]->key, key)) {  // held already: no lock, the entry cannot change under a holder
+            BgPlate* e = s->plates[i];
+            s->plates.erase(s->plates.begin() + static_cast<long>(i));
+            s->plates.push_back(e);
+            return e->ptr;
+        }
+    const size_t bytes = bg_plate_bytes(p.cfg);
+    if (bytes == 0 || bytes > kBgPlateBudget) return nullptr;
+    BgPlate* got = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_plate_mutex);
+        if (g_plates.size() <= static_cast<size_t>(s->device)) g_plates.resize(static_cast<size_t>(s->device) + 1);
+        DevicePlates& d = g_plates[static_cast<size_t>(s->device)];
+        ++d.clock;
+        BgPlate* e = nullptr;
+        for (BgPlate* q : d.entries)
+            if (same_key(q->key, key)) e = q;
+        if (!e) {
+            if (d.entries.size() >= static_cast<size_t>(kBgPlateKeys)) {  // the least recently used entry nobody holds becomes this key's
+                for (BgPlate* q : d.entries)
+                    if (q->users == 0 && (!e || q->last_use < e->last_use)) e = q;
+                if (!e) return nullptr;
+                free_plate(d, e);
+                *e = BgPlate{};
+            } else {
+                e = new BgPlate();
+                d.entries.push_back(e);
+            }
+            e->key = key;
+        }
+        e->last_use = d.clock;
+        if (!e->ptr) {
+            if (count_sighting) ++e->sightings;
+            if (e->sightings >= (mode == 2 ? 1 : 2)) build_plate(d, e, p, bytes);
+        }
+        if (e->ptr) {
+            ++e->users;
+            got = e;
+        }
+    }
+    if (!got) return nullptr;
+    if (s->plates.size() >= kHeldPlates) drop_held_plate(s);
+    s->plates.push_back(got);
+    return got->ptr;
+}
+void free_unused_bg_plates() {  // mcrt_trim
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    for (size_t dev = 0; dev < g_plates.size(); ++dev) {
+        DevicePlates& d = g_plates[dev];
+        (void)hipSetDevice(static_cast<int>(dev));
+        std::vector<BgPlate*> kept;
+        for (BgPlate* e : d.entries) {
+            if (e->users > 0) {
+                kept.push_back(e);
+                continue;
+            }
+            free_plate(d, e);
+            delete e;
+        }
+        d.entries.swap(kept);
+        if (d.stream) (void)hipStreamDestroy(d.stream);  // idle: every build waited for it under this mutex
+        d.stream = nullptr;
+    }
+}
+
 // keeps `s` for reuse unless it is large — MCRT_POOL_MB, by default a twelfth of the device's memory (24 GB of the
 // MI355X's 288: the 1080p and 4K frames of BASELINE.json stay pooled, and a host application that never calls
 // mcrt_trim() does not sit on a fifth of the card; the one-shot entry points plan their workspace to stay below it, see
@@ -1008,6 +1217,7 @@ void mcrt_trim(void) {
         destroy_scene_now(s);
     }
     free_unused_seed_tables();
+    free_unused_bg_plates();
 }
 
 namespace {
@@ -1016,6 +1226,7 @@ void destroy_scene_now(mcrt_scene* s) {
     unregister_live(s);  // before its events go
     if (s->holds_seed_table) release_seed_table(s->device);
     if (s->holds_full_table) release_full_seed_table(s->device);
+    release_bg_plates(s);
     s->blob.release();  // the other buffers are released by their destructors below
     for (auto& ln : s->lanes) {
         if (ln.stream) (void)hipStreamSynchronize(ln.stream);
@@ -1574,6 +1785,15 @@ int mcrt_render_png_ex(const mcrt_scene_desc* desc, const mcrt_config* cfg, int 
     return render_png_impl(desc, cfg, path, device, background);
 }
 
+int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds) {
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    const DevicePlates* d = (device >= 0 && static_cast<size_t>(device) < g_plates.size()) ? &g_plates[static_cast<size_t>(device)] : nullptr;
+    if (plates) *plates = d ? d->built : 0;
+    if (bytes) *bytes = d ? d->bytes : 0;
+    if (builds) *builds = d ? d->builds : 0;
+    return MCRT_OK;
+}
+
 int mcrt_last_timings(mcrt_timings* out) {
     if (!out) return MCRT_ERR_INVALID;
     *out = g_timings;
@@ -1884,6 +2104,7 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
     std::vector<mcrt_scene*> in_batch[2];
     std::vector<RenderParams> batch_p[2];
     std::vector<int> alone;
+    bool plate_sighted = false;
     for (int i = 0; i < n; ++i) {
         mcrt_scene* s = scenes[i];
         if (cfg->ao_enabled && cfg->ao_samples > 0 && !s->full_table_tried) {  // as the handle's first AO render would
@@ -1896,6 +2117,9 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
         const int rc = prepare(s, 0, 1, cfg, 0, 1, MCRT_LAYOUT_FRAME, f, b, p[static_cast<size_t>(i)]);
         if (rc != MCRT_OK) return rc;
         if (batch_eligible(p[static_cast<size_t>(i)])) {
+            // the device's background plate of the config, through the handle like a single render's; the batch is ONE sighting of its key
+            p[static_cast<size_t>(i)].bg_plate = acquire_bg_plate(s, p[static_cast<size_t>(i)], false, !plate_sighted);
+            plate_sighted = true;
             const int mode = p[static_cast<size_t>(i)].background == MCRT_BACKGROUND_TRANSPARENT ? 1 : 0;
             in_batch[mode].push_back(s);
             batch_p[mode].push_back(p[static_cast<size_t>(i)]);

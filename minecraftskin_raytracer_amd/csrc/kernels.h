@@ -95,6 +95,8 @@ struct RenderParams {
     float* out;            // float4 frame or packed rows (may be NULL when out8 is given)
     uint8_t* out8;         // RGBA8 frame or packed rows, quantised in the epilogue (may be NULL)
     uint32_t* tile_rng;    // owned_tiles x stream_parts x 624 mt19937 state words (NULL when no tile draws)
+    const float4* bg_plate;  // the device's background plate of this frame configuration (below), or NULL: `plan_tiles` computes
+                           //    the gradient background tiles itself
     WaveSpace ws;
     int draws_per_sample;  // 0, 2 or 4
     int stream_waves;      // waves per tile in `plan_tiles` (1, 2 or 4, <= stream_parts; choose_grids)
@@ -134,6 +136,25 @@ struct RenderParams {
 };
 
 Shard make_shard(const mcrt_config& cfg, int first, int step);
+
+// ---- background plate: the finished pixels of every gradient background tile of a frame configuration.  Such a tile's
+// pixels are a function of the frame's size, the tile size, the samples per pixel, the draws per sample, the gradient's
+// settings and the div_frame mode alone (the jitter comes from the tile's own mt19937 stream, seeded tile.y * width + tile.x);
+// scene, camera, light, shard and output layout do not enter.  Tile-major over ALL tiles of the frame: global tile
+// ty * tiles_x + tx owns tile_size^2 float4, a clipped edge tile's w x h pixels row-major at the front of its slot.  The
+// slots of the one-colour tiles (constant_background) are never written and never read.  Built once per device and key by
+// launch_fill_bg_plate with the code `plan_tiles` runs without a plate, immutable afterwards: `plan_tiles` copies from it.
+
+// whether a frame prepared as `p` can take a plate: opaque gradient background, jittered samples, rendered in `plan_tiles`,
+// a whole-frame entry point (not a renderTile rectangle)
+bool bg_plate_eligible(const RenderParams& p);
+// bytes of the plate of cfg's frame; 0 when the size does not fit 32-bit pixel indices
+size_t bg_plate_bytes(const mcrt_config& cfg);
+// bytes of the scratch launch_fill_bg_plate needs: the engine states of every tile of the frame
+size_t bg_plate_rng_bytes(const RenderParams& p);
+// Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
+// `tile_rng` is scratch of bg_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
+hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream);
 
 // Sizes of the workspace arrays for p.cfg / p.shard; fills p.parts_per_tile, p.rows_per_batch and
 // p.ws.cap / p.ws.stack_stride.  budget_bytes bounds the per-batch workspace (a batch is never

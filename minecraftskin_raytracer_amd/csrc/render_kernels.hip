@@ -103,6 +103,7 @@ struct FrameDiv {
 struct TileGeom {
     int x, y, w, h;
     int owned_row;  // index of this tile's row among the rows this launch owns
+    int frame_tile;  // row-major index of the tile in the whole frame (its slot in a background plate, kernels.h)
 };
 
 __device__ __forceinline__ TileGeom tile_of(const RenderParams& p, int owned_tile) {
@@ -110,6 +111,7 @@ __device__ __forceinline__ TileGeom tile_of(const RenderParams& p, int owned_til
     if (p.rect_w > 0) {  // the one tile of a renderTile call: any rectangle of the frame
         t.x = p.rect_x, t.y = p.rect_y, t.w = p.rect_w, t.h = p.rect_h;
         t.owned_row = 0;
+        t.frame_tile = 0;
         return t;
     }
     int k = owned_tile / p.shard.tiles_x;
@@ -121,6 +123,7 @@ __device__ __forceinline__ TileGeom tile_of(const RenderParams& p, int owned_til
     t.w = min(ts, p.cfg.width - t.x);
     t.h = min(ts, p.cfg.height - t.y);
     t.owned_row = k;
+    t.frame_tile = ty * p.shard.tiles_x + tx;
     return t;
 }
 
@@ -179,7 +182,8 @@ __device__ __forceinline__ void store_pixel(float4* __restrict__ out_frame, ucha
 // ---------------------------------------------------------------------------------------------
 constexpr int kStreamWaves = 4;  // tiles per workgroup
 // the pixels [lo, hi) of a background tile; draw(g, jx, jy) = draws number g, g + 1 of the tile's stream (g even)
-template <class DrawFn>
+// kToPlate: out_frame is a background plate (kernels.h) — the pixel goes to the tile's slot, tile-major, instead of the frame
+template <bool kToPlate = false, class DrawFn>
 __device__ __forceinline__ void background_pixels(const SceneView& sc, const RenderParams& p, const TileGeom& tg, float4* __restrict__ out_frame,
                                                   uchar4* __restrict__ out8, unsigned lo, unsigned hi, int lane, DrawFn&& draw) {
     const mcrt_config& cfg = p.cfg;
@@ -204,9 +208,13 @@ __device__ __forceinline__ void background_pixels(const SceneView& sc, const Ren
             ab += c.b;
             aa += c.a;
         }
-        const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
-        store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx),
-                    make_float4(ar * inv_spp, ag * inv_spp, ab * inv_spp, aa * inv_spp));
+        const float4 pixel = make_float4(ar * inv_spp, ag * inv_spp, ab * inv_spp, aa * inv_spp);
+        if constexpr (kToPlate) {
+            out_frame[static_cast<size_t>(tg.frame_tile) * static_cast<size_t>(cfg.tile_size) * static_cast<size_t>(cfg.tile_size) + pix] = pixel;
+        } else {
+            const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
+            store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx), pixel);
+        }
     }
 }
 
@@ -262,6 +270,23 @@ __device__ __forceinline__ void fill_tile(const RenderParams& p, const TileGeom&
     }
 }
 
+// the tile's pixels from its slot of the background plate (kernels.h): one coalesced 16-byte load per pixel, then the
+// frame's own store (layout, RGBA8 plane); `nthreads` threads, this one being number `tid`
+__device__ __forceinline__ void copy_plate_tile(const RenderParams& p, const TileGeom& tg, float4* __restrict__ out_frame, uchar4* __restrict__ out8,
+                                                unsigned tid, unsigned nthreads) {
+    const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+    const float4* __restrict__ src = p.bg_plate + static_cast<size_t>(tg.frame_tile) * static_cast<size_t>(p.cfg.tile_size) * static_cast<size_t>(p.cfg.tile_size);
+    const UDiv by_w(static_cast<unsigned>(tg.w));
+    for (unsigned pix = tid; pix < npix; pix += nthreads) {
+        const float4 pixel = src[pix];
+        const unsigned uly = by_w.div(pix);
+        const int ly = static_cast<int>(uly);
+        const int lx = static_cast<int>(pix - uly * static_cast<unsigned>(tg.w));
+        const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * p.cfg.tile_size + ly) : (tg.y + ly);
+        store_pixel(out_frame, out8, static_cast<size_t>(row) * p.cfg.width + (tg.x + lx), pixel);
+    }
+}
+
 // executed by one wave; `st` = its 2 x 624 words of LDS.  dst != nullptr: the tile's draws go there;
 // dst == nullptr: a background tile, rendered from the draws in LDS.
 // jitter_only (a background tile under depth of field, 4 draws per sample): only the samples' jitter pairs are stored,
@@ -275,6 +300,7 @@ __device__ __forceinline__ void fill_tile(const RenderParams& p, const TileGeom&
 // 64 spp: `plan_tiles` alone on the device is the latency of that chain at two waves per SIMD).  A wave writes its own
 // draws, or — background tile — renders the pixels whose FIRST draw lies in its parts; a pixel whose draws run over their
 // end is finished by one more twist of the same wave (the next wave makes the same words again).
+template <bool kToPlate = false>
 __device__ __forceinline__ void tile_stream_wave(const SceneView& sc, const uint32_t* __restrict__ tile_rng, float* __restrict__ dst,
                                                  float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams& p,
                                                  const TileGeom& tg, int tile, int part, int n_parts, uint32_t* st, int lane, bool jitter_only = false) {
@@ -353,7 +379,7 @@ __device__ __forceinline__ void tile_stream_wave(const SceneView& sc, const uint
             if (take > 0u) {
                 // (g and done are even: the pair is 8-byte aligned in either buffer — one LDS read instead of two, half the
                 // cycles of the 8-lanes-per-bank stride a lane per pixel reads the stream with)
-                background_pixels(sc, p, tg, out_frame, out8, pixels_done, pixels_done + take, lane, [&](unsigned g, float& jx, float& jy) __attribute__((always_inline)) {
+                background_pixels<kToPlate>(sc, p, tg, out_frame, out8, pixels_done, pixels_done + take, lane, [&](unsigned g, float& jx, float& jy) __attribute__((always_inline)) {
                     const uint2 w = *reinterpret_cast<const uint2*>((g >= done) ? n + (g - done) : o + (g + 624u - done));
                     jx = mt_to_unit(mt_temper(w.x));
                     jy = mt_to_unit(mt_temper(w.y));
@@ -650,8 +676,11 @@ __device__ __forceinline__ void plan_tiles_body(const uint8_t* __restrict__ scen
         fill_tile(p, tg, out_frame, out8, make_float4(0.0f, 0.0f, 0.0f, 0.0f), static_cast<unsigned>(part * 64 + lane), static_cast<unsigned>(parts) * 64u);
     } else if (float4 pixel; constant_background(sc, p, tg, pixel)) {  // background tile of one colour: no draws, no samples
         fill_tile(p, tg, out_frame, out8, pixel, static_cast<unsigned>(part * 64 + lane), static_cast<unsigned>(parts) * 64u);
-    } else if (p.cfg.samples_per_pixel > 1) {  // background tile, jittered samples
-        tile_stream_wave(sc, tile_rng, nullptr, out_frame, out8, p, tg, tile, part * per_wave, per_wave, s_state[wave], lane);
+    } else if (p.cfg.samples_per_pixel > 1) {  // background tile, jittered samples: from the device's plate when the frame has one
+        if (p.bg_plate)
+            copy_plate_tile(p, tg, out_frame, out8, static_cast<unsigned>(part * 64 + lane), static_cast<unsigned>(parts) * 64u);
+        else
+            tile_stream_wave(sc, tile_rng, nullptr, out_frame, out8, p, tg, tile, part * per_wave, per_wave, s_state[wave], lane);
     } else {  // background tile, one centred sample per pixel: no draws at all
         background_pixels(sc, p, tg, out_frame, out8, npix * static_cast<unsigned>(part) / static_cast<unsigned>(parts),
                           npix * static_cast<unsigned>(part + 1) / static_cast<unsigned>(parts), lane,
@@ -664,6 +693,23 @@ __global__ __launch_bounds__(64 * kStreamWaves) void plan_tiles_kernel(const uin
                                                                        uchar4* __restrict__ out8, const RenderParams p,
                                                                        const int tile_base, const int n_tiles) {
     plan_tiles_body(scene_blob, tile_rng, tile_draws, out_frame, out8, p, tile_base, n_tiles);
+}
+
+// Fills a background plate (kernels.h): every tile of the frame that is not of one colour, by `plan_tiles`' own routine for
+// a gradient background tile — whether or not meshes touch the tile in some scene.  p: a whole-frame shard, one wave per
+// stream part; p.scene is not read beyond its header (gradient background).
+__global__ __launch_bounds__(64 * kStreamWaves) void fill_bg_plate_kernel(const RenderParams p, float4* __restrict__ plate, const int n_tiles) {
+    __shared__ __align__(16) uint32_t s_state[kStreamWaves][2 * 624];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int parts = p.stream_parts;  // 1, 2 or 4: divides kStreamWaves
+    const int slot = static_cast<int>(blockIdx.x) * kStreamWaves + wave;
+    const int tile = slot / parts, part = slot - tile * parts;
+    if (tile >= n_tiles) return;  // wave-uniform; no workgroup barrier in this kernel
+    const TileGeom tg = tile_of(p, tile);
+    const SceneView sc = view_of(p.scene);
+    float4 unused;
+    if (constant_background(sc, p, tg, unused)) return;
+    tile_stream_wave<true>(sc, p.tile_rng, nullptr, plate, nullptr, p, tg, tile, part, 1, s_state[wave], lane);
 }
 
 // The engine states at the starts of a tile's parts 1 .. parts-1 (tile_stream_wave): one wave per tile twists the seeded
@@ -2348,6 +2394,44 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
             if (e != hipSuccess) return e;
         }
     }
+    return hipGetLastError();
+}
+
+// ---- background plate (kernels.h) ---------------------------------------------------------------
+bool bg_plate_eligible(const RenderParams& p) {
+    return p.background == MCRT_BACKGROUND_REFERENCE && p.cfg.gradient_bg != 0 && p.cfg.samples_per_pixel > 1 && p.bg_in_plan == 1 && p.rect_w <= 0 &&
+           p.draws_per_sample > 0;
+}
+size_t bg_plate_bytes(const mcrt_config& cfg) {
+    if (cfg.width <= 0 || cfg.height <= 0 || cfg.tile_size <= 0) return 0;
+    const size_t ts = static_cast<size_t>(cfg.tile_size);
+    const size_t tiles = ((static_cast<size_t>(cfg.width) + ts - 1) / ts) * ((static_cast<size_t>(cfg.height) + ts - 1) / ts);
+    if (ts > 0xffffull || tiles > 0x7fffffffull / (ts * ts)) return 0;
+    return tiles * ts * ts * sizeof(float4);
+}
+static RenderParams bg_plate_fill_params(const RenderParams& p) {
+    RenderParams q = p;
+    q.shard = make_shard(p.cfg, 0, 1);
+    q.layout = MCRT_LAYOUT_FRAME;
+    q.out = nullptr;
+    q.out8 = nullptr;
+    q.bg_plate = nullptr;
+    q.rect_x = q.rect_y = q.rect_w = q.rect_h = 0;
+    return q;
+}
+size_t bg_plate_rng_bytes(const RenderParams& p) {
+    const RenderParams q = bg_plate_fill_params(p);
+    return static_cast<size_t>(owned_tiles(q)) * 624 * 4 * static_cast<size_t>(q.stream_parts);
+}
+hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream) {
+    if (!bg_plate_eligible(p) || !plate || !tile_rng || bg_plate_bytes(p.cfg) == 0) return hipErrorInvalidValue;
+    RenderParams q = bg_plate_fill_params(p);
+    q.tile_rng = tile_rng;
+    const int n = owned_tiles(q);
+    if (n <= 0) return hipErrorInvalidValue;
+    hipError_t e = launch_seed_tiles(q, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fill_bg_plate_kernel, dim3((n * q.stream_parts + kStreamWaves - 1) / kStreamWaves), dim3(64 * kStreamWaves), 0, stream, q, plate, n);
     return hipGetLastError();
 }
 
