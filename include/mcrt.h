@@ -293,6 +293,68 @@ int mcrt_render_batch_ex(const mcrt_scene_desc* const* scenes, int n_frames, con
 /* mcrt_render_png with a background mode (the transparent PNG: colour type 6, straight alpha) */
 int mcrt_render_png_ex(const mcrt_scene_desc* scene, const mcrt_config* cfg, int background, const char* path, int device);
 
+/* ---- geometry layers: what is under each pixel ----------------------------------------------------------------------
+ * One ray per pixel through the pixel centre — u = (px + 0.5f) / width, v = (py + 0.5f) / height, Camera::generateRay(u, v,
+ * (float)width / (float)height): the reference's own primary ray at samplesPerPixel == 1 without depth of field
+ * (tile_renderer.cpp:92-103) — and the surface intersectScene finds for it (intersection.cpp:408-421).  No draws, no shading:
+ * of mcrt_config only width, height and tile_size are read (tile_size is the granularity of the culling and never changes a
+ * value); samples_per_pixel, depth of field, max_bounces, the shadow and ambient-occlusion settings and the background fields
+ * are IGNORED, and so is the handle's background mode.  Each layer is a plane of width * height pixels, row-major:
+ *   depth   1 float   HitResult::t                                   miss: FLT_MAX (what intersectScene leaves in t)
+ *   normal  4 floats  HitResult::normal, w = 0                       miss: 0 0 0 0
+ *   albedo  4 floats  HitResult::textureColor                        miss: 0 0 0 0
+ *   id      4 int32   {mesh, face, tx, ty}                           miss: {-1, 0, -1, -1}
+ * mesh: index into scene.meshes (the first mesh on a tie in t, as in the reference).  face & 7: the face slot in determineFace
+ * order — 0 back (-Z), 1 front (+Z), 2 left (+X), 3 right (-X), 4 top, 5 bottom; face & MCRT_ID_BACK: the hit is the outer
+ * layer's exit face (intersection.cpp:349-357); face & MCRT_ID_OUTER: HitResult::isOuterLayer.  tx, ty: the texel of the face's
+ * TextureRegion that sample() read; -1, -1 for a face without a texture or with an empty one (albedo then holds the reference's
+ * magenta or Color()).  Depth, normal and albedo are bit-identical to the reference's HitResult; a pixel whose id.mesh is -1 is
+ * (0,0,0,0) in the MCRT_BACKGROUND_TRANSPARENT frame of the same scene at samples_per_pixel 1 without depth of field.
+ * A layers pass reads the scene alone: it uses none of the handle's workspace, so it may run beside the handle's render on
+ * another stream; mcrt_scene_destroy and mcrt_scene_check wait for it.  Whole frames only (no tile-row shards, no packed
+ * layout, no lanes, not into a graph being recorded).
+ * MCRT_ERR_INVALID before any device work: a NULL config, handle, entry or layers struct, all four planes NULL, n < 0, a stride
+ * below width * height, handles on different devices.  Zero-size frames (width, height or tile_size <= 0) and n_frames = 0:
+ * MCRT_OK, nothing written. */
+#define MCRT_ID_BACK 8
+#define MCRT_ID_OUTER 16
+typedef struct mcrt_layers {
+    float* depth;  /* any may be NULL (that plane is not produced), not all */
+    float* normal;
+    float* albedo;
+    int32_t* id;
+} mcrt_layers;
+/* resident scene, device pointers, asynchronous on `stream` */
+int mcrt_render_layers_device(mcrt_scene* scene, const mcrt_config* cfg, const mcrt_layers* d_out, void* stream);
+/* n_frames scenes of one config in one launch, frame i at each plane + i * frame_stride_pixels pixels (>= width * height; the
+ * pixels between frames are not written).  A handle may be listed more than once. */
+int mcrt_render_layers_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_layers* d_out,
+                                    size_t frame_stride_pixels, void* stream);
+/* one-shot host forms: host pointers, rendered on `device` with pooled handles like mcrt_render; frame after frame */
+int mcrt_render_layers(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_layers* out, int device);
+int mcrt_render_layers_batch(const mcrt_scene_desc* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_layers* out, int device);
+
+/* Picking: the same question for n pixels, xy = n x {x, y} (host memory), one record per pixel into out (host memory): the
+ * four id fields, then depth, HitResult::point (0 0 0 at a miss), normal and albedo as in the planes — equal to the planes at
+ * that pixel.  Synchronous: one small launch, one small download.  A coordinate outside the frame → MCRT_ERR_INVALID (n = 0:
+ * MCRT_OK). */
+typedef struct mcrt_surface {
+    int32_t mesh, face, tx, ty;
+    float t;
+    float point[3];
+    float normal[4];
+    float albedo[4];
+} mcrt_surface; /* 64 bytes */
+int mcrt_scene_pick(mcrt_scene* scene, const mcrt_config* cfg, const int32_t* xy, int n, mcrt_surface* out);
+
+/* Skin coordinates (host only): (mesh, face slot 0..5, tx, ty) of a scene built by mcrt_build_skin_scene → the texel (x, y) of
+ * the skin image that face texel was cut from, by the builder's own tables (the mirrored left limbs of a legacy 64x32 skin
+ * included) — what an editor paints when the user clicks a pixel.  skin_height 64: meshes 0..11 = {head, body, right arm, left
+ * arm, right leg, left leg} x {inner, outer}; 32: 0 head, 1 head's outer layer, 2 body, 3 right arm, 4 left arm, 5 right leg,
+ * 6 left leg.  (The builder drops an outer part whose texels are all transparent, which moves the later meshes up: such a scene
+ * has fewer meshes than these tables.)  MCRT_ERR_INVALID for an argument out of range for that skin kind. */
+int mcrt_skin_texel(int skin_height, int mesh, int face_slot, int tx, int ty, int* skin_x, int* skin_y);
+
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);
 

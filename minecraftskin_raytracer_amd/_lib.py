@@ -26,6 +26,8 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_rgba8", "mcrt_render_rect", "mcrt_render_batch_device", "mcrt_render_batch", "mcrt_last_batch_info",
     "mcrt_scene_set_background", "mcrt_render_ex", "mcrt_render_batch_ex", "mcrt_render_png_ex",
     "mcrt_bg_plate_info",
+    "mcrt_render_layers_device", "mcrt_render_layers_batch_device", "mcrt_render_layers", "mcrt_render_layers_batch",
+    "mcrt_scene_pick", "mcrt_skin_texel",
 ]
 
 
@@ -44,6 +46,7 @@ def load():
     u8_p = C.POINTER(C.c_uint8)
     f_p = abi.c_float_p
     vp = C.c_void_p
+    layers_p = C.POINTER(abi.McrtLayers)
     sig = {
         "mcrt_config_init": (None, [cfg_p]),
         "mcrt_generate_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(abi.McrtTile), C.c_int]),
@@ -66,6 +69,12 @@ def load():
         "mcrt_render_ex": (C.c_int, [desc_p, cfg_p, C.c_int, f_p, u8_p, abi.PROGRESS_FN, vp, C.POINTER(C.c_int), C.c_int, C.c_int]),
         "mcrt_render_batch_ex": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, C.c_int, f_p, u8_p, C.c_int]),
         "mcrt_render_png_ex": (C.c_int, [desc_p, cfg_p, C.c_int, C.c_char_p, C.c_int]),
+        "mcrt_render_layers_device": (C.c_int, [vp, cfg_p, layers_p, vp]),
+        "mcrt_render_layers_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, layers_p, C.c_size_t, vp]),
+        "mcrt_render_layers": (C.c_int, [desc_p, cfg_p, layers_p, C.c_int]),
+        "mcrt_render_layers_batch": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, layers_p, C.c_int]),
+        "mcrt_scene_pick": (C.c_int, [vp, cfg_p, abi.c_int32_p, C.c_int, vp]),
+        "mcrt_skin_texel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),
         "mcrt_encode_png_rgba8": (C.c_size_t, [u8_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
         "mcrt_write_png_f32": (C.c_int, [C.c_char_p, f_p, C.c_int, C.c_int]),

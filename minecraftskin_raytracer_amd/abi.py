@@ -126,7 +126,62 @@ class McrtTimings(C.Structure):
     ]
 
 
+class McrtLayers(C.Structure):
+    """mcrt_layers: one pointer per plane (device or host memory, by entry point); NULL = not wanted."""
+
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("id", C.c_void_p)]
+
+
+class McrtSurface(C.Structure):
+    """mcrt_surface: what is under one pixel (mcrt_scene_pick)."""
+
+    _fields_ = [
+        ("mesh", C.c_int32),
+        ("face", C.c_int32),
+        ("tx", C.c_int32),
+        ("ty", C.c_int32),
+        ("t", C.c_float),
+        ("point", C.c_float * 3),
+        ("normal", C.c_float * 4),
+        ("albedo", C.c_float * 4),
+    ]
+
+
+ID_BACK = 8  # MCRT_ID_BACK: the outer layer's exit face
+ID_OUTER = 16  # MCRT_ID_OUTER: HitResult::isOuterLayer
+LAYER_NAMES = ("depth", "normal", "albedo", "id")
+# per pixel: (dtype, components) of each plane
+LAYER_FORMATS = {"depth": (np.float32, 1), "normal": (np.float32, 4), "albedo": (np.float32, 4), "id": (np.int32, 4)}
+
+
+def layer_names(layers) -> tuple:
+    """The wanted planes in the order of ``LAYER_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
+    if isinstance(layers, str):
+        layers = (layers,)
+    names = tuple(layers)
+    for n in names:
+        if not isinstance(n, str) or n not in LAYER_FORMATS:
+            raise ValueError(f"layers must be taken from {LAYER_NAMES}, not {n!r}")
+    if not names:
+        raise ValueError("no layer selected")
+    return tuple(n for n in LAYER_NAMES if n in names)
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
+
+SURFACE_DTYPE = np.dtype(
+    [
+        ("mesh", np.int32),
+        ("face", np.int32),
+        ("tx", np.int32),
+        ("ty", np.int32),
+        ("t", np.float32),
+        ("point", np.float32, 3),
+        ("normal", np.float32, 4),
+        ("albedo", np.float32, 4),
+    ]
+)
+assert SURFACE_DTYPE.itemsize == C.sizeof(McrtSurface) == 64
 
 HIT_DTYPE = np.dtype(
     [

@@ -259,6 +259,32 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderLayers(scene, config: Config, layers=abi.LAYER_NAMES, device: int = 0) -> dict:
+        """What is under each pixel (mcrt_render_layers): a dict of the wanted planes — ``depth`` (H, W) float32 (FLT_MAX at a
+        miss), ``normal`` and ``albedo`` (H, W, 4) float32, ``id`` (H, W, 4) int32 ``{mesh, face, tx, ty}`` (``{-1, 0, -1, -1}``
+        at a miss; ``face & 7`` the face slot, ``abi.ID_BACK`` / ``abi.ID_OUTER`` flags).  One pixel-centre ray per pixel, no
+        shading: of ``config`` only width, height and tileSize matter.  Failures raise ``McrtError``."""
+        out = TileRenderer.renderLayersBatch([scene], config, layers, device)
+        return {k: v[0] for k, v in out.items()}
+
+    @staticmethod
+    def renderLayersBatch(scenes, config: Config, layers=abi.LAYER_NAMES, device: int = 0) -> dict:
+        """``renderLayers`` for N scenes of one config in one launch (mcrt_render_layers_batch): the same planes with a leading
+        N."""
+        names = abi.layer_names(layers)
+        descs = [_as_desc(s) for s in scenes]
+        n = len(descs)
+        w, h = max(config.width, 0), max(config.height, 0)
+        out = {k: _empty_layer(k, n, h, w) for k in names}
+        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
+            return out
+        c = config.to_c()
+        arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*[d.ptr for d in descs])
+        planes = abi.McrtLayers(**{k: v.ctypes.data for k, v in out.items()})
+        check(load().mcrt_render_layers_batch(arr, n, C.byref(c), C.byref(planes), int(device)))
+        return out
+
+    @staticmethod
     def lastBatchInfo() -> dict:
         """How the last batch call on this thread ran (mcrt_last_batch_info): ``batched_frames`` taken by the batched
         kernels and ``launch_sequences`` enqueued (1 when the whole batch went through them at once)."""
@@ -273,6 +299,31 @@ class TileRenderer:
         t = abi.McrtTimings()
         load().mcrt_last_timings(C.byref(t))
         return {k: getattr(t, k) for k, _ in abi.McrtTimings._fields_}
+
+
+def _empty_layer(name: str, n: int, h: int, w: int) -> np.ndarray:
+    """One plane for n frames, holding the miss constants (what a frame of zero size keeps)."""
+    dtype, comps = abi.LAYER_FORMATS[name]
+    a = np.zeros((n, h, w) + ((comps,) if comps > 1 else ()), dtype)
+    if name == "depth":
+        a[...] = np.finfo(np.float32).max
+    elif name == "id":
+        a[...] = (-1, 0, -1, -1)
+    return a
+
+
+def skin_texel(kind, mesh: int, face: int, tx: int, ty: int) -> Tuple[int, int]:
+    """(mesh, face slot, tx, ty) of a scene built by ``MeshBuilder.buildScene`` → the skin image's texel ``(x, y)`` that face
+    texel was cut from (mcrt_skin_texel).  ``kind``: ``"S64"`` / ``"S32"`` or the skin's height.  Out-of-range arguments raise
+    ``ValueError``."""
+    heights = {"S64": 64, "S32": 32, 64: 64, 32: 32}
+    if isinstance(kind, bool) or kind not in heights:
+        raise ValueError("kind must be 'S64', 'S32', 64 or 32")
+    x, y = C.c_int(), C.c_int()
+    lib = load()
+    if lib.mcrt_skin_texel(heights[kind], int(mesh), int(face) & 7, int(tx), int(ty), C.byref(x), C.byref(y)) != 0:
+        raise ValueError(lib.mcrt_last_error().decode("utf-8", "replace"))
+    return int(x.value), int(y.value)
 
 
 def quantize_rgba8(image: np.ndarray) -> np.ndarray:
@@ -384,6 +435,34 @@ class DeviceScene:
                                              C.c_void_p(stream), iters, C.byref(a)))
         return float(a.value)
 
+    def render_layers_device(self, config: Config, depth_ptr: int = 0, normal_ptr: int = 0, albedo_ptr: int = 0, id_ptr: int = 0,
+                             stream: int = 0) -> None:
+        """The geometry layers of the frame into device memory (mcrt_render_layers_device): width * height pixels per plane —
+        depth 4 bytes per pixel, normal, albedo and id 16 — any pointer may be 0, not all.  Asynchronous on ``stream``;
+        uses none of the handle's workspace, so it may run beside a render of the handle on another stream."""
+        if not (depth_ptr or normal_ptr or albedo_ptr or id_ptr):
+            raise ValueError("give at least one of depth_ptr, normal_ptr, albedo_ptr, id_ptr")
+        c = config.to_c()
+        planes = abi.McrtLayers(depth_ptr or None, normal_ptr or None, albedo_ptr or None, id_ptr or None)
+        check(load().mcrt_render_layers_device(self._h, C.byref(c), C.byref(planes), C.c_void_p(stream)))
+
+    def pick(self, config: Config, xy) -> np.ndarray:
+        """What is under the pixels ``xy`` ((n, 2) integers, x then y, inside the frame): a structured array of
+        ``abi.SURFACE_DTYPE`` — mesh, face, tx, ty, t, point, normal, albedo — equal to the layers at those pixels
+        (mcrt_scene_pick).  Synchronous."""
+        a = np.asarray(xy)
+        if a.size == 0:
+            a = a.reshape(0, 2)
+        if a.ndim != 2 or a.shape[1] != 2 or a.dtype.kind not in "iu":
+            raise ValueError("xy must be an (n, 2) array of integer pixel coordinates")
+        if len(a) and (a.min() < 0 or (a[:, 0] >= config.width).any() or (a[:, 1] >= config.height).any()):
+            raise ValueError("a pick coordinate lies outside the frame")
+        q = np.ascontiguousarray(a, np.int32)
+        out = np.zeros(len(q), abi.SURFACE_DTYPE)
+        c = config.to_c()
+        check(load().mcrt_scene_pick(self._h, C.byref(c), q.ctypes.data_as(abi.c_int32_p), len(q), out.ctypes.data))
+        return out
+
     # ---- probes (per-function parity tests) ----
     def intersect(self, rays: np.ndarray) -> np.ndarray:
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
@@ -420,6 +499,28 @@ def render_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, 
     c = config.to_c()
     check(load().mcrt_render_batch_device(arr, n, C.byref(c), C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None),
                                           stride, C.c_void_p(stream)))
+
+
+def render_layers_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, depth_ptr: int = 0, normal_ptr: int = 0,
+                               albedo_ptr: int = 0, id_ptr: int = 0, frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
+    """The geometry layers of N resident scenes of one config in one launch (mcrt_render_layers_batch_device): frame i of
+    each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  Asynchronous on ``stream``."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    if not (depth_ptr or normal_ptr or albedo_ptr or id_ptr):
+        raise ValueError("give at least one of depth_ptr, normal_ptr, albedo_ptr, id_ptr")
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
+    if stride < px:
+        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    c = config.to_c()
+    planes = abi.McrtLayers(depth_ptr or None, normal_ptr or None, albedo_ptr or None, id_ptr or None)
+    check(load().mcrt_render_layers_batch_device(arr, n, C.byref(c), C.byref(planes), stride, C.c_void_p(stream)))
 
 
 def last_batch_info() -> dict:

@@ -165,6 +165,7 @@ struct mcrt_scene {
     bool flags_checked = true;  // no render since mcrt_scene_check last read (and cleared) the lanes' overflow words
     // the one-shot host path (mcrt_render & co): frame buffer, streams and events kept with the pooled workspace
     DeviceBuffer frame;                // float4 frame / packed rows / RGBA8 plane of a host-buffer render
+    DeviceBuffer pick;                 // mcrt_scene_pick: the pixels' coordinates, then their records (grown on demand)
     hipStream_t main_stream = nullptr;  // the render
     hipStream_t copy_stream = nullptr;  // downloads of finished tile rows, overlapping the render
     std::vector<hipEvent_t> marks;      // event pool of the row-group downloads
@@ -2225,6 +2226,201 @@ int mcrt_render_batch_ex(const mcrt_scene_desc* const* descs, int n_frames, cons
 int mcrt_last_batch_info(int* batched_frames, int* launch_sequences) {
     if (batched_frames) *batched_frames = g_batch_frames;
     if (launch_sequences) *launch_sequences = g_batch_sequences;
+    return MCRT_OK;
+}
+
+}  // extern "C"
+
+// ---- geometry layers: depth / normal / albedo / id planes and pixel picks (mcrt_render_layers_device & co) ----------------
+// A layers pass reads the scene blob alone — no workspace, no counters, no events of the handle — so it neither waits for the
+// handle's renders nor makes them wait; mcrt_scene_destroy and mcrt_scene_check synchronise the device, which covers it.
+namespace {
+
+bool no_plane(const mcrt_layers* l) { return !l->depth && !l->normal && !l->albedo && !l->id; }
+
+// frame `index` of a call: the handle's scene, the planes `index * stride` pixels on; returns the kernel variant it needs
+int layers_frame_of(const mcrt_scene* s, const mcrt_layers& out, size_t index, size_t stride, LayersFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.depth = out.depth ? out.depth + off : nullptr;
+    f.normal = out.normal ? reinterpret_cast<float4*>(out.normal) + off : nullptr;
+    f.albedo = out.albedo ? reinterpret_cast<float4*>(out.albedo) + off : nullptr;
+    f.id = out.id ? reinterpret_cast<int4*>(out.id) + off : nullptr;
+    return layers_view(f, s->alpha_words, s->n_meshes, s->posed);
+}
+
+int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream) {
+    // argument checks, before any device work (all but the last do not look inside the handles)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all four planes are NULL");
+    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    if (stride < static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height))
+        return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
+    const int device = scenes[0]->device;
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    LayersShape shape;
+    if (!make_layers_shape(*cfg, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(device));
+    if (n == 1) {  // one frame: its parameters travel as kernel arguments
+        LayersFrame f;
+        const int view = layers_frame_of(scenes[0], *d_out, 0, stride, f);
+        hipError_t e = launch_layers(f, shape, view, stream);
+        if (e != hipSuccess) return hip_fail(e, "layers launch");
+        return MCRT_OK;
+    }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(MCRT_ERR_INVALID, "a batch cannot be recorded into a caller's graph (its parameter table is uploaded per call)");
+    (void)hipGetLastError();
+    std::vector<LayersFrame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) views[static_cast<size_t>(i)] = layers_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
+    const int view = layers_batch_view(frames.data(), views.data(), n);
+    size_t dyn = 0;
+    for (const LayersFrame& f : frames) dyn = std::max(dyn, layers_lds_bytes(f));
+    // the frames' table: a slot of the batched renders' ring (refilled only after the launches that read it)
+    const size_t bytes = static_cast<size_t>(n) * sizeof(LayersFrame);
+    TableSlot* slot = acquire_table_slot(device);
+    if (!slot) return fail(MCRT_ERR_HIP, "too many batch calls filling parameter tables at once");
+    struct Release {
+        TableSlot* s;
+        ~Release() { release_table_slot(s); }
+    } release{slot};
+    if (slot->used) HIP_TRY(hipEventSynchronize(slot->done));
+    if (!slot->done) HIP_TRY(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    if (slot->host_bytes < bytes) {
+        if (slot->host) (void)hipHostFree(slot->host);
+        slot->host = nullptr;
+        slot->host_bytes = 0;
+        HIP_TRY(hipHostMalloc(&slot->host, bytes, hipHostMallocDefault));
+        slot->host_bytes = bytes;
+    }
+    HIP_TRY(slot->dev.reserve(bytes));
+    std::memcpy(slot->host, frames.data(), bytes);
+    hipError_t e = hipMemcpyAsync(slot->dev.ptr, slot->host, bytes, hipMemcpyHostToDevice, stream);
+    const LayersFrame* d_table = static_cast<const LayersFrame*>(slot->dev.ptr);
+    for (int c0 = 0; c0 < n && e == hipSuccess; c0 += kLayersBatchMaxFrames)  // one launch per kLayersBatchMaxFrames frames
+        e = launch_layers_batch(d_table + c0, std::min(kLayersBatchMaxFrames, n - c0), shape, view, dyn, stream);
+    if (e == hipSuccess) e = hipEventRecord(slot->done, stream);
+    if (e != hipSuccess) return hip_fail(e, "batched layers launches");
+    slot->used = true;
+    return MCRT_OK;
+}
+
+// bytes per pixel of the planes wanted, and the planes laid out one after the other in `base` for n_pixels pixels
+size_t layers_planes(const mcrt_layers& want, char* base, size_t n_pixels, mcrt_layers& at) {
+    size_t off = 0;
+    auto place = [&](bool wanted, size_t px_bytes) -> char* {
+        if (!wanted) return nullptr;
+        char* p = base ? base + off : nullptr;
+        off += n_pixels * px_bytes;
+        return p;
+    };
+    // the 16-byte planes first: every plane then starts on a 16-byte boundary
+    at.normal = reinterpret_cast<float*>(place(want.normal != nullptr, 16));
+    at.albedo = reinterpret_cast<float*>(place(want.albedo != nullptr, 16));
+    at.id = reinterpret_cast<int32_t*>(place(want.id != nullptr, 16));
+    at.depth = reinterpret_cast<float*>(place(want.depth != nullptr, 4));
+    return off;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcrt_render_layers_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_layers* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = (cfg && valid_frame(cfg)) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
+    return render_layers_batch_device(one, 1, cfg, d_out, px, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_layers_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_layers* d_out,
+                                    size_t frame_stride_pixels, void* stream) {
+    return render_layers_batch_device(scenes, n_frames, cfg, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_layers_batch(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_layers* out, int device) {
+    if (n_frames < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !out || (n_frames > 0 && !descs)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n_frames; ++i)
+        if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all four planes are NULL");
+    if (n_frames == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    std::vector<std::vector<uint8_t>> blobs(static_cast<size_t>(n_frames));
+    for (int i = 0; i < n_frames; ++i) {
+        std::string err;
+        if (!flatten_scene(descs[i], blobs[static_cast<size_t>(i)], err)) return fail(MCRT_ERR_INVALID, err);
+    }
+    const int visible = mcrt_device_count();
+    if (visible <= 0) return fail(MCRT_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= visible) return fail(MCRT_ERR_NO_DEVICE, "device index out of range");
+    std::vector<mcrt_scene*> h(static_cast<size_t>(n_frames), nullptr);
+    auto cleanup = [&](int code) {
+        for (mcrt_scene* s : h)
+            if (s) mcrt_scene_destroy(s);  // synchronises, pools a workspace
+        return code;
+    };
+    for (int i = 0; i < n_frames; ++i) {
+        const int rc = create_scene_from_blob(blobs[static_cast<size_t>(i)], device, &h[static_cast<size_t>(i)]);
+        if (rc != MCRT_OK) return cleanup(rc);
+    }
+    mcrt_scene* s0 = h[0];
+    if (one_shot_streams(s0) != MCRT_OK) return cleanup(MCRT_ERR_HIP);
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    const size_t total_px = px * static_cast<size_t>(n_frames);
+    mcrt_layers d{};
+    const size_t bytes = layers_planes(*out, nullptr, total_px, d);
+    hipError_t e = s0->frame.reserve(bytes);
+    if (e != hipSuccess) return cleanup(hip_fail(e, "layer planes"));
+    layers_planes(*out, static_cast<char*>(s0->frame.ptr), total_px, d);
+    int rc = render_layers_batch_device(h.data(), n_frames, cfg, &d, px, s0->main_stream);
+    auto download = [&](void* dst, const void* src, size_t px_bytes) {
+        if (rc != MCRT_OK || !dst) return;
+        e = hipMemcpyAsync(dst, src, total_px * px_bytes, hipMemcpyDeviceToHost, s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "download");
+    };
+    download(out->depth, d.depth, 4);
+    download(out->normal, d.normal, 16);
+    download(out->albedo, d.albedo, 16);
+    download(out->id, d.id, 16);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "layers render");
+    }
+    return cleanup(rc);
+}
+
+int mcrt_render_layers(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_layers* out, int device) {
+    if (!desc) return fail(MCRT_ERR_INVALID, "NULL argument");
+    const mcrt_scene_desc* one[1] = {desc};
+    return mcrt_render_layers_batch(one, 1, cfg, out, device);
+}
+
+int mcrt_scene_pick(mcrt_scene* s, const mcrt_config* cfg, const int32_t* xy, int n, mcrt_surface* out) {
+    if (!s || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n must be >= 0");
+    if (n == 0) return MCRT_OK;
+    if (!xy || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!valid_frame(cfg) || xy[2 * i] < 0 || xy[2 * i] >= cfg->width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= cfg->height)
+            return fail(MCRT_ERR_INVALID, "a pick coordinate lies outside the frame");
+    LayersShape shape;
+    if (!make_layers_shape(*cfg, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t xy_bytes = (static_cast<size_t>(n) * 8 + 63) & ~static_cast<size_t>(63);
+    HIP_TRY(s->pick.reserve(xy_bytes + static_cast<size_t>(n) * sizeof(mcrt_surface)));
+    int32_t* d_xy = static_cast<int32_t*>(s->pick.ptr);
+    mcrt_surface* d_out = reinterpret_cast<mcrt_surface*>(static_cast<char*>(s->pick.ptr) + xy_bytes);
+    HIP_TRY(hipMemcpy(d_xy, xy, static_cast<size_t>(n) * 8, hipMemcpyHostToDevice));
+    hipError_t e = launch_pick(static_cast<const uint8_t*>(s->blob.ptr), shape, d_xy, n, d_out, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, static_cast<size_t>(n) * sizeof(mcrt_surface), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "pick");
     return MCRT_OK;
 }
 

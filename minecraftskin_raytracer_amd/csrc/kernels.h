@@ -206,6 +206,41 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
+// ---- geometry layers (mcrt_render_layers_device & co): what is under each pixel — one pixel-centre ray per pixel
+// (Camera::generateRay at u = (px + 0.5f) / width, v = (py + 0.5f) / height), intersectScene, no draws, no shading.  The pass
+// reads the scene blob alone: no workspace, no counters.
+// One frame of a layers pass: its scene and its planes (any may be NULL, not all), row-major, width * height pixels each
+struct LayersFrame {
+    const uint8_t* scene;
+    float* depth;          // 1 float per pixel: HitResult::t, FLT_MAX at a miss
+    float4* normal;        // HitResult::normal, w = 0; zero at a miss
+    float4* albedo;        // HitResult::textureColor; zero at a miss
+    int4* id;              // {mesh, face slot | MCRT_ID_BACK | MCRT_ID_OUTER, tx, ty}; {-1, 0, -1, -1} at a miss
+    int lds_alpha_words;   // scene tables staged in LDS (as RenderParams'), 0 / 0 when the kernel reads them from HBM
+    int lds_face_entries;
+};
+// what the frames of one launch share: the frame's size (cfg: only width, height and tile_size are read) and its tile grid
+struct LayersShape {
+    mcrt_config cfg;
+    int tiles_x, tiles_y;
+    int parts;  // work units per tile: a workgroup takes 256 pixels of a tile
+};
+// false when the frame holds more units than the kernels index (2^31)
+bool make_layers_shape(const mcrt_config& cfg, LayersShape& shape);
+// fills f.lds_* for a scene of that size and returns the kernel variant it needs (kViewHbm, kViewLds or kViewLdsUnposed by
+// the rules of the beauty path)
+int layers_view(LayersFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
+// the variant of a batch: the most general any of its frames needs; rewrites the frames' LDS fields where it reads HBM
+int layers_batch_view(LayersFrame* frames, const int* views, int n);
+constexpr int kLayersBatchMaxFrames = 4096;  // frames per launch (blockIdx.y; larger batches take several launches)
+hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
+// frame's LDS tables
+hipError_t launch_layers_batch(const LayersFrame* d_table, int n_frames, const LayersShape& shape, int view, size_t max_dyn, hipStream_t stream);
+size_t layers_lds_bytes(const LayersFrame& f);
+// n pixels (d_xy: n x {x, y}, inside the frame) → n mcrt_surface records, by the device functions of the layers kernels
+hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream);
+
 hipError_t launch_unpack_rows(const mcrt_config& cfg, const Shard& sh, const float* packed, float* frame,
                               hipStream_t stream);
 hipError_t launch_unpack_rows8(const mcrt_config& cfg, const Shard& sh, const uint8_t* packed, uint8_t* frame, hipStream_t stream);  // RGBA8 plane

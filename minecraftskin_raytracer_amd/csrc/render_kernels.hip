@@ -39,6 +39,9 @@
 //   (general variants — per-hit RNG streams longer than 227 draws, or more than kFlatMaxBounces bounces — run
 //   light_samples / shadow / level_shade once per recursion level instead of lit, and `primary` traces no
 //   reflection rays)
+//   layers / pick   (not a stage of a render: mcrt_render_layers*, mcrt_scene_pick) a workgroup per tile: the tile's mesh
+//                                     mask, then either the miss constants or one pixel-centre ray per lane — depth, normal,
+//                                     albedo and {mesh, face, texel} planes straight from the scene blob, no workspace
 // Records live in HBM as SoA float4 arrays.  Every unit owns a fixed slot range (its samples); its
 // primary hits are compacted to the front of that range with an LDS prefix sum and a per-unit count —
 // NO global atomics on the hot path (a returning atomic on one word sustains only ~88 ops/us on this
@@ -420,14 +423,14 @@ struct LdsTables {
 };
 // dyn = dynamic LDS base; layout [face table: 4 ints per (mesh, face)][mesh table: kMeshTabWords per
 // mesh][alpha words].  Collective.
-__device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const RenderParams& p, unsigned char* dyn) {
+__device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const int lds_face_entries, const int lds_alpha_words, unsigned char* dyn) {
     int* s_faces = reinterpret_cast<int*>(dyn);
-    float* s_mtab = reinterpret_cast<float*>(dyn + static_cast<size_t>(p.lds_face_entries) * 16);
-    const int n_meshes = p.lds_face_entries / 6;
-    uint32_t* s_abits = reinterpret_cast<uint32_t*>(dyn + static_cast<size_t>(p.lds_face_entries) * 16 +
+    float* s_mtab = reinterpret_cast<float*>(dyn + static_cast<size_t>(lds_face_entries) * 16);
+    const int n_meshes = lds_face_entries / 6;
+    uint32_t* s_abits = reinterpret_cast<uint32_t*>(dyn + static_cast<size_t>(lds_face_entries) * 16 +
                                                     static_cast<size_t>(n_meshes) * kMeshTabWords * 4);
-    for (int i = threadIdx.x; i < p.lds_alpha_words; i += blockDim.x) s_abits[i] = g.abits[i];
-    for (int i = threadIdx.x; i < p.lds_face_entries; i += blockDim.x) {
+    for (int i = threadIdx.x; i < lds_alpha_words; i += blockDim.x) s_abits[i] = g.abits[i];
+    for (int i = threadIdx.x; i < lds_face_entries; i += blockDim.x) {
         const FlatMesh& fm = g.meshes[i / 6];
         const int f = i - (i / 6) * 6;
         s_faces[4 * i + 0] = fm.tex_off[f];
@@ -450,6 +453,9 @@ __device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const Rend
     }
     __syncthreads();
     return LdsTables{(const MCRT_LDS uint32_t*)s_abits, (const MCRT_LDS int*)s_faces, (const MCRT_LDS float*)s_mtab};
+}
+__device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const RenderParams& p, unsigned char* dyn) {
+    return stage_tables(g, p.lds_face_entries, p.lds_alpha_words, dyn);
 }
 // kernel variants by scene: kViewHbm — tables too large for LDS (reads HBM; any pose);
 // kViewLds — tables in LDS, posed meshes present; kViewLdsUnposed — tables in LDS, no posed mesh
@@ -1942,6 +1948,136 @@ __global__ __launch_bounds__(kBlock) void resolve_transparent_batch_kernel(Param
 }
 
 // ---------------------------------------------------------------------------------------------
+// geometry layers (kernels.h: LayersFrame): depth, normal, albedo and id planes, and single-pixel picks.  One pixel-centre
+// ray per pixel — the reference's primary ray at samplesPerPixel == 1 without depth of field (tile_renderer.cpp:92-103) —
+// and intersectScene; no draws, no records, no shading, no workspace.
+//   a workgroup per 256 pixels of a screen tile (grid-stride): every wave forms the tile's mesh mask as `plan_tiles` does
+//   (tile_mesh_mask without the lens padding); a tile nothing can touch — more than nine in ten of a full-size frame — is
+//   filled with the miss constants and builds no ray; the scene tables go to LDS at the workgroup's first touched tile only
+//   a touched tile: a lane per pixel, rows of the tile along the lanes, 16 B per lane and plane (the depths of four
+//   neighbouring pixels are collected into one lane where the rows are 16-byte aligned)
+// ---------------------------------------------------------------------------------------------
+struct Surface {  // mcrt_surface in registers
+    int mesh, face, tx, ty;
+    float t;
+    V3 p, n;
+    C4 tex;
+};
+__device__ __forceinline__ Surface miss_surface() {
+    return Surface{-1, 0, -1, -1, kFltMax, mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f), C4{0.0f, 0.0f, 0.0f, 0.0f}};
+}
+// what the pixel-centre ray of (px, py) meets, among the meshes of mesh_mask
+template <class SV>
+__device__ __forceinline__ Surface pixel_surface(const SV& sc, const mcrt_config& cfg, const float aspect, const int px, const int py,
+                                                 const unsigned long long mesh_mask) {
+    const float u = (static_cast<float>(px) + 0.5f) / static_cast<float>(cfg.width);
+    const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
+    const Ray ray = camera_ray(sc, u, v, aspect);
+    int mesh;
+    const Hit h = hit_scene(sc, ray, mesh_mask, &mesh);
+    Surface s = miss_surface();
+    if (h.hit) {
+        s.mesh = mesh;
+        s.face = face_slot(h.axis, h.neg) | (h.back ? MCRT_ID_BACK : 0) | (h.outer ? MCRT_ID_OUTER : 0);
+        hit_face_texel(sc, mesh, h, s.tx, s.ty);
+        s.t = h.t;
+        s.p = h.p;
+        s.n = h.n;
+        s.tex = h.tex;
+    }
+    return s;
+}
+// tile_mesh_mask for the pinhole camera: lane m of the calling wave tests mesh m
+__device__ __forceinline__ unsigned long long layers_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect, const int lane) {
+    const bool cull = sc.hdr->cull_ok != 0 && sc.n_meshes < 64;
+    bool touch = lane < sc.n_meshes;
+    if (touch && cull) touch = mesh_touches_tile(sc.meshes[lane], tg, cfg, aspect, 0.0f);
+    unsigned long long mask = __ballot(touch);
+    if (!cull && sc.n_meshes > 0) mask = ~0ull;
+    return mask;
+}
+template <int kView>
+__device__ __forceinline__ void layers_body(const LayersFrame& __restrict__ f, const LayersShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const int n_tiles = sh.tiles_x * sh.tiles_y;
+    // depths as one 16-byte store per four pixels: every tile row starts and ends on a 16-byte boundary of the plane
+    const bool quads = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.depth) & 15u) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    // a unit = kBlock pixels of a tile: a touched 32x32 tile is traced by four workgroups, a ray per lane each
+    const int parts = sh.parts;
+    const int n_units = n_tiles * parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        const int tile = unit / parts, part = unit - tile * parts;
+        const int tyi = tile / sh.tiles_x, txi = tile - tyi * sh.tiles_x;
+        TileGeom tg;
+        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+        tg.owned_row = tyi, tg.frame_tile = tile;
+        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
+        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
+        const unsigned long long mask = layers_tile_mask(scg, cfg, tg, aspect, lane);  // the same in every wave of the workgroup
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        const unsigned pix = p0 + static_cast<unsigned>(tid);
+        const bool valid = pix < npix;
+        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
+        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
+        Surface s = miss_surface();
+        if (mask != 0ull && valid) s = pixel_surface(sc, cfg, aspect, tg.x + lx, tg.y + ly, mask);
+        if (f.depth) {
+            if (quads) {  // tg.w is a multiple of 4: lanes 4k .. 4k+3 hold four neighbours of one row, all valid or none
+                const float t1 = __shfl_down(s.t, 1), t2 = __shfl_down(s.t, 2), t3 = __shfl_down(s.t, 3);
+                if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(f.depth + idx) = make_float4(s.t, t1, t2, t3);
+            } else if (valid) {
+                f.depth[idx] = s.t;
+            }
+        }
+        if (valid) {
+            if (f.normal) f.normal[idx] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
+            if (f.albedo) f.albedo[idx] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
+            if (f.id) f.id[idx] = make_int4(s.mesh, s.face, s.tx, s.ty);
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock) void layers_kernel(const LayersFrame f, const LayersShape sh) {
+    layers_body<kView>(f, sh);
+}
+using LayersTable = const __attribute__((address_space(4))) LayersFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock) void layers_batch_kernel(LayersTable table, const LayersShape sh) {
+    layers_body<kView>(*(const LayersFrame*)(table + blockIdx.y), sh);
+}
+// a lane per picked pixel, over the HBM view with every mesh tested (the tile masks only leave out meshes that cannot be hit)
+__global__ __launch_bounds__(64) void pick_kernel(const uint8_t* __restrict__ scene, const LayersShape sh, const int32_t* __restrict__ xy, const int n,
+                                                  mcrt_surface* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const SceneView sc = view_of(scene);
+    const float aspect = static_cast<float>(sh.cfg.width) / static_cast<float>(sh.cfg.height);
+    const Surface s = pixel_surface(sc, sh.cfg, aspect, xy[2 * i], xy[2 * i + 1], ~0ull);
+    float4* o = reinterpret_cast<float4*>(out + i);  // 64 bytes, 16-aligned (hipMalloc)
+    o[0] = make_float4(__int_as_float(s.mesh), __int_as_float(s.face), __int_as_float(s.tx), __int_as_float(s.ty));
+    o[1] = make_float4(s.t, s.p.x, s.p.y, s.p.z);
+    o[2] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
+    o[3] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
+}
+
+// ---------------------------------------------------------------------------------------------
 // small kernels
 // ---------------------------------------------------------------------------------------------
 template <class Pixel>  // float4, or uchar4 for the RGBA8 plane
@@ -2540,6 +2676,73 @@ hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& b, const
         hipLaunchKernelGGL(resolve_transparent_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
     else
         hipLaunchKernelGGL(resolve_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
+    return hipGetLastError();
+}
+
+// ---- geometry layers (kernels.h) ------------------------------------------------------------------
+int layers_view(LayersFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
+    const bool fits = alpha_words <= static_cast<uint32_t>(kAlphaLdsWordsMax) && n_meshes * 6 <= static_cast<uint32_t>(kFaceLdsEntriesMax);
+    f.lds_alpha_words = fits ? static_cast<int>(alpha_words) : 0;
+    f.lds_face_entries = fits ? static_cast<int>(n_meshes * 6) : 0;
+    return !fits ? kViewHbm : (posed ? kViewLds : kViewLdsUnposed);
+}
+int layers_batch_view(LayersFrame* frames, const int* views, int n) {
+    bool any_hbm = false, any_posed = false;
+    for (int i = 0; i < n; ++i) {
+        any_hbm = any_hbm || views[i] == kViewHbm;
+        any_posed = any_posed || views[i] == kViewLds;
+    }
+    if (any_hbm)
+        for (int i = 0; i < n; ++i) frames[i].lds_alpha_words = 0, frames[i].lds_face_entries = 0;
+    return any_hbm ? kViewHbm : (any_posed ? kViewLds : kViewLdsUnposed);
+}
+size_t layers_lds_bytes(const LayersFrame& f) {
+    return static_cast<size_t>(f.lds_face_entries) * 16 + static_cast<size_t>(f.lds_face_entries / 6) * kMeshTabWords * 4 + static_cast<size_t>(f.lds_alpha_words) * 4;
+}
+constexpr int kLayersGrid = 8192;  // workgroups per frame at most (the kernel strides over its units)
+bool make_layers_shape(const mcrt_config& cfg, LayersShape& shape) {
+    std::memset(&shape, 0, sizeof shape);
+    shape.cfg = cfg;
+    if (cfg.width <= 0 || cfg.height <= 0 || cfg.tile_size <= 0) return true;  // no tiles
+    shape.tiles_x = (cfg.width + cfg.tile_size - 1) / cfg.tile_size;
+    shape.tiles_y = (cfg.height + cfg.tile_size - 1) / cfg.tile_size;
+    const long long tile_px = static_cast<long long>(cfg.tile_size < cfg.width ? cfg.tile_size : cfg.width) * (cfg.tile_size < cfg.height ? cfg.tile_size : cfg.height);
+    const long long parts = (tile_px + kBlock - 1) / kBlock;
+    if (static_cast<long long>(shape.tiles_x) * shape.tiles_y * parts > 0x7fffffffll) return false;
+    shape.parts = static_cast<int>(parts);
+    return true;
+}
+static long long layers_units(const LayersShape& shape) { return static_cast<long long>(shape.tiles_x) * shape.tiles_y * shape.parts; }
+hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream) {
+    const long long n_units = layers_units(shape);
+    if (n_units <= 0) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid));
+    const size_t dyn = layers_lds_bytes(f);
+    if (view == kViewLdsUnposed)
+        hipLaunchKernelGGL(layers_kernel<kViewLdsUnposed>, grid, dim3(kBlock), dyn, stream, f, shape);
+    else if (view == kViewLds)
+        hipLaunchKernelGGL(layers_kernel<kViewLds>, grid, dim3(kBlock), dyn, stream, f, shape);
+    else
+        hipLaunchKernelGGL(layers_kernel<kViewHbm>, grid, dim3(kBlock), 0, stream, f, shape);
+    return hipGetLastError();
+}
+hipError_t launch_layers_batch(const LayersFrame* d_table, int n_frames, const LayersShape& shape, int view, size_t max_dyn, hipStream_t stream) {
+    const long long n_units = layers_units(shape);
+    if (n_units <= 0 || n_frames <= 0) return hipSuccess;
+    if (n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid), static_cast<unsigned>(n_frames));
+    LayersTable table = LayersTable(d_table);
+    if (view == kViewLdsUnposed)
+        hipLaunchKernelGGL(layers_batch_kernel<kViewLdsUnposed>, grid, dim3(kBlock), max_dyn, stream, table, shape);
+    else if (view == kViewLds)
+        hipLaunchKernelGGL(layers_batch_kernel<kViewLds>, grid, dim3(kBlock), max_dyn, stream, table, shape);
+    else
+        hipLaunchKernelGGL(layers_batch_kernel<kViewHbm>, grid, dim3(kBlock), 0, stream, table, shape);
+    return hipGetLastError();
+}
+hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pick_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, scene, shape, d_xy, n, d_out);
     return hipGetLastError();
 }
 

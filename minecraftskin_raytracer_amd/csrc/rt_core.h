@@ -676,9 +676,11 @@ DEV unsigned long long scene_candidates(const SV& sc, const RayQ& q, unsigned lo
 }
 
 // intersectScene :408-421.  mesh_mask: bit i set → mesh i is tested (primary-ray culling; all
-// ones for secondary rays).  Meshes beyond bit 63 are always tested.
+// ones for secondary rays).  Meshes beyond bit 63 are always tested.  mesh_out, if given, receives the mesh that was
+// hit (-1: none) — for the geometry layers; handed out of this function rather than out of a function of its own around the
+// loop, which cost `primary` 16 to 32 bytes of scratch and `lit` 5 VGPRs (profiles/layers/hit_scene_refactor.txt).
 template <bool kLeaving = false, class SV>
-DEV Hit hit_scene(const SV& sc, const Ray& r, uint64_t mesh_mask) {
+DEV Hit hit_scene(const SV& sc, const Ray& r, uint64_t mesh_mask, int* mesh_out = nullptr) {
     const RayQ q = prepare(r);
     Cand best;
     best.t = kFltMax;
@@ -731,7 +733,28 @@ DEV Hit hit_scene(const SV& sc, const Ray& r, uint64_t mesh_mask) {
         h.tex = texel_color(sc, best.texel);
         h.outer = best.back || (m.flags & MESH_OUTER) != 0;
     }
+    if (mesh_out) *mesh_out = best_mesh;
     return h;
+}
+
+// The texel of the face's TextureRegion that sample() read for a hit of mesh `mesh_index`: the pool index less the
+// face's offset, taken % and / the region's width.  (-1, -1) for a face without a texture or with an empty one.
+template <class SV>
+DEV void hit_face_texel(const SV& sc, int mesh_index, const Hit& h, int& tx, int& ty) {
+    tx = -1, ty = -1;
+    if (h.texel < 0) return;
+    const int face = face_slot(h.axis, h.neg);
+    int off, w;
+    if constexpr (SV::kLds) {
+        const MCRT_LDS int* f = sc.faces + (mesh_index * 6 + face) * 4;
+        off = f[0], w = f[1];
+    } else {
+        const FlatMesh& m = sc.meshes[mesh_index];
+        off = m.tex_off[face], w = m.tex_w[face];
+    }
+    const int rel = h.texel - off;
+    ty = rel / w;
+    tx = rel - ty * w;
 }
 
 // "hit && t < limit" over the scene without keeping the hit: isInShadow :25 and computeAO :72.

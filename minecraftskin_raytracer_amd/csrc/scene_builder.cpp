@@ -20,6 +20,8 @@
 #include <new>
 #include <vector>
 
+__attribute__((visibility("hidden"))) int mcrt_detail_fail(int code, const char* msg);  // api.cpp: sets mcrt_last_error()
+
 namespace {
 
 struct Region {  // TextureRegion
@@ -51,14 +53,42 @@ Region cut(const SkinImage& img, int x, int y, int w, int h) {
     return r;
 }
 
-PartTex unwrap(const SkinImage& img, int ox, int oy, int w, int h, int d) {
+// A body part in the skin image (skin_parser.cpp:11-20): origin of its box unwrap and the box's size in texels
+struct PartBox {
+    int ox, oy, w, h, d;
+};
+struct Rect {
+    int x, y, w, h;
+};
+// the rectangle of one face of the unwrap, faces in determineFace order: 0 back, 1 front, 2 left, 3 right, 4 top, 5 bottom
+Rect face_rect(const PartBox& b, int face) {
+    switch (face) {
+        case 0: return Rect{b.ox + 2 * b.d + b.w, b.oy + b.d, b.w, b.h};
+        case 1: return Rect{b.ox + b.d, b.oy + b.d, b.w, b.h};
+        case 2: return Rect{b.ox, b.oy + b.d, b.d, b.h};
+        case 3: return Rect{b.ox + b.d + b.w, b.oy + b.d, b.d, b.h};
+        case 4: return Rect{b.ox + b.d, b.oy, b.w, b.d};
+        default: return Rect{b.ox + b.d + b.w, b.oy, b.w, b.d};
+    }
+}
+// part origins (skin_parser.cpp:45-110): head, body, right arm, left arm, right leg, left leg.  A legacy 64x32 skin has the
+// head's outer layer only, and its left limbs are the right ones mirrored (mirror_part).
+const PartBox kInnerBox[6] = {{0, 0, 8, 8, 8}, {16, 16, 8, 12, 4}, {40, 16, 4, 12, 4}, {32, 48, 4, 12, 4}, {0, 16, 4, 12, 4}, {16, 48, 4, 12, 4}};
+const PartBox kOuterBox[6] = {{32, 0, 8, 8, 8}, {16, 32, 8, 12, 4}, {40, 32, 4, 12, 4}, {48, 48, 4, 12, 4}, {0, 32, 4, 12, 4}, {0, 48, 4, 12, 4}};
+const int kLegacyMirrorOf[6] = {-1, -1, -1, 2, -1, 4};  // legacy left arm = right arm mirrored, left leg = right leg mirrored
+
+PartTex unwrap(const SkinImage& img, const PartBox& b) {
+    auto face = [&](int f) {
+        const Rect r = face_rect(b, f);
+        return cut(img, r.x, r.y, r.w, r.h);
+    };
     PartTex p;
-    p.top = cut(img, ox + d, oy, w, d);
-    p.bottom = cut(img, ox + d + w, oy, w, d);
-    p.left = cut(img, ox, oy + d, d, h);
-    p.front = cut(img, ox + d, oy + d, w, h);
-    p.right = cut(img, ox + d + w, oy + d, d, h);
-    p.back = cut(img, ox + 2 * d + w, oy + d, w, h);
+    p.top = face(4);
+    p.bottom = face(5);
+    p.left = face(2);
+    p.front = face(1);
+    p.right = face(3);
+    p.back = face(0);
     return p;
 }
 
@@ -245,25 +275,44 @@ int mcrt_build_skin_scene(const uint8_t* rgba8, int w, int h, const float pose[1
     img.px.resize(static_cast<size_t>(w) * h * 4);
     for (size_t i = 0; i < img.px.size(); ++i) img.px[i] = rgba8[i] / 255.0f;
     Skin s;
-    // part origins: head, body, right arm, left arm, right leg, left leg
-    s.inner[0] = unwrap(img, 0, 0, 8, 8, 8);
-    s.outer[0] = unwrap(img, 32, 0, 8, 8, 8);
-    s.inner[1] = unwrap(img, 16, 16, 8, 12, 4);
-    s.inner[2] = unwrap(img, 40, 16, 4, 12, 4);
-    s.inner[4] = unwrap(img, 0, 16, 4, 12, 4);
+    s.inner[0] = unwrap(img, kInnerBox[0]);
+    s.outer[0] = unwrap(img, kOuterBox[0]);
+    s.inner[1] = unwrap(img, kInnerBox[1]);
+    s.inner[2] = unwrap(img, kInnerBox[2]);
+    s.inner[4] = unwrap(img, kInnerBox[4]);
     if (h == 64) {
-        s.outer[1] = unwrap(img, 16, 32, 8, 12, 4);
-        s.outer[2] = unwrap(img, 40, 32, 4, 12, 4);
-        s.inner[3] = unwrap(img, 32, 48, 4, 12, 4);
-        s.outer[3] = unwrap(img, 48, 48, 4, 12, 4);
-        s.outer[4] = unwrap(img, 0, 32, 4, 12, 4);
-        s.inner[5] = unwrap(img, 16, 48, 4, 12, 4);
-        s.outer[5] = unwrap(img, 0, 48, 4, 12, 4);
+        s.inner[3] = unwrap(img, kInnerBox[3]);
+        s.inner[5] = unwrap(img, kInnerBox[5]);
+        for (int p = 1; p < 6; ++p) s.outer[p] = unwrap(img, kOuterBox[p]);
     } else {
-        s.inner[3] = mirror_part(s.inner[2]);
-        s.inner[5] = mirror_part(s.inner[4]);
+        s.inner[3] = mirror_part(s.inner[kLegacyMirrorOf[3]]);
+        s.inner[5] = mirror_part(s.inner[kLegacyMirrorOf[5]]);
     }
     *out = &assemble(s, pose)->desc;
+    return MCRT_OK;
+}
+
+int mcrt_skin_texel(int skin_height, int mesh, int face_slot, int tx, int ty, int* skin_x, int* skin_y) {
+    if (!skin_x || !skin_y) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
+    if (skin_height != 64 && skin_height != 32) return mcrt_detail_fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    if (face_slot < 0 || face_slot > 5) return mcrt_detail_fail(MCRT_ERR_INVALID, "face_slot must be 0..5");
+    // assemble(): per part the inner box, then its outer box where the skin kind has one
+    int part, outer;
+    if (skin_height == 64) {
+        if (mesh < 0 || mesh >= 12) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..11 for a 64x64 skin");
+        part = mesh / 2, outer = mesh & 1;
+    } else {
+        if (mesh < 0 || mesh >= 7) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..6 for a 64x32 skin");
+        part = mesh < 2 ? 0 : mesh - 1, outer = mesh == 1 ? 1 : 0;
+    }
+    const int mirror_of = (skin_height == 32 && !outer) ? kLegacyMirrorOf[part] : -1;
+    const PartBox& box = outer ? kOuterBox[part] : kInnerBox[mirror_of >= 0 ? mirror_of : part];
+    int face = face_slot;
+    if (mirror_of >= 0 && (face == 2 || face == 3)) face = 5 - face;  // mirror_part: left = flip_h(right), right = flip_h(left)
+    const Rect r = face_rect(box, face);
+    if (tx < 0 || tx >= r.w || ty < 0 || ty >= r.h) return mcrt_detail_fail(MCRT_ERR_INVALID, "texel outside the face's region");
+    *skin_x = r.x + (mirror_of >= 0 ? r.w - 1 - tx : tx);  // flip_h
+    *skin_y = r.y + ty;
     return MCRT_OK;
 }
 
