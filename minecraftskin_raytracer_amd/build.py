@@ -17,8 +17,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(PKG, "libmcrt.so")
-SOURCES = ["render_kernels.hip", "api.cpp", "flatten.cpp", "scene_builder.cpp", "png_writer.cpp"]
-HEADERS = ["flat_scene.h", "flatten.h", "kernels.h", "rt_core.h"]
+SOURCES = ["render_kernels.hip", "api.cpp", "render_enqueue.cpp", "device_stores.cpp", "probes.cpp", "flatten.cpp", "scene_builder.cpp", "png_writer.cpp"]
+HEADERS = ["flat_scene.h", "flatten.h", "host_internal.h", "kernels.h", "rt_core.h"]
 ARCH = "gfx950"
 
 

@@ -1,0 +1,501 @@
+// device_stores.cpp — what libmcrt.so keeps per device or per process: the devices' memory sizes, the live list of scene
+// shells, the seed tables, the background plates, the pool of idle shells and the ring of parameter tables.  Each store
+// has a mutex of its own, and no function here holds one while it takes another.
+#include "host_internal.h"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <mutex>
+
+using namespace mcrt;
+
+namespace mcrt_host {
+
+// total memory of a device, asked once per device and process (hipMemGetInfo costs ~10 ms per call on this runtime: asked per
+// scene it made every one-shot render 12 ms longer)
+size_t device_total_memory(int device) {
+    static std::mutex mu;
+    static std::vector<size_t> totals;
+    std::lock_guard<std::mutex> lock(mu);
+    if (device < 0) return 0;
+    if (totals.size() <= static_cast<size_t>(device)) totals.resize(static_cast<size_t>(device) + 1, 0);
+    size_t& t = totals[static_cast<size_t>(device)];
+    if (t == 0) {
+        size_t total_b = 0;
+        if (hipDeviceTotalMem(&total_b, device) != hipSuccess) {
+            (void)hipGetLastError();
+            total_b = static_cast<size_t>(24) << 30;
+        }
+        t = total_b ? total_b : 1;
+    }
+    return t;
+}
+
+// Every shell of the process (pooled ones included).  A render sizes its launches by whether its device is busy with
+// another handle's frame at the moment it is enqueued (choose_grids): it asks the other shells' last-render events.
+namespace {
+std::mutex g_live_mutex;
+std::vector<mcrt_scene*> g_live;
+void unregister_live(mcrt_scene* s) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    g_live.erase(std::remove(g_live.begin(), g_live.end(), s), g_live.end());
+}
+}  // namespace
+void register_live(mcrt_scene* s) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    g_live.push_back(s);
+}
+bool device_shared(const mcrt_scene* s) {
+    static const int forced = [] {  // development knob: MCRT_SHARED_GRIDS=0 / 1 fixes the answer
+        const int v = env_int("MCRT_SHARED_GRIDS", INT_MIN);
+        return v == INT_MIN ? -1 : (v != 0 ? 1 : 0);
+    }();
+    if (forced >= 0) return forced != 0;
+    bool shared = false;
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        for (const mcrt_scene* q : g_live) {
+            if (q == s || q->device != s->device) continue;
+            hipEvent_t e = q->busy_probe.load(std::memory_order_acquire);
+            if (e && hipEventQuery(e) == hipErrorNotReady) {
+                shared = true;
+                break;
+            }
+        }
+    }
+    (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure of this render
+    return shared;
+}
+
+// ---- per-device seed tables (kernels.h): mt[397] of mt19937's seeding recurrence by seed, so that the kernels look up what
+// they would otherwise run 397 steps for.  Two tables of one shape — by device, built on first use (synchronously, on the
+// null stream), a `users` count of the scene shells, live or pooled, that hold the pointer, freed by mcrt_trim() when
+// nobody does — that differ in what is below.  No table (the knob, no room, a failed build): the kernels seed by the recurrence.
+namespace {
+struct SeedTables {
+    const char* knob;                 // environment variable: 0 turns the table off
+    size_t bytes;
+    bool small_part_only;             // built only where it is a small part of what is free (a third at most)
+    hipError_t (*fill)(uint32_t* p);  // the launches that fill it
+    struct Table {
+        uint32_t* ptr = nullptr;
+        int users = 0;
+    };
+    std::vector<Table> by_device;     // (g_seed_mutex)
+    int enabled = -1;                 // the knob, read at the first acquire
+
+    const uint32_t* acquire(int device);
+    void release(int device);
+    void free_unused();
+};
+std::mutex g_seed_mutex;
+
+const uint32_t* SeedTables::acquire(int device) {
+    std::lock_guard<std::mutex> lock(g_seed_mutex);
+    if (enabled < 0) enabled = env_int(knob, 1) != 0 ? 1 : 0;
+    if (!enabled) return nullptr;
+    if (by_device.size() <= static_cast<size_t>(device)) by_device.resize(static_cast<size_t>(device) + 1);
+    Table& t = by_device[static_cast<size_t>(device)];
+    if (!t.ptr) {
+        size_t free_b = 0, total_b = 0;
+        uint32_t* p = nullptr;
+        const bool room = !small_part_only || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= bytes * 3);
+        if (!room || hipMalloc(&p, bytes) != hipSuccess || fill(p) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipGetLastError();
+            if (p) (void)hipFree(p);
+            return nullptr;
+        }
+        t.ptr = p;
+    }
+    ++t.users;
+    return t.ptr;
+}
+void SeedTables::release(int device) {
+    std::lock_guard<std::mutex> lock(g_seed_mutex);
+    if (static_cast<size_t>(device) < by_device.size() && by_device[static_cast<size_t>(device)].users > 0) --by_device[static_cast<size_t>(device)].users;
+}
+void SeedTables::free_unused() {  // mcrt_trim
+    std::lock_guard<std::mutex> lock(g_seed_mutex);
+    for (size_t d = 0; d < by_device.size(); ++d) {
+        Table& t = by_device[d];
+        if (t.ptr && t.users == 0) {
+            (void)hipSetDevice(static_cast<int>(d));
+            (void)hipFree(t.ptr);
+            t.ptr = nullptr;
+        }
+    }
+}
+
+// The window table: kSeedWindow words, the seeds of a frame's tiles and hits; one ~2 ms kernel.  MCRT_SEED_TABLE=0 turns it off.
+SeedTables g_window_tables{"MCRT_SEED_TABLE", static_cast<size_t>(kSeedWindow) * 4, false, [](uint32_t* p) { return launch_build_seed_table(p, nullptr); }};
+// The table for EVERY seed: mt[397] of all 2^32 seeds, 16 GiB of the device's HBM.  The ambient-occlusion seeds,
+// (unsigned)(P.x * 73856093 + P.y * 19349663 + P.z * 83492791) (raytracer.cpp:122-123), cover the whole 32-bit range, and the
+// 397-step recurrence is over a quarter of the AO stage's cycles (its multiply issues at a quarter of the rate).  Built on
+// a device's first AO render (0.2 s), when the device has the room; MCRT_AO_SEED_TABLE=0 turns it off.
+SeedTables g_full_tables{"MCRT_AO_SEED_TABLE", static_cast<size_t>(1) << 34, true, [](uint32_t* p) {
+                             hipError_t e = hipSuccess;
+                             for (uint32_t part = 0; part < 16u && e == hipSuccess; ++part) e = launch_build_seed_table_range(p, part << 28, 1u << 28, nullptr);
+                             return e;
+                         }};
+}  // namespace
+
+const uint32_t* acquire_seed_table(int device) { return g_window_tables.acquire(device); }
+void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream) {
+    if (s->full_table_tried) return;
+    if (stream_capturing(stream)) return;  // (building it launches and waits)
+    s->full_table_tried = true;
+    s->seed_table_full = g_full_tables.acquire(s->device);
+    s->holds_full_table = s->seed_table_full != nullptr;
+}
+
+namespace {
+// ---- per-device background plates (kernels.h; mcrt.h states the memory cost and the knobs) -------------------------
+// A store per device, under one mutex, entries with a `users` count like the seed tables.  An entry starts as a sighting
+// record (no memory); the plate is built at the key's second render call on the device — one-shot calls and sweeps over
+// thousands of sizes never allocate — synchronously, on the store's own non-blocking stream, never on the null stream and
+// never while the caller records a graph.  Once built a plate is immutable: no validity flags, nothing published or
+// tested on the device, no writer beside a reader.  Plates nobody holds make way, least recently used first, when a
+// new one needs the room; one that does not fit gets no plate and the frame renders as it always did.
+constexpr size_t kBgPlateBudget = static_cast<size_t>(MCRT_BG_PLATE_BUDGET_MB) << 20;  // built plates of a device, together
+constexpr int kBgPlateBuilt = 8;     // built plates per device
+constexpr int kBgPlateKeys = 32;     // entries per device, sighting records included
+constexpr int kBgPlateRetryAfter = 16;  // sightings a key waits after a failed build before the next try
+constexpr size_t kHeldPlates = 4;    // plates one scene shell holds at a time (as many as it records launch graphs)
+struct DevicePlates {
+    std::vector<BgPlate*> entries;
+    unsigned long long clock = 0;
+    hipStream_t stream = nullptr;  // the builds
+    size_t bytes = 0;              // of the built plates
+    int built = 0;
+    int builds = 0;                // plates built so far (mcrt_bg_plate_info)
+};
+std::mutex g_plate_mutex;
+std::vector<DevicePlates> g_plates;  // by device
+
+int bg_plate_mode() {  // development knob MCRT_BG_PLATE: 0 no plates, 2 build at a key's first render (tests); else at the second
+    static const int mode = [] {
+        const int v = env_int("MCRT_BG_PLATE", 1);
+        return v == 0 ? 0 : (v == 2 ? 2 : 1);
+    }();
+    return mode;
+}
+BgPlateKey bg_plate_key_of(const RenderParams& p) {
+    BgPlateKey k;
+    std::memset(&k, 0, sizeof k);
+    k.width = p.cfg.width, k.height = p.cfg.height, k.tile_size = p.cfg.tile_size;
+    k.spp = p.cfg.samples_per_pixel > 1 ? p.cfg.samples_per_pixel : 1;
+    k.draws_per_sample = p.draws_per_sample;
+    k.gradient_bg = p.cfg.gradient_bg ? 1 : 0;
+    k.div_frame = p.div_frame;
+    k.gradient_scale = p.cfg.gradient_scale;
+    for (int i = 0; i < 3; ++i) k.bg_center[i] = p.cfg.bg_center[i], k.bg_edge[i] = p.cfg.bg_edge[i];
+    return k;
+}
+bool same_key(const BgPlateKey& a, const BgPlateKey& b) { return std::memcmp(&a, &b, sizeof a) == 0; }  // (floats by their bits)
+
+// g_plate_mutex held.  Frees a built plate nobody holds: every holder synchronised the device before it let go.
+void free_plate(DevicePlates& d, BgPlate* e) {
+    if (!e->ptr) return;
+    (void)hipFree(e->ptr);
+    e->ptr = nullptr;
+    d.bytes -= e->bytes;
+    e->bytes = 0;
+    --d.built;
+}
+// g_plate_mutex held, the device current.  Builds e's plate for the frame prepared as `p`; leaves e->ptr NULL when there is no room
+// (asked again at the key's next render) or the build fails (an allocation refused, for one: asked again kBgPlateRetryAfter sightings later).
+void build_plate(DevicePlates& d, BgPlate* e, const RenderParams& p, size_t bytes) {
+    while (d.built >= kBgPlateBuilt || d.bytes + bytes > kBgPlateBudget) {
+        BgPlate* victim = nullptr;
+        for (BgPlate* q : d.entries)
+            if (q != e && q->ptr && q->users == 0 && (!victim || q->last_use < victim->last_use)) victim = q;
+        if (!victim) return;
+        free_plate(d, victim);
+        victim->sightings = 0;
+    }
+    float4* plate = nullptr;
+    uint32_t* rng = nullptr;
+    hipError_t err = d.stream ? hipSuccess : hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipMalloc(&plate, bytes);
+    if (err == hipSuccess) err = hipMalloc(&rng, bg_plate_rng_bytes(p));
+    if (err == hipSuccess) err = launch_fill_bg_plate(p, plate, rng, d.stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(d.stream);
+    if (rng) (void)hipFree(rng);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        if (plate) (void)hipFree(plate);
+        e->sightings = -kBgPlateRetryAfter;
+        return;
+    }
+    e->ptr = plate;
+    e->bytes = bytes;
+    d.bytes += bytes;
+    ++d.built;
+    ++d.builds;
+}
+// The shell lets go of the plate it has held longest.  Its launches in flight and its recorded launch graphs may read the
+// plate: its last render is waited for — every render of a handle ends in `last_done`, lanes joined, and a handle's renders
+// run one after the other, so nothing of this handle reads the plate after it; other handles' frames are not waited
+// for — and those graphs are dropped first.
+void drop_held_plate(mcrt_scene* s) {
+    BgPlate* e = s->plates.front();
+    if (s->have_last && s->last_done) (void)hipEventSynchronize(s->last_done);
+    for (auto& r : s->recorded) {
+        bool reads = false;
+        for (int li = 0; li < kMaxLanes; ++li) reads = reads || (r.p[li].bg_plate != nullptr && r.p[li].bg_plate == e->ptr);
+        if (!reads) continue;
+        if (r.exec) (void)hipGraphExecDestroy(r.exec);
+        if (r.graph) (void)hipGraphDestroy(r.graph);
+        r.exec = nullptr;
+        r.graph = nullptr;
+        r.n_lanes = 0;
+        r.sightings = 0;
+    }
+    s->plates.erase(s->plates.begin());
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    --e->users;
+}
+void release_bg_plates(mcrt_scene* s) {  // the shell goes (its device work has been waited for)
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    for (BgPlate* e : s->plates) --e->users;
+    s->plates.clear();
+}
+
+void free_unused_bg_plates() {  // mcrt_trim
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    for (size_t dev = 0; dev < g_plates.size(); ++dev) {
+        DevicePlates& d = g_plates[dev];
+        (void)hipSetDevice(static_cast<int>(dev));
+        std::vector<BgPlate*> kept;
+        for (BgPlate* e : d.entries) {
+            if (e->users > 0) {
+                kept.push_back(e);
+                continue;
+            }
+            free_plate(d, e);
+            delete e;
+        }
+        d.entries.swap(kept);
+        if (d.stream) (void)hipStreamDestroy(d.stream);  // idle: every build waited for it under this mutex
+        d.stream = nullptr;
+    }
+}
+}  // namespace
+
+const float4* acquire_bg_plate(mcrt_scene* s, const RenderParams& p, bool capturing, bool count_sighting) {
+    const int mode = bg_plate_mode();
+    // (a caller's graph outlives this call in ways the library cannot see: a render recorded into it takes no plate)
+    if (mode == 0 || capturing || !bg_plate_eligible(p)) return nullptr;
+    const BgPlateKey key = bg_plate_key_of(p);
+    for (size_t i = 0; i < s->plates.size(); ++i)
+        if (same_key(s->plates[i]->key, key)) {  // held already: no lock, the entry cannot change under a holder
+            BgPlate* e = s->plates[i];
+            s->plates.erase(s->plates.begin() + static_cast<long>(i));
+            s->plates.push_back(e);
+            return e->ptr;
+        }
+    const size_t bytes = bg_plate_bytes(p.cfg);
+    if (bytes == 0 || bytes > kBgPlateBudget) return nullptr;
+    BgPlate* got = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_plate_mutex);
+        if (g_plates.size() <= static_cast<size_t>(s->device)) g_plates.resize(static_cast<size_t>(s->device) + 1);
+        DevicePlates& d = g_plates[static_cast<size_t>(s->device)];
+        ++d.clock;
+        BgPlate* e = nullptr;
+        for (BgPlate* q : d.entries)
+            if (same_key(q->key, key)) e = q;
+        if (!e) {
+            if (d.entries.size() >= static_cast<size_t>(kBgPlateKeys)) {  // the least recently used entry nobody holds becomes this key's
+                for (BgPlate* q : d.entries)
+                    if (q->users == 0 && (!e || q->last_use < e->last_use)) e = q;
+                if (!e) return nullptr;
+                free_plate(d, e);
+                *e = BgPlate{};
+            } else {
+                e = new BgPlate();
+                d.entries.push_back(e);
+            }
+            e->key = key;
+        }
+        e->last_use = d.clock;
+        if (!e->ptr) {
+            if (count_sighting) ++e->sightings;
+            if (e->sightings >= (mode == 2 ? 1 : 2)) build_plate(d, e, p, bytes);
+        }
+        if (e->ptr) {
+            ++e->users;
+            got = e;
+        }
+    }
+    if (!got) return nullptr;
+    if (s->plates.size() >= kHeldPlates) drop_held_plate(s);
+    s->plates.push_back(got);
+    return got->ptr;
+}
+
+// keeps `s` for reuse unless it is large — MCRT_POOL_MB, by default a twelfth of the device's memory (24 GB of the
+// MI355X's 288: the 1080p and 4K frames of BASELINE.json stay pooled, and a host application that never calls
+// mcrt_trim() does not sit on a fifth of the card; the one-shot entry points plan their workspace to stay below it, see
+// render_to_host) — or the device already has one
+size_t pool_limit(int device) {
+    static const long long forced_mb = env_ll("MCRT_POOL_MB", -1ll);
+    return forced_mb >= 0 ? static_cast<size_t>(forced_mb) << 20 : device_total_memory(device) / 12;
+}
+namespace {
+size_t workspace_bytes(const mcrt_scene* s) {
+    size_t n = s->blob.bytes + s->frame.bytes;
+    for (const Lane& ln : s->lanes) for_each_buffer(ln, [&](const DeviceBuffer& b) { n += b.bytes; });
+    return n;
+}
+
+std::mutex g_pool_mutex;
+std::vector<mcrt_scene*> g_pool;  // idle scene shells, at most one per device
+}  // namespace
+
+bool pool_scene(mcrt_scene* s) {
+    const size_t limit = pool_limit(s->device);
+    if (workspace_bytes(s) > limit) return false;
+    std::lock_guard<std::mutex> lock(g_pool_mutex);
+    for (mcrt_scene* q : g_pool)
+        if (q->device == s->device) return false;
+    g_pool.push_back(s);
+    return true;
+}
+// device < 0: any
+mcrt_scene* take_pooled_scene(int device) {
+    std::lock_guard<std::mutex> lock(g_pool_mutex);
+    for (size_t i = 0; i < g_pool.size(); ++i)
+        if (device < 0 || g_pool[i]->device == device) {
+            mcrt_scene* s = g_pool[i];
+            g_pool.erase(g_pool.begin() + static_cast<long>(i));
+            return s;
+        }
+    return nullptr;
+}
+
+void destroy_scene_now(mcrt_scene* s) {
+    if (!s) return;
+    unregister_live(s);  // before its events go
+    if (s->holds_seed_table) g_window_tables.release(s->device);
+    if (s->holds_full_table) g_full_tables.release(s->device);
+    release_bg_plates(s);
+    s->blob.release();  // the other buffers are released by their destructors below
+    for (auto& ln : s->lanes) {
+        if (ln.stream) (void)hipStreamSynchronize(ln.stream);
+        if (ln.done) (void)hipEventDestroy(ln.done);
+        if (ln.stream) (void)hipStreamDestroy(ln.stream);
+    }
+    for (auto& r : s->recorded) {
+        if (r.exec) (void)hipGraphExecDestroy(r.exec);
+        if (r.graph) (void)hipGraphDestroy(r.graph);
+    }
+    if (s->capture_stream) (void)hipStreamDestroy(s->capture_stream);
+    if (s->fork) (void)hipEventDestroy(s->fork);
+    if (s->last_done) (void)hipEventDestroy(s->last_done);
+    if (s->staging) (void)hipHostFree(s->staging);
+    if (s->main_stream) (void)hipStreamDestroy(s->main_stream);
+    if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
+    for (hipEvent_t m : s->marks) (void)hipEventDestroy(m);
+    for (auto& e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+// The parameter tables of the batched launches, per device: a ring of slots, each a device buffer, its pinned host
+// staging and an event recorded behind the launches that read it.  A slot is refilled only after that event: a table
+// is never overwritten while an earlier batch — on any stream — may still read it.
+struct TableSlot {
+    DeviceBuffer dev;
+    void* host = nullptr;
+    size_t host_bytes = 0;
+    hipEvent_t done = nullptr;
+    bool used = false;  // `done` has been recorded
+    bool busy = false;  // being filled by a thread
+};
+namespace {
+constexpr int kTableSlots = 8;
+struct DeviceTables {
+    TableSlot slot[kTableSlots];
+    int next = 0;
+};
+std::mutex g_table_mutex;
+std::vector<DeviceTables*> g_tables;  // by device; a few hundred KB each, kept for the process
+
+TableSlot* acquire_table_slot(int device) {
+    std::lock_guard<std::mutex> lock(g_table_mutex);
+    if (g_tables.size() <= static_cast<size_t>(device)) g_tables.resize(static_cast<size_t>(device) + 1, nullptr);
+    if (!g_tables[static_cast<size_t>(device)]) g_tables[static_cast<size_t>(device)] = new DeviceTables();
+    DeviceTables& t = *g_tables[static_cast<size_t>(device)];
+    for (int k = 0; k < kTableSlots; ++k) {
+        const int i = (t.next + k) % kTableSlots;
+        if (t.slot[i].busy) continue;
+        t.slot[i].busy = true;
+        t.next = (i + 1) % kTableSlots;
+        return &t.slot[i];
+    }
+    return nullptr;
+}
+void release_table_slot(TableSlot* s) {
+    std::lock_guard<std::mutex> lock(g_table_mutex);
+    s->busy = false;
+}
+}  // namespace
+
+int upload_table(int device, const void* rows, size_t bytes, hipStream_t stream, TableUpload& up) {
+    TableSlot* slot = acquire_table_slot(device);
+    if (!slot) return fail(MCRT_ERR_HIP, "too many batch calls filling parameter tables at once");
+    up.slot = slot;
+    if (slot->used) HIP_TRY(hipEventSynchronize(slot->done));  // the last launches that read this slot have finished
+    if (!slot->done) HIP_TRY(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    if (slot->host_bytes < bytes) {
+        if (slot->host) (void)hipHostFree(slot->host);
+        slot->host = nullptr;
+        slot->host_bytes = 0;
+        HIP_TRY(hipHostMalloc(&slot->host, bytes, hipHostMallocDefault));
+        slot->host_bytes = bytes;
+    }
+    HIP_TRY(slot->dev.reserve(bytes));
+    std::memcpy(slot->host, rows, bytes);
+    up.dev = slot->dev.ptr;
+    up.status = hipMemcpyAsync(slot->dev.ptr, slot->host, bytes, hipMemcpyHostToDevice, stream);
+    return MCRT_OK;
+}
+hipError_t TableUpload::commit(hipStream_t stream) {
+    const hipError_t e = hipEventRecord(slot->done, stream);
+    if (e == hipSuccess) slot->used = true;
+    return e;
+}
+TableUpload::~TableUpload() {
+    if (slot) release_table_slot(slot);
+}
+
+}  // namespace mcrt_host
+
+using namespace mcrt_host;
+
+extern "C" {
+
+void mcrt_trim(void) {
+    for (;;) {
+        mcrt_scene* s = take_pooled_scene(-1);
+        if (!s) break;
+        (void)hipSetDevice(s->device);
+        destroy_scene_now(s);
+    }
+    g_full_tables.free_unused();
+    g_window_tables.free_unused();
+    free_unused_bg_plates();
+}
+
+int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds) {
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    const DevicePlates* d = (device >= 0 && static_cast<size_t>(device) < g_plates.size()) ? &g_plates[static_cast<size_t>(device)] : nullptr;
+    if (plates) *plates = d ? d->built : 0;
+    if (bytes) *bytes = d ? d->bytes : 0;
+    if (builds) *builds = d ? d->builds : 0;
+    return MCRT_OK;
+}
+
+}  // extern "C"

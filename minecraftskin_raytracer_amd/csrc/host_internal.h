@@ -1,0 +1,234 @@
+// host_internal.h — what the host translation units of libmcrt.so share: api.cpp (the C ABI's scene and host-buffer
+// entry points), render_enqueue.cpp (a render's launches), device_stores.cpp (what is kept per device or process) and
+// probes.cpp.  Not installed; every declaration is hidden, so the library's dynamic symbol table holds none of it.
+#pragma once
+#include "flatten.h"
+#include "kernels.h"
+#include "mcrt.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+
+namespace mcrt_host {
+// set the calling thread's mcrt_last_error() text and return the code (api.cpp, next to the text itself)
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* what);
+}  // namespace mcrt_host
+#define HIP_TRY(call)                                               \
+    do {                                                            \
+        hipError_t e_ = (call);                                     \
+        if (e_ != hipSuccess) return mcrt_host::hip_fail(e_, #call); \
+    } while (0)
+
+struct DeviceBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    hipError_t reserve(size_t need) {
+        if (need <= bytes) return hipSuccess;
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+        hipError_t e = hipMalloc(&ptr, need);
+        if (e == hipSuccess) bytes = need;
+        return e;
+    }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { release(); }
+};
+
+// A lane renders every n-th tile row of a shard with its own workspace on its own stream.  The
+// pipeline of one lane is a chain of dependent kernels whose tails and sparse deeper levels leave
+// most of the chip idle; two or three lanes in flight fill those gaps (measured: 1080p 0.53 -> 0.43
+// ms, 4K/8 bounces/16 spp 9.6 -> 5.3 ms with three lanes).  Lane 0 runs on the caller's stream,
+// the others fork from it and join it through events, so the caller sees ordinary stream order.
+constexpr int kMaxLanes = 4;
+// what the seeded per-tile mt19937 states in Lane::tile_rng are a function of (tile_renderer.cpp:78: the
+// seed is tile.y * width + tile.x) — scene and every other setting do not enter
+struct RngKey {
+    const void* ptr = nullptr;
+    int width = 0, tile_size = 0, first = 0, step = 0, tiles_x = 0, owned_rows = 0;
+    int rect[4] = {0, 0, 0, 0};
+    int parts = 0, part_twists = 0;  // the engine states at the starts of the streams' parts depend on these too
+    bool operator==(const RngKey& o) const {
+        return parts == o.parts && part_twists == o.part_twists && ptr == o.ptr && width == o.width && tile_size == o.tile_size && first == o.first && step == o.step && tiles_x == o.tiles_x &&
+               owned_rows == o.owned_rows && rect[0] == o.rect[0] && rect[1] == o.rect[1] && rect[2] == o.rect[2] && rect[3] == o.rect[3];
+    }
+};
+struct Lane {
+    hipStream_t stream = nullptr;  // owned; unused for lane 0
+    hipEvent_t done = nullptr;
+    // wavefront workspace, grown on demand (never shrinks; no allocation in the steady state)
+    DeviceBuffer tile_rng, tile_draws, scol, end, units, unit_hits, tile_mask, queues[5], texel_refs, targets, cand, lit[2], stack, counters, hit_rng;
+    RngKey rng_key;               // which tile seeds tile_rng holds (ptr == nullptr: none)
+    bool counters_dirty = false;  // a render's launches failed half way: counters and their base no longer fit (cleared before the next render)
+};
+template <class LaneT, class F>
+void for_each_buffer(LaneT& ln, F f) {  // every workspace buffer of a lane
+    for (auto* b : {&ln.tile_rng, &ln.tile_draws, &ln.scol, &ln.end, &ln.units, &ln.unit_hits, &ln.tile_mask, &ln.texel_refs, &ln.targets, &ln.cand,
+                    &ln.lit[0], &ln.lit[1], &ln.stack, &ln.counters, &ln.hit_rng}) f(*b);
+    for (auto& q : ln.queues) f(q);
+}
+
+// One background plate of a device (kernels.h) and the frame settings its pixels are a function of — nothing else enters
+// (RngKey above says the same of the tile seeds).  Entries live in the per-device store further down.
+struct BgPlateKey {
+    int width, height, tile_size, spp, draws_per_sample, gradient_bg, div_frame;
+    float gradient_scale, bg_center[3], bg_edge[3];
+};
+struct BgPlate {
+    BgPlateKey key;
+    float4* ptr = nullptr;  // NULL: the key has been sighted, no plate built (yet)
+    size_t bytes = 0;
+    int users = 0;          // scene shells (live or pooled) that hold the pointer — in prepared parameters, recorded launch graphs, launches in flight
+    int sightings = 0;      // render calls with this key while it had no plate (negative after a failed build: see build_plate)
+    unsigned long long last_use = 0;
+};
+
+struct mcrt_scene {
+    int device = 0;
+    uint32_t alpha_words = 0;
+    uint32_t n_meshes = 0;
+    bool posed = false;  // any mesh with MESH_ROTATED
+    std::vector<uint8_t> host_meshes;  // host copy of FlatHeader + FlatMesh[] (screen bounds for workspace planning)
+    DeviceBuffer blob;
+    Lane lanes[kMaxLanes];
+    int forced_lanes = 0;  // mcrt_scene_set_lanes: 0 = automatic
+    int background = MCRT_BACKGROUND_REFERENCE;  // mcrt_scene_set_background
+    size_t budget = 0;     // current workspace budget (0 = workspace_budget()); halved when the device is short of memory
+    // recorded launch sequences of recent renders (hipGraph), replayed when the parameters repeat
+    struct Recorded {
+        int n_lanes = 0;
+        mcrt::RenderParams p[kMaxLanes];
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        unsigned long long last_use = 0;
+        int sightings = 0;
+    };
+    static constexpr int kRecorded = 4;
+    Recorded recorded[kRecorded];
+    unsigned long long use_clock = 0;
+    hipStream_t capture_stream = nullptr;
+    hipEvent_t fork = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // One handle = one frame in flight: all renders of a handle share its workspace.  `last_done` is recorded
+    // at the end of every render; a render enqueued on a different stream than the previous one waits for it.
+    hipEvent_t last_done = nullptr;
+    std::atomic<hipEvent_t> busy_probe{nullptr};  // = last_done once it exists: what OTHER handles' renders query (device_shared)
+    hipStream_t last_stream = nullptr;
+    bool have_last = false;
+    bool flags_checked = true;  // no render since mcrt_scene_check last read (and cleared) the lanes' overflow words
+    // the one-shot host path (mcrt_render & co): frame buffer, streams and events kept with the pooled workspace
+    DeviceBuffer frame;                // float4 frame / packed rows / RGBA8 plane of a host-buffer render
+    DeviceBuffer pick;                 // mcrt_scene_pick: the pixels' coordinates, then their records (grown on demand)
+    hipStream_t main_stream = nullptr;  // the render
+    hipStream_t copy_stream = nullptr;  // downloads of finished tile rows, overlapping the render
+    std::vector<hipEvent_t> marks;      // event pool of the row-group downloads
+    size_t marks_used = 0;
+    // pinned host staging for the small transfers of every call (the scene blob up, the lanes' flag words
+    // back): no pin / unpin of a few KB of pageable memory per call
+    void* staging = nullptr;
+    size_t staging_bytes = 0;
+    const uint32_t* seed_table = nullptr;  // the device's table of mt19937 seeding results (kernels.h), or NULL
+    bool holds_seed_table = false;
+    const uint32_t* seed_table_full = nullptr;  // the device's table for every 32-bit seed (ambient occlusion), or NULL
+    bool holds_full_table = false, full_table_tried = false;
+    // background plates this shell holds a `users` count of, least recently used first: its recorded launch graphs and its
+    // launches in flight may read them, so one is let go of only behind a device synchronisation (acquire_bg_plate)
+    std::vector<BgPlate*> plates;
+};
+
+namespace mcrt_host {
+
+// Environment knobs.  A knob is read once per process, into a function-local static where it is used — except
+// MCRT_WORKSPACE_MB, which workspace_budget() reads at every call.
+inline int env_int(const char* name, int fallback) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : fallback;
+}
+inline long long env_ll(const char* name, long long fallback) {
+    const char* e = std::getenv(name);
+    return e ? std::atoll(e) : fallback;
+}
+inline bool env_off(const char* name) {  // the kernel paths' development knobs: off when the value begins with '0'
+    const char* e = std::getenv(name);
+    return e && e[0] == '0';
+}
+
+inline bool stream_capturing(hipStream_t stream) {  // the caller records a graph of its own on `stream`
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+}
+inline bool valid_frame(const mcrt_config* c) { return c->width > 0 && c->height > 0 && c->tile_size > 0; }
+inline bool valid_background(int b) { return b == MCRT_BACKGROUND_REFERENCE || b == MCRT_BACKGROUND_TRANSPARENT; }
+inline int bad_background() { return fail(MCRT_ERR_INVALID, "background must be MCRT_BACKGROUND_REFERENCE or MCRT_BACKGROUND_TRANSPARENT"); }
+inline bool no_plane(const mcrt_layers* l) { return !l->depth && !l->normal && !l->albedo && !l->id; }
+
+// what the calling thread's last mcrt_render_batch* call did (mcrt_last_batch_info; thread-local in api.cpp, like the error text)
+struct BatchInfo {
+    int frames = 0, sequences = 0;
+};
+BatchInfo& last_batch();
+
+// ---- device_stores.cpp: per device or per process, each store under a mutex of its own (none is held while another is taken)
+size_t device_total_memory(int device);
+// every shell of the process is on the live list from its creation to destroy_scene_now
+void register_live(mcrt_scene* s);
+bool device_shared(const mcrt_scene* s);  // another handle's frame is in flight on s's device right now
+// the device's table of mt19937 seeding results for the seeds of a frame's tiles and hits, or nullptr; one `users` count per call
+const uint32_t* acquire_seed_table(int device);
+// the first ambient-occlusion render of a shell takes the device's table for every 32-bit seed (never built while `stream` is capturing)
+void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream);
+// the device's background plate for the frame prepared as `p`, or nullptr
+const float4* acquire_bg_plate(mcrt_scene* s, const mcrt::RenderParams& p, bool capturing, bool count_sighting);
+size_t pool_limit(int device);
+bool pool_scene(mcrt_scene* s);             // false: not kept, the caller destroys it
+mcrt_scene* take_pooled_scene(int device);  // device < 0: any
+void destroy_scene_now(mcrt_scene* s);
+// A parameter table of a batched launch set, in a slot of the device's ring.  upload_table() takes the slot, waits until
+// the launches that last read it have finished, and enqueues the rows' copy on `stream`; the caller launches what reads
+// `dev`, then commit()s.  The slot is given back when the guard goes, committed or not.
+struct TableSlot;
+struct TableUpload {
+    TableSlot* slot = nullptr;
+    const void* dev = nullptr;        // the rows on the device
+    hipError_t status = hipSuccess;   // of the rows' asynchronous copy: reported by the caller, with its launches
+    hipError_t commit(hipStream_t stream);  // behind the launches that read the table: records the slot's event
+    TableUpload() = default;
+    TableUpload(const TableUpload&) = delete;
+    TableUpload& operator=(const TableUpload&) = delete;
+    ~TableUpload();
+};
+int upload_table(int device, const void* rows, size_t bytes, hipStream_t stream, TableUpload& up);
+
+// ---- render_enqueue.cpp
+size_t workspace_budget(int device);
+int validate_config(const mcrt_config* cfg);
+// Tile rows that become final together, for a caller that downloads rows while the rest still renders.
+struct RowGroup {
+    std::vector<hipEvent_t> wait;  // recorded events after which the rows are complete in device memory
+    std::vector<int> rows;         // tile-row indices in the frame
+};
+hipEvent_t next_mark(mcrt_scene* s);  // an event of the shell's pool (nullptr: creation failed)
+// enqueue one render of the shard (first, step) on `stream`.  groups != nullptr (one-shot host path): the launches also record events
+// that tell when which tile rows are final, *groups lists them in completion order (direct launches: the events are this call's own).
+int enqueue_render(mcrt_scene* s, const mcrt_config* cfg, int first, int step, int layout, float* d_out, uint8_t* d_out8, hipStream_t stream,
+                   bool may_record = true, std::vector<RowGroup>* groups = nullptr, const mcrt_tile* rect = nullptr);
+int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream);
+int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream);
+
+}  // namespace mcrt_host
+
+#pragma GCC visibility pop

@@ -1,0 +1,735 @@
+// render_enqueue.cpp — from a scene handle and a config to launches on a stream: workspace planning, lanes, recorded
+// launch graphs, the one-frame, batched and layers device paths and their mcrt_*_device entry points.
+#include "host_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace mcrt;
+using namespace mcrt_host;
+
+namespace {
+
+int draws_per_sample(const mcrt_config& c) {
+    int spp = c.samples_per_pixel > 1 ? c.samples_per_pixel : 1;
+    return (spp > 1 ? 2 : 0) + ((c.dof_enabled && c.aperture > 1e-6f) ? 2 : 0);
+}
+
+// lanes for a shard: enough work per lane that the extra launches pay (MCRT_LANES forces a count)
+int lane_count(const mcrt_scene* s, const mcrt_config& cfg, const Shard& sh) {
+    static const int forced = env_int("MCRT_LANES", 0);
+    int lanes;
+    if (s->forced_lanes > 0) {
+        lanes = s->forced_lanes;
+    } else if (forced > 0) {
+        lanes = forced;
+    } else {
+        const int spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
+        const double samples = static_cast<double>(sh.owned_rows) * cfg.tile_size * cfg.width * spp;
+        // One lane up to 2.8e7 samples, three above.  With the launch shapes of a frame that is alone on ONE stream (four
+        // waves per tile stream, `lit` at 4 096 workgroups: choose_grids) a single lane beats two or three for every frame
+        // up to 2560x1440 / 6 spp (1080p / 4 spp alone: 0.189 / 0.224 / 0.215 ms with 1 / 2 / 3 lanes; 1440p / 6 spp: 0.416 /
+        // 0.439 / 0.423); 3840x2160 / 4 spp, 3.3e7 samples: 0.515 / 0.511 / 0.496, and the gap widens from there (GUI defaults,
+        // 1.3e8: 5.07 / 4.30 / 4.13).  Two lanes never came out first.
+        lanes = samples >= 2.8e7 ? 3 : 1;
+    }
+    lanes = std::min(lanes, kMaxLanes);
+    return std::max(1, std::min(lanes, sh.owned_rows));
+}
+
+// Upper bound, per owned tile row of `sh`, of the tiles that plan_tiles can find touched by a mesh.
+// It repeats the device's test (mesh_touches_tile + the thin-lens dilation) in double precision
+// with several pixels of extra margin, so it can only over-count; anything unusual → every tile.
+void touched_tiles_per_row(const mcrt_scene* sc, const mcrt_config& cfg, const Shard& sh, std::vector<int>& out) {
+    out.assign(static_cast<size_t>(sh.owned_rows > 0 ? sh.owned_rows : 0), sh.tiles_x);
+    if (sh.owned_rows <= 0 || sc->host_meshes.size() < sizeof(FlatHeader)) return;
+    const FlatHeader* h = reinterpret_cast<const FlatHeader*>(sc->host_meshes.data());
+    const FlatMesh* fm = reinterpret_cast<const FlatMesh*>(sc->host_meshes.data() + h->mesh_offset);
+    const int n = static_cast<int>(h->n_meshes);
+    if (n == 0) {
+        std::fill(out.begin(), out.end(), 0);
+        return;
+    }
+    if (!h->cull_ok || n >= 64) return;
+    const double W = cfg.width, H = cfg.height, T = cfg.tile_size;
+    const double aspect = static_cast<double>(static_cast<float>(cfg.width) / static_cast<float>(cfg.height));
+    const bool dof = cfg.dof_enabled && cfg.aperture > 1e-6f;
+    const double half_h = h->cam_half_h, half_w = half_h * aspect;
+    std::vector<uint8_t> grid(static_cast<size_t>(sh.tiles_x) * sh.tiles_y, 0);
+    for (int i = 0; i < n; ++i) {
+        const FlatMesh& m = fm[i];
+        double u0 = m.screen[0], v0 = m.screen[1], u1 = m.screen[2], v1 = m.screen[3];
+        if (!(u0 <= u1) || !std::isfinite(u0 + u1 + v0 + v1)) return;  // no bound: touches every tile
+        if (dof) {
+            const double focus = cfg.focus_distance > 0.0f ? cfg.focus_distance : h->cam_focus_auto;
+            if (!(m.depth[0] > 0.0f) || !(focus > 0.0)) return;
+            const double f_lo = 1.0 / focus, f_hi = std::sqrt(1.0 + half_w * half_w + half_h * half_h) / focus;
+            const double z_hi = 1.0 / m.depth[0], z_lo = 1.0 / m.depth[1];
+            const double d = std::max(std::max(std::fabs(z_hi - f_lo), std::fabs(z_hi - f_hi)),
+                                      std::max(std::fabs(z_lo - f_lo), std::fabs(z_lo - f_hi)));
+            const double pad = (cfg.aperture * d / half_h * 1.02 + 1e-3) * 1.01 + 1e-4;
+            if (!(pad < 1e6)) return;
+            u0 -= pad, v0 -= pad, u1 += pad, v1 += pad;
+        }
+        // bound units → pixels: u = (2x/W - 1) * aspect, v = 1 - 2y/H; the device pads tiles by 2 px + 1e-3 (u) / 2e-3 (v)
+        const double pad_x = 6.0 + (1e-3 * aspect + 1e-3) * W / (2.0 * aspect) + 1e-3 * W;
+        const double pad_y = 6.0 + 2e-3 * H / 2.0 + 1e-3 * H;
+        const double xa = (u0 / aspect + 1.0) * W * 0.5 - pad_x, xb = (u1 / aspect + 1.0) * W * 0.5 + pad_x;
+        const double ya = (1.0 - v1) * H * 0.5 - pad_y, yb = (1.0 - v0) * H * 0.5 + pad_y;
+        if (!std::isfinite(xa + xb + ya + yb)) return;
+        if (xb < 0.0 || yb < 0.0 || xa >= W || ya >= H) continue;
+        const int tx0 = static_cast<int>(std::max(0.0, std::floor(xa / T))), tx1 = static_cast<int>(std::min<double>(sh.tiles_x - 1, std::floor(xb / T)));
+        const int ty0 = static_cast<int>(std::max(0.0, std::floor(ya / T))), ty1 = static_cast<int>(std::min<double>(sh.tiles_y - 1, std::floor(yb / T)));
+        for (int ty = ty0; ty <= ty1; ++ty)
+            for (int tx = tx0; tx <= tx1; ++tx) grid[static_cast<size_t>(ty) * sh.tiles_x + tx] = 1;
+    }
+    for (int j = 0; j < sh.owned_rows; ++j) {
+        const int ty = sh.first + j * sh.step;
+        int c = 0;
+        for (int tx = 0; tx < sh.tiles_x; ++tx) c += grid[static_cast<size_t>(ty) * sh.tiles_x + tx];
+        out[static_cast<size_t>(j)] = c;
+    }
+}
+
+// fill RenderParams for lane `li` of `n_lanes` over the shard (first, step) + make sure its
+// workspace exists (allocation only when it has to grow)
+int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int first, int step, int layout, float* d_out,
+            uint8_t* d_out8, RenderParams& p, std::vector<int>* row_touched_out = nullptr, const mcrt_tile* rect = nullptr) {
+    Lane* s = &sc->lanes[li];
+    std::memset(&p, 0, sizeof p);
+    p.scene = static_cast<const uint8_t*>(sc->blob.ptr);
+    p.seed_table = sc->seed_table;
+    p.seed_table_full = sc->seed_table_full;
+    static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // development knob: =0 traces every hit's shadow rays
+    p.bundle_decisions = decisions ? 1 : 0;
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");  // development knob: =0 sends every candidate through the general routine
+    p.inside_fast = inside_fast ? 1 : 0;
+    p.cfg = *cfg;
+    if (cfg->width > 0 && cfg->height > 0) {
+        p.inv_width = 1.0f / static_cast<float>(cfg->width);
+        p.inv_height = 1.0f / static_cast<float>(cfg->height);
+        static const bool fast_div = !env_off("MCRT_DIV_FRAME");  // development knob: =0 takes the general division everywhere
+        p.div_frame = (fast_div && cfg->width <= kDivFrameMax && cfg->height <= kDivFrameMax) ? 1 : 0;
+    }
+    p.shard = make_shard(*cfg, first + li * step, step * n_lanes);
+    p.shard.pack_first = li;
+    p.shard.pack_step = n_lanes;
+    if (rect) {  // one tile: the rectangle (renderTile); the output holds its pixel rows, packed
+        p.rect_x = rect->x, p.rect_y = rect->y, p.rect_w = rect->width, p.rect_h = rect->height;
+        p.shard.first = 0, p.shard.step = 1, p.shard.tiles_x = 1, p.shard.tiles_y = 1, p.shard.owned_rows = 1;
+        p.shard.pack_first = 0, p.shard.pack_step = 1;
+    }
+    p.layout = layout;
+    p.out = d_out;
+    p.out8 = d_out8;
+    p.background = rect ? MCRT_BACKGROUND_REFERENCE : sc->background;  // (plan_workspace picks the draws layout by it)
+    p.draws_per_sample = draws_per_sample(*cfg);
+    const bool fits = sc->alpha_words <= static_cast<uint32_t>(kAlphaLdsWordsMax) && sc->n_meshes * 6 <= static_cast<uint32_t>(kFaceLdsEntriesMax);
+    p.scene_in_lds = fits ? 1 : 0;
+    p.scene_posed = sc->posed ? 1 : 0;
+    p.lds_alpha_words = fits ? static_cast<int>(sc->alpha_words) : 0;
+    p.lds_face_entries = fits ? static_cast<int>(sc->n_meshes * 6) : 0;
+    // The budget bounds the batch size; when the device cannot give that much right now (other
+    // allocations, a shared GPU) the budget is halved — down to one tile row per batch — and the
+    // lane's buffers are re-planned, instead of failing the render.
+    WorkspaceBytes w{};
+    std::vector<int> row_touched;
+    if (rect)
+        row_touched.assign(1, 1);  // the rectangle counts as touched (plan_tiles decides on the device)
+    else
+        touched_tiles_per_row(sc, *cfg, p.shard, row_touched);
+    for (;;) {
+        if (!sc->budget) sc->budget = workspace_budget(sc->device);
+        w = plan_workspace(p, sc->budget / static_cast<size_t>(n_lanes), row_touched.empty() ? nullptr : row_touched.data());
+        if (p.rows_per_batch <= 0 && p.shard.owned_rows > 0)
+            return fail(MCRT_ERR_INVALID, "one tile row holds more than 2^31 samples (width x tile size x samples per pixel)");
+        hipError_t e = hipSuccess;
+        auto want = [&](DeviceBuffer& b, size_t bytes) {
+            if (e == hipSuccess) e = b.reserve(bytes);
+        };
+        want(s->tile_rng, w.tile_rng);
+        want(s->tile_draws, w.tile_draws);
+        want(s->scol, w.scol);
+        want(s->end, w.end);
+        want(s->units, w.units);
+        want(s->tile_mask, w.tile_mask);
+        want(s->unit_hits, w.unit_hits);
+        for (auto& q : s->queues) want(q, w.queue_each);
+        want(s->texel_refs, w.texel_refs);
+        want(s->targets, w.targets);
+        want(s->cand, w.cand);
+        want(s->lit[0], w.lit0);
+        want(s->lit[1], w.lit1);
+        want(s->stack, w.stack);
+        {
+            const void* before = s->counters.ptr;
+            want(s->counters, w.counters);
+            if (e == hipSuccess && s->counters.ptr != before) e = hipMemset(s->counters.ptr, 0, w.counters);  // incl. the sticky overflow word
+        }
+        want(s->hit_rng, w.hit_rng);
+        if (e == hipSuccess) break;
+        (void)hipGetLastError();
+        if (e != hipErrorOutOfMemory || p.rows_per_batch <= 1 || sc->budget < (static_cast<size_t>(64) << 20))
+            return hip_fail(e, "workspace allocation");
+        // make room: this lane's partially grown buffers go, then try again with half the budget
+        (void)hipDeviceSynchronize();
+        for_each_buffer(*s, [](DeviceBuffer& b) { b.release(); });
+        sc->budget /= 2;
+    }
+    if (row_touched_out) *row_touched_out = row_touched;
+    p.tile_rng = w.tile_rng ? static_cast<uint32_t*>(s->tile_rng.ptr) : nullptr;
+    WaveSpace& ws = p.ws;
+    ws.tile_draws = static_cast<float*>(s->tile_draws.ptr);
+    ws.scol = static_cast<float4*>(s->scol.ptr);
+    ws.end = static_cast<uint32_t*>(s->end.ptr);
+    ws.units = static_cast<uint4*>(s->units.ptr);
+    ws.tile_mask = static_cast<unsigned long long*>(s->tile_mask.ptr);
+    for (int k = 0; k < 2; ++k) {  // [1] = [0] + cap: the second ping-pong queue (general variants) = the deep records (flat pipeline)
+        ws.q_o[k] = static_cast<float4*>(s->queues[0].ptr) + static_cast<size_t>(k) * ws.cap;
+        ws.q_d[k] = static_cast<float4*>(s->queues[1].ptr) + static_cast<size_t>(k) * ws.cap;
+        ws.q_p[k] = static_cast<float4*>(s->queues[2].ptr) + static_cast<size_t>(k) * ws.cap;
+        ws.q_n[k] = static_cast<float4*>(s->queues[3].ptr) + static_cast<size_t>(k) * ws.cap;
+        ws.q_t[k] = static_cast<float4*>(s->queues[4].ptr) + static_cast<size_t>(k) * ws.cap;
+    }
+    ws.q_x = static_cast<int32_t*>(s->texel_refs.ptr);
+    ws.targets = static_cast<float*>(s->targets.ptr);
+    ws.cand = static_cast<unsigned long long*>(s->cand.ptr);
+    ws.lit[0] = static_cast<uint32_t*>(s->lit[0].ptr);
+    ws.lit[1] = static_cast<uint32_t*>(s->lit[1].ptr);
+    ws.unit_hits = static_cast<uint32_t*>(s->unit_hits.ptr);
+    ws.stack = static_cast<float4*>(s->stack.ptr);
+    ws.counters = static_cast<uint32_t*>(s->counters.ptr);
+    ws.counter_base = ws.counters + kCounterWords;
+    ws.frame_info = ws.counters + 2 * kCounterWords;
+    ws.hit_rng = w.hit_rng ? static_cast<uint32_t*>(s->hit_rng.ptr) : nullptr;
+    return MCRT_OK;
+}
+
+// the launches of one render on `stream`: lanes fork from and join the stream
+// marks: per lane, or nullptr
+int launch_lanes(mcrt_scene* s, const RenderParams* p, int n_lanes, hipStream_t stream, const LaunchMarks* marks = nullptr) {
+    if (n_lanes > 1) {
+        if (!s->fork) HIP_TRY(hipEventCreateWithFlags(&s->fork, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(s->fork, stream));
+        for (int li = 1; li < n_lanes; ++li) {
+            Lane& ln = s->lanes[li];
+            HIP_TRY(hipStreamWaitEvent(ln.stream, s->fork, 0));
+            HIP_TRY(launch_render(p[li], ln.stream, marks ? &marks[li] : nullptr));
+            HIP_TRY(hipEventRecord(ln.done, ln.stream));
+        }
+    }
+    HIP_TRY(launch_render(p[0], stream, marks ? &marks[0] : nullptr));
+    for (int li = 1; li < n_lanes; ++li) HIP_TRY(hipStreamWaitEvent(stream, s->lanes[li].done, 0));
+    return MCRT_OK;
+}
+
+RngKey rng_key_of(const RenderParams& p) {
+    RngKey k;
+    k.ptr = p.tile_rng;
+    k.width = p.cfg.width, k.tile_size = p.cfg.tile_size;
+    k.first = p.shard.first, k.step = p.shard.step, k.tiles_x = p.shard.tiles_x, k.owned_rows = p.shard.owned_rows;
+    k.rect[0] = p.rect_x, k.rect[1] = p.rect_y, k.rect[2] = p.rect_w, k.rect[3] = p.rect_h;
+    k.parts = p.stream_parts, k.part_twists = p.stream_part_twists;
+    return k;
+}
+
+// MCRT_GRAPH=0 turns launch recording off (every render then issues its four launches per lane and pass itself)
+bool graphs_enabled() {
+    static const bool v = env_int("MCRT_GRAPH", 1) != 0;
+    return v;
+}
+
+// deepest recursion the workspace is laid out for (one stack slot per level and sample; the general
+// variants also keep one queue counter per level)
+constexpr int kMaxBounces = 4000;
+
+// The launches of one render, directly or — when the same parameters keep coming — as one replayed
+// hipGraph.  The launch sequence of a render is a pure function of its RenderParams (all control flow
+// that depends on data lives on the device), so it is recorded once through stream capture on a private
+// stream, lanes included, and replayed with a single hipGraphLaunch: ~75 us of launch calls per render
+// become one.
+int launch_or_replay(mcrt_scene* s, const RenderParams* p, int n_lanes, hipStream_t stream, bool may_record) {
+    if (!graphs_enabled() || !may_record) return launch_lanes(s, p, n_lanes, stream);
+    ++s->use_clock;
+    mcrt_scene::Recorded* slot = nullptr;
+    for (auto& r : s->recorded)
+        if (r.exec && r.n_lanes == n_lanes && std::memcmp(r.p, p, sizeof(RenderParams) * n_lanes) == 0) slot = &r;
+    if (!slot) {
+        // Recording costs tens of milliseconds (capture + instantiation): a parameter set is recorded
+        // at its kRecordAt-th sighting, earlier renders launch directly.
+        constexpr int kRecordAt = 4;
+        mcrt_scene::Recorded* victim = &s->recorded[0];
+        for (auto& r : s->recorded) {
+            if (!r.exec && r.n_lanes == n_lanes && std::memcmp(r.p, p, sizeof(RenderParams) * n_lanes) == 0) {
+                slot = &r;
+                break;
+            }
+            if (r.last_use < victim->last_use) victim = &r;
+        }
+        if (!slot) {  // first sighting: remember the parameters
+            if (victim->exec) {  // evicting a recorded sequence: an earlier launch of it may still be running
+                (void)hipDeviceSynchronize();
+                (void)hipGraphExecDestroy(victim->exec);
+            }
+            if (victim->graph) (void)hipGraphDestroy(victim->graph);
+            victim->exec = nullptr;
+            victim->graph = nullptr;
+            victim->n_lanes = n_lanes;
+            victim->sightings = 0;
+            std::memcpy(victim->p, p, sizeof(RenderParams) * kMaxLanes);
+            slot = victim;
+        }
+        slot->last_use = s->use_clock;
+        if (++slot->sightings < kRecordAt) return launch_lanes(s, p, n_lanes, stream);
+        if (!s->capture_stream) HIP_TRY(hipStreamCreateWithFlags(&s->capture_stream, hipStreamNonBlocking));
+        hipError_t e = hipStreamBeginCapture(s->capture_stream, hipStreamCaptureModeThreadLocal);
+        if (e == hipSuccess) {
+            const int rc = launch_lanes(s, p, n_lanes, s->capture_stream);
+            hipGraph_t g = nullptr;
+            e = hipStreamEndCapture(s->capture_stream, &g);
+            if (rc == MCRT_OK && e == hipSuccess && g) {
+                hipGraphExec_t ex = nullptr;
+                e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+                if (e == hipSuccess && ex) {
+                    slot->graph = g;
+                    slot->exec = ex;
+                } else {
+                    (void)hipGraphDestroy(g);
+                }
+            } else if (g) {
+                (void)hipGraphDestroy(g);
+            }
+        }
+        if (!slot->exec) {  // recording failed: forget it and launch directly
+            (void)hipGetLastError();
+            slot->n_lanes = 0;
+            return launch_lanes(s, p, n_lanes, stream);
+        }
+    }
+    slot->last_use = s->use_clock;
+    HIP_TRY(hipGraphLaunch(slot->exec, stream));
+    return MCRT_OK;
+}
+
+// One handle is one frame in flight: all renders of a handle share its workspace, so they run one after the other whatever
+// streams they are given.  Every render that uses the workspace sits between this pair, which owns the handle's `last_done`
+// event.  A render being captured into a caller's graph neither waits for nor records handle events (it runs when that
+// graph does, not now).  The pass counters run on from render to render (`resolve` leaves their values as the next pass's
+// base): no memset per pass.  Only after a render whose launches failed half way are they put back to zero: the counters
+// but their last four words (sticky flags, mcrt_scene_check's), and their base with the four words behind it.
+constexpr size_t kCounterResetBytes = static_cast<size_t>(kCounterWords - 4) * 4;    // from word 0
+constexpr size_t kBaseResetBytes = (static_cast<size_t>(kCounterWords) + 4) * 4;     // from word kCounterWords
+
+int begin_handle_render(mcrt_scene* s, int n_lanes, hipStream_t stream, bool capturing) {
+    if (!capturing && s->have_last && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->last_done, 0));
+    s->flags_checked = false;
+    if (!s->last_done) {
+        HIP_TRY(hipEventCreateWithFlags(&s->last_done, hipEventDisableTiming));
+        s->busy_probe.store(s->last_done, std::memory_order_release);
+    }
+    for (int li = 0; li < n_lanes; ++li) {
+        Lane& ln = s->lanes[li];
+        if (!ln.counters_dirty || !ln.counters.ptr) continue;
+        uint32_t* c = static_cast<uint32_t*>(ln.counters.ptr);
+        HIP_TRY(hipMemsetAsync(c, 0, kCounterResetBytes, stream));
+        HIP_TRY(hipMemsetAsync(c + kCounterWords, 0, kBaseResetBytes, stream));
+        ln.counters_dirty = false;
+    }
+    return MCRT_OK;
+}
+// rc: what the render's launches returned.  Failed launches leave the lanes' counters marked; otherwise `last_done` is
+// recorded behind them.  Returns rc, or the error of the record.
+int end_handle_render(mcrt_scene* s, int n_lanes, hipStream_t stream, int rc, bool capturing) {
+    if (rc != MCRT_OK) {
+        for (int li = 0; li < n_lanes; ++li) s->lanes[li].counters_dirty = true;
+        return rc;
+    }
+    if (capturing) return MCRT_OK;
+    HIP_TRY(hipEventRecord(s->last_done, stream));
+    s->last_stream = stream;
+    s->have_last = true;
+    return MCRT_OK;
+}
+
+// ---- batches: N frames of one config in one launch sequence (mcrt_render_batch_device) -----------------------------
+// one launch sequence for the frames p[0..m) of the handles sc[0..m), all eligible (batch_eligible) and prepared on lane 0
+int launch_batch_sequence(mcrt_scene* const* sc, RenderParams* p, int m, int device, hipStream_t stream) {
+    BatchPlan plan;
+    {
+        const bool others = device_shared(sc[0]);
+        if (plan_batch(p, m, others, plan) != hipSuccess) return fail(MCRT_ERR_HIP, "internal error: the frames of a batch do not share their launch shapes");
+    }
+    // the table: the frames' rows, then again the rows of the frames whose tile seeds have to be re-made (they are kept per
+    // lane with the key they were made for)
+    std::vector<RenderParams> rows;
+    rows.reserve(2 * static_cast<size_t>(m));
+    rows.assign(p, p + m);
+    for (int i = 0; i < m; ++i)
+        if (p[i].tile_rng && !(rng_key_of(p[i]) == sc[i]->lanes[0].rng_key)) rows.push_back(p[i]);
+    const int n_stale = static_cast<int>(rows.size()) - m;
+    for (int i = 0; i < m; ++i)
+        if (const int rc = begin_handle_render(sc[i], 1, stream, false); rc != MCRT_OK) return rc;
+    TableUpload table;
+    if (const int rc = upload_table(device, rows.data(), rows.size() * sizeof(RenderParams), stream, table); rc != MCRT_OK) return rc;
+    const RenderParams* d_table = static_cast<const RenderParams*>(table.dev);
+    hipError_t e = table.status;
+    if (e == hipSuccess && n_stale > 0) e = launch_seed_tiles_batch(rows[static_cast<size_t>(m)], d_table + m, n_stale, stream);
+    if (e == hipSuccess) e = launch_render_batch(p[0], plan, d_table, m, stream);
+    if (e == hipSuccess) e = table.commit(stream);
+    const int rc = e == hipSuccess ? MCRT_OK : hip_fail(e, "batched launches");
+    for (int i = 0; i < m; ++i) {
+        if (rc == MCRT_OK && p[i].tile_rng) sc[i]->lanes[0].rng_key = rng_key_of(p[i]);  // (unchanged where the seeds were kept)
+        const int ended = end_handle_render(sc[i], 1, stream, rc, false);
+        if (ended != rc) return ended;
+    }
+    return rc;
+}
+
+// ---- geometry layers: depth / normal / albedo / id planes and pixel picks (mcrt_render_layers_device & co) ----------------
+// A layers pass reads the scene blob alone — no workspace, no counters, no events of the handle — so it neither waits for the
+// handle's renders nor makes them wait; mcrt_scene_destroy and mcrt_scene_check synchronise the device, which covers it.
+// frame `index` of a call: the handle's scene, the planes `index * stride` pixels on; returns the kernel variant it needs
+int layers_frame_of(const mcrt_scene* s, const mcrt_layers& out, size_t index, size_t stride, LayersFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.depth = out.depth ? out.depth + off : nullptr;
+    f.normal = out.normal ? reinterpret_cast<float4*>(out.normal) + off : nullptr;
+    f.albedo = out.albedo ? reinterpret_cast<float4*>(out.albedo) + off : nullptr;
+    f.id = out.id ? reinterpret_cast<int4*>(out.id) + off : nullptr;
+    return layers_view(f, s->alpha_words, s->n_meshes, s->posed);
+}
+
+}  // namespace
+
+namespace mcrt_host {
+
+// workspace budget of a render (bytes, all lanes together); MCRT_WORKSPACE_MB overrides (tests use a
+// small value to force multi-batch renders).  By default a third of the scene's device's memory (96 GB of the
+// MI355X's 288): the workspace is sized for the worst case of every
+// sample hitting (~300 B per sample), buffers only ever grow to what a frame needs, and a frame cut into few large
+// batches is much faster than many small ones (4K / 8 bounces / 16 spp: 9.7 ms with 4 GiB, 6.1 ms in one batch).
+// (total memory of a device: device_stores.cpp)
+size_t workspace_budget(int device) {  // read per scene: tests switch MCRT_WORKSPACE_MB between renders
+    const long long mb = env_ll("MCRT_WORKSPACE_MB", 0);
+    if (mb > 0) return static_cast<size_t>(mb) << 20;
+    // (when the device cannot give that much right now — other allocations, a shared GPU — prepare() halves the budget
+    // and re-plans instead of failing)
+    return std::max<size_t>(static_cast<size_t>(256) << 20, device_total_memory(device) / 3);
+}
+
+int validate_config(const mcrt_config* cfg) {
+    if (cfg->max_bounces > kMaxBounces) return fail(MCRT_ERR_INVALID, "max_bounces above 4000 is not supported (one stack slot per level and sample)");
+    return MCRT_OK;
+}
+
+hipEvent_t next_mark(mcrt_scene* s) {
+    if (s->marks_used == s->marks.size()) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
+        s->marks.push_back(e);
+    }
+    return s->marks[s->marks_used++];
+}
+
+int enqueue_render(mcrt_scene* s, const mcrt_config* cfg, int first, int step, int layout, float* d_out, uint8_t* d_out8,
+                   hipStream_t stream, bool may_record, std::vector<RowGroup>* groups, const mcrt_tile* rect) {
+    Shard whole = make_shard(*cfg, first, step);
+    if (rect) whole.owned_rows = 1;
+    if (whole.owned_rows <= 0) return MCRT_OK;
+    if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
+    const int n_lanes = lane_count(s, *cfg, whole);
+    if (cfg->ao_enabled && cfg->ao_samples > 0) ensure_full_seed_table(s, stream);
+    RenderParams p[kMaxLanes];
+    std::memset(p, 0, sizeof p);
+    std::vector<int> row_touched[kMaxLanes];
+    for (int li = 0; li < n_lanes; ++li) {
+        int rc = prepare(s, li, n_lanes, cfg, first, step, layout, d_out, d_out8, p[li], groups ? &row_touched[li] : nullptr, rect);
+        if (rc != MCRT_OK) return rc;
+        Lane& ln = s->lanes[li];
+        if (li > 0 && !ln.stream) {
+            HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
+        }
+    }
+    if (n_lanes > 1 && !s->fork) HIP_TRY(hipEventCreateWithFlags(&s->fork, hipEventDisableTiming));
+    const bool capturing = stream_capturing(stream);
+    {  // Lanes share the device among themselves; a caller's graph is replayed in circumstances unknown now (no event queries
+       // while it records).  Frames of 6.4e7 samples and more keep the large grids: their kernels run for milliseconds,
+       // balance counts for more than room for the neighbours (GUI defaults and 4K / 16 spp, 1.3e8 samples: 3.14 / 3.20 ms,
+       // 1.49 / 1.48; 8K 17.9 / 18.0; but 4K / 4 spp, 3.3e7 samples: 0.351 / 0.340 ms).
+        const int spp = cfg->samples_per_pixel > 1 ? cfg->samples_per_pixel : 1;
+        const double samples = static_cast<double>(whole.owned_rows) * cfg->tile_size * cfg->width * spp;
+        const bool company = n_lanes > 1 || (!capturing && device_shared(s));
+        const bool shared = company && samples < 6.4e7;
+        for (int li = 0; li < n_lanes; ++li) choose_grids(p[li], shared, company);
+    }
+    if (capturing && groups) return fail(MCRT_ERR_INVALID, "row-group events cannot be recorded into a caller's graph");
+    {  // the gradient background tiles: copied from the device's plate of this frame configuration when it has one (built, if
+       // at all, before anything of this render is enqueued; every lane and shard reads the same plate)
+        const float4* plate = acquire_bg_plate(s, p[0], capturing, true);
+        for (int li = 0; li < n_lanes; ++li) p[li].bg_plate = plate;
+    }
+    if (const int rc = begin_handle_render(s, n_lanes, stream, capturing); rc != MCRT_OK) return rc;
+    // the tiles' seeded mt19937 states: kept across renders, re-made (on the caller's stream, ahead of
+    // the lanes' fork) only when the frame width, the tile size or the shard changed
+    for (int li = 0; li < n_lanes; ++li) {
+        if (!p[li].tile_rng) continue;
+        Lane& ln = s->lanes[li];
+        const RngKey k = rng_key_of(p[li]);
+        if (!capturing && k == ln.rng_key) continue;
+        HIP_TRY(launch_seed_tiles(p[li], stream));
+        ln.rng_key = capturing ? RngKey{} : k;  // a captured seeding pass runs when the caller's graph does, not now
+    }
+    if (groups) {
+        // which rows are final when: a row that holds no touched tile is complete behind plan_tiles (which
+        // renders background tiles itself); the rows of a pass behind its resolve; everything at the end
+        LaunchMarks marks[kMaxLanes];
+        std::vector<hipEvent_t> batch_events[kMaxLanes];
+        RowGroup early, late;
+        std::vector<RowGroup> per_batch;
+        for (int li = 0; li < n_lanes; ++li) {
+            const RenderParams& q = p[li];
+            const int batches = (q.shard.owned_rows + q.rows_per_batch - 1) / q.rows_per_batch;
+            auto row_of = [&](int j) { return q.shard.first + j * q.shard.step; };
+            if (batches <= 1) {
+                hipEvent_t planned = nullptr;
+                if (q.bg_in_plan) {
+                    planned = next_mark(s);
+                    if (!planned) return fail(MCRT_ERR_HIP, "event creation failed");
+                    marks[li].after_plan = planned;
+                    early.wait.push_back(planned);
+                }
+                for (int j = 0; j < q.shard.owned_rows; ++j) {
+                    const bool background_only = planned && static_cast<size_t>(j) < row_touched[li].size() && row_touched[li][static_cast<size_t>(j)] == 0;
+                    (background_only ? early : late).rows.push_back(row_of(j));
+                }
+            } else {
+                batch_events[li].resize(static_cast<size_t>(batches));
+                for (int b = 0; b < batches; ++b) {
+                    hipEvent_t e = next_mark(s);
+                    if (!e) return fail(MCRT_ERR_HIP, "event creation failed");
+                    batch_events[li][static_cast<size_t>(b)] = e;
+                    RowGroup g;
+                    g.wait.push_back(e);
+                    for (int j = b * q.rows_per_batch; j < q.shard.owned_rows && j < (b + 1) * q.rows_per_batch; ++j) g.rows.push_back(row_of(j));
+                    per_batch.push_back(std::move(g));
+                }
+                marks[li].batch_done = batch_events[li].data();
+                marks[li].n_batch_done = batches;
+            }
+        }
+        const int rc = end_handle_render(s, n_lanes, stream, launch_lanes(s, p, n_lanes, stream, marks), capturing);
+        if (rc == MCRT_OK) {
+            late.wait.push_back(s->last_done);
+            if (!early.rows.empty()) groups->push_back(std::move(early));
+            for (auto& g : per_batch) groups->push_back(std::move(g));
+            if (!late.rows.empty()) groups->push_back(std::move(late));
+        }
+        return rc;
+    }
+    const int rc = capturing ? launch_lanes(s, p, n_lanes, stream) : launch_or_replay(s, p, n_lanes, stream, may_record);
+    return end_handle_render(s, n_lanes, stream, rc, capturing);
+}
+
+int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream) {
+    BatchInfo& info = last_batch();
+    info = BatchInfo{};
+    // argument checks, before any device work (the first ones do not look inside the handles)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    {
+        std::vector<mcrt_scene*> sorted(scenes, scenes + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (each handle owns one workspace: one frame in flight)");
+    }
+    if (!d_f32 && !d_u8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
+    if (validate_config(cfg) != MCRT_OK) return MCRT_ERR_INVALID;
+    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    if (stride < static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height))
+        return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
+    const int device = scenes[0]->device;
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    HIP_TRY(hipSetDevice(device));
+    if (stream_capturing(stream))
+        return fail(MCRT_ERR_INVALID, "a batch cannot be recorded into a caller's graph (its parameter table is uploaded per call)");
+    (void)hipGetLastError();
+    // every frame on lane 0 of its handle, one lane: the batched kernels take it when it fits their envelope.  The frames
+    // of a launch sequence share their background mode (it selects the `resolve` kernel): one group per mode.
+    std::vector<RenderParams> p(static_cast<size_t>(n));
+    std::vector<mcrt_scene*> in_batch[2];
+    std::vector<RenderParams> batch_p[2];
+    std::vector<int> alone;
+    bool plate_sighted = false;
+    for (int i = 0; i < n; ++i) {
+        mcrt_scene* s = scenes[i];
+        if (cfg->ao_enabled && cfg->ao_samples > 0) ensure_full_seed_table(s, stream);  // as the handle's first AO render would
+        float* f = d_f32 ? d_f32 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        uint8_t* b = d_u8 ? d_u8 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        const int rc = prepare(s, 0, 1, cfg, 0, 1, MCRT_LAYOUT_FRAME, f, b, p[static_cast<size_t>(i)]);
+        if (rc != MCRT_OK) return rc;
+        if (batch_eligible(p[static_cast<size_t>(i)])) {
+            // the device's background plate of the config, through the handle like a single render's; the batch is ONE sighting of its key
+            p[static_cast<size_t>(i)].bg_plate = acquire_bg_plate(s, p[static_cast<size_t>(i)], false, !plate_sighted);
+            plate_sighted = true;
+            const int mode = p[static_cast<size_t>(i)].background == MCRT_BACKGROUND_TRANSPARENT ? 1 : 0;
+            in_batch[mode].push_back(s);
+            batch_p[mode].push_back(p[static_cast<size_t>(i)]);
+        } else {
+            alone.push_back(i);
+        }
+    }
+    for (int mode = 0; mode < 2; ++mode) {
+        const int nb = static_cast<int>(in_batch[mode].size());
+        for (int c0 = 0; c0 < nb; c0 += kBatchMaxFrames) {  // one launch sequence per kBatchMaxFrames frames
+            const int m = std::min(kBatchMaxFrames, nb - c0);
+            const int rc = launch_batch_sequence(in_batch[mode].data() + c0, batch_p[mode].data() + c0, m, device, stream);
+            if (rc != MCRT_OK) return rc;
+            info.frames += m;
+            ++info.sequences;
+        }
+    }
+    // the rest (more than one pass, or the general variants) one after the other through the single-frame path
+    for (int i : alone) {
+        float* f = d_f32 ? d_f32 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        uint8_t* b = d_u8 ? d_u8 + static_cast<size_t>(i) * stride * 4 : nullptr;
+        const int rc = enqueue_render(scenes[i], cfg, 0, 1, MCRT_LAYOUT_FRAME, f, b, stream);
+        if (rc != MCRT_OK) return rc;
+        ++info.sequences;
+    }
+    return MCRT_OK;
+}
+
+int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream) {
+    // argument checks, before any device work (all but the last do not look inside the handles)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all four planes are NULL");
+    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    if (stride < static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height))
+        return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
+    const int device = scenes[0]->device;
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    LayersShape shape;
+    if (!make_layers_shape(*cfg, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(device));
+    if (n == 1) {  // one frame: its parameters travel as kernel arguments
+        LayersFrame f;
+        const int view = layers_frame_of(scenes[0], *d_out, 0, stride, f);
+        hipError_t e = launch_layers(f, shape, view, stream);
+        if (e != hipSuccess) return hip_fail(e, "layers launch");
+        return MCRT_OK;
+    }
+    if (stream_capturing(stream))
+        return fail(MCRT_ERR_INVALID, "a batch cannot be recorded into a caller's graph (its parameter table is uploaded per call)");
+    (void)hipGetLastError();
+    std::vector<LayersFrame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) views[static_cast<size_t>(i)] = layers_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
+    const int view = layers_batch_view(frames.data(), views.data(), n);
+    size_t dyn = 0;
+    for (const LayersFrame& f : frames) dyn = std::max(dyn, layers_lds_bytes(f));
+    // the frames' table: a slot of the batched renders' ring (refilled only after the launches that read it)
+    TableUpload table;
+    if (const int rc = upload_table(device, frames.data(), static_cast<size_t>(n) * sizeof(LayersFrame), stream, table); rc != MCRT_OK) return rc;
+    const LayersFrame* d_table = static_cast<const LayersFrame*>(table.dev);
+    hipError_t e = table.status;
+    for (int c0 = 0; c0 < n && e == hipSuccess; c0 += kLayersBatchMaxFrames)  // one launch per kLayersBatchMaxFrames frames
+        e = launch_layers_batch(d_table + c0, std::min(kLayersBatchMaxFrames, n - c0), shape, view, dyn, stream);
+    if (e == hipSuccess) e = table.commit(stream);
+    if (e != hipSuccess) return hip_fail(e, "batched layers launches");
+    return MCRT_OK;
+}
+
+}  // namespace mcrt_host
+
+extern "C" {
+
+int mcrt_render_device(mcrt_scene* s, const mcrt_config* cfg, int first, int step, int layout, float* d_out,
+                       void* stream) {
+    return mcrt_render_device_ex(s, cfg, first, step, layout, d_out, nullptr, stream);
+}
+
+int mcrt_render_device_ex(mcrt_scene* s, const mcrt_config* cfg, int first, int step, int layout, float* d_out_f32,
+                          uint8_t* d_out_rgba8, void* stream) {
+    if (!s || !cfg || (!d_out_f32 && !d_out_rgba8)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles
+    if (first < 0 || step < 1) return fail(MCRT_ERR_INVALID, "tile_row_first must be >= 0 and tile_row_step >= 1");
+    HIP_TRY(hipSetDevice(s->device));
+    return enqueue_render(s, cfg, first, step, layout, d_out_f32, d_out_rgba8, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_time_render_device(mcrt_scene* s, const mcrt_config* cfg, int first, int step, int layout, float* d_out,
+                            void* stream, int iters, float* avg_render_ms) {
+    if (!s || !cfg || !d_out || iters < 1) return fail(MCRT_ERR_INVALID, "bad argument");
+    if (!valid_frame(cfg)) return fail(MCRT_ERR_INVALID, "empty frame");
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double sum = 0.0;
+    for (int i = 0; i < iters; ++i) {
+        // the events bracket the whole pipeline of the frame (fork, every lane, join) on `stream`
+        HIP_TRY(hipEventRecord(s->ev[0], st));
+        int rc = enqueue_render(s, cfg, first, step, layout, d_out, nullptr, st);
+        if (rc != MCRT_OK) return rc;
+        HIP_TRY(hipEventRecord(s->ev[3], st));
+        HIP_TRY(hipEventSynchronize(s->ev[3]));
+        float a = 0;
+        HIP_TRY(hipEventElapsedTime(&a, s->ev[0], s->ev[3]));
+        sum += a;
+    }
+    if (avg_render_ms) *avg_render_ms = static_cast<float>(sum / iters);
+    return MCRT_OK;
+}
+
+int mcrt_unpack_rows_device(const mcrt_config* cfg, int first, int step, const float* d_packed, float* d_frame,
+                            void* stream) {
+    if (!cfg || !d_packed || !d_frame) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (!valid_frame(cfg)) return MCRT_OK;
+    Shard sh = make_shard(*cfg, first, step);
+    HIP_TRY(launch_unpack_rows(*cfg, sh, d_packed, d_frame, static_cast<hipStream_t>(stream)));
+    return MCRT_OK;
+}
+
+int mcrt_assemble_frame_device(const mcrt_config* cfg, int world, const float* d_gathered, size_t rank_stride_pixels,
+                               float* d_frame, void* stream) {
+    if (!cfg || !d_gathered || !d_frame || world < 1) return fail(MCRT_ERR_INVALID, "bad argument");
+    if (!valid_frame(cfg)) return MCRT_OK;
+    const int tiles_y = (cfg->height + cfg->tile_size - 1) / cfg->tile_size;
+    const size_t need = static_cast<size_t>((tiles_y + world - 1) / world) * cfg->tile_size * cfg->width;
+    if (world > 1 && rank_stride_pixels < need) return fail(MCRT_ERR_INVALID, "rank stride smaller than a rank's packed rows");
+    HIP_TRY(launch_assemble_frame(*cfg, world, d_gathered, rank_stride_pixels, d_frame, static_cast<hipStream_t>(stream)));
+    return MCRT_OK;
+}
+
+int mcrt_quantize_rgba8_device(const float* d_rgba, uint8_t* d_out, size_t n_pixels, void* stream) {
+    if (!d_rgba || !d_out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    HIP_TRY(launch_quantize(d_rgba, d_out, n_pixels, static_cast<hipStream_t>(stream)));
+    return MCRT_OK;
+}
+
+int mcrt_render_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, float* d_out_f32, uint8_t* d_out_rgba8,
+                             size_t frame_stride_pixels, void* stream) {
+    return render_batch_device(scenes, n_frames, cfg, d_out_f32, d_out_rgba8, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_layers_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_layers* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = (cfg && valid_frame(cfg)) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
+    return render_layers_batch_device(one, 1, cfg, d_out, px, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_layers_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_layers* d_out,
+                                    size_t frame_stride_pixels, void* stream) {
+    return render_layers_batch_device(scenes, n_frames, cfg, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

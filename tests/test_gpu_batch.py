@@ -133,6 +133,56 @@ def test_handle_reuse_and_a_second_stream(mcrt, gpu):
             h.close()
 
 
+def test_table_ring_shared_by_renders_and_layers_wraps_without_mixing_frames(mcrt, gpu):
+    """Batched renders and batched layers passes draw their parameter tables from ONE ring of eight slots per device.  Twenty
+    calls of the two kinds, on two streams, with nothing synchronised in between, take the ring past its eighth slot twice:
+    a table overwritten while an earlier call still reads it, or a slot reused without its event, shows as another pose's frame."""
+    cfg = abi.Config(width=64, height=48, maxBounces=2, samplesPerPixel=1, tileSize=16)
+    px, n_calls, per_call = cfg.width * cfg.height, 20, 3
+    handles = [mcrt.DeviceScene(scenes.skin_scene("S64", i)) for i in (0, 2, 4, 6)]
+    try:
+        beauty, depth, ids = [], [], []
+        for h in handles:  # what every frame has to equal: single calls, each waited for
+            beauty.append(_single(mcrt, h, cfg))
+            d = torch.zeros((px,), dtype=torch.float32, device="cuda")
+            i4 = torch.zeros((px, 4), dtype=torch.int32, device="cuda")
+            h.render_layers_device(cfg, depth_ptr=d.data_ptr(), id_ptr=i4.data_ptr(), stream=_stream())
+            torch.cuda.synchronize()
+            depth.append(d.cpu().numpy())
+            ids.append(i4.cpu().numpy())
+        assert any(not np.array_equal(beauty[0], b) for b in beauty[1:])  # the poses differ: a mixed-up frame would show
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        out = []
+        for k in range(n_calls):  # every call writes into buffers of its own
+            if k % 2 == 0:
+                out.append((torch.zeros((per_call, px, 4), dtype=torch.float32, device="cuda"),))
+            else:
+                out.append((torch.zeros((per_call, px), dtype=torch.float32, device="cuda"),
+                            torch.zeros((per_call, px, 4), dtype=torch.int32, device="cuda")))
+        torch.cuda.synchronize()  # the buffers are filled; from here to the end nothing waits
+        order = [[(k + j) % len(handles) for j in range(per_call)] for k in range(n_calls)]
+        for k in range(n_calls):
+            hs, st = [handles[i] for i in order[k]], streams[k % 2].cuda_stream
+            if k % 2 == 0:
+                mcrt.render_batch_device(hs, cfg, out[k][0].data_ptr(), 0, px, st)
+            else:
+                mcrt.render_layers_batch_device(hs, cfg, depth_ptr=out[k][0].data_ptr(), id_ptr=out[k][1].data_ptr(), stream=st)
+        torch.cuda.synchronize()
+        for k in range(n_calls):
+            for j, i in enumerate(order[k]):
+                what = f"call {k}, frame {j} (handle {i})"
+                if k % 2 == 0:
+                    scenes.assert_bit_equal(out[k][0][j].cpu().numpy().reshape(cfg.height, cfg.width, 4), beauty[i], what)
+                else:
+                    scenes.assert_bit_equal(out[k][0][j].cpu().numpy(), depth[i], what + " depth")
+                    assert np.array_equal(out[k][1][j].cpu().numpy(), ids[i]), what + " id"
+        for h in handles:
+            h.check()
+    finally:
+        for h in handles:
+            h.close()
+
+
 def test_frame_stride_leaves_padding_untouched(mcrt, gpu):
     cfg = abi.Config(width=40, height=24, maxBounces=2, samplesPerPixel=1, tileSize=16)
     handles = [mcrt.DeviceScene(scenes.skin_scene("S64", i)) for i in (1, 4, 6)]

@@ -454,7 +454,7 @@ def test_workspace_is_reused_across_scenes_and_trim_frees_it(mcrt, gpu, oracle):
 
 def test_frames_in_flight_on_one_device_render_the_same_bits(mcrt, gpu, oracle):
     """A render enqueued while another handle's frame is still running on the device sizes its launches for sharing
-    (fewer workgroups per kernel, api.cpp device_shared / choose_grids), one enqueued on an idle device for its own
+    (fewer workgroups per kernel, device_stores.cpp device_shared / choose_grids), one enqueued on an idle device for its own
     latency; both are recorded as launch graphs of their own.  The schedule must not show in the pixels."""
     sd = scenes.skin_scene("S64", 6)
     cfg = abi.Config(width=480, height=272, maxBounces=3, samplesPerPixel=2)
