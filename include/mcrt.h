@@ -217,6 +217,24 @@ void mcrt_trim(void);
 /* plates currently kept on `device`, their bytes, and how many were built there since the process began (any may be NULL) */
 int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds);
 
+/* Draw plates.  The jitter and lens draws of a tile come from the tile's own mt19937 stream, seeded tile.y * width + tile.x:
+ * they are a function of width, height, tile_size, samples_per_pixel and depth of field on / off alone — scene, pose, camera,
+ * light, bounces and background do not enter.  The library keeps them like the background plates, under the same rules:
+ * the second time such a configuration is rendered on a device (every render call counts; any background, the transparent
+ * one included; up to 24 draws per pixel: 2 to 12 samples per pixel, 1 to 6 under depth of field; whole frames and shards,
+ * not mcrt_render_rect) the draws of every tile of the frame are written once into a plate on the device, and later renders
+ * read the draws of the tiles the figure touches from it instead of running each tile's chain of mt19937 twists again:
+ * identical frames.  A configuration that takes both plates gets both in the same render call.  Memory:
+ * ceil(width / tile_size) * ceil(height / tile_size) * tile_size^2 * samples_per_pixel * (2, or 4 under depth of field) * 4
+ * bytes per plate (1080p at tile 32 and 4 spp: 66.8 MB, 4K: 267 MB); at most 4 plates and MCRT_DRAW_PLATE_BUDGET_MB MiB per
+ * device.  Sightings, holding (four per scene handle and kind), eviction, failed builds, caller's graph captures and
+ * mcrt_trim() are as for the background plates.  MCRT_DRAW_PLATE=0 turns draw plates off, MCRT_DRAW_PLATE=2 builds at a
+ * configuration's first render (development knobs). */
+#define MCRT_DRAW_PLATE_BUDGET_MB 512
+/* draw plates currently kept on `device`, their bytes, and how many were built there since the process began (any may be NULL);
+ * mcrt_bg_plate_info reports background plates only */
+int mcrt_draw_plate_info(int device, int* plates, size_t* bytes, int* builds);
+
 /* Waits for the scene's device work and reports an internal inconsistency of the last renders (the
  * workspace is sized for the tiles the host expects meshes to touch; the device flags a tile beyond
  * that bound instead of writing past it).  MCRT_OK in every correct run; the one-shot entry points

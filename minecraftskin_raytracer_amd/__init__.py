@@ -5,6 +5,7 @@ from .api import (  # noqa: F401
     DeviceScene,
     assemble_frame_device,
     bg_plate_info,
+    draw_plate_info,
     ImageWriter,
     MeshBuilder,
     SceneDesc,
@@ -30,5 +31,5 @@ __all__ = [
     "Config", "Mesh", "Scene", "Texture", "synthetic_skin", "DeviceScene", "MeshBuilder", "SceneDesc",
     "TileRenderer", "device_count", "flatten", "getBuiltinPoses", "probe_detmath", "probe_detmath_range",
     "probe_mt_uniform", "quantize_rgba8", "quantize_rgba8_device", "unpack_rows_device", "ImageWriter", "render_png", "assemble_frame_device", "trim",
-    "render_batch_device", "last_batch_info", "bg_plate_info", "render_layers_batch_device", "skin_texel",
+    "render_batch_device", "last_batch_info", "bg_plate_info", "draw_plate_info", "render_layers_batch_device", "skin_texel",
 ]

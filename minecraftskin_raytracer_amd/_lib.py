@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_assemble_frame_device", "mcrt_scene_set_lanes", "mcrt_trim", "mcrt_scene_check", "mcrt_render_multi",
     "mcrt_render_rgba8", "mcrt_render_rect", "mcrt_render_batch_device", "mcrt_render_batch", "mcrt_last_batch_info",
     "mcrt_scene_set_background", "mcrt_render_ex", "mcrt_render_batch_ex", "mcrt_render_png_ex",
-    "mcrt_bg_plate_info",
+    "mcrt_bg_plate_info", "mcrt_draw_plate_info",
     "mcrt_render_layers_device", "mcrt_render_layers_batch_device", "mcrt_render_layers", "mcrt_render_layers_batch",
     "mcrt_scene_pick", "mcrt_skin_texel",
 ]

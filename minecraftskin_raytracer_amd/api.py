@@ -540,6 +540,16 @@ def bg_plate_info(device: int = 0) -> dict:
     return {"plates": int(n.value), "bytes": int(b.value), "builds": int(k.value)}
 
 
+def draw_plate_info(device: int = 0) -> dict:
+    """mcrt_draw_plate_info: ``{"plates": ..., "bytes": ..., "builds": ...}`` — the draw plates kept on ``device``, their
+    bytes, and how many were built there since the process began (include/mcrt.h, "Draw plates")."""
+    fn = load().mcrt_draw_plate_info  # bound here: a build selected with MCRT_LIB may predate it
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    n, b, k = C.c_int(), C.c_size_t(), C.c_int()
+    check(fn(int(device), C.byref(n), C.byref(b), C.byref(k)))
+    return {"plates": int(n.value), "bytes": int(b.value), "builds": int(k.value)}
+
+
 def unpack_rows_device(config: Config, first: int, step: int, packed_ptr: int, frame_ptr: int, stream: int = 0) -> None:
     c = config.to_c()
     check(load().mcrt_unpack_rows_device(C.byref(c), first, step, C.c_void_p(packed_ptr), C.c_void_p(frame_ptr), C.c_void_p(stream)))

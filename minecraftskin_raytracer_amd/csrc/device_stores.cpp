@@ -1,5 +1,5 @@
 // device_stores.cpp — what libmcrt.so keeps per device or per process: the devices' memory sizes, the live list of scene
-// shells, the seed tables, the background plates, the pool of idle shells and the ring of parameter tables.  Each store
+// shells, the seed tables, the background and draw plates, the pool of idle shells and the ring of parameter tables.  Each store
 // has a mutex of its own, and no function here holds one while it takes another.
 #include "host_internal.h"
 
@@ -150,38 +150,21 @@ void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream) {
 }
 
 namespace {
-// ---- per-device background plates (kernels.h; mcrt.h states the memory cost and the knobs) -------------------------
-// A store per device, under one mutex, entries with a `users` count like the seed tables.  An entry starts as a sighting
-// record (no memory); the plate is built at the key's second render call on the device — one-shot calls and sweeps over
-// thousands of sizes never allocate — synchronously, on the store's own non-blocking stream, never on the null stream and
-// never while the caller records a graph.  Once built a plate is immutable: no validity flags, nothing published or
-// tested on the device, no writer beside a reader.  Plates nobody holds make way, least recently used first, when a
-// new one needs the room; one that does not fit gets no plate and the frame renders as it always did.
-constexpr size_t kBgPlateBudget = static_cast<size_t>(MCRT_BG_PLATE_BUDGET_MB) << 20;  // built plates of a device, together
-constexpr int kBgPlateBuilt = 8;     // built plates per device
-constexpr int kBgPlateKeys = 32;     // entries per device, sighting records included
-constexpr int kBgPlateRetryAfter = 16;  // sightings a key waits after a failed build before the next try
-constexpr size_t kHeldPlates = 4;    // plates one scene shell holds at a time (as many as it records launch graphs)
-struct DevicePlates {
-    std::vector<BgPlate*> entries;
-    unsigned long long clock = 0;
-    hipStream_t stream = nullptr;  // the builds
-    size_t bytes = 0;              // of the built plates
-    int built = 0;
-    int builds = 0;                // plates built so far (mcrt_bg_plate_info)
-};
-std::mutex g_plate_mutex;
-std::vector<DevicePlates> g_plates;  // by device
+// ---- per-device plates (kernels.h; mcrt.h states the memory cost and the knobs) -------------------------------------
+// Two kinds — the background tiles' pixels, every tile's draws — in one store: per kind and device a list of entries with a
+// `users` count like the seed tables, all under one mutex; the kinds differ in the table below (key, bytes, fill launch,
+// budget, knob).  An entry starts as a sighting record (no memory); the plate is built at the key's second render call on
+// the device — one-shot calls and sweeps over thousands of sizes never allocate — synchronously, on the store's own
+// non-blocking stream, never on the null stream and never while the caller records a graph.  Once built a plate is
+// immutable: no validity flags, nothing published or tested on the device, no writer beside a reader.  Plates nobody holds
+// make way, least recently used first, when a new one needs the room; one that does not fit gets no plate and the frame
+// renders as it always did.
+constexpr int kPlateKeys = 32;        // entries per kind and device, sighting records included
+constexpr int kPlateRetryAfter = 16;  // sightings a key waits after a failed build before the next try
+constexpr size_t kHeldPlates = 4;     // plates of a kind one scene shell holds at a time (as many as it records launch graphs)
 
-int bg_plate_mode() {  // development knob MCRT_BG_PLATE: 0 no plates, 2 build at a key's first render (tests); else at the second
-    static const int mode = [] {
-        const int v = env_int("MCRT_BG_PLATE", 1);
-        return v == 0 ? 0 : (v == 2 ? 2 : 1);
-    }();
-    return mode;
-}
-BgPlateKey bg_plate_key_of(const RenderParams& p) {
-    BgPlateKey k;
+PlateKey pixel_key_of(const RenderParams& p) {
+    PlateKey k;
     std::memset(&k, 0, sizeof k);
     k.width = p.cfg.width, k.height = p.cfg.height, k.tile_size = p.cfg.tile_size;
     k.spp = p.cfg.samples_per_pixel > 1 ? p.cfg.samples_per_pixel : 1;
@@ -192,10 +175,58 @@ BgPlateKey bg_plate_key_of(const RenderParams& p) {
     for (int i = 0; i < 3; ++i) k.bg_center[i] = p.cfg.bg_center[i], k.bg_edge[i] = p.cfg.bg_edge[i];
     return k;
 }
-bool same_key(const BgPlateKey& a, const BgPlateKey& b) { return std::memcmp(&a, &b, sizeof a) == 0; }  // (floats by their bits)
+PlateKey draw_key_of(const RenderParams& p) {  // a tile's draws: the frame's size, the tile size, the samples and the draws per sample
+    PlateKey k;
+    std::memset(&k, 0, sizeof k);
+    k.width = p.cfg.width, k.height = p.cfg.height, k.tile_size = p.cfg.tile_size;
+    k.spp = p.cfg.samples_per_pixel > 1 ? p.cfg.samples_per_pixel : 1;
+    k.draws_per_sample = p.draws_per_sample;
+    return k;
+}
+bool same_key(const PlateKey& a, const PlateKey& b) { return std::memcmp(&a, &b, sizeof a) == 0; }  // (floats by their bits)
+
+struct PlateKindInfo {
+    const char* knob;   // development knob: 0 no plates, 2 build at a key's first render (tests); else at the second
+    size_t budget;      // built plates of a device, together
+    int max_built;      // built plates per device
+    bool (*eligible)(const RenderParams& p);
+    PlateKey (*key_of)(const RenderParams& p);
+    size_t (*bytes)(const RenderParams& p);
+    size_t (*rng_bytes)(const RenderParams& p);  // scratch of the fill: the engine states of every tile of the frame
+    hipError_t (*fill)(const RenderParams& p, void* plate, uint32_t* rng, hipStream_t stream);
+    int mode = -1;      // the knob, read once (plate_mode)
+};
+PlateKindInfo g_kinds[kPlateKinds] = {
+    {"MCRT_BG_PLATE", static_cast<size_t>(MCRT_BG_PLATE_BUDGET_MB) << 20, 8, bg_plate_eligible, pixel_key_of,
+     [](const RenderParams& p) { return bg_plate_bytes(p.cfg); }, bg_plate_rng_bytes,
+     [](const RenderParams& p, void* plate, uint32_t* rng, hipStream_t st) { return launch_fill_bg_plate(p, static_cast<float4*>(plate), rng, st); }},
+    {"MCRT_DRAW_PLATE", static_cast<size_t>(MCRT_DRAW_PLATE_BUDGET_MB) << 20, 4, draw_plate_eligible, draw_key_of, draw_plate_bytes, draw_plate_rng_bytes,
+     [](const RenderParams& p, void* plate, uint32_t* rng, hipStream_t st) { return launch_fill_draw_plate(p, static_cast<float*>(plate), rng, st); }},
+};
+struct DevicePlates {
+    std::vector<Plate*> entries;
+    unsigned long long clock = 0;
+    hipStream_t stream = nullptr;  // the builds
+    size_t bytes = 0;              // of the built plates
+    int built = 0;
+    int builds = 0;                // plates built so far (mcrt_bg_plate_info, mcrt_draw_plate_info)
+};
+std::mutex g_plate_mutex;
+std::vector<DevicePlates> g_plates[kPlateKinds];  // by device
+
+int plate_mode(int kind) {
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (PlateKindInfo& k : g_kinds) {
+            const int v = env_int(k.knob, 1);
+            k.mode = v == 0 ? 0 : (v == 2 ? 2 : 1);
+        }
+    });
+    return g_kinds[kind].mode;
+}
 
 // g_plate_mutex held.  Frees a built plate nobody holds: every holder synchronised the device before it let go.
-void free_plate(DevicePlates& d, BgPlate* e) {
+void free_plate(DevicePlates& d, Plate* e) {
     if (!e->ptr) return;
     (void)hipFree(e->ptr);
     e->ptr = nullptr;
@@ -204,46 +235,51 @@ void free_plate(DevicePlates& d, BgPlate* e) {
     --d.built;
 }
 // g_plate_mutex held, the device current.  Builds e's plate for the frame prepared as `p`; leaves e->ptr NULL when there is no room
-// (asked again at the key's next render) or the build fails (an allocation refused, for one: asked again kBgPlateRetryAfter sightings later).
-void build_plate(DevicePlates& d, BgPlate* e, const RenderParams& p, size_t bytes) {
-    while (d.built >= kBgPlateBuilt || d.bytes + bytes > kBgPlateBudget) {
-        BgPlate* victim = nullptr;
-        for (BgPlate* q : d.entries)
+// (false is returned; asked again at the key's next render) or the build fails (an allocation refused, for one: asked again
+// kPlateRetryAfter sightings later).
+bool build_plate(const PlateKindInfo& kind, DevicePlates& d, Plate* e, const RenderParams& p, size_t bytes) {
+    while (d.built >= kind.max_built || d.bytes + bytes > kind.budget) {
+        Plate* victim = nullptr;
+        for (Plate* q : d.entries)
             if (q != e && q->ptr && q->users == 0 && (!victim || q->last_use < victim->last_use)) victim = q;
-        if (!victim) return;
+        if (!victim) return false;
         free_plate(d, victim);
         victim->sightings = 0;
     }
-    float4* plate = nullptr;
+    void* plate = nullptr;
     uint32_t* rng = nullptr;
     hipError_t err = d.stream ? hipSuccess : hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking);
     if (err == hipSuccess) err = hipMalloc(&plate, bytes);
-    if (err == hipSuccess) err = hipMalloc(&rng, bg_plate_rng_bytes(p));
-    if (err == hipSuccess) err = launch_fill_bg_plate(p, plate, rng, d.stream);
+    if (err == hipSuccess) err = hipMalloc(&rng, kind.rng_bytes(p));
+    if (err == hipSuccess) err = kind.fill(p, plate, rng, d.stream);
     if (err == hipSuccess) err = hipStreamSynchronize(d.stream);
     if (rng) (void)hipFree(rng);
     if (err != hipSuccess) {
         (void)hipGetLastError();
         if (plate) (void)hipFree(plate);
-        e->sightings = -kBgPlateRetryAfter;
-        return;
+        e->sightings = -kPlateRetryAfter;
+        return true;
     }
     e->ptr = plate;
     e->bytes = bytes;
     d.bytes += bytes;
     ++d.built;
     ++d.builds;
+    return true;
 }
-// The shell lets go of the plate it has held longest.  Its launches in flight and its recorded launch graphs may read the
-// plate: its last render is waited for — every render of a handle ends in `last_done`, lanes joined, and a handle's renders
-// run one after the other, so nothing of this handle reads the plate after it; other handles' frames are not waited
-// for — and those graphs are dropped first.
-void drop_held_plate(mcrt_scene* s) {
-    BgPlate* e = s->plates.front();
+// The shell lets go of the plate of `kind` it has held longest.  Its launches in flight and its recorded launch graphs may
+// read the plate: its last render is waited for — every render of a handle ends in `last_done`, lanes joined, and a
+// handle's renders run one after the other, so nothing of this handle reads the plate after it; other handles' frames are
+// not waited for — and those graphs are dropped first.
+void drop_held_plate(mcrt_scene* s, int kind) {
+    Plate* e = s->plates[kind].front();
     if (s->have_last && s->last_done) (void)hipEventSynchronize(s->last_done);
     for (auto& r : s->recorded) {
         bool reads = false;
-        for (int li = 0; li < kMaxLanes; ++li) reads = reads || (r.p[li].bg_plate != nullptr && r.p[li].bg_plate == e->ptr);
+        for (int li = 0; li < kMaxLanes; ++li) {
+            const void* read = kind == kPlatePixels ? static_cast<const void*>(r.p[li].bg_plate) : static_cast<const void*>(r.p[li].draw_plate);
+            reads = reads || (read != nullptr && read == e->ptr);
+        }
         if (!reads) continue;
         if (r.exec) (void)hipGraphExecDestroy(r.exec);
         if (r.graph) (void)hipGraphDestroy(r.graph);
@@ -252,87 +288,119 @@ void drop_held_plate(mcrt_scene* s) {
         r.n_lanes = 0;
         r.sightings = 0;
     }
-    s->plates.erase(s->plates.begin());
+    s->plates[kind].erase(s->plates[kind].begin());
     std::lock_guard<std::mutex> lock(g_plate_mutex);
     --e->users;
 }
-void release_bg_plates(mcrt_scene* s) {  // the shell goes (its device work has been waited for)
+void release_plates(mcrt_scene* s) {  // the shell goes (its device work has been waited for)
     std::lock_guard<std::mutex> lock(g_plate_mutex);
-    for (BgPlate* e : s->plates) --e->users;
-    s->plates.clear();
-}
-
-void free_unused_bg_plates() {  // mcrt_trim
-    std::lock_guard<std::mutex> lock(g_plate_mutex);
-    for (size_t dev = 0; dev < g_plates.size(); ++dev) {
-        DevicePlates& d = g_plates[dev];
-        (void)hipSetDevice(static_cast<int>(dev));
-        std::vector<BgPlate*> kept;
-        for (BgPlate* e : d.entries) {
-            if (e->users > 0) {
-                kept.push_back(e);
-                continue;
-            }
-            free_plate(d, e);
-            delete e;
-        }
-        d.entries.swap(kept);
-        if (d.stream) (void)hipStreamDestroy(d.stream);  // idle: every build waited for it under this mutex
-        d.stream = nullptr;
+    for (auto& held : s->plates) {
+        for (Plate* e : held) --e->users;
+        held.clear();
     }
 }
-}  // namespace
 
-const float4* acquire_bg_plate(mcrt_scene* s, const RenderParams& p, bool capturing, bool count_sighting) {
-    const int mode = bg_plate_mode();
+void free_unused_plates() {  // mcrt_trim
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    for (auto& by_device : g_plates)
+        for (size_t dev = 0; dev < by_device.size(); ++dev) {
+            DevicePlates& d = by_device[dev];
+            (void)hipSetDevice(static_cast<int>(dev));
+            std::vector<Plate*> kept;
+            for (Plate* e : d.entries) {
+                if (e->users > 0) {
+                    kept.push_back(e);
+                    continue;
+                }
+                free_plate(d, e);
+                delete e;
+            }
+            d.entries.swap(kept);
+            if (d.stream) (void)hipStreamDestroy(d.stream);  // idle: every build waited for it under this mutex
+            d.stream = nullptr;
+        }
+}
+
+// the device's plate of `kind` for the frame prepared as `p`, or nullptr
+const void* acquire_plate(int kind, mcrt_scene* s, const RenderParams& p, bool capturing, bool count_sighting) {
+    const int mode = plate_mode(kind);
+    const PlateKindInfo& info = g_kinds[kind];
     // (a caller's graph outlives this call in ways the library cannot see: a render recorded into it takes no plate)
-    if (mode == 0 || capturing || !bg_plate_eligible(p)) return nullptr;
-    const BgPlateKey key = bg_plate_key_of(p);
-    for (size_t i = 0; i < s->plates.size(); ++i)
-        if (same_key(s->plates[i]->key, key)) {  // held already: no lock, the entry cannot change under a holder
-            BgPlate* e = s->plates[i];
-            s->plates.erase(s->plates.begin() + static_cast<long>(i));
-            s->plates.push_back(e);
+    if (mode == 0 || capturing || !info.eligible(p)) return nullptr;
+    const PlateKey key = info.key_of(p);
+    std::vector<Plate*>& held = s->plates[kind];
+    for (size_t i = 0; i < held.size(); ++i)
+        if (same_key(held[i]->key, key)) {  // held already: no lock, the entry cannot change under a holder
+            Plate* e = held[i];
+            held.erase(held.begin() + static_cast<long>(i));
+            held.push_back(e);
             return e->ptr;
         }
-    const size_t bytes = bg_plate_bytes(p.cfg);
-    if (bytes == 0 || bytes > kBgPlateBudget) return nullptr;
-    BgPlate* got = nullptr;
-    {
+    const size_t bytes = info.bytes(p);
+    if (bytes == 0 || bytes > info.budget) return nullptr;
+    Plate* got = nullptr;
+    // A shell may hold as many plates as the device keeps of a kind: when the store has no room because every built plate is
+    // held, the shell lets go of the one it has held longest and asks once more (a handle that goes through many
+    // configurations moves on with them instead of keeping the plates of its first ones for good).
+    for (int attempt = 0; attempt < 2 && !got; ++attempt) {
+        if (attempt == 1) {
+            if (held.empty()) break;
+            drop_held_plate(s, kind);
+        }
+        bool room = true;
         std::lock_guard<std::mutex> lock(g_plate_mutex);
-        if (g_plates.size() <= static_cast<size_t>(s->device)) g_plates.resize(static_cast<size_t>(s->device) + 1);
-        DevicePlates& d = g_plates[static_cast<size_t>(s->device)];
+        std::vector<DevicePlates>& by_device = g_plates[kind];
+        if (by_device.size() <= static_cast<size_t>(s->device)) by_device.resize(static_cast<size_t>(s->device) + 1);
+        DevicePlates& d = by_device[static_cast<size_t>(s->device)];
         ++d.clock;
-        BgPlate* e = nullptr;
-        for (BgPlate* q : d.entries)
+        Plate* e = nullptr;
+        for (Plate* q : d.entries)
             if (same_key(q->key, key)) e = q;
         if (!e) {
-            if (d.entries.size() >= static_cast<size_t>(kBgPlateKeys)) {  // the least recently used entry nobody holds becomes this key's
-                for (BgPlate* q : d.entries)
+            if (d.entries.size() >= static_cast<size_t>(kPlateKeys)) {  // the least recently used entry nobody holds becomes this key's
+                for (Plate* q : d.entries)
                     if (q->users == 0 && (!e || q->last_use < e->last_use)) e = q;
                 if (!e) return nullptr;
                 free_plate(d, e);
-                *e = BgPlate{};
+                *e = Plate{};
             } else {
-                e = new BgPlate();
+                e = new Plate();
                 d.entries.push_back(e);
             }
             e->key = key;
         }
         e->last_use = d.clock;
         if (!e->ptr) {
-            if (count_sighting) ++e->sightings;
-            if (e->sightings >= (mode == 2 ? 1 : 2)) build_plate(d, e, p, bytes);
+            if (count_sighting && attempt == 0) ++e->sightings;
+            if (e->sightings >= (mode == 2 ? 1 : 2)) room = build_plate(info, d, e, p, bytes);
         }
         if (e->ptr) {
             ++e->users;
             got = e;
         }
+        if (room) break;
     }
     if (!got) return nullptr;
-    if (s->plates.size() >= kHeldPlates) drop_held_plate(s);
-    s->plates.push_back(got);
+    if (held.size() >= kHeldPlates) drop_held_plate(s, kind);
+    held.push_back(got);
     return got->ptr;
+}
+
+int plate_info(int kind, int device, int* plates, size_t* bytes, int* builds) {
+    std::lock_guard<std::mutex> lock(g_plate_mutex);
+    const std::vector<DevicePlates>& by_device = g_plates[kind];
+    const DevicePlates* d = (device >= 0 && static_cast<size_t>(device) < by_device.size()) ? &by_device[static_cast<size_t>(device)] : nullptr;
+    if (plates) *plates = d ? d->built : 0;
+    if (bytes) *bytes = d ? d->bytes : 0;
+    if (builds) *builds = d ? d->builds : 0;
+    return MCRT_OK;
+}
+}  // namespace
+
+void acquire_plates(mcrt_scene* s, RenderParams* p, int n, bool capturing, bool count_sighting) {
+    const float4* pixels = static_cast<const float4*>(acquire_plate(kPlatePixels, s, p[0], capturing, count_sighting));
+    const float* draws = static_cast<const float*>(acquire_plate(kPlateDraws, s, p[0], capturing, count_sighting));
+    for (int i = 0; i < n; ++i) p[i].bg_plate = pixels, p[i].draw_plate = draws;
 }
 
 // keeps `s` for reuse unless it is large — MCRT_POOL_MB, by default a twelfth of the device's memory (24 GB of the
@@ -380,7 +448,7 @@ void destroy_scene_now(mcrt_scene* s) {
     unregister_live(s);  // before its events go
     if (s->holds_seed_table) g_window_tables.release(s->device);
     if (s->holds_full_table) g_full_tables.release(s->device);
-    release_bg_plates(s);
+    release_plates(s);
     s->blob.release();  // the other buffers are released by their destructors below
     for (auto& ln : s->lanes) {
         if (ln.stream) (void)hipStreamSynchronize(ln.stream);
@@ -486,16 +554,10 @@ void mcrt_trim(void) {
     }
     g_full_tables.free_unused();
     g_window_tables.free_unused();
-    free_unused_bg_plates();
+    free_unused_plates();
 }
 
-int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds) {
-    std::lock_guard<std::mutex> lock(g_plate_mutex);
-    const DevicePlates* d = (device >= 0 && static_cast<size_t>(device) < g_plates.size()) ? &g_plates[static_cast<size_t>(device)] : nullptr;
-    if (plates) *plates = d ? d->built : 0;
-    if (bytes) *bytes = d ? d->bytes : 0;
-    if (builds) *builds = d ? d->builds : 0;
-    return MCRT_OK;
-}
+int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds) { return plate_info(kPlatePixels, device, plates, bytes, builds); }
+int mcrt_draw_plate_info(int device, int* plates, size_t* bytes, int* builds) { return plate_info(kPlateDraws, device, plates, bytes, builds); }
 
 }  // extern "C"

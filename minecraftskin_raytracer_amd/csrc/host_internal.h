@@ -82,15 +82,17 @@ void for_each_buffer(LaneT& ln, F f) {  // every workspace buffer of a lane
     for (auto& q : ln.queues) f(q);
 }
 
-// One background plate of a device (kernels.h) and the frame settings its pixels are a function of — nothing else enters
-// (RngKey above says the same of the tile seeds).  Entries live in the per-device store further down.
-struct BgPlateKey {
+// One plate of a device (kernels.h) — of a kind: the finished pixels of the gradient background tiles, or every tile's
+// draws — and the frame settings its contents are a function of; nothing else enters (RngKey above says the same of the tile
+// seeds).  A draw plate's key is its first five fields, the others stay zero.  Entries live in the per-device stores further down.
+enum PlateKind { kPlatePixels = 0, kPlateDraws = 1, kPlateKinds = 2 };
+struct PlateKey {
     int width, height, tile_size, spp, draws_per_sample, gradient_bg, div_frame;
     float gradient_scale, bg_center[3], bg_edge[3];
 };
-struct BgPlate {
-    BgPlateKey key;
-    float4* ptr = nullptr;  // NULL: the key has been sighted, no plate built (yet)
+struct Plate {
+    PlateKey key;
+    void* ptr = nullptr;    // NULL: the key has been sighted, no plate built (yet)
     size_t bytes = 0;
     int users = 0;          // scene shells (live or pooled) that hold the pointer — in prepared parameters, recorded launch graphs, launches in flight
     int sightings = 0;      // render calls with this key while it had no plate (negative after a failed build: see build_plate)
@@ -145,9 +147,9 @@ struct mcrt_scene {
     bool holds_seed_table = false;
     const uint32_t* seed_table_full = nullptr;  // the device's table for every 32-bit seed (ambient occlusion), or NULL
     bool holds_full_table = false, full_table_tried = false;
-    // background plates this shell holds a `users` count of, least recently used first: its recorded launch graphs and its
-    // launches in flight may read them, so one is let go of only behind a device synchronisation (acquire_bg_plate)
-    std::vector<BgPlate*> plates;
+    // plates this shell holds a `users` count of, by kind, least recently used first: its recorded launch graphs and its
+    // launches in flight may read them, so one is let go of only behind a device synchronisation (acquire_plates)
+    std::vector<Plate*> plates[kPlateKinds];
 };
 
 namespace mcrt_host {
@@ -191,8 +193,9 @@ bool device_shared(const mcrt_scene* s);  // another handle's frame is in flight
 const uint32_t* acquire_seed_table(int device);
 // the first ambient-occlusion render of a shell takes the device's table for every 32-bit seed (never built while `stream` is capturing)
 void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream);
-// the device's background plate for the frame prepared as `p`, or nullptr
-const float4* acquire_bg_plate(mcrt_scene* s, const mcrt::RenderParams& p, bool capturing, bool count_sighting);
+// the device's background plate and draw plate for the frame prepared as p[0] — each or nullptr, both kinds under one sighting
+// rule in this one call — into bg_plate and draw_plate of p[0..n) (the lanes of one render read the same plates)
+void acquire_plates(mcrt_scene* s, mcrt::RenderParams* p, int n, bool capturing, bool count_sighting);
 size_t pool_limit(int device);
 bool pool_scene(mcrt_scene* s);             // false: not kept, the caller destroys it
 mcrt_scene* take_pooled_scene(int device);  // device < 0: any

@@ -34,6 +34,7 @@ struct WaveSpace {
     uint32_t* unit_hits;    // per unit: its primary hits (their records sit at the front of the unit's slot range)
     unsigned long long* tile_mask;  // per owned tile: meshes whose screen bound touches it
     float* tile_draws;      // [touched tiles (bg_in_plan) or all tiles of the batch][draws_stride] a tile's mt19937 draws, as uniform floats
+                            // (not written and not read when the frame has a draw plate: RenderParams::draw_plate)
     uint32_t draws_stride;  // tile slots * draws_per_sample
     uint32_t unit_cap;      // capacity of `units`
     uint32_t tile_cap;      // tiles of a batch that may be touched by meshes (host-side superset of the device's culling):
@@ -97,6 +98,8 @@ struct RenderParams {
     uint32_t* tile_rng;    // owned_tiles x stream_parts x 624 mt19937 state words (NULL when no tile draws)
     const float4* bg_plate;  // the device's background plate of this frame configuration (below), or NULL: `plan_tiles` computes
                            //    the gradient background tiles itself
+    const float* draw_plate;  // the device's draw plate of this frame configuration (below), or NULL: `plan_tiles` makes the touched
+                           //    tiles' draws itself, into ws.tile_draws
     WaveSpace ws;
     int draws_per_sample;  // 0, 2 or 4
     int stream_waves;      // waves per tile in `plan_tiles` (1, 2 or 4, <= stream_parts; choose_grids)
@@ -155,6 +158,25 @@ size_t bg_plate_rng_bytes(const RenderParams& p);
 // Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
 // `tile_rng` is scratch of bg_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
 hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream);
+
+// ---- draw plate: the mt19937 draws of EVERY tile of a frame configuration, as uniform floats — what `plan_tiles` writes
+// into a touched tile's slot of ws.tile_draws.  A tile's draws are a function of the frame's size, the tile size, the
+// samples per pixel and the draws per sample alone (the engine is seeded tile.y * width + tile.x): scene, pose, camera,
+// light, bounces, background, shard, layout and lanes do not enter.  [frame tile index (TileGeom::frame_tile)][draws_stride]
+// floats, a clipped tile's shorter stream at the front of its slot.  Built once per device and key by
+// launch_fill_draw_plate with the routine `plan_tiles` runs (tile_stream_wave), immutable afterwards: with a plate
+// `plan_tiles` twists nothing for a touched tile, and `primary` and `resolve` read the tile's draws from the plate.
+
+// whether a frame prepared as `p` can take a draw plate: jitter or lens draws, the touched-tiles layout (bg_in_plan), at
+// most 24 draws per pixel (the streams of 64 spp frames are gigabytes), a whole-frame entry point
+bool draw_plate_eligible(const RenderParams& p);
+// bytes of the plate of p's frame (p.ws.draws_stride set: plan_workspace); 0 when the frame cannot have one
+size_t draw_plate_bytes(const RenderParams& p);
+// bytes of the scratch launch_fill_draw_plate needs: the engine states of every tile of the frame
+size_t draw_plate_rng_bytes(const RenderParams& p);
+// Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
+// `tile_rng` is scratch of draw_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
+hipError_t launch_fill_draw_plate(const RenderParams& p, float* plate, uint32_t* tile_rng, hipStream_t stream);
 
 // Sizes of the workspace arrays for p.cfg / p.shard; fills p.parts_per_tile, p.rows_per_batch and
 // p.ws.cap / p.ws.stack_stride.  budget_bytes bounds the per-batch workspace (a batch is never

@@ -224,6 +224,18 @@ int launch_lanes(mcrt_scene* s, const RenderParams* p, int n_lanes, hipStream_t 
     return MCRT_OK;
 }
 
+// The frame's plates (device_stores.cpp), both kinds in one call, into the n parameter sets of one render.  Where nothing
+// twists any more — the touched tiles' draws come from the draw plate, and the background tiles are copied from their plate
+// or need no draws (transparent, one colour, one centred sample) — `plan_tiles` reads no engine state: the render then
+// carries no tile_rng, and its seeding and advancing launches are never made.
+void take_plates(mcrt_scene* s, RenderParams* p, int n, bool capturing, bool count_sighting) {
+    acquire_plates(s, p, n, capturing, count_sighting);
+    const RenderParams& a = p[0];
+    const bool background_twists = a.background == MCRT_BACKGROUND_REFERENCE && a.cfg.gradient_bg != 0 && a.cfg.samples_per_pixel > 1 && !a.bg_plate;
+    if (a.draw_plate && !background_twists)
+        for (int i = 0; i < n; ++i) p[i].tile_rng = nullptr;
+}
+
 RngKey rng_key_of(const RenderParams& p) {
     RngKey k;
     k.ptr = p.tile_rng;
@@ -466,11 +478,10 @@ int enqueue_render(mcrt_scene* s, const mcrt_config* cfg, int first, int step, i
         for (int li = 0; li < n_lanes; ++li) choose_grids(p[li], shared, company);
     }
     if (capturing && groups) return fail(MCRT_ERR_INVALID, "row-group events cannot be recorded into a caller's graph");
-    {  // the gradient background tiles: copied from the device's plate of this frame configuration when it has one (built, if
-       // at all, before anything of this render is enqueued; every lane and shard reads the same plate)
-        const float4* plate = acquire_bg_plate(s, p[0], capturing, true);
-        for (int li = 0; li < n_lanes; ++li) p[li].bg_plate = plate;
-    }
+    // the gradient background tiles are copied from the device's background plate of this frame configuration, the touched tiles'
+    // draws read from its draw plate, when it has them (built, if at all, before anything of this render is enqueued; every
+    // lane and shard reads the same plates)
+    take_plates(s, p, n_lanes, capturing, true);
     if (const int rc = begin_handle_render(s, n_lanes, stream, capturing); rc != MCRT_OK) return rc;
     // the tiles' seeded mt19937 states: kept across renders, re-made (on the caller's stream, ahead of
     // the lanes' fork) only when the frame width, the tile size or the shard changed
@@ -574,8 +585,8 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
         const int rc = prepare(s, 0, 1, cfg, 0, 1, MCRT_LAYOUT_FRAME, f, b, p[static_cast<size_t>(i)]);
         if (rc != MCRT_OK) return rc;
         if (batch_eligible(p[static_cast<size_t>(i)])) {
-            // the device's background plate of the config, through the handle like a single render's; the batch is ONE sighting of its key
-            p[static_cast<size_t>(i)].bg_plate = acquire_bg_plate(s, p[static_cast<size_t>(i)], false, !plate_sighted);
+            // the device's plates of the config, through the handle like a single render's; the batch is ONE sighting of their keys
+            take_plates(s, &p[static_cast<size_t>(i)], 1, false, !plate_sighted);
             plate_sighted = true;
             const int mode = p[static_cast<size_t>(i)].background == MCRT_BACKGROUND_TRANSPARENT ? 1 : 0;
             in_batch[mode].push_back(s);

@@ -106,7 +106,7 @@ struct FrameDiv {
 struct TileGeom {
     int x, y, w, h;
     int owned_row;  // index of this tile's row among the rows this launch owns
-    int frame_tile;  // row-major index of the tile in the whole frame (its slot in a background plate, kernels.h)
+    int frame_tile;  // row-major index of the tile in the whole frame (its slot in a background or draw plate, kernels.h)
 };
 
 __device__ __forceinline__ TileGeom tile_of(const RenderParams& p, int owned_tile) {
@@ -675,8 +675,8 @@ __device__ __forceinline__ void plan_tiles_body(const uint8_t* __restrict__ scen
         if (p.draws_per_sample > 0 && !(mask == 0ull && constant_background(sc, p, tg, unused)))
             tile_stream_wave(sc, tile_rng, tile_draws + static_cast<size_t>(t) * stride, nullptr, nullptr, p, tg, tile, part * per_wave, per_wave, s_state[wave], lane,
                              /*jitter_only=*/mask == 0ull && p.draws_per_sample == 4);
-    } else if (mask != 0ull) {  // a tile meshes can touch: its draws, at its touched-tile number
-        if (p.draws_per_sample > 0 && ord != ~0u)
+    } else if (mask != 0ull) {  // a tile meshes can touch: its draws, at its touched-tile number — unless the device's draw plate holds them
+        if (p.draws_per_sample > 0 && ord != ~0u && !p.draw_plate)
             tile_stream_wave(sc, tile_rng, tile_draws + static_cast<size_t>(ord) * stride, nullptr, nullptr, p, tg, tile, part * per_wave, per_wave, s_state[wave], lane);
     } else if (p.background == MCRT_BACKGROUND_TRANSPARENT) {  // no sample of the tile can hit: (0,0,0,0), no draws (bg_in_plan is 1)
         fill_tile(p, tg, out_frame, out8, make_float4(0.0f, 0.0f, 0.0f, 0.0f), static_cast<unsigned>(part * 64 + lane), static_cast<unsigned>(parts) * 64u);
@@ -716,6 +716,20 @@ __global__ __launch_bounds__(64 * kStreamWaves) void fill_bg_plate_kernel(const 
     float4 unused;
     if (constant_background(sc, p, tg, unused)) return;
     tile_stream_wave<true>(sc, p.tile_rng, nullptr, plate, nullptr, p, tg, tile, part, 1, s_state[wave], lane);
+}
+
+// Fills a draw plate (kernels.h): the draws of every tile of the frame, by `plan_tiles`' own routine for a touched tile, into
+// the tile's slot of the plate.  p: a whole-frame shard, one wave per stream part; p.scene is not read beyond its header.
+__global__ __launch_bounds__(64 * kStreamWaves) void fill_draw_plate_kernel(const RenderParams p, float* __restrict__ plate, const int n_tiles) {
+    __shared__ __align__(16) uint32_t s_state[kStreamWaves][2 * 624];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int parts = p.stream_parts;  // 1, 2 or 4: divides kStreamWaves
+    const int slot = static_cast<int>(blockIdx.x) * kStreamWaves + wave;
+    const int tile = slot / parts, part = slot - tile * parts;
+    if (tile >= n_tiles) return;  // wave-uniform; no workgroup barrier in this kernel
+    const TileGeom tg = tile_of(p, tile);
+    const SceneView sc = view_of(p.scene);  // (a stream with a destination renders nothing: the view is not used)
+    tile_stream_wave(sc, p.tile_rng, plate + static_cast<size_t>(tg.frame_tile) * p.ws.draws_stride, nullptr, nullptr, p, tg, tile, part, 1, s_state[wave], lane);
 }
 
 // The engine states at the starts of a tile's parts 1 .. parts-1 (tile_stream_wave): one wave per tile twists the seeded
@@ -813,8 +827,10 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
         const uint32_t slot_base = ud.w;
         const TileGeom tg = tile_of(p, tile);
         const unsigned long long mesh_mask = ws.tile_mask[tile];
-        // the tile's draws: at its touched-tile number, or (all tiles' streams in HBM) at its index in the batch
-        const float* draws = tile_draws + static_cast<size_t>(p.bg_in_plan ? slot_base / ws.tile_slots : static_cast<uint32_t>(tile - tile_base)) * stride;
+        // the tile's draws: in the draw plate (tile_draws is then the plate) at its index in the frame; else at its touched-tile
+        // number, or (all tiles' streams in HBM) at its index in the batch
+        const float* draws = tile_draws + static_cast<size_t>(p.draw_plate ? static_cast<uint32_t>(tg.frame_tile)
+                                                              : p.bg_in_plan ? slot_base / ws.tile_slots : static_cast<uint32_t>(tile - tile_base)) * stride;
         const unsigned n_samples = (pp1 - pp0) * static_cast<unsigned>(spp);
 
         uint32_t unit_hits = 0;  // hits so far: they occupy slots slot_base .. slot_base + unit_hits
@@ -1828,7 +1844,8 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
         const TileGeom tg = tile_of(p, static_cast<int>(d.x));
         const uint32_t pp0 = d.y, pp1 = d.z;
         // the tile's draws: at its touched-tile number, or (all tiles' streams in HBM) at its index in the batch — as in `primary`
-        const float* draws = tile_draws + static_cast<size_t>(p.bg_in_plan ? d.w / ws.tile_slots : static_cast<uint32_t>(static_cast<int>(d.x) - tile_base)) * ws.draws_stride;
+        const float* draws = tile_draws + static_cast<size_t>(p.draw_plate ? static_cast<uint32_t>(tg.frame_tile)
+                                                              : p.bg_in_plan ? d.w / ws.tile_slots : static_cast<uint32_t>(static_cast<int>(d.x) - tile_base)) * ws.draws_stride;
         if (chunk_px == 0u) {
             for (uint32_t i = pp0 + threadIdx.x; i < pp1; i += kBlock) {
                 float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1926,7 +1943,7 @@ __global__ __launch_bounds__(kBlock, MCRT_BG_WAVES) void background_batch_kernel
 template <int kView>
 __global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_batch_kernel(ParamTable table, const int n_tiles) {
     const RenderParams& p = frame_params(table);
-    primary_body<kView>(p.scene, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0, n_tiles);
+    primary_body<kView>(p.scene, p.draw_plate ? p.draw_plate : p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0, n_tiles);
 }
 template <int kView>
 __global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_batch_kernel(ParamTable table) {
@@ -1940,7 +1957,7 @@ __global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_batch_kernel(Param
 }
 __global__ __launch_bounds__(kBlock) void resolve_batch_kernel(ParamTable table) {
     const RenderParams& p = frame_params(table);
-    resolve_body<false>(p.scene, p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
+    resolve_body<false>(p.scene, p.draw_plate ? p.draw_plate : p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
 }
 __global__ __launch_bounds__(kBlock) void resolve_transparent_batch_kernel(ParamTable table) {
     const RenderParams& p = frame_params(table);
@@ -2499,6 +2516,7 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
         const int tile_base = r0 * p.shard.tiles_x;
         const int batch_tiles = rows * p.shard.tiles_x;
         hipError_t e = hipSuccess;  // (no counter memset: the counters run on, `resolve` moves their base)
+        const float* draws = p.draw_plate ? p.draw_plate : p.ws.tile_draws;  // what `primary` and `resolve` read the touched tiles' draws from
         hipLaunchKernelGGL(plan_tiles_kernel, dim3((batch_tiles * (p.stream_waves > 0 ? p.stream_waves : 1) + kStreamWaves - 1) / kStreamWaves), dim3(64 * kStreamWaves), 0, stream,
                            p.scene, p.tile_rng, p.ws.tile_draws, out, out8, p, tile_base, batch_tiles);
         if (marks && marks->after_plan && r0 == 0) {
@@ -2510,20 +2528,20 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
         const int primary_grid = p.grid_primary > 0 ? p.grid_primary : kPrimaryGrid, resolve_grid = p.grid_resolve > 0 ? p.grid_resolve : kResolveGrid;
         const int pgrid = batch_tiles * p.parts_per_tile < primary_grid ? batch_tiles * p.parts_per_tile : primary_grid;
         if (p.scene_in_lds && !p.scene_posed) {
-            hipLaunchKernelGGL(primary_kernel<kViewLdsUnposed>, dim3(pgrid), dim3(kBlock), dyn, stream, p.scene, p.ws.tile_draws, out, out8, p, tile_base, batch_tiles);
+            hipLaunchKernelGGL(primary_kernel<kViewLdsUnposed>, dim3(pgrid), dim3(kBlock), dyn, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
             launch_levels<kViewLdsUnposed>(p, stream, dyn);
         } else if (p.scene_in_lds) {
-            hipLaunchKernelGGL(primary_kernel<kViewLds>, dim3(pgrid), dim3(kBlock), dyn, stream, p.scene, p.ws.tile_draws, out, out8, p, tile_base, batch_tiles);
+            hipLaunchKernelGGL(primary_kernel<kViewLds>, dim3(pgrid), dim3(kBlock), dyn, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
             launch_levels<kViewLds>(p, stream, dyn);
         } else {
-            hipLaunchKernelGGL(primary_kernel<kViewHbm>, dim3(pgrid), dim3(kBlock), 0, stream, p.scene, p.ws.tile_draws, out, out8, p, tile_base, batch_tiles);
+            hipLaunchKernelGGL(primary_kernel<kViewHbm>, dim3(pgrid), dim3(kBlock), 0, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
             launch_levels<kViewHbm>(p, stream, 0);
         }
         const int rgrid = batch_tiles * p.parts_per_tile < resolve_grid ? batch_tiles * p.parts_per_tile : resolve_grid;
         if (p.background == MCRT_BACKGROUND_TRANSPARENT)
             hipLaunchKernelGGL(resolve_transparent_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, out, out8, p, tile_base);
         else
-            hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, p.ws.tile_draws, out, out8, p, tile_base);
+            hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, draws, out, out8, p, tile_base);
         const int batch = r0 / p.rows_per_batch;
         if (marks && batch < marks->n_batch_done) {
             e = hipEventRecord(marks->batch_done[batch], stream);
@@ -2568,6 +2586,33 @@ hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* 
     hipError_t e = launch_seed_tiles(q, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fill_bg_plate_kernel, dim3((n * q.stream_parts + kStreamWaves - 1) / kStreamWaves), dim3(64 * kStreamWaves), 0, stream, q, plate, n);
+    return hipGetLastError();
+}
+
+// ---- draw plate (kernels.h) -----------------------------------------------------------------------
+bool draw_plate_eligible(const RenderParams& p) {
+    const int spp = p.cfg.samples_per_pixel > 1 ? p.cfg.samples_per_pixel : 1;
+    return p.bg_in_plan == 1 && p.draws_per_sample > 0 && p.rect_w <= 0 && spp * p.draws_per_sample <= 24 && p.ws.draws_stride > 0;
+}
+size_t draw_plate_bytes(const RenderParams& p) {
+    const mcrt_config& cfg = p.cfg;
+    if (cfg.width <= 0 || cfg.height <= 0 || cfg.tile_size <= 0 || p.ws.draws_stride == 0) return 0;
+    const size_t ts = static_cast<size_t>(cfg.tile_size);
+    const size_t tiles = ((static_cast<size_t>(cfg.width) + ts - 1) / ts) * ((static_cast<size_t>(cfg.height) + ts - 1) / ts);
+    if (tiles > 0x7fffffffull) return 0;  // (TileGeom::frame_tile is an int)
+    return tiles * static_cast<size_t>(p.ws.draws_stride) * sizeof(float);
+}
+size_t draw_plate_rng_bytes(const RenderParams& p) { return bg_plate_rng_bytes(p); }  // the same whole-frame shard's engine states
+hipError_t launch_fill_draw_plate(const RenderParams& p, float* plate, uint32_t* tile_rng, hipStream_t stream) {
+    if (!draw_plate_eligible(p) || !plate || !tile_rng || draw_plate_bytes(p) == 0) return hipErrorInvalidValue;
+    RenderParams q = bg_plate_fill_params(p);
+    q.draw_plate = nullptr;
+    q.tile_rng = tile_rng;
+    const int n = owned_tiles(q);
+    if (n <= 0) return hipErrorInvalidValue;
+    hipError_t e = launch_seed_tiles(q, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fill_draw_plate_kernel, dim3((n * q.stream_parts + kStreamWaves - 1) / kStreamWaves), dim3(64 * kStreamWaves), 0, stream, q, plate, n);
     return hipGetLastError();
 }
 
