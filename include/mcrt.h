@@ -373,6 +373,56 @@ int mcrt_scene_pick(mcrt_scene* scene, const mcrt_config* cfg, const int32_t* xy
  * has fewer meshes than these tables.)  MCRT_ERR_INVALID for an argument out of range for that skin kind. */
 int mcrt_skin_texel(int skin_height, int mesh, int face_slot, int tx, int ty, int* skin_x, int* skin_y);
 
+/* ---- ground shadow: the figure's soft shadow on a floor plane, as a layer of its own --------------------------------------
+ * The reference's scene has no floor; this pass answers, per pixel, how much of the light reaches the point of the plane
+ * y = ground_y under that pixel — what a compositor puts under the MCRT_BACKGROUND_TRANSPARENT figure.  The ray is the geometry
+ * layers': u = (px + 0.5f) / width, v = (py + 0.5f) / height, Camera::generateRay(u, v, (float)width / (float)height), origin o
+ * and direction d.  The plane's normal is N = (0, 1, 0) from either side.  All arithmetic float32, uncontracted:
+ *   t = (ground_y - o.y) / d.y                      the pixel REACHES the plane iff d.y != 0 && t > 0 && t <= FLT_MAX
+ *   P = (o.x + d.x * t, ground_y, o.z + d.z * t)
+ *   seed = (unsigned)(P.x * 12345.0f + P.y * 67890.0f + P.z * 11111.0f)      summed left to right, the reference's cast
+ *                                                   (raytracer.cpp:110-112 at depth 0)
+ *   S = shadow_samples when soft_shadows && shadow_samples > 1, else 1
+ *   visibility = computeSoftShadow(P, N, scene.light, scene, S, seed)        (shading.cpp:28-60; at S = 1 or with a light
+ *                                                   radius below 1e-4 the one isInShadow ray)
+ * The figure in front of the plane plays no part: the shadow is computed for every pixel that reaches the plane (an edge pixel
+ * of the transparent figure shows the ground through it).  Planes of width * height pixels, row-major:
+ *   visibility  1 float   the value above (k / S)                                  not reached: 1.0f
+ *   distance    1 float   t                                                        not reached: FLT_MAX
+ *   matte       1 uint8   (uint8_t)(clamp(1.0f - visibility, 0, 1) * 255.0f + 0.5f)   not reached: 0
+ * matte is the alpha of a black shadow image, quantised as mcrt_quantize_rgba8 quantises a channel: page * (1 - matte / 255)
+ * under the straight-alpha figure.  Of mcrt_config the pass reads width, height, tile_size (the granularity of the culling,
+ * never a value), soft_shadows and shadow_samples; everything else and the handle's background mode are IGNORED.  The values
+ * are bit-identical to the reference's computeSoftShadow at those points.
+ * shadow_samples is limited to 113 when soft_shadows is on (MCRT_ERR_INVALID above): the pass draws a pixel's light samples
+ * from the truncated mt19937 form, which yields the first 227 draws of an engine and keeps no 624-word state per lane.
+ * The rules of the geometry layers hold: whole frames only; asynchronous on `stream`, not into a graph being recorded; no
+ * workspace, no counters and none of the handle's events, so the pass may run beside the handle's render on another stream;
+ * mcrt_scene_destroy and mcrt_scene_check wait for it; a handle may be listed more than once in a batch, with different
+ * ground_y; the pixels between frames are not written.
+ * MCRT_ERR_INVALID before any device work: a NULL config, handle, entry, ground_y array or planes struct, all three planes
+ * NULL, n_frames < 0, a stride below width * height, handles on different devices, a ground_y that is not finite,
+ * soft_shadows && shadow_samples > 113.  Zero-size frames and n_frames = 0: MCRT_OK, nothing written. */
+typedef struct mcrt_ground {
+    float* visibility; /* any may be NULL (that plane is not produced), not all */
+    float* distance;
+    uint8_t* matte;
+} mcrt_ground;
+/* resident scene, device pointers, asynchronous on `stream` */
+int mcrt_render_ground_device(mcrt_scene* scene, const mcrt_config* cfg, float ground_y, const mcrt_ground* d_out, void* stream);
+/* n_frames scenes of one config in one launch; ground_y: n_frames heights in HOST memory (read before the call returns); frame i
+ * at each plane + i * frame_stride_pixels pixels */
+int mcrt_render_ground_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y,
+                                    const mcrt_ground* d_out, size_t frame_stride_pixels, void* stream);
+/* one-shot host form: host pointers, rendered on `device` with a pooled handle like mcrt_render */
+int mcrt_render_ground(const mcrt_scene_desc* scene, const mcrt_config* cfg, float ground_y, const mcrt_ground* out, int device);
+/* The floor of a scene (host only): the smallest y of all tri_vertices — the posed, world-space boxes, so a lifted leg counts.
+ * At pose 0 that is 0.0 for the built-in default scene and for a 64x32 skin, and -0.5 for a 64x64 skin: its outer leg layers
+ * are boxes 0.5 larger than the legs on every side, and they are vertices like any other.  A plane at that floor lies 0.5
+ * below the soles of such a figure, so the shadow does not touch the feet; pass the height of the soles (0.0 for the builder's
+ * standing poses) for a contact shadow.  A scene without a vertex (or a NULL argument) → MCRT_ERR_INVALID. */
+int mcrt_scene_floor(const mcrt_scene_desc* scene, float* y);
+
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);
 

@@ -21,6 +21,8 @@ from .api import (  # noqa: F401
     quantize_rgba8_device,
     render_batch_device,
     render_layers_batch_device,
+    render_ground_batch_device,
+    scene_floor,
     skin_texel,
     render_png,
     trim,
@@ -32,4 +34,5 @@ __all__ = [
     "TileRenderer", "device_count", "flatten", "getBuiltinPoses", "probe_detmath", "probe_detmath_range",
     "probe_mt_uniform", "quantize_rgba8", "quantize_rgba8_device", "unpack_rows_device", "ImageWriter", "render_png", "assemble_frame_device", "trim",
     "render_batch_device", "last_batch_info", "bg_plate_info", "draw_plate_info", "render_layers_batch_device", "skin_texel",
+    "render_ground_batch_device", "scene_floor",
 ]

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_bg_plate_info", "mcrt_draw_plate_info",
     "mcrt_render_layers_device", "mcrt_render_layers_batch_device", "mcrt_render_layers", "mcrt_render_layers_batch",
     "mcrt_scene_pick", "mcrt_skin_texel",
+    "mcrt_render_ground_device", "mcrt_render_ground_batch_device", "mcrt_render_ground", "mcrt_scene_floor",
 ]
 
 
@@ -47,6 +48,7 @@ def load():
     f_p = abi.c_float_p
     vp = C.c_void_p
     layers_p = C.POINTER(abi.McrtLayers)
+    ground_p = C.POINTER(abi.McrtGround)
     sig = {
         "mcrt_config_init": (None, [cfg_p]),
         "mcrt_generate_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(abi.McrtTile), C.c_int]),
@@ -73,6 +75,10 @@ def load():
         "mcrt_render_layers_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, layers_p, C.c_size_t, vp]),
         "mcrt_render_layers": (C.c_int, [desc_p, cfg_p, layers_p, C.c_int]),
         "mcrt_render_layers_batch": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, layers_p, C.c_int]),
+        "mcrt_render_ground_device": (C.c_int, [vp, cfg_p, C.c_float, ground_p, vp]),
+        "mcrt_render_ground_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, f_p, ground_p, C.c_size_t, vp]),
+        "mcrt_render_ground": (C.c_int, [desc_p, cfg_p, C.c_float, ground_p, C.c_int]),
+        "mcrt_scene_floor": (C.c_int, [desc_p, f_p]),
         "mcrt_scene_pick": (C.c_int, [vp, cfg_p, abi.c_int32_p, C.c_int, vp]),
         "mcrt_skin_texel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),

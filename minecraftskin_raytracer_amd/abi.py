@@ -167,6 +167,31 @@ def layer_names(layers) -> tuple:
     return tuple(n for n in LAYER_NAMES if n in names)
 
 
+class McrtGround(C.Structure):
+    """mcrt_ground: one pointer per plane of a ground-shadow pass (device or host memory, by entry point); NULL = not wanted."""
+
+    _fields_ = [("visibility", C.c_void_p), ("distance", C.c_void_p), ("matte", C.c_void_p)]
+
+
+GROUND_NAMES = ("visibility", "distance", "matte")
+# per pixel: the dtype of each plane (one component each)
+GROUND_FORMATS = {"visibility": np.float32, "distance": np.float32, "matte": np.uint8}
+GROUND_MAX_SAMPLES = 113  # shadowSamples of a ground pass with softShadows on
+
+
+def ground_names(planes) -> tuple:
+    """The wanted ground planes in the order of ``GROUND_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
+    if isinstance(planes, str):
+        planes = (planes,)
+    names = tuple(planes)
+    for n in names:
+        if not isinstance(n, str) or n not in GROUND_FORMATS:
+            raise ValueError(f"planes must be taken from {GROUND_NAMES}, not {n!r}")
+    if not names:
+        raise ValueError("no plane selected")
+    return tuple(n for n in GROUND_NAMES if n in names)
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 
 SURFACE_DTYPE = np.dtype(

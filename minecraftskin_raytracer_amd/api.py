@@ -285,6 +285,37 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderGround(scene, config: Config, ground: Optional[float] = None, planes=abi.GROUND_NAMES, device: int = 0) -> dict:
+        """The figure's soft shadow on the floor plane y = ``ground`` (mcrt_render_ground; ``None``: the scene's floor,
+        ``scene_floor`` — the lowest vertex, which for a 64x64 skin is the outer leg layer, 0.5 below the soles): a dict of the wanted planes, (H, W) each — ``visibility`` float32, the share of the light's samples
+        that reach the plane's point under the pixel (1 where the pixel's ray misses the plane), ``distance`` float32, the ray
+        parameter of that point (FLT_MAX at a miss), ``matte`` uint8, the quantised ``1 - visibility``: the alpha of a black
+        shadow image to put under the transparent figure.  Of ``config`` only width, height, tileSize, softShadows and
+        shadowSamples (at most 113 with softShadows) matter.  Failures raise ``McrtError``."""
+        out = TileRenderer.renderGroundBatch([scene], config, ground, planes, device)
+        return {k: v[0] for k, v in out.items()}
+
+    @staticmethod
+    def renderGroundBatch(scenes, config: Config, ground=None, planes=abi.GROUND_NAMES, device: int = 0) -> dict:
+        """``renderGround`` for N scenes of one config: the same planes with a leading N.  ``ground``: ``None`` (every scene's
+        own floor), one height for all, or a sequence of N heights.  This host form is a LOOP of ``mcrt_render_ground`` calls —
+        each uploads its scene, launches, downloads and synchronises — and gains nothing from the batched kernel; the batched
+        path is ``render_ground_batch_device`` on resident ``DeviceScene`` handles (one launch per 4096 frames)."""
+        names = abi.ground_names(planes)
+        descs = [_as_desc(s) for s in scenes]
+        n = len(descs)
+        heights = _ground_heights(descs, ground)
+        w, h = max(config.width, 0), max(config.height, 0)
+        out = {k: _empty_ground(k, n, h, w) for k in names}
+        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
+            return out
+        c = config.to_c()
+        for i, d in enumerate(descs):
+            frame = abi.McrtGround(**{k: v[i].ctypes.data for k, v in out.items()})
+            check(load().mcrt_render_ground(d.ptr, C.byref(c), heights[i], C.byref(frame), int(device)))
+        return out
+
+    @staticmethod
     def lastBatchInfo() -> dict:
         """How the last batch call on this thread ran (mcrt_last_batch_info): ``batched_frames`` taken by the batched
         kernels and ``launch_sequences`` enqueued (1 when the whole batch went through them at once)."""
@@ -310,6 +341,42 @@ def _empty_layer(name: str, n: int, h: int, w: int) -> np.ndarray:
     elif name == "id":
         a[...] = (-1, 0, -1, -1)
     return a
+
+
+def _empty_ground(name: str, n: int, h: int, w: int) -> np.ndarray:
+    """One ground plane for n frames, holding the constants of a pixel that misses the plane."""
+    a = np.zeros((n, h, w), abi.GROUND_FORMATS[name])
+    if name == "visibility":
+        a[...] = 1.0
+    elif name == "distance":
+        a[...] = np.finfo(np.float32).max
+    return a
+
+
+def scene_floor(scene) -> float:
+    """The smallest y of the scene's (posed, world-space) box vertices (mcrt_scene_floor).  At pose 0: 0.0 for the built-in
+    default scene and a 64x32 skin, -0.5 for a 64x64 skin, whose outer leg layers are boxes 0.5 larger than the legs — a plane
+    there lies 0.5 below the soles; pass ``ground=0.0`` to ``renderGround`` for a shadow that touches the feet of a standing
+    figure.  A scene without a vertex raises ``McrtError``."""
+    y = C.c_float()
+    check(load().mcrt_scene_floor(_as_desc(scene).ptr, C.byref(y)))
+    return float(y.value)
+
+
+def _ground_heights(descs, ground) -> List[float]:
+    """One finite height per scene from ``None`` (its floor), a number, or a sequence of len(descs) numbers."""
+    if ground is None:
+        heights = [scene_floor(d) for d in descs]
+    elif isinstance(ground, (int, float, np.integer, np.floating)):
+        heights = [float(ground)] * len(descs)
+    else:
+        heights = [float(g) for g in ground]
+        if len(heights) != len(descs):
+            raise ValueError(f"{len(heights)} ground heights for {len(descs)} scenes")
+    for g in heights:
+        if not np.isfinite(np.float32(g)):
+            raise ValueError("ground must be finite")
+    return heights
 
 
 def skin_texel(kind, mesh: int, face: int, tx: int, ty: int) -> Tuple[int, int]:
@@ -446,6 +513,20 @@ class DeviceScene:
         planes = abi.McrtLayers(depth_ptr or None, normal_ptr or None, albedo_ptr or None, id_ptr or None)
         check(load().mcrt_render_layers_device(self._h, C.byref(c), C.byref(planes), C.c_void_p(stream)))
 
+    def render_ground_device(self, config: Config, ground: float, visibility_ptr: int = 0, distance_ptr: int = 0, matte_ptr: int = 0,
+                             stream: int = 0) -> None:
+        """The ground-shadow planes of the frame into device memory (mcrt_render_ground_device): width * height pixels per plane
+        — visibility and distance 4 bytes per pixel, matte 1 — any pointer may be 0, not all.  ``ground``: the plane's height
+        (``scene_floor`` of the description for the figure's own floor).  Asynchronous on ``stream``; uses none of the handle's
+        workspace, so it may run beside a render of the handle on another stream."""
+        if not (visibility_ptr or distance_ptr or matte_ptr):
+            raise ValueError("give at least one of visibility_ptr, distance_ptr, matte_ptr")
+        if not np.isfinite(np.float32(ground)):
+            raise ValueError("ground must be finite")
+        c = config.to_c()
+        planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
+        check(load().mcrt_render_ground_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
+
     def pick(self, config: Config, xy) -> np.ndarray:
         """What is under the pixels ``xy`` ((n, 2) integers, x then y, inside the frame): a structured array of
         ``abi.SURFACE_DTYPE`` — mesh, face, tx, ty, t, point, normal, albedo — equal to the layers at those pixels
@@ -521,6 +602,33 @@ def render_layers_batch_device(device_scenes: Sequence["DeviceScene"], config: C
     c = config.to_c()
     planes = abi.McrtLayers(depth_ptr or None, normal_ptr or None, albedo_ptr or None, id_ptr or None)
     check(load().mcrt_render_layers_batch_device(arr, n, C.byref(c), C.byref(planes), stride, C.c_void_p(stream)))
+
+
+def render_ground_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, ground, visibility_ptr: int = 0, distance_ptr: int = 0,
+                               matte_ptr: int = 0, frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
+    """The ground-shadow planes of N resident scenes of one config in one launch (mcrt_render_ground_batch_device): frame i of
+    each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  ``ground``: one height for all, or N
+    heights (a handle may be listed more than once, with different heights).  Asynchronous on ``stream``."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    if not (visibility_ptr or distance_ptr or matte_ptr):
+        raise ValueError("give at least one of visibility_ptr, distance_ptr, matte_ptr")
+    if ground is None:
+        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
+    heights = _ground_heights(handles, ground)
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
+    if stride < px:
+        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    gy = (C.c_float * max(n, 1))(*heights)
+    c = config.to_c()
+    planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
+    check(load().mcrt_render_ground_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
 
 
 def last_batch_info() -> dict:

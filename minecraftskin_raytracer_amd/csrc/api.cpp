@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <condition_variable>
 #include <mutex>
@@ -766,6 +767,58 @@ int mcrt_render_layers(const mcrt_scene_desc* desc, const mcrt_config* cfg, cons
     if (!desc) return fail(MCRT_ERR_INVALID, "NULL argument");
     const mcrt_scene_desc* one[1] = {desc};
     return mcrt_render_layers_batch(one, 1, cfg, out, device);
+}
+
+// ---- ground shadow: the one-shot host form (render_enqueue.cpp: render_ground_batch_device) and the scene's floor ------------
+int mcrt_render_ground(const mcrt_scene_desc* desc, const mcrt_config* cfg, float ground_y, const mcrt_ground* out, int device) {
+    if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
+    if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (cfg->soft_shadows && cfg->shadow_samples > kGroundMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a ground pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
+    if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    OneShotScenes set;
+    const mcrt_scene_desc* one[1] = {desc};
+    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
+    if (rc != MCRT_OK) return rc;
+    mcrt_scene* s0 = set.h[0];
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    // the float planes first: each starts on a 4-byte boundary
+    const size_t vis_bytes = out->visibility ? px * 4 : 0, dist_bytes = out->distance ? px * 4 : 0, matte_bytes = out->matte ? px : 0;
+    hipError_t e = s0->frame.reserve(vis_bytes + dist_bytes + matte_bytes);
+    if (e != hipSuccess) return hip_fail(e, "ground planes");
+    char* base = static_cast<char*>(s0->frame.ptr);
+    mcrt_ground d{};
+    d.visibility = out->visibility ? reinterpret_cast<float*>(base) : nullptr;
+    d.distance = out->distance ? reinterpret_cast<float*>(base + vis_bytes) : nullptr;
+    d.matte = out->matte ? reinterpret_cast<uint8_t*>(base + vis_bytes + dist_bytes) : nullptr;
+    rc = render_ground_batch_device(set.h.data(), 1, cfg, &ground_y, &d, px, s0->main_stream);
+    set.download(out->visibility, d.visibility, vis_bytes, rc);
+    set.download(out->distance, d.distance, dist_bytes, rc);
+    set.download(out->matte, d.matte, matte_bytes, rc);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "ground render");
+    }
+    return rc;
+}
+
+int mcrt_scene_floor(const mcrt_scene_desc* desc, float* y) {
+    if (!desc || !y) return fail(MCRT_ERR_INVALID, "NULL argument");
+    bool any = false;
+    float lowest = 0.0f;
+    for (int32_t m = 0; m < desc->n_meshes && desc->meshes; ++m) {
+        const mcrt_mesh& mesh = desc->meshes[m];
+        if (!mesh.tri_vertices) continue;
+        for (int64_t v = 0; v < static_cast<int64_t>(mesh.n_triangles) * 3; ++v) {
+            const float vy = mesh.tri_vertices[3 * v + 1];
+            if (!any || vy < lowest) lowest = vy;
+            any = true;
+        }
+    }
+    if (!any) return fail(MCRT_ERR_INVALID, "the scene holds no vertex");
+    *y = lowest;
+    return MCRT_OK;
 }
 
 int mcrt_scene_pick(mcrt_scene* s, const mcrt_config* cfg, const int32_t* xy, int n, mcrt_surface* out) {

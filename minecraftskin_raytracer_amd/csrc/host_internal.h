@@ -177,6 +177,7 @@ inline bool valid_frame(const mcrt_config* c) { return c->width > 0 && c->height
 inline bool valid_background(int b) { return b == MCRT_BACKGROUND_REFERENCE || b == MCRT_BACKGROUND_TRANSPARENT; }
 inline int bad_background() { return fail(MCRT_ERR_INVALID, "background must be MCRT_BACKGROUND_REFERENCE or MCRT_BACKGROUND_TRANSPARENT"); }
 inline bool no_plane(const mcrt_layers* l) { return !l->depth && !l->normal && !l->albedo && !l->id; }
+inline bool no_plane(const mcrt_ground* g) { return !g->visibility && !g->distance && !g->matte; }
 
 // what the calling thread's last mcrt_render_batch* call did (mcrt_last_batch_info; thread-local in api.cpp, like the error text)
 struct BatchInfo {
@@ -231,6 +232,8 @@ int enqueue_render(mcrt_scene* s, const mcrt_config* cfg, int first, int step, i
                    bool may_record = true, std::vector<RowGroup>* groups = nullptr, const mcrt_tile* rect = nullptr);
 int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream);
 int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream);
+int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_ground* d_out, size_t stride,
+                               hipStream_t stream);
 
 }  // namespace mcrt_host
 

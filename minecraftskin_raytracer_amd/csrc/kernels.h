@@ -263,6 +263,41 @@ size_t layers_lds_bytes(const LayersFrame& f);
 // n pixels (d_xy: n x {x, y}, inside the frame) → n mcrt_surface records, by the device functions of the layers kernels
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream);
 
+// ---- ground shadow (mcrt_render_ground_device & co): the figure's shadow on the plane y = ground_y — per pixel the
+// pixel-centre ray of the layers, its point P on the plane, and computeSoftShadow(P, (0, 1, 0)) with the seed the reference
+// forms for a hit at depth 0.  Like a layers pass it reads the scene blob alone (and the device's seed table).
+// One frame of a ground pass: its scene, its height and its planes (any may be NULL, not all), width * height pixels each
+struct GroundFrame {
+    const uint8_t* scene;
+    float* visibility;           // 1 float per pixel: lit light samples / samples; 1.0f where the ray misses the plane
+    float* distance;             // the ray parameter t of the plane; FLT_MAX where the ray misses it
+    uint8_t* matte;              // quantised 1 - visibility: the alpha of a black shadow image
+    const uint32_t* seed_table;  // the handle's window table (RenderParams::seed_table), or NULL: the recurrence
+    float ground_y;
+    int lds_alpha_words;         // scene tables staged in LDS, as LayersFrame's
+    int lds_face_entries;
+};
+constexpr int kGroundMaxSamples = 113;  // the truncated engine's 227 draws: no per-lane 624-word state
+// what the frames of one launch share
+struct GroundShape {
+    LayersShape tiles;     // the frame's size and its tile grid, as a layers pass cuts it
+    int samples;           // S: shadow_samples when soft_shadows && shadow_samples > 1, else 1
+    int pass;              // undecided pixels whose S sample positions fit the block's LDS area at once
+    int bundle_decisions;  // as RenderParams'
+    int inside_fast;
+};
+// false when the frame holds more units than the kernels index (2^31)
+bool make_ground_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, GroundShape& shape);
+// fills f.lds_* and returns the kernel variant by the layers' rule
+int ground_view(GroundFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
+int ground_batch_view(GroundFrame* frames, const int* views, int n);
+// dynamic LDS of a launch: the frame's scene tables, then the block's area (masks, points, counts and sample positions)
+size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape);
+hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
+// frame's ground_lds_bytes
+hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream);
+
 hipError_t launch_unpack_rows(const mcrt_config& cfg, const Shard& sh, const float* packed, float* frame,
                               hipStream_t stream);
 hipError_t launch_unpack_rows8(const mcrt_config& cfg, const Shard& sh, const uint8_t* packed, uint8_t* frame, hipStream_t stream);  // RGBA8 plane

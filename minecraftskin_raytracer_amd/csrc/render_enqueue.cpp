@@ -412,6 +412,60 @@ int layers_frame_of(const mcrt_scene* s, const mcrt_layers& out, size_t index, s
     f.id = out.id ? reinterpret_cast<int4*>(out.id) + off : nullptr;
     return layers_view(f, s->alpha_words, s->n_meshes, s->posed);
 }
+// the same for a ground pass (mcrt_render_ground_device & co), which also reads the device's seed table through the handle
+int ground_frame_of(const mcrt_scene* s, const mcrt_ground& out, float ground_y, size_t index, size_t stride, GroundFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.visibility = out.visibility ? out.visibility + off : nullptr;
+    f.distance = out.distance ? out.distance + off : nullptr;
+    f.matte = out.matte ? out.matte + off : nullptr;
+    f.seed_table = s->seed_table;
+    f.ground_y = ground_y;
+    return ground_view(f, s->alpha_words, s->n_meshes, s->posed);
+}
+
+// What the layers and the ground entry points check alike, before any device work (only the last check looks inside the
+// handles, at their device index).  run = false with MCRT_OK: zero tiles, nothing is written.
+int check_pass_arguments(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const void* d_out, size_t stride, bool& run, int& device) {
+    run = false;
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;
+    if (stride < static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height))
+        return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
+    device = scenes[0]->device;
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    run = true;
+    return MCRT_OK;
+}
+
+// The launches of such a pass.  One frame: its record travels as a kernel argument (`one`).  More: the records go to a slot
+// of the batched renders' table ring (refilled only after the launches that read it) and every kLayersBatchMaxFrames of them
+// take one launch (`many`).
+template <class Frame, class One, class Many>
+int launch_pass(int device, const std::vector<Frame>& frames, hipStream_t stream, const char* what, One one, Many many) {
+    const int n = static_cast<int>(frames.size());
+    if (n == 1) {
+        const hipError_t e = one(frames[0]);
+        if (e != hipSuccess) return hip_fail(e, what);
+        return MCRT_OK;
+    }
+    if (stream_capturing(stream))
+        return fail(MCRT_ERR_INVALID, "a batch cannot be recorded into a caller's graph (its parameter table is uploaded per call)");
+    (void)hipGetLastError();
+    TableUpload table;
+    if (const int rc = upload_table(device, frames.data(), static_cast<size_t>(n) * sizeof(Frame), stream, table); rc != MCRT_OK) return rc;
+    const Frame* d_table = static_cast<const Frame*>(table.dev);
+    hipError_t e = table.status;
+    for (int c0 = 0; c0 < n && e == hipSuccess; c0 += kLayersBatchMaxFrames) e = many(d_table + c0, std::min(kLayersBatchMaxFrames, n - c0));
+    if (e == hipSuccess) e = table.commit(stream);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return MCRT_OK;
+}
 
 }  // namespace
 
@@ -617,47 +671,54 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
 }
 
 int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream) {
-    // argument checks, before any device work (all but the last do not look inside the handles)
-    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
-    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
-    for (int i = 0; i < n; ++i)
-        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
-    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all four planes are NULL");
-    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
-    if (stride < static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height))
-        return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
-    const int device = scenes[0]->device;
-    for (int i = 1; i < n; ++i)
-        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    // argument checks, before any device work
+    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all four planes are NULL");
+    bool run;
+    int device = 0;
+    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
     LayersShape shape;
     if (!make_layers_shape(*cfg, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
     HIP_TRY(hipSetDevice(device));
-    if (n == 1) {  // one frame: its parameters travel as kernel arguments
-        LayersFrame f;
-        const int view = layers_frame_of(scenes[0], *d_out, 0, stride, f);
-        hipError_t e = launch_layers(f, shape, view, stream);
-        if (e != hipSuccess) return hip_fail(e, "layers launch");
-        return MCRT_OK;
-    }
-    if (stream_capturing(stream))
-        return fail(MCRT_ERR_INVALID, "a batch cannot be recorded into a caller's graph (its parameter table is uploaded per call)");
-    (void)hipGetLastError();
     std::vector<LayersFrame> frames(static_cast<size_t>(n));
     std::vector<int> views(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) views[static_cast<size_t>(i)] = layers_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
     const int view = layers_batch_view(frames.data(), views.data(), n);
     size_t dyn = 0;
     for (const LayersFrame& f : frames) dyn = std::max(dyn, layers_lds_bytes(f));
-    // the frames' table: a slot of the batched renders' ring (refilled only after the launches that read it)
-    TableUpload table;
-    if (const int rc = upload_table(device, frames.data(), static_cast<size_t>(n) * sizeof(LayersFrame), stream, table); rc != MCRT_OK) return rc;
-    const LayersFrame* d_table = static_cast<const LayersFrame*>(table.dev);
-    hipError_t e = table.status;
-    for (int c0 = 0; c0 < n && e == hipSuccess; c0 += kLayersBatchMaxFrames)  // one launch per kLayersBatchMaxFrames frames
-        e = launch_layers_batch(d_table + c0, std::min(kLayersBatchMaxFrames, n - c0), shape, view, dyn, stream);
-    if (e == hipSuccess) e = table.commit(stream);
-    if (e != hipSuccess) return hip_fail(e, "batched layers launches");
-    return MCRT_OK;
+    return launch_pass(
+        device, frames, stream, "layers launches", [&](const LayersFrame& f) { return launch_layers(f, shape, view, stream); },
+        [&](const LayersFrame* d_table, int m) { return launch_layers_batch(d_table, m, shape, view, dyn, stream); });
+}
+
+// ---- ground shadow (mcrt_render_ground_device & co): like a layers pass it reads the scene blob alone — and the device's seed
+// table, which lives as long as the handle — so it takes no workspace, no counters and none of the handle's events
+int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_ground* d_out, size_t stride,
+                               hipStream_t stream) {
+    // argument checks, before any device work
+    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
+    if (n > 0 && !ground_y) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (cfg && cfg->soft_shadows && cfg->shadow_samples > kGroundMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a ground pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
+    bool run;
+    int device = 0;
+    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
+    GroundShape shape;
+    if (!make_ground_shape(*cfg, decisions, inside_fast, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(device));
+    std::vector<GroundFrame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i)
+        views[static_cast<size_t>(i)] = ground_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
+    const int view = ground_batch_view(frames.data(), views.data(), n);
+    size_t dyn = 0;
+    for (const GroundFrame& f : frames) dyn = std::max(dyn, ground_lds_bytes(f, shape));
+    return launch_pass(
+        device, frames, stream, "ground launches", [&](const GroundFrame& f) { return launch_ground(f, shape, view, stream); },
+        [&](const GroundFrame* d_table, int m) { return launch_ground_batch(d_table, m, shape, view, dyn, stream); });
 }
 
 }  // namespace mcrt_host
@@ -741,6 +802,18 @@ int mcrt_render_layers_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_
 int mcrt_render_layers_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_layers* d_out,
                                     size_t frame_stride_pixels, void* stream) {
     return render_layers_batch_device(scenes, n_frames, cfg, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_ground_device(mcrt_scene* s, const mcrt_config* cfg, float ground_y, const mcrt_ground* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = (cfg && valid_frame(cfg)) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
+    return render_ground_batch_device(one, 1, cfg, &ground_y, d_out, px, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_ground_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y, const mcrt_ground* d_out,
+                                    size_t frame_stride_pixels, void* stream) {
+    return render_ground_batch_device(scenes, n_frames, cfg, ground_y, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -42,6 +42,9 @@
 //   layers / pick   (not a stage of a render: mcrt_render_layers*, mcrt_scene_pick) a workgroup per tile: the tile's mesh
 //                                     mask, then either the miss constants or one pixel-centre ray per lane — depth, normal,
 //                                     albedo and {mesh, face, texel} planes straight from the scene blob, no workspace
+//   ground          (not a stage of a render either: mcrt_render_ground*) the figure's soft shadow on a floor plane, per 256
+//                                     pixels of a tile: the meshes that can shadow the tile's ground points, then `lit`'s
+//                                     phases for the pixels' plane points — visibility, distance and matte planes
 // Records live in HBM as SoA float4 arrays.  Every unit owns a fixed slot range (its samples); its
 // primary hits are compacted to the front of that range with an LDS prefix sum and a per-unit count —
 // NO global atomics on the hot path (a returning atomic on one word sustains only ~88 ops/us on this
@@ -55,7 +58,8 @@
 
 // Verification hooks.  tools/decide_check.sh builds a variant of the library with -DMCRT_KERNEL_HOOKS='"decide_check_hooks.h"'
 // (tools/decide_check_hooks.h: every record `lit` decides is traced as well and contradictions are counted and printed);
-// the product build compiles the hooks to nothing.
+// the product build compiles the hooks to nothing.  tools/gpu_ground.py builds another variant with tools/ground_class_hooks.h: the
+// ground pass then writes every pixel's class (missed, culled by tile, decided, traced) into its visibility plane.
 #ifdef MCRT_KERNEL_HOOKS
 #include MCRT_KERNEL_HOOKS
 #else
@@ -63,6 +67,9 @@
 #define MCRT_HOOK_LIT_CLASSIFIED(known, undecided, cand, O)
 #define MCRT_HOOK_LIT_SHADED(lit, r)
 #define MCRT_HOOK_RESOLVE_BEGIN()
+#endif
+#ifndef MCRT_HOOK_GROUND_PIXEL
+#define MCRT_HOOK_GROUND_PIXEL(vis, reached, culled, undecided)
 #endif
 
 namespace mcrt {
@@ -1330,6 +1337,30 @@ __global__ __launch_bounds__(kBlock, MCRT_SHADOW_WAVES) void shadow_kernel(const
 // record: ~180 MB of the metric frame's counted traffic), and the VALU-bound seeding chains could not
 // overlap the latency-bound shadow rays.  Hard shadows / a point light: no phase A, one ray per record.
 // ---------------------------------------------------------------------------------------------
+// The S disk sample positions of one shaded point (shading.cpp:35-53), by the lane that owns it (`lit`, the ground pass): the
+// truncated engine seeded for (P, depth) — mt[397] from the device's tables where they hold the seed, else the 397-step
+// recurrence — and the light's frame at P.  dst: 3 * S floats.
+__device__ __forceinline__ void disk_sample_positions(const SceneView& scg, const uint32_t* __restrict__ seed_table, const uint32_t* __restrict__ seed_table_full,
+                                                      const V3 P, const int depth, const int S, float* __restrict__ dst) {
+    MtShort rng;
+    const uint32_t seed = shadow_seed(P, depth);
+    const uint32_t slot = seed + kSeedWindowHalf;  // wraps: the window is centred on seed 0
+    if (seed_table && slot < kSeedWindow)
+        rng.seed_known(seed, seed_table[slot]);  // mt[397] of this seed, from the device's table
+    else if (seed_table_full)
+        rng.seed_known(seed, seed_table_full[seed]);  // (a scene at another scale: its seeds leave the window)
+    else
+        rng.seed(seed);  // the 397-step recurrence
+    const LightFrame frame = light_frame(scg, P);
+    for (int i = 0; i < S; ++i) {
+        const float d0 = rng.uniform();
+        const float d1 = rng.uniform();
+        const V3 t = light_sample_on_frame(scg, frame, d0, d1);
+        dst[3 * i + 0] = t.x;
+        dst[3 * i + 1] = t.y;
+        dst[3 * i + 2] = t.z;
+    }
+}
 #ifndef MCRT_LIT_WAVES
 #define MCRT_LIT_WAVES 4
 #endif
@@ -1476,26 +1507,7 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
                 // ---- phase A2: a lane per undecided record — its mt19937 stream and the S disk sample positions
                 if (mode == SHADOW_SOFT && threadIdx.x < nu) {
                     const RecordGeom g = load_geom(ws, posed, base + s_und[u0 + threadIdx.x]);
-                    const V3 P = g.p;
-                    MtShort rng;
-                    const uint32_t seed = shadow_seed(P, g.depth);
-                    const uint32_t slot = seed + kSeedWindowHalf;  // wraps: the window is centred on seed 0
-                    if (p.seed_table && slot < kSeedWindow)
-                        rng.seed_known(seed, p.seed_table[slot]);  // mt[397] of this seed, from the device's table
-                    else if (p.seed_table_full)
-                        rng.seed_known(seed, p.seed_table_full[seed]);  // (a scene at another scale: its seeds leave the window)
-                    else
-                        rng.seed(seed);  // the 397-step recurrence
-                    const LightFrame frame = light_frame(scg, P);
-                    float* dst = s_pos + static_cast<size_t>(threadIdx.x) * 3 * S;
-                    for (int i = 0; i < S; ++i) {
-                        const float d0 = rng.uniform();
-                        const float d1 = rng.uniform();
-                        const V3 t = light_sample_on_frame(scg, frame, d0, d1);
-                        dst[3 * i + 0] = t.x;
-                        dst[3 * i + 1] = t.y;
-                        dst[3 * i + 2] = t.z;
-                    }
+                    disk_sample_positions(scg, p.seed_table, p.seed_table_full, g.p, g.depth, S, s_pos + static_cast<size_t>(threadIdx.x) * 3 * S);
                 }
                 __syncthreads();
                 // ---- phase B: a lane per (undecided record, light sample); every lane of a wave runs the same number of turns (ballot inside)
@@ -2092,6 +2104,272 @@ __global__ __launch_bounds__(64) void pick_kernel(const uint8_t* __restrict__ sc
     o[1] = make_float4(s.t, s.p.x, s.p.y, s.p.z);
     o[2] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
     o[3] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ground shadow (kernels.h: GroundFrame): the figure's soft shadow on the plane y = ground_y, as planes of their own.  Per
+// pixel the layers' pixel-centre ray, its point P on the plane, and computeSoftShadow(P, (0, 1, 0)) (shading.cpp:28-60) with
+// the seed of a hit at depth 0 (raytracer.cpp:110-112) — the figure in front of the plane plays no part.  No workspace.
+//   a workgroup per 256 pixels of a screen tile (grid-stride), in the phases of `lit`, handed over through LDS:
+//   1 lane / mesh (every wave)   which meshes can shadow ANY ground point under the tile (ground_tile_mask): none for most
+//                                tiles of a frame — their reached pixels are fully lit without a classification or a ray
+//   1 lane / pixel               ray, plane hit, P; the whole-bundle decision (rt::bundle_classify) from P + N * 1e-3f: lit by
+//                                all S light samples, by none, or undecided with a candidate mask; the undecided are packed
+//   1 lane / undecided pixel     truncated mt19937 (mt[397] from the seed table) → 2·S draws → S disk sample positions in LDS
+//   1 lane / (undecided pixel, light sample)   exact any-hit test on the candidates → lit count by ballot
+//   1 lane / pixel               visibility = lit / S, distance, matte: coalesced stores, 16 bytes per four pixels of a row
+//                                where the rows allow
+// ---------------------------------------------------------------------------------------------
+constexpr int kGroundPosBytes = 12 * 1024;  // LDS for the sample positions of the undecided pixels of one pass
+constexpr int kGroundFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // candidate and inside masks, P.x / P.z, lit counts, the undecided list
+constexpr int kGroundWaves = 4;  // waves per SIMD the kernels are built for: `lit`'s, whose device functions they inline
+__host__ __device__ __forceinline__ size_t scene_tables_lds_bytes(int face_entries, int alpha_words) {
+    return static_cast<size_t>(face_entries) * 16 + static_cast<size_t>(face_entries / 6) * kMeshTabWords * 4 + static_cast<size_t>(alpha_words) * 4;
+}
+struct GroundPoint {
+    bool reached;
+    float t;  // FLT_MAX where the ray does not reach the plane
+    V3 P;
+};
+// the ray through (fx, fy) pixels of the frame — a pixel centre is (px + 0.5f, py + 0.5f) — against the plane y = g
+__device__ __forceinline__ GroundPoint ground_point(const SceneView& sc, const mcrt_config& cfg, const float aspect, const float g, const float fx,
+                                                    const float fy) {
+    const float u = fx / static_cast<float>(cfg.width);
+    const float v = fy / static_cast<float>(cfg.height);
+    const Ray ray = camera_ray(sc, u, v, aspect);
+    const float t = (g - ray.o.y) / ray.d.y;
+    GroundPoint h;
+    h.reached = ray.d.y != 0.0f && t > 0.0f && t <= kFltMax;
+    h.t = h.reached ? t : kFltMax;
+    h.P = mk(ray.o.x + ray.d.x * t, g, ray.o.z + ray.d.z * t);
+    return h;
+}
+// The meshes that can shadow a ground point under the tile, conservatively: lane m of the calling wave tests mesh m.
+// The tile's pixel-centre rays lie inside its four corner rays; when all four reach the plane (well away from the horizon:
+// |d.y| >= 1e-2) the ground points of the tile lie in the bounding rectangle F of the four corner points — the image of a
+// screen rectangle on a plane in front of the camera is a convex quadrilateral.  A shadow ray leaves Q + (0, 1e-3, 0) for a
+// target T within Rb of the light centre L.  When the lowest target is above the top of a mesh's world box B (bounding
+// sphere when posed) and above the origins, the ray climbs, and it meets B at a point X with gy <= X.y <= B.hi.y only if
+// Q = X + (X - T) * k', 0 <= k' <= k = (L.y - Rb - gy) / (L.y - Rb - B.hi.y) - 1: per axis Q lies in
+// [B.lo - max(0, L + Rb - B.lo) * k, B.hi + max(0, B.hi - L + Rb) * k] — B's shadow from the light centre, widened by the
+// light's radius in the ratio of B's height to the light's clearance.  A mesh whose interval misses F on x or z, with margins
+// far above the float error of the points (2e-3 of the footprint's reach, 1e-4 of the interval, 16 slacks), shadows no
+// pixel of the tile.  Every other case keeps the mesh: a light that is not clear above the box, a corner that misses the
+// plane or grazes it, 64 meshes or more, cull_ok == 0, non-finite values (every comparison is written to fail open).
+__device__ __forceinline__ unsigned long long ground_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect,
+                                                               const float g, const float R, const int lane) {
+    const int n = sc.n_meshes;
+    if (n <= 0) return 0ull;
+    const unsigned long long all = n < 64 ? (1ull << n) - 1ull : ~0ull;
+    if (sc.hdr->cull_ok == 0 || n >= 64) return all;
+    const float slack = sc.hdr->mask_slack;
+    float fx0 = kFltMax, fx1 = -kFltMax, fz0 = kFltMax, fz1 = -kFltMax, reach = 0.0f;
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float fx = static_cast<float>(tg.x + ((c & 1) ? tg.w : 0)), fy = static_cast<float>(tg.y + ((c & 2) ? tg.h : 0));
+        const Ray ray = camera_ray(sc, fx / static_cast<float>(cfg.width), fy / static_cast<float>(cfg.height), aspect);
+        const float t = (g - ray.o.y) / ray.d.y;
+        ok = ok && __builtin_fabsf(ray.d.y) >= 1e-2f && t > 0.0f && t < 1e30f;
+        const float dx = ray.d.x * t, dz = ray.d.z * t;
+        const float x = ray.o.x + dx, z = ray.o.z + dz;
+        fx0 = __builtin_fminf(fx0, x), fx1 = __builtin_fmaxf(fx1, x), fz0 = __builtin_fminf(fz0, z), fz1 = __builtin_fmaxf(fz1, z);
+        reach = __builtin_fmaxf(reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dz)), t));
+        ok = ok && x == x && z == z;  // (fmin / fmax drop a NaN)
+    }
+    ok = ok && reach < 1e30f && slack < 1e30f;
+    if (!ok) return all;
+    const float fm = 2e-3f * reach + 16.0f * slack;
+    const V3 L = ld3(sc.hdr->light_pos);
+    const float Rb = R * 1.001f + slack;
+    const float gy = g + 1e-3f;     // the shadow rays' origins
+    const float low = L.y - Rb;     // the lowest target
+    bool touch = lane < n;
+    if (touch) {
+        const FlatMesh& m = sc.meshes[lane];
+        if (m.flags & MESH_EMPTY) {
+            touch = false;  // intersection.cpp:205: never hit
+        } else {
+            V3 lo = ld3(m.lo), hi = ld3(m.hi);
+            bool bounded = true;
+            if (m.flags & MESH_ROTATED) {
+                const float r = m.sphere[3];
+                bounded = r >= 0.0f;
+                lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
+                hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
+            }
+            const float h = low - gy, c = low - hi.y;  // the light's height above the origins and above the box
+            if (bounded && h > 0.0f && c > 0.01f * h && c > 64.0f * slack) {
+                if (hi.y < gy - 64.0f * slack) {
+                    touch = false;  // the box ends below the origins and every ray climbs
+                } else {
+                    const float k = __builtin_fmaxf(h / c - 1.0f, 0.0f);
+                    const float qx0 = lo.x - __builtin_fmaxf(0.0f, L.x + Rb - lo.x) * k, qx1 = hi.x + __builtin_fmaxf(0.0f, hi.x - L.x + Rb) * k;
+                    const float qz0 = lo.z - __builtin_fmaxf(0.0f, L.z + Rb - lo.z) * k, qz1 = hi.z + __builtin_fmaxf(0.0f, hi.z - L.z + Rb) * k;
+                    const float mg = fm + 1e-4f * (__builtin_fabsf(qx0) + __builtin_fabsf(qx1) + __builtin_fabsf(qz0) + __builtin_fabsf(qz1));
+                    const bool out = (qx1 + mg < fx0) | (qx0 - mg > fx1) | (qz1 + mg < fz0) | (qz0 - mg > fz1);
+                    touch = !out;
+                }
+            }
+        }
+    }
+    return __ballot(touch);
+}
+// one value per pixel into a plane: 16 bytes per four neighbouring pixels of a row where `quads` (lanes 4k .. 4k+3 then hold
+// four neighbours of one row, all valid or none)
+__device__ __forceinline__ void store_plane(float* __restrict__ plane, const bool quads, const bool valid, const int lane, const size_t idx, const float val) {
+    if (quads) {
+        const float v1 = __shfl_down(val, 1), v2 = __shfl_down(val, 2), v3 = __shfl_down(val, 3);
+        if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(plane + idx) = make_float4(val, v1, v2, v3);
+    } else if (valid) {
+        plane[idx] = val;
+    }
+}
+template <int kView>
+__device__ __forceinline__ void ground_body(const GroundFrame& __restrict__ f, const GroundShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks][inside masks][P.x, P.z][lit counts][undecided list][positions: pass x S x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.tiles.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const float g = f.ground_y;
+    const V3 lpos = ld3(scg.hdr->light_pos);
+    const float lradius = scg.hdr->light_radius;
+    const int S = sh.samples;
+    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
+    const float R = soft ? lradius : 0.0f;
+    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per pixel
+    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
+    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    const V3 N = mk(0.0f, 1.0f, 0.0f);
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(area);
+    unsigned long long* s_ins = s_cand + kBlock;
+    float2* s_pxz = reinterpret_cast<float2*>(s_ins + kBlock);
+    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_pxz + kBlock);
+    uint32_t* s_und = s_lit + kBlock;
+    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    // four neighbouring pixels of a row per store: every tile row starts and ends on a four-pixel boundary of the plane
+    const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
+    const bool quads_vis = quad_rows && (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
+    const bool quads_dist = quad_rows && (reinterpret_cast<uintptr_t>(f.distance) & 15u) == 0;
+    const bool quads_matte = quad_rows && (reinterpret_cast<uintptr_t>(f.matte) & 3u) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    const int parts = sh.tiles.parts;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        const int tile = unit / parts, part = unit - tile * parts;
+        const int tyi = tile / sh.tiles.tiles_x, txi = tile - tyi * sh.tiles.tiles_x;
+        TileGeom tg;
+        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+        tg.owned_row = tyi, tg.frame_tile = tile;
+        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
+        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
+        const unsigned long long mask = ground_tile_mask(scg, cfg, tg, aspect, g, R, lane);  // the same in every wave of the workgroup
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        const unsigned pix = p0 + static_cast<unsigned>(tid);
+        const bool valid = pix < npix;
+        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
+        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
+        GroundPoint gp = ground_point(scg, cfg, aspect, g, static_cast<float>(tg.x + lx) + 0.5f, static_cast<float>(tg.y + ly) + 0.5f);
+        if (!valid) gp.reached = false, gp.t = kFltMax;
+        if (f.distance) store_plane(f.distance, quads_dist, valid, lane, idx, gp.t);
+        uint32_t lit = pairs;  // a pixel that misses the plane, and every pixel of a tile no mesh can shadow
+        bool undecided = false;
+        if (mask != 0ull) {  // uniform
+            // ---- a lane per pixel: the whole-bundle decision
+            if (gp.reached) {
+                const V3 O = gp.P + N * 1e-3f;
+                unsigned long long cand;
+                const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
+                cand &= mask;
+                undecided = known < 0;
+                s_cand[tid] = cand;
+                s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
+                s_pxz[tid] = make_float2(gp.P.x, gp.P.z);
+                if (!undecided) lit = static_cast<uint32_t>(known);
+            }
+            s_lit[tid] = 0u;
+            int total = 0;
+            const int rank = block_rank(undecided, s_wcnt, total);
+            if (undecided) s_und[rank] = static_cast<uint32_t>(tid);
+            const uint32_t n_und = static_cast<uint32_t>(total);
+            if (n_und) __syncthreads();  // uniform
+            for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
+                const uint32_t nu = min(pass, n_und - u0);
+                if (u0) __syncthreads();  // the previous pass's rays have read the positions
+                // ---- a lane per undecided pixel: its mt19937 stream and the S disk sample positions
+                if (soft && static_cast<uint32_t>(tid) < nu) {
+                    const float2 xz = s_pxz[s_und[u0 + tid]];
+                    // (outside the seed table's window — ground points far out, at the horizon — the 397-step recurrence)
+                    disk_sample_positions(scg, f.seed_table, nullptr, mk(xz.x, g, xz.y), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
+                }
+                __syncthreads();
+                // ---- a lane per (undecided pixel, light sample); every lane of a wave runs the same number of turns (ballot inside)
+                const uint32_t n_rays = nu * pairs;
+                for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
+                    const uint32_t q = q0 + static_cast<uint32_t>(lane);
+                    bool visible = false;
+                    uint32_t k = 0;
+                    if (q < n_rays) {
+                        k = s_und[u0 + q / pairs];
+                        const float2 xz = s_pxz[k];
+                        const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
+                        visible = !in_shadow_masked(sc, mk(xz.x, g, xz.y), N, target, s_cand[k], s_ins[k]);
+                    }
+                    if (pow2) {
+                        const unsigned long long bal = __ballot(visible);
+                        if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
+                            const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
+                            s_lit[k] = static_cast<uint32_t>(__popcll(grp));
+                        }
+                    } else if (visible) {
+                        atomicAdd(&s_lit[k], 1u);
+                    }
+                }
+            }
+            // the counts are complete; behind this barrier nothing of the unit is read across lanes any more, so the next
+            // unit may overwrite the area
+            if (n_und) __syncthreads();
+            if (undecided) lit = s_lit[tid];
+        }
+        // ---- a lane per pixel: the planes
+        float vis = static_cast<float>(lit) / static_cast<float>(pairs);
+        MCRT_HOOK_GROUND_PIXEL(vis, gp.reached, mask == 0ull, undecided)
+        if (f.visibility) store_plane(f.visibility, quads_vis, valid, lane, idx, vis);
+        if (f.matte) {
+            const uint32_t a = static_cast<unsigned char>(sclamp(1.0f - vis, 0.0f, 1.0f) * 255.0f + 0.5f);
+            if (quads_matte) {
+                const uint32_t a1 = __shfl_down(a, 1), a2 = __shfl_down(a, 2), a3 = __shfl_down(a, 3);
+                if (valid && (lane & 3) == 0) *reinterpret_cast<uint32_t*>(f.matte + idx) = a | (a1 << 8) | (a2 << 16) | (a3 << 24);
+            } else if (valid) {
+                f.matte[idx] = static_cast<uint8_t>(a);
+            }
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_kernel(const GroundFrame f, const GroundShape sh) {
+    ground_body<kView>(f, sh);
+}
+using GroundTable = const __attribute__((address_space(4))) GroundFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_batch_kernel(GroundTable table, const GroundShape sh) {
+    ground_body<kView>(*(const GroundFrame*)(table + blockIdx.y), sh);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2731,7 +3009,8 @@ int layers_view(LayersFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool po
     f.lds_face_entries = fits ? static_cast<int>(n_meshes * 6) : 0;
     return !fits ? kViewHbm : (posed ? kViewLds : kViewLdsUnposed);
 }
-int layers_batch_view(LayersFrame* frames, const int* views, int n) {
+template <class Frame>  // LayersFrame or GroundFrame
+static int batch_view_of(Frame* frames, const int* views, int n) {
     bool any_hbm = false, any_posed = false;
     for (int i = 0; i < n; ++i) {
         any_hbm = any_hbm || views[i] == kViewHbm;
@@ -2741,6 +3020,7 @@ int layers_batch_view(LayersFrame* frames, const int* views, int n) {
         for (int i = 0; i < n; ++i) frames[i].lds_alpha_words = 0, frames[i].lds_face_entries = 0;
     return any_hbm ? kViewHbm : (any_posed ? kViewLds : kViewLdsUnposed);
 }
+int layers_batch_view(LayersFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
 size_t layers_lds_bytes(const LayersFrame& f) {
     return static_cast<size_t>(f.lds_face_entries) * 16 + static_cast<size_t>(f.lds_face_entries / 6) * kMeshTabWords * 4 + static_cast<size_t>(f.lds_alpha_words) * 4;
 }
@@ -2783,6 +3063,55 @@ hipError_t launch_layers_batch(const LayersFrame* d_table, int n_frames, const L
         hipLaunchKernelGGL(layers_batch_kernel<kViewLds>, grid, dim3(kBlock), max_dyn, stream, table, shape);
     else
         hipLaunchKernelGGL(layers_batch_kernel<kViewHbm>, grid, dim3(kBlock), 0, stream, table, shape);
+    return hipGetLastError();
+}
+// ---- ground shadow (kernels.h) --------------------------------------------------------------------
+bool make_ground_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, GroundShape& shape) {
+    std::memset(&shape, 0, sizeof shape);
+    if (!make_layers_shape(cfg, shape.tiles)) return false;
+    shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
+    const int fit = kGroundPosBytes / (12 * shape.samples);  // 113 samples: 9 pixels per pass
+    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.bundle_decisions = bundle_decisions ? 1 : 0;
+    shape.inside_fast = inside_fast ? 1 : 0;
+    return true;
+}
+int ground_view(GroundFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
+    LayersFrame l{};
+    const int view = layers_view(l, alpha_words, n_meshes, posed);
+    f.lds_alpha_words = l.lds_alpha_words, f.lds_face_entries = l.lds_face_entries;
+    return view;
+}
+int ground_batch_view(GroundFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
+size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape) {
+    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    return tables + kGroundFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
+}
+hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int view, hipStream_t stream) {
+    const long long n_units = layers_units(shape.tiles);
+    if (n_units <= 0) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid));
+    const size_t dyn = ground_lds_bytes(f, shape);
+    if (view == kViewLdsUnposed)
+        hipLaunchKernelGGL(ground_kernel<kViewLdsUnposed>, grid, dim3(kBlock), dyn, stream, f, shape);
+    else if (view == kViewLds)
+        hipLaunchKernelGGL(ground_kernel<kViewLds>, grid, dim3(kBlock), dyn, stream, f, shape);
+    else
+        hipLaunchKernelGGL(ground_kernel<kViewHbm>, grid, dim3(kBlock), dyn, stream, f, shape);
+    return hipGetLastError();
+}
+hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream) {
+    const long long n_units = layers_units(shape.tiles);
+    if (n_units <= 0 || n_frames <= 0) return hipSuccess;
+    if (n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid), static_cast<unsigned>(n_frames));
+    GroundTable table = GroundTable(d_table);
+    if (view == kViewLdsUnposed)
+        hipLaunchKernelGGL(ground_batch_kernel<kViewLdsUnposed>, grid, dim3(kBlock), max_dyn, stream, table, shape);
+    else if (view == kViewLds)
+        hipLaunchKernelGGL(ground_batch_kernel<kViewLds>, grid, dim3(kBlock), max_dyn, stream, table, shape);
+    else
+        hipLaunchKernelGGL(ground_batch_kernel<kViewHbm>, grid, dim3(kBlock), max_dyn, stream, table, shape);
     return hipGetLastError();
 }
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {

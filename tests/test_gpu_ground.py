@@ -1,0 +1,409 @@
+"""The ground-shadow pass on the GPU (mcrt_render_ground*): visibility and distance bit for bit and the matte byte for byte
+against the CPU oracle (tests/ground_checker.py) — skin frames, cameras below and above the plane, lights that defeat the tile
+culling, sample counts, box scenes at their own floor, plane subsets, batches, the host form, a pass beside the handle's render,
+the pass without whole-bundle decisions, and a 1920 x 1080 frame.
+
+So that a plane of ones cannot pass, a case asserts that its expectation holds at least 100 pixels with visibility 0 and at least
+100 with 0 < visibility < 1: the skin frames of 6144 and 4096 pixels, the plane through the legs, the top-down camera, the light
+below the figure's top, the sample counts (113 samples included), the hard light and the one-ray cases (dark only: they have no
+penumbra), the light inside the head (all dark), the batches and the 1080p tiles.  Cases whose frame, camera, light and plane
+are given and whose expectation holds fewer such pixels assert the oracle's EXACT counts (reached, dark, penumbra) instead, so
+that any change of the expectation is noticed: the camera below the plane at 64 x 48 (3072, 64, 15), the light below the ground
+(6144, 17, 16), the light of radius 25 (6144, 35, 2398: the floor holds for its penumbra), the five box scenes at their own floor
+(960, 12, 8 / 80, 0, 0 / 1152, 69, 9 / 1296, 36, 74 / 480, 23, 21), and the small skin frames 33 x 17 (264, 16, 9), 1 x 1 and the
+plane no pixel reaches (0, 0, 0)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import ground_checker as G  # noqa: E402
+import layers_checker as L  # noqa: E402
+import scenes
+from minecraftskin_raytracer_amd import abi
+
+gpu_test = pytest.mark.gpu
+SENTINEL = -12345.0
+MATTE_SENTINEL = 77
+PLANES = G.PLANES
+FLT_MAX = G.FLT_MAX
+ORBIT = (35.0, 35.0, 70.0)  # the camera of the light cases
+
+
+def _buffers(n, stride, names=PLANES):
+    """Device planes for n frames `stride` pixels apart, filled with a sentinel."""
+    return {k: (torch.full((n, stride), MATTE_SENTINEL, dtype=torch.uint8, device="cuda") if k == "matte"
+                else torch.full((n, stride), SENTINEL, dtype=torch.float32, device="cuda")) for k in names}
+
+
+def _ptrs(buf, names):
+    return {f"{k}_ptr": buf[k].data_ptr() for k in names}
+
+
+def _frames(buf, cfg, names):
+    px = cfg.width * cfg.height
+    return {k: buf[k].cpu().numpy()[:, :px].reshape(-1, cfg.height, cfg.width) for k in names}
+
+
+def _untouched(t):
+    return bool((t == (MATTE_SENTINEL if t.dtype == torch.uint8 else SENTINEL)).all().item())
+
+
+def _device_ground(ds, cfg, ground, names=PLANES, stream=None):
+    buf = _buffers(1, cfg.width * cfg.height)
+    ds.render_ground_device(cfg, ground, stream=stream if stream is not None else torch.cuda.current_stream().cuda_stream, **_ptrs(buf, names))
+    torch.cuda.synchronize()
+    return buf, {k: v[0] for k, v in _frames(buf, cfg, names).items()}
+
+
+def _check_both_forms(mcrt, sd, cfg, ground, exp, what):
+    """The one-shot host form and the device form of one frame against the expectation."""
+    got = mcrt.TileRenderer.renderGround(sd, cfg, ground)
+    assert list(got) == list(PLANES)
+    G.assert_ground_equal(got, exp, what)
+    ds = mcrt.DeviceScene(sd)
+    try:
+        G.assert_ground_equal(_device_ground(ds, cfg, ground)[1], exp, what + " (device form)")
+        ds.check()
+    finally:
+        ds.close()
+
+
+def _assert_miss_constants(exp):
+    miss = ~exp["reached"]
+    assert (exp["visibility"][miss] == 1.0).all() and (exp["distance"][miss] == FLT_MAX).all() and (exp["matte"][miss] == 0).all()
+
+
+# name -> (ground height, least dark pixels, least penumbra pixels) the expectation must hold
+SKIN_FRAMES = {
+    "pose0_default_96x64": (0.0, 100, 100),    # 3072 of 6144 reached, 228 dark, 149 penumbra, 59 seeds outside the seed-table window
+    "pose6_orbit_96x64": (0.0, 100, 100),      # 310, 182; posed meshes
+    "pose5_orbit_64x64_t16": (0.0, 100, 100),  # 1101, 459
+    "pose0_33x17_t7": (0.0, 16, 9),            # clipped tiles; the small frames: exact counts (EXACT_REACHED)
+    "pose0_1x1": (0.0, 0, 0),
+    "pose3_orbit_70x50": (0.0, 0, 0),          # no pixel reaches the plane
+    "pose3_orbit_70x50@10": (10.0, 100, 100),  # through the legs: 290, 110
+}
+
+
+EXACT_REACHED = {"pose0_33x17_t7": 264, "pose0_1x1": 0, "pose3_orbit_70x50": 0}
+
+
+@gpu_test
+@pytest.mark.parametrize("case", list(SKIN_FRAMES))
+def test_skin_frames_equal_the_oracle(mcrt, gpu, case):
+    ground, least_dark, least_pen = SKIN_FRAMES[case]
+    sd, cfg, exp = G.skin_expectation(case.split("@")[0], ground)
+    reached, dark, pen = G.counts(exp)
+    print(case, "reached", reached, "dark", dark, "penumbra", pen)
+    assert dark >= least_dark and pen >= least_pen
+    if case in EXACT_REACHED:
+        assert (reached, dark, pen) == (EXACT_REACHED[case], least_dark, least_pen)
+    _assert_miss_constants(exp)
+    if case == "pose0_default_96x64":
+        outside = (exp["seed"][exp["reached"]].astype(np.int64) + (1 << 24)) % (1 << 32) >= (1 << 25)
+        assert reached == 3072 and outside.sum() >= 10  # at the horizon: the 397-step recurrence instead of the table
+    if case == "pose3_orbit_70x50":
+        assert reached == 0
+    _check_both_forms(mcrt, sd, cfg, ground, exp, case)
+
+
+@gpu_test
+@pytest.mark.parametrize("case", ["below_the_plane", "top_down"])
+def test_cameras_below_and_above_the_plane(mcrt, gpu, case):
+    if case == "below_the_plane":  # the plane seen from underneath: N stays (0, 1, 0); 64 dark, 15 penumbra
+        sd, cfg, exp = G.orbit_expectation(0, (30.0, -60.0, 30.0), 64, 48)
+        assert float(sd.desc.camera_position[1]) < 0.0
+    else:  # 572 dark, 298 penumbra
+        sd, cfg, exp = G.orbit_expectation(6, (20.0, 80.0, 60.0), 64, 64)
+    reached, dark, pen = G.counts(exp)
+    print(case, "reached", reached, "dark", dark, "penumbra", pen)
+    if case == "below_the_plane":
+        assert (reached, dark, pen) == (3072, 64, 15)  # the given camera and frame hold no more: the exact counts
+    else:
+        assert dark >= 100 and pen >= 100
+    _check_both_forms(mcrt, sd, cfg, 0.0, exp, case)
+
+
+# light cases on ORBIT at 96 x 64: name -> (pose, light position, radius, least dark, least penumbra); EXACT_LIGHTS: the
+# oracle's exact (dark, penumbra) where the given light leaves fewer than 100
+LIGHTS = {
+    "below_the_figures_top": (6, (30.0, 10.0, 30.0), None, 100, 100),  # 333, 256: the tile culling's fall-back
+    "below_the_ground": (0, (10.0, -5.0, 20.0), None, 17, 16),         # exact
+    "radius_25": (3, None, 25.0, 35, 100),                             # dark exact; penumbra 2398
+    "radius_0": (3, None, 0.0, 100, 0),                                # 597 dark, no penumbra: the one isInShadow ray at S = 8
+    "inside_the_head": (0, (0.0, 28.0, 0.0), None, 6144, 0),           # all dark
+}
+
+
+EXACT_LIGHTS = {"below_the_ground": (17, 16), "radius_25": (35, 2398)}
+
+
+@gpu_test
+@pytest.mark.parametrize("case", list(LIGHTS))
+def test_lights(mcrt, gpu, case):
+    pose, light, radius, least_dark, least_pen = LIGHTS[case]
+    sd, cfg, exp = G.orbit_expectation(pose, ORBIT, 96, 64, light=light, radius=radius)
+    reached, dark, pen = G.counts(exp)
+    print(case, "reached", reached, "dark", dark, "penumbra", pen)
+    assert reached == 6144 and dark >= least_dark and pen >= least_pen
+    if case in EXACT_LIGHTS:
+        assert (dark, pen) == EXACT_LIGHTS[case]
+    if case == "radius_0":
+        assert pen == 0
+    _check_both_forms(mcrt, sd, cfg, 0.0, exp, case)
+
+
+@gpu_test
+@pytest.mark.parametrize("case", ["soft_shadows_off", "samples_1", "samples_3", "samples_113"])
+def test_sample_counts(mcrt, gpu, case):
+    if case == "samples_113":  # the engine's limit; 287 dark, 250 penumbra at 48 x 32
+        sd, cfg, exp = G.orbit_expectation(5, (40.0, 60.0, 28.0), 48, 32, samples=113)
+        least = (100, 100)
+    else:
+        kw = {"soft_shadows_off": dict(soft=False), "samples_1": dict(samples=1), "samples_3": dict(samples=3)}[case]
+        sd, cfg, exp = G.skin_expectation("pose6_orbit_96x64", 0.0, **kw)
+        least = (100, 100) if case == "samples_3" else (100, 0)  # 346 / 113; one ray per pixel: 403 dark, no penumbra
+    reached, dark, pen = G.counts(exp)
+    print(case, "reached", reached, "dark", dark, "penumbra", pen)
+    assert dark >= least[0] and pen >= least[1]
+    if case in ("soft_shadows_off", "samples_1"):
+        assert pen == 0
+    if case == "samples_113":
+        assert len(np.unique(exp["visibility"])) > 20  # multiples of 1/113
+    _check_both_forms(mcrt, sd, cfg, 0.0, exp, case)
+
+
+BOX_COUNTS = {"outer_back_face": (960, 12, 8), "camera_inside": (80, 0, 0), "null_and_empty": (1152, 69, 9), "posed": (1296, 36, 74),
+              "seventy_boxes": (480, 23, 21)}
+
+
+@gpu_test
+@pytest.mark.parametrize("name", L.BOX_CASES)
+def test_box_scenes_at_their_floor(mcrt, gpu, name):
+    sd, cfg, floor, exp = G.box_expectation(name)
+    reached, dark, pen = G.counts(exp)
+    print(name, "floor", floor, "reached", reached, "dark", dark, "penumbra", pen)
+    # the scenes, their frames and their floors are given: the oracle's exact (reached, dark, penumbra)
+    assert (reached, dark, pen) == BOX_COUNTS[name]
+    _check_both_forms(mcrt, sd, cfg, floor, exp, name)
+    got = mcrt.TileRenderer.renderGround(sd, cfg)  # ground=None: the scene's floor
+    G.assert_ground_equal(got, exp, name + " (ground=None)")
+
+
+@gpu_test
+def test_plane_subsets_leave_the_other_planes_alone(mcrt, gpu):
+    sd, cfg, exp = G.skin_expectation("pose3_orbit_70x50", 10.0)
+    assert (exp["matte"] == G.matte_of(exp["visibility"])).all() and len(np.unique(exp["matte"])) >= 5
+    ds = mcrt.DeviceScene(sd)
+    try:
+        subsets = [(a,) for a in PLANES] + [(a, b) for i, a in enumerate(PLANES) for b in PLANES[i + 1:]] + [PLANES]
+        assert len(subsets) == 7
+        for names in subsets:
+            buf, got = _device_ground(ds, cfg, 10.0, names)
+            G.assert_ground_equal(got, exp, "+".join(names))
+            for k in PLANES:
+                if k not in names:
+                    assert _untouched(buf[k]), f"{k} was written although only {names} were asked for"
+            if "matte" in names and "visibility" in names:
+                assert (got["matte"] == G.matte_of(got["visibility"])).all()
+        none, c = abi.McrtGround(None, None, None), cfg.to_c()
+        assert mcrt._lib.load().mcrt_render_ground_device(ds._h, C.byref(c), 10.0, C.byref(none), None) == abi.MCRT_ERR_INVALID
+    finally:
+        ds.close()
+
+
+@gpu_test
+def test_batch_of_five_scenes_at_five_heights_keeps_the_gaps(mcrt, gpu, oracle):
+    cfg = abi.Config(width=64, height=48, tileSize=32)
+    cams = [(0.0, 20.0, 50.0), (60.0, 35.0, 40.0), (200.0, 25.0, 36.0), (310.0, 45.0, 32.0), (135.0, 20.0, 34.0)]
+    sds = [L.skin_case("S64" if k % 2 else "S32", (k * 3) % 7, cams[k]) for k in range(5)]
+    heights = [0.0, -0.5, 3.0, 10.0, 1.25]
+    exps = [G.expected_ground(oracle, sd, cfg, g) for sd, g in zip(sds, heights)]
+    assert sum(G.counts(e)[1] for e in exps) >= 100 and sum(G.counts(e)[2] for e in exps) >= 100
+    handles = [mcrt.DeviceScene(sd) for sd in sds]
+    try:
+        px = cfg.width * cfg.height
+        stride = px + 101  # odd frames start off a 16-byte boundary of the float planes and off a 4-byte boundary of the matte
+        buf = _buffers(5, stride)
+        mcrt.render_ground_batch_device(handles, cfg, heights, frame_stride_pixels=stride, stream=torch.cuda.current_stream().cuda_stream, **_ptrs(buf, PLANES))
+        torch.cuda.synchronize()
+        batch = _frames(buf, cfg, PLANES)
+        for k in PLANES:
+            assert _untouched(buf[k][:, px:]), f"{k}: the pixels between two frames were written"
+        for i in range(5):
+            G.assert_ground_equal({k: v[i] for k, v in batch.items()}, exps[i], f"batch frame {i}")
+        # one handle listed twice, with two heights
+        buf = _buffers(2, px, ("visibility", "matte"))
+        mcrt.render_ground_batch_device([handles[3], handles[3]], cfg, [10.0, 0.0], stream=torch.cuda.current_stream().cuda_stream,
+                                        **_ptrs(buf, ("visibility", "matte")))
+        torch.cuda.synchronize()
+        twice = _frames(buf, cfg, ("visibility", "matte"))
+        G.assert_ground_equal({k: v[0] for k, v in twice.items()}, exps[3], "one handle, first height")
+        G.assert_ground_equal({k: v[1] for k, v in twice.items()}, G.expected_ground(oracle, sds[3], cfg, 0.0), "one handle, second height")
+        # the host wrapper, frame after frame
+        host = mcrt.TileRenderer.renderGroundBatch(sds, cfg, heights)
+        for i in range(5):
+            G.assert_ground_equal({k: v[i] for k, v in host.items()}, exps[i], f"host frame {i}")
+        for h in handles:
+            h.check()
+    finally:
+        for h in handles:
+            h.close()
+
+
+@gpu_test
+def test_batch_beyond_the_frames_of_one_launch(mcrt, gpu, oracle):
+    n = 4096 + 1  # one launch takes 4096 frames (blockIdx.y)
+    cfg = abi.Config(width=8, height=8, tileSize=8)
+    sds = [L.skin_case("S64", 6, (20.0, 80.0, 60.0)), L.skin_case("S64", 0, (135.0, 50.0, 34.0))]
+    heights = [0.0, 10.0, 4.0]
+    exps = [G.expected_ground(oracle, sds[i % 2], cfg, heights[i % 3]) for i in range(6)]  # every (scene, height) pair
+    assert any(G.counts(e)[1] for e in exps) and all(G.counts(e)[0] == 64 for e in exps)
+    handles = [mcrt.DeviceScene(sd) for sd in sds]
+    try:
+        px = cfg.width * cfg.height
+        buf = _buffers(n, px, ("visibility", "distance"))
+        mcrt.render_ground_batch_device([handles[i % 2] for i in range(n)], cfg, [heights[i % 3] for i in range(n)],
+                                        stream=torch.cuda.current_stream().cuda_stream, **_ptrs(buf, ("visibility", "distance")))
+        torch.cuda.synchronize()
+        got = _frames(buf, cfg, ("visibility", "distance"))
+        for k in ("visibility", "distance"):
+            want = np.stack([exps[i % 6][k] for i in range(n)])
+            assert np.array_equal(got[k].view(np.uint32), want.view(np.uint32)), k
+    finally:
+        for h in handles:
+            h.close()
+
+
+@gpu_test
+def test_ground_none_is_the_scenes_floor(mcrt, gpu, oracle):
+    cfg = abi.Config(width=64, height=48, tileSize=32)
+    sd = L.skin_case("S64", 4, (60.0, 35.0, 40.0))
+    floor = mcrt.scene_floor(sd)
+    assert floor == 9.5  # the pose lifts the figure: the plane is not the builder's y = 0
+    exp = G.expected_ground(oracle, sd, cfg, floor)
+    assert G.counts(exp)[1] >= 100
+    G.assert_ground_equal(mcrt.TileRenderer.renderGround(sd, cfg), exp, "ground=None")
+    G.assert_ground_equal(mcrt.TileRenderer.renderGround(sd, cfg, floor, planes=("matte",)), {"matte": exp["matte"]}, "matte alone")
+    both = mcrt.TileRenderer.renderGroundBatch([sd, sd], cfg, None, planes=("distance", "visibility"))
+    assert list(both) == ["visibility", "distance"]
+    for i in range(2):
+        G.assert_ground_equal({k: v[i] for k, v in both.items()}, exp, f"batch wrapper frame {i}")
+
+
+@gpu_test
+def test_ground_pass_beside_the_beauty_render_of_one_handle(mcrt, gpu):
+    sd, gcfg, exp = G.skin_expectation("pose0_default_96x64")
+    cfg = abi.Config(width=96, height=64, samplesPerPixel=2)  # the reference's defaults otherwise: 3 bounces, soft shadows
+    ds = mcrt.DeviceScene(sd)
+    try:
+        main, side = torch.cuda.Stream(), torch.cuda.Stream()
+        first = torch.zeros((cfg.height, cfg.width, 4), dtype=torch.float32, device="cuda")
+        second = torch.zeros_like(first)
+        single = torch.zeros_like(first)
+        buf = _buffers(1, cfg.width * cfg.height)
+        ds.render_device(cfg, single.data_ptr(), 0, 1, abi.LAYOUT_FRAME, main.cuda_stream)
+        ds.check()
+        torch.cuda.synchronize()
+        ds.render_device(cfg, first.data_ptr(), 0, 1, abi.LAYOUT_FRAME, main.cuda_stream)
+        ds.render_ground_device(gcfg, 0.0, stream=side.cuda_stream, **_ptrs(buf, PLANES))  # no wait for the render: it reads the scene alone
+        ds.render_device(cfg, second.data_ptr(), 0, 1, abi.LAYOUT_FRAME, main.cuda_stream)
+        ds.check()  # waits for all three
+        torch.cuda.synchronize()
+        scenes.assert_bit_equal(first.cpu().numpy(), single.cpu().numpy(), "beauty before the ground pass")
+        scenes.assert_bit_equal(second.cpu().numpy(), single.cpu().numpy(), "beauty after the ground pass")
+        assert float(single[..., 3].min().item()) > 0.0  # an opaque frame was rendered
+        G.assert_ground_equal({k: v[0] for k, v in _frames(buf, gcfg, PLANES).items()}, exp, "ground pass beside the render")
+    finally:
+        ds.close()
+
+
+def _child(argv):
+    """A fresh process: the frame of a skin case through the host form, saved as .npz (the development knobs are read once)."""
+    import minecraftskin_raytracer_amd as M
+
+    sd, cfg, _ = G.skin_expectation(argv[0])
+    got = M.TileRenderer.renderGround(sd, cfg, 0.0)
+    np.savez(argv[1], **got)
+
+
+@gpu_test
+def test_without_bundle_decisions_the_planes_are_the_same(mcrt, gpu, tmp_path):
+    sd, cfg, exp = G.skin_expectation("pose6_orbit_96x64")
+    assert G.counts(exp)[1] >= 100 and G.counts(exp)[2] >= 100
+    out = str(tmp_path / "traced.npz")
+    env = dict(os.environ, MCRT_BUNDLE_DECISIONS="0")
+    subprocess.run([sys.executable, os.path.abspath(__file__), "pose6_orbit_96x64", out], env=env, check=True, timeout=300)
+    z = np.load(out)
+    G.assert_ground_equal({k: z[k] for k in PLANES}, exp, "MCRT_BUNDLE_DECISIONS=0")
+
+
+@gpu_test
+def test_full_hd_frame(mcrt, gpu, oracle):
+    """1920 x 1080, pose 0, default camera: the rows above the horizon hold the miss constants, every visibility is a multiple of
+    1/8, and at most 16 tiles equal the oracle bit for bit — the tiles whose centre pixel is not fully lit in an oracle pre-pass
+    over the 1020 tile centres of the lower half (106 of them), evenly thinned to 14, one corner tile and one tile of the tile row
+    the horizon runs through."""
+    w, h, tile = 1920, 1080, 32
+    sd = L.skin_case("S64", 0)
+    cfg = abi.Config(width=w, height=h, tileSize=tile)
+    ds = mcrt.DeviceScene(sd)
+    try:
+        got = _device_ground(ds, cfg, 0.0)[1]
+        ds.check()
+    finally:
+        ds.close()
+    assert (got["visibility"][:540] == 1.0).all() and (got["distance"][:540] == FLT_MAX).all() and (got["matte"][:540] == 0).all()
+    assert (got["distance"][540:] < FLT_MAX).all()
+    eighths = got["visibility"] * np.float32(8.0)
+    assert (eighths == np.round(eighths)).all() and eighths.min() >= 0.0 and eighths.max() <= 8.0
+    assert (got["matte"] == G.matte_of(got["visibility"])).all()
+
+    def expect(xs, ys):
+        """visibility, distance of the pixels (xs, ys) from the oracle"""
+        aspect = np.float32(w) / np.float32(h)
+        rays = np.stack([oracle.camera_ray(sd.ptr, float((np.float32(x) + np.float32(0.5)) / np.float32(w)),
+                                           float((np.float32(y) + np.float32(0.5)) / np.float32(h)), float(aspect)) for x, y in zip(xs, ys)])
+        reached, t, P, sums = G.plane_points(rays, 0.0)
+        vis = np.ones(len(xs), np.float32)
+        idx = np.flatnonzero(reached)
+        vis[idx] = G.visibility_at(oracle, sd, P[idx], sums[idx], 8)
+        return vis, np.where(reached, t, FLT_MAX).astype(np.float32)
+
+    rows = range(17, 34)  # the tile rows wholly below the horizon
+    centres = [(tx, ty) for ty in rows for tx in range(60)]
+    assert len(centres) == 1020
+    cx = [tx * tile + 16 for tx, ty in centres]
+    cy = [ty * tile + min(tile, h - ty * tile) // 2 for tx, ty in centres]
+    centre_vis, _ = expect(cx, cy)
+    shadowed = [c for c, v in zip(centres, centre_vis) if v < 1.0]
+    print("tile centres not fully lit:", len(shadowed))
+    assert len(shadowed) >= 50
+    chosen = [shadowed[i] for i in np.linspace(0, len(shadowed) - 1, 14).round().astype(int)]
+    chosen += [(0, 33), (30, 16)]
+    assert len(set(chosen)) <= 16
+    dark = pen = 0
+    for tx, ty in sorted(set(chosen)):
+        x0, y0 = tx * tile, ty * tile
+        tw, th = min(tile, w - x0), min(tile, h - y0)
+        ys, xs = np.mgrid[y0:y0 + th, x0:x0 + tw]
+        vis, dist = expect(xs.ravel(), ys.ravel())
+        scenes.assert_bit_equal(got["visibility"][y0:y0 + th, x0:x0 + tw], vis.reshape(th, tw), f"tile ({tx}, {ty}) visibility")
+        scenes.assert_bit_equal(got["distance"][y0:y0 + th, x0:x0 + tw], dist.reshape(th, tw), f"tile ({tx}, {ty}) distance")
+        dark += int((vis == 0).sum())
+        pen += int(((vis > 0) & (vis < 1)).sum())
+    print("checked tiles: dark", dark, "penumbra", pen)
+    assert dark >= 100 and pen >= 100
+
+
+if __name__ == "__main__":
+    _child(sys.argv[1:])
