@@ -423,6 +423,44 @@ int mcrt_render_ground(const mcrt_scene_desc* scene, const mcrt_config* cfg, flo
  * standing poses) for a contact shadow.  A scene without a vertex (or a NULL argument) → MCRT_ERR_INVALID. */
 int mcrt_scene_floor(const mcrt_scene_desc* scene, float* y);
 
+/* ---- skins on resident scenes: a new skin for a scene that is already on the device -----------------------------------------
+ * Everything in a flattened skin scene but its texels is a function of pose, camera and light alone.  A REPAINTABLE handle takes
+ * a new skin from a 64 x skin_height RGBA8 image in device memory with one small kernel — no scene build, no flattening, no upload
+ * of the blob — and one launch repaints a whole batch of handles.
+ * A repaintable handle ALWAYS holds the full mesh table of its skin kind, the one mcrt_skin_texel describes: 12 meshes for a
+ * 64x64 skin, 7 for a 64x32 one.  mcrt_build_skin_scene (like the reference's MeshBuilder::buildScene) drops an outer part whose
+ * texels are all transparent; here that part stays, with its texels at alpha 0.  The frames are the same bit for bit: an outer
+ * box whose texels all have alpha 0 never produces a hit (intersection.cpp:311-360 finds the entry and the exit face transparent
+ * and returns a miss, and intersectScene keeps only hits).  The id layer's mesh index of such a handle therefore always follows
+ * mcrt_skin_texel's table: the "later meshes move up" caveat there does not apply.
+ *
+ * mcrt_scene_create_skin: the builder's figure for skin_height 64 or 32 at `pose` (NULL: pose 0) with every part present.  Of
+ * `look` (NULL: the builder's defaults) the light, camera and background fields are copied; its meshes and textures are ignored.
+ * Until the first repaint the texels are those of an all-(255,255,255,255) skin.  The handle is an ordinary mcrt_scene for every
+ * other call. */
+int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_scene_desc* look, int device, mcrt_scene** out);
+/* Repaints the handle from d_skin_rgba8: 64 * skin_height * 4 bytes of DEVICE memory, row-major, aligned to at least 4 bytes.
+ * Asynchronous on `stream` (not into a graph being recorded on it).  Afterwards the resident blob is byte for byte what
+ * mcrt_scene_flatten gives for the full-table scene with that skin's texels: texel = u8 / 255.0f (the floats are formed on the
+ * host), the alpha predicate words, and MESH_OPAQUE on a mesh iff none of its texels has alpha 0.
+ * Ordering: the repaint waits for the handle's earlier renders (mcrt_render_device[_ex], its frame of mcrt_render_batch_device)
+ * and earlier repaints, and the handle's next render waits for the repaint, whatever streams they are given — the handle's event
+ * chain, as for mcrt_render_batch_device.  Layers, ground and pick passes of the handle take none of its events: ordering THOSE
+ * against a repaint (stream order, or an event of the caller's) is the caller's job. */
+int mcrt_scene_set_skin_device(mcrt_scene* scene, const uint8_t* d_skin_rgba8, void* stream);
+/* One launch repaints n handles; skin i starts at d_skins + i * skin_stride_bytes.  The stride is at least the image size and a
+ * multiple of 4.  The handles are of one skin kind, on one device, none listed twice.  n = 0: MCRT_OK, nothing done. */
+int mcrt_scene_set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t skin_stride_bytes, void* stream);
+/* The host form: uploads the 16 KB (8 KB) image from HOST memory and repaints, synchronously. */
+int mcrt_scene_set_skin(mcrt_scene* scene, const uint8_t* skin_rgba8);
+/* Host only.  For each texel of the full-table figure's pool, in pool order (meshes, their face slots 0..5, a face's texels
+ * row-major), the skin pixel index y * 64 + x the texel is cut from, by the tables of mcrt_skin_texel (a legacy skin's mirrored
+ * limbs included).  Returns the count — 3264 for skin_height 64, 2016 for 32 — and writes min(count, capacity) entries. */
+int mcrt_skin_pool_map(int skin_height, int32_t* out, int capacity);
+/* MCRT_ERR_INVALID, before any device work: a NULL handle, entry, image or `out`; a skin_height other than 64 or 32; n < 0; a
+ * stride that is no multiple of 4 or smaller than the image; an image that is not 4-byte aligned; a handle that
+ * mcrt_scene_create_skin did not create; handles of different skin kinds or devices in one batch; a handle listed twice. */
+
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);
 
@@ -503,6 +541,10 @@ typedef struct mcrt_hit {
     int32_t is_outer_layer;
 } mcrt_hit;
 
+/* Waits for the device, then downloads the scene's resident blob (what mcrt_scene_flatten gave at creation, as later repaints
+ * left it) into out.  Returns the blob's size in bytes — never below 192, the header's size — and copies min(size, capacity);
+ * on failure an MCRT_ERR_* code (all of them below 192; a NULL argument: MCRT_ERR_INVALID). */
+int mcrt_probe_scene_blob(mcrt_scene* scene, void* out, size_t capacity);
 /* intersectScene (intersection.cpp:408-421) for n rays; rays = n*6 floats (origin, direction) */
 int mcrt_probe_intersect(mcrt_scene* scene, const float* rays, int n, mcrt_hit* out);
 /* RayTracer::traceRay(ray, scene, depth, maxBounces, ShadingParams{}, &cfg) (raytracer.cpp:82-148)

@@ -3,6 +3,7 @@ from .abi import Config, Mesh, Scene, Texture  # noqa: F401
 from .skins import synthetic_skin  # noqa: F401
 from .api import (  # noqa: F401
     DeviceScene,
+    SkinBatch,
     assemble_frame_device,
     bg_plate_info,
     draw_plate_info,
@@ -23,6 +24,8 @@ from .api import (  # noqa: F401
     render_layers_batch_device,
     render_ground_batch_device,
     scene_floor,
+    set_skins_batch_device,
+    skin_pool_map,
     skin_texel,
     render_png,
     trim,
@@ -34,5 +37,5 @@ __all__ = [
     "TileRenderer", "device_count", "flatten", "getBuiltinPoses", "probe_detmath", "probe_detmath_range",
     "probe_mt_uniform", "quantize_rgba8", "quantize_rgba8_device", "unpack_rows_device", "ImageWriter", "render_png", "assemble_frame_device", "trim",
     "render_batch_device", "last_batch_info", "bg_plate_info", "draw_plate_info", "render_layers_batch_device", "skin_texel",
-    "render_ground_batch_device", "scene_floor",
+    "render_ground_batch_device", "scene_floor", "SkinBatch", "set_skins_batch_device", "skin_pool_map",
 ]

@@ -29,6 +29,8 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_layers_device", "mcrt_render_layers_batch_device", "mcrt_render_layers", "mcrt_render_layers_batch",
     "mcrt_scene_pick", "mcrt_skin_texel",
     "mcrt_render_ground_device", "mcrt_render_ground_batch_device", "mcrt_render_ground", "mcrt_scene_floor",
+    "mcrt_scene_create_skin", "mcrt_scene_set_skin_device", "mcrt_scene_set_skins_batch_device", "mcrt_scene_set_skin",
+    "mcrt_skin_pool_map", "mcrt_probe_scene_blob",
 ]
 
 
@@ -81,6 +83,12 @@ def load():
         "mcrt_scene_floor": (C.c_int, [desc_p, f_p]),
         "mcrt_scene_pick": (C.c_int, [vp, cfg_p, abi.c_int32_p, C.c_int, vp]),
         "mcrt_skin_texel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mcrt_scene_create_skin": (C.c_int, [C.c_int, f_p, desc_p, C.c_int, C.POINTER(vp)]),
+        "mcrt_scene_set_skin_device": (C.c_int, [vp, vp, vp]),
+        "mcrt_scene_set_skins_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_size_t, vp]),
+        "mcrt_scene_set_skin": (C.c_int, [vp, u8_p]),
+        "mcrt_skin_pool_map": (C.c_int, [C.c_int, abi.c_int32_p, C.c_int]),
+        "mcrt_probe_scene_blob": (C.c_int, [vp, vp, C.c_size_t]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),
         "mcrt_encode_png_rgba8": (C.c_size_t, [u8_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
         "mcrt_write_png_f32": (C.c_int, [C.c_char_p, f_p, C.c_int, C.c_int]),

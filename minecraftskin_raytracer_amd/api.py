@@ -442,15 +442,91 @@ def render_png(scene, config: Config, path: str, device: int = 0, background: st
     return load().mcrt_render_png(_as_desc(scene).ptr, C.byref(c), os.fsencode(path), device) == 0
 
 
+SKIN_HEIGHTS = {"S64": 64, "S32": 32, 64: 64, 32: 32}
+
+
+def _skin_height(kind) -> int:
+    if isinstance(kind, bool) or kind not in SKIN_HEIGHTS:
+        raise ValueError("kind must be 'S64', 'S32', 64 or 32")
+    return SKIN_HEIGHTS[kind]
+
+
+def skin_pool_map(kind) -> np.ndarray:
+    """Per texel of the pool of a repaintable scene (``DeviceScene.for_skin``), in pool order, the skin pixel index
+    ``y * 64 + x`` it is cut from (mcrt_skin_pool_map): 3264 int32 for ``"S64"``, 2016 for ``"S32"``."""
+    h = _skin_height(kind)
+    lib = load()
+    out = np.zeros(3264 if h == 64 else 2016, np.int32)
+    n = lib.mcrt_skin_pool_map(h, out.ctypes.data_as(abi.c_int32_p), len(out))
+    if n != len(out):
+        raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
+    return out
+
+
 class DeviceScene:
     """A flattened scene resident in HBM on one device (mcrt_scene).  Renders go to device pointers
     (e.g. ``torch.Tensor.data_ptr()``) on a caller-chosen HIP stream."""
+
+    skin_height = 0  # 64 / 32 for a repaintable scene (for_skin)
 
     def __init__(self, scene, device: int = 0):
         self._desc = _as_desc(scene)
         self._h = C.c_void_p()
         self.device = device
         check(load().mcrt_scene_create(self._desc.ptr, device, C.byref(self._h)))
+
+    @classmethod
+    def for_skin(cls, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0) -> "DeviceScene":
+        """A REPAINTABLE scene (mcrt_scene_create_skin): the builder's figure for ``kind`` (``"S64"`` / ``"S32"`` or the skin's
+        height) at ``pose`` with every part present — always the full mesh table of ``skin_texel``, 12 or 7 meshes — which
+        ``set_skin`` / ``set_skin_device`` / ``set_skins_batch_device`` give a new skin without rebuilding the scene.  ``look``:
+        a ``Scene`` / ``SceneDesc`` whose light, camera and background are taken (its meshes are ignored); ``None``: the
+        builder's.  White and opaque until the first repaint."""
+        h = _skin_height(kind)
+        self = object.__new__(cls)
+        self._desc = _as_desc(look) if look is not None else None
+        self._h = C.c_void_p()
+        self.device = device
+        self.skin_height = h
+        p = np.ascontiguousarray(pose, np.float32) if pose is not None else None
+        if p is not None and p.shape != (12,):
+            raise ValueError("pose must hold 12 floats")
+        check(load().mcrt_scene_create_skin(h, abi.fptr(p) if p is not None else None, self._desc.ptr if self._desc is not None else None,
+                                            int(device), C.byref(self._h)))
+        return self
+
+    def _skin_bytes(self) -> int:
+        if not self.skin_height:
+            raise ValueError("not a repaintable scene: create it with DeviceScene.for_skin")
+        return 64 * self.skin_height * 4
+
+    def set_skin(self, skin: np.ndarray) -> None:
+        """Repaint from a host image, (skin_height, 64, 4) uint8; synchronous (mcrt_scene_set_skin)."""
+        n = self._skin_bytes()
+        a = np.ascontiguousarray(skin, np.uint8)
+        if a.shape != (self.skin_height, 64, 4):
+            raise ValueError(f"skin must be ({self.skin_height}, 64, 4) uint8")
+        assert a.nbytes == n
+        check(load().mcrt_scene_set_skin(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def set_skin_device(self, ptr: int, stream: int = 0) -> None:
+        """Repaint from 64 * skin_height * 4 bytes of RGBA8 in device memory, 4-byte aligned; asynchronous on ``stream``
+        (mcrt_scene_set_skin_device).  The handle's renders are ordered against it by the library; its layers, ground and
+        pick passes by the caller."""
+        self._skin_bytes()
+        check(load().mcrt_scene_set_skin_device(self._h, C.c_void_p(ptr or None), C.c_void_p(stream)))
+
+    def blob(self) -> bytes:
+        """The scene's resident blob, downloaded after waiting for the device (mcrt_probe_scene_blob)."""
+        lib = load()
+        head = C.create_string_buffer(192)
+        n = lib.mcrt_probe_scene_blob(self._h, head, 192)
+        if n < 192:
+            raise McrtError(n, lib.mcrt_last_error().decode("utf-8", "replace"))
+        buf = C.create_string_buffer(n)
+        if lib.mcrt_probe_scene_blob(self._h, buf, n) != n:
+            raise McrtError(abi.MCRT_ERR_HIP, lib.mcrt_last_error().decode("utf-8", "replace"))
+        return buf.raw
 
     def close(self):
         if self._h:
@@ -629,6 +705,138 @@ def render_ground_batch_device(device_scenes: Sequence["DeviceScene"], config: C
     c = config.to_c()
     planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
     check(load().mcrt_render_ground_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+
+
+def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, skin_stride_bytes: Optional[int] = None, stream: int = 0) -> None:
+    """One launch repaints N repaintable scenes of one skin kind (mcrt_scene_set_skins_batch_device): skin i is the RGBA8 image
+    at ``ptr + i * skin_stride_bytes`` in device memory (default: the image size, 64 * height * 4).  Asynchronous on ``stream``."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    n = len(handles)
+    if skin_stride_bytes is None:
+        skin_stride_bytes = device_scenes[0]._skin_bytes() if n else 64 * 64 * 4
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    check(load().mcrt_scene_set_skins_batch_device(arr, n, C.c_void_p(ptr or None), int(skin_stride_bytes), C.c_void_p(stream)))
+
+
+class SkinBatch:
+    """The farm case: ``n`` repaintable scenes of one skin kind, pose and look resident on ``device``, and a skin buffer there.
+    ``render(skins, config)`` gives the frames of ``m <= n`` skins with ONE upload (the images, 16 KB each), one repaint launch,
+    one ``render_batch_device`` call and one download — what ``TileRenderer.renderBatch([MeshBuilder.buildScene(s, pose) ...])``
+    returns, bit for bit, without building, flattening and uploading a scene per skin.  Device memory through torch."""
+
+    def __init__(self, n: int, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0):
+        import torch
+
+        self.kind_height = _skin_height(kind)
+        self.device = int(device)
+        self._torch = torch
+        self.scenes: List[DeviceScene] = []
+        try:
+            for _ in range(int(n)):
+                self.scenes.append(DeviceScene.for_skin(self.kind_height, pose, look, device))
+        except Exception:
+            self.close()
+            raise
+        self._dev = torch.device("cuda", self.device)
+        self._skins = torch.zeros((max(int(n), 1), self.kind_height, 64, 4), dtype=torch.uint8, device=self._dev)
+        self._staging = torch.zeros(self._skins.shape, dtype=torch.uint8).pin_memory()
+        self._out = {}  # (bytes per frame) -> device buffer, pinned host buffer
+        self._mode = None
+
+    def close(self) -> None:
+        for s in self.scenes:
+            s.close()
+        self.scenes = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_skins(self, skins) -> np.ndarray:
+        a = np.ascontiguousarray(skins, np.uint8)
+        if a.ndim != 4 or a.shape[1:] != (self.kind_height, 64, 4) or len(a) > len(self.scenes):
+            raise ValueError(f"skins must be (m <= {len(self.scenes)}, {self.kind_height}, 64, 4) uint8")
+        return a
+
+    def _paint(self, skins, stream) -> int:
+        """Uploads and repaints; every caller synchronises `stream` before it returns (the pinned staging buffer is reused)."""
+        torch = self._torch
+        a = self._check_skins(skins)
+        m = len(a)
+        if m:
+            self._staging[:m].numpy()[...] = a
+            with torch.cuda.stream(stream):
+                self._skins[:m].copy_(self._staging[:m], non_blocking=True)
+            set_skins_batch_device(self.scenes[:m], self._skins.data_ptr(), stream=stream.cuda_stream)
+        return m
+
+    def _buffers(self, key, shape, dtype):
+        torch = self._torch
+        got = self._out.get(key)
+        if got is None or got[0].shape != shape or got[0].dtype != dtype:
+            got = (torch.empty(shape, dtype=dtype, device=self._dev), torch.empty(shape, dtype=dtype).pin_memory())
+            self._out[key] = got
+        return got
+
+    def render(self, skins, config: Config, rgba8: bool = False, background: str = "reference") -> np.ndarray:
+        """``skins``: (m <= n, H, 64, 4) uint8.  Returns (m, height, width, 4) float32, or uint8 with ``rgba8``."""
+        torch = self._torch
+        mode = abi.background_mode(background)
+        w, h = max(config.width, 0), max(config.height, 0)
+        with torch.cuda.device(self._dev):
+            stream = torch.cuda.current_stream()
+            if w == 0 or h == 0 or config.tileSize <= 0:  # no frame: nothing is painted either (the staging buffer stays idle)
+                m = len(self._check_skins(skins))
+                out = np.zeros((m, h, w, 4), np.uint8 if rgba8 else np.float32)
+                out[..., 3] = 255 if rgba8 else 1.0
+                return out
+            m = self._paint(skins, stream)
+            dtype = torch.uint8 if rgba8 else torch.float32
+            if m == 0:
+                return np.zeros((0, h, w, 4), np.uint8 if rgba8 else np.float32)
+            if mode != self._mode:
+                for s in self.scenes:
+                    s.set_background(background)
+                self._mode = mode
+            dev, host = self._buffers("frames", (len(self.scenes), h, w, 4), dtype)
+            render_batch_device(self.scenes[:m], config, 0 if rgba8 else dev.data_ptr(), dev.data_ptr() if rgba8 else 0, w * h, stream.cuda_stream)
+            with torch.cuda.stream(stream):
+                host[:m].copy_(dev[:m], non_blocking=True)
+            stream.synchronize()
+            return host[:m].numpy().copy()
+
+    def layers(self, skins, config: Config, layers=abi.LAYER_NAMES) -> dict:
+        """The geometry layers of the ``m`` skins' frames (``TileRenderer.renderLayersBatch``'s planes) through
+        ``render_layers_batch_device``, behind the repaint on the same stream."""
+        torch = self._torch
+        names = abi.layer_names(layers)
+        w, h = max(config.width, 0), max(config.height, 0)
+        with torch.cuda.device(self._dev):
+            stream = torch.cuda.current_stream()
+            if w == 0 or h == 0 or config.tileSize <= 0:  # no frame: nothing is painted either
+                return {k: _empty_layer(k, len(self._check_skins(skins)), h, w) for k in names}
+            m = self._paint(skins, stream)
+            if m == 0:
+                return {k: _empty_layer(k, 0, h, w) for k in names}
+            n = len(self.scenes)
+            bufs = {}
+            for k in names:
+                dtype, comps = abi.LAYER_FORMATS[k]
+                shape = (n, h, w) + ((comps,) if comps > 1 else ())
+                bufs[k] = self._buffers(k, shape, torch.int32 if dtype is np.int32 else torch.float32)
+            render_layers_batch_device(self.scenes[:m], config, frame_stride_pixels=w * h, stream=stream.cuda_stream,
+                                       **{f"{k}_ptr": bufs[k][0].data_ptr() for k in names})
+            with torch.cuda.stream(stream):
+                for k in names:
+                    bufs[k][1][:m].copy_(bufs[k][0][:m], non_blocking=True)
+            stream.synchronize()
+            return {k: bufs[k][1][:m].numpy().copy() for k in names}
 
 
 def last_batch_info() -> dict:

@@ -123,6 +123,9 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     }
     s->forced_lanes = 0;
     s->background = MCRT_BACKGROUND_REFERENCE;
+    if (s->skin_tables) release_skin_tables(device, s->skin_height);  // a pooled shell that was a repaintable handle
+    s->skin_tables = nullptr;
+    s->skin_height = 0;
     s->budget = 0;  // a budget halved under memory pressure is not inherited
     s->have_last = false;  // a pooled shell was synchronised when its previous owner let go of it
     s->last_stream = nullptr;
@@ -170,6 +173,43 @@ int mcrt_scene_create(const mcrt_scene_desc* desc, int device, mcrt_scene** out)
     std::string err;
     if (!flatten_scene(desc, b, err)) return fail(MCRT_ERR_INVALID, err);
     return create_scene_from_blob(b, device, out);
+}
+
+int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_scene_desc* look, int device, mcrt_scene** out) {
+    if (!out) return fail(MCRT_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (skin_height != 64 && skin_height != 32) return fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    // the builder's figure of an all-opaque white skin: no outer part is dropped, so the mesh table is the full one of
+    // mcrt_skin_texel (12 meshes, or 7) and the pool holds a slot for every texel a skin of this kind can show
+    const std::vector<uint8_t> white(static_cast<size_t>(64) * static_cast<size_t>(skin_height) * 4, 255);
+    mcrt_scene_desc* desc = nullptr;
+    if (mcrt_build_skin_scene(white.data(), 64, skin_height, pose, &desc) != MCRT_OK || !desc) return fail(MCRT_ERR_INVALID, "the scene builder failed");
+    if (look) {
+        std::memcpy(desc->light_position, look->light_position, sizeof desc->light_position);
+        std::memcpy(desc->light_color, look->light_color, sizeof desc->light_color);
+        desc->light_intensity = look->light_intensity;
+        desc->light_radius = look->light_radius;
+        std::memcpy(desc->camera_position, look->camera_position, sizeof desc->camera_position);
+        std::memcpy(desc->camera_target, look->camera_target, sizeof desc->camera_target);
+        std::memcpy(desc->camera_up, look->camera_up, sizeof desc->camera_up);
+        desc->camera_fov = look->camera_fov;
+        std::memcpy(desc->background_color, look->background_color, sizeof desc->background_color);
+    }
+    std::vector<uint8_t> b;
+    std::string err;
+    const bool flat = flatten_scene(desc, b, err);
+    mcrt_scene_desc_free(desc);
+    if (!flat) return fail(MCRT_ERR_INVALID, err);
+    mcrt_scene* s = nullptr;
+    if (const int rc = create_scene_from_blob(b, device, &s); rc != MCRT_OK) return rc;
+    s->skin_tables = acquire_skin_tables(device, skin_height);
+    if (!s->skin_tables) {
+        mcrt_scene_destroy(s);
+        return fail(MCRT_ERR_HIP, "the device's repaint tables could not be built");
+    }
+    s->skin_height = skin_height;
+    *out = s;
+    return MCRT_OK;
 }
 
 void mcrt_scene_destroy(mcrt_scene* s) {

@@ -403,6 +403,65 @@ void acquire_plates(mcrt_scene* s, RenderParams* p, int n, bool capturing, bool 
     for (int i = 0; i < n; ++i) p[i].bg_plate = pixels, p[i].draw_plate = draws;
 }
 
+// ---- per-device repaint tables (kernels.h: SkinPaintShape), one per skin kind: the 256 floats i / 255.0f — formed HERE, on
+// the host, by the scene builder's own expression, so a repainted texel is the builder's float whatever the device's divide
+// does — then per pool texel (mesh << 12) | skin pixel, from the builder's tables (scene_builder.cpp).  6.6 KB and 4.9 KB;
+// a `users` count of the handles that hold them, like the seed tables.
+extern "C" int mcrt_detail_skin_pool(int skin_height, int32_t* pixel, int32_t* mesh_of, int capacity);  // scene_builder.cpp
+namespace {
+struct SkinTables {
+    void* ptr = nullptr;
+    int users = 0;
+};
+std::mutex g_skin_mutex;
+std::vector<SkinTables> g_skin_tables[2];  // [skin_height == 32], by device
+}  // namespace
+
+const void* acquire_skin_tables(int device, int skin_height) {
+    std::lock_guard<std::mutex> lock(g_skin_mutex);
+    std::vector<SkinTables>& by_device = g_skin_tables[skin_height == 32 ? 1 : 0];
+    if (by_device.size() <= static_cast<size_t>(device)) by_device.resize(static_cast<size_t>(device) + 1);
+    SkinTables& t = by_device[static_cast<size_t>(device)];
+    if (!t.ptr) {
+        int32_t pixel[kSkinMaxTexels], mesh_of[kSkinMaxTexels];
+        const int n = mcrt_detail_skin_pool(skin_height, pixel, mesh_of, kSkinMaxTexels);  // (writes kSkinMaxTexels entries at most)
+        if (n <= 0 || n > kSkinMaxTexels) return nullptr;  // the builder's tables outgrew the kernel's: no repaint, never an over-read
+        std::vector<uint8_t> host(skin_tables_bytes(n));
+        float* unit = reinterpret_cast<float*>(host.data());
+        for (int i = 0; i < 256; ++i) unit[i] = static_cast<uint8_t>(i) / 255.0f;  // image.cpp:16-21, as mcrt_build_skin_scene
+        uint16_t* map = reinterpret_cast<uint16_t*>(unit + 256);
+        for (int i = 0; i < n; ++i) map[i] = static_cast<uint16_t>((mesh_of[i] << 12) | pixel[i]);
+        void* p = nullptr;
+        if (hipMalloc(&p, host.size()) != hipSuccess || hipMemcpy(p, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            if (p) (void)hipFree(p);
+            return nullptr;
+        }
+        t.ptr = p;
+    }
+    ++t.users;
+    return t.ptr;
+}
+void release_skin_tables(int device, int skin_height) {
+    std::lock_guard<std::mutex> lock(g_skin_mutex);
+    std::vector<SkinTables>& by_device = g_skin_tables[skin_height == 32 ? 1 : 0];
+    if (static_cast<size_t>(device) < by_device.size() && by_device[static_cast<size_t>(device)].users > 0) --by_device[static_cast<size_t>(device)].users;
+}
+namespace {
+void free_unused_skin_tables() {  // mcrt_trim
+    std::lock_guard<std::mutex> lock(g_skin_mutex);
+    for (auto& by_device : g_skin_tables)
+        for (size_t d = 0; d < by_device.size(); ++d) {
+            SkinTables& t = by_device[d];
+            if (t.ptr && t.users == 0) {
+                (void)hipSetDevice(static_cast<int>(d));
+                (void)hipFree(t.ptr);
+                t.ptr = nullptr;
+            }
+        }
+}
+}  // namespace
+
 // keeps `s` for reuse unless it is large — MCRT_POOL_MB, by default a twelfth of the device's memory (24 GB of the
 // MI355X's 288: the 1080p and 4K frames of BASELINE.json stay pooled, and a host application that never calls
 // mcrt_trim() does not sit on a fifth of the card; the one-shot entry points plan their workspace to stay below it, see
@@ -448,6 +507,7 @@ void destroy_scene_now(mcrt_scene* s) {
     unregister_live(s);  // before its events go
     if (s->holds_seed_table) g_window_tables.release(s->device);
     if (s->holds_full_table) g_full_tables.release(s->device);
+    if (s->skin_tables) release_skin_tables(s->device, s->skin_height);
     release_plates(s);
     s->blob.release();  // the other buffers are released by their destructors below
     for (auto& ln : s->lanes) {
@@ -554,6 +614,7 @@ void mcrt_trim(void) {
     }
     g_full_tables.free_unused();
     g_window_tables.free_unused();
+    free_unused_skin_tables();
     free_unused_plates();
 }
 

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstddef>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -101,6 +102,10 @@ struct Plate {
 
 struct mcrt_scene {
     int device = 0;
+    int skin_height = 0;  // 64 / 32: a repaintable handle of mcrt_scene_create_skin (the full mesh table of that skin kind); 0: any other
+    // LAYOUT: `device` and `skin_height` stay the first two ints of the struct, in this order.  The argument checks that come before
+    // any device work read these two members of a handle and nothing else, and the no-device tests (tests/test_layers_abi.py,
+    // tests/test_skin_paint_abi.py) hand them zeroed blocks with just these two words set; the assertion below holds the order.
     uint32_t alpha_words = 0;
     uint32_t n_meshes = 0;
     bool posed = false;  // any mesh with MESH_ROTATED
@@ -147,10 +152,14 @@ struct mcrt_scene {
     bool holds_seed_table = false;
     const uint32_t* seed_table_full = nullptr;  // the device's table for every 32-bit seed (ambient occlusion), or NULL
     bool holds_full_table = false, full_table_tried = false;
+    const void* skin_tables = nullptr;  // a repaintable handle's share of the device's repaint tables (kernels.h: SkinPaintShape)
+    DeviceBuffer skin;                  // mcrt_scene_set_skin: the uploaded image
     // plates this shell holds a `users` count of, by kind, least recently used first: its recorded launch graphs and its
     // launches in flight may read them, so one is let go of only behind a device synchronisation (acquire_plates)
     std::vector<Plate*> plates[kPlateKinds];
 };
+
+static_assert(offsetof(mcrt_scene, device) == 0 && offsetof(mcrt_scene, skin_height) == sizeof(int), "mcrt_scene: device, then skin_height (see the member)");
 
 namespace mcrt_host {
 
@@ -197,6 +206,11 @@ void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream);
 // the device's background plate and draw plate for the frame prepared as p[0] — each or nullptr, both kinds under one sighting
 // rule in this one call — into bg_plate and draw_plate of p[0..n) (the lanes of one render read the same plates)
 void acquire_plates(mcrt_scene* s, mcrt::RenderParams* p, int n, bool capturing, bool count_sighting);
+// The device's repaint tables of a skin kind (64 / 32) — the 256 floats u8 / 255.0f, then per pool texel the mesh and the skin
+// pixel it is cut from (kernels.h: SkinPaintShape) — built at the kind's first repaintable handle on the device, one `users`
+// count per handle that holds them, freed by mcrt_trim() when nobody does.  nullptr: the allocation or the upload failed.
+const void* acquire_skin_tables(int device, int skin_height);
+void release_skin_tables(int device, int skin_height);
 size_t pool_limit(int device);
 bool pool_scene(mcrt_scene* s);             // false: not kept, the caller destroys it
 mcrt_scene* take_pooled_scene(int device);  // device < 0: any
@@ -234,6 +248,8 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
 int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream);
 int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_ground* d_out, size_t stride,
                                hipStream_t stream);
+// repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
+int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 
 }  // namespace mcrt_host
 

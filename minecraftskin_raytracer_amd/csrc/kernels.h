@@ -298,6 +298,30 @@ hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int vie
 // frame's ground_lds_bytes
 hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream);
 
+// ---- skins on resident scenes (mcrt_scene_set_skin_device & co): a repaintable handle's blob holds the full mesh table of
+// its skin kind, so texel i of its pool is cut from one fixed pixel of the skin image.  One workgroup per scene rewrites what
+// a skin decides of the blob: the float4 texel pool (u8 / 255.0f through a table the HOST formed), the 2-bit alpha predicates
+// and the MESH_OPAQUE bit of every mesh.  Nothing else of the blob is touched.
+constexpr int kSkinMaxMeshes = 12;
+constexpr int kSkinMaxTexels = 3264;
+// what the scenes of one launch share.  `tables` (device_stores.cpp, per device and skin kind): 256 floats i / 255.0f, then
+// n_texels uint16 (mesh << 12) | skin pixel index y * 64 + x, in pool order.
+struct SkinPaintShape {
+    const void* tables;
+    int n_texels;        // 3264 (64x64) or 2016 (64x32)
+    int n_meshes;        // 12 or 7
+    int skin_bytes;      // 64 * height * 4
+    uint32_t mesh_offset, texel_offset, alpha_offset, alpha_words;  // of the kind's blob (FlatHeader)
+};
+struct SkinPaintFrame {
+    uint8_t* scene;       // the resident blob
+    const uint8_t* skin;  // RGBA8, row-major, 4-byte aligned
+};
+size_t skin_tables_bytes(int n_texels);
+hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
+hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);
+
 hipError_t launch_unpack_rows(const mcrt_config& cfg, const Shard& sh, const float* packed, float* frame,
                               hipStream_t stream);
 hipError_t launch_unpack_rows8(const mcrt_config& cfg, const Shard& sh, const uint8_t* packed, uint8_t* frame, hipStream_t stream);  // RGBA8 plane

@@ -34,6 +34,16 @@ int mcrt_probe_intersect(mcrt_scene* s, const float* rays, int n, mcrt_hit* out)
     return finish_probe(e, out, d_out, static_cast<size_t>(n) * sizeof(mcrt_hit), "probe_intersect");
 }
 
+int mcrt_probe_scene_blob(mcrt_scene* s, void* out, size_t capacity) {
+    if (!s || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());  // renders and repaints of the handle, on whatever streams
+    if (s->host_meshes.size() < sizeof(FlatHeader) || !s->blob.ptr) return fail(MCRT_ERR_INVALID, "the handle holds no scene");
+    const size_t bytes = reinterpret_cast<const FlatHeader*>(s->host_meshes.data())->blob_bytes;
+    HIP_TRY(hipMemcpy(out, s->blob.ptr, bytes < capacity ? bytes : capacity, hipMemcpyDeviceToHost));
+    return static_cast<int>(bytes);
+}
+
 int mcrt_probe_trace(mcrt_scene* s, const mcrt_config* cfg, const float* rays, int n, int depth, float* out_rgba) {
     if (!s || !cfg || !rays || !out_rgba || n < 0) return fail(MCRT_ERR_INVALID, "bad argument");
     if (n == 0) return MCRT_OK;

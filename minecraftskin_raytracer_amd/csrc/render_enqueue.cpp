@@ -333,13 +333,27 @@ int launch_or_replay(mcrt_scene* s, const RenderParams* p, int n_lanes, hipStrea
 constexpr size_t kCounterResetBytes = static_cast<size_t>(kCounterWords - 4) * 4;    // from word 0
 constexpr size_t kBaseResetBytes = (static_cast<size_t>(kCounterWords) + 4) * 4;     // from word kCounterWords
 
-int begin_handle_render(mcrt_scene* s, int n_lanes, hipStream_t stream, bool capturing) {
-    if (!capturing && s->have_last && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->last_done, 0));
-    s->flags_checked = false;
+// The two halves of the handle's event chain, shared by everything that must run one after the other on a handle — its renders
+// (which use its workspace) and its repaints (which write the blob the renders read): `stream` waits for the handle's last such
+// work where that was enqueued on another stream, and `last_done` exists afterwards; behind the new work `last_done` is recorded.
+int join_handle_chain(mcrt_scene* s, hipStream_t stream) {
+    if (s->have_last && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->last_done, 0));
     if (!s->last_done) {
         HIP_TRY(hipEventCreateWithFlags(&s->last_done, hipEventDisableTiming));
         s->busy_probe.store(s->last_done, std::memory_order_release);
     }
+    return MCRT_OK;
+}
+int extend_handle_chain(mcrt_scene* s, hipStream_t stream) {
+    HIP_TRY(hipEventRecord(s->last_done, stream));
+    s->last_stream = stream;
+    s->have_last = true;
+    return MCRT_OK;
+}
+
+int begin_handle_render(mcrt_scene* s, int n_lanes, hipStream_t stream, bool capturing) {
+    if (const int rc = join_handle_chain(s, capturing ? s->last_stream : stream); rc != MCRT_OK) return rc;  // (capturing: no wait, the event alone)
+    s->flags_checked = false;
     for (int li = 0; li < n_lanes; ++li) {
         Lane& ln = s->lanes[li];
         if (!ln.counters_dirty || !ln.counters.ptr) continue;
@@ -358,10 +372,7 @@ int end_handle_render(mcrt_scene* s, int n_lanes, hipStream_t stream, int rc, bo
         return rc;
     }
     if (capturing) return MCRT_OK;
-    HIP_TRY(hipEventRecord(s->last_done, stream));
-    s->last_stream = stream;
-    s->have_last = true;
-    return MCRT_OK;
+    return extend_handle_chain(s, stream);
 }
 
 // ---- batches: N frames of one config in one launch sequence (mcrt_render_batch_device) -----------------------------
@@ -721,9 +732,90 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
         [&](const GroundFrame* d_table, int m) { return launch_ground_batch(d_table, m, shape, view, dyn, stream); });
 }
 
+// ---- skins on resident scenes (mcrt_scene_set_skin_device & co): one workgroup per handle rewrites the texel pool, the alpha
+// predicates and the MESH_OPAQUE bits of its blob.  The blob is what the handle's renders read, so a repaint sits in the
+// handle's event chain like a render (join_handle_chain / extend_handle_chain, the halves begin_ / end_handle_render use).
+// It uses no workspace and no counters: flags_checked and the lanes stay as they are.
+int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream) {
+    // argument checks, before any device work (the first ones do not look inside the handles)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n must be >= 0");
+    if (!d_skins || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (stride_bytes % 4 != 0) return fail(MCRT_ERR_INVALID, "skin_stride_bytes must be a multiple of 4");
+    if ((reinterpret_cast<uintptr_t>(d_skins) & 3u) != 0) return fail(MCRT_ERR_INVALID, "the skin images must be aligned to 4 bytes");
+    if (n == 0) return MCRT_OK;
+    const int kind = scenes[0]->skin_height, device = scenes[0]->device;
+    for (int i = 0; i < n; ++i)
+        if (scenes[i]->skin_height != 64 && scenes[i]->skin_height != 32)
+            return fail(MCRT_ERR_INVALID, "a handle was not created by mcrt_scene_create_skin (only those hold the full mesh table a repaint writes)");
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must be of one skin kind");
+    const size_t image_bytes = static_cast<size_t>(64) * static_cast<size_t>(kind) * 4;
+    if (stride_bytes < image_bytes) return fail(MCRT_ERR_INVALID, "skin_stride_bytes is smaller than the skin image");
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    {
+        std::vector<mcrt_scene*> sorted(scenes, scenes + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (two images for one blob)");
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a repaint cannot be recorded into a caller's graph (it takes the handles' events)");
+    (void)hipGetLastError();
+    const FlatHeader* h = reinterpret_cast<const FlatHeader*>(scenes[0]->host_meshes.data());  // one kind: one blob layout
+    SkinPaintShape shape{};
+    shape.tables = scenes[0]->skin_tables;
+    shape.n_texels = static_cast<int>(h->n_texels), shape.n_meshes = static_cast<int>(h->n_meshes), shape.skin_bytes = static_cast<int>(image_bytes);
+    shape.mesh_offset = h->mesh_offset, shape.texel_offset = h->texel_offset, shape.alpha_offset = h->alpha_offset, shape.alpha_words = h->alpha_words;
+    std::vector<SkinPaintFrame> frames(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        mcrt_scene* s = scenes[i];
+        frames[static_cast<size_t>(i)] = SkinPaintFrame{static_cast<uint8_t*>(s->blob.ptr), d_skins + static_cast<size_t>(i) * stride_bytes};
+        if (const int rc = join_handle_chain(s, stream); rc != MCRT_OK) return rc;
+    }
+    const int rc = launch_pass(
+        device, frames, stream, "repaint launches", [&](const SkinPaintFrame& f) { return launch_skin_paint(f, shape, stream); },
+        [&](const SkinPaintFrame* d_table, int m) { return launch_skin_paint_batch(d_table, m, shape, stream); });
+    if (rc != MCRT_OK) return rc;
+    // Should a record fail half way through the batch (the call then returns the error), the handles before it are chained
+    // behind the repaint and the others are not: those keep their earlier `last_done`, which still orders their renders among
+    // themselves, and the caller — who got an error — cannot count on the order of this repaint against them.
+    for (int i = 0; i < n; ++i)
+        if (const int rc = extend_handle_chain(scenes[i], stream); rc != MCRT_OK) return rc;
+    return MCRT_OK;
+}
+
 }  // namespace mcrt_host
 
 extern "C" {
+
+int mcrt_scene_set_skin_device(mcrt_scene* s, const uint8_t* d_skin_rgba8, void* stream) {
+    if (!s || !d_skin_rgba8) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t image_bytes = static_cast<size_t>(64) * static_cast<size_t>(s->skin_height > 0 ? s->skin_height : 0) * 4;  // (the kind is checked there)
+    return set_skins_batch_device(one, 1, d_skin_rgba8, image_bytes, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t skin_stride_bytes, void* stream) {
+    return set_skins_batch_device(scenes, n, d_skins, skin_stride_bytes, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_skin(mcrt_scene* s, const uint8_t* skin_rgba8) {
+    if (!s || !skin_rgba8) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (s->skin_height != 64 && s->skin_height != 32)
+        return fail(MCRT_ERR_INVALID, "the handle was not created by mcrt_scene_create_skin (only those hold the full mesh table a repaint writes)");
+    const size_t bytes = static_cast<size_t>(64) * static_cast<size_t>(s->skin_height) * 4;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(s->skin.reserve(bytes));
+    // (a second upload into s->skin may not overtake the repaint that reads the first: this call waits for its own)
+    HIP_TRY(hipMemcpy(s->skin.ptr, skin_rgba8, bytes, hipMemcpyHostToDevice));
+    const int rc = mcrt_scene_set_skin_device(s, static_cast<const uint8_t*>(s->skin.ptr), nullptr);
+    if (rc != MCRT_OK) return rc;
+    HIP_TRY(hipEventSynchronize(s->last_done));
+    return MCRT_OK;
+}
 
 int mcrt_render_device(mcrt_scene* s, const mcrt_config* cfg, int first, int step, int layout, float* d_out,
                        void* stream) {

@@ -2107,6 +2107,78 @@ __global__ __launch_bounds__(64) void pick_kernel(const uint8_t* __restrict__ sc
 }
 
 // ---------------------------------------------------------------------------------------------
+// skins on resident scenes (kernels.h: SkinPaintFrame): a repaintable handle's blob takes a new skin from an RGBA8 image in
+// device memory.  One workgroup of 256 threads per scene:
+//   the image (16 or 8 KB) and the host's 256 floats u8 / 255.0f go to LDS, 16 bytes per lane where the image's address allows
+//   1 lane / pool texel (strides of 256)   its skin pixel through the map, four table reads, one 16-byte store into the pool;
+//                                          two ballots per wave — alpha == 0 and alpha > 0, which for a byte is a == 0 and
+//                                          a != 0 — interleaved by lanes 0..3 into the wave's four alpha-predicate words;
+//                                          a texel with alpha 0 sets its mesh's bit in LDS
+//   1 lane / mesh                          the MESH_OPAQUE bit of FlatMesh::flags, an ordinary load and store
+// Every store is a vector store; nothing of the blob but the pool, the predicate words and that bit is written.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSkinBlock = 256;
+__device__ __forceinline__ uint32_t spread16(uint32_t x) {  // bit j of the low 16 bits → bit 2j
+    x = (x | (x << 8)) & 0x00ff00ffu;
+    x = (x | (x << 4)) & 0x0f0f0f0fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return x;
+}
+__device__ __forceinline__ void skin_paint_body(const SkinPaintFrame& __restrict__ f, const SkinPaintShape& __restrict__ sh) {
+    __shared__ __align__(16) uint32_t s_skin[64 * 64];
+    __shared__ float s_unit[256];
+    __shared__ uint32_t s_clear;  // bit m: a texel of mesh m has alpha 0
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float* __restrict__ unit = static_cast<const float*>(sh.tables);
+    const uint16_t* __restrict__ map = reinterpret_cast<const uint16_t*>(unit + 256);
+    const int n_pixels = sh.skin_bytes >> 2;
+    if ((reinterpret_cast<uintptr_t>(f.skin) & 15u) == 0) {
+        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(f.skin);
+        for (int i = tid; i < (n_pixels >> 2); i += kSkinBlock) reinterpret_cast<uint4*>(s_skin)[i] = src[i];
+    } else {
+        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(f.skin);
+        for (int i = tid; i < n_pixels; i += kSkinBlock) s_skin[i] = src[i];
+    }
+    s_unit[tid] = unit[tid];
+    if (tid == 0) s_clear = 0u;
+    __syncthreads();
+    float4* __restrict__ pool = reinterpret_cast<float4*>(f.scene + sh.texel_offset);
+    uint32_t* __restrict__ abits = reinterpret_cast<uint32_t*>(f.scene + sh.alpha_offset);
+    for (int base = 0; base < sh.n_texels; base += kSkinBlock) {  // (uniform per workgroup: every wave reaches its ballots)
+        const int i = base + tid;
+        const bool valid = i < sh.n_texels;
+        bool zero = false, positive = false;
+        if (valid) {
+            const uint32_t entry = map[i];
+            const uint32_t px = s_skin[entry & 4095u];
+            const uint32_t a = px >> 24;
+            pool[i] = make_float4(s_unit[px & 255u], s_unit[(px >> 8) & 255u], s_unit[(px >> 16) & 255u], s_unit[a]);
+            zero = a == 0u, positive = a != 0u;
+            if (zero) atomicOr(&s_clear, 1u << (entry >> 12));
+        }
+        const unsigned long long z = __ballot(zero), p = __ballot(positive);
+        // the wave's 64 texels are words w0 .. w0 + 3 (a wave starts at a multiple of 64 texels): lane k forms word k
+        const uint32_t word = static_cast<uint32_t>(i - lane) / 16u + static_cast<uint32_t>(lane);
+        if (lane < 4 && word < sh.alpha_words) {
+            const uint32_t zk = static_cast<uint32_t>(z >> (16 * lane)) & 0xffffu, pk = static_cast<uint32_t>(p >> (16 * lane)) & 0xffffu;
+            abits[word] = spread16(zk) | (spread16(pk) << 1);
+        }
+    }
+    __syncthreads();
+    if (tid < sh.n_meshes) {
+        FlatMesh* fm = reinterpret_cast<FlatMesh*>(f.scene + sh.mesh_offset) + tid;
+        const uint32_t flags = fm->flags;
+        fm->flags = ((s_clear >> tid) & 1u) ? (flags & ~MESH_OPAQUE) : (flags | MESH_OPAQUE);
+    }
+}
+__global__ __launch_bounds__(kSkinBlock) void skin_paint_kernel(const SkinPaintFrame f, const SkinPaintShape sh) { skin_paint_body(f, sh); }
+using SkinPaintTable = const __attribute__((address_space(4))) SkinPaintFrame*;
+__global__ __launch_bounds__(kSkinBlock) void skin_paint_batch_kernel(SkinPaintTable table, const SkinPaintShape sh) {
+    skin_paint_body(*(const SkinPaintFrame*)(table + blockIdx.y), sh);
+}
+
+// ---------------------------------------------------------------------------------------------
 // ground shadow (kernels.h: GroundFrame): the figure's soft shadow on the plane y = ground_y, as planes of their own.  Per
 // pixel the layers' pixel-centre ray, its point P on the plane, and computeSoftShadow(P, (0, 1, 0)) (shading.cpp:28-60) with
 // the seed of a hit at depth 0 (raytracer.cpp:110-112) — the figure in front of the plane plays no part.  No workspace.
@@ -3117,6 +3189,23 @@ hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const G
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(pick_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, scene, shape, d_xy, n, d_out);
+    return hipGetLastError();
+}
+// ---- skins on resident scenes (kernels.h) -----------------------------------------------------------
+size_t skin_tables_bytes(int n_texels) { return 256 * sizeof(float) + static_cast<size_t>(n_texels) * sizeof(uint16_t); }
+static bool skin_shape_ok(const SkinPaintShape& sh) {  // what the kernel's fixed LDS image and its 4-bit mesh field hold
+    return sh.tables && sh.n_texels > 0 && sh.n_texels <= kSkinMaxTexels && sh.n_meshes > 0 && sh.n_meshes <= kSkinMaxMeshes &&
+           (sh.skin_bytes == 64 * 64 * 4 || sh.skin_bytes == 64 * 32 * 4) && sh.alpha_words == static_cast<uint32_t>((sh.n_texels + 15) / 16);
+}
+hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream) {
+    if (!skin_shape_ok(shape) || !f.scene || !f.skin) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(skin_paint_kernel, dim3(1), dim3(kSkinBlock), 0, stream, f, shape);
+    return hipGetLastError();
+}
+hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream) {
+    if (n_frames <= 0) return hipSuccess;
+    if (!skin_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(skin_paint_batch_kernel, dim3(1, static_cast<unsigned>(n_frames)), dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shape);
     return hipGetLastError();
 }
 

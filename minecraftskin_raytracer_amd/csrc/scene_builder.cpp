@@ -263,6 +263,25 @@ OwnedDesc* assemble(const Skin& skin, const float pose[12]) {  // mesh_builder.c
     return o;
 }
 
+// where face `face_slot` of mesh `mesh` of a skin kind's full mesh table is cut from (arguments in range).  assemble(): per
+// part the inner box, then its outer box where the skin kind has one
+struct FaceSource {
+    Rect rect;
+    bool flipped;  // a legacy skin's mirrored left limb: the rectangle is read right to left (flip_h)
+};
+FaceSource face_source(int skin_height, int mesh, int face_slot) {
+    int part, outer;
+    if (skin_height == 64)
+        part = mesh / 2, outer = mesh & 1;
+    else
+        part = mesh < 2 ? 0 : mesh - 1, outer = mesh == 1 ? 1 : 0;
+    const int mirror_of = (skin_height == 32 && !outer) ? kLegacyMirrorOf[part] : -1;
+    const PartBox& box = outer ? kOuterBox[part] : kInnerBox[mirror_of >= 0 ? mirror_of : part];
+    int face = face_slot;
+    if (mirror_of >= 0 && (face == 2 || face == 3)) face = 5 - face;  // mirror_part: left = flip_h(right), right = flip_h(left)
+    return FaceSource{face_rect(box, face), mirror_of >= 0};
+}
+
 }  // namespace
 
 extern "C" {
@@ -296,24 +315,40 @@ int mcrt_skin_texel(int skin_height, int mesh, int face_slot, int tx, int ty, in
     if (!skin_x || !skin_y) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
     if (skin_height != 64 && skin_height != 32) return mcrt_detail_fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
     if (face_slot < 0 || face_slot > 5) return mcrt_detail_fail(MCRT_ERR_INVALID, "face_slot must be 0..5");
-    // assemble(): per part the inner box, then its outer box where the skin kind has one
-    int part, outer;
-    if (skin_height == 64) {
-        if (mesh < 0 || mesh >= 12) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..11 for a 64x64 skin");
-        part = mesh / 2, outer = mesh & 1;
-    } else {
-        if (mesh < 0 || mesh >= 7) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..6 for a 64x32 skin");
-        part = mesh < 2 ? 0 : mesh - 1, outer = mesh == 1 ? 1 : 0;
-    }
-    const int mirror_of = (skin_height == 32 && !outer) ? kLegacyMirrorOf[part] : -1;
-    const PartBox& box = outer ? kOuterBox[part] : kInnerBox[mirror_of >= 0 ? mirror_of : part];
-    int face = face_slot;
-    if (mirror_of >= 0 && (face == 2 || face == 3)) face = 5 - face;  // mirror_part: left = flip_h(right), right = flip_h(left)
-    const Rect r = face_rect(box, face);
+    if (skin_height == 64 && (mesh < 0 || mesh >= 12)) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..11 for a 64x64 skin");
+    if (skin_height == 32 && (mesh < 0 || mesh >= 7)) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..6 for a 64x32 skin");
+    const FaceSource src = face_source(skin_height, mesh, face_slot);
+    const Rect& r = src.rect;
     if (tx < 0 || tx >= r.w || ty < 0 || ty >= r.h) return mcrt_detail_fail(MCRT_ERR_INVALID, "texel outside the face's region");
-    *skin_x = r.x + (mirror_of >= 0 ? r.w - 1 - tx : tx);  // flip_h
+    *skin_x = r.x + (src.flipped ? r.w - 1 - tx : tx);  // flip_h
     *skin_y = r.y + ty;
     return MCRT_OK;
+}
+
+// The texel pool of the full-table figure of a skin kind, in pool order — assemble()'s meshes with every part present, their
+// six faces in slot order, a face's texels row-major, which is the order add_box hands the textures to the flattener in —
+// by the tables above: per texel its mesh and the skin pixel y * 64 + x it is cut from.  Returns the count.
+__attribute__((visibility("hidden"))) int mcrt_detail_skin_pool(int skin_height, int32_t* pixel, int32_t* mesh_of, int capacity) {
+    const int n_meshes = skin_height == 64 ? 12 : 7;
+    int n = 0;
+    for (int mesh = 0; mesh < n_meshes; ++mesh)
+        for (int face = 0; face < 6; ++face) {
+            const FaceSource src = face_source(skin_height, mesh, face);
+            const Rect& r = src.rect;
+            for (int ty = 0; ty < r.h; ++ty)
+                for (int tx = 0; tx < r.w; ++tx, ++n) {
+                    if (n >= capacity) continue;
+                    if (pixel) pixel[n] = (r.y + ty) * 64 + r.x + (src.flipped ? r.w - 1 - tx : tx);
+                    if (mesh_of) mesh_of[n] = mesh;
+                }
+        }
+    return n;
+}
+
+int mcrt_skin_pool_map(int skin_height, int32_t* out, int capacity) {
+    if (!out) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
+    if (skin_height != 64 && skin_height != 32) return mcrt_detail_fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    return mcrt_detail_skin_pool(skin_height, out, nullptr, capacity < 0 ? 0 : capacity);
 }
 
 int mcrt_build_default_scene(const float pose[12], mcrt_scene_desc** out) {
