@@ -1,6 +1,7 @@
 // api.cpp — C-ABI implementation of include/mcrt.h, host side: scenes, the host-buffer entry points and the calling
 // thread's error text and timings.  The launches of a render are in render_enqueue.cpp, what is kept per device in
-// device_stores.cpp, the probes in probes.cpp, the kernels in render_kernels.hip.
+// device_stores.cpp, the probes in probes.cpp, the planning of the launches in render_plan.cpp, the kernels in
+// render_kernels.hip, pass_kernels.hip and util_kernels.hip.
 //
 // There is deliberately no CPU fallback anywhere in the library: every render / probe entry point
 // needs a HIP device and fails with MCRT_ERR_NO_DEVICE / MCRT_ERR_HIP otherwise.

@@ -1,0 +1,190 @@
+// kernel_common.h — device-side helpers that more than one kernel file uses (render_kernels.hip, pass_kernels.hip,
+// util_kernels.hip): tile geometry, the scene tables staged in LDS and the kernel variants built on them, the block-wide
+// rank, the light's disk samples, the RGBA8 quantisation, and the launch-side dispatch over the variants.
+#ifndef MCRT_KERNEL_COMMON_H
+#define MCRT_KERNEL_COMMON_H
+
+#include "kernels.h"
+#include "rt_core.h"
+
+#include <type_traits>
+
+// Verification hooks.  tools/decide_check.sh builds a variant of the library with -DMCRT_KERNEL_HOOKS='"decide_check_hooks.h"'
+// (tools/decide_check_hooks.h: every record `lit` decides is traced as well and contradictions are counted and printed);
+// the product build compiles the hooks to nothing.  tools/gpu_ground.py builds another variant with tools/ground_class_hooks.h
+// (the ground pass's hook: pass_kernels.hip).
+#ifdef MCRT_KERNEL_HOOKS
+#include MCRT_KERNEL_HOOKS
+#else
+#define MCRT_HOOK_LIT_SHARED
+#define MCRT_HOOK_LIT_CLASSIFIED(known, undecided, cand, O)
+#define MCRT_HOOK_LIT_SHADED(lit, r)
+#define MCRT_HOOK_RESOLVE_BEGIN()
+#endif
+
+namespace mcrt {
+
+using namespace rt;
+
+// n / d for a divisor that is the same for the whole wave: a shift when it is a power of two (tile widths of 32,
+// 4 samples per pixel: the usual case) instead of the ~25-instruction expansion of a 32-bit division.
+struct UDiv {
+    unsigned d;
+    int shift;  // log2(d), or -1
+    __device__ __forceinline__ explicit UDiv(unsigned dv) : d(dv), shift((dv & (dv - 1u)) == 0u && dv != 0u ? static_cast<int>(__builtin_ctz(dv)) : -1) {}
+    __device__ __forceinline__ unsigned div(unsigned n) const { return shift >= 0 ? n >> shift : n / d; }
+};
+
+// ---------------------------------------------------------------------------------------------
+// tile geometry helpers (TileRenderer::generateTiles, tile_renderer.cpp:18-39)
+// ---------------------------------------------------------------------------------------------
+struct TileGeom {
+    int x, y, w, h;
+    int owned_row;  // index of this tile's row among the rows this launch owns
+    int frame_tile;  // row-major index of the tile in the whole frame (its slot in a background or draw plate, kernels.h)
+};
+
+// RGBA8 quantisation `(u8)(clamp(c,0,1)*255+0.5)` (image_writer.cpp:18-22 ≡ image.cpp:31-36)
+__device__ __forceinline__ uchar4 quantize_pixel(float4 c) {
+    uchar4 q;
+    q.x = static_cast<unsigned char>(sclamp(c.x, 0.0f, 1.0f) * 255.0f + 0.5f);
+    q.y = static_cast<unsigned char>(sclamp(c.y, 0.0f, 1.0f) * 255.0f + 0.5f);
+    q.z = static_cast<unsigned char>(sclamp(c.z, 0.0f, 1.0f) * 255.0f + 0.5f);
+    q.w = static_cast<unsigned char>(sclamp(c.w, 0.0f, 1.0f) * 255.0f + 0.5f);
+    return q;
+}
+
+// ---------------------------------------------------------------------------------------------
+// primary-ray culling mask of a tile
+// ---------------------------------------------------------------------------------------------
+// lens_pad: how far a thin-lens ray can displace the image of a point of this mesh, in the bound's
+// units (0 for the pinhole camera)
+__device__ __forceinline__ bool mesh_touches_tile(const FlatMesh& m, const TileGeom& t, const mcrt_config& cfg,
+                                                  float aspect, float lens_pad) {
+    float u0 = m.screen[0], v0 = m.screen[1], u1 = m.screen[2], v1 = m.screen[3];
+    if (u0 > u1) return true;  // no bound available
+    u0 -= lens_pad, v0 -= lens_pad, u1 += lens_pad, v1 += lens_pad;
+    const float W = static_cast<float>(cfg.width), H = static_cast<float>(cfg.height);
+    // tile extent padded by 2 pixels, in the bound's units (x: (2u-1)*aspect, y: 1-2v, +y up)
+    float tu0 = (2.0f * (static_cast<float>(t.x) - 2.0f) / W - 1.0f) * aspect - 1e-3f * aspect - 1e-3f;
+    float tu1 = (2.0f * (static_cast<float>(t.x + t.w) + 2.0f) / W - 1.0f) * aspect + 1e-3f * aspect + 1e-3f;
+    float tv1 = 1.0f - 2.0f * (static_cast<float>(t.y) - 2.0f) / H + 2e-3f;
+    float tv0 = 1.0f - 2.0f * (static_cast<float>(t.y + t.h) + 2.0f) / H - 2e-3f;
+    return !(u1 < tu0 || u0 > tu1 || v1 < tv0 || v0 > tv1);
+}
+
+// ---------------------------------------------------------------------------------------------
+// scene tables staged in LDS: what candidates index PER LANE (face → texture table, alpha bits)
+// ---------------------------------------------------------------------------------------------
+struct LdsTables {
+    const MCRT_LDS uint32_t* abits;
+    const MCRT_LDS int* faces;
+    const MCRT_LDS float* mtab;
+};
+// dyn = dynamic LDS base; layout [face table: 4 ints per (mesh, face)][mesh table: kMeshTabWords per
+// mesh][alpha words].  Collective.  The offsets below and scene_tables_lds_bytes (launch_shapes.h), by which every
+// launch sizes this area, are one formula: s_abits starts at scene_tables_lds_bytes(lds_face_entries, 0) and ends at
+// scene_tables_lds_bytes(lds_face_entries, lds_alpha_words) — change them together.
+__device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const int lds_face_entries, const int lds_alpha_words, unsigned char* dyn) {
+    int* s_faces = reinterpret_cast<int*>(dyn);
+    float* s_mtab = reinterpret_cast<float*>(dyn + static_cast<size_t>(lds_face_entries) * 16);
+    const int n_meshes = lds_face_entries / 6;
+    uint32_t* s_abits = reinterpret_cast<uint32_t*>(dyn + static_cast<size_t>(lds_face_entries) * 16 +
+                                                    static_cast<size_t>(n_meshes) * kMeshTabWords * 4);
+    for (int i = threadIdx.x; i < lds_alpha_words; i += blockDim.x) s_abits[i] = g.abits[i];
+    for (int i = threadIdx.x; i < lds_face_entries; i += blockDim.x) {
+        const FlatMesh& fm = g.meshes[i / 6];
+        const int f = i - (i / 6) * 6;
+        s_faces[4 * i + 0] = fm.tex_off[f];
+        s_faces[4 * i + 1] = fm.tex_w[f];
+        s_faces[4 * i + 2] = fm.tex_h[f];
+        s_faces[4 * i + 3] = 0;
+    }
+    for (int i = threadIdx.x; i < n_meshes; i += blockDim.x) {
+        const FlatMesh& fm = g.meshes[i];
+        float* t = s_mtab + i * kMeshTabWords;
+        t[0] = fm.lo[0], t[1] = fm.lo[1], t[2] = fm.lo[2];
+        t[3] = fm.hi[0], t[4] = fm.hi[1], t[5] = fm.hi[2];
+        t[6] = __uint_as_float(fm.flags);
+        t[7] = 0.0f;
+        t[8] = fm.pivot[0], t[9] = fm.pivot[1], t[10] = fm.pivot[2];
+        t[11] = 0.0f;
+        t[12] = fm.inv_z_cos, t[13] = fm.inv_z_sin, t[14] = fm.inv_x_cos, t[15] = fm.inv_x_sin;
+        t[16] = fm.fwd_x_cos, t[17] = fm.fwd_x_sin, t[18] = fm.fwd_z_cos, t[19] = fm.fwd_z_sin;
+        t[20] = fm.sphere[0], t[21] = fm.sphere[1], t[22] = fm.sphere[2], t[23] = fm.sphere[3];
+    }
+    __syncthreads();
+    return LdsTables{(const MCRT_LDS uint32_t*)s_abits, (const MCRT_LDS int*)s_faces, (const MCRT_LDS float*)s_mtab};
+}
+__device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const RenderParams& p, unsigned char* dyn) {
+    return stage_tables(g, p.lds_face_entries, p.lds_alpha_words, dyn);
+}
+template <int kView>
+struct ViewSel {
+    using type = SceneViewLdsT<kView == kViewLds>;
+    static __device__ __forceinline__ type make(const SceneView& g, const RenderParams& p, unsigned char* dyn) {
+        LdsTables t = stage_tables(g, p, dyn);
+        return view_with_lds<kView == kViewLds>(g, t.abits, t.faces, t.mtab);
+    }
+};
+template <>
+struct ViewSel<kViewHbm> {
+    using type = SceneView;
+    static __device__ __forceinline__ type make(const SceneView& g, const RenderParams&, unsigned char*) { return g; }
+};
+// launch side: calls f(std::integral_constant<int, kView>{}) for the variant `view` names, so a launcher writes its
+// kernel template once: [&](auto v) { ... kernel<decltype(v)::value> ... }
+template <class F>
+static void with_view(int view, F&& f) {
+    if (view == kViewLdsUnposed) return f(std::integral_constant<int, kViewLdsUnposed>{});
+    if (view == kViewLds) return f(std::integral_constant<int, kViewLds>{});
+    return f(std::integral_constant<int, kViewHbm>{});
+}
+
+// Rank of this thread's item among the workgroup's flagged items, and their total: ballot per wave,
+// four wave counts through LDS.  Collective (two barriers: the counts are reusable right after).
+__device__ __forceinline__ int block_rank(bool flag, int* s_wcnt, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(flag);
+    if (lane == 0) s_wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int wv = 0; wv < kBlock / 64; ++wv) {
+        const int c = s_wcnt[wv];
+        if (wv < wave) before += c;
+        total += c;
+    }
+    __syncthreads();
+    return before + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// The S disk sample positions of one shaded point (shading.cpp:35-53), by the lane that owns it (`lit`, the ground pass): the
+// truncated engine seeded for (P, depth) — mt[397] from the device's tables where they hold the seed, else the 397-step
+// recurrence — and the light's frame at P.  dst: 3 * S floats.
+__device__ __forceinline__ void disk_sample_positions(const SceneView& scg, const uint32_t* __restrict__ seed_table, const uint32_t* __restrict__ seed_table_full,
+                                                      const V3 P, const int depth, const int S, float* __restrict__ dst) {
+    MtShort rng;
+    const uint32_t seed = shadow_seed(P, depth);
+    const uint32_t slot = seed + kSeedWindowHalf;  // wraps: the window is centred on seed 0
+    if (seed_table && slot < kSeedWindow)
+        rng.seed_known(seed, seed_table[slot]);  // mt[397] of this seed, from the device's table
+    else if (seed_table_full)
+        rng.seed_known(seed, seed_table_full[seed]);  // (a scene at another scale: its seeds leave the window)
+    else
+        rng.seed(seed);  // the 397-step recurrence
+    const LightFrame frame = light_frame(scg, P);
+    for (int i = 0; i < S; ++i) {
+        const float d0 = rng.uniform();
+        const float d1 = rng.uniform();
+        const V3 t = light_sample_on_frame(scg, frame, d0, d1);
+        dst[3 * i + 0] = t.x;
+        dst[3 * i + 1] = t.y;
+        dst[3 * i + 2] = t.z;
+    }
+}
+
+}  // namespace mcrt
+
+#endif

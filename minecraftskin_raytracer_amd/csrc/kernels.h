@@ -1,11 +1,13 @@
-// kernels.h — launch interface between the C-ABI host code (api.cpp) and the HIP kernels
-// (render_kernels.hip).  Plain structs, no HIP types in the signatures beyond hipStream_t.
+// kernels.h — interface between the C-ABI host code (api.cpp, render_enqueue.cpp, device_stores.cpp, probes.cpp), the host
+// planning (render_plan.cpp) and the HIP kernels' launchers (render_kernels.hip, pass_kernels.hip, util_kernels.hip).
+// Plain structs, no HIP types in the signatures beyond hipStream_t.
 #ifndef MCRT_KERNELS_H
 #define MCRT_KERNELS_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_shapes.h"
 #include "mcrt.h"
 
 namespace mcrt {
@@ -138,7 +140,32 @@ struct RenderParams {
                            //    row-major order); the shard is then one tile row of one tile
 };
 
+// ======== planning (render_plan.cpp): pure host code ========
 Shard make_shard(const mcrt_config& cfg, int first, int step);
+inline int owned_tiles(const RenderParams& p) { return p.shard.owned_rows * p.shard.tiles_x; }
+inline bool soft_sampling(const mcrt_config& c) { return c.soft_shadows && c.shadow_samples > 1; }
+
+// Whether a scene's tables fit the LDS budget, the sizes a kernel then stages (0 / 0 when it reads them from HBM) and the
+// kernel variant the scene needs (launch_shapes.h: kViewHbm, kViewLds or kViewLdsUnposed).  One rule for the beauty path
+// and the layers and ground passes.
+constexpr int kAlphaLdsWordsMax = 4096;  // 64 Ki texels
+constexpr int kFaceLdsEntriesMax = 384;   // 64 meshes
+struct LdsFit { int face_entries, alpha_words, view; };
+LdsFit lds_fit(uint32_t alpha_words, uint32_t n_meshes, bool posed);
+// dynamic LDS of the scene tables p's kernels stage
+inline size_t scene_table_bytes(const RenderParams& p) { return p.scene_in_lds ? scene_tables_lds_bytes(p.lds_face_entries, p.lds_alpha_words) : 0; }
+
+// Sizes of the workspace arrays for p.cfg / p.shard; fills p.parts_per_tile, p.rows_per_batch and
+// p.ws.cap / p.ws.stack_stride.  budget_bytes bounds the per-batch workspace (a batch is never
+// smaller than one tile row).
+struct WorkspaceBytes {
+    size_t tile_rng, tile_draws, scol, end, units, unit_hits, tile_mask, queue_each, texel_refs, targets, cand, lit0, lit1, stack, counters, hit_rng;
+};
+// row_touched[j]: upper bound of the tiles meshes can touch in owned tile row j (NULL: every tile).
+WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched);
+// fills p.shared_device, p.grid_* and p.stream_waves (MCRT_*_GRID / MCRT_STREAM_WAVES override, development knobs)
+void choose_grids(RenderParams& p, bool shared_device, bool company);  // company: other frames or lanes run beside this launch set
+constexpr int kCounterWords = 4096;
 
 // ---- background plate: the finished pixels of every gradient background tile of a frame configuration.  Such a tile's
 // pixels are a function of the frame's size, the tile size, the samples per pixel, the draws per sample, the gradient's
@@ -155,9 +182,8 @@ bool bg_plate_eligible(const RenderParams& p);
 size_t bg_plate_bytes(const mcrt_config& cfg);
 // bytes of the scratch launch_fill_bg_plate needs: the engine states of every tile of the frame
 size_t bg_plate_rng_bytes(const RenderParams& p);
-// Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
-// `tile_rng` is scratch of bg_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
-hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream);
+// p with the whole-frame shard and no outputs: the parameters the plates' fill launches and their scratch sizes take
+RenderParams bg_plate_fill_params(const RenderParams& p);
 
 // ---- draw plate: the mt19937 draws of EVERY tile of a frame configuration, as uniform floats — what `plan_tiles` writes
 // into a touched tile's slot of ws.tile_draws.  A tile's draws are a function of the frame's size, the tile size, the
@@ -174,39 +200,6 @@ bool draw_plate_eligible(const RenderParams& p);
 size_t draw_plate_bytes(const RenderParams& p);
 // bytes of the scratch launch_fill_draw_plate needs: the engine states of every tile of the frame
 size_t draw_plate_rng_bytes(const RenderParams& p);
-// Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
-// `tile_rng` is scratch of draw_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
-hipError_t launch_fill_draw_plate(const RenderParams& p, float* plate, uint32_t* tile_rng, hipStream_t stream);
-
-// Sizes of the workspace arrays for p.cfg / p.shard; fills p.parts_per_tile, p.rows_per_batch and
-// p.ws.cap / p.ws.stack_stride.  budget_bytes bounds the per-batch workspace (a batch is never
-// smaller than one tile row).
-struct WorkspaceBytes {
-    size_t tile_rng, tile_draws, scol, end, units, unit_hits, tile_mask, queue_each, texel_refs, targets, cand, lit0, lit1, stack, counters, hit_rng;
-};
-// row_touched[j]: upper bound of the tiles meshes can touch in owned tile row j (NULL: every tile).
-WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched);
-// fills p.shared_device, p.grid_* and p.stream_waves (MCRT_*_GRID / MCRT_STREAM_WAVES override, development knobs)
-void choose_grids(RenderParams& p, bool shared_device, bool company);  // company: other frames or lanes run beside this launch set
-constexpr int kAlphaLdsWordsMax = 4096;  // 64 Ki texels
-constexpr int kFaceLdsEntriesMax = 384;   // 64 meshes
-constexpr int kCounterWords = 4096;
-
-// seeds p.tile_rng: one mt19937 per owned tile (tile_renderer.cpp:78).  A function of the frame width, the
-// tile size and the shard only — the caller keeps the result across renders and calls this when those change.
-hipError_t launch_seed_tiles(const RenderParams& p, hipStream_t stream);
-// enqueue the whole pipeline of one lane on `stream` (p.tile_rng already seeded): per batch of tile rows
-// plan → primary (+ the primary hits' reflection rays) → (ao →) lit (the rest of the chains, then light and shade) → resolve
-// Optional events for a caller that downloads tile rows as they become final (the one-shot host path):
-//  after_plan    recorded behind the first pass's plan_tiles: with bg_in_plan every tile row that holds no touched
-//                tile is complete then
-//  batch_done[b] recorded behind pass b's resolve: the rows of that pass are complete (n_batch_done entries, may be 0)
-struct LaunchMarks {
-    hipEvent_t after_plan = nullptr;
-    hipEvent_t* batch_done = nullptr;
-    int n_batch_done = 0;
-};
-hipError_t launch_render(const RenderParams& p, hipStream_t stream, const LaunchMarks* marks = nullptr);
 
 // ---- batches (mcrt_render_batch_device): N frames of one config in ONE launch sequence, blockIdx.y = frame; each
 // frame's RenderParams (its own scene, workspace, counters and output) are read from a device-resident table
@@ -218,15 +211,11 @@ struct BatchPlan {
     size_t dyn = 0;      // dynamic LDS of primary / ao: the largest frame's scene tables
     size_t lit_dyn = 0;  // dynamic LDS of lit: the largest frame's lit_lds_offset + lit_lds_bytes
 };
-constexpr int kBatchMaxFrames = 256;  // frames per launch sequence (larger batches are split: render_kernels.hip, batch_grid)
+constexpr int kBatchMaxFrames = 256;  // frames per launch sequence (larger batches are split: render_plan.cpp, batch_grid)
 // Makes frames[0..n) one batch: picks the variant (rewriting the frames' LDS fields where it reads HBM), checks the
 // lit_lds_offset invariant per frame and sets the grids (choose_grids with company, then the batch rule).
 // hipErrorInvalidValue when a frame is not eligible or the frames do not share the config's launch shapes.
 hipError_t plan_batch(RenderParams* frames, int n, bool others_running, BatchPlan& plan);
-// seeds the tile streams of the frames in d_table (launch_seed_tiles for each); p0: any one of them (host copy)
-hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d_table, int n_frames, hipStream_t stream);
-// plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
-hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
 // ---- geometry layers (mcrt_render_layers_device & co): what is under each pixel — one pixel-centre ray per pixel
 // (Camera::generateRay at u = (px + 0.5f) / width, v = (py + 0.5f) / height), intersectScene, no draws, no shading.  The pass
@@ -255,13 +244,7 @@ int layers_view(LayersFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool po
 // the variant of a batch: the most general any of its frames needs; rewrites the frames' LDS fields where it reads HBM
 int layers_batch_view(LayersFrame* frames, const int* views, int n);
 constexpr int kLayersBatchMaxFrames = 4096;  // frames per launch (blockIdx.y; larger batches take several launches)
-hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
-// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
-// frame's LDS tables
-hipError_t launch_layers_batch(const LayersFrame* d_table, int n_frames, const LayersShape& shape, int view, size_t max_dyn, hipStream_t stream);
 size_t layers_lds_bytes(const LayersFrame& f);
-// n pixels (d_xy: n x {x, y}, inside the frame) → n mcrt_surface records, by the device functions of the layers kernels
-hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream);
 
 // ---- ground shadow (mcrt_render_ground_device & co): the figure's shadow on the plane y = ground_y — per pixel the
 // pixel-centre ray of the layers, its point P on the plane, and computeSoftShadow(P, (0, 1, 0)) with the seed the reference
@@ -293,10 +276,6 @@ int ground_view(GroundFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool po
 int ground_batch_view(GroundFrame* frames, const int* views, int n);
 // dynamic LDS of a launch: the frame's scene tables, then the block's area (masks, points, counts and sample positions)
 size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape);
-hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int view, hipStream_t stream);
-// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
-// frame's ground_lds_bytes
-hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream);
 
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): a repaintable handle's blob holds the full mesh table of
 // its skin kind, so texel i of its pool is cut from one fixed pixel of the skin image.  One workgroup per scene rewrites what
@@ -318,10 +297,50 @@ struct SkinPaintFrame {
     const uint8_t* skin;  // RGBA8, row-major, 4-byte aligned
 };
 size_t skin_tables_bytes(int n_texels);
+
+// ======== pipeline launches (render_kernels.hip) ========
+// seeds p.tile_rng: one mt19937 per owned tile (tile_renderer.cpp:78).  A function of the frame width, the
+// tile size and the shard only — the caller keeps the result across renders and calls this when those change.
+hipError_t launch_seed_tiles(const RenderParams& p, hipStream_t stream);
+// enqueue the whole pipeline of one lane on `stream` (p.tile_rng already seeded): per batch of tile rows
+// plan → primary (+ the primary hits' reflection rays) → (ao →) lit (the rest of the chains, then light and shade) → resolve
+// Optional events for a caller that downloads tile rows as they become final (the one-shot host path):
+//  after_plan    recorded behind the first pass's plan_tiles: with bg_in_plan every tile row that holds no touched
+//                tile is complete then
+//  batch_done[b] recorded behind pass b's resolve: the rows of that pass are complete (n_batch_done entries, may be 0)
+struct LaunchMarks {
+    hipEvent_t after_plan = nullptr;
+    hipEvent_t* batch_done = nullptr;
+    int n_batch_done = 0;
+};
+hipError_t launch_render(const RenderParams& p, hipStream_t stream, const LaunchMarks* marks = nullptr);
+// Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
+// `tile_rng` is scratch of bg_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
+hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream);
+// Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
+// `tile_rng` is scratch of draw_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
+hipError_t launch_fill_draw_plate(const RenderParams& p, float* plate, uint32_t* tile_rng, hipStream_t stream);
+// seeds the tile streams of the frames in d_table (launch_seed_tiles for each); p0: any one of them (host copy)
+hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d_table, int n_frames, hipStream_t stream);
+// plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
+hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
+
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, skin repaints ========
+hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
+// frame's LDS tables
+hipError_t launch_layers_batch(const LayersFrame* d_table, int n_frames, const LayersShape& shape, int view, size_t max_dyn, hipStream_t stream);
+// n pixels (d_xy: n x {x, y}, inside the frame) → n mcrt_surface records, by the device functions of the layers kernels
+hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream);
+hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
+// frame's ground_lds_bytes
+hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream);
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);
 
+// ======== utilities and probes (util_kernels.hip) ========
 hipError_t launch_unpack_rows(const mcrt_config& cfg, const Shard& sh, const float* packed, float* frame,
                               hipStream_t stream);
 hipError_t launch_unpack_rows8(const mcrt_config& cfg, const Shard& sh, const uint8_t* packed, uint8_t* frame, hipStream_t stream);  // RGBA8 plane
@@ -332,10 +351,10 @@ hipError_t launch_quantize(const float* rgba, uint8_t* out, size_t n_pixels, hip
 hipError_t launch_build_seed_table(uint32_t* table, hipStream_t stream);
 // fills table[s] = mt[397] of std::mt19937(s) for the seeds first .. first + count - 1 (count a multiple of 256)
 hipError_t launch_build_seed_table_range(uint32_t* table, uint32_t first, uint32_t count, hipStream_t stream);
-// host_reciprocals: d_count floats in device memory, 1.0f / d as the host rounds it (what the render kernels get)
-hipError_t launch_probe_div_const(uint32_t d_first, uint32_t d_count, int mode, const float* host_reciprocals, unsigned long long* counts, hipStream_t stream);
 
 // probes
+// host_reciprocals: d_count floats in device memory, 1.0f / d as the host rounds it (what the render kernels get)
+hipError_t launch_probe_div_const(uint32_t d_first, uint32_t d_count, int mode, const float* host_reciprocals, unsigned long long* counts, hipStream_t stream);
 hipError_t launch_probe_intersect(const uint8_t* scene, const float* rays, int n, mcrt_hit* out,
                                   hipStream_t stream);
 hipError_t launch_probe_trace(const uint8_t* scene, const mcrt_config& cfg, const float* rays, int n,

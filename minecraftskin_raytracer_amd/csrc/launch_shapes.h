@@ -1,0 +1,63 @@
+// launch_shapes.h — the constants that the host planning (render_plan.cpp) shares with the kernels and their launchers
+// (render_kernels.hip, pass_kernels.hip, kernel_common.h): block and grid sizes, LDS areas, the kernel variants, and the
+// size of the scene tables a kernel stages in LDS.  Each is defined here alone.  Plain C++: no device construct.
+#ifndef MCRT_LAUNCH_SHAPES_H
+#define MCRT_LAUNCH_SHAPES_H
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+namespace rt {
+constexpr int kMeshTabWords = 24;  // words per mesh of the mesh table staged in LDS (rt_core.h: SceneViewLdsT::mtab)
+constexpr int kMtShortMax = 227;   // draws available from the two-recurrence form of mt19937 (rt_core.h: MtShort)
+}  // namespace rt
+
+namespace mcrt {
+
+constexpr int kBlock = 256;
+constexpr int kChunk = 256;        // work items per chunk: one per thread
+#ifndef MCRT_PRIMARY_GRID
+#define MCRT_PRIMARY_GRID 1280
+#endif
+constexpr int kPrimaryGrid = MCRT_PRIMARY_GRID; // persistent primary workgroups (5 per CU: the kernel is built for 5 waves per SIMD)
+constexpr int kQueueGrid = 2048;   // workgroups of the queue kernels (grid-stride over device-side counts)
+constexpr int kLitGridAlone = 4096;  // `lit` of a frame that has the device to itself
+constexpr int kResolveGrid = 4096;
+constexpr int kSharedGrid = 896;   // every kernel of a frame that shares the device (choose_grids): 3.5 workgroups per CU
+
+constexpr int kStreamWaves = 4;  // `plan_tiles`: tiles per workgroup
+constexpr int kSlabMinSpp = 33;  // `background_kernel` from this many samples per pixel on
+
+// The flat pipeline keeps the records of every level at once: its arrays are laid out for up to
+// kFlatMaxBounces reflection levels (1 + maxBounces records per sample slot in the worst case).
+constexpr int kFlatMaxBounces = 8;
+#ifndef MCRT_LIT_LDS_KB
+#define MCRT_LIT_LDS_KB 25
+#endif
+constexpr size_t kLitLdsBytes = MCRT_LIT_LDS_KB * 1024;  // `lit`: LDS for the sample positions of the records whose rays are traced, per pass
+
+// kernel variants by scene: kViewHbm — tables too large for LDS (reads HBM; any pose);
+// kViewLds — tables in LDS, posed meshes present; kViewLdsUnposed — tables in LDS, no posed mesh
+constexpr int kViewHbm = 0, kViewLds = 1, kViewLdsUnposed = 2;
+
+// dynamic LDS of the scene tables a kernel stages (kernel_common.h: stage_tables, which lays them out in this order):
+// face table (4 ints per (mesh, face)), mesh table (kMeshTabWords per mesh), alpha predicates
+__host__ __device__ __forceinline__ size_t scene_tables_lds_bytes(int face_entries, int alpha_words) {
+    return static_cast<size_t>(face_entries) * 16 + static_cast<size_t>(face_entries / 6) * rt::kMeshTabWords * 4 + static_cast<size_t>(alpha_words) * 4;
+}
+
+constexpr int kLayersGrid = 8192;  // layers and ground: workgroups per frame at most (the kernels stride over their units)
+constexpr int kGroundPosBytes = 12 * 1024;  // ground: LDS for the sample positions of the undecided pixels of one pass
+constexpr int kGroundFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // ground: candidate and inside masks, P.x / P.z, lit counts, the undecided list
+
+// Workgroups per frame of a batched launch.  Every kernel strides over its frame's device-side work, so the grid only
+// shapes the schedule: a batch aims at kBatchTarget workgroups per launch (8 per CU of the 256 — twice what the largest
+// stage keeps resident, enough to balance frames of unequal cost) spread evenly over its frames, never fewer than
+// kBatchMinGrid per frame (a frame's share of the work never waits on a handful of workgroups) and never more than the
+// frame would get on its own (choose_grids).  From 256 frames on the floor alone fills the target: kBatchMaxFrames.
+constexpr int kBatchTarget = 2048;
+constexpr int kBatchMinGrid = 8;
+
+}  // namespace mcrt
+
+#endif

@@ -1,0 +1,529 @@
+// pass_kernels.hip — the stand-alone passes over a resident scene (not stages of a render): geometry layers and pixel
+// picks, the ground shadow, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
+// and nothing else: no workspace, no counters.
+#include "kernel_common.h"
+
+// the ground pass's hook (kernel_common.h: verification hooks): tools/ground_class_hooks.h makes the pass write every pixel's
+// class (missed, culled by tile, decided, traced) into its visibility plane
+#ifndef MCRT_HOOK_GROUND_PIXEL
+#define MCRT_HOOK_GROUND_PIXEL(vis, reached, culled, undecided)
+#endif
+
+namespace mcrt {
+
+using namespace rt;
+
+// ---------------------------------------------------------------------------------------------
+// geometry layers (kernels.h: LayersFrame): depth, normal, albedo and id planes, and single-pixel picks.  One pixel-centre
+// ray per pixel — the reference's primary ray at samplesPerPixel == 1 without depth of field (tile_renderer.cpp:92-103) —
+// and intersectScene; no draws, no records, no shading, no workspace.
+//   a workgroup per 256 pixels of a screen tile (grid-stride): every wave forms the tile's mesh mask as `plan_tiles` does
+//   (tile_mesh_mask without the lens padding); a tile nothing can touch — more than nine in ten of a full-size frame — is
+//   filled with the miss constants and builds no ray; the scene tables go to LDS at the workgroup's first touched tile only
+//   a touched tile: a lane per pixel, rows of the tile along the lanes, 16 B per lane and plane (the depths of four
+//   neighbouring pixels are collected into one lane where the rows are 16-byte aligned)
+// ---------------------------------------------------------------------------------------------
+struct Surface {  // mcrt_surface in registers
+    int mesh, face, tx, ty;
+    float t;
+    V3 p, n;
+    C4 tex;
+};
+__device__ __forceinline__ Surface miss_surface() {
+    return Surface{-1, 0, -1, -1, kFltMax, mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f), C4{0.0f, 0.0f, 0.0f, 0.0f}};
+}
+// what the pixel-centre ray of (px, py) meets, among the meshes of mesh_mask
+template <class SV>
+__device__ __forceinline__ Surface pixel_surface(const SV& sc, const mcrt_config& cfg, const float aspect, const int px, const int py,
+                                                 const unsigned long long mesh_mask) {
+    const float u = (static_cast<float>(px) + 0.5f) / static_cast<float>(cfg.width);
+    const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
+    const Ray ray = camera_ray(sc, u, v, aspect);
+    int mesh;
+    const Hit h = hit_scene(sc, ray, mesh_mask, &mesh);
+    Surface s = miss_surface();
+    if (h.hit) {
+        s.mesh = mesh;
+        s.face = face_slot(h.axis, h.neg) | (h.back ? MCRT_ID_BACK : 0) | (h.outer ? MCRT_ID_OUTER : 0);
+        hit_face_texel(sc, mesh, h, s.tx, s.ty);
+        s.t = h.t;
+        s.p = h.p;
+        s.n = h.n;
+        s.tex = h.tex;
+    }
+    return s;
+}
+// tile_mesh_mask for the pinhole camera: lane m of the calling wave tests mesh m
+__device__ __forceinline__ unsigned long long layers_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect, const int lane) {
+    const bool cull = sc.hdr->cull_ok != 0 && sc.n_meshes < 64;
+    bool touch = lane < sc.n_meshes;
+    if (touch && cull) touch = mesh_touches_tile(sc.meshes[lane], tg, cfg, aspect, 0.0f);
+    unsigned long long mask = __ballot(touch);
+    if (!cull && sc.n_meshes > 0) mask = ~0ull;
+    return mask;
+}
+template <int kView>
+__device__ __forceinline__ void layers_body(const LayersFrame& __restrict__ f, const LayersShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const int n_tiles = sh.tiles_x * sh.tiles_y;
+    // depths as one 16-byte store per four pixels: every tile row starts and ends on a 16-byte boundary of the plane
+    const bool quads = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.depth) & 15u) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    // a unit = kBlock pixels of a tile: a touched 32x32 tile is traced by four workgroups, a ray per lane each
+    const int parts = sh.parts;
+    const int n_units = n_tiles * parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        const int tile = unit / parts, part = unit - tile * parts;
+        const int tyi = tile / sh.tiles_x, txi = tile - tyi * sh.tiles_x;
+        TileGeom tg;
+        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+        tg.owned_row = tyi, tg.frame_tile = tile;
+        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
+        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
+        const unsigned long long mask = layers_tile_mask(scg, cfg, tg, aspect, lane);  // the same in every wave of the workgroup
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        const unsigned pix = p0 + static_cast<unsigned>(tid);
+        const bool valid = pix < npix;
+        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
+        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
+        Surface s = miss_surface();
+        if (mask != 0ull && valid) s = pixel_surface(sc, cfg, aspect, tg.x + lx, tg.y + ly, mask);
+        if (f.depth) {
+            if (quads) {  // tg.w is a multiple of 4: lanes 4k .. 4k+3 hold four neighbours of one row, all valid or none
+                const float t1 = __shfl_down(s.t, 1), t2 = __shfl_down(s.t, 2), t3 = __shfl_down(s.t, 3);
+                if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(f.depth + idx) = make_float4(s.t, t1, t2, t3);
+            } else if (valid) {
+                f.depth[idx] = s.t;
+            }
+        }
+        if (valid) {
+            if (f.normal) f.normal[idx] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
+            if (f.albedo) f.albedo[idx] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
+            if (f.id) f.id[idx] = make_int4(s.mesh, s.face, s.tx, s.ty);
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock) void layers_kernel(const LayersFrame f, const LayersShape sh) {
+    layers_body<kView>(f, sh);
+}
+using LayersTable = const __attribute__((address_space(4))) LayersFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock) void layers_batch_kernel(LayersTable table, const LayersShape sh) {
+    layers_body<kView>(*(const LayersFrame*)(table + blockIdx.y), sh);
+}
+// a lane per picked pixel, over the HBM view with every mesh tested (the tile masks only leave out meshes that cannot be hit)
+__global__ __launch_bounds__(64) void pick_kernel(const uint8_t* __restrict__ scene, const LayersShape sh, const int32_t* __restrict__ xy, const int n,
+                                                  mcrt_surface* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const SceneView sc = view_of(scene);
+    const float aspect = static_cast<float>(sh.cfg.width) / static_cast<float>(sh.cfg.height);
+    const Surface s = pixel_surface(sc, sh.cfg, aspect, xy[2 * i], xy[2 * i + 1], ~0ull);
+    float4* o = reinterpret_cast<float4*>(out + i);  // 64 bytes, 16-aligned (hipMalloc)
+    o[0] = make_float4(__int_as_float(s.mesh), __int_as_float(s.face), __int_as_float(s.tx), __int_as_float(s.ty));
+    o[1] = make_float4(s.t, s.p.x, s.p.y, s.p.z);
+    o[2] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
+    o[3] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// skins on resident scenes (kernels.h: SkinPaintFrame): a repaintable handle's blob takes a new skin from an RGBA8 image in
+// device memory.  One workgroup of 256 threads per scene:
+//   the image (16 or 8 KB) and the host's 256 floats u8 / 255.0f go to LDS, 16 bytes per lane where the image's address allows
+//   1 lane / pool texel (strides of 256)   its skin pixel through the map, four table reads, one 16-byte store into the pool;
+//                                          two ballots per wave — alpha == 0 and alpha > 0, which for a byte is a == 0 and
+//                                          a != 0 — interleaved by lanes 0..3 into the wave's four alpha-predicate words;
+//                                          a texel with alpha 0 sets its mesh's bit in LDS
+//   1 lane / mesh                          the MESH_OPAQUE bit of FlatMesh::flags, an ordinary load and store
+// Every store is a vector store; nothing of the blob but the pool, the predicate words and that bit is written.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSkinBlock = 256;
+__device__ __forceinline__ uint32_t spread16(uint32_t x) {  // bit j of the low 16 bits → bit 2j
+    x = (x | (x << 8)) & 0x00ff00ffu;
+    x = (x | (x << 4)) & 0x0f0f0f0fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return x;
+}
+__device__ __forceinline__ void skin_paint_body(const SkinPaintFrame& __restrict__ f, const SkinPaintShape& __restrict__ sh) {
+    __shared__ __align__(16) uint32_t s_skin[64 * 64];
+    __shared__ float s_unit[256];
+    __shared__ uint32_t s_clear;  // bit m: a texel of mesh m has alpha 0
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float* __restrict__ unit = static_cast<const float*>(sh.tables);
+    const uint16_t* __restrict__ map = reinterpret_cast<const uint16_t*>(unit + 256);
+    const int n_pixels = sh.skin_bytes >> 2;
+    if ((reinterpret_cast<uintptr_t>(f.skin) & 15u) == 0) {
+        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(f.skin);
+        for (int i = tid; i < (n_pixels >> 2); i += kSkinBlock) reinterpret_cast<uint4*>(s_skin)[i] = src[i];
+    } else {
+        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(f.skin);
+        for (int i = tid; i < n_pixels; i += kSkinBlock) s_skin[i] = src[i];
+    }
+    s_unit[tid] = unit[tid];
+    if (tid == 0) s_clear = 0u;
+    __syncthreads();
+    float4* __restrict__ pool = reinterpret_cast<float4*>(f.scene + sh.texel_offset);
+    uint32_t* __restrict__ abits = reinterpret_cast<uint32_t*>(f.scene + sh.alpha_offset);
+    for (int base = 0; base < sh.n_texels; base += kSkinBlock) {  // (uniform per workgroup: every wave reaches its ballots)
+        const int i = base + tid;
+        const bool valid = i < sh.n_texels;
+        bool zero = false, positive = false;
+        if (valid) {
+            const uint32_t entry = map[i];
+            const uint32_t px = s_skin[entry & 4095u];
+            const uint32_t a = px >> 24;
+            pool[i] = make_float4(s_unit[px & 255u], s_unit[(px >> 8) & 255u], s_unit[(px >> 16) & 255u], s_unit[a]);
+            zero = a == 0u, positive = a != 0u;
+            if (zero) atomicOr(&s_clear, 1u << (entry >> 12));
+        }
+        const unsigned long long z = __ballot(zero), p = __ballot(positive);
+        // the wave's 64 texels are words w0 .. w0 + 3 (a wave starts at a multiple of 64 texels): lane k forms word k
+        const uint32_t word = static_cast<uint32_t>(i - lane) / 16u + static_cast<uint32_t>(lane);
+        if (lane < 4 && word < sh.alpha_words) {
+            const uint32_t zk = static_cast<uint32_t>(z >> (16 * lane)) & 0xffffu, pk = static_cast<uint32_t>(p >> (16 * lane)) & 0xffffu;
+            abits[word] = spread16(zk) | (spread16(pk) << 1);
+        }
+    }
+    __syncthreads();
+    if (tid < sh.n_meshes) {
+        FlatMesh* fm = reinterpret_cast<FlatMesh*>(f.scene + sh.mesh_offset) + tid;
+        const uint32_t flags = fm->flags;
+        fm->flags = ((s_clear >> tid) & 1u) ? (flags & ~MESH_OPAQUE) : (flags | MESH_OPAQUE);
+    }
+}
+__global__ __launch_bounds__(kSkinBlock) void skin_paint_kernel(const SkinPaintFrame f, const SkinPaintShape sh) { skin_paint_body(f, sh); }
+using SkinPaintTable = const __attribute__((address_space(4))) SkinPaintFrame*;
+__global__ __launch_bounds__(kSkinBlock) void skin_paint_batch_kernel(SkinPaintTable table, const SkinPaintShape sh) {
+    skin_paint_body(*(const SkinPaintFrame*)(table + blockIdx.y), sh);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ground shadow (kernels.h: GroundFrame): the figure's soft shadow on the plane y = ground_y, as planes of their own.  Per
+// pixel the layers' pixel-centre ray, its point P on the plane, and computeSoftShadow(P, (0, 1, 0)) (shading.cpp:28-60) with
+// the seed of a hit at depth 0 (raytracer.cpp:110-112) — the figure in front of the plane plays no part.  No workspace.
+//   a workgroup per 256 pixels of a screen tile (grid-stride), in the phases of `lit`, handed over through LDS:
+//   1 lane / mesh (every wave)   which meshes can shadow ANY ground point under the tile (ground_tile_mask): none for most
+//                                tiles of a frame — their reached pixels are fully lit without a classification or a ray
+//   1 lane / pixel               ray, plane hit, P; the whole-bundle decision (rt::bundle_classify) from P + N * 1e-3f: lit by
+//                                all S light samples, by none, or undecided with a candidate mask; the undecided are packed
+//   1 lane / undecided pixel     truncated mt19937 (mt[397] from the seed table) → 2·S draws → S disk sample positions in LDS
+//   1 lane / (undecided pixel, light sample)   exact any-hit test on the candidates → lit count by ballot
+//   1 lane / pixel               visibility = lit / S, distance, matte: coalesced stores, 16 bytes per four pixels of a row
+//                                where the rows allow
+// ---------------------------------------------------------------------------------------------
+constexpr int kGroundWaves = 4;  // waves per SIMD the kernels are built for: `lit`'s, whose device functions they inline
+struct GroundPoint {
+    bool reached;
+    float t;  // FLT_MAX where the ray does not reach the plane
+    V3 P;
+};
+// the ray through (fx, fy) pixels of the frame — a pixel centre is (px + 0.5f, py + 0.5f) — against the plane y = g
+__device__ __forceinline__ GroundPoint ground_point(const SceneView& sc, const mcrt_config& cfg, const float aspect, const float g, const float fx,
+                                                    const float fy) {
+    const float u = fx / static_cast<float>(cfg.width);
+    const float v = fy / static_cast<float>(cfg.height);
+    const Ray ray = camera_ray(sc, u, v, aspect);
+    const float t = (g - ray.o.y) / ray.d.y;
+    GroundPoint h;
+    h.reached = ray.d.y != 0.0f && t > 0.0f && t <= kFltMax;
+    h.t = h.reached ? t : kFltMax;
+    h.P = mk(ray.o.x + ray.d.x * t, g, ray.o.z + ray.d.z * t);
+    return h;
+}
+// The meshes that can shadow a ground point under the tile, conservatively: lane m of the calling wave tests mesh m.
+// The tile's pixel-centre rays lie inside its four corner rays; when all four reach the plane (well away from the horizon:
+// |d.y| >= 1e-2) the ground points of the tile lie in the bounding rectangle F of the four corner points — the image of a
+// screen rectangle on a plane in front of the camera is a convex quadrilateral.  A shadow ray leaves Q + (0, 1e-3, 0) for a
+// target T within Rb of the light centre L.  When the lowest target is above the top of a mesh's world box B (bounding
+// sphere when posed) and above the origins, the ray climbs, and it meets B at a point X with gy <= X.y <= B.hi.y only if
+// Q = X + (X - T) * k', 0 <= k' <= k = (L.y - Rb - gy) / (L.y - Rb - B.hi.y) - 1: per axis Q lies in
+// [B.lo - max(0, L + Rb - B.lo) * k, B.hi + max(0, B.hi - L + Rb) * k] — B's shadow from the light centre, widened by the
+// light's radius in the ratio of B's height to the light's clearance.  A mesh whose interval misses F on x or z, with margins
+// far above the float error of the points (2e-3 of the footprint's reach, 1e-4 of the interval, 16 slacks), shadows no
+// pixel of the tile.  Every other case keeps the mesh: a light that is not clear above the box, a corner that misses the
+// plane or grazes it, 64 meshes or more, cull_ok == 0, non-finite values (every comparison is written to fail open).
+__device__ __forceinline__ unsigned long long ground_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect,
+                                                               const float g, const float R, const int lane) {
+    const int n = sc.n_meshes;
+    if (n <= 0) return 0ull;
+    const unsigned long long all = n < 64 ? (1ull << n) - 1ull : ~0ull;
+    if (sc.hdr->cull_ok == 0 || n >= 64) return all;
+    const float slack = sc.hdr->mask_slack;
+    float fx0 = kFltMax, fx1 = -kFltMax, fz0 = kFltMax, fz1 = -kFltMax, reach = 0.0f;
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float fx = static_cast<float>(tg.x + ((c & 1) ? tg.w : 0)), fy = static_cast<float>(tg.y + ((c & 2) ? tg.h : 0));
+        const Ray ray = camera_ray(sc, fx / static_cast<float>(cfg.width), fy / static_cast<float>(cfg.height), aspect);
+        const float t = (g - ray.o.y) / ray.d.y;
+        ok = ok && __builtin_fabsf(ray.d.y) >= 1e-2f && t > 0.0f && t < 1e30f;
+        const float dx = ray.d.x * t, dz = ray.d.z * t;
+        const float x = ray.o.x + dx, z = ray.o.z + dz;
+        fx0 = __builtin_fminf(fx0, x), fx1 = __builtin_fmaxf(fx1, x), fz0 = __builtin_fminf(fz0, z), fz1 = __builtin_fmaxf(fz1, z);
+        reach = __builtin_fmaxf(reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dz)), t));
+        ok = ok && x == x && z == z;  // (fmin / fmax drop a NaN)
+    }
+    ok = ok && reach < 1e30f && slack < 1e30f;
+    if (!ok) return all;
+    const float fm = 2e-3f * reach + 16.0f * slack;
+    const V3 L = ld3(sc.hdr->light_pos);
+    const float Rb = R * 1.001f + slack;
+    const float gy = g + 1e-3f;     // the shadow rays' origins
+    const float low = L.y - Rb;     // the lowest target
+    bool touch = lane < n;
+    if (touch) {
+        const FlatMesh& m = sc.meshes[lane];
+        if (m.flags & MESH_EMPTY) {
+            touch = false;  // intersection.cpp:205: never hit
+        } else {
+            V3 lo = ld3(m.lo), hi = ld3(m.hi);
+            bool bounded = true;
+            if (m.flags & MESH_ROTATED) {
+                const float r = m.sphere[3];
+                bounded = r >= 0.0f;
+                lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
+                hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
+            }
+            const float h = low - gy, c = low - hi.y;  // the light's height above the origins and above the box
+            if (bounded && h > 0.0f && c > 0.01f * h && c > 64.0f * slack) {
+                if (hi.y < gy - 64.0f * slack) {
+                    touch = false;  // the box ends below the origins and every ray climbs
+                } else {
+                    const float k = __builtin_fmaxf(h / c - 1.0f, 0.0f);
+                    const float qx0 = lo.x - __builtin_fmaxf(0.0f, L.x + Rb - lo.x) * k, qx1 = hi.x + __builtin_fmaxf(0.0f, hi.x - L.x + Rb) * k;
+                    const float qz0 = lo.z - __builtin_fmaxf(0.0f, L.z + Rb - lo.z) * k, qz1 = hi.z + __builtin_fmaxf(0.0f, hi.z - L.z + Rb) * k;
+                    const float mg = fm + 1e-4f * (__builtin_fabsf(qx0) + __builtin_fabsf(qx1) + __builtin_fabsf(qz0) + __builtin_fabsf(qz1));
+                    const bool out = (qx1 + mg < fx0) | (qx0 - mg > fx1) | (qz1 + mg < fz0) | (qz0 - mg > fz1);
+                    touch = !out;
+                }
+            }
+        }
+    }
+    return __ballot(touch);
+}
+// one value per pixel into a plane: 16 bytes per four neighbouring pixels of a row where `quads` (lanes 4k .. 4k+3 then hold
+// four neighbours of one row, all valid or none)
+__device__ __forceinline__ void store_plane(float* __restrict__ plane, const bool quads, const bool valid, const int lane, const size_t idx, const float val) {
+    if (quads) {
+        const float v1 = __shfl_down(val, 1), v2 = __shfl_down(val, 2), v3 = __shfl_down(val, 3);
+        if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(plane + idx) = make_float4(val, v1, v2, v3);
+    } else if (valid) {
+        plane[idx] = val;
+    }
+}
+template <int kView>
+__device__ __forceinline__ void ground_body(const GroundFrame& __restrict__ f, const GroundShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks][inside masks][P.x, P.z][lit counts][undecided list][positions: pass x S x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.tiles.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const float g = f.ground_y;
+    const V3 lpos = ld3(scg.hdr->light_pos);
+    const float lradius = scg.hdr->light_radius;
+    const int S = sh.samples;
+    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
+    const float R = soft ? lradius : 0.0f;
+    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per pixel
+    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
+    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    const V3 N = mk(0.0f, 1.0f, 0.0f);
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(area);
+    unsigned long long* s_ins = s_cand + kBlock;
+    float2* s_pxz = reinterpret_cast<float2*>(s_ins + kBlock);
+    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_pxz + kBlock);
+    uint32_t* s_und = s_lit + kBlock;
+    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    // four neighbouring pixels of a row per store: every tile row starts and ends on a four-pixel boundary of the plane
+    const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
+    const bool quads_vis = quad_rows && (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
+    const bool quads_dist = quad_rows && (reinterpret_cast<uintptr_t>(f.distance) & 15u) == 0;
+    const bool quads_matte = quad_rows && (reinterpret_cast<uintptr_t>(f.matte) & 3u) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    const int parts = sh.tiles.parts;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        const int tile = unit / parts, part = unit - tile * parts;
+        const int tyi = tile / sh.tiles.tiles_x, txi = tile - tyi * sh.tiles.tiles_x;
+        TileGeom tg;
+        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+        tg.owned_row = tyi, tg.frame_tile = tile;
+        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
+        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
+        const unsigned long long mask = ground_tile_mask(scg, cfg, tg, aspect, g, R, lane);  // the same in every wave of the workgroup
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        const unsigned pix = p0 + static_cast<unsigned>(tid);
+        const bool valid = pix < npix;
+        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
+        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
+        GroundPoint gp = ground_point(scg, cfg, aspect, g, static_cast<float>(tg.x + lx) + 0.5f, static_cast<float>(tg.y + ly) + 0.5f);
+        if (!valid) gp.reached = false, gp.t = kFltMax;
+        if (f.distance) store_plane(f.distance, quads_dist, valid, lane, idx, gp.t);
+        uint32_t lit = pairs;  // a pixel that misses the plane, and every pixel of a tile no mesh can shadow
+        bool undecided = false;
+        if (mask != 0ull) {  // uniform
+            // ---- a lane per pixel: the whole-bundle decision
+            if (gp.reached) {
+                const V3 O = gp.P + N * 1e-3f;
+                unsigned long long cand;
+                const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
+                cand &= mask;
+                undecided = known < 0;
+                s_cand[tid] = cand;
+                s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
+                s_pxz[tid] = make_float2(gp.P.x, gp.P.z);
+                if (!undecided) lit = static_cast<uint32_t>(known);
+            }
+            s_lit[tid] = 0u;
+            int total = 0;
+            const int rank = block_rank(undecided, s_wcnt, total);
+            if (undecided) s_und[rank] = static_cast<uint32_t>(tid);
+            const uint32_t n_und = static_cast<uint32_t>(total);
+            if (n_und) __syncthreads();  // uniform
+            for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
+                const uint32_t nu = min(pass, n_und - u0);
+                if (u0) __syncthreads();  // the previous pass's rays have read the positions
+                // ---- a lane per undecided pixel: its mt19937 stream and the S disk sample positions
+                if (soft && static_cast<uint32_t>(tid) < nu) {
+                    const float2 xz = s_pxz[s_und[u0 + tid]];
+                    // (outside the seed table's window — ground points far out, at the horizon — the 397-step recurrence)
+                    disk_sample_positions(scg, f.seed_table, nullptr, mk(xz.x, g, xz.y), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
+                }
+                __syncthreads();
+                // ---- a lane per (undecided pixel, light sample); every lane of a wave runs the same number of turns (ballot inside)
+                const uint32_t n_rays = nu * pairs;
+                for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
+                    const uint32_t q = q0 + static_cast<uint32_t>(lane);
+                    bool visible = false;
+                    uint32_t k = 0;
+                    if (q < n_rays) {
+                        k = s_und[u0 + q / pairs];
+                        const float2 xz = s_pxz[k];
+                        const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
+                        visible = !in_shadow_masked(sc, mk(xz.x, g, xz.y), N, target, s_cand[k], s_ins[k]);
+                    }
+                    if (pow2) {
+                        const unsigned long long bal = __ballot(visible);
+                        if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
+                            const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
+                            s_lit[k] = static_cast<uint32_t>(__popcll(grp));
+                        }
+                    } else if (visible) {
+                        atomicAdd(&s_lit[k], 1u);
+                    }
+                }
+            }
+            // the counts are complete; behind this barrier nothing of the unit is read across lanes any more, so the next
+            // unit may overwrite the area
+            if (n_und) __syncthreads();
+            if (undecided) lit = s_lit[tid];
+        }
+        // ---- a lane per pixel: the planes
+        float vis = static_cast<float>(lit) / static_cast<float>(pairs);
+        MCRT_HOOK_GROUND_PIXEL(vis, gp.reached, mask == 0ull, undecided)
+        if (f.visibility) store_plane(f.visibility, quads_vis, valid, lane, idx, vis);
+        if (f.matte) {
+            const uint32_t a = static_cast<unsigned char>(sclamp(1.0f - vis, 0.0f, 1.0f) * 255.0f + 0.5f);
+            if (quads_matte) {
+                const uint32_t a1 = __shfl_down(a, 1), a2 = __shfl_down(a, 2), a3 = __shfl_down(a, 3);
+                if (valid && (lane & 3) == 0) *reinterpret_cast<uint32_t*>(f.matte + idx) = a | (a1 << 8) | (a2 << 16) | (a3 << 24);
+            } else if (valid) {
+                f.matte[idx] = static_cast<uint8_t>(a);
+            }
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_kernel(const GroundFrame f, const GroundShape sh) {
+    ground_body<kView>(f, sh);
+}
+using GroundTable = const __attribute__((address_space(4))) GroundFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_batch_kernel(GroundTable table, const GroundShape sh) {
+    ground_body<kView>(*(const GroundFrame*)(table + blockIdx.y), sh);
+}
+
+// ---- host-side launchers (the shapes and LDS sizes they take: render_plan.cpp) ----------------------
+// One launch of a tile pass (layers, ground) over the tile grid `tiles`.  arg: the frame, or the device table of n_frames
+// frames (blockIdx.y = frame); kernel_of(view tag): the kernel of that variant; dyn: its dynamic LDS, hbm_dyn: the HBM
+// variant's (which stages no tables)
+template <class Arg, class Shape, class KernelOf>
+static hipError_t launch_tile_pass(const Arg& arg, int n_frames, const Shape& shape, const LayersShape& tiles, int view, size_t dyn, size_t hbm_dyn,
+                                   hipStream_t stream, KernelOf kernel_of) {
+    const long long n_units = static_cast<long long>(tiles.tiles_x) * tiles.tiles_y * tiles.parts;
+    if (n_units <= 0 || n_frames <= 0) return hipSuccess;
+    if (n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid), static_cast<unsigned>(n_frames));
+    with_view(view, [&](auto v) { hipLaunchKernelGGL(kernel_of(v), grid, dim3(kBlock), decltype(v)::value == kViewHbm ? hbm_dyn : dyn, stream, arg, shape); });
+    return hipGetLastError();
+}
+hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream) {
+    return launch_tile_pass(f, 1, shape, shape, view, layers_lds_bytes(f), 0, stream, [](auto v) { return layers_kernel<decltype(v)::value>; });
+}
+hipError_t launch_layers_batch(const LayersFrame* d_table, int n_frames, const LayersShape& shape, int view, size_t max_dyn, hipStream_t stream) {
+    return launch_tile_pass(LayersTable(d_table), n_frames, shape, shape, view, max_dyn, 0, stream, [](auto v) { return layers_batch_kernel<decltype(v)::value>; });
+}
+// ---- ground shadow (kernels.h): the HBM variant keeps the block's area in dynamic LDS -----------------------
+hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int view, hipStream_t stream) {
+    const size_t dyn = ground_lds_bytes(f, shape);
+    return launch_tile_pass(f, 1, shape, shape.tiles, view, dyn, dyn, stream, [](auto v) { return ground_kernel<decltype(v)::value>; });
+}
+hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream) {
+    return launch_tile_pass(GroundTable(d_table), n_frames, shape, shape.tiles, view, max_dyn, max_dyn, stream, [](auto v) { return ground_batch_kernel<decltype(v)::value>; });
+}
+hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pick_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, scene, shape, d_xy, n, d_out);
+    return hipGetLastError();
+}
+// ---- skins on resident scenes (kernels.h) -----------------------------------------------------------
+static bool skin_shape_ok(const SkinPaintShape& sh) {  // what the kernel's fixed LDS image and its 4-bit mesh field hold
+    return sh.tables && sh.n_texels > 0 && sh.n_texels <= kSkinMaxTexels && sh.n_meshes > 0 && sh.n_meshes <= kSkinMaxMeshes &&
+           (sh.skin_bytes == 64 * 64 * 4 || sh.skin_bytes == 64 * 32 * 4) && sh.alpha_words == static_cast<uint32_t>((sh.n_texels + 15) / 16);
+}
+hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream) {
+    if (!skin_shape_ok(shape) || !f.scene || !f.skin) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(skin_paint_kernel, dim3(1), dim3(kSkinBlock), 0, stream, f, shape);
+    return hipGetLastError();
+}
+hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream) {
+    if (n_frames <= 0) return hipSuccess;
+    if (!skin_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(skin_paint_batch_kernel, dim3(1, static_cast<unsigned>(n_frames)), dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shape);
+    return hipGetLastError();
+}
+
+}  // namespace mcrt

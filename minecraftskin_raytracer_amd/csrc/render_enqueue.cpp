@@ -125,11 +125,11 @@ int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int fir
     p.out8 = d_out8;
     p.background = rect ? MCRT_BACKGROUND_REFERENCE : sc->background;  // (plan_workspace picks the draws layout by it)
     p.draws_per_sample = draws_per_sample(*cfg);
-    const bool fits = sc->alpha_words <= static_cast<uint32_t>(kAlphaLdsWordsMax) && sc->n_meshes * 6 <= static_cast<uint32_t>(kFaceLdsEntriesMax);
-    p.scene_in_lds = fits ? 1 : 0;
+    const LdsFit fit = lds_fit(sc->alpha_words, sc->n_meshes, sc->posed);
+    p.scene_in_lds = fit.view != kViewHbm ? 1 : 0;
     p.scene_posed = sc->posed ? 1 : 0;
-    p.lds_alpha_words = fits ? static_cast<int>(sc->alpha_words) : 0;
-    p.lds_face_entries = fits ? static_cast<int>(sc->n_meshes * 6) : 0;
+    p.lds_alpha_words = fit.alpha_words;
+    p.lds_face_entries = fit.face_entries;
     // The budget bounds the batch size; when the device cannot give that much right now (other
     // allocations, a shared GPU) the budget is halved — down to one tile row per batch — and the
     // lane's buffers are re-planned, instead of failing the render.

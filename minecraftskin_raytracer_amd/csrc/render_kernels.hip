@@ -1,4 +1,4 @@
-// render_kernels.hip — hand-written HIP kernels for gfx950 (MI355X / CDNA4).
+// render_kernels.hip — the render pipeline: hand-written HIP kernels for gfx950 (MI355X / CDNA4) and their launchers.
 //
 // The hot path of the reference, TileRenderer::renderTile (tile_renderer.cpp:71-127) with
 // RayTracer::traceRay underneath, as a wavefront pipeline: every stage is a small, high-occupancy
@@ -39,62 +39,20 @@
 //   (general variants — per-hit RNG streams longer than 227 draws, or more than kFlatMaxBounces bounces — run
 //   light_samples / shadow / level_shade once per recursion level instead of lit, and `primary` traces no
 //   reflection rays)
-//   layers / pick   (not a stage of a render: mcrt_render_layers*, mcrt_scene_pick) a workgroup per tile: the tile's mesh
-//                                     mask, then either the miss constants or one pixel-centre ray per lane — depth, normal,
-//                                     albedo and {mesh, face, texel} planes straight from the scene blob, no workspace
-//   ground          (not a stage of a render either: mcrt_render_ground*) the figure's soft shadow on a floor plane, per 256
-//                                     pixels of a tile: the meshes that can shadow the tile's ground points, then `lit`'s
-//                                     phases for the pixels' plane points — visibility, distance and matte planes
 // Records live in HBM as SoA float4 arrays.  Every unit owns a fixed slot range (its samples); its
 // primary hits are compacted to the front of that range with an LDS prefix sum and a per-unit count —
 // NO global atomics on the hot path (a returning atomic on one word sustains only ~88 ops/us on this
 // chip; per-wave queue claims made `primary` atomic-bound); deeper records take one atomic per 256.
 // A frame is cut into batches of tile rows so that the worst case (every sample of a touched tile hits) fits.
 // No MFMA: there is no dense contraction anywhere on this path.
-#include "kernels.h"
-
-#include <cstring>
-#include "rt_core.h"
-
-// Verification hooks.  tools/decide_check.sh builds a variant of the library with -DMCRT_KERNEL_HOOKS='"decide_check_hooks.h"'
-// (tools/decide_check_hooks.h: every record `lit` decides is traced as well and contradictions are counted and printed);
-// the product build compiles the hooks to nothing.  tools/gpu_ground.py builds another variant with tools/ground_class_hooks.h: the
-// ground pass then writes every pixel's class (missed, culled by tile, decided, traced) into its visibility plane.
-#ifdef MCRT_KERNEL_HOOKS
-#include MCRT_KERNEL_HOOKS
-#else
-#define MCRT_HOOK_LIT_SHARED
-#define MCRT_HOOK_LIT_CLASSIFIED(known, undecided, cand, O)
-#define MCRT_HOOK_LIT_SHADED(lit, r)
-#define MCRT_HOOK_RESOLVE_BEGIN()
-#endif
-#ifndef MCRT_HOOK_GROUND_PIXEL
-#define MCRT_HOOK_GROUND_PIXEL(vis, reached, culled, undecided)
-#endif
+// Beside this file: the stand-alone passes (layers and picks, ground shadow, skin repaints) in pass_kernels.hip, the small
+// kernels and the probes in util_kernels.hip, what the kernel files share in kernel_common.h, and the host planning that
+// sizes every launch here (workspace, batches, grids, plates) in render_plan.cpp.
+#include "kernel_common.h"
 
 namespace mcrt {
 
 using namespace rt;
-
-constexpr int kBlock = 256;
-constexpr int kChunk = 256;        // work items per chunk: one per thread
-#ifndef MCRT_PRIMARY_GRID
-#define MCRT_PRIMARY_GRID 1280
-#endif
-constexpr int kPrimaryGrid = MCRT_PRIMARY_GRID; // persistent primary workgroups (5 per CU: the kernel is built for 5 waves per SIMD)
-constexpr int kQueueGrid = 2048;   // workgroups of the queue kernels (grid-stride over device-side counts)
-constexpr int kLitGridAlone = 4096;  // `lit` of a frame that has the device to itself
-constexpr int kResolveGrid = 4096;
-constexpr int kSharedGrid = 896;   // every kernel of a frame that shares the device (choose_grids): 3.5 workgroups per CU
-
-// n / d for a divisor that is the same for the whole wave: a shift when it is a power of two (tile widths of 32,
-// 4 samples per pixel: the usual case) instead of the ~25-instruction expansion of a 32-bit division.
-struct UDiv {
-    unsigned d;
-    int shift;  // log2(d), or -1
-    __device__ __forceinline__ explicit UDiv(unsigned dv) : d(dv), shift((dv & (dv - 1u)) == 0u && dv != 0u ? static_cast<int>(__builtin_ctz(dv)) : -1) {}
-    __device__ __forceinline__ unsigned div(unsigned n) const { return shift >= 0 ? n >> shift : n / d; }
-};
 
 // (px + jitter) / width and (py + jitter) / height of a sample (tile_renderer.cpp:88-89): rt::div_frame where the
 // frame's size lies in its verified range, the general division otherwise
@@ -105,15 +63,6 @@ struct FrameDiv {
         : w(static_cast<float>(p.cfg.width)), h(static_cast<float>(p.cfg.height)), rw(p.inv_width), rh(p.inv_height), fast(p.div_frame != 0) {}
     __device__ __forceinline__ float u(float x) const { return fast ? div_frame(x, w, rw) : x / w; }
     __device__ __forceinline__ float v(float y) const { return fast ? div_frame(y, h, rh) : y / h; }
-};
-
-// ---------------------------------------------------------------------------------------------
-// tile geometry helpers (TileRenderer::generateTiles, tile_renderer.cpp:18-39)
-// ---------------------------------------------------------------------------------------------
-struct TileGeom {
-    int x, y, w, h;
-    int owned_row;  // index of this tile's row among the rows this launch owns
-    int frame_tile;  // row-major index of the tile in the whole frame (its slot in a background or draw plate, kernels.h)
 };
 
 __device__ __forceinline__ TileGeom tile_of(const RenderParams& p, int owned_tile) {
@@ -159,14 +108,6 @@ __global__ __launch_bounds__(64) void seed_tiles_kernel(RenderParams p, int n_ti
 // pixel store: the float4 frame and/or its RGBA8 quantisation `(u8)(clamp(c,0,1)*255+0.5)`
 // (image_writer.cpp:18-22 ≡ image.cpp:31-36) — the epilogue of `primary` (background tiles) and `resolve`
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uchar4 quantize_pixel(float4 c) {
-    uchar4 q;
-    q.x = static_cast<unsigned char>(sclamp(c.x, 0.0f, 1.0f) * 255.0f + 0.5f);
-    q.y = static_cast<unsigned char>(sclamp(c.y, 0.0f, 1.0f) * 255.0f + 0.5f);
-    q.z = static_cast<unsigned char>(sclamp(c.z, 0.0f, 1.0f) * 255.0f + 0.5f);
-    q.w = static_cast<unsigned char>(sclamp(c.w, 0.0f, 1.0f) * 255.0f + 0.5f);
-    return q;
-}
 __device__ __forceinline__ void store_pixel(float4* __restrict__ out_frame, uchar4* __restrict__ out8, size_t idx, float4 v) {
     if (out_frame) out_frame[idx] = v;
     if (out8) out8[idx] = quantize_pixel(v);
@@ -190,7 +131,6 @@ __device__ __forceinline__ void store_pixel(float4* __restrict__ out_frame, ucha
 // (Generating the stream inside `primary` with block-wide twists made that kernel barrier-bound: 3
 // barriers per 624 draws, ~60 us of the 1080p / 4 spp frame, milliseconds at 64 spp.)
 // ---------------------------------------------------------------------------------------------
-constexpr int kStreamWaves = 4;  // tiles per workgroup
 // the pixels [lo, hi) of a background tile; draw(g, jx, jy) = draws number g, g + 1 of the tile's stream (g even)
 // kToPlate: out_frame is a background plate (kernels.h) — the pixel goes to the tile's slot, tile-major, instead of the frame
 template <bool kToPlate = false, class DrawFn>
@@ -402,86 +342,6 @@ __device__ __forceinline__ void tile_stream_wave(const SceneView& sc, const uint
 }
 
 // ---------------------------------------------------------------------------------------------
-// primary-ray culling mask of a tile
-// ---------------------------------------------------------------------------------------------
-// lens_pad: how far a thin-lens ray can displace the image of a point of this mesh, in the bound's
-// units (0 for the pinhole camera)
-__device__ __forceinline__ bool mesh_touches_tile(const FlatMesh& m, const TileGeom& t, const mcrt_config& cfg,
-                                                  float aspect, float lens_pad) {
-    float u0 = m.screen[0], v0 = m.screen[1], u1 = m.screen[2], v1 = m.screen[3];
-    if (u0 > u1) return true;  // no bound available
-    u0 -= lens_pad, v0 -= lens_pad, u1 += lens_pad, v1 += lens_pad;
-    const float W = static_cast<float>(cfg.width), H = static_cast<float>(cfg.height);
-    // tile extent padded by 2 pixels, in the bound's units (x: (2u-1)*aspect, y: 1-2v, +y up)
-    float tu0 = (2.0f * (static_cast<float>(t.x) - 2.0f) / W - 1.0f) * aspect - 1e-3f * aspect - 1e-3f;
-    float tu1 = (2.0f * (static_cast<float>(t.x + t.w) + 2.0f) / W - 1.0f) * aspect + 1e-3f * aspect + 1e-3f;
-    float tv1 = 1.0f - 2.0f * (static_cast<float>(t.y) - 2.0f) / H + 2e-3f;
-    float tv0 = 1.0f - 2.0f * (static_cast<float>(t.y + t.h) + 2.0f) / H - 2e-3f;
-    return !(u1 < tu0 || u0 > tu1 || v1 < tv0 || v0 > tv1);
-}
-
-// ---------------------------------------------------------------------------------------------
-// scene tables staged in LDS: what candidates index PER LANE (face → texture table, alpha bits)
-// ---------------------------------------------------------------------------------------------
-struct LdsTables {
-    const MCRT_LDS uint32_t* abits;
-    const MCRT_LDS int* faces;
-    const MCRT_LDS float* mtab;
-};
-// dyn = dynamic LDS base; layout [face table: 4 ints per (mesh, face)][mesh table: kMeshTabWords per
-// mesh][alpha words].  Collective.
-__device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const int lds_face_entries, const int lds_alpha_words, unsigned char* dyn) {
-    int* s_faces = reinterpret_cast<int*>(dyn);
-    float* s_mtab = reinterpret_cast<float*>(dyn + static_cast<size_t>(lds_face_entries) * 16);
-    const int n_meshes = lds_face_entries / 6;
-    uint32_t* s_abits = reinterpret_cast<uint32_t*>(dyn + static_cast<size_t>(lds_face_entries) * 16 +
-                                                    static_cast<size_t>(n_meshes) * kMeshTabWords * 4);
-    for (int i = threadIdx.x; i < lds_alpha_words; i += blockDim.x) s_abits[i] = g.abits[i];
-    for (int i = threadIdx.x; i < lds_face_entries; i += blockDim.x) {
-        const FlatMesh& fm = g.meshes[i / 6];
-        const int f = i - (i / 6) * 6;
-        s_faces[4 * i + 0] = fm.tex_off[f];
-        s_faces[4 * i + 1] = fm.tex_w[f];
-        s_faces[4 * i + 2] = fm.tex_h[f];
-        s_faces[4 * i + 3] = 0;
-    }
-    for (int i = threadIdx.x; i < n_meshes; i += blockDim.x) {
-        const FlatMesh& fm = g.meshes[i];
-        float* t = s_mtab + i * kMeshTabWords;
-        t[0] = fm.lo[0], t[1] = fm.lo[1], t[2] = fm.lo[2];
-        t[3] = fm.hi[0], t[4] = fm.hi[1], t[5] = fm.hi[2];
-        t[6] = __uint_as_float(fm.flags);
-        t[7] = 0.0f;
-        t[8] = fm.pivot[0], t[9] = fm.pivot[1], t[10] = fm.pivot[2];
-        t[11] = 0.0f;
-        t[12] = fm.inv_z_cos, t[13] = fm.inv_z_sin, t[14] = fm.inv_x_cos, t[15] = fm.inv_x_sin;
-        t[16] = fm.fwd_x_cos, t[17] = fm.fwd_x_sin, t[18] = fm.fwd_z_cos, t[19] = fm.fwd_z_sin;
-        t[20] = fm.sphere[0], t[21] = fm.sphere[1], t[22] = fm.sphere[2], t[23] = fm.sphere[3];
-    }
-    __syncthreads();
-    return LdsTables{(const MCRT_LDS uint32_t*)s_abits, (const MCRT_LDS int*)s_faces, (const MCRT_LDS float*)s_mtab};
-}
-__device__ __forceinline__ LdsTables stage_tables(const SceneView& g, const RenderParams& p, unsigned char* dyn) {
-    return stage_tables(g, p.lds_face_entries, p.lds_alpha_words, dyn);
-}
-// kernel variants by scene: kViewHbm — tables too large for LDS (reads HBM; any pose);
-// kViewLds — tables in LDS, posed meshes present; kViewLdsUnposed — tables in LDS, no posed mesh
-constexpr int kViewHbm = 0, kViewLds = 1, kViewLdsUnposed = 2;
-template <int kView>
-struct ViewSel {
-    using type = SceneViewLdsT<kView == kViewLds>;
-    static __device__ __forceinline__ type make(const SceneView& g, const RenderParams& p, unsigned char* dyn) {
-        LdsTables t = stage_tables(g, p, dyn);
-        return view_with_lds<kView == kViewLds>(g, t.abits, t.faces, t.mtab);
-    }
-};
-template <>
-struct ViewSel<kViewHbm> {
-    using type = SceneView;
-    static __device__ __forceinline__ type make(const SceneView& g, const RenderParams&, unsigned char*) { return g; }
-};
-
-// ---------------------------------------------------------------------------------------------
 // queue helpers
 // ---------------------------------------------------------------------------------------------
 // counters[0]: number of planned units (one atomic add per touched tile, in plan_tiles)
@@ -503,25 +363,6 @@ constexpr int kCntOverflow = kCounterWords - 1;  // set if more tiles are touche
 // launch of a lone frame's 195.)  `resolve` itself reads the one count it needs from frame_info, which `primary` leaves.
 __device__ __forceinline__ uint32_t counted(const WaveSpace& ws, int i) { return ws.counters[i] - ws.counter_base[i]; }
 __device__ __forceinline__ uint32_t count_add(const WaveSpace& ws, int i, uint32_t n) { return atomicAdd(&ws.counters[i], n) - ws.counter_base[i]; }
-
-// Rank of this thread's item among the workgroup's flagged items, and their total: ballot per wave,
-// four wave counts through LDS.  Collective (two barriers: the counts are reusable right after).
-__device__ __forceinline__ int block_rank(bool flag, int* s_wcnt, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(flag);
-    if (lane == 0) s_wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int wv = 0; wv < kBlock / 64; ++wv) {
-        const int c = s_wcnt[wv];
-        if (wv < wave) before += c;
-        total += c;
-    }
-    __syncthreads();
-    return before + __popcll(bal & ((1ull << lane) - 1ull));
-}
 
 __device__ __forceinline__ void push_entry(const WaveSpace& ws, int parity, uint32_t e, const Ray& ray, const Hit& hit,
                                            uint32_t root, int depth) {
@@ -991,7 +832,6 @@ __global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_kernel(con
 // 17.1 ms alone; at 16 spp the staging costs 3-5 % more than it saves (same-box A/B, profiles/r03_experiments).
 // ---------------------------------------------------------------------------------------------
 constexpr int kSlabSamples = 16;
-constexpr int kSlabMinSpp = 33;  // `background_kernel` from this many samples per pixel on
 #ifndef MCRT_BG_WAVES
 #define MCRT_BG_WAVES 3
 #endif
@@ -1337,30 +1177,6 @@ __global__ __launch_bounds__(kBlock, MCRT_SHADOW_WAVES) void shadow_kernel(const
 // record: ~180 MB of the metric frame's counted traffic), and the VALU-bound seeding chains could not
 // overlap the latency-bound shadow rays.  Hard shadows / a point light: no phase A, one ray per record.
 // ---------------------------------------------------------------------------------------------
-// The S disk sample positions of one shaded point (shading.cpp:35-53), by the lane that owns it (`lit`, the ground pass): the
-// truncated engine seeded for (P, depth) — mt[397] from the device's tables where they hold the seed, else the 397-step
-// recurrence — and the light's frame at P.  dst: 3 * S floats.
-__device__ __forceinline__ void disk_sample_positions(const SceneView& scg, const uint32_t* __restrict__ seed_table, const uint32_t* __restrict__ seed_table_full,
-                                                      const V3 P, const int depth, const int S, float* __restrict__ dst) {
-    MtShort rng;
-    const uint32_t seed = shadow_seed(P, depth);
-    const uint32_t slot = seed + kSeedWindowHalf;  // wraps: the window is centred on seed 0
-    if (seed_table && slot < kSeedWindow)
-        rng.seed_known(seed, seed_table[slot]);  // mt[397] of this seed, from the device's table
-    else if (seed_table_full)
-        rng.seed_known(seed, seed_table_full[seed]);  // (a scene at another scale: its seeds leave the window)
-    else
-        rng.seed(seed);  // the 397-step recurrence
-    const LightFrame frame = light_frame(scg, P);
-    for (int i = 0; i < S; ++i) {
-        const float d0 = rng.uniform();
-        const float d1 = rng.uniform();
-        const V3 t = light_sample_on_frame(scg, frame, d0, d1);
-        dst[3 * i + 0] = t.x;
-        dst[3 * i + 1] = t.y;
-        dst[3 * i + 2] = t.z;
-    }
-}
 #ifndef MCRT_LIT_WAVES
 #define MCRT_LIT_WAVES 4
 #endif
@@ -1976,852 +1792,7 @@ __global__ __launch_bounds__(kBlock) void resolve_transparent_batch_kernel(Param
     resolve_body<true>(p.scene, nullptr, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
 }
 
-// ---------------------------------------------------------------------------------------------
-// geometry layers (kernels.h: LayersFrame): depth, normal, albedo and id planes, and single-pixel picks.  One pixel-centre
-// ray per pixel — the reference's primary ray at samplesPerPixel == 1 without depth of field (tile_renderer.cpp:92-103) —
-// and intersectScene; no draws, no records, no shading, no workspace.
-//   a workgroup per 256 pixels of a screen tile (grid-stride): every wave forms the tile's mesh mask as `plan_tiles` does
-//   (tile_mesh_mask without the lens padding); a tile nothing can touch — more than nine in ten of a full-size frame — is
-//   filled with the miss constants and builds no ray; the scene tables go to LDS at the workgroup's first touched tile only
-//   a touched tile: a lane per pixel, rows of the tile along the lanes, 16 B per lane and plane (the depths of four
-//   neighbouring pixels are collected into one lane where the rows are 16-byte aligned)
-// ---------------------------------------------------------------------------------------------
-struct Surface {  // mcrt_surface in registers
-    int mesh, face, tx, ty;
-    float t;
-    V3 p, n;
-    C4 tex;
-};
-__device__ __forceinline__ Surface miss_surface() {
-    return Surface{-1, 0, -1, -1, kFltMax, mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f), C4{0.0f, 0.0f, 0.0f, 0.0f}};
-}
-// what the pixel-centre ray of (px, py) meets, among the meshes of mesh_mask
-template <class SV>
-__device__ __forceinline__ Surface pixel_surface(const SV& sc, const mcrt_config& cfg, const float aspect, const int px, const int py,
-                                                 const unsigned long long mesh_mask) {
-    const float u = (static_cast<float>(px) + 0.5f) / static_cast<float>(cfg.width);
-    const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
-    const Ray ray = camera_ray(sc, u, v, aspect);
-    int mesh;
-    const Hit h = hit_scene(sc, ray, mesh_mask, &mesh);
-    Surface s = miss_surface();
-    if (h.hit) {
-        s.mesh = mesh;
-        s.face = face_slot(h.axis, h.neg) | (h.back ? MCRT_ID_BACK : 0) | (h.outer ? MCRT_ID_OUTER : 0);
-        hit_face_texel(sc, mesh, h, s.tx, s.ty);
-        s.t = h.t;
-        s.p = h.p;
-        s.n = h.n;
-        s.tex = h.tex;
-    }
-    return s;
-}
-// tile_mesh_mask for the pinhole camera: lane m of the calling wave tests mesh m
-__device__ __forceinline__ unsigned long long layers_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect, const int lane) {
-    const bool cull = sc.hdr->cull_ok != 0 && sc.n_meshes < 64;
-    bool touch = lane < sc.n_meshes;
-    if (touch && cull) touch = mesh_touches_tile(sc.meshes[lane], tg, cfg, aspect, 0.0f);
-    unsigned long long mask = __ballot(touch);
-    if (!cull && sc.n_meshes > 0) mask = ~0ull;
-    return mask;
-}
-template <int kView>
-__device__ __forceinline__ void layers_body(const LayersFrame& __restrict__ f, const LayersShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];
-    const SceneView scg = view_of(f.scene);
-    const mcrt_config& cfg = sh.cfg;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
-    const int n_tiles = sh.tiles_x * sh.tiles_y;
-    // depths as one 16-byte store per four pixels: every tile row starts and ends on a 16-byte boundary of the plane
-    const bool quads = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.depth) & 15u) == 0;
-    typename ViewSel<kView>::type sc;
-    bool staged = false;
-    // a unit = kBlock pixels of a tile: a touched 32x32 tile is traced by four workgroups, a ray per lane each
-    const int parts = sh.parts;
-    const int n_units = n_tiles * parts;
-    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        const int tile = unit / parts, part = unit - tile * parts;
-        const int tyi = tile / sh.tiles_x, txi = tile - tyi * sh.tiles_x;
-        TileGeom tg;
-        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
-        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
-        tg.owned_row = tyi, tg.frame_tile = tile;
-        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
-        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
-        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
-        const unsigned long long mask = layers_tile_mask(scg, cfg, tg, aspect, lane);  // the same in every wave of the workgroup
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
-        const unsigned pix = p0 + static_cast<unsigned>(tid);
-        const bool valid = pix < npix;
-        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
-        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
-        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
-        Surface s = miss_surface();
-        if (mask != 0ull && valid) s = pixel_surface(sc, cfg, aspect, tg.x + lx, tg.y + ly, mask);
-        if (f.depth) {
-            if (quads) {  // tg.w is a multiple of 4: lanes 4k .. 4k+3 hold four neighbours of one row, all valid or none
-                const float t1 = __shfl_down(s.t, 1), t2 = __shfl_down(s.t, 2), t3 = __shfl_down(s.t, 3);
-                if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(f.depth + idx) = make_float4(s.t, t1, t2, t3);
-            } else if (valid) {
-                f.depth[idx] = s.t;
-            }
-        }
-        if (valid) {
-            if (f.normal) f.normal[idx] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
-            if (f.albedo) f.albedo[idx] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
-            if (f.id) f.id[idx] = make_int4(s.mesh, s.face, s.tx, s.ty);
-        }
-    }
-}
-template <int kView>
-__global__ __launch_bounds__(kBlock) void layers_kernel(const LayersFrame f, const LayersShape sh) {
-    layers_body<kView>(f, sh);
-}
-using LayersTable = const __attribute__((address_space(4))) LayersFrame*;
-template <int kView>
-__global__ __launch_bounds__(kBlock) void layers_batch_kernel(LayersTable table, const LayersShape sh) {
-    layers_body<kView>(*(const LayersFrame*)(table + blockIdx.y), sh);
-}
-// a lane per picked pixel, over the HBM view with every mesh tested (the tile masks only leave out meshes that cannot be hit)
-__global__ __launch_bounds__(64) void pick_kernel(const uint8_t* __restrict__ scene, const LayersShape sh, const int32_t* __restrict__ xy, const int n,
-                                                  mcrt_surface* __restrict__ out) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const SceneView sc = view_of(scene);
-    const float aspect = static_cast<float>(sh.cfg.width) / static_cast<float>(sh.cfg.height);
-    const Surface s = pixel_surface(sc, sh.cfg, aspect, xy[2 * i], xy[2 * i + 1], ~0ull);
-    float4* o = reinterpret_cast<float4*>(out + i);  // 64 bytes, 16-aligned (hipMalloc)
-    o[0] = make_float4(__int_as_float(s.mesh), __int_as_float(s.face), __int_as_float(s.tx), __int_as_float(s.ty));
-    o[1] = make_float4(s.t, s.p.x, s.p.y, s.p.z);
-    o[2] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
-    o[3] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
-}
-
-// ---------------------------------------------------------------------------------------------
-// skins on resident scenes (kernels.h: SkinPaintFrame): a repaintable handle's blob takes a new skin from an RGBA8 image in
-// device memory.  One workgroup of 256 threads per scene:
-//   the image (16 or 8 KB) and the host's 256 floats u8 / 255.0f go to LDS, 16 bytes per lane where the image's address allows
-//   1 lane / pool texel (strides of 256)   its skin pixel through the map, four table reads, one 16-byte store into the pool;
-//                                          two ballots per wave — alpha == 0 and alpha > 0, which for a byte is a == 0 and
-//                                          a != 0 — interleaved by lanes 0..3 into the wave's four alpha-predicate words;
-//                                          a texel with alpha 0 sets its mesh's bit in LDS
-//   1 lane / mesh                          the MESH_OPAQUE bit of FlatMesh::flags, an ordinary load and store
-// Every store is a vector store; nothing of the blob but the pool, the predicate words and that bit is written.
-// ---------------------------------------------------------------------------------------------
-constexpr int kSkinBlock = 256;
-__device__ __forceinline__ uint32_t spread16(uint32_t x) {  // bit j of the low 16 bits → bit 2j
-    x = (x | (x << 8)) & 0x00ff00ffu;
-    x = (x | (x << 4)) & 0x0f0f0f0fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    x = (x | (x << 1)) & 0x55555555u;
-    return x;
-}
-__device__ __forceinline__ void skin_paint_body(const SkinPaintFrame& __restrict__ f, const SkinPaintShape& __restrict__ sh) {
-    __shared__ __align__(16) uint32_t s_skin[64 * 64];
-    __shared__ float s_unit[256];
-    __shared__ uint32_t s_clear;  // bit m: a texel of mesh m has alpha 0
-    const int tid = threadIdx.x, lane = tid & 63;
-    const float* __restrict__ unit = static_cast<const float*>(sh.tables);
-    const uint16_t* __restrict__ map = reinterpret_cast<const uint16_t*>(unit + 256);
-    const int n_pixels = sh.skin_bytes >> 2;
-    if ((reinterpret_cast<uintptr_t>(f.skin) & 15u) == 0) {
-        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(f.skin);
-        for (int i = tid; i < (n_pixels >> 2); i += kSkinBlock) reinterpret_cast<uint4*>(s_skin)[i] = src[i];
-    } else {
-        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(f.skin);
-        for (int i = tid; i < n_pixels; i += kSkinBlock) s_skin[i] = src[i];
-    }
-    s_unit[tid] = unit[tid];
-    if (tid == 0) s_clear = 0u;
-    __syncthreads();
-    float4* __restrict__ pool = reinterpret_cast<float4*>(f.scene + sh.texel_offset);
-    uint32_t* __restrict__ abits = reinterpret_cast<uint32_t*>(f.scene + sh.alpha_offset);
-    for (int base = 0; base < sh.n_texels; base += kSkinBlock) {  // (uniform per workgroup: every wave reaches its ballots)
-        const int i = base + tid;
-        const bool valid = i < sh.n_texels;
-        bool zero = false, positive = false;
-        if (valid) {
-            const uint32_t entry = map[i];
-            const uint32_t px = s_skin[entry & 4095u];
-            const uint32_t a = px >> 24;
-            pool[i] = make_float4(s_unit[px & 255u], s_unit[(px >> 8) & 255u], s_unit[(px >> 16) & 255u], s_unit[a]);
-            zero = a == 0u, positive = a != 0u;
-            if (zero) atomicOr(&s_clear, 1u << (entry >> 12));
-        }
-        const unsigned long long z = __ballot(zero), p = __ballot(positive);
-        // the wave's 64 texels are words w0 .. w0 + 3 (a wave starts at a multiple of 64 texels): lane k forms word k
-        const uint32_t word = static_cast<uint32_t>(i - lane) / 16u + static_cast<uint32_t>(lane);
-        if (lane < 4 && word < sh.alpha_words) {
-            const uint32_t zk = static_cast<uint32_t>(z >> (16 * lane)) & 0xffffu, pk = static_cast<uint32_t>(p >> (16 * lane)) & 0xffffu;
-            abits[word] = spread16(zk) | (spread16(pk) << 1);
-        }
-    }
-    __syncthreads();
-    if (tid < sh.n_meshes) {
-        FlatMesh* fm = reinterpret_cast<FlatMesh*>(f.scene + sh.mesh_offset) + tid;
-        const uint32_t flags = fm->flags;
-        fm->flags = ((s_clear >> tid) & 1u) ? (flags & ~MESH_OPAQUE) : (flags | MESH_OPAQUE);
-    }
-}
-__global__ __launch_bounds__(kSkinBlock) void skin_paint_kernel(const SkinPaintFrame f, const SkinPaintShape sh) { skin_paint_body(f, sh); }
-using SkinPaintTable = const __attribute__((address_space(4))) SkinPaintFrame*;
-__global__ __launch_bounds__(kSkinBlock) void skin_paint_batch_kernel(SkinPaintTable table, const SkinPaintShape sh) {
-    skin_paint_body(*(const SkinPaintFrame*)(table + blockIdx.y), sh);
-}
-
-// ---------------------------------------------------------------------------------------------
-// ground shadow (kernels.h: GroundFrame): the figure's soft shadow on the plane y = ground_y, as planes of their own.  Per
-// pixel the layers' pixel-centre ray, its point P on the plane, and computeSoftShadow(P, (0, 1, 0)) (shading.cpp:28-60) with
-// the seed of a hit at depth 0 (raytracer.cpp:110-112) — the figure in front of the plane plays no part.  No workspace.
-//   a workgroup per 256 pixels of a screen tile (grid-stride), in the phases of `lit`, handed over through LDS:
-//   1 lane / mesh (every wave)   which meshes can shadow ANY ground point under the tile (ground_tile_mask): none for most
-//                                tiles of a frame — their reached pixels are fully lit without a classification or a ray
-//   1 lane / pixel               ray, plane hit, P; the whole-bundle decision (rt::bundle_classify) from P + N * 1e-3f: lit by
-//                                all S light samples, by none, or undecided with a candidate mask; the undecided are packed
-//   1 lane / undecided pixel     truncated mt19937 (mt[397] from the seed table) → 2·S draws → S disk sample positions in LDS
-//   1 lane / (undecided pixel, light sample)   exact any-hit test on the candidates → lit count by ballot
-//   1 lane / pixel               visibility = lit / S, distance, matte: coalesced stores, 16 bytes per four pixels of a row
-//                                where the rows allow
-// ---------------------------------------------------------------------------------------------
-constexpr int kGroundPosBytes = 12 * 1024;  // LDS for the sample positions of the undecided pixels of one pass
-constexpr int kGroundFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // candidate and inside masks, P.x / P.z, lit counts, the undecided list
-constexpr int kGroundWaves = 4;  // waves per SIMD the kernels are built for: `lit`'s, whose device functions they inline
-__host__ __device__ __forceinline__ size_t scene_tables_lds_bytes(int face_entries, int alpha_words) {
-    return static_cast<size_t>(face_entries) * 16 + static_cast<size_t>(face_entries / 6) * kMeshTabWords * 4 + static_cast<size_t>(alpha_words) * 4;
-}
-struct GroundPoint {
-    bool reached;
-    float t;  // FLT_MAX where the ray does not reach the plane
-    V3 P;
-};
-// the ray through (fx, fy) pixels of the frame — a pixel centre is (px + 0.5f, py + 0.5f) — against the plane y = g
-__device__ __forceinline__ GroundPoint ground_point(const SceneView& sc, const mcrt_config& cfg, const float aspect, const float g, const float fx,
-                                                    const float fy) {
-    const float u = fx / static_cast<float>(cfg.width);
-    const float v = fy / static_cast<float>(cfg.height);
-    const Ray ray = camera_ray(sc, u, v, aspect);
-    const float t = (g - ray.o.y) / ray.d.y;
-    GroundPoint h;
-    h.reached = ray.d.y != 0.0f && t > 0.0f && t <= kFltMax;
-    h.t = h.reached ? t : kFltMax;
-    h.P = mk(ray.o.x + ray.d.x * t, g, ray.o.z + ray.d.z * t);
-    return h;
-}
-// The meshes that can shadow a ground point under the tile, conservatively: lane m of the calling wave tests mesh m.
-// The tile's pixel-centre rays lie inside its four corner rays; when all four reach the plane (well away from the horizon:
-// |d.y| >= 1e-2) the ground points of the tile lie in the bounding rectangle F of the four corner points — the image of a
-// screen rectangle on a plane in front of the camera is a convex quadrilateral.  A shadow ray leaves Q + (0, 1e-3, 0) for a
-// target T within Rb of the light centre L.  When the lowest target is above the top of a mesh's world box B (bounding
-// sphere when posed) and above the origins, the ray climbs, and it meets B at a point X with gy <= X.y <= B.hi.y only if
-// Q = X + (X - T) * k', 0 <= k' <= k = (L.y - Rb - gy) / (L.y - Rb - B.hi.y) - 1: per axis Q lies in
-// [B.lo - max(0, L + Rb - B.lo) * k, B.hi + max(0, B.hi - L + Rb) * k] — B's shadow from the light centre, widened by the
-// light's radius in the ratio of B's height to the light's clearance.  A mesh whose interval misses F on x or z, with margins
-// far above the float error of the points (2e-3 of the footprint's reach, 1e-4 of the interval, 16 slacks), shadows no
-// pixel of the tile.  Every other case keeps the mesh: a light that is not clear above the box, a corner that misses the
-// plane or grazes it, 64 meshes or more, cull_ok == 0, non-finite values (every comparison is written to fail open).
-__device__ __forceinline__ unsigned long long ground_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect,
-                                                               const float g, const float R, const int lane) {
-    const int n = sc.n_meshes;
-    if (n <= 0) return 0ull;
-    const unsigned long long all = n < 64 ? (1ull << n) - 1ull : ~0ull;
-    if (sc.hdr->cull_ok == 0 || n >= 64) return all;
-    const float slack = sc.hdr->mask_slack;
-    float fx0 = kFltMax, fx1 = -kFltMax, fz0 = kFltMax, fz1 = -kFltMax, reach = 0.0f;
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float fx = static_cast<float>(tg.x + ((c & 1) ? tg.w : 0)), fy = static_cast<float>(tg.y + ((c & 2) ? tg.h : 0));
-        const Ray ray = camera_ray(sc, fx / static_cast<float>(cfg.width), fy / static_cast<float>(cfg.height), aspect);
-        const float t = (g - ray.o.y) / ray.d.y;
-        ok = ok && __builtin_fabsf(ray.d.y) >= 1e-2f && t > 0.0f && t < 1e30f;
-        const float dx = ray.d.x * t, dz = ray.d.z * t;
-        const float x = ray.o.x + dx, z = ray.o.z + dz;
-        fx0 = __builtin_fminf(fx0, x), fx1 = __builtin_fmaxf(fx1, x), fz0 = __builtin_fminf(fz0, z), fz1 = __builtin_fmaxf(fz1, z);
-        reach = __builtin_fmaxf(reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dz)), t));
-        ok = ok && x == x && z == z;  // (fmin / fmax drop a NaN)
-    }
-    ok = ok && reach < 1e30f && slack < 1e30f;
-    if (!ok) return all;
-    const float fm = 2e-3f * reach + 16.0f * slack;
-    const V3 L = ld3(sc.hdr->light_pos);
-    const float Rb = R * 1.001f + slack;
-    const float gy = g + 1e-3f;     // the shadow rays' origins
-    const float low = L.y - Rb;     // the lowest target
-    bool touch = lane < n;
-    if (touch) {
-        const FlatMesh& m = sc.meshes[lane];
-        if (m.flags & MESH_EMPTY) {
-            touch = false;  // intersection.cpp:205: never hit
-        } else {
-            V3 lo = ld3(m.lo), hi = ld3(m.hi);
-            bool bounded = true;
-            if (m.flags & MESH_ROTATED) {
-                const float r = m.sphere[3];
-                bounded = r >= 0.0f;
-                lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
-                hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
-            }
-            const float h = low - gy, c = low - hi.y;  // the light's height above the origins and above the box
-            if (bounded && h > 0.0f && c > 0.01f * h && c > 64.0f * slack) {
-                if (hi.y < gy - 64.0f * slack) {
-                    touch = false;  // the box ends below the origins and every ray climbs
-                } else {
-                    const float k = __builtin_fmaxf(h / c - 1.0f, 0.0f);
-                    const float qx0 = lo.x - __builtin_fmaxf(0.0f, L.x + Rb - lo.x) * k, qx1 = hi.x + __builtin_fmaxf(0.0f, hi.x - L.x + Rb) * k;
-                    const float qz0 = lo.z - __builtin_fmaxf(0.0f, L.z + Rb - lo.z) * k, qz1 = hi.z + __builtin_fmaxf(0.0f, hi.z - L.z + Rb) * k;
-                    const float mg = fm + 1e-4f * (__builtin_fabsf(qx0) + __builtin_fabsf(qx1) + __builtin_fabsf(qz0) + __builtin_fabsf(qz1));
-                    const bool out = (qx1 + mg < fx0) | (qx0 - mg > fx1) | (qz1 + mg < fz0) | (qz0 - mg > fz1);
-                    touch = !out;
-                }
-            }
-        }
-    }
-    return __ballot(touch);
-}
-// one value per pixel into a plane: 16 bytes per four neighbouring pixels of a row where `quads` (lanes 4k .. 4k+3 then hold
-// four neighbours of one row, all valid or none)
-__device__ __forceinline__ void store_plane(float* __restrict__ plane, const bool quads, const bool valid, const int lane, const size_t idx, const float val) {
-    if (quads) {
-        const float v1 = __shfl_down(val, 1), v2 = __shfl_down(val, 2), v3 = __shfl_down(val, 3);
-        if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(plane + idx) = make_float4(val, v1, v2, v3);
-    } else if (valid) {
-        plane[idx] = val;
-    }
-}
-template <int kView>
-__device__ __forceinline__ void ground_body(const GroundFrame& __restrict__ f, const GroundShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks][inside masks][P.x, P.z][lit counts][undecided list][positions: pass x S x 3 floats]
-    __shared__ int s_wcnt[kBlock / 64];
-    const SceneView scg = view_of(f.scene);
-    const mcrt_config& cfg = sh.tiles.cfg;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
-    const float g = f.ground_y;
-    const V3 lpos = ld3(scg.hdr->light_pos);
-    const float lradius = scg.hdr->light_radius;
-    const int S = sh.samples;
-    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
-    const float R = soft ? lradius : 0.0f;
-    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per pixel
-    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
-    const uint32_t pass = static_cast<uint32_t>(sh.pass);
-    const V3 N = mk(0.0f, 1.0f, 0.0f);
-    constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(area);
-    unsigned long long* s_ins = s_cand + kBlock;
-    float2* s_pxz = reinterpret_cast<float2*>(s_ins + kBlock);
-    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_pxz + kBlock);
-    uint32_t* s_und = s_lit + kBlock;
-    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
-    // four neighbouring pixels of a row per store: every tile row starts and ends on a four-pixel boundary of the plane
-    const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
-    const bool quads_vis = quad_rows && (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
-    const bool quads_dist = quad_rows && (reinterpret_cast<uintptr_t>(f.distance) & 15u) == 0;
-    const bool quads_matte = quad_rows && (reinterpret_cast<uintptr_t>(f.matte) & 3u) == 0;
-    typename ViewSel<kView>::type sc;
-    bool staged = false;
-    const int parts = sh.tiles.parts;
-    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * parts;
-    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        const int tile = unit / parts, part = unit - tile * parts;
-        const int tyi = tile / sh.tiles.tiles_x, txi = tile - tyi * sh.tiles.tiles_x;
-        TileGeom tg;
-        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
-        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
-        tg.owned_row = tyi, tg.frame_tile = tile;
-        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
-        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
-        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
-        const unsigned long long mask = ground_tile_mask(scg, cfg, tg, aspect, g, R, lane);  // the same in every wave of the workgroup
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
-        const unsigned pix = p0 + static_cast<unsigned>(tid);
-        const bool valid = pix < npix;
-        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
-        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
-        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
-        GroundPoint gp = ground_point(scg, cfg, aspect, g, static_cast<float>(tg.x + lx) + 0.5f, static_cast<float>(tg.y + ly) + 0.5f);
-        if (!valid) gp.reached = false, gp.t = kFltMax;
-        if (f.distance) store_plane(f.distance, quads_dist, valid, lane, idx, gp.t);
-        uint32_t lit = pairs;  // a pixel that misses the plane, and every pixel of a tile no mesh can shadow
-        bool undecided = false;
-        if (mask != 0ull) {  // uniform
-            // ---- a lane per pixel: the whole-bundle decision
-            if (gp.reached) {
-                const V3 O = gp.P + N * 1e-3f;
-                unsigned long long cand;
-                const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
-                cand &= mask;
-                undecided = known < 0;
-                s_cand[tid] = cand;
-                s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
-                s_pxz[tid] = make_float2(gp.P.x, gp.P.z);
-                if (!undecided) lit = static_cast<uint32_t>(known);
-            }
-            s_lit[tid] = 0u;
-            int total = 0;
-            const int rank = block_rank(undecided, s_wcnt, total);
-            if (undecided) s_und[rank] = static_cast<uint32_t>(tid);
-            const uint32_t n_und = static_cast<uint32_t>(total);
-            if (n_und) __syncthreads();  // uniform
-            for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
-                const uint32_t nu = min(pass, n_und - u0);
-                if (u0) __syncthreads();  // the previous pass's rays have read the positions
-                // ---- a lane per undecided pixel: its mt19937 stream and the S disk sample positions
-                if (soft && static_cast<uint32_t>(tid) < nu) {
-                    const float2 xz = s_pxz[s_und[u0 + tid]];
-                    // (outside the seed table's window — ground points far out, at the horizon — the 397-step recurrence)
-                    disk_sample_positions(scg, f.seed_table, nullptr, mk(xz.x, g, xz.y), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
-                }
-                __syncthreads();
-                // ---- a lane per (undecided pixel, light sample); every lane of a wave runs the same number of turns (ballot inside)
-                const uint32_t n_rays = nu * pairs;
-                for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
-                    const uint32_t q = q0 + static_cast<uint32_t>(lane);
-                    bool visible = false;
-                    uint32_t k = 0;
-                    if (q < n_rays) {
-                        k = s_und[u0 + q / pairs];
-                        const float2 xz = s_pxz[k];
-                        const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
-                        visible = !in_shadow_masked(sc, mk(xz.x, g, xz.y), N, target, s_cand[k], s_ins[k]);
-                    }
-                    if (pow2) {
-                        const unsigned long long bal = __ballot(visible);
-                        if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
-                            const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
-                            s_lit[k] = static_cast<uint32_t>(__popcll(grp));
-                        }
-                    } else if (visible) {
-                        atomicAdd(&s_lit[k], 1u);
-                    }
-                }
-            }
-            // the counts are complete; behind this barrier nothing of the unit is read across lanes any more, so the next
-            // unit may overwrite the area
-            if (n_und) __syncthreads();
-            if (undecided) lit = s_lit[tid];
-        }
-        // ---- a lane per pixel: the planes
-        float vis = static_cast<float>(lit) / static_cast<float>(pairs);
-        MCRT_HOOK_GROUND_PIXEL(vis, gp.reached, mask == 0ull, undecided)
-        if (f.visibility) store_plane(f.visibility, quads_vis, valid, lane, idx, vis);
-        if (f.matte) {
-            const uint32_t a = static_cast<unsigned char>(sclamp(1.0f - vis, 0.0f, 1.0f) * 255.0f + 0.5f);
-            if (quads_matte) {
-                const uint32_t a1 = __shfl_down(a, 1), a2 = __shfl_down(a, 2), a3 = __shfl_down(a, 3);
-                if (valid && (lane & 3) == 0) *reinterpret_cast<uint32_t*>(f.matte + idx) = a | (a1 << 8) | (a2 << 16) | (a3 << 24);
-            } else if (valid) {
-                f.matte[idx] = static_cast<uint8_t>(a);
-            }
-        }
-    }
-}
-template <int kView>
-__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_kernel(const GroundFrame f, const GroundShape sh) {
-    ground_body<kView>(f, sh);
-}
-using GroundTable = const __attribute__((address_space(4))) GroundFrame*;
-template <int kView>
-__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_batch_kernel(GroundTable table, const GroundShape sh) {
-    ground_body<kView>(*(const GroundFrame*)(table + blockIdx.y), sh);
-}
-
-// ---------------------------------------------------------------------------------------------
-// small kernels
-// ---------------------------------------------------------------------------------------------
-template <class Pixel>  // float4, or uchar4 for the RGBA8 plane
-__global__ void unpack_rows_kernel(mcrt_config cfg, Shard sh, const Pixel* packed, Pixel* frame) {
-    // one thread per packed pixel
-    size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    int W = cfg.width, T = cfg.tile_size;
-    size_t prow = i / W;
-    int x = static_cast<int>(i - prow * W);
-    int k = static_cast<int>(prow / T);
-    int ly = static_cast<int>(prow - static_cast<size_t>(k) * T);
-    if (k >= sh.owned_rows) return;
-    int y = (sh.first + k * sh.step) * T + ly;
-    if (y >= cfg.height) return;
-    frame[static_cast<size_t>(y) * W + x] = packed[i];
-}
-
-// every rank's packed rows (rank-major, `rank_stride` float4 apart) → the frame, one thread per output
-// pixel: tile row r belongs to rank r mod world and is that rank's (r div world)-th packed tile row
-__global__ void assemble_frame_kernel(mcrt_config cfg, int world, const float4* __restrict__ gathered, size_t rank_stride,
-                                      float4* __restrict__ frame) {
-    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int W = cfg.width, T = cfg.tile_size;
-    if (i >= static_cast<size_t>(W) * cfg.height) return;
-    const int y = static_cast<int>(i / W);
-    const int x = static_cast<int>(i - static_cast<size_t>(y) * W);
-    const int r = y / T, ly = y - r * T;
-    const int rank = r % world, k = r / world;
-    frame[i] = gathered[static_cast<size_t>(rank) * rank_stride + (static_cast<size_t>(k) * T + ly) * W + x];
-}
-
-// the device's seed table (kernels.h): entry i = mt[397] of std::mt19937(i - kSeedWindowHalf)
-__global__ __launch_bounds__(256) void seed_table_kernel(uint32_t* __restrict__ table) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < kSeedWindow) table[i] = MtShort::word397(i - kSeedWindowHalf);
-}
-
-// the full table: entry s = mt[397] of std::mt19937(s), for the seeds first + (this thread)
-__global__ __launch_bounds__(256) void seed_table_range_kernel(uint32_t* __restrict__ table, uint32_t first) {
-    const uint32_t s = first + blockIdx.x * 256u + threadIdx.x;
-    table[s] = MtShort::word397(s);
-}
-
-__global__ void quantize_kernel(const float4* rgba, uchar4* out, size_t n) {  // image_writer.cpp:18-22
-    size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = quantize_pixel(rgba[i]);
-}
-
-__global__ void probe_intersect_kernel(const uint8_t* scene, const float* rays, int n, mcrt_hit* out) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    SceneView sc = view_of(scene);
-    Ray r{ld3(rays + 6 * i), ld3(rays + 6 * i + 3)};
-    Hit h = hit_scene(sc, r, ~0ull);
-    mcrt_hit o;
-    o.hit = h.hit ? 1 : 0;
-    o.t = h.t;
-    o.point[0] = h.p.x, o.point[1] = h.p.y, o.point[2] = h.p.z;
-    o.normal[0] = h.n.x, o.normal[1] = h.n.y, o.normal[2] = h.n.z;
-    o.texture_color[0] = h.tex.r, o.texture_color[1] = h.tex.g, o.texture_color[2] = h.tex.b,
-    o.texture_color[3] = h.tex.a;
-    o.is_outer_layer = h.outer ? 1 : 0;
-    out[i] = o;
-}
-
-__global__ void probe_trace_kernel(const uint8_t* scene, mcrt_config cfg, const float* rays, int n, int depth,
-                                   float* out, uint32_t* hit_rng, float* deep_stack) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    SceneView sc = view_of(scene);
-    Ray r{ld3(rays + 6 * i), ld3(rays + 6 * i + 3)};
-    C4 local_stack[kMaxStack];
-    C4* stack = deep_stack ? reinterpret_cast<C4*>(deep_stack) + static_cast<size_t>(i) * max(cfg.max_bounces, 1)
-                           : local_stack;
-    uint32_t* rng = hit_rng ? hit_rng + static_cast<size_t>(i) * 624 : nullptr;
-    C4 c;
-    if (depth > cfg.max_bounces) {
-        c = background(sc, cfg, 0.5f, 0.5f);
-    } else {
-        Hit h = hit_scene(sc, r, ~0ull);
-        if (!h.hit) {
-            const float* b = sc.hdr->background;
-            c = (depth == 0) ? background(sc, cfg, 0.5f, 0.5f) : C4{b[0], b[1], b[2], b[3]};
-        } else {
-            c = trace_from_hit(sc, cfg, r, h, depth, stack, rng);
-        }
-    }
-    out[4 * i + 0] = c.r, out[4 * i + 1] = c.g, out[4 * i + 2] = c.b, out[4 * i + 3] = c.a;
-}
-
-__global__ void probe_mt_kernel(const uint32_t* seeds, int n_seeds, int n_draws, float* out, uint32_t* storage) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_seeds) return;
-    HitRng g;
-    g.seed(seeds[i], n_draws, storage ? storage + static_cast<size_t>(i) * 624 : nullptr);
-    for (int k = 0; k < n_draws; ++k) out[static_cast<size_t>(i) * n_draws + k] = g.uniform();
-}
-
-__device__ __forceinline__ float detmath_op(int op, float x, float y) {
-    if (op == 3 || op == 4) {  // the fused form: .s / .c
-        float sn, cs;
-        mcrt_sincosf(x, &sn, &cs);
-        return op == 3 ? sn : cs;
-    }
-    if (op == 5) return rcp_exact(x);  // held against the host's IEEE 1.0f / x
-    return op == 0 ? mcrt_sinf(x) : (op == 1 ? mcrt_cosf(x) : mcrt_powf(x, y));
-}
-__global__ void probe_detmath_kernel(int op, const float* x, const float* y, size_t n, float* out) {
-    size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = detmath_op(op, x[i], y ? y[i] : 0.0f);
-}
-__global__ void probe_detmath_range_kernel(int op, uint32_t lo_bits, uint64_t count, float y0, float* out) {
-    uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    out[i] = detmath_op(op, mcrt_u2f(lo_bits + static_cast<uint32_t>(i)), y0);
-}
-
-// div_frame against the general division for the divisors d_first .. d_first + gridDim.y - 1 and every float x in
-// {0} and [2^-33, d + 1] (by bit pattern).  counts[0] += mismatches, counts[1] = a failing divisor
-// rds: the divisors' reciprocals as the HOST forms them (what the render kernels are given: RenderParams::inv_width / inv_height)
-__global__ void probe_div_const_kernel(uint32_t d_first, int mode, const float* __restrict__ rds, unsigned long long* counts) {
-    const float d = static_cast<float>(d_first + blockIdx.y);
-    const float rd = rds[blockIdx.y];
-    if (mode == 4) {  // the device's own 1.0f / d against the host's reciprocal
-        if (blockIdx.x == 0 && threadIdx.x == 0 && __float_as_uint(1.0f / d) != __float_as_uint(rd)) {
-            atomicAdd(&counts[0], 1ull);
-            counts[1] = d_first + blockIdx.y;
-        }
-        return;
-    }
-    if (mode == 3) {  // rt::sqrt_pos against sqrtf for 0 and every float from 2^-96 to infinity (the divisor plays no part)
-        unsigned long long bad = 0;
-        const uint32_t lo = 0x0f800000u /* 2^-96 */, hi = 0x7f800000u;
-        for (uint64_t b = static_cast<uint64_t>(lo) + static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; b <= hi + 1ull;
-             b += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-            const float x = b > hi ? 0.0f : __uint_as_float(static_cast<uint32_t>(b));
-            if (__float_as_uint(__builtin_sqrtf(x)) != __float_as_uint(sqrt_pos(x))) ++bad;
-        }
-        if (bad) atomicAdd(&counts[0], bad);
-        return;
-    }
-    const uint32_t lo = 0x2f000000u /* 2^-33 */, hi = __float_as_uint(d + 1.0f);
-    unsigned long long bad = 0;
-    for (uint64_t b = static_cast<uint64_t>(lo) + static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; b <= hi + 1ull;
-         b += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const float x = b > hi ? 0.0f : __uint_as_float(static_cast<uint32_t>(b));
-        const float want = x / d;
-        const float got = mode == 2 ? x * rd : (mode ? div_frame2(x, d, rd) : div_frame(x, d, rd));  // mode 1: two corrections; mode 2: none (the probe's own check)
-        if (__float_as_uint(want) != __float_as_uint(got)) ++bad;
-    }
-    if (bad) {
-        atomicAdd(&counts[0], bad);
-        counts[1] = d_first + blockIdx.y;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// host-side launchers
-// ---------------------------------------------------------------------------------------------
-hipError_t launch_probe_div_const(uint32_t d_first, uint32_t d_count, int mode, const float* host_reciprocals, unsigned long long* counts, hipStream_t stream) {
-    if (d_count == 0) return hipSuccess;
-    hipLaunchKernelGGL(probe_div_const_kernel, dim3(mode == 4 ? 1 : 2048, d_count), dim3(256), 0, stream, d_first, mode, host_reciprocals, counts);
-    return hipGetLastError();
-}
-
-Shard make_shard(const mcrt_config& cfg, int first, int step) {
-    Shard s{};
-    s.first = first;
-    s.step = step < 1 ? 1 : step;
-    s.pack_first = 0;
-    s.pack_step = 1;
-    if (cfg.width <= 0 || cfg.height <= 0 || cfg.tile_size <= 0) return s;
-    s.tiles_x = (cfg.width + cfg.tile_size - 1) / cfg.tile_size;
-    s.tiles_y = (cfg.height + cfg.tile_size - 1) / cfg.tile_size;
-    s.owned_rows = (first < s.tiles_y && first >= 0) ? (s.tiles_y - first + s.step - 1) / s.step : 0;
-    return s;
-}
-
-// dynamic LDS of the scene tables a kernel stages (stage_tables): face table, mesh table, alpha predicates
-static size_t scene_table_bytes(const RenderParams& p) {
-    return p.scene_in_lds ? static_cast<size_t>(p.lds_face_entries) * 16 + static_cast<size_t>(p.lds_face_entries / 6) * kMeshTabWords * 4 +
-                                static_cast<size_t>(p.lds_alpha_words) * 4
-                          : 0;
-}
-static int owned_tiles(const RenderParams& p) { return p.shard.owned_rows * p.shard.tiles_x; }
-static bool soft_sampling(const mcrt_config& c) { return c.soft_shadows && c.shadow_samples > 1; }
-
-// The flat pipeline keeps the records of every level at once: its arrays are laid out for up to
-// kFlatMaxBounces reflection levels (1 + maxBounces records per sample slot in the worst case).
-constexpr int kFlatMaxBounces = 8;
-#ifndef MCRT_LIT_LDS_KB
-#define MCRT_LIT_LDS_KB 25
-#endif
-constexpr size_t kLitLdsBytes = MCRT_LIT_LDS_KB * 1024;  // `lit`: LDS for the sample positions of the records whose rays are traced, per pass
-// rare features that need the general kernel variants (one launch set per level, ping-pong queues): per-hit RNG
-// streams longer than the register-only engine covers (they run AO inside `level_shade`, sequentially), or
-// more bounces than the flat record arrays are laid out for
-static bool needs_general_variant(const mcrt_config& c) {
-    return (c.ao_enabled && (c.ao_samples <= 0 || 2 * c.ao_samples > kMtShortMax)) || (soft_sampling(c) && 2 * c.shadow_samples > kMtShortMax) ||
-           c.max_bounces > kFlatMaxBounces;
-}
-
-// Parts of a tile that meshes can touch: one 256-sample chunk each, at most 16 — fine enough that
-// the few tiles holding the character spread over the chip.  Every part reads its samples' draws from
-// the tile's stream in HBM (plan_tiles).  Background tiles are never split.
-static int choose_parts_per_tile(const RenderParams& p) {
-    const mcrt_config& cfg = p.cfg;
-    const long long spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
-    const long long tile_items = p.rect_w > 0 ? static_cast<long long>(p.rect_w) * p.rect_h * spp : static_cast<long long>(cfg.tile_size) * cfg.tile_size * spp;
-    long long parts = (tile_items + kChunk - 1) / kChunk;
-    const long long most = p.rect_w > 0 ? 4096 : 16;  // a renderTile rectangle may be as large as the frame: it is the launch's only tile
-    if (parts > most) parts = most;
-    if (parts < 1) parts = 1;
-    return static_cast<int>(parts);
-}
-
-WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched) {
-    WorkspaceBytes w{};
-    const mcrt_config& c = p.cfg;
-    const int n_tiles = owned_tiles(p);
-    p.parts_per_tile = choose_parts_per_tile(p);
-    p.flat = needs_general_variant(c) ? 0 : 1;
-    p.ws.stack_stride = c.max_bounces > 0 ? c.max_bounces + 1 : 1;
-    const size_t spp = c.samples_per_pixel > 1 ? c.samples_per_pixel : 1;
-    // every tile that meshes can touch owns one slot per sample of a full (frame-clipped) tile
-    const size_t tile_w = p.rect_w > 0 ? static_cast<size_t>(p.rect_w) : static_cast<size_t>(c.tile_size < c.width ? c.tile_size : c.width);
-    const size_t tile_h = p.rect_w > 0 ? static_cast<size_t>(p.rect_h) : static_cast<size_t>(c.tile_size < c.height ? c.tile_size : c.height);
-    const size_t tile_slots = tile_w * tile_h * spp;
-    const size_t S = soft_sampling(c) ? static_cast<size_t>(c.shadow_samples) : 0;
-    const size_t A = c.ao_enabled && c.ao_samples > 0 ? static_cast<size_t>(c.ao_samples) : 0;
-    const size_t rays = S > A ? S : A;  // light samples and AO directions share one array
-    // records per slot: flat — the primary hit and one per reflection level; general — two ping-pong queues
-    const size_t recs = p.flat ? static_cast<size_t>(1 + (c.max_bounces > 0 ? c.max_bounces : 0)) : 2;
-    // bytes per slot: colour + end code, per record 5 float4 + light samples + mask + lit, AO counts, stack
-    // light sample positions and bundle masks in HBM: general variants (per record) and the AO directions of
-    // the primary hits; the flat pipeline's `lit` keeps the light samples in LDS
-    const size_t hbm_rays = p.flat ? 0 : rays;  // the flat pipeline keeps light samples in LDS and AO directions in registers
-    const size_t ray_recs = p.flat ? 1 : recs;
-    const size_t per_entry = 16 + 4 + recs * (5 * 16 + 4) + ray_recs * (12 * hbm_rays + (hbm_rays ? 8 : 0) + 4) + 4 + 16 * static_cast<size_t>(p.ws.stack_stride);
-    // `lit`: a round is a block of up to 256 records (masks, counts and the list of traced records in LDS); the sample
-    // positions of the records whose rays are traced go through an area of kLitLdsBytes, `lit_pass` records at a time
-    {
-        const size_t pairs = S ? S : 1;
-        size_t pass = kLitLdsBytes / (12 * pairs);
-        if (pass > static_cast<size_t>(kBlock)) pass = kBlock;
-        if (pass < 1) pass = 1;
-        p.lit_round = kBlock;
-        p.lit_pass = static_cast<int>(pass);
-        p.lit_lds_bytes = static_cast<int>(pass * 12 * pairs + static_cast<size_t>(kBlock) * 24);  // positions + (candidates, inside, lit count, traced list) per record of a round
-        p.lit_lds_offset = static_cast<int>((scene_table_bytes(p) + 15) & ~static_cast<size_t>(15));
-    }
-    const int owned = p.shard.owned_rows;
-    auto row_count = [&](int j) -> size_t { return row_touched ? static_cast<size_t>(row_touched[j]) : static_cast<size_t>(p.shard.tiles_x); };
-    // touched tiles of the fullest batch when the shard is cut into batches of R owned rows
-    auto fullest = [&](int R) -> size_t {
-        size_t mx = 0;
-        for (int r0 = 0; r0 < owned; r0 += R) {
-            size_t sum = 0;
-            for (int j = r0; j < owned && j < r0 + R; ++j) sum += row_count(j);
-            if (sum > mx) mx = sum;
-        }
-        return mx;
-    };
-    // the tiles' jitter / lens draws: of the touched tiles only when `plan_tiles` renders the background tiles
-    // itself (few draws per pixel: a 624-word twist then completes >= 26 pixels, enough for whole rounds of
-    // the wave's 64 lanes), of every tile of the batch otherwise
-    const size_t draws_stride = tile_slots * static_cast<size_t>(p.draws_per_sample);
-    // A transparent frame takes the touched-tiles layout at every sample count: its background tiles are (0,0,0,0) and need
-    // no stream at all, so only the touched tiles' draws exist (no `background_kernel`, no background work in `primary`).
-    p.bg_in_plan = (p.background == MCRT_BACKGROUND_TRANSPARENT || spp * static_cast<size_t>(p.draws_per_sample) <= 24) ? 1 : 0;
-    static const size_t slab_min_spp = [] {  // development knob (the parity sweeps run the slab kernel at every sample count with it)
-        const char* e = getenv("MCRT_SLAB_MIN_SPP");
-        const int v = e ? atoi(e) : 0;
-        return static_cast<size_t>(v > 0 ? v : kSlabMinSpp);
-    }();
-    p.bg_kernel = (!p.bg_in_plan && spp >= slab_min_spp) ? 1 : 0;
-    const size_t draws_row_bytes = p.bg_in_plan ? 0 : draws_stride * 4 * static_cast<size_t>(p.shard.tiles_x);
-    const size_t draws_tile_bytes = p.bg_in_plan ? draws_stride * 4 : 0;
-    p.ws.draws_stride = static_cast<uint32_t>(draws_stride > 0xffffffffull ? 0xffffffffull : draws_stride);
-    p.ws.tile_slots = static_cast<uint32_t>(tile_slots > 0xffffffffull ? 0xffffffffull : tile_slots);
-    // records are indexed with 32 bits (with room for the 3·S multiplier done in size_t)
-    const size_t index_limit = 0x7ffffff0ull / recs;
-    size_t tile_budget = budget_bytes / (per_entry * (tile_slots ? tile_slots : 1) + draws_tile_bytes);
-    if (tile_slots && tile_budget > index_limit / tile_slots) tile_budget = index_limit / tile_slots;
-    int rows = owned > 0 ? owned : 1;
-    // a batch of R rows fits when its hit workspace and its draws fit the budget together
-    auto fits = [&](int R) -> bool {
-        const size_t f = fullest(R);
-        if (f > tile_budget) return false;
-        return f * (tile_slots * per_entry + draws_tile_bytes) + static_cast<size_t>(R) * draws_row_bytes <= budget_bytes;
-    };
-    if (owned > 0 && !fits(rows)) {  // largest R that fits (monotone in R)
-        int lo = 1, hi = owned;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) / 2;
-            if (fits(mid)) lo = mid; else hi = mid - 1;
-        }
-        rows = lo;  // a batch is never smaller than one tile row
-    }
-    size_t cap_tiles = owned > 0 ? fullest(rows) : 0;
-    if (cap_tiles < 1) cap_tiles = 1;
-    p.rows_per_batch = rows;
-    if (tile_slots == 0 || cap_tiles > index_limit / tile_slots || draws_stride > 0xffff0000ull)
-        p.rows_per_batch = 0;  // one tile (row) alone exceeds the 32-bit index ranges: refused by the caller
-    const size_t cap = p.rows_per_batch ? cap_tiles * tile_slots : 1;
-    // (+ 256 x recs: `lit`'s chase regions start at the level-1 count rounded up to a whole block)
-    const size_t rec_cap = cap * recs + (p.flat ? static_cast<size_t>(kBlock) * recs : 0);
-    p.ws.cap = static_cast<uint32_t>(cap);
-    p.ws.tile_cap = static_cast<uint32_t>(cap_tiles);
-    {  // the tile streams' parts (tile_stream_wave): four waves per tile unless the stream is too short for that
-        static const int parts_knob = [] {  // development knob: MCRT_STREAM_PARTS=1 / 2 / 4
-            const char* e = getenv("MCRT_STREAM_PARTS");
-            const int v = e ? atoi(e) : 0;
-            return (v == 1 || v == 2 || v == 4) ? v : 0;
-        }();
-        const size_t twists = (draws_stride + 623) / 624;  // of a full tile's stream
-        int parts = parts_knob ? parts_knob : kStreamWaves;
-        while (parts > 1 && twists < static_cast<size_t>(2 * parts)) parts >>= 1;  // at least two twists per part
-        p.stream_parts = p.draws_per_sample > 0 ? parts : 1;
-        p.stream_part_twists = static_cast<int>((twists + static_cast<size_t>(p.stream_parts) - 1) / static_cast<size_t>(p.stream_parts));
-        if (p.stream_part_twists < 1) p.stream_part_twists = 1;
-    }
-    w.tile_rng = p.draws_per_sample > 0 ? static_cast<size_t>(n_tiles) * 624 * 4 * static_cast<size_t>(p.stream_parts) : 0;
-    w.tile_draws = static_cast<size_t>(rows) * draws_row_bytes + cap_tiles * draws_tile_bytes;
-    w.scol = cap * 16;
-    w.end = cap * 4;
-    p.ws.unit_cap = static_cast<uint32_t>(cap_tiles * static_cast<size_t>(p.parts_per_tile));
-    w.units = static_cast<size_t>(p.ws.unit_cap) * 16;
-    w.unit_hits = static_cast<size_t>(p.ws.unit_cap) * 4;
-    w.tile_mask = static_cast<size_t>(n_tiles > 0 ? n_tiles : 1) * 8;
-    w.queue_each = rec_cap * 16;
-    w.texel_refs = p.flat ? rec_cap * 4 : 4;
-    w.targets = (p.flat ? cap : rec_cap) * 12 * hbm_rays;
-    w.cand = hbm_rays ? (p.flat ? cap : rec_cap) * 8 : 0;
-    w.lit0 = p.flat ? 4 : cap * 4;  // the flat pipeline keeps the lit counts in LDS
-    w.lit1 = cap * 4;
-    w.stack = cap * 16 * static_cast<size_t>(p.ws.stack_stride);
-    w.counters = (static_cast<size_t>(kCounterWords) * 2 + 4) * 4;  // the counters, their base (the previous pass's last values), frame_info
-    w.hit_rng = p.flat ? 0 : static_cast<size_t>(256) * kBlock * 624 * 4;  // general grids are capped at 256 WGs
-    return w;
-}
-
-static int grid_knob(const char* name, int fallback) {
-    const char* e = getenv(name);
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : fallback;
-}
-
-// Workgroup caps of a render's launches.  Every kernel strides over device-side counts, so a cap changes nothing but
-// the schedule.  A frame alone on the device finishes soonest with many workgroups per kernel (`lit`'s rounds differ in
-// cost: 16 per CU balance better than 8, -7 us); frames that share the device — four handles in flight, or the lanes of
-// one large frame — get through fastest with FEWER workgroups per kernel (4 per CU), which leaves CU slots to the other
-// frames' kernels instead of queueing whole kernels behind each other (+4 % frames/s at 1080p; profiles/r03_experiments/grid_sweep*.txt).
-void choose_grids(RenderParams& p, bool shared_device, bool company) {
-    static const int queue_knob = grid_knob("MCRT_QUEUE_GRID", 0);
-    static const int primary_knob = grid_knob("MCRT_PRIMARY_GRID", 0),
-                     ao_knob = grid_knob("MCRT_AO_GRID", queue_knob), lit_knob = grid_knob("MCRT_LIT_GRID", queue_knob),
-                     resolve_knob = grid_knob("MCRT_RESOLVE_GRID", 0);
-    p.shared_device = shared_device ? 1 : 0;
-    // `plan_tiles`: a tile's stream by as many waves as it has parts when the chain of twists is what the kernel waits for —
-    // long streams (64 spp: 210-420 twists per tile; GUI defaults alone 4.50 -> 4.10 ms, 8K 18.2 -> 16.8), or a frame that has
-    // no company at all, neither other frames nor lanes of its own (1080p: -7 us) — and by ONE wave otherwise: four times the waves bring four times the tile set-up, state
-    // loads and partial rounds and take the slots that other frames' or lanes' kernels would fill (-8 % frames/s at 1080p
-    // with four frames in flight, -7 % for 4K / 4 spp on three lanes; profiles/r03_experiments/stream_waves.txt)
-    static const int waves_knob = grid_knob("MCRT_STREAM_WAVES", 0);  // development knob: 1 / 2 / 4
-    const bool long_streams = p.stream_part_twists * p.stream_parts >= 128;
-    p.stream_waves = (long_streams || !company) ? p.stream_parts : 1;
-    if (waves_knob == 1 || waves_knob == 2 || waves_knob == 4) p.stream_waves = waves_knob < p.stream_parts ? waves_knob : p.stream_parts;
-    if (p.stream_waves < 1) p.stream_waves = 1;
-    p.grid_primary = primary_knob ? primary_knob : (shared_device ? kSharedGrid : kPrimaryGrid);
-    p.grid_ao = ao_knob ? ao_knob : (shared_device ? kSharedGrid : kQueueGrid);
-    p.grid_lit = lit_knob ? lit_knob : (shared_device ? kSharedGrid : kLitGridAlone);
-    p.grid_resolve = resolve_knob ? resolve_knob : (shared_device ? kSharedGrid : kResolveGrid);
-}
-
+// ---- host-side launchers (the planning that sizes them: render_plan.cpp) ----------------------------
 template <int kView>
 static void launch_levels(const RenderParams& p, hipStream_t stream, size_t dyn) {
     const mcrt_config& c = p.cfg;
@@ -2877,16 +1848,12 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
             hipLaunchKernelGGL(background_kernel, dim3(batch_tiles < kQueueGrid ? batch_tiles : kQueueGrid), dim3(kBlock), 0, stream, p.scene, p.ws.tile_draws, out, out8, p, tile_base, batch_tiles);
         const int primary_grid = p.grid_primary > 0 ? p.grid_primary : kPrimaryGrid, resolve_grid = p.grid_resolve > 0 ? p.grid_resolve : kResolveGrid;
         const int pgrid = batch_tiles * p.parts_per_tile < primary_grid ? batch_tiles * p.parts_per_tile : primary_grid;
-        if (p.scene_in_lds && !p.scene_posed) {
-            hipLaunchKernelGGL(primary_kernel<kViewLdsUnposed>, dim3(pgrid), dim3(kBlock), dyn, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
-            launch_levels<kViewLdsUnposed>(p, stream, dyn);
-        } else if (p.scene_in_lds) {
-            hipLaunchKernelGGL(primary_kernel<kViewLds>, dim3(pgrid), dim3(kBlock), dyn, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
-            launch_levels<kViewLds>(p, stream, dyn);
-        } else {
-            hipLaunchKernelGGL(primary_kernel<kViewHbm>, dim3(pgrid), dim3(kBlock), 0, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
-            launch_levels<kViewHbm>(p, stream, 0);
-        }
+        with_view(p.scene_in_lds ? (p.scene_posed ? kViewLds : kViewLdsUnposed) : kViewHbm, [&](auto v) {
+            constexpr int kView = decltype(v)::value;
+            const size_t view_dyn = kView == kViewHbm ? 0 : dyn;
+            hipLaunchKernelGGL(primary_kernel<kView>, dim3(pgrid), dim3(kBlock), view_dyn, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
+            launch_levels<kView>(p, stream, view_dyn);
+        });
         const int rgrid = batch_tiles * p.parts_per_tile < resolve_grid ? batch_tiles * p.parts_per_tile : resolve_grid;
         if (p.background == MCRT_BACKGROUND_TRANSPARENT)
             hipLaunchKernelGGL(resolve_transparent_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, out, out8, p, tile_base);
@@ -2901,137 +1868,29 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
     return hipGetLastError();
 }
 
-// ---- background plate (kernels.h) ---------------------------------------------------------------
-bool bg_plate_eligible(const RenderParams& p) {
-    return p.background == MCRT_BACKGROUND_REFERENCE && p.cfg.gradient_bg != 0 && p.cfg.samples_per_pixel > 1 && p.bg_in_plan == 1 && p.rect_w <= 0 &&
-           p.draws_per_sample > 0;
-}
-size_t bg_plate_bytes(const mcrt_config& cfg) {
-    if (cfg.width <= 0 || cfg.height <= 0 || cfg.tile_size <= 0) return 0;
-    const size_t ts = static_cast<size_t>(cfg.tile_size);
-    const size_t tiles = ((static_cast<size_t>(cfg.width) + ts - 1) / ts) * ((static_cast<size_t>(cfg.height) + ts - 1) / ts);
-    if (ts > 0xffffull || tiles > 0x7fffffffull / (ts * ts)) return 0;
-    return tiles * ts * ts * sizeof(float4);
-}
-static RenderParams bg_plate_fill_params(const RenderParams& p) {
-    RenderParams q = p;
-    q.shard = make_shard(p.cfg, 0, 1);
-    q.layout = MCRT_LAYOUT_FRAME;
-    q.out = nullptr;
-    q.out8 = nullptr;
-    q.bg_plate = nullptr;
-    q.rect_x = q.rect_y = q.rect_w = q.rect_h = 0;
-    return q;
-}
-size_t bg_plate_rng_bytes(const RenderParams& p) {
-    const RenderParams q = bg_plate_fill_params(p);
-    return static_cast<size_t>(owned_tiles(q)) * 624 * 4 * static_cast<size_t>(q.stream_parts);
-}
-hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream) {
-    if (!bg_plate_eligible(p) || !plate || !tile_rng || bg_plate_bytes(p.cfg) == 0) return hipErrorInvalidValue;
-    RenderParams q = bg_plate_fill_params(p);
+// ---- background and draw plates (kernels.h): q's tile streams seeded in the scratch `tile_rng`, then `kernel` over every tile
+template <class Kernel, class Plate>
+static hipError_t launch_fill_plate(RenderParams q, Kernel kernel, Plate* plate, uint32_t* tile_rng, hipStream_t stream) {
     q.tile_rng = tile_rng;
     const int n = owned_tiles(q);
     if (n <= 0) return hipErrorInvalidValue;
     hipError_t e = launch_seed_tiles(q, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fill_bg_plate_kernel, dim3((n * q.stream_parts + kStreamWaves - 1) / kStreamWaves), dim3(64 * kStreamWaves), 0, stream, q, plate, n);
+    hipLaunchKernelGGL(kernel, dim3((n * q.stream_parts + kStreamWaves - 1) / kStreamWaves), dim3(64 * kStreamWaves), 0, stream, q, plate, n);
     return hipGetLastError();
 }
-
-// ---- draw plate (kernels.h) -----------------------------------------------------------------------
-bool draw_plate_eligible(const RenderParams& p) {
-    const int spp = p.cfg.samples_per_pixel > 1 ? p.cfg.samples_per_pixel : 1;
-    return p.bg_in_plan == 1 && p.draws_per_sample > 0 && p.rect_w <= 0 && spp * p.draws_per_sample <= 24 && p.ws.draws_stride > 0;
+hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream) {
+    if (!bg_plate_eligible(p) || !plate || !tile_rng || bg_plate_bytes(p.cfg) == 0) return hipErrorInvalidValue;
+    return launch_fill_plate(bg_plate_fill_params(p), fill_bg_plate_kernel, plate, tile_rng, stream);
 }
-size_t draw_plate_bytes(const RenderParams& p) {
-    const mcrt_config& cfg = p.cfg;
-    if (cfg.width <= 0 || cfg.height <= 0 || cfg.tile_size <= 0 || p.ws.draws_stride == 0) return 0;
-    const size_t ts = static_cast<size_t>(cfg.tile_size);
-    const size_t tiles = ((static_cast<size_t>(cfg.width) + ts - 1) / ts) * ((static_cast<size_t>(cfg.height) + ts - 1) / ts);
-    if (tiles > 0x7fffffffull) return 0;  // (TileGeom::frame_tile is an int)
-    return tiles * static_cast<size_t>(p.ws.draws_stride) * sizeof(float);
-}
-size_t draw_plate_rng_bytes(const RenderParams& p) { return bg_plate_rng_bytes(p); }  // the same whole-frame shard's engine states
 hipError_t launch_fill_draw_plate(const RenderParams& p, float* plate, uint32_t* tile_rng, hipStream_t stream) {
     if (!draw_plate_eligible(p) || !plate || !tile_rng || draw_plate_bytes(p) == 0) return hipErrorInvalidValue;
     RenderParams q = bg_plate_fill_params(p);
     q.draw_plate = nullptr;
-    q.tile_rng = tile_rng;
-    const int n = owned_tiles(q);
-    if (n <= 0) return hipErrorInvalidValue;
-    hipError_t e = launch_seed_tiles(q, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fill_draw_plate_kernel, dim3((n * q.stream_parts + kStreamWaves - 1) / kStreamWaves), dim3(64 * kStreamWaves), 0, stream, q, plate, n);
-    return hipGetLastError();
+    return launch_fill_plate(q, fill_draw_plate_kernel, plate, tile_rng, stream);
 }
 
 // ---- batches ----------------------------------------------------------------------------------
-bool batch_eligible(const RenderParams& p) {
-    return p.flat && p.rect_w <= 0 && p.shard.owned_rows > 0 && p.rows_per_batch >= p.shard.owned_rows;
-}
-
-// Workgroups per frame of a batched launch.  Every kernel strides over its frame's device-side work, so the grid only
-// shapes the schedule: a batch aims at kBatchTarget workgroups per launch (8 per CU of the 256 — twice what the largest
-// stage keeps resident, enough to balance frames of unequal cost) spread evenly over its frames, never fewer than
-// kBatchMinGrid per frame (a frame's share of the work never waits on a handful of workgroups) and never more than the
-// frame would get on its own (choose_grids).  From 256 frames on the floor alone fills the target: kBatchMaxFrames.
-constexpr int kBatchTarget = 2048;
-constexpr int kBatchMinGrid = 8;
-static int batch_grid(int single, int n_frames) {
-    if (n_frames <= 1) return single;
-    int g = (kBatchTarget + n_frames - 1) / n_frames;
-    if (g < kBatchMinGrid) g = kBatchMinGrid;
-    return g < single ? g : single;
-}
-
-hipError_t plan_batch(RenderParams* f, int n, bool others_running, BatchPlan& plan) {
-    plan = BatchPlan{};
-    if (n < 1) return hipErrorInvalidValue;
-    const RenderParams& a = f[0];
-    bool any_hbm = false, any_posed = false;
-    for (int i = 0; i < n; ++i) {
-        const RenderParams& q = f[i];
-        // the launch shapes are functions of the config: frames that disagree cannot share a launch
-        if (!batch_eligible(q) || std::memcmp(&q.cfg, &a.cfg, sizeof(mcrt_config)) != 0 || std::memcmp(&q.shard, &a.shard, sizeof(Shard)) != 0 ||
-            q.parts_per_tile != a.parts_per_tile || q.stream_parts != a.stream_parts || q.stream_part_twists != a.stream_part_twists ||
-            q.draws_per_sample != a.draws_per_sample || q.bg_in_plan != a.bg_in_plan || q.bg_kernel != a.bg_kernel || q.lit_lds_bytes != a.lit_lds_bytes ||
-            q.background != a.background)
-            return hipErrorInvalidValue;
-        any_hbm = any_hbm || !q.scene_in_lds;
-        any_posed = any_posed || q.scene_posed;
-    }
-    // one variant for the whole batch, the most general any frame needs: kViewHbm > kViewLds > kViewLdsUnposed.  The
-    // kernels decide the record layout from p.scene_posed, not from the variant, so a frame under a more general variant
-    // renders exactly as alone; under kViewHbm its tables are read from HBM and lit's area starts at offset 0.
-    plan.view = any_hbm ? kViewHbm : (any_posed ? kViewLds : kViewLdsUnposed);
-    for (int i = 0; i < n; ++i) {
-        RenderParams& q = f[i];
-        if (any_hbm) {
-            q.scene_in_lds = 0, q.lds_alpha_words = 0, q.lds_face_entries = 0;
-            q.lit_lds_offset = 0;
-        }
-        const size_t tables = scene_table_bytes(q);
-        if (static_cast<size_t>(q.lit_lds_offset) != ((tables + 15) & ~static_cast<size_t>(15))) return hipErrorInvalidValue;
-        plan.dyn = tables > plan.dyn ? tables : plan.dyn;
-        const size_t lit = static_cast<size_t>(q.lit_lds_offset) + static_cast<size_t>(q.lit_lds_bytes);
-        plan.lit_dyn = lit > plan.lit_dyn ? lit : plan.lit_dyn;
-    }
-    // grids: what a frame would get with company (the other frames of the batch), then the batch rule above
-    const int spp = a.cfg.samples_per_pixel > 1 ? a.cfg.samples_per_pixel : 1;
-    const double samples = static_cast<double>(a.shard.owned_rows) * a.cfg.tile_size * a.cfg.width * spp;
-    const bool company = n > 1 || others_running;
-    for (int i = 0; i < n; ++i) {
-        RenderParams& q = f[i];
-        choose_grids(q, company && samples < 6.4e7, company);
-        q.grid_primary = batch_grid(q.grid_primary, n);
-        q.grid_ao = batch_grid(q.grid_ao, n);
-        q.grid_lit = batch_grid(q.grid_lit, n);
-        q.grid_resolve = batch_grid(q.grid_resolve, n);
-    }
-    return hipSuccess;
-}
-
 hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d_table, int n_frames, hipStream_t stream) {
     const int n = owned_tiles(p0);
     if (n <= 0 || n_frames <= 0 || p0.draws_per_sample <= 0 || !p0.tile_rng) return hipSuccess;
@@ -3060,228 +1919,12 @@ hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& b, const
     const int waves = p0.stream_waves > 0 ? p0.stream_waves : 1;
     hipLaunchKernelGGL(plan_tiles_batch_kernel, dim3((n * waves + kStreamWaves - 1) / kStreamWaves, F), dim3(64 * kStreamWaves), 0, stream, ParamTable(d_table), n);
     if (p0.bg_kernel) hipLaunchKernelGGL(background_batch_kernel, dim3(n < kQueueGrid ? n : kQueueGrid, F), dim3(kBlock), 0, stream, ParamTable(d_table), n);
-    if (b.view == kViewLdsUnposed)
-        launch_batch_stages<kViewLdsUnposed>(p0, b, d_table, F, n, stream);
-    else if (b.view == kViewLds)
-        launch_batch_stages<kViewLds>(p0, b, d_table, F, n, stream);
-    else
-        launch_batch_stages<kViewHbm>(p0, b, d_table, F, n, stream);
+    with_view(b.view, [&](auto v) { launch_batch_stages<decltype(v)::value>(p0, b, d_table, F, n, stream); });
     const int rgrid = n * p0.parts_per_tile < p0.grid_resolve ? n * p0.parts_per_tile : p0.grid_resolve;
     if (p0.background == MCRT_BACKGROUND_TRANSPARENT)
         hipLaunchKernelGGL(resolve_transparent_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
     else
         hipLaunchKernelGGL(resolve_batch_kernel, dim3(rgrid, F), dim3(kBlock), 0, stream, ParamTable(d_table));
-    return hipGetLastError();
-}
-
-// ---- geometry layers (kernels.h) ------------------------------------------------------------------
-int layers_view(LayersFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
-    const bool fits = alpha_words <= static_cast<uint32_t>(kAlphaLdsWordsMax) && n_meshes * 6 <= static_cast<uint32_t>(kFaceLdsEntriesMax);
-    f.lds_alpha_words = fits ? static_cast<int>(alpha_words) : 0;
-    f.lds_face_entries = fits ? static_cast<int>(n_meshes * 6) : 0;
-    return !fits ? kViewHbm : (posed ? kViewLds : kViewLdsUnposed);
-}
-template <class Frame>  // LayersFrame or GroundFrame
-static int batch_view_of(Frame* frames, const int* views, int n) {
-    bool any_hbm = false, any_posed = false;
-    for (int i = 0; i < n; ++i) {
-        any_hbm = any_hbm || views[i] == kViewHbm;
-        any_posed = any_posed || views[i] == kViewLds;
-    }
-    if (any_hbm)
-        for (int i = 0; i < n; ++i) frames[i].lds_alpha_words = 0, frames[i].lds_face_entries = 0;
-    return any_hbm ? kViewHbm : (any_posed ? kViewLds : kViewLdsUnposed);
-}
-int layers_batch_view(LayersFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
-size_t layers_lds_bytes(const LayersFrame& f) {
-    return static_cast<size_t>(f.lds_face_entries) * 16 + static_cast<size_t>(f.lds_face_entries / 6) * kMeshTabWords * 4 + static_cast<size_t>(f.lds_alpha_words) * 4;
-}
-constexpr int kLayersGrid = 8192;  // workgroups per frame at most (the kernel strides over its units)
-bool make_layers_shape(const mcrt_config& cfg, LayersShape& shape) {
-    std::memset(&shape, 0, sizeof shape);
-    shape.cfg = cfg;
-    if (cfg.width <= 0 || cfg.height <= 0 || cfg.tile_size <= 0) return true;  // no tiles
-    shape.tiles_x = (cfg.width + cfg.tile_size - 1) / cfg.tile_size;
-    shape.tiles_y = (cfg.height + cfg.tile_size - 1) / cfg.tile_size;
-    const long long tile_px = static_cast<long long>(cfg.tile_size < cfg.width ? cfg.tile_size : cfg.width) * (cfg.tile_size < cfg.height ? cfg.tile_size : cfg.height);
-    const long long parts = (tile_px + kBlock - 1) / kBlock;
-    if (static_cast<long long>(shape.tiles_x) * shape.tiles_y * parts > 0x7fffffffll) return false;
-    shape.parts = static_cast<int>(parts);
-    return true;
-}
-static long long layers_units(const LayersShape& shape) { return static_cast<long long>(shape.tiles_x) * shape.tiles_y * shape.parts; }
-hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream) {
-    const long long n_units = layers_units(shape);
-    if (n_units <= 0) return hipSuccess;
-    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid));
-    const size_t dyn = layers_lds_bytes(f);
-    if (view == kViewLdsUnposed)
-        hipLaunchKernelGGL(layers_kernel<kViewLdsUnposed>, grid, dim3(kBlock), dyn, stream, f, shape);
-    else if (view == kViewLds)
-        hipLaunchKernelGGL(layers_kernel<kViewLds>, grid, dim3(kBlock), dyn, stream, f, shape);
-    else
-        hipLaunchKernelGGL(layers_kernel<kViewHbm>, grid, dim3(kBlock), 0, stream, f, shape);
-    return hipGetLastError();
-}
-hipError_t launch_layers_batch(const LayersFrame* d_table, int n_frames, const LayersShape& shape, int view, size_t max_dyn, hipStream_t stream) {
-    const long long n_units = layers_units(shape);
-    if (n_units <= 0 || n_frames <= 0) return hipSuccess;
-    if (n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
-    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid), static_cast<unsigned>(n_frames));
-    LayersTable table = LayersTable(d_table);
-    if (view == kViewLdsUnposed)
-        hipLaunchKernelGGL(layers_batch_kernel<kViewLdsUnposed>, grid, dim3(kBlock), max_dyn, stream, table, shape);
-    else if (view == kViewLds)
-        hipLaunchKernelGGL(layers_batch_kernel<kViewLds>, grid, dim3(kBlock), max_dyn, stream, table, shape);
-    else
-        hipLaunchKernelGGL(layers_batch_kernel<kViewHbm>, grid, dim3(kBlock), 0, stream, table, shape);
-    return hipGetLastError();
-}
-// ---- ground shadow (kernels.h) --------------------------------------------------------------------
-bool make_ground_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, GroundShape& shape) {
-    std::memset(&shape, 0, sizeof shape);
-    if (!make_layers_shape(cfg, shape.tiles)) return false;
-    shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
-    const int fit = kGroundPosBytes / (12 * shape.samples);  // 113 samples: 9 pixels per pass
-    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
-    shape.bundle_decisions = bundle_decisions ? 1 : 0;
-    shape.inside_fast = inside_fast ? 1 : 0;
-    return true;
-}
-int ground_view(GroundFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
-    LayersFrame l{};
-    const int view = layers_view(l, alpha_words, n_meshes, posed);
-    f.lds_alpha_words = l.lds_alpha_words, f.lds_face_entries = l.lds_face_entries;
-    return view;
-}
-int ground_batch_view(GroundFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
-size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
-    return tables + kGroundFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
-}
-hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int view, hipStream_t stream) {
-    const long long n_units = layers_units(shape.tiles);
-    if (n_units <= 0) return hipSuccess;
-    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid));
-    const size_t dyn = ground_lds_bytes(f, shape);
-    if (view == kViewLdsUnposed)
-        hipLaunchKernelGGL(ground_kernel<kViewLdsUnposed>, grid, dim3(kBlock), dyn, stream, f, shape);
-    else if (view == kViewLds)
-        hipLaunchKernelGGL(ground_kernel<kViewLds>, grid, dim3(kBlock), dyn, stream, f, shape);
-    else
-        hipLaunchKernelGGL(ground_kernel<kViewHbm>, grid, dim3(kBlock), dyn, stream, f, shape);
-    return hipGetLastError();
-}
-hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream) {
-    const long long n_units = layers_units(shape.tiles);
-    if (n_units <= 0 || n_frames <= 0) return hipSuccess;
-    if (n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
-    const dim3 grid(static_cast<unsigned>(n_units < kLayersGrid ? n_units : kLayersGrid), static_cast<unsigned>(n_frames));
-    GroundTable table = GroundTable(d_table);
-    if (view == kViewLdsUnposed)
-        hipLaunchKernelGGL(ground_batch_kernel<kViewLdsUnposed>, grid, dim3(kBlock), max_dyn, stream, table, shape);
-    else if (view == kViewLds)
-        hipLaunchKernelGGL(ground_batch_kernel<kViewLds>, grid, dim3(kBlock), max_dyn, stream, table, shape);
-    else
-        hipLaunchKernelGGL(ground_batch_kernel<kViewHbm>, grid, dim3(kBlock), max_dyn, stream, table, shape);
-    return hipGetLastError();
-}
-hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pick_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, scene, shape, d_xy, n, d_out);
-    return hipGetLastError();
-}
-// ---- skins on resident scenes (kernels.h) -----------------------------------------------------------
-size_t skin_tables_bytes(int n_texels) { return 256 * sizeof(float) + static_cast<size_t>(n_texels) * sizeof(uint16_t); }
-static bool skin_shape_ok(const SkinPaintShape& sh) {  // what the kernel's fixed LDS image and its 4-bit mesh field hold
-    return sh.tables && sh.n_texels > 0 && sh.n_texels <= kSkinMaxTexels && sh.n_meshes > 0 && sh.n_meshes <= kSkinMaxMeshes &&
-           (sh.skin_bytes == 64 * 64 * 4 || sh.skin_bytes == 64 * 32 * 4) && sh.alpha_words == static_cast<uint32_t>((sh.n_texels + 15) / 16);
-}
-hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream) {
-    if (!skin_shape_ok(shape) || !f.scene || !f.skin) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(skin_paint_kernel, dim3(1), dim3(kSkinBlock), 0, stream, f, shape);
-    return hipGetLastError();
-}
-hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream) {
-    if (n_frames <= 0) return hipSuccess;
-    if (!skin_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(skin_paint_batch_kernel, dim3(1, static_cast<unsigned>(n_frames)), dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shape);
-    return hipGetLastError();
-}
-
-hipError_t launch_unpack_rows(const mcrt_config& cfg, const Shard& sh, const float* packed, float* frame,
-                              hipStream_t stream) {
-    size_t n = static_cast<size_t>(sh.owned_rows) * cfg.tile_size * cfg.width;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(unpack_rows_kernel<float4>, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, cfg, sh,
-                       reinterpret_cast<const float4*>(packed), reinterpret_cast<float4*>(frame));
-    return hipGetLastError();
-}
-hipError_t launch_unpack_rows8(const mcrt_config& cfg, const Shard& sh, const uint8_t* packed, uint8_t* frame, hipStream_t stream) {
-    size_t n = static_cast<size_t>(sh.owned_rows) * cfg.tile_size * cfg.width;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(unpack_rows_kernel<uchar4>, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, cfg, sh,
-                       reinterpret_cast<const uchar4*>(packed), reinterpret_cast<uchar4*>(frame));
-    return hipGetLastError();
-}
-
-hipError_t launch_assemble_frame(const mcrt_config& cfg, int world, const float* gathered, size_t rank_stride_pixels,
-                                 float* frame, hipStream_t stream) {
-    const size_t n = static_cast<size_t>(cfg.width) * cfg.height;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(assemble_frame_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, cfg, world,
-                       reinterpret_cast<const float4*>(gathered), rank_stride_pixels, reinterpret_cast<float4*>(frame));
-    return hipGetLastError();
-}
-
-hipError_t launch_quantize(const float* rgba, uint8_t* out, size_t n_pixels, hipStream_t stream) {
-    if (n_pixels == 0) return hipSuccess;
-    hipLaunchKernelGGL(quantize_kernel, dim3(static_cast<unsigned>((n_pixels + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const float4*>(rgba), reinterpret_cast<uchar4*>(out), n_pixels);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_seed_table(uint32_t* table, hipStream_t stream) {
-    hipLaunchKernelGGL(seed_table_kernel, dim3(kSeedWindow / 256u), dim3(256), 0, stream, table);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_seed_table_range(uint32_t* table, uint32_t first, uint32_t count, hipStream_t stream) {
-    if (count == 0u || (count & 255u)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(seed_table_range_kernel, dim3(count / 256u), dim3(256), 0, stream, table, first);
-    return hipGetLastError();
-}
-
-hipError_t launch_probe_intersect(const uint8_t* scene, const float* rays, int n, mcrt_hit* out, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(probe_intersect_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, scene, rays, n, out);
-    return hipGetLastError();
-}
-hipError_t launch_probe_trace(const uint8_t* scene, const mcrt_config& cfg, const float* rays, int n, int depth,
-                              float* out, uint32_t* hit_rng, float* deep_stack, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(probe_trace_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, scene, cfg, rays, n, depth, out,
-                       hit_rng, deep_stack);
-    return hipGetLastError();
-}
-hipError_t launch_probe_mt(const uint32_t* seeds, int n_seeds, int n_draws, float* out, uint32_t* storage,
-                           hipStream_t stream) {
-    if (n_seeds <= 0) return hipSuccess;
-    hipLaunchKernelGGL(probe_mt_kernel, dim3((n_seeds + 63) / 64), dim3(64), 0, stream, seeds, n_seeds, n_draws, out,
-                       storage);
-    return hipGetLastError();
-}
-hipError_t launch_probe_detmath(int op, const float* x, const float* y, size_t n, float* out, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(probe_detmath_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, op, x,
-                       y, n, out);
-    return hipGetLastError();
-}
-hipError_t launch_probe_detmath_range(int op, uint32_t lo_bits, uint64_t count, float y0, float* out,
-                                      hipStream_t stream) {
-    if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(probe_detmath_range_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0,
-                       stream, op, lo_bits, count, y0, out);
     return hipGetLastError();
 }
 

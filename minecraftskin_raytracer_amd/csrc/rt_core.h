@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "flat_scene.h"
+#include "launch_shapes.h"  // kMeshTabWords, kMtShortMax
 #include "mcrt.h"
 #include "mcrt_detmath.h"
 
@@ -168,7 +169,6 @@ struct SceneViewLdsT {
     DEV SceneView global() const { return SceneView{hdr, meshes, texels, abits_hbm, roots, n_meshes}; }
 };
 using SceneViewLds = SceneViewLdsT<true>;
-constexpr int kMeshTabWords = 24;
 DEV SceneView view_of(const uint8_t* blob) {
     SceneView s;
     s.hdr = reinterpret_cast<const FlatHeader*>(blob);
@@ -222,8 +222,6 @@ DEV float mt_to_unit(uint32_t x) {
     const float r = static_cast<float>(x) * 0x1p-32f;  // in [0, 1]
     return __builtin_fminf(r, 0x1.fffffep-1f);         // (r >= 1) ? nextafter(1, 0) : r
 }
-
-constexpr int kMtShortMax = 227;  // draws available from the two-recurrence form
 
 struct MtShort {
     uint32_t lo, hi;  // mt[i], mt[i+397]

@@ -261,6 +261,31 @@ def test_batch_of_five_scenes_at_five_heights_keeps_the_gaps(mcrt, gpu, oracle):
 
 
 @gpu_test
+def test_batch_of_unposed_posed_and_hbm_scenes(mcrt, gpu):
+    # as the layers' test of this name: an un-posed and a posed figure and seventy boxes in one launch (the HBM variant for
+    # all three), every frame at a height of its own, 8 shadow samples; each frame must be what its own call gives
+    cfg = abi.Config(width=70, height=45, tileSize=32)
+    assert cfg.softShadows and cfg.shadowSamples == 8
+    sds = [L.skin_case("S64", 0), L.skin_case("S64", 6, (135.0, 20.0, 34.0)), mcrt.SceneDesc(L.box_scene("seventy_boxes")[0])]
+    heights = [0.0, 0.5, mcrt.scene_floor(sds[2])]
+    assert len(set(heights)) == 3
+    handles = [mcrt.DeviceScene(sd) for sd in sds]
+    try:
+        buf = _buffers(3, cfg.width * cfg.height)
+        mcrt.render_ground_batch_device(handles, cfg, heights, stream=torch.cuda.current_stream().cuda_stream, **_ptrs(buf, PLANES))
+        torch.cuda.synchronize()
+        batch = _frames(buf, cfg, PLANES)
+        for i, h in enumerate(handles):
+            single = _device_ground(h, cfg, heights[i])[1]
+            assert (single["visibility"] < 1.0).sum() >= 20, f"frame {i} holds too little shadow"
+            G.assert_ground_equal({k: v[i] for k, v in batch.items()}, single, f"mixed batch frame {i}")
+            h.check()
+    finally:
+        for h in handles:
+            h.close()
+
+
+@gpu_test
 def test_batch_beyond_the_frames_of_one_launch(mcrt, gpu, oracle):
     n = 4096 + 1  # one launch takes 4096 frames (blockIdx.y)
     cfg = abi.Config(width=8, height=8, tileSize=8)

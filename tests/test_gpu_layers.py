@@ -178,6 +178,28 @@ def test_batch_equals_single_calls_and_keeps_the_gaps(mcrt, gpu):
 
 
 @gpu_test
+def test_batch_of_unposed_posed_and_hbm_scenes(mcrt, gpu):
+    # one launch for three kernel variants' worth of scenes: an un-posed figure and a posed one (tables in LDS) and seventy
+    # boxes (tables read from HBM), so the whole batch runs the HBM variant; each frame must be what its own call gives
+    cfg = abi.Config(width=70, height=45, tileSize=32)
+    sds = [L.skin_case("S64", 0), L.skin_case("S64", 6, (135.0, 20.0, 34.0)), mcrt.SceneDesc(L.box_scene("seventy_boxes")[0])]
+    handles = [mcrt.DeviceScene(sd) for sd in sds]
+    try:
+        buf = _buffers(3, cfg.width * cfg.height)
+        mcrt.render_layers_batch_device(handles, cfg, stream=torch.cuda.current_stream().cuda_stream, **_ptrs(buf, PLANES))
+        torch.cuda.synchronize()
+        batch = _frames(buf, cfg, PLANES)
+        for i, h in enumerate(handles):
+            single = _device_layers(h, cfg)[1]
+            assert (single["id"][..., 0] >= 0).sum() >= 100, f"frame {i} shows too little of its scene"
+            L.assert_layers_equal({k: v[i] for k, v in batch.items()}, single, f"mixed batch frame {i}")
+            h.check()
+    finally:
+        for h in handles:
+            h.close()
+
+
+@gpu_test
 def test_batch_beyond_the_frames_of_one_launch(mcrt, gpu):
     # one launch takes 4096 frames (blockIdx.y); a handle may be listed any number of times
     n = 4096 + 5

@@ -4,11 +4,10 @@
 # decision the traced rays contradict is printed and counted.  The product library contains none of this.  usage: tools/decide_check.sh build   (here, no GPU needed)
 #                                            tools/decide_check.sh run [first_seed count]   (on the GPU box)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-C=$R/minecraftskin_raytracer_amd/csrc
 if [ "$1" = build ]; then
   mkdir -p $R/variants
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -I$R/include -I$C -I$R/tools '-DMCRT_KERNEL_HOOKS="decide_check_hooks.h"' \
-    $C/render_kernels.hip $C/api.cpp $C/render_enqueue.cpp $C/device_stores.cpp $C/probes.cpp $C/flatten.cpp $C/scene_builder.cpp $C/png_writer.cpp -o $R/variants/decide_check.so -lpthread
+  cd $R && python3 -c "from minecraftskin_raytracer_amd.build import build
+build(force=True, out='$R/variants/decide_check.so', extra_flags=['-I$R/tools', '-DMCRT_KERNEL_HOOKS=\"decide_check_hooks.h\"'])"
   exit $?
 fi
 first=${2:-900000}; count=${3:-2000}

@@ -34,15 +34,14 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ("1080p_pose0", "1080p_pose6", "4k_pose0", "4k_pose6", "batch64", "variants_pose0", "variants_pose6")
 VARIANT = os.path.join(ROOT, "variants", "ground_class.so")
-SOURCES = ["render_kernels.hip", "api.cpp", "render_enqueue.cpp", "device_stores.cpp", "probes.cpp", "flatten.cpp", "scene_builder.cpp", "png_writer.cpp"]
 
 
 def build_variant():
-    csrc = os.path.join(ROOT, "minecraftskin_raytracer_amd", "csrc")
+    sys.path.insert(0, ROOT)
+    from minecraftskin_raytracer_amd.build import build
+
     os.makedirs(os.path.dirname(VARIANT), exist_ok=True)
-    hipcc = os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", f"-I{ROOT}/include", f"-I{csrc}",
-                           f"-I{ROOT}/tools", '-DMCRT_KERNEL_HOOKS="ground_class_hooks.h"'] + [os.path.join(csrc, f) for f in SOURCES] + ["-o", VARIANT, "-lpthread"])
+    build(force=True, out=VARIANT, extra_flags=[f"-I{ROOT}/tools", '-DMCRT_KERNEL_HOOKS="ground_class_hooks.h"'])
     print(VARIANT)
 
 

@@ -1,4 +1,4 @@
-// ground_class_hooks.h — measurement hook for csrc/render_kernels.hip (NOT part of the product build).
+// ground_class_hooks.h — measurement hook for csrc/pass_kernels.hip (NOT part of the product build).
 // tools/gpu_ground.py builds a variant of the library with
 //     -DMCRT_KERNEL_HOOKS='"ground_class_hooks.h"' -Itools
 // in which the ground pass writes, instead of the visibility, how each pixel got it: 0 the ray misses the plane, 1 reached
