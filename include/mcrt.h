@@ -423,6 +423,55 @@ int mcrt_render_ground(const mcrt_scene_desc* scene, const mcrt_config* cfg, flo
  * standing poses) for a contact shadow.  A scene without a vertex (or a NULL argument) → MCRT_ERR_INVALID. */
 int mcrt_scene_floor(const mcrt_scene_desc* scene, float* y);
 
+/* ---- ground reflection: the figure mirrored in a floor plane, as a layer of its own ---------------------------------------
+ * The other half of a figure standing on a glossy floor: per pixel, the colour the reference's own recursion would return for
+ * the reflection ray of a floor at y = ground_y — traceRay(reflectRay, depth + 1) (raytracer.cpp:133-142) with the floor as the
+ * depth-0 surface.  A flipped copy of the figure cannot replace it: it shows the wrong faces and does not meet the feet.
+ * The ray is the geometry layers' pixel-centre ray, origin o and direction d; the plane point is the ground shadow's, with
+ * N = (0, 1, 0) from either side.  All arithmetic float32 with one rounding per operation, uncontracted:
+ *   t = (ground_y - o.y) / d.y                      the pixel REACHES the plane iff d.y != 0 && t > 0 && t <= FLT_MAX
+ *   P = (o.x + d.x * t, ground_y, o.z + d.z * t)
+ *   reflection ray = the reference's own (raytracer.cpp:134-140) for a hit at P with normal N and incoming direction d:
+ *     Nn = normalize(N); D = normalize(d); R = normalize(D - Nn * (2 * dot(D, Nn))); origin = P + Nn * 1e-3f
+ *   hit = intersectScene(reflection ray)
+ *   colour = traceRay(reflection ray, depth = 1, maxBounces = cfg.max_bounces)      where hit.hit
+ * So the shadow seed of the reflected hit carries + 1 * 99999.0f, no ambient occlusion applies (the reference computes it at
+ * depth 0 only), the chain may bounce on to max_bounces, and a bounced miss folds scene.backgroundColor, flat.  Alpha is the hit
+ * texel's originalAlpha.  Planes of width * height pixels, row-major:
+ *   rgba      4 floats  the colour above, straight alpha                                    no reflected hit: (0, 0, 0, 0)
+ *   rgba8     4 uint8   each channel (uint8_t)(clamp(c, 0, 1) * 255.0f + 0.5f), as mcrt_quantize_rgba8    no hit: 0, 0, 0, 0
+ *   distance  1 float   HitResult::t of the reflection ray's closest hit                   no reflected hit: FLT_MAX
+ * ("no reflected hit": the pixel does not reach the plane, or its reflection ray misses the scene.)
+ * With the ground shadow's matte m, this layer R and a floor reflectivity k of the compositor's choice (possibly faded by
+ * distance), the floor under the straight-alpha figure is   page * (1 - m) * (1 - k * R.a) + R.rgb * k * R.a.
+ * Of mcrt_config the pass reads width, height, tile_size (the granularity of the culling, never a value), max_bounces,
+ * soft_shadows and shadow_samples; everything else — the ambient-occlusion fields, depth of field, samples_per_pixel, the
+ * gradient — and the handle's background mode are IGNORED.  max_bounces < 1: the reference returns before it intersects
+ * (depth > maxBounces); the call returns MCRT_OK and every pixel gets the no-hit constants.
+ * The rules of the ground shadow hold: whole frames only; asynchronous on `stream`, not into a graph being recorded; no
+ * workspace, no counters and none of the handle's events; the pass reads the device's seed table through the handle;
+ * mcrt_scene_destroy and mcrt_scene_check wait for it; a handle may be listed more than once in a batch, with different
+ * ground_y; the pixels between frames are not written.
+ * MCRT_ERR_INVALID before any device work: everything the ground shadow refuses (a NULL config, handle, entry, ground_y array
+ * or planes struct, n_frames < 0, a stride below width * height, handles on different devices), all three planes NULL, a
+ * ground_y that is not finite, soft_shadows && shadow_samples > 113 (as for the ground shadow), max_bounces > 8 (the chain's
+ * level colours are folded back to front from a stack of that depth, the depth the render pipeline's arrays are laid out for).
+ * Zero-size frames and n_frames = 0: MCRT_OK, nothing written.
+ * MCRT_REFLECT_CULL=0 in the environment turns the pass's tile culling off (a development knob: the values do not change). */
+typedef struct mcrt_reflection {
+    float* rgba; /* any may be NULL (that plane is not produced), not all */
+    uint8_t* rgba8;
+    float* distance;
+} mcrt_reflection;
+/* resident scene, device pointers, asynchronous on `stream` */
+int mcrt_render_reflection_device(mcrt_scene* scene, const mcrt_config* cfg, float ground_y, const mcrt_reflection* d_out, void* stream);
+/* n_frames scenes of one config in one launch; ground_y: n_frames heights in HOST memory (read before the call returns); frame i
+ * at each plane + i * frame_stride_pixels pixels */
+int mcrt_render_reflection_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y,
+                                        const mcrt_reflection* d_out, size_t frame_stride_pixels, void* stream);
+/* one-shot host form: host pointers, rendered on `device` with a pooled handle like mcrt_render */
+int mcrt_render_reflection(const mcrt_scene_desc* scene, const mcrt_config* cfg, float ground_y, const mcrt_reflection* out, int device);
+
 /* ---- skins on resident scenes: a new skin for a scene that is already on the device -----------------------------------------
  * Everything in a flattened skin scene but its texels is a function of pose, camera and light alone.  A REPAINTABLE handle takes
  * a new skin from a 64 x skin_height RGBA8 image in device memory with one small kernel — no scene build, no flattening, no upload

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_layers_device", "mcrt_render_layers_batch_device", "mcrt_render_layers", "mcrt_render_layers_batch",
     "mcrt_scene_pick", "mcrt_skin_texel",
     "mcrt_render_ground_device", "mcrt_render_ground_batch_device", "mcrt_render_ground", "mcrt_scene_floor",
+    "mcrt_render_reflection_device", "mcrt_render_reflection_batch_device", "mcrt_render_reflection",
     "mcrt_scene_create_skin", "mcrt_scene_set_skin_device", "mcrt_scene_set_skins_batch_device", "mcrt_scene_set_skin",
     "mcrt_skin_pool_map", "mcrt_probe_scene_blob",
 ]
@@ -51,6 +52,7 @@ def load():
     vp = C.c_void_p
     layers_p = C.POINTER(abi.McrtLayers)
     ground_p = C.POINTER(abi.McrtGround)
+    reflection_p = C.POINTER(abi.McrtReflection)
     sig = {
         "mcrt_config_init": (None, [cfg_p]),
         "mcrt_generate_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(abi.McrtTile), C.c_int]),
@@ -81,6 +83,9 @@ def load():
         "mcrt_render_ground_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, f_p, ground_p, C.c_size_t, vp]),
         "mcrt_render_ground": (C.c_int, [desc_p, cfg_p, C.c_float, ground_p, C.c_int]),
         "mcrt_scene_floor": (C.c_int, [desc_p, f_p]),
+        "mcrt_render_reflection_device": (C.c_int, [vp, cfg_p, C.c_float, reflection_p, vp]),
+        "mcrt_render_reflection_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, f_p, reflection_p, C.c_size_t, vp]),
+        "mcrt_render_reflection": (C.c_int, [desc_p, cfg_p, C.c_float, reflection_p, C.c_int]),
         "mcrt_scene_pick": (C.c_int, [vp, cfg_p, abi.c_int32_p, C.c_int, vp]),
         "mcrt_skin_texel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mcrt_scene_create_skin": (C.c_int, [C.c_int, f_p, desc_p, C.c_int, C.POINTER(vp)]),

@@ -192,6 +192,31 @@ def ground_names(planes) -> tuple:
     return tuple(n for n in GROUND_NAMES if n in names)
 
 
+class McrtReflection(C.Structure):
+    """mcrt_reflection: one pointer per plane of a ground-reflection pass (device or host memory, by entry point); NULL = not wanted."""
+
+    _fields_ = [("rgba", C.c_void_p), ("rgba8", C.c_void_p), ("distance", C.c_void_p)]
+
+
+REFLECTION_NAMES = ("rgba", "rgba8", "distance")
+# per pixel: (dtype, components) of each plane
+REFLECTION_FORMATS = {"rgba": (np.float32, 4), "rgba8": (np.uint8, 4), "distance": (np.float32, 1)}
+REFLECTION_MAX_BOUNCES = 8  # maxBounces of a reflection pass
+
+
+def reflection_names(planes) -> tuple:
+    """The wanted reflection planes in the order of ``REFLECTION_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
+    if isinstance(planes, str):
+        planes = (planes,)
+    names = tuple(planes)
+    for n in names:
+        if not isinstance(n, str) or n not in REFLECTION_FORMATS:
+            raise ValueError(f"planes must be taken from {REFLECTION_NAMES}, not {n!r}")
+    if not names:
+        raise ValueError("no plane selected")
+    return tuple(n for n in REFLECTION_NAMES if n in names)
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 
 SURFACE_DTYPE = np.dtype(

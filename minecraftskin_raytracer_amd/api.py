@@ -316,6 +316,37 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderReflection(scene, config: Config, ground: Optional[float] = None, planes=abi.REFLECTION_NAMES, device: int = 0) -> dict:
+        """The figure mirrored in the floor plane y = ``ground`` (mcrt_render_reflection; ``None``: the scene's floor,
+        ``scene_floor``): a dict of the wanted planes — ``rgba`` (H, W, 4) float32, the colour the reference's recursion returns
+        for the floor's reflection ray, straight alpha, zero where nothing is mirrored; ``rgba8`` (H, W, 4) uint8, the same
+        quantised; ``distance`` (H, W) float32, the reflection ray's hit distance (FLT_MAX without a hit).  Of ``config`` only
+        width, height, tileSize, maxBounces (at most 8), softShadows and shadowSamples (at most 113 with softShadows) matter.
+        Failures raise ``McrtError``."""
+        out = TileRenderer.renderReflectionBatch([scene], config, ground, planes, device)
+        return {k: v[0] for k, v in out.items()}
+
+    @staticmethod
+    def renderReflectionBatch(scenes, config: Config, ground=None, planes=abi.REFLECTION_NAMES, device: int = 0) -> dict:
+        """``renderReflection`` for N scenes of one config: the same planes with a leading N.  ``ground``: ``None`` (every
+        scene's own floor), one height for all, or a sequence of N heights.  This host form is a LOOP of
+        ``mcrt_render_reflection`` calls; the batched path is ``render_reflection_batch_device`` on resident ``DeviceScene``
+        handles (one launch per 4096 frames)."""
+        names = abi.reflection_names(planes)
+        descs = [_as_desc(s) for s in scenes]
+        n = len(descs)
+        heights = _ground_heights(descs, ground)
+        w, h = max(config.width, 0), max(config.height, 0)
+        out = {k: _empty_reflection(k, n, h, w) for k in names}
+        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
+            return out
+        c = config.to_c()
+        for i, d in enumerate(descs):
+            frame = abi.McrtReflection(**{k: v[i].ctypes.data for k, v in out.items()})
+            check(load().mcrt_render_reflection(d.ptr, C.byref(c), heights[i], C.byref(frame), int(device)))
+        return out
+
+    @staticmethod
     def lastBatchInfo() -> dict:
         """How the last batch call on this thread ran (mcrt_last_batch_info): ``batched_frames`` taken by the batched
         kernels and ``launch_sequences`` enqueued (1 when the whole batch went through them at once)."""
@@ -349,6 +380,15 @@ def _empty_ground(name: str, n: int, h: int, w: int) -> np.ndarray:
     if name == "visibility":
         a[...] = 1.0
     elif name == "distance":
+        a[...] = np.finfo(np.float32).max
+    return a
+
+
+def _empty_reflection(name: str, n: int, h: int, w: int) -> np.ndarray:
+    """One reflection plane for n frames, holding the constants of a pixel without a reflected hit."""
+    dtype, comps = abi.REFLECTION_FORMATS[name]
+    a = np.zeros((n, h, w) + ((comps,) if comps > 1 else ()), dtype)
+    if name == "distance":
         a[...] = np.finfo(np.float32).max
     return a
 
@@ -603,6 +643,20 @@ class DeviceScene:
         planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
         check(load().mcrt_render_ground_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
 
+    def render_reflection_device(self, config: Config, ground: float, rgba_ptr: int = 0, rgba8_ptr: int = 0, distance_ptr: int = 0,
+                                 stream: int = 0) -> None:
+        """The ground-reflection planes of the frame into device memory (mcrt_render_reflection_device): width * height pixels
+        per plane — rgba 16 bytes per pixel, rgba8 and distance 4 — any pointer may be 0, not all.  ``ground``: the plane's
+        height.  Asynchronous on ``stream``; uses none of the handle's workspace, so it may run beside a render of the handle on
+        another stream."""
+        if not (rgba_ptr or rgba8_ptr or distance_ptr):
+            raise ValueError("give at least one of rgba_ptr, rgba8_ptr, distance_ptr")
+        if not np.isfinite(np.float32(ground)):
+            raise ValueError("ground must be finite")
+        c = config.to_c()
+        planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
+        check(load().mcrt_render_reflection_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
+
     def pick(self, config: Config, xy) -> np.ndarray:
         """What is under the pixels ``xy`` ((n, 2) integers, x then y, inside the frame): a structured array of
         ``abi.SURFACE_DTYPE`` — mesh, face, tx, ty, t, point, normal, albedo — equal to the layers at those pixels
@@ -705,6 +759,33 @@ def render_ground_batch_device(device_scenes: Sequence["DeviceScene"], config: C
     c = config.to_c()
     planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
     check(load().mcrt_render_ground_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+
+
+def render_reflection_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, ground, rgba_ptr: int = 0, rgba8_ptr: int = 0,
+                                   distance_ptr: int = 0, frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
+    """The ground-reflection planes of N resident scenes of one config in one launch (mcrt_render_reflection_batch_device): frame
+    i of each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  ``ground``: one height for all, or N
+    heights (a handle may be listed more than once, with different heights).  Asynchronous on ``stream``."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    if not (rgba_ptr or rgba8_ptr or distance_ptr):
+        raise ValueError("give at least one of rgba_ptr, rgba8_ptr, distance_ptr")
+    if ground is None:
+        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
+    heights = _ground_heights(handles, ground)
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
+    if stride < px:
+        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    gy = (C.c_float * max(n, 1))(*heights)
+    c = config.to_c()
+    planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
+    check(load().mcrt_render_reflection_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
 
 
 def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, skin_stride_bytes: Optional[int] = None, stream: int = 0) -> None:

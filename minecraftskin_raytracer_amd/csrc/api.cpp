@@ -844,6 +844,41 @@ int mcrt_render_ground(const mcrt_scene_desc* desc, const mcrt_config* cfg, floa
     return rc;
 }
 
+// ---- ground reflection: the one-shot host form (render_enqueue.cpp: render_reflection_batch_device) -----------------------------
+int mcrt_render_reflection(const mcrt_scene_desc* desc, const mcrt_config* cfg, float ground_y, const mcrt_reflection* out, int device) {
+    if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
+    if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (cfg->soft_shadows && cfg->shadow_samples > kGroundMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
+    if (cfg->max_bounces > kReflectMaxBounces) return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 8 bounces (its per-lane colour stack)");
+    if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    OneShotScenes set;
+    const mcrt_scene_desc* one[1] = {desc};
+    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
+    if (rc != MCRT_OK) return rc;
+    mcrt_scene* s0 = set.h[0];
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    // the widest elements first: each plane starts on a boundary of its own element size
+    const size_t rgba_bytes = out->rgba ? px * 16 : 0, dist_bytes = out->distance ? px * 4 : 0, u8_bytes = out->rgba8 ? px * 4 : 0;
+    hipError_t e = s0->frame.reserve(rgba_bytes + dist_bytes + u8_bytes);
+    if (e != hipSuccess) return hip_fail(e, "reflection planes");
+    char* base = static_cast<char*>(s0->frame.ptr);
+    mcrt_reflection d{};
+    d.rgba = out->rgba ? reinterpret_cast<float*>(base) : nullptr;
+    d.distance = out->distance ? reinterpret_cast<float*>(base + rgba_bytes) : nullptr;
+    d.rgba8 = out->rgba8 ? reinterpret_cast<uint8_t*>(base + rgba_bytes + dist_bytes) : nullptr;
+    rc = render_reflection_batch_device(set.h.data(), 1, cfg, &ground_y, &d, px, s0->main_stream);
+    set.download(out->rgba, d.rgba, rgba_bytes, rc);
+    set.download(out->distance, d.distance, dist_bytes, rc);
+    set.download(out->rgba8, d.rgba8, u8_bytes, rc);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "reflection render");
+    }
+    return rc;
+}
+
 int mcrt_scene_floor(const mcrt_scene_desc* desc, float* y) {
     if (!desc || !y) return fail(MCRT_ERR_INVALID, "NULL argument");
     bool any = false;

@@ -187,6 +187,7 @@ inline bool valid_background(int b) { return b == MCRT_BACKGROUND_REFERENCE || b
 inline int bad_background() { return fail(MCRT_ERR_INVALID, "background must be MCRT_BACKGROUND_REFERENCE or MCRT_BACKGROUND_TRANSPARENT"); }
 inline bool no_plane(const mcrt_layers* l) { return !l->depth && !l->normal && !l->albedo && !l->id; }
 inline bool no_plane(const mcrt_ground* g) { return !g->visibility && !g->distance && !g->matte; }
+inline bool no_plane(const mcrt_reflection* r) { return !r->rgba && !r->rgba8 && !r->distance; }
 
 // what the calling thread's last mcrt_render_batch* call did (mcrt_last_batch_info; thread-local in api.cpp, like the error text)
 struct BatchInfo {
@@ -248,6 +249,8 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
 int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream);
 int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_ground* d_out, size_t stride,
                                hipStream_t stream);
+int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_reflection* d_out,
+                                   size_t stride, hipStream_t stream);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 

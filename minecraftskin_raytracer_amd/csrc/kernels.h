@@ -277,6 +277,40 @@ int ground_batch_view(GroundFrame* frames, const int* views, int n);
 // dynamic LDS of a launch: the frame's scene tables, then the block's area (masks, points, counts and sample positions)
 size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape);
 
+// ---- ground reflection (mcrt_render_reflection_device & co): the figure mirrored in the plane y = ground_y — per pixel the
+// pixel-centre ray of the layers, its point P on the plane, the reference's reflection ray for a hit at P with normal (0, 1, 0),
+// and traceRay(that ray, depth 1): shading, shadows and further bounces as the reference's recursion runs them below a depth-0
+// surface.  Reads the scene blob and the device's seed table, like a ground pass.
+// One frame of a reflection pass: its scene, its height and its planes (any may be NULL, not all), width * height pixels each
+struct ReflectionFrame {
+    const uint8_t* scene;
+    float* rgba;                 // 4 floats per pixel, straight alpha; zero where the plane is not reached or the reflected ray misses
+    uint8_t* rgba8;              // the same colour quantised as mcrt_quantize_rgba8 quantises it
+    float* distance;             // HitResult::t of the reflection ray's closest hit; FLT_MAX without one
+    const uint32_t* seed_table;  // the handle's window table, or NULL: the recurrence
+    float ground_y;
+    int lds_alpha_words;         // scene tables staged in LDS, as LayersFrame's
+    int lds_face_entries;
+};
+constexpr int kReflectMaxBounces = 8;  // levels of the per-lane colour stack (the depth the flat pipeline is laid out for: kFlatMaxBounces)
+// what the frames of one launch share
+struct ReflectionShape {
+    LayersShape tiles;     // the frame's size and its tile grid, as a layers pass cuts it
+    int samples;           // S: shadow_samples when soft_shadows && shadow_samples > 1, else 1
+    int pass;              // undecided hits whose S sample positions fit the block's LDS area at once
+    int max_bounces;       // below 1: every pixel keeps the miss constants
+    int bundle_decisions;  // as RenderParams'
+    int inside_fast;
+    int cull;              // 0 (MCRT_REFLECT_CULL=0): every mesh is tested for every tile
+};
+// false when the frame holds more units than the kernels index (2^31)
+bool make_reflection_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, bool cull, ReflectionShape& shape);
+// fills f.lds_* and returns the kernel variant by the layers' rule
+int reflection_view(ReflectionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
+int reflection_batch_view(ReflectionFrame* frames, const int* views, int n);
+// dynamic LDS of a launch: the frame's scene tables, then the block's area (hit records, masks, counts and sample positions)
+size_t reflection_lds_bytes(const ReflectionFrame& f, const ReflectionShape& shape);
+
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): a repaintable handle's blob holds the full mesh table of
 // its skin kind, so texel i of its pool is cut from one fixed pixel of the skin image.  One workgroup per scene rewrites what
 // a skin decides of the blob: the float4 texel pool (u8 / 255.0f through a table the HOST formed), the 2-bit alpha predicates
@@ -325,7 +359,7 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
-// ======== passes (pass_kernels.hip): layers and picks, ground shadow, skin repaints ========
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, skin repaints ========
 hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's LDS tables
@@ -336,6 +370,10 @@ hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int vie
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's ground_lds_bytes
 hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream);
+hipError_t launch_reflection(const ReflectionFrame& f, const ReflectionShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
+// frame's reflection_lds_bytes
+hipError_t launch_reflection_batch(const ReflectionFrame* d_table, int n_frames, const ReflectionShape& shape, int view, size_t max_dyn, hipStream_t stream);
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);

@@ -1,5 +1,5 @@
 // pass_kernels.hip — the stand-alone passes over a resident scene (not stages of a render): geometry layers and pixel
-// picks, the ground shadow, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
+// picks, the ground shadow, the ground reflection, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
 // and nothing else: no workspace, no counters.
 #include "kernel_common.h"
 
@@ -476,6 +476,333 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void ground_batch_kernel(Grou
     ground_body<kView>(*(const GroundFrame*)(table + blockIdx.y), sh);
 }
 
+// ---------------------------------------------------------------------------------------------
+// ground reflection (kernels.h: ReflectionFrame): the figure mirrored in the plane y = ground_y, as planes of their own.  Per
+// pixel the layers' pixel-centre ray, its point P on the plane, the reference's reflection ray for a hit at P with normal
+// (0, 1, 0) (raytracer.cpp:134-140) and traceRay(that ray, depth 1) (raytracer.cpp:82-148): the colour the recursion would
+// return for a floor at depth 0.  No ambient occlusion (depth 0 only), a bounced miss folds the flat background.  No workspace.
+//   a workgroup per 256 pixels of a screen tile (grid-stride), in phases handed over through LDS:
+//   1 lane / mesh (every wave)   which meshes a reflection ray of the tile can meet (reflection_tile_mask): none for most
+//                                tiles of a frame — they get the miss constants and form no ray
+//   1 lane / pixel               ray, plane point, reflection ray, closest hit among the tile's meshes; the hits are packed
+//                                onto the block's first lanes as records in LDS (point, normal, texel colour, ray)
+//   1 lane / hit                 the whole-bundle decision (rt::bundle_classify) from the hit's shadow origin; the undecided
+//                                are packed again
+//   1 lane / undecided hit       truncated mt19937 (mt[397] from the seed table) at depth 1 → the S disk sample positions in LDS
+//   1 lane / (undecided hit, light sample)   exact any-hit test on the candidates → lit count by ballot
+//   1 lane / hit                 shade level 1; then the rest of its chain sequentially — reflect, closest hit over all meshes,
+//                                visibility, shade, to max_bounces (a tenth of the weight per level, a minority of the hits) —
+//                                and the fold back to front from a per-lane stack; the colour returns through LDS
+//   1 lane / pixel               the planes: 16 bytes per store where rows and alignment allow
+// ---------------------------------------------------------------------------------------------
+// The meshes a reflection ray of the tile can meet, conservatively: lane m of the calling wave tests mesh m.  With N = (0, 1, 0)
+// the reflected direction R is the camera ray's direction D with its y component negated, so the point P + s R is the mirror
+// image in the plane of P + s D — the camera ray continued beyond the plane.  A reflection ray therefore meets a box B only
+// if the camera ray's LINE meets B mirrored about y = g, and a line through the camera meets a box in front of it only if the
+// pixel lies in the box's image: inside the bounding rectangle of its eight projected corners.  The ray really leaves
+// P + (0, 1e-3, 0), a parallel line 1e-3 away: the mirrored box (of a posed mesh: of its padded bounding sphere) is inflated by
+// 2e-3 + 16 slacks on every side, orders above the float error of R and P; the rectangle takes a relative 1e-3, and the tile
+// the two pixels of mesh_touches_tile.  Every other case keeps the mesh: a corner at or behind the camera plane, cull_ok == 0,
+// 64 meshes or more, a negative sphere radius, non-finite values (every comparison is written to fail open).
+__device__ __forceinline__ unsigned long long reflection_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& t, const float aspect,
+                                                                   const float g, const bool cull, const int lane) {
+    const int n = sc.n_meshes;
+    if (n <= 0) return 0ull;
+    const unsigned long long all = n < 64 ? (1ull << n) - 1ull : ~0ull;
+    if (!cull || sc.hdr->cull_ok == 0 || n >= 64) return all;
+    const float slack = sc.hdr->mask_slack;
+    const float W = static_cast<float>(cfg.width), H = static_cast<float>(cfg.height);
+    // tile extent padded by 2 pixels, in the units of FlatMesh::screen (x: (2u-1)*aspect, y: 1-2v, +y up), as mesh_touches_tile
+    const float tu0 = (2.0f * (static_cast<float>(t.x) - 2.0f) / W - 1.0f) * aspect - 1e-3f * aspect - 1e-3f;
+    const float tu1 = (2.0f * (static_cast<float>(t.x + t.w) + 2.0f) / W - 1.0f) * aspect + 1e-3f * aspect + 1e-3f;
+    const float tv1 = 1.0f - 2.0f * (static_cast<float>(t.y) - 2.0f) / H + 2e-3f;
+    const float tv0 = 1.0f - 2.0f * (static_cast<float>(t.y + t.h) + 2.0f) / H - 2e-3f;
+    const V3 pos = ld3(sc.hdr->cam_pos), fwd = ld3(sc.hdr->cam_fwd), right = ld3(sc.hdr->cam_right), up = ld3(sc.hdr->cam_up);
+    const float inv_h = 1.0f / sc.hdr->cam_half_h;  // cull_ok: finite, in (1e-4, 1e4)
+    bool touch = lane < n;
+    if (touch) {
+        const FlatMesh& m = sc.meshes[lane];
+        if (m.flags & MESH_EMPTY) {
+            touch = false;  // intersection.cpp:205: never hit
+        } else {
+            V3 lo = ld3(m.lo), hi = ld3(m.hi);
+            bool ok = true;
+            if (m.flags & MESH_ROTATED) {
+                const float r = m.sphere[3];
+                ok = r >= 0.0f;
+                lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
+                hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
+            }
+            const float pad = 2e-3f + 16.0f * slack;
+            // mirrored about y = g and inflated
+            const V3 blo = mk(lo.x - pad, g + (g - hi.y) - pad, lo.z - pad), bhi = mk(hi.x + pad, g + (g - lo.y) + pad, hi.z + pad);
+            float u0 = kFltMax, u1 = -kFltMax, v0 = kFltMax, v1 = -kFltMax;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const V3 rel = mk(((c & 1) ? bhi.x : blo.x) - pos.x, ((c & 2) ? bhi.y : blo.y) - pos.y, ((c & 4) ? bhi.z : blo.z) - pos.z);
+                const float zc = dot(rel, fwd), xc = dot(rel, right), yc = dot(rel, up);
+                const float extent = __builtin_fabsf(rel.x) + __builtin_fabsf(rel.y) + __builtin_fabsf(rel.z);
+                ok = ok && zc > 1e-3f * (1.0f + extent);  // a corner at or behind the camera plane: no bound
+                const float nu = xc / zc * inv_h, nv = yc / zc * inv_h;
+                ok = ok && __builtin_fabsf(nu) < 1e30f && __builtin_fabsf(nv) < 1e30f;  // (false for a NaN, which fmin / fmax would drop)
+                u0 = __builtin_fminf(u0, nu), u1 = __builtin_fmaxf(u1, nu), v0 = __builtin_fminf(v0, nv), v1 = __builtin_fmaxf(v1, nv);
+            }
+            if (ok) {
+                const float mg = 1e-3f * (1.0f + __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(u0), __builtin_fabsf(u1)), __builtin_fmaxf(__builtin_fabsf(v0), __builtin_fabsf(v1))));
+                const bool out = (u1 + mg < tu0) | (u0 - mg > tu1) | (v1 + mg < tv0) | (v0 - mg > tv1);
+                touch = !out;
+            }
+        }
+    }
+    return __ballot(touch);
+}
+// visibility term of a hit below level 1, sequential form (rt::hit_visibility with the stream seeded from the device's table)
+template <class SV>
+__device__ __forceinline__ float chain_visibility(const SceneView& scg, const SV& sc, const uint32_t* __restrict__ seed_table, const Hit& hit, const int depth,
+                                                  const int S, const bool soft) {
+    const V3 lpos = ld3(scg.hdr->light_pos);
+    if (!soft) return in_shadow(sc, hit.p, S > 1 ? hit.n : normalize(hit.n), lpos) ? 0.0f : 1.0f;  // shading.cpp:31 / :76-80
+    MtShort rng;
+    const uint32_t seed = shadow_seed(hit.p, depth);
+    const uint32_t slot = seed + kSeedWindowHalf;
+    if (seed_table && slot < kSeedWindow)
+        rng.seed_known(seed, seed_table[slot]);
+    else
+        rng.seed(seed);
+    const LightFrame frame = light_frame(scg, hit.p);
+    int lit = 0;
+    for (int i = 0; i < S; ++i) {
+        const float d0 = rng.uniform();
+        const float d1 = rng.uniform();
+        if (!in_shadow(sc, hit.p, hit.n, light_sample_on_frame(scg, frame, d0, d1))) ++lit;
+    }
+    return static_cast<float>(lit) / static_cast<float>(S);
+}
+template <int kView>
+__device__ __forceinline__ void reflection_body(const ReflectionFrame& __restrict__ f, const ReflectionShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][hit records: 4 planes of float4][candidate masks][inside masks][lit counts][undecided list][positions: pass x S x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.tiles.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const float g = f.ground_y;
+    const V3 lpos = ld3(scg.hdr->light_pos);
+    const float lradius = scg.hdr->light_radius;
+    const int S = sh.samples;
+    const int max_b = sh.max_bounces;
+    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
+    const bool raw_normal = S > 1;  // computeSoftShadow takes the hit's normal as it is; shade()'s own test normalises it (shading.cpp:76-80)
+    const float R = soft ? lradius : 0.0f;
+    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per hit
+    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
+    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    const V3 N = mk(0.0f, 1.0f, 0.0f);
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: hit point, ray origin x; 1: normal, origin y; 2: texel colour; 3: ray direction, origin z — then the hit's colour
+    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(s_rec + 4 * kBlock);
+    unsigned long long* s_ins = s_cand + kBlock;
+    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_ins + kBlock);
+    uint32_t* s_und = s_lit + kBlock;
+    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
+    const bool quads_dist = quad_rows && (reinterpret_cast<uintptr_t>(f.distance) & 15u) == 0;
+    const bool quads_u8 = quad_rows && (reinterpret_cast<uintptr_t>(f.rgba8) & 15u) == 0;
+    const bool vec_rgba = (reinterpret_cast<uintptr_t>(f.rgba) & 15u) == 0;
+    const bool word_u8 = (reinterpret_cast<uintptr_t>(f.rgba8) & 3u) == 0;
+    const float* bgc = scg.hdr->background;
+    const C4 flat_bg{bgc[0], bgc[1], bgc[2], bgc[3]};
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    const int parts = sh.tiles.parts;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        const int tile = unit / parts, part = unit - tile * parts;
+        const int tyi = tile / sh.tiles.tiles_x, txi = tile - tyi * sh.tiles.tiles_x;
+        TileGeom tg;
+        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+        tg.owned_row = tyi, tg.frame_tile = tile;
+        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
+        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
+        // the same in every wave of the workgroup; max_bounces < 1: the reference returns before it intersects
+        const unsigned long long mask = max_b >= 1 ? reflection_tile_mask(scg, cfg, tg, aspect, g, sh.cull != 0, lane) : 0ull;
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        const unsigned pix = p0 + static_cast<unsigned>(tid);
+        const bool valid = pix < npix;
+        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
+        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
+        float dist = kFltMax;
+        C4 col{0.0f, 0.0f, 0.0f, 0.0f};
+        if (mask != 0ull) {  // uniform
+            // ---- a lane per pixel: the ray, the plane point, the reflection ray and its closest hit
+            bool is_hit = false;
+            Hit h;
+            Ray rr{mk(0, 0, 0), mk(0, 0, 0)};
+            if (valid) {
+                const float u = (static_cast<float>(tg.x + lx) + 0.5f) / static_cast<float>(cfg.width);
+                const float v = (static_cast<float>(tg.y + ly) + 0.5f) / static_cast<float>(cfg.height);
+                const Ray ray = camera_ray(scg, u, v, aspect);
+                const float t = (g - ray.o.y) / ray.d.y;
+                if (ray.d.y != 0.0f && t > 0.0f && t <= kFltMax) {
+                    rr = reflect_ray(ray.d, mk(ray.o.x + ray.d.x * t, g, ray.o.z + ray.d.z * t), N);
+                    h = hit_scene(sc, rr, mask);
+                    is_hit = h.hit;
+                }
+            }
+            int n_hits = 0;
+            const int rank = block_rank(is_hit, s_wcnt, n_hits);
+            if (is_hit) {
+                dist = h.t;
+                s_rec[rank] = make_float4(h.p.x, h.p.y, h.p.z, rr.o.x);
+                s_rec[kBlock + rank] = make_float4(h.n.x, h.n.y, h.n.z, rr.o.y);
+                s_rec[2 * kBlock + rank] = make_float4(h.tex.r, h.tex.g, h.tex.b, h.tex.a);
+                s_rec[3 * kBlock + rank] = make_float4(rr.d.x, rr.d.y, rr.d.z, rr.o.z);
+            }
+            if (n_hits) {  // uniform
+                __syncthreads();
+                // ---- a lane per hit: the whole-bundle decision of its level-1 shadow rays
+                const bool mine = tid < n_hits;
+                Hit hit;
+                Ray ray{mk(0, 0, 0), mk(0, 0, 0)};
+                hit.hit = true;
+                bool undecided = false;
+                uint32_t lit = 0u;
+                if (mine) {
+                    const float4 a = s_rec[tid], b = s_rec[kBlock + tid], c = s_rec[2 * kBlock + tid], d = s_rec[3 * kBlock + tid];
+                    hit.p = mk(a.x, a.y, a.z), hit.n = mk(b.x, b.y, b.z), hit.tex = C4{c.x, c.y, c.z, c.w};
+                    ray.o = mk(a.w, b.w, d.w), ray.d = mk(d.x, d.y, d.z);
+                    const V3 O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
+                    unsigned long long cand;
+                    const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
+                    undecided = known < 0;
+                    s_cand[tid] = cand;
+                    s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
+                    if (!undecided) lit = static_cast<uint32_t>(known);
+                }
+                s_lit[tid] = 0u;
+                int total = 0;
+                const int urank = block_rank(undecided, s_wcnt, total);
+                if (undecided) s_und[urank] = static_cast<uint32_t>(tid);
+                const uint32_t n_und = static_cast<uint32_t>(total);
+                if (n_und) __syncthreads();  // uniform
+                for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
+                    const uint32_t nu = min(pass, n_und - u0);
+                    if (u0) __syncthreads();  // the previous pass's rays have read the positions
+                    // ---- a lane per undecided hit: its mt19937 stream at depth 1 and the S disk sample positions
+                    if (soft && static_cast<uint32_t>(tid) < nu) {
+                        const float4 a = s_rec[s_und[u0 + tid]];
+                        disk_sample_positions(scg, f.seed_table, nullptr, mk(a.x, a.y, a.z), 1, S, s_pos + static_cast<size_t>(tid) * 3 * S);
+                    }
+                    __syncthreads();
+                    // ---- a lane per (undecided hit, light sample); every lane of a wave runs the same number of turns (ballot inside)
+                    const uint32_t n_rays = nu * pairs;
+                    for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
+                        const uint32_t q = q0 + static_cast<uint32_t>(lane);
+                        bool visible = false;
+                        uint32_t k = 0;
+                        if (q < n_rays) {
+                            k = s_und[u0 + q / pairs];
+                            const float4 a = s_rec[k], b = s_rec[kBlock + k];
+                            V3 Nk = mk(b.x, b.y, b.z);
+                            if (!raw_normal) Nk = normalize(Nk);
+                            const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
+                            visible = !in_shadow_masked(sc, mk(a.x, a.y, a.z), Nk, target, s_cand[k], s_ins[k]);
+                        }
+                        if (pow2) {
+                            const unsigned long long bal = __ballot(visible);
+                            if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
+                                const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
+                                s_lit[k] = static_cast<uint32_t>(__popcll(grp));
+                            }
+                        } else if (visible) {
+                            atomicAdd(&s_lit[k], 1u);
+                        }
+                    }
+                }
+                if (n_und) __syncthreads();  // the counts are complete
+                if (undecided) lit = s_lit[tid];
+                // ---- a lane per hit: shade level 1, then the rest of the chain and the fold (rt::trace_from_hit's loop)
+                if (mine) {
+                    float vis = soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    C4 stack[kReflectMaxBounces];
+                    int top = 0, depth = 1;
+                    C4 tail;
+                    for (;;) {
+                        const C4 c = shade(scg, hit, normalize(ray.o - hit.p), vis);
+                        if (depth >= max_b) {  // no reflection: `shadedColor.a = originalAlpha; return clamp()`
+                            tail = clamp4(c);
+                            break;
+                        }
+                        stack[top++] = c;
+                        ray = reflect_ray(ray, hit);
+                        ++depth;
+                        hit = hit_scene<true>(sc, ray, ~0ull);
+                        if (!hit.hit) {  // bounced ray missed → flat scene.backgroundColor (:94-102, depth > 0)
+                            tail = flat_bg;
+                            break;
+                        }
+                        vis = chain_visibility(scg, sc, f.seed_table, hit, depth, S, soft);
+                    }
+                    while (top > 0) tail = fold_reflection(stack[--top], tail);
+                    s_rec[3 * kBlock + tid] = make_float4(tail.r, tail.g, tail.b, tail.a);  // (record tid is this lane's alone by now)
+                }
+                __syncthreads();
+                if (is_hit) {
+                    const float4 c = s_rec[3 * kBlock + rank];
+                    col = C4{c.x, c.y, c.z, c.w};
+                }
+                // (the next unit writes its records behind the two barriers of its block_rank)
+            }
+        }
+        // ---- a lane per pixel: the planes
+        if (f.distance) store_plane(f.distance, quads_dist, valid, lane, idx, dist);
+        if (f.rgba && valid) {
+            if (vec_rgba) {
+                reinterpret_cast<float4*>(f.rgba)[idx] = make_float4(col.r, col.g, col.b, col.a);
+            } else {
+                float* o = f.rgba + idx * 4;
+                o[0] = col.r, o[1] = col.g, o[2] = col.b, o[3] = col.a;
+            }
+        }
+        if (f.rgba8) {
+            const uchar4 q = quantize_pixel(make_float4(col.r, col.g, col.b, col.a));
+            const uint32_t w = static_cast<uint32_t>(q.x) | (static_cast<uint32_t>(q.y) << 8) | (static_cast<uint32_t>(q.z) << 16) | (static_cast<uint32_t>(q.w) << 24);
+            if (quads_u8) {  // lanes 4k .. 4k+3 hold four neighbours of one row, all valid or none
+                const uint32_t w1 = __shfl_down(w, 1), w2 = __shfl_down(w, 2), w3 = __shfl_down(w, 3);
+                if (valid && (lane & 3) == 0) *reinterpret_cast<uint4*>(f.rgba8 + idx * 4) = make_uint4(w, w1, w2, w3);
+            } else if (valid) {
+                if (word_u8) {
+                    *reinterpret_cast<uint32_t*>(f.rgba8 + idx * 4) = w;
+                } else {
+                    uint8_t* o = f.rgba8 + idx * 4;
+                    o[0] = q.x, o[1] = q.y, o[2] = q.z, o[3] = q.w;
+                }
+            }
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void reflection_kernel(const ReflectionFrame f, const ReflectionShape sh) {
+    reflection_body<kView>(f, sh);
+}
+using ReflectionTable = const __attribute__((address_space(4))) ReflectionFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void reflection_batch_kernel(ReflectionTable table, const ReflectionShape sh) {
+    reflection_body<kView>(*(const ReflectionFrame*)(table + blockIdx.y), sh);
+}
+
 // ---- host-side launchers (the shapes and LDS sizes they take: render_plan.cpp) ----------------------
 // One launch of a tile pass (layers, ground) over the tile grid `tiles`.  arg: the frame, or the device table of n_frames
 // frames (blockIdx.y = frame); kernel_of(view tag): the kernel of that variant; dyn: its dynamic LDS, hbm_dyn: the HBM
@@ -503,6 +830,17 @@ hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int vie
 }
 hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream) {
     return launch_tile_pass(GroundTable(d_table), n_frames, shape, shape.tiles, view, max_dyn, max_dyn, stream, [](auto v) { return ground_batch_kernel<decltype(v)::value>; });
+}
+// ---- ground reflection (kernels.h): as the ground pass, the HBM variant keeps the block's area in dynamic LDS --------------
+hipError_t launch_reflection(const ReflectionFrame& f, const ReflectionShape& shape, int view, hipStream_t stream) {
+    if (shape.max_bounces > kReflectMaxBounces) return hipErrorInvalidValue;  // the per-lane stack
+    const size_t dyn = reflection_lds_bytes(f, shape);
+    return launch_tile_pass(f, 1, shape, shape.tiles, view, dyn, dyn, stream, [](auto v) { return reflection_kernel<decltype(v)::value>; });
+}
+hipError_t launch_reflection_batch(const ReflectionFrame* d_table, int n_frames, const ReflectionShape& shape, int view, size_t max_dyn, hipStream_t stream) {
+    if (shape.max_bounces > kReflectMaxBounces) return hipErrorInvalidValue;
+    return launch_tile_pass(ReflectionTable(d_table), n_frames, shape, shape.tiles, view, max_dyn, max_dyn, stream,
+                            [](auto v) { return reflection_batch_kernel<decltype(v)::value>; });
 }
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;

@@ -435,6 +435,18 @@ int ground_frame_of(const mcrt_scene* s, const mcrt_ground& out, float ground_y,
     f.ground_y = ground_y;
     return ground_view(f, s->alpha_words, s->n_meshes, s->posed);
 }
+// and for a reflection pass (mcrt_render_reflection_device & co)
+int reflection_frame_of(const mcrt_scene* s, const mcrt_reflection& out, float ground_y, size_t index, size_t stride, ReflectionFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.rgba = out.rgba ? out.rgba + off * 4 : nullptr;
+    f.rgba8 = out.rgba8 ? out.rgba8 + off * 4 : nullptr;
+    f.distance = out.distance ? out.distance + off : nullptr;
+    f.seed_table = s->seed_table;
+    f.ground_y = ground_y;
+    return reflection_view(f, s->alpha_words, s->n_meshes, s->posed);
+}
 
 // What the layers and the ground entry points check alike, before any device work (only the last check looks inside the
 // handles, at their device index).  run = false with MCRT_OK: zero tiles, nothing is written.
@@ -732,6 +744,39 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
         [&](const GroundFrame* d_table, int m) { return launch_ground_batch(d_table, m, shape, view, dyn, stream); });
 }
 
+// ---- ground reflection (mcrt_render_reflection_device & co): the ground pass's host path with another kernel — the scene blob
+// and the device's seed table, no workspace, no counters and none of the handle's events
+int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_reflection* d_out,
+                                   size_t stride, hipStream_t stream) {
+    // argument checks, before any device work
+    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
+    if (n > 0 && !ground_y) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (cfg && cfg->soft_shadows && cfg->shadow_samples > kGroundMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
+    if (cfg && cfg->max_bounces > kReflectMaxBounces) return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 8 bounces (its per-lane colour stack)");
+    bool run;
+    int device = 0;
+    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
+    static const bool cull = !env_off("MCRT_REFLECT_CULL");  // the pass's own: 0 — every mesh for every tile
+    ReflectionShape shape;
+    if (!make_reflection_shape(*cfg, decisions, inside_fast, cull, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(device));
+    std::vector<ReflectionFrame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i)
+        views[static_cast<size_t>(i)] = reflection_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
+    const int view = reflection_batch_view(frames.data(), views.data(), n);
+    size_t dyn = 0;
+    for (const ReflectionFrame& f : frames) dyn = std::max(dyn, reflection_lds_bytes(f, shape));
+    return launch_pass(
+        device, frames, stream, "reflection launches", [&](const ReflectionFrame& f) { return launch_reflection(f, shape, view, stream); },
+        [&](const ReflectionFrame* d_table, int m) { return launch_reflection_batch(d_table, m, shape, view, dyn, stream); });
+}
+
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): one workgroup per handle rewrites the texel pool, the alpha
 // predicates and the MESH_OPAQUE bits of its blob.  The blob is what the handle's renders read, so a repaint sits in the
 // handle's event chain like a render (join_handle_chain / extend_handle_chain, the halves begin_ / end_handle_render use).
@@ -906,6 +951,18 @@ int mcrt_render_ground_device(mcrt_scene* s, const mcrt_config* cfg, float groun
 int mcrt_render_ground_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y, const mcrt_ground* d_out,
                                     size_t frame_stride_pixels, void* stream) {
     return render_ground_batch_device(scenes, n_frames, cfg, ground_y, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_reflection_device(mcrt_scene* s, const mcrt_config* cfg, float ground_y, const mcrt_reflection* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = (cfg && valid_frame(cfg)) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
+    return render_reflection_batch_device(one, 1, cfg, &ground_y, d_out, px, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_reflection_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y,
+                                        const mcrt_reflection* d_out, size_t frame_stride_pixels, void* stream) {
+    return render_reflection_batch_device(scenes, n_frames, cfg, ground_y, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

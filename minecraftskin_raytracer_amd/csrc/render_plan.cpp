@@ -305,7 +305,7 @@ LdsFit lds_fit(uint32_t alpha_words, uint32_t n_meshes, bool posed) {
     if (!fits) return LdsFit{0, 0, kViewHbm};
     return LdsFit{static_cast<int>(n_meshes * 6), static_cast<int>(alpha_words), posed ? kViewLds : kViewLdsUnposed};
 }
-template <class Frame>  // LayersFrame or GroundFrame
+template <class Frame>  // LayersFrame, GroundFrame or ReflectionFrame
 static int view_of_frame(Frame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
     const LdsFit fit = lds_fit(alpha_words, n_meshes, posed);
     f.lds_alpha_words = fit.alpha_words, f.lds_face_entries = fit.face_entries;
@@ -353,6 +353,28 @@ int ground_batch_view(GroundFrame* frames, const int* views, int n) { return bat
 size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape) {
     const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
     return tables + kGroundFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
+}
+// ---- ground reflection (kernels.h) ------------------------------------------------------------------
+bool make_reflection_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, bool cull, ReflectionShape& shape) {
+    std::memset(&shape, 0, sizeof shape);
+    if (!make_layers_shape(cfg, shape.tiles)) return false;
+    shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
+    const int fit = kReflectPosBytes / (12 * shape.samples);  // 8 samples: 85 hits per pass; 113 samples: 6
+    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.max_bounces = cfg.max_bounces;
+    shape.bundle_decisions = bundle_decisions ? 1 : 0;
+    shape.inside_fast = inside_fast ? 1 : 0;
+    shape.cull = cull ? 1 : 0;
+    return true;
+}
+int reflection_view(ReflectionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
+int reflection_batch_view(ReflectionFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
+// The 12-mesh character (72 face entries, 204 alpha words: 3120 bytes of tables) at 8 samples: 3120 + 22528 + 85 * 96 = 33808
+// bytes, four workgroups in a CU's 160 KiB.  The largest tables the LDS views take (28 KiB) make 59392 bytes, below the 64 KiB
+// a workgroup may ask for.
+size_t reflection_lds_bytes(const ReflectionFrame& f, const ReflectionShape& shape) {
+    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    return tables + kReflectFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
 }
 // ---- skins on resident scenes (kernels.h) -----------------------------------------------------------
 size_t skin_tables_bytes(int n_texels) { return 256 * sizeof(float) + static_cast<size_t>(n_texels) * sizeof(uint16_t); }
