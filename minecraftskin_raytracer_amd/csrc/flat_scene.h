@@ -79,6 +79,10 @@ struct FlatHeader {  // 192 bytes
     // error of the per-ray arithmetic being a few ulp of it.  Scale-free: a scene scaled or moved far from the origin
     // keeps the same margin in ulps.  2e-3 for the reference's character scene (camera 50 away); +inf for a scene
     // with non-finite coordinates (every mesh is then a candidate of every query).
+    // The ground pass (pass_kernels.hip: ground_body) hands bundle_classify origins that are NOT on the meshes: points
+    // P + N * 1e-3 of the plane y = ground_y, out to the horizon and on planes far below the figure — coordinates of
+    // 1e3 ... 1e7 in a scene of magnitude 50, whose ulp exceeds this slack — and ground_y is no part of the magnitude.
+    // Measured, not argued: tests/pass_fuzz_cases.py (long-shadow and far-plane cases), DESIGN.md §12.
     float mask_slack;
     float cam_up[3];  // trueUp = right x forward
     float pad1;

@@ -4,7 +4,9 @@ Per pixel the ray is ``oracle.camera_ray`` at the pixel centre (u = (px + 0.5f) 
 formed in float32), ``oracle.intersect`` gives depth, normal, albedo, point and the outer flag, and the mesh is the first
 one, in ascending index order, whose ``oracle.intersect_mesh`` hit has a strictly smaller t (intersectScene's own rule).
 Face and texel come from the colour: the scenes used here give every texel of a mesh its own colour, so ``texture_color``
-names (face, tx, ty).  The hit normal must be parallel to that face's outward direction; against it: MCRT_ID_BACK."""
+names (face, tx, ty).  The hit normal must be parallel to that face's outward direction; against it: MCRT_ID_BACK.
+``expected_surfaces`` is the part the oracle names by itself; for scenes whose textures repeat colours (tests/pass_fuzz_cases.py)
+``assert_ids_name_the_surfaces`` checks an id plane the other way round: the texel it names must hold the oracle's albedo."""
 from __future__ import annotations
 
 import functools
@@ -104,20 +106,31 @@ def _texel_table(scene_np):
 
 
 def _face_directions(scene_np):
-    """per mesh: (6, 3) outward directions of its faces in world space (face centre minus box centre, normalised)."""
+    """per mesh: (6, 3) outward directions of its faces in world space (face centre minus box centre, normalised).  A face whose
+    centre is the box's (a box of no thickness along that axis) takes the unit normal of its first triangle, which build_box and
+    the native builder wind to point outwards."""
     out = []
     for mesh in scene_np["meshes"]:
         v = np.asarray(mesh["triangles"], np.float64).reshape(12, 3, 3)
-        centre = v.reshape(-1, 3).mean(axis=0)
+        pts = v.reshape(-1, 3)
+        if mesh["hasRotation"]:
+            centre = pts.mean(axis=0)
+        else:  # exact for an axis-aligned box, also one of no thickness
+            centre = 0.5 * (pts.min(axis=0) + pts.max(axis=0))
         d = np.stack([v[2 * f:2 * f + 2].reshape(-1, 3).mean(axis=0) - centre for f in range(6)])
-        out.append(d / np.linalg.norm(d, axis=1, keepdims=True))
+        norms = np.linalg.norm(d, axis=1)
+        for f in range(6):
+            if not norms[f] > 1e-6 * norms.max():
+                d[f] = np.cross(v[2 * f, 1] - v[2 * f, 0], v[2 * f, 2] - v[2 * f, 0])
+        with np.errstate(all="ignore"):
+            out.append(d / np.linalg.norm(d, axis=1, keepdims=True))
     return out
 
 
-def expected_layers(oracle, sd, width, height) -> dict:
-    """{"depth" (H, W), "normal", "albedo" (H, W, 4), "id" (H, W, 4) int32, "point" (H, W, 3), "hit" (H, W) bool}."""
-    scene_np = sd.to_numpy()
-    n_meshes = len(scene_np["meshes"])
+def expected_surfaces(oracle, sd, width, height) -> dict:
+    """What the oracle itself names per pixel: {"depth" (H, W), "normal", "albedo" (H, W, 4), "point" (H, W, 3), "hit" (H, W)
+    bool, "mesh" (H, W) int32 (-1: none), "outer" (H, W) bool} — no face and no texel, which the oracle does not know."""
+    n_meshes = sd.desc.n_meshes
     rays = pixel_rays(oracle, sd.ptr, width, height)
     hits = oracle.intersect(sd.ptr, rays)
     n = len(rays)
@@ -138,14 +151,28 @@ def expected_layers(oracle, sd, width, height) -> dict:
     albedo[hit] = hits["texture_color"][hit]
     point = np.zeros((n, 3), f32)
     point[hit] = hits["point"][hit]
+    outer = hit & (hits["is_outer_layer"] != 0)
+    return {"depth": depth.reshape(height, width), "normal": normal.reshape(height, width, 4),
+            "albedo": albedo.reshape(height, width, 4), "point": point.reshape(height, width, 3),
+            "hit": hit.reshape(height, width), "mesh": mesh.reshape(height, width), "outer": outer.reshape(height, width)}
+
+
+def expected_layers(oracle, sd, width, height) -> dict:
+    """{"depth" (H, W), "normal", "albedo" (H, W, 4), "id" (H, W, 4) int32, "point" (H, W, 3), "hit" (H, W) bool} — for scenes
+    whose texels all differ within a mesh: the colour names (face, tx, ty)."""
+    scene_np = sd.to_numpy()
+    s = expected_surfaces(oracle, sd, width, height)
+    n = width * height
+    hit, mesh, outer = s["hit"].reshape(n), s["mesh"].reshape(n), s["outer"].reshape(n)
+    normal, albedo = s["normal"].reshape(n, 4), s["albedo"].reshape(n, 4)
     ids = np.tile(np.array([-1, 0, -1, -1], np.int32), (n, 1))
     table, textured = _texel_table(scene_np)
     dirs = _face_directions(scene_np)
     for i in np.flatnonzero(hit):
         m = int(mesh[i])
-        along = dirs[m] @ hits["normal"][i].astype(np.float64)
+        along = dirs[m] @ normal[i, :3].astype(np.float64)
         tx = ty = -1
-        by_colour = table.get((m, np.ascontiguousarray(hits["texture_color"][i], f32).tobytes()))
+        by_colour = table.get((m, np.ascontiguousarray(albedo[i], f32).tobytes()))
         if by_colour is not None:
             face, tx, ty = by_colour
         else:  # a face without texels: the one the normal points out of (an inner box seen from outside has no exit-face hits)
@@ -153,11 +180,40 @@ def expected_layers(oracle, sd, width, height) -> dict:
             face = int(np.argmax(along))
             assert not textured[(m, face)], f"pixel {i}: a colour that is none of mesh {m}'s texels"
         assert abs(along[face]) > 0.99, (i, face, along)  # the normal is that face's, or (exit face) its opposite
-        flags = (abi.ID_BACK if along[face] < 0 else 0) | (abi.ID_OUTER if hits["is_outer_layer"][i] else 0)
+        flags = (abi.ID_BACK if along[face] < 0 else 0) | (abi.ID_OUTER if outer[i] else 0)
         ids[i] = (m, face | flags, tx, ty)
-    return {"depth": depth.reshape(height, width), "normal": normal.reshape(height, width, 4),
-            "albedo": albedo.reshape(height, width, 4), "id": ids.reshape(height, width, 4),
-            "point": point.reshape(height, width, 3), "hit": hit.reshape(height, width)}
+    return {"depth": s["depth"], "normal": s["normal"], "albedo": s["albedo"], "id": ids.reshape(height, width, 4),
+            "point": s["point"], "hit": s["hit"]}
+
+
+def assert_ids_name_the_surfaces(ids: np.ndarray, surf: dict, scene_np: dict, what=""):
+    """The id plane (H, W, 4) against expected_surfaces, for scenes whose texels may share colours — the other way round than
+    expected_layers: mesh, the outer flag and the hit as the oracle has them; the face the pass names must be one the hit
+    normal is parallel to, with MCRT_ID_BACK iff the normal points against it; and the texel the pass names, looked up in
+    the scene description, must hold the oracle's albedo bit for bit.  A face without texels: tx = ty = -1.
+    A box of no thickness has two coincident faces, and the oracle cannot tell which was hit: either is accepted, with
+    MCRT_ID_BACK set for the one the normal points against and with its own texel holding the albedo."""
+    hit = surf["hit"]
+    bad = np.argwhere(ids[..., 0] != surf["mesh"])
+    assert len(bad) == 0, f"{what} id: the mesh of {len(bad)} pixels differs; first (y, x) = {tuple(bad[0])}: {ids[tuple(bad[0])]} vs mesh {surf['mesh'][tuple(bad[0])]}"
+    assert (ids[~hit] == np.array([-1, 0, -1, -1], np.int32)).all(), f"{what} id: a pixel without a hit is not (-1, 0, -1, -1)"
+    dirs = _face_directions(scene_np)
+    for y, x in np.argwhere(hit):
+        m, fword, tx, ty = (int(v) for v in ids[y, x])
+        face, where = fword & 7, f"{what} id at (y, x) = ({y}, {x}): {ids[y, x]}"
+        assert face < 6 and (fword & ~(7 | abi.ID_BACK | abi.ID_OUTER)) == 0, where
+        assert bool(fword & abi.ID_OUTER) == bool(surf["outer"][y, x]) == bool(scene_np["meshes"][m]["isOuterLayer"]), where
+        along = float(dirs[m][face] @ surf["normal"][y, x, :3].astype(np.float64))
+        assert abs(along) > 0.99, f"{where}: the hit normal is not that face's ({along})"
+        assert bool(fword & abi.ID_BACK) == (along < 0), where
+        t = int(scene_np["meshes"][m]["tri_texture"][2 * face])
+        tex = scene_np["textures"][t] if t >= 0 else None
+        if tex is None or tex["width"] <= 0 or tex["height"] <= 0 or len(tex["pixels"]) == 0:
+            assert (tx, ty) == (-1, -1), f"{where}: a face without texels"
+            continue
+        assert 0 <= tx < tex["width"] and 0 <= ty < tex["height"], where
+        texel = np.ascontiguousarray(tex["pixels"][ty * tex["width"] + tx], f32)
+        assert texel.tobytes() == np.ascontiguousarray(surf["albedo"][y, x], f32).tobytes(), f"{where}: texel {texel} is not the albedo {surf['albedo'][y, x]}"
 
 
 @functools.lru_cache(maxsize=None)

@@ -375,8 +375,22 @@ def test_render_survives_a_nearly_full_device(mcrt, gpu):
     free, _total = torch.cuda.mem_get_info()
     leave = 100 << 20  # the unconstrained workspace of this frame is ~0.25 GB (sized for the tiles meshes can touch)
     hog = torch.empty(max(0, free - leave), dtype=torch.uint8, device="cuda")
+    more = []
     try:
         free2, _ = torch.cuda.mem_get_info()
+        # The runtime gives memory back under this pressure that it still held when `free` was read: the scratch of a kernel
+        # with a large private segment that ran earlier in the process (the reflection pass: 448 B per lane x 64 lanes x 8192
+        # wave slots = 224 MiB per queue).  Observed on an MI355X in one process: after tests/test_gpu_png.py alone `free`
+        # read 294 010 MiB and 100 MiB were free behind the hog; after tests/test_gpu_pass_fuzz.py `free` read 293 880 MiB and
+        # 324 MiB = 100 + 224 were free behind it, torch reporting no allocation retry; 660 MiB after the whole suite up to here.
+        # That memory is taken as well, so that the device is as full as this test means it to be; a top-up that does not fit
+        # leaves the device as it is, and the bound below decides.
+        while free2 > leave + (16 << 20) and len(more) < 8:
+            try:
+                more.append(torch.empty(free2 - leave, dtype=torch.uint8, device="cuda"))
+            except torch.cuda.OutOfMemoryError:
+                break
+            free2, _ = torch.cuda.mem_get_info()
         assert free2 < (400 << 20)
         ds2 = mcrt.DeviceScene(sd)
         # the output frame is carved out of the hog so that it does not compete for the leftover
@@ -390,6 +404,7 @@ def test_render_survives_a_nearly_full_device(mcrt, gpu):
     finally:
         frame = None
         del hog
+        more.clear()
         torch.cuda.empty_cache()
 
 
