@@ -68,7 +68,11 @@ void touched_tiles_per_row(const mcrt_scene* sc, const mcrt_config& cfg, const S
             const double z_hi = 1.0 / m.depth[0], z_lo = 1.0 / m.depth[1];
             const double d = std::max(std::max(std::fabs(z_hi - f_lo), std::fabs(z_hi - f_hi)),
                                       std::max(std::fabs(z_lo - f_lo), std::fabs(z_lo - f_hi)));
-            const double pad = (cfg.aperture * d / half_h * 1.02 + 1e-3) * 1.01 + 1e-4;
+            // the rounding of lens_ray's origin and focus point at the camera's coordinate magnitude (tile_mesh_mask)
+            const double err = 4.0 * 1.1920929e-7 * (static_cast<double>(h->mask_slack) / kMaskSlack + focus + cfg.aperture);
+            const double rel = err * f_hi * (1.0 + std::sqrt(half_w * half_w + half_h * half_h));
+            if (!(rel < 0.045)) return;  // (the device: 0.05)
+            const double pad = (cfg.aperture * d / half_h * 1.02 + 1e-3 + (2.0 * rel + err * z_hi) / half_h) * 1.01 + 1e-4;
             if (!(pad < 1e6)) return;
             u0 -= pad, v0 -= pad, u1 += pad, v1 += pad;
         }

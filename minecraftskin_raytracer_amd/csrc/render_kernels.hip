@@ -452,7 +452,16 @@ __device__ __forceinline__ unsigned long long tile_mesh_mask(const SceneView& sc
             const float d = fmaxf(fmaxf(fabsf(inv_z_hi - inv_f_lo), fabsf(inv_z_hi - inv_f_hi)),
                                   fmaxf(fabsf(inv_z_lo - inv_f_lo), fabsf(inv_z_lo - inv_f_hi)));
             lens_pad = cfg.aperture * d / half_h * 1.02f + 1e-3f;
-            if (!(m.depth[0] > 0.0f) || !(focus > 0.0f) || !(lens_pad < 1e6f)) lens_pad = 1e30f;  // no bound
+            // That is the exact lens.  lens_ray forms the ray's origin (camera + lens offset) and its focus point (camera +
+            // direction * focus) in floats at the camera's coordinate magnitude: each is off by up to an ulp of it, so the
+            // direction, their difference of length ~ focus, is off by `err` / focus and the origin by `err`.  Far from the
+            // origin (a camera 5e7 out: an ulp of 4 against a focus distance of 10) that is no small angle; from a twentieth
+            // of the focus point's depth on there is no bound.  err: 4 ulp of the scene's magnitude (mask_slack / kMaskSlack).
+            const float err = 4.0f * 1.1920929e-7f * (sc.hdr->mask_slack * (1.0f / kMaskSlack) + focus + cfg.aperture);
+            const float r2 = half_w * half_w + half_h * half_h;
+            const float rel = err * inv_f_hi * (1.0f + __builtin_sqrtf(r2));  // in tangent units, at the frame's corner
+            lens_pad += (2.0f * rel + err * inv_z_hi) / half_h;
+            if (!(m.depth[0] > 0.0f) || !(focus > 0.0f) || !(lens_pad < 1e6f) || !(rel < 0.05f)) lens_pad = 1e30f;  // no bound
         }
         touch = mesh_touches_tile(m, tg, cfg, aspect, lens_pad);
     }

@@ -44,6 +44,15 @@ def simple_scene(meshes=(), light=(0, 50, 50), cam_pos=(0, 18, 40), cam_target=(
                      camera_fov=fov, backgroundColor=bg)
 
 
+def many_boxes(n=70):
+    # more than 64 meshes: the scene tables do not fit the LDS budget (kernels read them from HBM)
+    meshes = []
+    for i in range(n):
+        col = solid(((i * 37 % 255) / 255.0, (i * 91 % 255) / 255.0, 0.6, 1.0))
+        meshes.append(build_box(col, ((i % 10) * 3.0 - 13.5, (i // 10) * 3.0 + 8.0, 0.0), (2.0, 2.0, 2.0)))
+    return simple_scene(meshes)
+
+
 def skin_scene(kind="S64", pose_index=0) -> "M.SceneDesc":
     return M.MeshBuilder.buildScene(M.synthetic_skin(kind), M.getBuiltinPoses()[pose_index])
 

@@ -84,20 +84,11 @@ def test_turntable_equals_oracle(mcrt, gpu, oracle, extra):
         scenes.assert_bit_equal(imgs[i], oracle.render(sd.ptr, cfg), f"view {i}")
 
 
-def _many_boxes(n=70):
-    # more than 64 meshes: the scene tables do not fit the LDS budget (kernels read them from HBM)
-    meshes = []
-    for i in range(n):
-        col = scenes.solid(((i * 37 % 255) / 255.0, (i * 91 % 255) / 255.0, 0.6, 1.0))
-        meshes.append(scenes.build_box(col, ((i % 10) * 3.0 - 13.5, (i // 10) * 3.0 + 8.0, 0.0), (2.0, 2.0, 2.0)))
-    return scenes.simple_scene(meshes)
-
-
 def test_mixed_posed_unposed_and_hbm_scenes(mcrt, gpu, oracle):
     cfg = abi.Config(width=48, height=40, maxBounces=3, samplesPerPixel=2, tileSize=16)
     unposed = [scenes.skin_scene("S64", 0), mcrt.MeshBuilder.buildDefaultScene()]
     posed = [scenes.skin_scene("S64", 3), scenes.skin_scene("S32", 1)]
-    big = mcrt.SceneDesc(_many_boxes())
+    big = mcrt.SceneDesc(scenes.many_boxes())
     for batch in (unposed, unposed + posed, [posed[0], unposed[0], big, unposed[1]]):
         imgs = mcrt.TileRenderer.renderBatch(batch, cfg)
         assert mcrt.TileRenderer.lastBatchInfo() == {"batched_frames": len(batch), "launch_sequences": 1}

@@ -52,8 +52,10 @@ class Checker:
         if threads <= 1:
             run(list(tiles))
         else:
+            tiles = list(tiles)
+            chunks = [tiles[i::4 * threads] for i in range(min(4 * threads, len(tiles)))]  # (a frame of 1 x 1 tiles has thousands)
             with ThreadPoolExecutor(threads) as pool:  # ctypes releases the GIL during the call; tiles are disjoint
-                list(pool.map(run, [[t] for t in tiles]))
+                list(pool.map(run, chunks))
         return frame, hits
 
 

@@ -9,6 +9,12 @@ The scene-only passes (tests/pass_fuzz_cases.py), every plane of a pass, bit for
   layers       renderLayers on make_pass_case, odd seeds wide: depth, normal, albedo, and the texel the id plane names
   long-shadow  renderGround and renderReflection on make_long_shadow_case: ground points 200 ... 30 000 out along a shadow
   far-plane    renderGround and renderReflection on make_far_plane_case: planes 10 ... 10 000 scene heights down
+The batched entries (tests/batch_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_batch_fuzz.py):
+  batch        render_batch_device on make_beauty_batch(seed): 1 ... 16 frames of mixed scenes under one config, fresh and stale
+               tile seeds, a lead and a stride gap; every third seed also through TileRenderer.renderBatch
+  pass-batch   render_layers / ground / reflection_batch_device on 16 scenes under one config, each at its own plane height: the
+               groups bundle, wide, long-shadow and far-plane in turn from seed first + 16 k, every fifth batch four cases of each
+For these a mismatch prints the batch, the frame index, the plane, the count and the first pixel.
 A mismatch prints the case, the plane, the number of differing pixels and the first of them; the exit status is then 1.  After
 a HIP error (exit status 2) nothing more is started.  MCRT_BUNDLE_DECISIONS=0 / MCRT_REFLECT_CULL=0 in the environment render
 without the whole-bundle decisions / the reflection's tile culling: a mismatch that goes away with one is that shortcut's."""
@@ -23,8 +29,71 @@ from fuzz_cases import make_bundle_case, make_case, make_wide_case
 first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
-if mode not in ("", "bundle", "wide") + PASS_MODES:
+BATCH_MODES = ("batch", "pass-batch")
+if mode not in ("", "bundle", "wide") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
+
+
+def batch_sweep():
+    import batch_fuzz_cases as B, test_gpu_batch_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    # the oracle's frames are made ahead of the device by worker processes (forked before the device is first used; they never
+    # use it), in the order of the batches
+    import multiprocessing
+
+    workers = max(1, min(14, len(os.sched_getaffinity(0)) - 2, int(os.environ.get("OMP_NUM_THREADS", "16")) - 2))
+    keys = [("mixed", first + 16 * k) if k % 5 == 4 else (B.PASS_GROUPS[k % 4], first + 16 * k) for k in range(count)]
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    ahead = pool.imap(B.worker_beauty_frames, range(first, first + count)) if mode == "batch" else pool.imap(B.worker_pass_expectation, keys)
+    bad = frames = total = inside = 0
+    previous, what = None, ""
+    t0 = time.time()
+    for k in range(count):
+        lines = []
+        try:
+            if mode == "batch":
+                seed = first + k
+                case = B.make_beauty_batch(seed)
+                what = case[4]
+                exp = next(ahead)
+                handles = [M.DeviceScene(sd) for sd in case[0]]
+                try:
+                    lines += T.run_beauty_batch(M, handles, case, exp, previous, single=seed)
+                    for h in handles:
+                        h.check()
+                finally:
+                    for h in handles:
+                        h.close()
+                if seed % 3 == 0:
+                    lines += T.run_host_batch(M, case, exp)
+                previous = case[1]
+                frames += len(exp); total += sum(h for _, h in exp); inside += B.expected_envelope(case[1])
+            else:
+                what = f"pass batch {keys[k]}"
+                batch = B.make_pass_batch_of(keys[k])
+                ground, reflection, surfaces = next(ahead)
+                lines += T.run_pass_batch(M, batch, ground, reflection, surfaces)
+                frames += len(ground); total += np.asarray(B.pass_totals(ground, reflection, surfaces))
+        except McrtError as e:
+            print(f"HIP ERROR {what}: {e}", flush=True)
+            print(f"fuzz {mode}: stopped at batch {k} of {count} from seed {first}, {bad} mismatching batch(es)")
+            pool.terminate()
+            sys.exit(2)
+        if lines:
+            bad += 1
+            print("\n".join(lines[:20]), flush=True)
+        if k % 50 == 49:
+            print(f"... {k + 1} batches, {bad} mismatching, {time.time() - t0:.0f} s", flush=True)
+    if mode == "batch":
+        print(f"fuzz batch: {count} batches from seed {first}: {bad} mismatching batch(es); {frames} frames, {inside} batches inside the "
+              f"batched envelope; the oracle holds {total} hit pixels")
+    else:
+        d, p, r, l = (int(x) for x in np.atleast_1d(total))
+        print(f"fuzz pass-batch: {count} batches from seed {first}: {bad} mismatching batch(es); {frames} ground frames; the oracle holds "
+              f"{d} dark, {p} penumbra, {r} reflected and {l} layer-hit pixels")
+    pool.terminate()
+    sys.exit(1 if bad else 0)
 
 
 def pass_sweep():
@@ -91,6 +160,8 @@ def pass_sweep():
 
 if mode in PASS_MODES:
     pass_sweep()
+if mode in BATCH_MODES:
+    batch_sweep()
 if len(sys.argv) > 3 and sys.argv[3] == "bundle":
     make_case = make_bundle_case
 if len(sys.argv) > 3 and sys.argv[3] == "wide":
