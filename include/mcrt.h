@@ -472,6 +472,59 @@ int mcrt_render_reflection_batch_device(mcrt_scene* const* scenes, int n_frames,
 /* one-shot host form: host pointers, rendered on `device` with a pooled handle like mcrt_render */
 int mcrt_render_reflection(const mcrt_scene_desc* scene, const mcrt_config* cfg, float ground_y, const mcrt_reflection* out, int device);
 
+/* ---- light layers: per-pixel shadow, ambient occlusion and direct light on the figure itself ------------------------------
+ * The terms a relighting or an "ambient occlusion only" look is built from: how much of the disk light reaches the surface under
+ * a pixel, how occluded that surface is, and what shade() returns for it before ambient occlusion and the bounces are folded in
+ * — the reference's own computeSoftShadow, computeAO and shade at the primary hit.
+ * The ray is the geometry layers' ray: u = (px + 0.5f) / width, v = (py + 0.5f) / height, Camera::generateRay(u, v,
+ * (float)width / (float)height) with origin o, and h = intersectScene(ray).  All arithmetic float32 with one rounding per
+ * operation, uncontracted.  For a pixel with h.hit (planes of width * height pixels, row-major):
+ *   visibility  1 float   the value shade() multiplies diffuse and specular by in traceRay at depth 0 (raytracer.cpp:107-117,
+ *                         shading.cpp:76-81), in one of three modes:
+ *                           soft_shadows && shadow_samples > 1:
+ *                             computeSoftShadow(h.point, h.normal, scene.light, scene, shadow_samples, seed) with
+ *                             seed = (unsigned)(p.x * 12345.0f + p.y * 67890.0f + p.z * 11111.0f + 0.0f * 99999.0f), summed left
+ *                             to right, the reference's cast; inside it a light radius below 1e-4 takes the one isInShadow ray
+ *                             with the raw normal;
+ *                           otherwise shade()'s own fallback: isInShadow(h.point, normalize(h.normal), light.position) ? 0 : 1
+ *   occlusion   1 float   computeAO(h.point, h.normal, scene, ao_samples, ao_radius, aoSeed) = 1 - occluded / ao_samples with
+ *                         aoSeed = (unsigned)(p.x * 73856093.0f + p.y * 19349663.0f + p.z * 83492791.0f) (raytracer.cpp:38-78,
+ *                         :122-123).  Produced whenever the plane is asked for: ao_enabled and ao_intensity are IGNORED, the
+ *                         compositor applies 1 - k * (1 - occlusion) itself
+ *   direct      4 floats  shade(h, normalize(o - h.point), scene.light, scene, ShadingParams{}, visibility): shadedColor of
+ *                         raytracer.cpp:117 — Blinn-Phong, clamped, alpha = the texel's alpha
+ * At a miss: visibility 1.0f, occlusion 1.0f, direct (0, 0, 0, 0).
+ * RECOMPOSITION (part of the contract).  For every pixel with a hit, the beauty frame of the same scene at samples_per_pixel = 1,
+ * no depth of field, max_bounces = 0 and the same shadow settings
+ *   - with ao_enabled = 0 EQUALS direct, bit for bit;
+ *   - with ao_enabled = 1 equals, for that config's ao_samples, ao_radius and ao_intensity,
+ *       k = 1.0f - ao_intensity * (1.0f - occlusion);  rgb = clamp(direct.rgb * k, 0, 1);  a = direct.a
+ *     bit for bit.
+ * Of mcrt_config the pass reads width, height, tile_size (the granularity of the culling, never a value), soft_shadows,
+ * shadow_samples, ao_samples and ao_radius (the last two only when the occlusion plane is asked for); everything else and the
+ * handle's background mode are IGNORED.  ao_radius <= 0 is legal: no ray can be occluded, the plane is 1.0f.
+ * The rules of the geometry layers hold: whole frames only; asynchronous on `stream`, not into a graph being recorded; no
+ * workspace, no counters and none of the handle's events, so the pass may run beside the handle's render on another stream; the
+ * pass reads the device's seed tables through the handle and builds none; mcrt_scene_destroy and mcrt_scene_check wait for it;
+ * a handle may be listed more than once in a batch; the pixels between frames are not written.
+ * MCRT_ERR_INVALID before any device work: everything the ground shadow refuses (a NULL config, handle, entry or planes struct,
+ * all three planes NULL, n_frames < 0, a stride below width * height, handles on different devices), soft_shadows &&
+ * shadow_samples > 113 (the truncated mt19937 form yields 227 draws), and, when the occlusion plane is asked for, ao_samples < 1
+ * (the reference divides by it), ao_samples > 113 (an AO sample takes two draws) or an ao_radius that is not finite.
+ * Zero-size frames and n_frames = 0: MCRT_OK, nothing written. */
+typedef struct mcrt_light_planes {
+    float* visibility; /* any may be NULL (that plane is not produced), not all */
+    float* occlusion;
+    float* direct;
+} mcrt_light_planes;
+/* resident scene, device pointers, asynchronous on `stream` */
+int mcrt_render_light_device(mcrt_scene* scene, const mcrt_config* cfg, const mcrt_light_planes* d_out, void* stream);
+/* n_frames scenes of one config in one launch per kernel; frame i at each plane + i * frame_stride_pixels pixels */
+int mcrt_render_light_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_light_planes* d_out,
+                                   size_t frame_stride_pixels, void* stream);
+/* one-shot host form: host pointers, rendered on `device` with a pooled handle like mcrt_render */
+int mcrt_render_light(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_light_planes* out, int device);
+
 /* ---- skins on resident scenes: a new skin for a scene that is already on the device -----------------------------------------
  * Everything in a flattened skin scene but its texels is a function of pose, camera and light alone.  A REPAINTABLE handle takes
  * a new skin from a 64 x skin_height RGBA8 image in device memory with one small kernel — no scene build, no flattening, no upload

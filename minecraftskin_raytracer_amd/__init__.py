@@ -24,6 +24,7 @@ from .api import (  # noqa: F401
     render_layers_batch_device,
     render_ground_batch_device,
     render_reflection_batch_device,
+    render_light_batch_device,
     scene_floor,
     set_skins_batch_device,
     skin_pool_map,
@@ -38,5 +39,5 @@ __all__ = [
     "TileRenderer", "device_count", "flatten", "getBuiltinPoses", "probe_detmath", "probe_detmath_range",
     "probe_mt_uniform", "quantize_rgba8", "quantize_rgba8_device", "unpack_rows_device", "ImageWriter", "render_png", "assemble_frame_device", "trim",
     "render_batch_device", "last_batch_info", "bg_plate_info", "draw_plate_info", "render_layers_batch_device", "skin_texel",
-    "render_ground_batch_device", "render_reflection_batch_device", "scene_floor", "SkinBatch", "set_skins_batch_device", "skin_pool_map",
+    "render_ground_batch_device", "render_reflection_batch_device", "render_light_batch_device", "scene_floor", "SkinBatch", "set_skins_batch_device", "skin_pool_map",
 ]

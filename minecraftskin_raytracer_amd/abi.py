@@ -217,6 +217,31 @@ def reflection_names(planes) -> tuple:
     return tuple(n for n in REFLECTION_NAMES if n in names)
 
 
+class McrtLightPlanes(C.Structure):
+    """mcrt_light_planes: one pointer per plane of a light pass (device or host memory, by entry point); NULL = not wanted."""
+
+    _fields_ = [("visibility", C.c_void_p), ("occlusion", C.c_void_p), ("direct", C.c_void_p)]
+
+
+LIGHT_NAMES = ("visibility", "occlusion", "direct")
+# per pixel: (dtype, components) of each plane
+LIGHT_FORMATS = {"visibility": (np.float32, 1), "occlusion": (np.float32, 1), "direct": (np.float32, 4)}
+LIGHT_MAX_SAMPLES = 113  # shadowSamples (with softShadows on) and aoSamples (with the occlusion plane) of a light pass
+
+
+def light_names(planes) -> tuple:
+    """The wanted light planes in the order of ``LIGHT_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
+    if isinstance(planes, str):
+        planes = (planes,)
+    names = tuple(planes)
+    for n in names:
+        if not isinstance(n, str) or n not in LIGHT_FORMATS:
+            raise ValueError(f"planes must be taken from {LIGHT_NAMES}, not {n!r}")
+    if not names:
+        raise ValueError("no plane selected")
+    return tuple(n for n in LIGHT_NAMES if n in names)
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 
 SURFACE_DTYPE = np.dtype(

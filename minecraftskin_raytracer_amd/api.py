@@ -347,6 +347,36 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderLight(scene, config: Config, planes=abi.LIGHT_NAMES, device: int = 0) -> dict:
+        """What the light does on the figure itself (mcrt_render_light), at the primary hit of each pixel-centre ray: a dict of
+        the wanted planes — ``visibility`` (H, W) float32, the share of the disk light that reaches the surface (1 at a miss);
+        ``occlusion`` (H, W) float32, ``1 - occluded / aoSamples`` whatever ``aoEnabled`` says (1 at a miss); ``direct``
+        (H, W, 4) float32, ``shade()`` with that visibility before ambient occlusion and bounces, alpha the texel's (zero at a
+        miss).  The beauty frame at 1 spp, 0 bounces is ``direct`` without AO and ``clip(direct.rgb * (1 - aoIntensity *
+        (1 - occlusion)), 0, 1)`` with it, bit for bit.  Of ``config`` only width, height, tileSize, softShadows, shadowSamples
+        (at most 113 with softShadows), aoSamples (1 to 113) and aoRadius matter.  Failures raise ``McrtError``."""
+        out = TileRenderer.renderLightBatch([scene], config, planes, device)
+        return {k: v[0] for k, v in out.items()}
+
+    @staticmethod
+    def renderLightBatch(scenes, config: Config, planes=abi.LIGHT_NAMES, device: int = 0) -> dict:
+        """``renderLight`` for N scenes of one config: the same planes with a leading N.  This host form is a LOOP of
+        ``mcrt_render_light`` calls; the batched path is ``render_light_batch_device`` on resident ``DeviceScene`` handles (one
+        launch per kernel and 4096 frames)."""
+        names = abi.light_names(planes)
+        descs = [_as_desc(s) for s in scenes]
+        n = len(descs)
+        w, h = max(config.width, 0), max(config.height, 0)
+        out = {k: _empty_light(k, n, h, w) for k in names}
+        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
+            return out
+        c = config.to_c()
+        for i, d in enumerate(descs):
+            frame = abi.McrtLightPlanes(**{k: v[i].ctypes.data for k, v in out.items()})
+            check(load().mcrt_render_light(d.ptr, C.byref(c), C.byref(frame), int(device)))
+        return out
+
+    @staticmethod
     def lastBatchInfo() -> dict:
         """How the last batch call on this thread ran (mcrt_last_batch_info): ``batched_frames`` taken by the batched
         kernels and ``launch_sequences`` enqueued (1 when the whole batch went through them at once)."""
@@ -390,6 +420,15 @@ def _empty_reflection(name: str, n: int, h: int, w: int) -> np.ndarray:
     a = np.zeros((n, h, w) + ((comps,) if comps > 1 else ()), dtype)
     if name == "distance":
         a[...] = np.finfo(np.float32).max
+    return a
+
+
+def _empty_light(name: str, n: int, h: int, w: int) -> np.ndarray:
+    """One light plane for n frames, holding the constants of a pixel without a hit."""
+    dtype, comps = abi.LIGHT_FORMATS[name]
+    a = np.zeros((n, h, w) + ((comps,) if comps > 1 else ()), dtype)
+    if name != "direct":
+        a[...] = 1.0
     return a
 
 
@@ -657,6 +696,16 @@ class DeviceScene:
         planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
         check(load().mcrt_render_reflection_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
 
+    def render_light_device(self, config: Config, visibility_ptr: int = 0, occlusion_ptr: int = 0, direct_ptr: int = 0, stream: int = 0) -> None:
+        """The light planes of the frame into device memory (mcrt_render_light_device): width * height pixels per plane —
+        visibility and occlusion 4 bytes per pixel, direct 16 — any pointer may be 0, not all.  Asynchronous on ``stream``; uses
+        none of the handle's workspace, so it may run beside a render of the handle on another stream."""
+        if not (visibility_ptr or occlusion_ptr or direct_ptr):
+            raise ValueError("give at least one of visibility_ptr, occlusion_ptr, direct_ptr")
+        c = config.to_c()
+        planes = abi.McrtLightPlanes(visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
+        check(load().mcrt_render_light_device(self._h, C.byref(c), C.byref(planes), C.c_void_p(stream)))
+
     def pick(self, config: Config, xy) -> np.ndarray:
         """What is under the pixels ``xy`` ((n, 2) integers, x then y, inside the frame): a structured array of
         ``abi.SURFACE_DTYPE`` — mesh, face, tx, ty, t, point, normal, albedo — equal to the layers at those pixels
@@ -786,6 +835,29 @@ def render_reflection_batch_device(device_scenes: Sequence["DeviceScene"], confi
     c = config.to_c()
     planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
     check(load().mcrt_render_reflection_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+
+
+def render_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, visibility_ptr: int = 0, occlusion_ptr: int = 0,
+                              direct_ptr: int = 0, frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
+    """The light planes of N resident scenes of one config in one launch per kernel (mcrt_render_light_batch_device): frame i of
+    each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  A handle may be listed more than once.
+    Asynchronous on ``stream``."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    if not (visibility_ptr or occlusion_ptr or direct_ptr):
+        raise ValueError("give at least one of visibility_ptr, occlusion_ptr, direct_ptr")
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
+    if stride < px:
+        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    c = config.to_c()
+    planes = abi.McrtLightPlanes(visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
+    check(load().mcrt_render_light_batch_device(arr, n, C.byref(c), C.byref(planes), stride, C.c_void_p(stream)))
 
 
 def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, skin_stride_bytes: Optional[int] = None, stream: int = 0) -> None:

@@ -879,6 +879,38 @@ int mcrt_render_reflection(const mcrt_scene_desc* desc, const mcrt_config* cfg, 
     return rc;
 }
 
+// ---- light layers: the one-shot host form (render_enqueue.cpp: render_light_batch_device) ----------------------------------------
+int mcrt_render_light(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_light_planes* out, int device) {
+    if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
+    if (const int rc = check_light_config(cfg, out); rc != MCRT_OK) return rc;
+    if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    OneShotScenes set;
+    const mcrt_scene_desc* one[1] = {desc};
+    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
+    if (rc != MCRT_OK) return rc;
+    mcrt_scene* s0 = set.h[0];
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    // the widest elements first: each plane starts on a boundary of its own element size
+    const size_t direct_bytes = out->direct ? px * 16 : 0, vis_bytes = out->visibility ? px * 4 : 0, occ_bytes = out->occlusion ? px * 4 : 0;
+    hipError_t e = s0->frame.reserve(direct_bytes + vis_bytes + occ_bytes);
+    if (e != hipSuccess) return hip_fail(e, "light planes");
+    char* base = static_cast<char*>(s0->frame.ptr);
+    mcrt_light_planes d{};
+    d.direct = out->direct ? reinterpret_cast<float*>(base) : nullptr;
+    d.visibility = out->visibility ? reinterpret_cast<float*>(base + direct_bytes) : nullptr;
+    d.occlusion = out->occlusion ? reinterpret_cast<float*>(base + direct_bytes + vis_bytes) : nullptr;
+    rc = render_light_batch_device(set.h.data(), 1, cfg, &d, px, s0->main_stream);
+    set.download(out->direct, d.direct, direct_bytes, rc);
+    set.download(out->visibility, d.visibility, vis_bytes, rc);
+    set.download(out->occlusion, d.occlusion, occ_bytes, rc);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "light render");
+    }
+    return rc;
+}
+
 int mcrt_scene_floor(const mcrt_scene_desc* desc, float* y) {
     if (!desc || !y) return fail(MCRT_ERR_INVALID, "NULL argument");
     bool any = false;

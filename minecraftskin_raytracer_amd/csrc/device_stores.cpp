@@ -86,6 +86,7 @@ struct SeedTables {
     int enabled = -1;                 // the knob, read at the first acquire
 
     const uint32_t* acquire(int device);
+    const uint32_t* acquire_built(int device);  // only where the table exists: builds nothing
     void release(int device);
     void free_unused();
 };
@@ -108,6 +109,14 @@ const uint32_t* SeedTables::acquire(int device) {
         }
         t.ptr = p;
     }
+    ++t.users;
+    return t.ptr;
+}
+const uint32_t* SeedTables::acquire_built(int device) {
+    std::lock_guard<std::mutex> lock(g_seed_mutex);
+    if (device < 0 || static_cast<size_t>(device) >= by_device.size()) return nullptr;
+    Table& t = by_device[static_cast<size_t>(device)];
+    if (!t.ptr) return nullptr;
     ++t.users;
     return t.ptr;
 }
@@ -147,6 +156,12 @@ void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream) {
     s->full_table_tried = true;
     s->seed_table_full = g_full_tables.acquire(s->device);
     s->holds_full_table = s->seed_table_full != nullptr;
+}
+void share_full_seed_table(mcrt_scene* s) {
+    if (s->holds_full_table) return;
+    s->seed_table_full = g_full_tables.acquire_built(s->device);
+    s->holds_full_table = s->seed_table_full != nullptr;
+    if (s->holds_full_table) s->full_table_tried = true;
 }
 
 namespace {

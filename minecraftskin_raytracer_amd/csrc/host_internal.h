@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <string>
@@ -188,6 +189,17 @@ inline int bad_background() { return fail(MCRT_ERR_INVALID, "background must be 
 inline bool no_plane(const mcrt_layers* l) { return !l->depth && !l->normal && !l->albedo && !l->id; }
 inline bool no_plane(const mcrt_ground* g) { return !g->visibility && !g->distance && !g->matte; }
 inline bool no_plane(const mcrt_reflection* r) { return !r->rgba && !r->rgba8 && !r->distance; }
+inline bool no_plane(const mcrt_light_planes* l) { return !l->visibility && !l->occlusion && !l->direct; }
+// what a light pass refuses of a config (both entry points, before any device work): the truncated engine yields 227 draws — 113
+// light samples, 113 AO samples of two draws each — and computeAO divides by ao_samples
+inline int check_light_config(const mcrt_config* c, const mcrt_light_planes* out) {
+    if (c->soft_shadows && c->shadow_samples > mcrt::kLightMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a light pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
+    if (out->occlusion && (c->ao_samples < 1 || c->ao_samples > mcrt::kLightMaxSamples))
+        return fail(MCRT_ERR_INVALID, "the occlusion plane takes 1 to 113 ao_samples (the truncated engine's 227 draws, two per sample)");
+    if (out->occlusion && !std::isfinite(c->ao_radius)) return fail(MCRT_ERR_INVALID, "ao_radius must be finite");
+    return MCRT_OK;
+}
 
 // what the calling thread's last mcrt_render_batch* call did (mcrt_last_batch_info; thread-local in api.cpp, like the error text)
 struct BatchInfo {
@@ -204,6 +216,9 @@ bool device_shared(const mcrt_scene* s);  // another handle's frame is in flight
 const uint32_t* acquire_seed_table(int device);
 // the first ambient-occlusion render of a shell takes the device's table for every 32-bit seed (never built while `stream` is capturing)
 void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream);
+// a shell that does not hold the device's table for every seed takes it where it is ALREADY built (a light pass's occlusion
+// plane: it never builds the table); no launch, no wait
+void share_full_seed_table(mcrt_scene* s);
 // the device's background plate and draw plate for the frame prepared as p[0] — each or nullptr, both kinds under one sighting
 // rule in this one call — into bg_plate and draw_plate of p[0..n) (the lanes of one render read the same plates)
 void acquire_plates(mcrt_scene* s, mcrt::RenderParams* p, int n, bool capturing, bool count_sighting);
@@ -251,6 +266,7 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
                                hipStream_t stream);
 int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_reflection* d_out,
                                    size_t stride, hipStream_t stream);
+int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes* d_out, size_t stride, hipStream_t stream);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 

@@ -311,6 +311,40 @@ int reflection_batch_view(ReflectionFrame* frames, const int* views, int n);
 // dynamic LDS of a launch: the frame's scene tables, then the block's area (hit records, masks, counts and sample positions)
 size_t reflection_lds_bytes(const ReflectionFrame& f, const ReflectionShape& shape);
 
+// ---- light layers (mcrt_render_light_device & co): what the light does at the geometry layers' primary hit — the visibility
+// term of shade() (computeSoftShadow with the depth-0 seed, or shade()'s own isInShadow test), computeAO, and shade() with that
+// visibility.  Reads the scene blob and the device's seed tables, like a ground pass.
+// One frame of a light pass: its scene and its planes (any may be NULL, not all), width * height pixels each
+struct ShadeFrame {
+    const uint8_t* scene;
+    float* visibility;                // 1 float per pixel: the shadow factor of the hit; 1.0f at a miss
+    float* occlusion;                 // 1 float per pixel: computeAO; 1.0f at a miss
+    float* direct;                    // 4 floats per pixel: shade() with that visibility, alpha = the texel's; zero at a miss
+    const uint32_t* seed_table;       // the handle's window table (RenderParams::seed_table), or NULL: the recurrence
+    const uint32_t* seed_table_full;  // the device's table of all seeds where a render has built it, or NULL: the recurrence
+    int lds_alpha_words;              // scene tables staged in LDS, as LayersFrame's
+    int lds_face_entries;
+};
+constexpr int kLightMaxSamples = 113;  // shadow and AO samples: the truncated engine's 227 draws, two per sample
+// what the frames of one launch share
+struct ShadeShape {
+    LayersShape tiles;     // the frame's size and its tile grid, as a layers pass cuts it
+    int samples;           // S: shadow_samples when soft_shadows && shadow_samples > 1, else 1
+    int pass;              // undecided hits whose S sample positions fit the block's LDS area at once
+    int ao_samples;        // A (read by `occlusion` alone)
+    float ao_radius;
+    int bundle_decisions;  // as RenderParams'
+    int inside_fast;
+};
+// false when the frame holds more units than the kernels index (2^31)
+bool make_shade_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, ShadeShape& shape);
+// fills f.lds_* and returns the kernel variant by the layers' rule
+int shade_view(ShadeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
+int shade_batch_view(ShadeFrame* frames, const int* views, int n);
+// dynamic LDS of the two launches: the frame's scene tables, then the block's area
+size_t shade_lds_bytes(const ShadeFrame& f, const ShadeShape& shape);  // hit records, masks, counts and sample positions
+size_t occlusion_lds_bytes(const ShadeFrame& f);                         // hit records, masks, the traced list and the values
+
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): a repaintable handle's blob holds the full mesh table of
 // its skin kind, so texel i of its pool is cut from one fixed pixel of the skin image.  One workgroup per scene rewrites what
 // a skin decides of the blob: the float4 texel pool (u8 / 255.0f through a table the HOST formed), the 2-bit alpha predicates
@@ -359,7 +393,7 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
-// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, skin repaints ========
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, skin repaints ========
 hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's LDS tables
@@ -374,6 +408,12 @@ hipError_t launch_reflection(const ReflectionFrame& f, const ReflectionShape& sh
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's reflection_lds_bytes
 hipError_t launch_reflection_batch(const ReflectionFrame* d_table, int n_frames, const ReflectionShape& shape, int view, size_t max_dyn, hipStream_t stream);
+// `shade` where f.visibility or f.direct, then `occlusion` where f.occlusion
+hipError_t launch_light(const ShadeFrame& f, const ShadeShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; which kernels run (the
+// frames of a call share their planes) and the largest frame's shade_lds_bytes / occlusion_lds_bytes
+hipError_t launch_light_batch(const ShadeFrame* d_table, int n_frames, const ShadeShape& shape, int view, bool shade, size_t shade_dyn, bool occlusion,
+                              size_t occlusion_dyn, hipStream_t stream);
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);

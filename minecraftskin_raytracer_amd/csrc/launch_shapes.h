@@ -52,6 +52,11 @@ constexpr int kGroundFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // ground: cand
 constexpr int kReflectPosBytes = 8 * 1024;  // reflection: LDS for the sample positions of the undecided level-1 hits of one pass
 // reflection: per lane a hit record of four float4 (point, normal, texel colour, ray), candidate and inside masks, lit counts, the undecided list
 constexpr int kReflectFixedBytes = kBlock * (64 + 8 + 8 + 4 + 4);
+constexpr int kShadePosBytes = 8 * 1024;  // light layers, `shade`: LDS for the sample positions of the undecided hits of one pass
+// `shade`: per lane a hit record of three float4 (point, normal, texel colour), candidate and inside masks, lit counts, the undecided list
+constexpr int kShadeFixedBytes = kBlock * (48 + 8 + 8 + 4 + 4);
+// `occlusion`: per lane a hit record of two float4 (point, normal), the candidate mask, the traced list, the value
+constexpr int kOcclusionFixedBytes = kBlock * (32 + 8 + 4 + 4);
 
 // Workgroups per frame of a batched launch.  Every kernel strides over its frame's device-side work, so the grid only
 // shapes the schedule: a batch aims at kBatchTarget workgroups per launch (8 per CU of the 256 — twice what the largest

@@ -1,5 +1,5 @@
 // pass_kernels.hip — the stand-alone passes over a resident scene (not stages of a render): geometry layers and pixel
-// picks, the ground shadow, the ground reflection, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
+// picks, the ground shadow, the ground reflection, the light layers, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
 // and nothing else: no workspace, no counters.
 #include "kernel_common.h"
 
@@ -803,6 +803,331 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void reflection_batch_kernel(
     reflection_body<kView>(*(const ReflectionFrame*)(table + blockIdx.y), sh);
 }
 
+// ---------------------------------------------------------------------------------------------
+// light layers (kernels.h: ShadeFrame): what the light does on the figure itself, at the geometry layers' primary hit — the
+// visibility term shade() multiplies diffuse and specular by (computeSoftShadow at depth 0, or shade()'s own isInShadow test),
+// computeAO, and shade() before ambient occlusion and the bounces are folded in.  Two kernels, so that the AO loop's any-hit
+// test and the bundle classification do not share a register budget.  No workspace.
+// `shade` (visibility and direct), a workgroup per 256 pixels of a screen tile (grid-stride), in phases handed over through LDS:
+//   1 lane / mesh (every wave)   the geometry layers' tile mask: a tile nothing can touch gets the miss constants and forms no ray
+//   1 lane / pixel               ray, closest hit among the tile's meshes; the hits are packed onto the block's first lanes as
+//                                records in LDS (point, normal, texel colour)
+//   1 lane / hit                 the whole-bundle decision (rt::bundle_classify) from the hit's shadow origin; the undecided
+//                                are packed again
+//   1 lane / undecided hit       truncated mt19937 (mt[397] from the seed table) at depth 0 → the S disk sample positions in LDS
+//   1 lane / (undecided hit, light sample)   exact any-hit test on the candidates → lit count by ballot
+//   1 lane / hit                 visibility = lit / S (one ray in the hard modes), shade; both return through LDS
+//   1 lane / pixel               the planes: 16 bytes per store where rows and alignment allow
+// `occlusion`: the same culling, ray and packing, then the steps of `ao` (render_kernels.hip):
+//   1 lane / hit                 the meshes a ray of its hemisphere can meet within the radius (rt::hemisphere_candidates); hits
+//                                without one are done at 1.0, the rest are packed again
+//   1 lane / packed hit          truncated mt19937 (mt[397] from the device's table of all seeds where a render has built it,
+//                                else the recurrence), A cosine-weighted directions, the any-hit test, the count in a register
+// ---------------------------------------------------------------------------------------------
+// the unit's tile, and this lane's pixel in it
+struct UnitPixel {
+    TileGeom tg;
+    bool valid;
+    int px, py;
+    size_t idx;
+};
+__device__ __forceinline__ bool unit_pixel(const LayersShape& tiles, const int unit, const int tid, UnitPixel& up) {
+    const mcrt_config& cfg = tiles.cfg;
+    const int tile = unit / tiles.parts, part = unit - tile * tiles.parts;
+    const int tyi = tile / tiles.tiles_x, txi = tile - tyi * tiles.tiles_x;
+    TileGeom& tg = up.tg;
+    tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+    tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+    tg.owned_row = tyi, tg.frame_tile = tile;
+    const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+    const unsigned p0 = static_cast<unsigned>(part) * kBlock;
+    if (p0 >= npix) return false;  // a clipped edge tile holds fewer units
+    const unsigned pix = p0 + static_cast<unsigned>(tid);
+    up.valid = pix < npix;
+    const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(up.valid ? pix : 0u);
+    up.py = tg.y + static_cast<int>(uly), up.px = tg.x + static_cast<int>((up.valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+    up.idx = static_cast<size_t>(up.py) * static_cast<size_t>(cfg.width) + static_cast<size_t>(up.px);
+    return true;
+}
+// the pixel-centre ray's closest hit among the meshes of mesh_mask
+template <class SV>
+__device__ __forceinline__ Hit pixel_hit(const SceneView& scg, const SV& sc, const mcrt_config& cfg, const float aspect, const int px, const int py,
+                                         const unsigned long long mesh_mask) {
+    const float u = (static_cast<float>(px) + 0.5f) / static_cast<float>(cfg.width);
+    const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
+    return hit_scene(sc, camera_ray(scg, u, v, aspect), mesh_mask);
+}
+template <int kView>
+__device__ __forceinline__ void shade_body(const ShadeFrame& __restrict__ f, const ShadeShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][hit records: 3 planes of float4][candidate masks][inside masks][lit counts][undecided list][positions: pass x S x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.tiles.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const V3 lpos = ld3(scg.hdr->light_pos);
+    const V3 cam = ld3(scg.hdr->cam_pos);  // the origin of every pixel-centre ray (rt::camera_ray)
+    const float lradius = scg.hdr->light_radius;
+    const int S = sh.samples;
+    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
+    const bool raw_normal = S > 1;  // computeSoftShadow takes the hit's normal as it is; shade()'s own test normalises it (shading.cpp:76-80)
+    const float R = soft ? lradius : 0.0f;
+    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per hit
+    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
+    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: hit point; 1: normal; 2: texel colour — then the hit's colour
+    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(s_rec + 3 * kBlock);
+    unsigned long long* s_ins = s_cand + kBlock;
+    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_ins + kBlock);  // lit counts — then the hit's visibility, bit-cast
+    uint32_t* s_und = s_lit + kBlock;
+    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    const bool quads_vis = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
+    const bool vec_direct = (reinterpret_cast<uintptr_t>(f.direct) & 15u) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * sh.tiles.parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        UnitPixel up;
+        if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
+        const unsigned long long mask = layers_tile_mask(scg, cfg, up.tg, aspect, lane);  // the same in every wave of the workgroup
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        float vis = 1.0f;
+        C4 col{0.0f, 0.0f, 0.0f, 0.0f};
+        if (mask != 0ull) {  // uniform
+            // ---- a lane per pixel: the ray and its closest hit
+            bool is_hit = false;
+            Hit h;
+            if (up.valid) {
+                h = pixel_hit(scg, sc, cfg, aspect, up.px, up.py, mask);
+                is_hit = h.hit;
+            }
+            int n_hits = 0;
+            const int rank = block_rank(is_hit, s_wcnt, n_hits);
+            if (is_hit) {
+                s_rec[rank] = make_float4(h.p.x, h.p.y, h.p.z, 0.0f);
+                s_rec[kBlock + rank] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
+                s_rec[2 * kBlock + rank] = make_float4(h.tex.r, h.tex.g, h.tex.b, h.tex.a);
+            }
+            if (n_hits) {  // uniform
+                __syncthreads();
+                // ---- a lane per hit: the whole-bundle decision of its shadow rays
+                const bool mine = tid < n_hits;
+                Hit hit;
+                hit.hit = true;
+                bool undecided = false;
+                uint32_t lit = 0u;
+                if (mine) {
+                    const float4 a = s_rec[tid], b = s_rec[kBlock + tid], c = s_rec[2 * kBlock + tid];
+                    hit.p = mk(a.x, a.y, a.z), hit.n = mk(b.x, b.y, b.z), hit.tex = C4{c.x, c.y, c.z, c.w};
+                    const V3 O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
+                    unsigned long long cand;
+                    const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
+                    undecided = known < 0;
+                    s_cand[tid] = cand;
+                    s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
+                    if (!undecided) lit = static_cast<uint32_t>(known);
+                }
+                s_lit[tid] = 0u;
+                int total = 0;
+                const int urank = block_rank(undecided, s_wcnt, total);
+                if (undecided) s_und[urank] = static_cast<uint32_t>(tid);
+                const uint32_t n_und = static_cast<uint32_t>(total);
+                if (n_und) __syncthreads();  // uniform
+                for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
+                    const uint32_t nu = min(pass, n_und - u0);
+                    if (u0) __syncthreads();  // the previous pass's rays have read the positions
+                    // ---- a lane per undecided hit: its mt19937 stream at depth 0 and the S disk sample positions
+                    if (soft && static_cast<uint32_t>(tid) < nu) {
+                        const float4 a = s_rec[s_und[u0 + tid]];
+                        disk_sample_positions(scg, f.seed_table, nullptr, mk(a.x, a.y, a.z), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
+                    }
+                    __syncthreads();
+                    // ---- a lane per (undecided hit, light sample); every lane of a wave runs the same number of turns (ballot inside)
+                    const uint32_t n_rays = nu * pairs;
+                    for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
+                        const uint32_t q = q0 + static_cast<uint32_t>(lane);
+                        bool visible = false;
+                        uint32_t k = 0;
+                        if (q < n_rays) {
+                            k = s_und[u0 + q / pairs];
+                            const float4 a = s_rec[k], b = s_rec[kBlock + k];
+                            V3 Nk = mk(b.x, b.y, b.z);
+                            if (!raw_normal) Nk = normalize(Nk);
+                            const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
+                            visible = !in_shadow_masked(sc, mk(a.x, a.y, a.z), Nk, target, s_cand[k], s_ins[k]);
+                        }
+                        if (pow2) {
+                            const unsigned long long bal = __ballot(visible);
+                            if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
+                                const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
+                                s_lit[k] = static_cast<uint32_t>(__popcll(grp));
+                            }
+                        } else if (visible) {
+                            atomicAdd(&s_lit[k], 1u);
+                        }
+                    }
+                }
+                if (n_und) __syncthreads();  // the counts are complete
+                if (undecided) lit = s_lit[tid];
+                // ---- a lane per hit: the visibility term and shade (raytracer.cpp:107-117)
+                if (mine) {
+                    const float v = soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    const C4 c = shade(scg, hit, normalize(cam - hit.p), v);
+                    s_lit[tid] = __float_as_uint(v);  // (entry and record tid are this lane's alone by now)
+                    s_rec[2 * kBlock + tid] = make_float4(c.r, c.g, c.b, c.a);
+                }
+                __syncthreads();
+                if (is_hit) {
+                    const float4 c = s_rec[2 * kBlock + rank];
+                    vis = __uint_as_float(s_lit[rank]);
+                    col = C4{c.x, c.y, c.z, c.w};
+                }
+                // (the next unit writes its records behind the two barriers of its block_rank)
+            }
+        }
+        // ---- a lane per pixel: the planes
+        if (f.visibility) store_plane(f.visibility, quads_vis, up.valid, lane, up.idx, vis);
+        if (f.direct && up.valid) {
+            if (vec_direct) {
+                reinterpret_cast<float4*>(f.direct)[up.idx] = make_float4(col.r, col.g, col.b, col.a);
+            } else {
+                float* o = f.direct + up.idx * 4;
+                o[0] = col.r, o[1] = col.g, o[2] = col.b, o[3] = col.a;
+            }
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void shade_kernel(const ShadeFrame f, const ShadeShape sh) {
+    shade_body<kView>(f, sh);
+}
+using ShadeTable = const __attribute__((address_space(4))) ShadeFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void shade_batch_kernel(ShadeTable table, const ShadeShape sh) {
+    shade_body<kView>(*(const ShadeFrame*)(table + blockIdx.y), sh);
+}
+template <int kView>
+__device__ __forceinline__ void occlusion_body(const ShadeFrame& __restrict__ f, const ShadeShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][hit records: 2 planes of float4][candidate masks][traced list][values]
+    __shared__ int s_wcnt[kBlock / 64];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.tiles.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const int A = sh.ao_samples;
+    const float radius = sh.ao_radius;
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: hit point; 1: normal
+    unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(s_rec + 2 * kBlock);
+    uint32_t* s_list = reinterpret_cast<uint32_t*>(s_mask + kBlock);
+    float* s_val = reinterpret_cast<float*>(s_list + kBlock);
+    const bool quads = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.occlusion) & 15u) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * sh.tiles.parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        UnitPixel up;
+        if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
+        const unsigned long long mask = layers_tile_mask(scg, cfg, up.tg, aspect, lane);  // the same in every wave of the workgroup
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        float occ = 1.0f;
+        if (mask != 0ull) {  // uniform
+            // ---- a lane per pixel: the ray and its closest hit
+            bool is_hit = false;
+            Hit h;
+            if (up.valid) {
+                h = pixel_hit(scg, sc, cfg, aspect, up.px, up.py, mask);
+                is_hit = h.hit;
+            }
+            int n_hits = 0;
+            const int rank = block_rank(is_hit, s_wcnt, n_hits);
+            if (is_hit) {
+                s_rec[rank] = make_float4(h.p.x, h.p.y, h.p.z, 0.0f);
+                s_rec[kBlock + rank] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
+            }
+            if (n_hits) {  // uniform
+                __syncthreads();
+                // ---- a lane per hit: the meshes a ray of its hemisphere can meet (`ao`, step 1)
+                bool traced = false;
+                if (tid < n_hits) {
+                    const float4 a = s_rec[tid], b = s_rec[kBlock + tid];
+                    const V3 P = mk(a.x, a.y, a.z), N = normalize(mk(b.x, b.y, b.z));
+                    const unsigned long long cand = hemisphere_candidates<kPosed>(scg, P + N * 1e-3f, N, radius);
+                    s_mask[tid] = cand;
+                    traced = cand != 0ull || scg.n_meshes > 64;  // meshes beyond the mask are tested per ray
+                    if (!traced) s_val[tid] = 1.0f;  // 0 occluded
+                }
+                int total = 0;
+                const int trank = block_rank(traced, s_wcnt, total);
+                if (traced) s_list[trank] = static_cast<uint32_t>(tid);
+                __syncthreads();
+                // ---- a lane per traced hit: its mt19937 stream, the A directions and their any-hit tests (`ao`, step 3)
+                if (tid < total) {
+                    const uint32_t k = s_list[tid];
+                    const float4 a = s_rec[k], b = s_rec[kBlock + k];
+                    const V3 P = mk(a.x, a.y, a.z), N = normalize(mk(b.x, b.y, b.z));
+                    const V3 T = (__builtin_fabsf(N.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), N)) : normalize(cross(mk(0, 1, 0), N));
+                    const V3 B = cross(N, T);
+                    const unsigned long long cand = s_mask[k];
+                    const V3 O = P + N * 1e-3f;
+                    const unsigned long long inside = sh.inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the hit starts there
+                    MtShort rng;
+                    const uint32_t seed = ao_seed(P);
+                    if (f.seed_table_full)
+                        rng.seed_known(seed, f.seed_table_full[seed]);  // mt[397] of this seed: one load instead of the 397-step recurrence
+                    else
+                        rng.seed(seed);
+                    uint32_t occluded = 0;
+                    for (int i = 0; i < A; ++i) {
+                        const float r1 = rng.uniform();
+                        const float r2 = rng.uniform();
+                        const float sinT = sqrt_pos(1.0f - r1);
+                        const float cosT = sqrt_pos(r1);
+                        float sn, cs;
+                        mcrt_sincosf(kTwoPi * r2, &sn, &cs);
+                        const V3 local = mk(sinT * cs, cosT, sinT * sn);
+                        const V3 world = normalize(T * local.x + N * local.y + B * local.z);
+                        if (any_hit_masked(sc, Ray{O, world}, radius, cand, inside)) ++occluded;
+                    }
+                    s_val[k] = 1.0f - static_cast<float>(occluded) / static_cast<float>(A);  // raytracer.cpp:77
+                }
+                __syncthreads();
+                if (is_hit) occ = s_val[rank];
+                // (the next unit writes its records behind the two barriers of its block_rank)
+            }
+        }
+        // ---- a lane per pixel: the plane
+        store_plane(f.occlusion, quads, up.valid, lane, up.idx, occ);
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void occlusion_kernel(const ShadeFrame f, const ShadeShape sh) {
+    occlusion_body<kView>(f, sh);
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void occlusion_batch_kernel(ShadeTable table, const ShadeShape sh) {
+    occlusion_body<kView>(*(const ShadeFrame*)(table + blockIdx.y), sh);
+}
+
 // ---- host-side launchers (the shapes and LDS sizes they take: render_plan.cpp) ----------------------
 // One launch of a tile pass (layers, ground) over the tile grid `tiles`.  arg: the frame, or the device table of n_frames
 // frames (blockIdx.y = frame); kernel_of(view tag): the kernel of that variant; dyn: its dynamic LDS, hbm_dyn: the HBM
@@ -841,6 +1166,31 @@ hipError_t launch_reflection_batch(const ReflectionFrame* d_table, int n_frames,
     if (shape.max_bounces > kReflectMaxBounces) return hipErrorInvalidValue;
     return launch_tile_pass(ReflectionTable(d_table), n_frames, shape, shape.tiles, view, max_dyn, max_dyn, stream,
                             [](auto v) { return reflection_batch_kernel<decltype(v)::value>; });
+}
+// ---- light layers (kernels.h): `shade` when visibility or direct is asked for, `occlusion` when that plane is; the HBM variants
+// keep the block's area in dynamic LDS
+hipError_t launch_light(const ShadeFrame& f, const ShadeShape& shape, int view, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    if (f.visibility || f.direct) {
+        const size_t dyn = shade_lds_bytes(f, shape);
+        e = launch_tile_pass(f, 1, shape, shape.tiles, view, dyn, dyn, stream, [](auto v) { return shade_kernel<decltype(v)::value>; });
+    }
+    if (e == hipSuccess && f.occlusion) {
+        const size_t dyn = occlusion_lds_bytes(f);
+        e = launch_tile_pass(f, 1, shape, shape.tiles, view, dyn, dyn, stream, [](auto v) { return occlusion_kernel<decltype(v)::value>; });
+    }
+    return e;
+}
+hipError_t launch_light_batch(const ShadeFrame* d_table, int n_frames, const ShadeShape& shape, int view, bool shade, size_t shade_dyn, bool occlusion,
+                              size_t occlusion_dyn, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    if (shade)
+        e = launch_tile_pass(ShadeTable(d_table), n_frames, shape, shape.tiles, view, shade_dyn, shade_dyn, stream,
+                             [](auto v) { return shade_batch_kernel<decltype(v)::value>; });
+    if (e == hipSuccess && occlusion)
+        e = launch_tile_pass(ShadeTable(d_table), n_frames, shape, shape.tiles, view, occlusion_dyn, occlusion_dyn, stream,
+                             [](auto v) { return occlusion_batch_kernel<decltype(v)::value>; });
+    return e;
 }
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;

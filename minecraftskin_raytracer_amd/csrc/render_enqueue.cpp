@@ -451,6 +451,18 @@ int reflection_frame_of(const mcrt_scene* s, const mcrt_reflection& out, float g
     f.ground_y = ground_y;
     return reflection_view(f, s->alpha_words, s->n_meshes, s->posed);
 }
+// and for a light pass (mcrt_render_light_device & co), which reads both seed tables
+int shade_frame_of(const mcrt_scene* s, const mcrt_light_planes& out, size_t index, size_t stride, ShadeFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.visibility = out.visibility ? out.visibility + off : nullptr;
+    f.occlusion = out.occlusion ? out.occlusion + off : nullptr;
+    f.direct = out.direct ? out.direct + off * 4 : nullptr;
+    f.seed_table = s->seed_table;
+    f.seed_table_full = s->seed_table_full;
+    return shade_view(f, s->alpha_words, s->n_meshes, s->posed);
+}
 
 // What the layers and the ground entry points check alike, before any device work (only the last check looks inside the
 // handles, at their device index).  run = false with MCRT_OK: zero tiles, nothing is written.
@@ -781,6 +793,37 @@ int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_
         [&](const ReflectionFrame* d_table, int m) { return launch_reflection_batch(d_table, m, shape, view, dyn, stream); });
 }
 
+// ---- light layers (mcrt_render_light_device & co): the ground pass's host path with two kernels — `shade` for visibility and
+// direct, `occlusion` for that plane — over one frame record.  The occlusion kernel seeds from the device's table of all seeds
+// only where an ambient-occlusion render has built it: the pass never builds the 16 GiB table itself.
+int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes* d_out, size_t stride, hipStream_t stream) {
+    // argument checks, before any device work
+    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
+    if (cfg && d_out)
+        if (const int rc = check_light_config(cfg, d_out); rc != MCRT_OK) return rc;
+    bool run;
+    int device = 0;
+    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
+    ShadeShape shape;
+    if (!make_shade_shape(*cfg, decisions, inside_fast, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(device));
+    const bool shade = d_out->visibility || d_out->direct, occlusion = d_out->occlusion != nullptr;
+    std::vector<ShadeFrame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        if (occlusion) share_full_seed_table(scenes[i]);
+        views[static_cast<size_t>(i)] = shade_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
+    }
+    const int view = shade_batch_view(frames.data(), views.data(), n);
+    size_t shade_dyn = 0, occlusion_dyn = 0;
+    for (const ShadeFrame& f : frames) shade_dyn = std::max(shade_dyn, shade_lds_bytes(f, shape)), occlusion_dyn = std::max(occlusion_dyn, occlusion_lds_bytes(f));
+    return launch_pass(
+        device, frames, stream, "light launches", [&](const ShadeFrame& f) { return launch_light(f, shape, view, stream); },
+        [&](const ShadeFrame* d_table, int m) { return launch_light_batch(d_table, m, shape, view, shade, shade_dyn, occlusion, occlusion_dyn, stream); });
+}
+
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): one workgroup per handle rewrites the texel pool, the alpha
 // predicates and the MESH_OPAQUE bits of its blob.  The blob is what the handle's renders read, so a repaint sits in the
 // handle's event chain like a render (join_handle_chain / extend_handle_chain, the halves begin_ / end_handle_render use).
@@ -967,6 +1010,18 @@ int mcrt_render_reflection_device(mcrt_scene* s, const mcrt_config* cfg, float g
 int mcrt_render_reflection_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y,
                                         const mcrt_reflection* d_out, size_t frame_stride_pixels, void* stream) {
     return render_reflection_batch_device(scenes, n_frames, cfg, ground_y, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_light_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_light_planes* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = cfg ? static_cast<size_t>(cfg->width > 0 ? cfg->width : 0) * static_cast<size_t>(cfg->height > 0 ? cfg->height : 0) : 0;
+    return render_light_batch_device(one, 1, cfg, d_out, px, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_light_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_light_planes* d_out,
+                                   size_t frame_stride_pixels, void* stream) {
+    return render_light_batch_device(scenes, n_frames, cfg, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

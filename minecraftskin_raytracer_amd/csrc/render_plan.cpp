@@ -1,5 +1,5 @@
 // render_plan.cpp — host-side planning of the launches: shards, the workspace and its batches, grids, plates, batches of
-// frames, and the shapes, variants and LDS sizes of the layers, ground and skin passes.  Pure host code: what it decides
+// frames, and the shapes, variants and LDS sizes of the layers, ground, reflection, light and skin passes.  Pure host code: what it decides
 // reaches the kernels through RenderParams and the other structs of kernels.h; the constants it shares with them are in
 // launch_shapes.h.
 #include "kernels.h"
@@ -305,7 +305,7 @@ LdsFit lds_fit(uint32_t alpha_words, uint32_t n_meshes, bool posed) {
     if (!fits) return LdsFit{0, 0, kViewHbm};
     return LdsFit{static_cast<int>(n_meshes * 6), static_cast<int>(alpha_words), posed ? kViewLds : kViewLdsUnposed};
 }
-template <class Frame>  // LayersFrame, GroundFrame or ReflectionFrame
+template <class Frame>  // LayersFrame, GroundFrame, ReflectionFrame or ShadeFrame
 static int view_of_frame(Frame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
     const LdsFit fit = lds_fit(alpha_words, n_meshes, posed);
     f.lds_alpha_words = fit.alpha_words, f.lds_face_entries = fit.face_entries;
@@ -375,6 +375,32 @@ int reflection_batch_view(ReflectionFrame* frames, const int* views, int n) { re
 size_t reflection_lds_bytes(const ReflectionFrame& f, const ReflectionShape& shape) {
     const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
     return tables + kReflectFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
+}
+// ---- light layers (kernels.h) -----------------------------------------------------------------------
+bool make_shade_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, ShadeShape& shape) {
+    std::memset(&shape, 0, sizeof shape);
+    if (!make_layers_shape(cfg, shape.tiles)) return false;
+    shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
+    const int fit = kShadePosBytes / (12 * shape.samples);  // 8 samples: 85 hits per pass; 113 samples: 6
+    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.ao_samples = cfg.ao_samples;
+    shape.ao_radius = cfg.ao_radius;
+    shape.bundle_decisions = bundle_decisions ? 1 : 0;
+    shape.inside_fast = inside_fast ? 1 : 0;
+    return true;
+}
+int shade_view(ShadeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
+int shade_batch_view(ShadeFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
+// The 12-mesh character (72 face entries, 204 alpha words: 3120 bytes of tables) at 8 samples: `shade` 3120 + 18432 + 85 * 96 =
+// 29712 bytes, `occlusion` 3120 + 12288 = 15408 bytes: four workgroups of either in a CU's 160 KiB.  The largest tables the LDS
+// views take (28 KiB) make 55296 and 40960 bytes, below the 64 KiB a workgroup may ask for.
+size_t shade_lds_bytes(const ShadeFrame& f, const ShadeShape& shape) {
+    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    return tables + kShadeFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
+}
+size_t occlusion_lds_bytes(const ShadeFrame& f) {
+    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    return tables + kOcclusionFixedBytes;
 }
 // ---- skins on resident scenes (kernels.h) -----------------------------------------------------------
 size_t skin_tables_bytes(int n_texels) { return 256 * sizeof(float) + static_cast<size_t>(n_texels) * sizeof(uint16_t); }

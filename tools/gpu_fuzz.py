@@ -9,6 +9,11 @@ The scene-only passes (tests/pass_fuzz_cases.py), every plane of a pass, bit for
   layers       renderLayers on make_pass_case, odd seeds wide: depth, normal, albedo, and the texel the id plane names
   long-shadow  renderGround and renderReflection on make_long_shadow_case: ground points 200 ... 30 000 out along a shadow
   far-plane    renderGround and renderReflection on make_far_plane_case: planes 10 ... 10 000 scene heights down
+The light layers (tests/light_checker.py), visibility, occlusion and direct bit for bit:
+  light        render_light_device on light_checker.sweep_case(seed): make_pass_case, make_wide_pass_case and make_bundle_case in
+               turn, AO settings drawn per case (1 ... 113 samples, a radius of 0.01 ... 10 scene heights); every fourth case into
+               planes 1 or 2 floats off their allocation, every other case also twice through the batched kernels; the summary
+               records the hits, penumbra hits and partly occluded hits compared
 The batched entries (tests/batch_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_batch_fuzz.py):
   batch        render_batch_device on make_beauty_batch(seed): 1 ... 16 frames of mixed scenes under one config, fresh and stale
                tile seeds, a lead and a stride gap; every third seed also through TileRenderer.renderBatch
@@ -30,7 +35,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -92,6 +97,43 @@ def batch_sweep():
         d, p, r, l = (int(x) for x in np.atleast_1d(total))
         print(f"fuzz pass-batch: {count} batches from seed {first}: {bad} mismatching batch(es); {frames} ground frames; the oracle holds "
               f"{d} dark, {p} penumbra, {r} reflected and {l} layer-hit pixels")
+    pool.terminate()
+    sys.exit(1 if bad else 0)
+
+
+def light_sweep():
+    import light_checker as LC, test_gpu_light_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    # the oracle's planes are made ahead of the device by worker processes (forked before the device is first used; they never
+    # use it), in the order of the seeds
+    import multiprocessing
+
+    workers = max(1, min(14, len(os.sched_getaffinity(0)) - 2, int(os.environ.get("OMP_NUM_THREADS", "16")) - 2))
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    ahead = pool.imap(LC.worker_sweep_expectation, range(first, first + count))
+    bad = 0
+    total = np.zeros(5, np.int64)
+    t0 = time.time()
+    for k, seed in enumerate(range(first, first + count)):
+        case = LC.sweep_case(seed)
+        exp = next(ahead)
+        LC.assert_miss_constants(exp)
+        try:
+            lines = T.run_case(M, case, exp, T.lead_of(k), twice=k % 2 == 0)
+        except McrtError as e:
+            print(f"HIP ERROR {case[2]}: {e}", flush=True)
+            print(f"fuzz light: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
+            pool.terminate()
+            sys.exit(2)
+        total += np.asarray(LC.counts(exp))
+        if lines:
+            bad += 1
+            print("\n".join("MISMATCH " + l for l in lines[:20]), flush=True)
+        if k % 100 == 99:
+            print(f"... {k + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
+    print(f"fuzz light: {count} cases from seed {first}: {bad} mismatch(es); the oracle holds {int(total[0])} hits, {int(total[1])} of them dark and "
+          f"{int(total[2])} in the penumbra, and {int(total[3])} partly occluded hits ({int(total[4])} fully occluded)")
     pool.terminate()
     sys.exit(1 if bad else 0)
 
@@ -162,6 +204,8 @@ if mode in PASS_MODES:
     pass_sweep()
 if mode in BATCH_MODES:
     batch_sweep()
+if mode == "light":
+    light_sweep()
 if len(sys.argv) > 3 and sys.argv[3] == "bundle":
     make_case = make_bundle_case
 if len(sys.argv) > 3 and sys.argv[3] == "wide":
