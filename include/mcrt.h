@@ -235,6 +235,11 @@ int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds);
  * mcrt_bg_plate_info reports background plates only */
 int mcrt_draw_plate_info(int device, int* plates, size_t* bytes, int* builds);
 
+/* Work lists by ticket.  Within `primary` and `lit` a workgroup takes its first work item by its index and claims every later
+ * one from an atomic counter of the pass, so that workgroups that drew cheap items take more of them (DESIGN.md §4 "Work
+ * lists by ticket").  The frames do not depend on it.  MCRT_WORK_TICKETS=0 makes the workgroups stride over the lists by
+ * the grid's size instead (development knob, read once per process like MCRT_BG_PLATE and MCRT_DRAW_PLATE). */
+
 /* Waits for the scene's device work and reports an internal inconsistency of the last renders (the
  * workspace is sized for the tiles the host expects meshes to touch; the device flags a tile beyond
  * that bound instead of writing past it).  MCRT_OK in every correct run; the one-shot entry points

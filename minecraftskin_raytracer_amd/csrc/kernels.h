@@ -67,7 +67,8 @@ struct WaveSpace {
     uint32_t* counter_base; // the counters' values when the pass began (the previous pass's `resolve` left them): a pass's counts are differences
     uint32_t* frame_info;   // [0] units of the pass, left by `primary` for `resolve`
     uint32_t* counters;     // [0] units in `units`, [1] touched tiles, [8 + L] entries of level L >= 1
-                            // ([9] = level-1 records), [last] touched-tile bound exceeded (never, by construction; sticky);
+                            // ([9] = level-1 records), [kCounterWords - 64] / [kCounterWords - 32] work tickets of `primary` / `lit`,
+                            // [last] touched-tile bound exceeded (never, by construction; sticky);
                             // never cleared: running counts (modulo 2^32) against counter_base
     uint32_t* hit_rng;      // general variants: per-thread 624-word mt19937 states (long streams)
     uint32_t cap;           // slot capacity (= samples of the touched tiles of the largest batch)
@@ -131,6 +132,8 @@ struct RenderParams {
                            //    rt::mesh_candidate_inside (the exit face alone); 0 (MCRT_INSIDE_FAST=0) — the general routine
     int bundle_decisions;  // `lit`: 1 — a hit whose whole bundle of shadow rays is decided (rt::bundle_decide) draws no light
                            //    samples and traces no rays; 0 (MCRT_BUNDLE_DECISIONS=0) — every hit's rays are traced
+    int work_tickets;      // `primary`, `lit`: 1 — a workgroup claims the items of the work list behind its first by ticket (an atomic
+                           //    counter per kernel); 0 (MCRT_WORK_TICKETS=0) — it strides over the list by the grid's size
     int shared_device;     // 1: this render shares the device with others (another lane of its frame, or another handle's frame still
                            //    running when it was enqueued): the grids below are then sized for throughput — fewer, longer-lived
                            //    workgroups per kernel leave room for the other frames' kernels —, otherwise for the frame's own latency

@@ -109,6 +109,8 @@ int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int fir
     p.bundle_decisions = decisions ? 1 : 0;
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");  // development knob: =0 sends every candidate through the general routine
     p.inside_fast = inside_fast ? 1 : 0;
+    static const bool work_tickets = !env_off("MCRT_WORK_TICKETS");  // development knob: =0 strides `primary` and `lit` statically over their work lists
+    p.work_tickets = work_tickets ? 1 : 0;
     p.cfg = *cfg;
     if (cfg->width > 0 && cfg->height > 0) {
         p.inv_width = 1.0f / static_cast<float>(cfg->width);

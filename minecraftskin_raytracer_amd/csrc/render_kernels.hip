@@ -364,6 +364,31 @@ constexpr int kCntOverflow = kCounterWords - 1;  // set if more tiles are touche
 __device__ __forceinline__ uint32_t counted(const WaveSpace& ws, int i) { return ws.counters[i] - ws.counter_base[i]; }
 __device__ __forceinline__ uint32_t count_add(const WaveSpace& ws, int i, uint32_t n) { return atomicAdd(&ws.counters[i], n) - ws.counter_base[i]; }
 
+// Work lists by ticket (`primary`, `lit`).  The items of these kernels' lists differ widely in cost — a unit without a hit
+// is nothing, a full one a whole round, a chase block three dependent scene queries — and a grid smaller than the list
+// (a frame that shares the device) that strides over it statically ends when its unluckiest workgroup does.  So a
+// workgroup's FIRST item is blockIdx.x (no atomic, no burst at the kernel's start) and every later one is gridDim.x + a
+// ticket: one more word of the pass counters per kernel, run on like the others (`resolve` snapshots it with them), each in
+// a 128-byte line of its own (the level counters of the general variants end below word 4032).  Thread 0 claims; the item
+// reaches the workgroup through LDS and one barrier (two slots taken in turn: a slot is written again only behind the
+// barrier of the claim between, which every thread passes after reading it).  No workgroup ever waits for another: a
+// ticket only grows, every claim is answered at once, and a workgroup leaves — all its threads, the item is uniform — with
+// the first item at or past the end of the list, so the kernel ends after list + grid claims at the most.  A grid that
+// covers the list takes no ticket at all.  p.work_tickets == 0: the static stride.  A ticket is, like every count, the
+// word's difference to counter_base modulo 2^32: right across the word's wrap as long as a pass claims fewer than 2^32
+// items, and gridDim.x + ticket stays below 2^32 for any list the 32-bit record indices allow.  (Claiming the NEXT ticket at
+// the start of the current item, to hide the round trip, was measured and lost: DESIGN.md §4 "Measured and rejected: work
+// tickets", profiles/work_tickets/README.md.)
+constexpr int kCntTicketPrimary = kCounterWords - 64;
+constexpr int kCntTicketLit = kCounterWords - 32;
+__device__ __forceinline__ uint32_t next_work(const RenderParams& p, int word, uint32_t current, uint32_t end, uint32_t* s_ticket, uint32_t& turn) {
+    if (!p.work_tickets || gridDim.x >= end) return current + gridDim.x;  // uniform
+    uint32_t* slot = s_ticket + (turn++ & 1u);
+    if (threadIdx.x == 0) *slot = gridDim.x + count_add(p.ws, word, 1u);
+    __syncthreads();
+    return *slot;
+}
+
 __device__ __forceinline__ void push_entry(const WaveSpace& ws, int parity, uint32_t e, const Ray& ray, const Hit& hit,
                                            uint32_t root, int depth) {
     ws.q_o[parity][e] = make_float4(ray.o.x, ray.o.y, ray.o.z, __uint_as_float(root));
@@ -652,6 +677,7 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
     __shared__ int s_wcnt[kBlock / 64];
     __shared__ float4 s_bd[kBlock], s_bp[kBlock], s_bn[kBlock];  // the chunk's primary hits, packed, for their reflection rays
     __shared__ uint32_t s_out_base;
+    __shared__ uint32_t s_ticket[2];
     extern __shared__ __align__(16) unsigned char s_dyn[];
 
     const SceneView scg = view_of(scene_blob);
@@ -677,7 +703,9 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
     const size_t stride = ws.draws_stride;
 
     // ================= units of tiles that meshes can touch: thread per sample =================
-    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+    // (the list by ticket: next_work)
+    uint32_t turn = 0;
+    for (uint32_t u = blockIdx.x; u < n_units; u = next_work(p, kCntTicketPrimary, u, n_units, s_ticket, turn)) {
         const uint4 ud = ws.units[u];
         const int tile = static_cast<int>(ud.x);
         const unsigned pp0 = ud.y, pp1 = ud.z;
@@ -1193,6 +1221,7 @@ template <int kView>
 __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob, const RenderParams& __restrict__ p) {
     extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks: lit_round][inside masks: lit_round][positions: lit_pass x S x 3 floats][lit counts: lit_round][undecided list: lit_round]
     __shared__ int s_wcnt[kBlock / 64];
+    __shared__ uint32_t s_ticket[2];
     MCRT_HOOK_LIT_SHARED
     const SceneView scg = view_of(scene_blob);
     const WaveSpace& ws = p.ws;
@@ -1233,7 +1262,9 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
     const bool posed = kView != kViewLdsUnposed && p.scene_posed != 0;  // the un-posed variants never read q_n
     const bool dof = cfg.dof_enabled && cfg.aperture > 1e-6f;
     const V3 cam_pos = ld3(scg.hdr->cam_pos);
-    for (uint32_t work = blockIdx.x; work < n_work; work += gridDim.x) {
+    // (the list by ticket: next_work; its order — chase blocks, units, dense blocks — puts the dearest items first)
+    uint32_t turn = 0;
+    for (uint32_t work = blockIdx.x; work < n_work; work = next_work(p, kCntTicketLit, work, n_work, s_ticket, turn)) {
         uint32_t first, n;
         if (work < n_chase) {
             // the chains of level-1 records [k0, k0 + 256): a lane per chain — reflect, closest hit, append — until the ray
