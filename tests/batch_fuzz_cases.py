@@ -46,6 +46,35 @@ def expected_envelope(cfg) -> bool:
     return not general
 
 
+K_FACE_LDS_ENTRIES_MAX = 384  # kernels.h: kFaceLdsEntriesMax — six face entries per mesh: 64 meshes
+K_ALPHA_LDS_WORDS_MAX = 4096  # kernels.h: kAlphaLdsWordsMax — 16 texels per word: 65 536 texels
+MESH_OUTER, MESH_ROTATED = 1, 2  # flat_scene.h
+
+
+def flat_header(scene) -> dict:
+    """What render_plan.cpp's lds_fit is given, and the first-pass groups, read from the flattened blob (flat_scene.h) and never
+    asked of the code under test: n_meshes, n_texels, alpha_words, posed (any mesh with MESH_ROTATED), roots (bit i: mesh
+    i < 64 is a group root), and per mesh flags, group (64-bit word), lo, hi (3 floats each) and tex_off / tex_w / tex_h (6 ints)."""
+    blob = M.flatten(scene)
+    hdr = np.frombuffer(blob[:192], np.uint32)
+    n, mesh_off = int(hdr[1]), int(hdr[32])
+    mesh = np.frombuffer(blob[mesh_off:mesh_off + 192 * n], np.uint32).reshape(n, 48)
+    flags = mesh[:, 17].copy()
+    return {"n_meshes": n, "n_texels": int(hdr[2]), "alpha_words": int(hdr[36]), "posed": bool((flags & MESH_ROTATED).any()),
+            "roots": int(hdr[37]) | (int(hdr[38]) << 32), "flags": flags,
+            "group": [int(lo) | (int(hi) << 32) for lo, hi in zip(mesh[:, 44], mesh[:, 45])],
+            "lo": mesh[:, 0:3].copy().view(f32), "hi": mesh[:, 3:6].copy().view(f32),
+            "tex_off": mesh[:, 18:24].copy().view(np.int32), "tex_w": mesh[:, 24:30].copy().view(np.int32), "tex_h": mesh[:, 30:36].copy().view(np.int32)}
+
+
+def expected_view(header: dict) -> str:
+    """The scene view the kernels of a frame ALONE are compiled against — render_plan.cpp's lds_fit, restated: the tables go to LDS
+    only if six face entries per mesh and the alpha words both fit; then the un-posed variants serve a scene without a rotated
+    mesh.  "hbm" (kViewHbm), "lds" (kViewLds) or "lds-unposed" (kViewLdsUnposed).  A batch takes the weakest view of its frames."""
+    fits = header["alpha_words"] <= K_ALPHA_LDS_WORDS_MAX and header["n_meshes"] * 6 <= K_FACE_LDS_ENTRIES_MAX
+    return "hbm" if not fits else ("lds" if header["posed"] else "lds-unposed")
+
+
 def expected_batch_info(cfg, n: int) -> dict:
     """last_batch_info() of a batch of n frames of one background mode."""
     if expected_envelope(cfg):

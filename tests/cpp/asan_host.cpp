@@ -115,6 +115,17 @@ static int plan_checks() {
     if (f[0].lit_lds_offset == 0 || f[1].lit_lds_offset != 0 || !mcrt::batch_eligible(f[0]) || !mcrt::batch_eligible(f[1])) { std::printf("plan: batch set-up\n"); ++bad; }
     if (mcrt::plan_batch(f, 2, false, plan) != hipSuccess || plan.view != mcrt::kViewHbm || plan.dyn != 0 || f[0].lit_lds_offset != 0 || f[1].lit_lds_offset != 0 ||
         plan.lit_dyn != static_cast<size_t>(f[0].lit_lds_bytes)) { std::printf("plan: mixed batch\n"); ++bad; }
+    // lds_fit at the limits of the staged tables: 64 meshes (384 face entries) and 4096 alpha words (65 536 texels) fit, one more
+    // of either does not; the un-posed variants serve a fitting scene without a rotated mesh
+    for (uint32_t n : {63u, 64u, 65u}) for (uint32_t words : {4096u, 4097u}) for (int posed = 0; posed < 2; ++posed) {
+        const mcrt::LdsFit fit = mcrt::lds_fit(words, n, posed != 0);
+        const bool fits = n <= 64 && words <= 4096;
+        const int view = !fits ? mcrt::kViewHbm : (posed ? mcrt::kViewLds : mcrt::kViewLdsUnposed);
+        if (fit.view != view || fit.face_entries != (fits ? static_cast<int>(n * 6) : 0) || fit.alpha_words != (fits ? static_cast<int>(words) : 0)) {
+            std::printf("plan: lds_fit(%u words, %u meshes, posed %d) = view %d, %d entries, %d words\n", words, n, posed, fit.view, fit.face_entries, fit.alpha_words);
+            ++bad;
+        }
+    }
     std::printf("plan driver: %d combinations, %d of them split into batches of several rows\n", combos, split);
     if (split == 0) ++bad;  // the budgets no longer reach the batching: the loop would check nothing of it
     return bad;

@@ -110,6 +110,13 @@ class CpuLib:
         a, b = (np.asarray(x, np.float32) for x in (point, normal))
         return float(self._f("ao")(desc_ptr, abi.fptr(a), abi.fptr(b), samples, C.c_float(radius), seed & 0xFFFFFFFF))
 
+    def soft_shadow_many(self, desc_ptr, points, normals, samples: int, seeds) -> np.ndarray:
+        """soft_shadow at every row of points / normals (n, 3) with its own seed: (n,) float32."""
+        return np.array([self.soft_shadow(desc_ptr, p, n, samples, int(s)) for p, n, s in zip(points, normals, seeds)], np.float32)
+
+    def ao_many(self, desc_ptr, points, normals, samples: int, radius: float, seeds) -> np.ndarray:
+        return np.array([self.ao(desc_ptr, p, n, samples, radius, int(s)) for p, n, s in zip(points, normals, seeds)], np.float32)
+
     def background(self, desc_ptr, cfg, u: float, v: float) -> np.ndarray:
         out = np.zeros(4, np.float32)
         c = cfg.to_c() if cfg is not None else None
@@ -199,7 +206,7 @@ class Reference(CpuLib):
 
 # ---- the compiled reference's answers, stored: the oracle-vs-reference tests where oracle/_ref cannot be built ----
 REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "reference_outputs.npz")
-_REPLAYED = ("builtin_pose", "build_skin_scene", "build_default_scene", "render", "intersect", "seed_cast")
+_REPLAYED = ("builtin_pose", "build_skin_scene", "build_default_scene", "render", "intersect", "seed_cast", "soft_shadow_many", "ao_many")
 
 
 STORED_IN_FULL_BYTES = 256  # larger answers (and structured ones) are stored as digests (RecordedArray)
@@ -251,7 +258,7 @@ class RecordedArray:
 
 
 # which comparison each method's answers meet in the tests (scenes.assert_bit_equal / assert_hits_equal / same_bytes)
-_DIGEST_KIND = {"render": "floats", "intersect": "hits"}
+_DIGEST_KIND = {"render": "floats", "intersect": "hits", "soft_shadow_many": "floats", "ao_many": "floats"}
 
 
 def _to_spec(value, blob: bytearray, kind: str):

@@ -40,11 +40,14 @@ def render(ds, cfg, lead=0) -> dict:
     return out
 
 
-def run_case(mcrt, case, exp, lead=0, twice=False) -> list:
-    """One DeviceScene, the three planes, check(); the mismatches as texts (a HIP error raises)."""
+def run_case(mcrt, case, exp, lead=0, twice=False, ds=None) -> list:
+    """One DeviceScene (the caller's `ds`, which stays open, or one made and closed here), the three planes, check(); the
+    mismatches as texts (a HIP error raises)."""
     sd, cfg, what = case
     failures = []
-    ds = mcrt.DeviceScene(sd)
+    own = ds is None
+    if own:
+        ds = mcrt.DeviceScene(sd)
     try:
         got = render(ds, cfg, lead)
         try:
@@ -63,7 +66,8 @@ def run_case(mcrt, case, exp, lead=0, twice=False) -> list:
                         failures.append(f"{what}: batch frame {i} plane {k} differs from the single call")
         ds.check()
     finally:
-        ds.close()
+        if own:
+            ds.close()
     return failures
 
 

@@ -84,8 +84,9 @@ def _check_layers(ds, sd, cfg, got, surf, seed, what):
     scenes.assert_bit_equal(rec["point"], surf["point"][at], f"{what} pick point")
 
 
-def run_case(mcrt, case, lead, ground_exp=None, reflection_exp=None, surfaces=None, seed=0) -> list:
-    """One DeviceScene, every pass an expectation is given for, check(); the mismatches as texts (a HIP error raises)."""
+def run_case(mcrt, case, lead, ground_exp=None, reflection_exp=None, surfaces=None, seed=0, ds=None) -> list:
+    """One DeviceScene (the caller's `ds`, which stays open, or one made and closed here), every pass an expectation is given for,
+    check(); the mismatches as texts (a HIP error raises)."""
     sd, cfg, ground, what = case
     failures = []
 
@@ -95,7 +96,9 @@ def run_case(mcrt, case, lead, ground_exp=None, reflection_exp=None, surfaces=No
         except AssertionError as e:
             failures.append(str(e)[:600])
 
-    ds = mcrt.DeviceScene(sd)
+    own = ds is None
+    if own:
+        ds = mcrt.DeviceScene(sd)
     try:
         if ground_exp is not None:
             got = _ground(ds, cfg, ground, lead)
@@ -108,7 +111,8 @@ def run_case(mcrt, case, lead, ground_exp=None, reflection_exp=None, surfaces=No
             compare(lambda: _check_layers(ds, sd, cfg, got_l, surfaces, seed, what + " | layers"))
         ds.check()
     finally:
-        ds.close()
+        if own:
+            ds.close()
     return failures
 
 

@@ -97,6 +97,39 @@ def test_bundle_decision_scenes(mcrt, oracle, reference, block):
         scenes.assert_bit_equal(oracle.render(sd.ptr, cfg), reference.render(sd.ptr, cfg), what)
 
 
+BIG_BLOCKS = [(group, first) for group in ("count", "posed", "texels") for first in (36000, 36036)]
+
+
+@pytest.mark.parametrize("group, first", BIG_BLOCKS, ids=[f"{g}-{f}" for g, f in BIG_BLOCKS])
+def test_big_scenes(mcrt, oracle, reference, group, first):
+    """The scenes of tests/big_scene_cases.py — up to 200 meshes, rotated meshes among boxes, texel pools beyond 65 536 texels,
+    general-variant configs (114 ... 160 shadow or AO samples, up to 20 bounces) — 24 cases of each group: the oracle the GPU sweeps
+    trust there is the reference's equal in the render, in intersectScene on rays aimed at the scene, and, for the passes'
+    expectations, in computeSoftShadow and computeAmbientOcclusion at 200 of its own hit points per case."""
+    import big_scene_cases as BS
+    import light_checker as LC
+
+    general = 0
+    for seed in BS.block_seeds(group, first):
+        sd, cfg, ground, what = BS.make_big_case(seed, group)
+        general += BS.is_general(cfg)
+        scenes.assert_bit_equal(oracle.render(sd.ptr, cfg), reference.render(sd.ptr, cfg), what)
+        rays = BS.case_rays(sd, seed)
+        hits = oracle.intersect(sd.ptr, rays)
+        scenes.assert_hits_equal(hits, reference.intersect(sd.ptr, rays), what + " | intersect")
+        at = np.flatnonzero(hits["hit"] != 0)[:200]
+        assert len(at) == 200, what
+        p, nrm = hits["point"][at].astype(np.float32), hits["normal"][at].astype(np.float32)
+        pc = BS.pass_config(cfg)
+        seeds = [oracle.seed_cast(float(x)) for x in LC.shadow_sums(p)]
+        vis = oracle.soft_shadow_many(sd.ptr, p, nrm, pc.shadowSamples, seeds)
+        scenes.assert_bit_equal(vis, reference.soft_shadow_many(sd.ptr, p, nrm, pc.shadowSamples, seeds), what + " | soft shadow")
+        seeds = [oracle.seed_cast(float(x)) for x in LC.ao_sums(p)]
+        occ = oracle.ao_many(sd.ptr, p, nrm, pc.aoSamples, pc.aoRadius, seeds)
+        scenes.assert_bit_equal(occ, reference.ao_many(sd.ptr, p, nrm, pc.aoSamples, pc.aoRadius, seeds), what + " | ao")
+    assert general == 3
+
+
 def test_degenerate_cameras_and_lights(mcrt, oracle, reference):
     box = scenes.build_box(scenes.solid((0.8, 0.3, 0.2, 1)), (0, 0, 0), (4, 4, 4))
     for kw in (dict(cam_pos=(0, 10, 0), cam_target=(0, 0, 0)),  # up parallel to forward → zero right vector

@@ -20,6 +20,13 @@ The batched entries (tests/batch_fuzz_cases.py; the runs and comparisons are tho
   pass-batch   render_layers / ground / reflection_batch_device on 16 scenes under one config, each at its own plane height: the
                groups bundle, wide, long-shadow and far-plane in turn from seed first + 16 k, every fifth batch four cases of each
 For these a mismatch prints the batch, the frame index, the plane, the count and the first pixel.
+The limits of the scene tables (tests/big_scene_cases.py; the runs and comparisons are those of tests/test_gpu_big_scene_fuzz.py):
+  big          seed k is make_big_case(k, ("count", "posed", "texels")[k % 3]): 48 ... 200 boxes around the 64-mesh limit of the masks,
+               culling, decisions and groups; posed figures among 40 ... 140 meshes; texel pools of 65 520 ... 90 000 texels; every
+               fourth case of a group under a general-variant config.  Per case the beauty render (host and device form, every third
+               transparent), intersect on 1 500 rays, ground, reflection, layers with picks and the light planes; the summary
+               records the census of what the oracle's planes held (big_scene_cases.CENSUS); a case whose expectation cannot be
+               made (the generator's own assertions) ends the run with exit status 3
 A mismatch prints the case, the plane, the number of differing pixels and the first of them; the exit status is then 1.  After
 a HIP error (exit status 2) nothing more is started.  MCRT_BUNDLE_DECISIONS=0 / MCRT_REFLECT_CULL=0 in the environment render
 without the whole-bundle decisions / the reflection's tile culling: a mismatch that goes away with one is that shortcut's."""
@@ -35,7 +42,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide", "light") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light", "big") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -138,6 +145,51 @@ def light_sweep():
     sys.exit(1 if bad else 0)
 
 
+def big_sweep():
+    import big_scene_cases as BS, test_gpu_big_scene_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    # the oracle's frames and planes are made ahead of the device by worker processes (forked before the device is first used;
+    # they never use it), in the order of the seeds
+    import multiprocessing
+
+    workers = max(1, min(14, len(os.sched_getaffinity(0)) - 2, int(os.environ.get("OMP_NUM_THREADS", "16")) - 2))
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    ahead = pool.imap(BS.worker_sweep_expectation, [(first + k, k) for k in range(count)])
+    bad = 0
+    total = np.zeros(len(BS.CENSUS), np.int64)
+    views = {}
+    t0 = time.time()
+    for k, seed in enumerate(range(first, first + count)):
+        case = BS.make_big_case_info(seed, BS.GROUPS[seed % 3])
+        try:
+            pexp, bexp, census = next(ahead)
+        except Exception as e:  # a worker's: the generator's own assertions, or the oracle's
+            print(f"CASE ERROR {case[3]}: {type(e).__name__}: {e}", flush=True)
+            print(f"fuzz big: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
+            pool.terminate()
+            sys.exit(3)
+        try:
+            lines = T.run_big_case(M, case, pexp, bexp, k, seed)
+        except McrtError as e:
+            print(f"HIP ERROR {case[3]}: {e}", flush=True)
+            print(f"fuzz big: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
+            pool.terminate()
+            sys.exit(2)
+        total += census
+        view = BS.B.expected_view(BS.B.flat_header(case[0]))
+        views[view] = views.get(view, 0) + 1
+        if lines:
+            bad += 1
+            print("\n".join(lines[:20]), flush=True)
+        if k % 50 == 49:
+            print(f"... {k + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
+    print(f"fuzz big: {count} cases from seed {first}: {bad} mismatch(es); views {dict(sorted(views.items()))}; the oracle holds "
+          + ", ".join(f"{int(t)} {name}" for name, t in zip(BS.CENSUS, total)))
+    pool.terminate()
+    sys.exit(1 if bad else 0)
+
+
 def pass_sweep():
     import ground_checker as G, layers_checker as L, pass_fuzz_cases as PF, reflection_checker as R
     from minecraftskin_raytracer_amd._lib import McrtError
@@ -206,6 +258,8 @@ if mode in BATCH_MODES:
     batch_sweep()
 if mode == "light":
     light_sweep()
+if mode == "big":
+    big_sweep()
 if len(sys.argv) > 3 and sys.argv[3] == "bundle":
     make_case = make_bundle_case
 if len(sys.argv) > 3 and sys.argv[3] == "wide":
