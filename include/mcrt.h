@@ -530,6 +530,75 @@ int mcrt_render_light_batch_device(mcrt_scene* const* scenes, int n_frames, cons
 /* one-shot host form: host pointers, rendered on `device` with a pooled handle like mcrt_render */
 int mcrt_render_light(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_light_planes* out, int device);
 
+/* ---- light bake: per-texel shadow, ambient occlusion and direct light in texture space ------------------------------------
+ * The terms of the light layers on the skin itself instead of on a view of it: for every texel of every face how much of the
+ * disk light reaches it, how occluded it is and what shade() makes of it — a light map, an ambient-occlusion bake, a pre-shaded
+ * skin.  No camera enters: the faces where the arm meets the body are baked like any other.  All arithmetic float32 with one
+ * rounding per operation, uncontracted, in the order written; every division is correctly rounded.
+ * OWNER FACE.  Face slot f (0..5, determineFace order: 0 back -Z, 1 front +Z, 2 left +X, 3 right -X, 4 top, 5 bottom) of mesh m
+ * with a texture references the pool texels tex_off[f] ... tex_off[f] + w * h - 1, row-major.  Faces may share a texture, so a
+ * pool texel is baked on its OWNER: of the faces that reference it the one with the lowest mesh index, then the lowest face
+ * slot.  A texel no face references has no owner.  mcrt_bake_texel_table (host only, no device) returns the number of pool
+ * texels n_texels, or -1 with MCRT_ERR_INVALID's text for a scene that cannot be flattened, and writes for the first
+ * min(n_texels, capacity) texels {mesh, face, tx, ty}, {-1, 0, -1, -1} without an owner.  The planes are indexed like this
+ * table.  For a repaintable handle it agrees with mcrt_skin_pool_map / mcrt_skin_texel.
+ * SAMPLE POINTS.  grid = q, 1..4.  Sub-sample (i, j), 0 <= i, j < q, of texel (tx, ty) of a w x h face:
+ *     u = ((float)tx + ((float)i + 0.5f) / (float)q) / (float)w        v = ((float)ty + ((float)j + 0.5f) / (float)q) / (float)h
+ * The local point p is the inverse of computeFaceUV (intersection.cpp:136-196) on the face's plane, with lo, hi the mesh's
+ * box, ext = hi - lo and neg = the face on the min side of its axis (slots 0, 3, 5):
+ *     slots 0, 1 (axis z)   lx = neg ? 1.0f - u : u,  ly = 1.0f - v   p = (lo.x + lx * ext.x, lo.y + ly * ext.y, neg ? lo.z : hi.z)
+ *     slots 2, 3 (axis x)   lz = neg ? u : 1.0f - u,  ly = 1.0f - v   p = (neg ? lo.x : hi.x, lo.y + ly * ext.y, lo.z + lz * ext.z)
+ *     slots 4, 5 (axis y)   lx = u,  lz = neg ? 1.0f - v : v          p = (lo.x + lx * ext.x, neg ? lo.y : hi.y, lo.z + lz * ext.z)
+ * P = rotatePoint(p) forwards (rotX, then rotZ, about the pivot: the reference's hit point, intersection.cpp:399) for a mesh with
+ * hasRotation, p otherwise.  N is the normal intersectMesh gives a front hit of that face: the face's axis vector, and for a
+ * mesh with hasRotation normalize(rotateDir(n)) (intersection.cpp:400).
+ * PER SUB-SAMPLE, the light layers' terms with P, N in place of the hit:
+ *   vis   soft_shadows && shadow_samples > 1: computeSoftShadow(P, N, light, scene, shadow_samples, seed) with
+ *         seed = (unsigned)(P.x * 12345.0f + P.y * 67890.0f + P.z * 11111.0f + 0.0f * 99999.0f); otherwise
+ *         isInShadow(P, normalize(N), light.position) ? 0 : 1
+ *   occ   computeAO(P, N, scene, ao_samples, ao_radius, (unsigned)(P.x * 73856093.0f + P.y * 19349663.0f + P.z * 83492791.0f)),
+ *         whatever ao_enabled says
+ *   dir   shade(hit{P, N, the texel's colour, isOuterLayer of the mesh}, viewDir = N, light, scene, ShadingParams{}, vis); its
+ *         alpha is the texel's.  A texel has no camera: the view vector is the normal, the usual convention of a bake.
+ * PLANES, in pool order.  A texel is DEAD when it has no owner or its alpha == 0.0f, LIVE otherwise.  "Mean": the q * q
+ * sub-sample values added left to right, j outer and i inner, starting from the first value, then divided by (float)(q * q);
+ * with q = 1 the value itself.
+ *   position    4 floats  P of the texel centre (the q = 1 formula), w = 1.0f; dead: the same point with w = 0.0f, all zero
+ *                         without an owner
+ *   normal      4 floats  N, w = 0.0f; zero without an owner
+ *   visibility  1 float   mean of vis; dead: 1.0f
+ *   occlusion   1 float   mean of occ; dead: 1.0f
+ *   direct      4 floats  componentwise mean of dir; dead: (0, 0, 0, 0)
+ * Of mcrt_config the pass reads soft_shadows, shadow_samples, ao_samples and ao_radius (the last two only when the occlusion
+ * plane is asked for) and nothing else — no frame size —, and not the handle's background mode.
+ * Asynchronous on `stream`, not into a graph being recorded (a batch); no workspace, no counters and none of the handle's
+ * events, so a bake may run beside the handle's render on another stream; it reads the device's seed tables through the handle
+ * and builds none; mcrt_scene_destroy and mcrt_scene_check wait for it.  Ordering a bake against a REPAINT of the handle
+ * (mcrt_scene_set_skin_device & co) — stream order, or an event of the caller's — is the caller's job, as for the layers.
+ * Batch: frame i starts i * texel_stride texels on in every plane; the scenes may hold different numbers of texels, and
+ * texel_stride is at least the largest; the texels between frames are not written; a handle may be listed more than once; one
+ * launch per kernel and 4096 frames.
+ * MCRT_ERR_INVALID before any device work, the planes untouched: a NULL config, handle, entry or planes struct; all five
+ * planes NULL; n_frames < 0; handles on different devices; grid outside 1..4; a texel_stride below a scene's texel count;
+ * soft_shadows && shadow_samples > 113; and, when the occlusion plane is asked for, ao_samples < 1, ao_samples > 113 or an
+ * ao_radius that is not finite.  n_frames = 0 and scenes without texels: MCRT_OK, nothing written. */
+typedef struct mcrt_bake_planes {
+    float* position; /* any may be NULL (that plane is not produced), not all */
+    float* normal;
+    float* visibility;
+    float* occlusion;
+    float* direct;
+} mcrt_bake_planes;
+/* resident scene, device pointers, asynchronous on `stream` */
+int mcrt_bake_light_device(mcrt_scene* scene, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, void* stream);
+int mcrt_bake_light_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out,
+                                 size_t texel_stride, void* stream);
+/* one-shot host form: host pointers (mcrt_bake_texel_table's count of texels per plane), baked on `device` with a pooled handle */
+int mcrt_bake_light(const mcrt_scene_desc* scene, const mcrt_config* cfg, int grid, const mcrt_bake_planes* out, int device);
+int mcrt_bake_texel_table(const mcrt_scene_desc* scene, int32_t (*out)[4], int capacity);
+/* the number of pool texels of a resident scene: the texels per plane of its bake */
+int mcrt_scene_texels(mcrt_scene* scene, int* n_texels);
+
 /* ---- skins on resident scenes: a new skin for a scene that is already on the device -----------------------------------------
  * Everything in a flattened skin scene but its texels is a function of pose, camera and light alone.  A REPAINTABLE handle takes
  * a new skin from a 64 x skin_height RGBA8 image in device memory with one small kernel — no scene build, no flattening, no upload

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_light_device", "mcrt_render_light_batch_device", "mcrt_render_light",
     "mcrt_scene_create_skin", "mcrt_scene_set_skin_device", "mcrt_scene_set_skins_batch_device", "mcrt_scene_set_skin",
     "mcrt_skin_pool_map", "mcrt_probe_scene_blob",
+    "mcrt_bake_light_device", "mcrt_bake_light_batch_device", "mcrt_bake_light", "mcrt_bake_texel_table", "mcrt_scene_texels",
 ]
 
 
@@ -55,6 +56,7 @@ def load():
     ground_p = C.POINTER(abi.McrtGround)
     reflection_p = C.POINTER(abi.McrtReflection)
     light_p = C.POINTER(abi.McrtLightPlanes)
+    bake_p = C.POINTER(abi.McrtBakePlanes)
     sig = {
         "mcrt_config_init": (None, [cfg_p]),
         "mcrt_generate_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(abi.McrtTile), C.c_int]),
@@ -91,6 +93,11 @@ def load():
         "mcrt_render_light_device": (C.c_int, [vp, cfg_p, light_p, vp]),
         "mcrt_render_light_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, light_p, C.c_size_t, vp]),
         "mcrt_render_light": (C.c_int, [desc_p, cfg_p, light_p, C.c_int]),
+        "mcrt_bake_light_device": (C.c_int, [vp, cfg_p, C.c_int, bake_p, vp]),
+        "mcrt_bake_light_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, C.c_int, bake_p, C.c_size_t, vp]),
+        "mcrt_bake_light": (C.c_int, [desc_p, cfg_p, C.c_int, bake_p, C.c_int]),
+        "mcrt_bake_texel_table": (C.c_int, [desc_p, abi.c_int32_p, C.c_int]),
+        "mcrt_scene_texels": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "mcrt_scene_pick": (C.c_int, [vp, cfg_p, abi.c_int32_p, C.c_int, vp]),
         "mcrt_skin_texel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mcrt_scene_create_skin": (C.c_int, [C.c_int, f_p, desc_p, C.c_int, C.POINTER(vp)]),

@@ -242,6 +242,32 @@ def light_names(planes) -> tuple:
     return tuple(n for n in LIGHT_NAMES if n in names)
 
 
+class McrtBakePlanes(C.Structure):
+    """mcrt_bake_planes: one pointer per plane of a light bake (device or host memory, by entry point); NULL = not wanted."""
+
+    _fields_ = [("position", C.c_void_p), ("normal", C.c_void_p), ("visibility", C.c_void_p), ("occlusion", C.c_void_p), ("direct", C.c_void_p)]
+
+
+BAKE_NAMES = ("position", "normal", "visibility", "occlusion", "direct")
+# per pool texel: (dtype, components) of each plane
+BAKE_FORMATS = {"position": (np.float32, 4), "normal": (np.float32, 4), "visibility": (np.float32, 1), "occlusion": (np.float32, 1),
+                "direct": (np.float32, 4)}
+BAKE_MAX_GRID = 4  # sub-samples per texel and axis of a light bake: grid 1..4
+
+
+def bake_names(planes) -> tuple:
+    """The wanted bake planes in the order of ``BAKE_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
+    if isinstance(planes, str):
+        planes = (planes,)
+    names = tuple(planes)
+    for n in names:
+        if not isinstance(n, str) or n not in BAKE_FORMATS:
+            raise ValueError(f"planes must be taken from {BAKE_NAMES}, not {n!r}")
+    if not names:
+        raise ValueError("no plane selected")
+    return tuple(n for n in BAKE_NAMES if n in names)
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 
 SURFACE_DTYPE = np.dtype(

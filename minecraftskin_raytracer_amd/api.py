@@ -377,6 +377,28 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def bakeLight(scene, config: Config, grid: int = 1, planes=abi.BAKE_NAMES, device: int = 0) -> dict:
+        """The light terms in TEXTURE space (mcrt_bake_light): one value per texel of the scene's texel pool, in pool order —
+        ``texel_table(scene)`` names each texel's owner face.  A dict of the wanted planes, n = the pool's size: ``position``
+        (n, 4) float32, the texel centre on its face with w = 1 (w = 0 for a dead texel: one without an owner or with alpha 0);
+        ``normal`` (n, 4), the face's outward normal; ``visibility`` (n,) and ``occlusion`` (n,), the means of computeSoftShadow
+        (or shade()'s own shadow test) and computeAO over ``grid`` x ``grid`` sub-samples of the texel (1 for a dead texel);
+        ``direct`` (n, 4), the mean of ``shade()`` with the view vector along the normal, alpha the texel's (zero for a dead
+        texel).  Of ``config`` only softShadows, shadowSamples (at most 113 with softShadows), aoSamples (1 to 113) and aoRadius
+        matter.  Failures raise ``McrtError``."""
+        names = abi.bake_names(planes)
+        grid = _bake_grid(grid)
+        d = _as_desc(scene)
+        n = len(texel_table(d))
+        out = {k: _empty_bake(k, n) for k in names}
+        if n == 0:
+            return out
+        c = config.to_c()
+        frame = abi.McrtBakePlanes(**{k: v.ctypes.data for k, v in out.items()})
+        check(load().mcrt_bake_light(d.ptr, C.byref(c), grid, C.byref(frame), int(device)))
+        return out
+
+    @staticmethod
     def lastBatchInfo() -> dict:
         """How the last batch call on this thread ran (mcrt_last_batch_info): ``batched_frames`` taken by the batched
         kernels and ``launch_sequences`` enqueued (1 when the whole batch went through them at once)."""
@@ -430,6 +452,21 @@ def _empty_light(name: str, n: int, h: int, w: int) -> np.ndarray:
     if name != "direct":
         a[...] = 1.0
     return a
+
+
+def _empty_bake(name: str, n: int) -> np.ndarray:
+    """One bake plane for n texels, holding the constants of a texel without an owner face."""
+    dtype, comps = abi.BAKE_FORMATS[name]
+    a = np.zeros((n,) + ((comps,) if comps > 1 else ()), dtype)
+    if name in ("visibility", "occlusion"):
+        a[...] = 1.0
+    return a
+
+
+def _bake_grid(grid) -> int:
+    if isinstance(grid, bool) or int(grid) != grid or not 1 <= int(grid) <= abi.BAKE_MAX_GRID:
+        raise ValueError(f"grid must be an integer from 1 to {abi.BAKE_MAX_GRID}")
+    return int(grid)
 
 
 def scene_floor(scene) -> float:
@@ -540,6 +577,38 @@ def skin_pool_map(kind) -> np.ndarray:
     if n != len(out):
         raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
     return out
+
+
+def texel_table(scene) -> np.ndarray:
+    """Per texel of the scene's texel pool, in pool order, its OWNER face (mcrt_bake_texel_table): (n, 4) int32 rows
+    ``mesh, face slot, tx, ty`` — of the faces that reference the texel the one with the lowest mesh index, then the lowest face
+    slot — and ``-1, 0, -1, -1`` for a texel no face references.  The planes of a light bake are indexed like this table.  For
+    a figure of ``MeshBuilder.buildScene`` / ``DeviceScene.for_skin`` with every part present it agrees with ``skin_pool_map``
+    and ``skin_texel``."""
+    d = _as_desc(scene)
+    lib = load()
+    n = lib.mcrt_bake_texel_table(d.ptr, None, 0)
+    if n < 0:
+        raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
+    out = np.zeros((n, 4), np.int32)
+    if n and lib.mcrt_bake_texel_table(d.ptr, out.ctypes.data_as(abi.c_int32_p), n) != n:
+        raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
+    return out
+
+
+def pool_to_skin(kind, values, fill=0) -> np.ndarray:
+    """Scatters a pool-order plane of a repaintable scene (``DeviceScene.for_skin``) or of a builder figure with every part
+    present — ``values``: (n,) or (n, c) with n = 3264 for ``"S64"``, 2016 for ``"S32"`` — into a skin-shaped image
+    ``(skin_height, 64[, c])`` through ``skin_pool_map``.  Where a legacy skin maps two pool texels to one pixel (its mirrored
+    left limbs) the lowest pool index wins; pixels no pool texel is cut from hold ``fill``.  Pure numpy."""
+    h = _skin_height(kind)
+    pmap = skin_pool_map(h)
+    v = np.asarray(values)
+    if v.ndim not in (1, 2) or v.shape[0] != len(pmap):
+        raise ValueError(f"values must be ({len(pmap)},) or ({len(pmap)}, c) for this skin kind")
+    out = np.full((h * 64,) + v.shape[1:], fill, v.dtype)
+    out[pmap[::-1]] = v[::-1]  # assigned last to first: of two texels of one pixel the lowest pool index is written last
+    return out.reshape((h, 64) + v.shape[1:])
 
 
 class DeviceScene:
@@ -706,6 +775,25 @@ class DeviceScene:
         planes = abi.McrtLightPlanes(visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
         check(load().mcrt_render_light_device(self._h, C.byref(c), C.byref(planes), C.c_void_p(stream)))
 
+    @property
+    def texels(self) -> int:
+        """The size of the scene's texel pool (mcrt_scene_texels): the texels per plane of a light bake."""
+        n = C.c_int()
+        check(load().mcrt_scene_texels(self._h, C.byref(n)))
+        return int(n.value)
+
+    def bake_light_device(self, config: Config, grid: int = 1, position_ptr: int = 0, normal_ptr: int = 0, visibility_ptr: int = 0,
+                          occlusion_ptr: int = 0, direct_ptr: int = 0, stream: int = 0) -> None:
+        """The planes of a light bake into device memory (mcrt_bake_light_device): ``texels`` texels per plane in pool order —
+        visibility and occlusion 4 bytes per texel, position, normal and direct 16 — any pointer may be 0, not all.
+        Asynchronous on ``stream``; uses none of the handle's workspace, so it may run beside a render of the handle on another
+        stream.  Ordering against a repaint of the handle is the caller's job."""
+        if not (position_ptr or normal_ptr or visibility_ptr or occlusion_ptr or direct_ptr):
+            raise ValueError("give at least one of position_ptr, normal_ptr, visibility_ptr, occlusion_ptr, direct_ptr")
+        c = config.to_c()
+        planes = abi.McrtBakePlanes(position_ptr or None, normal_ptr or None, visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
+        check(load().mcrt_bake_light_device(self._h, C.byref(c), _bake_grid(grid), C.byref(planes), C.c_void_p(stream)))
+
     def pick(self, config: Config, xy) -> np.ndarray:
         """What is under the pixels ``xy`` ((n, 2) integers, x then y, inside the frame): a structured array of
         ``abi.SURFACE_DTYPE`` — mesh, face, tx, ty, t, point, normal, albedo — equal to the layers at those pixels
@@ -858,6 +946,31 @@ def render_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Co
     c = config.to_c()
     planes = abi.McrtLightPlanes(visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
     check(load().mcrt_render_light_batch_device(arr, n, C.byref(c), C.byref(planes), stride, C.c_void_p(stream)))
+
+
+def bake_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, grid: int = 1, position_ptr: int = 0, normal_ptr: int = 0,
+                            visibility_ptr: int = 0, occlusion_ptr: int = 0, direct_ptr: int = 0, texel_stride: Optional[int] = None,
+                            stream: int = 0) -> None:
+    """The light bakes of N resident scenes in one launch per kernel (mcrt_bake_light_batch_device): frame i of each plane starts
+    ``i * texel_stride`` texels on (default: the largest ``texels`` of the scenes, which may differ).  A handle may be listed more
+    than once.  Asynchronous on ``stream``."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    if not (position_ptr or normal_ptr or visibility_ptr or occlusion_ptr or direct_ptr):
+        raise ValueError("give at least one of position_ptr, normal_ptr, visibility_ptr, occlusion_ptr, direct_ptr")
+    g = _bake_grid(grid)
+    n = len(handles)
+    if texel_stride is None:
+        texel_stride = max([s.texels for s in device_scenes], default=0)
+    if int(texel_stride) < 0:
+        raise ValueError("texel_stride must be >= 0")
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    c = config.to_c()
+    planes = abi.McrtBakePlanes(position_ptr or None, normal_ptr or None, visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
+    check(load().mcrt_bake_light_batch_device(arr, n, C.byref(c), g, C.byref(planes), int(texel_stride), C.c_void_p(stream)))
 
 
 def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, skin_stride_bytes: Optional[int] = None, stream: int = 0) -> None:

@@ -142,8 +142,15 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     s->posed = false;
     for (uint32_t i = 0; i < fh->n_meshes; ++i) s->posed = s->posed || (fm[i].flags & MESH_ROTATED) != 0;
     s->host_meshes.assign(b.begin(), b.begin() + fh->mesh_offset + sizeof(FlatMesh) * fh->n_meshes);
-    hipError_t e = s->blob.reserve(b.size());
-    const size_t staging_need = b.size() + 64;  // the blob, then the lanes' flag words
+    // the owner faces of a light bake travel with the blob, 16-byte aligned behind it
+    std::vector<BakeFace> owners;
+    bake_owner_faces(b.data(), owners);
+    s->n_texels = static_cast<int>(fh->n_texels);
+    s->bake_faces_offset = (b.size() + 15) & ~static_cast<size_t>(15);
+    s->bake_n_faces = static_cast<int>(owners.size());
+    const size_t upload = s->bake_faces_offset + owners.size() * sizeof(BakeFace);
+    hipError_t e = s->blob.reserve(upload);
+    const size_t staging_need = upload + 64;  // the blob and the owner faces, then the lanes' flag words
     if (e == hipSuccess && s->staging_bytes < staging_need) {
         if (s->staging) (void)hipHostFree(s->staging);
         s->staging = nullptr;
@@ -153,7 +160,9 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     }
     if (e == hipSuccess) {
         std::memcpy(s->staging, b.data(), b.size());
-        e = hipMemcpy(s->blob.ptr, s->staging, b.size(), hipMemcpyHostToDevice);
+        std::memset(static_cast<char*>(s->staging) + b.size(), 0, s->bake_faces_offset - b.size());
+        if (!owners.empty()) std::memcpy(static_cast<char*>(s->staging) + s->bake_faces_offset, owners.data(), owners.size() * sizeof(BakeFace));
+        e = hipMemcpy(s->blob.ptr, s->staging, upload, hipMemcpyHostToDevice);
     }
     for (int i = 0; i < 4 && e == hipSuccess; ++i)
         if (!s->ev[i]) e = hipEventCreate(&s->ev[i]);
@@ -907,6 +916,63 @@ int mcrt_render_light(const mcrt_scene_desc* desc, const mcrt_config* cfg, const
     if (rc == MCRT_OK) {
         e = hipStreamSynchronize(s0->main_stream);
         if (e != hipSuccess) rc = hip_fail(e, "light render");
+    }
+    return rc;
+}
+
+// ---- light bake: the owner table (host only) and the one-shot host form (render_enqueue.cpp: bake_light_batch_device) ----------
+int mcrt_bake_texel_table(const mcrt_scene_desc* desc, int32_t (*out)[4], int capacity) {
+    std::vector<uint8_t> b;
+    std::string err;
+    if (!flatten_scene(desc, b, err)) {
+        (void)fail(MCRT_ERR_INVALID, err);
+        return -1;
+    }
+    const int n = static_cast<int>(reinterpret_cast<const FlatHeader*>(b.data())->n_texels);
+    const int fill = out ? std::min(n, capacity) : 0;
+    for (int i = 0; i < fill; ++i) out[i][0] = -1, out[i][1] = 0, out[i][2] = -1, out[i][3] = -1;
+    std::vector<BakeFace> owners;
+    bake_owner_faces(b.data(), owners);
+    for (const BakeFace& f : owners)
+        for (int rel = 0; rel < f.w * f.h && f.tex_off + rel < fill; ++rel) {
+            int32_t* o = out[f.tex_off + rel];
+            o[0] = f.code >> 3, o[1] = f.code & 7, o[2] = rel % f.w, o[3] = rel / f.w;
+        }
+    return n;
+}
+
+int mcrt_bake_light(const mcrt_scene_desc* desc, const mcrt_config* cfg, int grid, const mcrt_bake_planes* out, int device) {
+    if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all five planes are NULL");
+    if (const int rc = check_bake_config(cfg, grid, out); rc != MCRT_OK) return rc;
+    OneShotScenes set;
+    const mcrt_scene_desc* one[1] = {desc};
+    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
+    if (rc != MCRT_OK) return rc;
+    mcrt_scene* s0 = set.h[0];
+    const size_t n = static_cast<size_t>(s0->n_texels);
+    if (n == 0) return MCRT_OK;  // no texel: nothing is written
+    // the widest elements first: each plane starts on a boundary of its own element size
+    const size_t pos_bytes = out->position ? n * 16 : 0, nrm_bytes = out->normal ? n * 16 : 0, direct_bytes = out->direct ? n * 16 : 0;
+    const size_t vis_bytes = out->visibility ? ((n * 4 + 15) & ~static_cast<size_t>(15)) : 0, occ_bytes = out->occlusion ? n * 4 : 0;
+    hipError_t e = s0->frame.reserve(pos_bytes + nrm_bytes + direct_bytes + vis_bytes + occ_bytes);
+    if (e != hipSuccess) return hip_fail(e, "bake planes");
+    char* base = static_cast<char*>(s0->frame.ptr);
+    mcrt_bake_planes d{};
+    d.position = out->position ? reinterpret_cast<float*>(base) : nullptr;
+    d.normal = out->normal ? reinterpret_cast<float*>(base + pos_bytes) : nullptr;
+    d.direct = out->direct ? reinterpret_cast<float*>(base + pos_bytes + nrm_bytes) : nullptr;
+    d.visibility = out->visibility ? reinterpret_cast<float*>(base + pos_bytes + nrm_bytes + direct_bytes) : nullptr;
+    d.occlusion = out->occlusion ? reinterpret_cast<float*>(base + pos_bytes + nrm_bytes + direct_bytes + vis_bytes) : nullptr;
+    rc = bake_light_batch_device(set.h.data(), 1, cfg, grid, &d, n, s0->main_stream);
+    set.download(out->position, d.position, pos_bytes, rc);
+    set.download(out->normal, d.normal, nrm_bytes, rc);
+    set.download(out->direct, d.direct, direct_bytes, rc);
+    set.download(out->visibility, d.visibility, n * 4, rc);
+    set.download(out->occlusion, d.occlusion, occ_bytes, rc);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "light bake");
     }
     return rc;
 }

@@ -107,11 +107,18 @@ struct mcrt_scene {
     // LAYOUT: `device` and `skin_height` stay the first two ints of the struct, in this order.  The argument checks that come before
     // any device work read these two members of a handle and nothing else, and the no-device tests (tests/test_layers_abi.py,
     // tests/test_skin_paint_abi.py) hand them zeroed blocks with just these two words set; the assertion below holds the order.
+    // `n_texels`, the size of the scene's texel pool, is the third word for the same reason: a bake's stride check reads it
+    // (tests/test_bake_abi.py).
+    int n_texels = 0;
     uint32_t alpha_words = 0;
     uint32_t n_meshes = 0;
     bool posed = false;  // any mesh with MESH_ROTATED
     std::vector<uint8_t> host_meshes;  // host copy of FlatHeader + FlatMesh[] (screen bounds for workspace planning)
     DeviceBuffer blob;
+    // the owner faces of a light bake (kernels.h: BakeFace), uploaded with the blob and kept behind it in the same buffer: a
+    // repaint writes texels, alpha predicates and mesh flags only, so the list survives it; a pooled shell gets the next scene's
+    size_t bake_faces_offset = 0;
+    int bake_n_faces = 0;
     Lane lanes[kMaxLanes];
     int forced_lanes = 0;  // mcrt_scene_set_lanes: 0 = automatic
     int background = MCRT_BACKGROUND_REFERENCE;  // mcrt_scene_set_background
@@ -161,6 +168,7 @@ struct mcrt_scene {
 };
 
 static_assert(offsetof(mcrt_scene, device) == 0 && offsetof(mcrt_scene, skin_height) == sizeof(int), "mcrt_scene: device, then skin_height (see the member)");
+static_assert(offsetof(mcrt_scene, n_texels) == 2 * sizeof(int), "mcrt_scene: n_texels is the third word (see the member)");
 
 namespace mcrt_host {
 
@@ -195,6 +203,18 @@ inline bool no_plane(const mcrt_light_planes* l) { return !l->visibility && !l->
 inline int check_light_config(const mcrt_config* c, const mcrt_light_planes* out) {
     if (c->soft_shadows && c->shadow_samples > mcrt::kLightMaxSamples)
         return fail(MCRT_ERR_INVALID, "a light pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
+    if (out->occlusion && (c->ao_samples < 1 || c->ao_samples > mcrt::kLightMaxSamples))
+        return fail(MCRT_ERR_INVALID, "the occlusion plane takes 1 to 113 ao_samples (the truncated engine's 227 draws, two per sample)");
+    if (out->occlusion && !std::isfinite(c->ao_radius)) return fail(MCRT_ERR_INVALID, "ao_radius must be finite");
+    return MCRT_OK;
+}
+
+inline bool no_plane(const mcrt_bake_planes* b) { return !b->position && !b->normal && !b->visibility && !b->occlusion && !b->direct; }
+// what a light bake refuses of its grid and config (every entry point, before any device work): the light pass's limits
+inline int check_bake_config(const mcrt_config* c, int grid, const mcrt_bake_planes* out) {
+    if (grid < 1 || grid > mcrt::kBakeMaxGrid) return fail(MCRT_ERR_INVALID, "grid must be 1 to 4 (sub-samples per texel and axis)");
+    if (c->soft_shadows && c->shadow_samples > mcrt::kLightMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a light bake takes at most 113 shadow samples (the truncated engine's 227 draws)");
     if (out->occlusion && (c->ao_samples < 1 || c->ao_samples > mcrt::kLightMaxSamples))
         return fail(MCRT_ERR_INVALID, "the occlusion plane takes 1 to 113 ao_samples (the truncated engine's 227 draws, two per sample)");
     if (out->occlusion && !std::isfinite(c->ao_radius)) return fail(MCRT_ERR_INVALID, "ao_radius must be finite");
@@ -267,6 +287,7 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
 int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_reflection* d_out,
                                    size_t stride, hipStream_t stream);
 int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes* d_out, size_t stride, hipStream_t stream);
+int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "launch_shapes.h"
 #include "mcrt.h"
 
@@ -348,6 +350,54 @@ int shade_batch_view(ShadeFrame* frames, const int* views, int n);
 size_t shade_lds_bytes(const ShadeFrame& f, const ShadeShape& shape);  // hit records, masks, counts and sample positions
 size_t occlusion_lds_bytes(const ShadeFrame& f);                         // hit records, masks, the traced list and the values
 
+// ---- light bake (mcrt_bake_light_device & co): the light layers' terms per TEXEL of the scene's pool, at points of the texel on
+// its owner face (include/mcrt.h, "light bake") — no camera, no tiles.  Reads the scene blob, the handle's owner-face list and
+// the device's seed tables.
+// One owner face: the pool texels tex_off .. tex_off + w * h - 1 are baked on face `code & 7` of mesh `code >> 3`
+struct BakeFace {
+    int32_t tex_off, w, h, code;
+};
+// The owner faces of the flattened scene `blob` (header and mesh table are read), sorted by tex_off: of the faces that share a
+// texture the one with the lowest mesh index, then the lowest face slot.  Their ranges are disjoint (flatten.cpp gives every
+// texture a range of its own).
+void bake_owner_faces(const uint8_t* blob, std::vector<BakeFace>& out);
+// One frame of a bake: its scene, its owner faces and its planes (any may be NULL, not all), n_texels texels each
+struct BakeFrame {
+    const uint8_t* scene;
+    const BakeFace* faces;            // device memory, behind the handle's blob
+    int n_faces, n_texels;
+    float4* position;                 // the texel centre's P, w = 1 live / 0 dead; zero without an owner
+    float4* normal;                   // N, w = 0; zero without an owner
+    float* visibility;                // mean of the sub-samples' shadow factors; 1.0f for a dead texel
+    float* occlusion;                 // mean of computeAO; 1.0f for a dead texel
+    float* direct;                    // 4 floats per texel: mean of shade(); zero for a dead texel
+    const uint32_t* seed_table;       // as ShadeFrame's
+    const uint32_t* seed_table_full;
+    int lds_alpha_words;              // scene tables staged in LDS, as LayersFrame's
+    int lds_face_entries;
+};
+constexpr int kBakeMaxGrid = 4;
+// what the frames of one launch share
+struct BakeShape {
+    int grid;              // q: q * q sub-samples per texel
+    int samples;           // S: shadow_samples when soft_shadows && shadow_samples > 1, else 1
+    int pass;              // undecided points whose S sample positions fit the block's LDS area at once
+    int ao_samples;        // A (read by `bake_occlusion` alone)
+    float ao_radius;
+    int bundle_decisions;  // as RenderParams'
+    int inside_fast;
+    int max_units;         // work units (256 pool texels) of the largest frame
+    int geometry;          // set per launch: this kernel writes the position and normal planes
+    int rays;              // `bake_shade`: visibility or direct is asked for (otherwise it writes position / normal alone)
+};
+void make_bake_shape(const mcrt_config& cfg, int grid, bool bundle_decisions, bool inside_fast, int max_texels, BakeShape& shape);
+// fills f.lds_* and returns the kernel variant by the layers' rule
+int bake_view(BakeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
+int bake_batch_view(BakeFrame* frames, const int* views, int n);
+// dynamic LDS of the two launches: the frame's scene tables, then the block's area
+size_t bake_shade_lds_bytes(const BakeFrame& f, const BakeShape& shape);  // point records, texel records, masks, counts and sample positions
+size_t bake_occlusion_lds_bytes(const BakeFrame& f);                         // point records, texel records, masks, the traced list and the values
+
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): a repaintable handle's blob holds the full mesh table of
 // its skin kind, so texel i of its pool is cut from one fixed pixel of the skin image.  One workgroup per scene rewrites what
 // a skin decides of the blob: the float4 texel pool (u8 / 255.0f through a table the HOST formed), the 2-bit alpha predicates
@@ -396,7 +446,7 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
-// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, skin repaints ========
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, light bake, skin repaints ========
 hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's LDS tables
@@ -417,6 +467,13 @@ hipError_t launch_light(const ShadeFrame& f, const ShadeShape& shape, int view, 
 // frames of a call share their planes) and the largest frame's shade_lds_bytes / occlusion_lds_bytes
 hipError_t launch_light_batch(const ShadeFrame* d_table, int n_frames, const ShadeShape& shape, int view, bool shade, size_t shade_dyn, bool occlusion,
                               size_t occlusion_dyn, hipStream_t stream);
+// `bake_shade` where visibility, direct or no occlusion plane is asked for, then `bake_occlusion` where f.occlusion; position and
+// normal are written by the first kernel that runs
+hipError_t launch_bake(const BakeFrame& f, const BakeShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; which kernels run (the
+// frames of a call share their planes) and the largest frame's bake_shade_lds_bytes / bake_occlusion_lds_bytes
+hipError_t launch_bake_batch(const BakeFrame* d_table, int n_frames, const BakeShape& shape, int view, bool shade, size_t shade_dyn, bool occlusion,
+                             size_t occlusion_dyn, hipStream_t stream);
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);

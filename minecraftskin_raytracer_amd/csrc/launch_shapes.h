@@ -57,6 +57,12 @@ constexpr int kShadePosBytes = 8 * 1024;  // light layers, `shade`: LDS for the 
 constexpr int kShadeFixedBytes = kBlock * (48 + 8 + 8 + 4 + 4);
 // `occlusion`: per lane a hit record of two float4 (point, normal), the candidate mask, the traced list, the value
 constexpr int kOcclusionFixedBytes = kBlock * (32 + 8 + 4 + 4);
+constexpr int kBakePosBytes = 8 * 1024;  // light bake, `bake_shade`: LDS for the sample positions of the undecided points of one pass
+// `bake_shade`: per lane a point record of two float4 (point, normal), a texel record of two (colour; owner face, texel, size), candidate and
+// inside masks, lit counts, the undecided list
+constexpr int kBakeShadeFixedBytes = kBlock * (32 + 32 + 8 + 8 + 4 + 4);
+// `bake_occlusion`: per lane a point record, the owner-face half of the texel record, the candidate mask, the traced list, the value
+constexpr int kBakeOcclusionFixedBytes = kBlock * (32 + 16 + 8 + 4 + 4);
 
 // Workgroups per frame of a batched launch.  Every kernel strides over its frame's device-side work, so the grid only
 // shapes the schedule: a batch aims at kBatchTarget workgroups per launch (8 per CU of the 256 — twice what the largest

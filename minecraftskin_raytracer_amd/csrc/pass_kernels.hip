@@ -1,5 +1,5 @@
 // pass_kernels.hip — the stand-alone passes over a resident scene (not stages of a render): geometry layers and pixel
-// picks, the ground shadow, the ground reflection, the light layers, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
+// picks, the ground shadow, the ground reflection, the light layers, the light bake, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
 // and nothing else: no workspace, no counters.
 #include "kernel_common.h"
 
@@ -1128,6 +1128,413 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void occlusion_batch_kernel(S
     occlusion_body<kView>(*(const ShadeFrame*)(table + blockIdx.y), sh);
 }
 
+// ---------------------------------------------------------------------------------------------
+// light bake (kernels.h: BakeFrame; include/mcrt.h, "light bake"): the light layers' terms per TEXEL of the scene's pool, at
+// the q x q sub-sample points of the texel on its owner face — no camera, no tile, no culling.  Two kernels, for the reason of
+// the light layers.  No workspace.
+// `bake_shade` (visibility and direct), a workgroup per 256 consecutive pool texels (grid-stride), in phases handed over through LDS:
+//   1 lane / texel               owner face by a binary search of the handle's face list, texel colour; position and normal
+//                                planes; the LIVE texels (an owner, alpha != 0) are packed onto the block's first lanes as
+//                                records in LDS (owner face, texel and size; colour)
+//   then per sub-sample (j outer, i inner), the steps of `shade` with the sub-sample's P, N in place of the hit:
+//   1 lane / live texel          P, N; the whole-bundle decision from P + N * 1e-3f; the undecided are packed again
+//   1 lane / undecided point     truncated mt19937 at depth 0 → the S disk sample positions in LDS
+//   1 lane / (undecided point, light sample)   exact any-hit test on the candidates → lit count by ballot
+//   1 lane / live texel          visibility = lit / S (one ray in the hard modes), shade with the view vector N; both are
+//                                ADDED to the lane's sums in the order the header defines
+//   1 lane / texel               the means return through LDS; the planes: 16 bytes per store where the alignment allows
+// `bake_occlusion`: the same lookup and packing, then per sub-sample the steps of `occlusion`.
+// ---------------------------------------------------------------------------------------------
+struct BakeTexel {  // a pool texel on its owner face
+    int code;       // mesh * 8 + face slot; -1: no face references the texel
+    int tx, ty, w, h;
+};
+__device__ __forceinline__ BakeTexel bake_owner(const BakeFace* __restrict__ faces, const int n_faces, const int texel) {
+    int lo = 0, hi = n_faces;  // the faces before `lo` start at or before the texel, those from `hi` on behind it
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (faces[mid].tex_off <= texel)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    BakeTexel t{-1, -1, -1, 0, 0};
+    if (lo > 0) {
+        const BakeFace f = faces[lo - 1];
+        const int rel = texel - f.tex_off;
+        if (rel < f.w * f.h) {
+            t.code = f.code, t.w = f.w, t.h = f.h;
+            t.ty = rel / f.w;
+            t.tx = rel - t.ty * f.w;
+        }
+    }
+    return t;
+}
+// sub-sample (i, j) of q x q of the texel: the world point and the normal of a front hit there (include/mcrt.h: the inverse of
+// face_uv on the face's plane, then hit_scene's forward rotation for a posed mesh)
+template <class SV>
+__device__ __forceinline__ void bake_point(const SV& sc, const BakeTexel& t, const int i, const int j, const int q, V3& P, V3& N) {
+    const int mesh = t.code >> 3, face = t.code & 7;
+    const int axis = face < 2 ? 2 : (face < 4 ? 0 : 1);
+    const bool neg = face == 0 || face == 3 || face == 5;
+    const MeshData m = mesh_lane(sc, mesh);
+    const float u = (static_cast<float>(t.tx) + (static_cast<float>(i) + 0.5f) / static_cast<float>(q)) / static_cast<float>(t.w);
+    const float v = (static_cast<float>(t.ty) + (static_cast<float>(j) + 0.5f) / static_cast<float>(q)) / static_cast<float>(t.h);
+    const V3 lo = m.lo, hi = m.hi, ext = hi - lo;
+    V3 p;
+    if (axis == 2) {
+        const float lx = neg ? (1.0f - u) : u, ly = 1.0f - v;
+        p = mk(lo.x + lx * ext.x, lo.y + ly * ext.y, neg ? lo.z : hi.z);
+    } else if (axis == 0) {
+        const float lz = neg ? u : (1.0f - u), ly = 1.0f - v;
+        p = mk(neg ? lo.x : hi.x, lo.y + ly * ext.y, lo.z + lz * ext.z);
+    } else {
+        const float lx = u, lz = neg ? (1.0f - v) : v;
+        p = mk(lo.x + lx * ext.x, neg ? lo.y : hi.y, lo.z + lz * ext.z);
+    }
+    P = p;
+    N = face_normal(axis, neg);
+    if (SV::kPosed && (m.flags & MESH_ROTATED)) {
+        P = to_world(m, p);
+        N = normalize(spin(N, mk(0.0f, 0.0f, 0.0f), (m.flags & MESH_APPLY_X) != 0, m.fwd_x_cos, m.fwd_x_sin, (m.flags & MESH_APPLY_Z) != 0, m.fwd_z_cos,
+                           m.fwd_z_sin));
+    }
+}
+// one value per texel into a plane: 16 bytes per four consecutive texels where `quads` (the plane is 16-byte aligned at the
+// frame's first texel) and all four are texels of the frame
+__device__ __forceinline__ void bake_store_plane(float* __restrict__ plane, const bool quads, const int texel, const int n_texels, const int lane, const float val) {
+    const float v1 = __shfl_down(val, 1), v2 = __shfl_down(val, 2), v3 = __shfl_down(val, 3);
+    if (quads && (texel | 3) < n_texels) {
+        if ((lane & 3) == 0) *reinterpret_cast<float4*>(plane + texel) = make_float4(val, v1, v2, v3);
+    } else if (texel < n_texels) {
+        plane[texel] = val;
+    }
+}
+__device__ __forceinline__ void bake_store4(float* __restrict__ plane, const bool vec, const int texel, const float4 val) {
+    if (vec) {
+        reinterpret_cast<float4*>(plane)[texel] = val;
+    } else {
+        float* o = plane + static_cast<size_t>(texel) * 4;
+        o[0] = val.x, o[1] = val.y, o[2] = val.z, o[3] = val.w;
+    }
+}
+// the first phase of both kernels: this lane's texel, its owner and colour, the position and normal planes
+struct BakeLane {
+    int texel;
+    bool valid, live;
+    BakeTexel t;
+    float4 tex;
+};
+template <class SV>
+__device__ __forceinline__ BakeLane bake_lane(const BakeFrame& __restrict__ f, const SceneView& scg, const SV& sc, const int unit, const int tid, const bool geometry) {
+    BakeLane b;
+    b.texel = unit * kBlock + tid;
+    b.valid = b.texel < f.n_texels;
+    b.t = BakeTexel{-1, -1, -1, 0, 0};
+    b.tex = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (b.valid) {
+        b.t = bake_owner(f.faces, f.n_faces, b.texel);
+        b.tex = scg.texels[b.texel];
+    }
+    const bool owned = b.t.code >= 0;
+    b.live = owned && !(b.tex.w == 0.0f);
+    if (geometry && b.valid) {
+        float4 pos = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nrm = pos;
+        if (owned) {
+            V3 P, N;
+            bake_point(sc, b.t, 0, 0, 1, P, N);
+            pos = make_float4(P.x, P.y, P.z, b.live ? 1.0f : 0.0f);
+            nrm = make_float4(N.x, N.y, N.z, 0.0f);
+        }
+        if (f.position) bake_store4(reinterpret_cast<float*>(f.position), (reinterpret_cast<uintptr_t>(f.position) & 15u) == 0, b.texel, pos);
+        if (f.normal) bake_store4(reinterpret_cast<float*>(f.normal), (reinterpret_cast<uintptr_t>(f.normal) & 15u) == 0, b.texel, nrm);
+    }
+    return b;
+}
+template <int kView>
+__device__ __forceinline__ void bake_shade_body(const BakeFrame& __restrict__ f, const BakeShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][point records: 2 planes of float4][texel records: colour, owner][candidate masks][inside masks][lit counts][undecided list][positions: pass x S x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const int n_units = (f.n_texels + kBlock - 1) / kBlock;
+    if (static_cast<int>(blockIdx.x) >= n_units) return;  // (uniform; before the collective staging: the frames of a batch differ in size)
+    const SceneView scg = view_of(f.scene);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const V3 lpos = ld3(scg.hdr->light_pos);
+    const float lradius = scg.hdr->light_radius;
+    const int S = sh.samples, q = sh.grid;
+    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
+    const bool raw_normal = S > 1;  // computeSoftShadow takes the normal as it is; shade()'s own test normalises it (shading.cpp:76-80)
+    const float R = soft ? lradius : 0.0f;
+    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per point
+    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
+    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: point; 1: normal
+    float4* s_tex = s_rec + 2 * kBlock;               // the live texel's colour — then its mean colour
+    int4* s_own = reinterpret_cast<int4*>(s_tex + kBlock);  // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
+    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(s_own + kBlock);
+    unsigned long long* s_ins = s_cand + kBlock;
+    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_ins + kBlock);  // lit counts — then the texel's mean visibility, bit-cast
+    uint32_t* s_und = s_lit + kBlock;
+    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    const bool quads_vis = (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
+    const bool vec_direct = (reinterpret_cast<uintptr_t>(f.direct) & 15u) == 0;
+    typename ViewSel<kView>::type sc;
+    if constexpr (kView == kViewHbm) {
+        sc = scg;
+    } else {
+        const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+        sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+    }
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        // ---- a lane per texel: owner, colour, the geometry planes; the live texels are packed
+        const BakeLane b = bake_lane(f, scg, sc, unit, tid, sh.geometry != 0);
+        if (!sh.rays) continue;  // uniform: position / normal alone
+        float vis = 1.0f;
+        C4 col{0.0f, 0.0f, 0.0f, 0.0f};
+        int n_live = 0;
+        const int rank = block_rank(b.live, s_wcnt, n_live);
+        if (b.live) {
+            s_tex[rank] = b.tex;
+            s_own[rank] = make_int4(b.t.code, b.t.ty * b.t.w + b.t.tx, b.t.w, b.t.h);
+        }
+        if (n_live) {  // uniform
+            __syncthreads();
+            const bool mine = tid < n_live;
+            BakeTexel t{-1, -1, -1, 0, 0};
+            Hit hit;
+            hit.hit = true;
+            float vsum = 0.0f;
+            C4 csum{0.0f, 0.0f, 0.0f, 0.0f};
+            if (mine) {
+                const int4 o = s_own[tid];
+                const float4 c = s_tex[tid];
+                t.code = o.x, t.w = o.z, t.h = o.w;
+                t.ty = o.y / o.z;
+                t.tx = o.y - t.ty * o.z;
+                hit.tex = C4{c.x, c.y, c.z, c.w};
+                hit.outer = (mesh_lane(sc, o.x >> 3).flags & MESH_OUTER) != 0;
+            }
+            for (int sub = 0; sub < q * q; ++sub) {  // uniform: j outer, i inner
+                const int sj = sub / q, si = sub - sj * q;
+                // ---- a lane per live texel: the sub-sample's point and the whole-bundle decision of its shadow rays
+                bool undecided = false;
+                uint32_t lit = 0u;
+                if (mine) {
+                    bake_point(sc, t, si, sj, q, hit.p, hit.n);
+                    s_rec[tid] = make_float4(hit.p.x, hit.p.y, hit.p.z, 0.0f);
+                    s_rec[kBlock + tid] = make_float4(hit.n.x, hit.n.y, hit.n.z, 0.0f);
+                    const V3 O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
+                    unsigned long long cand;
+                    const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
+                    undecided = known < 0;
+                    s_cand[tid] = cand;
+                    s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
+                    if (!undecided) lit = static_cast<uint32_t>(known);
+                }
+                s_lit[tid] = 0u;
+                int total = 0;
+                const int urank = block_rank(undecided, s_wcnt, total);
+                if (undecided) s_und[urank] = static_cast<uint32_t>(tid);
+                const uint32_t n_und = static_cast<uint32_t>(total);
+                if (n_und) __syncthreads();  // uniform
+                for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
+                    const uint32_t nu = min(pass, n_und - u0);
+                    if (u0) __syncthreads();  // the previous pass's rays have read the positions
+                    // ---- a lane per undecided point: its mt19937 stream at depth 0 and the S disk sample positions
+                    if (soft && static_cast<uint32_t>(tid) < nu) {
+                        const float4 a = s_rec[s_und[u0 + tid]];
+                        disk_sample_positions(scg, f.seed_table, nullptr, mk(a.x, a.y, a.z), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
+                    }
+                    __syncthreads();
+                    // ---- a lane per (undecided point, light sample); every lane of a wave runs the same number of turns (ballot inside)
+                    const uint32_t n_rays = nu * pairs;
+                    for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
+                        const uint32_t qi = q0 + static_cast<uint32_t>(lane);
+                        bool visible = false;
+                        uint32_t k = 0;
+                        if (qi < n_rays) {
+                            k = s_und[u0 + qi / pairs];
+                            const float4 a = s_rec[k], nb = s_rec[kBlock + k];
+                            V3 Nk = mk(nb.x, nb.y, nb.z);
+                            if (!raw_normal) Nk = normalize(Nk);
+                            const V3 target = soft ? ld3(s_pos + static_cast<size_t>(qi) * 3) : lpos;
+                            visible = !in_shadow_masked(sc, mk(a.x, a.y, a.z), Nk, target, s_cand[k], s_ins[k]);
+                        }
+                        if (pow2) {
+                            const unsigned long long bal = __ballot(visible);
+                            if (qi < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
+                                const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
+                                s_lit[k] = static_cast<uint32_t>(__popcll(grp));
+                            }
+                        } else if (visible) {
+                            atomicAdd(&s_lit[k], 1u);
+                        }
+                    }
+                }
+                if (n_und) __syncthreads();  // the counts are complete; nothing of this sub-sample is read across lanes any more
+                if (undecided) lit = s_lit[tid];
+                // ---- a lane per live texel: the visibility term and shade, added in the defined order
+                if (mine) {
+                    const float v = soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    const C4 c = shade(scg, hit, hit.n, v);
+                    if (sub == 0) {
+                        vsum = v, csum = c;
+                    } else {
+                        vsum = vsum + v;
+                        csum = C4{csum.r + c.r, csum.g + c.g, csum.b + c.b, csum.a + c.a};
+                    }
+                }
+            }
+            if (mine) {
+                if (q > 1) {
+                    const float d = static_cast<float>(q * q);
+                    vsum = vsum / d;
+                    csum = C4{csum.r / d, csum.g / d, csum.b / d, csum.a / d};
+                }
+                s_lit[tid] = __float_as_uint(vsum);  // (entry and record tid are this lane's alone by now)
+                s_tex[tid] = make_float4(csum.r, csum.g, csum.b, csum.a);
+            }
+            __syncthreads();
+            if (b.live) {
+                const float4 c = s_tex[rank];
+                vis = __uint_as_float(s_lit[rank]);
+                col = C4{c.x, c.y, c.z, c.w};
+            }
+            // (the next unit writes its records behind the two barriers of its block_rank)
+        }
+        // ---- a lane per texel: the planes
+        if (f.visibility) bake_store_plane(f.visibility, quads_vis, b.texel, f.n_texels, lane, vis);
+        if (f.direct && b.valid) bake_store4(f.direct, vec_direct, b.texel, make_float4(col.r, col.g, col.b, col.a));
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void bake_shade_kernel(const BakeFrame f, const BakeShape sh) {
+    bake_shade_body<kView>(f, sh);
+}
+using BakeTable = const __attribute__((address_space(4))) BakeFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void bake_shade_batch_kernel(BakeTable table, const BakeShape sh) {
+    bake_shade_body<kView>(*(const BakeFrame*)(table + blockIdx.y), sh);
+}
+template <int kView>
+__device__ __forceinline__ void bake_occlusion_body(const BakeFrame& __restrict__ f, const BakeShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][point records: 2 planes of float4][texel records: owner][candidate masks][traced list][values]
+    __shared__ int s_wcnt[kBlock / 64];
+    const int n_units = (f.n_texels + kBlock - 1) / kBlock;
+    if (static_cast<int>(blockIdx.x) >= n_units) return;  // (uniform; before the collective staging)
+    const SceneView scg = view_of(f.scene);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int A = sh.ao_samples, q = sh.grid;
+    const float radius = sh.ao_radius;
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: point; 1: normal
+    int4* s_own = reinterpret_cast<int4*>(s_rec + 2 * kBlock);  // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
+    unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(s_own + kBlock);
+    uint32_t* s_list = reinterpret_cast<uint32_t*>(s_mask + kBlock);
+    float* s_val = reinterpret_cast<float*>(s_list + kBlock);
+    const bool quads = (reinterpret_cast<uintptr_t>(f.occlusion) & 15u) == 0;
+    typename ViewSel<kView>::type sc;
+    if constexpr (kView == kViewHbm) {
+        sc = scg;
+    } else {
+        const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+        sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+    }
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        // ---- a lane per texel: owner, colour, the geometry planes; the live texels are packed
+        const BakeLane b = bake_lane(f, scg, sc, unit, tid, sh.geometry != 0);
+        float occ = 1.0f;
+        int n_live = 0;
+        const int rank = block_rank(b.live, s_wcnt, n_live);
+        if (b.live) s_own[rank] = make_int4(b.t.code, b.t.ty * b.t.w + b.t.tx, b.t.w, b.t.h);
+        if (n_live) {  // uniform
+            __syncthreads();
+            const bool mine = tid < n_live;
+            BakeTexel t{-1, -1, -1, 0, 0};
+            float sum = 0.0f;
+            if (mine) {
+                const int4 o = s_own[tid];
+                t.code = o.x, t.w = o.z, t.h = o.w;
+                t.ty = o.y / o.z;
+                t.tx = o.y - t.ty * o.z;
+            }
+            for (int sub = 0; sub < q * q; ++sub) {  // uniform: j outer, i inner
+                const int sj = sub / q, si = sub - sj * q;
+                // ---- a lane per live texel: the sub-sample's point and the meshes a ray of its hemisphere can meet (`ao`, step 1)
+                bool traced = false;
+                if (mine) {
+                    V3 P, Nr;
+                    bake_point(sc, t, si, sj, q, P, Nr);
+                    s_rec[tid] = make_float4(P.x, P.y, P.z, 0.0f);
+                    s_rec[kBlock + tid] = make_float4(Nr.x, Nr.y, Nr.z, 0.0f);
+                    const V3 N = normalize(Nr);
+                    const unsigned long long cand = hemisphere_candidates<kPosed>(scg, P + N * 1e-3f, N, radius);
+                    s_mask[tid] = cand;
+                    traced = cand != 0ull || scg.n_meshes > 64;  // meshes beyond the mask are tested per ray
+                    if (!traced) s_val[tid] = 1.0f;  // 0 occluded
+                }
+                int total = 0;
+                const int trank = block_rank(traced, s_wcnt, total);
+                if (traced) s_list[trank] = static_cast<uint32_t>(tid);
+                __syncthreads();
+                // ---- a lane per traced point: its mt19937 stream, the A directions and their any-hit tests (`ao`, step 3)
+                if (tid < total) {
+                    const uint32_t k = s_list[tid];
+                    const float4 a = s_rec[k], nb = s_rec[kBlock + k];
+                    const V3 P = mk(a.x, a.y, a.z), N = normalize(mk(nb.x, nb.y, nb.z));
+                    const V3 T = (__builtin_fabsf(N.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), N)) : normalize(cross(mk(0, 1, 0), N));
+                    const V3 B = cross(N, T);
+                    const unsigned long long cand = s_mask[k];
+                    const V3 O = P + N * 1e-3f;
+                    const unsigned long long inside = sh.inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the point starts there
+                    MtShort rng;
+                    const uint32_t seed = ao_seed(P);
+                    if (f.seed_table_full)
+                        rng.seed_known(seed, f.seed_table_full[seed]);  // mt[397] of this seed: one load instead of the 397-step recurrence
+                    else
+                        rng.seed(seed);
+                    uint32_t occluded = 0;
+                    for (int s = 0; s < A; ++s) {
+                        const float r1 = rng.uniform();
+                        const float r2 = rng.uniform();
+                        const float sinT = sqrt_pos(1.0f - r1);
+                        const float cosT = sqrt_pos(r1);
+                        float sn, cs;
+                        mcrt_sincosf(kTwoPi * r2, &sn, &cs);
+                        const V3 local = mk(sinT * cs, cosT, sinT * sn);
+                        const V3 world = normalize(T * local.x + N * local.y + B * local.z);
+                        if (any_hit_masked(sc, Ray{O, world}, radius, cand, inside)) ++occluded;
+                    }
+                    s_val[k] = 1.0f - static_cast<float>(occluded) / static_cast<float>(A);  // raytracer.cpp:77
+                }
+                __syncthreads();
+                if (mine) {
+                    const float v = s_val[tid];
+                    sum = sub == 0 ? v : sum + v;
+                }
+                // (the next sub-sample writes this lane's own entries; its lists are read behind the barriers of its block_rank)
+            }
+            if (mine) s_val[tid] = q > 1 ? sum / static_cast<float>(q * q) : sum;
+            __syncthreads();
+            if (b.live) occ = s_val[rank];
+            // (the next unit writes its records behind the two barriers of its block_rank)
+        }
+        // ---- a lane per texel: the plane
+        bake_store_plane(f.occlusion, quads, b.texel, f.n_texels, lane, occ);
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void bake_occlusion_kernel(const BakeFrame f, const BakeShape sh) {
+    bake_occlusion_body<kView>(f, sh);
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void bake_occlusion_batch_kernel(BakeTable table, const BakeShape sh) {
+    bake_occlusion_body<kView>(*(const BakeFrame*)(table + blockIdx.y), sh);
+}
+
 // ---- host-side launchers (the shapes and LDS sizes they take: render_plan.cpp) ----------------------
 // One launch of a tile pass (layers, ground) over the tile grid `tiles`.  arg: the frame, or the device table of n_frames
 // frames (blockIdx.y = frame); kernel_of(view tag): the kernel of that variant; dyn: its dynamic LDS, hbm_dyn: the HBM
@@ -1190,6 +1597,46 @@ hipError_t launch_light_batch(const ShadeFrame* d_table, int n_frames, const Sha
     if (e == hipSuccess && occlusion)
         e = launch_tile_pass(ShadeTable(d_table), n_frames, shape, shape.tiles, view, occlusion_dyn, occlusion_dyn, stream,
                              [](auto v) { return occlusion_batch_kernel<decltype(v)::value>; });
+    return e;
+}
+// ---- light bake (kernels.h): a workgroup per 256 pool texels of the largest frame; `bake_shade` when visibility or direct is asked
+// for — or no occlusion plane, then for position / normal alone —, `bake_occlusion` when that plane is; position and normal by the
+// first kernel that runs
+template <class Arg, class KernelOf>
+static hipError_t launch_bake_pass(const Arg& arg, int n_frames, const BakeShape& shape, int view, size_t dyn, hipStream_t stream, KernelOf kernel_of) {
+    if (shape.max_units <= 0 || n_frames <= 0) return hipSuccess;
+    if (n_frames > kLayersBatchMaxFrames || shape.grid < 1 || shape.grid > kBakeMaxGrid) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>(shape.max_units < kLayersGrid ? shape.max_units : kLayersGrid), static_cast<unsigned>(n_frames));
+    with_view(view, [&](auto v) { hipLaunchKernelGGL(kernel_of(v), grid, dim3(kBlock), dyn, stream, arg, shape); });
+    return hipGetLastError();
+}
+hipError_t launch_bake(const BakeFrame& f, const BakeShape& shape, int view, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    BakeShape sh = shape;
+    const bool shade = f.visibility || f.direct || !f.occlusion;
+    if (shade) {
+        sh.geometry = 1, sh.rays = (f.visibility || f.direct) ? 1 : 0;
+        e = launch_bake_pass(f, 1, sh, view, bake_shade_lds_bytes(f, sh), stream, [](auto v) { return bake_shade_kernel<decltype(v)::value>; });
+    }
+    if (e == hipSuccess && f.occlusion) {
+        sh.geometry = shade ? 0 : 1, sh.rays = 1;
+        e = launch_bake_pass(f, 1, sh, view, bake_occlusion_lds_bytes(f), stream, [](auto v) { return bake_occlusion_kernel<decltype(v)::value>; });
+    }
+    return e;
+}
+hipError_t launch_bake_batch(const BakeFrame* d_table, int n_frames, const BakeShape& shape, int view, bool shade, size_t shade_dyn, bool occlusion,
+                             size_t occlusion_dyn, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    BakeShape sh = shape;
+    const bool first = shade || !occlusion;
+    if (first) {
+        sh.geometry = 1, sh.rays = shade ? 1 : 0;
+        e = launch_bake_pass(BakeTable(d_table), n_frames, sh, view, shade_dyn, stream, [](auto v) { return bake_shade_batch_kernel<decltype(v)::value>; });
+    }
+    if (e == hipSuccess && occlusion) {
+        sh.geometry = first ? 0 : 1, sh.rays = 1;
+        e = launch_bake_pass(BakeTable(d_table), n_frames, sh, view, occlusion_dyn, stream, [](auto v) { return bake_occlusion_batch_kernel<decltype(v)::value>; });
+    }
     return e;
 }
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {

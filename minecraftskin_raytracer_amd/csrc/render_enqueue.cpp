@@ -465,6 +465,23 @@ int shade_frame_of(const mcrt_scene* s, const mcrt_light_planes& out, size_t ind
     f.seed_table_full = s->seed_table_full;
     return shade_view(f, s->alpha_words, s->n_meshes, s->posed);
 }
+// and for a light bake (mcrt_bake_light_device & co): the planes `index * stride` TEXELS on, the handle's owner faces behind its blob
+int bake_frame_of(const mcrt_scene* s, const mcrt_bake_planes& out, size_t index, size_t stride, BakeFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.faces = reinterpret_cast<const BakeFace*>(static_cast<const uint8_t*>(s->blob.ptr) + s->bake_faces_offset);
+    f.n_faces = s->bake_n_faces;
+    f.n_texels = s->n_texels;
+    f.position = out.position ? reinterpret_cast<float4*>(out.position + off * 4) : nullptr;
+    f.normal = out.normal ? reinterpret_cast<float4*>(out.normal + off * 4) : nullptr;
+    f.visibility = out.visibility ? out.visibility + off : nullptr;
+    f.occlusion = out.occlusion ? out.occlusion + off : nullptr;
+    f.direct = out.direct ? out.direct + off * 4 : nullptr;
+    f.seed_table = s->seed_table;
+    f.seed_table_full = s->seed_table_full;
+    return bake_view(f, s->alpha_words, s->n_meshes, s->posed);
+}
 
 // What the layers and the ground entry points check alike, before any device work (only the last check looks inside the
 // handles, at their device index).  run = false with MCRT_OK: zero tiles, nothing is written.
@@ -826,6 +843,46 @@ int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_confi
         [&](const ShadeFrame* d_table, int m) { return launch_light_batch(d_table, m, shape, view, shade, shade_dyn, occlusion, occlusion_dyn, stream); });
 }
 
+// ---- light bake (mcrt_bake_light_device & co): the light pass's host path over the texel pool instead of a frame — two kernels
+// over one frame record, the scene blob, the handle's owner faces and the device's seed tables; no workspace, no counters and none
+// of the handle's events.  No frame size enters: what check_pass_arguments checks of the other arguments is checked here.
+int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream) {
+    // argument checks, before any device work (only the last ones look inside the handles: device index and texel count)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all five planes are NULL");
+    if (const int rc = check_bake_config(cfg, grid, d_out); rc != MCRT_OK) return rc;
+    if (n == 0) return MCRT_OK;
+    const int device = scenes[0]->device;
+    int max_texels = 0;
+    for (int i = 0; i < n; ++i) {
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+        if (scenes[i]->n_texels > 0 && stride < static_cast<size_t>(scenes[i]->n_texels)) return fail(MCRT_ERR_INVALID, "texel_stride is smaller than a scene's texel count");
+        max_texels = std::max(max_texels, scenes[i]->n_texels);
+    }
+    if (max_texels <= 0) return MCRT_OK;  // no texel: nothing is written
+    static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
+    BakeShape shape;
+    make_bake_shape(*cfg, grid, decisions, inside_fast, max_texels, shape);
+    HIP_TRY(hipSetDevice(device));
+    const bool shade = d_out->visibility || d_out->direct, occlusion = d_out->occlusion != nullptr;
+    std::vector<BakeFrame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        if (occlusion) share_full_seed_table(scenes[i]);
+        views[static_cast<size_t>(i)] = bake_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
+    }
+    const int view = bake_batch_view(frames.data(), views.data(), n);
+    size_t shade_dyn = 0, occlusion_dyn = 0;
+    for (const BakeFrame& f : frames) shade_dyn = std::max(shade_dyn, bake_shade_lds_bytes(f, shape)), occlusion_dyn = std::max(occlusion_dyn, bake_occlusion_lds_bytes(f));
+    return launch_pass(
+        device, frames, stream, "bake launches", [&](const BakeFrame& f) { return launch_bake(f, shape, view, stream); },
+        [&](const BakeFrame* d_table, int m) { return launch_bake_batch(d_table, m, shape, view, shade, shade_dyn, occlusion, occlusion_dyn, stream); });
+}
+
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): one workgroup per handle rewrites the texel pool, the alpha
 // predicates and the MESH_OPAQUE bits of its blob.  The blob is what the handle's renders read, so a repaint sits in the
 // handle's event chain like a render (join_handle_chain / extend_handle_chain, the halves begin_ / end_handle_render use).
@@ -1024,6 +1081,23 @@ int mcrt_render_light_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_l
 int mcrt_render_light_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_light_planes* d_out,
                                    size_t frame_stride_pixels, void* stream) {
     return render_light_batch_device(scenes, n_frames, cfg, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_bake_light_device(mcrt_scene* s, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    return bake_light_batch_device(one, 1, cfg, grid, d_out, ~static_cast<size_t>(0), static_cast<hipStream_t>(stream));  // (one frame: no stride)
+}
+
+int mcrt_bake_light_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out,
+                                 size_t texel_stride, void* stream) {
+    return bake_light_batch_device(scenes, n_frames, cfg, grid, d_out, texel_stride, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_texels(mcrt_scene* s, int* n_texels) {
+    if (!s || !n_texels) return fail(MCRT_ERR_INVALID, "NULL argument");
+    *n_texels = s->n_texels;
+    return MCRT_OK;
 }
 
 }  // extern "C"

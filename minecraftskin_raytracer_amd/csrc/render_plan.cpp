@@ -1,9 +1,12 @@
 // render_plan.cpp — host-side planning of the launches: shards, the workspace and its batches, grids, plates, batches of
-// frames, and the shapes, variants and LDS sizes of the layers, ground, reflection, light and skin passes.  Pure host code: what it decides
+// frames, and the shapes, variants and LDS sizes of the layers, ground, reflection, light, bake and skin passes.  Pure host code: what it decides
 // reaches the kernels through RenderParams and the other structs of kernels.h; the constants it shares with them are in
 // launch_shapes.h.
 #include "kernels.h"
 
+#include "flat_scene.h"
+
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -401,6 +404,44 @@ size_t shade_lds_bytes(const ShadeFrame& f, const ShadeShape& shape) {
 size_t occlusion_lds_bytes(const ShadeFrame& f) {
     const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
     return tables + kOcclusionFixedBytes;
+}
+// ---- light bake (kernels.h) ---------------------------------------------------------------------------
+void bake_owner_faces(const uint8_t* blob, std::vector<BakeFace>& out) {
+    out.clear();
+    const FlatHeader* h = reinterpret_cast<const FlatHeader*>(blob);
+    const FlatMesh* fm = reinterpret_cast<const FlatMesh*>(blob + h->mesh_offset);
+    for (uint32_t m = 0; m < h->n_meshes; ++m)  // ascending (mesh, face): the stable sort keeps the owner first among equals
+        for (int face = 0; face < 6; ++face)
+            if (fm[m].tex_off[face] >= 0 && fm[m].tex_w[face] > 0 && fm[m].tex_h[face] > 0)
+                out.push_back(BakeFace{fm[m].tex_off[face], fm[m].tex_w[face], fm[m].tex_h[face], static_cast<int32_t>(m * 8 + static_cast<uint32_t>(face))});
+    std::stable_sort(out.begin(), out.end(), [](const BakeFace& a, const BakeFace& b) { return a.tex_off < b.tex_off; });
+    out.erase(std::unique(out.begin(), out.end(), [](const BakeFace& a, const BakeFace& b) { return a.tex_off == b.tex_off; }), out.end());
+}
+void make_bake_shape(const mcrt_config& cfg, int grid, bool bundle_decisions, bool inside_fast, int max_texels, BakeShape& shape) {
+    std::memset(&shape, 0, sizeof shape);
+    shape.grid = grid;
+    shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
+    const int fit = kBakePosBytes / (12 * shape.samples);  // 8 samples: 85 points per pass; 113 samples: 6
+    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.ao_samples = cfg.ao_samples;
+    shape.ao_radius = cfg.ao_radius;
+    shape.bundle_decisions = bundle_decisions ? 1 : 0;
+    shape.inside_fast = inside_fast ? 1 : 0;
+    shape.max_units = max_texels > 0 ? (max_texels - 1) / kBlock + 1 : 0;
+    shape.geometry = 1, shape.rays = 1;
+}
+int bake_view(BakeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
+int bake_batch_view(BakeFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
+// The 12-mesh character (72 face entries, 204 alpha words: 3120 bytes of tables) at 8 samples: `bake_shade` 3120 + 22528 + 85 * 96 =
+// 33808 bytes, `bake_occlusion` 3120 + 16384 = 19504 bytes: four workgroups of either in a CU's 160 KiB.  The largest tables the LDS
+// views take (28 KiB) make 59392 and 45056 bytes, below the 64 KiB a workgroup may ask for.
+size_t bake_shade_lds_bytes(const BakeFrame& f, const BakeShape& shape) {
+    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    return tables + kBakeShadeFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
+}
+size_t bake_occlusion_lds_bytes(const BakeFrame& f) {
+    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    return tables + kBakeOcclusionFixedBytes;
 }
 // ---- skins on resident scenes (kernels.h) -----------------------------------------------------------
 size_t skin_tables_bytes(int n_texels) { return 256 * sizeof(float) + static_cast<size_t>(n_texels) * sizeof(uint16_t); }

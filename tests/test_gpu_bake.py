@@ -1,0 +1,332 @@
+"""The light bake on the GPU (mcrt_bake_light*): position, normal, visibility, occlusion and direct of every pool texel bit for bit
+(as uint32) against the CPU oracle (tests/bake_checker.py), no case and no texel skipped — the S64 figure at pose 0 with its buried
+contact faces, the posed S32 figure, a repaintable handle before and after dead texels become live, two boxes at 1 to 16
+sub-samples per texel, a shared texture, NULL and EMPTY textures, a posed box pair, seventy boxes (the HBM view), the shadow modes,
+ambient occlusion at its limits, plane subsets and alignments, batches, the host form and the wrappers, a bake beside the handle's
+renders, the pass without bundle decisions and without the inside fast path, and the occlusion plane before and after the device
+holds the table of all seeds.
+
+So that planes of constants cannot pass, every case asserts the oracle's EXACT counts of live, fully dark, penumbra, partly occluded
+and fully occluded texels first (bake_checker.COUNTS, pinned on the CPU by tests/test_bake_checker.py)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import bake_checker as B  # noqa: E402
+import layers_checker as L  # noqa: E402
+import scenes  # noqa: E402
+from minecraftskin_raytracer_amd import abi  # noqa: E402
+
+gpu_test = pytest.mark.gpu
+SENTINEL = -12345.0
+PLANES = B.PLANES
+COMPONENTS = {k: c for k, (_, c) in abi.BAKE_FORMATS.items()}
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _buffers(n, stride, names=PLANES, lead=0):
+    """Device planes for n frames `stride` texels apart, filled with a sentinel; `lead` floats in front of frame 0."""
+    return {k: torch.full((lead + n * stride * COMPONENTS[k],), SENTINEL, dtype=torch.float32, device="cuda") for k in names}
+
+
+def _ptrs(buf, names, lead=0):
+    return {f"{k}_ptr": buf[k].data_ptr() + lead * 4 for k in names}
+
+
+def _frame(buf, names, i, stride, n_texels, lead=0):
+    out = {}
+    for k in names:
+        c = COMPONENTS[k]
+        a = buf[k].cpu().numpy()[lead + i * stride * c:lead + (i * stride + n_texels) * c]
+        out[k] = a.reshape((n_texels, c) if c > 1 else (n_texels,))
+    return out
+
+
+def _untouched(t):
+    return bool((t == SENTINEL).all().item())
+
+
+def _device_bake(ds, cfg, grid=1, names=PLANES, stream=None, lead=0):
+    n = ds.texels
+    buf = _buffers(1, n, lead=lead)
+    ds.bake_light_device(cfg, grid, stream=stream if stream is not None else _stream(), **_ptrs(buf, names, lead))
+    torch.cuda.synchronize()
+    return buf, _frame(buf, names, 0, n, n, lead)
+
+
+def _case(name, classes=True):
+    sd, cfg, grid, exp = B.case_expectation(name)
+    B.assert_counts(name, exp, classes)
+    B.assert_dead_constants(exp)
+    return sd, cfg, grid, exp
+
+
+def _check_both_forms(mcrt, sd, cfg, grid, exp, what, names=PLANES):
+    """The one-shot host form and the device form of one bake against the expectation."""
+    got = mcrt.TileRenderer.bakeLight(sd, cfg, grid, planes=names)
+    assert list(got) == [k for k in PLANES if k in names]
+    B.assert_bake_equal(got, exp, what)
+    ds = mcrt.DeviceScene(sd)
+    try:
+        assert ds.texels == len(exp["table"])
+        B.assert_bake_equal(_device_bake(ds, cfg, grid, names)[1], exp, what + " (device form)")
+        ds.check()
+    finally:
+        ds.close()
+
+
+@gpu_test
+@pytest.mark.parametrize("name", ["s64_pose0", "s32_pose6", "two_boxes_q1", "two_boxes_q2", "two_boxes_q3", "two_boxes_q4", "shared_texture",
+                                  "null_and_empty", "posed", "seventy_boxes"])
+def test_scenes_equal_the_oracle(mcrt, gpu, name):
+    sd, cfg, grid, exp = _case(name)
+    assert np.array_equal(mcrt.texel_table(sd), exp["table"])
+    _check_both_forms(mcrt, sd, cfg, grid, exp, name)
+
+
+@gpu_test
+@pytest.mark.parametrize("name", list(B.MODE_CASES))
+def test_shadow_modes_and_occlusion_limits(mcrt, gpu, name):
+    """On the two boxes: soft shadows off, 1, 3 and 113 samples, a light of radius 0; ambient occlusion with 1 and 113 samples at
+    the radii 0 and 1000.  (No penumbra without a disk and no occlusion at radius 0: the counts say so.)"""
+    sd, cfg, grid, exp = _case(name, classes=False)
+    names = PLANES if name.startswith("ao_") else ("position", "normal", "visibility", "direct")
+    _check_both_forms(mcrt, sd, cfg, grid, exp, name, names)
+
+
+@gpu_test
+def test_a_repainted_handle_before_and_after_dead_texels_become_live(mcrt, gpu):
+    head, cfg, _, exp_head = _case("overlay_head_only")
+    full, _, _, exp_full = _case("overlay_all_opaque")
+    assert int(exp_full["live"].sum()) - int(exp_head["live"].sum()) == 1248  # the body, arm and leg overlays
+    ds = mcrt.DeviceScene.for_skin("S64", mcrt.getBuiltinPoses()[0], look=head)
+    try:
+        assert ds.texels == 3264
+        white = _device_bake(ds, cfg)[1]  # white and opaque until the first repaint
+        B.assert_bake_equal({k: white[k] for k in ("position", "normal", "visibility", "occlusion")},
+                            {k: exp_full[k] for k in ("position", "normal", "visibility", "occlusion")}, "the white figure")
+        ds.set_skin(B.overlay_skin("head_only"))
+        B.assert_bake_equal(_device_bake(ds, cfg)[1], exp_head, "head overlay only")
+        ds.set_skin(B.overlay_skin("all_opaque"))
+        B.assert_bake_equal(_device_bake(ds, cfg)[1], exp_full, "all overlays opaque")
+        ds.set_skin(B.overlay_skin("head_only"))
+        B.assert_bake_equal(_device_bake(ds, cfg, names=("visibility", "occlusion", "direct"))[1], exp_head, "head overlay only again")
+        ds.check()
+        # in skin space: live exactly where a pixel some texel is cut from is not transparent
+        skin, cut = mcrt.pool_to_skin("S64", exp_head["live"], False), mcrt.pool_to_skin("S64", np.ones(3264, bool), False)
+        assert skin.shape == (64, 64) and int(skin.sum()) == int(exp_head["live"].sum()) == 2016
+        assert np.array_equal(skin[cut], B.overlay_skin("head_only")[..., 3][cut] > 0)
+    finally:
+        ds.close()
+
+
+SUBSETS = [("position",), ("normal",), ("position", "normal"), ("visibility",), ("direct",), ("occlusion",), ("normal", "occlusion"),
+           ("position", "visibility"), ("visibility", "occlusion"), ("direct", "occlusion", "position"), PLANES]
+
+
+@gpu_test
+def test_plane_subsets_leave_the_other_planes_alone(mcrt, gpu):
+    """Every set of planes that launches another kernel set: geometry alone (the first kernel without its rays), the first
+    kernel, the second alone (which then writes the geometry), both."""
+    sd, cfg, grid, exp = _case("two_boxes_q2")
+    ds = mcrt.DeviceScene(sd)
+    try:
+        for names in SUBSETS:
+            buf, got = _device_bake(ds, cfg, grid, names)
+            B.assert_bake_equal(got, exp, "+".join(names))
+            for k in PLANES:
+                if k not in names:
+                    assert _untouched(buf[k]), f"{k} was written although only {names} were asked for"
+        none, c = abi.McrtBakePlanes(None, None, None, None, None), cfg.to_c()
+        assert mcrt._lib.load().mcrt_bake_light_device(ds._h, C.byref(c), 1, C.byref(none), None) == abi.MCRT_ERR_INVALID
+    finally:
+        ds.close()
+
+
+@gpu_test
+@pytest.mark.parametrize("lead", [1, 2, 3])
+def test_planes_off_their_alignment(mcrt, gpu, lead):
+    """Planes `lead` floats off their allocation — 4, 8 or 12 bytes off a 16-byte boundary — for a pool that is no multiple of
+    four texels long per frame either (the posed pair: 144) and for the figure."""
+    for name in ("posed", "s32_pose6"):
+        sd, cfg, grid, exp = _case(name)
+        ds = mcrt.DeviceScene(sd)
+        try:
+            buf, got = _device_bake(ds, cfg, grid, lead=lead)
+            B.assert_bake_equal(got, exp, f"{name}, planes {lead} floats on")
+            for k in PLANES:
+                assert _untouched(buf[k][:lead]), f"{k}: written in front of the plane"
+            ds.check()
+        finally:
+            ds.close()
+
+
+@gpu_test
+def test_batch_of_five_scenes_of_unequal_size_keeps_the_gaps(mcrt, gpu):
+    names = ["two_boxes_q1", "posed", "s32_pose6", "shared_texture", "seventy_boxes"]  # un-posed, posed and the HBM view in one launch
+    cases = [_case(n) for n in names]
+    cfg = cases[0][1]
+    handles = [mcrt.DeviceScene(c[0]) for c in cases]
+    try:
+        sizes = [h.texels for h in handles]
+        assert sizes == [192, 144, 2016, 64, 1680]
+        stride = max(sizes) + 101  # odd frames start off a 16-byte boundary of visibility and occlusion
+        buf = _buffers(5, stride)
+        mcrt.bake_light_batch_device(handles, cfg, texel_stride=stride, stream=_stream(), **_ptrs(buf, PLANES))
+        torch.cuda.synchronize()
+        for i, (sd, _, _, exp) in enumerate(cases):
+            got = _frame(buf, PLANES, i, stride, sizes[i])
+            B.assert_bake_equal(got, exp, f"batch frame {i} ({names[i]})")
+            # a batch equals the same frames baked singly
+            B.assert_bake_equal(got, _device_bake(handles[i], cfg)[1], f"batch frame {i} against its own call")
+            for k in PLANES:
+                c = COMPONENTS[k]
+                assert _untouched(buf[k][(i * stride + sizes[i]) * c:(i + 1) * stride * c]), f"{k}: the texels behind frame {i} were written"
+        # the default stride is the largest scene's size; one handle listed twice
+        sub = ("occlusion", "direct")
+        buf = _buffers(3, 2016, sub)
+        mcrt.bake_light_batch_device([handles[2], handles[0], handles[2]], cfg, stream=_stream(), **_ptrs(buf, sub))
+        torch.cuda.synchronize()
+        for i, k in ((0, 2), (1, 0), (2, 2)):
+            B.assert_bake_equal(_frame(buf, sub, i, 2016, sizes[k]), cases[k][3], f"one handle twice, frame {i}")
+        # a stride below a scene's size is refused before any work
+        buf = _buffers(2, 2016, sub)
+        with pytest.raises(mcrt._lib.McrtError):
+            mcrt.bake_light_batch_device([handles[0], handles[2]], cfg, texel_stride=2015, stream=_stream(), **_ptrs(buf, sub))
+        torch.cuda.synchronize()
+        assert all(_untouched(buf[k]) for k in sub)
+        for h in handles:
+            h.check()
+    finally:
+        for h in handles:
+            h.close()
+
+
+@gpu_test
+def test_batch_beyond_the_frames_of_one_launch(mcrt, gpu):
+    n = 4096 + 1  # one launch takes 4096 frames (blockIdx.y)
+    a, cfg, _, exp_a = _case("two_boxes_q1")
+    b, _, _, exp_b = _case("shared_texture")
+    exps = [exp_a, exp_b]
+    handles = [mcrt.DeviceScene(a), mcrt.DeviceScene(b)]
+    try:
+        stride = 192
+        buf = _buffers(n, stride)
+        mcrt.bake_light_batch_device([handles[i % 2] for i in range(n)], cfg, texel_stride=stride, stream=_stream(), **_ptrs(buf, PLANES))
+        torch.cuda.synchronize()
+        for i in (0, 4095, 4096):
+            B.assert_bake_equal(_frame(buf, PLANES, i, stride, len(exps[i % 2]["table"])), exps[i % 2], f"frame {i} of {n}")
+        for k in PLANES:  # and every other frame is one of the two (the 128 texels behind a frame of 64 untouched)
+            c = COMPONENTS[k]
+            got = buf[k].cpu().numpy().reshape(n, stride * c)
+            even, odd = np.ascontiguousarray(exp_a[k]).reshape(-1), np.ascontiguousarray(exp_b[k]).reshape(-1)
+            assert np.array_equal(got[0::2].view(np.uint32), np.tile(even.view(np.uint32), (len(got[0::2]), 1))), k
+            assert np.array_equal(got[1::2, :64 * c].view(np.uint32), np.tile(odd.view(np.uint32), (len(got[1::2]), 1))), k
+            assert (got[1::2, 64 * c:] == SENTINEL).all(), k
+    finally:
+        for h in handles:
+            h.close()
+
+
+@gpu_test
+def test_the_wrappers(mcrt, gpu):
+    sd, cfg, grid, exp = _case("two_boxes_q3")
+    sub = mcrt.TileRenderer.bakeLight(sd, cfg, grid, planes=("direct", "position"))
+    assert list(sub) == ["position", "direct"] and sub["direct"].shape == (192, 4)
+    B.assert_bake_equal(sub, exp, "host wrapper, two planes")
+    one = mcrt.TileRenderer.bakeLight(sd, cfg, grid, planes="occlusion")
+    assert list(one) == ["occlusion"] and one["occlusion"].shape == (192,) and one["occlusion"].dtype == np.float32
+    B.assert_bake_equal(one, exp, "host wrapper, one plane")
+    empty = mcrt.TileRenderer.bakeLight(scenes.simple_scene([]), cfg)  # no texel: nothing to bake
+    assert all(v.shape[0] == 0 for v in empty.values())
+
+
+@gpu_test
+def test_bake_between_two_renders_of_one_handle(mcrt, gpu):
+    sd, bcfg, grid, exp = _case("s64_pose0")
+    cfg = abi.Config(width=96, height=64, samplesPerPixel=2, aoEnabled=True)  # the reference's defaults otherwise: 3 bounces, soft shadows
+    ds = mcrt.DeviceScene(sd)
+    try:
+        main, side = torch.cuda.Stream(), torch.cuda.Stream()
+        first = torch.zeros((cfg.height, cfg.width, 4), dtype=torch.float32, device="cuda")
+        second, single = torch.zeros_like(first), torch.zeros_like(first)
+        buf = _buffers(1, ds.texels)
+        ds.render_device(cfg, single.data_ptr(), 0, 1, abi.LAYOUT_FRAME, main.cuda_stream)
+        ds.check()
+        torch.cuda.synchronize()
+        ds.render_device(cfg, first.data_ptr(), 0, 1, abi.LAYOUT_FRAME, main.cuda_stream)
+        ds.bake_light_device(bcfg, grid, stream=side.cuda_stream, **_ptrs(buf, PLANES))  # no wait for the render: it reads the scene alone
+        ds.render_device(cfg, second.data_ptr(), 0, 1, abi.LAYOUT_FRAME, main.cuda_stream)
+        ds.check()  # waits for all three
+        torch.cuda.synchronize()
+        scenes.assert_bit_equal(first.cpu().numpy(), single.cpu().numpy(), "beauty before the bake")
+        scenes.assert_bit_equal(second.cpu().numpy(), single.cpu().numpy(), "beauty after the bake")
+        assert float(single[..., 3].min().item()) > 0.0  # an opaque frame was rendered
+        B.assert_bake_equal(_frame(buf, PLANES, 0, ds.texels, ds.texels), exp, "bake beside the renders")
+    finally:
+        ds.close()
+
+
+def _child(argv):
+    """A fresh process: a case's bake through the host form, saved as .npz (the development knobs are read once)."""
+    import minecraftskin_raytracer_amd as M
+
+    kind, scene, kw = B.CASES[argv[0]]
+    sd = L.skin_case(*scene)
+    np.savez(argv[1], **M.TileRenderer.bakeLight(sd, B.config(), kw.get("grid", 1)))
+
+
+@gpu_test
+@pytest.mark.parametrize("knob", ["MCRT_BUNDLE_DECISIONS", "MCRT_INSIDE_FAST"])
+def test_without_a_development_knob_the_planes_are_the_same(mcrt, gpu, tmp_path, knob):
+    sd, cfg, grid, exp = _case("s64_pose0")
+    default = mcrt.TileRenderer.bakeLight(sd, cfg, grid)
+    out = str(tmp_path / "knob.npz")
+    env = dict(os.environ, **{knob: "0"})
+    subprocess.run([sys.executable, os.path.abspath(__file__), "s64_pose0", out], env=env, check=True, timeout=300)
+    z = np.load(out)
+    for k in PLANES:
+        assert z[k].tobytes() == default[k].tobytes(), f"{knob}=0 changes {k}"
+    B.assert_bake_equal({k: z[k] for k in PLANES}, exp, f"{knob}=0")
+
+
+@gpu_test
+def test_occlusion_before_and_after_the_device_holds_the_table_of_all_seeds(mcrt, gpu):
+    """The occlusion kernel seeds its engines by the recurrence until an ambient-occlusion RENDER on the device has built the table
+    of all seeds; then it reads mt[397] from it.  The same bytes either way (when an earlier test of the session has rendered with
+    ambient occlusion, the table exists from the start, and both bakes read it)."""
+    sd, cfg, grid, exp = _case("s32_pose6")
+    ds, other = mcrt.DeviceScene(sd), mcrt.DeviceScene(L.skin_case("S64", 0))
+    try:
+        before = _device_bake(ds, cfg, grid, ("occlusion",))[1]
+        B.assert_bake_equal(before, exp, "before the AO render")
+        frame = torch.zeros((32, 32, 4), dtype=torch.float32, device="cuda")
+        other.render_device(abi.Config(width=32, height=32, aoEnabled=True), frame.data_ptr(), 0, 1, abi.LAYOUT_FRAME, _stream())
+        other.check()
+        after = _device_bake(ds, cfg, grid, ("occlusion",))[1]
+        assert after["occlusion"].tobytes() == before["occlusion"].tobytes()
+        fresh = mcrt.DeviceScene(sd)
+        try:
+            B.assert_bake_equal(_device_bake(fresh, cfg, grid, ("occlusion",))[1], exp, "a handle created after the AO render")
+        finally:
+            fresh.close()
+        ds.check()
+    finally:
+        ds.close()
+        other.close()
+
+
+if __name__ == "__main__":
+    _child(sys.argv[1:])

@@ -14,6 +14,10 @@ The light layers (tests/light_checker.py), visibility, occlusion and direct bit 
                turn, AO settings drawn per case (1 ... 113 samples, a radius of 0.01 ... 10 scene heights); every fourth case into
                planes 1 or 2 floats off their allocation, every other case also twice through the batched kernels; the summary
                records the hits, penumbra hits and partly occluded hits compared
+The light bake (tests/bake_checker.py), position, normal, visibility, occlusion and direct of every pool texel bit for bit:
+  bake         bake_light_device on bake_checker.sweep_case(seed): light's cases, grid 1 + seed % 4; every fourth case into planes 1 or
+               2 floats off their allocation, every other case also twice through the batched kernels; the summary records the
+               texels and the live, dark, penumbra and partly occluded texels compared
 The batched entries (tests/batch_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_batch_fuzz.py):
   batch        render_batch_device on make_beauty_batch(seed): 1 ... 16 frames of mixed scenes under one config, fresh and stale
                tile seeds, a lead and a stride gap; every third seed also through TileRenderer.renderBatch
@@ -42,7 +46,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide", "light", "big") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light", "bake", "big") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -141,6 +145,44 @@ def light_sweep():
             print(f"... {k + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
     print(f"fuzz light: {count} cases from seed {first}: {bad} mismatch(es); the oracle holds {int(total[0])} hits, {int(total[1])} of them dark and "
           f"{int(total[2])} in the penumbra, and {int(total[3])} partly occluded hits ({int(total[4])} fully occluded)")
+    pool.terminate()
+    sys.exit(1 if bad else 0)
+
+
+def bake_sweep():
+    import bake_checker as BC, test_gpu_bake_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    # the oracle's planes are made ahead of the device by worker processes (forked before the device is first used; they never
+    # use it), in the order of the seeds
+    import multiprocessing
+
+    workers = max(1, min(14, len(os.sched_getaffinity(0)) - 2, int(os.environ.get("OMP_NUM_THREADS", "16")) - 2))
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    ahead = pool.imap(BC.worker_sweep_expectation, range(first, first + count))
+    bad = texels = 0
+    total = np.zeros(5, np.int64)
+    t0 = time.time()
+    for k, seed in enumerate(range(first, first + count)):
+        sd, cfg, grid, what = BC.sweep_case(seed)
+        exp = next(ahead)
+        BC.assert_dead_constants(exp)
+        try:
+            lines = T.run_case(M, (sd, cfg, what), exp, T.lead_of(k), twice=k % 2 == 0, grid=grid)
+        except McrtError as e:
+            print(f"HIP ERROR {what}: {e}", flush=True)
+            print(f"fuzz bake: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
+            pool.terminate()
+            sys.exit(2)
+        total += np.asarray(BC.counts(exp))
+        texels += len(exp["table"])
+        if lines:
+            bad += 1
+            print("\n".join("MISMATCH " + l for l in lines[:20]), flush=True)
+        if k % 100 == 99:
+            print(f"... {k + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
+    print(f"fuzz bake: {count} cases from seed {first}: {bad} mismatch(es); the oracle holds {texels} texels, {int(total[0])} of them live, "
+          f"{int(total[1])} fully dark, {int(total[2])} in the penumbra, {int(total[3])} partly occluded and {int(total[4])} fully occluded")
     pool.terminate()
     sys.exit(1 if bad else 0)
 
@@ -258,6 +300,8 @@ if mode in BATCH_MODES:
     batch_sweep()
 if mode == "light":
     light_sweep()
+if mode == "bake":
+    bake_sweep()
 if mode == "big":
     big_sweep()
 if len(sys.argv) > 3 and sys.argv[3] == "bundle":
