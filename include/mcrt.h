@@ -637,6 +637,38 @@ int mcrt_skin_pool_map(int skin_height, int32_t* out, int capacity);
  * stride that is no multiple of 4 or smaller than the image; an image that is not 4-byte aligned; a handle that
  * mcrt_scene_create_skin did not create; handles of different skin kinds or devices in one batch; a handle listed twice. */
 
+/* ---- views of resident scenes: another pose, camera or light for a scene that is already on the device ----------------------
+ * The part of a repaintable handle's blob that pose, camera, light and background decide is its prefix [header][mesh table] —
+ * 2 496 bytes for a 64x64 skin, 1 536 for a 64x32 one; the texel pool, the alpha words and the owner faces of a bake behind it
+ * do not depend on the view.  A view change flattens that prefix on the host, with the flattener's own code and without
+ * reading a texel, and one small kernel writes it over the resident blob, keeping the one thing in it the skin owns: the
+ * MESH_OPAQUE bit of every mesh.  No scene build with textures, no upload of the blob, no new handle, no repaint.
+ * DEFINITION: after a view change the handle is indistinguishable from a fresh mcrt_scene_create_skin(kind, pose, look) that
+ * was repainted with the handle's current skin — its blob is byte for byte mcrt_scene_flatten of the full-table scene, and
+ * every frame, layer, pick, ground, reflection, light and bake result follows bit for bit.  Before the first repaint that is
+ * the white figure at the new view.
+ * pose NULL: the handle keeps its pose; look NULL: it keeps its look (as created, or as last set).  Both are HOST memory, read
+ * before the call returns; of a look the fields mcrt_scene_create_skin reads are read, its meshes and textures are ignored.
+ * Ordering: exactly a repaint's.  The view change waits for the handle's earlier renders, repaints and view changes, and the
+ * handle's next render waits for it, whatever streams they are given (the handle's event chain); the library's recorded
+ * launch graphs are replayed only where the render's parameters still hold.  Layers, ground, reflection, light, bake and pick
+ * passes take none of the handle's events: ordering THOSE against a view change (stream order, or an event of the caller's)
+ * is the caller's job, as for a repaint.
+ * mcrt_scene_set_view is synchronous; the _device forms are asynchronous on `stream` (not into a graph being recorded on it). */
+int mcrt_scene_set_view(mcrt_scene* scene, const float pose[12], const mcrt_scene_desc* look);
+int mcrt_scene_set_view_device(mcrt_scene* scene, const float pose[12], const mcrt_scene_desc* look, void* stream);
+/* One launch gives n handles their views: poses[i], looks[i].  `poses` NULL, `looks` NULL or an entry looks[i] NULL: keep.  The
+ * tables travel in one asynchronous copy.  The handles are of one skin kind, on one device, none listed twice.  n = 0: MCRT_OK. */
+int mcrt_scene_set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12],
+                                      const mcrt_scene_desc* const* looks, void* stream);
+/* Host only, no device.  The view-dependent prefix [0, texel_offset) of the blob of mcrt_scene_create_skin(skin_height, pose,
+ * look) — the white figure's, so with MESH_OPAQUE on every mesh; NULL: the builder's own pose or look.  Returns its byte count
+ * (0 and the error text for a skin_height other than 64 or 32) and copies min(count, capacity) bytes into `out` (may be NULL). */
+int mcrt_skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, void* out, size_t capacity);
+/* MCRT_ERR_INVALID, before any device work and with the blobs and the handles' state untouched: a NULL handle, `scenes` or
+ * entry; n < 0; a handle that mcrt_scene_create_skin did not create; handles of different skin kinds or devices in one batch; a
+ * handle listed twice; a stream that is being captured. */
+
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);
 

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_scene_create_skin", "mcrt_scene_set_skin_device", "mcrt_scene_set_skins_batch_device", "mcrt_scene_set_skin",
     "mcrt_skin_pool_map", "mcrt_probe_scene_blob",
     "mcrt_bake_light_device", "mcrt_bake_light_batch_device", "mcrt_bake_light", "mcrt_bake_texel_table", "mcrt_scene_texels",
+    "mcrt_scene_set_view", "mcrt_scene_set_view_device", "mcrt_scene_set_views_batch_device", "mcrt_skin_view_table",
 ]
 
 
@@ -105,6 +106,10 @@ def load():
         "mcrt_scene_set_skins_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_size_t, vp]),
         "mcrt_scene_set_skin": (C.c_int, [vp, u8_p]),
         "mcrt_skin_pool_map": (C.c_int, [C.c_int, abi.c_int32_p, C.c_int]),
+        "mcrt_scene_set_view": (C.c_int, [vp, f_p, desc_p]),
+        "mcrt_scene_set_view_device": (C.c_int, [vp, f_p, desc_p, vp]),
+        "mcrt_scene_set_views_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.POINTER(desc_p), vp]),
+        "mcrt_skin_view_table": (C.c_int, [C.c_int, f_p, desc_p, vp, C.c_size_t]),
         "mcrt_probe_scene_blob": (C.c_int, [vp, vp, C.c_size_t]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),
         "mcrt_encode_png_rgba8": (C.c_size_t, [u8_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),

@@ -579,6 +579,58 @@ def skin_pool_map(kind) -> np.ndarray:
     return out
 
 
+def _view_pose(pose) -> Optional[np.ndarray]:
+    if pose is None:
+        return None
+    p = np.ascontiguousarray(pose, np.float32)
+    if p.shape != (12,):
+        raise ValueError("pose must hold 12 floats")
+    return p
+
+
+def skin_view_table(kind, pose: Optional[Sequence[float]] = None, look=None) -> bytes:
+    """The view-dependent prefix ``[header][mesh table]`` of the blob of ``DeviceScene.for_skin(kind, pose, look)`` — bytes
+    ``[0, texel_offset)``, 2496 for ``"S64"`` and 1536 for ``"S32"`` — computed on the host (mcrt_skin_view_table): what a
+    view change writes into a resident scene, but for the MESH_OPAQUE bits, which are the white figure's here."""
+    h = _skin_height(kind)
+    p, d = _view_pose(pose), _as_desc(look) if look is not None else None
+    lib = load()
+    args = (h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None)
+    n = lib.mcrt_skin_view_table(*args, None, 0)
+    buf = C.create_string_buffer(max(n, 1))
+    if n <= 0 or lib.mcrt_skin_view_table(*args, buf, n) != n:
+        raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
+    return buf.raw[:n]
+
+
+_LOOK_ARRAYS = ("light_position", "light_color", "camera_position", "camera_target", "camera_up", "background_color")
+_LOOK_SCALARS = ("light_intensity", "light_radius", "camera_fov")
+
+
+def orbit_look(yaw_deg: float, pitch_deg: float, distance: float, target=(0.0, 18.0, 0.0), base=None) -> SceneDesc:
+    """A look — a description whose light, camera and background count, for ``DeviceScene.for_skin`` and ``set_view`` — with
+    the camera on an orbit about ``target`` (yaw 0: the default camera's side, +Z), on a copy of ``base`` (a ``Scene`` /
+    ``SceneDesc``; ``None``: the builder's default look).  ``base`` is not modified."""
+    import math
+
+    sd = MeshBuilder.buildDefaultScene()
+    d = sd.desc
+    if base is not None:
+        b = _as_desc(base).desc
+        for k in _LOOK_ARRAYS:
+            for i in range(len(getattr(d, k))):
+                getattr(d, k)[i] = getattr(b, k)[i]
+        for k in _LOOK_SCALARS:
+            setattr(d, k, getattr(b, k))
+    yaw, pitch = math.radians(yaw_deg), math.radians(pitch_deg)
+    pos = (target[0] + distance * math.cos(pitch) * math.sin(yaw), target[1] + distance * math.sin(pitch),
+           target[2] + distance * math.cos(pitch) * math.cos(yaw))
+    for k in range(3):
+        d.camera_position[k] = pos[k]
+        d.camera_target[k] = target[k]
+    return sd
+
+
 def texel_table(scene) -> np.ndarray:
     """Per texel of the scene's texel pool, in pool order, its OWNER face (mcrt_bake_texel_table): (n, 4) int32 rows
     ``mesh, face slot, tx, ty`` — of the faces that reference the texel the one with the lowest mesh index, then the lowest face
@@ -663,6 +715,21 @@ class DeviceScene:
         pick passes by the caller."""
         self._skin_bytes()
         check(load().mcrt_scene_set_skin_device(self._h, C.c_void_p(ptr or None), C.c_void_p(stream)))
+
+    def set_view(self, pose: Optional[Sequence[float]] = None, look=None) -> None:
+        """Another pose and / or look for this repaintable scene, synchronously (mcrt_scene_set_view): afterwards it is what
+        ``for_skin(kind, pose, look)`` repainted with the current skin would be, bit for bit.  ``None`` keeps the scene's own."""
+        self._skin_bytes()
+        p, d = _view_pose(pose), _as_desc(look) if look is not None else None
+        check(load().mcrt_scene_set_view(self._h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None))
+
+    def set_view_device(self, pose: Optional[Sequence[float]] = None, look=None, stream: int = 0) -> None:
+        """The same, asynchronous on ``stream`` (mcrt_scene_set_view_device); ``pose`` and ``look`` are read before the call
+        returns.  The handle's renders are ordered against it by the library; its layers, ground, reflection, light, bake and
+        pick passes by the caller."""
+        self._skin_bytes()
+        p, d = _view_pose(pose), _as_desc(look) if look is not None else None
+        check(load().mcrt_scene_set_view_device(self._h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None, C.c_void_p(stream)))
 
     def blob(self) -> bytes:
         """The scene's resident blob, downloaded after waiting for the device (mcrt_probe_scene_blob)."""
@@ -988,6 +1055,36 @@ def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, ski
     check(load().mcrt_scene_set_skins_batch_device(arr, n, C.c_void_p(ptr or None), int(skin_stride_bytes), C.c_void_p(stream)))
 
 
+def set_views_batch_device(device_scenes: Sequence["DeviceScene"], poses=None, looks=None, stream: int = 0) -> None:
+    """One launch gives N repaintable scenes of one skin kind their views (mcrt_scene_set_views_batch_device): ``poses`` — N
+    poses of 12 floats, or ``None``: every scene keeps its own; ``looks`` — N entries, each a ``Scene`` / ``SceneDesc`` or
+    ``None`` (that scene keeps its look), or ``None`` for all.  Asynchronous on ``stream``; the arguments are read before the
+    call returns."""
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    n = len(handles)
+    p = None
+    if poses is not None:
+        p = np.ascontiguousarray(poses, np.float32)
+        if p.shape != (n, 12):
+            raise ValueError(f"poses must be ({n}, 12) floats: one pose per scene")
+    descs = None
+    if looks is not None:
+        looks = list(looks)
+        if len(looks) != n:
+            raise ValueError(f"looks must hold {n} entries: one look (or None) per scene")
+        descs = [_as_desc(k) if k is not None else None for k in looks]
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    look_arr = None
+    if descs is not None:
+        ptrs = [d.ptr if d is not None else None for d in descs]  # (kept alive until the call has returned)
+        look_arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*[C.cast(q, C.POINTER(abi.McrtSceneDesc)) if q is not None else C.POINTER(abi.McrtSceneDesc)() for q in ptrs])
+    check(load().mcrt_scene_set_views_batch_device(arr, n, p.ctypes.data_as(C.c_void_p) if p is not None and n else None, look_arr, C.c_void_p(stream)))
+
+
 class SkinBatch:
     """The farm case: ``n`` repaintable scenes of one skin kind, pose and look resident on ``device``, and a skin buffer there.
     ``render(skins, config)`` gives the frames of ``m <= n`` skins with ONE upload (the images, 16 KB each), one repaint launch,
@@ -1023,6 +1120,28 @@ class SkinBatch:
             self.close()
         except Exception:
             pass
+
+    def set_views(self, poses=None, looks=None) -> None:
+        """Another pose and / or look for the batch's scenes without rebuilding them (``set_views_batch_device``): ``poses`` —
+        one pose of 12 floats for all scenes, or one per scene (n, 12); ``looks`` — one ``Scene`` / ``SceneDesc`` for all, or a
+        sequence of n (entries may be ``None``); ``None`` keeps what the scenes have.  On the current torch stream, ahead of the
+        next ``render`` / ``layers``."""
+        n = len(self.scenes)
+        if poses is not None:
+            p = np.ascontiguousarray(poses, np.float32)
+            if p.shape == (12,):
+                p = np.tile(p, (n, 1))
+            elif p.shape != (n, 12):
+                raise ValueError(f"poses must be one pose of 12 floats or ({n}, 12)")
+            poses = p
+        if looks is not None:
+            looks = [looks] * n if isinstance(looks, (Scene, SceneDesc)) else list(looks)
+            if len(looks) != n:
+                raise ValueError(f"looks must be one look or {n} of them")
+        if n == 0 or (poses is None and looks is None):
+            return
+        with self._torch.cuda.device(self._dev):
+            set_views_batch_device(self.scenes, poses, looks, stream=self._torch.cuda.current_stream().cuda_stream)
 
     def _check_skins(self, skins) -> np.ndarray:
         a = np.ascontiguousarray(skins, np.uint8)

@@ -127,6 +127,7 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     if (s->skin_tables) release_skin_tables(device, s->skin_height);  // a pooled shell that was a repaintable handle
     s->skin_tables = nullptr;
     s->skin_height = 0;
+    s->has_pose = s->has_look = false;  // (mcrt_scene_create_skin notes its own)
     s->budget = 0;  // a budget halved under memory pressure is not inherited
     s->have_last = false;  // a pooled shell was synchronised when its previous owner let go of it
     s->last_stream = nullptr;
@@ -173,7 +174,47 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     *out = s;
     return MCRT_OK;
 }
+
+// what a NULL pose or look of the handle's next view keeps (host_internal.h: view_pose, view_look)
+void remember_view(mcrt_scene* s, const float pose[12], const mcrt_scene_desc* look) {
+    s->has_pose = pose != nullptr;
+    if (pose) std::memcpy(s->view_pose, pose, sizeof s->view_pose);
+    s->has_look = look != nullptr;
+    if (look) apply_look(&s->view_look, look);  // (the other fields stay zero)
+}
 }  // namespace
+
+extern "C" mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, const float pose[12]);  // scene_builder.cpp
+
+namespace mcrt_host {
+void apply_look(mcrt_scene_desc* desc, const mcrt_scene_desc* look) {
+    std::memcpy(desc->light_position, look->light_position, sizeof desc->light_position);
+    std::memcpy(desc->light_color, look->light_color, sizeof desc->light_color);
+    desc->light_intensity = look->light_intensity;
+    desc->light_radius = look->light_radius;
+    std::memcpy(desc->camera_position, look->camera_position, sizeof desc->camera_position);
+    std::memcpy(desc->camera_target, look->camera_target, sizeof desc->camera_target);
+    std::memcpy(desc->camera_up, look->camera_up, sizeof desc->camera_up);
+    desc->camera_fov = look->camera_fov;
+    std::memcpy(desc->background_color, look->background_color, sizeof desc->background_color);
+}
+
+int skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, std::vector<uint8_t>& table) {
+    if (skin_height != 64 && skin_height != 32) return fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    mcrt_scene_desc* desc = mcrt_detail_white_figure(skin_height, pose);
+    if (look) apply_look(desc, look);
+    std::string err;
+    const bool flat = flatten_view_table(desc, table, err);
+    mcrt_scene_desc_free(desc);
+    if (!flat) return fail(MCRT_ERR_INVALID, err);
+    // the white figure's own MESH_OPAQUE bits: every texel of an all-(255,255,255,255) skin is opaque
+    const FlatHeader* h = reinterpret_cast<const FlatHeader*>(table.data());
+    FlatMesh* fm = reinterpret_cast<FlatMesh*>(table.data() + h->mesh_offset);
+    for (uint32_t i = 0; i < h->n_meshes; ++i) fm[i].flags |= MESH_OPAQUE;
+    return MCRT_OK;
+}
+}  // namespace mcrt_host
+
 extern "C" {
 
 int mcrt_scene_create(const mcrt_scene_desc* desc, int device, mcrt_scene** out) {
@@ -194,17 +235,7 @@ int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_sce
     const std::vector<uint8_t> white(static_cast<size_t>(64) * static_cast<size_t>(skin_height) * 4, 255);
     mcrt_scene_desc* desc = nullptr;
     if (mcrt_build_skin_scene(white.data(), 64, skin_height, pose, &desc) != MCRT_OK || !desc) return fail(MCRT_ERR_INVALID, "the scene builder failed");
-    if (look) {
-        std::memcpy(desc->light_position, look->light_position, sizeof desc->light_position);
-        std::memcpy(desc->light_color, look->light_color, sizeof desc->light_color);
-        desc->light_intensity = look->light_intensity;
-        desc->light_radius = look->light_radius;
-        std::memcpy(desc->camera_position, look->camera_position, sizeof desc->camera_position);
-        std::memcpy(desc->camera_target, look->camera_target, sizeof desc->camera_target);
-        std::memcpy(desc->camera_up, look->camera_up, sizeof desc->camera_up);
-        desc->camera_fov = look->camera_fov;
-        std::memcpy(desc->background_color, look->background_color, sizeof desc->background_color);
-    }
+    if (look) apply_look(desc, look);
     std::vector<uint8_t> b;
     std::string err;
     const bool flat = flatten_scene(desc, b, err);
@@ -218,8 +249,16 @@ int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_sce
         return fail(MCRT_ERR_HIP, "the device's repaint tables could not be built");
     }
     s->skin_height = skin_height;
+    remember_view(s, pose, look);
     *out = s;
     return MCRT_OK;
+}
+
+int mcrt_skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, void* out, size_t capacity) {
+    std::vector<uint8_t> t;
+    if (skin_view_table(skin_height, pose, look, t) != MCRT_OK) return 0;
+    if (out && capacity) std::memcpy(out, t.data(), t.size() < capacity ? t.size() : capacity);
+    return static_cast<int>(t.size());
 }
 
 void mcrt_scene_destroy(mcrt_scene* s) {

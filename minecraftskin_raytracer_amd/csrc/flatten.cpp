@@ -65,9 +65,14 @@ void rotate_fwd_d(const mcrt_mesh& m, const double in[3], double out[3]) {
     out[2] = p[2] + m.pivot[2];
 }
 
-}  // namespace
+// where the parts of a description's blob lie: a function of the counts and the textures' sizes alone
+struct Layout {
+    std::vector<int64_t> tex_base;  // per texture: its first texel in the pool, or MCRT_TEX_EMPTY
+    int64_t n_texels = 0;
+    size_t mesh_off = 0, texel_off = 0, alpha_off = 0, alpha_words = 0, total = 0;
+};
 
-bool flatten_scene(const mcrt_scene_desc* d, std::vector<uint8_t>& blob, std::string& err) {
+bool plan_layout(const mcrt_scene_desc* d, Layout& L, std::string& err) {
     if (!d) {
         err = "scene description is NULL";
         return false;
@@ -78,8 +83,8 @@ bool flatten_scene(const mcrt_scene_desc* d, std::vector<uint8_t>& blob, std::st
         return false;
     }
     // ---- texel pool -------------------------------------------------------------------------
-    std::vector<int64_t> tex_base(d->n_textures, MCRT_TEX_EMPTY);
-    int64_t n_texels = 0;
+    L.tex_base.assign(d->n_textures, MCRT_TEX_EMPTY);
+    L.n_texels = 0;
     for (int i = 0; i < d->n_textures; ++i) {
         const mcrt_texture& t = d->textures[i];
         if (t.width <= 0 || t.height <= 0 || t.n_pixels <= 0) continue;  // sample() → Color()
@@ -87,38 +92,27 @@ bool flatten_scene(const mcrt_scene_desc* d, std::vector<uint8_t>& blob, std::st
             err = "texture " + std::to_string(i) + ": fewer pixels than width*height (out-of-bounds read in the reference)";
             return false;
         }
-        tex_base[i] = n_texels;
-        n_texels += static_cast<int64_t>(t.width) * t.height;
+        L.tex_base[i] = L.n_texels;
+        L.n_texels += static_cast<int64_t>(t.width) * t.height;
     }
-    if (n_texels > 0x7fffffff / 4) {
+    if (L.n_texels > 0x7fffffff / 4) {
         err = "texel pool too large";
         return false;
     }
+    L.mesh_off = sizeof(FlatHeader);
+    L.texel_off = L.mesh_off + sizeof(FlatMesh) * static_cast<size_t>(d->n_meshes);
+    L.alpha_off = L.texel_off + static_cast<size_t>(L.n_texels) * 16;
+    L.alpha_words = static_cast<size_t>((L.n_texels + 15) / 16);
+    L.total = L.alpha_off + L.alpha_words * 4;
+    return true;
+}
 
-    const size_t mesh_off = sizeof(FlatHeader);
-    const size_t texel_off = mesh_off + sizeof(FlatMesh) * static_cast<size_t>(d->n_meshes);
-    const size_t alpha_off = texel_off + static_cast<size_t>(n_texels) * 16;
-    const size_t alpha_words = static_cast<size_t>((n_texels + 15) / 16);
-    const size_t total = alpha_off + alpha_words * 4;
-    blob.assign(total, 0);
-    FlatHeader* h = reinterpret_cast<FlatHeader*>(blob.data());
-    FlatMesh* fm = reinterpret_cast<FlatMesh*>(blob.data() + mesh_off);
-    float* pool = reinterpret_cast<float*>(blob.data() + texel_off);
-
-    for (int i = 0; i < d->n_textures; ++i) {
-        if (tex_base[i] < 0) continue;
-        const mcrt_texture& t = d->textures[i];
-        std::memcpy(pool + 4 * tex_base[i], t.rgba, static_cast<size_t>(t.width) * t.height * 16);
-    }
-    // alpha predicates: the only two ways a texel's value decides hit/miss
-    // (texColor.a == 0.0f, intersection.cpp:311; backTexColor.a > 0.0f, :349)
-    uint32_t* abits = reinterpret_cast<uint32_t*>(blob.data() + alpha_off);
-    for (int64_t i = 0; i < n_texels; ++i) {
-        const float a = pool[4 * i + 3];
-        uint32_t bits = (a == 0.0f ? 1u : 0u) | (a > 0.0f ? 2u : 0u);
-        abits[i >> 4] |= bits << ((i & 15) * 2);
-    }
-
+// The half of the blob that pose, camera and light decide: the header at `h` and the mesh table at `fm` (zeroed memory), every
+// word of them but the MESH_OPAQUE bits — those are the texels' (flatten_scene sets them; a view table leaves them to the device).
+bool fill_view(const mcrt_scene_desc* d, const Layout& L, FlatHeader* h, FlatMesh* fm, std::string& err) {
+    const std::vector<int64_t>& tex_base = L.tex_base;
+    const int64_t n_texels = L.n_texels;
+    const size_t mesh_off = L.mesh_off, texel_off = L.texel_off, alpha_off = L.alpha_off, alpha_words = L.alpha_words, total = L.total;
     // ---- camera -----------------------------------------------------------------------------
     V3 pos{d->camera_position[0], d->camera_position[1], d->camera_position[2]};
     V3 tgt{d->camera_target[0], d->camera_target[1], d->camera_target[2]};
@@ -230,16 +224,6 @@ bool flatten_scene(const mcrt_scene_desc* d, std::vector<uint8_t>& blob, std::st
                 f.tex_h[face] = d->textures[ti].height;
             }
         }
-        {  // MESH_OPAQUE: a null texture is opaque magenta, an empty one Color() with alpha 1
-            bool opaque = true;
-            for (int face = 0; face < 6 && opaque; ++face) {
-                if (f.tex_off[face] < 0) continue;
-                const int64_t n = static_cast<int64_t>(f.tex_w[face]) * f.tex_h[face];
-                for (int64_t k = 0; k < n && opaque; ++k) opaque = !(pool[4 * (f.tex_off[face] + k) + 3] == 0.0f);
-            }
-            if (opaque) f.flags |= MESH_OPAQUE;
-        }
-
         // Bounding sphere in world space: centre = (posed) box centre, radius = half diagonal, padded.
         {
             double c[3] = {0.5 * (static_cast<double>(lo[0]) + hi[0]), 0.5 * (static_cast<double>(lo[1]) + hi[1]),
@@ -342,6 +326,51 @@ bool flatten_scene(const mcrt_scene_desc* d, std::vector<uint8_t>& blob, std::st
         h->root_hi = static_cast<uint32_t>(roots >> 32);
     }
     return true;
+}
+
+}  // namespace
+
+bool flatten_scene(const mcrt_scene_desc* d, std::vector<uint8_t>& blob, std::string& err) {
+    Layout L;
+    if (!plan_layout(d, L, err)) return false;
+    const int64_t n_texels = L.n_texels;
+    blob.assign(L.total, 0);
+    FlatHeader* h = reinterpret_cast<FlatHeader*>(blob.data());
+    FlatMesh* fm = reinterpret_cast<FlatMesh*>(blob.data() + L.mesh_off);
+    float* pool = reinterpret_cast<float*>(blob.data() + L.texel_off);
+
+    for (int i = 0; i < d->n_textures; ++i) {
+        if (L.tex_base[i] < 0) continue;
+        const mcrt_texture& t = d->textures[i];
+        std::memcpy(pool + 4 * L.tex_base[i], t.rgba, static_cast<size_t>(t.width) * t.height * 16);
+    }
+    // alpha predicates: the only two ways a texel's value decides hit/miss
+    // (texColor.a == 0.0f, intersection.cpp:311; backTexColor.a > 0.0f, :349)
+    uint32_t* abits = reinterpret_cast<uint32_t*>(blob.data() + L.alpha_off);
+    for (int64_t i = 0; i < n_texels; ++i) {
+        const float a = pool[4 * i + 3];
+        uint32_t bits = (a == 0.0f ? 1u : 0u) | (a > 0.0f ? 2u : 0u);
+        abits[i >> 4] |= bits << ((i & 15) * 2);
+    }
+    if (!fill_view(d, L, h, fm, err)) return false;
+    for (int i = 0; i < d->n_meshes; ++i) {  // MESH_OPAQUE: a null texture is opaque magenta, an empty one Color() with alpha 1
+        FlatMesh& f = fm[i];
+        bool opaque = true;
+        for (int face = 0; face < 6 && opaque; ++face) {
+            if (f.tex_off[face] < 0) continue;
+            const int64_t n = static_cast<int64_t>(f.tex_w[face]) * f.tex_h[face];
+            for (int64_t k = 0; k < n && opaque; ++k) opaque = !(pool[4 * (f.tex_off[face] + k) + 3] == 0.0f);
+        }
+        if (opaque) f.flags |= MESH_OPAQUE;
+    }
+    return true;
+}
+
+bool flatten_view_table(const mcrt_scene_desc* d, std::vector<uint8_t>& table, std::string& err) {
+    Layout L;
+    if (!plan_layout(d, L, err)) return false;
+    table.assign(L.texel_off, 0);
+    return fill_view(d, L, reinterpret_cast<FlatHeader*>(table.data()), reinterpret_cast<FlatMesh*>(table.data() + L.mesh_off), err);
 }
 
 }  // namespace mcrt

@@ -113,6 +113,12 @@ struct mcrt_scene {
     uint32_t alpha_words = 0;
     uint32_t n_meshes = 0;
     bool posed = false;  // any mesh with MESH_ROTATED
+    // A repaintable handle's view, as mcrt_scene_create_skin or the last mcrt_scene_set_view* gave it: what a NULL pose or look
+    // of the next view keeps.  has_pose / has_look false: the builder's own (a NULL argument so far).  Of view_look the light,
+    // camera and background fields count; its meshes and textures are NULL.  Reset where a pooled shell is reused.
+    bool has_pose = false, has_look = false;
+    float view_pose[12] = {};
+    mcrt_scene_desc view_look = {};
     std::vector<uint8_t> host_meshes;  // host copy of FlatHeader + FlatMesh[] (screen bounds for workspace planning)
     DeviceBuffer blob;
     // the owner faces of a light bake (kernels.h: BakeFace), uploaded with the blob and kept behind it in the same buffer: a
@@ -290,6 +296,16 @@ int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_confi
 int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
+// gives the n repaintable handles the views (poses[i], looks[i]); NULL poses, looks or looks[i]: the handle's own
+// (mcrt_scene_set_views_batch_device)
+int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, hipStream_t stream);
+
+// ---- api.cpp
+// the light, camera and background fields of `look` into `desc` (what mcrt_scene_create_skin reads of a look)
+void apply_look(mcrt_scene_desc* desc, const mcrt_scene_desc* look);
+// The prefix [FlatHeader][FlatMesh x n] of the blob of the kind's white figure at pose / look (NULL: the builder's own), with
+// MESH_OPAQUE on every mesh as that figure has it.  No device work.
+int skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, std::vector<uint8_t>& table);
 
 }  // namespace mcrt_host
 

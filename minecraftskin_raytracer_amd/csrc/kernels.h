@@ -419,6 +419,21 @@ struct SkinPaintFrame {
 };
 size_t skin_tables_bytes(int n_texels);
 
+// ---- views of resident scenes (mcrt_scene_set_view_device & co): the prefix [FlatHeader][FlatMesh x n] of a repaintable
+// handle's blob is what pose, camera and light decide, but for the MESH_OPAQUE bit of every FlatMesh::flags, which the skin
+// owns.  One wave per scene copies a table the host flattened (flatten_view_table) over that prefix in 16-byte chunks and
+// keeps those bits as the blob has them.  Nothing from texel_offset on is touched.
+constexpr int kViewMaxChunks = 192;  // 64 lanes x 3 chunks: (192 + 12 * 192) / 16 = 156 for a 64x64 skin, 96 for a 64x32 one
+struct SceneViewShape {
+    uint32_t mesh_offset;  // of the kind's blob (FlatHeader), a multiple of 16
+    int n_meshes;          // 12 or 7
+    int n_chunks;          // texel_offset / 16
+};
+struct SceneViewFrame {
+    uint8_t* scene;        // the resident blob
+    const uint8_t* table;  // the staged prefix in device memory, 16-byte aligned
+};
+
 // ======== pipeline launches (render_kernels.hip) ========
 // seeds p.tile_rng: one mt19937 per owned tile (tile_renderer.cpp:78).  A function of the frame width, the
 // tile size and the shard only — the caller keeps the result across renders and calls this when those change.
@@ -446,7 +461,7 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
-// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, light bake, skin repaints ========
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, light bake, skin repaints, views ========
 hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's LDS tables
@@ -477,6 +492,9 @@ hipError_t launch_bake_batch(const BakeFrame* d_table, int n_frames, const BakeS
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);
+hipError_t launch_scene_view(const SceneViewFrame& f, const SceneViewShape& shape, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
+hipError_t launch_scene_view_batch(const SceneViewFrame* d_table, int n_frames, const SceneViewShape& shape, hipStream_t stream);
 
 // ======== utilities and probes (util_kernels.hip) ========
 hipError_t launch_unpack_rows(const mcrt_config& cfg, const Shard& sh, const float* packed, float* frame,

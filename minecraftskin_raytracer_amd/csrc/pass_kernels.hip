@@ -216,6 +216,43 @@ __global__ __launch_bounds__(kSkinBlock) void skin_paint_batch_kernel(SkinPaintT
 }
 
 // ---------------------------------------------------------------------------------------------
+// views of resident scenes (kernels.h: SceneViewFrame): a repaintable handle's blob takes the header and the mesh table of
+// another pose, camera and light from a table the host flattened.  One wave per scene:
+//   lane i   chunks i, i + 64, i + 128 of the prefix [0, texel_offset), 16 bytes each, one load and one store per chunk;
+//            the chunk that holds a mesh's `flags` (byte 68 of its FlatMesh: word 1 of the chunk at byte 64) first loads the
+//            blob's own word and keeps its MESH_OPAQUE bit — the skin's, not the view's
+// A lane reads and writes its own chunks only: no LDS, no barrier.  Every store is a vector store; nothing from texel_offset
+// on is written.
+// ---------------------------------------------------------------------------------------------
+constexpr int kViewBlock = 64;
+constexpr uint32_t kMeshChunks = sizeof(FlatMesh) / 16, kFlagsChunk = 4;  // chunks per mesh; the one with `flags`, as word 1
+static_assert(sizeof(FlatMesh) % 16 == 0 && offsetof(FlatMesh, flags) == kFlagsChunk * 16 + 4, "scene_view_body: where FlatMesh::flags lies");
+static_assert(kViewMaxChunks == 3 * kViewBlock, "scene_view_body: three chunks per lane");
+__device__ __forceinline__ void scene_view_body(const SceneViewFrame& __restrict__ f, const SceneViewShape& __restrict__ sh) {
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(f.table);
+    uint4* dst = reinterpret_cast<uint4*>(f.scene);
+    const uint32_t first = sh.mesh_offset / 16u + kFlagsChunk;  // mesh 0's flags chunk
+    const uint32_t n_chunks = static_cast<uint32_t>(sh.n_chunks);
+#pragma unroll
+    for (uint32_t k = 0; k < 3; ++k) {
+        const uint32_t c = threadIdx.x + k * kViewBlock;
+        if (c >= n_chunks) break;
+        uint4 v = src[c];
+        const uint32_t r = c - first;
+        if (c >= first && r % kMeshChunks == 0u && r / kMeshChunks < static_cast<uint32_t>(sh.n_meshes)) {
+            const uint32_t current = reinterpret_cast<const uint32_t*>(f.scene)[4u * c + 1u];
+            v.y = (v.y & ~static_cast<uint32_t>(MESH_OPAQUE)) | (current & MESH_OPAQUE);
+        }
+        dst[c] = v;
+    }
+}
+__global__ __launch_bounds__(kViewBlock) void scene_view_kernel(const SceneViewFrame f, const SceneViewShape sh) { scene_view_body(f, sh); }
+using SceneViewTable = const __attribute__((address_space(4))) SceneViewFrame*;
+__global__ __launch_bounds__(kViewBlock) void scene_view_batch_kernel(SceneViewTable table, const SceneViewShape sh) {
+    scene_view_body(*(const SceneViewFrame*)(table + blockIdx.y), sh);
+}
+
+// ---------------------------------------------------------------------------------------------
 // ground shadow (kernels.h: GroundFrame): the figure's soft shadow on the plane y = ground_y, as planes of their own.  Per
 // pixel the layers' pixel-centre ray, its point P on the plane, and computeSoftShadow(P, (0, 1, 0)) (shading.cpp:28-60) with
 // the seed of a hit at depth 0 (raytracer.cpp:110-112) — the figure in front of the plane plays no part.  No workspace.
@@ -1658,6 +1695,22 @@ hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, 
     if (n_frames <= 0) return hipSuccess;
     if (!skin_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
     hipLaunchKernelGGL(skin_paint_batch_kernel, dim3(1, static_cast<unsigned>(n_frames)), dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shape);
+    return hipGetLastError();
+}
+// ---- views of resident scenes (kernels.h) -------------------------------------------------------------
+static bool view_shape_ok(const SceneViewShape& sh) {  // three chunks per lane; the mesh table inside the prefix
+    return sh.n_chunks > 0 && sh.n_chunks <= kViewMaxChunks && sh.mesh_offset % 16u == 0 && sh.n_meshes >= 0 && sh.n_meshes <= kSkinMaxMeshes &&
+           sh.mesh_offset / 16u + kMeshChunks * static_cast<uint32_t>(sh.n_meshes) <= static_cast<uint32_t>(sh.n_chunks);
+}
+hipError_t launch_scene_view(const SceneViewFrame& f, const SceneViewShape& shape, hipStream_t stream) {
+    if (!view_shape_ok(shape) || !f.scene || !f.table || (reinterpret_cast<uintptr_t>(f.table) & 15u) != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scene_view_kernel, dim3(1), dim3(kViewBlock), 0, stream, f, shape);
+    return hipGetLastError();
+}
+hipError_t launch_scene_view_batch(const SceneViewFrame* d_table, int n_frames, const SceneViewShape& shape, hipStream_t stream) {
+    if (n_frames <= 0) return hipSuccess;
+    if (!view_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scene_view_batch_kernel, dim3(1, static_cast<unsigned>(n_frames)), dim3(kViewBlock), 0, stream, SceneViewTable(d_table), shape);
     return hipGetLastError();
 }
 

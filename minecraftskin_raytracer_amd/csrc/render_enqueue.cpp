@@ -938,6 +938,107 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
     return MCRT_OK;
 }
 
+// ---- views of resident scenes (mcrt_scene_set_view_device & co): the prefix [FlatHeader][FlatMesh x n] of a repaintable
+// handle's blob is flattened on the host for the new pose and look (skin_view_table: the flattener's own code, no texel read),
+// the tables of a call travel in ONE asynchronous copy through a slot of the table ring — pinned staging, a device buffer
+// that grows on demand, and an event behind the launches that read it, so a later call refills neither too early — and one
+// wave per handle writes its table over the blob's prefix, keeping the MESH_OPAQUE bits the skin owns.  The call sits in the
+// handles' event chains like a repaint.  Behind the launch the handles' host state follows: host_meshes, posed and the
+// remembered view — what touched_tiles_per_row, lds_fit and the passes' views plan from, so a render's RenderParams (and with
+// them the recorded launch graph it may replay: launch_or_replay compares every word) are those of a fresh handle at that view.
+int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, hipStream_t stream) {
+    // argument checks, before any device work (they read `device` and `skin_height` of a handle, nothing else)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n must be >= 0");
+    if (n > 0 && !scenes) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (n == 0) return MCRT_OK;
+    const int kind = scenes[0]->skin_height, device = scenes[0]->device;
+    for (int i = 0; i < n; ++i)
+        if (scenes[i]->skin_height != 64 && scenes[i]->skin_height != 32)
+            return fail(MCRT_ERR_INVALID, "a handle was not created by mcrt_scene_create_skin (only those hold the full mesh table a view is flattened for)");
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must be of one skin kind");
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    {
+        std::vector<mcrt_scene*> sorted(scenes, scenes + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (two views for one blob)");
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a view change cannot be recorded into a caller's graph (it takes the handles' events)");
+    (void)hipGetLastError();
+    // the tables, on the host; each must have the layout of the blob it goes into
+    const size_t table_bytes = scenes[0]->host_meshes.size();  // one kind: one blob layout
+    std::vector<uint8_t> staged(static_cast<size_t>(n) * table_bytes), table;
+    for (int i = 0; i < n; ++i) {
+        const mcrt_scene* s = scenes[i];
+        const float* pose = poses ? poses[i] : (s->has_pose ? s->view_pose : nullptr);
+        const mcrt_scene_desc* look = (looks && looks[i]) ? looks[i] : (s->has_look ? &s->view_look : nullptr);
+        if (const int rc = skin_view_table(kind, pose, look, table); rc != MCRT_OK) return rc;
+        bool same = table_bytes >= sizeof(FlatHeader) && table.size() == table_bytes && s->host_meshes.size() == table_bytes;
+        if (same) {
+            const FlatHeader* a = reinterpret_cast<const FlatHeader*>(table.data());
+            const FlatHeader* b = reinterpret_cast<const FlatHeader*>(s->host_meshes.data());
+            same = a->magic == b->magic && a->n_meshes == b->n_meshes && a->n_texels == b->n_texels && a->mesh_offset == b->mesh_offset &&
+                   a->texel_offset == b->texel_offset && a->blob_bytes == b->blob_bytes && a->alpha_offset == b->alpha_offset &&
+                   a->alpha_words == b->alpha_words && a->texel_offset == table_bytes;
+        }
+        if (!same) return fail(MCRT_ERR_HIP, "internal error: a view's table does not have the layout of the handle's blob");
+        std::memcpy(staged.data() + static_cast<size_t>(i) * table_bytes, table.data(), table_bytes);
+    }
+    const FlatHeader* h = reinterpret_cast<const FlatHeader*>(scenes[0]->host_meshes.data());
+    SceneViewShape shape{};
+    shape.mesh_offset = h->mesh_offset, shape.n_meshes = static_cast<int>(h->n_meshes), shape.n_chunks = static_cast<int>(table_bytes / 16);
+    if (table_bytes % 16 != 0 || shape.n_chunks > kViewMaxChunks) return fail(MCRT_ERR_HIP, "internal error: a view's table does not fit the kernel's three chunks per lane");
+    TableUpload tables;
+    if (const int rc = upload_table(device, staged.data(), staged.size(), stream, tables); rc != MCRT_OK) return rc;
+    if (tables.status != hipSuccess) return hip_fail(tables.status, "view tables upload");
+    std::vector<SceneViewFrame> frames(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        mcrt_scene* s = scenes[i];
+        frames[static_cast<size_t>(i)] = SceneViewFrame{static_cast<uint8_t*>(s->blob.ptr), static_cast<const uint8_t*>(tables.dev) + static_cast<size_t>(i) * table_bytes};
+        if (const int rc = join_handle_chain(s, stream); rc != MCRT_OK) return rc;
+    }
+    int launched = 0;  // handles whose launch was enqueued (a batch beyond kLayersBatchMaxFrames takes several)
+    int rc = launch_pass(
+        device, frames, stream, "view launches",
+        [&](const SceneViewFrame& f) {
+            const hipError_t e = launch_scene_view(f, shape, stream);
+            if (e == hipSuccess) launched = 1;
+            return e;
+        },
+        [&](const SceneViewFrame* d_table, int m) {
+            const hipError_t e = launch_scene_view_batch(d_table, m, shape, stream);
+            if (e == hipSuccess) launched += m;
+            return e;
+        });
+    if (launched > 0)
+        if (const hipError_t e = tables.commit(stream); e != hipSuccess && rc == MCRT_OK) rc = hip_fail(e, "view launches");
+    // the host state of the handles whose blob the device now rewrites, and their chains behind the launch (a handle whose
+    // launch was not enqueued keeps its view, its state and its earlier `last_done`)
+    for (int i = 0; i < launched; ++i) {
+        mcrt_scene* s = scenes[i];
+        const uint8_t* t = staged.data() + static_cast<size_t>(i) * table_bytes;
+        s->host_meshes.assign(t, t + table_bytes);
+        const FlatMesh* fm = reinterpret_cast<const FlatMesh*>(t + shape.mesh_offset);
+        s->posed = false;
+        for (int m = 0; m < shape.n_meshes; ++m) s->posed = s->posed || (fm[m].flags & MESH_ROTATED) != 0;
+        if (poses) {
+            s->has_pose = true;
+            std::memcpy(s->view_pose, poses[i], sizeof s->view_pose);
+        }
+        if (looks && looks[i]) {
+            s->has_look = true;
+            apply_look(&s->view_look, looks[i]);
+        }
+        if (const int chained = extend_handle_chain(s, stream); chained != MCRT_OK && rc == MCRT_OK) rc = chained;
+    }
+    return rc;
+}
+
 }  // namespace mcrt_host
 
 extern "C" {
@@ -963,6 +1064,24 @@ int mcrt_scene_set_skin(mcrt_scene* s, const uint8_t* skin_rgba8) {
     // (a second upload into s->skin may not overtake the repaint that reads the first: this call waits for its own)
     HIP_TRY(hipMemcpy(s->skin.ptr, skin_rgba8, bytes, hipMemcpyHostToDevice));
     const int rc = mcrt_scene_set_skin_device(s, static_cast<const uint8_t*>(s->skin.ptr), nullptr);
+    if (rc != MCRT_OK) return rc;
+    HIP_TRY(hipEventSynchronize(s->last_done));
+    return MCRT_OK;
+}
+
+int mcrt_scene_set_view_device(mcrt_scene* s, const float pose[12], const mcrt_scene_desc* look, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const mcrt_scene_desc* one_look[1] = {look};
+    return set_views_batch_device(one, 1, reinterpret_cast<const float(*)[12]>(pose), one_look, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, void* stream) {
+    return set_views_batch_device(scenes, n, poses, looks, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_view(mcrt_scene* s, const float pose[12], const mcrt_scene_desc* look) {
+    const int rc = mcrt_scene_set_view_device(s, pose, look, nullptr);
     if (rc != MCRT_OK) return rc;
     HIP_TRY(hipEventSynchronize(s->last_done));
     return MCRT_OK;

@@ -282,12 +282,7 @@ FaceSource face_source(int skin_height, int mesh, int face_slot) {
     return FaceSource{face_rect(box, face), mirror_of >= 0};
 }
 
-}  // namespace
-
-extern "C" {
-
-int mcrt_build_skin_scene(const uint8_t* rgba8, int w, int h, const float pose[12], mcrt_scene_desc** out) {
-    if (!rgba8 || !out || w != 64 || (h != 64 && h != 32)) return MCRT_ERR_INVALID;  // skin_parser.cpp:122-131
+Skin parse_skin(const uint8_t* rgba8, int w, int h) {  // w == 64, h == 64 or 32
     SkinImage img;
     img.w = w;
     img.h = h;
@@ -307,7 +302,23 @@ int mcrt_build_skin_scene(const uint8_t* rgba8, int w, int h, const float pose[1
         s.inner[3] = mirror_part(s.inner[kLegacyMirrorOf[3]]);
         s.inner[5] = mirror_part(s.inner[kLegacyMirrorOf[5]]);
     }
-    *out = &assemble(s, pose)->desc;
+    return s;
+}
+}  // namespace
+
+// The figure mcrt_build_skin_scene builds from an all-(255,255,255,255) skin of the kind (64 / 32) — every part present — at
+// `pose`: what a view of a repaintable handle is flattened from (api.cpp).  The white skin is parsed once per kind and process.
+extern "C" __attribute__((visibility("hidden"))) mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, const float pose[12]) {
+    static const Skin white[2] = {parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64),
+                                  parse_skin(std::vector<uint8_t>(64 * 32 * 4, 255).data(), 64, 32)};
+    return &assemble(white[skin_height == 32 ? 1 : 0], pose)->desc;
+}
+
+extern "C" {
+
+int mcrt_build_skin_scene(const uint8_t* rgba8, int w, int h, const float pose[12], mcrt_scene_desc** out) {
+    if (!rgba8 || !out || w != 64 || (h != 64 && h != 32)) return MCRT_ERR_INVALID;  // skin_parser.cpp:122-131
+    *out = &assemble(parse_skin(rgba8, w, h), pose)->desc;
     return MCRT_OK;
 }
 
