@@ -31,6 +31,12 @@ The limits of the scene tables (tests/big_scene_cases.py; the runs and compariso
                transparent), intersect on 1 500 rays, ground, reflection, layers with picks and the light planes; the summary
                records the census of what the oracle's planes held (big_scene_cases.CENSUS); a case whose expectation cannot be
                made (the generator's own assertions) ends the run with exit status 3
+Repaintable resident scenes (tests/resident_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_resident_fuzz.py):
+  resident     seed k is make_script(k): 2 ... 4 handles of DeviceScene.for_skin walked through repaints, views, background modes,
+               renders (some until the launch graph replays), the single and batched passes, picks and blob checkpoints on two
+               streams, even seeds with a stretch of more than kTableSlots batch calls without a host wait; every checkpoint
+               against the oracle and the host flattener; the summary records the scripts, the checkpoints compared by kind and
+               the census of what the oracle saw (resident_fuzz_cases.census)
 A mismatch prints the case, the plane, the number of differing pixels and the first of them; the exit status is then 1.  After
 a HIP error (exit status 2) nothing more is started.  MCRT_BUNDLE_DECISIONS=0 / MCRT_REFLECT_CULL=0 in the environment render
 without the whole-bundle decisions / the reflection's tile culling: a mismatch that goes away with one is that shortcut's."""
@@ -46,7 +52,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide", "light", "bake", "big") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -232,6 +238,43 @@ def big_sweep():
     sys.exit(1 if bad else 0)
 
 
+def resident_sweep():
+    import resident_fuzz_cases as RF, test_gpu_resident_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    # the expectations are made ahead of the device by worker processes (forked before the device is first used; they never use
+    # it), in the order of the seeds
+    import multiprocessing
+
+    workers = max(1, min(14, len(os.sched_getaffinity(0)) - 2, int(os.environ.get("OMP_NUM_THREADS", "16")) - 2))
+    RF._transparent_checker()  # built once, before the fork
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    ahead = pool.imap(RF.worker_script_expectation, range(first, first + count))
+    orc = oraclelib.Oracle()
+    bad, compared, total = 0, {}, {}
+    t0 = time.time()
+    for k, seed in enumerate(range(first, first + count)):
+        script = RF.make_script(seed)
+        exp = next(ahead)
+        try:
+            lines = T.run_script(M, orc, script, exp, compared)
+        except (McrtError, RuntimeError) as e:  # the library's, or torch's at a host wait
+            print(f"HIP ERROR script {seed}: {e}", flush=True)
+            print(f"fuzz resident: stopped at seed {seed} after {k} scripts, {bad} mismatching script(s)")
+            pool.terminate()
+            sys.exit(2)
+        RF.add_census(total, RF.census([script], [exp]))
+        if lines:
+            bad += 1
+            print("\n".join(lines[:20]), flush=True)
+        if k % 50 == 49:
+            print(f"... {k + 1} scripts, {bad} mismatching, {time.time() - t0:.0f} s", flush=True)
+    print(f"fuzz resident: {count} scripts from seed {first}: {bad} mismatching script(s); checkpoints compared {dict(sorted(compared.items()))}; "
+          f"{time.time() - t0:.0f} s; the oracle's census {total}")
+    pool.terminate()
+    sys.exit(1 if bad else 0)
+
+
 def pass_sweep():
     import ground_checker as G, layers_checker as L, pass_fuzz_cases as PF, reflection_checker as R
     from minecraftskin_raytracer_amd._lib import McrtError
@@ -304,6 +347,8 @@ if mode == "bake":
     bake_sweep()
 if mode == "big":
     big_sweep()
+if mode == "resident":
+    resident_sweep()
 if len(sys.argv) > 3 and sys.argv[3] == "bundle":
     make_case = make_bundle_case
 if len(sys.argv) > 3 and sys.argv[3] == "wide":
