@@ -669,6 +669,113 @@ int mcrt_skin_view_table(int skin_height, const float pose[12], const mcrt_scene
  * entry; n < 0; a handle that mcrt_scene_create_skin did not create; handles of different skin kinds or devices in one batch; a
  * handle listed twice; a stream that is being captured. */
 
+/* ---- studio shot: the figure on a page, with its ground shadow and its floor reflection, as ONE finished image ---------------
+ * The transparent figure, the ground shadow and the ground reflection are layers for a compositor; this is that compositor, on
+ * the device: one call takes a scene — or n of them — to the finished RGBA8 image (or float frame, or PNG), and one image of
+ * 4 bytes per pixel leaves the card instead of float planes of 16 + 4 + 16 + 4.
+ * DEFINITION.  Per pixel, four quantities enter:
+ *   F       the MCRT_BACKGROUND_TRANSPARENT frame of cfg: the full beauty render — samples per pixel, depth of field, ambient
+ *           occlusion, bounces — in straight alpha
+ *   vis     the ground pass's visibility at ground_y (1.0f where the plane is not reached)
+ *   R, dR   the reflection pass's rgba and distance at ground_y ((0, 0, 0, 0) and FLT_MAX without a reflected hit)
+ *   pg      the page colour: page_color (MCRT_PAGE_COLOR), or RayTracer::backgroundColor(scene, u, v, &cfg).rgb at the pixel
+ *           centre u = (px + 0.5f) / width, v = (py + 0.5f) / height (MCRT_PAGE_REFERENCE; raytracer.cpp:16-34): cfg's
+ *           gradient, or scene.backgroundColor when gradient_bg is 0
+ * With s = shadow_strength, k = reflectivity, fade = reflection_fade, all arithmetic float32, one rounding per operation,
+ * uncontracted, in the order written, the division correctly rounded:
+ *   sh    = s * (1.0f - vis)
+ *   f     = fade > 0 ? clamp(1.0f - dR / fade, 0, 1) : 1.0f
+ *   ar    = (k * R.a) * f                                        (0 where there is no reflected hit)
+ *   keep  = (1.0f - sh) * (1.0f - ar)
+ *   fl.c  = pg.c * keep + R.c * ar                               c = r, g, b
+ *   out.c = F.c * F.a + fl.c * (1.0f - F.a)
+ *   out.a = 1.0f
+ *   rgba8 = (uint8_t)(clamp(out.c, 0, 1) * 255.0f + 0.5f) per channel, the quantiser of mcrt_quantize_rgba8
+ * CONSEQUENCES (part of the contract).
+ *   - A pixel with F.a == 1 holds F.rgb bit for bit: every pixel whose samples all hit opaque texels keeps the reference
+ *     render's rgb.
+ *   - With s == 0 the ground pass is not run, and its limit on shadow_samples does not apply; with k == 0 the reflection pass
+ *     is not run, and its limits on max_bounces and shadow_samples do not apply.  The image is the same bit for bit as if
+ *     the passes had run: sh and ar are exactly +0 either way, and R.c * 0 adds +0.
+ *   - The page under an EDGE pixel of the figure is the pixel-centre colour.  With MCRT_PAGE_REFERENCE and s = k = 0 the
+ *     image therefore equals the reference frame where F.a is 0 or 1 — under one sample per pixel without depth of field,
+ *     everywhere — but not at the figure's edges under several samples: there the reference blends the gradient's values at
+ *     the samples' own jittered positions, the shot blends the figure's samples over the value at the centre.
+ * The shadow is black and the page opaque (out.a = 1): a coloured shadow and a transparent page are not offered. */
+#define MCRT_PAGE_COLOR 0     /* page = page_color */
+#define MCRT_PAGE_REFERENCE 1 /* page = the reference's background at the pixel centre */
+typedef struct mcrt_shot {
+    int32_t page;           /* MCRT_PAGE_* */
+    float page_color[3];    /* read with MCRT_PAGE_COLOR; finite */
+    float shadow_strength;  /* s, 0..1: how dark the fully shadowed page is */
+    float reflectivity;     /* k, 0..1 */
+    float reflection_fade;  /* >= 0, finite: the reflection distance at which the mirror image has vanished; 0 = no fade */
+} mcrt_shot;
+/* MCRT_PAGE_REFERENCE, page_color white (1, 1, 1), shadow_strength 0.6, reflectivity 0.35, reflection_fade 0 */
+void mcrt_shot_init(mcrt_shot* shot);
+
+/* The blend alone, on planes the caller already has — device memory, frame i of every input in_stride_pixels pixels on, of
+ * every output out_stride_pixels pixels on (both >= width * height; the pixels between frames are neither read nor written).
+ * figure is required.  visibility NULL: vis = 1; reflection NULL: no mirror image; reflection_distance NULL is legal only
+ * with reflection_fade == 0 (whether or not there is a reflection plane).  The inputs must not hold NaN.  The rgba planes are
+ * read and written 16 bytes at a time where they lie on a 16-byte boundary and 4 bytes at a time elsewhere; the 1-float
+ * planes need their natural alignment only.  Of a handle the call reads the device and — with MCRT_PAGE_REFERENCE and
+ * gradient_bg 0, on the device in stream order — the scene's background colour; a handle may be listed more than once; of
+ * cfg it reads width, height, tile_size (> 0, as everywhere), gradient_bg, gradient_scale, bg_center and bg_edge.  One launch
+ * per 4096 frames, asynchronous on `stream`; none of the handles' events. */
+typedef struct mcrt_shot_inputs {
+    const float* figure;               /* 4 floats per pixel */
+    const float* visibility;           /* 1 float per pixel, or NULL */
+    const float* reflection;           /* 4 floats per pixel, or NULL */
+    const float* reflection_distance;  /* 1 float per pixel, or NULL */
+} mcrt_shot_inputs;
+int mcrt_composite_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot,
+                                     const mcrt_shot_inputs* d_in, size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8,
+                                     size_t out_stride_pixels, void* stream);
+
+/* Render + ground + reflection + blend.  The figure of every scene is rendered with MCRT_BACKGROUND_TRANSPARENT whatever the
+ * handle's background mode is, through an override inside the call: the handle's mode is never written, other threads never
+ * see another one, and it is the same afterwards.  The intermediate planes live in d_scratch, device memory of the caller's,
+ * 16-byte aligned, of at least mcrt_shot_scratch_bytes(cfg, shot, n_frames) bytes (host only; 0 for a NULL argument, an
+ * invalid shot, a zero-size frame or n_frames <= 0): the library allocates nothing behind the device forms.  It holds only
+ * the planes the shot needs, one after the other, each for all n_frames frames (width * height pixels apart) and each
+ * starting on a 16-byte boundary:
+ *     figure 16 B/px   reflection rgba 16 B/px if k > 0   visibility 4 B/px if s > 0   reflection distance 4 B/px if k > 0 && fade > 0
+ * ORDERING.  Everything is enqueued on `stream`, in order: the batched render (each handle's event chain as for
+ * mcrt_render_batch_device: it waits for the handle's earlier renders, repaints and view changes, and the handle's next
+ * render waits for it), the ground pass, the reflection pass, the blend.  So a shot enqueued behind
+ * mcrt_scene_set_skin_device / mcrt_scene_set_view_device on the same stream shows the new skin and view without a
+ * synchronisation.  Nothing is forked onto internal streams beside the render.  ground_y: n_frames heights in HOST memory,
+ * read before the call returns.  Frame i lands at d_out_f32 + i * frame_stride_pixels * 4 floats and / or d_out_rgba8 +
+ * i * frame_stride_pixels * 4 bytes.
+ * MCRT_ERR_INVALID, before any device work, with outputs and scratch untouched: a NULL argument (cfg, shot, the array, an
+ * entry, ground_y); n_frames < 0; a page other than the two constants; shadow_strength or reflectivity outside [0, 1] or NaN;
+ * a reflection_fade that is negative or not finite; a page colour that is not finite; a ground_y that is not finite; both
+ * outputs NULL; a handle listed twice (each owns one workspace); max_bounces > 4000; soft_shadows && shadow_samples > 113
+ * when s > 0 or k > 0; max_bounces > 8 when k > 0; a frame of 2^31 pixels or more; a stride below width * height; scratch
+ * NULL, too small or not 16-byte aligned; handles on different devices; a stream that is being captured (shots are not
+ * recorded into a caller's graph).  The composite call refuses what applies to it: the NULL arguments (figure included), the
+ * shot's fields, reflection_distance NULL with reflection_fade > 0, both outputs NULL, the frame size, either stride, the
+ * devices, a captured stream.  Zero-size frames (width, height or tile_size <= 0) and n_frames == 0: MCRT_OK, nothing
+ * written, checked behind the argument checks above it in this list and before strides and scratch. */
+size_t mcrt_shot_scratch_bytes(const mcrt_config* cfg, const mcrt_shot* shot, int n_frames);
+int mcrt_render_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot,
+                                  const float* ground_y, void* d_scratch, size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8,
+                                  size_t frame_stride_pixels, void* stream);
+/* one scene, one height */
+int mcrt_render_shot_device(mcrt_scene* scene, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, void* d_scratch,
+                            size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8, void* stream);
+/* One-shot host forms: host pointers, rendered on `device` with pooled handles like mcrt_render_batch; they allocate and free
+ * their own scratch.  out_rgba: n * width * height * 4 floats and / or out_rgba8: as many bytes, frame after frame. */
+int mcrt_render_shot(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, float* out_rgba,
+                     uint8_t* out_rgba8, int device);
+int mcrt_render_shot_batch(const mcrt_scene_desc* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot,
+                           const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device);
+/* mcrt_render_shot's RGBA8 image as a PNG (colour type 6, alpha 255 everywhere); a zero-size frame: MCRT_ERR_INVALID, as
+ * for mcrt_render_png */
+int mcrt_render_shot_png(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, const char* path,
+                         int device);
+
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);
 

@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "mcrt_skin_pool_map", "mcrt_probe_scene_blob",
     "mcrt_bake_light_device", "mcrt_bake_light_batch_device", "mcrt_bake_light", "mcrt_bake_texel_table", "mcrt_scene_texels",
     "mcrt_scene_set_view", "mcrt_scene_set_view_device", "mcrt_scene_set_views_batch_device", "mcrt_skin_view_table",
+    "mcrt_shot_init", "mcrt_shot_scratch_bytes", "mcrt_composite_shot_batch_device", "mcrt_render_shot_batch_device",
+    "mcrt_render_shot_device", "mcrt_render_shot", "mcrt_render_shot_batch", "mcrt_render_shot_png",
 ]
 
 
@@ -58,6 +60,7 @@ def load():
     reflection_p = C.POINTER(abi.McrtReflection)
     light_p = C.POINTER(abi.McrtLightPlanes)
     bake_p = C.POINTER(abi.McrtBakePlanes)
+    shot_p = C.POINTER(abi.McrtShot)
     sig = {
         "mcrt_config_init": (None, [cfg_p]),
         "mcrt_generate_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(abi.McrtTile), C.c_int]),
@@ -110,6 +113,14 @@ def load():
         "mcrt_scene_set_view_device": (C.c_int, [vp, f_p, desc_p, vp]),
         "mcrt_scene_set_views_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.POINTER(desc_p), vp]),
         "mcrt_skin_view_table": (C.c_int, [C.c_int, f_p, desc_p, vp, C.c_size_t]),
+        "mcrt_shot_init": (None, [shot_p]),
+        "mcrt_shot_scratch_bytes": (C.c_size_t, [cfg_p, shot_p, C.c_int]),
+        "mcrt_composite_shot_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, shot_p, C.POINTER(abi.McrtShotInputs), C.c_size_t, vp, vp, C.c_size_t, vp]),
+        "mcrt_render_shot_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, shot_p, f_p, vp, C.c_size_t, vp, vp, C.c_size_t, vp]),
+        "mcrt_render_shot_device": (C.c_int, [vp, cfg_p, shot_p, C.c_float, vp, C.c_size_t, vp, vp, vp]),
+        "mcrt_render_shot": (C.c_int, [desc_p, cfg_p, shot_p, C.c_float, f_p, u8_p, C.c_int]),
+        "mcrt_render_shot_batch": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, shot_p, f_p, f_p, u8_p, C.c_int]),
+        "mcrt_render_shot_png": (C.c_int, [desc_p, cfg_p, shot_p, C.c_float, C.c_char_p, C.c_int]),
         "mcrt_probe_scene_blob": (C.c_int, [vp, vp, C.c_size_t]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),
         "mcrt_encode_png_rgba8": (C.c_size_t, [u8_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),

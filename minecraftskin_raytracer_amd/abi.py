@@ -268,6 +268,49 @@ def bake_names(planes) -> tuple:
     return tuple(n for n in BAKE_NAMES if n in names)
 
 
+PAGE_COLOR = 0  # MCRT_PAGE_*: the page of a studio shot is Shot.pageColor
+PAGE_REFERENCE = 1  # the reference's background (the config's gradient, or the scene's colour) at the pixel centre
+PAGES = {"color": PAGE_COLOR, "reference": PAGE_REFERENCE}
+
+
+class McrtShot(C.Structure):
+    """mcrt_shot: the settings of a studio shot's blend (include/mcrt.h)."""
+
+    _fields_ = [("page", C.c_int32), ("page_color", C.c_float * 3), ("shadow_strength", C.c_float), ("reflectivity", C.c_float),
+                ("reflection_fade", C.c_float)]
+
+
+class McrtShotInputs(C.Structure):
+    """mcrt_shot_inputs: the device planes mcrt_composite_shot_batch_device blends; all but the figure may be NULL."""
+
+    _fields_ = [("figure", C.c_void_p), ("visibility", C.c_void_p), ("reflection", C.c_void_p), ("reflection_distance", C.c_void_p)]
+
+
+@dataclass
+class Shot:
+    """mcrt_shot with mcrt_shot_init's defaults: the figure over the reference's background, a ground shadow of strength 0.6
+    and a floor reflection of reflectivity 0.35 that does not fade.  ``page``: ``"reference"`` or ``"color"`` (then
+    ``pageColor``); ``reflectionFade``: the reflection distance at which the mirror image has vanished, 0 = no fade."""
+
+    page: str = "reference"
+    pageColor: Sequence[float] = (1.0, 1.0, 1.0)
+    shadowStrength: float = 0.6
+    reflectivity: float = 0.35
+    reflectionFade: float = 0.0
+
+    def to_c(self) -> McrtShot:
+        if not isinstance(self.page, str) or self.page not in PAGES:
+            raise ValueError(f"page must be 'reference' or 'color', not {self.page!r}")
+        s = McrtShot()
+        s.page = PAGES[self.page]
+        for i in range(3):
+            s.page_color[i] = float(self.pageColor[i])
+        s.shadow_strength = float(self.shadowStrength)
+        s.reflectivity = float(self.reflectivity)
+        s.reflection_fade = float(self.reflectionFade)
+        return s
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 
 SURFACE_DTYPE = np.dtype(

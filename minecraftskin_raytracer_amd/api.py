@@ -347,6 +347,37 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderShot(scene, config: Config, shot: Optional[abi.Shot] = None, ground: Optional[float] = None, rgba8: bool = True,
+                   device: int = 0) -> np.ndarray:
+        """The studio shot (mcrt_render_shot): the figure on a page, with its ground shadow and its floor reflection at
+        y = ``ground`` (``None``: the scene's floor, ``scene_floor``), blended on the device — (H, W, 4) uint8, or float32 with
+        ``rgba8=False``; alpha is 255 / 1.0 everywhere.  ``shot``: ``abi.Shot`` (``None``: its defaults).  The figure is the
+        ``background="transparent"`` render of ``config``; the definition of the blend is in include/mcrt.h.  Failures raise
+        ``McrtError``."""
+        return TileRenderer.renderShotBatch([scene], config, shot, ground, rgba8, device)[0]
+
+    @staticmethod
+    def renderShotBatch(scenes, config: Config, shot: Optional[abi.Shot] = None, ground=None, rgba8: bool = True, device: int = 0) -> np.ndarray:
+        """``renderShot`` for N scenes of one config in one call (mcrt_render_shot_batch): one batched render, one ground and
+        one reflection launch, one blend, one download.  ``ground``: ``None`` (every scene's own floor), one height for all, or
+        N heights.  Returns (N, H, W, 4) uint8, or float32 with ``rgba8=False``."""
+        s = (shot if shot is not None else abi.Shot()).to_c()
+        descs = [_as_desc(d) for d in scenes]
+        n = len(descs)
+        heights = _ground_heights(descs, ground)
+        w, h = max(config.width, 0), max(config.height, 0)
+        out = np.zeros((n, h, w, 4), np.uint8 if rgba8 else np.float32)
+        out[..., 3] = 255 if rgba8 else 1.0
+        c = config.to_c()
+        arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*[d.ptr for d in descs])
+        gy = (C.c_float * max(n, 1))(*heights)
+        buf = out if out.size else np.zeros(4, out.dtype)  # (no frame: the call checks its arguments and writes nothing)
+        f = None if rgba8 else abi.fptr(buf)
+        b = buf.ctypes.data_as(C.POINTER(C.c_uint8)) if rgba8 else None
+        check(load().mcrt_render_shot_batch(arr, n, C.byref(c), C.byref(s), gy, f, b, int(device)))
+        return out
+
+    @staticmethod
     def renderLight(scene, config: Config, planes=abi.LIGHT_NAMES, device: int = 0) -> dict:
         """What the light does on the figure itself (mcrt_render_light), at the primary hit of each pixel-centre ray: a dict of
         the wanted planes — ``visibility`` (H, W) float32, the share of the disk light that reaches the surface (1 at a miss);
@@ -556,6 +587,25 @@ def render_png(scene, config: Config, path: str, device: int = 0, background: st
     if mode != abi.BACKGROUND_REFERENCE:
         return load().mcrt_render_png_ex(_as_desc(scene).ptr, C.byref(c), mode, os.fsencode(path), device) == 0
     return load().mcrt_render_png(_as_desc(scene).ptr, C.byref(c), os.fsencode(path), device) == 0
+
+
+def render_shot_png(scene, config: Config, path: str, shot: Optional[abi.Shot] = None, ground: Optional[float] = None, device: int = 0) -> bool:
+    """``TileRenderer.renderShot`` + ``ImageWriter.writePNG8`` in one call (mcrt_render_shot_png): the finished studio shot as
+    a PNG, 4 B/pixel copied back.  ``ground=None``: the scene's floor.  False on failure, like ``render_png``."""
+    s = (shot if shot is not None else abi.Shot()).to_c()
+    d = _as_desc(scene)
+    g = _ground_heights([d], ground)[0]
+    c = config.to_c()
+    return load().mcrt_render_shot_png(d.ptr, C.byref(c), C.byref(s), g, os.fsencode(path), int(device)) == 0
+
+
+def shot_scratch_bytes(config: Config, shot: Optional[abi.Shot] = None, n_frames: int = 1) -> int:
+    """Bytes of device scratch ``render_shot_batch_device`` / ``DeviceScene.render_shot_device`` need for ``n_frames`` frames
+    (mcrt_shot_scratch_bytes; host only): 16 per pixel, + 16 with a reflection, + 4 with a shadow, + 4 with a fading
+    reflection, every plane on a 16-byte boundary.  0 for a zero-size frame or ``n_frames <= 0``."""
+    s = (shot if shot is not None else abi.Shot()).to_c()
+    c = config.to_c()
+    return int(load().mcrt_shot_scratch_bytes(C.byref(c), C.byref(s), int(n_frames)))
 
 
 SKIN_HEIGHTS = {"S64": 64, "S32": 32, 64: 64, 32: 32}
@@ -832,6 +882,20 @@ class DeviceScene:
         planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
         check(load().mcrt_render_reflection_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
 
+    def render_shot_device(self, config: Config, shot: Optional[abi.Shot], ground: float, scratch_ptr: int, scratch_bytes: int,
+                           out_f32_ptr: int = 0, out_rgba8_ptr: int = 0, stream: int = 0) -> None:
+        """The studio shot of the frame into device memory (mcrt_render_shot_device): render, ground pass, reflection pass and
+        blend, in order on ``stream``, the intermediate planes in the caller's scratch (``shot_scratch_bytes`` bytes, 16-byte
+        aligned).  The figure is rendered transparent whatever ``set_background`` says; the handle's mode is untouched."""
+        if not out_f32_ptr and not out_rgba8_ptr:
+            raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
+        if not np.isfinite(np.float32(ground)):
+            raise ValueError("ground must be finite")
+        s = (shot if shot is not None else abi.Shot()).to_c()
+        c = config.to_c()
+        check(load().mcrt_render_shot_device(self._h, C.byref(c), C.byref(s), float(ground), C.c_void_p(scratch_ptr or None), int(scratch_bytes),
+                                             C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), C.c_void_p(stream)))
+
     def render_light_device(self, config: Config, visibility_ptr: int = 0, occlusion_ptr: int = 0, direct_ptr: int = 0, stream: int = 0) -> None:
         """The light planes of the frame into device memory (mcrt_render_light_device): width * height pixels per plane —
         visibility and occlusion 4 bytes per pixel, direct 16 — any pointer may be 0, not all.  Asynchronous on ``stream``; uses
@@ -990,6 +1054,70 @@ def render_reflection_batch_device(device_scenes: Sequence["DeviceScene"], confi
     c = config.to_c()
     planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
     check(load().mcrt_render_reflection_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+
+
+def _shot_handles(device_scenes) -> list:
+    handles = []
+    for s in device_scenes:
+        if not isinstance(s, DeviceScene):
+            raise TypeError("device_scenes must be DeviceScene objects")
+        handles.append(s._h)
+    return handles
+
+
+def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, shot: Optional[abi.Shot], ground, scratch_ptr: int,
+                             scratch_bytes: int, out_f32_ptr: int = 0, out_rgba8_ptr: int = 0, frame_stride_pixels: Optional[int] = None,
+                             stream: int = 0) -> None:
+    """The studio shots of N resident scenes of one config (mcrt_render_shot_batch_device): one batched render, one ground and
+    one reflection launch and one blend, in order on ``stream``; frame i lands ``i * frame_stride_pixels`` pixels on (default
+    width * height) in ``out_f32_ptr`` (16 B/pixel) and / or ``out_rgba8_ptr`` (4 B/pixel).  ``ground``: one height for all, or
+    N heights.  ``scratch_ptr``: device memory, 16-byte aligned, ``shot_scratch_bytes(config, shot, N)`` bytes."""
+    handles = _shot_handles(device_scenes)
+    if not out_f32_ptr and not out_rgba8_ptr:
+        raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
+    if ground is None:
+        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
+    heights = _ground_heights(handles, ground)
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
+    if stride < px:
+        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
+    s = (shot if shot is not None else abi.Shot()).to_c()
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    gy = (C.c_float * max(n, 1))(*heights)
+    c = config.to_c()
+    check(load().mcrt_render_shot_batch_device(arr, n, C.byref(c), C.byref(s), gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
+                                               C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride, C.c_void_p(stream)))
+
+
+def composite_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, shot: Optional[abi.Shot], figure_ptr: int,
+                                visibility_ptr: int = 0, reflection_ptr: int = 0, reflection_distance_ptr: int = 0, out_f32_ptr: int = 0,
+                                out_rgba8_ptr: int = 0, in_stride_pixels: Optional[int] = None, out_stride_pixels: Optional[int] = None,
+                                stream: int = 0) -> None:
+    """The studio shot's blend alone, on device planes the caller already has (mcrt_composite_shot_batch_device): the
+    transparent figure (required, 16 B/pixel), the ground pass's visibility (0: none, no shadow), the reflection pass's rgba
+    (0: no mirror image) and distance (0 only with ``shot.reflectionFade == 0``).  Frame i of the inputs starts
+    ``i * in_stride_pixels`` pixels on, of the outputs ``i * out_stride_pixels`` (default width * height)."""
+    handles = _shot_handles(device_scenes)
+    if not figure_ptr:
+        raise ValueError("figure_ptr is required")
+    if not out_f32_ptr and not out_rgba8_ptr:
+        raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
+    px = max(config.width, 0) * max(config.height, 0)
+    strides = []
+    for name, value in (("in_stride_pixels", in_stride_pixels), ("out_stride_pixels", out_stride_pixels)):
+        stride = px if value is None else int(value)
+        if stride < px:
+            raise ValueError(f"{name} {stride} is smaller than width * height = {px}")
+        strides.append(stride)
+    s = (shot if shot is not None else abi.Shot()).to_c()
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    c = config.to_c()
+    planes = abi.McrtShotInputs(figure_ptr, visibility_ptr or None, reflection_ptr or None, reflection_distance_ptr or None)
+    check(load().mcrt_composite_shot_batch_device(arr, n, C.byref(c), C.byref(s), C.byref(planes), strides[0], C.c_void_p(out_f32_ptr or None),
+                                                  C.c_void_p(out_rgba8_ptr or None), strides[1], C.c_void_p(stream)))
 
 
 def render_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, visibility_ptr: int = 0, occlusion_ptr: int = 0,
@@ -1194,6 +1322,42 @@ class SkinBatch:
             with torch.cuda.stream(stream):
                 host[:m].copy_(dev[:m], non_blocking=True)
             stream.synchronize()
+            return host[:m].numpy().copy()
+
+    def shots(self, skins, config: Config, shot: Optional[abi.Shot] = None, ground=0.0, rgba8: bool = True) -> np.ndarray:
+        """The studio shots of the ``m`` skins (``TileRenderer.renderShotBatch`` of the scenes built per skin, bit for bit): one
+        upload, one repaint, one ``render_shot_batch_device`` call — render, ground, reflection and blend on the device — and
+        one download of 4 B/pixel (16 with ``rgba8=False``).  ``ground``: one height for all (0.0: the soles of the builder's
+        standing figure), or ``m`` heights.  The scenes' background mode (``render``'s) is not touched."""
+        torch = self._torch
+        w, h = max(config.width, 0), max(config.height, 0)
+        np_dtype = np.uint8 if rgba8 else np.float32
+        with torch.cuda.device(self._dev):
+            stream = torch.cuda.current_stream()
+            if w == 0 or h == 0 or config.tileSize <= 0:  # no frame: nothing is painted either
+                out = np.zeros((len(self._check_skins(skins)), h, w, 4), np_dtype)
+                out[..., 3] = 255 if rgba8 else 1.0
+                return out
+            a = self._check_skins(skins)
+            if ground is None:
+                raise ValueError("ground heights are needed: a resident scene does not keep its description")
+            heights = _ground_heights(list(range(len(a))), ground)
+            need = shot_scratch_bytes(config, shot, len(self.scenes))  # (raises nothing: an invalid shot is refused by the call below)
+            m = self._paint(a, stream)
+            if m == 0:
+                return np.zeros((0, h, w, 4), np_dtype)
+            scratch = self._out.get("shot_scratch")
+            if scratch is None or scratch.numel() < need:
+                scratch = torch.empty((max(need, 16),), dtype=torch.uint8, device=self._dev)
+                self._out["shot_scratch"] = scratch
+            dev, host = self._buffers("shots", (len(self.scenes), h, w, 4), torch.uint8 if rgba8 else torch.float32)
+            try:
+                render_shot_batch_device(self.scenes[:m], config, shot, heights, scratch.data_ptr(), scratch.numel(), 0 if rgba8 else dev.data_ptr(),
+                                         dev.data_ptr() if rgba8 else 0, w * h, stream.cuda_stream)
+                with torch.cuda.stream(stream):
+                    host[:m].copy_(dev[:m], non_blocking=True)
+            finally:
+                stream.synchronize()  # (a refused shot too: the repaint reads the pinned staging buffer)
             return host[:m].numpy().copy()
 
     def layers(self, skins, config: Config, layers=abi.LAYER_NAMES) -> dict:

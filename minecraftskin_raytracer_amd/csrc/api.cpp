@@ -927,6 +927,81 @@ int mcrt_render_reflection(const mcrt_scene_desc* desc, const mcrt_config* cfg, 
     return rc;
 }
 
+// ---- studio shot: defaults, the scratch size and the one-shot host forms (render_enqueue.cpp: render_shot_batch_device) ----------
+void mcrt_shot_init(mcrt_shot* shot) {
+    if (!shot) return;
+    shot->page = MCRT_PAGE_REFERENCE;
+    shot->page_color[0] = shot->page_color[1] = shot->page_color[2] = 1.0f;
+    shot->shadow_strength = 0.6f;
+    shot->reflectivity = 0.35f;
+    shot->reflection_fade = 0.0f;
+}
+
+size_t mcrt_shot_scratch_bytes(const mcrt_config* cfg, const mcrt_shot* shot, int n_frames) {
+    if (!cfg || !shot || n_frames <= 0 || !valid_frame(cfg) || shot_frame_too_large(cfg)) return 0;
+    if (check_shot(shot) != MCRT_OK) return 0;
+    return shot_scratch(cfg, shot, n_frames).bytes;
+}
+
+int mcrt_render_shot_batch(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y,
+                           float* out_rgba, uint8_t* out_rgba8, int device) {
+    // the device form's checks that need no handle, before anything is created
+    if (n_frames < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !shot || (n_frames > 0 && (!descs || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n_frames; ++i)
+        if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
+    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    for (int i = 0; i < n_frames; ++i)
+        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (!out_rgba && !out_rgba8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
+    if (const int rc = check_shot_config(cfg, shot); rc != MCRT_OK) return rc;
+    if (n_frames == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
+    OneShotScenes set;
+    int rc = set.create(descs, n_frames, device, MCRT_BACKGROUND_REFERENCE);
+    if (rc != MCRT_OK) return rc;
+    mcrt_scene* s0 = set.h[0];
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    // the scratch (a multiple of 16 bytes), then the outputs, widest elements first
+    const size_t scratch_bytes = shot_scratch(cfg, shot, n_frames).bytes;
+    const size_t f32_bytes = out_rgba ? px * 16 * static_cast<size_t>(n_frames) : 0;
+    const size_t u8_bytes = out_rgba8 ? px * 4 * static_cast<size_t>(n_frames) : 0;
+    hipError_t e = s0->frame.reserve(scratch_bytes + f32_bytes + u8_bytes);
+    if (e != hipSuccess) return hip_fail(e, "shot planes");
+    char* base = static_cast<char*>(s0->frame.ptr);
+    float* d_f32 = out_rgba ? reinterpret_cast<float*>(base + scratch_bytes) : nullptr;
+    uint8_t* d_u8 = out_rgba8 ? reinterpret_cast<uint8_t*>(base + scratch_bytes + f32_bytes) : nullptr;
+    rc = render_shot_batch_device(set.h.data(), n_frames, cfg, shot, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream);
+    set.download(out_rgba, d_f32, f32_bytes, rc);
+    set.download(out_rgba8, d_u8, u8_bytes, rc);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "shot render");
+    }
+    for (int i = 0; i < n_frames && rc == MCRT_OK; ++i) rc = mcrt_scene_check(set.h[static_cast<size_t>(i)]);
+    return rc;
+}
+
+int mcrt_render_shot(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, float* out_rgba, uint8_t* out_rgba8,
+                     int device) {
+    if (!desc) return fail(MCRT_ERR_INVALID, "NULL argument");
+    const mcrt_scene_desc* one[1] = {desc};
+    return mcrt_render_shot_batch(one, 1, cfg, shot, &ground_y, out_rgba, out_rgba8, device);
+}
+
+int mcrt_render_shot_png(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, const char* path, int device) {
+    if (!desc || !cfg || !shot || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (const int rc = check_shot_config(cfg, shot); rc != MCRT_OK) return rc;
+    if (!valid_frame(cfg)) return fail(MCRT_ERR_INVALID, "empty image");
+    if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
+    std::vector<uint8_t> host(static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) * 4);
+    const int rc = mcrt_render_shot(desc, cfg, shot, ground_y, nullptr, host.data(), device);
+    if (rc != MCRT_OK) return rc;
+    return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
+}
+
 // ---- light layers: the one-shot host form (render_enqueue.cpp: render_light_batch_device) ----------------------------------------
 int mcrt_render_light(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_light_planes* out, int device) {
     if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");

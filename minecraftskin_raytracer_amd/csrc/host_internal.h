@@ -227,6 +227,48 @@ inline int check_bake_config(const mcrt_config* c, int grid, const mcrt_bake_pla
     return MCRT_OK;
 }
 
+// what every studio-shot entry point refuses of the shot itself (before any device work)
+inline int check_shot(const mcrt_shot* s) {
+    if (s->page != MCRT_PAGE_COLOR && s->page != MCRT_PAGE_REFERENCE) return fail(MCRT_ERR_INVALID, "page must be MCRT_PAGE_COLOR or MCRT_PAGE_REFERENCE");
+    if (!(s->shadow_strength >= 0.0f && s->shadow_strength <= 1.0f)) return fail(MCRT_ERR_INVALID, "shadow_strength must lie in [0, 1]");
+    if (!(s->reflectivity >= 0.0f && s->reflectivity <= 1.0f)) return fail(MCRT_ERR_INVALID, "reflectivity must lie in [0, 1]");
+    if (!(s->reflection_fade >= 0.0f) || !std::isfinite(s->reflection_fade)) return fail(MCRT_ERR_INVALID, "reflection_fade must be finite and >= 0");
+    for (const float c : s->page_color)
+        if (!std::isfinite(c)) return fail(MCRT_ERR_INVALID, "page_color must be finite");
+    return MCRT_OK;
+}
+// and of the config of a shot that renders: the render's limit, and the limits of the passes the shot runs
+int validate_config(const mcrt_config* cfg);
+inline int check_shot_config(const mcrt_config* c, const mcrt_shot* s) {
+    if (validate_config(c) != MCRT_OK) return MCRT_ERR_INVALID;
+    const bool ground = s->shadow_strength > 0.0f, mirror = s->reflectivity > 0.0f;
+    if ((ground || mirror) && c->soft_shadows && c->shadow_samples > mcrt::kGroundMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a shot with a shadow or a reflection takes at most 113 shadow samples (the truncated engine's 227 draws)");
+    if (mirror && c->max_bounces > mcrt::kReflectMaxBounces)
+        return fail(MCRT_ERR_INVALID, "a shot with a reflection takes at most 8 bounces (the reflection pass's per-lane colour stack)");
+    return MCRT_OK;
+}
+inline bool shot_frame_too_large(const mcrt_config* c) { return static_cast<long long>(c->width) * c->height >= (1ll << 31); }
+// The scratch of a shot that renders (include/mcrt.h): the planes it needs, each for n frames and each on a 16-byte boundary.
+// Offsets of the absent planes are SIZE_MAX.
+struct ShotScratch {
+    size_t figure = 0, reflection = SIZE_MAX, visibility = SIZE_MAX, distance = SIZE_MAX, bytes = 0;
+};
+inline ShotScratch shot_scratch(const mcrt_config* c, const mcrt_shot* s, int n) {
+    ShotScratch l;
+    const size_t px = static_cast<size_t>(c->width) * static_cast<size_t>(c->height) * static_cast<size_t>(n);
+    auto place = [&](size_t px_bytes) {
+        const size_t at = l.bytes;
+        l.bytes += (px * px_bytes + 15) & ~static_cast<size_t>(15);
+        return at;
+    };
+    l.figure = place(16);
+    if (s->reflectivity > 0.0f) l.reflection = place(16);
+    if (s->shadow_strength > 0.0f) l.visibility = place(4);
+    if (s->reflectivity > 0.0f && s->reflection_fade > 0.0f) l.distance = place(4);
+    return l;
+}
+
 // what the calling thread's last mcrt_render_batch* call did (mcrt_last_batch_info; thread-local in api.cpp, like the error text)
 struct BatchInfo {
     int frames = 0, sequences = 0;
@@ -294,6 +336,12 @@ int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_
                                    size_t stride, hipStream_t stream);
 int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes* d_out, size_t stride, hipStream_t stream);
 int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream);
+// the studio shot's blend on the caller's planes (mcrt_composite_shot_batch_device), and render + ground + reflection + blend on
+// `stream` in order with the planes in the caller's scratch (mcrt_render_shot_batch_device)
+int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in, size_t in_stride,
+                                float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream);
+int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y, void* d_scratch,
+                             size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 // gives the n repaintable handles the views (poses[i], looks[i]); NULL poses, looks or looks[i]: the handle's own

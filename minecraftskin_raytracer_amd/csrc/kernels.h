@@ -434,6 +434,27 @@ struct SceneViewFrame {
     const uint8_t* table;  // the staged prefix in device memory, 16-byte aligned
 };
 
+// ---- studio shot (mcrt_composite_shot_batch_device & co): the blend of include/mcrt.h — the straight-alpha figure over a page
+// with the ground shadow and the floor reflection — per pixel, from planes that are already on the device.  Of the scene it
+// reads the header's background colour alone, and only for MCRT_PAGE_REFERENCE without a gradient.
+// One frame of a shot: its inputs (all but the figure may be NULL) and its outputs (either may be NULL, not both)
+struct ShotFrame {
+    const uint8_t* scene;
+    const float* figure;      // 4 floats per pixel: the MCRT_BACKGROUND_TRANSPARENT frame, straight alpha
+    const float* visibility;  // 1 float per pixel: the ground pass's; NULL: 1.0f everywhere
+    const float* reflection;  // 4 floats per pixel: the reflection pass's rgba; NULL: (0, 0, 0, 0) everywhere
+    const float* distance;    // 1 float per pixel: the reflection pass's; read only with reflection_fade > 0
+    float* out;               // 4 floats per pixel
+    uint8_t* out8;            // RGBA8, quantised as mcrt_quantize_rgba8 quantises it
+};
+// what the frames of one launch share: the frame's size and gradient (cfg) and the shot's settings
+struct ShotShape {
+    mcrt_config cfg;
+    int page;  // MCRT_PAGE_*
+    float page_color[3];
+    float shadow_strength, reflectivity, reflection_fade;
+};
+
 // ======== pipeline launches (render_kernels.hip) ========
 // seeds p.tile_rng: one mt19937 per owned tile (tile_renderer.cpp:78).  A function of the frame width, the
 // tile size and the shard only — the caller keeps the result across renders and calls this when those change.
@@ -461,7 +482,7 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
-// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, light bake, skin repaints, views ========
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, light bake, studio shot, skin repaints, views ========
 hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's LDS tables
@@ -489,6 +510,9 @@ hipError_t launch_bake(const BakeFrame& f, const BakeShape& shape, int view, hip
 // frames of a call share their planes) and the largest frame's bake_shade_lds_bytes / bake_occlusion_lds_bytes
 hipError_t launch_bake_batch(const BakeFrame* d_table, int n_frames, const BakeShape& shape, int view, bool shade, size_t shade_dyn, bool occlusion,
                              size_t occlusion_dyn, hipStream_t stream);
+hipError_t launch_shot(const ShotFrame& f, const ShotShape& shape, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
+hipError_t launch_shot_batch(const ShotFrame* d_table, int n_frames, const ShotShape& shape, hipStream_t stream);
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);

@@ -1572,6 +1572,90 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void bake_occlusion_batch_ker
     bake_occlusion_body<kView>(*(const BakeFrame*)(table + blockIdx.y), sh);
 }
 
+// ---------------------------------------------------------------------------------------------
+// studio shot (kernels.h: ShotFrame): the blend of include/mcrt.h, "studio shot" — the straight-alpha figure over a page that
+// carries the ground shadow and the floor reflection — as one streaming pass.  No scene geometry, no LDS, no atomics:
+//   1 lane / pixel (grid-stride over the frame's pixels, blockIdx.y = frame)
+//     figure and reflection rgba   one 16-byte load each where the plane is 16-byte aligned, else four 4-byte loads
+//     visibility and distance      one 4-byte load each: 256 contiguous bytes per wave (the planes have pixel granularity)
+//     page                         the constant, or rt::background at the pixel centre — u, v by IEEE division
+//     out                          one 16-byte store (four 4-byte ones for a plane off a 16-byte boundary) and / or 4 bytes
+//                                  of RGBA8 (byte stores for a plane off a 4-byte boundary)
+// At most 40 B read and 20 B written per pixel.  The arithmetic is the header's, in its order, one rounding per operation; an
+// absent input enters with its miss constant (visibility 1, reflection (0,0,0,0)) through the same operations, which is why a
+// shot that skips a pass equals one that ran it.
+// ---------------------------------------------------------------------------------------------
+struct ShotPage {  // what rt::background reads of a scene view
+    const FlatHeader* hdr;
+};
+__device__ __forceinline__ float4 load_rgba(const float* __restrict__ plane, const size_t i, const bool aligned) {
+    if (aligned) return reinterpret_cast<const float4*>(plane)[i];
+    const float* p = plane + 4 * i;
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+__device__ __forceinline__ void shot_body(const ShotFrame& __restrict__ f, const ShotShape& __restrict__ sh) {
+    const mcrt_config& cfg = sh.cfg;
+    const unsigned width = static_cast<unsigned>(cfg.width);
+    const unsigned n_pixels = width * static_cast<unsigned>(cfg.height);  // (the host refuses frames of 2^31 pixels and more)
+    const bool fig16 = (reinterpret_cast<uintptr_t>(f.figure) & 15u) == 0;
+    const bool ref16 = (reinterpret_cast<uintptr_t>(f.reflection) & 15u) == 0;
+    const bool out16 = (reinterpret_cast<uintptr_t>(f.out) & 15u) == 0;
+    const bool out8_4 = (reinterpret_cast<uintptr_t>(f.out8) & 3u) == 0;
+    const bool page_reference = sh.page == MCRT_PAGE_REFERENCE;
+    const ShotPage scene{reinterpret_cast<const FlatHeader*>(f.scene)};
+    const UDiv by_width(width);
+    const float s = sh.shadow_strength, k = sh.reflectivity, fade = sh.reflection_fade;
+    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n_pixels; i += gridDim.x * kBlock) {
+        const float4 F = load_rgba(f.figure, i, fig16);
+        const float vis = f.visibility ? f.visibility[i] : 1.0f;
+        const float4 R = f.reflection ? load_rgba(f.reflection, i, ref16) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float pr = sh.page_color[0], pg = sh.page_color[1], pb = sh.page_color[2];
+        if (page_reference) {
+            const unsigned py = by_width.div(i), px = i - py * width;
+            const float u = (static_cast<float>(px) + 0.5f) / static_cast<float>(cfg.width);
+            const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
+            const C4 c = background(scene, cfg, u, v);
+            pr = c.r, pg = c.g, pb = c.b;
+        }
+        const float shade = s * (1.0f - vis);
+        float fd = 1.0f;
+        if (fade > 0.0f) {
+            const float dR = (f.reflection && f.distance) ? f.distance[i] : kFltMax;
+            fd = sclamp(1.0f - dR / fade, 0.0f, 1.0f);
+        }
+        const float ar = (k * R.w) * fd;
+        const float keep = (1.0f - shade) * (1.0f - ar);
+        const float under = 1.0f - F.w;
+        float4 o;
+        o.x = F.x * F.w + (pr * keep + R.x * ar) * under;
+        o.y = F.y * F.w + (pg * keep + R.y * ar) * under;
+        o.z = F.z * F.w + (pb * keep + R.z * ar) * under;
+        o.w = 1.0f;
+        if (f.out) {
+            if (out16) {
+                reinterpret_cast<float4*>(f.out)[i] = o;
+            } else {
+                float* p = f.out + 4 * static_cast<size_t>(i);
+                p[0] = o.x, p[1] = o.y, p[2] = o.z, p[3] = o.w;
+            }
+        }
+        if (f.out8) {
+            const uchar4 q = quantize_pixel(o);
+            if (out8_4) {
+                reinterpret_cast<uchar4*>(f.out8)[i] = q;
+            } else {
+                uint8_t* p = f.out8 + 4 * static_cast<size_t>(i);
+                p[0] = q.x, p[1] = q.y, p[2] = q.z, p[3] = q.w;
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(kBlock) void shot_kernel(const ShotFrame f, const ShotShape sh) { shot_body(f, sh); }
+using ShotTable = const __attribute__((address_space(4))) ShotFrame*;
+__global__ __launch_bounds__(kBlock) void shot_batch_kernel(ShotTable table, const ShotShape sh) {
+    shot_body(*(const ShotFrame*)(table + blockIdx.y), sh);
+}
+
 // ---- host-side launchers (the shapes and LDS sizes they take: render_plan.cpp) ----------------------
 // One launch of a tile pass (layers, ground) over the tile grid `tiles`.  arg: the frame, or the device table of n_frames
 // frames (blockIdx.y = frame); kernel_of(view tag): the kernel of that variant; dyn: its dynamic LDS, hbm_dyn: the HBM
@@ -1679,6 +1763,26 @@ hipError_t launch_bake_batch(const BakeFrame* d_table, int n_frames, const BakeS
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(pick_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, scene, shape, d_xy, n, d_out);
+    return hipGetLastError();
+}
+// ---- studio shot (kernels.h): a workgroup per 256 pixels, at most kLayersGrid per frame (the kernel strides) ----------------
+static unsigned shot_grid(const ShotShape& sh) {
+    const long long px = static_cast<long long>(sh.cfg.width) * sh.cfg.height;
+    const long long groups = (px + kBlock - 1) / kBlock;
+    return static_cast<unsigned>(groups < kLayersGrid ? groups : kLayersGrid);
+}
+static bool shot_shape_ok(const ShotShape& sh) {
+    return sh.cfg.width > 0 && sh.cfg.height > 0 && static_cast<long long>(sh.cfg.width) * sh.cfg.height < (1ll << 31);
+}
+hipError_t launch_shot(const ShotFrame& f, const ShotShape& shape, hipStream_t stream) {
+    if (!shot_shape_ok(shape) || !f.figure || (!f.out && !f.out8)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shot_kernel, dim3(shot_grid(shape)), dim3(kBlock), 0, stream, f, shape);
+    return hipGetLastError();
+}
+hipError_t launch_shot_batch(const ShotFrame* d_table, int n_frames, const ShotShape& shape, hipStream_t stream) {
+    if (n_frames <= 0) return hipSuccess;
+    if (!shot_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shot_batch_kernel, dim3(shot_grid(shape), static_cast<unsigned>(n_frames)), dim3(kBlock), 0, stream, ShotTable(d_table), shape);
     return hipGetLastError();
 }
 // ---- skins on resident scenes (kernels.h) -----------------------------------------------------------

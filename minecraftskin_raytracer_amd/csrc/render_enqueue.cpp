@@ -11,6 +11,17 @@ using namespace mcrt_host;
 
 namespace {
 
+// The background mode of the renders the calling thread prepares while a BackgroundOverride lives, instead of each handle's
+// own (mcrt_scene::background, which is never written here): a studio shot renders its figures transparent whatever the
+// handles are set to, and no other thread sees a handle in another mode meanwhile.  -1: none.
+thread_local int t_background_override = -1;
+struct BackgroundOverride {
+    explicit BackgroundOverride(int mode) { t_background_override = mode; }
+    ~BackgroundOverride() { t_background_override = -1; }
+    BackgroundOverride(const BackgroundOverride&) = delete;
+    BackgroundOverride& operator=(const BackgroundOverride&) = delete;
+};
+
 int draws_per_sample(const mcrt_config& c) {
     int spp = c.samples_per_pixel > 1 ? c.samples_per_pixel : 1;
     return (spp > 1 ? 2 : 0) + ((c.dof_enabled && c.aperture > 1e-6f) ? 2 : 0);
@@ -129,7 +140,7 @@ int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int fir
     p.layout = layout;
     p.out = d_out;
     p.out8 = d_out8;
-    p.background = rect ? MCRT_BACKGROUND_REFERENCE : sc->background;  // (plan_workspace picks the draws layout by it)
+    p.background = rect ? MCRT_BACKGROUND_REFERENCE : (t_background_override >= 0 ? t_background_override : sc->background);  // (plan_workspace picks the draws layout by it)
     p.draws_per_sample = draws_per_sample(*cfg);
     const LdsFit fit = lds_fit(sc->alpha_words, sc->n_meshes, sc->posed);
     p.scene_in_lds = fit.view != kViewHbm ? 1 : 0;
@@ -1039,6 +1050,123 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
     return rc;
 }
 
+// ---- studio shot (mcrt_composite_shot_batch_device & co): the blend is a pass like the ground pass — frame records through
+// launch_pass, none of the handles' events — over planes instead of a scene; of a handle it takes the blob's address (the
+// header's background colour, read on the device) and the device index
+namespace {
+// the launches of the blend, behind every check: frame i of the inputs in_stride pixels on, of the outputs out_stride pixels on
+int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs& in, size_t in_stride,
+                       float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
+    ShotShape shape;
+    std::memset(&shape, 0, sizeof shape);
+    shape.cfg = *cfg;
+    shape.page = shot->page;
+    std::memcpy(shape.page_color, shot->page_color, sizeof shape.page_color);
+    shape.shadow_strength = shot->shadow_strength, shape.reflectivity = shot->reflectivity, shape.reflection_fade = shot->reflection_fade;
+    std::vector<ShotFrame> frames(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        ShotFrame& f = frames[static_cast<size_t>(i)];
+        std::memset(&f, 0, sizeof f);
+        const size_t from = static_cast<size_t>(i) * in_stride, to = static_cast<size_t>(i) * out_stride;
+        f.scene = static_cast<const uint8_t*>(scenes[i]->blob.ptr);
+        f.figure = in.figure + from * 4;
+        f.visibility = in.visibility ? in.visibility + from : nullptr;
+        f.reflection = in.reflection ? in.reflection + from * 4 : nullptr;
+        f.distance = in.reflection_distance ? in.reflection_distance + from : nullptr;
+        f.out = d_f32 ? d_f32 + to * 4 : nullptr;
+        f.out8 = d_u8 ? d_u8 + to * 4 : nullptr;
+    }
+    return launch_pass(
+        device, frames, stream, "shot launches", [&](const ShotFrame& f) { return launch_shot(f, shape, stream); },
+        [&](const ShotFrame* d_table, int m) { return launch_shot_batch(d_table, m, shape, stream); });
+}
+}  // namespace
+
+int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in, size_t in_stride,
+                                float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
+    // argument checks, before any device work (only the last one looks inside the handles, at their device index)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !shot || !d_in || !d_in->figure || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (shot->reflection_fade > 0.0f && !d_in->reflection_distance)
+        return fail(MCRT_ERR_INVALID, "reflection_distance may be NULL only with reflection_fade == 0");
+    if (!d_f32 && !d_u8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
+    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    if (in_stride < px) return fail(MCRT_ERR_INVALID, "in_stride_pixels is smaller than width * height");
+    if (out_stride < px) return fail(MCRT_ERR_INVALID, "out_stride_pixels is smaller than width * height");
+    const int device = scenes[0]->device;
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    HIP_TRY(hipSetDevice(device));
+    if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a shot cannot be recorded into a caller's graph");
+    (void)hipGetLastError();
+    return launch_shot_frames(scenes, n, device, cfg, shot, *d_in, in_stride, d_f32, d_u8, out_stride, stream);
+}
+
+// Render + ground + reflection + blend, all on `stream` in order.  The render goes through render_batch_device (the handles'
+// event chains, batched kernels where the frames fit them) under the transparent override; the passes and the blend follow it
+// in stream order and take no events.  Nothing is forked beside the render.
+int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y, void* d_scratch,
+                             size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream) {
+    // argument checks, before any device work (only the last ones look inside the handles, at their device index)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !shot || (n > 0 && (!scenes || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (!d_f32 && !d_u8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
+    {
+        std::vector<mcrt_scene*> sorted(scenes, scenes + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (each handle owns one workspace: one frame in flight)");
+    }
+    if (const int rc = check_shot_config(cfg, shot); rc != MCRT_OK) return rc;
+    if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    if (stride < px) return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
+    const ShotScratch at = shot_scratch(cfg, shot, n);
+    if (!d_scratch) return fail(MCRT_ERR_INVALID, "d_scratch is NULL");
+    if ((reinterpret_cast<uintptr_t>(d_scratch) & 15u) != 0) return fail(MCRT_ERR_INVALID, "d_scratch is not 16-byte aligned");
+    if (scratch_bytes < at.bytes) return fail(MCRT_ERR_INVALID, "scratch_bytes is smaller than mcrt_shot_scratch_bytes");
+    const int device = scenes[0]->device;
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    HIP_TRY(hipSetDevice(device));
+    if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a shot cannot be recorded into a caller's graph");
+    (void)hipGetLastError();
+    char* base = static_cast<char*>(d_scratch);
+    auto plane = [&](size_t offset) { return offset == SIZE_MAX ? nullptr : reinterpret_cast<float*>(base + offset); };
+    mcrt_shot_inputs in{};
+    in.figure = plane(at.figure);
+    in.visibility = plane(at.visibility);
+    in.reflection = plane(at.reflection);
+    in.reflection_distance = plane(at.distance);
+    {
+        const BackgroundOverride transparent(MCRT_BACKGROUND_TRANSPARENT);
+        if (const int rc = render_batch_device(scenes, n, cfg, plane(at.figure), nullptr, px, stream); rc != MCRT_OK) return rc;
+    }
+    if (in.visibility) {
+        mcrt_ground g{};
+        g.visibility = plane(at.visibility);
+        if (const int rc = render_ground_batch_device(scenes, n, cfg, ground_y, &g, px, stream); rc != MCRT_OK) return rc;
+    }
+    if (in.reflection) {
+        mcrt_reflection r{};
+        r.rgba = plane(at.reflection);
+        r.distance = plane(at.distance);
+        if (const int rc = render_reflection_batch_device(scenes, n, cfg, ground_y, &r, px, stream); rc != MCRT_OK) return rc;
+    }
+    return launch_shot_frames(scenes, n, device, cfg, shot, in, px, d_f32, d_u8, stride, stream);
+}
+
 }  // namespace mcrt_host
 
 extern "C" {
@@ -1188,6 +1316,26 @@ int mcrt_render_reflection_device(mcrt_scene* s, const mcrt_config* cfg, float g
 int mcrt_render_reflection_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y,
                                         const mcrt_reflection* d_out, size_t frame_stride_pixels, void* stream) {
     return render_reflection_batch_device(scenes, n_frames, cfg, ground_y, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_composite_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
+                                     size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8, size_t out_stride_pixels, void* stream) {
+    return composite_shot_batch_device(scenes, n_frames, cfg, shot, d_in, in_stride_pixels, d_out_f32, d_out_rgba8, out_stride_pixels,
+                                       static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y, void* d_scratch,
+                                  size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8, size_t frame_stride_pixels, void* stream) {
+    return render_shot_batch_device(scenes, n_frames, cfg, shot, ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, frame_stride_pixels,
+                                    static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_shot_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, void* d_scratch, size_t scratch_bytes,
+                            float* d_out_f32, uint8_t* d_out_rgba8, void* stream) {
+    if (!s || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = valid_frame(cfg) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
+    return render_shot_batch_device(one, 1, cfg, shot, &ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, px, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_light_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_light_planes* d_out, void* stream) {

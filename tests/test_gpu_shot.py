@@ -1,0 +1,405 @@
+"""The studio shot on the GPU (mcrt_composite_shot_batch_device, mcrt_render_shot*): the blend kernel alone on synthetic planes,
+bit for bit against tests/shot_checker.py's ``compose``; whole shots against the CPU oracle alone (transparent checker, ground
+checker, reflection checker, the oracle's background); shots against the library's own four calls plus ``compose`` — a batch of
+five posed scenes with depth of field and ambient occlusion, and a 1920 x 1080 frame; the shots that skip a pass; the handle's
+background mode; stream order behind a repaint and a view change; ``SkinBatch.shots``; the PNG.
+
+So that a page-only or figure-only image cannot pass, each oracle case asserts what its expectation holds, by pixel class
+(``shot_checker.classes``): at least 400 opaque figure pixels, 50 edge pixels, 100 shadowed and 50 penumbra pixels beside the
+figure and 50 mirrored pixels beside it — the 33 x 17 case its exact counts."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import layers_checker as L  # noqa: E402
+import scenes  # noqa: E402
+import shot_checker as S  # noqa: E402
+import skin_paint_checker as P  # noqa: E402
+from minecraftskin_raytracer_amd import abi  # noqa: E402
+
+gpu_test = pytest.mark.gpu
+f32 = np.float32
+SENTINEL = -12345.0
+BYTE_SENTINEL = 77
+FLOORS = (400, 50, 100, 50, 50)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _dev(a):
+    return torch.from_numpy(np.array(a)).cuda()  # (a copy: the suite's skins are read-only)
+
+
+def _scratch(mcrt, cfg, shot, n):
+    need = mcrt.shot_scratch_bytes(cfg, shot, n)
+    return torch.full((need + 64,), BYTE_SENTINEL, dtype=torch.uint8, device="cuda"), need
+
+
+def _shoot(mcrt, handles, cfg, shot, heights, stride=None, stream=None):
+    """render_shot_batch_device into sentinel-filled buffers → (f32 (n, H, W, 4), u8 (n, H, W, 4)); checks the gaps between the
+    frames and the bytes behind the scratch."""
+    n, px = len(handles), cfg.width * cfg.height
+    stride = px if stride is None else stride
+    out = torch.full((n * stride * 4,), SENTINEL, dtype=torch.float32, device="cuda")
+    out8 = torch.full((n * stride * 4,), BYTE_SENTINEL, dtype=torch.uint8, device="cuda")
+    scratch, need = _scratch(mcrt, cfg, shot, n)
+    mcrt.render_shot_batch_device(handles, cfg, shot, heights, scratch.data_ptr(), need, out.data_ptr(), out8.data_ptr(), stride,
+                                  stream if stream is not None else _stream())
+    torch.cuda.synchronize()
+    assert bool((scratch[need:] == BYTE_SENTINEL).all().item()), "written behind the scratch"
+    a, b = out.cpu().numpy().reshape(n, stride * 4), out8.cpu().numpy().reshape(n, stride * 4)
+    assert (a[:, px * 4:] == SENTINEL).all() and (b[:, px * 4:] == BYTE_SENTINEL).all(), "the pixels between two frames were written"
+    return a[:, :px * 4].reshape(n, cfg.height, cfg.width, 4), b[:, :px * 4].reshape(n, cfg.height, cfg.width, 4)
+
+
+# ---- the kernel alone ---------------------------------------------------------------------------------------------------
+def _synthetic(rng, n, h, w):
+    F = rng.random((n, h, w, 4), dtype=f32)
+    pick = rng.integers(0, 3, (n, h, w))
+    F[..., 3] = np.where(pick == 0, f32(0), np.where(pick == 1, f32(1), F[..., 3]))
+    vis = (rng.integers(0, 9, (n, h, w)).astype(f32) / f32(8)).astype(f32)
+    R = rng.random((n, h, w, 4), dtype=f32)
+    dR = (rng.random((n, h, w), dtype=f32) * f32(40)).astype(f32)
+    miss = rng.random((n, h, w)) < 0.4
+    R[miss] = 0
+    dR[miss] = S.FLT_MAX
+    return F, vis, R, dR
+
+
+def _strided(planes, comps, stride, lead=0):
+    """(n, H, W[, 4]) → a device buffer with frame i `stride` pixels on behind `lead` elements, sentinels elsewhere."""
+    n = planes.shape[0]
+    px = planes.shape[1] * planes.shape[2]
+    host = np.full(lead + n * stride * comps, SENTINEL, f32)
+    host[lead:].reshape(n, stride * comps)[:, :px * comps] = planes.reshape(n, px * comps)
+    return _dev(host)
+
+
+BACKGROUNDS = [(0.125, 0.5, 0.75, 1.0), (0.9, 0.1, 0.3, 1.0), (0.0, 1.0, 0.25, 1.0)]
+PAGES = {"color": (abi.Shot(page="color", pageColor=(0.93, 0.87, 0.2)), dict()),
+         "gradient_0.7": (abi.Shot(), dict(gradientScale=0.7)),
+         "scene_colour": (abi.Shot(), dict(gradientBg=False))}
+
+
+@pytest.fixture(scope="module")
+def three_handles(mcrt, gpu):
+    sds = []
+    for bg in BACKGROUNDS:
+        sd = mcrt.MeshBuilder.buildDefaultScene()
+        for i in range(4):
+            sd.desc.background_color[i] = bg[i]
+        sds.append(sd)
+    handles = [mcrt.DeviceScene(sd) for sd in sds]
+    yield sds, handles
+    for h in handles:
+        h.close()
+
+
+@gpu_test
+@pytest.mark.parametrize("lead", [0, 1], ids=["aligned", "planes_4_bytes_on"])
+@pytest.mark.parametrize("size", [(1, 1), (33, 17), (96, 64), (130, 3)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_kernel_alone_equals_compose(mcrt, gpu, oracle, three_handles, size, lead):
+    """Three frames, input stride W * H + 5, output stride W * H + 3, both outputs; each optional input absent in turn; the
+    three pages.  lead = 1: every plane one element on — the rgba planes 4 bytes off a 16-byte boundary, RGBA8 one byte off a
+    4-byte boundary."""
+    w, h = size
+    sds, handles = three_handles
+    n, px = 3, w * h
+    sin, sout = px + 5, px + 3
+    rng = np.random.default_rng(1000 * w + h)
+    F, vis, R, dR = _synthetic(rng, n, h, w)
+    dF, dvis, dRr, ddR = _strided(F, 4, sin, lead), _strided(vis, 1, sin, lead), _strided(R, 4, sin, lead), _strided(dR, 1, sin, lead)
+    at = lambda t: t.data_ptr() + lead * t.element_size()  # noqa: E731
+    for page_name, (page_shot, cfg_kw) in PAGES.items():
+        cfg = abi.Config(width=w, height=h, **cfg_kw)
+        pages = [S.page_plane(oracle, sd, cfg, page_shot) for sd in (sds if page_name == "scene_colour" else sds[:1])]
+        page = np.stack(pages if len(pages) == n else pages * n)
+        if page_name == "scene_colour":
+            assert all((page[i] == np.asarray(BACKGROUNDS[i][:3], f32)).all() for i in range(n))
+        for absent in ("none", "visibility", "reflection", "distance"):
+            shot = abi.Shot(page=page_shot.page, pageColor=page_shot.pageColor, shadowStrength=0.6, reflectivity=0.35,
+                            reflectionFade=0.0 if absent == "distance" else 24.0)
+            want = S.compose(F, None if absent == "visibility" else vis, None if absent == "reflection" else R, None if absent == "distance" else dR,
+                             page, shot)
+            out = torch.full((lead + n * sout * 4,), SENTINEL, dtype=torch.float32, device="cuda")
+            out8 = torch.full((lead + n * sout * 4,), BYTE_SENTINEL, dtype=torch.uint8, device="cuda")
+            mcrt.composite_shot_batch_device(
+                handles, cfg, shot, at(dF), 0 if absent == "visibility" else at(dvis), 0 if absent == "reflection" else at(dRr),
+                0 if absent == "distance" else at(ddR), at(out), at(out8), sin, sout, _stream())
+            torch.cuda.synchronize()
+            a, b = out.cpu().numpy(), out8.cpu().numpy()
+            what = f"{w}x{h} {page_name}, {absent} absent"
+            assert (a[:lead] == SENTINEL).all() and (b[:lead] == BYTE_SENTINEL).all(), what + ": written in front of the planes"
+            a, b = a[lead:].reshape(n, sout * 4), b[lead:].reshape(n, sout * 4)
+            assert (a[:, px * 4:] == SENTINEL).all() and (b[:, px * 4:] == BYTE_SENTINEL).all(), what + ": the gaps were written"
+            S.assert_shot_equal(a[:, :px * 4].reshape(n, h, w, 4), b[:, :px * 4].reshape(n, h, w, 4), want, what)
+        # one output at a time
+        shot = abi.Shot(page=page_shot.page, pageColor=page_shot.pageColor, reflectionFade=24.0)
+        want = S.compose(F, vis, R, dR, page, shot)
+        for which in ("f32", "u8"):
+            out = torch.full((n * sout * 4,), SENTINEL, dtype=torch.float32, device="cuda")
+            out8 = torch.full((n * sout * 4,), BYTE_SENTINEL, dtype=torch.uint8, device="cuda")
+            mcrt.composite_shot_batch_device(handles, cfg, shot, at(dF), at(dvis), at(dRr), at(ddR), out.data_ptr() if which == "f32" else 0,
+                                             out8.data_ptr() if which == "u8" else 0, sin, sout, _stream())
+            torch.cuda.synchronize()
+            a, b = out.cpu().numpy().reshape(n, sout * 4), out8.cpu().numpy().reshape(n, sout * 4)
+            if which == "f32":
+                assert (b == BYTE_SENTINEL).all()
+                S.assert_shot_equal(a[:, :px * 4].reshape(n, h, w, 4), None, want, f"{w}x{h} {page_name}, f32 alone")
+            else:
+                assert (a == SENTINEL).all()
+                S.assert_shot_equal(None, b[:, :px * 4].reshape(n, h, w, 4), want, f"{w}x{h} {page_name}, rgba8 alone")
+    # one frame: the record travels as a kernel argument
+    cfg = abi.Config(width=w, height=h)
+    shot = abi.Shot(reflectionFade=24.0)
+    out = torch.full((px * 4,), SENTINEL, dtype=torch.float32, device="cuda")
+    mcrt.composite_shot_batch_device(handles[:1], cfg, shot, at(dF), at(dvis), at(dRr), at(ddR), out.data_ptr(), 0, sin, px, _stream())
+    torch.cuda.synchronize()
+    want = S.compose(F[0], vis[0], R[0], dR[0], S.page_plane(oracle, sds[0], cfg, shot), shot)
+    S.assert_shot_equal(out.cpu().numpy().reshape(h, w, 4), None, want, f"{w}x{h} one frame")
+
+
+# ---- against the oracle alone -------------------------------------------------------------------------------------------
+ORACLE_CASES = ["pose0_default_96x64", "pose6_orbit_96x64", "pose5_orbit_64x64_t16", "pose0_33x17_t7", "pose0_1x1"]
+COUNTS = {"pose0_default_96x64": (507, 84, 150, 78, 108), "pose6_orbit_96x64": (1037, 104, 416, 177, 63),
+          "pose5_orbit_64x64_t16": (1743, 116, 473, 77, 150), "pose0_33x17_t7": (31, 14, 10, 6, 8), "pose0_1x1": (0, 1, 0, 0, 0)}
+
+
+@gpu_test
+@pytest.mark.parametrize("name", ORACLE_CASES)
+def test_shots_equal_the_oracle(mcrt, gpu, name):
+    sd, cfg, exp = S.skin_expectation(name)
+    got_classes = S.classes(exp)
+    print(name, dict(zip(S.CLASSES, got_classes)))
+    if cfg.width * cfg.height >= 3000:
+        assert all(c >= f for c, f in zip(got_classes, FLOORS)), got_classes
+    assert got_classes == COUNTS[name]  # the oracle's counts: any change of the expectation is noticed
+    assert not np.isnan(exp["out"]).any()
+    # the one-shot host form, both outputs
+    S.assert_shot_equal(mcrt.TileRenderer.renderShot(sd, cfg, S.SHOT, 0.0, rgba8=False), mcrt.TileRenderer.renderShot(sd, cfg, S.SHOT, 0.0), exp["out"],
+                        name + " (host form)")
+    # the device form
+    ds = mcrt.DeviceScene(sd)
+    try:
+        a, b = _shoot(mcrt, [ds], cfg, S.SHOT, [0.0])
+        S.assert_shot_equal(a[0], b[0], exp["out"], name + " (device form)")
+        # and mcrt_render_shot_device itself
+        out8 = torch.full((cfg.height, cfg.width, 4), BYTE_SENTINEL, dtype=torch.uint8, device="cuda")
+        scratch, need = _scratch(mcrt, cfg, S.SHOT, 1)
+        ds.render_shot_device(cfg, S.SHOT, 0.0, scratch.data_ptr(), need, 0, out8.data_ptr(), _stream())
+        torch.cuda.synchronize()
+        S.assert_shot_equal(None, out8.cpu().numpy(), exp["out"], name + " (single device form)")
+        ds.check()
+    finally:
+        ds.close()
+
+
+# ---- against the library's own four calls plus compose ------------------------------------------------------------------------
+def _own_planes(mcrt, handles, cfg, heights, pass_cfg=None):
+    """The transparent frames, ground visibilities and reflection planes of the handles through the library's own calls.
+    pass_cfg: the config of the two passes where cfg's is outside their limits."""
+    n, h, w = len(handles), cfg.height, cfg.width
+    pass_cfg = pass_cfg or cfg
+    F = torch.zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
+    vis = torch.zeros((n, h, w), dtype=torch.float32, device="cuda")
+    R = torch.zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
+    dR = torch.zeros((n, h, w), dtype=torch.float32, device="cuda")
+    for ds in handles:
+        ds.set_background("transparent")
+    mcrt.render_batch_device(handles, cfg, F.data_ptr(), 0, stream=_stream())
+    for ds in handles:
+        ds.set_background("reference")
+    mcrt.render_ground_batch_device(handles, pass_cfg, heights, visibility_ptr=vis.data_ptr(), stream=_stream())
+    mcrt.render_reflection_batch_device(handles, pass_cfg, heights, rgba_ptr=R.data_ptr(), distance_ptr=dR.data_ptr(), stream=_stream())
+    torch.cuda.synchronize()
+    return F.cpu().numpy(), vis.cpu().numpy(), R.cpu().numpy(), dR.cpu().numpy()
+
+
+LOOKS_CFG = dict(samplesPerPixel=2, maxBounces=8, dofEnabled=True, aperture=0.4, aoEnabled=True, aoSamples=4, shadowSamples=4)
+
+
+@gpu_test
+def test_a_batch_of_five_posed_scenes_equals_the_four_calls(mcrt, gpu):
+    cfg = abi.Config(width=80, height=56, **LOOKS_CFG)
+    cams = [(0.0, 20.0, 50.0), (60.0, 35.0, 40.0), (200.0, 25.0, 36.0), (310.0, 45.0, 32.0), (135.0, 20.0, 34.0)]
+    sds = [L.skin_case("S64" if k % 2 else "S32", (k * 3 + 1) % 7, cams[k]) for k in range(5)]
+    heights = [0.0, -0.5, 3.0, 1.25, 0.5]
+    shot = abi.Shot(shadowStrength=0.7, reflectivity=0.4, reflectionFade=30.0)
+    handles = [mcrt.DeviceScene(sd) for sd in sds]
+    try:
+        F, vis, R, dR = _own_planes(mcrt, handles, cfg, heights)
+        page = S.gradient_plane(cfg)
+        want = S.compose(F, vis, R, dR, np.broadcast_to(page, (5,) + page.shape), shot)
+        exp = {"F": F, "vis": vis, "R": R}
+        print("five frames:", dict(zip(S.CLASSES, S.classes(exp))))
+        assert all(c >= 50 for c in S.classes(exp)) and all(S.classes({k: v[i] for k, v in exp.items()})[0] > 0 for i in range(5))
+        a, b = _shoot(mcrt, handles, cfg, shot, heights, stride=cfg.width * cfg.height + 7)
+        S.assert_shot_equal(a, b, want, "five posed scenes")
+        host = mcrt.TileRenderer.renderShotBatch(sds, cfg, shot, heights)
+        S.assert_shot_equal(None, host, want, "five posed scenes (host form)")
+        for ds in handles:
+            ds.check()
+    finally:
+        for ds in handles:
+            ds.close()
+
+
+@gpu_test
+def test_full_hd_shot_equals_the_four_calls(mcrt, gpu):
+    cfg = abi.Config(width=1920, height=1080, **LOOKS_CFG)
+    sd = L.skin_case("S64", 6)
+    shot = abi.Shot(reflectionFade=30.0)
+    ds = mcrt.DeviceScene(sd)
+    try:
+        F, vis, R, dR = _own_planes(mcrt, [ds], cfg, [0.0])
+        want = S.compose(F[0], vis[0], R[0], dR[0], S.gradient_plane(cfg), shot)
+        got_classes = S.classes({"F": F[0], "vis": vis[0], "R": R[0]})
+        print("1920 x 1080:", dict(zip(S.CLASSES, got_classes)))
+        assert all(c >= 1000 for c in got_classes)
+        a, b = _shoot(mcrt, [ds], cfg, shot, [0.0])
+        S.assert_shot_equal(a[0], b[0], want, "1920 x 1080")
+        ds.check()
+    finally:
+        ds.close()
+
+
+# ---- shots that skip a pass -----------------------------------------------------------------------------------------------
+@gpu_test
+def test_shots_without_shadow_or_reflection(mcrt, gpu):
+    """s = 0, k = 0 and both, against the oracle's planes; and the configs only such shots accept — 200 shadow samples, 12
+    bounces — against the library's own calls."""
+    name = "pose0_33x17_t7"
+    sd, cfg, exp = S.skin_expectation(name)
+    ds = mcrt.DeviceScene(sd)
+    try:
+        for s, k in ((0.0, 0.35), (0.6, 0.0), (0.0, 0.0)):
+            shot = abi.Shot(shadowStrength=s, reflectivity=k, reflectionFade=24.0)
+            want = S.compose(exp["F"], exp["vis"], exp["R"], exp["dR"], exp["page"], shot)  # running the passes ...
+            skipped = S.compose(exp["F"], exp["vis"] if s > 0 else None, exp["R"] if k > 0 else None, exp["dR"] if k > 0 else None, exp["page"], shot)
+            scenes.assert_bit_equal(want, skipped, "... equals skipping them")
+            a, b = _shoot(mcrt, [ds], cfg, shot, [0.0])
+            S.assert_shot_equal(a[0], b[0], want, f"s = {s}, k = {k}")
+            assert mcrt.shot_scratch_bytes(cfg, shot, 1) < mcrt.shot_scratch_bytes(cfg, S.SHOT, 1)
+        full = abi.Shot(reflectionFade=24.0)
+        base = dict(width=cfg.width, height=cfg.height, tileSize=cfg.tileSize, samplesPerPixel=2)
+        legal = abi.Config(**base)  # for the library's own ground pass where the shot's config is outside a pass's limit
+        # k = 0 accepts 12 bounces (the ground pass does not read them) — and the shadow is still there
+        deep = abi.Config(maxBounces=12, **base)
+        shot = abi.Shot(reflectivity=0.0)
+        F, vis, _, _ = _own_planes(mcrt, [ds], deep, [0.0], pass_cfg=legal)
+        assert (vis < 1).sum() >= 10
+        a, b = _shoot(mcrt, [ds], deep, shot, [0.0])
+        S.assert_shot_equal(a[0], b[0], S.compose(F[0], vis[0], None, None, exp["page"], shot), "k = 0 at 12 bounces")
+        with pytest.raises(mcrt._lib.McrtError, match="at most 8 bounces"):
+            _shoot(mcrt, [ds], deep, full, [0.0])
+        # s = k = 0 accepts 200 shadow samples and 12 bounces
+        heavy = abi.Config(maxBounces=12, shadowSamples=200, **base)
+        shot = abi.Shot(shadowStrength=0.0, reflectivity=0.0)
+        F = _own_planes(mcrt, [ds], heavy, [0.0], pass_cfg=legal)[0]
+        a, b = _shoot(mcrt, [ds], heavy, shot, [0.0])
+        S.assert_shot_equal(a[0], b[0], S.compose(F[0], None, None, None, exp["page"], shot), "s = k = 0 at 200 samples, 12 bounces")
+        for refused in (full, abi.Shot(reflectivity=0.0), abi.Shot(shadowStrength=0.0)):
+            with pytest.raises(mcrt._lib.McrtError, match="113 shadow samples"):
+                _shoot(mcrt, [ds], abi.Config(shadowSamples=200, **base), refused, [0.0])
+        ds.check()
+    finally:
+        ds.close()
+
+
+# ---- the handle's background mode -------------------------------------------------------------------------------------------
+@gpu_test
+@pytest.mark.parametrize("mode", ["reference", "transparent"])
+def test_the_handles_background_mode_survives_a_shot(mcrt, gpu, mode):
+    sd, cfg, exp = S.skin_expectation("pose0_33x17_t7")
+    ds = mcrt.DeviceScene(sd)
+    try:
+        ds.set_background(mode)
+
+        def frame():
+            out = torch.zeros((cfg.height, cfg.width, 4), dtype=torch.float32, device="cuda")
+            ds.render_device(cfg, out.data_ptr(), 0, 1, abi.LAYOUT_FRAME, _stream())
+            torch.cuda.synchronize()
+            return out.cpu().numpy()
+
+        before = frame()
+        if mode == "transparent":
+            scenes.assert_bit_equal(before, exp["F"], "the transparent frame")
+        else:
+            assert (before[..., 3] == 1).all()
+        a, b = _shoot(mcrt, [ds], cfg, S.SHOT, [0.0])
+        S.assert_shot_equal(a[0], b[0], exp["out"], f"shot of a handle set to {mode}")
+        scenes.assert_bit_equal(frame(), before, f"{mode}: the frame after the shot")
+        ds.check()
+    finally:
+        ds.close()
+
+
+# ---- stream order --------------------------------------------------------------------------------------------------------------
+@gpu_test
+def test_a_shot_behind_a_repaint_and_a_view_change_on_one_stream(mcrt, gpu):
+    cfg = S.case_config("pose6_orbit_96x64")
+    skin, poses = P.skin("inner_hole"), mcrt.getBuiltinPoses()
+    want = mcrt.TileRenderer.renderShot(P.reference_scene(skin, poses[6], P.LOOK), cfg, S.SHOT, 0.0)
+    stale = mcrt.TileRenderer.renderShot(P.reference_scene(P.skin("synthetic_S64"), poses[0]), cfg, S.SHOT, 0.0)
+    assert want.tobytes() != stale.tobytes()
+    side = torch.cuda.Stream()
+    ds = mcrt.DeviceScene.for_skin("S64", poses[0])
+    try:
+        ds.set_skin(P.skin("synthetic_S64"))
+        first = _shoot(mcrt, [ds], cfg, S.SHOT, [0.0])[1][0]  # the handle has rendered the old skin and view
+        assert np.array_equal(first, stale)
+        d_skin = _dev(skin)
+        torch.cuda.synchronize()
+        ds.set_skin_device(d_skin.data_ptr(), side.cuda_stream)
+        ds.set_view_device(poses[6], P.look_desc(P.LOOK), side.cuda_stream)
+        got = _shoot(mcrt, [ds], cfg, S.SHOT, [0.0], stream=side.cuda_stream)[1][0]  # no synchronisation in between
+        assert np.array_equal(got, want)
+        ds.check()
+    finally:
+        ds.close()
+
+
+# ---- the farm ------------------------------------------------------------------------------------------------------------------
+@gpu_test
+def test_skin_batch_shots_equal_render_shot_batch(mcrt, gpu):
+    cfg = abi.Config(width=64, height=64, samplesPerPixel=2)
+    pose = mcrt.getBuiltinPoses()[3]
+    skins = np.stack([P.skin("synthetic_S64"), P.skin("all_transparent"), P.variant(P.skin("inner_hole"), 5)])
+    shot = abi.Shot(reflectionFade=30.0)
+    want = mcrt.TileRenderer.renderShotBatch([P.reference_scene(s, pose) for s in skins], cfg, shot, 0.0)
+    assert want[0].tobytes() != want[1].tobytes() and (want[..., 3] == 255).all()
+    batch = mcrt.SkinBatch(4, "S64", pose)
+    try:
+        got = batch.shots(skins, cfg, shot)
+        assert got.dtype == np.uint8 and np.array_equal(got, want)
+        floats = batch.shots(skins[:2], cfg, shot, ground=[0.0, 0.0], rgba8=False)
+        assert floats.dtype == np.float32 and np.array_equal(S.quantize(floats), want[:2])
+        # the batch's renders keep their mode
+        plain = batch.render(skins[:1], cfg, rgba8=True)
+        assert np.array_equal(plain, mcrt.TileRenderer.renderBatch([P.reference_scene(skins[0], pose)], cfg, rgba8=True))
+        assert batch.shots(skins[:0], cfg, shot).shape == (0, 64, 64, 4)
+    finally:
+        batch.close()
+
+
+# ---- the PNG -------------------------------------------------------------------------------------------------------------------
+@gpu_test
+def test_render_shot_png_decodes_to_the_rgba8_plane(mcrt, gpu, tmp_path):
+    from test_png import decode_png
+
+    sd, cfg, exp = S.skin_expectation("pose0_33x17_t7")
+    path = str(tmp_path / "shot.png")
+    assert mcrt.render_shot_png(sd, cfg, path, S.SHOT, 0.0) is True
+    with open(path, "rb") as f:
+        img = decode_png(f.read())
+    assert np.array_equal(np.asarray(img).reshape(cfg.height, cfg.width, 4), exp["rgba8"])
+    assert mcrt.render_shot_png(sd, abi.Config(width=0, height=4), path, S.SHOT, 0.0) is False
