@@ -109,12 +109,15 @@ def transparent_oracle() -> T.Checker:
     return T.Checker(T.build(tmp))
 
 
-def expected_shot(oracle, sd, cfg, shot: abi.Shot, ground_y) -> dict:
+def expected_shot(oracle, sd, cfg, shot: abi.Shot, ground_y, pass_cfg=None, threads=None) -> dict:
     """{"F" (H, W, 4), "vis" (H, W), "R" (H, W, 4), "dR" (H, W), "page" (H, W, 3), "out" (H, W, 4) float32, "rgba8" (H, W, 4)
-    uint8} — every input from the CPU oracle, whether or not the shot uses it."""
-    F, _ = transparent_oracle().render(sd.ptr, cfg, "transparent", threads=T.threads())
-    vis = G.expected_ground(oracle, sd, cfg, ground_y)["visibility"]
-    refl = R_.expected_reflection(oracle, sd, cfg, ground_y)
+    uint8} — every input from the CPU oracle, whether or not the shot uses it.  pass_cfg: the config of the two passes where
+    cfg's is outside their limits (a shot that skips a pass accepts such a config; it does not read the pass's plane).
+    threads: of the transparent checker (default: transparent_checker.threads())."""
+    pass_cfg = pass_cfg or cfg
+    F, _ = transparent_oracle().render(sd.ptr, cfg, "transparent", threads=threads or T.threads())
+    vis = G.expected_ground(oracle, sd, pass_cfg, ground_y)["visibility"]
+    refl = R_.expected_reflection(oracle, sd, pass_cfg, ground_y)
     page = page_plane(oracle, sd, cfg, shot)
     out = compose(F, vis, refl["rgba"], refl["distance"], page, shot)
     return {"F": F, "vis": vis, "R": refl["rgba"], "dR": refl["distance"], "page": page, "out": out, "rgba8": quantize(out)}
@@ -127,6 +130,30 @@ def classes(exp: dict) -> tuple:
     beside = a == 0
     return (int((a == 1).sum()), int(((a > 0) & (a < 1)).sum()), int((beside & (vis < 1)).sum()), int((beside & (vis > 0) & (vis < 1)).sum()),
             int((beside & (ra > 0)).sum()))
+
+
+def own_planes(mcrt, handles, cfg, heights, pass_cfg=None, stream=None):
+    """The transparent frames, ground visibilities and reflection planes of the handles through the library's own calls, as
+    numpy arrays (F, vis, R, dR).  pass_cfg: the config of the two passes where cfg's is outside their limits.  Needs the device;
+    the handles' background mode is "reference" afterwards."""
+    import torch
+
+    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    n, h, w = len(handles), cfg.height, cfg.width
+    pass_cfg = pass_cfg or cfg
+    F = torch.zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
+    vis = torch.zeros((n, h, w), dtype=torch.float32, device="cuda")
+    R = torch.zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
+    dR = torch.zeros((n, h, w), dtype=torch.float32, device="cuda")
+    for ds in handles:
+        ds.set_background("transparent")
+    mcrt.render_batch_device(handles, cfg, F.data_ptr(), 0, stream=stream)
+    for ds in handles:
+        ds.set_background("reference")
+    mcrt.render_ground_batch_device(handles, pass_cfg, heights, visibility_ptr=vis.data_ptr(), stream=stream)
+    mcrt.render_reflection_batch_device(handles, pass_cfg, heights, rgba_ptr=R.data_ptr(), distance_ptr=dR.data_ptr(), stream=stream)
+    torch.cuda.synchronize()
+    return F.cpu().numpy(), vis.cpu().numpy(), R.cpu().numpy(), dR.cpu().numpy()
 
 
 SHOT = abi.Shot(shadowStrength=0.6, reflectivity=0.35, reflectionFade=24.0)  # the shot of the oracle cases

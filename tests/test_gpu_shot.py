@@ -205,23 +205,7 @@ def test_shots_equal_the_oracle(mcrt, gpu, name):
 
 # ---- against the library's own four calls plus compose ------------------------------------------------------------------------
 def _own_planes(mcrt, handles, cfg, heights, pass_cfg=None):
-    """The transparent frames, ground visibilities and reflection planes of the handles through the library's own calls.
-    pass_cfg: the config of the two passes where cfg's is outside their limits."""
-    n, h, w = len(handles), cfg.height, cfg.width
-    pass_cfg = pass_cfg or cfg
-    F = torch.zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
-    vis = torch.zeros((n, h, w), dtype=torch.float32, device="cuda")
-    R = torch.zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
-    dR = torch.zeros((n, h, w), dtype=torch.float32, device="cuda")
-    for ds in handles:
-        ds.set_background("transparent")
-    mcrt.render_batch_device(handles, cfg, F.data_ptr(), 0, stream=_stream())
-    for ds in handles:
-        ds.set_background("reference")
-    mcrt.render_ground_batch_device(handles, pass_cfg, heights, visibility_ptr=vis.data_ptr(), stream=_stream())
-    mcrt.render_reflection_batch_device(handles, pass_cfg, heights, rgba_ptr=R.data_ptr(), distance_ptr=dR.data_ptr(), stream=_stream())
-    torch.cuda.synchronize()
-    return F.cpu().numpy(), vis.cpu().numpy(), R.cpu().numpy(), dR.cpu().numpy()
+    return S.own_planes(mcrt, handles, cfg, heights, pass_cfg, _stream())
 
 
 LOOKS_CFG = dict(samplesPerPixel=2, maxBounces=8, dofEnabled=True, aperture=0.4, aoEnabled=True, aoSamples=4, shadowSamples=4)

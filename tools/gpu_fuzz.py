@@ -37,6 +37,13 @@ Repaintable resident scenes (tests/resident_fuzz_cases.py; the runs and comparis
                streams, even seeds with a stretch of more than kTableSlots batch calls without a host wait; every checkpoint
                against the oracle and the host flattener; the summary records the scripts, the checkpoints compared by kind and
                the census of what the oracle saw (resident_fuzz_cases.census)
+The studio shot (tests/shot_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_shot_fuzz.py):
+  shot         even seeds are make_blend_case(seed): planes of 1 ... 70 x 1 ... 40 pixels and 1 ... 6 frames drawn per pixel from
+               classes of values (denormals, the quantiser's boundaries, dR at and beside fade, infinities, values up to 1e18),
+               three runs each through composite_shot_batch_device with leads, absent inputs and lone outputs of their own, against
+               shot_checker.compose; odd seeds are make_shot_case(seed): 1 ... 4 scenes of random skins and views, two calls through
+               the batched, single, host and PNG forms against the CPU oracle alone; the summary records the pixels compared and
+               the oracle's totals of shot_checker.classes
 A mismatch prints the case, the plane, the number of differing pixels and the first of them; the exit status is then 1.  After
 a HIP error (exit status 2) nothing more is started.  MCRT_BUNDLE_DECISIONS=0 / MCRT_REFLECT_CULL=0 in the environment render
 without the whole-bundle decisions / the reflection's tile culling: a mismatch that goes away with one is that shortcut's."""
@@ -52,7 +59,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident", "shot") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -275,6 +282,58 @@ def resident_sweep():
     sys.exit(1 if bad else 0)
 
 
+def shot_sweep():
+    import tempfile
+    import shot_checker as S, shot_fuzz_cases as SF, test_gpu_shot_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    # the oracle's planes of the whole shots (the odd seeds) are made ahead of the device by worker processes (forked before the
+    # device is first used; they never use it), in the order of the seeds
+    import multiprocessing
+
+    workers = max(1, min(14, len(os.sched_getaffinity(0)) - 2, int(os.environ.get("OMP_NUM_THREADS", "16")) - 2))
+    S.transparent_oracle()  # built once, before the fork
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    seeds = range(first, first + count)
+    ahead = pool.imap(SF.worker_shot_expectation, [s for s in seeds if s % 2])
+    shared = T._coloured_handles(M, [(0.125, 0.5, 0.75, 1.0), (0.9, 0.1, 0.3, 1.0), (0.0, 1.0, 0.25, 1.0)])
+    tmp = tempfile.mkdtemp(prefix="fuzz_shot_")
+    bad = blends = shots = pixels = frames = 0
+    total = np.zeros(len(S.CLASSES), np.int64)
+    t0 = time.time()
+    for k, seed in enumerate(seeds):
+        try:
+            if seed % 2 == 0:
+                case = SF.make_blend_case(seed)
+                lines = T.run_blend_case(M, shared, case)
+                blends += 1; pixels += 3 * case["n"] * case["w"] * case["h"]
+            else:
+                case = SF.make_shot_case(seed)
+                exps = next(ahead)
+                lines = T.run_shot_case(M, case, exps, tmp)
+                shots += 1; frames += sum(len(per_scene) for per_scene in exps)
+                for exp in exps[0]:
+                    total += np.asarray(S.classes(exp))
+        except (McrtError, RuntimeError) as e:  # the library's, or torch's at a host wait
+            print(f"HIP ERROR shot seed {seed}: {e}", flush=True)
+            print(f"fuzz shot: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
+            pool.terminate()
+            sys.exit(2)
+        if lines:
+            bad += 1
+            print("\n".join(lines[:20]), flush=True)
+        if k % 500 == 499:
+            print(f"... {k + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
+    for h in shared:
+        h.close()
+    import shutil
+    shutil.rmtree(tmp, ignore_errors=True)
+    print(f"fuzz shot: {count} cases from seed {first}: {bad} mismatch(es); {blends} blend cases with {pixels} pixels blended, {shots} shot cases "
+          f"with {frames} frames; {time.time() - t0:.0f} s; the oracle holds " + ", ".join(f"{int(t)} {name}" for name, t in zip(S.CLASSES, total)))
+    pool.terminate()
+    sys.exit(1 if bad else 0)
+
+
 def pass_sweep():
     import ground_checker as G, layers_checker as L, pass_fuzz_cases as PF, reflection_checker as R
     from minecraftskin_raytracer_amd._lib import McrtError
@@ -349,6 +408,8 @@ if mode == "big":
     big_sweep()
 if mode == "resident":
     resident_sweep()
+if mode == "shot":
+    shot_sweep()
 if len(sys.argv) > 3 and sys.argv[3] == "bundle":
     make_case = make_bundle_case
 if len(sys.argv) > 3 and sys.argv[3] == "wide":
