@@ -428,6 +428,48 @@ int mcrt_render_ground(const mcrt_scene_desc* scene, const mcrt_config* cfg, flo
  * standing poses) for a contact shadow.  A scene without a vertex (or a NULL argument) → MCRT_ERR_INVALID. */
 int mcrt_scene_floor(const mcrt_scene_desc* scene, float* y);
 
+/* ---- ground occlusion: the figure's contact occlusion on a floor plane, as a layer of its own -----------------------------
+ * The ground shadow is the disk light's shadow alone: it falls away from the light, so the floor between and right around the
+ * feet stays fully lit.  This pass answers, per pixel, how open the hemisphere above the point of the plane y = ground_y under
+ * that pixel is — the reference's ambient occlusion, asked at the floor.  The ray, the plane hit, t and P are the ground
+ * shadow's: the pixel-centre ray, t = (ground_y - o.y) / d.y, the pixel REACHES the plane iff d.y != 0 && t > 0 && t <= FLT_MAX,
+ * P = (o.x + d.x * t, ground_y, o.z + d.z * t), N = (0, 1, 0) from either side.  All arithmetic float32, uncontracted:
+ *   seed      = (unsigned)(P.x * 73856093.0f + P.y * 19349663.0f + P.z * 83492791.0f)     summed left to right, the reference's
+ *                                                   cast (raytracer.cpp:122-123)
+ *   occlusion = computeAO(P, N, scene, ao_samples, ao_radius, seed)                        (raytracer.cpp:38-78)
+ *             = 1 - occluded / ao_samples           occluded: the samples whose ray from P + N * 1e-3f meets a mesh before ao_radius
+ * The figure in front of the plane plays no part.  Planes of width * height pixels, row-major:
+ *   occlusion   1 float   the value above                                               not reached: 1.0f
+ *   matte       1 uint8   (uint8_t)(clamp(1.0f - occlusion, 0, 1) * 255.0f + 0.5f)         not reached: 0
+ * The distance plane is the ground pass's and is not repeated.  Of mcrt_config the pass reads width, height, tile_size (the
+ * granularity of the culling, never a value), ao_samples and ao_radius; everything else — ao_enabled, ao_intensity, the shadow
+ * fields — and the handle's background mode are IGNORED.  The values are bit-identical to the reference's computeAO at those
+ * points.  ao_radius <= 0 is legal: no ray can be occluded, every value is 1.0f and nothing is traced.
+ * ao_samples is limited to 1 .. 113 (MCRT_ERR_INVALID outside): the reference divides by it, and the pass draws a pixel's
+ * samples from the truncated mt19937 form, which yields the first 227 draws of an engine — a sample takes two.
+ * The rules of the ground shadow hold word for word: whole frames only; asynchronous on `stream`, not into a graph being
+ * recorded; no workspace, no counters and none of the handle's events, so the pass may run beside the handle's render on
+ * another stream; it reads the device's seed tables through the handle and builds none; mcrt_scene_destroy and
+ * mcrt_scene_check wait for it; a handle may be listed more than once in a batch, with different ground_y; the pixels between
+ * frames are not written; ground_y of a batch is host memory read before the call returns.
+ * MCRT_ERR_INVALID before any device work: a NULL config, handle, entry, ground_y array or planes struct, both planes NULL,
+ * n_frames < 0, a stride below width * height, handles on different devices, a ground_y that is not finite, ao_samples < 1,
+ * ao_samples > 113, an ao_radius that is not finite.  Zero-size frames and n_frames = 0: MCRT_OK, nothing written. */
+typedef struct mcrt_ground_occlusion {
+    float* occlusion; /* either may be NULL (that plane is not produced), not both */
+    uint8_t* matte;
+} mcrt_ground_occlusion;
+/* resident scene, device pointers, asynchronous on `stream` */
+int mcrt_render_ground_occlusion_device(mcrt_scene* scene, const mcrt_config* cfg, float ground_y, const mcrt_ground_occlusion* d_out,
+                                        void* stream);
+/* n_frames scenes of one config in one launch; ground_y: n_frames heights in HOST memory (read before the call returns); frame i
+ * at each plane + i * frame_stride_pixels pixels */
+int mcrt_render_ground_occlusion_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y,
+                                              const mcrt_ground_occlusion* d_out, size_t frame_stride_pixels, void* stream);
+/* one-shot host form: host pointers, rendered on `device` with a pooled handle like mcrt_render */
+int mcrt_render_ground_occlusion(const mcrt_scene_desc* scene, const mcrt_config* cfg, float ground_y, const mcrt_ground_occlusion* out,
+                                 int device);
+
 /* ---- ground reflection: the figure mirrored in a floor plane, as a layer of its own ---------------------------------------
  * The other half of a figure standing on a glossy floor: per pixel, the colour the reference's own recursion would return for
  * the reflection ray of a floor at y = ground_y — traceRay(reflectRay, depth + 1) (raytracer.cpp:133-142) with the floor as the
@@ -775,6 +817,35 @@ int mcrt_render_shot_batch(const mcrt_scene_desc* const* scenes, int n_frames, c
  * for mcrt_render_png */
 int mcrt_render_shot_png(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, const char* path,
                          int device);
+
+/* The shot with a FLOOR-OCCLUSION term.  A strength o = floor_occlusion in [0, 1] and the ground-occlusion pass's plane occ
+ * (1.0f where the plane is absent) enter the blend between the shadow and the reflection; everything else is as above:
+ *   oc    = o * (1.0f - occ)
+ *   keep  = ((1.0f - sh) * (1.0f - oc)) * (1.0f - ar)
+ * CONSEQUENCE.  With o == 0, or without an occlusion plane, oc is +0 and (1 - sh) * 1.0f is (1 - sh) exactly: the image is
+ * the one of the entries above bit for bit, the ground-occlusion pass is not run, and its limits on ao_samples / ao_radius
+ * do not apply.  The entries above are these with o = 0 and no plane; mcrt_shot and mcrt_shot_inputs are unchanged.
+ * The floor's sampling is cfg's ao_samples / ao_radius — the fields the figure's own ambient occlusion reads when ao_enabled.
+ *   mcrt_shot_scratch_bytes_occ        the layout above, and behind it an occlusion plane of 4 B/px when o > 0 (the offsets of
+ *                                      the other planes do not move); 0 also for an o outside [0, 1] or NaN
+ *   mcrt_render_shot_batch_device_occ  render, ground, reflection, ground occlusion, blend, in that order on `stream`; the
+ *                                      event rules and argument checks of mcrt_render_shot_batch_device, and MCRT_ERR_INVALID
+ *                                      also for a floor_occlusion outside [0, 1] or NaN and, with o > 0, for ao_samples < 1,
+ *                                      ao_samples > 113 or an ao_radius that is not finite
+ *   mcrt_composite_shot_batch_device_occ   the blend alone; d_occlusion: 1 float per pixel, frame i in_stride_pixels pixels
+ *                                      on, or NULL; it refuses a floor_occlusion outside [0, 1] or NaN
+ *   mcrt_render_shot_batch_occ, mcrt_render_shot_png_occ   the host forms */
+size_t mcrt_shot_scratch_bytes_occ(const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, int n_frames);
+int mcrt_render_shot_batch_device_occ(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot,
+                                      float floor_occlusion, const float* ground_y, void* d_scratch, size_t scratch_bytes, float* d_out_f32,
+                                      uint8_t* d_out_rgba8, size_t frame_stride_pixels, void* stream);
+int mcrt_composite_shot_batch_device_occ(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot,
+                                         const mcrt_shot_inputs* d_in, const float* d_occlusion, float floor_occlusion, size_t in_stride_pixels,
+                                         float* d_out_f32, uint8_t* d_out_rgba8, size_t out_stride_pixels, void* stream);
+int mcrt_render_shot_batch_occ(const mcrt_scene_desc* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot,
+                               float floor_occlusion, const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device);
+int mcrt_render_shot_png_occ(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, float ground_y,
+                             const char* path, int device);
 
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);

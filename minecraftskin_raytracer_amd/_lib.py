@@ -37,6 +37,9 @@ EXPORTED_SYMBOLS = [
     "mcrt_scene_set_view", "mcrt_scene_set_view_device", "mcrt_scene_set_views_batch_device", "mcrt_skin_view_table",
     "mcrt_shot_init", "mcrt_shot_scratch_bytes", "mcrt_composite_shot_batch_device", "mcrt_render_shot_batch_device",
     "mcrt_render_shot_device", "mcrt_render_shot", "mcrt_render_shot_batch", "mcrt_render_shot_png",
+    "mcrt_render_ground_occlusion_device", "mcrt_render_ground_occlusion_batch_device", "mcrt_render_ground_occlusion",
+    "mcrt_shot_scratch_bytes_occ", "mcrt_render_shot_batch_device_occ", "mcrt_composite_shot_batch_device_occ",
+    "mcrt_render_shot_batch_occ", "mcrt_render_shot_png_occ",
 ]
 
 
@@ -57,6 +60,7 @@ def load():
     vp = C.c_void_p
     layers_p = C.POINTER(abi.McrtLayers)
     ground_p = C.POINTER(abi.McrtGround)
+    ground_occlusion_p = C.POINTER(abi.McrtGroundOcclusion)
     reflection_p = C.POINTER(abi.McrtReflection)
     light_p = C.POINTER(abi.McrtLightPlanes)
     bake_p = C.POINTER(abi.McrtBakePlanes)
@@ -91,6 +95,9 @@ def load():
         "mcrt_render_ground_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, f_p, ground_p, C.c_size_t, vp]),
         "mcrt_render_ground": (C.c_int, [desc_p, cfg_p, C.c_float, ground_p, C.c_int]),
         "mcrt_scene_floor": (C.c_int, [desc_p, f_p]),
+        "mcrt_render_ground_occlusion_device": (C.c_int, [vp, cfg_p, C.c_float, ground_occlusion_p, vp]),
+        "mcrt_render_ground_occlusion_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, f_p, ground_occlusion_p, C.c_size_t, vp]),
+        "mcrt_render_ground_occlusion": (C.c_int, [desc_p, cfg_p, C.c_float, ground_occlusion_p, C.c_int]),
         "mcrt_render_reflection_device": (C.c_int, [vp, cfg_p, C.c_float, reflection_p, vp]),
         "mcrt_render_reflection_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, f_p, reflection_p, C.c_size_t, vp]),
         "mcrt_render_reflection": (C.c_int, [desc_p, cfg_p, C.c_float, reflection_p, C.c_int]),
@@ -121,6 +128,12 @@ def load():
         "mcrt_render_shot": (C.c_int, [desc_p, cfg_p, shot_p, C.c_float, f_p, u8_p, C.c_int]),
         "mcrt_render_shot_batch": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, shot_p, f_p, f_p, u8_p, C.c_int]),
         "mcrt_render_shot_png": (C.c_int, [desc_p, cfg_p, shot_p, C.c_float, C.c_char_p, C.c_int]),
+        "mcrt_shot_scratch_bytes_occ": (C.c_size_t, [cfg_p, shot_p, C.c_float, C.c_int]),
+        "mcrt_render_shot_batch_device_occ": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, shot_p, C.c_float, f_p, vp, C.c_size_t, vp, vp, C.c_size_t, vp]),
+        "mcrt_composite_shot_batch_device_occ": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, shot_p, C.POINTER(abi.McrtShotInputs), vp, C.c_float, C.c_size_t, vp,
+                                                           vp, C.c_size_t, vp]),
+        "mcrt_render_shot_batch_occ": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, shot_p, C.c_float, f_p, f_p, u8_p, C.c_int]),
+        "mcrt_render_shot_png_occ": (C.c_int, [desc_p, cfg_p, shot_p, C.c_float, C.c_float, C.c_char_p, C.c_int]),
         "mcrt_probe_scene_blob": (C.c_int, [vp, vp, C.c_size_t]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),
         "mcrt_encode_png_rgba8": (C.c_size_t, [u8_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),

@@ -6,7 +6,7 @@ oracle / compiled-reference loaders live under ``tests/``.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import InitVar, dataclass, field, fields
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -192,6 +192,31 @@ def ground_names(planes) -> tuple:
     return tuple(n for n in GROUND_NAMES if n in names)
 
 
+class McrtGroundOcclusion(C.Structure):
+    """mcrt_ground_occlusion: one pointer per plane of a ground-occlusion pass (device or host memory, by entry point); NULL = not wanted."""
+
+    _fields_ = [("occlusion", C.c_void_p), ("matte", C.c_void_p)]
+
+
+GROUND_OCCLUSION_NAMES = ("occlusion", "matte")
+# per pixel: the dtype of each plane (one component each)
+GROUND_OCCLUSION_FORMATS = {"occlusion": np.float32, "matte": np.uint8}
+GROUND_OCCLUSION_MAX_SAMPLES = 113  # aoSamples of a ground-occlusion pass: 1 .. 113
+
+
+def ground_occlusion_names(planes) -> tuple:
+    """The wanted ground-occlusion planes in the order of ``GROUND_OCCLUSION_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
+    if isinstance(planes, str):
+        planes = (planes,)
+    names = tuple(planes)
+    for n in names:
+        if not isinstance(n, str) or n not in GROUND_OCCLUSION_FORMATS:
+            raise ValueError(f"planes must be taken from {GROUND_OCCLUSION_NAMES}, not {n!r}")
+    if not names:
+        raise ValueError("no plane selected")
+    return tuple(n for n in GROUND_OCCLUSION_NAMES if n in names)
+
+
 class McrtReflection(C.Structure):
     """mcrt_reflection: one pointer per plane of a ground-reflection pass (device or host memory, by entry point); NULL = not wanted."""
 
@@ -290,13 +315,30 @@ class McrtShotInputs(C.Structure):
 class Shot:
     """mcrt_shot with mcrt_shot_init's defaults: the figure over the reference's background, a ground shadow of strength 0.6
     and a floor reflection of reflectivity 0.35 that does not fade.  ``page``: ``"reference"`` or ``"color"`` (then
-    ``pageColor``); ``reflectionFade``: the reflection distance at which the mirror image has vanished, 0 = no fade."""
+    ``pageColor``); ``reflectionFade``: the reflection distance at which the mirror image has vanished, 0 = no fade;
+    ``floorOcclusion``: the strength of the floor's contact occlusion (the ground-occlusion pass at the config's ``aoSamples`` /
+    ``aoRadius``), 0 = none.  It is no field of mcrt_shot: the entries that take it (``*_occ``) take it as an argument."""
 
     page: str = "reference"
     pageColor: Sequence[float] = (1.0, 1.0, 1.0)
     shadowStrength: float = 0.6
     reflectivity: float = 0.35
     reflectionFade: float = 0.0
+    # the last parameter of the constructor and an attribute like the others, but no dataclass field: ``dataclasses.asdict`` and
+    # ``fields`` — what describes mcrt_shot — stay as they were
+    floorOcclusion: InitVar[float] = 0.0
+
+    def __post_init__(self, floorOcclusion):
+        self.floorOcclusion = float(floorOcclusion)
+
+    def __eq__(self, other):
+        if other.__class__ is not self.__class__:
+            return NotImplemented
+        return all(getattr(self, f.name) == getattr(other, f.name) for f in fields(self)) and self.floorOcclusion == other.floorOcclusion
+
+    def __repr__(self):
+        body = ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in fields(self))
+        return f"Shot({body})" if self.floorOcclusion == 0.0 else f"Shot({body}, floorOcclusion={self.floorOcclusion!r})"
 
     def to_c(self) -> McrtShot:
         if not isinstance(self.page, str) or self.page not in PAGES:

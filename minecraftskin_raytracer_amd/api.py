@@ -316,6 +316,37 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderGroundOcclusion(scene, config: Config, ground: Optional[float] = None, planes=abi.GROUND_OCCLUSION_NAMES, device: int = 0) -> dict:
+        """The figure's contact occlusion on the floor plane y = ``ground`` (mcrt_render_ground_occlusion; ``None``: the scene's
+        floor, ``scene_floor``): a dict of the wanted planes, (H, W) each — ``occlusion`` float32, the reference's ambient
+        occlusion at the plane's point under the pixel (1 where nothing is near, and where the pixel's ray misses the plane),
+        ``matte`` uint8, the quantised ``1 - occlusion``: the alpha of a black contact-shadow image to put under the transparent
+        figure.  Of ``config`` only width, height, tileSize, aoSamples (1 to 113) and aoRadius matter — not aoEnabled.  Failures
+        raise ``McrtError``."""
+        out = TileRenderer.renderGroundOcclusionBatch([scene], config, ground, planes, device)
+        return {k: v[0] for k, v in out.items()}
+
+    @staticmethod
+    def renderGroundOcclusionBatch(scenes, config: Config, ground=None, planes=abi.GROUND_OCCLUSION_NAMES, device: int = 0) -> dict:
+        """``renderGroundOcclusion`` for N scenes of one config: the same planes with a leading N.  ``ground``: ``None`` (every
+        scene's own floor), one height for all, or a sequence of N heights.  This host form is a LOOP of
+        ``mcrt_render_ground_occlusion`` calls, like ``renderGroundBatch``; the batched path is
+        ``render_ground_occlusion_batch_device`` on resident ``DeviceScene`` handles (one launch per 4096 frames)."""
+        names = abi.ground_occlusion_names(planes)
+        descs = [_as_desc(s) for s in scenes]
+        n = len(descs)
+        heights = _ground_heights(descs, ground)
+        w, h = max(config.width, 0), max(config.height, 0)
+        out = {k: _empty_ground_occlusion(k, n, h, w) for k in names}
+        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
+            return out
+        c = config.to_c()
+        for i, d in enumerate(descs):
+            frame = abi.McrtGroundOcclusion(**{k: v[i].ctypes.data for k, v in out.items()})
+            check(load().mcrt_render_ground_occlusion(d.ptr, C.byref(c), heights[i], C.byref(frame), int(device)))
+        return out
+
+    @staticmethod
     def renderReflection(scene, config: Config, ground: Optional[float] = None, planes=abi.REFLECTION_NAMES, device: int = 0) -> dict:
         """The figure mirrored in the floor plane y = ``ground`` (mcrt_render_reflection; ``None``: the scene's floor,
         ``scene_floor``): a dict of the wanted planes — ``rgba`` (H, W, 4) float32, the colour the reference's recursion returns
@@ -352,8 +383,9 @@ class TileRenderer:
         """The studio shot (mcrt_render_shot): the figure on a page, with its ground shadow and its floor reflection at
         y = ``ground`` (``None``: the scene's floor, ``scene_floor``), blended on the device — (H, W, 4) uint8, or float32 with
         ``rgba8=False``; alpha is 255 / 1.0 everywhere.  ``shot``: ``abi.Shot`` (``None``: its defaults).  The figure is the
-        ``background="transparent"`` render of ``config``; the definition of the blend is in include/mcrt.h.  Failures raise
-        ``McrtError``."""
+        ``background="transparent"`` render of ``config``; the definition of the blend is in include/mcrt.h.  With
+        ``shot.floorOcclusion`` > 0 the floor's contact occlusion (``renderGroundOcclusion`` at the config's aoSamples /
+        aoRadius) darkens the page too.  Failures raise ``McrtError``."""
         return TileRenderer.renderShotBatch([scene], config, shot, ground, rgba8, device)[0]
 
     @staticmethod
@@ -361,7 +393,7 @@ class TileRenderer:
         """``renderShot`` for N scenes of one config in one call (mcrt_render_shot_batch): one batched render, one ground and
         one reflection launch, one blend, one download.  ``ground``: ``None`` (every scene's own floor), one height for all, or
         N heights.  Returns (N, H, W, 4) uint8, or float32 with ``rgba8=False``."""
-        s = (shot if shot is not None else abi.Shot()).to_c()
+        s, o = _shot_c(shot)
         descs = [_as_desc(d) for d in scenes]
         n = len(descs)
         heights = _ground_heights(descs, ground)
@@ -374,7 +406,10 @@ class TileRenderer:
         buf = out if out.size else np.zeros(4, out.dtype)  # (no frame: the call checks its arguments and writes nothing)
         f = None if rgba8 else abi.fptr(buf)
         b = buf.ctypes.data_as(C.POINTER(C.c_uint8)) if rgba8 else None
-        check(load().mcrt_render_shot_batch(arr, n, C.byref(c), C.byref(s), gy, f, b, int(device)))
+        if o != 0.0:
+            check(load().mcrt_render_shot_batch_occ(arr, n, C.byref(c), C.byref(s), o, gy, f, b, int(device)))
+        else:
+            check(load().mcrt_render_shot_batch(arr, n, C.byref(c), C.byref(s), gy, f, b, int(device)))
         return out
 
     @staticmethod
@@ -465,6 +500,21 @@ def _empty_ground(name: str, n: int, h: int, w: int) -> np.ndarray:
     elif name == "distance":
         a[...] = np.finfo(np.float32).max
     return a
+
+
+def _empty_ground_occlusion(name: str, n: int, h: int, w: int) -> np.ndarray:
+    """One ground-occlusion plane for n frames, holding the constants of a pixel that misses the plane."""
+    a = np.zeros((n, h, w), abi.GROUND_OCCLUSION_FORMATS[name])
+    if name == "occlusion":
+        a[...] = 1.0
+    return a
+
+
+def _shot_c(shot):
+    """(mcrt_shot, floor-occlusion strength) of ``shot`` (``None``: the defaults).  The entries take the ``*_occ`` form of the
+    library whenever the strength is not 0, so the library refuses one that is negative, above 1 or NaN."""
+    sh = shot if shot is not None else abi.Shot()
+    return sh.to_c(), float(sh.floorOcclusion)
 
 
 def _empty_reflection(name: str, n: int, h: int, w: int) -> np.ndarray:
@@ -592,19 +642,24 @@ def render_png(scene, config: Config, path: str, device: int = 0, background: st
 def render_shot_png(scene, config: Config, path: str, shot: Optional[abi.Shot] = None, ground: Optional[float] = None, device: int = 0) -> bool:
     """``TileRenderer.renderShot`` + ``ImageWriter.writePNG8`` in one call (mcrt_render_shot_png): the finished studio shot as
     a PNG, 4 B/pixel copied back.  ``ground=None``: the scene's floor.  False on failure, like ``render_png``."""
-    s = (shot if shot is not None else abi.Shot()).to_c()
+    s, o = _shot_c(shot)
     d = _as_desc(scene)
     g = _ground_heights([d], ground)[0]
     c = config.to_c()
+    if o != 0.0:
+        return load().mcrt_render_shot_png_occ(d.ptr, C.byref(c), C.byref(s), o, g, os.fsencode(path), int(device)) == 0
     return load().mcrt_render_shot_png(d.ptr, C.byref(c), C.byref(s), g, os.fsencode(path), int(device)) == 0
 
 
 def shot_scratch_bytes(config: Config, shot: Optional[abi.Shot] = None, n_frames: int = 1) -> int:
     """Bytes of device scratch ``render_shot_batch_device`` / ``DeviceScene.render_shot_device`` need for ``n_frames`` frames
     (mcrt_shot_scratch_bytes; host only): 16 per pixel, + 16 with a reflection, + 4 with a shadow, + 4 with a fading
-    reflection, every plane on a 16-byte boundary.  0 for a zero-size frame or ``n_frames <= 0``."""
-    s = (shot if shot is not None else abi.Shot()).to_c()
+    reflection, + 4 behind them with ``floorOcclusion`` > 0 (mcrt_shot_scratch_bytes_occ), every plane on a 16-byte boundary.
+    0 for a zero-size frame or ``n_frames <= 0``."""
+    s, o = _shot_c(shot)
     c = config.to_c()
+    if o != 0.0:
+        return int(load().mcrt_shot_scratch_bytes_occ(C.byref(c), C.byref(s), o, int(n_frames)))
     return int(load().mcrt_shot_scratch_bytes(C.byref(c), C.byref(s), int(n_frames)))
 
 
@@ -868,6 +923,19 @@ class DeviceScene:
         planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
         check(load().mcrt_render_ground_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
 
+    def render_ground_occlusion_device(self, config: Config, ground: float, occlusion_ptr: int = 0, matte_ptr: int = 0, stream: int = 0) -> None:
+        """The ground-occlusion planes of the frame into device memory (mcrt_render_ground_occlusion_device): width * height
+        pixels per plane — occlusion 4 bytes per pixel, matte 1 — either pointer may be 0, not both.  ``ground``: the plane's
+        height.  Asynchronous on ``stream``; uses none of the handle's workspace, so it may run beside a render of the handle on
+        another stream."""
+        if not (occlusion_ptr or matte_ptr):
+            raise ValueError("give at least one of occlusion_ptr, matte_ptr")
+        if not np.isfinite(np.float32(ground)):
+            raise ValueError("ground must be finite")
+        c = config.to_c()
+        planes = abi.McrtGroundOcclusion(occlusion_ptr or None, matte_ptr or None)
+        check(load().mcrt_render_ground_occlusion_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
+
     def render_reflection_device(self, config: Config, ground: float, rgba_ptr: int = 0, rgba8_ptr: int = 0, distance_ptr: int = 0,
                                  stream: int = 0) -> None:
         """The ground-reflection planes of the frame into device memory (mcrt_render_reflection_device): width * height pixels
@@ -891,8 +959,15 @@ class DeviceScene:
             raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
         if not np.isfinite(np.float32(ground)):
             raise ValueError("ground must be finite")
-        s = (shot if shot is not None else abi.Shot()).to_c()
+        s, o = _shot_c(shot)
         c = config.to_c()
+        if o != 0.0:  # the floor-occlusion term: the batch entry with one handle
+            px = max(config.width, 0) * max(config.height, 0)
+            arr = (C.c_void_p * 1)(self._h.value)
+            gy = (C.c_float * 1)(float(ground))
+            check(load().mcrt_render_shot_batch_device_occ(arr, 1, C.byref(c), C.byref(s), o, gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
+                                                           C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), px, C.c_void_p(stream)))
+            return
         check(load().mcrt_render_shot_device(self._h, C.byref(c), C.byref(s), float(ground), C.c_void_p(scratch_ptr or None), int(scratch_bytes),
                                              C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), C.c_void_p(stream)))
 
@@ -1029,6 +1104,29 @@ def render_ground_batch_device(device_scenes: Sequence["DeviceScene"], config: C
     check(load().mcrt_render_ground_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
 
 
+def render_ground_occlusion_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, ground, occlusion_ptr: int = 0, matte_ptr: int = 0,
+                                         frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
+    """The ground-occlusion planes of N resident scenes of one config in one launch (mcrt_render_ground_occlusion_batch_device):
+    frame i of each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  ``ground``: one height for
+    all, or N heights (a handle may be listed more than once, with different heights).  Asynchronous on ``stream``."""
+    handles = _shot_handles(device_scenes)
+    if not (occlusion_ptr or matte_ptr):
+        raise ValueError("give at least one of occlusion_ptr, matte_ptr")
+    if ground is None:
+        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
+    heights = _ground_heights(handles, ground)
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
+    if stride < px:
+        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
+    n = len(handles)
+    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    gy = (C.c_float * max(n, 1))(*heights)
+    c = config.to_c()
+    planes = abi.McrtGroundOcclusion(occlusion_ptr or None, matte_ptr or None)
+    check(load().mcrt_render_ground_occlusion_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+
+
 def render_reflection_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, ground, rgba_ptr: int = 0, rgba8_ptr: int = 0,
                                    distance_ptr: int = 0, frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
     """The ground-reflection planes of N resident scenes of one config in one launch (mcrt_render_reflection_batch_device): frame
@@ -1071,7 +1169,9 @@ def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Con
     """The studio shots of N resident scenes of one config (mcrt_render_shot_batch_device): one batched render, one ground and
     one reflection launch and one blend, in order on ``stream``; frame i lands ``i * frame_stride_pixels`` pixels on (default
     width * height) in ``out_f32_ptr`` (16 B/pixel) and / or ``out_rgba8_ptr`` (4 B/pixel).  ``ground``: one height for all, or
-    N heights.  ``scratch_ptr``: device memory, 16-byte aligned, ``shot_scratch_bytes(config, shot, N)`` bytes."""
+    N heights.  ``scratch_ptr``: device memory, 16-byte aligned, ``shot_scratch_bytes(config, shot, N)`` bytes.  With
+    ``shot.floorOcclusion`` > 0 the ground-occlusion pass runs between the reflection and the blend
+    (mcrt_render_shot_batch_device_occ)."""
     handles = _shot_handles(device_scenes)
     if not out_f32_ptr and not out_rgba8_ptr:
         raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
@@ -1082,11 +1182,15 @@ def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Con
     stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
     if stride < px:
         raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    s = (shot if shot is not None else abi.Shot()).to_c()
+    s, o = _shot_c(shot)
     n = len(handles)
     arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
     gy = (C.c_float * max(n, 1))(*heights)
     c = config.to_c()
+    if o != 0.0:
+        check(load().mcrt_render_shot_batch_device_occ(arr, n, C.byref(c), C.byref(s), o, gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
+                                                       C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride, C.c_void_p(stream)))
+        return
     check(load().mcrt_render_shot_batch_device(arr, n, C.byref(c), C.byref(s), gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
                                                C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride, C.c_void_p(stream)))
 
@@ -1094,11 +1198,13 @@ def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Con
 def composite_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, shot: Optional[abi.Shot], figure_ptr: int,
                                 visibility_ptr: int = 0, reflection_ptr: int = 0, reflection_distance_ptr: int = 0, out_f32_ptr: int = 0,
                                 out_rgba8_ptr: int = 0, in_stride_pixels: Optional[int] = None, out_stride_pixels: Optional[int] = None,
-                                stream: int = 0) -> None:
+                                stream: int = 0, occlusion_ptr: int = 0) -> None:
     """The studio shot's blend alone, on device planes the caller already has (mcrt_composite_shot_batch_device): the
     transparent figure (required, 16 B/pixel), the ground pass's visibility (0: none, no shadow), the reflection pass's rgba
     (0: no mirror image) and distance (0 only with ``shot.reflectionFade == 0``).  Frame i of the inputs starts
-    ``i * in_stride_pixels`` pixels on, of the outputs ``i * out_stride_pixels`` (default width * height)."""
+    ``i * in_stride_pixels`` pixels on, of the outputs ``i * out_stride_pixels`` (default width * height).  With
+    ``shot.floorOcclusion`` > 0 the blend takes the ground-occlusion pass's plane at ``occlusion_ptr`` (4 B/pixel; 0: none)
+    through mcrt_composite_shot_batch_device_occ."""
     handles = _shot_handles(device_scenes)
     if not figure_ptr:
         raise ValueError("figure_ptr is required")
@@ -1111,11 +1217,15 @@ def composite_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: 
         if stride < px:
             raise ValueError(f"{name} {stride} is smaller than width * height = {px}")
         strides.append(stride)
-    s = (shot if shot is not None else abi.Shot()).to_c()
+    s, o = _shot_c(shot)
     n = len(handles)
     arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
     c = config.to_c()
     planes = abi.McrtShotInputs(figure_ptr, visibility_ptr or None, reflection_ptr or None, reflection_distance_ptr or None)
+    if o != 0.0:
+        check(load().mcrt_composite_shot_batch_device_occ(arr, n, C.byref(c), C.byref(s), C.byref(planes), C.c_void_p(occlusion_ptr or None), o, strides[0],
+                                                          C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), strides[1], C.c_void_p(stream)))
+        return
     check(load().mcrt_composite_shot_batch_device(arr, n, C.byref(c), C.byref(s), C.byref(planes), strides[0], C.c_void_p(out_f32_ptr or None),
                                                   C.c_void_p(out_rgba8_ptr or None), strides[1], C.c_void_p(stream)))
 

@@ -892,6 +892,37 @@ int mcrt_render_ground(const mcrt_scene_desc* desc, const mcrt_config* cfg, floa
     return rc;
 }
 
+// ---- ground occlusion: the one-shot host form (render_enqueue.cpp: render_ground_occlusion_batch_device) ------------------------
+int mcrt_render_ground_occlusion(const mcrt_scene_desc* desc, const mcrt_config* cfg, float ground_y, const mcrt_ground_occlusion* out, int device) {
+    if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "both planes are NULL");
+    if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (const int rc = check_ground_occlusion_config(cfg); rc != MCRT_OK) return rc;
+    if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    OneShotScenes set;
+    const mcrt_scene_desc* one[1] = {desc};
+    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
+    if (rc != MCRT_OK) return rc;
+    mcrt_scene* s0 = set.h[0];
+    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
+    // the float plane first: it starts on a 4-byte boundary
+    const size_t occ_bytes = out->occlusion ? px * 4 : 0, matte_bytes = out->matte ? px : 0;
+    hipError_t e = s0->frame.reserve(occ_bytes + matte_bytes);
+    if (e != hipSuccess) return hip_fail(e, "ground occlusion planes");
+    char* base = static_cast<char*>(s0->frame.ptr);
+    mcrt_ground_occlusion d{};
+    d.occlusion = out->occlusion ? reinterpret_cast<float*>(base) : nullptr;
+    d.matte = out->matte ? reinterpret_cast<uint8_t*>(base + occ_bytes) : nullptr;
+    rc = render_ground_occlusion_batch_device(set.h.data(), 1, cfg, &ground_y, &d, px, s0->main_stream);
+    set.download(out->occlusion, d.occlusion, occ_bytes, rc);
+    set.download(out->matte, d.matte, matte_bytes, rc);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, "ground occlusion render");
+    }
+    return rc;
+}
+
 // ---- ground reflection: the one-shot host form (render_enqueue.cpp: render_reflection_batch_device) -----------------------------
 int mcrt_render_reflection(const mcrt_scene_desc* desc, const mcrt_config* cfg, float ground_y, const mcrt_reflection* out, int device) {
     if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
@@ -943,18 +974,26 @@ size_t mcrt_shot_scratch_bytes(const mcrt_config* cfg, const mcrt_shot* shot, in
     return shot_scratch(cfg, shot, n_frames).bytes;
 }
 
-int mcrt_render_shot_batch(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y,
-                           float* out_rgba, uint8_t* out_rgba8, int device) {
+size_t mcrt_shot_scratch_bytes_occ(const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, int n_frames) {
+    if (!cfg || !shot || n_frames <= 0 || !valid_frame(cfg) || shot_frame_too_large(cfg)) return 0;
+    if (check_shot(shot) != MCRT_OK || check_floor_occlusion(floor_occlusion) != MCRT_OK) return 0;
+    return shot_scratch(cfg, shot, n_frames, floor_occlusion).bytes;
+}
+
+// the host forms with and without the floor-occlusion term (the latter: floor_occlusion = 0)
+static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion,
+                                  const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device) {
     // the device form's checks that need no handle, before anything is created
     if (n_frames < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || (n_frames > 0 && (!descs || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n_frames; ++i)
         if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
     if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     for (int i = 0; i < n_frames; ++i)
         if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
     if (!out_rgba && !out_rgba8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
-    if (const int rc = check_shot_config(cfg, shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot_config(cfg, shot, floor_occlusion); rc != MCRT_OK) return rc;
     if (n_frames == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
     if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
     OneShotScenes set;
@@ -963,7 +1002,7 @@ int mcrt_render_shot_batch(const mcrt_scene_desc* const* descs, int n_frames, co
     mcrt_scene* s0 = set.h[0];
     const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
     // the scratch (a multiple of 16 bytes), then the outputs, widest elements first
-    const size_t scratch_bytes = shot_scratch(cfg, shot, n_frames).bytes;
+    const size_t scratch_bytes = shot_scratch(cfg, shot, n_frames, floor_occlusion).bytes;
     const size_t f32_bytes = out_rgba ? px * 16 * static_cast<size_t>(n_frames) : 0;
     const size_t u8_bytes = out_rgba8 ? px * 4 * static_cast<size_t>(n_frames) : 0;
     hipError_t e = s0->frame.reserve(scratch_bytes + f32_bytes + u8_bytes);
@@ -971,7 +1010,7 @@ int mcrt_render_shot_batch(const mcrt_scene_desc* const* descs, int n_frames, co
     char* base = static_cast<char*>(s0->frame.ptr);
     float* d_f32 = out_rgba ? reinterpret_cast<float*>(base + scratch_bytes) : nullptr;
     uint8_t* d_u8 = out_rgba8 ? reinterpret_cast<uint8_t*>(base + scratch_bytes + f32_bytes) : nullptr;
-    rc = render_shot_batch_device(set.h.data(), n_frames, cfg, shot, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream);
+    rc = render_shot_batch_device(set.h.data(), n_frames, cfg, shot, floor_occlusion, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream);
     set.download(out_rgba, d_f32, f32_bytes, rc);
     set.download(out_rgba8, d_u8, u8_bytes, rc);
     if (rc == MCRT_OK) {
@@ -982,6 +1021,16 @@ int mcrt_render_shot_batch(const mcrt_scene_desc* const* descs, int n_frames, co
     return rc;
 }
 
+int mcrt_render_shot_batch(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y,
+                           float* out_rgba, uint8_t* out_rgba8, int device) {
+    return render_shot_batch_host(descs, n_frames, cfg, shot, 0.0f, ground_y, out_rgba, out_rgba8, device);
+}
+
+int mcrt_render_shot_batch_occ(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion,
+                               const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device) {
+    return render_shot_batch_host(descs, n_frames, cfg, shot, floor_occlusion, ground_y, out_rgba, out_rgba8, device);
+}
+
 int mcrt_render_shot(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, float* out_rgba, uint8_t* out_rgba8,
                      int device) {
     if (!desc) return fail(MCRT_ERR_INVALID, "NULL argument");
@@ -989,17 +1038,29 @@ int mcrt_render_shot(const mcrt_scene_desc* desc, const mcrt_config* cfg, const 
     return mcrt_render_shot_batch(one, 1, cfg, shot, &ground_y, out_rgba, out_rgba8, device);
 }
 
-int mcrt_render_shot_png(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, const char* path, int device) {
+static int render_shot_png_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, float ground_y, const char* path,
+                                int device) {
     if (!desc || !cfg || !shot || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
     if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
-    if (const int rc = check_shot_config(cfg, shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot_config(cfg, shot, floor_occlusion); rc != MCRT_OK) return rc;
     if (!valid_frame(cfg)) return fail(MCRT_ERR_INVALID, "empty image");
     if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
     std::vector<uint8_t> host(static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) * 4);
-    const int rc = mcrt_render_shot(desc, cfg, shot, ground_y, nullptr, host.data(), device);
+    const mcrt_scene_desc* one[1] = {desc};
+    const int rc = render_shot_batch_host(one, 1, cfg, shot, floor_occlusion, &ground_y, nullptr, host.data(), device);
     if (rc != MCRT_OK) return rc;
     return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
+}
+
+int mcrt_render_shot_png(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, const char* path, int device) {
+    return render_shot_png_host(desc, cfg, shot, 0.0f, ground_y, path, device);
+}
+
+int mcrt_render_shot_png_occ(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, float ground_y, const char* path,
+                             int device) {
+    return render_shot_png_host(desc, cfg, shot, floor_occlusion, ground_y, path, device);
 }
 
 // ---- light layers: the one-shot host form (render_enqueue.cpp: render_light_batch_device) ----------------------------------------

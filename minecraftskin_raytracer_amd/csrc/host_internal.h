@@ -202,6 +202,7 @@ inline bool valid_background(int b) { return b == MCRT_BACKGROUND_REFERENCE || b
 inline int bad_background() { return fail(MCRT_ERR_INVALID, "background must be MCRT_BACKGROUND_REFERENCE or MCRT_BACKGROUND_TRANSPARENT"); }
 inline bool no_plane(const mcrt_layers* l) { return !l->depth && !l->normal && !l->albedo && !l->id; }
 inline bool no_plane(const mcrt_ground* g) { return !g->visibility && !g->distance && !g->matte; }
+inline bool no_plane(const mcrt_ground_occlusion* g) { return !g->occlusion && !g->matte; }
 inline bool no_plane(const mcrt_reflection* r) { return !r->rgba && !r->rgba8 && !r->distance; }
 inline bool no_plane(const mcrt_light_planes* l) { return !l->visibility && !l->occlusion && !l->direct; }
 // what a light pass refuses of a config (both entry points, before any device work): the truncated engine yields 227 draws — 113
@@ -212,6 +213,16 @@ inline int check_light_config(const mcrt_config* c, const mcrt_light_planes* out
     if (out->occlusion && (c->ao_samples < 1 || c->ao_samples > mcrt::kLightMaxSamples))
         return fail(MCRT_ERR_INVALID, "the occlusion plane takes 1 to 113 ao_samples (the truncated engine's 227 draws, two per sample)");
     if (out->occlusion && !std::isfinite(c->ao_radius)) return fail(MCRT_ERR_INVALID, "ao_radius must be finite");
+    return MCRT_OK;
+}
+
+// what a ground-occlusion pass refuses of a config (every entry point, before any device work): computeAO divides by ao_samples,
+// and the truncated engine yields 227 draws, two per sample
+inline int check_ground_occlusion_config(const mcrt_config* c) {
+    if (c->ao_samples < 1) return fail(MCRT_ERR_INVALID, "a ground-occlusion pass takes at least 1 of ao_samples (the reference divides by it)");
+    if (c->ao_samples > mcrt::kLightMaxSamples)
+        return fail(MCRT_ERR_INVALID, "a ground-occlusion pass takes at most 113 ao_samples (the truncated engine's 227 draws, two per sample)");
+    if (!std::isfinite(c->ao_radius)) return fail(MCRT_ERR_INVALID, "ao_radius must be finite");
     return MCRT_OK;
 }
 
@@ -237,24 +248,30 @@ inline int check_shot(const mcrt_shot* s) {
         if (!std::isfinite(c)) return fail(MCRT_ERR_INVALID, "page_color must be finite");
     return MCRT_OK;
 }
+// the strength of the floor-occlusion term (the _occ entry points)
+inline int check_floor_occlusion(float o) {
+    if (!(o >= 0.0f && o <= 1.0f)) return fail(MCRT_ERR_INVALID, "floor_occlusion must lie in [0, 1]");
+    return MCRT_OK;
+}
 // and of the config of a shot that renders: the render's limit, and the limits of the passes the shot runs
 int validate_config(const mcrt_config* cfg);
-inline int check_shot_config(const mcrt_config* c, const mcrt_shot* s) {
+inline int check_shot_config(const mcrt_config* c, const mcrt_shot* s, float floor_occlusion = 0.0f) {
     if (validate_config(c) != MCRT_OK) return MCRT_ERR_INVALID;
     const bool ground = s->shadow_strength > 0.0f, mirror = s->reflectivity > 0.0f;
     if ((ground || mirror) && c->soft_shadows && c->shadow_samples > mcrt::kGroundMaxSamples)
         return fail(MCRT_ERR_INVALID, "a shot with a shadow or a reflection takes at most 113 shadow samples (the truncated engine's 227 draws)");
     if (mirror && c->max_bounces > mcrt::kReflectMaxBounces)
         return fail(MCRT_ERR_INVALID, "a shot with a reflection takes at most 8 bounces (the reflection pass's per-lane colour stack)");
+    if (floor_occlusion > 0.0f) return check_ground_occlusion_config(c);
     return MCRT_OK;
 }
 inline bool shot_frame_too_large(const mcrt_config* c) { return static_cast<long long>(c->width) * c->height >= (1ll << 31); }
 // The scratch of a shot that renders (include/mcrt.h): the planes it needs, each for n frames and each on a 16-byte boundary.
-// Offsets of the absent planes are SIZE_MAX.
+// Offsets of the absent planes are SIZE_MAX.  The floor-occlusion plane lies behind the others, so they keep their offsets.
 struct ShotScratch {
-    size_t figure = 0, reflection = SIZE_MAX, visibility = SIZE_MAX, distance = SIZE_MAX, bytes = 0;
+    size_t figure = 0, reflection = SIZE_MAX, visibility = SIZE_MAX, distance = SIZE_MAX, occlusion = SIZE_MAX, bytes = 0;
 };
-inline ShotScratch shot_scratch(const mcrt_config* c, const mcrt_shot* s, int n) {
+inline ShotScratch shot_scratch(const mcrt_config* c, const mcrt_shot* s, int n, float floor_occlusion = 0.0f) {
     ShotScratch l;
     const size_t px = static_cast<size_t>(c->width) * static_cast<size_t>(c->height) * static_cast<size_t>(n);
     auto place = [&](size_t px_bytes) {
@@ -266,6 +283,7 @@ inline ShotScratch shot_scratch(const mcrt_config* c, const mcrt_shot* s, int n)
     if (s->reflectivity > 0.0f) l.reflection = place(16);
     if (s->shadow_strength > 0.0f) l.visibility = place(4);
     if (s->reflectivity > 0.0f && s->reflection_fade > 0.0f) l.distance = place(4);
+    if (floor_occlusion > 0.0f) l.occlusion = place(4);
     return l;
 }
 
@@ -332,16 +350,20 @@ int render_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg
 int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_layers* d_out, size_t stride, hipStream_t stream);
 int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_ground* d_out, size_t stride,
                                hipStream_t stream);
+int render_ground_occlusion_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_ground_occlusion* d_out,
+                                         size_t stride, hipStream_t stream);
 int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_reflection* d_out,
                                    size_t stride, hipStream_t stream);
 int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes* d_out, size_t stride, hipStream_t stream);
 int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream);
-// the studio shot's blend on the caller's planes (mcrt_composite_shot_batch_device), and render + ground + reflection + blend on
-// `stream` in order with the planes in the caller's scratch (mcrt_render_shot_batch_device)
-int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in, size_t in_stride,
-                                float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream);
-int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y, void* d_scratch,
-                             size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream);
+// the studio shot's blend on the caller's planes (mcrt_composite_shot_batch_device[_occ]), and render + ground + reflection +
+// ground occlusion + blend on `stream` in order with the planes in the caller's scratch (mcrt_render_shot_batch_device[_occ]);
+// the entries without the floor-occlusion term pass floor_occlusion = 0 and no plane
+int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
+                                const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride,
+                                hipStream_t stream);
+int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, const float* ground_y,
+                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 // gives the n repaintable handles the views (poses[i], looks[i]); NULL poses, looks or looks[i]: the handle's own

@@ -12,7 +12,7 @@
 // Verification hooks.  tools/decide_check.sh builds a variant of the library with -DMCRT_KERNEL_HOOKS='"decide_check_hooks.h"'
 // (tools/decide_check_hooks.h: every record `lit` decides is traced as well and contradictions are counted and printed);
 // the product build compiles the hooks to nothing.  tools/gpu_ground.py builds another variant with tools/ground_class_hooks.h
-// (the ground pass's hook: pass_kernels.hip).
+// (the ground pass's hook: pass_kernels.hip), tools/gpu_ground_occlusion.py one with tools/ground_occlusion_class_hooks.h.
 #ifdef MCRT_KERNEL_HOOKS
 #include MCRT_KERNEL_HOOKS
 #else

@@ -282,6 +282,35 @@ int ground_batch_view(GroundFrame* frames, const int* views, int n);
 // dynamic LDS of a launch: the frame's scene tables, then the block's area (masks, points, counts and sample positions)
 size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape);
 
+// ---- ground occlusion (mcrt_render_ground_occlusion_device & co): the figure's contact occlusion on the plane y = ground_y — per
+// pixel the ground pass's ray and point P, and computeAO(P, (0, 1, 0)) with the seed the reference forms for a hit at P.  Reads
+// the scene blob and, where the handle holds it, the device's table of all seeds.
+// One frame of a ground-occlusion pass: its scene, its height and its planes (either may be NULL, not both)
+struct GroundOcclusionFrame {
+    const uint8_t* scene;
+    float* occlusion;                 // 1 float per pixel: 1 - occluded / ao_samples; 1.0f where the ray misses the plane
+    uint8_t* matte;                   // quantised 1 - occlusion: the alpha of a black contact-shadow image
+    const uint32_t* seed_table_full;  // the device's table of all seeds where a render has built it, or NULL: the recurrence
+    float ground_y;
+    int lds_alpha_words;              // scene tables staged in LDS, as LayersFrame's
+    int lds_face_entries;
+};
+// what the frames of one launch share
+struct GroundOcclusionShape {
+    LayersShape tiles;  // the frame's size and its tile grid, as a layers pass cuts it
+    int ao_samples;     // A: 1 .. kLightMaxSamples
+    float ao_radius;    // <= 0: nothing is traced
+    int pass;           // traced pixels whose A directions fit the block's LDS area at once
+    int inside_fast;    // as RenderParams'
+};
+// false when the frame holds more units than the kernels index (2^31)
+bool make_ground_occlusion_shape(const mcrt_config& cfg, bool inside_fast, GroundOcclusionShape& shape);
+// fills f.lds_* and returns the kernel variant by the layers' rule
+int ground_occlusion_view(GroundOcclusionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
+int ground_occlusion_batch_view(GroundOcclusionFrame* frames, const int* views, int n);
+// dynamic LDS of a launch: the frame's scene tables, then the block's area (masks, points, counts, the traced list and directions)
+size_t ground_occlusion_lds_bytes(const GroundOcclusionFrame& f, const GroundOcclusionShape& shape);
+
 // ---- ground reflection (mcrt_render_reflection_device & co): the figure mirrored in the plane y = ground_y — per pixel the
 // pixel-centre ray of the layers, its point P on the plane, the reference's reflection ray for a hit at P with normal (0, 1, 0),
 // and traceRay(that ray, depth 1): shading, shadows and further bounces as the reference's recursion runs them below a depth-0
@@ -444,6 +473,7 @@ struct ShotFrame {
     const float* visibility;  // 1 float per pixel: the ground pass's; NULL: 1.0f everywhere
     const float* reflection;  // 4 floats per pixel: the reflection pass's rgba; NULL: (0, 0, 0, 0) everywhere
     const float* distance;    // 1 float per pixel: the reflection pass's; read only with reflection_fade > 0
+    const float* occlusion;   // 1 float per pixel: the ground-occlusion pass's; NULL: 1.0f everywhere
     float* out;               // 4 floats per pixel
     uint8_t* out8;            // RGBA8, quantised as mcrt_quantize_rgba8 quantises it
 };
@@ -453,6 +483,7 @@ struct ShotShape {
     int page;  // MCRT_PAGE_*
     float page_color[3];
     float shadow_strength, reflectivity, reflection_fade;
+    float floor_occlusion;  // o, 0..1: read only where a frame has an occlusion plane
 };
 
 // ======== pipeline launches (render_kernels.hip) ========
@@ -482,7 +513,7 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
-// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground reflection, light layers, light bake, studio shot, skin repaints, views ========
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground occlusion, ground reflection, light layers, light bake, studio shot, skin repaints, views ========
 hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's LDS tables
@@ -493,6 +524,11 @@ hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int vie
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's ground_lds_bytes
 hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream);
+hipError_t launch_ground_occlusion(const GroundOcclusionFrame& f, const GroundOcclusionShape& shape, int view, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
+// frame's ground_occlusion_lds_bytes
+hipError_t launch_ground_occlusion_batch(const GroundOcclusionFrame* d_table, int n_frames, const GroundOcclusionShape& shape, int view, size_t max_dyn,
+                                         hipStream_t stream);
 hipError_t launch_reflection(const ReflectionFrame& f, const ReflectionShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's reflection_lds_bytes

@@ -49,6 +49,8 @@ __host__ __device__ __forceinline__ size_t scene_tables_lds_bytes(int face_entri
 constexpr int kLayersGrid = 8192;  // layers and ground: workgroups per frame at most (the kernels stride over their units)
 constexpr int kGroundPosBytes = 12 * 1024;  // ground: LDS for the sample positions of the undecided pixels of one pass
 constexpr int kGroundFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // ground: candidate and inside masks, P.x / P.z, lit counts, the undecided list
+constexpr int kGroundOccDirBytes = 12 * 1024;  // ground occlusion: LDS for the A directions of the traced pixels of one pass
+constexpr int kGroundOccFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // ground occlusion: candidate and inside masks, P.x / P.z, occluded counts, the traced list
 constexpr int kReflectPosBytes = 8 * 1024;  // reflection: LDS for the sample positions of the undecided level-1 hits of one pass
 // reflection: per lane a hit record of four float4 (point, normal, texel colour, ray), candidate and inside masks, lit counts, the undecided list
 constexpr int kReflectFixedBytes = kBlock * (64 + 8 + 8 + 4 + 4);

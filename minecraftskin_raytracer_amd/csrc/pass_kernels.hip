@@ -1,5 +1,5 @@
 // pass_kernels.hip — the stand-alone passes over a resident scene (not stages of a render): geometry layers and pixel
-// picks, the ground shadow, the ground reflection, the light layers, the light bake, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
+// picks, the ground shadow, the ground occlusion, the ground reflection, the light layers, the light bake, skin repaints.  They share scene staging and tile geometry with the pipeline (kernel_common.h)
 // and nothing else: no workspace, no counters.
 #include "kernel_common.h"
 
@@ -7,6 +7,12 @@
 // class (missed, culled by tile, decided, traced) into its visibility plane
 #ifndef MCRT_HOOK_GROUND_PIXEL
 #define MCRT_HOOK_GROUND_PIXEL(vis, reached, culled, undecided)
+#endif
+
+// the ground-occlusion pass's hook: tools/ground_occlusion_class_hooks.h makes the pass write every pixel's class (missed, culled by
+// tile, without a candidate, traced) into its occlusion plane
+#ifndef MCRT_HOOK_GROUND_OCCLUSION_PIXEL
+#define MCRT_HOOK_GROUND_OCCLUSION_PIXEL(occ, reached, culled, traced)
 #endif
 
 namespace mcrt {
@@ -513,6 +519,262 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void ground_batch_kernel(Grou
     ground_body<kView>(*(const GroundFrame*)(table + blockIdx.y), sh);
 }
 
+// the unit's tile, and this lane's pixel in it
+struct UnitPixel {
+    TileGeom tg;
+    bool valid;
+    int px, py;
+    size_t idx;
+};
+__device__ __forceinline__ bool unit_pixel(const LayersShape& tiles, const int unit, const int tid, UnitPixel& up) {
+    const mcrt_config& cfg = tiles.cfg;
+    const int tile = unit / tiles.parts, part = unit - tile * tiles.parts;
+    const int tyi = tile / tiles.tiles_x, txi = tile - tyi * tiles.tiles_x;
+    TileGeom& tg = up.tg;
+    tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+    tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+    tg.owned_row = tyi, tg.frame_tile = tile;
+    const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+    const unsigned p0 = static_cast<unsigned>(part) * kBlock;
+    if (p0 >= npix) return false;  // a clipped edge tile holds fewer units
+    const unsigned pix = p0 + static_cast<unsigned>(tid);
+    up.valid = pix < npix;
+    const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(up.valid ? pix : 0u);
+    up.py = tg.y + static_cast<int>(uly), up.px = tg.x + static_cast<int>((up.valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+    up.idx = static_cast<size_t>(up.py) * static_cast<size_t>(cfg.width) + static_cast<size_t>(up.px);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// ground occlusion (kernels.h: GroundOcclusionFrame): the figure's contact occlusion on the plane y = ground_y, as planes of their
+// own.  Per pixel the ground pass's ray and point P, and computeAO(P, (0, 1, 0)) (raytracer.cpp:38-78) with the seed of a hit at P
+// (raytracer.cpp:122-123).  No workspace.  Only the pixels within ao_radius of a box are traced — a few per cent of a frame — so
+// the rays, not the pixels, are spread over the lanes:
+//   a workgroup per 256 pixels of a screen tile (grid-stride), in the phases of the ground pass, handed over through LDS:
+//   1 lane / mesh (every wave)   which meshes an AO ray from ANY ground point under the tile can meet (ground_occlusion_tile_mask):
+//                                none for most tiles of a frame — their pixels are unoccluded without a point or a ray
+//   1 lane / pixel               ray, plane hit, P; the meshes a ray of its hemisphere can meet within the radius
+//                                (rt::hemisphere_candidates) among the tile's; the pixels with one are packed
+//   1 lane / traced pixel        truncated mt19937 (mt[397] from the table of all seeds where the handle has it) → 2·A draws → the
+//                                A world directions in LDS
+//   1 lane / (traced pixel, sample)   exact any-hit test within the radius on the candidates → occluded count by ballot
+//   1 lane / pixel               occlusion = 1 - occluded / A, matte: coalesced stores, 16 bytes per four pixels of a row where
+//                                the rows allow
+// ---------------------------------------------------------------------------------------------
+// The meshes an AO ray of the tile can meet, conservatively: lane m of the calling wave tests mesh m.  The ground points of the
+// tile lie in the bounding rectangle F of its four corner points, as for ground_tile_mask.  A ray leaves O = Q + (0, 1e-3, 0),
+// never downwards (its y component is sqrt(r1) >= 0 before and after the normalisation), and is cut at `radius`: it meets a
+// mesh's world box B (bounding sphere when posed) only at a point within radius of O and not below it.  So Q lies within
+// Rr = radius * 1.001 + slack of B on x and z, B reaches up to the origins' height gy = g + 1e-3 and starts below gy + Rr.  A
+// mesh that misses one of these, with margins far above the float error of the points (2e-3 of the footprint's reach, 16
+// slacks; 64 slacks and 1e-5 of the heights on y), occludes no pixel of the tile.  Every other case keeps the mesh: a corner
+// that misses the plane or grazes it, 64 meshes or more, cull_ok == 0, a negative sphere radius, non-finite values (every
+// comparison is written to fail open).
+__device__ __forceinline__ unsigned long long ground_occlusion_tile_mask(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect,
+                                                                         const float g, const float radius, const int lane) {
+    const int n = sc.n_meshes;
+    if (n <= 0) return 0ull;
+    const unsigned long long all = n < 64 ? (1ull << n) - 1ull : ~0ull;
+    if (sc.hdr->cull_ok == 0 || n >= 64) return all;
+    const float slack = sc.hdr->mask_slack;
+    float fx0 = kFltMax, fx1 = -kFltMax, fz0 = kFltMax, fz1 = -kFltMax, reach = 0.0f;
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float fx = static_cast<float>(tg.x + ((c & 1) ? tg.w : 0)), fy = static_cast<float>(tg.y + ((c & 2) ? tg.h : 0));
+        const Ray ray = camera_ray(sc, fx / static_cast<float>(cfg.width), fy / static_cast<float>(cfg.height), aspect);
+        const float t = (g - ray.o.y) / ray.d.y;
+        ok = ok && __builtin_fabsf(ray.d.y) >= 1e-2f && t > 0.0f && t < 1e30f;
+        const float dx = ray.d.x * t, dz = ray.d.z * t;
+        const float x = ray.o.x + dx, z = ray.o.z + dz;
+        fx0 = __builtin_fminf(fx0, x), fx1 = __builtin_fmaxf(fx1, x), fz0 = __builtin_fminf(fz0, z), fz1 = __builtin_fmaxf(fz1, z);
+        reach = __builtin_fmaxf(reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dz)), t));
+        ok = ok && x == x && z == z;  // (fmin / fmax drop a NaN)
+    }
+    const float Rr = radius * 1.001f + slack;
+    ok = ok && reach < 1e30f && slack < 1e30f && Rr < 1e30f;
+    if (!ok) return all;
+    const float fm = 2e-3f * reach + 16.0f * slack;
+    const float gy = g + 1e-3f;  // the AO rays' origins
+    bool touch = lane < n;
+    if (touch) {
+        const FlatMesh& m = sc.meshes[lane];
+        if (m.flags & MESH_EMPTY) {
+            touch = false;  // intersection.cpp:205: never hit
+        } else {
+            V3 lo = ld3(m.lo), hi = ld3(m.hi);
+            bool bounded = true;
+            if (m.flags & MESH_ROTATED) {
+                const float r = m.sphere[3];
+                bounded = r >= 0.0f;
+                lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
+                hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
+            }
+            if (bounded) {
+                const float mx = fm + 1e-4f * (__builtin_fabsf(lo.x) + __builtin_fabsf(hi.x) + __builtin_fabsf(lo.z) + __builtin_fabsf(hi.z));
+                const float my = 64.0f * slack + 1e-5f * (__builtin_fabsf(gy) + __builtin_fabsf(lo.y) + __builtin_fabsf(hi.y));
+                const bool out = (hi.y < gy - my) | (lo.y > gy + Rr + my) | (hi.x + Rr + mx < fx0) | (lo.x - Rr - mx > fx1) | (hi.z + Rr + mx < fz0) |
+                                 (lo.z - Rr - mx > fz1);
+                touch = !out;
+            }
+        }
+    }
+    return __ballot(touch);
+}
+template <int kView>
+__device__ __forceinline__ void ground_occlusion_body(const GroundOcclusionFrame& __restrict__ f, const GroundOcclusionShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks][inside masks][P.x, P.z][occluded counts][traced list][directions: pass x A x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.tiles.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const float g = f.ground_y;
+    const int A = sh.ao_samples;
+    const float radius = sh.ao_radius;
+    const bool live = radius > 0.0f;  // otherwise no ray can be occluded
+    const uint32_t rays = static_cast<uint32_t>(A);  // rays per traced pixel
+    const bool pow2 = (rays & (rays - 1u)) == 0u && rays <= 64u;
+    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    const V3 N = mk(0.0f, 1.0f, 0.0f);
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
+    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(area);
+    unsigned long long* s_ins = s_cand + kBlock;
+    float2* s_pxz = reinterpret_cast<float2*>(s_ins + kBlock);
+    uint32_t* s_occ = reinterpret_cast<uint32_t*>(s_pxz + kBlock);
+    uint32_t* s_list = s_occ + kBlock;
+    float* s_dir = reinterpret_cast<float*>(s_list + kBlock);
+    // four neighbouring pixels of a row per store: every tile row starts and ends on a four-pixel boundary of the plane
+    const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
+    const bool quads_occ = quad_rows && (reinterpret_cast<uintptr_t>(f.occlusion) & 15u) == 0;
+    const bool quads_matte = quad_rows && (reinterpret_cast<uintptr_t>(f.matte) & 3u) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * sh.tiles.parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        UnitPixel up;
+        if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
+        const unsigned long long mask = live ? ground_occlusion_tile_mask(scg, cfg, up.tg, aspect, g, radius, lane) : 0ull;  // the same in every wave of the workgroup
+        if (mask != 0ull && !staged) {
+            if constexpr (kView == kViewHbm) {
+                sc = scg;
+            } else {
+                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
+                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
+            }
+            staged = true;
+        }
+        uint32_t occluded = 0u;  // a pixel that misses the plane or has no candidate, and every pixel of a tile no mesh can occlude
+        bool traced = false;
+#ifdef MCRT_KERNEL_HOOKS
+        const bool reached = up.valid && ground_point(scg, cfg, aspect, g, static_cast<float>(up.px) + 0.5f, static_cast<float>(up.py) + 0.5f).reached;
+#endif
+        if (mask != 0ull) {  // uniform
+            // ---- a lane per pixel: the plane point and the meshes its hemisphere can meet
+            if (up.valid) {
+                const GroundPoint gp = ground_point(scg, cfg, aspect, g, static_cast<float>(up.px) + 0.5f, static_cast<float>(up.py) + 0.5f);
+                if (gp.reached) {
+                    const V3 O = gp.P + N * 1e-3f;
+                    const unsigned long long cand = hemisphere_candidates<kPosed>(scg, O, N, radius) & mask;
+                    traced = cand != 0ull || scg.n_meshes > 64;  // meshes beyond the mask are tested per ray
+                    if (traced) {
+                        s_cand[tid] = cand;
+                        s_ins[tid] = sh.inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the pixel starts there
+                        s_pxz[tid] = make_float2(gp.P.x, gp.P.z);
+                    }
+                }
+            }
+            s_occ[tid] = 0u;
+            int total = 0;
+            const int rank = block_rank(traced, s_wcnt, total);
+            if (traced) s_list[rank] = static_cast<uint32_t>(tid);
+            const uint32_t n_traced = static_cast<uint32_t>(total);
+            if (n_traced) __syncthreads();  // uniform
+            for (uint32_t u0 = 0; u0 < n_traced; u0 += pass) {  // uniform
+                const uint32_t nu = min(pass, n_traced - u0);
+                if (u0) __syncthreads();  // the previous pass's rays have read the directions
+                // ---- a lane per traced pixel: its mt19937 stream and the A directions (raytracer.cpp:42-68)
+                if (static_cast<uint32_t>(tid) < nu) {
+                    const float2 xz = s_pxz[s_list[u0 + tid]];
+                    const V3 P = mk(xz.x, g, xz.y);
+                    const V3 T = (__builtin_fabsf(N.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), N)) : normalize(cross(mk(0, 1, 0), N));
+                    const V3 B = cross(N, T);
+                    MtShort rng;
+                    const uint32_t seed = ao_seed(P);
+                    if (f.seed_table_full)
+                        rng.seed_known(seed, f.seed_table_full[seed]);  // mt[397] of this seed: one load instead of the 397-step recurrence
+                    else
+                        rng.seed(seed);
+                    float* dst = s_dir + static_cast<size_t>(tid) * 3 * rays;
+                    for (int i = 0; i < A; ++i) {
+                        const float r1 = rng.uniform();
+                        const float r2 = rng.uniform();
+                        const float sinT = sqrt_pos(1.0f - r1);
+                        const float cosT = sqrt_pos(r1);
+                        float sn, cs;
+                        mcrt_sincosf(kTwoPi * r2, &sn, &cs);
+                        const V3 local = mk(sinT * cs, cosT, sinT * sn);
+                        const V3 world = normalize(T * local.x + N * local.y + B * local.z);
+                        dst[3 * i + 0] = world.x;
+                        dst[3 * i + 1] = world.y;
+                        dst[3 * i + 2] = world.z;
+                    }
+                }
+                __syncthreads();
+                // ---- a lane per (traced pixel, sample); every lane of a wave runs the same number of turns (ballot inside)
+                const uint32_t n_rays = nu * rays;
+                for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
+                    const uint32_t q = q0 + static_cast<uint32_t>(lane);
+                    bool blocked = false;
+                    uint32_t k = 0;
+                    if (q < n_rays) {
+                        k = s_list[u0 + q / rays];
+                        const float2 xz = s_pxz[k];
+                        const V3 O = mk(xz.x, g, xz.y) + N * 1e-3f;
+                        blocked = any_hit_masked(sc, Ray{O, ld3(s_dir + static_cast<size_t>(q) * 3)}, radius, s_cand[k], s_ins[k]);
+                    }
+                    if (pow2) {
+                        const unsigned long long bal = __ballot(blocked);
+                        if (q < n_rays && (static_cast<uint32_t>(lane) & (rays - 1u)) == 0u) {
+                            const unsigned long long grp = (rays == 64u) ? bal : ((bal >> lane) & ((1ull << rays) - 1ull));
+                            s_occ[k] = static_cast<uint32_t>(__popcll(grp));
+                        }
+                    } else if (blocked) {
+                        atomicAdd(&s_occ[k], 1u);
+                    }
+                }
+            }
+            // the counts are complete; behind this barrier nothing of the unit is read across lanes any more, so the next
+            // unit may overwrite the area
+            if (n_traced) __syncthreads();
+            if (traced) occluded = s_occ[tid];
+        }
+        // ---- a lane per pixel: the planes
+        float occ = 1.0f - static_cast<float>(occluded) / static_cast<float>(A);  // raytracer.cpp:77
+        MCRT_HOOK_GROUND_OCCLUSION_PIXEL(occ, reached, mask == 0ull, traced)
+        if (f.occlusion) store_plane(f.occlusion, quads_occ, up.valid, lane, up.idx, occ);
+        if (f.matte) {
+            const uint32_t a = static_cast<unsigned char>(sclamp(1.0f - occ, 0.0f, 1.0f) * 255.0f + 0.5f);
+            if (quads_matte) {
+                const uint32_t a1 = __shfl_down(a, 1), a2 = __shfl_down(a, 2), a3 = __shfl_down(a, 3);
+                if (up.valid && (lane & 3) == 0) *reinterpret_cast<uint32_t*>(f.matte + up.idx) = a | (a1 << 8) | (a2 << 16) | (a3 << 24);
+            } else if (up.valid) {
+                f.matte[up.idx] = static_cast<uint8_t>(a);
+            }
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_occlusion_kernel(const GroundOcclusionFrame f, const GroundOcclusionShape sh) {
+    ground_occlusion_body<kView>(f, sh);
+}
+using GroundOcclusionTable = const __attribute__((address_space(4))) GroundOcclusionFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void ground_occlusion_batch_kernel(GroundOcclusionTable table, const GroundOcclusionShape sh) {
+    ground_occlusion_body<kView>(*(const GroundOcclusionFrame*)(table + blockIdx.y), sh);
+}
+
 // ---------------------------------------------------------------------------------------------
 // ground reflection (kernels.h: ReflectionFrame): the figure mirrored in the plane y = ground_y, as planes of their own.  Per
 // pixel the layers' pixel-centre ray, its point P on the plane, the reference's reflection ray for a hit at P with normal
@@ -861,31 +1123,6 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void reflection_batch_kernel(
 //   1 lane / packed hit          truncated mt19937 (mt[397] from the device's table of all seeds where a render has built it,
 //                                else the recurrence), A cosine-weighted directions, the any-hit test, the count in a register
 // ---------------------------------------------------------------------------------------------
-// the unit's tile, and this lane's pixel in it
-struct UnitPixel {
-    TileGeom tg;
-    bool valid;
-    int px, py;
-    size_t idx;
-};
-__device__ __forceinline__ bool unit_pixel(const LayersShape& tiles, const int unit, const int tid, UnitPixel& up) {
-    const mcrt_config& cfg = tiles.cfg;
-    const int tile = unit / tiles.parts, part = unit - tile * tiles.parts;
-    const int tyi = tile / tiles.tiles_x, txi = tile - tyi * tiles.tiles_x;
-    TileGeom& tg = up.tg;
-    tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
-    tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
-    tg.owned_row = tyi, tg.frame_tile = tile;
-    const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
-    const unsigned p0 = static_cast<unsigned>(part) * kBlock;
-    if (p0 >= npix) return false;  // a clipped edge tile holds fewer units
-    const unsigned pix = p0 + static_cast<unsigned>(tid);
-    up.valid = pix < npix;
-    const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(up.valid ? pix : 0u);
-    up.py = tg.y + static_cast<int>(uly), up.px = tg.x + static_cast<int>((up.valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
-    up.idx = static_cast<size_t>(up.py) * static_cast<size_t>(cfg.width) + static_cast<size_t>(up.px);
-    return true;
-}
 // the pixel-centre ray's closest hit among the meshes of mesh_mask
 template <class SV>
 __device__ __forceinline__ Hit pixel_hit(const SceneView& scg, const SV& sc, const mcrt_config& cfg, const float aspect, const int px, const int py,
@@ -1577,11 +1814,12 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void bake_occlusion_batch_ker
 // carries the ground shadow and the floor reflection — as one streaming pass.  No scene geometry, no LDS, no atomics:
 //   1 lane / pixel (grid-stride over the frame's pixels, blockIdx.y = frame)
 //     figure and reflection rgba   one 16-byte load each where the plane is 16-byte aligned, else four 4-byte loads
-//     visibility and distance      one 4-byte load each: 256 contiguous bytes per wave (the planes have pixel granularity)
+//     visibility, distance and floor occlusion   one 4-byte load each: 256 contiguous bytes per wave (the planes have pixel
+//                                  granularity); the occlusion only where the frame has that plane
 //     page                         the constant, or rt::background at the pixel centre — u, v by IEEE division
 //     out                          one 16-byte store (four 4-byte ones for a plane off a 16-byte boundary) and / or 4 bytes
 //                                  of RGBA8 (byte stores for a plane off a 4-byte boundary)
-// At most 40 B read and 20 B written per pixel.  The arithmetic is the header's, in its order, one rounding per operation; an
+// At most 44 B read and 20 B written per pixel.  The arithmetic is the header's, in its order, one rounding per operation; an
 // absent input enters with its miss constant (visibility 1, reflection (0,0,0,0)) through the same operations, which is why a
 // shot that skips a pass equals one that ran it.
 // ---------------------------------------------------------------------------------------------
@@ -1624,7 +1862,9 @@ __device__ __forceinline__ void shot_body(const ShotFrame& __restrict__ f, const
             fd = sclamp(1.0f - dR / fade, 0.0f, 1.0f);
         }
         const float ar = (k * R.w) * fd;
-        const float keep = (1.0f - shade) * (1.0f - ar);
+        float keep = 1.0f - shade;
+        if (f.occlusion) keep = keep * (1.0f - sh.floor_occlusion * (1.0f - f.occlusion[i]));  // absent: oc = +0, and x * 1.0f is x
+        keep = keep * (1.0f - ar);
         const float under = 1.0f - F.w;
         float4 o;
         o.x = F.x * F.w + (pr * keep + R.x * ar) * under;
@@ -1683,6 +1923,22 @@ hipError_t launch_ground(const GroundFrame& f, const GroundShape& shape, int vie
 }
 hipError_t launch_ground_batch(const GroundFrame* d_table, int n_frames, const GroundShape& shape, int view, size_t max_dyn, hipStream_t stream) {
     return launch_tile_pass(GroundTable(d_table), n_frames, shape, shape.tiles, view, max_dyn, max_dyn, stream, [](auto v) { return ground_batch_kernel<decltype(v)::value>; });
+}
+// ---- ground occlusion (kernels.h): as the ground pass, the HBM variant keeps the block's area in dynamic LDS ---------------
+static bool ground_occlusion_shape_ok(const GroundOcclusionShape& sh) {  // what the draws and the LDS area are laid out for
+    return sh.ao_samples >= 1 && sh.ao_samples <= kLightMaxSamples && sh.pass >= 1 && sh.pass <= kBlock &&
+           static_cast<size_t>(sh.pass) * sh.ao_samples * 12 <= static_cast<size_t>(kGroundOccDirBytes);
+}
+hipError_t launch_ground_occlusion(const GroundOcclusionFrame& f, const GroundOcclusionShape& shape, int view, hipStream_t stream) {
+    if (!ground_occlusion_shape_ok(shape)) return hipErrorInvalidValue;
+    const size_t dyn = ground_occlusion_lds_bytes(f, shape);
+    return launch_tile_pass(f, 1, shape, shape.tiles, view, dyn, dyn, stream, [](auto v) { return ground_occlusion_kernel<decltype(v)::value>; });
+}
+hipError_t launch_ground_occlusion_batch(const GroundOcclusionFrame* d_table, int n_frames, const GroundOcclusionShape& shape, int view, size_t max_dyn,
+                                         hipStream_t stream) {
+    if (!ground_occlusion_shape_ok(shape)) return hipErrorInvalidValue;
+    return launch_tile_pass(GroundOcclusionTable(d_table), n_frames, shape, shape.tiles, view, max_dyn, max_dyn, stream,
+                            [](auto v) { return ground_occlusion_batch_kernel<decltype(v)::value>; });
 }
 // ---- ground reflection (kernels.h): as the ground pass, the HBM variant keeps the block's area in dynamic LDS --------------
 hipError_t launch_reflection(const ReflectionFrame& f, const ReflectionShape& shape, int view, hipStream_t stream) {

@@ -452,6 +452,17 @@ int ground_frame_of(const mcrt_scene* s, const mcrt_ground& out, float ground_y,
     f.ground_y = ground_y;
     return ground_view(f, s->alpha_words, s->n_meshes, s->posed);
 }
+// and for a ground-occlusion pass (mcrt_render_ground_occlusion_device & co), which reads the table of all seeds where the handle holds it
+int ground_occlusion_frame_of(const mcrt_scene* s, const mcrt_ground_occlusion& out, float ground_y, size_t index, size_t stride, GroundOcclusionFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.occlusion = out.occlusion ? out.occlusion + off : nullptr;
+    f.matte = out.matte ? out.matte + off : nullptr;
+    f.seed_table_full = s->seed_table_full;
+    f.ground_y = ground_y;
+    return ground_occlusion_view(f, s->alpha_words, s->n_meshes, s->posed);
+}
 // and for a reflection pass (mcrt_render_reflection_device & co)
 int reflection_frame_of(const mcrt_scene* s, const mcrt_reflection& out, float ground_y, size_t index, size_t stride, ReflectionFrame& f) {
     std::memset(&f, 0, sizeof f);
@@ -790,6 +801,40 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
         [&](const GroundFrame* d_table, int m) { return launch_ground_batch(d_table, m, shape, view, dyn, stream); });
 }
 
+// ---- ground occlusion (mcrt_render_ground_occlusion_device & co): the ground pass's host path with another kernel — the scene
+// blob and, where an ambient-occlusion render has built it, the device's table of all seeds (the pass never builds it); no
+// workspace, no counters and none of the handle's events
+int render_ground_occlusion_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_ground_occlusion* d_out,
+                                         size_t stride, hipStream_t stream) {
+    // argument checks, before any device work
+    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "both planes are NULL");
+    if (n > 0 && !ground_y) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (cfg)
+        if (const int rc = check_ground_occlusion_config(cfg); rc != MCRT_OK) return rc;
+    bool run;
+    int device = 0;
+    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");  // the development knob of `lit` (prepare)
+    GroundOcclusionShape shape;
+    if (!make_ground_occlusion_shape(*cfg, inside_fast, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(device));
+    std::vector<GroundOcclusionFrame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        share_full_seed_table(scenes[i]);
+        views[static_cast<size_t>(i)] =
+            ground_occlusion_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
+    }
+    const int view = ground_occlusion_batch_view(frames.data(), views.data(), n);
+    size_t dyn = 0;
+    for (const GroundOcclusionFrame& f : frames) dyn = std::max(dyn, ground_occlusion_lds_bytes(f, shape));
+    return launch_pass(
+        device, frames, stream, "ground occlusion launches", [&](const GroundOcclusionFrame& f) { return launch_ground_occlusion(f, shape, view, stream); },
+        [&](const GroundOcclusionFrame* d_table, int m) { return launch_ground_occlusion_batch(d_table, m, shape, view, dyn, stream); });
+}
+
 // ---- ground reflection (mcrt_render_reflection_device & co): the ground pass's host path with another kernel — the scene blob
 // and the device's seed table, no workspace, no counters and none of the handle's events
 int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const float* ground_y, const mcrt_reflection* d_out,
@@ -1055,14 +1100,16 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
 // header's background colour, read on the device) and the device index
 namespace {
 // the launches of the blend, behind every check: frame i of the inputs in_stride pixels on, of the outputs out_stride pixels on
-int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs& in, size_t in_stride,
-                       float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
+int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs& in,
+                       const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
     ShotShape shape;
     std::memset(&shape, 0, sizeof shape);
     shape.cfg = *cfg;
     shape.page = shot->page;
     std::memcpy(shape.page_color, shot->page_color, sizeof shape.page_color);
     shape.shadow_strength = shot->shadow_strength, shape.reflectivity = shot->reflectivity, shape.reflection_fade = shot->reflection_fade;
+    shape.floor_occlusion = floor_occlusion;
+    if (!(floor_occlusion > 0.0f)) d_occlusion = nullptr;  // oc = +0 either way: the plane is not read
     std::vector<ShotFrame> frames(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
         ShotFrame& f = frames[static_cast<size_t>(i)];
@@ -1073,6 +1120,7 @@ int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_
         f.visibility = in.visibility ? in.visibility + from : nullptr;
         f.reflection = in.reflection ? in.reflection + from * 4 : nullptr;
         f.distance = in.reflection_distance ? in.reflection_distance + from : nullptr;
+        f.occlusion = d_occlusion ? d_occlusion + from : nullptr;
         f.out = d_f32 ? d_f32 + to * 4 : nullptr;
         f.out8 = d_u8 ? d_u8 + to * 4 : nullptr;
     }
@@ -1082,14 +1130,16 @@ int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_
 }
 }  // namespace
 
-int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in, size_t in_stride,
-                                float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
+int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
+                                const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride,
+                                hipStream_t stream) {
     // argument checks, before any device work (only the last one looks inside the handles, at their device index)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || !d_in || !d_in->figure || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n; ++i)
         if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
     if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     if (shot->reflection_fade > 0.0f && !d_in->reflection_distance)
         return fail(MCRT_ERR_INVALID, "reflection_distance may be NULL only with reflection_fade == 0");
     if (!d_f32 && !d_u8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
@@ -1104,20 +1154,21 @@ int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_con
     HIP_TRY(hipSetDevice(device));
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a shot cannot be recorded into a caller's graph");
     (void)hipGetLastError();
-    return launch_shot_frames(scenes, n, device, cfg, shot, *d_in, in_stride, d_f32, d_u8, out_stride, stream);
+    return launch_shot_frames(scenes, n, device, cfg, shot, *d_in, d_occlusion, floor_occlusion, in_stride, d_f32, d_u8, out_stride, stream);
 }
 
-// Render + ground + reflection + blend, all on `stream` in order.  The render goes through render_batch_device (the handles'
+// Render + ground + reflection + ground occlusion + blend, all on `stream` in order.  The render goes through render_batch_device (the handles'
 // event chains, batched kernels where the frames fit them) under the transparent override; the passes and the blend follow it
 // in stream order and take no events.  Nothing is forked beside the render.
-int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y, void* d_scratch,
-                             size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream) {
+int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, const float* ground_y,
+                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream) {
     // argument checks, before any device work (only the last ones look inside the handles, at their device index)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || (n > 0 && (!scenes || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n; ++i)
         if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
     if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
     if (!d_f32 && !d_u8) return fail(MCRT_ERR_INVALID, "both outputs are NULL");
@@ -1127,15 +1178,16 @@ int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config
         if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
             return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (each handle owns one workspace: one frame in flight)");
     }
-    if (const int rc = check_shot_config(cfg, shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot_config(cfg, shot, floor_occlusion); rc != MCRT_OK) return rc;
     if (n == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
     if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
     const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
     if (stride < px) return fail(MCRT_ERR_INVALID, "frame_stride_pixels is smaller than width * height");
-    const ShotScratch at = shot_scratch(cfg, shot, n);
+    const ShotScratch at = shot_scratch(cfg, shot, n, floor_occlusion);
     if (!d_scratch) return fail(MCRT_ERR_INVALID, "d_scratch is NULL");
     if ((reinterpret_cast<uintptr_t>(d_scratch) & 15u) != 0) return fail(MCRT_ERR_INVALID, "d_scratch is not 16-byte aligned");
-    if (scratch_bytes < at.bytes) return fail(MCRT_ERR_INVALID, "scratch_bytes is smaller than mcrt_shot_scratch_bytes");
+    if (scratch_bytes < at.bytes)
+        return fail(MCRT_ERR_INVALID, floor_occlusion > 0.0f ? "scratch_bytes is smaller than mcrt_shot_scratch_bytes_occ" : "scratch_bytes is smaller than mcrt_shot_scratch_bytes");
     const int device = scenes[0]->device;
     for (int i = 1; i < n; ++i)
         if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
@@ -1164,7 +1216,12 @@ int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config
         r.distance = plane(at.distance);
         if (const int rc = render_reflection_batch_device(scenes, n, cfg, ground_y, &r, px, stream); rc != MCRT_OK) return rc;
     }
-    return launch_shot_frames(scenes, n, device, cfg, shot, in, px, d_f32, d_u8, stride, stream);
+    if (at.occlusion != SIZE_MAX) {
+        mcrt_ground_occlusion o{};
+        o.occlusion = plane(at.occlusion);
+        if (const int rc = render_ground_occlusion_batch_device(scenes, n, cfg, ground_y, &o, px, stream); rc != MCRT_OK) return rc;
+    }
+    return launch_shot_frames(scenes, n, device, cfg, shot, in, plane(at.occlusion), floor_occlusion, px, d_f32, d_u8, stride, stream);
 }
 
 }  // namespace mcrt_host
@@ -1306,6 +1363,18 @@ int mcrt_render_ground_batch_device(mcrt_scene* const* scenes, int n_frames, con
     return render_ground_batch_device(scenes, n_frames, cfg, ground_y, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
+int mcrt_render_ground_occlusion_device(mcrt_scene* s, const mcrt_config* cfg, float ground_y, const mcrt_ground_occlusion* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = (cfg && valid_frame(cfg)) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
+    return render_ground_occlusion_batch_device(one, 1, cfg, &ground_y, d_out, px, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_ground_occlusion_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const float* ground_y,
+                                              const mcrt_ground_occlusion* d_out, size_t frame_stride_pixels, void* stream) {
+    return render_ground_occlusion_batch_device(scenes, n_frames, cfg, ground_y, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
 int mcrt_render_reflection_device(mcrt_scene* s, const mcrt_config* cfg, float ground_y, const mcrt_reflection* d_out, void* stream) {
     if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
     mcrt_scene* one[1] = {s};
@@ -1320,14 +1389,28 @@ int mcrt_render_reflection_batch_device(mcrt_scene* const* scenes, int n_frames,
 
 int mcrt_composite_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
                                      size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8, size_t out_stride_pixels, void* stream) {
-    return composite_shot_batch_device(scenes, n_frames, cfg, shot, d_in, in_stride_pixels, d_out_f32, d_out_rgba8, out_stride_pixels,
+    return composite_shot_batch_device(scenes, n_frames, cfg, shot, d_in, nullptr, 0.0f, in_stride_pixels, d_out_f32, d_out_rgba8, out_stride_pixels,
                                        static_cast<hipStream_t>(stream));
+}
+
+int mcrt_composite_shot_batch_device_occ(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
+                                         const float* d_occlusion, float floor_occlusion, size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8,
+                                         size_t out_stride_pixels, void* stream) {
+    return composite_shot_batch_device(scenes, n_frames, cfg, shot, d_in, d_occlusion, floor_occlusion, in_stride_pixels, d_out_f32, d_out_rgba8,
+                                       out_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y, void* d_scratch,
                                   size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8, size_t frame_stride_pixels, void* stream) {
-    return render_shot_batch_device(scenes, n_frames, cfg, shot, ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, frame_stride_pixels,
+    return render_shot_batch_device(scenes, n_frames, cfg, shot, 0.0f, ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, frame_stride_pixels,
                                     static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_shot_batch_device_occ(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion,
+                                      const float* ground_y, void* d_scratch, size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8,
+                                      size_t frame_stride_pixels, void* stream) {
+    return render_shot_batch_device(scenes, n_frames, cfg, shot, floor_occlusion, ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8,
+                                    frame_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_shot_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, void* d_scratch, size_t scratch_bytes,
@@ -1335,7 +1418,7 @@ int mcrt_render_shot_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_sh
     if (!s || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
     mcrt_scene* one[1] = {s};
     const size_t px = valid_frame(cfg) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
-    return render_shot_batch_device(one, 1, cfg, shot, &ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, px, static_cast<hipStream_t>(stream));
+    return render_shot_batch_device(one, 1, cfg, shot, 0.0f, &ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, px, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_light_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_light_planes* d_out, void* stream) {

@@ -1,5 +1,5 @@
 // render_plan.cpp — host-side planning of the launches: shards, the workspace and its batches, grids, plates, batches of
-// frames, and the shapes, variants and LDS sizes of the layers, ground, reflection, light, bake and skin passes.  Pure host code: what it decides
+// frames, and the shapes, variants and LDS sizes of the layers, ground, ground-occlusion, reflection, light, bake and skin passes.  Pure host code: what it decides
 // reaches the kernels through RenderParams and the other structs of kernels.h; the constants it shares with them are in
 // launch_shapes.h.
 #include "kernels.h"
@@ -356,6 +356,26 @@ int ground_batch_view(GroundFrame* frames, const int* views, int n) { return bat
 size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape) {
     const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
     return tables + kGroundFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
+}
+// ---- ground occlusion (kernels.h) -------------------------------------------------------------------
+bool make_ground_occlusion_shape(const mcrt_config& cfg, bool inside_fast, GroundOcclusionShape& shape) {
+    std::memset(&shape, 0, sizeof shape);
+    if (!make_layers_shape(cfg, shape.tiles)) return false;
+    shape.ao_samples = cfg.ao_samples;
+    shape.ao_radius = cfg.ao_radius;
+    const int fit = kGroundOccDirBytes / (12 * (cfg.ao_samples > 0 ? cfg.ao_samples : 1));  // 8 samples: 128 pixels per pass; 113 samples: 9
+    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.inside_fast = inside_fast ? 1 : 0;
+    return true;
+}
+int ground_occlusion_view(GroundOcclusionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
+int ground_occlusion_batch_view(GroundOcclusionFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
+// The 12-mesh character (3120 bytes of tables) at 8 samples: 3120 + 8192 + 128 * 96 = 23600 bytes, four workgroups in a CU's
+// 160 KiB.  The directions never take more than kGroundOccDirBytes (the pass shrinks with A), so the largest tables the LDS
+// views take (28 KiB) make 49152 bytes, below the 64 KiB a workgroup may ask for.
+size_t ground_occlusion_lds_bytes(const GroundOcclusionFrame& f, const GroundOcclusionShape& shape) {
+    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    return tables + kGroundOccFixedBytes + static_cast<size_t>(shape.pass) * static_cast<size_t>(shape.ao_samples > 0 ? shape.ao_samples : 1) * 12;
 }
 // ---- ground reflection (kernels.h) ------------------------------------------------------------------
 bool make_reflection_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, bool cull, ReflectionShape& shape) {

@@ -44,6 +44,12 @@ The studio shot (tests/shot_fuzz_cases.py; the runs and comparisons are those of
                shot_checker.compose; odd seeds are make_shot_case(seed): 1 ... 4 scenes of random skins and views, two calls through
                the batched, single, host and PNG forms against the CPU oracle alone; the summary records the pixels compared and
                the oracle's totals of shot_checker.classes
+The ground-occlusion pass (tests/ground_occlusion_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_ground_occlusion_fuzz.py):
+  ground_occlusion   seed k is make_case(k): skins and 48 ... 80-mesh box scenes, posed and not, scaled by 1e-3 ... 1e3, cameras above,
+               below and grazing the plane, planes at, below, inside and above the scene, 1 ... 113 samples, radii from 0 to larger than
+               the scene, frames of 1 ... 96 pixels a side; every third seed also through the device form into planes off their
+               alignment, every eighth seed also make_batch(k) through the batched kernel; the summary records the reached and the
+               occluded pixels the oracle held
 A mismatch prints the case, the plane, the number of differing pixels and the first of them; the exit status is then 1.  After
 a HIP error (exit status 2) nothing more is started.  MCRT_BUNDLE_DECISIONS=0 / MCRT_REFLECT_CULL=0 in the environment render
 without the whole-bundle decisions / the reflection's tile culling: a mismatch that goes away with one is that shortcut's."""
@@ -59,7 +65,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident", "shot") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident", "shot", "ground_occlusion") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -396,6 +402,36 @@ def pass_sweep():
     sys.exit(1 if bad else 0)
 
 
+def ground_occlusion_sweep():
+    import test_gpu_ground_occlusion_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    orc = oraclelib.Oracle()
+    bad = reached = occluded = batches = frames = 0
+    t0 = time.time()
+    for seed in range(first, first + count):
+        try:
+            lines, r, o = T.run_case(M, orc, seed)
+            reached += r; occluded += o
+            if seed % 8 == 0:
+                more, n = T.run_batch(M, orc, seed)
+                lines += more; batches += 1; frames += n
+        except (McrtError, RuntimeError) as e:  # the library's, or torch's at a host wait
+            print(f"HIP ERROR ground_occlusion seed {seed}: {e}", flush=True)
+            print(f"fuzz ground_occlusion: stopped at seed {seed} after {seed - first} cases, {bad} mismatch(es)")
+            sys.exit(2)
+        if lines:
+            bad += 1
+            print("\n".join(lines[:20]), flush=True)
+        if (seed - first) % 100 == 99:
+            print(f"... {seed - first + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
+    print(f"fuzz ground_occlusion: {count} cases from seed {first}: {bad} mismatch(es); {batches} batches with {frames} frames; {time.time() - t0:.0f} s; "
+          f"the oracle holds {reached} reached pixels, {occluded} of them with occlusion < 1")
+    sys.exit(1 if bad else 0)
+
+
+if mode == "ground_occlusion":
+    ground_occlusion_sweep()
 if mode in PASS_MODES:
     pass_sweep()
 if mode in BATCH_MODES:
