@@ -1,6 +1,7 @@
 // kernel_common.h — device-side helpers that more than one kernel file uses (render_kernels.hip, pass_kernels.hip,
 // util_kernels.hip): tile geometry, the scene tables staged in LDS and the kernel variants built on them, the block-wide
-// rank, the light's disk samples, the RGBA8 quantisation, and the launch-side dispatch over the variants.
+// rank, the light's disk samples, the RGBA8 quantisation, the launch-side dispatch over the variants, and the phases the
+// stand-alone passes share (the (item, sample) ray loop, the shadow-bundle resolver, the AO stream).
 #ifndef MCRT_KERNEL_COMMON_H
 #define MCRT_KERNEL_COMMON_H
 
@@ -132,6 +133,22 @@ struct ViewSel<kViewHbm> {
     using type = SceneView;
     static __device__ __forceinline__ type make(const SceneView& g, const RenderParams&, unsigned char*) { return g; }
 };
+// The view of variant kView, made the first time a unit of the workgroup needs it: the passes stage the scene tables at
+// their first touched tile only (a bake, which has no tiles, at once).  Collective for the LDS variants (stage_tables):
+// all 256 threads reach it under uniform control flow, and `needed` and `staged` are the same in every thread.
+template <int kView>
+__device__ __forceinline__ void stage_view_once(const SceneView& g, const int lds_face_entries, const int lds_alpha_words, unsigned char* dyn, const bool needed,
+                                                typename ViewSel<kView>::type& sc, bool& staged) {
+    if (needed && !staged) {
+        if constexpr (kView == kViewHbm) {
+            sc = g;
+        } else {
+            const LdsTables t = stage_tables(g, lds_face_entries, lds_alpha_words, dyn);
+            sc = view_with_lds<kView == kViewLds>(g, t.abits, t.faces, t.mtab);
+        }
+        staged = true;
+    }
+}
 // launch side: calls f(std::integral_constant<int, kView>{}) for the variant `view` names, so a launcher writes its
 // kernel template once: [&](auto v) { ... kernel<decltype(v)::value> ... }
 template <class F>
@@ -142,7 +159,8 @@ static void with_view(int view, F&& f) {
 }
 
 // Rank of this thread's item among the workgroup's flagged items, and their total: ballot per wave,
-// four wave counts through LDS.  Collective (two barriers: the counts are reusable right after).
+// four wave counts through LDS.  COLLECTIVE (two barriers: the counts are reusable right after): all 256 threads must
+// reach it under uniform control flow — a barrier under a divergent branch hangs the device.
 __device__ __forceinline__ int block_rank(bool flag, int* s_wcnt, int& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long bal = __ballot(flag);
@@ -184,6 +202,150 @@ __device__ __forceinline__ void disk_sample_positions(const SceneView& scg, cons
         dst[3 * i + 2] = t.z;
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// phases the stand-alone passes share (pass_kernels.hip; DESIGN.md, "phases the passes share")
+// ---------------------------------------------------------------------------------------------
+// A lane per (item, sample): ray q = i * per + s belongs to item items[i], i < n_items, and counts[item] becomes the number
+// of the item's `per` rays for which test(item, q) holds.  By ballot where a wave holds whole groups (per a power of two up
+// to 64; per == 64 is the whole ballot, which a shift by 64 would not give), the first lane of a group storing its popcount;
+// else by atomicAdd onto counts the caller has zeroed.  No barrier, but a ballot: all lanes of a wave reach it together
+// (every lane of a wave runs the same number of turns).
+template <class Test>
+__device__ __forceinline__ void count_item_rays(const uint32_t* __restrict__ items, const uint32_t n_items, const uint32_t per, uint32_t* __restrict__ counts,
+                                                Test test) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const bool pow2 = (per & (per - 1u)) == 0u && per <= 64u;
+    const uint32_t n_rays = n_items * per;
+    for (uint32_t q0 = tid & ~63u; q0 < n_rays; q0 += kBlock) {
+        const uint32_t q = q0 + lane;
+        bool flag = false;
+        uint32_t k = 0;
+        if (q < n_rays) {
+            k = items[q / per];
+            flag = test(k, q);
+        }
+        if (pow2) {
+            const unsigned long long bal = __ballot(flag);
+            if (q < n_rays && (lane & (per - 1u)) == 0u) {
+                const unsigned long long grp = (per == 64u) ? bal : ((bal >> lane) & ((1ull << per) - 1ull));
+                counts[k] = static_cast<uint32_t>(__popcll(grp));
+            }
+        } else if (flag) {
+            atomicAdd(&counts[k], 1u);
+        }
+    }
+}
+
+// What the shadow resolver reads of a pass: the light and the shape's sampling, and the pass's LDS area — a candidate mask,
+// an inside mask, a lit count and a list entry per lane, the sample positions of one pass of items (pass x S x 3 floats)
+// and the four wave counts of block_rank.
+struct ShadowBundles {
+    V3 lpos;
+    float R;          // the light's radius, 0 in the hard modes
+    bool soft;        // S rays per item towards disk samples; otherwise one towards the light's centre (shading.cpp:31)
+    int S;
+    uint32_t pairs;   // rays per item
+    uint32_t pass;    // items per pass
+    bool decisions, inside_fast;
+    const uint32_t* seed_table;
+    unsigned long long* cand;
+    unsigned long long* ins;
+    uint32_t* lit;
+    uint32_t* und;
+    float* pos;
+    int* wcnt;
+};
+__device__ __forceinline__ ShadowBundles shadow_bundles(const SceneView& scg, const int samples, const int pass, const int decisions, const int inside_fast,
+                                                        const uint32_t* seed_table, unsigned long long* cand, unsigned long long* ins, uint32_t* lit,
+                                                        uint32_t* und, float* pos, int* wcnt) {
+    const float lradius = scg.hdr->light_radius;
+    const bool soft = samples > 1 && !(lradius < 1e-4f);
+    return ShadowBundles{ld3(scg.hdr->light_pos), soft ? lradius : 0.0f, soft, samples, soft ? static_cast<uint32_t>(samples) : 1u, static_cast<uint32_t>(pass),
+                         decisions != 0, inside_fast != 0, seed_table, cand, ins, lit, und, pos, wcnt};
+}
+// The lit counts of the workgroup's items, one per lane (item = lane index; `active`: the lane holds one, with shadow origin O):
+// the whole-bundle decision (rt::bundle_classify, its candidates ANDed with tile_mask) and the inside masks by the item's
+// lane; the undecided packed (block_rank); then in passes of b.pass items a lane per item forms the S disk sample positions
+// of the engine seeded for (point, depth), and a lane per (item, sample) runs the exact any-hit test (count_item_rays).
+// point_of(k, P, N): the point of item k and the normal its shadow rays leave along, read from the caller's LDS records.
+// Returns whether the lane's item was undecided; `lit` takes its count (decided or traced) and stays as it is on a lane
+// without an item.
+// COLLECTIVE: two barriers of block_rank, then — only where the workgroup has undecided items — one before the passes, one
+// per pass (and one between passes) and one behind the counts.  All 256 threads must reach it under uniform control flow;
+// a barrier under a divergent branch hangs the device.  Behind it nothing of the area is read across lanes any more.
+template <bool kPosed, class SV, class PointOf>
+__device__ __forceinline__ bool resolve_shadow_bundles(const SceneView& scg, const SV& sc, const ShadowBundles b, const bool active, const V3 O,
+                                                       const unsigned long long tile_mask, const int depth, PointOf point_of, uint32_t& lit) {
+    const uint32_t tid = threadIdx.x;
+    const V3 lpos = b.lpos;  // (a value of its own: selected against a load below, b.lpos would be selected by address and keep b in memory)
+    bool undecided = false;
+    // ---- a lane per item: the whole-bundle decision
+    if (active) {
+        unsigned long long cand;
+        const int known = bundle_classify<kPosed>(scg, sc, O, lpos, b.R, static_cast<int>(b.pairs), b.decisions, cand);
+        cand &= tile_mask;
+        undecided = known < 0;
+        b.cand[tid] = cand;
+        b.ins[tid] = (undecided && b.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
+        if (!undecided) lit = static_cast<uint32_t>(known);
+    }
+    b.lit[tid] = 0u;
+    int total = 0;
+    const int rank = block_rank(undecided, b.wcnt, total);
+    if (undecided) b.und[rank] = tid;
+    const uint32_t n_und = static_cast<uint32_t>(total);
+    if (n_und) __syncthreads();  // uniform
+    for (uint32_t u0 = 0; u0 < n_und; u0 += b.pass) {  // uniform
+        const uint32_t nu = min(b.pass, n_und - u0);
+        if (u0) __syncthreads();  // the previous pass's rays have read the positions
+        // ---- a lane per undecided item: its mt19937 stream and the S disk sample positions
+        // (outside the seed table's window — points far out, at the horizon — the 397-step recurrence)
+        if (b.soft && tid < nu) {
+            V3 P, N;  // (N goes unused here: the accessor is inlined and its fetch of the normal falls away)
+            point_of(b.und[u0 + tid], P, N);
+            disk_sample_positions(scg, b.seed_table, nullptr, P, depth, b.S, b.pos + static_cast<size_t>(tid) * 3 * b.S);
+        }
+        __syncthreads();
+        // ---- a lane per (undecided item, light sample)
+        count_item_rays(b.und + u0, nu, b.pairs, b.lit, [&](const uint32_t k, const uint32_t q) __attribute__((always_inline)) {
+            V3 P, N;
+            point_of(k, P, N);
+            const V3 target = b.soft ? ld3(b.pos + static_cast<size_t>(q) * 3) : lpos;
+            return !in_shadow_masked(sc, P, N, target, b.cand[k], b.ins[k]);
+        });
+    }
+    if (n_und) __syncthreads();  // the counts are complete
+    if (undecided) lit = b.lit[tid];
+    return undecided;
+}
+
+// The cosine-weighted directions of computeAO at P with unit normal N (raytracer.cpp:42-68), by the lane that owns the
+// point: the truncated engine seeded for P — mt[397] from the device's table of all seeds where the handle holds it, one
+// load instead of the 397-step recurrence — and the frame T, N, B; next() is the following world direction.
+struct AoStream {
+    V3 T, N, B;
+    MtShort rng;
+    __device__ __forceinline__ AoStream(const uint32_t* __restrict__ seed_table_full, const V3 P, const V3 Nu) : N(Nu) {
+        T = (__builtin_fabsf(N.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), N)) : normalize(cross(mk(0, 1, 0), N));
+        B = cross(N, T);
+        const uint32_t seed = ao_seed(P);
+        if (seed_table_full)
+            rng.seed_known(seed, seed_table_full[seed]);
+        else
+            rng.seed(seed);
+    }
+    __device__ __forceinline__ V3 next() {
+        const float r1 = rng.uniform();
+        const float r2 = rng.uniform();
+        const float sinT = sqrt_pos(1.0f - r1);
+        const float cosT = sqrt_pos(r1);
+        float sn, cs;
+        mcrt_sincosf(kTwoPi * r2, &sn, &cs);
+        const V3 local = mk(sinT * cs, cosT, sinT * sn);
+        return normalize(T * local.x + N * local.y + B * local.z);
+    }
+};
 
 }  // namespace mcrt
 

@@ -157,6 +157,26 @@ constexpr int kAlphaLdsWordsMax = 4096;  // 64 Ki texels
 constexpr int kFaceLdsEntriesMax = 384;   // 64 meshes
 struct LdsFit { int face_entries, alpha_words, view; };
 LdsFit lds_fit(uint32_t alpha_words, uint32_t n_meshes, bool posed);
+// A pass's frame record (LayersFrame, GroundFrame, ... BakeFrame): fills f.lds_* for a scene of that size and returns the
+// kernel variant it needs
+template <class Frame>
+int view_of_frame(Frame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
+    const LdsFit fit = lds_fit(alpha_words, n_meshes, posed);
+    f.lds_alpha_words = fit.alpha_words, f.lds_face_entries = fit.face_entries;
+    return fit.view;
+}
+// the variant of a batch of such frames: the most general any of them needs; rewrites the frames' LDS fields where it reads HBM
+template <class Frame>
+int batch_view_of(Frame* frames, const int* views, int n) {
+    bool any_hbm = false, any_posed = false;
+    for (int i = 0; i < n; ++i) {
+        any_hbm = any_hbm || views[i] == kViewHbm;
+        any_posed = any_posed || views[i] == kViewLds;
+    }
+    if (any_hbm)
+        for (int i = 0; i < n; ++i) frames[i].lds_alpha_words = 0, frames[i].lds_face_entries = 0;
+    return any_hbm ? kViewHbm : (any_posed ? kViewLds : kViewLdsUnposed);
+}
 // dynamic LDS of the scene tables p's kernels stage
 inline size_t scene_table_bytes(const RenderParams& p) { return p.scene_in_lds ? scene_tables_lds_bytes(p.lds_face_entries, p.lds_alpha_words) : 0; }
 
@@ -243,11 +263,6 @@ struct LayersShape {
 };
 // false when the frame holds more units than the kernels index (2^31)
 bool make_layers_shape(const mcrt_config& cfg, LayersShape& shape);
-// fills f.lds_* for a scene of that size and returns the kernel variant it needs (kViewHbm, kViewLds or kViewLdsUnposed by
-// the rules of the beauty path)
-int layers_view(LayersFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
-// the variant of a batch: the most general any of its frames needs; rewrites the frames' LDS fields where it reads HBM
-int layers_batch_view(LayersFrame* frames, const int* views, int n);
 constexpr int kLayersBatchMaxFrames = 4096;  // frames per launch (blockIdx.y; larger batches take several launches)
 size_t layers_lds_bytes(const LayersFrame& f);
 
@@ -276,9 +291,6 @@ struct GroundShape {
 };
 // false when the frame holds more units than the kernels index (2^31)
 bool make_ground_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, GroundShape& shape);
-// fills f.lds_* and returns the kernel variant by the layers' rule
-int ground_view(GroundFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
-int ground_batch_view(GroundFrame* frames, const int* views, int n);
 // dynamic LDS of a launch: the frame's scene tables, then the block's area (masks, points, counts and sample positions)
 size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape);
 
@@ -305,9 +317,6 @@ struct GroundOcclusionShape {
 };
 // false when the frame holds more units than the kernels index (2^31)
 bool make_ground_occlusion_shape(const mcrt_config& cfg, bool inside_fast, GroundOcclusionShape& shape);
-// fills f.lds_* and returns the kernel variant by the layers' rule
-int ground_occlusion_view(GroundOcclusionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
-int ground_occlusion_batch_view(GroundOcclusionFrame* frames, const int* views, int n);
 // dynamic LDS of a launch: the frame's scene tables, then the block's area (masks, points, counts, the traced list and directions)
 size_t ground_occlusion_lds_bytes(const GroundOcclusionFrame& f, const GroundOcclusionShape& shape);
 
@@ -339,9 +348,6 @@ struct ReflectionShape {
 };
 // false when the frame holds more units than the kernels index (2^31)
 bool make_reflection_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, bool cull, ReflectionShape& shape);
-// fills f.lds_* and returns the kernel variant by the layers' rule
-int reflection_view(ReflectionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
-int reflection_batch_view(ReflectionFrame* frames, const int* views, int n);
 // dynamic LDS of a launch: the frame's scene tables, then the block's area (hit records, masks, counts and sample positions)
 size_t reflection_lds_bytes(const ReflectionFrame& f, const ReflectionShape& shape);
 
@@ -372,9 +378,6 @@ struct ShadeShape {
 };
 // false when the frame holds more units than the kernels index (2^31)
 bool make_shade_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, ShadeShape& shape);
-// fills f.lds_* and returns the kernel variant by the layers' rule
-int shade_view(ShadeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
-int shade_batch_view(ShadeFrame* frames, const int* views, int n);
 // dynamic LDS of the two launches: the frame's scene tables, then the block's area
 size_t shade_lds_bytes(const ShadeFrame& f, const ShadeShape& shape);  // hit records, masks, counts and sample positions
 size_t occlusion_lds_bytes(const ShadeFrame& f);                         // hit records, masks, the traced list and the values
@@ -420,9 +423,6 @@ struct BakeShape {
     int rays;              // `bake_shade`: visibility or direct is asked for (otherwise it writes position / normal alone)
 };
 void make_bake_shape(const mcrt_config& cfg, int grid, bool bundle_decisions, bool inside_fast, int max_texels, BakeShape& shape);
-// fills f.lds_* and returns the kernel variant by the layers' rule
-int bake_view(BakeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed);
-int bake_batch_view(BakeFrame* frames, const int* views, int n);
 // dynamic LDS of the two launches: the frame's scene tables, then the block's area
 size_t bake_shade_lds_bytes(const BakeFrame& f, const BakeShape& shape);  // point records, texel records, masks, counts and sample positions
 size_t bake_occlusion_lds_bytes(const BakeFrame& f);                         // point records, texel records, masks, the traced list and the values

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 namespace rt {
 constexpr int kMeshTabWords = 24;  // words per mesh of the mesh table staged in LDS (rt_core.h: SceneViewLdsT::mtab)
@@ -46,25 +47,67 @@ __host__ __device__ __forceinline__ size_t scene_tables_lds_bytes(int face_entri
     return static_cast<size_t>(face_entries) * 16 + static_cast<size_t>(face_entries / 6) * rt::kMeshTabWords * 4 + static_cast<size_t>(alpha_words) * 4;
 }
 
+// where a pass's own area starts behind them: their size rounded up to 16 bytes — what the kernels carve by and the host sizes by
+__host__ __device__ __forceinline__ size_t scene_tables_lds_span(int face_entries, int alpha_words) {
+    return (scene_tables_lds_bytes(face_entries, alpha_words) + 15u) & ~static_cast<size_t>(15);
+}
+
 constexpr int kLayersGrid = 8192;  // layers and ground: workgroups per frame at most (the kernels stride over their units)
+
+// The fixed LDS area of a pass, behind the tables: one struct per kernel body, an array of kBlock entries (one per lane) per
+// member.  The body reaches its area through the struct and the host sizes it by sizeof (render_plan.cpp: *_lds_bytes), so
+// the two cannot drift; the sample area of a pass (pass x samples x 3 floats) follows it.  The asserts pin today's sizes.
+struct ShadowLanes {  // what the shadow resolver keeps per lane (kernel_common.h: ShadowBundles)
+    unsigned long long cand[kBlock], ins[kBlock];  // candidate and inside masks
+    uint32_t lit[kBlock], und[kBlock];             // lit counts, the undecided list
+};
+struct GroundArea {  // ground, ground occlusion
+    unsigned long long cand[kBlock], ins[kBlock];  // candidate and inside masks
+    float2 pxz[kBlock];                            // P.x, P.z
+    uint32_t count[kBlock], list[kBlock];          // lit / occluded counts, the undecided / traced list
+};
+struct ReflectionArea {
+    float4 rec[4 * kBlock];  // a hit record of four planes: point, normal, texel colour, ray
+    ShadowLanes sh;
+};
+struct ShadeArea {
+    float4 rec[3 * kBlock];  // a hit record of three planes: point, normal, texel colour
+    ShadowLanes sh;
+};
+struct OcclusionArea {
+    float4 rec[2 * kBlock];  // a hit record of two planes: point, normal
+    unsigned long long mask[kBlock];  // the candidate mask
+    uint32_t list[kBlock];            // the traced list
+    float val[kBlock];                // the value
+};
+struct BakeShadeArea {
+    float4 rec[2 * kBlock];  // a point record of two planes: point, normal
+    float4 tex[kBlock];      // the texel record: colour,
+    int4 own[kBlock];        // and owner face, texel, size
+    ShadowLanes sh;
+};
+struct BakeOcclusionArea {
+    float4 rec[2 * kBlock];  // the point record
+    int4 own[kBlock];        // the owner-face half of the texel record
+    unsigned long long mask[kBlock];
+    uint32_t list[kBlock];
+    float val[kBlock];
+};
 constexpr int kGroundPosBytes = 12 * 1024;  // ground: LDS for the sample positions of the undecided pixels of one pass
-constexpr int kGroundFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // ground: candidate and inside masks, P.x / P.z, lit counts, the undecided list
+constexpr int kGroundFixedBytes = sizeof(GroundArea);
 constexpr int kGroundOccDirBytes = 12 * 1024;  // ground occlusion: LDS for the A directions of the traced pixels of one pass
-constexpr int kGroundOccFixedBytes = kBlock * (8 + 8 + 8 + 4 + 4);  // ground occlusion: candidate and inside masks, P.x / P.z, occluded counts, the traced list
+constexpr int kGroundOccFixedBytes = sizeof(GroundArea);
 constexpr int kReflectPosBytes = 8 * 1024;  // reflection: LDS for the sample positions of the undecided level-1 hits of one pass
-// reflection: per lane a hit record of four float4 (point, normal, texel colour, ray), candidate and inside masks, lit counts, the undecided list
-constexpr int kReflectFixedBytes = kBlock * (64 + 8 + 8 + 4 + 4);
+constexpr int kReflectFixedBytes = sizeof(ReflectionArea);
 constexpr int kShadePosBytes = 8 * 1024;  // light layers, `shade`: LDS for the sample positions of the undecided hits of one pass
-// `shade`: per lane a hit record of three float4 (point, normal, texel colour), candidate and inside masks, lit counts, the undecided list
-constexpr int kShadeFixedBytes = kBlock * (48 + 8 + 8 + 4 + 4);
-// `occlusion`: per lane a hit record of two float4 (point, normal), the candidate mask, the traced list, the value
-constexpr int kOcclusionFixedBytes = kBlock * (32 + 8 + 4 + 4);
+constexpr int kShadeFixedBytes = sizeof(ShadeArea);
+constexpr int kOcclusionFixedBytes = sizeof(OcclusionArea);
 constexpr int kBakePosBytes = 8 * 1024;  // light bake, `bake_shade`: LDS for the sample positions of the undecided points of one pass
-// `bake_shade`: per lane a point record of two float4 (point, normal), a texel record of two (colour; owner face, texel, size), candidate and
-// inside masks, lit counts, the undecided list
-constexpr int kBakeShadeFixedBytes = kBlock * (32 + 32 + 8 + 8 + 4 + 4);
-// `bake_occlusion`: per lane a point record, the owner-face half of the texel record, the candidate mask, the traced list, the value
-constexpr int kBakeOcclusionFixedBytes = kBlock * (32 + 16 + 8 + 4 + 4);
+constexpr int kBakeShadeFixedBytes = sizeof(BakeShadeArea);
+constexpr int kBakeOcclusionFixedBytes = sizeof(BakeOcclusionArea);
+static_assert(kGroundFixedBytes == kBlock * 32 && kReflectFixedBytes == kBlock * 88 && kShadeFixedBytes == kBlock * 72 && kOcclusionFixedBytes == kBlock * 48 &&
+                  kBakeShadeFixedBytes == kBlock * 88 && kBakeOcclusionFixedBytes == kBlock * 64,
+              "the passes' LDS areas: sizes the launches were tuned for, every member 16-byte aligned");
 
 // Workgroups per frame of a batched launch.  Every kernel strides over its frame's device-side work, so the grid only
 // shapes the schedule: a batch aims at kBatchTarget workgroups per launch (8 per CU of the 256 — twice what the largest

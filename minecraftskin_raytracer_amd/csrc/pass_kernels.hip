@@ -68,6 +68,51 @@ __device__ __forceinline__ unsigned long long layers_tile_mask(const SceneView& 
     if (!cull && sc.n_meshes > 0) mask = ~0ull;
     return mask;
 }
+// a unit = kBlock pixels of a tile (a touched 32x32 tile is traced by four workgroups, a ray per lane each): the unit's tile,
+// and this lane's pixel in it.  Two halves — unit_tile, which is the same in every lane, and lane_pixel — for the reflection
+// pass, which forms its mask between them (with the pixel decoded first it takes 16 bytes more scratch); unit_pixel is both.
+struct UnitPixel {
+    TileGeom tg;
+    unsigned p0, npix;  // the unit's first pixel in the tile, the tile's pixels
+    bool valid;
+    int px, py;
+    size_t idx;
+};
+__device__ __forceinline__ bool unit_tile(const LayersShape& tiles, const int unit, UnitPixel& up) {
+    const mcrt_config& cfg = tiles.cfg;
+    const int tile = unit / tiles.parts, part = unit - tile * tiles.parts;
+    const int tyi = tile / tiles.tiles_x, txi = tile - tyi * tiles.tiles_x;
+    TileGeom& tg = up.tg;
+    tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
+    tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
+    tg.owned_row = tyi, tg.frame_tile = tile;
+    up.npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
+    up.p0 = static_cast<unsigned>(part) * kBlock;
+    return up.p0 < up.npix;  // a clipped edge tile holds fewer units
+}
+__device__ __forceinline__ void lane_pixel(const mcrt_config& cfg, const int tid, UnitPixel& up) {
+    const TileGeom& tg = up.tg;
+    const unsigned pix = up.p0 + static_cast<unsigned>(tid);
+    up.valid = pix < up.npix;
+    const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(up.valid ? pix : 0u);
+    up.py = tg.y + static_cast<int>(uly), up.px = tg.x + static_cast<int>((up.valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
+    up.idx = static_cast<size_t>(up.py) * static_cast<size_t>(cfg.width) + static_cast<size_t>(up.px);
+}
+__device__ __forceinline__ bool unit_pixel(const LayersShape& tiles, const int unit, const int tid, UnitPixel& up) {
+    if (!unit_tile(tiles, unit, up)) return false;
+    lane_pixel(tiles.cfg, tid, up);
+    return true;
+}
+// one value per pixel into a plane: 16 bytes per four neighbouring pixels of a row where `quads` (lanes 4k .. 4k+3 then hold
+// four neighbours of one row, all valid or none)
+__device__ __forceinline__ void store_plane(float* __restrict__ plane, const bool quads, const bool valid, const int lane, const size_t idx, const float val) {
+    if (quads) {
+        const float v1 = __shfl_down(val, 1), v2 = __shfl_down(val, 2), v3 = __shfl_down(val, 3);
+        if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(plane + idx) = make_float4(val, v1, v2, v3);
+    } else if (valid) {
+        plane[idx] = val;
+    }
+}
 template <int kView>
 __device__ __forceinline__ void layers_body(const LayersFrame& __restrict__ f, const LayersShape& __restrict__ sh) {
     extern __shared__ __align__(16) unsigned char s_dyn[];
@@ -75,53 +120,23 @@ __device__ __forceinline__ void layers_body(const LayersFrame& __restrict__ f, c
     const mcrt_config& cfg = sh.cfg;
     const int tid = threadIdx.x, lane = tid & 63;
     const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
-    const int n_tiles = sh.tiles_x * sh.tiles_y;
     // depths as one 16-byte store per four pixels: every tile row starts and ends on a 16-byte boundary of the plane
     const bool quads = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.depth) & 15u) == 0;
     typename ViewSel<kView>::type sc;
     bool staged = false;
-    // a unit = kBlock pixels of a tile: a touched 32x32 tile is traced by four workgroups, a ray per lane each
-    const int parts = sh.parts;
-    const int n_units = n_tiles * parts;
+    const int n_units = sh.tiles_x * sh.tiles_y * sh.parts;
     for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        const int tile = unit / parts, part = unit - tile * parts;
-        const int tyi = tile / sh.tiles_x, txi = tile - tyi * sh.tiles_x;
-        TileGeom tg;
-        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
-        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
-        tg.owned_row = tyi, tg.frame_tile = tile;
-        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
-        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
-        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
-        const unsigned long long mask = layers_tile_mask(scg, cfg, tg, aspect, lane);  // the same in every wave of the workgroup
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
-        const unsigned pix = p0 + static_cast<unsigned>(tid);
-        const bool valid = pix < npix;
-        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
-        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
-        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
+        UnitPixel up;
+        if (!unit_pixel(sh, unit, tid, up)) continue;
+        const unsigned long long mask = layers_tile_mask(scg, cfg, up.tg, aspect, lane);  // the same in every wave of the workgroup
+        stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
         Surface s = miss_surface();
-        if (mask != 0ull && valid) s = pixel_surface(sc, cfg, aspect, tg.x + lx, tg.y + ly, mask);
-        if (f.depth) {
-            if (quads) {  // tg.w is a multiple of 4: lanes 4k .. 4k+3 hold four neighbours of one row, all valid or none
-                const float t1 = __shfl_down(s.t, 1), t2 = __shfl_down(s.t, 2), t3 = __shfl_down(s.t, 3);
-                if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(f.depth + idx) = make_float4(s.t, t1, t2, t3);
-            } else if (valid) {
-                f.depth[idx] = s.t;
-            }
-        }
-        if (valid) {
-            if (f.normal) f.normal[idx] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
-            if (f.albedo) f.albedo[idx] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
-            if (f.id) f.id[idx] = make_int4(s.mesh, s.face, s.tx, s.ty);
+        if (mask != 0ull && up.valid) s = pixel_surface(sc, cfg, aspect, up.px, up.py, mask);
+        if (f.depth) store_plane(f.depth, quads, up.valid, lane, up.idx, s.t);
+        if (up.valid) {
+            if (f.normal) f.normal[up.idx] = make_float4(s.n.x, s.n.y, s.n.z, 0.0f);
+            if (f.albedo) f.albedo[up.idx] = make_float4(s.tex.r, s.tex.g, s.tex.b, s.tex.a);
+            if (f.id) f.id[up.idx] = make_int4(s.mesh, s.face, s.tx, s.ty);
         }
     }
 }
@@ -269,6 +284,7 @@ __global__ __launch_bounds__(kViewBlock) void scene_view_batch_kernel(SceneViewT
 //                                all S light samples, by none, or undecided with a candidate mask; the undecided are packed
 //   1 lane / undecided pixel     truncated mt19937 (mt[397] from the seed table) → 2·S draws → S disk sample positions in LDS
 //   1 lane / (undecided pixel, light sample)   exact any-hit test on the candidates → lit count by ballot
+//                                (these three phases: resolve_shadow_bundles, kernel_common.h)
 //   1 lane / pixel               visibility = lit / S, distance, matte: coalesced stores, 16 bytes per four pixels of a row
 //                                where the rows allow
 // ---------------------------------------------------------------------------------------------
@@ -291,6 +307,38 @@ __device__ __forceinline__ GroundPoint ground_point(const SceneView& sc, const m
     h.P = mk(ray.o.x + ray.d.x * t, g, ray.o.z + ray.d.z * t);
     return h;
 }
+// The tile's footprint on the plane y = g: the bounding rectangle of the points where its four corner rays meet the plane,
+// and `reach`, the largest of their distances along x, z and the ray.  ok: all four reach the plane well away from the
+// horizon (|d.y| >= 1e-2) at finite points; otherwise the callers keep every mesh.
+struct TileFootprint {
+    bool ok;
+    float x0, x1, z0, z1, reach;
+};
+__device__ __forceinline__ TileFootprint tile_footprint(const SceneView& sc, const mcrt_config& cfg, const TileGeom& tg, const float aspect, const float g) {
+    TileFootprint fp{true, kFltMax, -kFltMax, kFltMax, -kFltMax, 0.0f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float fx = static_cast<float>(tg.x + ((c & 1) ? tg.w : 0)), fy = static_cast<float>(tg.y + ((c & 2) ? tg.h : 0));
+        const Ray ray = camera_ray(sc, fx / static_cast<float>(cfg.width), fy / static_cast<float>(cfg.height), aspect);
+        const float t = (g - ray.o.y) / ray.d.y;
+        fp.ok = fp.ok && __builtin_fabsf(ray.d.y) >= 1e-2f && t > 0.0f && t < 1e30f;
+        const float dx = ray.d.x * t, dz = ray.d.z * t;
+        const float x = ray.o.x + dx, z = ray.o.z + dz;
+        fp.x0 = __builtin_fminf(fp.x0, x), fp.x1 = __builtin_fmaxf(fp.x1, x), fp.z0 = __builtin_fminf(fp.z0, z), fp.z1 = __builtin_fmaxf(fp.z1, z);
+        fp.reach = __builtin_fmaxf(fp.reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dz)), t));
+        fp.ok = fp.ok && x == x && z == z;  // (fmin / fmax drop a NaN)
+    }
+    return fp;
+}
+// world bounds of a mesh: its box, or its padded bounding sphere's when it is posed; false for a sphere without a radius
+__device__ __forceinline__ bool mesh_world_bounds(const FlatMesh& m, V3& lo, V3& hi) {
+    lo = ld3(m.lo), hi = ld3(m.hi);
+    if (!(m.flags & MESH_ROTATED)) return true;
+    const float r = m.sphere[3];
+    lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
+    hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
+    return r >= 0.0f;
+}
 // The meshes that can shadow a ground point under the tile, conservatively: lane m of the calling wave tests mesh m.
 // The tile's pixel-centre rays lie inside its four corner rays; when all four reach the plane (well away from the horizon:
 // |d.y| >= 1e-2) the ground points of the tile lie in the bounding rectangle F of the four corner points — the image of a
@@ -310,23 +358,10 @@ __device__ __forceinline__ unsigned long long ground_tile_mask(const SceneView& 
     const unsigned long long all = n < 64 ? (1ull << n) - 1ull : ~0ull;
     if (sc.hdr->cull_ok == 0 || n >= 64) return all;
     const float slack = sc.hdr->mask_slack;
-    float fx0 = kFltMax, fx1 = -kFltMax, fz0 = kFltMax, fz1 = -kFltMax, reach = 0.0f;
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float fx = static_cast<float>(tg.x + ((c & 1) ? tg.w : 0)), fy = static_cast<float>(tg.y + ((c & 2) ? tg.h : 0));
-        const Ray ray = camera_ray(sc, fx / static_cast<float>(cfg.width), fy / static_cast<float>(cfg.height), aspect);
-        const float t = (g - ray.o.y) / ray.d.y;
-        ok = ok && __builtin_fabsf(ray.d.y) >= 1e-2f && t > 0.0f && t < 1e30f;
-        const float dx = ray.d.x * t, dz = ray.d.z * t;
-        const float x = ray.o.x + dx, z = ray.o.z + dz;
-        fx0 = __builtin_fminf(fx0, x), fx1 = __builtin_fmaxf(fx1, x), fz0 = __builtin_fminf(fz0, z), fz1 = __builtin_fmaxf(fz1, z);
-        reach = __builtin_fmaxf(reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dz)), t));
-        ok = ok && x == x && z == z;  // (fmin / fmax drop a NaN)
-    }
-    ok = ok && reach < 1e30f && slack < 1e30f;
-    if (!ok) return all;
-    const float fm = 2e-3f * reach + 16.0f * slack;
+    const TileFootprint fp = tile_footprint(sc, cfg, tg, aspect, g);
+    const float fx0 = fp.x0, fx1 = fp.x1, fz0 = fp.z0, fz1 = fp.z1;
+    if (!(fp.ok && fp.reach < 1e30f && slack < 1e30f)) return all;
+    const float fm = 2e-3f * fp.reach + 16.0f * slack;
     const V3 L = ld3(sc.hdr->light_pos);
     const float Rb = R * 1.001f + slack;
     const float gy = g + 1e-3f;     // the shadow rays' origins
@@ -337,14 +372,8 @@ __device__ __forceinline__ unsigned long long ground_tile_mask(const SceneView& 
         if (m.flags & MESH_EMPTY) {
             touch = false;  // intersection.cpp:205: never hit
         } else {
-            V3 lo = ld3(m.lo), hi = ld3(m.hi);
-            bool bounded = true;
-            if (m.flags & MESH_ROTATED) {
-                const float r = m.sphere[3];
-                bounded = r >= 0.0f;
-                lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
-                hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
-            }
+            V3 lo, hi;
+            const bool bounded = mesh_world_bounds(m, lo, hi);
             const float h = low - gy, c = low - hi.y;  // the light's height above the origins and above the box
             if (bounded && h > 0.0f && c > 0.01f * h && c > 64.0f * slack) {
                 if (hi.y < gy - 64.0f * slack) {
@@ -362,42 +391,31 @@ __device__ __forceinline__ unsigned long long ground_tile_mask(const SceneView& 
     }
     return __ballot(touch);
 }
-// one value per pixel into a plane: 16 bytes per four neighbouring pixels of a row where `quads` (lanes 4k .. 4k+3 then hold
-// four neighbours of one row, all valid or none)
-__device__ __forceinline__ void store_plane(float* __restrict__ plane, const bool quads, const bool valid, const int lane, const size_t idx, const float val) {
+// the 8-bit matte of a value per pixel, (u8)(clamp(1 - val, 0, 1) * 255 + 0.5): four pixels of a row per word where `quads`
+// (as store_plane)
+__device__ __forceinline__ void store_matte(uint8_t* __restrict__ matte, const bool quads, const bool valid, const int lane, const size_t idx, const float val) {
+    const uint32_t a = static_cast<unsigned char>(sclamp(1.0f - val, 0.0f, 1.0f) * 255.0f + 0.5f);
     if (quads) {
-        const float v1 = __shfl_down(val, 1), v2 = __shfl_down(val, 2), v3 = __shfl_down(val, 3);
-        if (valid && (lane & 3) == 0) *reinterpret_cast<float4*>(plane + idx) = make_float4(val, v1, v2, v3);
+        const uint32_t a1 = __shfl_down(a, 1), a2 = __shfl_down(a, 2), a3 = __shfl_down(a, 3);
+        if (valid && (lane & 3) == 0) *reinterpret_cast<uint32_t*>(matte + idx) = a | (a1 << 8) | (a2 << 16) | (a3 << 24);
     } else if (valid) {
-        plane[idx] = val;
+        matte[idx] = static_cast<uint8_t>(a);
     }
 }
 template <int kView>
 __device__ __forceinline__ void ground_body(const GroundFrame& __restrict__ f, const GroundShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks][inside masks][P.x, P.z][lit counts][undecided list][positions: pass x S x 3 floats]
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][GroundArea][positions: pass x S x 3 floats]
     __shared__ int s_wcnt[kBlock / 64];
     const SceneView scg = view_of(f.scene);
     const mcrt_config& cfg = sh.tiles.cfg;
     const int tid = threadIdx.x, lane = tid & 63;
     const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
     const float g = f.ground_y;
-    const V3 lpos = ld3(scg.hdr->light_pos);
-    const float lradius = scg.hdr->light_radius;
-    const int S = sh.samples;
-    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
-    const float R = soft ? lradius : 0.0f;
-    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per pixel
-    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
-    const uint32_t pass = static_cast<uint32_t>(sh.pass);
     const V3 N = mk(0.0f, 1.0f, 0.0f);
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(area);
-    unsigned long long* s_ins = s_cand + kBlock;
-    float2* s_pxz = reinterpret_cast<float2*>(s_ins + kBlock);
-    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_pxz + kBlock);
-    uint32_t* s_und = s_lit + kBlock;
-    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    GroundArea& area = *reinterpret_cast<GroundArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    const ShadowBundles sb = shadow_bundles(scg, sh.samples, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.cand, area.ins, area.count,
+                                            area.list, reinterpret_cast<float*>(&area + 1), s_wcnt);
     // four neighbouring pixels of a row per store: every tile row starts and ends on a four-pixel boundary of the plane
     const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
     const bool quads_vis = quad_rows && (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
@@ -405,108 +423,33 @@ __device__ __forceinline__ void ground_body(const GroundFrame& __restrict__ f, c
     const bool quads_matte = quad_rows && (reinterpret_cast<uintptr_t>(f.matte) & 3u) == 0;
     typename ViewSel<kView>::type sc;
     bool staged = false;
-    const int parts = sh.tiles.parts;
-    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * parts;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * sh.tiles.parts;
     for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        const int tile = unit / parts, part = unit - tile * parts;
-        const int tyi = tile / sh.tiles.tiles_x, txi = tile - tyi * sh.tiles.tiles_x;
-        TileGeom tg;
-        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
-        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
-        tg.owned_row = tyi, tg.frame_tile = tile;
-        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
-        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
-        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
-        const unsigned long long mask = ground_tile_mask(scg, cfg, tg, aspect, g, R, lane);  // the same in every wave of the workgroup
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
-        const unsigned pix = p0 + static_cast<unsigned>(tid);
-        const bool valid = pix < npix;
-        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
-        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
-        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
-        GroundPoint gp = ground_point(scg, cfg, aspect, g, static_cast<float>(tg.x + lx) + 0.5f, static_cast<float>(tg.y + ly) + 0.5f);
-        if (!valid) gp.reached = false, gp.t = kFltMax;
-        if (f.distance) store_plane(f.distance, quads_dist, valid, lane, idx, gp.t);
-        uint32_t lit = pairs;  // a pixel that misses the plane, and every pixel of a tile no mesh can shadow
-        bool undecided = false;
+        UnitPixel up;
+        if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
+        const unsigned long long mask = ground_tile_mask(scg, cfg, up.tg, aspect, g, sb.R, lane);  // the same in every wave of the workgroup
+        stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
+        GroundPoint gp = ground_point(scg, cfg, aspect, g, static_cast<float>(up.px) + 0.5f, static_cast<float>(up.py) + 0.5f);
+        if (!up.valid) gp.reached = false, gp.t = kFltMax;
+        if (f.distance) store_plane(f.distance, quads_dist, up.valid, lane, up.idx, gp.t);
+        uint32_t lit = sb.pairs;  // a pixel that misses the plane, and every pixel of a tile no mesh can shadow
+        [[maybe_unused]] bool undecided = false;  // (the hook's)
         if (mask != 0ull) {  // uniform
-            // ---- a lane per pixel: the whole-bundle decision
-            if (gp.reached) {
-                const V3 O = gp.P + N * 1e-3f;
-                unsigned long long cand;
-                const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
-                cand &= mask;
-                undecided = known < 0;
-                s_cand[tid] = cand;
-                s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
-                s_pxz[tid] = make_float2(gp.P.x, gp.P.z);
-                if (!undecided) lit = static_cast<uint32_t>(known);
-            }
-            s_lit[tid] = 0u;
-            int total = 0;
-            const int rank = block_rank(undecided, s_wcnt, total);
-            if (undecided) s_und[rank] = static_cast<uint32_t>(tid);
-            const uint32_t n_und = static_cast<uint32_t>(total);
-            if (n_und) __syncthreads();  // uniform
-            for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
-                const uint32_t nu = min(pass, n_und - u0);
-                if (u0) __syncthreads();  // the previous pass's rays have read the positions
-                // ---- a lane per undecided pixel: its mt19937 stream and the S disk sample positions
-                if (soft && static_cast<uint32_t>(tid) < nu) {
-                    const float2 xz = s_pxz[s_und[u0 + tid]];
-                    // (outside the seed table's window — ground points far out, at the horizon — the 397-step recurrence)
-                    disk_sample_positions(scg, f.seed_table, nullptr, mk(xz.x, g, xz.y), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
-                }
-                __syncthreads();
-                // ---- a lane per (undecided pixel, light sample); every lane of a wave runs the same number of turns (ballot inside)
-                const uint32_t n_rays = nu * pairs;
-                for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
-                    const uint32_t q = q0 + static_cast<uint32_t>(lane);
-                    bool visible = false;
-                    uint32_t k = 0;
-                    if (q < n_rays) {
-                        k = s_und[u0 + q / pairs];
-                        const float2 xz = s_pxz[k];
-                        const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
-                        visible = !in_shadow_masked(sc, mk(xz.x, g, xz.y), N, target, s_cand[k], s_ins[k]);
-                    }
-                    if (pow2) {
-                        const unsigned long long bal = __ballot(visible);
-                        if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
-                            const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
-                            s_lit[k] = static_cast<uint32_t>(__popcll(grp));
-                        }
-                    } else if (visible) {
-                        atomicAdd(&s_lit[k], 1u);
-                    }
-                }
-            }
-            // the counts are complete; behind this barrier nothing of the unit is read across lanes any more, so the next
-            // unit may overwrite the area
-            if (n_und) __syncthreads();
-            if (undecided) lit = s_lit[tid];
+            // ---- resolve_shadow_bundles: the pixel's point goes to LDS as P.x, P.z; the normal is the plane's
+            if (gp.reached) area.pxz[tid] = make_float2(gp.P.x, gp.P.z);
+            undecided = resolve_shadow_bundles<kPosed>(scg, sc, sb, gp.reached, gp.P + N * 1e-3f, mask, 0,
+                                                       [&](const uint32_t k, V3& P, V3& Nk) __attribute__((always_inline)) {
+                                                           const float2 xz = area.pxz[k];
+                                                           P = mk(xz.x, g, xz.y), Nk = N;
+                                                       },
+                                                       lit);
+            // (behind the resolver nothing of the unit is read across lanes any more, so the next unit may overwrite the area)
         }
         // ---- a lane per pixel: the planes
-        float vis = static_cast<float>(lit) / static_cast<float>(pairs);
+        float vis = static_cast<float>(lit) / static_cast<float>(sb.pairs);
         MCRT_HOOK_GROUND_PIXEL(vis, gp.reached, mask == 0ull, undecided)
-        if (f.visibility) store_plane(f.visibility, quads_vis, valid, lane, idx, vis);
-        if (f.matte) {
-            const uint32_t a = static_cast<unsigned char>(sclamp(1.0f - vis, 0.0f, 1.0f) * 255.0f + 0.5f);
-            if (quads_matte) {
-                const uint32_t a1 = __shfl_down(a, 1), a2 = __shfl_down(a, 2), a3 = __shfl_down(a, 3);
-                if (valid && (lane & 3) == 0) *reinterpret_cast<uint32_t*>(f.matte + idx) = a | (a1 << 8) | (a2 << 16) | (a3 << 24);
-            } else if (valid) {
-                f.matte[idx] = static_cast<uint8_t>(a);
-            }
-        }
+        if (f.visibility) store_plane(f.visibility, quads_vis, up.valid, lane, up.idx, vis);
+        if (f.matte) store_matte(f.matte, quads_matte, up.valid, lane, up.idx, vis);
     }
 }
 template <int kView>
@@ -517,32 +460,6 @@ using GroundTable = const __attribute__((address_space(4))) GroundFrame*;
 template <int kView>
 __global__ __launch_bounds__(kBlock, kGroundWaves) void ground_batch_kernel(GroundTable table, const GroundShape sh) {
     ground_body<kView>(*(const GroundFrame*)(table + blockIdx.y), sh);
-}
-
-// the unit's tile, and this lane's pixel in it
-struct UnitPixel {
-    TileGeom tg;
-    bool valid;
-    int px, py;
-    size_t idx;
-};
-__device__ __forceinline__ bool unit_pixel(const LayersShape& tiles, const int unit, const int tid, UnitPixel& up) {
-    const mcrt_config& cfg = tiles.cfg;
-    const int tile = unit / tiles.parts, part = unit - tile * tiles.parts;
-    const int tyi = tile / tiles.tiles_x, txi = tile - tyi * tiles.tiles_x;
-    TileGeom& tg = up.tg;
-    tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
-    tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
-    tg.owned_row = tyi, tg.frame_tile = tile;
-    const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
-    const unsigned p0 = static_cast<unsigned>(part) * kBlock;
-    if (p0 >= npix) return false;  // a clipped edge tile holds fewer units
-    const unsigned pix = p0 + static_cast<unsigned>(tid);
-    up.valid = pix < npix;
-    const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(up.valid ? pix : 0u);
-    up.py = tg.y + static_cast<int>(uly), up.px = tg.x + static_cast<int>((up.valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
-    up.idx = static_cast<size_t>(up.py) * static_cast<size_t>(cfg.width) + static_cast<size_t>(up.px);
-    return true;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -556,8 +473,9 @@ __device__ __forceinline__ bool unit_pixel(const LayersShape& tiles, const int u
 //   1 lane / pixel               ray, plane hit, P; the meshes a ray of its hemisphere can meet within the radius
 //                                (rt::hemisphere_candidates) among the tile's; the pixels with one are packed
 //   1 lane / traced pixel        truncated mt19937 (mt[397] from the table of all seeds where the handle has it) → 2·A draws → the
-//                                A world directions in LDS
+//                                A world directions in LDS (AoStream)
 //   1 lane / (traced pixel, sample)   exact any-hit test within the radius on the candidates → occluded count by ballot
+//                                (count_item_rays)
 //   1 lane / pixel               occlusion = 1 - occluded / A, matte: coalesced stores, 16 bytes per four pixels of a row where
 //                                the rows allow
 // ---------------------------------------------------------------------------------------------
@@ -577,24 +495,11 @@ __device__ __forceinline__ unsigned long long ground_occlusion_tile_mask(const S
     const unsigned long long all = n < 64 ? (1ull << n) - 1ull : ~0ull;
     if (sc.hdr->cull_ok == 0 || n >= 64) return all;
     const float slack = sc.hdr->mask_slack;
-    float fx0 = kFltMax, fx1 = -kFltMax, fz0 = kFltMax, fz1 = -kFltMax, reach = 0.0f;
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float fx = static_cast<float>(tg.x + ((c & 1) ? tg.w : 0)), fy = static_cast<float>(tg.y + ((c & 2) ? tg.h : 0));
-        const Ray ray = camera_ray(sc, fx / static_cast<float>(cfg.width), fy / static_cast<float>(cfg.height), aspect);
-        const float t = (g - ray.o.y) / ray.d.y;
-        ok = ok && __builtin_fabsf(ray.d.y) >= 1e-2f && t > 0.0f && t < 1e30f;
-        const float dx = ray.d.x * t, dz = ray.d.z * t;
-        const float x = ray.o.x + dx, z = ray.o.z + dz;
-        fx0 = __builtin_fminf(fx0, x), fx1 = __builtin_fmaxf(fx1, x), fz0 = __builtin_fminf(fz0, z), fz1 = __builtin_fmaxf(fz1, z);
-        reach = __builtin_fmaxf(reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dz)), t));
-        ok = ok && x == x && z == z;  // (fmin / fmax drop a NaN)
-    }
+    const TileFootprint fp = tile_footprint(sc, cfg, tg, aspect, g);
+    const float fx0 = fp.x0, fx1 = fp.x1, fz0 = fp.z0, fz1 = fp.z1;
     const float Rr = radius * 1.001f + slack;
-    ok = ok && reach < 1e30f && slack < 1e30f && Rr < 1e30f;
-    if (!ok) return all;
-    const float fm = 2e-3f * reach + 16.0f * slack;
+    if (!(fp.ok && fp.reach < 1e30f && slack < 1e30f && Rr < 1e30f)) return all;
+    const float fm = 2e-3f * fp.reach + 16.0f * slack;
     const float gy = g + 1e-3f;  // the AO rays' origins
     bool touch = lane < n;
     if (touch) {
@@ -602,15 +507,8 @@ __device__ __forceinline__ unsigned long long ground_occlusion_tile_mask(const S
         if (m.flags & MESH_EMPTY) {
             touch = false;  // intersection.cpp:205: never hit
         } else {
-            V3 lo = ld3(m.lo), hi = ld3(m.hi);
-            bool bounded = true;
-            if (m.flags & MESH_ROTATED) {
-                const float r = m.sphere[3];
-                bounded = r >= 0.0f;
-                lo = mk(m.sphere[0] - r, m.sphere[1] - r, m.sphere[2] - r);
-                hi = mk(m.sphere[0] + r, m.sphere[1] + r, m.sphere[2] + r);
-            }
-            if (bounded) {
+            V3 lo, hi;
+            if (mesh_world_bounds(m, lo, hi)) {
                 const float mx = fm + 1e-4f * (__builtin_fabsf(lo.x) + __builtin_fabsf(hi.x) + __builtin_fabsf(lo.z) + __builtin_fabsf(hi.z));
                 const float my = 64.0f * slack + 1e-5f * (__builtin_fabsf(gy) + __builtin_fabsf(lo.y) + __builtin_fabsf(hi.y));
                 const bool out = (hi.y < gy - my) | (lo.y > gy + Rr + my) | (hi.x + Rr + mx < fx0) | (lo.x - Rr - mx > fx1) | (hi.z + Rr + mx < fz0) |
@@ -623,7 +521,7 @@ __device__ __forceinline__ unsigned long long ground_occlusion_tile_mask(const S
 }
 template <int kView>
 __device__ __forceinline__ void ground_occlusion_body(const GroundOcclusionFrame& __restrict__ f, const GroundOcclusionShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks][inside masks][P.x, P.z][occluded counts][traced list][directions: pass x A x 3 floats]
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][GroundArea][directions: pass x A x 3 floats]
     __shared__ int s_wcnt[kBlock / 64];
     const SceneView scg = view_of(f.scene);
     const mcrt_config& cfg = sh.tiles.cfg;
@@ -634,17 +532,11 @@ __device__ __forceinline__ void ground_occlusion_body(const GroundOcclusionFrame
     const float radius = sh.ao_radius;
     const bool live = radius > 0.0f;  // otherwise no ray can be occluded
     const uint32_t rays = static_cast<uint32_t>(A);  // rays per traced pixel
-    const bool pow2 = (rays & (rays - 1u)) == 0u && rays <= 64u;
     const uint32_t pass = static_cast<uint32_t>(sh.pass);
     const V3 N = mk(0.0f, 1.0f, 0.0f);
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(area);
-    unsigned long long* s_ins = s_cand + kBlock;
-    float2* s_pxz = reinterpret_cast<float2*>(s_ins + kBlock);
-    uint32_t* s_occ = reinterpret_cast<uint32_t*>(s_pxz + kBlock);
-    uint32_t* s_list = s_occ + kBlock;
-    float* s_dir = reinterpret_cast<float*>(s_list + kBlock);
+    GroundArea& area = *reinterpret_cast<GroundArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float* s_dir = reinterpret_cast<float*>(&area + 1);
     // four neighbouring pixels of a row per store: every tile row starts and ends on a four-pixel boundary of the plane
     const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
     const bool quads_occ = quad_rows && (reinterpret_cast<uintptr_t>(f.occlusion) & 15u) == 0;
@@ -656,15 +548,7 @@ __device__ __forceinline__ void ground_occlusion_body(const GroundOcclusionFrame
         UnitPixel up;
         if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
         const unsigned long long mask = live ? ground_occlusion_tile_mask(scg, cfg, up.tg, aspect, g, radius, lane) : 0ull;  // the same in every wave of the workgroup
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
+        stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
         uint32_t occluded = 0u;  // a pixel that misses the plane or has no candidate, and every pixel of a tile no mesh can occlude
         bool traced = false;
 #ifdef MCRT_KERNEL_HOOKS
@@ -679,90 +563,51 @@ __device__ __forceinline__ void ground_occlusion_body(const GroundOcclusionFrame
                     const unsigned long long cand = hemisphere_candidates<kPosed>(scg, O, N, radius) & mask;
                     traced = cand != 0ull || scg.n_meshes > 64;  // meshes beyond the mask are tested per ray
                     if (traced) {
-                        s_cand[tid] = cand;
-                        s_ins[tid] = sh.inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the pixel starts there
-                        s_pxz[tid] = make_float2(gp.P.x, gp.P.z);
+                        area.cand[tid] = cand;
+                        area.ins[tid] = sh.inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the pixel starts there
+                        area.pxz[tid] = make_float2(gp.P.x, gp.P.z);
                     }
                 }
             }
-            s_occ[tid] = 0u;
+            area.count[tid] = 0u;
             int total = 0;
             const int rank = block_rank(traced, s_wcnt, total);
-            if (traced) s_list[rank] = static_cast<uint32_t>(tid);
+            if (traced) area.list[rank] = static_cast<uint32_t>(tid);
             const uint32_t n_traced = static_cast<uint32_t>(total);
             if (n_traced) __syncthreads();  // uniform
             for (uint32_t u0 = 0; u0 < n_traced; u0 += pass) {  // uniform
                 const uint32_t nu = min(pass, n_traced - u0);
                 if (u0) __syncthreads();  // the previous pass's rays have read the directions
-                // ---- a lane per traced pixel: its mt19937 stream and the A directions (raytracer.cpp:42-68)
+                // ---- a lane per traced pixel: its AoStream, the A directions into LDS
                 if (static_cast<uint32_t>(tid) < nu) {
-                    const float2 xz = s_pxz[s_list[u0 + tid]];
-                    const V3 P = mk(xz.x, g, xz.y);
-                    const V3 T = (__builtin_fabsf(N.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), N)) : normalize(cross(mk(0, 1, 0), N));
-                    const V3 B = cross(N, T);
-                    MtShort rng;
-                    const uint32_t seed = ao_seed(P);
-                    if (f.seed_table_full)
-                        rng.seed_known(seed, f.seed_table_full[seed]);  // mt[397] of this seed: one load instead of the 397-step recurrence
-                    else
-                        rng.seed(seed);
+                    const float2 xz = area.pxz[area.list[u0 + tid]];
                     float* dst = s_dir + static_cast<size_t>(tid) * 3 * rays;
+                    AoStream ao(f.seed_table_full, mk(xz.x, g, xz.y), N);
                     for (int i = 0; i < A; ++i) {
-                        const float r1 = rng.uniform();
-                        const float r2 = rng.uniform();
-                        const float sinT = sqrt_pos(1.0f - r1);
-                        const float cosT = sqrt_pos(r1);
-                        float sn, cs;
-                        mcrt_sincosf(kTwoPi * r2, &sn, &cs);
-                        const V3 local = mk(sinT * cs, cosT, sinT * sn);
-                        const V3 world = normalize(T * local.x + N * local.y + B * local.z);
+                        const V3 world = ao.next();
                         dst[3 * i + 0] = world.x;
                         dst[3 * i + 1] = world.y;
                         dst[3 * i + 2] = world.z;
                     }
                 }
                 __syncthreads();
-                // ---- a lane per (traced pixel, sample); every lane of a wave runs the same number of turns (ballot inside)
-                const uint32_t n_rays = nu * rays;
-                for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
-                    const uint32_t q = q0 + static_cast<uint32_t>(lane);
-                    bool blocked = false;
-                    uint32_t k = 0;
-                    if (q < n_rays) {
-                        k = s_list[u0 + q / rays];
-                        const float2 xz = s_pxz[k];
-                        const V3 O = mk(xz.x, g, xz.y) + N * 1e-3f;
-                        blocked = any_hit_masked(sc, Ray{O, ld3(s_dir + static_cast<size_t>(q) * 3)}, radius, s_cand[k], s_ins[k]);
-                    }
-                    if (pow2) {
-                        const unsigned long long bal = __ballot(blocked);
-                        if (q < n_rays && (static_cast<uint32_t>(lane) & (rays - 1u)) == 0u) {
-                            const unsigned long long grp = (rays == 64u) ? bal : ((bal >> lane) & ((1ull << rays) - 1ull));
-                            s_occ[k] = static_cast<uint32_t>(__popcll(grp));
-                        }
-                    } else if (blocked) {
-                        atomicAdd(&s_occ[k], 1u);
-                    }
-                }
+                // ---- a lane per (traced pixel, sample): count_item_rays over the any-hit test within the radius
+                count_item_rays(area.list + u0, nu, rays, area.count, [&](const uint32_t k, const uint32_t q) __attribute__((always_inline)) {
+                    const float2 xz = area.pxz[k];
+                    const V3 O = mk(xz.x, g, xz.y) + N * 1e-3f;
+                    return any_hit_masked(sc, Ray{O, ld3(s_dir + static_cast<size_t>(q) * 3)}, radius, area.cand[k], area.ins[k]);
+                });
             }
             // the counts are complete; behind this barrier nothing of the unit is read across lanes any more, so the next
             // unit may overwrite the area
             if (n_traced) __syncthreads();
-            if (traced) occluded = s_occ[tid];
+            if (traced) occluded = area.count[tid];
         }
         // ---- a lane per pixel: the planes
         float occ = 1.0f - static_cast<float>(occluded) / static_cast<float>(A);  // raytracer.cpp:77
         MCRT_HOOK_GROUND_OCCLUSION_PIXEL(occ, reached, mask == 0ull, traced)
         if (f.occlusion) store_plane(f.occlusion, quads_occ, up.valid, lane, up.idx, occ);
-        if (f.matte) {
-            const uint32_t a = static_cast<unsigned char>(sclamp(1.0f - occ, 0.0f, 1.0f) * 255.0f + 0.5f);
-            if (quads_matte) {
-                const uint32_t a1 = __shfl_down(a, 1), a2 = __shfl_down(a, 2), a3 = __shfl_down(a, 3);
-                if (up.valid && (lane & 3) == 0) *reinterpret_cast<uint32_t*>(f.matte + up.idx) = a | (a1 << 8) | (a2 << 16) | (a3 << 24);
-            } else if (up.valid) {
-                f.matte[up.idx] = static_cast<uint8_t>(a);
-            }
-        }
+        if (f.matte) store_matte(f.matte, quads_matte, up.valid, lane, up.idx, occ);
     }
 }
 template <int kView>
@@ -789,6 +634,8 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void ground_occlusion_batch_k
 //                                are packed again
 //   1 lane / undecided hit       truncated mt19937 (mt[397] from the seed table) at depth 1 → the S disk sample positions in LDS
 //   1 lane / (undecided hit, light sample)   exact any-hit test on the candidates → lit count by ballot
+//                                (decision, packing and pass loop mirror resolve_shadow_bundles at depth 1 in a copy of the pass's own;
+//                                the ray loop is count_item_rays)
 //   1 lane / hit                 shade level 1; then the rest of its chain sequentially — reflect, closest hit over all meshes,
 //                                visibility, shade, to max_bounces (a tenth of the weight per level, a minority of the hits) —
 //                                and the fold back to front from a per-lane stack; the colour returns through LDS
@@ -879,32 +726,31 @@ __device__ __forceinline__ float chain_visibility(const SceneView& scg, const SV
 }
 template <int kView>
 __device__ __forceinline__ void reflection_body(const ReflectionFrame& __restrict__ f, const ReflectionShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][hit records: 4 planes of float4][candidate masks][inside masks][lit counts][undecided list][positions: pass x S x 3 floats]
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][ReflectionArea][positions: pass x S x 3 floats]
     __shared__ int s_wcnt[kBlock / 64];
     const SceneView scg = view_of(f.scene);
     const mcrt_config& cfg = sh.tiles.cfg;
     const int tid = threadIdx.x, lane = tid & 63;
     const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
     const float g = f.ground_y;
-    const V3 lpos = ld3(scg.hdr->light_pos);
-    const float lradius = scg.hdr->light_radius;
     const int S = sh.samples;
     const int max_b = sh.max_bounces;
-    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
-    const bool raw_normal = S > 1;  // computeSoftShadow takes the hit's normal as it is; shade()'s own test normalises it (shading.cpp:76-80)
-    const float R = soft ? lradius : 0.0f;
-    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per hit
-    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
-    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    const bool raw_normal = S > 1;
     const V3 N = mk(0.0f, 1.0f, 0.0f);
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: hit point, ray origin x; 1: normal, origin y; 2: texel colour; 3: ray direction, origin z — then the hit's colour
-    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(s_rec + 4 * kBlock);
-    unsigned long long* s_ins = s_cand + kBlock;
-    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_ins + kBlock);
-    uint32_t* s_und = s_lit + kBlock;
-    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    ReflectionArea& area = *reinterpret_cast<ReflectionArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float4* s_rec = area.rec;  // plane 0: hit point, ray origin x; 1: normal, origin y; 2: texel colour; 3: ray direction, origin z — then the hit's colour
+    const V3 lpos = ld3(scg.hdr->light_pos);
+    const float lradius = scg.hdr->light_radius;
+    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
+    const float R = soft ? lradius : 0.0f;
+    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per hit
+    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    unsigned long long* s_cand = area.sh.cand;
+    unsigned long long* s_ins = area.sh.ins;
+    uint32_t* s_lit = area.sh.lit;
+    uint32_t* s_und = area.sh.und;
+    float* s_pos = reinterpret_cast<float*>(&area + 1);
     const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
     const bool quads_dist = quad_rows && (reinterpret_cast<uintptr_t>(f.distance) & 15u) == 0;
     const bool quads_u8 = quad_rows && (reinterpret_cast<uintptr_t>(f.rgba8) & 15u) == 0;
@@ -914,34 +760,16 @@ __device__ __forceinline__ void reflection_body(const ReflectionFrame& __restric
     const C4 flat_bg{bgc[0], bgc[1], bgc[2], bgc[3]};
     typename ViewSel<kView>::type sc;
     bool staged = false;
-    const int parts = sh.tiles.parts;
-    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * parts;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * sh.tiles.parts;
     for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        const int tile = unit / parts, part = unit - tile * parts;
-        const int tyi = tile / sh.tiles.tiles_x, txi = tile - tyi * sh.tiles.tiles_x;
-        TileGeom tg;
-        tg.x = txi * cfg.tile_size, tg.y = tyi * cfg.tile_size;
-        tg.w = min(cfg.tile_size, cfg.width - tg.x), tg.h = min(cfg.tile_size, cfg.height - tg.y);
-        tg.owned_row = tyi, tg.frame_tile = tile;
-        const unsigned npix = static_cast<unsigned>(tg.w) * static_cast<unsigned>(tg.h);
-        const unsigned p0 = static_cast<unsigned>(part) * kBlock;
-        if (p0 >= npix) continue;  // a clipped edge tile holds fewer units
+        UnitPixel up;
+        if (!unit_tile(sh.tiles, unit, up)) continue;
         // the same in every wave of the workgroup; max_bounces < 1: the reference returns before it intersects
-        const unsigned long long mask = max_b >= 1 ? reflection_tile_mask(scg, cfg, tg, aspect, g, sh.cull != 0, lane) : 0ull;
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
-        const unsigned pix = p0 + static_cast<unsigned>(tid);
-        const bool valid = pix < npix;
-        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(valid ? pix : 0u);
-        const int ly = static_cast<int>(uly), lx = static_cast<int>((valid ? pix : 0u) - uly * static_cast<unsigned>(tg.w));
-        const size_t idx = static_cast<size_t>(tg.y + ly) * static_cast<size_t>(cfg.width) + static_cast<size_t>(tg.x + lx);
+        const unsigned long long mask = max_b >= 1 ? reflection_tile_mask(scg, cfg, up.tg, aspect, g, sh.cull != 0, lane) : 0ull;
+        stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
+        lane_pixel(cfg, tid, up);
+        const bool valid = up.valid;
+        const size_t idx = up.idx;
         float dist = kFltMax;
         C4 col{0.0f, 0.0f, 0.0f, 0.0f};
         if (mask != 0ull) {  // uniform
@@ -950,8 +778,8 @@ __device__ __forceinline__ void reflection_body(const ReflectionFrame& __restric
             Hit h;
             Ray rr{mk(0, 0, 0), mk(0, 0, 0)};
             if (valid) {
-                const float u = (static_cast<float>(tg.x + lx) + 0.5f) / static_cast<float>(cfg.width);
-                const float v = (static_cast<float>(tg.y + ly) + 0.5f) / static_cast<float>(cfg.height);
+                const float u = (static_cast<float>(up.px) + 0.5f) / static_cast<float>(cfg.width);
+                const float v = (static_cast<float>(up.py) + 0.5f) / static_cast<float>(cfg.height);
                 const Ray ray = camera_ray(scg, u, v, aspect);
                 const float t = (g - ray.o.y) / ray.d.y;
                 if (ray.d.y != 0.0f && t > 0.0f && t <= kFltMax) {
@@ -971,7 +799,10 @@ __device__ __forceinline__ void reflection_body(const ReflectionFrame& __restric
             }
             if (n_hits) {  // uniform
                 __syncthreads();
-                // ---- a lane per hit: the whole-bundle decision of its level-1 shadow rays
+                // ---- a lane per hit: the whole-bundle decision of its level-1 shadow rays.  Down to "the counts are complete" this
+                // mirrors resolve_shadow_bundles (kernel_common.h) at depth 1 — decision, packing and pass loop are the pass's own
+                // copy, the ray loop is the shared count_item_rays: through the whole helper the pose-6 frame at 1080p fell outside
+                // the parent's spread in three A/B runs of six (profiles/pass_fold).  A fix to either goes into both
                 const bool mine = tid < n_hits;
                 Hit hit;
                 Ray ray{mk(0, 0, 0), mk(0, 0, 0)};
@@ -1005,30 +836,14 @@ __device__ __forceinline__ void reflection_body(const ReflectionFrame& __restric
                         disk_sample_positions(scg, f.seed_table, nullptr, mk(a.x, a.y, a.z), 1, S, s_pos + static_cast<size_t>(tid) * 3 * S);
                     }
                     __syncthreads();
-                    // ---- a lane per (undecided hit, light sample); every lane of a wave runs the same number of turns (ballot inside)
-                    const uint32_t n_rays = nu * pairs;
-                    for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
-                        const uint32_t q = q0 + static_cast<uint32_t>(lane);
-                        bool visible = false;
-                        uint32_t k = 0;
-                        if (q < n_rays) {
-                            k = s_und[u0 + q / pairs];
-                            const float4 a = s_rec[k], b = s_rec[kBlock + k];
-                            V3 Nk = mk(b.x, b.y, b.z);
-                            if (!raw_normal) Nk = normalize(Nk);
-                            const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
-                            visible = !in_shadow_masked(sc, mk(a.x, a.y, a.z), Nk, target, s_cand[k], s_ins[k]);
-                        }
-                        if (pow2) {
-                            const unsigned long long bal = __ballot(visible);
-                            if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
-                                const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
-                                s_lit[k] = static_cast<uint32_t>(__popcll(grp));
-                            }
-                        } else if (visible) {
-                            atomicAdd(&s_lit[k], 1u);
-                        }
-                    }
+                    // ---- a lane per (undecided hit, light sample): count_item_rays
+                    count_item_rays(s_und + u0, nu, pairs, s_lit, [&](const uint32_t k, const uint32_t q) __attribute__((always_inline)) {
+                        const float4 a = s_rec[k], b = s_rec[kBlock + k];
+                        V3 Nk = mk(b.x, b.y, b.z);
+                        if (!raw_normal) Nk = normalize(Nk);
+                        const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
+                        return !in_shadow_masked(sc, mk(a.x, a.y, a.z), Nk, target, s_cand[k], s_ins[k]);
+                    });
                 }
                 if (n_und) __syncthreads();  // the counts are complete
                 if (undecided) lit = s_lit[tid];
@@ -1115,6 +930,7 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void reflection_batch_kernel(
 //                                are packed again
 //   1 lane / undecided hit       truncated mt19937 (mt[397] from the seed table) at depth 0 → the S disk sample positions in LDS
 //   1 lane / (undecided hit, light sample)   exact any-hit test on the candidates → lit count by ballot
+//                                (the decision and these two phases: resolve_shadow_bundles at depth 0)
 //   1 lane / hit                 visibility = lit / S (one ray in the hard modes), shade; both return through LDS
 //   1 lane / pixel               the planes: 16 bytes per store where rows and alignment allow
 // `occlusion`: the same culling, ray and packing, then the steps of `ao` (render_kernels.hip):
@@ -1122,6 +938,7 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void reflection_batch_kernel(
 //                                without one are done at 1.0, the rest are packed again
 //   1 lane / packed hit          truncated mt19937 (mt[397] from the device's table of all seeds where a render has built it,
 //                                else the recurrence), A cosine-weighted directions, the any-hit test, the count in a register
+//                                (record_occlusion over kernel_common.h's AoStream)
 // ---------------------------------------------------------------------------------------------
 // the pixel-centre ray's closest hit among the meshes of mesh_mask
 template <class SV>
@@ -1131,32 +948,34 @@ __device__ __forceinline__ Hit pixel_hit(const SceneView& scg, const SV& sc, con
     const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
     return hit_scene(sc, camera_ray(scg, u, v, aspect), mesh_mask);
 }
+// resolve_shadow_bundles' accessor over records in LDS whose plane 0 holds the point and plane 1 the normal (`shade`, `bake_shade`):
+// computeSoftShadow takes the normal as it is (raw), shade()'s own test normalises it (shading.cpp:76-80)
+struct RecordPoint {
+    const float4* rec;
+    bool raw_normal;
+    __device__ __forceinline__ void operator()(const uint32_t k, V3& P, V3& N) const {
+        const float4 a = rec[k], b = rec[kBlock + k];
+        P = mk(a.x, a.y, a.z), N = mk(b.x, b.y, b.z);
+        if (!raw_normal) N = normalize(N);
+    }
+};
 template <int kView>
 __device__ __forceinline__ void shade_body(const ShadeFrame& __restrict__ f, const ShadeShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][hit records: 3 planes of float4][candidate masks][inside masks][lit counts][undecided list][positions: pass x S x 3 floats]
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][ShadeArea][positions: pass x S x 3 floats]
     __shared__ int s_wcnt[kBlock / 64];
     const SceneView scg = view_of(f.scene);
     const mcrt_config& cfg = sh.tiles.cfg;
     const int tid = threadIdx.x, lane = tid & 63;
     const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
-    const V3 lpos = ld3(scg.hdr->light_pos);
     const V3 cam = ld3(scg.hdr->cam_pos);  // the origin of every pixel-centre ray (rt::camera_ray)
-    const float lradius = scg.hdr->light_radius;
     const int S = sh.samples;
-    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
-    const bool raw_normal = S > 1;  // computeSoftShadow takes the hit's normal as it is; shade()'s own test normalises it (shading.cpp:76-80)
-    const float R = soft ? lradius : 0.0f;
-    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per hit
-    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
-    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    const bool raw_normal = S > 1;
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: hit point; 1: normal; 2: texel colour — then the hit's colour
-    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(s_rec + 3 * kBlock);
-    unsigned long long* s_ins = s_cand + kBlock;
-    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_ins + kBlock);  // lit counts — then the hit's visibility, bit-cast
-    uint32_t* s_und = s_lit + kBlock;
-    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    ShadeArea& area = *reinterpret_cast<ShadeArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float4* s_rec = area.rec;      // plane 0: hit point; 1: normal; 2: texel colour — then the hit's colour
+    uint32_t* s_lit = area.sh.lit;  // lit counts — then the hit's visibility, bit-cast
+    const ShadowBundles sb = shadow_bundles(scg, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins, area.sh.lit, area.sh.und,
+                                            reinterpret_cast<float*>(&area + 1), s_wcnt);
     const bool quads_vis = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
     const bool vec_direct = (reinterpret_cast<uintptr_t>(f.direct) & 15u) == 0;
     typename ViewSel<kView>::type sc;
@@ -1166,15 +985,7 @@ __device__ __forceinline__ void shade_body(const ShadeFrame& __restrict__ f, con
         UnitPixel up;
         if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
         const unsigned long long mask = layers_tile_mask(scg, cfg, up.tg, aspect, lane);  // the same in every wave of the workgroup
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
+        stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
         float vis = 1.0f;
         C4 col{0.0f, 0.0f, 0.0f, 0.0f};
         if (mask != 0ull) {  // uniform
@@ -1194,68 +1005,21 @@ __device__ __forceinline__ void shade_body(const ShadeFrame& __restrict__ f, con
             }
             if (n_hits) {  // uniform
                 __syncthreads();
-                // ---- a lane per hit: the whole-bundle decision of its shadow rays
+                // ---- a lane per hit: its record, then resolve_shadow_bundles over its shadow rays (depth 0)
                 const bool mine = tid < n_hits;
                 Hit hit;
                 hit.hit = true;
-                bool undecided = false;
                 uint32_t lit = 0u;
+                V3 O = mk(0, 0, 0);
                 if (mine) {
                     const float4 a = s_rec[tid], b = s_rec[kBlock + tid], c = s_rec[2 * kBlock + tid];
                     hit.p = mk(a.x, a.y, a.z), hit.n = mk(b.x, b.y, b.z), hit.tex = C4{c.x, c.y, c.z, c.w};
-                    const V3 O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
-                    unsigned long long cand;
-                    const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
-                    undecided = known < 0;
-                    s_cand[tid] = cand;
-                    s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
-                    if (!undecided) lit = static_cast<uint32_t>(known);
+                    O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
                 }
-                s_lit[tid] = 0u;
-                int total = 0;
-                const int urank = block_rank(undecided, s_wcnt, total);
-                if (undecided) s_und[urank] = static_cast<uint32_t>(tid);
-                const uint32_t n_und = static_cast<uint32_t>(total);
-                if (n_und) __syncthreads();  // uniform
-                for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
-                    const uint32_t nu = min(pass, n_und - u0);
-                    if (u0) __syncthreads();  // the previous pass's rays have read the positions
-                    // ---- a lane per undecided hit: its mt19937 stream at depth 0 and the S disk sample positions
-                    if (soft && static_cast<uint32_t>(tid) < nu) {
-                        const float4 a = s_rec[s_und[u0 + tid]];
-                        disk_sample_positions(scg, f.seed_table, nullptr, mk(a.x, a.y, a.z), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
-                    }
-                    __syncthreads();
-                    // ---- a lane per (undecided hit, light sample); every lane of a wave runs the same number of turns (ballot inside)
-                    const uint32_t n_rays = nu * pairs;
-                    for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
-                        const uint32_t q = q0 + static_cast<uint32_t>(lane);
-                        bool visible = false;
-                        uint32_t k = 0;
-                        if (q < n_rays) {
-                            k = s_und[u0 + q / pairs];
-                            const float4 a = s_rec[k], b = s_rec[kBlock + k];
-                            V3 Nk = mk(b.x, b.y, b.z);
-                            if (!raw_normal) Nk = normalize(Nk);
-                            const V3 target = soft ? ld3(s_pos + static_cast<size_t>(q) * 3) : lpos;
-                            visible = !in_shadow_masked(sc, mk(a.x, a.y, a.z), Nk, target, s_cand[k], s_ins[k]);
-                        }
-                        if (pow2) {
-                            const unsigned long long bal = __ballot(visible);
-                            if (q < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
-                                const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
-                                s_lit[k] = static_cast<uint32_t>(__popcll(grp));
-                            }
-                        } else if (visible) {
-                            atomicAdd(&s_lit[k], 1u);
-                        }
-                    }
-                }
-                if (n_und) __syncthreads();  // the counts are complete
-                if (undecided) lit = s_lit[tid];
+                resolve_shadow_bundles<kPosed>(scg, sc, sb, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
                 // ---- a lane per hit: the visibility term and shade (raytracer.cpp:107-117)
                 if (mine) {
-                    const float v = soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
                     const C4 c = shade(scg, hit, normalize(cam - hit.p), v);
                     s_lit[tid] = __float_as_uint(v);  // (entry and record tid are this lane's alone by now)
                     s_rec[2 * kBlock + tid] = make_float4(c.r, c.g, c.b, c.a);
@@ -1290,9 +1054,24 @@ template <int kView>
 __global__ __launch_bounds__(kBlock, kGroundWaves) void shade_batch_kernel(ShadeTable table, const ShadeShape sh) {
     shade_body<kView>(*(const ShadeFrame*)(table + blockIdx.y), sh);
 }
+// computeAO's value at the point of record k by the lane that owns it (`ao`, step 3): its AoStream traced in place against the
+// record's candidates, the count in a register
+template <class SV>
+__device__ __forceinline__ float record_occlusion(const SV& sc, const uint32_t* __restrict__ seed_table_full, const float4* s_rec, const uint32_t k,
+                                                  const unsigned long long cand, const bool inside_fast, const float radius, const int A) {
+    const float4 a = s_rec[k], b = s_rec[kBlock + k];
+    const V3 P = mk(a.x, a.y, a.z), N = normalize(mk(b.x, b.y, b.z));
+    const V3 O = P + N * 1e-3f;
+    const unsigned long long inside = inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the point starts there
+    uint32_t occluded = 0;
+    AoStream ao(seed_table_full, P, N);
+    for (int i = 0; i < A; ++i)
+        if (any_hit_masked(sc, Ray{O, ao.next()}, radius, cand, inside)) ++occluded;
+    return 1.0f - static_cast<float>(occluded) / static_cast<float>(A);  // raytracer.cpp:77
+}
 template <int kView>
 __device__ __forceinline__ void occlusion_body(const ShadeFrame& __restrict__ f, const ShadeShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][hit records: 2 planes of float4][candidate masks][traced list][values]
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][OcclusionArea]
     __shared__ int s_wcnt[kBlock / 64];
     const SceneView scg = view_of(f.scene);
     const mcrt_config& cfg = sh.tiles.cfg;
@@ -1301,11 +1080,11 @@ __device__ __forceinline__ void occlusion_body(const ShadeFrame& __restrict__ f,
     const int A = sh.ao_samples;
     const float radius = sh.ao_radius;
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: hit point; 1: normal
-    unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(s_rec + 2 * kBlock);
-    uint32_t* s_list = reinterpret_cast<uint32_t*>(s_mask + kBlock);
-    float* s_val = reinterpret_cast<float*>(s_list + kBlock);
+    OcclusionArea& area = *reinterpret_cast<OcclusionArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float4* s_rec = area.rec;  // plane 0: hit point; 1: normal
+    unsigned long long* s_mask = area.mask;
+    uint32_t* s_list = area.list;
+    float* s_val = area.val;
     const bool quads = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.occlusion) & 15u) == 0;
     typename ViewSel<kView>::type sc;
     bool staged = false;
@@ -1314,15 +1093,7 @@ __device__ __forceinline__ void occlusion_body(const ShadeFrame& __restrict__ f,
         UnitPixel up;
         if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
         const unsigned long long mask = layers_tile_mask(scg, cfg, up.tg, aspect, lane);  // the same in every wave of the workgroup
-        if (mask != 0ull && !staged) {
-            if constexpr (kView == kViewHbm) {
-                sc = scg;
-            } else {
-                const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-                sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-            }
-            staged = true;
-        }
+        stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
         float occ = 1.0f;
         if (mask != 0ull) {  // uniform
             // ---- a lane per pixel: the ray and its closest hit
@@ -1354,35 +1125,10 @@ __device__ __forceinline__ void occlusion_body(const ShadeFrame& __restrict__ f,
                 const int trank = block_rank(traced, s_wcnt, total);
                 if (traced) s_list[trank] = static_cast<uint32_t>(tid);
                 __syncthreads();
-                // ---- a lane per traced hit: its mt19937 stream, the A directions and their any-hit tests (`ao`, step 3)
+                // ---- a lane per traced hit: record_occlusion
                 if (tid < total) {
                     const uint32_t k = s_list[tid];
-                    const float4 a = s_rec[k], b = s_rec[kBlock + k];
-                    const V3 P = mk(a.x, a.y, a.z), N = normalize(mk(b.x, b.y, b.z));
-                    const V3 T = (__builtin_fabsf(N.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), N)) : normalize(cross(mk(0, 1, 0), N));
-                    const V3 B = cross(N, T);
-                    const unsigned long long cand = s_mask[k];
-                    const V3 O = P + N * 1e-3f;
-                    const unsigned long long inside = sh.inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the hit starts there
-                    MtShort rng;
-                    const uint32_t seed = ao_seed(P);
-                    if (f.seed_table_full)
-                        rng.seed_known(seed, f.seed_table_full[seed]);  // mt[397] of this seed: one load instead of the 397-step recurrence
-                    else
-                        rng.seed(seed);
-                    uint32_t occluded = 0;
-                    for (int i = 0; i < A; ++i) {
-                        const float r1 = rng.uniform();
-                        const float r2 = rng.uniform();
-                        const float sinT = sqrt_pos(1.0f - r1);
-                        const float cosT = sqrt_pos(r1);
-                        float sn, cs;
-                        mcrt_sincosf(kTwoPi * r2, &sn, &cs);
-                        const V3 local = mk(sinT * cs, cosT, sinT * sn);
-                        const V3 world = normalize(T * local.x + N * local.y + B * local.z);
-                        if (any_hit_masked(sc, Ray{O, world}, radius, cand, inside)) ++occluded;
-                    }
-                    s_val[k] = 1.0f - static_cast<float>(occluded) / static_cast<float>(A);  // raytracer.cpp:77
+                    s_val[k] = record_occlusion(sc, f.seed_table_full, s_rec, k, s_mask[k], sh.inside_fast != 0, radius, A);
                 }
                 __syncthreads();
                 if (is_hit) occ = s_val[rank];
@@ -1414,6 +1160,7 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void occlusion_batch_kernel(S
 //   1 lane / live texel          P, N; the whole-bundle decision from P + N * 1e-3f; the undecided are packed again
 //   1 lane / undecided point     truncated mt19937 at depth 0 → the S disk sample positions in LDS
 //   1 lane / (undecided point, light sample)   exact any-hit test on the candidates → lit count by ballot
+//                                (the decision and these two phases: resolve_shadow_bundles at depth 0)
 //   1 lane / live texel          visibility = lit / S (one ray in the hard modes), shade with the view vector N; both are
 //                                ADDED to the lane's sums in the order the header defines
 //   1 lane / texel               the means return through LDS; the planes: 16 bytes per store where the alignment allows
@@ -1527,40 +1274,27 @@ __device__ __forceinline__ BakeLane bake_lane(const BakeFrame& __restrict__ f, c
 }
 template <int kView>
 __device__ __forceinline__ void bake_shade_body(const BakeFrame& __restrict__ f, const BakeShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][point records: 2 planes of float4][texel records: colour, owner][candidate masks][inside masks][lit counts][undecided list][positions: pass x S x 3 floats]
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][BakeShadeArea][positions: pass x S x 3 floats]
     __shared__ int s_wcnt[kBlock / 64];
     const int n_units = (f.n_texels + kBlock - 1) / kBlock;
     if (static_cast<int>(blockIdx.x) >= n_units) return;  // (uniform; before the collective staging: the frames of a batch differ in size)
     const SceneView scg = view_of(f.scene);
     const int tid = threadIdx.x, lane = tid & 63;
-    const V3 lpos = ld3(scg.hdr->light_pos);
-    const float lradius = scg.hdr->light_radius;
     const int S = sh.samples, q = sh.grid;
-    const bool soft = S > 1 && !(lradius < 1e-4f);  // shading.cpp:31: otherwise the one isInShadow ray towards the light's centre
-    const bool raw_normal = S > 1;  // computeSoftShadow takes the normal as it is; shade()'s own test normalises it (shading.cpp:76-80)
-    const float R = soft ? lradius : 0.0f;
-    const uint32_t pairs = soft ? static_cast<uint32_t>(S) : 1u;  // rays per point
-    const bool pow2 = (pairs & (pairs - 1u)) == 0u && pairs <= 64u;
-    const uint32_t pass = static_cast<uint32_t>(sh.pass);
+    const bool raw_normal = S > 1;
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: point; 1: normal
-    float4* s_tex = s_rec + 2 * kBlock;               // the live texel's colour — then its mean colour
-    int4* s_own = reinterpret_cast<int4*>(s_tex + kBlock);  // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
-    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(s_own + kBlock);
-    unsigned long long* s_ins = s_cand + kBlock;
-    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_ins + kBlock);  // lit counts — then the texel's mean visibility, bit-cast
-    uint32_t* s_und = s_lit + kBlock;
-    float* s_pos = reinterpret_cast<float*>(s_und + kBlock);
+    BakeShadeArea& area = *reinterpret_cast<BakeShadeArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float4* s_rec = area.rec;       // plane 0: point; 1: normal
+    float4* s_tex = area.tex;       // the live texel's colour — then its mean colour
+    int4* s_own = area.own;         // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
+    uint32_t* s_lit = area.sh.lit;  // lit counts — then the texel's mean visibility, bit-cast
+    const ShadowBundles sb = shadow_bundles(scg, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins, area.sh.lit, area.sh.und,
+                                            reinterpret_cast<float*>(&area + 1), s_wcnt);
     const bool quads_vis = (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
     const bool vec_direct = (reinterpret_cast<uintptr_t>(f.direct) & 15u) == 0;
     typename ViewSel<kView>::type sc;
-    if constexpr (kView == kViewHbm) {
-        sc = scg;
-    } else {
-        const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-        sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-    }
+    bool staged = false;
+    stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, true, sc, staged);
     for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
         // ---- a lane per texel: owner, colour, the geometry planes; the live texels are packed
         const BakeLane b = bake_lane(f, scg, sc, unit, tid, sh.geometry != 0);
@@ -1592,66 +1326,19 @@ __device__ __forceinline__ void bake_shade_body(const BakeFrame& __restrict__ f,
             }
             for (int sub = 0; sub < q * q; ++sub) {  // uniform: j outer, i inner
                 const int sj = sub / q, si = sub - sj * q;
-                // ---- a lane per live texel: the sub-sample's point and the whole-bundle decision of its shadow rays
-                bool undecided = false;
+                // ---- a lane per live texel: the sub-sample's point, then resolve_shadow_bundles over its shadow rays (depth 0)
                 uint32_t lit = 0u;
+                V3 O = mk(0, 0, 0);
                 if (mine) {
                     bake_point(sc, t, si, sj, q, hit.p, hit.n);
                     s_rec[tid] = make_float4(hit.p.x, hit.p.y, hit.p.z, 0.0f);
                     s_rec[kBlock + tid] = make_float4(hit.n.x, hit.n.y, hit.n.z, 0.0f);
-                    const V3 O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
-                    unsigned long long cand;
-                    const int known = bundle_classify<kPosed>(scg, sc, O, lpos, R, static_cast<int>(pairs), sh.bundle_decisions != 0, cand);
-                    undecided = known < 0;
-                    s_cand[tid] = cand;
-                    s_ins[tid] = (undecided && sh.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
-                    if (!undecided) lit = static_cast<uint32_t>(known);
+                    O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
                 }
-                s_lit[tid] = 0u;
-                int total = 0;
-                const int urank = block_rank(undecided, s_wcnt, total);
-                if (undecided) s_und[urank] = static_cast<uint32_t>(tid);
-                const uint32_t n_und = static_cast<uint32_t>(total);
-                if (n_und) __syncthreads();  // uniform
-                for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
-                    const uint32_t nu = min(pass, n_und - u0);
-                    if (u0) __syncthreads();  // the previous pass's rays have read the positions
-                    // ---- a lane per undecided point: its mt19937 stream at depth 0 and the S disk sample positions
-                    if (soft && static_cast<uint32_t>(tid) < nu) {
-                        const float4 a = s_rec[s_und[u0 + tid]];
-                        disk_sample_positions(scg, f.seed_table, nullptr, mk(a.x, a.y, a.z), 0, S, s_pos + static_cast<size_t>(tid) * 3 * S);
-                    }
-                    __syncthreads();
-                    // ---- a lane per (undecided point, light sample); every lane of a wave runs the same number of turns (ballot inside)
-                    const uint32_t n_rays = nu * pairs;
-                    for (uint32_t q0 = static_cast<uint32_t>(tid) & ~63u; q0 < n_rays; q0 += kBlock) {
-                        const uint32_t qi = q0 + static_cast<uint32_t>(lane);
-                        bool visible = false;
-                        uint32_t k = 0;
-                        if (qi < n_rays) {
-                            k = s_und[u0 + qi / pairs];
-                            const float4 a = s_rec[k], nb = s_rec[kBlock + k];
-                            V3 Nk = mk(nb.x, nb.y, nb.z);
-                            if (!raw_normal) Nk = normalize(Nk);
-                            const V3 target = soft ? ld3(s_pos + static_cast<size_t>(qi) * 3) : lpos;
-                            visible = !in_shadow_masked(sc, mk(a.x, a.y, a.z), Nk, target, s_cand[k], s_ins[k]);
-                        }
-                        if (pow2) {
-                            const unsigned long long bal = __ballot(visible);
-                            if (qi < n_rays && (static_cast<uint32_t>(lane) & (pairs - 1u)) == 0u) {
-                                const unsigned long long grp = (pairs == 64u) ? bal : ((bal >> lane) & ((1ull << pairs) - 1ull));
-                                s_lit[k] = static_cast<uint32_t>(__popcll(grp));
-                            }
-                        } else if (visible) {
-                            atomicAdd(&s_lit[k], 1u);
-                        }
-                    }
-                }
-                if (n_und) __syncthreads();  // the counts are complete; nothing of this sub-sample is read across lanes any more
-                if (undecided) lit = s_lit[tid];
+                resolve_shadow_bundles<kPosed>(scg, sc, sb, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
                 // ---- a lane per live texel: the visibility term and shade, added in the defined order
                 if (mine) {
-                    const float v = soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
                     const C4 c = shade(scg, hit, hit.n, v);
                     if (sub == 0) {
                         vsum = v, csum = c;
@@ -1694,7 +1381,7 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void bake_shade_batch_kernel(
 }
 template <int kView>
 __device__ __forceinline__ void bake_occlusion_body(const BakeFrame& __restrict__ f, const BakeShape& __restrict__ sh) {
-    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][point records: 2 planes of float4][texel records: owner][candidate masks][traced list][values]
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][BakeOcclusionArea]
     __shared__ int s_wcnt[kBlock / 64];
     const int n_units = (f.n_texels + kBlock - 1) / kBlock;
     if (static_cast<int>(blockIdx.x) >= n_units) return;  // (uniform; before the collective staging)
@@ -1703,20 +1390,16 @@ __device__ __forceinline__ void bake_occlusion_body(const BakeFrame& __restrict_
     const int A = sh.ao_samples, q = sh.grid;
     const float radius = sh.ao_radius;
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    unsigned char* area = s_dyn + ((scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15));
-    float4* s_rec = reinterpret_cast<float4*>(area);  // plane 0: point; 1: normal
-    int4* s_own = reinterpret_cast<int4*>(s_rec + 2 * kBlock);  // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
-    unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(s_own + kBlock);
-    uint32_t* s_list = reinterpret_cast<uint32_t*>(s_mask + kBlock);
-    float* s_val = reinterpret_cast<float*>(s_list + kBlock);
+    BakeOcclusionArea& area = *reinterpret_cast<BakeOcclusionArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float4* s_rec = area.rec;  // plane 0: point; 1: normal
+    int4* s_own = area.own;    // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
+    unsigned long long* s_mask = area.mask;
+    uint32_t* s_list = area.list;
+    float* s_val = area.val;
     const bool quads = (reinterpret_cast<uintptr_t>(f.occlusion) & 15u) == 0;
     typename ViewSel<kView>::type sc;
-    if constexpr (kView == kViewHbm) {
-        sc = scg;
-    } else {
-        const LdsTables t = stage_tables(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn);
-        sc = view_with_lds<kView == kViewLds>(scg, t.abits, t.faces, t.mtab);
-    }
+    bool staged = false;
+    stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, true, sc, staged);
     for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
         // ---- a lane per texel: owner, colour, the geometry planes; the live texels are packed
         const BakeLane b = bake_lane(f, scg, sc, unit, tid, sh.geometry != 0);
@@ -1754,35 +1437,10 @@ __device__ __forceinline__ void bake_occlusion_body(const BakeFrame& __restrict_
                 const int trank = block_rank(traced, s_wcnt, total);
                 if (traced) s_list[trank] = static_cast<uint32_t>(tid);
                 __syncthreads();
-                // ---- a lane per traced point: its mt19937 stream, the A directions and their any-hit tests (`ao`, step 3)
+                // ---- a lane per traced point: record_occlusion
                 if (tid < total) {
                     const uint32_t k = s_list[tid];
-                    const float4 a = s_rec[k], nb = s_rec[kBlock + k];
-                    const V3 P = mk(a.x, a.y, a.z), N = normalize(mk(nb.x, nb.y, nb.z));
-                    const V3 T = (__builtin_fabsf(N.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), N)) : normalize(cross(mk(0, 1, 0), N));
-                    const V3 B = cross(N, T);
-                    const unsigned long long cand = s_mask[k];
-                    const V3 O = P + N * 1e-3f;
-                    const unsigned long long inside = sh.inside_fast ? origin_inside_boxes(sc, O, cand) : 0ull;  // every ray of the point starts there
-                    MtShort rng;
-                    const uint32_t seed = ao_seed(P);
-                    if (f.seed_table_full)
-                        rng.seed_known(seed, f.seed_table_full[seed]);  // mt[397] of this seed: one load instead of the 397-step recurrence
-                    else
-                        rng.seed(seed);
-                    uint32_t occluded = 0;
-                    for (int s = 0; s < A; ++s) {
-                        const float r1 = rng.uniform();
-                        const float r2 = rng.uniform();
-                        const float sinT = sqrt_pos(1.0f - r1);
-                        const float cosT = sqrt_pos(r1);
-                        float sn, cs;
-                        mcrt_sincosf(kTwoPi * r2, &sn, &cs);
-                        const V3 local = mk(sinT * cs, cosT, sinT * sn);
-                        const V3 world = normalize(T * local.x + N * local.y + B * local.z);
-                        if (any_hit_masked(sc, Ray{O, world}, radius, cand, inside)) ++occluded;
-                    }
-                    s_val[k] = 1.0f - static_cast<float>(occluded) / static_cast<float>(A);  // raytracer.cpp:77
+                    s_val[k] = record_occlusion(sc, f.seed_table_full, s_rec, k, s_mask[k], sh.inside_fast != 0, radius, A);
                 }
                 __syncthreads();
                 if (mine) {

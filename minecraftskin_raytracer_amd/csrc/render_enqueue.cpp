@@ -438,7 +438,7 @@ int layers_frame_of(const mcrt_scene* s, const mcrt_layers& out, size_t index, s
     f.normal = out.normal ? reinterpret_cast<float4*>(out.normal) + off : nullptr;
     f.albedo = out.albedo ? reinterpret_cast<float4*>(out.albedo) + off : nullptr;
     f.id = out.id ? reinterpret_cast<int4*>(out.id) + off : nullptr;
-    return layers_view(f, s->alpha_words, s->n_meshes, s->posed);
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
 }
 // the same for a ground pass (mcrt_render_ground_device & co), which also reads the device's seed table through the handle
 int ground_frame_of(const mcrt_scene* s, const mcrt_ground& out, float ground_y, size_t index, size_t stride, GroundFrame& f) {
@@ -450,7 +450,7 @@ int ground_frame_of(const mcrt_scene* s, const mcrt_ground& out, float ground_y,
     f.matte = out.matte ? out.matte + off : nullptr;
     f.seed_table = s->seed_table;
     f.ground_y = ground_y;
-    return ground_view(f, s->alpha_words, s->n_meshes, s->posed);
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
 }
 // and for a ground-occlusion pass (mcrt_render_ground_occlusion_device & co), which reads the table of all seeds where the handle holds it
 int ground_occlusion_frame_of(const mcrt_scene* s, const mcrt_ground_occlusion& out, float ground_y, size_t index, size_t stride, GroundOcclusionFrame& f) {
@@ -461,7 +461,7 @@ int ground_occlusion_frame_of(const mcrt_scene* s, const mcrt_ground_occlusion& 
     f.matte = out.matte ? out.matte + off : nullptr;
     f.seed_table_full = s->seed_table_full;
     f.ground_y = ground_y;
-    return ground_occlusion_view(f, s->alpha_words, s->n_meshes, s->posed);
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
 }
 // and for a reflection pass (mcrt_render_reflection_device & co)
 int reflection_frame_of(const mcrt_scene* s, const mcrt_reflection& out, float ground_y, size_t index, size_t stride, ReflectionFrame& f) {
@@ -473,7 +473,7 @@ int reflection_frame_of(const mcrt_scene* s, const mcrt_reflection& out, float g
     f.distance = out.distance ? out.distance + off : nullptr;
     f.seed_table = s->seed_table;
     f.ground_y = ground_y;
-    return reflection_view(f, s->alpha_words, s->n_meshes, s->posed);
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
 }
 // and for a light pass (mcrt_render_light_device & co), which reads both seed tables
 int shade_frame_of(const mcrt_scene* s, const mcrt_light_planes& out, size_t index, size_t stride, ShadeFrame& f) {
@@ -485,7 +485,7 @@ int shade_frame_of(const mcrt_scene* s, const mcrt_light_planes& out, size_t ind
     f.direct = out.direct ? out.direct + off * 4 : nullptr;
     f.seed_table = s->seed_table;
     f.seed_table_full = s->seed_table_full;
-    return shade_view(f, s->alpha_words, s->n_meshes, s->posed);
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
 }
 // and for a light bake (mcrt_bake_light_device & co): the planes `index * stride` TEXELS on, the handle's owner faces behind its blob
 int bake_frame_of(const mcrt_scene* s, const mcrt_bake_planes& out, size_t index, size_t stride, BakeFrame& f) {
@@ -502,7 +502,7 @@ int bake_frame_of(const mcrt_scene* s, const mcrt_bake_planes& out, size_t index
     f.direct = out.direct ? out.direct + off * 4 : nullptr;
     f.seed_table = s->seed_table;
     f.seed_table_full = s->seed_table_full;
-    return bake_view(f, s->alpha_words, s->n_meshes, s->posed);
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
 }
 
 // What the layers and the ground entry points check alike, before any device work (only the last check looks inside the
@@ -544,6 +544,35 @@ int launch_pass(int device, const std::vector<Frame>& frames, hipStream_t stream
     for (int c0 = 0; c0 < n && e == hipSuccess; c0 += kLayersBatchMaxFrames) e = many(d_table + c0, std::min(kLayersBatchMaxFrames, n - c0));
     if (e == hipSuccess) e = table.commit(stream);
     if (e != hipSuccess) return hip_fail(e, what);
+    return MCRT_OK;
+}
+
+// The tail the six pass entry points share, behind their argument checks: the n frame records from frame_of(i, frame) (which
+// returns the frame's kernel variant), the batch's variant, the largest dynamic LDS of the pass's one or two kernels over the
+// frames (lds_of(frame), PassLds), and the launches: one(frame, view) or many(d_table, m, view, lds).
+struct PassLds {
+    size_t first = 0, second = 0;
+};
+template <class Frame, class FrameOf, class LdsOf, class One, class Many>
+int enqueue_pass(int device, int n, hipStream_t stream, const char* what, FrameOf frame_of, LdsOf lds_of, One one, Many many) {
+    std::vector<Frame> frames(static_cast<size_t>(n));
+    std::vector<int> views(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) views[static_cast<size_t>(i)] = frame_of(i, frames[static_cast<size_t>(i)]);
+    const int view = batch_view_of(frames.data(), views.data(), n);
+    PassLds dyn;
+    for (const Frame& f : frames) {
+        const PassLds d = lds_of(f);
+        dyn.first = std::max(dyn.first, d.first), dyn.second = std::max(dyn.second, d.second);
+    }
+    return launch_pass(
+        device, frames, stream, what, [&](const Frame& f) { return one(f, view); }, [&](const Frame* d_table, int m) { return many(d_table, m, view, dyn); });
+}
+
+// the floor passes' heights: one per frame, finite
+int check_ground_y(int n, const float* ground_y) {
+    if (n > 0 && !ground_y) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
     return MCRT_OK;
 }
 
@@ -759,15 +788,10 @@ int render_layers_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
     LayersShape shape;
     if (!make_layers_shape(*cfg, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
     HIP_TRY(hipSetDevice(device));
-    std::vector<LayersFrame> frames(static_cast<size_t>(n));
-    std::vector<int> views(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) views[static_cast<size_t>(i)] = layers_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
-    const int view = layers_batch_view(frames.data(), views.data(), n);
-    size_t dyn = 0;
-    for (const LayersFrame& f : frames) dyn = std::max(dyn, layers_lds_bytes(f));
-    return launch_pass(
-        device, frames, stream, "layers launches", [&](const LayersFrame& f) { return launch_layers(f, shape, view, stream); },
-        [&](const LayersFrame* d_table, int m) { return launch_layers_batch(d_table, m, shape, view, dyn, stream); });
+    return enqueue_pass<LayersFrame>(
+        device, n, stream, "layers launches", [&](int i, LayersFrame& f) { return layers_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, f); },
+        [&](const LayersFrame& f) { return PassLds{layers_lds_bytes(f), 0}; }, [&](const LayersFrame& f, int view) { return launch_layers(f, shape, view, stream); },
+        [&](const LayersFrame* d_table, int m, int view, PassLds dyn) { return launch_layers_batch(d_table, m, shape, view, dyn.first, stream); });
 }
 
 // ---- ground shadow (mcrt_render_ground_device & co): like a layers pass it reads the scene blob alone — and the device's seed
@@ -776,9 +800,7 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
                                hipStream_t stream) {
     // argument checks, before any device work
     if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
-    if (n > 0 && !ground_y) return fail(MCRT_ERR_INVALID, "NULL argument");
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (const int rc = check_ground_y(n, ground_y); rc != MCRT_OK) return rc;
     if (cfg && cfg->soft_shadows && cfg->shadow_samples > kGroundMaxSamples)
         return fail(MCRT_ERR_INVALID, "a ground pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
     bool run;
@@ -789,16 +811,10 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
     GroundShape shape;
     if (!make_ground_shape(*cfg, decisions, inside_fast, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
     HIP_TRY(hipSetDevice(device));
-    std::vector<GroundFrame> frames(static_cast<size_t>(n));
-    std::vector<int> views(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i)
-        views[static_cast<size_t>(i)] = ground_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
-    const int view = ground_batch_view(frames.data(), views.data(), n);
-    size_t dyn = 0;
-    for (const GroundFrame& f : frames) dyn = std::max(dyn, ground_lds_bytes(f, shape));
-    return launch_pass(
-        device, frames, stream, "ground launches", [&](const GroundFrame& f) { return launch_ground(f, shape, view, stream); },
-        [&](const GroundFrame* d_table, int m) { return launch_ground_batch(d_table, m, shape, view, dyn, stream); });
+    return enqueue_pass<GroundFrame>(
+        device, n, stream, "ground launches", [&](int i, GroundFrame& f) { return ground_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, f); },
+        [&](const GroundFrame& f) { return PassLds{ground_lds_bytes(f, shape), 0}; }, [&](const GroundFrame& f, int view) { return launch_ground(f, shape, view, stream); },
+        [&](const GroundFrame* d_table, int m, int view, PassLds dyn) { return launch_ground_batch(d_table, m, shape, view, dyn.first, stream); });
 }
 
 // ---- ground occlusion (mcrt_render_ground_occlusion_device & co): the ground pass's host path with another kernel — the scene
@@ -808,9 +824,7 @@ int render_ground_occlusion_batch_device(mcrt_scene* const* scenes, int n, const
                                          size_t stride, hipStream_t stream) {
     // argument checks, before any device work
     if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "both planes are NULL");
-    if (n > 0 && !ground_y) return fail(MCRT_ERR_INVALID, "NULL argument");
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (const int rc = check_ground_y(n, ground_y); rc != MCRT_OK) return rc;
     if (cfg)
         if (const int rc = check_ground_occlusion_config(cfg); rc != MCRT_OK) return rc;
     bool run;
@@ -820,19 +834,15 @@ int render_ground_occlusion_batch_device(mcrt_scene* const* scenes, int n, const
     GroundOcclusionShape shape;
     if (!make_ground_occlusion_shape(*cfg, inside_fast, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
     HIP_TRY(hipSetDevice(device));
-    std::vector<GroundOcclusionFrame> frames(static_cast<size_t>(n));
-    std::vector<int> views(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) {
-        share_full_seed_table(scenes[i]);
-        views[static_cast<size_t>(i)] =
-            ground_occlusion_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
-    }
-    const int view = ground_occlusion_batch_view(frames.data(), views.data(), n);
-    size_t dyn = 0;
-    for (const GroundOcclusionFrame& f : frames) dyn = std::max(dyn, ground_occlusion_lds_bytes(f, shape));
-    return launch_pass(
-        device, frames, stream, "ground occlusion launches", [&](const GroundOcclusionFrame& f) { return launch_ground_occlusion(f, shape, view, stream); },
-        [&](const GroundOcclusionFrame* d_table, int m) { return launch_ground_occlusion_batch(d_table, m, shape, view, dyn, stream); });
+    return enqueue_pass<GroundOcclusionFrame>(
+        device, n, stream, "ground occlusion launches",
+        [&](int i, GroundOcclusionFrame& f) {
+            share_full_seed_table(scenes[i]);
+            return ground_occlusion_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, f);
+        },
+        [&](const GroundOcclusionFrame& f) { return PassLds{ground_occlusion_lds_bytes(f, shape), 0}; },
+        [&](const GroundOcclusionFrame& f, int view) { return launch_ground_occlusion(f, shape, view, stream); },
+        [&](const GroundOcclusionFrame* d_table, int m, int view, PassLds dyn) { return launch_ground_occlusion_batch(d_table, m, shape, view, dyn.first, stream); });
 }
 
 // ---- ground reflection (mcrt_render_reflection_device & co): the ground pass's host path with another kernel — the scene blob
@@ -841,9 +851,7 @@ int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_
                                    size_t stride, hipStream_t stream) {
     // argument checks, before any device work
     if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
-    if (n > 0 && !ground_y) return fail(MCRT_ERR_INVALID, "NULL argument");
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
+    if (const int rc = check_ground_y(n, ground_y); rc != MCRT_OK) return rc;
     if (cfg && cfg->soft_shadows && cfg->shadow_samples > kGroundMaxSamples)
         return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
     if (cfg && cfg->max_bounces > kReflectMaxBounces) return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 8 bounces (its per-lane colour stack)");
@@ -856,16 +864,12 @@ int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_
     ReflectionShape shape;
     if (!make_reflection_shape(*cfg, decisions, inside_fast, cull, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
     HIP_TRY(hipSetDevice(device));
-    std::vector<ReflectionFrame> frames(static_cast<size_t>(n));
-    std::vector<int> views(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i)
-        views[static_cast<size_t>(i)] = reflection_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
-    const int view = reflection_batch_view(frames.data(), views.data(), n);
-    size_t dyn = 0;
-    for (const ReflectionFrame& f : frames) dyn = std::max(dyn, reflection_lds_bytes(f, shape));
-    return launch_pass(
-        device, frames, stream, "reflection launches", [&](const ReflectionFrame& f) { return launch_reflection(f, shape, view, stream); },
-        [&](const ReflectionFrame* d_table, int m) { return launch_reflection_batch(d_table, m, shape, view, dyn, stream); });
+    return enqueue_pass<ReflectionFrame>(
+        device, n, stream, "reflection launches",
+        [&](int i, ReflectionFrame& f) { return reflection_frame_of(scenes[i], *d_out, ground_y[i], static_cast<size_t>(i), stride, f); },
+        [&](const ReflectionFrame& f) { return PassLds{reflection_lds_bytes(f, shape), 0}; },
+        [&](const ReflectionFrame& f, int view) { return launch_reflection(f, shape, view, stream); },
+        [&](const ReflectionFrame* d_table, int m, int view, PassLds dyn) { return launch_reflection_batch(d_table, m, shape, view, dyn.first, stream); });
 }
 
 // ---- light layers (mcrt_render_light_device & co): the ground pass's host path with two kernels — `shade` for visibility and
@@ -885,18 +889,17 @@ int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_confi
     if (!make_shade_shape(*cfg, decisions, inside_fast, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
     HIP_TRY(hipSetDevice(device));
     const bool shade = d_out->visibility || d_out->direct, occlusion = d_out->occlusion != nullptr;
-    std::vector<ShadeFrame> frames(static_cast<size_t>(n));
-    std::vector<int> views(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) {
-        if (occlusion) share_full_seed_table(scenes[i]);
-        views[static_cast<size_t>(i)] = shade_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
-    }
-    const int view = shade_batch_view(frames.data(), views.data(), n);
-    size_t shade_dyn = 0, occlusion_dyn = 0;
-    for (const ShadeFrame& f : frames) shade_dyn = std::max(shade_dyn, shade_lds_bytes(f, shape)), occlusion_dyn = std::max(occlusion_dyn, occlusion_lds_bytes(f));
-    return launch_pass(
-        device, frames, stream, "light launches", [&](const ShadeFrame& f) { return launch_light(f, shape, view, stream); },
-        [&](const ShadeFrame* d_table, int m) { return launch_light_batch(d_table, m, shape, view, shade, shade_dyn, occlusion, occlusion_dyn, stream); });
+    return enqueue_pass<ShadeFrame>(
+        device, n, stream, "light launches",
+        [&](int i, ShadeFrame& f) {
+            if (occlusion) share_full_seed_table(scenes[i]);
+            return shade_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, f);
+        },
+        [&](const ShadeFrame& f) { return PassLds{shade_lds_bytes(f, shape), occlusion_lds_bytes(f)}; },
+        [&](const ShadeFrame& f, int view) { return launch_light(f, shape, view, stream); },
+        [&](const ShadeFrame* d_table, int m, int view, PassLds dyn) {
+            return launch_light_batch(d_table, m, shape, view, shade, dyn.first, occlusion, dyn.second, stream);
+        });
 }
 
 // ---- light bake (mcrt_bake_light_device & co): the light pass's host path over the texel pool instead of a frame — two kernels
@@ -925,18 +928,17 @@ int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config*
     make_bake_shape(*cfg, grid, decisions, inside_fast, max_texels, shape);
     HIP_TRY(hipSetDevice(device));
     const bool shade = d_out->visibility || d_out->direct, occlusion = d_out->occlusion != nullptr;
-    std::vector<BakeFrame> frames(static_cast<size_t>(n));
-    std::vector<int> views(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) {
-        if (occlusion) share_full_seed_table(scenes[i]);
-        views[static_cast<size_t>(i)] = bake_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, frames[static_cast<size_t>(i)]);
-    }
-    const int view = bake_batch_view(frames.data(), views.data(), n);
-    size_t shade_dyn = 0, occlusion_dyn = 0;
-    for (const BakeFrame& f : frames) shade_dyn = std::max(shade_dyn, bake_shade_lds_bytes(f, shape)), occlusion_dyn = std::max(occlusion_dyn, bake_occlusion_lds_bytes(f));
-    return launch_pass(
-        device, frames, stream, "bake launches", [&](const BakeFrame& f) { return launch_bake(f, shape, view, stream); },
-        [&](const BakeFrame* d_table, int m) { return launch_bake_batch(d_table, m, shape, view, shade, shade_dyn, occlusion, occlusion_dyn, stream); });
+    return enqueue_pass<BakeFrame>(
+        device, n, stream, "bake launches",
+        [&](int i, BakeFrame& f) {
+            if (occlusion) share_full_seed_table(scenes[i]);
+            return bake_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, f);
+        },
+        [&](const BakeFrame& f) { return PassLds{bake_shade_lds_bytes(f, shape), bake_occlusion_lds_bytes(f)}; },
+        [&](const BakeFrame& f, int view) { return launch_bake(f, shape, view, stream); },
+        [&](const BakeFrame* d_table, int m, int view, PassLds dyn) {
+            return launch_bake_batch(d_table, m, shape, view, shade, dyn.first, occlusion, dyn.second, stream);
+        });
 }
 
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): one workgroup per handle rewrites the texel pool, the alpha

@@ -308,25 +308,6 @@ LdsFit lds_fit(uint32_t alpha_words, uint32_t n_meshes, bool posed) {
     if (!fits) return LdsFit{0, 0, kViewHbm};
     return LdsFit{static_cast<int>(n_meshes * 6), static_cast<int>(alpha_words), posed ? kViewLds : kViewLdsUnposed};
 }
-template <class Frame>  // LayersFrame, GroundFrame, ReflectionFrame or ShadeFrame
-static int view_of_frame(Frame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) {
-    const LdsFit fit = lds_fit(alpha_words, n_meshes, posed);
-    f.lds_alpha_words = fit.alpha_words, f.lds_face_entries = fit.face_entries;
-    return fit.view;
-}
-int layers_view(LayersFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
-template <class Frame>
-static int batch_view_of(Frame* frames, const int* views, int n) {
-    bool any_hbm = false, any_posed = false;
-    for (int i = 0; i < n; ++i) {
-        any_hbm = any_hbm || views[i] == kViewHbm;
-        any_posed = any_posed || views[i] == kViewLds;
-    }
-    if (any_hbm)
-        for (int i = 0; i < n; ++i) frames[i].lds_alpha_words = 0, frames[i].lds_face_entries = 0;
-    return any_hbm ? kViewHbm : (any_posed ? kViewLds : kViewLdsUnposed);
-}
-int layers_batch_view(LayersFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
 size_t layers_lds_bytes(const LayersFrame& f) { return scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words); }
 bool make_layers_shape(const mcrt_config& cfg, LayersShape& shape) {
     std::memset(&shape, 0, sizeof shape);
@@ -340,21 +321,23 @@ bool make_layers_shape(const mcrt_config& cfg, LayersShape& shape) {
     shape.parts = static_cast<int>(parts);
     return true;
 }
+// items of a pass whose `samples` positions or directions (12 bytes each) fit an LDS area of `bytes` at once: 1 .. kBlock
+static int pass_items_that_fit(int bytes, int samples) {
+    const int fit = bytes / (12 * (samples > 0 ? samples : 1));
+    return fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+}
 // ---- ground shadow (kernels.h) --------------------------------------------------------------------
 bool make_ground_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside_fast, GroundShape& shape) {
     std::memset(&shape, 0, sizeof shape);
     if (!make_layers_shape(cfg, shape.tiles)) return false;
     shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
-    const int fit = kGroundPosBytes / (12 * shape.samples);  // 113 samples: 9 pixels per pass
-    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.pass = pass_items_that_fit(kGroundPosBytes, shape.samples);  // 113 samples: 9 pixels per pass
     shape.bundle_decisions = bundle_decisions ? 1 : 0;
     shape.inside_fast = inside_fast ? 1 : 0;
     return true;
 }
-int ground_view(GroundFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
-int ground_batch_view(GroundFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
 size_t ground_lds_bytes(const GroundFrame& f, const GroundShape& shape) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    const size_t tables = scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words);
     return tables + kGroundFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
 }
 // ---- ground occlusion (kernels.h) -------------------------------------------------------------------
@@ -363,18 +346,15 @@ bool make_ground_occlusion_shape(const mcrt_config& cfg, bool inside_fast, Groun
     if (!make_layers_shape(cfg, shape.tiles)) return false;
     shape.ao_samples = cfg.ao_samples;
     shape.ao_radius = cfg.ao_radius;
-    const int fit = kGroundOccDirBytes / (12 * (cfg.ao_samples > 0 ? cfg.ao_samples : 1));  // 8 samples: 128 pixels per pass; 113 samples: 9
-    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.pass = pass_items_that_fit(kGroundOccDirBytes, cfg.ao_samples);  // 8 samples: 128 pixels per pass; 113 samples: 9
     shape.inside_fast = inside_fast ? 1 : 0;
     return true;
 }
-int ground_occlusion_view(GroundOcclusionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
-int ground_occlusion_batch_view(GroundOcclusionFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
 // The 12-mesh character (3120 bytes of tables) at 8 samples: 3120 + 8192 + 128 * 96 = 23600 bytes, four workgroups in a CU's
 // 160 KiB.  The directions never take more than kGroundOccDirBytes (the pass shrinks with A), so the largest tables the LDS
 // views take (28 KiB) make 49152 bytes, below the 64 KiB a workgroup may ask for.
 size_t ground_occlusion_lds_bytes(const GroundOcclusionFrame& f, const GroundOcclusionShape& shape) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    const size_t tables = scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words);
     return tables + kGroundOccFixedBytes + static_cast<size_t>(shape.pass) * static_cast<size_t>(shape.ao_samples > 0 ? shape.ao_samples : 1) * 12;
 }
 // ---- ground reflection (kernels.h) ------------------------------------------------------------------
@@ -382,21 +362,18 @@ bool make_reflection_shape(const mcrt_config& cfg, bool bundle_decisions, bool i
     std::memset(&shape, 0, sizeof shape);
     if (!make_layers_shape(cfg, shape.tiles)) return false;
     shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
-    const int fit = kReflectPosBytes / (12 * shape.samples);  // 8 samples: 85 hits per pass; 113 samples: 6
-    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.pass = pass_items_that_fit(kReflectPosBytes, shape.samples);  // 8 samples: 85 hits per pass; 113 samples: 6
     shape.max_bounces = cfg.max_bounces;
     shape.bundle_decisions = bundle_decisions ? 1 : 0;
     shape.inside_fast = inside_fast ? 1 : 0;
     shape.cull = cull ? 1 : 0;
     return true;
 }
-int reflection_view(ReflectionFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
-int reflection_batch_view(ReflectionFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
 // The 12-mesh character (72 face entries, 204 alpha words: 3120 bytes of tables) at 8 samples: 3120 + 22528 + 85 * 96 = 33808
 // bytes, four workgroups in a CU's 160 KiB.  The largest tables the LDS views take (28 KiB) make 59392 bytes, below the 64 KiB
 // a workgroup may ask for.
 size_t reflection_lds_bytes(const ReflectionFrame& f, const ReflectionShape& shape) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    const size_t tables = scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words);
     return tables + kReflectFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
 }
 // ---- light layers (kernels.h) -----------------------------------------------------------------------
@@ -404,25 +381,22 @@ bool make_shade_shape(const mcrt_config& cfg, bool bundle_decisions, bool inside
     std::memset(&shape, 0, sizeof shape);
     if (!make_layers_shape(cfg, shape.tiles)) return false;
     shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
-    const int fit = kShadePosBytes / (12 * shape.samples);  // 8 samples: 85 hits per pass; 113 samples: 6
-    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.pass = pass_items_that_fit(kShadePosBytes, shape.samples);  // 8 samples: 85 hits per pass; 113 samples: 6
     shape.ao_samples = cfg.ao_samples;
     shape.ao_radius = cfg.ao_radius;
     shape.bundle_decisions = bundle_decisions ? 1 : 0;
     shape.inside_fast = inside_fast ? 1 : 0;
     return true;
 }
-int shade_view(ShadeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
-int shade_batch_view(ShadeFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
 // The 12-mesh character (72 face entries, 204 alpha words: 3120 bytes of tables) at 8 samples: `shade` 3120 + 18432 + 85 * 96 =
 // 29712 bytes, `occlusion` 3120 + 12288 = 15408 bytes: four workgroups of either in a CU's 160 KiB.  The largest tables the LDS
 // views take (28 KiB) make 55296 and 40960 bytes, below the 64 KiB a workgroup may ask for.
 size_t shade_lds_bytes(const ShadeFrame& f, const ShadeShape& shape) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    const size_t tables = scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words);
     return tables + kShadeFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
 }
 size_t occlusion_lds_bytes(const ShadeFrame& f) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    const size_t tables = scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words);
     return tables + kOcclusionFixedBytes;
 }
 // ---- light bake (kernels.h) ---------------------------------------------------------------------------
@@ -441,8 +415,7 @@ void make_bake_shape(const mcrt_config& cfg, int grid, bool bundle_decisions, bo
     std::memset(&shape, 0, sizeof shape);
     shape.grid = grid;
     shape.samples = soft_sampling(cfg) ? cfg.shadow_samples : 1;
-    const int fit = kBakePosBytes / (12 * shape.samples);  // 8 samples: 85 points per pass; 113 samples: 6
-    shape.pass = fit < 1 ? 1 : (fit > kBlock ? kBlock : fit);
+    shape.pass = pass_items_that_fit(kBakePosBytes, shape.samples);  // 8 samples: 85 points per pass; 113 samples: 6
     shape.ao_samples = cfg.ao_samples;
     shape.ao_radius = cfg.ao_radius;
     shape.bundle_decisions = bundle_decisions ? 1 : 0;
@@ -450,17 +423,15 @@ void make_bake_shape(const mcrt_config& cfg, int grid, bool bundle_decisions, bo
     shape.max_units = max_texels > 0 ? (max_texels - 1) / kBlock + 1 : 0;
     shape.geometry = 1, shape.rays = 1;
 }
-int bake_view(BakeFrame& f, uint32_t alpha_words, uint32_t n_meshes, bool posed) { return view_of_frame(f, alpha_words, n_meshes, posed); }
-int bake_batch_view(BakeFrame* frames, const int* views, int n) { return batch_view_of(frames, views, n); }
 // The 12-mesh character (72 face entries, 204 alpha words: 3120 bytes of tables) at 8 samples: `bake_shade` 3120 + 22528 + 85 * 96 =
 // 33808 bytes, `bake_occlusion` 3120 + 16384 = 19504 bytes: four workgroups of either in a CU's 160 KiB.  The largest tables the LDS
 // views take (28 KiB) make 59392 and 45056 bytes, below the 64 KiB a workgroup may ask for.
 size_t bake_shade_lds_bytes(const BakeFrame& f, const BakeShape& shape) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    const size_t tables = scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words);
     return tables + kBakeShadeFixedBytes + static_cast<size_t>(shape.pass) * shape.samples * 12;
 }
 size_t bake_occlusion_lds_bytes(const BakeFrame& f) {
-    const size_t tables = (scene_tables_lds_bytes(f.lds_face_entries, f.lds_alpha_words) + 15u) & ~static_cast<size_t>(15);
+    const size_t tables = scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words);
     return tables + kBakeOcclusionFixedBytes;
 }
 // ---- skins on resident scenes (kernels.h) -----------------------------------------------------------

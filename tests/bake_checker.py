@@ -267,6 +267,13 @@ MODE_CASES = {
     "samples_1": dict(radius=25.0, samples=1),
     "samples_3": dict(radius=25.0, samples=3),
     "samples_113": dict(radius=25.0, samples=113),
+    # the (item, sample) ray loop's other branches: a group smaller than a wave, the whole ballot, the first count past it
+    "samples_2": dict(radius=25.0, samples=2),
+    "samples_64": dict(radius=25.0, samples=64),
+    "samples_65": dict(radius=25.0, samples=65),
+    "ao_2": dict(radius=25.0, ao_samples=2, ao_radius=3.0),
+    "ao_64": dict(radius=25.0, ao_samples=64, ao_radius=3.0),
+    "ao_65": dict(radius=25.0, ao_samples=65, ao_radius=3.0),
     "radius_0": dict(radius=0.0),
     "ao_1_radius_0": dict(radius=25.0, ao_samples=1, ao_radius=0.0),
     "ao_1_radius_1000": dict(radius=25.0, ao_samples=1, ao_radius=1000.0),
@@ -292,6 +299,12 @@ COUNTS = {
     "samples_1": (192, 140, 0, 41, 5),
     "samples_3": (192, 83, 51, 41, 5),
     "samples_113": (192, 66, 76, 41, 5),
+    "samples_2": (192, 92, 40, 41, 5),
+    "samples_64": (192, 66, 76, 41, 5),
+    "samples_65": (192, 66, 76, 41, 5),
+    "ao_2": (192, 67, 73, 12, 14),
+    "ao_64": (192, 67, 73, 68, 0),
+    "ao_65": (192, 67, 73, 68, 0),
     "radius_0": (192, 140, 0, 41, 5),
     "ao_1_radius_0": (192, 67, 73, 0, 0),
     "ao_1_radius_1000": (192, 67, 73, 0, 25),

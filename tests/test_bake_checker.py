@@ -87,6 +87,11 @@ def test_mode_counts_are_pinned(name):
         assert c[2] == 0  # one ray per point: no penumbra
     if name.endswith("radius_0") and name.startswith("ao_"):
         assert c[3] == 0 and c[4] == 0 and (exp["occlusion"] == 1.0).all()
+    # the cases that walk the ray loop's branches hold enough undecided points (penumbra) or traced ones (partly occluded)
+    if name in ("samples_2", "samples_64", "samples_65"):
+        assert c[2] == (40 if name == "samples_2" else 76)
+    if name in ("ao_2", "ao_64", "ao_65"):
+        assert c[3] == (12 if name == "ao_2" else 68)
 
 
 def test_the_repainted_handles_scenes_hold_the_full_table(mcrt):

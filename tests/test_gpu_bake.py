@@ -99,8 +99,9 @@ def test_scenes_equal_the_oracle(mcrt, gpu, name):
 @gpu_test
 @pytest.mark.parametrize("name", list(B.MODE_CASES))
 def test_shadow_modes_and_occlusion_limits(mcrt, gpu, name):
-    """On the two boxes: soft shadows off, 1, 3 and 113 samples, a light of radius 0; ambient occlusion with 1 and 113 samples at
-    the radii 0 and 1000.  (No penumbra without a disk and no occlusion at radius 0: the counts say so.)"""
+    """On the two boxes: soft shadows off, 1, 2, 3, 64, 65 and 113 samples, a light of radius 0; ambient occlusion with 1 and 113
+    samples at the radii 0 and 1000, and with 2, 64 and 65 at radius 3.  (No penumbra without a disk and no occlusion at radius 0:
+    the counts say so.  2, 64 and 65 walk the ray loop's branches: a group smaller than a wave, the whole ballot, the atomics.)"""
     sd, cfg, grid, exp = _case(name, classes=False)
     names = PLANES if name.startswith("ao_") else ("position", "normal", "visibility", "direct")
     _check_both_forms(mcrt, sd, cfg, grid, exp, name, names)

@@ -163,11 +163,16 @@ def test_lights(mcrt, gpu, case):
 
 
 @gpu_test
-@pytest.mark.parametrize("case", ["soft_shadows_off", "samples_1", "samples_3", "samples_113"])
+@pytest.mark.parametrize("case", ["soft_shadows_off", "samples_1", "samples_2", "samples_3", "samples_64", "samples_65", "samples_113"])
 def test_sample_counts(mcrt, gpu, case):
     if case == "samples_113":  # the engine's limit; 287 dark, 250 penumbra at 48 x 32
         sd, cfg, exp = G.orbit_expectation(5, (40.0, 60.0, 28.0), 48, 32, samples=113)
         least = (100, 100)
+    elif case in ("samples_2", "samples_64", "samples_65"):
+        # the ray loop's other branches — a group smaller than a wave, the whole ballot, the first count past it — on frames
+        # with enough undecided pixels to enter it: 75 penumbra pixels at 2 samples, 238 at 64 and at 65
+        sd, cfg, exp = G.orbit_expectation(5, (40.0, 60.0, 28.0), 48, 32, samples=int(case[8:]))
+        least = (100, 50 if case == "samples_2" else 100)
     else:
         kw = {"soft_shadows_off": dict(soft=False), "samples_1": dict(samples=1), "samples_3": dict(samples=3)}[case]
         sd, cfg, exp = G.skin_expectation("pose6_orbit_96x64", 0.0, **kw)

@@ -134,6 +134,10 @@ MODES = {  # pose 6 under the light of radius 25: name -> (checker arguments, ex
     "samples_3": (dict(samples=3), (1079, 897, 176)),
     "samples_8": (dict(samples=8), (1079, 790, 288)),
     "samples_113": (dict(samples=113), (1079, 697, 382)),
+    # the ray loop's other branches: a group smaller than a wave, the whole ballot, the first count past it
+    "samples_2": (dict(samples=2), (1079, 931, 123)),
+    "samples_64": (dict(samples=64), (1079, 700, 379)),
+    "samples_65": (dict(samples=65), (1079, 700, 379)),
 }
 
 

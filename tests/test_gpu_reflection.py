@@ -151,6 +151,11 @@ LIGHTS = {  # on pose 6 at the floor (137 hits, 70 second-level): name -> (light
     "radius_0": (None, 0.0, 0),             # the one isInShadow ray at S = 8
     "below_the_ground": ((10.0, -5.0, 20.0), None, 7),
     "inside_the_head": ((0.0, 28.0, 0.0), None, 0),
+    # the ray loop's other branches under the radius-25 light, where enough level-1 hits are undecided to enter it: a group
+    # smaller than a wave, the whole ballot, the first count past it
+    "samples_2": (None, 25.0, 16),
+    "samples_64": (None, 25.0, 63),
+    "samples_65": (None, 25.0, 63),
 }
 
 
@@ -158,11 +163,14 @@ LIGHTS = {  # on pose 6 at the floor (137 hits, 70 second-level): name -> (light
 @pytest.mark.parametrize("case", list(LIGHTS))
 def test_lights(mcrt, gpu, case):
     light, radius, pen_exact = LIGHTS[case]
-    sd, cfg, exp = R.skin_expectation("pose6_orbit_96x64", 0.0, light=light, radius=radius)
+    samples = int(case[8:]) if case.startswith("samples_") else 8
+    sd, cfg, exp = R.skin_expectation("pose6_orbit_96x64", 0.0, samples=samples, light=light, radius=radius)
     reached, hits, second, pen = _counts(case, exp)
     assert hits >= 100 and second >= 20 and pen == pen_exact
-    if case == "radius_25":
+    if case in ("radius_25", "samples_64", "samples_65"):
         assert pen >= 40
+    if case == "samples_2":
+        assert pen >= 10
     _check_both_forms(mcrt, sd, cfg, 0.0, exp, case)
 
 
