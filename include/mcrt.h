@@ -743,7 +743,8 @@ int mcrt_skin_view_table(int skin_height, const float pose[12], const mcrt_scene
  *     image therefore equals the reference frame where F.a is 0 or 1 — under one sample per pixel without depth of field,
  *     everywhere — but not at the figure's edges under several samples: there the reference blends the gradient's values at
  *     the samples' own jittered positions, the shot blends the figure's samples over the value at the centre.
- * The shadow is black and the page opaque (out.a = 1): a coloured shadow and a transparent page are not offered. */
+ * Here the shadow is black and the page opaque (out.a = 1); a coloured shadow and a transparent page come with the _ex entries
+ * below ("the shot as a cut-out"). */
 #define MCRT_PAGE_COLOR 0     /* page = page_color */
 #define MCRT_PAGE_REFERENCE 1 /* page = the reference's background at the pixel centre */
 typedef struct mcrt_shot {
@@ -846,6 +847,80 @@ int mcrt_render_shot_batch_occ(const mcrt_scene_desc* const* scenes, int n_frame
                                float floor_occlusion, const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device);
 int mcrt_render_shot_png_occ(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, float ground_y,
                              const char* path, int device);
+
+/* The shot as a CUT-OUT, with a shadow colour and crop bounds.  One straight-alpha RGBA image holds figure, shadow, occlusion
+ * and reflection; composited over any page it gives what the opaque shot gives for that page.  New are a page mode,
+ * MCRT_PAGE_TRANSPARENT (only the _ex entries accept it; the entries above keep refusing every page but 0 and 1), and a shadow
+ * colour C = shadow_color[3], finite, default (0, 0, 0), which the floor-occlusion darkening uses too.
+ * DEFINITION.  The inputs F, vis, R, dR, pg, occ and the settings s, k, fade, o are those above.  All arithmetic float32, one
+ * rounding per operation, uncontracted, in the order written, divisions correctly rounded:
+ *   sh   = s * (1.0f - vis)
+ *   f    = fade > 0 ? clamp(1.0f - dR / fade, 0, 1) : 1.0f
+ *   ar   = (k * R.a) * f
+ *   oc   = o * (1.0f - occ)                      (multiplied in only where there is an occlusion plane, as above)
+ *   lit  = (1.0f - sh) * (1.0f - oc)
+ *   keep = lit * (1.0f - ar)                     (the keep above, same bits)
+ *   dk   = (1.0f - lit) * (1.0f - ar)            (the weight of the shadow colour)
+ * OPAQUE PAGES (MCRT_PAGE_COLOR, MCRT_PAGE_REFERENCE):
+ *   fl.c  = (pg.c * keep + C.c * dk) + R.c * ar
+ *   out.c = F.c * F.a + fl.c * (1.0f - F.a)
+ *   out.a = 1.0f
+ * When all three channels of C compare equal to 0 the C term is not formed at all: fl.c = pg.c * keep + R.c * ar, and the
+ * result is byte for byte that of the _occ entries with the same settings, signs of zero included.
+ * TRANSPARENT PAGE:
+ *   af   = 1.0f - keep                           (the floor's alpha)
+ *   fp.c = C.c * dk + R.c * ar                   (the floor's colour, premultiplied; C = 0: fp.c = R.c * ar)
+ *   u    = 1.0f - F.a
+ *   if af == 0:   out = F                        (all four channels as they are)
+ *   else:         A = F.a + af * u
+ *                 out.a = A
+ *                 out.c = A > 0 ? (F.c * F.a + fp.c * u) / A : 0      (A <= 0: out = (0, 0, 0, 0))
+ * The RGBA8 plane quantises all four channels with the quantiser of mcrt_quantize_rgba8; out.c may exceed 1 at alphas near
+ * one float ulp, and the quantiser clamps it.  The page evaluation (the reference's background, page_color) is not read with
+ * the transparent page; a page_color that is not finite is refused all the same.
+ * CONSEQUENCES (part of the contract).
+ *   - With s = k = o = 0, or with the planes absent, af is exactly +0 and the image is the MCRT_BACKGROUND_TRANSPARENT render
+ *     itself, bit for bit; the passes are not run and their limits on shadow_samples, max_bounces, ao_samples and ao_radius
+ *     do not apply.
+ *   - A pixel with F.a == 1 holds F.rgb and alpha 1 (a channel that is -0 in F may come out +0).
+ *   - A pixel with no figure and nothing on the floor is F, so (0, 0, 0, 0); one with a black shadow only is (0, 0, 0, af).
+ *   - OVER ANY PAGE.  For a finite pg, out.c * out.a + pg.c * (1 - out.a) equals the opaque shot's out.c for that page up to
+ *     rounding — in exact arithmetic they are one expression, 1 - A = u * keep: within 16 * 2^-24 in float and one level in
+ *     RGBA8.
+ *   - A straight-alpha 8-bit image cannot carry colour precision at alphas that quantise to 0 or 1 level: a property of the
+ *     format (PNG's colour type 6), not of this blend.  Compositors that need it take the float plane.
+ * BOUNDS, only with the transparent page: d_bounds, optional, one int32[4] per frame: {x0, y0, x1, y1}, x0 and y0 the minima
+ * of x and y over the pixels with float out.a > 0.0f, x1 and y1 the maxima of x + 1 and y + 1 over them; a frame without such
+ * a pixel gets {width, height, 0, 0}.  The set is a superset of the pixels whose 8-bit alpha is above 0.  The call writes
+ * every entry completely (the caller initialises nothing; 4-byte alignment); the result is valid in stream order behind the
+ * blend.  Zero-size frames and n_frames == 0 write nothing.
+ * ENTRIES.  Ordering, events, scratch and argument checks are those of the _occ entries, in the same order;
+ * mcrt_shot_scratch_bytes_ex has the layout and sizes of mcrt_shot_scratch_bytes_occ for the same s, k, fade and o.
+ * MCRT_ERR_INVALID before any device work also for: a page outside 0..2; a shadow_color that is not finite; a non-NULL bounds
+ * pointer, a non-zero crop or a non-NULL out_bounds with an opaque page.
+ * mcrt_render_shot_png_ex writes colour type 6 with the image's real alpha; crop != 0 writes only the bounds rectangle — an
+ * empty rectangle writes the whole frame, so the call never fails for an all-transparent skin — and out_bounds (int32[4] or
+ * NULL) receives the rectangle either way. */
+#define MCRT_PAGE_TRANSPARENT 2 /* no page: the shot as a straight-alpha cut-out (the _ex entries only) */
+typedef struct mcrt_shot_ex {
+    mcrt_shot shot;         /* page may also be MCRT_PAGE_TRANSPARENT */
+    float floor_occlusion;  /* o */
+    float shadow_color[3];  /* C, finite */
+} mcrt_shot_ex;
+/* mcrt_shot_init, o = 0, C = (0, 0, 0); NULL is ignored */
+void mcrt_shot_ex_init(mcrt_shot_ex* shot);
+size_t mcrt_shot_scratch_bytes_ex(const mcrt_config* cfg, const mcrt_shot_ex* shot, int n_frames);
+int mcrt_composite_shot_batch_device_ex(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot,
+                                        const mcrt_shot_inputs* d_in, const float* d_occlusion, size_t in_stride_pixels, float* d_out_f32,
+                                        uint8_t* d_out_rgba8, size_t out_stride_pixels, int32_t (*d_bounds)[4], void* stream);
+int mcrt_render_shot_batch_device_ex(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot,
+                                     const float* ground_y, void* d_scratch, size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8,
+                                     size_t frame_stride_pixels, int32_t (*d_bounds)[4], void* stream);
+/* host form: out_bounds NULL or n_frames entries in host memory */
+int mcrt_render_shot_batch_ex(const mcrt_scene_desc* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot,
+                              const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int32_t (*out_bounds)[4], int device);
+int mcrt_render_shot_png_ex(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_shot_ex* shot, float ground_y, const char* path,
+                            int crop, int32_t* out_bounds, int device);
 
 /* number of pixel rows owned by (first, step) and therefore the packed buffer height */
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int tile_row_first, int tile_row_step);

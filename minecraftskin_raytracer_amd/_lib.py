@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_ground_occlusion_device", "mcrt_render_ground_occlusion_batch_device", "mcrt_render_ground_occlusion",
     "mcrt_shot_scratch_bytes_occ", "mcrt_render_shot_batch_device_occ", "mcrt_composite_shot_batch_device_occ",
     "mcrt_render_shot_batch_occ", "mcrt_render_shot_png_occ",
+    "mcrt_shot_ex_init", "mcrt_shot_scratch_bytes_ex", "mcrt_composite_shot_batch_device_ex", "mcrt_render_shot_batch_device_ex",
+    "mcrt_render_shot_batch_ex", "mcrt_render_shot_png_ex",
 ]
 
 
@@ -65,6 +67,7 @@ def load():
     light_p = C.POINTER(abi.McrtLightPlanes)
     bake_p = C.POINTER(abi.McrtBakePlanes)
     shot_p = C.POINTER(abi.McrtShot)
+    shot_ex_p = C.POINTER(abi.McrtShotEx)
     sig = {
         "mcrt_config_init": (None, [cfg_p]),
         "mcrt_generate_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(abi.McrtTile), C.c_int]),
@@ -134,6 +137,13 @@ def load():
                                                            vp, C.c_size_t, vp]),
         "mcrt_render_shot_batch_occ": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, shot_p, C.c_float, f_p, f_p, u8_p, C.c_int]),
         "mcrt_render_shot_png_occ": (C.c_int, [desc_p, cfg_p, shot_p, C.c_float, C.c_float, C.c_char_p, C.c_int]),
+        "mcrt_shot_ex_init": (None, [shot_ex_p]),
+        "mcrt_shot_scratch_bytes_ex": (C.c_size_t, [cfg_p, shot_ex_p, C.c_int]),
+        "mcrt_composite_shot_batch_device_ex": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, shot_ex_p, C.POINTER(abi.McrtShotInputs), vp, C.c_size_t, vp, vp,
+                                                          C.c_size_t, vp, vp]),
+        "mcrt_render_shot_batch_device_ex": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, shot_ex_p, f_p, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp]),
+        "mcrt_render_shot_batch_ex": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, shot_ex_p, f_p, f_p, u8_p, vp, C.c_int]),
+        "mcrt_render_shot_png_ex": (C.c_int, [desc_p, cfg_p, shot_ex_p, C.c_float, C.c_char_p, C.c_int, vp, C.c_int]),
         "mcrt_probe_scene_blob": (C.c_int, [vp, vp, C.c_size_t]),
         "mcrt_write_png_rgba8": (C.c_int, [C.c_char_p, u8_p, C.c_int, C.c_int]),
         "mcrt_encode_png_rgba8": (C.c_size_t, [u8_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),

@@ -295,7 +295,9 @@ def bake_names(planes) -> tuple:
 
 PAGE_COLOR = 0  # MCRT_PAGE_*: the page of a studio shot is Shot.pageColor
 PAGE_REFERENCE = 1  # the reference's background (the config's gradient, or the scene's colour) at the pixel centre
+PAGE_TRANSPARENT = 2  # no page: the shot as a straight-alpha cut-out (the ``_ex`` entries only)
 PAGES = {"color": PAGE_COLOR, "reference": PAGE_REFERENCE}
+PAGES_EX = {**PAGES, "transparent": PAGE_TRANSPARENT}
 
 
 class McrtShot(C.Structure):
@@ -303,6 +305,12 @@ class McrtShot(C.Structure):
 
     _fields_ = [("page", C.c_int32), ("page_color", C.c_float * 3), ("shadow_strength", C.c_float), ("reflectivity", C.c_float),
                 ("reflection_fade", C.c_float)]
+
+
+class McrtShotEx(C.Structure):
+    """mcrt_shot_ex: mcrt_shot (whose page may be PAGE_TRANSPARENT), the floor-occlusion strength and the shadow's colour."""
+
+    _fields_ = [("shot", McrtShot), ("floor_occlusion", C.c_float), ("shadow_color", C.c_float * 3)]
 
 
 class McrtShotInputs(C.Structure):
@@ -317,7 +325,10 @@ class Shot:
     and a floor reflection of reflectivity 0.35 that does not fade.  ``page``: ``"reference"`` or ``"color"`` (then
     ``pageColor``); ``reflectionFade``: the reflection distance at which the mirror image has vanished, 0 = no fade;
     ``floorOcclusion``: the strength of the floor's contact occlusion (the ground-occlusion pass at the config's ``aoSamples`` /
-    ``aoRadius``), 0 = none.  It is no field of mcrt_shot: the entries that take it (``*_occ``) take it as an argument."""
+    ``aoRadius``), 0 = none.  It is no field of mcrt_shot: the entries that take it (``*_occ``) take it as an argument.
+    ``page="transparent"``: no page — the shot as a straight-alpha cut-out; ``shadowColor``: the colour of the shadow and of the
+    floor occlusion, (0, 0, 0) = black.  Both travel in mcrt_shot_ex (``to_c_ex``), and ``shadowColor`` is carried like
+    ``floorOcclusion``."""
 
     page: str = "reference"
     pageColor: Sequence[float] = (1.0, 1.0, 1.0)
@@ -327,30 +338,67 @@ class Shot:
     # the last parameter of the constructor and an attribute like the others, but no dataclass field: ``dataclasses.asdict`` and
     # ``fields`` — what describes mcrt_shot — stay as they were
     floorOcclusion: InitVar[float] = 0.0
+    # ``shadowColor``: a keyword of the constructor (``_shot_init`` below) and an attribute, and nothing the dataclass knows of
 
     def __post_init__(self, floorOcclusion):
         self.floorOcclusion = float(floorOcclusion)
+        self.shadowColor = (0.0, 0.0, 0.0)
 
     def __eq__(self, other):
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return all(getattr(self, f.name) == getattr(other, f.name) for f in fields(self)) and self.floorOcclusion == other.floorOcclusion
+        return (all(getattr(self, f.name) == getattr(other, f.name) for f in fields(self)) and self.floorOcclusion == other.floorOcclusion
+                and self.shadowColor == other.shadowColor)
 
     def __repr__(self):
         body = ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in fields(self))
-        return f"Shot({body})" if self.floorOcclusion == 0.0 else f"Shot({body}, floorOcclusion={self.floorOcclusion!r})"
+        if self.floorOcclusion != 0.0:
+            body += f", floorOcclusion={self.floorOcclusion!r}"
+        if self.shadowColor != (0.0, 0.0, 0.0):
+            body += f", shadowColor={self.shadowColor!r}"
+        return f"Shot({body})"
 
     def to_c(self) -> McrtShot:
-        if not isinstance(self.page, str) or self.page not in PAGES:
-            raise ValueError(f"page must be 'reference' or 'color', not {self.page!r}")
+        if self.page == "transparent":
+            raise ValueError("page 'transparent' has no mcrt_shot: it travels in mcrt_shot_ex, see Shot.to_c_ex()")
+        return self._base(PAGES)
+
+    def to_c_ex(self) -> "McrtShotEx":
+        """mcrt_shot_ex: every page, with ``floorOcclusion`` and ``shadowColor``."""
+        s = McrtShotEx()
+        s.shot = self._base(PAGES_EX)
+        s.floor_occlusion = float(self.floorOcclusion)
+        for i in range(3):
+            s.shadow_color[i] = self.shadowColor[i]
+        return s
+
+    def needs_ex(self) -> bool:
+        """Whether the shot needs the ``_ex`` entries by itself: a transparent page or a shadow colour other than 0."""
+        return self.page == "transparent" or any(c != 0.0 for c in self.shadowColor)
+
+    def _base(self, pages) -> McrtShot:
+        if not isinstance(self.page, str) or self.page not in pages:
+            raise ValueError(f"page must be {', '.join(repr(p) for p in pages)}, not {self.page!r}")
         s = McrtShot()
-        s.page = PAGES[self.page]
+        s.page = pages[self.page]
         for i in range(3):
             s.page_color[i] = float(self.pageColor[i])
         s.shadow_strength = float(self.shadowStrength)
         s.reflectivity = float(self.reflectivity)
         s.reflection_fade = float(self.reflectionFade)
         return s
+
+
+def _shot_init(self, *args, shadowColor=(0.0, 0.0, 0.0), **kw):
+    _shot_fields_init(self, *args, **kw)
+    self.shadowColor = tuple(float(c) for c in shadowColor)
+    if len(self.shadowColor) != 3:
+        raise ValueError(f"shadowColor must hold three channels, not {len(self.shadowColor)}")
+
+
+_shot_fields_init = Shot.__init__
+_shot_init.__doc__ = _shot_fields_init.__doc__
+Shot.__init__ = _shot_init
 
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)

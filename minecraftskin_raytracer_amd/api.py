@@ -379,21 +379,27 @@ class TileRenderer:
 
     @staticmethod
     def renderShot(scene, config: Config, shot: Optional[abi.Shot] = None, ground: Optional[float] = None, rgba8: bool = True,
-                   device: int = 0) -> np.ndarray:
+                   device: int = 0, bounds: bool = False):
         """The studio shot (mcrt_render_shot): the figure on a page, with its ground shadow and its floor reflection at
         y = ``ground`` (``None``: the scene's floor, ``scene_floor``), blended on the device — (H, W, 4) uint8, or float32 with
         ``rgba8=False``; alpha is 255 / 1.0 everywhere.  ``shot``: ``abi.Shot`` (``None``: its defaults).  The figure is the
         ``background="transparent"`` render of ``config``; the definition of the blend is in include/mcrt.h.  With
         ``shot.floorOcclusion`` > 0 the floor's contact occlusion (``renderGroundOcclusion`` at the config's aoSamples /
-        aoRadius) darkens the page too.  Failures raise ``McrtError``."""
-        return TileRenderer.renderShotBatch([scene], config, shot, ground, rgba8, device)[0]
+        aoRadius) darkens the page too.  ``Shot(page="transparent")``: the shot as a straight-alpha cut-out, and with
+        ``bounds=True`` the pair (image, (4,) int32 {x0, y0, x1, y1}): the box of the pixels with alpha > 0.  Failures raise
+        ``McrtError``."""
+        got = TileRenderer.renderShotBatch([scene], config, shot, ground, rgba8, device, bounds)
+        return (got[0][0], got[1][0]) if bounds else got[0]
 
     @staticmethod
-    def renderShotBatch(scenes, config: Config, shot: Optional[abi.Shot] = None, ground=None, rgba8: bool = True, device: int = 0) -> np.ndarray:
+    def renderShotBatch(scenes, config: Config, shot: Optional[abi.Shot] = None, ground=None, rgba8: bool = True, device: int = 0,
+                        bounds: bool = False):
         """``renderShot`` for N scenes of one config in one call (mcrt_render_shot_batch): one batched render, one ground and
         one reflection launch, one blend, one download.  ``ground``: ``None`` (every scene's own floor), one height for all, or
-        N heights.  Returns (N, H, W, 4) uint8, or float32 with ``rgba8=False``."""
-        s, o = _shot_c(shot)
+        N heights.  Returns (N, H, W, 4) uint8, or float32 with ``rgba8=False``; with ``bounds=True`` (transparent page only)
+        the pair (images, (N, 4) int32 boxes) through mcrt_render_shot_batch_ex."""
+        ex = _shot_ex_c(shot, bounds)
+        s, o = (None, 0.0) if ex is not None else _shot_c(shot)
         descs = [_as_desc(d) for d in scenes]
         n = len(descs)
         heights = _ground_heights(descs, ground)
@@ -406,6 +412,10 @@ class TileRenderer:
         buf = out if out.size else np.zeros(4, out.dtype)  # (no frame: the call checks its arguments and writes nothing)
         f = None if rgba8 else abi.fptr(buf)
         b = buf.ctypes.data_as(C.POINTER(C.c_uint8)) if rgba8 else None
+        if ex is not None:
+            boxes = _empty_bounds(max(n, 1), w, h)
+            check(load().mcrt_render_shot_batch_ex(arr, n, C.byref(c), C.byref(ex), gy, f, b, C.c_void_p(boxes.ctypes.data if bounds else None), int(device)))
+            return (out, boxes[:n]) if bounds else out
         if o != 0.0:
             check(load().mcrt_render_shot_batch_occ(arr, n, C.byref(c), C.byref(s), o, gy, f, b, int(device)))
         else:
@@ -515,6 +525,20 @@ def _shot_c(shot):
     library whenever the strength is not 0, so the library refuses one that is negative, above 1 or NaN."""
     sh = shot if shot is not None else abi.Shot()
     return sh.to_c(), float(sh.floorOcclusion)
+
+
+def _shot_ex_c(shot, asked: bool = False):
+    """mcrt_shot_ex of ``shot`` where the call needs the ``_ex`` entries — a transparent page, a shadow colour other than 0, or
+    ``asked`` (bounds or a crop are wanted) — and ``None`` where the calls made before them are made unchanged."""
+    sh = shot if shot is not None else abi.Shot()
+    return sh.to_c_ex() if asked or sh.needs_ex() else None
+
+
+def _empty_bounds(n: int, w: int, h: int) -> np.ndarray:
+    """(n, 4) int32 holding the box of a frame without content, {width, height, 0, 0}."""
+    b = np.zeros((n, 4), np.int32)
+    b[:, 0], b[:, 1] = w, h
+    return b
 
 
 def _empty_reflection(name: str, n: int, h: int, w: int) -> np.ndarray:
@@ -639,25 +663,37 @@ def render_png(scene, config: Config, path: str, device: int = 0, background: st
     return load().mcrt_render_png(_as_desc(scene).ptr, C.byref(c), os.fsencode(path), device) == 0
 
 
-def render_shot_png(scene, config: Config, path: str, shot: Optional[abi.Shot] = None, ground: Optional[float] = None, device: int = 0) -> bool:
+def render_shot_png(scene, config: Config, path: str, shot: Optional[abi.Shot] = None, ground: Optional[float] = None, device: int = 0,
+                    crop: bool = False) -> bool:
     """``TileRenderer.renderShot`` + ``ImageWriter.writePNG8`` in one call (mcrt_render_shot_png): the finished studio shot as
-    a PNG, 4 B/pixel copied back.  ``ground=None``: the scene's floor.  False on failure, like ``render_png``."""
-    s, o = _shot_c(shot)
+    a PNG, 4 B/pixel copied back.  ``ground=None``: the scene's floor.  False on failure, like ``render_png``.  With
+    ``Shot(page="transparent")`` the file carries the cut-out's alpha, and ``crop=True`` writes its bounds rectangle alone (the
+    whole frame where nothing is visible) through mcrt_render_shot_png_ex."""
+    ex = _shot_ex_c(shot, crop)
     d = _as_desc(scene)
     g = _ground_heights([d], ground)[0]
     c = config.to_c()
+    if ex is not None:
+        return load().mcrt_render_shot_png_ex(d.ptr, C.byref(c), C.byref(ex), g, os.fsencode(path), int(bool(crop)), None, int(device)) == 0
+    s, o = _shot_c(shot)
     if o != 0.0:
         return load().mcrt_render_shot_png_occ(d.ptr, C.byref(c), C.byref(s), o, g, os.fsencode(path), int(device)) == 0
     return load().mcrt_render_shot_png(d.ptr, C.byref(c), C.byref(s), g, os.fsencode(path), int(device)) == 0
 
 
-def shot_scratch_bytes(config: Config, shot: Optional[abi.Shot] = None, n_frames: int = 1) -> int:
+def shot_scratch_bytes(config: Config, shot: Optional[abi.Shot] = None, n_frames: int = 1, bounds: bool = False) -> int:
     """Bytes of device scratch ``render_shot_batch_device`` / ``DeviceScene.render_shot_device`` need for ``n_frames`` frames
     (mcrt_shot_scratch_bytes; host only): 16 per pixel, + 16 with a reflection, + 4 with a shadow, + 4 with a fading
     reflection, + 4 behind them with ``floorOcclusion`` > 0 (mcrt_shot_scratch_bytes_occ), every plane on a 16-byte boundary.
-    0 for a zero-size frame or ``n_frames <= 0``."""
-    s, o = _shot_c(shot)
+    0 for a zero-size frame or ``n_frames <= 0``.  A transparent page, a shadow colour and ``bounds`` change nothing of the size
+    (mcrt_shot_scratch_bytes_ex); bounds with an opaque page are refused like an invalid shot: 0."""
     c = config.to_c()
+    ex = _shot_ex_c(shot, bounds)
+    if ex is not None:
+        if bounds and ex.shot.page != abi.PAGE_TRANSPARENT:
+            return 0
+        return int(load().mcrt_shot_scratch_bytes_ex(C.byref(c), C.byref(ex), int(n_frames)))
+    s, o = _shot_c(shot)
     if o != 0.0:
         return int(load().mcrt_shot_scratch_bytes_occ(C.byref(c), C.byref(s), o, int(n_frames)))
     return int(load().mcrt_shot_scratch_bytes(C.byref(c), C.byref(s), int(n_frames)))
@@ -951,14 +987,19 @@ class DeviceScene:
         check(load().mcrt_render_reflection_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
 
     def render_shot_device(self, config: Config, shot: Optional[abi.Shot], ground: float, scratch_ptr: int, scratch_bytes: int,
-                           out_f32_ptr: int = 0, out_rgba8_ptr: int = 0, stream: int = 0) -> None:
+                           out_f32_ptr: int = 0, out_rgba8_ptr: int = 0, stream: int = 0, bounds_ptr: int = 0) -> None:
         """The studio shot of the frame into device memory (mcrt_render_shot_device): render, ground pass, reflection pass and
         blend, in order on ``stream``, the intermediate planes in the caller's scratch (``shot_scratch_bytes`` bytes, 16-byte
-        aligned).  The figure is rendered transparent whatever ``set_background`` says; the handle's mode is untouched."""
+        aligned).  The figure is rendered transparent whatever ``set_background`` says; the handle's mode is untouched.
+        ``bounds_ptr``: device memory for 4 int32, the cut-out's box (transparent page only; 0: none)."""
         if not out_f32_ptr and not out_rgba8_ptr:
             raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
         if not np.isfinite(np.float32(ground)):
             raise ValueError("ground must be finite")
+        ex = _shot_ex_c(shot, bool(bounds_ptr))
+        if ex is not None:
+            render_shot_batch_device([self], config, shot, float(ground), scratch_ptr, scratch_bytes, out_f32_ptr, out_rgba8_ptr, None, stream, bounds_ptr)
+            return
         s, o = _shot_c(shot)
         c = config.to_c()
         if o != 0.0:  # the floor-occlusion term: the batch entry with one handle
@@ -1165,13 +1206,15 @@ def _shot_handles(device_scenes) -> list:
 
 def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, shot: Optional[abi.Shot], ground, scratch_ptr: int,
                              scratch_bytes: int, out_f32_ptr: int = 0, out_rgba8_ptr: int = 0, frame_stride_pixels: Optional[int] = None,
-                             stream: int = 0) -> None:
+                             stream: int = 0, bounds_ptr: int = 0) -> None:
     """The studio shots of N resident scenes of one config (mcrt_render_shot_batch_device): one batched render, one ground and
     one reflection launch and one blend, in order on ``stream``; frame i lands ``i * frame_stride_pixels`` pixels on (default
     width * height) in ``out_f32_ptr`` (16 B/pixel) and / or ``out_rgba8_ptr`` (4 B/pixel).  ``ground``: one height for all, or
     N heights.  ``scratch_ptr``: device memory, 16-byte aligned, ``shot_scratch_bytes(config, shot, N)`` bytes.  With
     ``shot.floorOcclusion`` > 0 the ground-occlusion pass runs between the reflection and the blend
-    (mcrt_render_shot_batch_device_occ)."""
+    (mcrt_render_shot_batch_device_occ).  ``bounds_ptr``: device memory for N x 4 int32, the cut-outs' boxes, valid in stream
+    order behind the call (transparent page only; 0: none).  A transparent page, a shadow colour or bounds take
+    mcrt_render_shot_batch_device_ex."""
     handles = _shot_handles(device_scenes)
     if not out_f32_ptr and not out_rgba8_ptr:
         raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
@@ -1182,11 +1225,17 @@ def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Con
     stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
     if stride < px:
         raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    s, o = _shot_c(shot)
+    ex = _shot_ex_c(shot, bool(bounds_ptr))
     n = len(handles)
     arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
     gy = (C.c_float * max(n, 1))(*heights)
     c = config.to_c()
+    if ex is not None:
+        check(load().mcrt_render_shot_batch_device_ex(arr, n, C.byref(c), C.byref(ex), gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
+                                                      C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride,
+                                                      C.c_void_p(bounds_ptr or None), C.c_void_p(stream)))
+        return
+    s, o = _shot_c(shot)
     if o != 0.0:
         check(load().mcrt_render_shot_batch_device_occ(arr, n, C.byref(c), C.byref(s), o, gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
                                                        C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride, C.c_void_p(stream)))
@@ -1198,13 +1247,14 @@ def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Con
 def composite_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, shot: Optional[abi.Shot], figure_ptr: int,
                                 visibility_ptr: int = 0, reflection_ptr: int = 0, reflection_distance_ptr: int = 0, out_f32_ptr: int = 0,
                                 out_rgba8_ptr: int = 0, in_stride_pixels: Optional[int] = None, out_stride_pixels: Optional[int] = None,
-                                stream: int = 0, occlusion_ptr: int = 0) -> None:
+                                stream: int = 0, occlusion_ptr: int = 0, bounds_ptr: int = 0) -> None:
     """The studio shot's blend alone, on device planes the caller already has (mcrt_composite_shot_batch_device): the
     transparent figure (required, 16 B/pixel), the ground pass's visibility (0: none, no shadow), the reflection pass's rgba
     (0: no mirror image) and distance (0 only with ``shot.reflectionFade == 0``).  Frame i of the inputs starts
     ``i * in_stride_pixels`` pixels on, of the outputs ``i * out_stride_pixels`` (default width * height).  With
     ``shot.floorOcclusion`` > 0 the blend takes the ground-occlusion pass's plane at ``occlusion_ptr`` (4 B/pixel; 0: none)
-    through mcrt_composite_shot_batch_device_occ."""
+    through mcrt_composite_shot_batch_device_occ.  ``bounds_ptr``: as for ``render_shot_batch_device``; a transparent page, a
+    shadow colour or bounds take mcrt_composite_shot_batch_device_ex."""
     handles = _shot_handles(device_scenes)
     if not figure_ptr:
         raise ValueError("figure_ptr is required")
@@ -1217,11 +1267,17 @@ def composite_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: 
         if stride < px:
             raise ValueError(f"{name} {stride} is smaller than width * height = {px}")
         strides.append(stride)
-    s, o = _shot_c(shot)
+    ex = _shot_ex_c(shot, bool(bounds_ptr))
     n = len(handles)
     arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
     c = config.to_c()
     planes = abi.McrtShotInputs(figure_ptr, visibility_ptr or None, reflection_ptr or None, reflection_distance_ptr or None)
+    if ex is not None:
+        check(load().mcrt_composite_shot_batch_device_ex(arr, n, C.byref(c), C.byref(ex), C.byref(planes), C.c_void_p(occlusion_ptr or None), strides[0],
+                                                         C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), strides[1],
+                                                         C.c_void_p(bounds_ptr or None), C.c_void_p(stream)))
+        return
+    s, o = _shot_c(shot)
     if o != 0.0:
         check(load().mcrt_composite_shot_batch_device_occ(arr, n, C.byref(c), C.byref(s), C.byref(planes), C.c_void_p(occlusion_ptr or None), o, strides[0],
                                                           C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), strides[1], C.c_void_p(stream)))
@@ -1434,11 +1490,13 @@ class SkinBatch:
             stream.synchronize()
             return host[:m].numpy().copy()
 
-    def shots(self, skins, config: Config, shot: Optional[abi.Shot] = None, ground=0.0, rgba8: bool = True) -> np.ndarray:
+    def shots(self, skins, config: Config, shot: Optional[abi.Shot] = None, ground=0.0, rgba8: bool = True, bounds: bool = False):
         """The studio shots of the ``m`` skins (``TileRenderer.renderShotBatch`` of the scenes built per skin, bit for bit): one
         upload, one repaint, one ``render_shot_batch_device`` call — render, ground, reflection and blend on the device — and
         one download of 4 B/pixel (16 with ``rgba8=False``).  ``ground``: one height for all (0.0: the soles of the builder's
-        standing figure), or ``m`` heights.  The scenes' background mode (``render``'s) is not touched."""
+        standing figure), or ``m`` heights.  The scenes' background mode (``render``'s) is not touched.  ``bounds=True``
+        (``Shot(page="transparent")`` only): the pair (images, (m, 4) int32 boxes {x0, y0, x1, y1}), the boxes written by the
+        blend and downloaded with the images."""
         torch = self._torch
         w, h = max(config.width, 0), max(config.height, 0)
         np_dtype = np.uint8 if rgba8 else np.float32
@@ -1447,28 +1505,32 @@ class SkinBatch:
             if w == 0 or h == 0 or config.tileSize <= 0:  # no frame: nothing is painted either
                 out = np.zeros((len(self._check_skins(skins)), h, w, 4), np_dtype)
                 out[..., 3] = 255 if rgba8 else 1.0
-                return out
+                return (out, _empty_bounds(len(out), w, h)) if bounds else out
             a = self._check_skins(skins)
             if ground is None:
                 raise ValueError("ground heights are needed: a resident scene does not keep its description")
             heights = _ground_heights(list(range(len(a))), ground)
-            need = shot_scratch_bytes(config, shot, len(self.scenes))  # (raises nothing: an invalid shot is refused by the call below)
+            need = shot_scratch_bytes(config, shot, len(self.scenes), bounds)  # (raises nothing: an invalid shot is refused by the call below)
             m = self._paint(a, stream)
             if m == 0:
-                return np.zeros((0, h, w, 4), np_dtype)
+                none = np.zeros((0, h, w, 4), np_dtype)
+                return (none, _empty_bounds(0, w, h)) if bounds else none
             scratch = self._out.get("shot_scratch")
             if scratch is None or scratch.numel() < need:
                 scratch = torch.empty((max(need, 16),), dtype=torch.uint8, device=self._dev)
                 self._out["shot_scratch"] = scratch
             dev, host = self._buffers("shots", (len(self.scenes), h, w, 4), torch.uint8 if rgba8 else torch.float32)
+            box_dev, box_host = self._buffers("shot_bounds", (len(self.scenes), 4), torch.int32) if bounds else (None, None)
             try:
                 render_shot_batch_device(self.scenes[:m], config, shot, heights, scratch.data_ptr(), scratch.numel(), 0 if rgba8 else dev.data_ptr(),
-                                         dev.data_ptr() if rgba8 else 0, w * h, stream.cuda_stream)
+                                         dev.data_ptr() if rgba8 else 0, w * h, stream.cuda_stream, box_dev.data_ptr() if bounds else 0)
                 with torch.cuda.stream(stream):
                     host[:m].copy_(dev[:m], non_blocking=True)
+                    if bounds:
+                        box_host[:m].copy_(box_dev[:m], non_blocking=True)
             finally:
                 stream.synchronize()  # (a refused shot too: the repaint reads the pinned staging buffer)
-            return host[:m].numpy().copy()
+            return (host[:m].numpy().copy(), box_host[:m].numpy().copy()) if bounds else host[:m].numpy().copy()
 
     def layers(self, skins, config: Config, layers=abi.LAYER_NAMES) -> dict:
         """The geometry layers of the ``m`` skins' frames (``TileRenderer.renderLayersBatch``'s planes) through

@@ -980,15 +980,31 @@ size_t mcrt_shot_scratch_bytes_occ(const mcrt_config* cfg, const mcrt_shot* shot
     return shot_scratch(cfg, shot, n_frames, floor_occlusion).bytes;
 }
 
-// the host forms with and without the floor-occlusion term (the latter: floor_occlusion = 0)
+void mcrt_shot_ex_init(mcrt_shot_ex* shot) {
+    if (!shot) return;
+    mcrt_shot_init(&shot->shot);
+    shot->floor_occlusion = 0.0f;
+    shot->shadow_color[0] = shot->shadow_color[1] = shot->shadow_color[2] = 0.0f;
+}
+
+size_t mcrt_shot_scratch_bytes_ex(const mcrt_config* cfg, const mcrt_shot_ex* shot, int n_frames) {
+    if (!cfg || !shot || n_frames <= 0 || !valid_frame(cfg) || shot_frame_too_large(cfg)) return 0;
+    ShotExtra ex;
+    std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
+    if (check_shot_ex(&shot->shot, ex) != MCRT_OK || check_floor_occlusion(shot->floor_occlusion) != MCRT_OK) return 0;
+    return shot_scratch(cfg, &shot->shot, n_frames, shot->floor_occlusion).bytes;
+}
+
+// the host forms with and without the floor-occlusion term (the latter: floor_occlusion = 0); ex: the _ex entries' additions
+// (bounds: n_frames entries in HOST memory, downloaded with the image), nullptr for the entries before them
 static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion,
-                                  const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device) {
+                                  const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device, const ShotExtra* ex = nullptr) {
     // the device form's checks that need no handle, before anything is created
     if (n_frames < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || (n_frames > 0 && (!descs || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n_frames; ++i)
         if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
-    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     for (int i = 0; i < n_frames; ++i)
         if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
@@ -1005,14 +1021,20 @@ static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_fra
     const size_t scratch_bytes = shot_scratch(cfg, shot, n_frames, floor_occlusion).bytes;
     const size_t f32_bytes = out_rgba ? px * 16 * static_cast<size_t>(n_frames) : 0;
     const size_t u8_bytes = out_rgba8 ? px * 4 * static_cast<size_t>(n_frames) : 0;
-    hipError_t e = s0->frame.reserve(scratch_bytes + f32_bytes + u8_bytes);
+    const size_t bounds_bytes = ex && ex->bounds ? sizeof(int32_t[4]) * static_cast<size_t>(n_frames) : 0;
+    hipError_t e = s0->frame.reserve(scratch_bytes + f32_bytes + u8_bytes + bounds_bytes);
     if (e != hipSuccess) return hip_fail(e, "shot planes");
     char* base = static_cast<char*>(s0->frame.ptr);
     float* d_f32 = out_rgba ? reinterpret_cast<float*>(base + scratch_bytes) : nullptr;
     uint8_t* d_u8 = out_rgba8 ? reinterpret_cast<uint8_t*>(base + scratch_bytes + f32_bytes) : nullptr;
-    rc = render_shot_batch_device(set.h.data(), n_frames, cfg, shot, floor_occlusion, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream);
+    ShotExtra on_device;  // the caller's additions, with the bounds in device memory behind the outputs (u8_bytes is a multiple of 4)
+    if (ex) on_device = *ex;
+    on_device.bounds = bounds_bytes ? reinterpret_cast<int32_t(*)[4]>(base + scratch_bytes + f32_bytes + u8_bytes) : nullptr;
+    rc = render_shot_batch_device(set.h.data(), n_frames, cfg, shot, floor_occlusion, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream,
+                                  ex ? &on_device : nullptr);
     set.download(out_rgba, d_f32, f32_bytes, rc);
     set.download(out_rgba8, d_u8, u8_bytes, rc);
+    if (bounds_bytes) set.download(ex->bounds, on_device.bounds, bounds_bytes, rc);
     if (rc == MCRT_OK) {
         e = hipStreamSynchronize(s0->main_stream);
         if (e != hipSuccess) rc = hip_fail(e, "shot render");
@@ -1038,10 +1060,11 @@ int mcrt_render_shot(const mcrt_scene_desc* desc, const mcrt_config* cfg, const 
     return mcrt_render_shot_batch(one, 1, cfg, shot, &ground_y, out_rgba, out_rgba8, device);
 }
 
+// ex: mcrt_render_shot_png_ex's additions — bounds (one entry in host memory, or nullptr) and crop
 static int render_shot_png_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, float ground_y, const char* path,
-                                int device) {
+                                int device, const ShotExtra* ex = nullptr) {
     if (!desc || !cfg || !shot || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
-    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
     if (const int rc = check_shot_config(cfg, shot, floor_occlusion); rc != MCRT_OK) return rc;
@@ -1049,9 +1072,42 @@ static int render_shot_png_host(const mcrt_scene_desc* desc, const mcrt_config* 
     if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
     std::vector<uint8_t> host(static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) * 4);
     const mcrt_scene_desc* one[1] = {desc};
-    const int rc = render_shot_batch_host(one, 1, cfg, shot, floor_occlusion, &ground_y, nullptr, host.data(), device);
+    if (!ex) {
+        const int rc = render_shot_batch_host(one, 1, cfg, shot, floor_occlusion, &ground_y, nullptr, host.data(), device);
+        if (rc != MCRT_OK) return rc;
+        return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
+    }
+    // the cut-out's file: the box comes down with the image where the page is transparent and somebody wants it
+    int32_t box[1][4] = {{0, 0, cfg->width, cfg->height}};
+    ShotExtra with_box = *ex;
+    with_box.bounds = shot->page == MCRT_PAGE_TRANSPARENT && (ex->bounds || ex->crop) ? box : nullptr;
+    const int rc = render_shot_batch_host(one, 1, cfg, shot, floor_occlusion, &ground_y, nullptr, host.data(), device, &with_box);
     if (rc != MCRT_OK) return rc;
-    return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
+    if (ex->bounds) std::memcpy(ex->bounds[0], box[0], sizeof box[0]);
+    const int x0 = box[0][0], y0 = box[0][1], x1 = box[0][2], y1 = box[0][3];
+    if (!ex->crop || x1 <= x0 || y1 <= y0) return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);  // an empty box: the whole frame
+    const size_t row = static_cast<size_t>(x1 - x0) * 4;
+    std::vector<uint8_t> cut(row * static_cast<size_t>(y1 - y0));
+    for (int y = y0; y < y1; ++y)
+        std::memcpy(cut.data() + static_cast<size_t>(y - y0) * row, host.data() + (static_cast<size_t>(y) * static_cast<size_t>(cfg->width) + static_cast<size_t>(x0)) * 4, row);
+    return mcrt_write_png_rgba8(path, cut.data(), x1 - x0, y1 - y0);
+}
+
+int mcrt_render_shot_batch_ex(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot, const float* ground_y,
+                              float* out_rgba, uint8_t* out_rgba8, int32_t (*out_bounds)[4], int device) {
+    ShotExtra ex;
+    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
+    ex.bounds = out_bounds;
+    return render_shot_batch_host(descs, n_frames, cfg, shot ? &shot->shot : nullptr, shot ? shot->floor_occlusion : 0.0f, ground_y, out_rgba, out_rgba8, device, &ex);
+}
+
+int mcrt_render_shot_png_ex(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot_ex* shot, float ground_y, const char* path, int crop,
+                            int32_t* out_bounds, int device) {
+    ShotExtra ex;
+    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
+    ex.bounds = reinterpret_cast<int32_t(*)[4]>(out_bounds);
+    ex.crop = crop != 0;
+    return render_shot_png_host(desc, cfg, shot ? &shot->shot : nullptr, shot ? shot->floor_occlusion : 0.0f, ground_y, path, device, &ex);
 }
 
 int mcrt_render_shot_png(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, const char* path, int device) {

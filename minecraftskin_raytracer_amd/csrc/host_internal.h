@@ -253,6 +253,26 @@ inline int check_floor_occlusion(float o) {
     if (!(o >= 0.0f && o <= 1.0f)) return fail(MCRT_ERR_INVALID, "floor_occlusion must lie in [0, 1]");
     return MCRT_OK;
 }
+// What the _ex entry points add to a shot (the entries before them pass nullptr): the shadow's colour and the bounds — device
+// memory behind the device forms, host memory behind the host forms.  With it the shot's page may be MCRT_PAGE_TRANSPARENT.
+struct ShotExtra {
+    float shadow_color[3] = {0.0f, 0.0f, 0.0f};
+    int32_t (*bounds)[4] = nullptr;
+    bool crop = false;  // mcrt_render_shot_png_ex's: like the bounds, only with the transparent page
+};
+// what they refuse of the shot: check_shot's list with the third page, then the colour and what needs the transparent page
+inline int check_shot_ex(const mcrt_shot* s, const ShotExtra& ex) {
+    if (s->page < MCRT_PAGE_COLOR || s->page > MCRT_PAGE_TRANSPARENT)
+        return fail(MCRT_ERR_INVALID, "page must be MCRT_PAGE_COLOR, MCRT_PAGE_REFERENCE or MCRT_PAGE_TRANSPARENT");
+    mcrt_shot on_a_page = *s;
+    if (s->page == MCRT_PAGE_TRANSPARENT) on_a_page.page = MCRT_PAGE_COLOR;
+    if (const int rc = check_shot(&on_a_page); rc != MCRT_OK) return rc;
+    for (const float c : ex.shadow_color)
+        if (!std::isfinite(c)) return fail(MCRT_ERR_INVALID, "shadow_color must be finite");
+    if (s->page != MCRT_PAGE_TRANSPARENT && (ex.bounds || ex.crop)) return fail(MCRT_ERR_INVALID, "bounds and crop come with MCRT_PAGE_TRANSPARENT only");
+    return MCRT_OK;
+}
+inline int check_shot(const mcrt_shot* s, const ShotExtra* ex) { return ex ? check_shot_ex(s, *ex) : check_shot(s); }
 // and of the config of a shot that renders: the render's limit, and the limits of the passes the shot runs
 int validate_config(const mcrt_config* cfg);
 inline int check_shot_config(const mcrt_config* c, const mcrt_shot* s, float floor_occlusion = 0.0f) {
@@ -358,12 +378,14 @@ int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_confi
 int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream);
 // the studio shot's blend on the caller's planes (mcrt_composite_shot_batch_device[_occ]), and render + ground + reflection +
 // ground occlusion + blend on `stream` in order with the planes in the caller's scratch (mcrt_render_shot_batch_device[_occ]);
-// the entries without the floor-occlusion term pass floor_occlusion = 0 and no plane
+// the entries without the floor-occlusion term pass floor_occlusion = 0 and no plane; ex: the _ex entries' additions (bounds:
+// device memory), nullptr for the entries before them, which then launch the kernels they always launched
 int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
                                 const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride,
-                                hipStream_t stream);
+                                hipStream_t stream, const ShotExtra* ex = nullptr);
 int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, const float* ground_y,
-                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream);
+                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream,
+                             const ShotExtra* ex = nullptr);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 // gives the n repaintable handles the views (poses[i], looks[i]); NULL poses, looks or looks[i]: the handle's own

@@ -1103,7 +1103,8 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
 namespace {
 // the launches of the blend, behind every check: frame i of the inputs in_stride pixels on, of the outputs out_stride pixels on
 int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs& in,
-                       const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
+                       const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream,
+                       const ShotExtra* ex) {
     ShotShape shape;
     std::memset(&shape, 0, sizeof shape);
     shape.cfg = *cfg;
@@ -1126,21 +1127,37 @@ int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_
         f.out = d_f32 ? d_f32 + to * 4 : nullptr;
         f.out8 = d_u8 ? d_u8 + to * 4 : nullptr;
     }
+    if (!ex)
+        return launch_pass(
+            device, frames, stream, "shot launches", [&](const ShotFrame& f) { return launch_shot(f, shape, stream); },
+            [&](const ShotFrame* d_table, int m) { return launch_shot_batch(d_table, m, shape, stream); });
+    // the _ex kernels; the bounds' identities lie ahead of them in the stream, and each launch takes the entries of its frames
+    ShotShapeEx shape_ex;
+    shape_ex.shot = shape;
+    std::memcpy(shape_ex.shadow_color, ex->shadow_color, sizeof shape_ex.shadow_color);
+    int32_t* d_bounds = ex->bounds ? &ex->bounds[0][0] : nullptr;
+    if (d_bounds)
+        if (const hipError_t e = launch_shot_bounds_init(d_bounds, n, cfg->width, cfg->height, stream); e != hipSuccess) return hip_fail(e, "shot launches");
+    int done = 0;  // frames in the launches so far
     return launch_pass(
-        device, frames, stream, "shot launches", [&](const ShotFrame& f) { return launch_shot(f, shape, stream); },
-        [&](const ShotFrame* d_table, int m) { return launch_shot_batch(d_table, m, shape, stream); });
+        device, frames, stream, "shot launches", [&](const ShotFrame& f) { return launch_shot_ex(f, shape_ex, d_bounds, stream); },
+        [&](const ShotFrame* d_table, int m) {
+            const hipError_t e = launch_shot_ex_batch(d_table, m, shape_ex, d_bounds ? d_bounds + 4 * static_cast<size_t>(done) : nullptr, stream);
+            done += m;
+            return e;
+        });
 }
 }  // namespace
 
 int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
                                 const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride,
-                                hipStream_t stream) {
+                                hipStream_t stream, const ShotExtra* ex) {
     // argument checks, before any device work (only the last one looks inside the handles, at their device index)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || !d_in || !d_in->figure || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n; ++i)
         if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
-    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     if (shot->reflection_fade > 0.0f && !d_in->reflection_distance)
         return fail(MCRT_ERR_INVALID, "reflection_distance may be NULL only with reflection_fade == 0");
@@ -1156,20 +1173,20 @@ int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_con
     HIP_TRY(hipSetDevice(device));
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a shot cannot be recorded into a caller's graph");
     (void)hipGetLastError();
-    return launch_shot_frames(scenes, n, device, cfg, shot, *d_in, d_occlusion, floor_occlusion, in_stride, d_f32, d_u8, out_stride, stream);
+    return launch_shot_frames(scenes, n, device, cfg, shot, *d_in, d_occlusion, floor_occlusion, in_stride, d_f32, d_u8, out_stride, stream, ex);
 }
 
 // Render + ground + reflection + ground occlusion + blend, all on `stream` in order.  The render goes through render_batch_device (the handles'
 // event chains, batched kernels where the frames fit them) under the transparent override; the passes and the blend follow it
 // in stream order and take no events.  Nothing is forked beside the render.
 int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, const float* ground_y,
-                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream) {
+                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream, const ShotExtra* ex) {
     // argument checks, before any device work (only the last ones look inside the handles, at their device index)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || (n > 0 && (!scenes || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n; ++i)
         if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
-    if (const int rc = check_shot(shot); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
@@ -1189,7 +1206,9 @@ int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config
     if (!d_scratch) return fail(MCRT_ERR_INVALID, "d_scratch is NULL");
     if ((reinterpret_cast<uintptr_t>(d_scratch) & 15u) != 0) return fail(MCRT_ERR_INVALID, "d_scratch is not 16-byte aligned");
     if (scratch_bytes < at.bytes)
-        return fail(MCRT_ERR_INVALID, floor_occlusion > 0.0f ? "scratch_bytes is smaller than mcrt_shot_scratch_bytes_occ" : "scratch_bytes is smaller than mcrt_shot_scratch_bytes");
+        return fail(MCRT_ERR_INVALID, ex                       ? "scratch_bytes is smaller than mcrt_shot_scratch_bytes_ex"
+                                      : floor_occlusion > 0.0f ? "scratch_bytes is smaller than mcrt_shot_scratch_bytes_occ"
+                                                               : "scratch_bytes is smaller than mcrt_shot_scratch_bytes");
     const int device = scenes[0]->device;
     for (int i = 1; i < n; ++i)
         if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
@@ -1223,7 +1242,7 @@ int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config
         o.occlusion = plane(at.occlusion);
         if (const int rc = render_ground_occlusion_batch_device(scenes, n, cfg, ground_y, &o, px, stream); rc != MCRT_OK) return rc;
     }
-    return launch_shot_frames(scenes, n, device, cfg, shot, in, plane(at.occlusion), floor_occlusion, px, d_f32, d_u8, stride, stream);
+    return launch_shot_frames(scenes, n, device, cfg, shot, in, plane(at.occlusion), floor_occlusion, px, d_f32, d_u8, stride, stream, ex);
 }
 
 }  // namespace mcrt_host
@@ -1421,6 +1440,27 @@ int mcrt_render_shot_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_sh
     mcrt_scene* one[1] = {s};
     const size_t px = valid_frame(cfg) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
     return render_shot_batch_device(one, 1, cfg, shot, 0.0f, &ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, px, static_cast<hipStream_t>(stream));
+}
+
+// the _ex entries: the _occ entries' paths with the shot's additions beside it (a NULL shot is refused there, as theirs is)
+int mcrt_composite_shot_batch_device_ex(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot, const mcrt_shot_inputs* d_in,
+                                        const float* d_occlusion, size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8, size_t out_stride_pixels,
+                                        int32_t (*d_bounds)[4], void* stream) {
+    ShotExtra ex;
+    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
+    ex.bounds = d_bounds;
+    return composite_shot_batch_device(scenes, n_frames, cfg, shot ? &shot->shot : nullptr, d_in, d_occlusion, shot ? shot->floor_occlusion : 0.0f,
+                                       in_stride_pixels, d_out_f32, d_out_rgba8, out_stride_pixels, static_cast<hipStream_t>(stream), &ex);
+}
+
+int mcrt_render_shot_batch_device_ex(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot, const float* ground_y,
+                                     void* d_scratch, size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8, size_t frame_stride_pixels,
+                                     int32_t (*d_bounds)[4], void* stream) {
+    ShotExtra ex;
+    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
+    ex.bounds = d_bounds;
+    return render_shot_batch_device(scenes, n_frames, cfg, shot ? &shot->shot : nullptr, shot ? shot->floor_occlusion : 0.0f, ground_y, d_scratch, scratch_bytes,
+                                    d_out_f32, d_out_rgba8, frame_stride_pixels, static_cast<hipStream_t>(stream), &ex);
 }
 
 int mcrt_render_light_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_light_planes* d_out, void* stream) {
