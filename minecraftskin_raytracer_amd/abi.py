@@ -149,22 +149,11 @@ class McrtSurface(C.Structure):
 
 ID_BACK = 8  # MCRT_ID_BACK: the outer layer's exit face
 ID_OUTER = 16  # MCRT_ID_OUTER: HitResult::isOuterLayer
-LAYER_NAMES = ("depth", "normal", "albedo", "id")
-# per pixel: (dtype, components) of each plane
-LAYER_FORMATS = {"depth": (np.float32, 1), "normal": (np.float32, 4), "albedo": (np.float32, 4), "id": (np.int32, 4)}
-
-
-def layer_names(layers) -> tuple:
-    """The wanted planes in the order of ``LAYER_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
-    if isinstance(layers, str):
-        layers = (layers,)
-    names = tuple(layers)
-    for n in names:
-        if not isinstance(n, str) or n not in LAYER_FORMATS:
-            raise ValueError(f"layers must be taken from {LAYER_NAMES}, not {n!r}")
-    if not names:
-        raise ValueError("no layer selected")
-    return tuple(n for n in LAYER_NAMES if n in names)
+GROUND_MAX_SAMPLES = 113  # shadowSamples of a ground pass with softShadows on
+GROUND_OCCLUSION_MAX_SAMPLES = 113  # aoSamples of a ground-occlusion pass: 1 .. 113
+REFLECTION_MAX_BOUNCES = 8  # maxBounces of a reflection pass
+LIGHT_MAX_SAMPLES = 113  # shadowSamples (with softShadows on) and aoSamples (with the occlusion plane) of a light pass
+BAKE_MAX_GRID = 4  # sub-samples per texel and axis of a light bake: grid 1..4
 
 
 class McrtGround(C.Structure):
@@ -173,48 +162,10 @@ class McrtGround(C.Structure):
     _fields_ = [("visibility", C.c_void_p), ("distance", C.c_void_p), ("matte", C.c_void_p)]
 
 
-GROUND_NAMES = ("visibility", "distance", "matte")
-# per pixel: the dtype of each plane (one component each)
-GROUND_FORMATS = {"visibility": np.float32, "distance": np.float32, "matte": np.uint8}
-GROUND_MAX_SAMPLES = 113  # shadowSamples of a ground pass with softShadows on
-
-
-def ground_names(planes) -> tuple:
-    """The wanted ground planes in the order of ``GROUND_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
-    if isinstance(planes, str):
-        planes = (planes,)
-    names = tuple(planes)
-    for n in names:
-        if not isinstance(n, str) or n not in GROUND_FORMATS:
-            raise ValueError(f"planes must be taken from {GROUND_NAMES}, not {n!r}")
-    if not names:
-        raise ValueError("no plane selected")
-    return tuple(n for n in GROUND_NAMES if n in names)
-
-
 class McrtGroundOcclusion(C.Structure):
     """mcrt_ground_occlusion: one pointer per plane of a ground-occlusion pass (device or host memory, by entry point); NULL = not wanted."""
 
     _fields_ = [("occlusion", C.c_void_p), ("matte", C.c_void_p)]
-
-
-GROUND_OCCLUSION_NAMES = ("occlusion", "matte")
-# per pixel: the dtype of each plane (one component each)
-GROUND_OCCLUSION_FORMATS = {"occlusion": np.float32, "matte": np.uint8}
-GROUND_OCCLUSION_MAX_SAMPLES = 113  # aoSamples of a ground-occlusion pass: 1 .. 113
-
-
-def ground_occlusion_names(planes) -> tuple:
-    """The wanted ground-occlusion planes in the order of ``GROUND_OCCLUSION_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
-    if isinstance(planes, str):
-        planes = (planes,)
-    names = tuple(planes)
-    for n in names:
-        if not isinstance(n, str) or n not in GROUND_OCCLUSION_FORMATS:
-            raise ValueError(f"planes must be taken from {GROUND_OCCLUSION_NAMES}, not {n!r}")
-    if not names:
-        raise ValueError("no plane selected")
-    return tuple(n for n in GROUND_OCCLUSION_NAMES if n in names)
 
 
 class McrtReflection(C.Structure):
@@ -223,48 +174,10 @@ class McrtReflection(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("rgba8", C.c_void_p), ("distance", C.c_void_p)]
 
 
-REFLECTION_NAMES = ("rgba", "rgba8", "distance")
-# per pixel: (dtype, components) of each plane
-REFLECTION_FORMATS = {"rgba": (np.float32, 4), "rgba8": (np.uint8, 4), "distance": (np.float32, 1)}
-REFLECTION_MAX_BOUNCES = 8  # maxBounces of a reflection pass
-
-
-def reflection_names(planes) -> tuple:
-    """The wanted reflection planes in the order of ``REFLECTION_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
-    if isinstance(planes, str):
-        planes = (planes,)
-    names = tuple(planes)
-    for n in names:
-        if not isinstance(n, str) or n not in REFLECTION_FORMATS:
-            raise ValueError(f"planes must be taken from {REFLECTION_NAMES}, not {n!r}")
-    if not names:
-        raise ValueError("no plane selected")
-    return tuple(n for n in REFLECTION_NAMES if n in names)
-
-
 class McrtLightPlanes(C.Structure):
     """mcrt_light_planes: one pointer per plane of a light pass (device or host memory, by entry point); NULL = not wanted."""
 
     _fields_ = [("visibility", C.c_void_p), ("occlusion", C.c_void_p), ("direct", C.c_void_p)]
-
-
-LIGHT_NAMES = ("visibility", "occlusion", "direct")
-# per pixel: (dtype, components) of each plane
-LIGHT_FORMATS = {"visibility": (np.float32, 1), "occlusion": (np.float32, 1), "direct": (np.float32, 4)}
-LIGHT_MAX_SAMPLES = 113  # shadowSamples (with softShadows on) and aoSamples (with the occlusion plane) of a light pass
-
-
-def light_names(planes) -> tuple:
-    """The wanted light planes in the order of ``LIGHT_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
-    if isinstance(planes, str):
-        planes = (planes,)
-    names = tuple(planes)
-    for n in names:
-        if not isinstance(n, str) or n not in LIGHT_FORMATS:
-            raise ValueError(f"planes must be taken from {LIGHT_NAMES}, not {n!r}")
-    if not names:
-        raise ValueError("no plane selected")
-    return tuple(n for n in LIGHT_NAMES if n in names)
 
 
 class McrtBakePlanes(C.Structure):
@@ -273,24 +186,67 @@ class McrtBakePlanes(C.Structure):
     _fields_ = [("position", C.c_void_p), ("normal", C.c_void_p), ("visibility", C.c_void_p), ("occlusion", C.c_void_p), ("direct", C.c_void_p)]
 
 
-BAKE_NAMES = ("position", "normal", "visibility", "occlusion", "direct")
-# per pool texel: (dtype, components) of each plane
-BAKE_FORMATS = {"position": (np.float32, 4), "normal": (np.float32, 4), "visibility": (np.float32, 1), "occlusion": (np.float32, 1),
-                "direct": (np.float32, 4)}
-BAKE_MAX_GRID = 4  # sub-samples per texel and axis of a light bake: grid 1..4
+@dataclass(frozen=True)
+class PlaneFamily:
+    """The output planes of one pass.  ``struct``: the ctypes structure, one pointer per plane in the order of ``formats``;
+    ``entry``: the C name of the pass's one-shot host form, which ``_device`` and ``_batch_device`` follow for the forms on
+    resident scenes; ``formats``: per plane, in canonical order, ``(dtype, components)`` of one pixel (of one pool texel for a
+    bake); ``miss``: what a plane holds where nothing is hit, 0 for a plane not listed; ``noun``: what the selection's messages
+    call a plane."""
+
+    struct: type
+    entry: str
+    formats: dict
+    miss: dict
+    noun: str = "plane"
+
+    @property
+    def names(self) -> tuple:
+        return tuple(self.formats)
+
+    def select(self, planes) -> tuple:
+        """The wanted planes in canonical order; an empty selection or an unknown name raises ``ValueError``."""
+        if isinstance(planes, str):
+            planes = (planes,)
+        names = tuple(planes)
+        for n in names:
+            if not isinstance(n, str) or n not in self.formats:
+                raise ValueError(f"{self.noun}s must be taken from {self.names}, not {n!r}")
+        if not names:
+            raise ValueError(f"no {self.noun} selected")
+        return tuple(n for n in self.formats if n in names)
+
+    def empty(self, name: str, n: int, *shape: int) -> np.ndarray:
+        """One plane for n frames of ``shape`` (height, width; none for a bake's n texels), holding the miss value: what a frame
+        of zero size keeps."""
+        dtype, comps = self.formats[name]
+        a = np.zeros((n,) + shape + ((comps,) if comps > 1 else ()), dtype)
+        if name in self.miss:
+            a[...] = self.miss[name]
+        return a
 
 
-def bake_names(planes) -> tuple:
-    """The wanted bake planes in the order of ``BAKE_NAMES``; an empty selection or an unknown name raises ``ValueError``."""
-    if isinstance(planes, str):
-        planes = (planes,)
-    names = tuple(planes)
-    for n in names:
-        if not isinstance(n, str) or n not in BAKE_FORMATS:
-            raise ValueError(f"planes must be taken from {BAKE_NAMES}, not {n!r}")
-    if not names:
-        raise ValueError("no plane selected")
-    return tuple(n for n in BAKE_NAMES if n in names)
+_F1, _F4, _FLT_MAX = (np.float32, 1), (np.float32, 4), np.finfo(np.float32).max
+# One row per family: a new pass, or a new plane of a pass, is added here (and to its structure above).
+LAYERS = PlaneFamily(McrtLayers, "mcrt_render_layers", {"depth": _F1, "normal": _F4, "albedo": _F4, "id": (np.int32, 4)},
+                     {"depth": _FLT_MAX, "id": (-1, 0, -1, -1)}, noun="layer")
+GROUND = PlaneFamily(McrtGround, "mcrt_render_ground", {"visibility": _F1, "distance": _F1, "matte": (np.uint8, 1)},
+                     {"visibility": 1, "distance": _FLT_MAX})
+GROUND_OCCLUSION = PlaneFamily(McrtGroundOcclusion, "mcrt_render_ground_occlusion", {"occlusion": _F1, "matte": (np.uint8, 1)}, {"occlusion": 1})
+REFLECTION = PlaneFamily(McrtReflection, "mcrt_render_reflection", {"rgba": _F4, "rgba8": (np.uint8, 4), "distance": _F1}, {"distance": _FLT_MAX})
+LIGHT = PlaneFamily(McrtLightPlanes, "mcrt_render_light", {"visibility": _F1, "occlusion": _F1, "direct": _F4}, {"visibility": 1, "occlusion": 1})
+BAKE = PlaneFamily(McrtBakePlanes, "mcrt_bake_light", {"position": _F4, "normal": _F4, "visibility": _F1, "occlusion": _F1, "direct": _F4},
+                   {"visibility": 1, "occlusion": 1})
+FAMILIES = {"layers": LAYERS, "ground": GROUND, "ground_occlusion": GROUND_OCCLUSION, "reflection": REFLECTION, "light": LIGHT, "bake": BAKE}
+
+# the names these had before the table
+LAYER_NAMES, LAYER_FORMATS, layer_names = LAYERS.names, LAYERS.formats, LAYERS.select
+GROUND_NAMES, GROUND_FORMATS, ground_names = GROUND.names, {k: d for k, (d, _) in GROUND.formats.items()}, GROUND.select  # (a bare dtype per plane)
+GROUND_OCCLUSION_NAMES, GROUND_OCCLUSION_FORMATS, ground_occlusion_names = (
+    GROUND_OCCLUSION.names, {k: d for k, (d, _) in GROUND_OCCLUSION.formats.items()}, GROUND_OCCLUSION.select)  # (a bare dtype per plane)
+REFLECTION_NAMES, REFLECTION_FORMATS, reflection_names = REFLECTION.names, REFLECTION.formats, REFLECTION.select
+LIGHT_NAMES, LIGHT_FORMATS, light_names = LIGHT.names, LIGHT.formats, LIGHT.select
+BAKE_NAMES, BAKE_FORMATS, bake_names = BAKE.names, BAKE.formats, BAKE.select
 
 
 PAGE_COLOR = 0  # MCRT_PAGE_*: the page of a studio shot is Shot.pageColor

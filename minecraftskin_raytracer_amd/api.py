@@ -134,6 +134,23 @@ def _devices(device):
     return d, None
 
 
+def _frame(config: Config) -> Tuple[int, int, bool]:
+    """(width, height) with negatives as 0, and whether the frame holds no tile: then a call writes nothing."""
+    w, h = max(config.width, 0), max(config.height, 0)
+    return w, h, w == 0 or h == 0 or config.tileSize <= 0
+
+
+def _default_frames(n: int, h: int, w: int, rgba8: bool) -> np.ndarray:
+    """n frames of Image(w, h)'s default Color() = (0, 0, 0, 1): (n, h, w, 4) float32, or uint8 (0, 0, 0, 255) with ``rgba8``."""
+    out = np.zeros((n, h, w, 4), np.uint8 if rgba8 else np.float32)
+    out[..., 3] = 255 if rgba8 else 1.0
+    return out
+
+
+def _desc_array(descs):
+    return (C.POINTER(abi.McrtSceneDesc) * max(len(descs), 1))(*[d.ptr for d in descs])
+
+
 class TileRenderer:
     """raytracer/tile_renderer.h:16-47."""
 
@@ -164,14 +181,13 @@ class TileRenderer:
         lib = load()
         d = _as_desc(scene)
         c = config.to_c()
-        w, h = max(config.width, 0), max(config.height, 0)
+        w, h, no_frame = _frame(config)
         if out is None:
-            out = np.zeros((h, w, 4), np.float32)
-            out[..., 3] = 1.0  # Image(w,h): default Color() = (0,0,0,1)
+            out = _default_frames(1, h, w, False)[0]
         elif out.shape != (h, w, 4) or out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"]:
             raise ValueError("out must be a C-contiguous (height, width, 4) float32 array")
         TileRenderer._errors = []
-        if w == 0 or h == 0 or config.tileSize <= 0:
+        if no_frame:
             return out
         cb = abi.PROGRESS_FN((lambda done, total, _u: progressCallback(done, total))) if progressCallback else C.cast(None, abi.PROGRESS_FN)
         one, devs = _devices(device)
@@ -212,11 +228,10 @@ class TileRenderer:
         mode = abi.background_mode(background)
         lib = load()
         c = config.to_c()
-        w, h = max(config.width, 0), max(config.height, 0)
-        out = np.zeros((h, w, 4), np.uint8)
-        out[..., 3] = 255
+        w, h, no_frame = _frame(config)
+        out = _default_frames(1, h, w, True)[0]
         TileRenderer._errors = []
-        if w == 0 or h == 0 or config.tileSize <= 0:
+        if no_frame:
             return out
         one, devs = _devices(device)
         if one is not None:
@@ -243,13 +258,10 @@ class TileRenderer:
         mode = abi.background_mode(background)
         descs = [_as_desc(s) for s in scenes]
         n = len(descs)
-        w, h = max(config.width, 0), max(config.height, 0)
-        dtype = np.uint8 if rgba8 else np.float32
-        out = np.zeros((n, h, w, 4), dtype)
-        out[..., 3] = 255 if rgba8 else 1.0  # Image(w,h): default Color() = (0,0,0,1)
+        w, h, _ = _frame(config)
+        out = _default_frames(n, h, w, rgba8)
         c = config.to_c()
-        ptrs = [d.ptr for d in descs]
-        arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*ptrs)
+        arr = _desc_array(descs)
         f = None if rgba8 else abi.fptr(out)
         b = out.ctypes.data_as(C.POINTER(C.c_uint8)) if rgba8 else None
         if mode != abi.BACKGROUND_REFERENCE:
@@ -271,17 +283,16 @@ class TileRenderer:
     def renderLayersBatch(scenes, config: Config, layers=abi.LAYER_NAMES, device: int = 0) -> dict:
         """``renderLayers`` for N scenes of one config in one launch (mcrt_render_layers_batch): the same planes with a leading
         N."""
-        names = abi.layer_names(layers)
+        names = abi.LAYERS.select(layers)
         descs = [_as_desc(s) for s in scenes]
         n = len(descs)
-        w, h = max(config.width, 0), max(config.height, 0)
-        out = {k: _empty_layer(k, n, h, w) for k in names}
-        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
+        w, h, no_frame = _frame(config)
+        out = {k: abi.LAYERS.empty(k, n, h, w) for k in names}
+        if n == 0 or no_frame:
             return out
         c = config.to_c()
-        arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*[d.ptr for d in descs])
         planes = abi.McrtLayers(**{k: v.ctypes.data for k, v in out.items()})
-        check(load().mcrt_render_layers_batch(arr, n, C.byref(c), C.byref(planes), int(device)))
+        check(load().mcrt_render_layers_batch(_desc_array(descs), n, C.byref(c), C.byref(planes), int(device)))
         return out
 
     @staticmethod
@@ -301,19 +312,7 @@ class TileRenderer:
         own floor), one height for all, or a sequence of N heights.  This host form is a LOOP of ``mcrt_render_ground`` calls —
         each uploads its scene, launches, downloads and synchronises — and gains nothing from the batched kernel; the batched
         path is ``render_ground_batch_device`` on resident ``DeviceScene`` handles (one launch per 4096 frames)."""
-        names = abi.ground_names(planes)
-        descs = [_as_desc(s) for s in scenes]
-        n = len(descs)
-        heights = _ground_heights(descs, ground)
-        w, h = max(config.width, 0), max(config.height, 0)
-        out = {k: _empty_ground(k, n, h, w) for k in names}
-        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
-            return out
-        c = config.to_c()
-        for i, d in enumerate(descs):
-            frame = abi.McrtGround(**{k: v[i].ctypes.data for k, v in out.items()})
-            check(load().mcrt_render_ground(d.ptr, C.byref(c), heights[i], C.byref(frame), int(device)))
-        return out
+        return _render_pass_loop(abi.GROUND, scenes, config, planes, device, ground)
 
     @staticmethod
     def renderGroundOcclusion(scene, config: Config, ground: Optional[float] = None, planes=abi.GROUND_OCCLUSION_NAMES, device: int = 0) -> dict:
@@ -332,19 +331,7 @@ class TileRenderer:
         scene's own floor), one height for all, or a sequence of N heights.  This host form is a LOOP of
         ``mcrt_render_ground_occlusion`` calls, like ``renderGroundBatch``; the batched path is
         ``render_ground_occlusion_batch_device`` on resident ``DeviceScene`` handles (one launch per 4096 frames)."""
-        names = abi.ground_occlusion_names(planes)
-        descs = [_as_desc(s) for s in scenes]
-        n = len(descs)
-        heights = _ground_heights(descs, ground)
-        w, h = max(config.width, 0), max(config.height, 0)
-        out = {k: _empty_ground_occlusion(k, n, h, w) for k in names}
-        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
-            return out
-        c = config.to_c()
-        for i, d in enumerate(descs):
-            frame = abi.McrtGroundOcclusion(**{k: v[i].ctypes.data for k, v in out.items()})
-            check(load().mcrt_render_ground_occlusion(d.ptr, C.byref(c), heights[i], C.byref(frame), int(device)))
-        return out
+        return _render_pass_loop(abi.GROUND_OCCLUSION, scenes, config, planes, device, ground)
 
     @staticmethod
     def renderReflection(scene, config: Config, ground: Optional[float] = None, planes=abi.REFLECTION_NAMES, device: int = 0) -> dict:
@@ -363,19 +350,7 @@ class TileRenderer:
         scene's own floor), one height for all, or a sequence of N heights.  This host form is a LOOP of
         ``mcrt_render_reflection`` calls; the batched path is ``render_reflection_batch_device`` on resident ``DeviceScene``
         handles (one launch per 4096 frames)."""
-        names = abi.reflection_names(planes)
-        descs = [_as_desc(s) for s in scenes]
-        n = len(descs)
-        heights = _ground_heights(descs, ground)
-        w, h = max(config.width, 0), max(config.height, 0)
-        out = {k: _empty_reflection(k, n, h, w) for k in names}
-        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
-            return out
-        c = config.to_c()
-        for i, d in enumerate(descs):
-            frame = abi.McrtReflection(**{k: v[i].ctypes.data for k, v in out.items()})
-            check(load().mcrt_render_reflection(d.ptr, C.byref(c), heights[i], C.byref(frame), int(device)))
-        return out
+        return _render_pass_loop(abi.REFLECTION, scenes, config, planes, device, ground)
 
     @staticmethod
     def renderShot(scene, config: Config, shot: Optional[abi.Shot] = None, ground: Optional[float] = None, rgba8: bool = True,
@@ -398,29 +373,21 @@ class TileRenderer:
         one reflection launch, one blend, one download.  ``ground``: ``None`` (every scene's own floor), one height for all, or
         N heights.  Returns (N, H, W, 4) uint8, or float32 with ``rgba8=False``; with ``bounds=True`` (transparent page only)
         the pair (images, (N, 4) int32 boxes) through mcrt_render_shot_batch_ex."""
-        ex = _shot_ex_c(shot, bounds)
-        s, o = (None, 0.0) if ex is not None else _shot_c(shot)
+        variant, shot_args = _shot_variant(shot, bounds)
         descs = [_as_desc(d) for d in scenes]
         n = len(descs)
         heights = _ground_heights(descs, ground)
-        w, h = max(config.width, 0), max(config.height, 0)
-        out = np.zeros((n, h, w, 4), np.uint8 if rgba8 else np.float32)
-        out[..., 3] = 255 if rgba8 else 1.0
+        w, h, _ = _frame(config)
+        out = _default_frames(n, h, w, rgba8)
         c = config.to_c()
-        arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*[d.ptr for d in descs])
-        gy = (C.c_float * max(n, 1))(*heights)
         buf = out if out.size else np.zeros(4, out.dtype)  # (no frame: the call checks its arguments and writes nothing)
         f = None if rgba8 else abi.fptr(buf)
         b = buf.ctypes.data_as(C.POINTER(C.c_uint8)) if rgba8 else None
-        if ex is not None:
-            boxes = _empty_bounds(max(n, 1), w, h)
-            check(load().mcrt_render_shot_batch_ex(arr, n, C.byref(c), C.byref(ex), gy, f, b, C.c_void_p(boxes.ctypes.data if bounds else None), int(device)))
-            return (out, boxes[:n]) if bounds else out
-        if o != 0.0:
-            check(load().mcrt_render_shot_batch_occ(arr, n, C.byref(c), C.byref(s), o, gy, f, b, int(device)))
-        else:
-            check(load().mcrt_render_shot_batch(arr, n, C.byref(c), C.byref(s), gy, f, b, int(device)))
-        return out
+        boxes = _empty_bounds(max(n, 1), w, h)
+        ex_args = (C.c_void_p(boxes.ctypes.data if bounds else None),) if variant == "_ex" else ()
+        check(getattr(load(), "mcrt_render_shot_batch" + variant)(_desc_array(descs), n, C.byref(c), *shot_args, _height_array(heights), f, b, *ex_args,
+                                                                  int(device)))
+        return (out, boxes[:n]) if bounds else out
 
     @staticmethod
     def renderLight(scene, config: Config, planes=abi.LIGHT_NAMES, device: int = 0) -> dict:
@@ -439,18 +406,7 @@ class TileRenderer:
         """``renderLight`` for N scenes of one config: the same planes with a leading N.  This host form is a LOOP of
         ``mcrt_render_light`` calls; the batched path is ``render_light_batch_device`` on resident ``DeviceScene`` handles (one
         launch per kernel and 4096 frames)."""
-        names = abi.light_names(planes)
-        descs = [_as_desc(s) for s in scenes]
-        n = len(descs)
-        w, h = max(config.width, 0), max(config.height, 0)
-        out = {k: _empty_light(k, n, h, w) for k in names}
-        if n == 0 or w == 0 or h == 0 or config.tileSize <= 0:
-            return out
-        c = config.to_c()
-        for i, d in enumerate(descs):
-            frame = abi.McrtLightPlanes(**{k: v[i].ctypes.data for k, v in out.items()})
-            check(load().mcrt_render_light(d.ptr, C.byref(c), C.byref(frame), int(device)))
-        return out
+        return _render_pass_loop(abi.LIGHT, scenes, config, planes, device)
 
     @staticmethod
     def bakeLight(scene, config: Config, grid: int = 1, planes=abi.BAKE_NAMES, device: int = 0) -> dict:
@@ -462,11 +418,11 @@ class TileRenderer:
         ``direct`` (n, 4), the mean of ``shade()`` with the view vector along the normal, alpha the texel's (zero for a dead
         texel).  Of ``config`` only softShadows, shadowSamples (at most 113 with softShadows), aoSamples (1 to 113) and aoRadius
         matter.  Failures raise ``McrtError``."""
-        names = abi.bake_names(planes)
+        names = abi.BAKE.select(planes)
         grid = _bake_grid(grid)
         d = _as_desc(scene)
         n = len(texel_table(d))
-        out = {k: _empty_bake(k, n) for k in names}
+        out = {k: abi.BAKE.empty(k, n) for k in names}
         if n == 0:
             return out
         c = config.to_c()
@@ -491,47 +447,36 @@ class TileRenderer:
         return {k: getattr(t, k) for k, _ in abi.McrtTimings._fields_}
 
 
-def _empty_layer(name: str, n: int, h: int, w: int) -> np.ndarray:
-    """One plane for n frames, holding the miss constants (what a frame of zero size keeps)."""
-    dtype, comps = abi.LAYER_FORMATS[name]
-    a = np.zeros((n, h, w) + ((comps,) if comps > 1 else ()), dtype)
-    if name == "depth":
-        a[...] = np.finfo(np.float32).max
-    elif name == "id":
-        a[...] = (-1, 0, -1, -1)
-    return a
+def _render_pass_loop(family: abi.PlaneFamily, scenes, config: Config, planes, device, *ground) -> dict:
+    """The host form of a pass for N scenes: a loop of calls of the family's one-shot entry, frame i into row i of the wanted
+    planes.  ``ground``: the heights argument of a pass that has a floor plane, nothing for one that has none."""
+    names = family.select(planes)
+    descs = [_as_desc(s) for s in scenes]
+    n = len(descs)
+    heights = [_ground_heights(descs, g) for g in ground]
+    w, h, no_frame = _frame(config)
+    out = {k: family.empty(k, n, h, w) for k in names}
+    if n == 0 or no_frame:
+        return out
+    c = config.to_c()
+    entry = getattr(load(), family.entry)
+    for i, d in enumerate(descs):
+        frame = family.struct(**{k: v[i].ctypes.data for k, v in out.items()})
+        check(entry(d.ptr, C.byref(c), *[hs[i] for hs in heights], C.byref(frame), int(device)))
+    return out
 
 
-def _empty_ground(name: str, n: int, h: int, w: int) -> np.ndarray:
-    """One ground plane for n frames, holding the constants of a pixel that misses the plane."""
-    a = np.zeros((n, h, w), abi.GROUND_FORMATS[name])
-    if name == "visibility":
-        a[...] = 1.0
-    elif name == "distance":
-        a[...] = np.finfo(np.float32).max
-    return a
-
-
-def _empty_ground_occlusion(name: str, n: int, h: int, w: int) -> np.ndarray:
-    """One ground-occlusion plane for n frames, holding the constants of a pixel that misses the plane."""
-    a = np.zeros((n, h, w), abi.GROUND_OCCLUSION_FORMATS[name])
-    if name == "occlusion":
-        a[...] = 1.0
-    return a
-
-
-def _shot_c(shot):
-    """(mcrt_shot, floor-occlusion strength) of ``shot`` (``None``: the defaults).  The entries take the ``*_occ`` form of the
-    library whenever the strength is not 0, so the library refuses one that is negative, above 1 or NaN."""
+def _shot_variant(shot, asked: bool = False) -> Tuple[str, tuple]:
+    """Which of the three forms of a shot entry a call takes, as the suffix of its C name, and the arguments that stand for the
+    shot in it (``None``: the defaults).  ``"_ex"`` with (mcrt_shot_ex,) where the call needs it — a transparent page, a shadow
+    colour other than 0, or ``asked`` (bounds or a crop are wanted); otherwise the calls made before ``_ex`` existed are made
+    unchanged: ``"_occ"`` with (mcrt_shot, strength) whenever the floor-occlusion strength is not 0, so the library refuses one
+    that is negative, above 1 or NaN, and ``""`` with (mcrt_shot,)."""
     sh = shot if shot is not None else abi.Shot()
-    return sh.to_c(), float(sh.floorOcclusion)
-
-
-def _shot_ex_c(shot, asked: bool = False):
-    """mcrt_shot_ex of ``shot`` where the call needs the ``_ex`` entries — a transparent page, a shadow colour other than 0, or
-    ``asked`` (bounds or a crop are wanted) — and ``None`` where the calls made before them are made unchanged."""
-    sh = shot if shot is not None else abi.Shot()
-    return sh.to_c_ex() if asked or sh.needs_ex() else None
+    if asked or sh.needs_ex():
+        return "_ex", (sh.to_c_ex(),)
+    s, o = sh.to_c(), float(sh.floorOcclusion)
+    return ("_occ", (s, o)) if o != 0.0 else ("", (s,))
 
 
 def _empty_bounds(n: int, w: int, h: int) -> np.ndarray:
@@ -539,33 +484,6 @@ def _empty_bounds(n: int, w: int, h: int) -> np.ndarray:
     b = np.zeros((n, 4), np.int32)
     b[:, 0], b[:, 1] = w, h
     return b
-
-
-def _empty_reflection(name: str, n: int, h: int, w: int) -> np.ndarray:
-    """One reflection plane for n frames, holding the constants of a pixel without a reflected hit."""
-    dtype, comps = abi.REFLECTION_FORMATS[name]
-    a = np.zeros((n, h, w) + ((comps,) if comps > 1 else ()), dtype)
-    if name == "distance":
-        a[...] = np.finfo(np.float32).max
-    return a
-
-
-def _empty_light(name: str, n: int, h: int, w: int) -> np.ndarray:
-    """One light plane for n frames, holding the constants of a pixel without a hit."""
-    dtype, comps = abi.LIGHT_FORMATS[name]
-    a = np.zeros((n, h, w) + ((comps,) if comps > 1 else ()), dtype)
-    if name != "direct":
-        a[...] = 1.0
-    return a
-
-
-def _empty_bake(name: str, n: int) -> np.ndarray:
-    """One bake plane for n texels, holding the constants of a texel without an owner face."""
-    dtype, comps = abi.BAKE_FORMATS[name]
-    a = np.zeros((n,) + ((comps,) if comps > 1 else ()), dtype)
-    if name in ("visibility", "occlusion"):
-        a[...] = 1.0
-    return a
 
 
 def _bake_grid(grid) -> int:
@@ -604,12 +522,9 @@ def skin_texel(kind, mesh: int, face: int, tx: int, ty: int) -> Tuple[int, int]:
     """(mesh, face slot, tx, ty) of a scene built by ``MeshBuilder.buildScene`` → the skin image's texel ``(x, y)`` that face
     texel was cut from (mcrt_skin_texel).  ``kind``: ``"S64"`` / ``"S32"`` or the skin's height.  Out-of-range arguments raise
     ``ValueError``."""
-    heights = {"S64": 64, "S32": 32, 64: 64, 32: 32}
-    if isinstance(kind, bool) or kind not in heights:
-        raise ValueError("kind must be 'S64', 'S32', 64 or 32")
     x, y = C.c_int(), C.c_int()
     lib = load()
-    if lib.mcrt_skin_texel(heights[kind], int(mesh), int(face) & 7, int(tx), int(ty), C.byref(x), C.byref(y)) != 0:
+    if lib.mcrt_skin_texel(_skin_height(kind), int(mesh), int(face) & 7, int(tx), int(ty), C.byref(x), C.byref(y)) != 0:
         raise ValueError(lib.mcrt_last_error().decode("utf-8", "replace"))
     return int(x.value), int(y.value)
 
@@ -669,16 +584,12 @@ def render_shot_png(scene, config: Config, path: str, shot: Optional[abi.Shot] =
     a PNG, 4 B/pixel copied back.  ``ground=None``: the scene's floor.  False on failure, like ``render_png``.  With
     ``Shot(page="transparent")`` the file carries the cut-out's alpha, and ``crop=True`` writes its bounds rectangle alone (the
     whole frame where nothing is visible) through mcrt_render_shot_png_ex."""
-    ex = _shot_ex_c(shot, crop)
+    variant, shot_args = _shot_variant(shot, crop)
     d = _as_desc(scene)
     g = _ground_heights([d], ground)[0]
     c = config.to_c()
-    if ex is not None:
-        return load().mcrt_render_shot_png_ex(d.ptr, C.byref(c), C.byref(ex), g, os.fsencode(path), int(bool(crop)), None, int(device)) == 0
-    s, o = _shot_c(shot)
-    if o != 0.0:
-        return load().mcrt_render_shot_png_occ(d.ptr, C.byref(c), C.byref(s), o, g, os.fsencode(path), int(device)) == 0
-    return load().mcrt_render_shot_png(d.ptr, C.byref(c), C.byref(s), g, os.fsencode(path), int(device)) == 0
+    ex_args = (int(bool(crop)), None) if variant == "_ex" else ()
+    return getattr(load(), "mcrt_render_shot_png" + variant)(d.ptr, C.byref(c), *shot_args, g, os.fsencode(path), *ex_args, int(device)) == 0
 
 
 def shot_scratch_bytes(config: Config, shot: Optional[abi.Shot] = None, n_frames: int = 1, bounds: bool = False) -> int:
@@ -688,15 +599,10 @@ def shot_scratch_bytes(config: Config, shot: Optional[abi.Shot] = None, n_frames
     0 for a zero-size frame or ``n_frames <= 0``.  A transparent page, a shadow colour and ``bounds`` change nothing of the size
     (mcrt_shot_scratch_bytes_ex); bounds with an opaque page are refused like an invalid shot: 0."""
     c = config.to_c()
-    ex = _shot_ex_c(shot, bounds)
-    if ex is not None:
-        if bounds and ex.shot.page != abi.PAGE_TRANSPARENT:
-            return 0
-        return int(load().mcrt_shot_scratch_bytes_ex(C.byref(c), C.byref(ex), int(n_frames)))
-    s, o = _shot_c(shot)
-    if o != 0.0:
-        return int(load().mcrt_shot_scratch_bytes_occ(C.byref(c), C.byref(s), o, int(n_frames)))
-    return int(load().mcrt_shot_scratch_bytes(C.byref(c), C.byref(s), int(n_frames)))
+    variant, shot_args = _shot_variant(shot, bounds)
+    if bounds and shot_args[0].shot.page != abi.PAGE_TRANSPARENT:
+        return 0
+    return int(getattr(load(), "mcrt_shot_scratch_bytes" + variant)(C.byref(c), *shot_args, int(n_frames)))
 
 
 SKIN_HEIGHTS = {"S64": 64, "S32": 32, 64: 64, 32: 32}
@@ -829,9 +735,7 @@ class DeviceScene:
         self._h = C.c_void_p()
         self.device = device
         self.skin_height = h
-        p = np.ascontiguousarray(pose, np.float32) if pose is not None else None
-        if p is not None and p.shape != (12,):
-            raise ValueError("pose must hold 12 floats")
+        p = _view_pose(pose)
         check(load().mcrt_scene_create_skin(h, abi.fptr(p) if p is not None else None, self._desc.ptr if self._desc is not None else None,
                                             int(device), C.byref(self._h)))
         return self
@@ -934,16 +838,18 @@ class DeviceScene:
                                              C.c_void_p(stream), iters, C.byref(a)))
         return float(a.value)
 
+    def _pass_device(self, family: abi.PlaneFamily, config: Config, planes, stream: int, *middle) -> None:
+        """One pass of ``family`` into the device planes (``_device_planes``) through its ``_device`` entry.  ``middle``: what
+        the entry takes between the config and the planes — a ground height, a bake's grid."""
+        c = config.to_c()
+        check(getattr(load(), family.entry + "_device")(self._h, C.byref(c), *middle, C.byref(planes), C.c_void_p(stream)))
+
     def render_layers_device(self, config: Config, depth_ptr: int = 0, normal_ptr: int = 0, albedo_ptr: int = 0, id_ptr: int = 0,
                              stream: int = 0) -> None:
         """The geometry layers of the frame into device memory (mcrt_render_layers_device): width * height pixels per plane —
         depth 4 bytes per pixel, normal, albedo and id 16 — any pointer may be 0, not all.  Asynchronous on ``stream``;
         uses none of the handle's workspace, so it may run beside a render of the handle on another stream."""
-        if not (depth_ptr or normal_ptr or albedo_ptr or id_ptr):
-            raise ValueError("give at least one of depth_ptr, normal_ptr, albedo_ptr, id_ptr")
-        c = config.to_c()
-        planes = abi.McrtLayers(depth_ptr or None, normal_ptr or None, albedo_ptr or None, id_ptr or None)
-        check(load().mcrt_render_layers_device(self._h, C.byref(c), C.byref(planes), C.c_void_p(stream)))
+        self._pass_device(abi.LAYERS, config, _device_planes(abi.LAYERS, depth_ptr, normal_ptr, albedo_ptr, id_ptr), stream)
 
     def render_ground_device(self, config: Config, ground: float, visibility_ptr: int = 0, distance_ptr: int = 0, matte_ptr: int = 0,
                              stream: int = 0) -> None:
@@ -951,26 +857,14 @@ class DeviceScene:
         — visibility and distance 4 bytes per pixel, matte 1 — any pointer may be 0, not all.  ``ground``: the plane's height
         (``scene_floor`` of the description for the figure's own floor).  Asynchronous on ``stream``; uses none of the handle's
         workspace, so it may run beside a render of the handle on another stream."""
-        if not (visibility_ptr or distance_ptr or matte_ptr):
-            raise ValueError("give at least one of visibility_ptr, distance_ptr, matte_ptr")
-        if not np.isfinite(np.float32(ground)):
-            raise ValueError("ground must be finite")
-        c = config.to_c()
-        planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
-        check(load().mcrt_render_ground_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
+        self._pass_device(abi.GROUND, config, _device_planes(abi.GROUND, visibility_ptr, distance_ptr, matte_ptr), stream, _finite_ground(ground))
 
     def render_ground_occlusion_device(self, config: Config, ground: float, occlusion_ptr: int = 0, matte_ptr: int = 0, stream: int = 0) -> None:
         """The ground-occlusion planes of the frame into device memory (mcrt_render_ground_occlusion_device): width * height
         pixels per plane — occlusion 4 bytes per pixel, matte 1 — either pointer may be 0, not both.  ``ground``: the plane's
         height.  Asynchronous on ``stream``; uses none of the handle's workspace, so it may run beside a render of the handle on
         another stream."""
-        if not (occlusion_ptr or matte_ptr):
-            raise ValueError("give at least one of occlusion_ptr, matte_ptr")
-        if not np.isfinite(np.float32(ground)):
-            raise ValueError("ground must be finite")
-        c = config.to_c()
-        planes = abi.McrtGroundOcclusion(occlusion_ptr or None, matte_ptr or None)
-        check(load().mcrt_render_ground_occlusion_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
+        self._pass_device(abi.GROUND_OCCLUSION, config, _device_planes(abi.GROUND_OCCLUSION, occlusion_ptr, matte_ptr), stream, _finite_ground(ground))
 
     def render_reflection_device(self, config: Config, ground: float, rgba_ptr: int = 0, rgba8_ptr: int = 0, distance_ptr: int = 0,
                                  stream: int = 0) -> None:
@@ -978,13 +872,7 @@ class DeviceScene:
         per plane — rgba 16 bytes per pixel, rgba8 and distance 4 — any pointer may be 0, not all.  ``ground``: the plane's
         height.  Asynchronous on ``stream``; uses none of the handle's workspace, so it may run beside a render of the handle on
         another stream."""
-        if not (rgba_ptr or rgba8_ptr or distance_ptr):
-            raise ValueError("give at least one of rgba_ptr, rgba8_ptr, distance_ptr")
-        if not np.isfinite(np.float32(ground)):
-            raise ValueError("ground must be finite")
-        c = config.to_c()
-        planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
-        check(load().mcrt_render_reflection_device(self._h, C.byref(c), float(ground), C.byref(planes), C.c_void_p(stream)))
+        self._pass_device(abi.REFLECTION, config, _device_planes(abi.REFLECTION, rgba_ptr, rgba8_ptr, distance_ptr), stream, _finite_ground(ground))
 
     def render_shot_device(self, config: Config, shot: Optional[abi.Shot], ground: float, scratch_ptr: int, scratch_bytes: int,
                            out_f32_ptr: int = 0, out_rgba8_ptr: int = 0, stream: int = 0, bounds_ptr: int = 0) -> None:
@@ -992,35 +880,21 @@ class DeviceScene:
         blend, in order on ``stream``, the intermediate planes in the caller's scratch (``shot_scratch_bytes`` bytes, 16-byte
         aligned).  The figure is rendered transparent whatever ``set_background`` says; the handle's mode is untouched.
         ``bounds_ptr``: device memory for 4 int32, the cut-out's box (transparent page only; 0: none)."""
-        if not out_f32_ptr and not out_rgba8_ptr:
-            raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
-        if not np.isfinite(np.float32(ground)):
-            raise ValueError("ground must be finite")
-        ex = _shot_ex_c(shot, bool(bounds_ptr))
-        if ex is not None:
-            render_shot_batch_device([self], config, shot, float(ground), scratch_ptr, scratch_bytes, out_f32_ptr, out_rgba8_ptr, None, stream, bounds_ptr)
+        _need_output(out_f32_ptr, out_rgba8_ptr)
+        g = _finite_ground(ground)
+        variant, shot_args = _shot_variant(shot, bool(bounds_ptr))
+        if variant:  # the batch entries with one handle: there is no single-handle _occ or _ex entry
+            render_shot_batch_device([self], config, shot, g, scratch_ptr, scratch_bytes, out_f32_ptr, out_rgba8_ptr, None, stream, bounds_ptr)
             return
-        s, o = _shot_c(shot)
         c = config.to_c()
-        if o != 0.0:  # the floor-occlusion term: the batch entry with one handle
-            px = max(config.width, 0) * max(config.height, 0)
-            arr = (C.c_void_p * 1)(self._h.value)
-            gy = (C.c_float * 1)(float(ground))
-            check(load().mcrt_render_shot_batch_device_occ(arr, 1, C.byref(c), C.byref(s), o, gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
-                                                           C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), px, C.c_void_p(stream)))
-            return
-        check(load().mcrt_render_shot_device(self._h, C.byref(c), C.byref(s), float(ground), C.c_void_p(scratch_ptr or None), int(scratch_bytes),
+        check(load().mcrt_render_shot_device(self._h, C.byref(c), *shot_args, g, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
                                              C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), C.c_void_p(stream)))
 
     def render_light_device(self, config: Config, visibility_ptr: int = 0, occlusion_ptr: int = 0, direct_ptr: int = 0, stream: int = 0) -> None:
         """The light planes of the frame into device memory (mcrt_render_light_device): width * height pixels per plane —
         visibility and occlusion 4 bytes per pixel, direct 16 — any pointer may be 0, not all.  Asynchronous on ``stream``; uses
         none of the handle's workspace, so it may run beside a render of the handle on another stream."""
-        if not (visibility_ptr or occlusion_ptr or direct_ptr):
-            raise ValueError("give at least one of visibility_ptr, occlusion_ptr, direct_ptr")
-        c = config.to_c()
-        planes = abi.McrtLightPlanes(visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
-        check(load().mcrt_render_light_device(self._h, C.byref(c), C.byref(planes), C.c_void_p(stream)))
+        self._pass_device(abi.LIGHT, config, _device_planes(abi.LIGHT, visibility_ptr, occlusion_ptr, direct_ptr), stream)
 
     @property
     def texels(self) -> int:
@@ -1035,11 +909,7 @@ class DeviceScene:
         visibility and occlusion 4 bytes per texel, position, normal and direct 16 — any pointer may be 0, not all.
         Asynchronous on ``stream``; uses none of the handle's workspace, so it may run beside a render of the handle on another
         stream.  Ordering against a repaint of the handle is the caller's job."""
-        if not (position_ptr or normal_ptr or visibility_ptr or occlusion_ptr or direct_ptr):
-            raise ValueError("give at least one of position_ptr, normal_ptr, visibility_ptr, occlusion_ptr, direct_ptr")
-        c = config.to_c()
-        planes = abi.McrtBakePlanes(position_ptr or None, normal_ptr or None, visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
-        check(load().mcrt_bake_light_device(self._h, C.byref(c), _bake_grid(grid), C.byref(planes), C.c_void_p(stream)))
+        self._pass_device(abi.BAKE, config, _device_planes(abi.BAKE, position_ptr, normal_ptr, visibility_ptr, occlusion_ptr, direct_ptr), stream, _bake_grid(grid))
 
     def pick(self, config: Config, xy) -> np.ndarray:
         """What is under the pixels ``xy`` ((n, 2) integers, x then y, inside the frame): a structured array of
@@ -1078,21 +948,11 @@ def render_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, 
     """N frames of one config from resident scenes into device memory, one launch sequence (mcrt_render_batch_device).
     Frame i is written at ``out_f32_ptr + i * frame_stride_pixels * 16`` bytes and/or ``out_rgba8_ptr + i *
     frame_stride_pixels * 4``; ``frame_stride_pixels`` defaults to width * height.  Asynchronous on ``stream``."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
-    if not out_f32_ptr and not out_rgba8_ptr:
-        raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
-    px = max(config.width, 0) * max(config.height, 0)
-    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
-    if stride < px:
-        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    handles = _handles(device_scenes)
+    _need_output(out_f32_ptr, out_rgba8_ptr)
+    stride = _frame_stride(config, frame_stride_pixels)
     c = config.to_c()
-    check(load().mcrt_render_batch_device(arr, n, C.byref(c), C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None),
+    check(load().mcrt_render_batch_device(_handle_array(handles), len(handles), C.byref(c), C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None),
                                           stride, C.c_void_p(stream)))
 
 
@@ -1100,22 +960,7 @@ def render_layers_batch_device(device_scenes: Sequence["DeviceScene"], config: C
                                albedo_ptr: int = 0, id_ptr: int = 0, frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
     """The geometry layers of N resident scenes of one config in one launch (mcrt_render_layers_batch_device): frame i of
     each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  Asynchronous on ``stream``."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
-    if not (depth_ptr or normal_ptr or albedo_ptr or id_ptr):
-        raise ValueError("give at least one of depth_ptr, normal_ptr, albedo_ptr, id_ptr")
-    px = max(config.width, 0) * max(config.height, 0)
-    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
-    if stride < px:
-        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
-    c = config.to_c()
-    planes = abi.McrtLayers(depth_ptr or None, normal_ptr or None, albedo_ptr or None, id_ptr or None)
-    check(load().mcrt_render_layers_batch_device(arr, n, C.byref(c), C.byref(planes), stride, C.c_void_p(stream)))
+    _pass_batch_device(abi.LAYERS, device_scenes, config, (depth_ptr, normal_ptr, albedo_ptr, id_ptr), frame_stride_pixels, stream)
 
 
 def render_ground_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, ground, visibility_ptr: int = 0, distance_ptr: int = 0,
@@ -1123,26 +968,7 @@ def render_ground_batch_device(device_scenes: Sequence["DeviceScene"], config: C
     """The ground-shadow planes of N resident scenes of one config in one launch (mcrt_render_ground_batch_device): frame i of
     each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  ``ground``: one height for all, or N
     heights (a handle may be listed more than once, with different heights).  Asynchronous on ``stream``."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
-    if not (visibility_ptr or distance_ptr or matte_ptr):
-        raise ValueError("give at least one of visibility_ptr, distance_ptr, matte_ptr")
-    if ground is None:
-        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
-    heights = _ground_heights(handles, ground)
-    px = max(config.width, 0) * max(config.height, 0)
-    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
-    if stride < px:
-        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
-    gy = (C.c_float * max(n, 1))(*heights)
-    c = config.to_c()
-    planes = abi.McrtGround(visibility_ptr or None, distance_ptr or None, matte_ptr or None)
-    check(load().mcrt_render_ground_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+    _pass_batch_device(abi.GROUND, device_scenes, config, (visibility_ptr, distance_ptr, matte_ptr), frame_stride_pixels, stream, ground)
 
 
 def render_ground_occlusion_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, ground, occlusion_ptr: int = 0, matte_ptr: int = 0,
@@ -1150,22 +976,7 @@ def render_ground_occlusion_batch_device(device_scenes: Sequence["DeviceScene"],
     """The ground-occlusion planes of N resident scenes of one config in one launch (mcrt_render_ground_occlusion_batch_device):
     frame i of each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  ``ground``: one height for
     all, or N heights (a handle may be listed more than once, with different heights).  Asynchronous on ``stream``."""
-    handles = _shot_handles(device_scenes)
-    if not (occlusion_ptr or matte_ptr):
-        raise ValueError("give at least one of occlusion_ptr, matte_ptr")
-    if ground is None:
-        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
-    heights = _ground_heights(handles, ground)
-    px = max(config.width, 0) * max(config.height, 0)
-    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
-    if stride < px:
-        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
-    gy = (C.c_float * max(n, 1))(*heights)
-    c = config.to_c()
-    planes = abi.McrtGroundOcclusion(occlusion_ptr or None, matte_ptr or None)
-    check(load().mcrt_render_ground_occlusion_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+    _pass_batch_device(abi.GROUND_OCCLUSION, device_scenes, config, (occlusion_ptr, matte_ptr), frame_stride_pixels, stream, ground)
 
 
 def render_reflection_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, ground, rgba_ptr: int = 0, rgba8_ptr: int = 0,
@@ -1173,35 +984,70 @@ def render_reflection_batch_device(device_scenes: Sequence["DeviceScene"], confi
     """The ground-reflection planes of N resident scenes of one config in one launch (mcrt_render_reflection_batch_device): frame
     i of each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  ``ground``: one height for all, or N
     heights (a handle may be listed more than once, with different heights).  Asynchronous on ``stream``."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
-    if not (rgba_ptr or rgba8_ptr or distance_ptr):
-        raise ValueError("give at least one of rgba_ptr, rgba8_ptr, distance_ptr")
-    if ground is None:
-        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
-    heights = _ground_heights(handles, ground)
-    px = max(config.width, 0) * max(config.height, 0)
-    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
-    if stride < px:
-        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
-    gy = (C.c_float * max(n, 1))(*heights)
-    c = config.to_c()
-    planes = abi.McrtReflection(rgba_ptr or None, rgba8_ptr or None, distance_ptr or None)
-    check(load().mcrt_render_reflection_batch_device(arr, n, C.byref(c), gy, C.byref(planes), stride, C.c_void_p(stream)))
+    _pass_batch_device(abi.REFLECTION, device_scenes, config, (rgba_ptr, rgba8_ptr, distance_ptr), frame_stride_pixels, stream, ground)
 
 
-def _shot_handles(device_scenes) -> list:
+def _handles(device_scenes) -> list:
     handles = []
     for s in device_scenes:
         if not isinstance(s, DeviceScene):
             raise TypeError("device_scenes must be DeviceScene objects")
         handles.append(s._h)
     return handles
+
+
+def _handle_array(handles):
+    return (C.c_void_p * max(len(handles), 1))(*[h.value for h in handles])
+
+
+def _height_array(heights):
+    return (C.c_float * max(len(heights), 1))(*heights)
+
+
+def _need_output(out_f32_ptr: int, out_rgba8_ptr: int) -> None:
+    if not out_f32_ptr and not out_rgba8_ptr:
+        raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
+
+
+def _device_planes(family: abi.PlaneFamily, *ptrs: int):
+    """The family's structure of device pointers, one per plane in the family's order, 0 = not wanted; all 0 raises."""
+    if not any(ptrs):
+        raise ValueError("give at least one of " + ", ".join(f"{k}_ptr" for k in family.names))
+    return family.struct(*[p or None for p in ptrs])
+
+
+def _finite_ground(ground) -> float:
+    if not np.isfinite(np.float32(ground)):
+        raise ValueError("ground must be finite")
+    return float(ground)
+
+
+def _resident_heights(handles, ground) -> List[float]:
+    """``_ground_heights`` for resident scenes, which have no floor of their own to fall back to."""
+    if ground is None:
+        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
+    return _ground_heights(handles, ground)
+
+
+def _frame_stride(config: Config, value: Optional[int], name: str = "frame_stride_pixels") -> int:
+    """The stride between the frames of a batch, in pixels: ``value``, or width * height for ``None``; never less than that."""
+    px = max(config.width, 0) * max(config.height, 0)
+    stride = px if value is None else int(value)
+    if stride < px:
+        raise ValueError(f"{name} {stride} is smaller than width * height = {px}")
+    return stride
+
+
+def _pass_batch_device(family: abi.PlaneFamily, device_scenes, config: Config, ptrs, frame_stride_pixels, stream: int, *ground) -> None:
+    """One pass of ``family`` for N resident scenes through its ``_batch_device`` entry.  ``ptrs``: one device pointer per plane in
+    the family's order; ``ground``: the heights argument of a pass that has a floor plane, nothing for one that has none."""
+    handles = _handles(device_scenes)
+    planes = _device_planes(family, *ptrs)
+    heights = [_height_array(_resident_heights(handles, g)) for g in ground]
+    stride = _frame_stride(config, frame_stride_pixels)
+    c = config.to_c()
+    check(getattr(load(), family.entry + "_batch_device")(_handle_array(handles), len(handles), C.byref(c), *heights, C.byref(planes), stride,
+                                                          C.c_void_p(stream)))
 
 
 def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, shot: Optional[abi.Shot], ground, scratch_ptr: int,
@@ -1215,33 +1061,16 @@ def render_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Con
     (mcrt_render_shot_batch_device_occ).  ``bounds_ptr``: device memory for N x 4 int32, the cut-outs' boxes, valid in stream
     order behind the call (transparent page only; 0: none).  A transparent page, a shadow colour or bounds take
     mcrt_render_shot_batch_device_ex."""
-    handles = _shot_handles(device_scenes)
-    if not out_f32_ptr and not out_rgba8_ptr:
-        raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
-    if ground is None:
-        raise ValueError("ground heights are needed: a resident scene does not keep its description (see scene_floor)")
-    heights = _ground_heights(handles, ground)
-    px = max(config.width, 0) * max(config.height, 0)
-    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
-    if stride < px:
-        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    ex = _shot_ex_c(shot, bool(bounds_ptr))
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
-    gy = (C.c_float * max(n, 1))(*heights)
+    handles = _handles(device_scenes)
+    _need_output(out_f32_ptr, out_rgba8_ptr)
+    heights = _resident_heights(handles, ground)
+    stride = _frame_stride(config, frame_stride_pixels)
+    variant, shot_args = _shot_variant(shot, bool(bounds_ptr))
     c = config.to_c()
-    if ex is not None:
-        check(load().mcrt_render_shot_batch_device_ex(arr, n, C.byref(c), C.byref(ex), gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
-                                                      C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride,
-                                                      C.c_void_p(bounds_ptr or None), C.c_void_p(stream)))
-        return
-    s, o = _shot_c(shot)
-    if o != 0.0:
-        check(load().mcrt_render_shot_batch_device_occ(arr, n, C.byref(c), C.byref(s), o, gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
-                                                       C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride, C.c_void_p(stream)))
-        return
-    check(load().mcrt_render_shot_batch_device(arr, n, C.byref(c), C.byref(s), gy, C.c_void_p(scratch_ptr or None), int(scratch_bytes),
-                                               C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride, C.c_void_p(stream)))
+    ex_args = (C.c_void_p(bounds_ptr or None),) if variant == "_ex" else ()
+    check(getattr(load(), "mcrt_render_shot_batch_device" + variant)(
+        _handle_array(handles), len(handles), C.byref(c), *shot_args, _height_array(heights), C.c_void_p(scratch_ptr or None), int(scratch_bytes),
+        C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), stride, *ex_args, C.c_void_p(stream)))
 
 
 def composite_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, shot: Optional[abi.Shot], figure_ptr: int,
@@ -1255,35 +1084,21 @@ def composite_shot_batch_device(device_scenes: Sequence["DeviceScene"], config: 
     ``shot.floorOcclusion`` > 0 the blend takes the ground-occlusion pass's plane at ``occlusion_ptr`` (4 B/pixel; 0: none)
     through mcrt_composite_shot_batch_device_occ.  ``bounds_ptr``: as for ``render_shot_batch_device``; a transparent page, a
     shadow colour or bounds take mcrt_composite_shot_batch_device_ex."""
-    handles = _shot_handles(device_scenes)
+    handles = _handles(device_scenes)
     if not figure_ptr:
         raise ValueError("figure_ptr is required")
-    if not out_f32_ptr and not out_rgba8_ptr:
-        raise ValueError("give out_f32_ptr and/or out_rgba8_ptr")
-    px = max(config.width, 0) * max(config.height, 0)
-    strides = []
-    for name, value in (("in_stride_pixels", in_stride_pixels), ("out_stride_pixels", out_stride_pixels)):
-        stride = px if value is None else int(value)
-        if stride < px:
-            raise ValueError(f"{name} {stride} is smaller than width * height = {px}")
-        strides.append(stride)
-    ex = _shot_ex_c(shot, bool(bounds_ptr))
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    _need_output(out_f32_ptr, out_rgba8_ptr)
+    in_stride = _frame_stride(config, in_stride_pixels, "in_stride_pixels")
+    out_stride = _frame_stride(config, out_stride_pixels, "out_stride_pixels")
+    variant, shot_args = _shot_variant(shot, bool(bounds_ptr))
     c = config.to_c()
     planes = abi.McrtShotInputs(figure_ptr, visibility_ptr or None, reflection_ptr or None, reflection_distance_ptr or None)
-    if ex is not None:
-        check(load().mcrt_composite_shot_batch_device_ex(arr, n, C.byref(c), C.byref(ex), C.byref(planes), C.c_void_p(occlusion_ptr or None), strides[0],
-                                                         C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), strides[1],
-                                                         C.c_void_p(bounds_ptr or None), C.c_void_p(stream)))
-        return
-    s, o = _shot_c(shot)
-    if o != 0.0:
-        check(load().mcrt_composite_shot_batch_device_occ(arr, n, C.byref(c), C.byref(s), C.byref(planes), C.c_void_p(occlusion_ptr or None), o, strides[0],
-                                                          C.c_void_p(out_f32_ptr or None), C.c_void_p(out_rgba8_ptr or None), strides[1], C.c_void_p(stream)))
-        return
-    check(load().mcrt_composite_shot_batch_device(arr, n, C.byref(c), C.byref(s), C.byref(planes), strides[0], C.c_void_p(out_f32_ptr or None),
-                                                  C.c_void_p(out_rgba8_ptr or None), strides[1], C.c_void_p(stream)))
+    shot_c, *strength = shot_args  # (here the _occ form takes its strength behind the occlusion plane, not behind the shot)
+    occ_args = (C.c_void_p(occlusion_ptr or None), *strength) if variant else ()
+    ex_args = (C.c_void_p(bounds_ptr or None),) if variant == "_ex" else ()
+    check(getattr(load(), "mcrt_composite_shot_batch_device" + variant)(
+        _handle_array(handles), len(handles), C.byref(c), shot_c, C.byref(planes), *occ_args, in_stride, C.c_void_p(out_f32_ptr or None),
+        C.c_void_p(out_rgba8_ptr or None), out_stride, *ex_args, C.c_void_p(stream)))
 
 
 def render_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, visibility_ptr: int = 0, occlusion_ptr: int = 0,
@@ -1291,22 +1106,7 @@ def render_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Co
     """The light planes of N resident scenes of one config in one launch per kernel (mcrt_render_light_batch_device): frame i of
     each plane starts ``i * frame_stride_pixels`` pixels on (default width * height).  A handle may be listed more than once.
     Asynchronous on ``stream``."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
-    if not (visibility_ptr or occlusion_ptr or direct_ptr):
-        raise ValueError("give at least one of visibility_ptr, occlusion_ptr, direct_ptr")
-    px = max(config.width, 0) * max(config.height, 0)
-    stride = px if frame_stride_pixels is None else int(frame_stride_pixels)
-    if stride < px:
-        raise ValueError(f"frame_stride_pixels {stride} is smaller than width * height = {px}")
-    n = len(handles)
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
-    c = config.to_c()
-    planes = abi.McrtLightPlanes(visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
-    check(load().mcrt_render_light_batch_device(arr, n, C.byref(c), C.byref(planes), stride, C.c_void_p(stream)))
+    _pass_batch_device(abi.LIGHT, device_scenes, config, (visibility_ptr, occlusion_ptr, direct_ptr), frame_stride_pixels, stream)
 
 
 def bake_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, grid: int = 1, position_ptr: int = 0, normal_ptr: int = 0,
@@ -1315,37 +1115,25 @@ def bake_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Conf
     """The light bakes of N resident scenes in one launch per kernel (mcrt_bake_light_batch_device): frame i of each plane starts
     ``i * texel_stride`` texels on (default: the largest ``texels`` of the scenes, which may differ).  A handle may be listed more
     than once.  Asynchronous on ``stream``."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
-    if not (position_ptr or normal_ptr or visibility_ptr or occlusion_ptr or direct_ptr):
-        raise ValueError("give at least one of position_ptr, normal_ptr, visibility_ptr, occlusion_ptr, direct_ptr")
+    handles = _handles(device_scenes)
+    planes = _device_planes(abi.BAKE, position_ptr, normal_ptr, visibility_ptr, occlusion_ptr, direct_ptr)
     g = _bake_grid(grid)
-    n = len(handles)
     if texel_stride is None:
         texel_stride = max([s.texels for s in device_scenes], default=0)
     if int(texel_stride) < 0:
         raise ValueError("texel_stride must be >= 0")
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
     c = config.to_c()
-    planes = abi.McrtBakePlanes(position_ptr or None, normal_ptr or None, visibility_ptr or None, occlusion_ptr or None, direct_ptr or None)
-    check(load().mcrt_bake_light_batch_device(arr, n, C.byref(c), g, C.byref(planes), int(texel_stride), C.c_void_p(stream)))
+    check(load().mcrt_bake_light_batch_device(_handle_array(handles), len(handles), C.byref(c), g, C.byref(planes), int(texel_stride), C.c_void_p(stream)))
 
 
 def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, skin_stride_bytes: Optional[int] = None, stream: int = 0) -> None:
     """One launch repaints N repaintable scenes of one skin kind (mcrt_scene_set_skins_batch_device): skin i is the RGBA8 image
     at ``ptr + i * skin_stride_bytes`` in device memory (default: the image size, 64 * height * 4).  Asynchronous on ``stream``."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
+    handles = _handles(device_scenes)
     n = len(handles)
     if skin_stride_bytes is None:
         skin_stride_bytes = device_scenes[0]._skin_bytes() if n else 64 * 64 * 4
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    arr = _handle_array(handles)
     check(load().mcrt_scene_set_skins_batch_device(arr, n, C.c_void_p(ptr or None), int(skin_stride_bytes), C.c_void_p(stream)))
 
 
@@ -1354,11 +1142,7 @@ def set_views_batch_device(device_scenes: Sequence["DeviceScene"], poses=None, l
     poses of 12 floats, or ``None``: every scene keeps its own; ``looks`` — N entries, each a ``Scene`` / ``SceneDesc`` or
     ``None`` (that scene keeps its look), or ``None`` for all.  Asynchronous on ``stream``; the arguments are read before the
     call returns."""
-    handles = []
-    for s in device_scenes:
-        if not isinstance(s, DeviceScene):
-            raise TypeError("device_scenes must be DeviceScene objects")
-        handles.append(s._h)
+    handles = _handles(device_scenes)
     n = len(handles)
     p = None
     if poses is not None:
@@ -1371,7 +1155,7 @@ def set_views_batch_device(device_scenes: Sequence["DeviceScene"], poses=None, l
         if len(looks) != n:
             raise ValueError(f"looks must hold {n} entries: one look (or None) per scene")
         descs = [_as_desc(k) if k is not None else None for k in looks]
-    arr = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    arr = _handle_array(handles)
     look_arr = None
     if descs is not None:
         ptrs = [d.ptr if d is not None else None for d in descs]  # (kept alive until the call has returned)
@@ -1467,18 +1251,15 @@ class SkinBatch:
         """``skins``: (m <= n, H, 64, 4) uint8.  Returns (m, height, width, 4) float32, or uint8 with ``rgba8``."""
         torch = self._torch
         mode = abi.background_mode(background)
-        w, h = max(config.width, 0), max(config.height, 0)
+        w, h, no_frame = _frame(config)
         with torch.cuda.device(self._dev):
             stream = torch.cuda.current_stream()
-            if w == 0 or h == 0 or config.tileSize <= 0:  # no frame: nothing is painted either (the staging buffer stays idle)
-                m = len(self._check_skins(skins))
-                out = np.zeros((m, h, w, 4), np.uint8 if rgba8 else np.float32)
-                out[..., 3] = 255 if rgba8 else 1.0
-                return out
+            if no_frame:  # nothing is painted either (the staging buffer stays idle)
+                return _default_frames(len(self._check_skins(skins)), h, w, rgba8)
             m = self._paint(skins, stream)
             dtype = torch.uint8 if rgba8 else torch.float32
             if m == 0:
-                return np.zeros((0, h, w, 4), np.uint8 if rgba8 else np.float32)
+                return _default_frames(0, h, w, rgba8)
             if mode != self._mode:
                 for s in self.scenes:
                     s.set_background(background)
@@ -1498,13 +1279,11 @@ class SkinBatch:
         (``Shot(page="transparent")`` only): the pair (images, (m, 4) int32 boxes {x0, y0, x1, y1}), the boxes written by the
         blend and downloaded with the images."""
         torch = self._torch
-        w, h = max(config.width, 0), max(config.height, 0)
-        np_dtype = np.uint8 if rgba8 else np.float32
+        w, h, no_frame = _frame(config)
         with torch.cuda.device(self._dev):
             stream = torch.cuda.current_stream()
-            if w == 0 or h == 0 or config.tileSize <= 0:  # no frame: nothing is painted either
-                out = np.zeros((len(self._check_skins(skins)), h, w, 4), np_dtype)
-                out[..., 3] = 255 if rgba8 else 1.0
+            if no_frame:  # nothing is painted either
+                out = _default_frames(len(self._check_skins(skins)), h, w, rgba8)
                 return (out, _empty_bounds(len(out), w, h)) if bounds else out
             a = self._check_skins(skins)
             if ground is None:
@@ -1513,7 +1292,7 @@ class SkinBatch:
             need = shot_scratch_bytes(config, shot, len(self.scenes), bounds)  # (raises nothing: an invalid shot is refused by the call below)
             m = self._paint(a, stream)
             if m == 0:
-                none = np.zeros((0, h, w, 4), np_dtype)
+                none = _default_frames(0, h, w, rgba8)
                 return (none, _empty_bounds(0, w, h)) if bounds else none
             scratch = self._out.get("shot_scratch")
             if scratch is None or scratch.numel() < need:
@@ -1536,19 +1315,19 @@ class SkinBatch:
         """The geometry layers of the ``m`` skins' frames (``TileRenderer.renderLayersBatch``'s planes) through
         ``render_layers_batch_device``, behind the repaint on the same stream."""
         torch = self._torch
-        names = abi.layer_names(layers)
-        w, h = max(config.width, 0), max(config.height, 0)
+        names = abi.LAYERS.select(layers)
+        w, h, no_frame = _frame(config)
         with torch.cuda.device(self._dev):
             stream = torch.cuda.current_stream()
-            if w == 0 or h == 0 or config.tileSize <= 0:  # no frame: nothing is painted either
-                return {k: _empty_layer(k, len(self._check_skins(skins)), h, w) for k in names}
+            if no_frame:  # nothing is painted either
+                return {k: abi.LAYERS.empty(k, len(self._check_skins(skins)), h, w) for k in names}
             m = self._paint(skins, stream)
             if m == 0:
-                return {k: _empty_layer(k, 0, h, w) for k in names}
+                return {k: abi.LAYERS.empty(k, 0, h, w) for k in names}
             n = len(self.scenes)
             bufs = {}
             for k in names:
-                dtype, comps = abi.LAYER_FORMATS[k]
+                dtype, comps = abi.LAYERS.formats[k]
                 shape = (n, h, w) + ((comps,) if comps > 1 else ())
                 bufs[k] = self._buffers(k, shape, torch.int32 if dtype is np.int32 else torch.float32)
             render_layers_batch_device(self.scenes[:m], config, frame_stride_pixels=w * h, stream=stream.cuda_stream,
@@ -1567,24 +1346,24 @@ def last_batch_info() -> dict:
     return {"batched_frames": int(f.value), "launch_sequences": int(q.value)}
 
 
-def bg_plate_info(device: int = 0) -> dict:
-    """mcrt_bg_plate_info: ``{"plates": ..., "bytes": ..., "builds": ...}`` — the background plates kept on ``device``, their
-    bytes, and how many were built there since the process began (include/mcrt.h, "Background plates")."""
-    fn = load().mcrt_bg_plate_info  # bound here: a build selected with MCRT_LIB may predate it
+def _plate_info(symbol: str, device: int) -> dict:
+    fn = getattr(load(), symbol)  # bound here: a build selected with MCRT_LIB may predate it
     fn.restype, fn.argtypes = C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     n, b, k = C.c_int(), C.c_size_t(), C.c_int()
     check(fn(int(device), C.byref(n), C.byref(b), C.byref(k)))
     return {"plates": int(n.value), "bytes": int(b.value), "builds": int(k.value)}
+
+
+def bg_plate_info(device: int = 0) -> dict:
+    """mcrt_bg_plate_info: ``{"plates": ..., "bytes": ..., "builds": ...}`` — the background plates kept on ``device``, their
+    bytes, and how many were built there since the process began (include/mcrt.h, "Background plates")."""
+    return _plate_info("mcrt_bg_plate_info", device)
 
 
 def draw_plate_info(device: int = 0) -> dict:
     """mcrt_draw_plate_info: ``{"plates": ..., "bytes": ..., "builds": ...}`` — the draw plates kept on ``device``, their
     bytes, and how many were built there since the process began (include/mcrt.h, "Draw plates")."""
-    fn = load().mcrt_draw_plate_info  # bound here: a build selected with MCRT_LIB may predate it
-    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
-    n, b, k = C.c_int(), C.c_size_t(), C.c_int()
-    check(fn(int(device), C.byref(n), C.byref(b), C.byref(k)))
-    return {"plates": int(n.value), "bytes": int(b.value), "builds": int(k.value)}
+    return _plate_info("mcrt_draw_plate_info", device)
 
 
 def unpack_rows_device(config: Config, first: int, step: int, packed_ptr: int, frame_ptr: int, stream: int = 0) -> None:

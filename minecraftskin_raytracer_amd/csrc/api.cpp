@@ -332,6 +332,8 @@ int one_shot_streams(mcrt_scene* s) {
     return MCRT_OK;
 }
 
+size_t frame_pixels(const mcrt_config* c) { return static_cast<size_t>(c->width) * static_cast<size_t>(c->height); }
+
 // pixel rows of tile row r of the frame
 int tile_row_height(const mcrt_config& c, int r) { return std::min(c.tile_size, c.height - r * c.tile_size); }
 
@@ -632,20 +634,30 @@ int render_png_impl(const mcrt_scene_desc* desc, const mcrt_config* cfg, const c
     return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
 }
 
-// bytes per pixel of the planes wanted, and the planes laid out one after the other in `base` for n_pixels pixels
-size_t layers_planes(const mcrt_layers& want, char* base, size_t n_pixels, mcrt_layers& at) {
+// One output plane of a host form: where the caller wants it (NULL: not wanted), the bytes of one element, and the pointer
+// that takes its device address — a member of the struct the device form is given, of the host pointer's type (the constructor
+// holds the two types together; the address goes in and out as a pointer's bytes, whatever it points to).
+struct Plane {
+    void* host;
+    size_t elem_bytes;
+    void* slot;
+    template <class T>
+    Plane(T* host_plane, size_t bytes, T** device_plane) : host(host_plane), elem_bytes(bytes), slot(device_plane) {}
+};
+
+// The wanted planes of `count` elements each, one after the other from `base`, every one on a 16-byte boundary (the start of
+// a frame buffer is allocation-aligned).  Without a base: the bytes they take, and no slot is written.
+template <size_t N>
+size_t place_planes(const Plane (&planes)[N], size_t count, char* base) {
     size_t off = 0;
-    auto place = [&](bool wanted, size_t px_bytes) -> char* {
-        if (!wanted) return nullptr;
-        char* p = base ? base + off : nullptr;
-        off += n_pixels * px_bytes;
-        return p;
-    };
-    // the 16-byte planes first: every plane then starts on a 16-byte boundary
-    at.normal = reinterpret_cast<float*>(place(want.normal != nullptr, 16));
-    at.albedo = reinterpret_cast<float*>(place(want.albedo != nullptr, 16));
-    at.id = reinterpret_cast<int32_t*>(place(want.id != nullptr, 16));
-    at.depth = reinterpret_cast<float*>(place(want.depth != nullptr, 4));
+    for (const Plane& p : planes) {
+        if (!p.host) continue;
+        if (base) {
+            char* at = base + off;
+            std::memcpy(p.slot, &at, sizeof at);
+        }
+        off += (count * p.elem_bytes + 15) & ~static_cast<size_t>(15);
+    }
     return off;
 }
 
@@ -667,10 +679,17 @@ struct OneShotScenes {
         }
         return one_shot_streams(h[0]) == MCRT_OK ? MCRT_OK : MCRT_ERR_HIP;
     }
-    void download(void* dst, const void* src, size_t bytes, int& rc) {  // on the first shell's stream, unless the call has failed already
-        if (rc != MCRT_OK || !dst) return;
-        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h[0]->main_stream);
-        if (e != hipSuccess) rc = hip_fail(e, "download");
+    // every wanted plane (count elements each, placed by place_planes) to its host address, on the first shell's stream,
+    // unless the call has failed already
+    template <size_t N>
+    void download(const Plane (&planes)[N], size_t count, int& rc) {
+        for (const Plane& p : planes) {
+            if (rc != MCRT_OK || !p.host) continue;
+            const void* src = nullptr;
+            std::memcpy(&src, p.slot, sizeof src);
+            const hipError_t e = hipMemcpyAsync(p.host, src, count * p.elem_bytes, hipMemcpyDeviceToHost, h[0]->main_stream);
+            if (e != hipSuccess) rc = hip_fail(e, "download");
+        }
     }
     void destroy() {
         for (mcrt_scene* s : h)
@@ -682,6 +701,33 @@ struct OneShotScenes {
     OneShotScenes& operator=(const OneShotScenes&) = delete;
     ~OneShotScenes() { destroy(); }
 };
+
+constexpr size_t kPerTexel = 0;  // one_shot_pass's count of a pass over the texels of the scene's pool (the bake), not over pixels
+
+// A one-shot pass form behind its argument checks: the shells of the n descriptions are created, the wanted planes of `count`
+// elements each (kPerTexel: the first scene's texel pool; nothing is written where that is empty) are reserved and placed in the
+// first shell's frame buffer, enqueue(handles, count, stream) makes the *_batch_device call on the struct the planes' slots
+// belong to, every wanted plane is downloaded and the stream synchronised.  what_planes, what_render: hip_fail's texts.
+template <size_t N, class Enqueue>
+int one_shot_pass(const mcrt_scene_desc* const* descs, int n, int device, const Plane (&planes)[N], size_t count, const char* what_planes,
+                  const char* what_render, Enqueue enqueue) {
+    OneShotScenes set;
+    int rc = set.create(descs, n, device, MCRT_BACKGROUND_REFERENCE);
+    if (rc != MCRT_OK) return rc;
+    mcrt_scene* s0 = set.h[0];
+    if (count == kPerTexel) count = static_cast<size_t>(s0->n_texels);
+    if (count == 0) return MCRT_OK;
+    hipError_t e = s0->frame.reserve(place_planes(planes, count, nullptr));
+    if (e != hipSuccess) return hip_fail(e, what_planes);
+    place_planes(planes, count, static_cast<char*>(s0->frame.ptr));
+    rc = enqueue(set.h.data(), count, s0->main_stream);
+    set.download(planes, count, rc);
+    if (rc == MCRT_OK) {
+        e = hipStreamSynchronize(s0->main_stream);
+        if (e != hipSuccess) rc = hip_fail(e, what_render);
+    }
+    return rc;
+}
 
 }  // namespace
 extern "C" {
@@ -794,18 +840,16 @@ int mcrt_render_batch_ex(const mcrt_scene_desc* const* descs, int n_frames, cons
     int rc = set.create(descs, n_frames, device, background);
     if (rc != MCRT_OK) return rc;
     mcrt_scene* s0 = set.h[0];
-    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
-    const size_t f32_bytes = out_rgba ? px * 16 * static_cast<size_t>(n_frames) : 0;
-    const size_t u8_bytes = out_rgba8 ? px * 4 * static_cast<size_t>(n_frames) : 0;
-    hipError_t e = s0->frame.reserve(f32_bytes + u8_bytes);
+    const size_t px = frame_pixels(cfg), total_px = px * static_cast<size_t>(n_frames);
+    float* d_f32 = nullptr;
+    uint8_t* d_u8 = nullptr;
+    const Plane planes[] = {{out_rgba, 16, &d_f32}, {out_rgba8, 4, &d_u8}};
+    hipError_t e = s0->frame.reserve(place_planes(planes, total_px, nullptr));
     if (e != hipSuccess) return hip_fail(e, "frame buffer");
-    char* base = static_cast<char*>(s0->frame.ptr);
-    float* d_f32 = out_rgba ? reinterpret_cast<float*>(base) : nullptr;
-    uint8_t* d_u8 = out_rgba8 ? reinterpret_cast<uint8_t*>(base + f32_bytes) : nullptr;
+    place_planes(planes, total_px, static_cast<char*>(s0->frame.ptr));
     rc = render_batch_device(set.h.data(), n_frames, cfg, d_f32, d_u8, px, s0->main_stream);
     const BatchInfo done = g_batch;
-    set.download(out_rgba, d_f32, f32_bytes, rc);
-    set.download(out_rgba8, d_u8, u8_bytes, rc);
+    set.download(planes, total_px, rc);
     if (rc == MCRT_OK) {
         e = hipStreamSynchronize(s0->main_stream);
         if (e != hipSuccess) rc = hip_fail(e, "batch render");
@@ -829,27 +873,11 @@ int mcrt_render_layers_batch(const mcrt_scene_desc* const* descs, int n_frames, 
         if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
     if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all four planes are NULL");
     if (n_frames == 0 || !valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
-    OneShotScenes set;
-    int rc = set.create(descs, n_frames, device, MCRT_BACKGROUND_REFERENCE);
-    if (rc != MCRT_OK) return rc;
-    mcrt_scene* s0 = set.h[0];
-    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
-    const size_t total_px = px * static_cast<size_t>(n_frames);
+    const size_t px = frame_pixels(cfg);
     mcrt_layers d{};
-    const size_t bytes = layers_planes(*out, nullptr, total_px, d);
-    hipError_t e = s0->frame.reserve(bytes);
-    if (e != hipSuccess) return hip_fail(e, "layer planes");
-    layers_planes(*out, static_cast<char*>(s0->frame.ptr), total_px, d);
-    rc = render_layers_batch_device(set.h.data(), n_frames, cfg, &d, px, s0->main_stream);
-    set.download(out->depth, d.depth, total_px * 4, rc);
-    set.download(out->normal, d.normal, total_px * 16, rc);
-    set.download(out->albedo, d.albedo, total_px * 16, rc);
-    set.download(out->id, d.id, total_px * 16, rc);
-    if (rc == MCRT_OK) {
-        e = hipStreamSynchronize(s0->main_stream);
-        if (e != hipSuccess) rc = hip_fail(e, "layers render");
-    }
-    return rc;
+    const Plane planes[] = {{out->depth, 4, &d.depth}, {out->normal, 16, &d.normal}, {out->albedo, 16, &d.albedo}, {out->id, 16, &d.id}};
+    return one_shot_pass(descs, n_frames, device, planes, px * static_cast<size_t>(n_frames), "layer planes", "layers render",
+                         [&](mcrt_scene* const* h, size_t, hipStream_t stream) { return render_layers_batch_device(h, n_frames, cfg, &d, px, stream); });
 }
 
 int mcrt_render_layers(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_layers* out, int device) {
@@ -866,30 +894,11 @@ int mcrt_render_ground(const mcrt_scene_desc* desc, const mcrt_config* cfg, floa
     if (cfg->soft_shadows && cfg->shadow_samples > kGroundMaxSamples)
         return fail(MCRT_ERR_INVALID, "a ground pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
     if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
-    OneShotScenes set;
-    const mcrt_scene_desc* one[1] = {desc};
-    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
-    if (rc != MCRT_OK) return rc;
-    mcrt_scene* s0 = set.h[0];
-    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
-    // the float planes first: each starts on a 4-byte boundary
-    const size_t vis_bytes = out->visibility ? px * 4 : 0, dist_bytes = out->distance ? px * 4 : 0, matte_bytes = out->matte ? px : 0;
-    hipError_t e = s0->frame.reserve(vis_bytes + dist_bytes + matte_bytes);
-    if (e != hipSuccess) return hip_fail(e, "ground planes");
-    char* base = static_cast<char*>(s0->frame.ptr);
     mcrt_ground d{};
-    d.visibility = out->visibility ? reinterpret_cast<float*>(base) : nullptr;
-    d.distance = out->distance ? reinterpret_cast<float*>(base + vis_bytes) : nullptr;
-    d.matte = out->matte ? reinterpret_cast<uint8_t*>(base + vis_bytes + dist_bytes) : nullptr;
-    rc = render_ground_batch_device(set.h.data(), 1, cfg, &ground_y, &d, px, s0->main_stream);
-    set.download(out->visibility, d.visibility, vis_bytes, rc);
-    set.download(out->distance, d.distance, dist_bytes, rc);
-    set.download(out->matte, d.matte, matte_bytes, rc);
-    if (rc == MCRT_OK) {
-        e = hipStreamSynchronize(s0->main_stream);
-        if (e != hipSuccess) rc = hip_fail(e, "ground render");
-    }
-    return rc;
+    const Plane planes[] = {{out->visibility, 4, &d.visibility}, {out->distance, 4, &d.distance}, {out->matte, 1, &d.matte}};
+    return one_shot_pass(&desc, 1, device, planes, frame_pixels(cfg), "ground planes", "ground render", [&](mcrt_scene* const* h, size_t px, hipStream_t stream) {
+        return render_ground_batch_device(h, 1, cfg, &ground_y, &d, px, stream);
+    });
 }
 
 // ---- ground occlusion: the one-shot host form (render_enqueue.cpp: render_ground_occlusion_batch_device) ------------------------
@@ -899,28 +908,10 @@ int mcrt_render_ground_occlusion(const mcrt_scene_desc* desc, const mcrt_config*
     if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
     if (const int rc = check_ground_occlusion_config(cfg); rc != MCRT_OK) return rc;
     if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
-    OneShotScenes set;
-    const mcrt_scene_desc* one[1] = {desc};
-    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
-    if (rc != MCRT_OK) return rc;
-    mcrt_scene* s0 = set.h[0];
-    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
-    // the float plane first: it starts on a 4-byte boundary
-    const size_t occ_bytes = out->occlusion ? px * 4 : 0, matte_bytes = out->matte ? px : 0;
-    hipError_t e = s0->frame.reserve(occ_bytes + matte_bytes);
-    if (e != hipSuccess) return hip_fail(e, "ground occlusion planes");
-    char* base = static_cast<char*>(s0->frame.ptr);
     mcrt_ground_occlusion d{};
-    d.occlusion = out->occlusion ? reinterpret_cast<float*>(base) : nullptr;
-    d.matte = out->matte ? reinterpret_cast<uint8_t*>(base + occ_bytes) : nullptr;
-    rc = render_ground_occlusion_batch_device(set.h.data(), 1, cfg, &ground_y, &d, px, s0->main_stream);
-    set.download(out->occlusion, d.occlusion, occ_bytes, rc);
-    set.download(out->matte, d.matte, matte_bytes, rc);
-    if (rc == MCRT_OK) {
-        e = hipStreamSynchronize(s0->main_stream);
-        if (e != hipSuccess) rc = hip_fail(e, "ground occlusion render");
-    }
-    return rc;
+    const Plane planes[] = {{out->occlusion, 4, &d.occlusion}, {out->matte, 1, &d.matte}};
+    return one_shot_pass(&desc, 1, device, planes, frame_pixels(cfg), "ground occlusion planes", "ground occlusion render",
+                         [&](mcrt_scene* const* h, size_t px, hipStream_t stream) { return render_ground_occlusion_batch_device(h, 1, cfg, &ground_y, &d, px, stream); });
 }
 
 // ---- ground reflection: the one-shot host form (render_enqueue.cpp: render_reflection_batch_device) -----------------------------
@@ -932,30 +923,11 @@ int mcrt_render_reflection(const mcrt_scene_desc* desc, const mcrt_config* cfg, 
         return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 113 shadow samples (the truncated engine's 227 draws)");
     if (cfg->max_bounces > kReflectMaxBounces) return fail(MCRT_ERR_INVALID, "a reflection pass takes at most 8 bounces (its per-lane colour stack)");
     if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
-    OneShotScenes set;
-    const mcrt_scene_desc* one[1] = {desc};
-    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
-    if (rc != MCRT_OK) return rc;
-    mcrt_scene* s0 = set.h[0];
-    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
-    // the widest elements first: each plane starts on a boundary of its own element size
-    const size_t rgba_bytes = out->rgba ? px * 16 : 0, dist_bytes = out->distance ? px * 4 : 0, u8_bytes = out->rgba8 ? px * 4 : 0;
-    hipError_t e = s0->frame.reserve(rgba_bytes + dist_bytes + u8_bytes);
-    if (e != hipSuccess) return hip_fail(e, "reflection planes");
-    char* base = static_cast<char*>(s0->frame.ptr);
     mcrt_reflection d{};
-    d.rgba = out->rgba ? reinterpret_cast<float*>(base) : nullptr;
-    d.distance = out->distance ? reinterpret_cast<float*>(base + rgba_bytes) : nullptr;
-    d.rgba8 = out->rgba8 ? reinterpret_cast<uint8_t*>(base + rgba_bytes + dist_bytes) : nullptr;
-    rc = render_reflection_batch_device(set.h.data(), 1, cfg, &ground_y, &d, px, s0->main_stream);
-    set.download(out->rgba, d.rgba, rgba_bytes, rc);
-    set.download(out->distance, d.distance, dist_bytes, rc);
-    set.download(out->rgba8, d.rgba8, u8_bytes, rc);
-    if (rc == MCRT_OK) {
-        e = hipStreamSynchronize(s0->main_stream);
-        if (e != hipSuccess) rc = hip_fail(e, "reflection render");
-    }
-    return rc;
+    const Plane planes[] = {{out->rgba, 16, &d.rgba}, {out->distance, 4, &d.distance}, {out->rgba8, 4, &d.rgba8}};
+    return one_shot_pass(&desc, 1, device, planes, frame_pixels(cfg), "reflection planes", "reflection render", [&](mcrt_scene* const* h, size_t px, hipStream_t stream) {
+        return render_reflection_batch_device(h, 1, cfg, &ground_y, &d, px, stream);
+    });
 }
 
 // ---- studio shot: defaults, the scratch size and the one-shot host forms (render_enqueue.cpp: render_shot_batch_device) ----------
@@ -1016,25 +988,26 @@ static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_fra
     int rc = set.create(descs, n_frames, device, MCRT_BACKGROUND_REFERENCE);
     if (rc != MCRT_OK) return rc;
     mcrt_scene* s0 = set.h[0];
-    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
-    // the scratch (a multiple of 16 bytes), then the outputs, widest elements first
+    const size_t px = frame_pixels(cfg), total_px = px * static_cast<size_t>(n_frames);
+    // the scratch (a multiple of 16 bytes), then the outputs, then the bounds: n_frames elements, so a plane list of their own
     const size_t scratch_bytes = shot_scratch(cfg, shot, n_frames, floor_occlusion).bytes;
-    const size_t f32_bytes = out_rgba ? px * 16 * static_cast<size_t>(n_frames) : 0;
-    const size_t u8_bytes = out_rgba8 ? px * 4 * static_cast<size_t>(n_frames) : 0;
-    const size_t bounds_bytes = ex && ex->bounds ? sizeof(int32_t[4]) * static_cast<size_t>(n_frames) : 0;
-    hipError_t e = s0->frame.reserve(scratch_bytes + f32_bytes + u8_bytes + bounds_bytes);
+    float* d_f32 = nullptr;
+    uint8_t* d_u8 = nullptr;
+    ShotExtra on_device;  // the caller's additions, with the bounds in device memory
+    if (ex) on_device = *ex;
+    on_device.bounds = nullptr;
+    const Plane planes[] = {{out_rgba, 16, &d_f32}, {out_rgba8, 4, &d_u8}};
+    const Plane boxes[] = {{ex ? ex->bounds : nullptr, sizeof(int32_t[4]), &on_device.bounds}};
+    const size_t out_bytes = place_planes(planes, total_px, nullptr);
+    hipError_t e = s0->frame.reserve(scratch_bytes + out_bytes + place_planes(boxes, static_cast<size_t>(n_frames), nullptr));
     if (e != hipSuccess) return hip_fail(e, "shot planes");
     char* base = static_cast<char*>(s0->frame.ptr);
-    float* d_f32 = out_rgba ? reinterpret_cast<float*>(base + scratch_bytes) : nullptr;
-    uint8_t* d_u8 = out_rgba8 ? reinterpret_cast<uint8_t*>(base + scratch_bytes + f32_bytes) : nullptr;
-    ShotExtra on_device;  // the caller's additions, with the bounds in device memory behind the outputs (u8_bytes is a multiple of 4)
-    if (ex) on_device = *ex;
-    on_device.bounds = bounds_bytes ? reinterpret_cast<int32_t(*)[4]>(base + scratch_bytes + f32_bytes + u8_bytes) : nullptr;
+    place_planes(planes, total_px, base + scratch_bytes);
+    place_planes(boxes, static_cast<size_t>(n_frames), base + scratch_bytes + out_bytes);
     rc = render_shot_batch_device(set.h.data(), n_frames, cfg, shot, floor_occlusion, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream,
                                   ex ? &on_device : nullptr);
-    set.download(out_rgba, d_f32, f32_bytes, rc);
-    set.download(out_rgba8, d_u8, u8_bytes, rc);
-    if (bounds_bytes) set.download(ex->bounds, on_device.bounds, bounds_bytes, rc);
+    set.download(planes, total_px, rc);
+    set.download(boxes, static_cast<size_t>(n_frames), rc);
     if (rc == MCRT_OK) {
         e = hipStreamSynchronize(s0->main_stream);
         if (e != hipSuccess) rc = hip_fail(e, "shot render");
@@ -1125,30 +1098,10 @@ int mcrt_render_light(const mcrt_scene_desc* desc, const mcrt_config* cfg, const
     if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
     if (const int rc = check_light_config(cfg, out); rc != MCRT_OK) return rc;
     if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
-    OneShotScenes set;
-    const mcrt_scene_desc* one[1] = {desc};
-    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
-    if (rc != MCRT_OK) return rc;
-    mcrt_scene* s0 = set.h[0];
-    const size_t px = static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height);
-    // the widest elements first: each plane starts on a boundary of its own element size
-    const size_t direct_bytes = out->direct ? px * 16 : 0, vis_bytes = out->visibility ? px * 4 : 0, occ_bytes = out->occlusion ? px * 4 : 0;
-    hipError_t e = s0->frame.reserve(direct_bytes + vis_bytes + occ_bytes);
-    if (e != hipSuccess) return hip_fail(e, "light planes");
-    char* base = static_cast<char*>(s0->frame.ptr);
     mcrt_light_planes d{};
-    d.direct = out->direct ? reinterpret_cast<float*>(base) : nullptr;
-    d.visibility = out->visibility ? reinterpret_cast<float*>(base + direct_bytes) : nullptr;
-    d.occlusion = out->occlusion ? reinterpret_cast<float*>(base + direct_bytes + vis_bytes) : nullptr;
-    rc = render_light_batch_device(set.h.data(), 1, cfg, &d, px, s0->main_stream);
-    set.download(out->direct, d.direct, direct_bytes, rc);
-    set.download(out->visibility, d.visibility, vis_bytes, rc);
-    set.download(out->occlusion, d.occlusion, occ_bytes, rc);
-    if (rc == MCRT_OK) {
-        e = hipStreamSynchronize(s0->main_stream);
-        if (e != hipSuccess) rc = hip_fail(e, "light render");
-    }
-    return rc;
+    const Plane planes[] = {{out->direct, 16, &d.direct}, {out->visibility, 4, &d.visibility}, {out->occlusion, 4, &d.occlusion}};
+    return one_shot_pass(&desc, 1, device, planes, frame_pixels(cfg), "light planes", "light render",
+                         [&](mcrt_scene* const* h, size_t px, hipStream_t stream) { return render_light_batch_device(h, 1, cfg, &d, px, stream); });
 }
 
 // ---- light bake: the owner table (host only) and the one-shot host form (render_enqueue.cpp: bake_light_batch_device) ----------
@@ -1176,36 +1129,11 @@ int mcrt_bake_light(const mcrt_scene_desc* desc, const mcrt_config* cfg, int gri
     if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
     if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all five planes are NULL");
     if (const int rc = check_bake_config(cfg, grid, out); rc != MCRT_OK) return rc;
-    OneShotScenes set;
-    const mcrt_scene_desc* one[1] = {desc};
-    int rc = set.create(one, 1, device, MCRT_BACKGROUND_REFERENCE);
-    if (rc != MCRT_OK) return rc;
-    mcrt_scene* s0 = set.h[0];
-    const size_t n = static_cast<size_t>(s0->n_texels);
-    if (n == 0) return MCRT_OK;  // no texel: nothing is written
-    // the widest elements first: each plane starts on a boundary of its own element size
-    const size_t pos_bytes = out->position ? n * 16 : 0, nrm_bytes = out->normal ? n * 16 : 0, direct_bytes = out->direct ? n * 16 : 0;
-    const size_t vis_bytes = out->visibility ? ((n * 4 + 15) & ~static_cast<size_t>(15)) : 0, occ_bytes = out->occlusion ? n * 4 : 0;
-    hipError_t e = s0->frame.reserve(pos_bytes + nrm_bytes + direct_bytes + vis_bytes + occ_bytes);
-    if (e != hipSuccess) return hip_fail(e, "bake planes");
-    char* base = static_cast<char*>(s0->frame.ptr);
     mcrt_bake_planes d{};
-    d.position = out->position ? reinterpret_cast<float*>(base) : nullptr;
-    d.normal = out->normal ? reinterpret_cast<float*>(base + pos_bytes) : nullptr;
-    d.direct = out->direct ? reinterpret_cast<float*>(base + pos_bytes + nrm_bytes) : nullptr;
-    d.visibility = out->visibility ? reinterpret_cast<float*>(base + pos_bytes + nrm_bytes + direct_bytes) : nullptr;
-    d.occlusion = out->occlusion ? reinterpret_cast<float*>(base + pos_bytes + nrm_bytes + direct_bytes + vis_bytes) : nullptr;
-    rc = bake_light_batch_device(set.h.data(), 1, cfg, grid, &d, n, s0->main_stream);
-    set.download(out->position, d.position, pos_bytes, rc);
-    set.download(out->normal, d.normal, nrm_bytes, rc);
-    set.download(out->direct, d.direct, direct_bytes, rc);
-    set.download(out->visibility, d.visibility, n * 4, rc);
-    set.download(out->occlusion, d.occlusion, occ_bytes, rc);
-    if (rc == MCRT_OK) {
-        e = hipStreamSynchronize(s0->main_stream);
-        if (e != hipSuccess) rc = hip_fail(e, "light bake");
-    }
-    return rc;
+    const Plane planes[] = {{out->position, 16, &d.position}, {out->normal, 16, &d.normal}, {out->direct, 16, &d.direct},
+                            {out->visibility, 4, &d.visibility}, {out->occlusion, 4, &d.occlusion}};
+    return one_shot_pass(&desc, 1, device, planes, kPerTexel, "bake planes", "light bake",
+                         [&](mcrt_scene* const* h, size_t n, hipStream_t stream) { return bake_light_batch_device(h, 1, cfg, grid, &d, n, stream); });
 }
 
 int mcrt_scene_floor(const mcrt_scene_desc* desc, float* y) {
