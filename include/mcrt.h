@@ -667,7 +667,9 @@ int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_sce
  * against a repaint (stream order, or an event of the caller's) is the caller's job. */
 int mcrt_scene_set_skin_device(mcrt_scene* scene, const uint8_t* d_skin_rgba8, void* stream);
 /* One launch repaints n handles; skin i starts at d_skins + i * skin_stride_bytes.  The stride is at least the image size and a
- * multiple of 4.  The handles are of one skin kind, on one device, none listed twice.  n = 0: MCRT_OK, nothing done. */
+ * multiple of 4.  The handles take images of one size — 64x64 classic and 64x64 slim handles (mcrt_scene_create_skin_model) may
+ * be mixed freely, the launch chooses each workgroup's tables by its handle; 64x64 with 64x32 may not — and are on one device,
+ * none listed twice.  n = 0: MCRT_OK, nothing done. */
 int mcrt_scene_set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t skin_stride_bytes, void* stream);
 /* The host form: uploads the 16 KB (8 KB) image from HOST memory and repaints, synchronously. */
 int mcrt_scene_set_skin(mcrt_scene* scene, const uint8_t* skin_rgba8);
@@ -677,7 +679,7 @@ int mcrt_scene_set_skin(mcrt_scene* scene, const uint8_t* skin_rgba8);
 int mcrt_skin_pool_map(int skin_height, int32_t* out, int capacity);
 /* MCRT_ERR_INVALID, before any device work: a NULL handle, entry, image or `out`; a skin_height other than 64 or 32; n < 0; a
  * stride that is no multiple of 4 or smaller than the image; an image that is not 4-byte aligned; a handle that
- * mcrt_scene_create_skin did not create; handles of different skin kinds or devices in one batch; a handle listed twice. */
+ * mcrt_scene_create_skin did not create; handles of different image sizes or devices in one batch; a handle listed twice. */
 
 /* ---- views of resident scenes: another pose, camera or light for a scene that is already on the device ----------------------
  * The part of a repaintable handle's blob that pose, camera, light and background decide is its prefix [header][mesh table] —
@@ -700,7 +702,8 @@ int mcrt_skin_pool_map(int skin_height, int32_t* out, int capacity);
 int mcrt_scene_set_view(mcrt_scene* scene, const float pose[12], const mcrt_scene_desc* look);
 int mcrt_scene_set_view_device(mcrt_scene* scene, const float pose[12], const mcrt_scene_desc* look, void* stream);
 /* One launch gives n handles their views: poses[i], looks[i].  `poses` NULL, `looks` NULL or an entry looks[i] NULL: keep.  The
- * tables travel in one asynchronous copy.  The handles are of one skin kind, on one device, none listed twice.  n = 0: MCRT_OK. */
+ * tables travel in one asynchronous copy.  The handles take images of one size (classic and slim 64x64 handles may be mixed: each
+ * table is flattened for its handle's model), are on one device, none listed twice.  n = 0: MCRT_OK. */
 int mcrt_scene_set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12],
                                       const mcrt_scene_desc* const* looks, void* stream);
 /* Host only, no device.  The view-dependent prefix [0, texel_offset) of the blob of mcrt_scene_create_skin(skin_height, pose,
@@ -708,7 +711,7 @@ int mcrt_scene_set_views_batch_device(mcrt_scene* const* scenes, int n, const fl
  * (0 and the error text for a skin_height other than 64 or 32) and copies min(count, capacity) bytes into `out` (may be NULL). */
 int mcrt_skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, void* out, size_t capacity);
 /* MCRT_ERR_INVALID, before any device work and with the blobs and the handles' state untouched: a NULL handle, `scenes` or
- * entry; n < 0; a handle that mcrt_scene_create_skin did not create; handles of different skin kinds or devices in one batch; a
+ * entry; n < 0; a handle that mcrt_scene_create_skin did not create; handles of different image sizes or devices in one batch; a
  * handle listed twice; a stream that is being captured. */
 
 /* ---- studio shot: the figure on a page, with its ground shadow and its floor reflection, as ONE finished image ---------------
@@ -980,6 +983,29 @@ int mcrt_time_render_device(mcrt_scene* scene, const mcrt_config* cfg, int tile_
  * The returned description owns its arrays; free with mcrt_scene_desc_free(). */
 int mcrt_build_skin_scene(const uint8_t* skin_rgba8, int skin_width, int skin_height,
                           const float pose[12], mcrt_scene_desc** out);
+/* ---- player models.  MCRT_SKIN_CLASSIC is the reference's figure, arms 4 texels wide, and what every entry without a model
+ * argument means.  MCRT_SKIN_SLIM is Minecraft's slim ("Alex") model, for 64x64 skins only: it differs in the four arm boxes
+ * and nowhere else.  Their unwrap boxes {ox, oy, w, h, d} are {40,16,3,12,4} (right arm), {32,48,3,12,4} (left arm),
+ * {40,32,3,12,4} and {48,48,3,12,4} (their outer layers) — front and back 3x12, top and bottom 3x4, sides 4x12 — and the
+ * arm is the box of size {3, 12, 4} at {-+5.5, 18, 0}, x = -7 .. -4 and 4 .. 7, flush with the body as the classic arm is,
+ * rotated about the pivot {-+5.5, 24, 0} on its own axis; the outer layer's offset stays 0.5 and the mesh order is classic's.
+ * A slim figure with every part present has 12 meshes, 72 textures, 3264 - 4 * 32 = 3136 pool texels and 196 alpha words;
+ * its blob prefix [header][mesh table] has classic's 2496 bytes.  Every `_model` entry with MCRT_SKIN_CLASSIC is exactly
+ * its entry without; a model other than these two, or slim with skin_height 32, is MCRT_ERR_INVALID. */
+#define MCRT_SKIN_CLASSIC 0
+#define MCRT_SKIN_SLIM 1
+int mcrt_build_skin_scene_model(const uint8_t* skin_rgba8, int skin_width, int skin_height, int model,
+                                const float pose[12], mcrt_scene_desc** out);
+int mcrt_scene_create_skin_model(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, int device, mcrt_scene** out);
+int mcrt_skin_texel_model(int skin_height, int model, int mesh, int face_slot, int tx, int ty, int* skin_x, int* skin_y);
+int mcrt_skin_pool_map_model(int skin_height, int model, int32_t* out, int capacity); /* 3136 entries for slim */
+int mcrt_skin_view_table_model(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, void* out, size_t capacity);
+/* Host only.  Which model a skin image was painted for, by the rule the common skin viewers use — a HEURISTIC, since the image
+ * itself does not say: MCRT_SKIN_SLIM for a 64x64 image whose 64 pixels in the rectangles (x, y, w, h) = (50,16,2,4),
+ * (54,20,2,12), (42,48,2,4) and (46,52,2,12) — columns of the inner arms that a slim unwrap leaves unused — all have alpha 0,
+ * MCRT_SKIN_CLASSIC for every other 64x64 or 64x32 image.  A classic skin with transparent arms reads as slim; a slim skin
+ * whose painter filled those columns reads as classic.  -1 and the error text for NULL or another size. */
+int mcrt_skin_model_of(const uint8_t* skin_rgba8, int skin_width, int skin_height);
 /* MeshBuilder::buildDefaultScene (mesh_builder.cpp:204-223): white 1x1 textures, no outer layer */
 int mcrt_build_default_scene(const float pose[12], mcrt_scene_desc** out);
 /* one of the 7 built-in poses of pose.h:25-92 (index 0..6) → 12 floats; returns MCRT_ERR_INVALID

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_shot_batch_occ", "mcrt_render_shot_png_occ",
     "mcrt_shot_ex_init", "mcrt_shot_scratch_bytes_ex", "mcrt_composite_shot_batch_device_ex", "mcrt_render_shot_batch_device_ex",
     "mcrt_render_shot_batch_ex", "mcrt_render_shot_png_ex",
+    "mcrt_build_skin_scene_model", "mcrt_scene_create_skin_model", "mcrt_skin_texel_model", "mcrt_skin_pool_map_model",
+    "mcrt_skin_view_table_model", "mcrt_skin_model_of",
 ]
 
 
@@ -115,6 +117,12 @@ def load():
         "mcrt_scene_pick": (C.c_int, [vp, cfg_p, abi.c_int32_p, C.c_int, vp]),
         "mcrt_skin_texel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mcrt_scene_create_skin": (C.c_int, [C.c_int, f_p, desc_p, C.c_int, C.POINTER(vp)]),
+        "mcrt_scene_create_skin_model": (C.c_int, [C.c_int, C.c_int, f_p, desc_p, C.c_int, C.POINTER(vp)]),
+        "mcrt_skin_texel_model": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mcrt_skin_pool_map_model": (C.c_int, [C.c_int, C.c_int, abi.c_int32_p, C.c_int]),
+        "mcrt_skin_view_table_model": (C.c_int, [C.c_int, C.c_int, f_p, desc_p, vp, C.c_size_t]),
+        "mcrt_skin_model_of": (C.c_int, [u8_p, C.c_int, C.c_int]),
+        "mcrt_build_skin_scene_model": (C.c_int, [u8_p, C.c_int, C.c_int, C.c_int, f_p, C.POINTER(desc_p)]),
         "mcrt_scene_set_skin_device": (C.c_int, [vp, vp, vp]),
         "mcrt_scene_set_skins_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_size_t, vp]),
         "mcrt_scene_set_skin": (C.c_int, [vp, u8_p]),

@@ -19,6 +19,8 @@ MCRT_ERR_INVALID = 1
 MCRT_ERR_NO_DEVICE = 2
 MCRT_ERR_HIP = 3
 MCRT_ERR_NOMEM = 4
+SKIN_CLASSIC = 0  # MCRT_SKIN_*: the player model of a skin scene
+SKIN_SLIM = 1
 LAYOUT_FRAME = 0
 LAYOUT_PACKED = 1
 BACKGROUND_REFERENCE = 0  # MCRT_BACKGROUND_*: every pixel as the reference renders it (the default)

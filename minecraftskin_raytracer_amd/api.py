@@ -79,15 +79,25 @@ class MeshBuilder:
     """scene/mesh_builder.h:7-34 (scene construction from skin data; native implementation)."""
 
     @staticmethod
-    def buildScene(skin_rgba8: np.ndarray, pose: Optional[Sequence[float]] = None) -> SceneDesc:
-        """SkinParser::parse (64x64 / 64x32 RGBA8) + MeshBuilder::buildScene."""
+    def buildScene(skin_rgba8: np.ndarray, pose: Optional[Sequence[float]] = None, model: str = "classic") -> SceneDesc:
+        """SkinParser::parse (64x64 / 64x32 RGBA8) + MeshBuilder::buildScene.  ``model``: ``"classic"`` (the reference's figure),
+        ``"slim"`` (arms 3 texels wide, 64x64 skins only) or ``"auto"`` (``skin_model`` of the image)."""
         skin = np.ascontiguousarray(skin_rgba8, np.uint8)
         if skin.ndim != 3 or skin.shape[2] != 4:
             raise ValueError("skin must be (H, W, 4) uint8")
         h, w = skin.shape[:2]
+        if model == "auto" and w == 64 and h in (64, 32):
+            model = skin_model(skin)
+        if model not in ("classic", "slim", "auto"):
+            raise ValueError("model must be 'classic', 'slim' or 'auto'")
+        if model == "slim" and h != 64:
+            raise ValueError("the slim model exists for 64x64 skins only")
         p = np.asarray(pose if pose is not None else [0.0] * 12, np.float32)
         out = C.POINTER(abi.McrtSceneDesc)()
-        rc = load().mcrt_build_skin_scene(skin.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, abi.fptr(p), C.byref(out))
+        if model == "slim":
+            rc = load().mcrt_build_skin_scene_model(skin.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, abi.SKIN_SLIM, abi.fptr(p), C.byref(out))
+        else:
+            rc = load().mcrt_build_skin_scene(skin.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, abi.fptr(p), C.byref(out))
         if rc != 0:
             # skin_parser.cpp:122-131: only 64x64 and 64x32 are valid
             raise ValueError(f"Invalid skin dimensions: {w}x{h} (expected 64x64 or 64x32)")
@@ -520,11 +530,11 @@ def _ground_heights(descs, ground) -> List[float]:
 
 def skin_texel(kind, mesh: int, face: int, tx: int, ty: int) -> Tuple[int, int]:
     """(mesh, face slot, tx, ty) of a scene built by ``MeshBuilder.buildScene`` → the skin image's texel ``(x, y)`` that face
-    texel was cut from (mcrt_skin_texel).  ``kind``: ``"S64"`` / ``"S32"`` or the skin's height.  Out-of-range arguments raise
-    ``ValueError``."""
+    texel was cut from (mcrt_skin_texel_model).  ``kind``: ``"S64"`` / ``"S32"`` or the skin's height, ``"S64S"`` / ``"slim"`` for
+    the slim model.  Out-of-range arguments raise ``ValueError``."""
     x, y = C.c_int(), C.c_int()
     lib = load()
-    if lib.mcrt_skin_texel(_skin_height(kind), int(mesh), int(face) & 7, int(tx), int(ty), C.byref(x), C.byref(y)) != 0:
+    if lib.mcrt_skin_texel_model(*_skin_kind(kind), int(mesh), int(face) & 7, int(tx), int(ty), C.byref(x), C.byref(y)) != 0:
         raise ValueError(lib.mcrt_last_error().decode("utf-8", "replace"))
     return int(x.value), int(y.value)
 
@@ -614,13 +624,39 @@ def _skin_height(kind) -> int:
     return SKIN_HEIGHTS[kind]
 
 
+# a skin kind with its player model: (skin height, model).  "S64S" / "slim": a 64x64 skin on the slim model
+SKIN_KINDS = {"S64S": (64, abi.SKIN_SLIM), "slim": (64, abi.SKIN_SLIM)}
+SKIN_KINDS.update({k: (h, abi.SKIN_CLASSIC) for k, h in SKIN_HEIGHTS.items()})
+SKIN_POOL_TEXELS = {(64, abi.SKIN_CLASSIC): 3264, (32, abi.SKIN_CLASSIC): 2016, (64, abi.SKIN_SLIM): 3136}
+
+
+def _skin_kind(kind) -> Tuple[int, int]:
+    if isinstance(kind, bool) or kind not in SKIN_KINDS:
+        raise ValueError("kind must be 'S64', 'S32', 'S64S' ('slim'), 64 or 32")
+    return SKIN_KINDS[kind]
+
+
+def skin_model(image) -> str:
+    """``"slim"`` or ``"classic"``: the player model a skin image, (64 | 32, 64, 4) uint8, was painted for, by the rule the common
+    skin viewers use (mcrt_skin_model_of) — a heuristic: slim iff the image is 64x64 and the 64 pixels of the inner arms'
+    unwraps that a slim figure never reads all have alpha 0."""
+    a = np.ascontiguousarray(image, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("skin must be (H, W, 4) uint8")
+    lib = load()
+    m = lib.mcrt_skin_model_of(a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0])
+    if m < 0:
+        raise ValueError(lib.mcrt_last_error().decode("utf-8", "replace"))
+    return "slim" if m == abi.SKIN_SLIM else "classic"
+
+
 def skin_pool_map(kind) -> np.ndarray:
     """Per texel of the pool of a repaintable scene (``DeviceScene.for_skin``), in pool order, the skin pixel index
-    ``y * 64 + x`` it is cut from (mcrt_skin_pool_map): 3264 int32 for ``"S64"``, 2016 for ``"S32"``."""
-    h = _skin_height(kind)
+    ``y * 64 + x`` it is cut from (mcrt_skin_pool_map_model): 3264 int32 for ``"S64"``, 2016 for ``"S32"``, 3136 for ``"S64S"``."""
+    h, model = _skin_kind(kind)
     lib = load()
-    out = np.zeros(3264 if h == 64 else 2016, np.int32)
-    n = lib.mcrt_skin_pool_map(h, out.ctypes.data_as(abi.c_int32_p), len(out))
+    out = np.zeros(SKIN_POOL_TEXELS[h, model], np.int32)
+    n = lib.mcrt_skin_pool_map_model(h, model, out.ctypes.data_as(abi.c_int32_p), len(out))
     if n != len(out):
         raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
     return out
@@ -637,15 +673,16 @@ def _view_pose(pose) -> Optional[np.ndarray]:
 
 def skin_view_table(kind, pose: Optional[Sequence[float]] = None, look=None) -> bytes:
     """The view-dependent prefix ``[header][mesh table]`` of the blob of ``DeviceScene.for_skin(kind, pose, look)`` — bytes
-    ``[0, texel_offset)``, 2496 for ``"S64"`` and 1536 for ``"S32"`` — computed on the host (mcrt_skin_view_table): what a
-    view change writes into a resident scene, but for the MESH_OPAQUE bits, which are the white figure's here."""
-    h = _skin_height(kind)
+    ``[0, texel_offset)``, 2496 for ``"S64"`` and ``"S64S"``, 1536 for ``"S32"`` — computed on the host
+    (mcrt_skin_view_table_model): what a view change writes into a resident scene, but for the MESH_OPAQUE bits, which are the
+    white figure's here."""
+    h, model = _skin_kind(kind)
     p, d = _view_pose(pose), _as_desc(look) if look is not None else None
     lib = load()
-    args = (h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None)
-    n = lib.mcrt_skin_view_table(*args, None, 0)
+    args = (h, model, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None)
+    n = lib.mcrt_skin_view_table_model(*args, None, 0)
     buf = C.create_string_buffer(max(n, 1))
-    if n <= 0 or lib.mcrt_skin_view_table(*args, buf, n) != n:
+    if n <= 0 or lib.mcrt_skin_view_table_model(*args, buf, n) != n:
         raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
     return buf.raw[:n]
 
@@ -697,11 +734,11 @@ def texel_table(scene) -> np.ndarray:
 
 def pool_to_skin(kind, values, fill=0) -> np.ndarray:
     """Scatters a pool-order plane of a repaintable scene (``DeviceScene.for_skin``) or of a builder figure with every part
-    present — ``values``: (n,) or (n, c) with n = 3264 for ``"S64"``, 2016 for ``"S32"`` — into a skin-shaped image
+    present — ``values``: (n,) or (n, c) with n = 3264 for ``"S64"``, 2016 for ``"S32"``, 3136 for ``"S64S"`` — into a skin-shaped image
     ``(skin_height, 64[, c])`` through ``skin_pool_map``.  Where a legacy skin maps two pool texels to one pixel (its mirrored
     left limbs) the lowest pool index wins; pixels no pool texel is cut from hold ``fill``.  Pure numpy."""
-    h = _skin_height(kind)
-    pmap = skin_pool_map(h)
+    h = _skin_kind(kind)[0]
+    pmap = skin_pool_map(kind)
     v = np.asarray(values)
     if v.ndim not in (1, 2) or v.shape[0] != len(pmap):
         raise ValueError(f"values must be ({len(pmap)},) or ({len(pmap)}, c) for this skin kind")
@@ -715,6 +752,7 @@ class DeviceScene:
     (e.g. ``torch.Tensor.data_ptr()``) on a caller-chosen HIP stream."""
 
     skin_height = 0  # 64 / 32 for a repaintable scene (for_skin)
+    skin_model = "classic"  # "slim" for a repaintable scene of the slim model (for_skin("S64S", ...))
 
     def __init__(self, scene, device: int = 0):
         self._desc = _as_desc(scene)
@@ -724,19 +762,20 @@ class DeviceScene:
 
     @classmethod
     def for_skin(cls, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0) -> "DeviceScene":
-        """A REPAINTABLE scene (mcrt_scene_create_skin): the builder's figure for ``kind`` (``"S64"`` / ``"S32"`` or the skin's
-        height) at ``pose`` with every part present — always the full mesh table of ``skin_texel``, 12 or 7 meshes — which
+        """A REPAINTABLE scene (mcrt_scene_create_skin_model): the builder's figure for ``kind`` (``"S64"`` / ``"S32"`` or the skin's
+        height, ``"S64S"`` / ``"slim"`` for a 64x64 skin on the slim model) at ``pose`` with every part present — always the full mesh table of ``skin_texel``, 12 or 7 meshes — which
         ``set_skin`` / ``set_skin_device`` / ``set_skins_batch_device`` give a new skin without rebuilding the scene.  ``look``:
         a ``Scene`` / ``SceneDesc`` whose light, camera and background are taken (its meshes are ignored); ``None``: the
         builder's.  White and opaque until the first repaint."""
-        h = _skin_height(kind)
+        h, model = _skin_kind(kind)
         self = object.__new__(cls)
         self._desc = _as_desc(look) if look is not None else None
         self._h = C.c_void_p()
         self.device = device
         self.skin_height = h
+        self.skin_model = "slim" if model == abi.SKIN_SLIM else "classic"
         p = _view_pose(pose)
-        check(load().mcrt_scene_create_skin(h, abi.fptr(p) if p is not None else None, self._desc.ptr if self._desc is not None else None,
+        check(load().mcrt_scene_create_skin_model(h, model, abi.fptr(p) if p is not None else None, self._desc.ptr if self._desc is not None else None,
                                             int(device), C.byref(self._h)))
         return self
 
@@ -1127,7 +1166,8 @@ def bake_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Conf
 
 
 def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, skin_stride_bytes: Optional[int] = None, stream: int = 0) -> None:
-    """One launch repaints N repaintable scenes of one skin kind (mcrt_scene_set_skins_batch_device): skin i is the RGBA8 image
+    """One launch repaints N repaintable scenes that take images of one size — ``"S64"`` and ``"S64S"`` scenes may be mixed —
+    (mcrt_scene_set_skins_batch_device): skin i is the RGBA8 image
     at ``ptr + i * skin_stride_bytes`` in device memory (default: the image size, 64 * height * 4).  Asynchronous on ``stream``."""
     handles = _handles(device_scenes)
     n = len(handles)
@@ -1138,7 +1178,7 @@ def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, ski
 
 
 def set_views_batch_device(device_scenes: Sequence["DeviceScene"], poses=None, looks=None, stream: int = 0) -> None:
-    """One launch gives N repaintable scenes of one skin kind their views (mcrt_scene_set_views_batch_device): ``poses`` — N
+    """One launch gives N repaintable scenes of one image size their views (mcrt_scene_set_views_batch_device): ``poses`` — N
     poses of 12 floats, or ``None``: every scene keeps its own; ``looks`` — N entries, each a ``Scene`` / ``SceneDesc`` or
     ``None`` (that scene keeps its look), or ``None`` for all.  Asynchronous on ``stream``; the arguments are read before the
     call returns."""
@@ -1167,18 +1207,26 @@ class SkinBatch:
     """The farm case: ``n`` repaintable scenes of one skin kind, pose and look resident on ``device``, and a skin buffer there.
     ``render(skins, config)`` gives the frames of ``m <= n`` skins with ONE upload (the images, 16 KB each), one repaint launch,
     one ``render_batch_device`` call and one download — what ``TileRenderer.renderBatch([MeshBuilder.buildScene(s, pose) ...])``
-    returns, bit for bit, without building, flattening and uploading a scene per skin.  Device memory through torch."""
+    returns, bit for bit, without building, flattening and uploading a scene per skin.  Device memory through torch.
+    ``slim=True`` (``"S64"`` only): every slot also keeps a scene of the slim model, and ``render`` / ``shots`` / ``layers`` take
+    ``models`` — ``None``: all classic; ``"auto"``: ``skin_model`` of each image; or one of ``"classic"`` / ``"slim"`` per skin —
+    and repaint the chosen scenes of a mixed batch in the same ONE launch."""
 
-    def __init__(self, n: int, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0):
+    def __init__(self, n: int, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0, slim: bool = False):
         import torch
 
         self.kind_height = _skin_height(kind)
+        if slim and self.kind_height != 64:
+            raise ValueError("the slim model exists for 64x64 skins only")
         self.device = int(device)
         self._torch = torch
         self.scenes: List[DeviceScene] = []
+        self.slim_scenes: List[DeviceScene] = []  # slot i's scene of the slim model (slim=True), else empty
         try:
             for _ in range(int(n)):
                 self.scenes.append(DeviceScene.for_skin(self.kind_height, pose, look, device))
+            for _ in range(int(n) if slim else 0):
+                self.slim_scenes.append(DeviceScene.for_skin("S64S", pose, look, device))
         except Exception:
             self.close()
             raise
@@ -1189,9 +1237,9 @@ class SkinBatch:
         self._mode = None
 
     def close(self) -> None:
-        for s in self.scenes:
+        for s in self.scenes + self.slim_scenes:
             s.close()
-        self.scenes = []
+        self.scenes, self.slim_scenes = [], []
 
     def __del__(self):
         try:
@@ -1218,8 +1266,11 @@ class SkinBatch:
                 raise ValueError(f"looks must be one look or {n} of them")
         if n == 0 or (poses is None and looks is None):
             return
+        if self.slim_scenes:  # both scenes of every slot, in the one launch
+            poses = np.concatenate([poses, poses]) if poses is not None else None
+            looks = looks + looks if looks is not None else None
         with self._torch.cuda.device(self._dev):
-            set_views_batch_device(self.scenes, poses, looks, stream=self._torch.cuda.current_stream().cuda_stream)
+            set_views_batch_device(self.scenes + self.slim_scenes, poses, looks, stream=self._torch.cuda.current_stream().cuda_stream)
 
     def _check_skins(self, skins) -> np.ndarray:
         a = np.ascontiguousarray(skins, np.uint8)
@@ -1227,17 +1278,31 @@ class SkinBatch:
             raise ValueError(f"skins must be (m <= {len(self.scenes)}, {self.kind_height}, 64, 4) uint8")
         return a
 
-    def _paint(self, skins, stream) -> int:
-        """Uploads and repaints; every caller synchronises `stream` before it returns (the pinned staging buffer is reused)."""
+    def _chosen(self, a, models) -> List[DeviceScene]:
+        """Slot i's scene for skin i: the classic one, or the slim one where ``models`` says so."""
+        m = len(a)
+        if models is None:
+            return self.scenes[:m]
+        names = [skin_model(k) for k in a] if isinstance(models, str) and models == "auto" else list(models)
+        if len(names) != m or any(k not in ("classic", "slim") for k in names):
+            raise ValueError(f"models must be None, 'auto' or {m} entries 'classic' / 'slim': one per skin")
+        if "slim" in names and not self.slim_scenes:
+            raise ValueError("this batch holds no slim scenes: create it with slim=True")
+        return [self.slim_scenes[i] if k == "slim" else self.scenes[i] for i, k in enumerate(names)]
+
+    def _paint(self, skins, stream, models=None) -> List[DeviceScene]:
+        """Uploads and repaints; returns the scenes that now hold the skins.  Every caller synchronises `stream` before it
+        returns (the pinned staging buffer is reused)."""
         torch = self._torch
         a = self._check_skins(skins)
+        chosen = self._chosen(a, models)
         m = len(a)
         if m:
             self._staging[:m].numpy()[...] = a
             with torch.cuda.stream(stream):
                 self._skins[:m].copy_(self._staging[:m], non_blocking=True)
-            set_skins_batch_device(self.scenes[:m], self._skins.data_ptr(), stream=stream.cuda_stream)
-        return m
+            set_skins_batch_device(chosen, self._skins.data_ptr(), stream=stream.cuda_stream)
+        return chosen
 
     def _buffers(self, key, shape, dtype):
         torch = self._torch
@@ -1247,7 +1312,7 @@ class SkinBatch:
             self._out[key] = got
         return got
 
-    def render(self, skins, config: Config, rgba8: bool = False, background: str = "reference") -> np.ndarray:
+    def render(self, skins, config: Config, rgba8: bool = False, background: str = "reference", models=None) -> np.ndarray:
         """``skins``: (m <= n, H, 64, 4) uint8.  Returns (m, height, width, 4) float32, or uint8 with ``rgba8``."""
         torch = self._torch
         mode = abi.background_mode(background)
@@ -1256,22 +1321,23 @@ class SkinBatch:
             stream = torch.cuda.current_stream()
             if no_frame:  # nothing is painted either (the staging buffer stays idle)
                 return _default_frames(len(self._check_skins(skins)), h, w, rgba8)
-            m = self._paint(skins, stream)
+            chosen = self._paint(skins, stream, models)
+            m = len(chosen)
             dtype = torch.uint8 if rgba8 else torch.float32
             if m == 0:
                 return _default_frames(0, h, w, rgba8)
             if mode != self._mode:
-                for s in self.scenes:
+                for s in self.scenes + self.slim_scenes:
                     s.set_background(background)
                 self._mode = mode
             dev, host = self._buffers("frames", (len(self.scenes), h, w, 4), dtype)
-            render_batch_device(self.scenes[:m], config, 0 if rgba8 else dev.data_ptr(), dev.data_ptr() if rgba8 else 0, w * h, stream.cuda_stream)
+            render_batch_device(chosen, config, 0 if rgba8 else dev.data_ptr(), dev.data_ptr() if rgba8 else 0, w * h, stream.cuda_stream)
             with torch.cuda.stream(stream):
                 host[:m].copy_(dev[:m], non_blocking=True)
             stream.synchronize()
             return host[:m].numpy().copy()
 
-    def shots(self, skins, config: Config, shot: Optional[abi.Shot] = None, ground=0.0, rgba8: bool = True, bounds: bool = False):
+    def shots(self, skins, config: Config, shot: Optional[abi.Shot] = None, ground=0.0, rgba8: bool = True, bounds: bool = False, models=None):
         """The studio shots of the ``m`` skins (``TileRenderer.renderShotBatch`` of the scenes built per skin, bit for bit): one
         upload, one repaint, one ``render_shot_batch_device`` call — render, ground, reflection and blend on the device — and
         one download of 4 B/pixel (16 with ``rgba8=False``).  ``ground``: one height for all (0.0: the soles of the builder's
@@ -1290,7 +1356,8 @@ class SkinBatch:
                 raise ValueError("ground heights are needed: a resident scene does not keep its description")
             heights = _ground_heights(list(range(len(a))), ground)
             need = shot_scratch_bytes(config, shot, len(self.scenes), bounds)  # (raises nothing: an invalid shot is refused by the call below)
-            m = self._paint(a, stream)
+            chosen = self._paint(a, stream, models)
+            m = len(chosen)
             if m == 0:
                 none = _default_frames(0, h, w, rgba8)
                 return (none, _empty_bounds(0, w, h)) if bounds else none
@@ -1301,7 +1368,7 @@ class SkinBatch:
             dev, host = self._buffers("shots", (len(self.scenes), h, w, 4), torch.uint8 if rgba8 else torch.float32)
             box_dev, box_host = self._buffers("shot_bounds", (len(self.scenes), 4), torch.int32) if bounds else (None, None)
             try:
-                render_shot_batch_device(self.scenes[:m], config, shot, heights, scratch.data_ptr(), scratch.numel(), 0 if rgba8 else dev.data_ptr(),
+                render_shot_batch_device(chosen, config, shot, heights, scratch.data_ptr(), scratch.numel(), 0 if rgba8 else dev.data_ptr(),
                                          dev.data_ptr() if rgba8 else 0, w * h, stream.cuda_stream, box_dev.data_ptr() if bounds else 0)
                 with torch.cuda.stream(stream):
                     host[:m].copy_(dev[:m], non_blocking=True)
@@ -1311,7 +1378,7 @@ class SkinBatch:
                 stream.synchronize()  # (a refused shot too: the repaint reads the pinned staging buffer)
             return (host[:m].numpy().copy(), box_host[:m].numpy().copy()) if bounds else host[:m].numpy().copy()
 
-    def layers(self, skins, config: Config, layers=abi.LAYER_NAMES) -> dict:
+    def layers(self, skins, config: Config, layers=abi.LAYER_NAMES, models=None) -> dict:
         """The geometry layers of the ``m`` skins' frames (``TileRenderer.renderLayersBatch``'s planes) through
         ``render_layers_batch_device``, behind the repaint on the same stream."""
         torch = self._torch
@@ -1321,7 +1388,8 @@ class SkinBatch:
             stream = torch.cuda.current_stream()
             if no_frame:  # nothing is painted either
                 return {k: abi.LAYERS.empty(k, len(self._check_skins(skins)), h, w) for k in names}
-            m = self._paint(skins, stream)
+            chosen = self._paint(skins, stream, models)
+            m = len(chosen)
             if m == 0:
                 return {k: abi.LAYERS.empty(k, 0, h, w) for k in names}
             n = len(self.scenes)
@@ -1330,7 +1398,7 @@ class SkinBatch:
                 dtype, comps = abi.LAYERS.formats[k]
                 shape = (n, h, w) + ((comps,) if comps > 1 else ())
                 bufs[k] = self._buffers(k, shape, torch.int32 if dtype is np.int32 else torch.float32)
-            render_layers_batch_device(self.scenes[:m], config, frame_stride_pixels=w * h, stream=stream.cuda_stream,
+            render_layers_batch_device(chosen, config, frame_stride_pixels=w * h, stream=stream.cuda_stream,
                                        **{f"{k}_ptr": bufs[k][0].data_ptr() for k in names})
             with torch.cuda.stream(stream):
                 for k in names:

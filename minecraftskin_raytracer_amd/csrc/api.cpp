@@ -124,9 +124,10 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     }
     s->forced_lanes = 0;
     s->background = MCRT_BACKGROUND_REFERENCE;
-    if (s->skin_tables) release_skin_tables(device, s->skin_height);  // a pooled shell that was a repaintable handle
+    if (s->skin_tables) release_skin_tables(device, s->skin_height, s->skin_model);  // a pooled shell that was a repaintable handle
     s->skin_tables = nullptr;
     s->skin_height = 0;
+    s->skin_model = MCRT_SKIN_CLASSIC;
     s->has_pose = s->has_look = false;  // (mcrt_scene_create_skin notes its own)
     s->budget = 0;  // a budget halved under memory pressure is not inherited
     s->have_last = false;  // a pooled shell was synchronised when its previous owner let go of it
@@ -184,7 +185,7 @@ void remember_view(mcrt_scene* s, const float pose[12], const mcrt_scene_desc* l
 }
 }  // namespace
 
-extern "C" mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, const float pose[12]);  // scene_builder.cpp
+extern "C" mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, int model, const float pose[12]);  // scene_builder.cpp
 
 namespace mcrt_host {
 void apply_look(mcrt_scene_desc* desc, const mcrt_scene_desc* look) {
@@ -199,9 +200,11 @@ void apply_look(mcrt_scene_desc* desc, const mcrt_scene_desc* look) {
     std::memcpy(desc->background_color, look->background_color, sizeof desc->background_color);
 }
 
-int skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, std::vector<uint8_t>& table) {
+int skin_view_table(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, std::vector<uint8_t>& table) {
     if (skin_height != 64 && skin_height != 32) return fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
-    mcrt_scene_desc* desc = mcrt_detail_white_figure(skin_height, pose);
+    if (model != MCRT_SKIN_CLASSIC && !(model == MCRT_SKIN_SLIM && skin_height == 64))
+        return fail(MCRT_ERR_INVALID, "model must be MCRT_SKIN_CLASSIC, or MCRT_SKIN_SLIM with a 64x64 skin");
+    mcrt_scene_desc* desc = mcrt_detail_white_figure(skin_height, model, pose);
     if (look) apply_look(desc, look);
     std::string err;
     const bool flat = flatten_view_table(desc, table, err);
@@ -227,14 +230,20 @@ int mcrt_scene_create(const mcrt_scene_desc* desc, int device, mcrt_scene** out)
 }
 
 int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_scene_desc* look, int device, mcrt_scene** out) {
+    return mcrt_scene_create_skin_model(skin_height, MCRT_SKIN_CLASSIC, pose, look, device, out);
+}
+
+int mcrt_scene_create_skin_model(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, int device, mcrt_scene** out) {
     if (!out) return fail(MCRT_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (skin_height != 64 && skin_height != 32) return fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    if (model != MCRT_SKIN_CLASSIC && !(model == MCRT_SKIN_SLIM && skin_height == 64))
+        return fail(MCRT_ERR_INVALID, "model must be MCRT_SKIN_CLASSIC, or MCRT_SKIN_SLIM with a 64x64 skin");
     // the builder's figure of an all-opaque white skin: no outer part is dropped, so the mesh table is the full one of
-    // mcrt_skin_texel (12 meshes, or 7) and the pool holds a slot for every texel a skin of this kind can show
+    // mcrt_skin_texel[_model] (12 meshes, or 7) and the pool holds a slot for every texel a skin of this kind can show
     const std::vector<uint8_t> white(static_cast<size_t>(64) * static_cast<size_t>(skin_height) * 4, 255);
     mcrt_scene_desc* desc = nullptr;
-    if (mcrt_build_skin_scene(white.data(), 64, skin_height, pose, &desc) != MCRT_OK || !desc) return fail(MCRT_ERR_INVALID, "the scene builder failed");
+    if (mcrt_build_skin_scene_model(white.data(), 64, skin_height, model, pose, &desc) != MCRT_OK || !desc) return fail(MCRT_ERR_INVALID, "the scene builder failed");
     if (look) apply_look(desc, look);
     std::vector<uint8_t> b;
     std::string err;
@@ -243,8 +252,10 @@ int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_sce
     if (!flat) return fail(MCRT_ERR_INVALID, err);
     mcrt_scene* s = nullptr;
     if (const int rc = create_scene_from_blob(b, device, &s); rc != MCRT_OK) return rc;
-    s->skin_tables = acquire_skin_tables(device, skin_height);
+    s->skin_model = model;  // (before the tables: a shell's release names the store by its own height and model)
+    s->skin_tables = acquire_skin_tables(device, skin_height, model);
     if (!s->skin_tables) {
+        s->skin_model = MCRT_SKIN_CLASSIC;
         mcrt_scene_destroy(s);
         return fail(MCRT_ERR_HIP, "the device's repaint tables could not be built");
     }
@@ -255,8 +266,12 @@ int mcrt_scene_create_skin(int skin_height, const float pose[12], const mcrt_sce
 }
 
 int mcrt_skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, void* out, size_t capacity) {
+    return mcrt_skin_view_table_model(skin_height, MCRT_SKIN_CLASSIC, pose, look, out, capacity);
+}
+
+int mcrt_skin_view_table_model(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, void* out, size_t capacity) {
     std::vector<uint8_t> t;
-    if (skin_view_table(skin_height, pose, look, t) != MCRT_OK) return 0;
+    if (skin_view_table(skin_height, model, pose, look, t) != MCRT_OK) return 0;
     if (out && capacity) std::memcpy(out, t.data(), t.size() < capacity ? t.size() : capacity);
     return static_cast<int>(t.size());
 }

@@ -420,26 +420,26 @@ void acquire_plates(mcrt_scene* s, RenderParams* p, int n, bool capturing, bool 
 
 // ---- per-device repaint tables (kernels.h: SkinPaintShape), one per skin kind: the 256 floats i / 255.0f — formed HERE, on
 // the host, by the scene builder's own expression, so a repainted texel is the builder's float whatever the device's divide
-// does — then per pool texel (mesh << 12) | skin pixel, from the builder's tables (scene_builder.cpp).  6.6 KB and 4.9 KB;
+// does — then per pool texel (mesh << 12) | skin pixel, from the builder's tables (scene_builder.cpp).  6.6, 4.9 and 6.3 KB;
 // a `users` count of the handles that hold them, like the seed tables.
-extern "C" int mcrt_detail_skin_pool(int skin_height, int32_t* pixel, int32_t* mesh_of, int capacity);  // scene_builder.cpp
+extern "C" int mcrt_detail_skin_pool(int skin_height, int model, int32_t* pixel, int32_t* mesh_of, int capacity);  // scene_builder.cpp
 namespace {
 struct SkinTables {
     void* ptr = nullptr;
     int users = 0;
 };
 std::mutex g_skin_mutex;
-std::vector<SkinTables> g_skin_tables[2];  // [skin_height == 32], by device
+std::vector<SkinTables> g_skin_tables[kSkinKinds];  // [skin_kind_index], by device
 }  // namespace
 
-const void* acquire_skin_tables(int device, int skin_height) {
+const void* acquire_skin_tables(int device, int skin_height, int model) {
     std::lock_guard<std::mutex> lock(g_skin_mutex);
-    std::vector<SkinTables>& by_device = g_skin_tables[skin_height == 32 ? 1 : 0];
+    std::vector<SkinTables>& by_device = g_skin_tables[skin_kind_index(skin_height, model)];
     if (by_device.size() <= static_cast<size_t>(device)) by_device.resize(static_cast<size_t>(device) + 1);
     SkinTables& t = by_device[static_cast<size_t>(device)];
     if (!t.ptr) {
         int32_t pixel[kSkinMaxTexels], mesh_of[kSkinMaxTexels];
-        const int n = mcrt_detail_skin_pool(skin_height, pixel, mesh_of, kSkinMaxTexels);  // (writes kSkinMaxTexels entries at most)
+        const int n = mcrt_detail_skin_pool(skin_height, model, pixel, mesh_of, kSkinMaxTexels);  // (writes kSkinMaxTexels entries at most)
         if (n <= 0 || n > kSkinMaxTexels) return nullptr;  // the builder's tables outgrew the kernel's: no repaint, never an over-read
         std::vector<uint8_t> host(skin_tables_bytes(n));
         float* unit = reinterpret_cast<float*>(host.data());
@@ -457,9 +457,9 @@ const void* acquire_skin_tables(int device, int skin_height) {
     ++t.users;
     return t.ptr;
 }
-void release_skin_tables(int device, int skin_height) {
+void release_skin_tables(int device, int skin_height, int model) {
     std::lock_guard<std::mutex> lock(g_skin_mutex);
-    std::vector<SkinTables>& by_device = g_skin_tables[skin_height == 32 ? 1 : 0];
+    std::vector<SkinTables>& by_device = g_skin_tables[skin_kind_index(skin_height, model)];
     if (static_cast<size_t>(device) < by_device.size() && by_device[static_cast<size_t>(device)].users > 0) --by_device[static_cast<size_t>(device)].users;
 }
 namespace {
@@ -522,7 +522,7 @@ void destroy_scene_now(mcrt_scene* s) {
     unregister_live(s);  // before its events go
     if (s->holds_seed_table) g_window_tables.release(s->device);
     if (s->holds_full_table) g_full_tables.release(s->device);
-    if (s->skin_tables) release_skin_tables(s->device, s->skin_height);
+    if (s->skin_tables) release_skin_tables(s->device, s->skin_height, s->skin_model);
     release_plates(s);
     s->blob.release();  // the other buffers are released by their destructors below
     for (auto& ln : s->lanes) {

@@ -110,6 +110,10 @@ struct mcrt_scene {
     // `n_texels`, the size of the scene's texel pool, is the third word for the same reason: a bake's stride check reads it
     // (tests/test_bake_abi.py).
     int n_texels = 0;
+    // The player model of a repaintable handle (mcrt.h: MCRT_SKIN_CLASSIC 0, MCRT_SKIN_SLIM 1), the fourth word: directly behind
+    // the three words the no-device tests already own, so their zeroed blocks stay classic handles.  The batch entries' argument
+    // checks do not read it (handles of both models may be mixed); what follows them does.
+    int skin_model = 0;
     uint32_t alpha_words = 0;
     uint32_t n_meshes = 0;
     bool posed = false;  // any mesh with MESH_ROTATED
@@ -175,6 +179,7 @@ struct mcrt_scene {
 
 static_assert(offsetof(mcrt_scene, device) == 0 && offsetof(mcrt_scene, skin_height) == sizeof(int), "mcrt_scene: device, then skin_height (see the member)");
 static_assert(offsetof(mcrt_scene, n_texels) == 2 * sizeof(int), "mcrt_scene: n_texels is the third word (see the member)");
+static_assert(offsetof(mcrt_scene, skin_model) == 3 * sizeof(int), "mcrt_scene: skin_model is the fourth word (see the member)");
 
 namespace mcrt_host {
 
@@ -331,8 +336,11 @@ void acquire_plates(mcrt_scene* s, mcrt::RenderParams* p, int n, bool capturing,
 // The device's repaint tables of a skin kind (64 / 32) — the 256 floats u8 / 255.0f, then per pool texel the mesh and the skin
 // pixel it is cut from (kernels.h: SkinPaintShape) — built at the kind's first repaintable handle on the device, one `users`
 // count per handle that holds them, freed by mcrt_trim() when nobody does.  nullptr: the allocation or the upload failed.
-const void* acquire_skin_tables(int device, int skin_height);
-void release_skin_tables(int device, int skin_height);
+// the kinds of the kind-keyed stores: 0 a classic 64x64 skin, 1 a 64x32 one, 2 a slim 64x64 one
+constexpr int kSkinKinds = 3;
+inline int skin_kind_index(int skin_height, int model) { return skin_height == 32 ? 1 : (model == 1 ? 2 : 0); }
+const void* acquire_skin_tables(int device, int skin_height, int model);
+void release_skin_tables(int device, int skin_height, int model);
 size_t pool_limit(int device);
 bool pool_scene(mcrt_scene* s);             // false: not kept, the caller destroys it
 mcrt_scene* take_pooled_scene(int device);  // device < 0: any
@@ -397,7 +405,7 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
 void apply_look(mcrt_scene_desc* desc, const mcrt_scene_desc* look);
 // The prefix [FlatHeader][FlatMesh x n] of the blob of the kind's white figure at pose / look (NULL: the builder's own), with
 // MESH_OPAQUE on every mesh as that figure has it.  No device work.
-int skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, std::vector<uint8_t>& table);
+int skin_view_table(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, std::vector<uint8_t>& table);
 
 }  // namespace mcrt_host
 

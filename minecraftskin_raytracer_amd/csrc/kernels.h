@@ -437,14 +437,17 @@ constexpr int kSkinMaxTexels = 3264;
 // n_texels uint16 (mesh << 12) | skin pixel index y * 64 + x, in pool order.
 struct SkinPaintShape {
     const void* tables;
-    int n_texels;        // 3264 (64x64) or 2016 (64x32)
+    int n_texels;        // 3264 (64x64), 3136 (64x64 slim) or 2016 (64x32)
     int n_meshes;        // 12 or 7
     int skin_bytes;      // 64 * height * 4
     uint32_t mesh_offset, texel_offset, alpha_offset, alpha_words;  // of the kind's blob (FlatHeader)
 };
+constexpr int kSkinBatchShapes = 2;  // the shapes one batch launch carries: the two 64x64 models may be mixed in it
 struct SkinPaintFrame {
     uint8_t* scene;       // the resident blob
     const uint8_t* skin;  // RGBA8, row-major, 4-byte aligned
+    int kind;             // a batch launch: which of its kSkinBatchShapes shapes this frame takes (0 or 1); else 0
+    int reserved[3];      // (32 bytes: a frame is two aligned scalar loads)
 };
 size_t skin_tables_bytes(int n_texels);
 
@@ -562,8 +565,9 @@ hipError_t launch_shot_ex_batch(const ShotFrame* d_table, int n_frames, const Sh
 // {width, height, 0, 0} into each of the n entries of d_bounds
 hipError_t launch_shot_bounds_init(int32_t* d_bounds, int n, int width, int height, hipStream_t stream);
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);
-// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
-hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; frame i takes
+// shapes[frame i's kind] — the two 64x64 models of one batch; a batch of one kind passes its shape twice
+hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape shapes[kSkinBatchShapes], hipStream_t stream);
 hipError_t launch_scene_view(const SceneViewFrame& f, const SceneViewShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_scene_view_batch(const SceneViewFrame* d_table, int n_frames, const SceneViewShape& shape, hipStream_t stream);

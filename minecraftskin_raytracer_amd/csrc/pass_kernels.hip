@@ -232,8 +232,26 @@ __device__ __forceinline__ void skin_paint_body(const SkinPaintFrame& __restrict
 }
 __global__ __launch_bounds__(kSkinBlock) void skin_paint_kernel(const SkinPaintFrame f, const SkinPaintShape sh) { skin_paint_body(f, sh); }
 using SkinPaintTable = const __attribute__((address_space(4))) SkinPaintFrame*;
-__global__ __launch_bounds__(kSkinBlock) void skin_paint_batch_kernel(SkinPaintTable table, const SkinPaintShape sh) {
+__global__ __launch_bounds__(kSkinBlock) void skin_paint_batch_kernel(SkinPaintTable table, const SkinPaintShape sh) {  // a batch of one kind
     skin_paint_body(*(const SkinPaintFrame*)(table + blockIdx.y), sh);
+}
+// A batch may mix the two 64x64 models (classic, slim): their tables, texel counts and alpha words differ, so both shapes
+// travel by value and a workgroup takes the one its frame names.  `kind` comes from the frame table through blockIdx.y and the
+// shapes from the kernel arguments — all uniform, scalar loads and scalar selects — so the texel loop's bound and the
+// `word < alpha_words` guard stay wave-uniform and every wave reaches both ballots.
+__global__ __launch_bounds__(kSkinBlock) void skin_paint_mixed_kernel(SkinPaintTable table, const SkinPaintShape sh0, const SkinPaintShape sh1) {
+    const SkinPaintFrame f = *(const SkinPaintFrame*)(table + blockIdx.y);
+    const bool second = f.kind != 0;
+    SkinPaintShape sh;
+    sh.tables = second ? sh1.tables : sh0.tables;
+    sh.n_texels = second ? sh1.n_texels : sh0.n_texels;
+    sh.n_meshes = second ? sh1.n_meshes : sh0.n_meshes;
+    sh.skin_bytes = second ? sh1.skin_bytes : sh0.skin_bytes;
+    sh.mesh_offset = second ? sh1.mesh_offset : sh0.mesh_offset;
+    sh.texel_offset = second ? sh1.texel_offset : sh0.texel_offset;
+    sh.alpha_offset = second ? sh1.alpha_offset : sh0.alpha_offset;
+    sh.alpha_words = second ? sh1.alpha_words : sh0.alpha_words;
+    skin_paint_body(f, sh);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1904,10 +1922,19 @@ hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shap
     hipLaunchKernelGGL(skin_paint_kernel, dim3(1), dim3(kSkinBlock), 0, stream, f, shape);
     return hipGetLastError();
 }
-hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape& shape, hipStream_t stream) {
+hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape shapes[kSkinBatchShapes], hipStream_t stream) {
     if (n_frames <= 0) return hipSuccess;
-    if (!skin_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(skin_paint_batch_kernel, dim3(1, static_cast<unsigned>(n_frames)), dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shape);
+    // both shapes are checked whatever the frames name: a workgroup may take either, and one image size fills the LDS image
+    if (!skin_shape_ok(shapes[0]) || !skin_shape_ok(shapes[1]) || shapes[0].skin_bytes != shapes[1].skin_bytes || n_frames > kLayersBatchMaxFrames)
+        return hipErrorInvalidValue;
+    const dim3 grid(1, static_cast<unsigned>(n_frames));
+    const SkinPaintShape &a = shapes[0], &b = shapes[1];
+    const bool one_kind = a.tables == b.tables && a.n_texels == b.n_texels && a.n_meshes == b.n_meshes && a.mesh_offset == b.mesh_offset &&
+                          a.texel_offset == b.texel_offset && a.alpha_offset == b.alpha_offset && a.alpha_words == b.alpha_words;
+    if (one_kind)  // the single-shape kernel, whatever the frames name
+        hipLaunchKernelGGL(skin_paint_batch_kernel, grid, dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shapes[0]);
+    else
+        hipLaunchKernelGGL(skin_paint_mixed_kernel, grid, dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shapes[0], shapes[1]);
     return hipGetLastError();
 }
 // ---- views of resident scenes (kernels.h) -------------------------------------------------------------

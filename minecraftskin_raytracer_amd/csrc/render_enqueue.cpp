@@ -959,7 +959,7 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
         if (scenes[i]->skin_height != 64 && scenes[i]->skin_height != 32)
             return fail(MCRT_ERR_INVALID, "a handle was not created by mcrt_scene_create_skin (only those hold the full mesh table a repaint writes)");
     for (int i = 1; i < n; ++i)
-        if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must be of one skin kind");
+        if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must take images of one size (one skin kind, but for the two 64x64 models)");
     const size_t image_bytes = static_cast<size_t>(64) * static_cast<size_t>(kind) * 4;
     if (stride_bytes < image_bytes) return fail(MCRT_ERR_INVALID, "skin_stride_bytes is smaller than the skin image");
     for (int i = 1; i < n; ++i)
@@ -973,20 +973,40 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
     HIP_TRY(hipSetDevice(device));
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a repaint cannot be recorded into a caller's graph (it takes the handles' events)");
     (void)hipGetLastError();
-    const FlatHeader* h = reinterpret_cast<const FlatHeader*>(scenes[0]->host_meshes.data());  // one kind: one blob layout
-    SkinPaintShape shape{};
-    shape.tables = scenes[0]->skin_tables;
-    shape.n_texels = static_cast<int>(h->n_texels), shape.n_meshes = static_cast<int>(h->n_meshes), shape.skin_bytes = static_cast<int>(image_bytes);
-    shape.mesh_offset = h->mesh_offset, shape.texel_offset = h->texel_offset, shape.alpha_offset = h->alpha_offset, shape.alpha_words = h->alpha_words;
+    // one image size: one blob layout per model.  shapes[k] is the layout of the handles of model k — classic 0, slim 1 — each
+    // from the header of the first such handle, the device's tables of its kind with it; a model the batch does not hold takes
+    // the other's shape, which no frame then names
+    SkinPaintShape shapes[kSkinBatchShapes] = {};
+    for (int i = 0; i < n; ++i) {
+        const mcrt_scene* s = scenes[i];
+        if (s->skin_model < 0 || s->skin_model >= kSkinBatchShapes) return fail(MCRT_ERR_INVALID, "a handle's model is neither classic nor slim");
+        SkinPaintShape& shape = shapes[s->skin_model];
+        if (shape.tables) continue;
+        const FlatHeader* h = reinterpret_cast<const FlatHeader*>(s->host_meshes.data());
+        shape.tables = s->skin_tables;
+        shape.n_texels = static_cast<int>(h->n_texels), shape.n_meshes = static_cast<int>(h->n_meshes), shape.skin_bytes = static_cast<int>(image_bytes);
+        shape.mesh_offset = h->mesh_offset, shape.texel_offset = h->texel_offset, shape.alpha_offset = h->alpha_offset, shape.alpha_words = h->alpha_words;
+    }
+    for (int k = 0; k < kSkinBatchShapes; ++k)
+        if (!shapes[k].tables) shapes[k] = shapes[1 - k];
     std::vector<SkinPaintFrame> frames(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
         mcrt_scene* s = scenes[i];
-        frames[static_cast<size_t>(i)] = SkinPaintFrame{static_cast<uint8_t*>(s->blob.ptr), d_skins + static_cast<size_t>(i) * stride_bytes};
-        if (const int rc = join_handle_chain(s, stream); rc != MCRT_OK) return rc;
+        SkinPaintFrame& f = frames[static_cast<size_t>(i)];
+        f = SkinPaintFrame{};
+        f.scene = static_cast<uint8_t*>(s->blob.ptr), f.skin = d_skins + static_cast<size_t>(i) * stride_bytes, f.kind = s->skin_model;
+        // every handle of a model has that model's layout: a frame writes n_texels texels and alpha_words words of ITS blob
+        const FlatHeader* h = reinterpret_cast<const FlatHeader*>(s->host_meshes.data());
+        const SkinPaintShape& shape = shapes[f.kind];
+        if (s->skin_tables != shape.tables || static_cast<int>(h->n_texels) != shape.n_texels || static_cast<int>(h->n_meshes) != shape.n_meshes ||
+            h->mesh_offset != shape.mesh_offset || h->texel_offset != shape.texel_offset || h->alpha_offset != shape.alpha_offset || h->alpha_words != shape.alpha_words)
+            return fail(MCRT_ERR_HIP, "internal error: a handle's blob does not have the layout of its skin kind");
     }
+    for (int i = 0; i < n; ++i)
+        if (const int rc = join_handle_chain(scenes[i], stream); rc != MCRT_OK) return rc;
     const int rc = launch_pass(
-        device, frames, stream, "repaint launches", [&](const SkinPaintFrame& f) { return launch_skin_paint(f, shape, stream); },
-        [&](const SkinPaintFrame* d_table, int m) { return launch_skin_paint_batch(d_table, m, shape, stream); });
+        device, frames, stream, "repaint launches", [&](const SkinPaintFrame& f) { return launch_skin_paint(f, shapes[f.kind], stream); },
+        [&](const SkinPaintFrame* d_table, int m) { return launch_skin_paint_batch(d_table, m, shapes, stream); });
     if (rc != MCRT_OK) return rc;
     // Should a record fail half way through the batch (the call then returns the error), the handles before it are chained
     // behind the repaint and the others are not: those keep their earlier `last_done`, which still orders their renders among
@@ -1016,7 +1036,7 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
         if (scenes[i]->skin_height != 64 && scenes[i]->skin_height != 32)
             return fail(MCRT_ERR_INVALID, "a handle was not created by mcrt_scene_create_skin (only those hold the full mesh table a view is flattened for)");
     for (int i = 1; i < n; ++i)
-        if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must be of one skin kind");
+        if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must take images of one size (one skin kind, but for the two 64x64 models)");
     for (int i = 1; i < n; ++i)
         if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
     {
@@ -1029,13 +1049,13 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a view change cannot be recorded into a caller's graph (it takes the handles' events)");
     (void)hipGetLastError();
     // the tables, on the host; each must have the layout of the blob it goes into
-    const size_t table_bytes = scenes[0]->host_meshes.size();  // one kind: one blob layout
+    const size_t table_bytes = scenes[0]->host_meshes.size();  // one image size: one prefix layout (the two 64x64 models share it)
     std::vector<uint8_t> staged(static_cast<size_t>(n) * table_bytes), table;
     for (int i = 0; i < n; ++i) {
         const mcrt_scene* s = scenes[i];
         const float* pose = poses ? poses[i] : (s->has_pose ? s->view_pose : nullptr);
         const mcrt_scene_desc* look = (looks && looks[i]) ? looks[i] : (s->has_look ? &s->view_look : nullptr);
-        if (const int rc = skin_view_table(kind, pose, look, table); rc != MCRT_OK) return rc;
+        if (const int rc = skin_view_table(kind, s->skin_model, pose, look, table); rc != MCRT_OK) return rc;  // the handle's own model
         bool same = table_bytes >= sizeof(FlatHeader) && table.size() == table_bytes && s->host_meshes.size() == table_bytes;
         if (same) {
             const FlatHeader* a = reinterpret_cast<const FlatHeader*>(table.data());

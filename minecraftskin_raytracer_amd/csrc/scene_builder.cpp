@@ -76,6 +76,16 @@ Rect face_rect(const PartBox& b, int face) {
 const PartBox kInnerBox[6] = {{0, 0, 8, 8, 8}, {16, 16, 8, 12, 4}, {40, 16, 4, 12, 4}, {32, 48, 4, 12, 4}, {0, 16, 4, 12, 4}, {16, 48, 4, 12, 4}};
 const PartBox kOuterBox[6] = {{32, 0, 8, 8, 8}, {16, 32, 8, 12, 4}, {40, 32, 4, 12, 4}, {48, 48, 4, 12, 4}, {0, 32, 4, 12, 4}, {0, 48, 4, 12, 4}};
 const int kLegacyMirrorOf[6] = {-1, -1, -1, 2, -1, 4};  // legacy left arm = right arm mirrored, left leg = right leg mirrored
+// The slim ("Alex") player model, 64x64 skins only — Minecraft's own; the reference knows the classic model alone.  It differs
+// from classic in the four arm boxes and nowhere else: the arms are 3 texels wide, unwrapped at the classic origins in
+// narrower rectangles (front and back 3x12, top and bottom 3x4, sides 4x12), which leaves the unwrap's last columns unread.
+const PartBox kSlimInnerArm[2] = {{40, 16, 3, 12, 4}, {32, 48, 3, 12, 4}};  // right, left
+const PartBox kSlimOuterArm[2] = {{40, 32, 3, 12, 4}, {48, 48, 3, 12, 4}};
+bool is_arm(int part) { return part == 2 || part == 3; }
+const PartBox& part_box(int model, bool outer, int part) {
+    if (model == MCRT_SKIN_SLIM && is_arm(part)) return (outer ? kSlimOuterArm : kSlimInnerArm)[part - 2];
+    return (outer ? kOuterBox : kInnerBox)[part];
+}
 
 PartTex unwrap(const SkinImage& img, const PartBox& b) {
     auto face = [&](int f) {
@@ -230,17 +240,25 @@ void add_box(OwnedDesc& o, const PartTex& tex, const float pos[3], const float s
     o.meshes.push_back(m);
 }
 
-OwnedDesc* assemble(const Skin& skin, const float pose[12]) {  // mesh_builder.cpp:145-202
+OwnedDesc* assemble(const Skin& skin, const float pose[12], int model = MCRT_SKIN_CLASSIC) {  // mesh_builder.cpp:145-202
     auto* o = new OwnedDesc();
     static const float position[6][3] = {{0, 28, 0}, {0, 18, 0}, {-6, 18, 0}, {6, 18, 0}, {-2, 6, 0}, {2, 6, 0}};
     static const float size[6][3] = {{8, 8, 8}, {8, 12, 4}, {4, 12, 4}, {4, 12, 4}, {4, 12, 4}, {4, 12, 4}};
     static const float pivot[6][3] = {{0, 24, 0}, {0, 18, 0}, {-6, 24, 0}, {6, 24, 0}, {-2, 12, 0}, {2, 12, 0}};
+    // a slim arm: 3 wide, x = -7 .. -4 and 4 .. 7 — flush with the body as the classic arm is — and its pivot on its own axis
+    static const float slim_position[2][3] = {{-5.5f, 18, 0}, {5.5f, 18, 0}};
+    static const float slim_size[3] = {3, 12, 4};
+    static const float slim_pivot[2][3] = {{-5.5f, 24, 0}, {5.5f, 24, 0}};
     for (int p = 0; p < 6; ++p) {
         float rx = pose ? pose[2 * p] : 0.0f, rz = pose ? pose[2 * p + 1] : 0.0f;
         bool posed = std::fabs(rx) > 0.01f || std::fabs(rz) > 0.01f;
-        add_box(*o, skin.inner[p], position[p], size[p], 0.0f, posed, pivot[p], rx, rz);
+        const bool slim_arm = model == MCRT_SKIN_SLIM && is_arm(p);
+        const float* at = slim_arm ? slim_position[p - 2] : position[p];
+        const float* sz = slim_arm ? slim_size : size[p];
+        const float* pv = slim_arm ? slim_pivot[p - 2] : pivot[p];
+        add_box(*o, skin.inner[p], at, sz, 0.0f, posed, pv, rx, rz);
         if (!fully_transparent(skin.outer[p]))
-            add_box(*o, skin.outer[p], position[p], size[p], 0.5f, posed, pivot[p], rx, rz);
+            add_box(*o, skin.outer[p], at, sz, 0.5f, posed, pv, rx, rz);
     }
     mcrt_scene_desc& d = o->desc;
     std::memset(&d, 0, sizeof d);
@@ -269,20 +287,20 @@ struct FaceSource {
     Rect rect;
     bool flipped;  // a legacy skin's mirrored left limb: the rectangle is read right to left (flip_h)
 };
-FaceSource face_source(int skin_height, int mesh, int face_slot) {
+FaceSource face_source(int skin_height, int model, int mesh, int face_slot) {
     int part, outer;
     if (skin_height == 64)
         part = mesh / 2, outer = mesh & 1;
     else
         part = mesh < 2 ? 0 : mesh - 1, outer = mesh == 1 ? 1 : 0;
     const int mirror_of = (skin_height == 32 && !outer) ? kLegacyMirrorOf[part] : -1;
-    const PartBox& box = outer ? kOuterBox[part] : kInnerBox[mirror_of >= 0 ? mirror_of : part];
+    const PartBox& box = part_box(model, outer != 0, (!outer && mirror_of >= 0) ? mirror_of : part);
     int face = face_slot;
     if (mirror_of >= 0 && (face == 2 || face == 3)) face = 5 - face;  // mirror_part: left = flip_h(right), right = flip_h(left)
     return FaceSource{face_rect(box, face), mirror_of >= 0};
 }
 
-Skin parse_skin(const uint8_t* rgba8, int w, int h) {  // w == 64, h == 64 or 32
+Skin parse_skin(const uint8_t* rgba8, int w, int h, int model = MCRT_SKIN_CLASSIC) {  // w == 64, h == 64 or 32; slim: h == 64
     SkinImage img;
     img.w = w;
     img.h = h;
@@ -292,26 +310,33 @@ Skin parse_skin(const uint8_t* rgba8, int w, int h) {  // w == 64, h == 64 or 32
     s.inner[0] = unwrap(img, kInnerBox[0]);
     s.outer[0] = unwrap(img, kOuterBox[0]);
     s.inner[1] = unwrap(img, kInnerBox[1]);
-    s.inner[2] = unwrap(img, kInnerBox[2]);
+    s.inner[2] = unwrap(img, part_box(model, false, 2));
     s.inner[4] = unwrap(img, kInnerBox[4]);
     if (h == 64) {
-        s.inner[3] = unwrap(img, kInnerBox[3]);
+        s.inner[3] = unwrap(img, part_box(model, false, 3));
         s.inner[5] = unwrap(img, kInnerBox[5]);
-        for (int p = 1; p < 6; ++p) s.outer[p] = unwrap(img, kOuterBox[p]);
+        for (int p = 1; p < 6; ++p) s.outer[p] = unwrap(img, part_box(model, true, p));
     } else {
         s.inner[3] = mirror_part(s.inner[kLegacyMirrorOf[3]]);
         s.inner[5] = mirror_part(s.inner[kLegacyMirrorOf[5]]);
     }
     return s;
 }
+
+bool model_ok(int skin_height, int model) {  // slim exists for 64x64 skins only
+    return model == MCRT_SKIN_CLASSIC || (model == MCRT_SKIN_SLIM && skin_height == 64);
+}
+const char* const kBadModel = "model must be MCRT_SKIN_CLASSIC, or MCRT_SKIN_SLIM with a 64x64 skin";
 }  // namespace
 
-// The figure mcrt_build_skin_scene builds from an all-(255,255,255,255) skin of the kind (64 / 32) — every part present — at
-// `pose`: what a view of a repaintable handle is flattened from (api.cpp).  The white skin is parsed once per kind and process.
-extern "C" __attribute__((visibility("hidden"))) mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, const float pose[12]) {
-    static const Skin white[2] = {parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64),
-                                  parse_skin(std::vector<uint8_t>(64 * 32 * 4, 255).data(), 64, 32)};
-    return &assemble(white[skin_height == 32 ? 1 : 0], pose)->desc;
+// The figure mcrt_build_skin_scene_model builds from an all-(255,255,255,255) skin of the kind (64 / 32, classic / slim) — every
+// part present — at `pose`: what a view of a repaintable handle is flattened from (api.cpp).  The white skin is parsed once
+// per kind and process.
+extern "C" __attribute__((visibility("hidden"))) mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, int model, const float pose[12]) {
+    static const Skin white[3] = {parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64),
+                                  parse_skin(std::vector<uint8_t>(64 * 32 * 4, 255).data(), 64, 32),
+                                  parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64, MCRT_SKIN_SLIM)};
+    return &assemble(white[skin_height == 32 ? 1 : (model == MCRT_SKIN_SLIM ? 2 : 0)], pose, model)->desc;
 }
 
 extern "C" {
@@ -322,13 +347,37 @@ int mcrt_build_skin_scene(const uint8_t* rgba8, int w, int h, const float pose[1
     return MCRT_OK;
 }
 
+int mcrt_build_skin_scene_model(const uint8_t* rgba8, int w, int h, int model, const float pose[12], mcrt_scene_desc** out) {
+    if (!rgba8 || !out || w != 64 || (h != 64 && h != 32) || !model_ok(h, model)) return MCRT_ERR_INVALID;
+    *out = &assemble(parse_skin(rgba8, w, h, model), pose, model)->desc;
+    return MCRT_OK;
+}
+
+int mcrt_skin_model_of(const uint8_t* rgba8, int w, int h) {
+    if (!rgba8) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument"), -1;
+    if (w != 64 || (h != 64 && h != 32)) return mcrt_detail_fail(MCRT_ERR_INVALID, "a skin image is 64x64 or 64x32"), -1;
+    if (h != 64) return MCRT_SKIN_CLASSIC;
+    // the columns a slim unwrap leaves unused, of the inner right arm and the inner left arm
+    static const Rect unused[4] = {{50, 16, 2, 4}, {54, 20, 2, 12}, {42, 48, 2, 4}, {46, 52, 2, 12}};
+    for (const Rect& r : unused)
+        for (int y = r.y; y < r.y + r.h; ++y)
+            for (int x = r.x; x < r.x + r.w; ++x)
+                if (rgba8[4 * (static_cast<size_t>(y) * 64 + x) + 3] != 0) return MCRT_SKIN_CLASSIC;
+    return MCRT_SKIN_SLIM;
+}
+
 int mcrt_skin_texel(int skin_height, int mesh, int face_slot, int tx, int ty, int* skin_x, int* skin_y) {
+    return mcrt_skin_texel_model(skin_height, MCRT_SKIN_CLASSIC, mesh, face_slot, tx, ty, skin_x, skin_y);
+}
+
+int mcrt_skin_texel_model(int skin_height, int model, int mesh, int face_slot, int tx, int ty, int* skin_x, int* skin_y) {
     if (!skin_x || !skin_y) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
     if (skin_height != 64 && skin_height != 32) return mcrt_detail_fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    if (!model_ok(skin_height, model)) return mcrt_detail_fail(MCRT_ERR_INVALID, kBadModel);
     if (face_slot < 0 || face_slot > 5) return mcrt_detail_fail(MCRT_ERR_INVALID, "face_slot must be 0..5");
     if (skin_height == 64 && (mesh < 0 || mesh >= 12)) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..11 for a 64x64 skin");
     if (skin_height == 32 && (mesh < 0 || mesh >= 7)) return mcrt_detail_fail(MCRT_ERR_INVALID, "mesh must be 0..6 for a 64x32 skin");
-    const FaceSource src = face_source(skin_height, mesh, face_slot);
+    const FaceSource src = face_source(skin_height, model, mesh, face_slot);
     const Rect& r = src.rect;
     if (tx < 0 || tx >= r.w || ty < 0 || ty >= r.h) return mcrt_detail_fail(MCRT_ERR_INVALID, "texel outside the face's region");
     *skin_x = r.x + (src.flipped ? r.w - 1 - tx : tx);  // flip_h
@@ -339,12 +388,12 @@ int mcrt_skin_texel(int skin_height, int mesh, int face_slot, int tx, int ty, in
 // The texel pool of the full-table figure of a skin kind, in pool order — assemble()'s meshes with every part present, their
 // six faces in slot order, a face's texels row-major, which is the order add_box hands the textures to the flattener in —
 // by the tables above: per texel its mesh and the skin pixel y * 64 + x it is cut from.  Returns the count.
-__attribute__((visibility("hidden"))) int mcrt_detail_skin_pool(int skin_height, int32_t* pixel, int32_t* mesh_of, int capacity) {
+__attribute__((visibility("hidden"))) int mcrt_detail_skin_pool(int skin_height, int model, int32_t* pixel, int32_t* mesh_of, int capacity) {
     const int n_meshes = skin_height == 64 ? 12 : 7;
     int n = 0;
     for (int mesh = 0; mesh < n_meshes; ++mesh)
         for (int face = 0; face < 6; ++face) {
-            const FaceSource src = face_source(skin_height, mesh, face);
+            const FaceSource src = face_source(skin_height, model, mesh, face);
             const Rect& r = src.rect;
             for (int ty = 0; ty < r.h; ++ty)
                 for (int tx = 0; tx < r.w; ++tx, ++n) {
@@ -356,10 +405,13 @@ __attribute__((visibility("hidden"))) int mcrt_detail_skin_pool(int skin_height,
     return n;
 }
 
-int mcrt_skin_pool_map(int skin_height, int32_t* out, int capacity) {
+int mcrt_skin_pool_map(int skin_height, int32_t* out, int capacity) { return mcrt_skin_pool_map_model(skin_height, MCRT_SKIN_CLASSIC, out, capacity); }
+
+int mcrt_skin_pool_map_model(int skin_height, int model, int32_t* out, int capacity) {
     if (!out) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
     if (skin_height != 64 && skin_height != 32) return mcrt_detail_fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
-    return mcrt_detail_skin_pool(skin_height, out, nullptr, capacity < 0 ? 0 : capacity);
+    if (!model_ok(skin_height, model)) return mcrt_detail_fail(MCRT_ERR_INVALID, kBadModel);
+    return mcrt_detail_skin_pool(skin_height, model, out, nullptr, capacity < 0 ? 0 : capacity);
 }
 
 int mcrt_build_default_scene(const float pose[12], mcrt_scene_desc** out) {

@@ -10,6 +10,16 @@ warm-up, repeated with the order of the ways alternated in one process:
           alone, and both together — what the repaint adds on the device
 
     python tools/gpu_skin_paint.py [--n 64,256] [--reps 7] [--warmup 3] [--json out.json]
+
+--mixed: the farm's real stream instead, N skins of which every second one is for the slim player model, the ways alternated
+in the same manner:
+
+  classic      SkinBatch.render of N classic skins (the case before the slim model: what the mixed launch may not slow down)
+  mixed        SkinBatch(N, slim=True).render(models=...): one upload, ONE repaint launch over classic and slim handles, one render
+  two_batches  the alternative: a classic SkinBatch of the N/2 classic skins, then a slim one of the N/2 slim skins
+  device       by device events: the repaint launch of N classic handles, of N mixed handles, and the two launches of the halves
+
+    python tools/gpu_skin_paint.py --mixed [--n 64] [--reps 7] [--warmup 3] [--json out.json]
 """
 import argparse
 import json
@@ -41,13 +51,106 @@ def summary(ms):
     return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
 
 
+def alternated(ways, reps):
+    """name -> the milliseconds of `reps` calls of each way (a callable that returns ms), the order reversed every other round."""
+    times = {k: [] for k in ways}
+    for r in range(reps):
+        for k in (list(ways) if r % 2 == 0 else list(ways)[::-1]):
+            times[k].append(ways[k]())
+    return times
+
+
+def mixed(a):
+    cfg = abi.Config()
+    pose = M.getBuiltinPoses()[1]
+    results = []
+    for n in [int(v) for v in a.n.split(",")]:
+        half = n // 2
+        n = 2 * half
+        models = ["classic", "slim"] * half
+        skins = skins_of(n)
+        skins[1::2, M.skins.slim_unused_mask(), 3] = 0  # every second skin is a slim one
+        assert [M.skin_model(s) for s in skins] == models
+        both = M.SkinBatch(n, "S64", pose, slim=True)
+        classic_half, slim_half = M.SkinBatch(half, "S64", pose), M.SkinBatch(half, "S64", pose, slim=True)
+        stream = torch.cuda.current_stream()
+
+        def host(fn):
+            def timed():
+                t = time.perf_counter()
+                fn()
+                return (time.perf_counter() - t) * 1e3
+            return timed
+
+        def two_batches():
+            return classic_half.render(skins[0::2], cfg, rgba8=True), slim_half.render(skins[1::2], cfg, rgba8=True, models=["slim"] * half)
+
+        ways = {"classic": host(lambda: both.render(skins, cfg, rgba8=True)),
+                "mixed": host(lambda: both.render(skins, cfg, rgba8=True, models=models)),
+                "two_batches": host(two_batches)}
+        for _ in range(a.warmup):
+            for w in ways.values():
+                w()
+        got, (c, s) = both.render(skins, cfg, rgba8=True, models=models), two_batches()
+        if got[0::2].tobytes() != c.tobytes() or got[1::2].tobytes() != s.tobytes():
+            raise SystemExit(f"N={n}: the mixed batch differs from the two batches")
+        times = alternated(ways, a.reps)
+
+        d_skins = torch.from_numpy(skins).cuda()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        chosen = [both.slim_scenes[i] if m == "slim" else both.scenes[i] for i, m in enumerate(models)]
+        halves = (chosen[0::2], chosen[1::2])
+
+        def events(fn):
+            def timed():
+                t0.record(stream)
+                fn()
+                t1.record(stream)
+                t1.synchronize()
+                return t0.elapsed_time(t1)
+            return timed
+
+        def two_launches():
+            M.set_skins_batch_device(halves[0], d_skins.data_ptr(), 2 * skins[0].nbytes, stream.cuda_stream)
+            M.set_skins_batch_device(halves[1], d_skins.data_ptr() + skins[0].nbytes, 2 * skins[0].nbytes, stream.cuda_stream)
+
+        dev = {"classic": events(lambda: M.set_skins_batch_device(both.scenes, d_skins.data_ptr(), stream=stream.cuda_stream)),
+               "mixed": events(lambda: M.set_skins_batch_device(chosen, d_skins.data_ptr(), stream=stream.cuda_stream)),
+               "two_launches": events(two_launches)}
+        for _ in range(a.warmup + 2):
+            for w in dev.values():
+                w()
+        torch.cuda.synchronize()
+        dtimes = alternated(dev, a.reps)
+        row = {"n": n, "slim": half, "config": "default 256x256, rgba8", "host_to_host": {k: summary(v) for k, v in times.items()},
+               "repaint_device_events": {k: summary(v) for k, v in dtimes.items()}}
+        results.append(row)
+        for title, part in (("host to host", "host_to_host"), ("repaint launch, device events", "repaint_device_events")):
+            line = f"N={n:4d} ({half} slim)  {title}:"
+            for k, v in row[part].items():
+                line += f"  {k} {v['ms_median']:.4f} ms ({v['ms_min']:.4f}-{v['ms_max']:.4f})"
+            print(line, flush=True)
+        for b in (both, classic_half, slim_half):
+            b.close()
+        del d_skins
+        torch.cuda.synchronize()
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", default="64,256")
+    ap.add_argument("--n", default="")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--json", default="")
+    ap.add_argument("--mixed", action="store_true")
     a = ap.parse_args()
+    a.n = a.n or ("64" if a.mixed else "64,256")
+    if a.mixed:
+        return mixed(a)
     cfg = abi.Config()  # 256x256, 3 bounces, 1 spp, soft shadows, tile 32
     pose = M.getBuiltinPoses()[1]
     results = []
