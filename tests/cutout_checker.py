@@ -90,7 +90,7 @@ def compose_ex(F, vis, R, dR, occ, page, shot: abi.Shot) -> np.ndarray:
     af = _f32(ONE - keep, "af")
     A = _f32(F[..., 3] + _f32(af * under, "af * u"), "A")
     through, seen = af == 0, A > 0
-    with np.errstate(divide="ignore", invalid="ignore"):  # (the quotients of the pixels that take another branch)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):  # (the quotients of the pixels that take another branch)
         for c in range(3):
             fp = _f32(R[..., c] * ar, "R.c * ar")
             if colored:
@@ -121,14 +121,17 @@ def over(out, page) -> np.ndarray:
     return out[..., :3].astype(np.float64) * a + np.asarray(page, np.float64) * (1.0 - a)
 
 
-def expected_shot_ex(oracle, sd, cfg, shot: abi.Shot, ground) -> dict:
+def expected_shot_ex(oracle, sd, cfg, shot: abi.Shot, ground, pass_cfg=None, threads=None) -> dict:
     """{"F", "vis", "R", "dR", "occ" (1.0 everywhere without the term), "page" (None with the transparent page), "out" (H, W, 4)
-    float32, "rgba8" (H, W, 4) uint8, "bounds" (4,) int32 — the box of out's alpha} — every input from the CPU oracle."""
-    F, _ = S.transparent_oracle().render(sd.ptr, cfg, "transparent", threads=T.threads())
-    vis = G.expected_ground(oracle, sd, cfg, ground)["visibility"]
-    refl = R_.expected_reflection(oracle, sd, cfg, ground)
+    float32, "rgba8" (H, W, 4) uint8, "bounds" (4,) int32 — the box of out's alpha} — every input from the CPU oracle.
+    pass_cfg: the config of the passes where cfg's is outside their limits (a shot that skips a pass accepts such a config; it
+    does not read the pass's plane).  threads: of the transparent checker (default: transparent_checker.threads())."""
+    pass_cfg = pass_cfg or cfg
+    F, _ = S.transparent_oracle().render(sd.ptr, cfg, "transparent", threads=threads or T.threads())
+    vis = G.expected_ground(oracle, sd, pass_cfg, ground)["visibility"]
+    refl = R_.expected_reflection(oracle, sd, pass_cfg, ground)
     if shot.floorOcclusion > 0:
-        occ = GO.expected_ground_occlusion(oracle, sd, cfg, ground)["occlusion"]
+        occ = GO.expected_ground_occlusion(oracle, sd, pass_cfg, ground)["occlusion"]
     else:
         occ = np.ones((cfg.height, cfg.width), f32)
     page = None if shot.page == "transparent" else S.page_plane(oracle, sd, cfg, shot)

@@ -37,7 +37,7 @@ f32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MESH_ROTATED, MESH_OPAQUE = 2, 32  # flat_scene.h
 SKIN_SENTINEL = 0xA5
-N_MESHES = {"S64": 12, "S32": 7}
+N_MESHES = {"S64": 12, "S32": 7, "slim": 12}
 BLOCK_SIZE = 6
 
 CONFIGS = {
@@ -72,7 +72,14 @@ _LAYOUT = {}
 
 
 def layout(kind) -> dict:
-    """{"pool": (n,) skin pixel index y * 64 + x per pool texel, "mesh", "face": (n,) per pool texel} of the full table of `kind`."""
+    """{"pool": (n,) skin pixel index y * 64 + x per pool texel, "mesh", "face": (n,) per pool texel} of the full table of `kind`:
+    "S64", "S32", or "slim" — the 64 x 64 skin on the slim model, from slim_checker's restated tables."""
+    if kind == "slim" and kind not in _LAYOUT:
+        import slim_checker
+
+        rows = slim_checker.pool_rows("slim")
+        assert len(rows) == slim_checker.N_TEXELS["slim"]
+        _LAYOUT[kind] = {"pool": rows[:, 4].astype(np.int64), "mesh": rows[:, 0].copy(), "face": rows[:, 1].copy()}
     if kind not in _LAYOUT:
         h = 64 if kind == "S64" else 32
         table = M.texel_table(S.full_table_scene(np.full((h, 64, 4), 255, np.uint8), np.zeros(12, f32)))
@@ -87,8 +94,8 @@ def layout(kind) -> dict:
 
 
 def make_skin(g, kind, drop=None) -> np.ndarray:
-    """drop: how many outer parts are cleared whole (default: drawn)."""
-    h = 64 if kind == "S64" else 32
+    """drop: how many outer parts are cleared whole (default: drawn).  kind "slim": a 64 x 64 skin cut by the slim model's layout."""
+    h = 32 if kind == "S32" else 64
     lay = layout(kind)
     a = g.integers(0, 256, (h, 64, 4), dtype=np.uint8)
     mode = int(g.integers(4))
@@ -105,7 +112,7 @@ def make_skin(g, kind, drop=None) -> np.ndarray:
         alpha = g.integers(0, 256, (h, 64))
     flat = alpha.reshape(-1).astype(np.uint8)
     n_meshes = N_MESHES[kind]
-    outer = [m for m in range(n_meshes) if m % 2 == 1] if kind == "S64" else [1]
+    outer = [m for m in range(n_meshes) if m % 2 == 1] if kind != "S32" else [1]
     n_drop = (int(g.integers(len(outer) + 1)) if g.random() < 0.8 else 0) if drop is None else min(int(drop), len(outer))
     dropped = set(g.choice(outer, n_drop, replace=False).tolist())
     for m in range(n_meshes):

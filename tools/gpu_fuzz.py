@@ -44,6 +44,13 @@ The studio shot (tests/shot_fuzz_cases.py; the runs and comparisons are those of
                shot_checker.compose; odd seeds are make_shot_case(seed): 1 ... 4 scenes of random skins and views, two calls through
                the batched, single, host and PNG forms against the CPU oracle alone; the summary records the pixels compared and
                the oracle's totals of shot_checker.classes
+The shot as a cut-out (tests/cutout_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_cutout_fuzz.py):
+  cutout       even seeds k are make_blend_case(k // 2): the shot mode's planes with vis above 1 and below 0 and an occlusion plane
+               from the same classes, o and the shadow colour from classes of their own, the transparent page at five places of
+               eight (an opaque page with a black shadow and o > 0 takes the _occ entry), boxes asked for behind a lead, against
+               cutout_checker.compose_ex and bounds_of; odd seeds k are make_shot_case(k // 2): 1 ... 4 scenes (S64, S32, slim), two
+               calls through the batched, single, host, PNG, cropped PNG and SkinBatch forms with the refusals beside them, against
+               the CPU oracle alone; the summary records the pixels compared and the oracle's totals of cutout_checker.classes
 The ground-occlusion pass (tests/ground_occlusion_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_ground_occlusion_fuzz.py):
   ground_occlusion   seed k is make_case(k): skins and 48 ... 80-mesh box scenes, posed and not, scaled by 1e-3 ... 1e3, cameras above,
                below and grazing the plane, planes at, below, inside and above the scene, 1 ... 113 samples, radii from 0 to larger than
@@ -65,7 +72,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident", "shot", "ground_occlusion") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident", "shot", "cutout", "ground_occlusion") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -288,10 +295,19 @@ def resident_sweep():
     sys.exit(1 if bad else 0)
 
 
-def shot_sweep():
+def shot_sweep(cutout=False):
     import tempfile
-    import shot_checker as S, shot_fuzz_cases as SF, test_gpu_shot_fuzz as T
+    import shot_checker as S, test_gpu_shot_fuzz as T
     from minecraftskin_raytracer_amd._lib import McrtError
+
+    if cutout:  # the same sweep over the cut-out's cases, runs and classes
+        import cutout_checker as X, cutout_fuzz_cases as SF, test_gpu_cutout_fuzz as TC
+        run_blend, run_shot, class_names = TC.run_cutout_blend_case, TC.run_cutout_shot_case, X.CLASSES
+        classes_of = lambda case, exp: X.classes(exp, case["calls"][0]["shot"])  # noqa: E731
+    else:
+        import shot_fuzz_cases as SF
+        run_blend, run_shot, class_names = T.run_blend_case, T.run_shot_case, S.CLASSES
+        classes_of = lambda case, exp: S.classes(exp)  # noqa: E731
 
     # the oracle's planes of the whole shots (the odd seeds) are made ahead of the device by worker processes (forked before the
     # device is first used; they never use it), in the order of the seeds
@@ -301,28 +317,31 @@ def shot_sweep():
     S.transparent_oracle()  # built once, before the fork
     pool = multiprocessing.get_context("fork").Pool(workers)
     seeds = range(first, first + count)
-    ahead = pool.imap(SF.worker_shot_expectation, [s for s in seeds if s % 2])
+    # (a cut-out case's place in its block is its seed modulo 8 or 4, so there seed k stands for case k // 2 of its kind: every
+    # place is met; the shot mode keeps its numbering)
+    case_seed = (lambda s: s // 2) if cutout else (lambda s: s)  # noqa: E731
+    ahead = pool.imap(SF.worker_shot_expectation, [case_seed(s) for s in seeds if s % 2])
     shared = T._coloured_handles(M, [(0.125, 0.5, 0.75, 1.0), (0.9, 0.1, 0.3, 1.0), (0.0, 1.0, 0.25, 1.0)])
     tmp = tempfile.mkdtemp(prefix="fuzz_shot_")
     bad = blends = shots = pixels = frames = 0
-    total = np.zeros(len(S.CLASSES), np.int64)
+    total = np.zeros(len(class_names), np.int64)
     t0 = time.time()
     for k, seed in enumerate(seeds):
         try:
             if seed % 2 == 0:
-                case = SF.make_blend_case(seed)
-                lines = T.run_blend_case(M, shared, case)
+                case = SF.make_blend_case(case_seed(seed))
+                lines = run_blend(M, shared, case)
                 blends += 1; pixels += 3 * case["n"] * case["w"] * case["h"]
             else:
-                case = SF.make_shot_case(seed)
+                case = SF.make_shot_case(case_seed(seed))
                 exps = next(ahead)
-                lines = T.run_shot_case(M, case, exps, tmp)
+                lines = run_shot(M, case, exps, tmp)
                 shots += 1; frames += sum(len(per_scene) for per_scene in exps)
                 for exp in exps[0]:
-                    total += np.asarray(S.classes(exp))
+                    total += np.asarray(classes_of(case, exp))
         except (McrtError, RuntimeError) as e:  # the library's, or torch's at a host wait
-            print(f"HIP ERROR shot seed {seed}: {e}", flush=True)
-            print(f"fuzz shot: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
+            print(f"HIP ERROR {mode} seed {seed}: {e}", flush=True)
+            print(f"fuzz {mode}: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
             pool.terminate()
             sys.exit(2)
         if lines:
@@ -334,8 +353,8 @@ def shot_sweep():
         h.close()
     import shutil
     shutil.rmtree(tmp, ignore_errors=True)
-    print(f"fuzz shot: {count} cases from seed {first}: {bad} mismatch(es); {blends} blend cases with {pixels} pixels blended, {shots} shot cases "
-          f"with {frames} frames; {time.time() - t0:.0f} s; the oracle holds " + ", ".join(f"{int(t)} {name}" for name, t in zip(S.CLASSES, total)))
+    print(f"fuzz {mode}: {count} cases from seed {first}: {bad} mismatch(es); {blends} blend cases with {pixels} pixels blended, {shots} shot cases "
+          f"with {frames} frames; {time.time() - t0:.0f} s; the oracle holds " + ", ".join(f"{int(t)} {name}" for name, t in zip(class_names, total)))
     pool.terminate()
     sys.exit(1 if bad else 0)
 
@@ -446,6 +465,8 @@ if mode == "resident":
     resident_sweep()
 if mode == "shot":
     shot_sweep()
+if mode == "cutout":
+    shot_sweep(cutout=True)
 if len(sys.argv) > 3 and sys.argv[3] == "bundle":
     make_case = make_bundle_case
 if len(sys.argv) > 3 and sys.argv[3] == "wide":
