@@ -1032,6 +1032,12 @@ typedef struct mcrt_hit {
  * left it) into out.  Returns the blob's size in bytes — never below 192, the header's size — and copies min(size, capacity);
  * on failure an MCRT_ERR_* code (all of them below 192; a NULL argument: MCRT_ERR_INVALID). */
 int mcrt_probe_scene_blob(mcrt_scene* scene, void* out, size_t capacity);
+/* Waits for the device, then reads the work units that the last pass of the handle's last render queued on its first lane:
+ * per unit its record (4 x uint32: owned tile | block flag << 31, then a pixel range {first, end} of the tile's row-major
+ * order or a block {x | y << 16, width | height << 16} inside the tile, then its first sample slot) and its primary hits.
+ * Returns the number of units and copies min(units, capacity) entries into each array that is not NULL; 0 before the first
+ * render; on failure an MCRT_ERR_* code. */
+int mcrt_probe_units(mcrt_scene* scene, uint32_t* records, uint32_t* hits, int capacity);
 /* intersectScene (intersection.cpp:408-421) for n rays; rays = n*6 floats (origin, direction) */
 int mcrt_probe_intersect(mcrt_scene* scene, const float* rays, int n, mcrt_hit* out);
 /* RayTracer::traceRay(ray, scene, depth, maxBounces, ShadingParams{}, &cfg) (raytracer.cpp:82-148)

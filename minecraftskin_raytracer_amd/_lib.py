@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_reflection_device", "mcrt_render_reflection_batch_device", "mcrt_render_reflection",
     "mcrt_render_light_device", "mcrt_render_light_batch_device", "mcrt_render_light",
     "mcrt_scene_create_skin", "mcrt_scene_set_skin_device", "mcrt_scene_set_skins_batch_device", "mcrt_scene_set_skin",
-    "mcrt_skin_pool_map", "mcrt_probe_scene_blob",
+    "mcrt_skin_pool_map", "mcrt_probe_scene_blob", "mcrt_probe_units",
     "mcrt_bake_light_device", "mcrt_bake_light_batch_device", "mcrt_bake_light", "mcrt_bake_texel_table", "mcrt_scene_texels",
     "mcrt_scene_set_view", "mcrt_scene_set_view_device", "mcrt_scene_set_views_batch_device", "mcrt_skin_view_table",
     "mcrt_shot_init", "mcrt_shot_scratch_bytes", "mcrt_composite_shot_batch_device", "mcrt_render_shot_batch_device",

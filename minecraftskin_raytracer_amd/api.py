@@ -827,6 +827,19 @@ class DeviceScene:
             raise McrtError(abi.MCRT_ERR_HIP, lib.mcrt_last_error().decode("utf-8", "replace"))
         return buf.raw
 
+    def units(self) -> dict:
+        """The work units of the last pass of the handle's last render, first lane (mcrt_probe_units), after waiting for the
+        device: ``{"records": (n, 4) uint32, "hits": (n,) uint32}``."""
+        fn = load().mcrt_probe_units  # bound here: a build selected with MCRT_LIB may predate it
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        n = fn(self._h, None, None, 0)
+        if n < 0:
+            raise McrtError(n, load().mcrt_last_error().decode("utf-8", "replace"))
+        rec, hits = np.zeros((n, 4), np.uint32), np.zeros(n, np.uint32)
+        if n and fn(self._h, rec.ctypes.data, hits.ctypes.data, n) != n:
+            raise McrtError(abi.MCRT_ERR_HIP, load().mcrt_last_error().decode("utf-8", "replace"))
+        return {"records": rec, "hits": hits}
+
     def close(self):
         if self._h:
             load().mcrt_scene_destroy(self._h)

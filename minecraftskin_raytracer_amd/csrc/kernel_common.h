@@ -45,6 +45,37 @@ struct TileGeom {
     int frame_tile;  // row-major index of the tile in the whole frame (its slot in a background or draw plate, kernels.h)
 };
 
+// ---------------------------------------------------------------------------------------------
+// work units of a touched tile (WaveSpace::units): a pixel range of the tile's row-major order, or a block of the tile
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kUnitBlock = 1u << 31;  // in .x of a unit record: the record is a block
+__device__ __forceinline__ int unit_tile(const uint4& ud) { return static_cast<int>(ud.x & ~kUnitBlock); }
+__device__ __forceinline__ uint32_t unit_pixels(const uint4& ud) { return (ud.x & kUnitBlock) ? (ud.z & 0xffffu) * (ud.z >> 16) : ud.z - ud.y; }
+// Pixel k (< unit_pixels) of unit ud, in the unit's own order — a range: the tile's row-major order; a block: the block's —
+// as (lx, ly) in its tile tg.  The one place that knows the two forms: a sample's draws sit at ((ly * tg.w + lx) * spp + s) *
+// draws_per_sample of the tile's stream whichever unit holds the pixel, and its slot is the unit's slot base + k * spp + s.
+// Both forms are one: pixel k lies k + koff pixels into a rectangle that is `by_w.d` wide and starts at (x0, y0) of the tile —
+// the block itself, or the whole tile with koff = the range's first pixel.  A kernel that walks a unit forms the map once.
+struct UnitMap {
+    uint32_t koff, x0, y0;
+    UDiv by_w;
+    __device__ __forceinline__ UnitMap(const uint4& ud, const TileGeom& tg)
+        : koff((ud.x & kUnitBlock) ? 0u : ud.y), x0((ud.x & kUnitBlock) ? (ud.y & 0xffffu) : 0u), y0((ud.x & kUnitBlock) ? (ud.y >> 16) : 0u),
+          by_w((ud.x & kUnitBlock) ? (ud.z & 0xffffu) : static_cast<uint32_t>(tg.w)) {}
+    // column and row of pixel k in that rectangle: (lx, ly) = (x0 + col, y0 + row)
+    __device__ __forceinline__ void rel(uint32_t k, uint32_t& col, uint32_t& row) const {
+        const uint32_t q = k + koff;
+        row = by_w.div(q);
+        col = q - row * by_w.d;
+    }
+    __device__ __forceinline__ void pixel(uint32_t k, int& lx, int& ly) const {
+        uint32_t col, row;
+        rel(k, col, row);
+        lx = static_cast<int>(x0 + col);
+        ly = static_cast<int>(y0 + row);
+    }
+};
+__device__ __forceinline__ void unit_pixel(const uint4& ud, const TileGeom& tg, uint32_t k, int& lx, int& ly) { UnitMap(ud, tg).pixel(k, lx, ly); }
 // RGBA8 quantisation `(u8)(clamp(c,0,1)*255+0.5)` (image_writer.cpp:18-22 ≡ image.cpp:31-36)
 __device__ __forceinline__ uchar4 quantize_pixel(float4 c) {
     uchar4 q;

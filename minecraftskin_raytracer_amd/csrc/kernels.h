@@ -34,7 +34,9 @@ struct WaveSpace {
     float4* scol;           // [cap] per-sample colour, where the sample did not start a chain (miss, background)
     uint32_t* end;          // [cap] per sample: 0 = the colour is in `scol`; else how its chain ended:
                             //       (records of the chain << 1) | (1 = stopped at maxBounces, 0 = the last reflection ray missed)
-    uint4* units;           // units of the tiles meshes can touch: {owned tile, first pixel, end pixel, slot base}
+    uint4* units;           // queued units of the tiles meshes can touch, in one of two forms (kernel_common.h, unit_pixel):
+                            //       a pixel range {owned tile, first pixel, end pixel, slot base}, or
+                            //       a block {owned tile | kUnitBlock, lx0 | ly0 << 16, width | height << 16, slot base}
     uint32_t* unit_hits;    // per unit: its primary hits (their records sit at the front of the unit's slot range)
     unsigned long long* tile_mask;  // per owned tile: meshes whose screen bound touches it
     float* tile_draws;      // [touched tiles (bg_in_plan) or all tiles of the batch][draws_stride] a tile's mt19937 draws, as uniform floats
@@ -111,7 +113,10 @@ struct RenderParams {
     int stream_parts;      // a tile's mt19937 stream can be generated in this many parts (1, 2 or 4),
     int stream_part_twists;  //   of this many 624-word twists each, from engine states kept with the tile seeds (tile_rng:
                            //   owned_tiles x stream_parts x 624 words)
-    int parts_per_tile;    // a tile that meshes can touch is split into this many pixel-aligned work units
+    int parts_per_tile;    // a tile that meshes can touch is split into at most this many work units
+    int unit_blocks;       // 1: the units of a tile are the blocks of a unit_gx x unit_gy grid, unit_bw x unit_bh pixels each (clipped
+                           //    with the tile; choose_parts_per_tile); 0 (MCRT_UNIT_BLOCKS=0, renderTile rectangles): pixel ranges
+    int unit_gx, unit_gy, unit_bw, unit_bh;
     int lds_alpha_words;   // dynamic LDS: alpha-predicate words staged per workgroup
     int lds_face_entries;  // dynamic LDS: n_meshes * 6 face-table entries
     int scene_in_lds;      // 1 when both tables fit the LDS budget (otherwise the kernels read HBM)

@@ -44,6 +44,21 @@ int mcrt_probe_scene_blob(mcrt_scene* s, void* out, size_t capacity) {
     return static_cast<int>(bytes);
 }
 
+int mcrt_probe_units(mcrt_scene* s, uint32_t* records, uint32_t* hits, int capacity) {
+    if (!s || capacity < 0) return fail(MCRT_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());  // the handle's renders, on whatever streams
+    const Lane& ln = s->lanes[0];
+    if (!ln.counters.ptr || !ln.units.ptr || !ln.unit_hits.ptr) return 0;  // nothing rendered yet
+    uint32_t n_units = 0;  // frame_info[0]: what `primary` left for `resolve`
+    HIP_TRY(hipMemcpy(&n_units, static_cast<const uint32_t*>(ln.counters.ptr) + 2 * kCounterWords, 4, hipMemcpyDeviceToHost));
+    if (n_units > 0x7fffffffu || static_cast<size_t>(n_units) * 16 > ln.units.bytes) return fail(MCRT_ERR_INVALID, "the lane's unit count does not fit its workspace");
+    const size_t n = n_units < static_cast<uint32_t>(capacity) ? n_units : static_cast<size_t>(capacity);
+    if (records && n) HIP_TRY(hipMemcpy(records, ln.units.ptr, n * 16, hipMemcpyDeviceToHost));
+    if (hits && n) HIP_TRY(hipMemcpy(hits, ln.unit_hits.ptr, n * 4, hipMemcpyDeviceToHost));
+    return static_cast<int>(n_units);
+}
+
 int mcrt_probe_trace(mcrt_scene* s, const mcrt_config* cfg, const float* rays, int n, int depth, float* out_rgba) {
     if (!s || !cfg || !rays || !out_rgba || n < 0) return fail(MCRT_ERR_INVALID, "bad argument");
     if (n == 0) return MCRT_OK;

@@ -122,6 +122,8 @@ int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int fir
     p.inside_fast = inside_fast ? 1 : 0;
     static const bool work_tickets = !env_off("MCRT_WORK_TICKETS");  // development knob: =0 strides `primary` and `lit` statically over their work lists
     p.work_tickets = work_tickets ? 1 : 0;
+    static const bool unit_blocks = !env_off("MCRT_UNIT_BLOCKS");  // development knob: =0 cuts a touched tile into pixel ranges, not blocks
+    p.unit_blocks = (unit_blocks && !rect) ? 1 : 0;
     p.cfg = *cfg;
     if (cfg->width > 0 && cfg->height > 0) {
         p.inv_width = 1.0f / static_cast<float>(cfg->width);

@@ -494,31 +494,61 @@ __device__ __forceinline__ unsigned long long tile_mesh_mask(const SceneView& sc
     if (!cull && sc.n_meshes > 0) mask = ~0ull;
     return mask;
 }
-// lane 0 of the tile's wave: units and slot range of a tile that meshes can touch; returns its number
-// among the batch's touched tiles
-__device__ __forceinline__ uint32_t plan_touched_tile(const RenderParams& p, const TileGeom& tg, int tile, unsigned long long mask) {
-    const mcrt_config& cfg = p.cfg;
-    const WaveSpace& ws = p.ws;
-    ws.tile_mask[tile] = mask;
-    if (mask == 0ull) return ~0u;  // background tile: never queued
-    const uint32_t spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
+// The units a touched tile is cut into (choose_parts_per_tile): their number, and unit i as a record (kernel_common.h) whose
+// .x holds the form's flag alone and whose .w is the number of the tile's pixels in the units before it.  Pixel ranges: equal
+// parts of the tile's row-major order.  Blocks: the grid's blocks that the (clipped) tile reaches, row by row, clipped with it.
+__device__ __forceinline__ uint32_t tile_unit_count(const RenderParams& p, const TileGeom& tg) {
+    if (p.unit_blocks)
+        return static_cast<uint32_t>((tg.w + p.unit_bw - 1) / p.unit_bw) * static_cast<uint32_t>((tg.h + p.unit_bh - 1) / p.unit_bh);
     const uint32_t npix = static_cast<uint32_t>(tg.w) * static_cast<uint32_t>(tg.h);  // npix * spp <= ws.tile_slots
     const uint32_t parts = static_cast<uint32_t>(p.parts_per_tile);
     const uint32_t per = (npix + parts - 1u) / parts;
-    const uint32_t used = (npix + per - 1u) / per;
+    return (npix + per - 1u) / per;
+}
+__device__ __forceinline__ uint4 tile_unit(const RenderParams& p, const TileGeom& tg, uint32_t i) {
+    if (p.unit_blocks) {
+        const uint32_t cols = static_cast<uint32_t>((tg.w + p.unit_bw - 1) / p.unit_bw);
+        const uint32_t by = i / cols, bx = i - by * cols;
+        const uint32_t x0 = bx * static_cast<uint32_t>(p.unit_bw), y0 = by * static_cast<uint32_t>(p.unit_bh);
+        const uint32_t w = min(static_cast<uint32_t>(p.unit_bw), static_cast<uint32_t>(tg.w) - x0);
+        const uint32_t h = min(static_cast<uint32_t>(p.unit_bh), static_cast<uint32_t>(tg.h) - y0);
+        return make_uint4(kUnitBlock, x0 | (y0 << 16), w | (h << 16), y0 * static_cast<uint32_t>(tg.w) + h * x0);
+    }
+    const uint32_t npix = static_cast<uint32_t>(tg.w) * static_cast<uint32_t>(tg.h);
+    const uint32_t parts = static_cast<uint32_t>(p.parts_per_tile);
+    const uint32_t per = (npix + parts - 1u) / parts;
+    const uint32_t a = i * per;
+    return make_uint4(0u, a, min(npix, a + per), a);
+}
+// The tile's wave: units and slot range of a tile that meshes can touch; returns its number among the batch's touched tiles
+// (the same in every lane), ~0u for a tile that is not queued.  A lane per unit writes the records.
+__device__ __forceinline__ uint32_t plan_touched_tile(const RenderParams& p, const TileGeom& tg, int tile, unsigned long long mask, int lane) {
+    const mcrt_config& cfg = p.cfg;
+    const WaveSpace& ws = p.ws;
+    if (lane == 0) ws.tile_mask[tile] = mask;
+    if (mask == 0ull) return ~0u;  // background tile: never queued
+    const uint32_t spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
+    const uint32_t used = tile_unit_count(p, tg);
     // the k-th touched tile of the batch owns slot range k: the workspace is sized for the tiles that can
     // be touched (host-side superset), not for every sample of the batch
-    const uint32_t ord = count_add(ws, kCntTiles, 1u);
-    if (ord >= ws.tile_cap) {  // cannot happen; keep memory safe and leave a mark if it ever does
-        ws.counters[kCntOverflow] = 1u;
-        ws.tile_mask[tile] = 0ull;
-        return ~0u;
+    uint32_t ord = 0, slot0 = 0;
+    if (lane == 0) {
+        ord = count_add(ws, kCntTiles, 1u);
+        if (ord >= ws.tile_cap) {  // cannot happen; keep memory safe and leave a mark if it ever does
+            ws.counters[kCntOverflow] = 1u;
+            ws.tile_mask[tile] = 0ull;
+            ord = ~0u;
+        } else {
+            slot0 = count_add(ws, kCntUnits, used);
+        }
     }
-    const uint32_t slot0 = count_add(ws, kCntUnits, used);
+    ord = static_cast<uint32_t>(__shfl(static_cast<int>(ord), 0));
+    slot0 = static_cast<uint32_t>(__shfl(static_cast<int>(slot0), 0));
+    if (ord == ~0u) return ~0u;
     const uint32_t base = ord * ws.tile_slots;
-    for (uint32_t i = 0; i < used; ++i) {
-        const uint32_t a = i * per, b = min(npix, a + per);
-        ws.units[slot0 + i] = make_uint4(static_cast<uint32_t>(tile), a, b, base + a * spp);
+    for (uint32_t i = static_cast<uint32_t>(lane); i < used; i += 64u) {
+        const uint4 u = tile_unit(p, tg, i);
+        ws.units[slot0 + i] = make_uint4(static_cast<uint32_t>(tile) | u.x, u.y, u.z, base + u.w * spp);
     }
     return ord;
 }
@@ -541,7 +571,10 @@ __device__ __forceinline__ void plan_tiles_body(const uint8_t* __restrict__ scen
     const SceneView sc = view_of(scene_blob);
     // the tile's mesh mask: every wave of the tile forms it (the same ballot); its slot range and units: the first wave
     const unsigned long long mask = valid ? tile_mesh_mask(sc, p, tg, lane) : 0ull;
-    if (valid && part == 0 && lane == 0) s_ord[wave] = plan_touched_tile(p, tg, tile, mask);
+    if (valid && part == 0) {  // wave-uniform
+        const uint32_t planned = plan_touched_tile(p, tg, tile, mask, lane);
+        if (lane == 0) s_ord[wave] = planned;
+    }
     if (parts > 1) {
         __syncthreads();  // the only workgroup barrier of the kernel: the tile's number among the touched tiles
     } else {
@@ -707,16 +740,21 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
     uint32_t turn = 0;
     for (uint32_t u = blockIdx.x; u < n_units; u = next_work(p, kCntTicketPrimary, u, n_units, s_ticket, turn)) {
         const uint4 ud = ws.units[u];
-        const int tile = static_cast<int>(ud.x);
-        const unsigned pp0 = ud.y, pp1 = ud.z;
+        const int tile = unit_tile(ud);
         const uint32_t slot_base = ud.w;
+        const unsigned n_samples = unit_pixels(ud) * static_cast<unsigned>(spp);
         const TileGeom tg = tile_of(p, tile);
         const unsigned long long mesh_mask = ws.tile_mask[tile];
         // the tile's draws: in the draw plate (tile_draws is then the plate) at its index in the frame; else at its touched-tile
         // number, or (all tiles' streams in HBM) at its index in the batch
         const float* draws = tile_draws + static_cast<size_t>(p.draw_plate ? static_cast<uint32_t>(tg.frame_tile)
                                                               : p.bg_in_plan ? slot_base / ws.tile_slots : static_cast<uint32_t>(tile - tile_base)) * stride;
-        const unsigned n_samples = (pp1 - pp0) * static_cast<unsigned>(spp);
+        // the unit's pixels (kernel_common.h); its origin folded into the frame position and the draws' address, which leaves the
+        // loop below the column and row inside the unit's rectangle
+        const UnitMap um(ud, tg);
+        const int px0 = tg.x + static_cast<int>(um.x0), py0 = tg.y + static_cast<int>(um.y0);
+        const unsigned tile_w = static_cast<unsigned>(tg.w);
+        const float* unit_draws = draws + static_cast<size_t>(um.y0 * tile_w + um.x0) * spp * dd;
 
         uint32_t unit_hits = 0;  // hits so far: they occupy slots slot_base .. slot_base + unit_hits
         for (unsigned s0 = 0; s0 < n_samples; s0 += kChunk) {  // uniform trip count
@@ -727,12 +765,11 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
             uint32_t sample_slot = 0;
             const unsigned sidx = s0 + tid;  // sample of the unit, in stream order
             if (sidx < n_samples) {
-                const unsigned pix = pp0 + UDiv(static_cast<unsigned>(spp)).div(sidx);
-                const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(pix);
-                const int ly = static_cast<int>(uly);
-                const int lx = static_cast<int>(pix - uly * static_cast<unsigned>(tg.w));
-                const int px = tg.x + lx, py = tg.y + ly;
-                const float* jd = draws + (static_cast<size_t>(pp0) * spp + sidx) * dd;
+                const unsigned k = UDiv(static_cast<unsigned>(spp)).div(sidx);  // pixel of the unit; sidx - k * spp: its sample
+                unsigned col, row;
+                um.rel(k, col, row);
+                const int px = px0 + static_cast<int>(col), py = py0 + static_cast<int>(row);
+                const float* jd = unit_draws + (static_cast<size_t>(row * tile_w + col - k) * spp + sidx) * dd;  // ((ly w + lx) spp + s) dd, s = sidx - k spp
                 float jx = 0.5f, jy = 0.5f;
                 int dpos = 0;
                 if (spp > 1) {
@@ -1659,12 +1696,13 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
         const uint32_t slot = d.w + sidx;
         const uint32_t code = ws.end[slot];
         if (code != kEndMiss) return sample_colour(ws, slot, code, C4{scg.hdr->background[0], scg.hdr->background[1], scg.hdr->background[2], scg.hdr->background[3]});
-        const unsigned pix = d.y + UDiv(spp_).div(sidx);
-        const unsigned uly = UDiv(static_cast<unsigned>(tg.w)).div(pix);
-        const int px = tg.x + static_cast<int>(pix - uly * static_cast<unsigned>(tg.w)), py = tg.y + static_cast<int>(uly);
+        const uint32_t k = UDiv(spp_).div(sidx);  // pixel of the unit
+        int lx, ly;
+        unit_pixel(d, tg, k, lx, ly);
+        const int px = tg.x + lx, py = tg.y + ly;
         float jx = 0.5f, jy = 0.5f;
         if (spp_ > 1u) {
-            const float2 j = *reinterpret_cast<const float2*>(draws + (static_cast<size_t>(d.y) * spp_ + sidx) * dd);  // dd is even: 8-byte aligned
+            const float2 j = *reinterpret_cast<const float2*>(draws + (static_cast<size_t>(ly * tg.w + lx) * spp_ + (sidx - k * spp_)) * dd);  // dd is even: 8-byte aligned
             jx = j.x, jy = j.y;
         }
         const C4 c = background(scg, cfg, fd.u(static_cast<float>(px) + jx), fd.v(static_cast<float>(py) + jy));
@@ -1674,10 +1712,9 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
     const uint32_t spp = cfg.samples_per_pixel > 1 ? static_cast<uint32_t>(cfg.samples_per_pixel) : 1u;
     const float inv_spp = 1.0f / static_cast<float>(spp);
     const uint32_t chunk_px = spp <= static_cast<uint32_t>(kBlock) ? static_cast<uint32_t>(kBlock) / spp : 0u;  // pixels per pass (0: a pixel per thread, serially)
-    auto put_pixel = [&](const TileGeom& tg, uint32_t i, float4 acc) __attribute__((always_inline)) {
-        const uint32_t uly = i / static_cast<uint32_t>(tg.w);
-        const int ly = static_cast<int>(uly);
-        const int lx = static_cast<int>(i - uly * static_cast<uint32_t>(tg.w));
+    auto put_pixel = [&](const uint4& d, const TileGeom& tg, uint32_t k, float4 acc) __attribute__((always_inline)) {  // pixel k of unit d
+        int lx, ly;
+        unit_pixel(d, tg, k, lx, ly);
         const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
         store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx),
                     make_float4(acc.x * inv_spp, acc.y * inv_spp, acc.z * inv_spp, acc.w * inv_spp));
@@ -1691,15 +1728,14 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
         return sample_colour(ws, slot, code, C4{scg.hdr->background[0], scg.hdr->background[1], scg.hdr->background[2], scg.hdr->background[3]});
     };
     // transparent: the sum of the n samples that hit
-    auto put_pixel_transparent = [&](const TileGeom& tg, uint32_t i, float4 acc, uint32_t n) __attribute__((always_inline)) {
+    auto put_pixel_transparent = [&](const uint4& d, const TileGeom& tg, uint32_t k, float4 acc, uint32_t n) __attribute__((always_inline)) {
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (n > 0u) {
             const float inv_n = 1.0f / static_cast<float>(n);
             v = make_float4(acc.x * inv_n, acc.y * inv_n, acc.z * inv_n, acc.w * inv_spp);
         }
-        const uint32_t uly = i / static_cast<uint32_t>(tg.w);
-        const int ly = static_cast<int>(uly);
-        const int lx = static_cast<int>(i - uly * static_cast<uint32_t>(tg.w));
+        int lx, ly;
+        unit_pixel(d, tg, k, lx, ly);
         const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
         store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx), v);
     };
@@ -1709,11 +1745,12 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
     }
     for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
         const uint4 d = ws.units[u];
-        const TileGeom tg = tile_of(p, static_cast<int>(d.x));
-        const uint32_t pp0 = d.y, pp1 = d.z;
+        const int tile = unit_tile(d);
+        const TileGeom tg = tile_of(p, tile);
+        const uint32_t pp0 = 0u, pp1 = unit_pixels(d);  // the unit's pixels, in its own order (unit_pixel)
         // the tile's draws: at its touched-tile number, or (all tiles' streams in HBM) at its index in the batch — as in `primary`
         const float* draws = tile_draws + static_cast<size_t>(p.draw_plate ? static_cast<uint32_t>(tg.frame_tile)
-                                                              : p.bg_in_plan ? d.w / ws.tile_slots : static_cast<uint32_t>(static_cast<int>(d.x) - tile_base)) * ws.draws_stride;
+                                                              : p.bg_in_plan ? d.w / ws.tile_slots : static_cast<uint32_t>(tile - tile_base)) * ws.draws_stride;
         if (chunk_px == 0u) {
             for (uint32_t i = pp0 + threadIdx.x; i < pp1; i += kBlock) {
                 float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1726,13 +1763,13 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
                         acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
                         ++n;
                     }
-                    put_pixel_transparent(tg, i, acc, n);
+                    put_pixel_transparent(d, tg, i, acc, n);
                 } else {
                     for (uint32_t s = 0; s < spp; ++s) {
                         const float4 c = unit_sample(d, tg, draws, (i - pp0) * spp + s, spp);
                         acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
                     }
-                    put_pixel(tg, i, acc);
+                    put_pixel(d, tg, i, acc);
                 }
             }
             continue;
@@ -1759,13 +1796,13 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
                         acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
                         ++n;
                     }
-                    put_pixel_transparent(tg, p0 + threadIdx.x, acc, n);
+                    put_pixel_transparent(d, tg, p0 + threadIdx.x, acc, n);
                 } else {
                     for (uint32_t s = 0; s < spp; ++s) {
                         const float4 c = s_col[threadIdx.x * spp + s];
                         acc.x += c.x, acc.y += c.y, acc.z += c.z, acc.w += c.w;
                     }
-                    put_pixel(tg, p0 + threadIdx.x, acc);
+                    put_pixel(d, tg, p0 + threadIdx.x, acc);
                 }
             }
             __syncthreads();

@@ -45,7 +45,17 @@ static bool needs_general_variant(const mcrt_config& c) {
 // Parts of a tile that meshes can touch: one 256-sample chunk each, at most 16 — fine enough that
 // the few tiles holding the character spread over the chip.  Every part reads its samples' draws from
 // the tile's stream in HBM (plan_tiles).  Background tiles are never split.
-static int choose_parts_per_tile(const RenderParams& p) {
+//
+// Units by block (p.unit_blocks; not for a renderTile rectangle, which keeps pixel ranges): the tile is cut by a grid of
+// gx x gy blocks of ceil(T / gx) x ceil(T / gy) pixels, gx * gy <= 16.  Of the grids whose block is at most one chunk of
+// samples and no more than twice as long as it is wide, the one with the FEWEST blocks is taken (the fullest chunks); among
+// those the squarest, then the wider one.  8 x 8 blocks at 4 spp on a tile of 16, 24 or 32, 16 x 16 at 1 spp, 16 x 8 at 2 spp
+// and 11 x 7 at 3 spp of a tile of 32.  A workgroup's samples then lie in a square patch of the screen instead of a 32 x 2
+// strip: their rays meet the same few meshes and the same faces (DESIGN.md §4 "Units by block").  Where no such grid exists
+// — more than 4 spp on a tile of 32, where the cap of 16 makes a unit several chunks, or a tile too large — the tile keeps
+// its pixel ranges: a chunk of a range is then a few neighbouring pixels already, and blocks only gather the hits into
+// fewer units, which the kernels that stride over the units statically (`ao`, `resolve`) pay for (gui_defaults -2.1 %).
+static int choose_parts_per_tile(RenderParams& p) {
     const mcrt_config& cfg = p.cfg;
     const long long spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
     const long long tile_items = p.rect_w > 0 ? static_cast<long long>(p.rect_w) * p.rect_h * spp : static_cast<long long>(cfg.tile_size) * cfg.tile_size * spp;
@@ -53,7 +63,27 @@ static int choose_parts_per_tile(const RenderParams& p) {
     const long long most = p.rect_w > 0 ? 4096 : 16;  // a renderTile rectangle may be as large as the frame: it is the launch's only tile
     if (parts > most) parts = most;
     if (parts < 1) parts = 1;
-    return static_cast<int>(parts);
+    p.unit_gx = p.unit_gy = p.unit_bw = p.unit_bh = 0;
+    if (p.rect_w > 0 || cfg.tile_size <= 0 || cfg.tile_size > 0xffff) p.unit_blocks = 0;  // (a block's origin and size are 16-bit fields of its record)
+    if (!p.unit_blocks) return static_cast<int>(parts);
+    const long long T = cfg.tile_size;
+    long long best_key = -1;
+    for (long long gx = 1; gx <= 16; ++gx)
+        for (long long gy = 1; gx * gy <= 16; ++gy) {
+            const long long bw = (T + gx - 1) / gx, bh = (T + gy - 1) / gy;
+            const long long lo = bw < bh ? bw : bh, hi = bw < bh ? bh : bw;
+            if (bw * bh * spp > kChunk || hi > 2 * lo) continue;
+            const long long key = ((gx * gy) << 40) | ((hi - lo) << 8) | (bw >= bh ? 0 : 1);  // fewest blocks, then the squarest, then the wider one
+            if (best_key < 0 || key < best_key) {
+                best_key = key;
+                p.unit_gx = static_cast<int>(gx), p.unit_gy = static_cast<int>(gy), p.unit_bw = static_cast<int>(bw), p.unit_bh = static_cast<int>(bh);
+            }
+        }
+    if (best_key < 0) {  // no grid of one chunk per block: pixel ranges
+        p.unit_blocks = 0;
+        return static_cast<int>(parts);
+    }
+    return p.unit_gx * p.unit_gy;
 }
 
 WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched) {
