@@ -37,6 +37,26 @@ struct UDiv {
 };
 
 // ---------------------------------------------------------------------------------------------
+// Parameters by phase.  A kernel of the render pipeline holds its RenderParams where scalar loads reach them at any time:
+// in its own kernarg segment (the single-frame entries take them by value, as their FIRST argument) or in the batch's
+// device-resident table — constant address space either way.  Read through a plain reference, the compiler loads every
+// field a kernel will ever need at its entry and keeps it live across the persistent item loop: 106 SGPRs do not hold
+// ~150 dwords of parameters and 25 workspace pointers beside the loop's own state, and the overflow is parked in VGPR
+// lanes (v_writelane / v_readlane: VALU work inside the hot loops, DESIGN.md §4 "Scalar registers").  So the item loops
+// take the parameters BY PHASE: phase_params(pp) at a phase's start gives a reference the optimiser cannot merge with an
+// earlier one — the pointer passes through an empty asm in a scalar register pair — and what the phase reads comes in
+// by scalar loads right there (no VALU slot; other waves hide the wait) and dies with the phase.  Only the pointer
+// itself (2 SGPRs) lives across the loops.
+// ---------------------------------------------------------------------------------------------
+using ParamPtr = const __attribute__((address_space(4))) RenderParams*;
+__device__ __forceinline__ const RenderParams& phase_params(ParamPtr pp) {
+    asm volatile("" : "+s"(pp));
+    return *(const RenderParams*)pp;
+}
+// the by-value RenderParams that is a kernel's first argument, in its kernarg segment
+__device__ __forceinline__ ParamPtr kernarg_params() { return (ParamPtr)__builtin_amdgcn_kernarg_segment_ptr(); }
+
+// ---------------------------------------------------------------------------------------------
 // tile geometry helpers (TileRenderer::generateTiles, tile_renderer.cpp:18-39)
 // ---------------------------------------------------------------------------------------------
 struct TileGeom {

@@ -61,9 +61,16 @@ struct FrameDiv {
     bool fast;
     __device__ __forceinline__ explicit FrameDiv(const RenderParams& p)
         : w(static_cast<float>(p.cfg.width)), h(static_cast<float>(p.cfg.height)), rw(p.inv_width), rh(p.inv_height), fast(p.div_frame != 0) {}
+    // with the frame's size as floats already at hand (`resolve` forms them once per kernel)
+    __device__ __forceinline__ FrameDiv(float fw, float fh, const RenderParams& p) : w(fw), h(fh), rw(p.inv_width), rh(p.inv_height), fast(p.div_frame != 0) {}
     __device__ __forceinline__ float u(float x) const { return fast ? div_frame(x, w, rw) : x / w; }
     __device__ __forceinline__ float v(float y) const { return fast ? div_frame(y, h, rh) : y / h; }
 };
+
+// A wave-uniform float that a kernel forms once and keeps across its item loop, in a scalar register: conversions and
+// divisions run on the vector unit, and their result would otherwise hold a VGPR — or be formed again by every phase.
+// (`resolve`, which has registers to spare.  In `primary` the three scalars cost more lane moves than they saved.)
+__device__ __forceinline__ float uniform_float(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 
 __device__ __forceinline__ TileGeom tile_of(const RenderParams& p, int owned_tile) {
     TileGeom t;
@@ -705,7 +712,7 @@ __global__ __launch_bounds__(64 * kStreamWaves) void advance_tiles_kernel(Render
 #endif
 template <int kView>
 __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
-                                             float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams& __restrict__ p,
+                                             float4* __restrict__ out_frame, uchar4* __restrict__ out8, const ParamPtr pp,
                                              const int tile_base, const int n_tiles) {
     __shared__ int s_wcnt[kBlock / 64];
     __shared__ float4 s_bd[kBlock], s_bp[kBlock], s_bn[kBlock];  // the chunk's primary hits, packed, for their reflection rays
@@ -713,48 +720,43 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
     __shared__ uint32_t s_ticket[2];
     extern __shared__ __align__(16) unsigned char s_dyn[];
 
+    // The parameters by phase (kernel_common.h, phase_params): across the unit loop live the loop's own state, the scene
+    // view and `pp` — every phase below reads what it needs of the parameters where it begins.
     const SceneView scg = view_of(scene_blob);
-    const mcrt_config& cfg = p.cfg;
-    const WaveSpace& ws = p.ws;
-    const uint32_t n_units = counted(ws, kCntUnits);
-    if (blockIdx.x == 0 && threadIdx.x == 0) ws.frame_info[0] = n_units;  // for `resolve`, which takes the next pass's counter base
-    if ((p.bg_in_plan || p.bg_kernel) && blockIdx.x >= n_units) return;  // nothing for this workgroup: leave before the collective staging
-    // flat pipeline: the reflection ray of every primary hit (raytracer.cpp:133-139) is traced right here, by the first
-    // `total` threads of the block on the chunk's packed hits (as a launch of its own this stage re-read every record:
-    // 39 + 28 us became 59 us)
-    const bool bounce_here = p.flat && cfg.max_bounces >= 1;
-    const bool posed = kView != kViewLdsUnposed && p.scene_posed != 0;
-    const typename ViewSel<kView>::type sc = ViewSel<kView>::make(scg, p, s_dyn);
     const int tid = threadIdx.x;
-    const int spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
-    const int dd = p.draws_per_sample;
-    const bool dof = cfg.dof_enabled && cfg.aperture > 1e-6f;
-    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
-    const FrameDiv fd(p);
-    float focusDist = cfg.focus_distance;
-    if (focusDist <= 0.0f) focusDist = sc.hdr->cam_focus_auto;
-    const size_t stride = ws.draws_stride;
+    uint32_t n_units;
+    {  // ---- entry: the pass's unit count, and whether this workgroup has anything to do
+        const RenderParams& p = phase_params(pp);
+        n_units = counted(p.ws, kCntUnits);
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.ws.frame_info[0] = n_units;  // for `resolve`, which takes the next pass's counter base
+        if ((p.bg_in_plan || p.bg_kernel) && blockIdx.x >= n_units) return;  // nothing for this workgroup: leave before the collective staging
+    }
+    const typename ViewSel<kView>::type sc = ViewSel<kView>::make(scg, phase_params(pp), s_dyn);
 
     // ================= units of tiles that meshes can touch: thread per sample =================
     // (the list by ticket: next_work)
     uint32_t turn = 0;
-    for (uint32_t u = blockIdx.x; u < n_units; u = next_work(p, kCntTicketPrimary, u, n_units, s_ticket, turn)) {
-        const uint4 ud = ws.units[u];
+    for (uint32_t u = blockIdx.x; u < n_units; u = next_work(phase_params(pp), kCntTicketPrimary, u, n_units, s_ticket, turn)) {
+        // ---- phase: the unit — its record, its tile, where its draws are
+        const RenderParams& pu = phase_params(pp);
+        const uint4 ud = pu.ws.units[u];
         const int tile = unit_tile(ud);
         const uint32_t slot_base = ud.w;
-        const unsigned n_samples = unit_pixels(ud) * static_cast<unsigned>(spp);
-        const TileGeom tg = tile_of(p, tile);
-        const unsigned long long mesh_mask = ws.tile_mask[tile];
+        const int spp_u = pu.cfg.samples_per_pixel > 1 ? pu.cfg.samples_per_pixel : 1;
+        const unsigned n_samples = unit_pixels(ud) * static_cast<unsigned>(spp_u);
+        const TileGeom tg = tile_of(pu, tile);
+        const unsigned long long mesh_mask = pu.ws.tile_mask[tile];
         // the tile's draws: in the draw plate (tile_draws is then the plate) at its index in the frame; else at its touched-tile
         // number, or (all tiles' streams in HBM) at its index in the batch
-        const float* draws = tile_draws + static_cast<size_t>(p.draw_plate ? static_cast<uint32_t>(tg.frame_tile)
-                                                              : p.bg_in_plan ? slot_base / ws.tile_slots : static_cast<uint32_t>(tile - tile_base)) * stride;
+        const float* draws = tile_draws + static_cast<size_t>(pu.draw_plate ? static_cast<uint32_t>(tg.frame_tile)
+                                                              : pu.bg_in_plan ? slot_base / pu.ws.tile_slots : static_cast<uint32_t>(tile - tile_base)) *
+                                              static_cast<size_t>(pu.ws.draws_stride);
         // the unit's pixels (kernel_common.h); its origin folded into the frame position and the draws' address, which leaves the
         // loop below the column and row inside the unit's rectangle
         const UnitMap um(ud, tg);
         const int px0 = tg.x + static_cast<int>(um.x0), py0 = tg.y + static_cast<int>(um.y0);
         const unsigned tile_w = static_cast<unsigned>(tg.w);
-        const float* unit_draws = draws + static_cast<size_t>(um.y0 * tile_w + um.x0) * spp * dd;
+        const float* unit_draws = draws + static_cast<size_t>(um.y0 * tile_w + um.x0) * spp_u * pu.draws_per_sample;
 
         uint32_t unit_hits = 0;  // hits so far: they occupy slots slot_base .. slot_base + unit_hits
         for (unsigned s0 = 0; s0 < n_samples; s0 += kChunk) {  // uniform trip count
@@ -765,6 +767,14 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
             uint32_t sample_slot = 0;
             const unsigned sidx = s0 + tid;  // sample of the unit, in stream order
             if (sidx < n_samples) {
+                // ---- phase: the camera ray of the sample and its closest hit
+                const RenderParams& p = phase_params(pp);
+                const mcrt_config& cfg = p.cfg;
+                const int spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
+                const int dd = p.draws_per_sample;
+                const bool dof = cfg.dof_enabled && cfg.aperture > 1e-6f;
+                const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+                const FrameDiv fd(p);
                 const unsigned k = UDiv(static_cast<unsigned>(spp)).div(sidx);  // pixel of the unit; sidx - k * spp: its sample
                 unsigned col, row;
                 um.rel(k, col, row);
@@ -780,25 +790,36 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
                 const float su = fd.u(static_cast<float>(px) + jx);
                 const float sv = fd.v(static_cast<float>(py) + jy);
                 sample_slot = slot_base + sidx;
-                ray = dof ? lens_ray(sc, su, sv, aspect, cfg.aperture, focusDist, jd[dpos], jd[dpos + 1])
-                          : camera_ray(sc, su, sv, aspect);
+                if (dof) {
+                    float focusDist = cfg.focus_distance;
+                    if (focusDist <= 0.0f) focusDist = sc.hdr->cam_focus_auto;
+                    ray = lens_ray(sc, su, sv, aspect, cfg.aperture, focusDist, jd[dpos], jd[dpos + 1]);
+                } else {
+                    ray = camera_ray(sc, su, sv, aspect);
+                }
                 hit = hit_scene(sc, ray, mesh_mask);
+            }
+            // ---- phase: how the sample ends, and the hits' records
+            const RenderParams& q = phase_params(pp);
+            const bool flat = q.flat != 0;
+            const bool bounce_here = flat && q.cfg.max_bounces >= 1;
+            if (sidx < n_samples) {
                 // A miss: its colour is a function of the sample's jitter pair alone (tile_renderer.cpp:111-114) — `resolve`
                 // forms it from the pair in the tile's stream (8 B) instead of a colour stored here and read back there
                 // (2 x 16 B per miss of a touched tile: 13 MB of the metric frame's counted HBM traffic).
                 uint32_t code = kEndMiss;
-                if (hit.hit && cfg.max_bounces < 0) {
-                    const C4 col = background(sc, cfg, 0.5f, 0.5f);  // raytracer.cpp:86-90 (depth 0 > maxBounces)
-                    ws.scol[sample_slot] = make_float4(col.r, col.g, col.b, col.a);
+                if (hit.hit && q.cfg.max_bounces < 0) {
+                    const C4 col = background(sc, q.cfg, 0.5f, 0.5f);  // raytracer.cpp:86-90 (depth 0 > maxBounces)
+                    q.ws.scol[sample_slot] = make_float4(col.r, col.g, col.b, col.a);
                     code = 0u;
                 } else if (hit.hit) {
                     is_hit = true;
                     // 0: the colour is in scol (general variants: `level_shade` puts the hits' colours there).  Flat pipeline:
                     // the second phase below / `lit` overwrite a hit's word with its chain's end code — unless maxBounces is 0
                     // and the chain is its primary hit alone.
-                    code = (p.flat && cfg.max_bounces == 0) ? 3u : 0u;
+                    code = (flat && q.cfg.max_bounces == 0) ? 3u : 0u;
                 }
-                ws.end[sample_slot] = code;
+                q.ws.end[sample_slot] = code;
             }
             // hits → dense entries at the front of the unit's slot range (no global atomics)
             int total = 0;
@@ -806,10 +827,10 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
             if (is_hit) {
                 const uint32_t e = slot_base + unit_hits + static_cast<uint32_t>(rank);
                 // root of the chain = its sample's colour slot
-                if (p.flat)
-                    push_record(ws, posed, e, ray, hit, sample_slot, 0, dof);
+                if (flat)
+                    push_record(q.ws, kView != kViewLdsUnposed && q.scene_posed != 0, e, ray, hit, sample_slot, 0, q.cfg.dof_enabled && q.cfg.aperture > 1e-6f);
                 else
-                    push_entry(ws, 0, e, ray, hit, sample_slot, 0);
+                    push_entry(q.ws, 0, e, ray, hit, sample_slot, 0);
                 if (bounce_here) {
                     s_bd[rank] = make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(sample_slot));
                     s_bp[rank] = make_float4(hit.p.x, hit.p.y, hit.p.z, 0.0f);
@@ -817,6 +838,9 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
                 }
             }
             unit_hits += static_cast<uint32_t>(total);
+            // flat pipeline: the reflection ray of every primary hit (raytracer.cpp:133-139) is traced right here, by the first
+            // `total` threads of the block on the chunk's packed hits (as a launch of its own this stage re-read every record:
+            // 39 + 28 us became 59 us)
             if (bounce_here && total > 0) {  // uniform
                 __syncthreads();
                 bool next_hit = false;
@@ -829,22 +853,27 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
                     root = __float_as_uint(bd.w);
                     nray = reflect_ray(mk(bd.x, bd.y, bd.z), mk(bp.x, bp.y, bp.z), mk(bn.x, bn.y, bn.z));
                     nhit = hit_scene<true>(sc, nray, ~0ull);
+                }
+                // ---- phase: the level-1 records
+                const RenderParams& r = phase_params(pp);
+                if (tid < total) {
                     if (nhit.hit)
                         next_hit = true;
                     else
-                        ws.end[root] = chain_code(1, false);  // bounced ray missed → flat background (raytracer.cpp:94-102)
+                        r.ws.end[root] = chain_code(1, false);  // bounced ray missed → flat background (raytracer.cpp:94-102)
                 }
                 int survivors = 0;
                 const int srank = block_rank(next_hit, s_wcnt, survivors);
                 if (survivors > 0) {  // uniform
-                    if (tid == 0) s_out_base = count_add(ws, kCntDeep1, static_cast<uint32_t>(survivors));
+                    if (tid == 0) s_out_base = count_add(r.ws, kCntDeep1, static_cast<uint32_t>(survivors));
                     __syncthreads();
-                    if (next_hit) push_record(ws, posed, ws.cap + s_out_base + static_cast<uint32_t>(srank), nray, nhit, root, 1, true);
+                    if (next_hit)
+                        push_record(r.ws, kView != kViewLdsUnposed && r.scene_posed != 0, r.ws.cap + s_out_base + static_cast<uint32_t>(srank), nray, nhit, root, 1, true);
                 }
                 __syncthreads();  // s_bd .. s_out_base are reused by the next chunk
             }
         }
-        if (tid == 0) ws.unit_hits[u] = unit_hits;
+        if (tid == 0) phase_params(pp).ws.unit_hits[u] = unit_hits;
     }
 
 
@@ -852,7 +881,13 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
     // (only when a pixel takes more than 24 draws — otherwise `plan_tiles` has rendered them from LDS — and at most
     // kSlabMinSpp - 1 samples: above that `background_kernel` does it)
     // thread per pixel, its samples in order as renderTile sums them (tile_renderer.cpp:116-124); no barriers
+    const RenderParams& p = phase_params(pp);
     if (p.bg_in_plan || p.bg_kernel) return;
+    const mcrt_config& cfg = p.cfg;
+    const WaveSpace& ws = p.ws;
+    const int spp = cfg.samples_per_pixel > 1 ? cfg.samples_per_pixel : 1;
+    const FrameDiv fd(p);
+    const size_t stride = ws.draws_stride;
     const float inv_spp = 1.0f / static_cast<float>(spp);
     for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const int tile = tile_base + t;
@@ -887,11 +922,11 @@ __device__ __forceinline__ void primary_body(const uint8_t* __restrict__ scene_b
     }
 }
 template <int kView>
-__global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_kernel(const uint8_t* __restrict__ scene_blob,
+__global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_kernel(const RenderParams p, const uint8_t* __restrict__ scene_blob,
                                                          const float* __restrict__ tile_draws,
-                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
+                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8,
                                                          const int tile_base, const int n_tiles) {
-    primary_body<kView>(scene_blob, tile_draws, out_frame, out8, p, tile_base, n_tiles);
+    primary_body<kView>(scene_blob, tile_draws, out_frame, out8, kernarg_params(), tile_base, n_tiles);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1254,13 +1289,51 @@ __global__ __launch_bounds__(kBlock, MCRT_SHADOW_WAVES) void shadow_kernel(const
 #ifndef MCRT_LIT_WAVES
 #define MCRT_LIT_WAVES 4
 #endif
+// What `lit`'s phases read of the shadow configuration, and the workgroup's LDS area behind the scene tables.  Five scalars
+// (LitKnobs) live across the work-item loop; a phase forms the rest from them where it begins, by scalar arithmetic alone —
+// no load, no wait.  (Formed from the parameters in every phase, with the light's radius from the scene header, a round
+// waited eight times for scalar loads behind its barriers: `lit` spilled less still, and the 4K workload lost 2 % of its
+// throughput — profiles/sgpr_spills/README.md, "Measured and rejected".)
+struct LitKnobs {
+    int mode, S, lds_offset;
+    uint32_t round, pass;
+    __device__ __forceinline__ LitKnobs(const SceneView& scg, const RenderParams& p)
+        : mode(shadow_mode(scg, p.cfg)), S(p.cfg.shadow_samples), lds_offset(p.lit_lds_offset), round(static_cast<uint32_t>(p.lit_round)),
+          pass(static_cast<uint32_t>(p.lit_pass)) {}  // pass: records whose sample positions fit the LDS area at once
+};
+struct LitShape {
+    int mode, S;
+    uint32_t pairs_per_hit;
+    bool pow2;
+    unsigned long long* s_cand;
+    unsigned long long* s_ins;  // of the candidates, the boxes that hold the record's ray origin strictly inside (rt::mesh_candidate_inside)
+    float* s_pos;
+    uint32_t* s_lit;
+    uint32_t* s_und;  // the round's undecided records, packed
+    __device__ __forceinline__ LitShape(const LitKnobs& k, unsigned char* s_dyn) {
+        int off = k.lds_offset;
+        asm volatile("" : "+s"(off));  // formed here, not once above the loop and carried
+        mode = k.mode;
+        S = k.S;
+        pairs_per_hit = (mode == SHADOW_SOFT) ? static_cast<uint32_t>(S) : 1u;
+        pow2 = (pairs_per_hit & (pairs_per_hit - 1u)) == 0u && pairs_per_hit <= 64u;
+        s_cand = reinterpret_cast<unsigned long long*>(s_dyn + off);  // 16-aligned
+        s_ins = s_cand + k.round;
+        s_pos = reinterpret_cast<float*>(s_ins + k.round);
+        s_lit = reinterpret_cast<uint32_t*>(s_pos + static_cast<size_t>(k.pass) * pairs_per_hit * 3);
+        s_und = s_lit + k.round;
+    }
+};
 template <int kView>
-__device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob, const RenderParams& __restrict__ p) {
+__device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob, const ParamPtr pp) {
     extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][candidate masks: lit_round][inside masks: lit_round][positions: lit_pass x S x 3 floats][lit counts: lit_round][undecided list: lit_round]
     __shared__ int s_wcnt[kBlock / 64];
     __shared__ uint32_t s_ticket[2];
     MCRT_HOOK_LIT_SHARED
+    // The parameters by phase (kernel_common.h, phase_params): across the work-item loop live the list's counts, the scene
+    // view and `pp`.
     const SceneView scg = view_of(scene_blob);
+    const RenderParams& p = phase_params(pp);  // ---- entry: the work list
     const WaveSpace& ws = p.ws;
     const Scope scope{0, 1};
     // ONE work list — the units' record ranges, then the dense queue in blocks of 256 — so that the three phases
@@ -1281,28 +1354,16 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
     if (blockIdx.x >= n_work) return;  // before the collective staging
     const typename ViewSel<kView>::type sc = ViewSel<kView>::make(scg, p, s_dyn);
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    const int mode = shadow_mode(scg, p.cfg);
-    const int S = p.cfg.shadow_samples;
-    const uint32_t pairs_per_hit = (mode == SHADOW_SOFT) ? static_cast<uint32_t>(S) : 1u;
-    const bool pow2 = (pairs_per_hit & (pairs_per_hit - 1u)) == 0u && pairs_per_hit <= 64u;
-    const uint32_t round = static_cast<uint32_t>(p.lit_round);
-    unsigned long long* s_cand = reinterpret_cast<unsigned long long*>(s_dyn + p.lit_lds_offset);  // 16-aligned
-    unsigned long long* s_ins = s_cand + round;  // of those, the boxes that hold the record's ray origin strictly inside (rt::mesh_candidate_inside)
-    float* s_pos = reinterpret_cast<float*>(s_ins + round);
-    const uint32_t pass = static_cast<uint32_t>(p.lit_pass);  // records whose sample positions fit the LDS area at once
-    uint32_t* s_lit = reinterpret_cast<uint32_t*>(s_pos + static_cast<size_t>(pass) * pairs_per_hit * 3);
-    uint32_t* s_und = s_lit + round;  // the round's undecided records, packed
-    const V3 lpos = ld3(scg.hdr->light_pos);
-    const float lradius = scg.hdr->light_radius;
+    const LitKnobs knobs(scg, p);
     const uint32_t lane = threadIdx.x & 63u;
-    const mcrt_config& cfg = p.cfg;
-    const bool posed = kView != kViewLdsUnposed && p.scene_posed != 0;  // the un-posed variants never read q_n
-    const bool dof = cfg.dof_enabled && cfg.aperture > 1e-6f;
-    const V3 cam_pos = ld3(scg.hdr->cam_pos);
     // (the list by ticket: next_work; its order — chase blocks, units, dense blocks — puts the dearest items first)
     uint32_t turn = 0;
-    for (uint32_t work = blockIdx.x; work < n_work; work = next_work(p, kCntTicketLit, work, n_work, s_ticket, turn)) {
+    for (uint32_t work = blockIdx.x; work < n_work; work = next_work(phase_params(pp), kCntTicketLit, work, n_work, s_ticket, turn)) {
         uint32_t first, n;
+        // ---- phase: the work item — a chase block, a unit's records or a block of the dense queue
+        const RenderParams& p = phase_params(pp);
+        const WaveSpace& ws = p.ws;
+        const bool posed = kView != kViewLdsUnposed && p.scene_posed != 0;  // the un-posed variants never read q_n
         if (work < n_chase) {
             // the chains of level-1 records [k0, k0 + 256): a lane per chain — reflect, closest hit, append — until the ray
             // misses or the chain reaches maxBounces; ~10 % of the lanes go on per turn, the loop is workgroup-uniform
@@ -1324,7 +1385,7 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
                 nhit.hit = false;
                 if (active) {
                     if (r.depth >= max_b) {  // no reflection at the last level
-                        ws.end[r.root] = chain_code(r.depth + 1, true);
+                        phase_params(pp).ws.end[r.root] = chain_code(r.depth + 1, true);
                         active = false;
                     } else {
                         nray = reflect_ray(r.d, r.p, r.n);
@@ -1332,7 +1393,7 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
                         if (nhit.hit) {
                             next_hit = true;
                         } else {
-                            ws.end[r.root] = chain_code(r.depth + 1, false);
+                            phase_params(pp).ws.end[r.root] = chain_code(r.depth + 1, false);
                             active = false;
                         }
                     }
@@ -1341,7 +1402,7 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
                 const int rank = block_rank(next_hit, s_wcnt, total);
                 if (total == 0) break;  // uniform: no chain of this block goes on
                 if (next_hit) {
-                    push_record(ws, posed, region + filled + static_cast<uint32_t>(rank), nray, nhit, r.root, r.depth + 1, true);
+                    push_record(phase_params(pp).ws, posed, region + filled + static_cast<uint32_t>(rank), nray, nhit, r.root, r.depth + 1, true);
                     r.d = nray.d;
                     r.p = nhit.p;
                     r.n = nhit.n;
@@ -1360,74 +1421,88 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
             first = ws.cap + k0;
             n = min(static_cast<uint32_t>(kBlock), n_dense - k0);
         }
+        const uint32_t round = knobs.round;
         for (uint32_t r0 = 0; r0 < n; r0 += round) {  // uniform
             const uint32_t m = min(round, n - r0);
             const uint32_t base = first + r0;
-            // ---- phase A1: a lane per record — the bundle mask, and whether the whole bundle is decided (rt::bundle_classify)
-            bool undecided = false;
-            if (threadIdx.x < m) {
-                if (mode == SHADOW_SOFT) {
-                    const RecordGeom g = load_geom(ws, posed, base + threadIdx.x);
-                    const V3 O = g.p + g.n * 1e-3f;
-                    unsigned long long cand;
-                    const int known = bundle_classify<kPosed>(scg, sc, O, lpos, lradius, S, p.bundle_decisions != 0, cand);
-                    undecided = known < 0;
-                    MCRT_HOOK_LIT_CLASSIFIED(known, undecided, cand, O)
-                    s_cand[threadIdx.x] = cand;
-                    s_ins[threadIdx.x] = (undecided && p.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
-                    s_lit[threadIdx.x] = undecided ? 0u : static_cast<uint32_t>(known);
-                } else {
-                    s_lit[threadIdx.x] = 0u;
-                }
-            }
             uint32_t n_und = m;  // records whose rays are traced
-            if (mode == SHADOW_SOFT) {
-                int total = 0;
-                const int rank = block_rank(undecided, s_wcnt, total);
-                if (undecided) s_und[rank] = threadIdx.x;
-                n_und = static_cast<uint32_t>(total);
-                if (n_und == 0u) {  // uniform: no ray of this round needs tracing
-                    __syncthreads();
-                    goto shade_round;
+            {
+                // ---- phase A1: a lane per record — the bundle mask, and whether the whole bundle is decided (rt::bundle_classify)
+                const RenderParams& p = phase_params(pp);
+                const LitShape ls(knobs, s_dyn);
+                bool undecided = false;
+                if (threadIdx.x < m) {
+                    if (ls.mode == SHADOW_SOFT) {
+                        const RecordGeom g = load_geom(p.ws, kView != kViewLdsUnposed && p.scene_posed != 0, base + threadIdx.x);
+                        const V3 O = g.p + g.n * 1e-3f;
+                        const V3 lpos = ld3(scg.hdr->light_pos);
+                        const float lradius = scg.hdr->light_radius;
+                        unsigned long long cand;
+                        const int known = bundle_classify<kPosed>(scg, sc, O, lpos, lradius, ls.S, p.bundle_decisions != 0, cand);
+                        undecided = known < 0;
+                        MCRT_HOOK_LIT_CLASSIFIED(known, undecided, cand, O)
+                        ls.s_cand[threadIdx.x] = cand;
+                        ls.s_ins[threadIdx.x] = (undecided && p.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
+                        ls.s_lit[threadIdx.x] = undecided ? 0u : static_cast<uint32_t>(known);
+                    } else {
+                        ls.s_lit[threadIdx.x] = 0u;
+                    }
                 }
-                __syncthreads();
+                if (ls.mode == SHADOW_SOFT) {
+                    int total = 0;
+                    const int rank = block_rank(undecided, s_wcnt, total);
+                    if (undecided) ls.s_und[rank] = threadIdx.x;
+                    n_und = static_cast<uint32_t>(total);
+                    if (n_und == 0u) {  // uniform: no ray of this round needs tracing
+                        __syncthreads();
+                        goto shade_round;
+                    }
+                    __syncthreads();
+                }
             }
             // the traced records in passes of up to `pass` (their sample positions share the LDS area: with the
             // bundle decisions few records of a round are left, and the area is sized for those)
-            for (uint32_t u0 = 0; u0 < n_und; u0 += pass) {  // uniform
+            for (uint32_t u0 = 0, pass = knobs.pass; u0 < n_und; u0 += pass) {  // uniform
                 const uint32_t nu = min(pass, n_und - u0);
                 if (u0) __syncthreads();  // the previous pass's rays have read the positions
-                // ---- phase A2: a lane per undecided record — its mt19937 stream and the S disk sample positions
-                if (mode == SHADOW_SOFT && threadIdx.x < nu) {
-                    const RecordGeom g = load_geom(ws, posed, base + s_und[u0 + threadIdx.x]);
-                    disk_sample_positions(scg, p.seed_table, p.seed_table_full, g.p, g.depth, S, s_pos + static_cast<size_t>(threadIdx.x) * 3 * S);
+                {
+                    // ---- phase A2: a lane per undecided record — its mt19937 stream and the S disk sample positions
+                    const RenderParams& p = phase_params(pp);
+                    const LitShape ls(knobs, s_dyn);
+                    if (ls.mode == SHADOW_SOFT && threadIdx.x < nu) {
+                        const RecordGeom g = load_geom(p.ws, kView != kViewLdsUnposed && p.scene_posed != 0, base + ls.s_und[u0 + threadIdx.x]);
+                        disk_sample_positions(scg, p.seed_table, p.seed_table_full, g.p, g.depth, ls.S, ls.s_pos + static_cast<size_t>(threadIdx.x) * 3 * ls.S);
+                    }
                 }
                 __syncthreads();
                 // ---- phase B: a lane per (undecided record, light sample); every lane of a wave runs the same number of turns (ballot inside)
-                const uint32_t total = nu * pairs_per_hit;
+                const RenderParams& p = phase_params(pp);
+                const LitShape ls(knobs, s_dyn);
+                const bool posed = kView != kViewLdsUnposed && p.scene_posed != 0;
+                const uint32_t total = nu * ls.pairs_per_hit;
                 for (uint32_t q0 = threadIdx.x & ~63u; q0 < total; q0 += kBlock) {
                     const uint32_t q = q0 + lane;
                     bool visible = false;
                     uint32_t k = 0;
                     if (q < total) {
-                        const uint32_t j = u0 + q / pairs_per_hit;
-                        k = (mode == SHADOW_SOFT) ? s_und[j] : j;
+                        const uint32_t j = u0 + q / ls.pairs_per_hit;
+                        k = (ls.mode == SHADOW_SOFT) ? ls.s_und[j] : j;
                         V3 P, N;
-                        load_point_normal(ws, posed, base + k, P, N);
-                        if (mode == SHADOW_HARD) N = normalize(N);
-                        if (mode == SHADOW_SOFT)
-                            visible = !in_shadow_masked(sc, P, N, ld3(s_pos + static_cast<size_t>(q) * 3), s_cand[k], s_ins[k]);
+                        load_point_normal(p.ws, posed, base + k, P, N);
+                        if (ls.mode == SHADOW_HARD) N = normalize(N);
+                        if (ls.mode == SHADOW_SOFT)
+                            visible = !in_shadow_masked(sc, P, N, ld3(ls.s_pos + static_cast<size_t>(q) * 3), ls.s_cand[k], ls.s_ins[k]);
                         else
-                            visible = !in_shadow_inline(sc, P, N, lpos);
+                            visible = !in_shadow_inline(sc, P, N, ld3(scg.hdr->light_pos));
                     }
-                    if (pow2) {
+                    if (ls.pow2) {
                         const unsigned long long bal = __ballot(visible);
-                        if (q < total && (lane & (pairs_per_hit - 1u)) == 0u) {
-                            const unsigned long long grp = (pairs_per_hit == 64u) ? bal : ((bal >> lane) & ((1ull << pairs_per_hit) - 1ull));
-                            s_lit[k] = static_cast<uint32_t>(__popcll(grp));
+                        if (q < total && (lane & (ls.pairs_per_hit - 1u)) == 0u) {
+                            const unsigned long long grp = (ls.pairs_per_hit == 64u) ? bal : ((bal >> lane) & ((1ull << ls.pairs_per_hit) - 1ull));
+                            ls.s_lit[k] = static_cast<uint32_t>(__popcll(grp));
                         }
                     } else if (visible) {
-                        atomicAdd(&s_lit[k], 1u);
+                        atomicAdd(&ls.s_lit[k], 1u);
                     }
                 }
             }
@@ -1435,21 +1510,26 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
         shade_round:
             // ---- phase C: a lane per record
             if (threadIdx.x < m) {
+                const RenderParams& p = phase_params(pp);
+                const WaveSpace& ws = p.ws;
+                const mcrt_config& cfg = p.cfg;
+                const LitShape ls(knobs, s_dyn);
+                const int mode = ls.mode;
                 const uint32_t e = base + threadIdx.x;
-                const RecordGeom r = load_geom(ws, posed, e);
+                const RecordGeom r = load_geom(ws, kView != kViewLdsUnposed && p.scene_posed != 0, e);
                 Hit hit;
                 hit.hit = true;
                 hit.p = r.p;
                 hit.n = r.n;
                 hit.tex = texel_color(scg, ws.q_x[e]);  // the colour of the face's texel, from the pool
-                V3 origin = cam_pos;
-                if (r.depth > 0 || dof) {
+                V3 origin = ld3(scg.hdr->cam_pos);
+                if (r.depth > 0 || (cfg.dof_enabled && cfg.aperture > 1e-6f)) {
                     const float4 qo = ws.q_o[0][e];
                     origin = mk(qo.x, qo.y, qo.z);
                 }
-                const uint32_t lit = s_lit[threadIdx.x];
+                const uint32_t lit = ls.s_lit[threadIdx.x];
                 MCRT_HOOK_LIT_SHADED(lit, r)
-                const float vis = (mode == SHADOW_SOFT) ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                const float vis = (mode == SHADOW_SOFT) ? static_cast<float>(lit) / static_cast<float>(ls.S) : (lit ? 1.0f : 0.0f);
                 C4 c = shade(scg, hit, normalize(origin - hit.p), vis);
                 if (cfg.ao_enabled && r.depth == 0) {  // occluded count from the ao stage (e < cap: a primary hit)
                     const float ao = 1.0f - static_cast<float>(ws.lit[1][e]) / static_cast<float>(cfg.ao_samples);
@@ -1464,8 +1544,8 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
     }
 }
 template <int kView>
-__global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p) {
-    lit_body<kView>(scene_blob, p);
+__global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_kernel(const RenderParams p, const uint8_t* __restrict__ scene_blob) {
+    lit_body<kView>(scene_blob, kernarg_params());
 }
 
 // ambient occlusion (raytracer.cpp:38-78, depth 0 only) as one stage over the primary hits, a lane per hit:
@@ -1483,23 +1563,25 @@ __global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_kernel(const uint8
 #define MCRT_AO_WAVES 4
 #endif
 template <int kView>
-__device__ __forceinline__ void ao_body(const uint8_t* __restrict__ scene_blob, const RenderParams& __restrict__ p) {
+__device__ __forceinline__ void ao_body(const uint8_t* __restrict__ scene_blob, const ParamPtr pp) {
     __shared__ int s_wcnt[kBlock / 64];
     __shared__ uint32_t s_list[kBlock];
     __shared__ unsigned long long s_mask[kBlock];
     extern __shared__ __align__(16) unsigned char s_dyn[];
+    // The parameters by phase (kernel_common.h, phase_params): the two halves of a block of hits read them where they begin
     const SceneView scg = view_of(scene_blob);
-    const WaveSpace& ws = p.ws;
-    if (blockIdx.x >= counted(ws, kCntUnits)) return;
-    const typename ViewSel<kView>::type sc = ViewSel<kView>::make(scg, p, s_dyn);
+    if (blockIdx.x >= counted(phase_params(pp).ws, kCntUnits)) return;
+    const typename ViewSel<kView>::type sc = ViewSel<kView>::make(scg, phase_params(pp), s_dyn);
     constexpr bool kPosed = kView != kViewLdsUnposed;
-    const bool posed = kPosed && p.scene_posed != 0;
-    const int A = p.cfg.ao_samples;
-    const float radius = p.cfg.ao_radius;
-    uint32_t* occ_out = ws.lit[1];
-    for_each_unit_block(ws, [&](uint32_t first, uint32_t n) __attribute__((always_inline)) {
+    for_each_unit_block(phase_params(pp).ws, [&](uint32_t first, uint32_t n) __attribute__((always_inline)) {
         bool traced = false;
         if (threadIdx.x < n) {
+            // ---- phase: the meshes the hit's hemisphere of rays can meet
+            const RenderParams& p = phase_params(pp);
+            const WaveSpace& ws = p.ws;
+            const bool posed = kPosed && p.scene_posed != 0;
+            const float radius = p.cfg.ao_radius;
+            uint32_t* occ_out = ws.lit[1];
             const uint32_t e = first + threadIdx.x;
             V3 P, Nraw;
             load_point_normal(ws, posed, e, P, Nraw);
@@ -1514,6 +1596,13 @@ __device__ __forceinline__ void ao_body(const uint8_t* __restrict__ scene_blob, 
         if (traced) s_list[rank] = threadIdx.x;
         __syncthreads();
         if (static_cast<int>(threadIdx.x) < total) {
+            // ---- phase: the packed hits' rays
+            const RenderParams& p = phase_params(pp);
+            const WaveSpace& ws = p.ws;
+            const bool posed = kPosed && p.scene_posed != 0;
+            const int A = p.cfg.ao_samples;
+            const float radius = p.cfg.ao_radius;
+            uint32_t* occ_out = ws.lit[1];
             const uint32_t k = s_list[threadIdx.x];
             const uint32_t e = first + k;
             V3 P, Nraw;
@@ -1548,8 +1637,8 @@ __device__ __forceinline__ void ao_body(const uint8_t* __restrict__ scene_blob, 
     });
 }
 template <int kView>
-__global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p) {
-    ao_body<kView>(scene_blob, p);
+__global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_kernel(const RenderParams p, const uint8_t* __restrict__ scene_blob) {
+    ao_body<kView>(scene_blob, kernarg_params());
 }
 
 // level_shade (general variants): colour of the level, reflection ray, closest hit of the next level →
@@ -1681,69 +1770,80 @@ __device__ __forceinline__ float4 sample_colour(const WaveSpace& ws, uint32_t sl
 }
 template <bool kTransparent>
 __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
-                                             float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams& __restrict__ p,
+                                             float4* __restrict__ out_frame, uchar4* __restrict__ out8, const ParamPtr pp,
                                              const int tile_base) {
     __shared__ ResolveLds<kTransparent> s_lds;
     float4* s_col = s_lds.col;
-    const WaveSpace& ws = p.ws;
-    const mcrt_config& cfg = p.cfg;
+    // The parameters by phase (kernel_common.h, phase_params): a unit reads what it needs of them where it begins; across
+    // the unit loop live its count, the scene view and `pp`.
     const SceneView scg = view_of(scene_blob);
-    const FrameDiv fd(p);
-    const uint32_t dd = static_cast<uint32_t>(p.draws_per_sample);
-    // the colour of sample `sidx` (stream order) of unit d: a miss from its jitter pair — the expressions of `primary`'s
-    // sample loop (tile_renderer.cpp:93-114) — else the chain's fold
-    auto unit_sample = [&](const uint4& d, const TileGeom& tg, const float* draws, uint32_t sidx, uint32_t spp_) __attribute__((always_inline)) -> float4 {
-        const uint32_t slot = d.w + sidx;
-        const uint32_t code = ws.end[slot];
-        if (code != kEndMiss) return sample_colour(ws, slot, code, C4{scg.hdr->background[0], scg.hdr->background[1], scg.hdr->background[2], scg.hdr->background[3]});
-        const uint32_t k = UDiv(spp_).div(sidx);  // pixel of the unit
-        int lx, ly;
-        unit_pixel(d, tg, k, lx, ly);
-        const int px = tg.x + lx, py = tg.y + ly;
-        float jx = 0.5f, jy = 0.5f;
-        if (spp_ > 1u) {
-            const float2 j = *reinterpret_cast<const float2*>(draws + (static_cast<size_t>(ly * tg.w + lx) * spp_ + (sidx - k * spp_)) * dd);  // dd is even: 8-byte aligned
-            jx = j.x, jy = j.y;
+    uint32_t n_units;
+    float frame_w, frame_h, inv_spp;  // formed once (vector-unit conversions and a division), kept as scalars
+    {  // ---- entry
+        const RenderParams& p = phase_params(pp);
+        const WaveSpace& ws = p.ws;
+        n_units = ws.frame_info[0];  // (not from the counters: this kernel moves their base)
+        frame_w = uniform_float(static_cast<float>(p.cfg.width)), frame_h = uniform_float(static_cast<float>(p.cfg.height));
+        inv_spp = uniform_float(1.0f / static_cast<float>(p.cfg.samples_per_pixel > 1 ? static_cast<uint32_t>(p.cfg.samples_per_pixel) : 1u));
+        MCRT_HOOK_RESOLVE_BEGIN()
+        if (blockIdx.x == 0) {  // the pass has counted everything: where the counters stand is the next pass's base
+            for (int i = threadIdx.x; i < kCounterWords - 4; i += kBlock) ws.counter_base[i] = ws.counters[i];
         }
-        const C4 c = background(scg, cfg, fd.u(static_cast<float>(px) + jx), fd.v(static_cast<float>(py) + jy));
-        return make_float4(c.r, c.g, c.b, c.a);
-    };
-    const uint32_t n_units = ws.frame_info[0];  // (not from the counters: this kernel moves their base)
-    const uint32_t spp = cfg.samples_per_pixel > 1 ? static_cast<uint32_t>(cfg.samples_per_pixel) : 1u;
-    const float inv_spp = 1.0f / static_cast<float>(spp);
-    const uint32_t chunk_px = spp <= static_cast<uint32_t>(kBlock) ? static_cast<uint32_t>(kBlock) / spp : 0u;  // pixels per pass (0: a pixel per thread, serially)
-    auto put_pixel = [&](const uint4& d, const TileGeom& tg, uint32_t k, float4 acc) __attribute__((always_inline)) {  // pixel k of unit d
-        int lx, ly;
-        unit_pixel(d, tg, k, lx, ly);
-        const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
-        store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx),
-                    make_float4(acc.x * inv_spp, acc.y * inv_spp, acc.z * inv_spp, acc.w * inv_spp));
-    };
-    // transparent: the colour of a sample whose primary ray hit (else `hit` = false and nothing is formed)
-    auto hit_sample = [&](const uint4& d, uint32_t sidx, bool& hit) __attribute__((always_inline)) -> float4 {
-        const uint32_t slot = d.w + sidx;
-        const uint32_t code = ws.end[slot];
-        hit = code != kEndMiss;
-        if (!hit) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        return sample_colour(ws, slot, code, C4{scg.hdr->background[0], scg.hdr->background[1], scg.hdr->background[2], scg.hdr->background[3]});
-    };
-    // transparent: the sum of the n samples that hit
-    auto put_pixel_transparent = [&](const uint4& d, const TileGeom& tg, uint32_t k, float4 acc, uint32_t n) __attribute__((always_inline)) {
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (n > 0u) {
-            const float inv_n = 1.0f / static_cast<float>(n);
-            v = make_float4(acc.x * inv_n, acc.y * inv_n, acc.z * inv_n, acc.w * inv_spp);
-        }
-        int lx, ly;
-        unit_pixel(d, tg, k, lx, ly);
-        const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
-        store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx), v);
-    };
-    MCRT_HOOK_RESOLVE_BEGIN()
-    if (blockIdx.x == 0) {  // the pass has counted everything: where the counters stand is the next pass's base
-        for (int i = threadIdx.x; i < kCounterWords - 4; i += kBlock) ws.counter_base[i] = ws.counters[i];
     }
     for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        // ---- phase: the unit
+        const RenderParams& p = phase_params(pp);
+        const WaveSpace& ws = p.ws;
+        const mcrt_config& cfg = p.cfg;
+        const FrameDiv fd(frame_w, frame_h, p);
+        const uint32_t dd = static_cast<uint32_t>(p.draws_per_sample);
+        // the colour of sample `sidx` (stream order) of unit d: a miss from its jitter pair — the expressions of `primary`'s
+        // sample loop (tile_renderer.cpp:93-114) — else the chain's fold
+        auto unit_sample = [&](const uint4& d, const TileGeom& tg, const float* draws, uint32_t sidx, uint32_t spp_) __attribute__((always_inline)) -> float4 {
+            const uint32_t slot = d.w + sidx;
+            const uint32_t code = ws.end[slot];
+            if (code != kEndMiss) return sample_colour(ws, slot, code, C4{scg.hdr->background[0], scg.hdr->background[1], scg.hdr->background[2], scg.hdr->background[3]});
+            const uint32_t k = UDiv(spp_).div(sidx);  // pixel of the unit
+            int lx, ly;
+            unit_pixel(d, tg, k, lx, ly);
+            const int px = tg.x + lx, py = tg.y + ly;
+            float jx = 0.5f, jy = 0.5f;
+            if (spp_ > 1u) {
+                const float2 j = *reinterpret_cast<const float2*>(draws + (static_cast<size_t>(ly * tg.w + lx) * spp_ + (sidx - k * spp_)) * dd);  // dd is even: 8-byte aligned
+                jx = j.x, jy = j.y;
+            }
+            const C4 c = background(scg, cfg, fd.u(static_cast<float>(px) + jx), fd.v(static_cast<float>(py) + jy));
+            return make_float4(c.r, c.g, c.b, c.a);
+        };
+        const uint32_t spp = cfg.samples_per_pixel > 1 ? static_cast<uint32_t>(cfg.samples_per_pixel) : 1u;
+        const uint32_t chunk_px = spp <= static_cast<uint32_t>(kBlock) ? static_cast<uint32_t>(kBlock) / spp : 0u;  // pixels per pass (0: a pixel per thread, serially)
+        auto put_pixel = [&](const uint4& d, const TileGeom& tg, uint32_t k, float4 acc) __attribute__((always_inline)) {  // pixel k of unit d
+            int lx, ly;
+            unit_pixel(d, tg, k, lx, ly);
+            const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
+            store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx),
+                        make_float4(acc.x * inv_spp, acc.y * inv_spp, acc.z * inv_spp, acc.w * inv_spp));
+        };
+        // transparent: the colour of a sample whose primary ray hit (else `hit` = false and nothing is formed)
+        auto hit_sample = [&](const uint4& d, uint32_t sidx, bool& hit) __attribute__((always_inline)) -> float4 {
+            const uint32_t slot = d.w + sidx;
+            const uint32_t code = ws.end[slot];
+            hit = code != kEndMiss;
+            if (!hit) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            return sample_colour(ws, slot, code, C4{scg.hdr->background[0], scg.hdr->background[1], scg.hdr->background[2], scg.hdr->background[3]});
+        };
+        // transparent: the sum of the n samples that hit
+        auto put_pixel_transparent = [&](const uint4& d, const TileGeom& tg, uint32_t k, float4 acc, uint32_t n) __attribute__((always_inline)) {
+            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (n > 0u) {
+                const float inv_n = 1.0f / static_cast<float>(n);
+                v = make_float4(acc.x * inv_n, acc.y * inv_n, acc.z * inv_n, acc.w * inv_spp);
+            }
+            int lx, ly;
+            unit_pixel(d, tg, k, lx, ly);
+            const int row = (p.layout == MCRT_LAYOUT_PACKED) ? ((p.shard.pack_first + tg.owned_row * p.shard.pack_step) * cfg.tile_size + ly) : (tg.y + ly);
+            store_pixel(out_frame, out8, static_cast<size_t>(row) * cfg.width + (tg.x + lx), v);
+        };
         const uint4 d = ws.units[u];
         const int tile = unit_tile(d);
         const TileGeom tg = tile_of(p, tile);
@@ -1809,14 +1909,13 @@ __device__ __forceinline__ void resolve_body(const uint8_t* __restrict__ scene_b
         }
     }
 }
-__global__ __launch_bounds__(kBlock) void resolve_kernel(const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
-                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8, const RenderParams p,
-                                                         const int tile_base) {
-    resolve_body<false>(scene_blob, tile_draws, out_frame, out8, p, tile_base);
+__global__ __launch_bounds__(kBlock) void resolve_kernel(const RenderParams p, const uint8_t* __restrict__ scene_blob, const float* __restrict__ tile_draws,
+                                                         float4* __restrict__ out_frame, uchar4* __restrict__ out8, const int tile_base) {
+    resolve_body<false>(scene_blob, tile_draws, out_frame, out8, kernarg_params(), tile_base);
 }
-__global__ __launch_bounds__(kBlock) void resolve_transparent_kernel(const uint8_t* __restrict__ scene_blob, float4* __restrict__ out_frame,
-                                                                     uchar4* __restrict__ out8, const RenderParams p, const int tile_base) {
-    resolve_body<true>(scene_blob, nullptr, out_frame, out8, p, tile_base);
+__global__ __launch_bounds__(kBlock) void resolve_transparent_kernel(const RenderParams p, const uint8_t* __restrict__ scene_blob, float4* __restrict__ out_frame,
+                                                                     uchar4* __restrict__ out8, const int tile_base) {
+    resolve_body<true>(scene_blob, nullptr, out_frame, out8, kernarg_params(), tile_base);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1848,25 +1947,23 @@ __global__ __launch_bounds__(kBlock, MCRT_BG_WAVES) void background_batch_kernel
 template <int kView>
 __global__ __launch_bounds__(kBlock, MCRT_PRIMARY_WAVES) void primary_batch_kernel(ParamTable table, const int n_tiles) {
     const RenderParams& p = frame_params(table);
-    primary_body<kView>(p.scene, p.draw_plate ? p.draw_plate : p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0, n_tiles);
+    primary_body<kView>(p.scene, p.draw_plate ? p.draw_plate : p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), table + blockIdx.y, 0, n_tiles);
 }
 template <int kView>
 __global__ __launch_bounds__(kBlock, MCRT_AO_WAVES) void ao_batch_kernel(ParamTable table) {
-    const RenderParams& p = frame_params(table);
-    ao_body<kView>(p.scene, p);
+    ao_body<kView>(frame_params(table).scene, table + blockIdx.y);
 }
 template <int kView>
 __global__ __launch_bounds__(kBlock, MCRT_LIT_WAVES) void lit_batch_kernel(ParamTable table) {
-    const RenderParams& p = frame_params(table);
-    lit_body<kView>(p.scene, p);
+    lit_body<kView>(frame_params(table).scene, table + blockIdx.y);
 }
 __global__ __launch_bounds__(kBlock) void resolve_batch_kernel(ParamTable table) {
     const RenderParams& p = frame_params(table);
-    resolve_body<false>(p.scene, p.draw_plate ? p.draw_plate : p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
+    resolve_body<false>(p.scene, p.draw_plate ? p.draw_plate : p.ws.tile_draws, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), table + blockIdx.y, 0);
 }
 __global__ __launch_bounds__(kBlock) void resolve_transparent_batch_kernel(ParamTable table) {
     const RenderParams& p = frame_params(table);
-    resolve_body<true>(p.scene, nullptr, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), p, 0);
+    resolve_body<true>(p.scene, nullptr, reinterpret_cast<float4*>(p.out), reinterpret_cast<uchar4*>(p.out8), table + blockIdx.y, 0);
 }
 
 // ---- host-side launchers (the planning that sizes them: render_plan.cpp) ----------------------------
@@ -1889,9 +1986,9 @@ static void launch_levels(const RenderParams& p, hipStream_t stream, size_t dyn)
     }
     const int ao_grid = p.grid_ao > 0 ? p.grid_ao : kQueueGrid, lit_grid = p.grid_lit > 0 ? p.grid_lit : kQueueGrid;
     if (c.ao_enabled && c.ao_samples > 0) {  // ahead of `lit`, whose last phase applies the AO factor
-        hipLaunchKernelGGL(ao_kernel<kView>, dim3(ao_grid), dim3(kBlock), dyn, stream, p.scene, p);
+        hipLaunchKernelGGL(ao_kernel<kView>, dim3(ao_grid), dim3(kBlock), dyn, stream, p, p.scene);
     }
-    hipLaunchKernelGGL(lit_kernel<kView>, dim3(lit_grid), dim3(kBlock), static_cast<size_t>(p.lit_lds_offset) + static_cast<size_t>(p.lit_lds_bytes), stream, p.scene, p);
+    hipLaunchKernelGGL(lit_kernel<kView>, dim3(lit_grid), dim3(kBlock), static_cast<size_t>(p.lit_lds_offset) + static_cast<size_t>(p.lit_lds_bytes), stream, p, p.scene);
 }
 
 hipError_t launch_seed_tiles(const RenderParams& p, hipStream_t stream) {
@@ -1928,14 +2025,14 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
         with_view(p.scene_in_lds ? (p.scene_posed ? kViewLds : kViewLdsUnposed) : kViewHbm, [&](auto v) {
             constexpr int kView = decltype(v)::value;
             const size_t view_dyn = kView == kViewHbm ? 0 : dyn;
-            hipLaunchKernelGGL(primary_kernel<kView>, dim3(pgrid), dim3(kBlock), view_dyn, stream, p.scene, draws, out, out8, p, tile_base, batch_tiles);
+            hipLaunchKernelGGL(primary_kernel<kView>, dim3(pgrid), dim3(kBlock), view_dyn, stream, p, p.scene, draws, out, out8, tile_base, batch_tiles);
             launch_levels<kView>(p, stream, view_dyn);
         });
         const int rgrid = batch_tiles * p.parts_per_tile < resolve_grid ? batch_tiles * p.parts_per_tile : resolve_grid;
         if (p.background == MCRT_BACKGROUND_TRANSPARENT)
-            hipLaunchKernelGGL(resolve_transparent_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, out, out8, p, tile_base);
+            hipLaunchKernelGGL(resolve_transparent_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p, p.scene, out, out8, tile_base);
         else
-            hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p.scene, draws, out, out8, p, tile_base);
+            hipLaunchKernelGGL(resolve_kernel, dim3(rgrid), dim3(kBlock), 0, stream, p, p.scene, draws, out, out8, tile_base);
         const int batch = r0 / p.rows_per_batch;
         if (marks && batch < marks->n_batch_done) {
             e = hipEventRecord(marks->batch_done[batch], stream);
