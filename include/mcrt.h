@@ -316,6 +316,52 @@ int mcrt_render_batch_ex(const mcrt_scene_desc* const* scenes, int n_frames, con
 /* mcrt_render_png with a background mode (the transparent PNG: colour type 6, straight alpha) */
 int mcrt_render_png_ex(const mcrt_scene_desc* scene, const mcrt_config* cfg, int background, const char* path, int device);
 
+/* ---- extra lights: fill and rim lights in the beauty render ------------------------------------------------------------
+ * The reference's Scene has one Light; a handle carries 0 to MCRT_MAX_EXTRA_LIGHTS more: light_1 .. light_K behind light_0,
+ * the scene's own.  With K = 0 nothing changes anywhere.  With K >= 1 RayTracer::traceRay (raytracer.cpp:82-148) changes in
+ * exactly one place — lines 107-117 become, in float32:
+ *
+ *     seed as today (one shadowSeed per hit and depth, shared by all lights)
+ *     for k = 0 .. K:
+ *         vis_k = config && softShadows && shadowSamples > 1
+ *                   ? computeSoftShadow(hit.point, hit.normal, light_k, scene, shadowSamples, shadowSeed)
+ *                   : -1
+ *     C   = shade(hit, viewDir, light_0, scene, ShadingParams{}, vis_0)
+ *     E_k = shade(hit, viewDir, light_k, scene, ShadingParams{kd, ks, ambient = 0, shininess}, vis_k)      k = 1 .. K
+ *     shadedColor.rgb = clamp(((C.rgb + E_1.rgb) + E_2.rgb) + E_3.rgb, 0, 1);   shadedColor.a = C.a
+ *
+ * computeSoftShadow (shading.cpp:28-60) decides by light_k's OWN radius between the disk and the single ray (:30), and every
+ * light draws the SAME 2 * shadowSamples mt19937 draws of the hit: one seeding chain per hit, K + 1 disks.  vis_k = -1 is
+ * shade()'s own isInShadow test with the normalised normal (:76-81).  C and every E_k are clamped by shade() itself (:95),
+ * the sum runs left to right.  Ambient occlusion at depth 0, the reflection fold (:133-147), renderTile's sample loop and
+ * the background are untouched.  A light whose colour is (0, 0, 0) adds exactly +0: the frame is then the single-light frame
+ * bit for bit.
+ * The beauty renders of a handle honour its extra lights: mcrt_render_device[_ex], mcrt_time_render_device, the handle's
+ * frame in mcrt_render_batch_device (it is then enqueued on its own), row shards and both background modes.  The lights
+ * survive mcrt_scene_set_skin* and mcrt_scene_set_view*.  The passes whose result depends on the light — ground shadow,
+ * reflection, light layers, light bake and every studio-shot entry — return MCRT_ERR_INVALID ("extra lights: beauty render
+ * only") for a handle with K >= 1, and work again after n = 0; layers, picks and ground occlusion run unchanged.
+ * mcrt_probe_trace ignores extra lights. */
+#define MCRT_MAX_EXTRA_LIGHTS 3
+typedef struct mcrt_light_source {
+    float position[3];
+    float radius;   /* < 1e-4: a point light */
+    float color[4]; /* rgb; the fourth channel is not read */
+} mcrt_light_source; /* 32 bytes */
+/* n = 0: none, the handle is as before.  A NULL handle, n < 0 or n > MCRT_MAX_EXTRA_LIGHTS, lights NULL with n > 0, a
+ * position, radius or colour component that is not finite → MCRT_ERR_INVALID, before any device work.  Host state only:
+ * renders enqueued before the call keep the lights they were enqueued with. */
+int mcrt_scene_set_extra_lights(mcrt_scene* scene, const mcrt_light_source* lights, int n);
+/* Returns the handle's count and copies min(count, capacity) lights into out (which may be NULL); a NULL handle: 0. */
+int mcrt_scene_extra_lights(const mcrt_scene* scene, mcrt_light_source* out, int capacity);
+/* mcrt_render_ex with extra lights (n_lights = 0: mcrt_render_ex itself); the same argument checks as
+ * mcrt_scene_set_extra_lights, right behind the NULL-argument checks. */
+int mcrt_render_lights(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights, int background,
+                       float* out_rgba, uint8_t* out_rgba8, mcrt_progress_fn progress, void* user, const int* devices, int n_devices, int gather);
+/* mcrt_render_png_ex with extra lights */
+int mcrt_render_png_lights(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights, int background,
+                           const char* path, int device);
+
 /* ---- geometry layers: what is under each pixel ----------------------------------------------------------------------
  * One ray per pixel through the pixel centre — u = (px + 0.5f) / width, v = (py + 0.5f) / height, Camera::generateRay(u, v,
  * (float)width / (float)height): the reference's own primary ray at samplesPerPixel == 1 without depth of field
@@ -1041,7 +1087,7 @@ int mcrt_probe_units(mcrt_scene* scene, uint32_t* records, uint32_t* hits, int c
 /* intersectScene (intersection.cpp:408-421) for n rays; rays = n*6 floats (origin, direction) */
 int mcrt_probe_intersect(mcrt_scene* scene, const float* rays, int n, mcrt_hit* out);
 /* RayTracer::traceRay(ray, scene, depth, maxBounces, ShadingParams{}, &cfg) (raytracer.cpp:82-148)
- * for n rays; out = n*4 floats */
+ * for n rays; out = n*4 floats.  The handle's extra lights are ignored: the probe is the reference's own function. */
 int mcrt_probe_trace(mcrt_scene* scene, const mcrt_config* cfg, const float* rays, int n, int depth,
                      float* out_rgba);
 /* first n outputs of uniform_real_distribution<float>(0,1) over std::mt19937(seed) for each seed */

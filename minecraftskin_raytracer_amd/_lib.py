@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_render_shot_batch_ex", "mcrt_render_shot_png_ex",
     "mcrt_build_skin_scene_model", "mcrt_scene_create_skin_model", "mcrt_skin_texel_model", "mcrt_skin_pool_map_model",
     "mcrt_skin_view_table_model", "mcrt_skin_model_of",
+    "mcrt_scene_set_extra_lights", "mcrt_scene_extra_lights", "mcrt_render_lights", "mcrt_render_png_lights",
 ]
 
 
@@ -70,6 +71,7 @@ def load():
     bake_p = C.POINTER(abi.McrtBakePlanes)
     shot_p = C.POINTER(abi.McrtShot)
     shot_ex_p = C.POINTER(abi.McrtShotEx)
+    lights_p = C.POINTER(abi.McrtLightSource)
     sig = {
         "mcrt_config_init": (None, [cfg_p]),
         "mcrt_generate_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(abi.McrtTile), C.c_int]),
@@ -92,6 +94,10 @@ def load():
         "mcrt_render_ex": (C.c_int, [desc_p, cfg_p, C.c_int, f_p, u8_p, abi.PROGRESS_FN, vp, C.POINTER(C.c_int), C.c_int, C.c_int]),
         "mcrt_render_batch_ex": (C.c_int, [C.POINTER(desc_p), C.c_int, cfg_p, C.c_int, f_p, u8_p, C.c_int]),
         "mcrt_render_png_ex": (C.c_int, [desc_p, cfg_p, C.c_int, C.c_char_p, C.c_int]),
+        "mcrt_scene_set_extra_lights": (C.c_int, [vp, lights_p, C.c_int]),
+        "mcrt_scene_extra_lights": (C.c_int, [vp, lights_p, C.c_int]),
+        "mcrt_render_lights": (C.c_int, [desc_p, cfg_p, lights_p, C.c_int, C.c_int, f_p, u8_p, abi.PROGRESS_FN, vp, C.POINTER(C.c_int), C.c_int, C.c_int]),
+        "mcrt_render_png_lights": (C.c_int, [desc_p, cfg_p, lights_p, C.c_int, C.c_int, C.c_char_p, C.c_int]),
         "mcrt_render_layers_device": (C.c_int, [vp, cfg_p, layers_p, vp]),
         "mcrt_render_layers_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, layers_p, C.c_size_t, vp]),
         "mcrt_render_layers": (C.c_int, [desc_p, cfg_p, layers_p, C.c_int]),

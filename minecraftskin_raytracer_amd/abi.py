@@ -359,6 +359,52 @@ _shot_init.__doc__ = _shot_fields_init.__doc__
 Shot.__init__ = _shot_init
 
 
+MAX_EXTRA_LIGHTS = 3  # MCRT_MAX_EXTRA_LIGHTS: the lights a handle carries beside the scene's own
+
+
+class McrtLightSource(C.Structure):
+    """mcrt_light_source: one extra light (include/mcrt.h, "extra lights")."""
+
+    _fields_ = [("position", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 4)]
+
+
+assert C.sizeof(McrtLightSource) == 32
+
+
+@dataclass
+class Light:
+    """An extra light — a fill or rim light beside the scene's own: the reference's Light{position, color, radius}.  A radius
+    below 1e-4 is a point light.  Of ``color`` the first three channels count."""
+
+    position: Sequence[float]
+    color: Sequence[float] = (1.0, 1.0, 1.0, 1.0)
+    radius: float = 3.0
+
+    def to_c(self) -> McrtLightSource:
+        if len(self.position) != 3 or len(self.color) not in (3, 4):
+            raise ValueError("a Light takes a position of three coordinates and a colour of three or four channels")
+        l = McrtLightSource()
+        for i in range(3):
+            l.position[i] = float(self.position[i])
+        for i in range(4):
+            l.color[i] = float(self.color[i]) if i < len(self.color) else 1.0
+        l.radius = float(self.radius)
+        return l
+
+
+def light_array(lights):
+    """(ctypes array or None, count) of a sequence of ``Light`` (None or empty: no extra lights) for the entries that take them."""
+    lights = list(lights) if lights is not None else []
+    if len(lights) > MAX_EXTRA_LIGHTS:
+        raise ValueError(f"at most {MAX_EXTRA_LIGHTS} extra lights, not {len(lights)}")
+    for l in lights:
+        if not isinstance(l, Light):
+            raise TypeError(f"extra lights are abi.Light values, not {type(l).__name__}")
+    if not lights:
+        return None, 0
+    return (McrtLightSource * len(lights))(*[l.to_c() for l in lights]), len(lights)
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 
 SURFACE_DTYPE = np.dtype(

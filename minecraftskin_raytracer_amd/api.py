@@ -176,7 +176,7 @@ class TileRenderer:
 
     @staticmethod
     def render(scene, config: Config, progressCallback: Optional[Callable[[int, int], None]] = None,
-               device=0, gather: bool = False, out: Optional[np.ndarray] = None, background: str = "reference") -> Image:
+               device=0, gather: bool = False, out: Optional[np.ndarray] = None, background: str = "reference", lights=None) -> Image:
         """TileRenderer::render.  Per-frame failures never raise (tile_renderer.cpp:158-166): they are
         recorded as one ``(-1, message)`` entry in ``lastErrors()`` and the image keeps Color() =
         (0,0,0,1) pixels.
@@ -186,8 +186,10 @@ class TileRenderer:
         device instead of per-device downloads).  ``out``: a (H, W, 4) float32 C-contiguous array to render
         into (the reference returns a fresh Image per call; a caller that renders repeatedly can keep one).
         ``background``: ``"reference"`` (the default) or ``"transparent"`` — the figure alone, straight alpha, pixels
-        without a hit (0,0,0,0) (MCRT_BACKGROUND_TRANSPARENT, include/mcrt.h)."""
+        without a hit (0,0,0,0) (MCRT_BACKGROUND_TRANSPARENT, include/mcrt.h).  ``lights``: up to three ``abi.Light`` — fill
+        and rim lights beside the scene's own (include/mcrt.h, "extra lights")."""
         mode = abi.background_mode(background)
+        extra, n_extra = abi.light_array(lights)
         lib = load()
         d = _as_desc(scene)
         c = config.to_c()
@@ -201,7 +203,13 @@ class TileRenderer:
             return out
         cb = abi.PROGRESS_FN((lambda done, total, _u: progressCallback(done, total))) if progressCallback else C.cast(None, abi.PROGRESS_FN)
         one, devs = _devices(device)
-        if mode != abi.BACKGROUND_REFERENCE:
+        if n_extra:
+            if one is not None:
+                devs = [one]
+            arr = (C.c_int * max(len(devs), 1))(*devs)
+            rc = lib.mcrt_render_lights(d.ptr, C.byref(c), extra, n_extra, mode, abi.fptr(out), None, cb, None, arr if devs else None, len(devs),
+                                        1 if gather else 0)
+        elif mode != abi.BACKGROUND_REFERENCE:
             if one is not None:
                 devs = [one]
             arr = (C.c_int * max(len(devs), 1))(*devs)
@@ -231,11 +239,12 @@ class TileRenderer:
             TileRenderer._errors.append((-1, lib.mcrt_last_error().decode("utf-8", "replace")))
 
     @staticmethod
-    def renderRGBA8(scene, config: Config, device=0, gather: bool = False, background: str = "reference") -> np.ndarray:
+    def renderRGBA8(scene, config: Config, device=0, gather: bool = False, background: str = "reference", lights=None) -> np.ndarray:
         """The frame as the RGBA8 plane ImageWriter::writePNG would encode ((H, W, 4) uint8), quantised in the kernels'
-        epilogue: 4 B per pixel over PCIe / xGMI instead of 16 (mcrt_render_rgba8).  ``device`` and ``background`` as for
-        ``render``."""
+        epilogue: 4 B per pixel over PCIe / xGMI instead of 16 (mcrt_render_rgba8).  ``device``, ``background`` and ``lights``
+        as for ``render``."""
         mode = abi.background_mode(background)
+        extra, n_extra = abi.light_array(lights)
         lib = load()
         c = config.to_c()
         w, h, no_frame = _frame(config)
@@ -247,7 +256,10 @@ class TileRenderer:
         if one is not None:
             devs = [one]
         arr = (C.c_int * max(len(devs), 1))(*devs)
-        if mode != abi.BACKGROUND_REFERENCE:
+        if n_extra:
+            rc = lib.mcrt_render_lights(_as_desc(scene).ptr, C.byref(c), extra, n_extra, mode, None, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        C.cast(None, abi.PROGRESS_FN), None, arr if devs else None, len(devs), 1 if gather else 0)
+        elif mode != abi.BACKGROUND_REFERENCE:
             rc = lib.mcrt_render_ex(_as_desc(scene).ptr, C.byref(c), mode, None, out.ctypes.data_as(C.POINTER(C.c_uint8)),
                                     C.cast(None, abi.PROGRESS_FN), None, arr if devs else None, len(devs), 1 if gather else 0)
         else:
@@ -578,11 +590,15 @@ class ImageWriter:
         return bytes(buf[:got])
 
 
-def render_png(scene, config: Config, path: str, device: int = 0, background: str = "reference") -> bool:
+def render_png(scene, config: Config, path: str, device: int = 0, background: str = "reference", lights=None) -> bool:
     """TileRenderer::render + ImageWriter::writePNG in one call (RGBA8 quantised in the kernel epilogue,
-    4 B/pixel copied back).  ``background="transparent"``: the figure alone on a transparent background (straight alpha)."""
+    4 B/pixel copied back).  ``background="transparent"``: the figure alone on a transparent background (straight alpha).
+    ``lights``: extra lights, as for ``TileRenderer.render``."""
     mode = abi.background_mode(background)
     c = config.to_c()
+    extra, n_extra = abi.light_array(lights)
+    if n_extra:
+        return load().mcrt_render_png_lights(_as_desc(scene).ptr, C.byref(c), extra, n_extra, mode, os.fsencode(path), device) == 0
     if mode != abi.BACKGROUND_REFERENCE:
         return load().mcrt_render_png_ex(_as_desc(scene).ptr, C.byref(c), mode, os.fsencode(path), device) == 0
     return load().mcrt_render_png(_as_desc(scene).ptr, C.byref(c), os.fsencode(path), device) == 0
@@ -864,6 +880,20 @@ class DeviceScene:
         (mcrt_scene_set_background)."""
         m = abi.background_mode(mode)
         check(load().mcrt_scene_set_background(self._h, m))
+
+    def set_extra_lights(self, lights) -> None:
+        """Up to three ``abi.Light`` beside the scene's own for every later beauty render of this handle, batches included; an
+        empty sequence takes them off (mcrt_scene_set_extra_lights).  The passes that depend on the light refuse the handle
+        while it carries any."""
+        extra, n = abi.light_array(lights)
+        check(load().mcrt_scene_set_extra_lights(self._h, extra, n))
+
+    @property
+    def extra_lights(self) -> List[abi.Light]:
+        """The handle's extra lights (mcrt_scene_extra_lights)."""
+        buf = (abi.McrtLightSource * abi.MAX_EXTRA_LIGHTS)()
+        n = int(load().mcrt_scene_extra_lights(self._h, buf, abi.MAX_EXTRA_LIGHTS))
+        return [abi.Light(tuple(buf[i].position), tuple(buf[i].color), float(buf[i].radius)) for i in range(n)]
 
     def owned_pixel_rows(self, config: Config, first: int = 0, step: int = 1) -> int:
         c = config.to_c()
@@ -1259,6 +1289,12 @@ class SkinBatch:
             self.close()
         except Exception:
             pass
+
+    def set_extra_lights(self, lights) -> None:
+        """The same extra lights (``DeviceScene.set_extra_lights``) for every scene of the batch; ``render`` then enqueues each
+        frame on its own (``render_batch_device`` sends such frames through the single-frame path), and ``shots`` refuses."""
+        for s in self.scenes + self.slim_scenes:
+            s.set_extra_lights(lights)
 
     def set_views(self, poses=None, looks=None) -> None:
         """Another pose and / or look for the batch's scenes without rebuilding them (``set_views_batch_device``): ``poses`` —

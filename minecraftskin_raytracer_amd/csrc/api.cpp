@@ -124,6 +124,7 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     }
     s->forced_lanes = 0;
     s->background = MCRT_BACKGROUND_REFERENCE;
+    s->extra = mcrt::LightSet{};  // a pooled shell's extra lights go with its previous scene
     if (s->skin_tables) release_skin_tables(device, s->skin_height, s->skin_model);  // a pooled shell that was a repaintable handle
     s->skin_tables = nullptr;
     s->skin_height = 0;
@@ -326,6 +327,19 @@ int mcrt_scene_set_background(mcrt_scene* s, int background) {
     return MCRT_OK;
 }
 
+int mcrt_scene_set_extra_lights(mcrt_scene* s, const mcrt_light_source* lights, int n) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (const int rc = check_extra_lights(lights, n); rc != MCRT_OK) return rc;
+    s->extra = light_set_of(lights, n);
+    return MCRT_OK;
+}
+
+int mcrt_scene_extra_lights(const mcrt_scene* s, mcrt_light_source* out, int capacity) {
+    if (!s) return 0;
+    for (int i = 0; out && i < s->extra.n_extra && i < capacity; ++i) out[i] = s->extra.extra[i];
+    return s->extra.n_extra;
+}
+
 int mcrt_owned_pixel_rows(const mcrt_config* cfg, int first, int step) {
     if (!cfg || !valid_frame(cfg)) return 0;
     Shard sh = make_shard(*cfg, first, step);
@@ -334,6 +348,16 @@ int mcrt_owned_pixel_rows(const mcrt_config* cfg, int first, int step) {
 
 }  // extern "C"
 namespace {
+
+// The extra lights of the one-shot renders the calling thread makes while a OneShotLights lives (mcrt_render_lights & co): the
+// shells render_to_host creates take them.  nullptr: none.
+thread_local const mcrt::LightSet* t_one_shot_lights = nullptr;
+struct OneShotLights {
+    explicit OneShotLights(const mcrt::LightSet* set) { t_one_shot_lights = set; }
+    ~OneShotLights() { t_one_shot_lights = nullptr; }
+    OneShotLights(const OneShotLights&) = delete;
+    OneShotLights& operator=(const OneShotLights&) = delete;
+};
 
 struct CopySpan {  // a contiguous run: device bytes → host bytes
     const char* src;
@@ -434,6 +458,7 @@ int render_to_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, void* ou
         // for a host-buffer render the download, not the chain of kernels, is the longer part.
         s->forced_lanes = 1;
         s->background = background;
+        if (t_one_shot_lights) s->extra = *t_one_shot_lights;
         rc = one_shot_streams(s);
         if (rc != MCRT_OK) break;
         const Shard mine = make_shard(*cfg, r, n_ranks);
@@ -827,6 +852,25 @@ int mcrt_render_png_ex(const mcrt_scene_desc* desc, const mcrt_config* cfg, int 
     if (!desc || !cfg || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
     if (!valid_background(background)) return bad_background();
     return render_png_impl(desc, cfg, path, device, background);
+}
+
+// ---- extra lights, one-shot forms (mcrt.h, "extra lights") ------------------------------------------
+int mcrt_render_lights(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights, int background,
+                       float* out_rgba, uint8_t* out_rgba8, mcrt_progress_fn progress, void* user, const int* devices, int n_devices, int gather) {
+    if (!desc || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (const int rc = check_extra_lights(lights, n_lights); rc != MCRT_OK) return rc;
+    const mcrt::LightSet set = light_set_of(lights, n_lights);
+    const OneShotLights carried(&set);
+    return mcrt_render_ex(desc, cfg, background, out_rgba, out_rgba8, progress, user, devices, n_devices, gather);
+}
+
+int mcrt_render_png_lights(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights, int background,
+                           const char* path, int device) {
+    if (!desc || !cfg || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (const int rc = check_extra_lights(lights, n_lights); rc != MCRT_OK) return rc;
+    const mcrt::LightSet set = light_set_of(lights, n_lights);
+    const OneShotLights carried(&set);
+    return mcrt_render_png_ex(desc, cfg, background, path, device);
 }
 
 int mcrt_last_timings(mcrt_timings* out) {

@@ -114,6 +114,11 @@ struct mcrt_scene {
     // the three words the no-device tests already own, so their zeroed blocks stay classic handles.  The batch entries' argument
     // checks do not read it (handles of both models may be mixed); what follows them does.
     int skin_model = 0;
+    // The handle's extra lights (mcrt.h, "extra lights"; mcrt_scene_set_extra_lights), unused entries zero.  Directly behind the
+    // four words above: the passes that refuse a handle with extra lights read the count behind their other argument checks,
+    // and the zeroed blocks of the no-device tests then read 0.  Host state only — a render's launches carry a copy as a kernel
+    // argument — so a change needs no ordering against renders in flight.  Reset where a pooled shell is reused.
+    mcrt::LightSet extra = {};
     uint32_t alpha_words = 0;
     uint32_t n_meshes = 0;
     bool posed = false;  // any mesh with MESH_ROTATED
@@ -137,6 +142,7 @@ struct mcrt_scene {
     struct Recorded {
         int n_lanes = 0;
         mcrt::RenderParams p[kMaxLanes];
+        mcrt::LightSet lights = {};  // the extra lights the launches carry: part of what a replay must match
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         unsigned long long last_use = 0;
@@ -205,6 +211,31 @@ inline bool stream_capturing(hipStream_t stream) {  // the caller records a grap
 inline bool valid_frame(const mcrt_config* c) { return c->width > 0 && c->height > 0 && c->tile_size > 0; }
 inline bool valid_background(int b) { return b == MCRT_BACKGROUND_REFERENCE || b == MCRT_BACKGROUND_TRANSPARENT; }
 inline int bad_background() { return fail(MCRT_ERR_INVALID, "background must be MCRT_BACKGROUND_REFERENCE or MCRT_BACKGROUND_TRANSPARENT"); }
+// what the passes whose result depends on the light refuse (mcrt.h, "extra lights"), behind their other argument checks
+inline int refuse_extra_lights(mcrt_scene* const* scenes, int n) {
+    for (int i = 0; i < n; ++i)
+        if (scenes[i]->extra.n_extra > 0) return fail(MCRT_ERR_INVALID, "extra lights: beauty render only (mcrt_scene_set_extra_lights with n = 0 takes them off)");
+    return MCRT_OK;
+}
+// a list of extra lights as mcrt_scene_set_extra_lights and mcrt_render_lights take it
+inline int check_extra_lights(const mcrt_light_source* lights, int n) {
+    if (n < 0 || n > MCRT_MAX_EXTRA_LIGHTS) return fail(MCRT_ERR_INVALID, "a handle takes 0 to 3 extra lights (MCRT_MAX_EXTRA_LIGHTS)");
+    if (n > 0 && !lights) return fail(MCRT_ERR_INVALID, "lights is NULL");
+    for (int i = 0; i < n; ++i) {
+        const mcrt_light_source& l = lights[i];
+        bool finite = std::isfinite(l.radius);
+        for (const float v : l.position) finite = finite && std::isfinite(v);
+        for (const float v : l.color) finite = finite && std::isfinite(v);
+        if (!finite) return fail(MCRT_ERR_INVALID, "an extra light's position, radius and colour must be finite");
+    }
+    return MCRT_OK;
+}
+inline mcrt::LightSet light_set_of(const mcrt_light_source* lights, int n) {
+    mcrt::LightSet set = {};
+    set.n_extra = n;
+    for (int i = 0; i < n; ++i) set.extra[i] = lights[i];
+    return set;
+}
 inline bool no_plane(const mcrt_layers* l) { return !l->depth && !l->normal && !l->albedo && !l->id; }
 inline bool no_plane(const mcrt_ground* g) { return !g->visibility && !g->distance && !g->matte; }
 inline bool no_plane(const mcrt_ground_occlusion* g) { return !g->occlusion && !g->matte; }

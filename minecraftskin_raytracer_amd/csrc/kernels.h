@@ -150,6 +150,16 @@ struct RenderParams {
                            //    row-major order); the shard is then one tile row of one tile
 };
 
+// ---- extra lights (include/mcrt.h, "extra lights"): the handle's lights 1 .. n_extra; light 0 is the scene header's.  They
+// travel as an argument of their own to the kernels that read them (render_kernels.hip, "extra lights") and are no part of
+// RenderParams: a larger RenderParams would move the arguments of every kernel that was there before.
+constexpr int kMaxLights = MCRT_MAX_EXTRA_LIGHTS + 1;
+struct LightSet {
+    int n_extra;
+    int reserved[3];
+    mcrt_light_source extra[MCRT_MAX_EXTRA_LIGHTS];
+};
+
 // ======== planning (render_plan.cpp): pure host code ========
 Shard make_shard(const mcrt_config& cfg, int first, int step);
 inline int owned_tiles(const RenderParams& p) { return p.shard.owned_rows * p.shard.tiles_x; }
@@ -192,7 +202,8 @@ struct WorkspaceBytes {
     size_t tile_rng, tile_draws, scol, end, units, unit_hits, tile_mask, queue_each, texel_refs, targets, cand, lit0, lit1, stack, counters, hit_rng;
 };
 // row_touched[j]: upper bound of the tiles meshes can touch in owned tile row j (NULL: every tile).
-WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched);
+// extra_lights > 0: the general variants, with `targets`, `cand` and `lit` sized for extra_lights + 1 lights per record.
+WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched, int extra_lights = 0);
 // fills p.shared_device, p.grid_* and p.stream_waves (MCRT_*_GRID / MCRT_STREAM_WAVES override, development knobs)
 void choose_grids(RenderParams& p, bool shared_device, bool company);  // company: other frames or lanes run beside this launch set
 constexpr int kCounterWords = 4096;
@@ -515,7 +526,8 @@ struct LaunchMarks {
     hipEvent_t* batch_done = nullptr;
     int n_batch_done = 0;
 };
-hipError_t launch_render(const RenderParams& p, hipStream_t stream, const LaunchMarks* marks = nullptr);
+// lights with n_extra > 0 (p planned for them: plan_workspace): the levels run the multi-light stages
+hipError_t launch_render(const RenderParams& p, hipStream_t stream, const LaunchMarks* marks = nullptr, const LightSet* lights = nullptr);
 // Fills `plate` for p's configuration (p: any eligible frame's parameters; its shard, layout and outputs are not read).
 // `tile_rng` is scratch of bg_plate_rng_bytes(p) bytes.  Enqueues on `stream`; the caller synchronises.
 hipError_t launch_fill_bg_plate(const RenderParams& p, float4* plate, uint32_t* tile_rng, hipStream_t stream);

@@ -160,7 +160,7 @@ int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int fir
         touched_tiles_per_row(sc, *cfg, p.shard, row_touched);
     for (;;) {
         if (!sc->budget) sc->budget = workspace_budget(sc->device);
-        w = plan_workspace(p, sc->budget / static_cast<size_t>(n_lanes), row_touched.empty() ? nullptr : row_touched.data());
+        w = plan_workspace(p, sc->budget / static_cast<size_t>(n_lanes), row_touched.empty() ? nullptr : row_touched.data(), rect ? 0 : sc->extra.n_extra);
         if (p.rows_per_batch <= 0 && p.shard.owned_rows > 0)
             return fail(MCRT_ERR_INVALID, "one tile row holds more than 2^31 samples (width x tile size x samples per pixel)");
         hipError_t e = hipSuccess;
@@ -228,17 +228,18 @@ int prepare(mcrt_scene* sc, int li, int n_lanes, const mcrt_config* cfg, int fir
 // the launches of one render on `stream`: lanes fork from and join the stream
 // marks: per lane, or nullptr
 int launch_lanes(mcrt_scene* s, const RenderParams* p, int n_lanes, hipStream_t stream, const LaunchMarks* marks = nullptr) {
+    const LightSet* lights = (s->extra.n_extra > 0 && p[0].rect_w <= 0) ? &s->extra : nullptr;  // (prepare planned the workspace for them)
     if (n_lanes > 1) {
         if (!s->fork) HIP_TRY(hipEventCreateWithFlags(&s->fork, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(s->fork, stream));
         for (int li = 1; li < n_lanes; ++li) {
             Lane& ln = s->lanes[li];
             HIP_TRY(hipStreamWaitEvent(ln.stream, s->fork, 0));
-            HIP_TRY(launch_render(p[li], ln.stream, marks ? &marks[li] : nullptr));
+            HIP_TRY(launch_render(p[li], ln.stream, marks ? &marks[li] : nullptr, lights));
             HIP_TRY(hipEventRecord(ln.done, ln.stream));
         }
     }
-    HIP_TRY(launch_render(p[0], stream, marks ? &marks[0] : nullptr));
+    HIP_TRY(launch_render(p[0], stream, marks ? &marks[0] : nullptr, lights));
     for (int li = 1; li < n_lanes; ++li) HIP_TRY(hipStreamWaitEvent(stream, s->lanes[li].done, 0));
     return MCRT_OK;
 }
@@ -284,15 +285,19 @@ int launch_or_replay(mcrt_scene* s, const RenderParams* p, int n_lanes, hipStrea
     if (!graphs_enabled() || !may_record) return launch_lanes(s, p, n_lanes, stream);
     ++s->use_clock;
     mcrt_scene::Recorded* slot = nullptr;
+    // (a recorded sequence carries the extra lights it was recorded with as kernel arguments: it is replayed only while they hold)
+    auto same = [&](const mcrt_scene::Recorded& r) {
+        return r.n_lanes == n_lanes && std::memcmp(r.p, p, sizeof(RenderParams) * n_lanes) == 0 && std::memcmp(&r.lights, &s->extra, sizeof(LightSet)) == 0;
+    };
     for (auto& r : s->recorded)
-        if (r.exec && r.n_lanes == n_lanes && std::memcmp(r.p, p, sizeof(RenderParams) * n_lanes) == 0) slot = &r;
+        if (r.exec && same(r)) slot = &r;
     if (!slot) {
         // Recording costs tens of milliseconds (capture + instantiation): a parameter set is recorded
         // at its kRecordAt-th sighting, earlier renders launch directly.
         constexpr int kRecordAt = 4;
         mcrt_scene::Recorded* victim = &s->recorded[0];
         for (auto& r : s->recorded) {
-            if (!r.exec && r.n_lanes == n_lanes && std::memcmp(r.p, p, sizeof(RenderParams) * n_lanes) == 0) {
+            if (!r.exec && same(r)) {
                 slot = &r;
                 break;
             }
@@ -309,6 +314,7 @@ int launch_or_replay(mcrt_scene* s, const RenderParams* p, int n_lanes, hipStrea
             victim->n_lanes = n_lanes;
             victim->sightings = 0;
             std::memcpy(victim->p, p, sizeof(RenderParams) * kMaxLanes);
+            victim->lights = s->extra;
             slot = victim;
         }
         slot->last_use = s->use_clock;
@@ -808,6 +814,7 @@ int render_ground_batch_device(mcrt_scene* const* scenes, int n, const mcrt_conf
     bool run;
     int device = 0;
     if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
     GroundShape shape;
@@ -860,6 +867,7 @@ int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_
     bool run;
     int device = 0;
     if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
     static const bool cull = !env_off("MCRT_REFLECT_CULL");  // the pass's own: 0 — every mesh for every tile
@@ -885,6 +893,7 @@ int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_confi
     bool run;
     int device = 0;
     if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
     ShadeShape shape;
@@ -924,6 +933,7 @@ int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config*
         max_texels = std::max(max_texels, scenes[i]->n_texels);
     }
     if (max_texels <= 0) return MCRT_OK;  // no texel: nothing is written
+    if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
     BakeShape shape;
@@ -1192,6 +1202,7 @@ int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_con
     const int device = scenes[0]->device;
     for (int i = 1; i < n; ++i)
         if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     HIP_TRY(hipSetDevice(device));
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a shot cannot be recorded into a caller's graph");
     (void)hipGetLastError();
@@ -1234,6 +1245,7 @@ int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config
     const int device = scenes[0]->device;
     for (int i = 1; i < n; ++i)
         if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     HIP_TRY(hipSetDevice(device));
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a shot cannot be recorded into a caller's graph");
     (void)hipGetLastError();

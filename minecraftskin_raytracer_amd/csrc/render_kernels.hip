@@ -1731,6 +1731,277 @@ __global__ __launch_bounds__(kBlock, 2) void level_shade_kernel(const uint8_t* _
     });
 }
 
+// ---------------------------------------------------------------------------------------------
+// Extra lights (mcrt.h, "extra lights"): the three stages of the general variants for a handle that carries M = K + 1 lights,
+// light 0 the scene header's, lights 1 .. K the LightSet argument's.  Kernels of their own beside light_samples, shadow and
+// level_shade, which stay exactly as they are.  A record's lights sit side by side: light k of entry e owns the S sample
+// positions at targets[(e * M + k) * 3 * S], the bundle mask cand[e * M + k] and the count lit[par][e * M + k]
+// (plan_workspace sizes the three arrays for M).  One seeding chain and one set of 2·S draws per record feed all M disks; a
+// light whose radius is below 1e-4 has no disk: computeSoftShadow's single ray (shading.cpp:30) is traced by its sample 0.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ LightAt light_at(const FlatHeader* h, const LightSet& ls, uint32_t k) {
+    // (selects, not an index: k differs from lane to lane in `shadow_lights`, and an indexed kernel argument goes through scratch)
+    const mcrt_light_source& a = ls.extra[0];
+    const mcrt_light_source& b = ls.extra[1];
+    const mcrt_light_source& c = ls.extra[2];
+    auto pick = [k](float x0, float x1, float x2, float x3) { return k == 0u ? x0 : (k == 1u ? x1 : (k == 2u ? x2 : x3)); };
+    LightAt l;
+    l.pos = mk(pick(h->light_pos[0], a.position[0], b.position[0], c.position[0]), pick(h->light_pos[1], a.position[1], b.position[1], c.position[1]),
+               pick(h->light_pos[2], a.position[2], b.position[2], c.position[2]));
+    l.radius = pick(h->light_radius, a.radius, b.radius, c.radius);
+    for (int i = 0; i < 3; ++i) l.col[i] = pick(h->light_color[i], a.color[i], b.color[i], c.color[i]);
+    return l;
+}
+
+// The light samples of one record for every disk light: the seeding chain and the 2·S draws once, then per light its frame,
+// its bundle mask and its S positions.
+template <bool kPosed>
+__device__ __forceinline__ void emit_lights_samples(const SceneView& sc, const WaveSpace& ws, const LightSet& ls, uint32_t e, V3 P, V3 N, int depth, int S,
+                                                    uint32_t* my_rng) {
+    const uint32_t M = static_cast<uint32_t>(ls.n_extra) + 1u;
+    HitRng rng;
+    rng.seed(shadow_seed(P, depth), 2 * S, my_rng);
+    LightAt light[kMaxLights];
+    LightFrame frame[kMaxLights];
+#pragma unroll
+    for (uint32_t k = 0; k < static_cast<uint32_t>(kMaxLights); ++k) {  // (unrolled: the arrays stay in registers)
+        light[k] = light_at(sc.hdr, ls, k);
+        if (k >= M || light[k].radius < 1e-4f) continue;
+        ws.cand[static_cast<size_t>(e) * M + k] = bundle_candidates<kPosed>(sc, P + N * 1e-3f, light[k].pos, light[k].radius);
+        frame[k] = light_frame_at(light[k].pos, P);
+    }
+    for (int i = 0; i < S; ++i) {
+        const float d0 = rng.uniform();
+        const float d1 = rng.uniform();
+#pragma unroll
+        for (uint32_t k = 0; k < static_cast<uint32_t>(kMaxLights); ++k) {
+            if (k >= M || light[k].radius < 1e-4f) continue;
+            const V3 t = light_sample_at(light[k], frame[k], d0, d1);
+            float* dst = ws.targets + ((static_cast<size_t>(e) * M + k) * static_cast<size_t>(S) + static_cast<size_t>(i)) * 3;
+            dst[0] = t.x;
+            dst[1] = t.y;
+            dst[2] = t.z;
+        }
+    }
+}
+// whether any of the M lights has a disk (else no record needs samples)
+__device__ __forceinline__ bool any_disk_light(const FlatHeader* h, const LightSet& ls) {
+    bool any = !(h->light_radius < 1e-4f);
+    for (int k = 0; k < ls.n_extra; ++k) any = any || !(ls.extra[k].radius < 1e-4f);
+    return any;
+}
+
+template <bool kPosed>
+__global__ __launch_bounds__(kBlock) void light_samples_lights_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p, const int level,
+                                                                      const LightSet ls) {
+    const SceneView sc = view_of(scene_blob);
+    const WaveSpace& ws = p.ws;
+    const Scope scope{level, 0};
+    const int par = scope.par();
+    const int S = p.cfg.shadow_samples;
+    if (!any_disk_light(sc.hdr, ls)) return;
+    uint32_t* my_rng = ws.hit_rng + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) * 624;
+    for_each_entry_block(ws, scope, [&](uint32_t first, uint32_t n) __attribute__((always_inline)) {
+        if (threadIdx.x >= n) return;
+        const uint32_t e = first + threadIdx.x;
+        const float4 hp = ws.q_p[par][e], hn = ws.q_n[par][e];
+        emit_lights_samples<kPosed>(sc, ws, ls, e, mk(hp.x, hp.y, hp.z), mk(hn.x, hn.y, hn.z), __float_as_int(ws.q_d[par][e].w), S, my_rng);
+    });
+}
+
+// shadow_lights: one (record, light, sample) triple per lane.  A *group* is the pairs_per_group consecutive lanes of one
+// (record, light): group v = e * M + k, so `shadow`'s two ways of counting — ballot + popcount where the group size is a
+// power of two <= 64, atomics on a zeroed counter otherwise — carry over with groups in the place of records.
+template <int kView>
+__global__ __launch_bounds__(kBlock, MCRT_SHADOW_WAVES) void shadow_lights_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p, const int level,
+                                                                                  const LightSet ls) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    const SceneView scg = view_of(scene_blob);
+    const WaveSpace& ws = p.ws;
+    const Scope scope{level, 0};
+    const int par = scope.par();
+    const bool soft = p.cfg.soft_shadows && p.cfg.shadow_samples > 1;
+    const int S = p.cfg.shadow_samples;
+    const uint32_t M = static_cast<uint32_t>(ls.n_extra) + 1u;
+    const uint32_t pairs_per_group = soft ? static_cast<uint32_t>(S) : 1u;
+    const bool pow2 = (pairs_per_group & (pairs_per_group - 1u)) == 0u && pairs_per_group <= 64u;
+    const uint32_t n_dense = scope.dense() ? dense_count(ws, scope) : 0u;
+    {  // leave before the collective staging when this workgroup gets nothing
+        const bool some_units = scope.units() && blockIdx.x < counted(ws, kCntUnits);
+        const unsigned long long dense_items = pow2 ? static_cast<unsigned long long>(n_dense) * M * pairs_per_group : n_dense;  // pow2: strided over pairs
+        if (!some_units && static_cast<unsigned long long>(blockIdx.x) * kBlock >= dense_items) return;
+    }
+    const typename ViewSel<kView>::type sc = ViewSel<kView>::make(scg, p, s_dyn);
+    uint32_t* lit = ws.lit[par];
+    const uint32_t lane = threadIdx.x & 63u;
+    // one wave-aligned run of up to 64 consecutive pairs of the groups first_group .. : pairs q0 .. of `total`
+    auto trace_pairs = [&](uint32_t first_group, uint32_t q0, uint32_t total) __attribute__((always_inline)) {
+        const uint32_t q = q0 + lane;
+        bool visible = false;
+        uint32_t v = 0;
+        if (q < total) {
+            const uint32_t g = q / pairs_per_group;
+            const uint32_t j = q - g * pairs_per_group;
+            v = first_group + g;
+            const uint32_t e = v / M;
+            const LightAt l = light_at(sc.hdr, ls, v - e * M);
+            const float4 hp = ws.q_p[par][e], hn = ws.q_n[par][e];
+            const V3 P = mk(hp.x, hp.y, hp.z);
+            const V3 N = mk(hn.x, hn.y, hn.z);
+            if (!soft) {  // shade()'s own test, normalised normal
+                visible = !in_shadow_inline(sc, P, normalize(N), l.pos);
+            } else if (l.radius < 1e-4f) {  // computeSoftShadow's single ray, raw normal: sample 0 alone
+                if (j == 0u) visible = !in_shadow_inline(sc, P, N, l.pos);
+            } else {
+                const V3 target = ld3(ws.targets + (static_cast<size_t>(v) * S + j) * 3);
+                visible = !in_shadow_masked(sc, P, N, target, ws.cand[v]);
+            }
+        }
+        if (pow2) {
+            const unsigned long long m = __ballot(visible);
+            if (q < total && (lane & (pairs_per_group - 1u)) == 0u) {
+                const unsigned long long grp = (pairs_per_group == 64u) ? m : ((m >> lane) & ((1ull << pairs_per_group) - 1ull));
+                lit[v] = static_cast<uint32_t>(__popcll(grp));
+            }
+        } else if (visible) {
+            atomicAdd(&lit[v], 1u);
+        }
+    };
+    auto entry_block = [&](uint32_t first, uint32_t n) __attribute__((always_inline)) {
+        const uint32_t first_group = first * M, groups = n * M;
+        if (!pow2) {
+            for (uint32_t i = threadIdx.x; i < groups; i += kBlock) lit[first_group + i] = 0u;
+            __syncthreads();
+        }
+        const uint32_t total = groups * pairs_per_group;
+        // every lane of a wave runs the same number of iterations (ballot inside)
+        for (uint32_t q0 = threadIdx.x & ~63u; q0 < total; q0 += kBlock) trace_pairs(first_group, q0, total);
+    };
+    if (scope.units()) for_each_unit_block(ws, entry_block);
+    if (!scope.dense()) return;
+    const uint32_t base = dense_base(ws, scope);
+    if (pow2) {
+        // dense queue: stride over PAIRS so that even a sparse queue spreads over all workgroups
+        const unsigned long long total = static_cast<unsigned long long>(n_dense) * M * pairs_per_group;
+        const unsigned long long step = static_cast<unsigned long long>(gridDim.x) * kBlock;
+        for (unsigned long long q0 = static_cast<unsigned long long>(blockIdx.x) * kBlock + (threadIdx.x & ~63u); q0 < total; q0 += step) {
+            // 64 consecutive pairs start at group q0 / pairs_per_group exactly (pairs_per_group divides 64)
+            const uint32_t first_group = base * M + static_cast<uint32_t>(q0 / pairs_per_group);
+            const uint32_t left = static_cast<uint32_t>(min(total - q0, 64ull));
+            trace_pairs(first_group, 0u, left);
+        }
+    } else {
+        for_each_dense_block(base, n_dense, entry_block);
+    }
+}
+
+// colour of a hit level under M lights (mcrt.h): C + E_1 .. E_K left to right, clamped, then the AO factor of level_color
+template <class SV>
+__device__ __forceinline__ C4 level_color_lights(const SV& sc, const mcrt_config& cfg, const LightSet& ls, V3 ray_origin, const Hit& hit, int depth,
+                                                 const uint32_t* lit, bool soft, uint32_t* mt_storage) {
+    const V3 view = normalize(ray_origin - hit.p);
+    const float S = static_cast<float>(cfg.shadow_samples);
+    auto vis_of = [&](uint32_t k, float radius) { return (soft && !(radius < 1e-4f)) ? static_cast<float>(lit[k]) / S : (lit[k] ? 1.0f : 0.0f); };
+    C4 c = shade(sc, hit, view, vis_of(0u, sc.hdr->light_radius));
+    for (int k = 1; k <= ls.n_extra; ++k) {
+        const LightAt l = light_at(sc.hdr, ls, static_cast<uint32_t>(k));
+        const C4 e = shade_at(l, hit, view, 0.0f, vis_of(static_cast<uint32_t>(k), l.radius));
+        c.r += e.r;
+        c.g += e.g;
+        c.b += e.b;
+    }
+    c = clamp4(c);
+    if (cfg.ao_enabled && depth == 0) {  // raytracer.cpp:121-130
+        const float ao = ambient_occlusion(sc, hit.p, hit.n, cfg.ao_samples, cfg.ao_radius, ao_seed(hit.p), mt_storage);
+        const float k = 1.0f - cfg.ao_intensity * (1.0f - ao);
+        c.r *= k;
+        c.g *= k;
+        c.b *= k;
+    }
+    return c;
+}
+
+// level_shade_lights: level_shade with the level's colour summed over the lights and the next level's samples emitted for all of them
+template <int kView>
+__global__ __launch_bounds__(kBlock, 2) void level_shade_lights_kernel(const uint8_t* __restrict__ scene_blob, const RenderParams p, const int level,
+                                                                     const LightSet ls) {
+    __shared__ int s_wcnt[kBlock / 64];
+    __shared__ uint32_t s_out_base;
+    __shared__ float4 s_np[kBlock], s_nn[kBlock];  // new hits handed to the packed threads
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    const SceneView scg = view_of(scene_blob);
+    const WaveSpace& ws = p.ws;
+    const Scope scope{level, 0};
+    if (no_entry_blocks(ws, scope)) return;  // before the collective staging
+    const typename ViewSel<kView>::type sc = ViewSel<kView>::make(scg, p, s_dyn);
+    const mcrt_config& cfg = p.cfg;
+    const int par = level & 1;
+    const bool soft = cfg.soft_shadows && cfg.shadow_samples > 1;
+    const bool emit = soft && any_disk_light(scg.hdr, ls);
+    const int S = cfg.shadow_samples;
+    const uint32_t M = static_cast<uint32_t>(ls.n_extra) + 1u;
+    const float* fb = sc.hdr->background;
+    const C4 flat_bg{fb[0], fb[1], fb[2], fb[3]};
+    uint32_t* my_rng = nullptr;
+    if (ws.hit_rng) my_rng = ws.hit_rng + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) * 624;
+    for_each_entry_block(ws, scope, [&](uint32_t first, uint32_t n) __attribute__((always_inline)) {
+        bool next_hit = false;
+        Ray nray{mk(0, 0, 0), mk(0, 0, 0)};
+        Hit nhit;
+        nhit.hit = false;
+        uint32_t root = 0;
+        int depth = 0;
+        if (threadIdx.x < n) {
+            const uint32_t e = first + threadIdx.x;
+            const Record r = load_record(ws, par, e, true);
+            root = r.root;
+            depth = r.depth;
+            const C4 c = level_color_lights(sc, cfg, ls, r.ray.o, r.hit, depth, ws.lit[par] + static_cast<size_t>(e) * M, soft, my_rng);
+            bool done = false;
+            C4 tail = flat_bg;
+            if (depth >= cfg.max_bounces) {  // no reflection: `shadedColor.a = originalAlpha; return clamp()`
+                tail = clamp4(c);
+                done = true;
+            } else {
+                nray = reflect_ray(r.ray, r.hit);
+                nhit = hit_scene<true>(sc, nray, ~0ull);
+                if (nhit.hit) {  // the chain goes on: its level colour waits on the stack for the fold
+                    ws.stack[static_cast<size_t>(depth) * ws.cap + root] = make_float4(c.r, c.g, c.b, c.a);
+                    next_hit = true;
+                } else {  // bounced ray missed → flat background (raytracer.cpp:94-102), folded in at once (:143-147)
+                    tail = fold_reflection(c, flat_bg);
+                    done = true;
+                }
+            }
+            if (done) {  // unwind the recursion: fold the shallower levels' colours back to front
+                for (int d = depth - 1; d >= 0; --d) {
+                    const float4 sd = ws.stack[static_cast<size_t>(d) * ws.cap + root];
+                    tail = fold_reflection(C4{sd.x, sd.y, sd.z, sd.w}, tail);
+                }
+                ws.scol[root] = make_float4(tail.r, tail.g, tail.b, tail.a);
+            }
+        }
+        // survivors → dense level+1 queue: one atomic per block
+        int total = 0;
+        const int rank = block_rank(next_hit, s_wcnt, total);
+        if (total > 0) {  // uniform
+            if (threadIdx.x == 0) s_out_base = count_add(ws, kCntDense + level + 1, static_cast<uint32_t>(total));
+            if (next_hit && emit) {  // hand the new hit to thread `rank`: the survivors' work below runs packed
+                s_np[rank] = make_float4(nhit.p.x, nhit.p.y, nhit.p.z, __int_as_float(depth + 1));
+                s_nn[rank] = make_float4(nhit.n.x, nhit.n.y, nhit.n.z, 0.0f);
+            }
+            __syncthreads();
+            if (next_hit) push_entry(ws, par ^ 1, s_out_base + static_cast<uint32_t>(rank), nray, nhit, root, depth + 1);
+            if (emit && static_cast<int>(threadIdx.x) < total) {  // the new entries' light samples and bundle masks, for every disk light
+                const float4 np = s_np[threadIdx.x], nn = s_nn[threadIdx.x];
+                emit_lights_samples<kView != kViewLdsUnposed>(scg, ws, ls, s_out_base + threadIdx.x, mk(np.x, np.y, np.z), mk(nn.x, nn.y, nn.z),
+                                                              __float_as_int(np.w), S, my_rng);
+            }
+            __syncthreads();
+        }
+    });
+}
+
 // resolve: ordered per-pixel sum of the queued units' sample colours (tile_renderer.cpp:116-124).  A
 // sample that started a chain gets its colour here: the chain's level colours folded back to front
 // (raytracer.cpp:143-147) from where the chain ended — the flat background when its last reflection ray
@@ -1968,7 +2239,7 @@ __global__ __launch_bounds__(kBlock) void resolve_transparent_batch_kernel(Param
 
 // ---- host-side launchers (the planning that sizes them: render_plan.cpp) ----------------------------
 template <int kView>
-static void launch_levels(const RenderParams& p, hipStream_t stream, size_t dyn) {
+static void launch_levels(const RenderParams& p, hipStream_t stream, size_t dyn, const LightSet* lights) {
     const mcrt_config& c = p.cfg;
     const bool soft = soft_sampling(c);
     const int levels = c.max_bounces < 0 ? 0 : c.max_bounces + 1;
@@ -1977,6 +2248,14 @@ static void launch_levels(const RenderParams& p, hipStream_t stream, size_t dyn)
     (void)soft;
     if (!p.flat) {  // general variants: one launch set per level; `level_shade` emits the light samples of the entries it appends
         const int grid = 256;
+        if (lights && lights->n_extra > 0) {  // extra lights: the same sequence through the multi-light stages
+            for (int L = 0; L < levels; ++L) {
+                if (soft && L == 0) hipLaunchKernelGGL(light_samples_lights_kernel<posed>, dim3(grid), dim3(kBlock), 0, stream, p.scene, p, L, *lights);
+                hipLaunchKernelGGL(shadow_lights_kernel<kView>, dim3(grid), dim3(kBlock), dyn, stream, p.scene, p, L, *lights);
+                hipLaunchKernelGGL(level_shade_lights_kernel<kView>, dim3(grid), dim3(kBlock), dyn, stream, p.scene, p, L, *lights);
+            }
+            return;
+        }
         for (int L = 0; L < levels; ++L) {
             if (soft && L == 0) hipLaunchKernelGGL((light_samples_kernel<true, posed>), dim3(grid), dim3(kBlock), 0, stream, p.scene, p, L);
             hipLaunchKernelGGL(shadow_kernel<kView>, dim3(grid), dim3(kBlock), dyn, stream, p.scene, p, L);
@@ -1999,9 +2278,10 @@ hipError_t launch_seed_tiles(const RenderParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_render(const RenderParams& p, hipStream_t stream, const LaunchMarks* marks) {
+hipError_t launch_render(const RenderParams& p, hipStream_t stream, const LaunchMarks* marks, const LightSet* lights) {
     const int n = owned_tiles(p);
     if (n <= 0) return hipSuccess;
+    if (lights && lights->n_extra > 0 && (p.flat || lights->n_extra > MCRT_MAX_EXTRA_LIGHTS)) return hipErrorInvalidValue;  // (plan_workspace sizes the workspace for them)
     const size_t dyn = scene_table_bytes(p);
     float4* out = reinterpret_cast<float4*>(p.out);
     uchar4* out8 = reinterpret_cast<uchar4*>(p.out8);
@@ -2026,7 +2306,7 @@ hipError_t launch_render(const RenderParams& p, hipStream_t stream, const Launch
             constexpr int kView = decltype(v)::value;
             const size_t view_dyn = kView == kViewHbm ? 0 : dyn;
             hipLaunchKernelGGL(primary_kernel<kView>, dim3(pgrid), dim3(kBlock), view_dyn, stream, p, p.scene, draws, out, out8, tile_base, batch_tiles);
-            launch_levels<kView>(p, stream, view_dyn);
+            launch_levels<kView>(p, stream, view_dyn, lights);
         });
         const int rgrid = batch_tiles * p.parts_per_tile < resolve_grid ? batch_tiles * p.parts_per_tile : resolve_grid;
         if (p.background == MCRT_BACKGROUND_TRANSPARENT)

@@ -36,9 +36,9 @@ static int int_knob(const char* name, int fallback) {
 
 // rare features that need the general kernel variants (one launch set per level, ping-pong queues): per-hit RNG
 // streams longer than the register-only engine covers (they run AO inside `level_shade`, sequentially), or
-// more bounces than the flat record arrays are laid out for
-static bool needs_general_variant(const mcrt_config& c) {
-    return (c.ao_enabled && (c.ao_samples <= 0 || 2 * c.ao_samples > kMtShortMax)) || (soft_sampling(c) && 2 * c.shadow_samples > kMtShortMax) ||
+// more bounces than the flat record arrays are laid out for, or extra lights (mcrt.h: the multi-light stages are general ones)
+static bool needs_general_variant(const mcrt_config& c, int extra_lights) {
+    return extra_lights > 0 || (c.ao_enabled && (c.ao_samples <= 0 || 2 * c.ao_samples > kMtShortMax)) || (soft_sampling(c) && 2 * c.shadow_samples > kMtShortMax) ||
            c.max_bounces > kFlatMaxBounces;
 }
 
@@ -86,12 +86,13 @@ static int choose_parts_per_tile(RenderParams& p) {
     return p.unit_gx * p.unit_gy;
 }
 
-WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched) {
+WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* row_touched, int extra_lights) {
     WorkspaceBytes w{};
     const mcrt_config& c = p.cfg;
     const int n_tiles = owned_tiles(p);
     p.parts_per_tile = choose_parts_per_tile(p);
-    p.flat = needs_general_variant(c) ? 0 : 1;
+    p.flat = needs_general_variant(c, extra_lights) ? 0 : 1;
+    const size_t lights = extra_lights > 0 ? static_cast<size_t>(extra_lights) + 1 : 1;  // per record: a disk, a bundle mask and a lit count per light
     p.ws.stack_stride = c.max_bounces > 0 ? c.max_bounces + 1 : 1;
     const size_t spp = c.samples_per_pixel > 1 ? c.samples_per_pixel : 1;
     // every tile that meshes can touch owns one slot per sample of a full (frame-clipped) tile
@@ -108,7 +109,7 @@ WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* r
     // the primary hits; the flat pipeline's `lit` keeps the light samples in LDS
     const size_t hbm_rays = p.flat ? 0 : rays;  // the flat pipeline keeps light samples in LDS and AO directions in registers
     const size_t ray_recs = p.flat ? 1 : recs;
-    const size_t per_entry = 16 + 4 + recs * (5 * 16 + 4) + ray_recs * (12 * hbm_rays + (hbm_rays ? 8 : 0) + 4) + 4 + 16 * static_cast<size_t>(p.ws.stack_stride);
+    const size_t per_entry = 16 + 4 + recs * (5 * 16 + 4) + ray_recs * lights * (12 * hbm_rays + (hbm_rays ? 8 : 0) + 4) + 4 + 16 * static_cast<size_t>(p.ws.stack_stride);
     // `lit`: a round is a block of up to 256 records (masks, counts and the list of traced records in LDS); the sample
     // positions of the records whose rays are traced go through an area of kLitLdsBytes, `lit_pass` records at a time
     {
@@ -147,7 +148,7 @@ WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* r
     p.ws.draws_stride = static_cast<uint32_t>(draws_stride > 0xffffffffull ? 0xffffffffull : draws_stride);
     p.ws.tile_slots = static_cast<uint32_t>(tile_slots > 0xffffffffull ? 0xffffffffull : tile_slots);
     // records are indexed with 32 bits (with room for the 3·S multiplier done in size_t)
-    const size_t index_limit = 0x7ffffff0ull / recs;
+    const size_t index_limit = 0x7ffffff0ull / (recs * lights);  // (a record's lights are indexed record * lights + k)
     size_t tile_budget = budget_bytes / (per_entry * (tile_slots ? tile_slots : 1) + draws_tile_bytes);
     if (tile_slots && tile_budget > index_limit / tile_slots) tile_budget = index_limit / tile_slots;
     int rows = owned > 0 ? owned : 1;
@@ -194,10 +195,10 @@ WorkspaceBytes plan_workspace(RenderParams& p, size_t budget_bytes, const int* r
     w.tile_mask = static_cast<size_t>(n_tiles > 0 ? n_tiles : 1) * 8;
     w.queue_each = rec_cap * 16;
     w.texel_refs = p.flat ? rec_cap * 4 : 4;
-    w.targets = (p.flat ? cap : rec_cap) * 12 * hbm_rays;
-    w.cand = hbm_rays ? (p.flat ? cap : rec_cap) * 8 : 0;
-    w.lit0 = p.flat ? 4 : cap * 4;  // the flat pipeline keeps the lit counts in LDS
-    w.lit1 = cap * 4;
+    w.targets = (p.flat ? cap : rec_cap) * 12 * hbm_rays * lights;
+    w.cand = hbm_rays ? (p.flat ? cap : rec_cap) * 8 * lights : 0;
+    w.lit0 = p.flat ? 4 : cap * 4 * lights;  // the flat pipeline keeps the lit counts in LDS
+    w.lit1 = cap * 4 * lights;
     w.stack = cap * 16 * static_cast<size_t>(p.ws.stack_stride);
     w.counters = (static_cast<size_t>(kCounterWords) * 2 + 4) * 4;  // the counters, their base (the previous pass's last values), frame_info
     w.hit_rng = p.flat ? 0 : static_cast<size_t>(256) * kBlock * 624 * 4;  // general grids are capped at 256 WGs

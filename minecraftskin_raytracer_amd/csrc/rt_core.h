@@ -1422,6 +1422,47 @@ DEV C4 shade(const SV& sc, const Hit& hit, V3 viewDir, float vis) {
     return clamp4(out);
 }
 
+// ---- a light that is not the scene header's (mcrt.h, "extra lights").  light_frame, light_sample_on_frame and shade above
+// stated for a light given by value; they stay as they are, so the code of the kernels that call them does not move.
+struct LightAt {
+    V3 pos;
+    float radius;
+    float col[3];
+};
+DEV LightFrame light_frame_at(V3 lpos, V3 point) {  // shading.cpp:35-41
+    V3 toPoint = normalize(point - lpos);
+    V3 tangent = (__builtin_fabsf(toPoint.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), toPoint))
+                                                     : normalize(cross(mk(0, 1, 0), toPoint));
+    return LightFrame{tangent, cross(toPoint, tangent)};
+}
+DEV V3 light_sample_at(const LightAt& l, const LightFrame& f, float d0, float d1) {  // shading.cpp:46-53
+    float angle = kTwoPi * d0;
+    float rr = l.radius * sqrt_pos(d1);
+    float sn, cs;
+    mcrt_sincosf(angle, &sn, &cs);
+    V3 off = f.tangent * (rr * cs) + f.bitangent * (rr * sn);
+    return l.pos + off;
+}
+// shade :62-96 for that light with ShadingParams{kd .75, ks .15, ambient, shininess 16} and the visibility term given
+DEV C4 shade_at(const LightAt& l, const Hit& hit, V3 viewDir, float ambient, float vis) {
+    const float kd = 0.75f, ks = 0.15f, shininess = 16.0f;
+    C4 tex = hit.tex;
+    V3 L = normalize(l.pos - hit.p);
+    V3 N = normalize(hit.n);
+    V3 V = normalize(viewDir);
+    float ndl = smax(0.0f, dot(N, L));
+    float kdiff = kd * ndl * vis;
+    V3 H = normalize(L + V);
+    float ndh = smax(0.0f, dot(N, H));
+    float kspec = ks * dev_powf(ndh, shininess) * vis;
+    C4 out;
+    out.r = tex.r * ambient + tex.r * l.col[0] * kdiff + l.col[0] * kspec;
+    out.g = tex.g * ambient + tex.g * l.col[1] * kdiff + l.col[1] * kspec;
+    out.b = tex.b * ambient + tex.b * l.col[2] * kdiff + l.col[2] * kspec;
+    out.a = tex.a;
+    return clamp4(out);
+}
+
 // ---------------------------------------------------------------------------------------------
 // raytracer.cpp
 // ---------------------------------------------------------------------------------------------

@@ -14,6 +14,11 @@ The light layers (tests/light_checker.py), visibility, occlusion and direct bit 
                turn, AO settings drawn per case (1 ... 113 samples, a radius of 0.01 ... 10 scene heights); every fourth case into
                planes 1 or 2 floats off their allocation, every other case also twice through the batched kernels; the summary
                records the hits, penumbra hits and partly occluded hits compared
+Extra lights (tests/extra_lights_fuzz_cases.py; the runs and comparisons are those of tests/test_gpu_extra_lights_fuzz.py):
+  lights       render_device_ex on extra_lights_fuzz_cases.sweep_case(seed): make_bundle_case and make_pass_case in turn, frames of at
+               most 64 x 64 at 1 spp, 1 ... 3 extra lights inside, below, behind and around the figure, radius 0 ... 25, colours 0 ... 2,
+               against tests/extra_lights_checker.py; every other case also through the one-shot form; the summary records the hits,
+               the hits the extra lights changed, the hits over 1 before the clamp and the penumbra pairs compared
 The light bake (tests/bake_checker.py), position, normal, visibility, occlusion and direct of every pool texel bit for bit:
   bake         bake_light_device on bake_checker.sweep_case(seed): light's cases, grid 1 + seed % 4; every fourth case into planes 1 or
                2 floats off their allocation, every other case also twice through the batched kernels; the summary records the
@@ -72,7 +77,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 mode = sys.argv[3] if len(sys.argv) > 3 else ""
 PASS_MODES = ("ground", "reflection", "layers", "long-shadow", "far-plane")
 BATCH_MODES = ("batch", "pass-batch")
-if mode not in ("", "bundle", "wide", "light", "bake", "big", "resident", "shot", "cutout", "ground_occlusion") + PASS_MODES + BATCH_MODES:
+if mode not in ("", "bundle", "wide", "light", "lights", "bake", "big", "resident", "shot", "cutout", "ground_occlusion") + PASS_MODES + BATCH_MODES:
     sys.exit(f"unknown mode {mode!r}")
 
 
@@ -171,6 +176,42 @@ def light_sweep():
             print(f"... {k + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
     print(f"fuzz light: {count} cases from seed {first}: {bad} mismatch(es); the oracle holds {int(total[0])} hits, {int(total[1])} of them dark and "
           f"{int(total[2])} in the penumbra, and {int(total[3])} partly occluded hits ({int(total[4])} fully occluded)")
+    pool.terminate()
+    sys.exit(1 if bad else 0)
+
+
+def lights_sweep():
+    import extra_lights_fuzz_cases as F, test_gpu_extra_lights_fuzz as T
+    from minecraftskin_raytracer_amd._lib import McrtError
+
+    # the expected frames are made ahead of the device by worker processes (forked before the device is first used; they never
+    # use it), in the order of the seeds
+    import multiprocessing
+
+    workers = max(1, min(14, len(os.sched_getaffinity(0)) - 2, int(os.environ.get("OMP_NUM_THREADS", "16")) - 2))
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    ahead = pool.imap(F.worker_sweep_expectation, range(first, first + count))
+    bad = 0
+    total = np.zeros(4, np.int64)
+    t0 = time.time()
+    for k, seed in enumerate(range(first, first + count)):
+        case = F.sweep_case(seed)
+        want, counts = next(ahead)
+        try:
+            lines = T.run_case(M, case, want, one_shot=k % 2 == 0)
+        except McrtError as e:
+            print(f"HIP ERROR {case[3]}: {e}", flush=True)
+            print(f"fuzz lights: stopped at seed {seed} after {k} cases, {bad} mismatch(es)")
+            pool.terminate()
+            sys.exit(2)
+        total += np.asarray(counts)
+        if lines:
+            bad += 1
+            print("\n".join("MISMATCH " + l for l in lines[:20]), flush=True)
+        if k % 100 == 99:
+            print(f"... {k + 1} cases, {bad} mismatches, {time.time() - t0:.0f} s", flush=True)
+    print(f"fuzz lights: {count} cases from seed {first}: {bad} mismatch(es); the oracle holds {int(total[0])} hits, {int(total[1])} of them changed by "
+          f"the extra lights, {int(total[2])} over 1 before the clamp, and {int(total[3])} penumbra (hit, extra light) pairs")
     pool.terminate()
     sys.exit(1 if bad else 0)
 
@@ -457,6 +498,8 @@ if mode in BATCH_MODES:
     batch_sweep()
 if mode == "light":
     light_sweep()
+if mode == "lights":
+    lights_sweep()
 if mode == "bake":
     bake_sweep()
 if mode == "big":
