@@ -195,6 +195,17 @@ void mcrt_trim(void);
  * (state word 397 for the seeds -2^24 .. 2^24-1, which is where the per-hit shadow seeds of a scene at the
  * reference's scale lie): built once in ~2 ms, it replaces a 397-step recurrence per hit by one load, with
  * identical results.  MCRT_SEED_TABLE=0 turns it off; mcrt_trim() frees it when no scene handle is left. */
+/* Sample table.  What a hit's soft-shadow samples are before the light enters — the cosine, the sine and the radius
+ * factor of each light-disk sample — depends on the hit's shadow seed and the sample's index alone, not on the scene, the
+ * light or the pose.  A device keeps them for the seeds -2^22 .. 2^22-1 (the built-in character's hits stay below 3.3 M
+ * in magnitude) and up to 8 samples: 2^23 rows of 128 bytes, 1 GiB of the device's memory, filled in about a millisecond by
+ * the routines the renderer itself runs, so frames are identical with and without it.  It is built at a device's SECOND
+ * render with soft shadows of 2 .. 8 samples — a process that renders once never allocates it — and only where 3 GiB are
+ * free; never inside a caller's stream capture (such a render does not read it either).  Seeds outside the window, more
+ * than 8 samples, the extra-lights path and the stand-alone passes compute their samples as before.
+ * MCRT_SAMPLE_TABLE=0 turns it off, =2 builds it at the first such render; mcrt_trim() frees it when no scene handle is left.
+ * mcrt_sample_table_info: the bytes of the device's table (0: none) and how often it was built since the process began. */
+int mcrt_sample_table_info(int device, size_t* bytes, int* builds);
 
 /* Background plates.  The gradient background tiles of a frame (three quarters of the tiles of a 1080p frame of the
  * character) do not depend on the scene: their pixels are a function of width, height, tile_size, samples_per_pixel,
@@ -1092,6 +1103,10 @@ int mcrt_probe_trace(mcrt_scene* scene, const mcrt_config* cfg, const float* ray
                      float* out_rgba);
 /* first n outputs of uniform_real_distribution<float>(0,1) over std::mt19937(seed) for each seed */
 int mcrt_probe_mt_uniform(int device, const uint32_t* seeds, int n_seeds, int n_draws, float* out);
+/* The rows of the device's sample table ("Sample table" above) for n seeds in -2^22 .. 2^22-1: out = n x 8 x 4 floats,
+ * {cos, sin, sqrt, 0} per sample.  Builds the table if the device has none yet; MCRT_ERR_INVALID for a seed outside the
+ * window, MCRT_ERR_HIP where there is no table (MCRT_SAMPLE_TABLE=0, no room). */
+int mcrt_probe_sample_rows(int device, const int32_t* seeds, int n, float* out);
 /* device detmath: op 0 = sinf, 1 = cosf, 2 = powf(x, y), 3 / 4 = sin / cos output of the fused
  * mcrt_sincosf, 5 = the kernels' 3-instruction reciprocal (reference: IEEE 1.0f / x), over n inputs */
 int mcrt_probe_detmath(int device, int op, const float* x, const float* y, size_t n, float* out);

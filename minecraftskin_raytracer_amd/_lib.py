@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_build_skin_scene_model", "mcrt_scene_create_skin_model", "mcrt_skin_texel_model", "mcrt_skin_pool_map_model",
     "mcrt_skin_view_table_model", "mcrt_skin_model_of",
     "mcrt_scene_set_extra_lights", "mcrt_scene_extra_lights", "mcrt_render_lights", "mcrt_render_png_lights",
+    "mcrt_probe_sample_rows", "mcrt_sample_table_info",
 ]
 
 

@@ -1483,6 +1483,16 @@ def draw_plate_info(device: int = 0) -> dict:
     return _plate_info("mcrt_draw_plate_info", device)
 
 
+def sample_table_info(device: int = 0) -> dict:
+    """mcrt_sample_table_info: ``{"bytes": ..., "builds": ...}`` — the bytes of the sample table kept on ``device`` (0: none) and
+    how often it was built there since the process began (include/mcrt.h, "Sample table")."""
+    fn = load().mcrt_sample_table_info  # bound here: a build selected with MCRT_LIB may predate it
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    b, k = C.c_size_t(), C.c_int()
+    check(fn(int(device), C.byref(b), C.byref(k)))
+    return {"bytes": int(b.value), "builds": int(k.value)}
+
+
 def unpack_rows_device(config: Config, first: int, step: int, packed_ptr: int, frame_ptr: int, stream: int = 0) -> None:
     c = config.to_c()
     check(load().mcrt_unpack_rows_device(C.byref(c), first, step, C.c_void_p(packed_ptr), C.c_void_p(frame_ptr), C.c_void_p(stream)))
@@ -1504,6 +1514,16 @@ def probe_mt_uniform(seeds: Sequence[int], n_draws: int, device: int = 0) -> np.
     s = np.asarray(seeds, np.uint32)
     out = np.zeros((len(s), n_draws), np.float32)
     check(load().mcrt_probe_mt_uniform(device, s.ctypes.data_as(C.POINTER(C.c_uint32)), len(s), n_draws, abi.fptr(out)))
+    return out
+
+
+def probe_sample_rows(seeds: Sequence[int], device: int = 0) -> np.ndarray:
+    """(n, 8, 4) float32: the rows {cos, sin, sqrt, 0} of the device's sample table for seeds in -2^22 .. 2^22-1 (mcrt.h)."""
+    s = np.asarray(seeds, np.int32)
+    out = np.zeros((len(s), 8, 4), np.float32)
+    fn = load().mcrt_probe_sample_rows  # bound here: a build selected with MCRT_LIB may predate it
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, abi.c_int32_p, C.c_int, abi.c_float_p]
+    check(fn(device, s.ctypes.data_as(abi.c_int32_p), len(s), abi.fptr(out)))
     return out
 
 

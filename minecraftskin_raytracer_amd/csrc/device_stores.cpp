@@ -72,42 +72,62 @@ bool device_shared(const mcrt_scene* s) {
 // they would otherwise run 397 steps for.  Two tables of one shape — by device, built on first use (synchronously, on the
 // null stream), a `users` count of the scene shells, live or pooled, that hold the pointer, freed by mcrt_trim() when
 // nobody does — that differ in what is below.  No table (the knob, no room, a failed build): the kernels seed by the recurrence.
+// The sample table (kernels.h: a hit's light-disk samples by shadow seed) is a third of the same shape, but `sighted`: built by
+// the plates' rule, at the device's second asking render (the knob at 2: the first) — a one-shot call never allocates — on a
+// non-blocking stream of its own that is waited for before the asking render enqueues anything, never on the null stream.
 namespace {
 struct SeedTables {
     const char* knob;                 // environment variable: 0 turns the table off
     size_t bytes;
     bool small_part_only;             // built only where it is a small part of what is free (a third at most)
-    hipError_t (*fill)(uint32_t* p);  // the launches that fill it
+    hipError_t (*fill)(uint32_t* p, hipStream_t stream);  // the launches that fill it
+    bool sighted;                     // the plates' rule (above)
     struct Table {
         uint32_t* ptr = nullptr;
         int users = 0;
+        int sightings = 0;            // (sighted) asking renders so far; negative after a failed build: that many are waited out
+        int builds = 0;               // times the table has been built (mcrt_sample_table_info)
     };
     std::vector<Table> by_device;     // (g_seed_mutex)
-    int enabled = -1;                 // the knob, read at the first acquire
+    int mode = -1;                    // the knob, read at the first acquire: 0 off, 2 (sighted) build at the first asking, else 1
 
-    const uint32_t* acquire(int device);
+    const uint32_t* acquire(int device, bool count_sighting = true);
     const uint32_t* acquire_built(int device);  // only where the table exists: builds nothing
     void release(int device);
     void free_unused();
 };
 std::mutex g_seed_mutex;
+constexpr int kTableRetryAfter = 16;  // asking renders a sighted table waits after a failed build (no room, for one) before the next try
 
-const uint32_t* SeedTables::acquire(int device) {
+const uint32_t* SeedTables::acquire(int device, bool count_sighting) {
     std::lock_guard<std::mutex> lock(g_seed_mutex);
-    if (enabled < 0) enabled = env_int(knob, 1) != 0 ? 1 : 0;
-    if (!enabled) return nullptr;
+    if (mode < 0) {
+        const int v = env_int(knob, 1);
+        mode = v == 0 ? 0 : (v == 2 ? 2 : 1);
+    }
+    if (!mode) return nullptr;
     if (by_device.size() <= static_cast<size_t>(device)) by_device.resize(static_cast<size_t>(device) + 1);
     Table& t = by_device[static_cast<size_t>(device)];
     if (!t.ptr) {
+        if (sighted) {
+            if (count_sighting) ++t.sightings;
+            if (t.sightings < (mode == 2 ? 1 : 2)) return nullptr;
+        }
         size_t free_b = 0, total_b = 0;
         uint32_t* p = nullptr;
+        hipStream_t stream = nullptr;  // (sighted: a stream of the build's own)
         const bool room = !small_part_only || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= bytes * 3);
-        if (!room || hipMalloc(&p, bytes) != hipSuccess || fill(p) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+        const bool built = room && (!sighted || hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess) && hipMalloc(&p, bytes) == hipSuccess &&
+                           fill(p, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+        if (stream) (void)hipStreamDestroy(stream);
+        if (!built) {
             (void)hipGetLastError();
             if (p) (void)hipFree(p);
+            if (sighted) t.sightings = -kTableRetryAfter;
             return nullptr;
         }
         t.ptr = p;
+        ++t.builds;
     }
     ++t.users;
     return t.ptr;
@@ -132,21 +152,26 @@ void SeedTables::free_unused() {  // mcrt_trim
             (void)hipSetDevice(static_cast<int>(d));
             (void)hipFree(t.ptr);
             t.ptr = nullptr;
+            t.sightings = 0;
         }
     }
 }
 
 // The window table: kSeedWindow words, the seeds of a frame's tiles and hits; one ~2 ms kernel.  MCRT_SEED_TABLE=0 turns it off.
-SeedTables g_window_tables{"MCRT_SEED_TABLE", static_cast<size_t>(kSeedWindow) * 4, false, [](uint32_t* p) { return launch_build_seed_table(p, nullptr); }};
+SeedTables g_window_tables{"MCRT_SEED_TABLE", static_cast<size_t>(kSeedWindow) * 4, false, [](uint32_t* p, hipStream_t st) { return launch_build_seed_table(p, st); }, false};
 // The table for EVERY seed: mt[397] of all 2^32 seeds, 16 GiB of the device's HBM.  The ambient-occlusion seeds,
 // (unsigned)(P.x * 73856093 + P.y * 19349663 + P.z * 83492791) (raytracer.cpp:122-123), cover the whole 32-bit range, and the
 // 397-step recurrence is over a quarter of the AO stage's cycles (its multiply issues at a quarter of the rate).  Built on
 // a device's first AO render (0.2 s), when the device has the room; MCRT_AO_SEED_TABLE=0 turns it off.
-SeedTables g_full_tables{"MCRT_AO_SEED_TABLE", static_cast<size_t>(1) << 34, true, [](uint32_t* p) {
+SeedTables g_full_tables{"MCRT_AO_SEED_TABLE", static_cast<size_t>(1) << 34, true, [](uint32_t* p, hipStream_t st) {
                              hipError_t e = hipSuccess;
-                             for (uint32_t part = 0; part < 16u && e == hipSuccess; ++part) e = launch_build_seed_table_range(p, part << 28, 1u << 28, nullptr);
+                             for (uint32_t part = 0; part < 16u && e == hipSuccess; ++part) e = launch_build_seed_table_range(p, part << 28, 1u << 28, st);
                              return e;
-                         }};
+                         }, false};
+// The sample table: kSampleWindow rows of 128 bytes, 1 GiB, the light-disk samples of the seeds a character scene's hits have;
+// one kernel of about a millisecond.  MCRT_SAMPLE_TABLE=0 turns it off, =2 builds it at the device's first asking render.
+SeedTables g_sample_tables{"MCRT_SAMPLE_TABLE", static_cast<size_t>(kSampleWindow) * kSampleRow * sizeof(float4), true,
+                           [](uint32_t* p, hipStream_t st) { return launch_build_sample_table(reinterpret_cast<float4*>(p), st); }, true};
 }  // namespace
 
 const uint32_t* acquire_seed_table(int device) { return g_window_tables.acquire(device); }
@@ -156,6 +181,31 @@ void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream) {
     s->full_table_tried = true;
     s->seed_table_full = g_full_tables.acquire(s->device);
     s->holds_full_table = s->seed_table_full != nullptr;
+}
+// The shell takes the device's sample table at a render whose soft shadows a row can serve (2 .. kSampleRow samples), building
+// it by the sighting rule; a render the caller is capturing takes none and builds none.
+static const float4* sample_table_for(mcrt_scene* s, const RenderParams& p, bool capturing, bool count_sighting) {
+    if (capturing) return nullptr;
+    if (!s->holds_sample_table && p.cfg.soft_shadows && p.cfg.shadow_samples > 1 && p.cfg.shadow_samples <= kSampleRow) {
+        s->sample_table = reinterpret_cast<const float4*>(g_sample_tables.acquire(s->device, count_sighting));
+        s->holds_sample_table = s->sample_table != nullptr;
+    }
+    return s->sample_table;
+}
+bool copy_sample_rows(int device, const int32_t* seeds, int n, float* out) {
+    const uint32_t* table = g_sample_tables.acquire(device);
+    if (!table) table = g_sample_tables.acquire(device);  // (the second asking builds)
+    if (!table) return false;
+    bool ok = true;
+    constexpr size_t row_bytes = kSampleRow * sizeof(float4);
+    for (int i = 0; i < n && ok; ++i) {
+        const uint32_t row = static_cast<uint32_t>(seeds[i]) + kSampleWindowHalf;
+        ok = row < kSampleWindow && hipMemcpy(reinterpret_cast<char*>(out) + static_cast<size_t>(i) * row_bytes,
+                                              reinterpret_cast<const char*>(table) + static_cast<size_t>(row) * row_bytes, row_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) (void)hipGetLastError();
+    g_sample_tables.release(device);
+    return ok;
 }
 void share_full_seed_table(mcrt_scene* s) {
     if (s->holds_full_table) return;
@@ -415,7 +465,8 @@ int plate_info(int kind, int device, int* plates, size_t* bytes, int* builds) {
 void acquire_plates(mcrt_scene* s, RenderParams* p, int n, bool capturing, bool count_sighting) {
     const float4* pixels = static_cast<const float4*>(acquire_plate(kPlatePixels, s, p[0], capturing, count_sighting));
     const float* draws = static_cast<const float*>(acquire_plate(kPlateDraws, s, p[0], capturing, count_sighting));
-    for (int i = 0; i < n; ++i) p[i].bg_plate = pixels, p[i].draw_plate = draws;
+    const float4* samples = sample_table_for(s, p[0], capturing, count_sighting);
+    for (int i = 0; i < n; ++i) p[i].bg_plate = pixels, p[i].draw_plate = draws, p[i].sample_table = samples;
 }
 
 // ---- per-device repaint tables (kernels.h: SkinPaintShape), one per skin kind: the 256 floats i / 255.0f — formed HERE, on
@@ -522,6 +573,7 @@ void destroy_scene_now(mcrt_scene* s) {
     unregister_live(s);  // before its events go
     if (s->holds_seed_table) g_window_tables.release(s->device);
     if (s->holds_full_table) g_full_tables.release(s->device);
+    if (s->holds_sample_table) g_sample_tables.release(s->device);
     if (s->skin_tables) release_skin_tables(s->device, s->skin_height, s->skin_model);
     release_plates(s);
     s->blob.release();  // the other buffers are released by their destructors below
@@ -629,10 +681,18 @@ void mcrt_trim(void) {
     }
     g_full_tables.free_unused();
     g_window_tables.free_unused();
+    g_sample_tables.free_unused();
     free_unused_skin_tables();
     free_unused_plates();
 }
 
+int mcrt_sample_table_info(int device, size_t* bytes, int* builds) {
+    std::lock_guard<std::mutex> lock(g_seed_mutex);
+    const bool known = device >= 0 && static_cast<size_t>(device) < g_sample_tables.by_device.size();
+    if (bytes) *bytes = (known && g_sample_tables.by_device[static_cast<size_t>(device)].ptr) ? g_sample_tables.bytes : 0;
+    if (builds) *builds = known ? g_sample_tables.by_device[static_cast<size_t>(device)].builds : 0;
+    return MCRT_OK;
+}
 int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds) { return plate_info(kPlatePixels, device, plates, bytes, builds); }
 int mcrt_draw_plate_info(int device, int* plates, size_t* bytes, int* builds) { return plate_info(kPlateDraws, device, plates, bytes, builds); }
 

@@ -176,6 +176,8 @@ struct mcrt_scene {
     bool holds_seed_table = false;
     const uint32_t* seed_table_full = nullptr;  // the device's table for every 32-bit seed (ambient occlusion), or NULL
     bool holds_full_table = false, full_table_tried = false;
+    const float4* sample_table = nullptr;  // the device's sample table (kernels.h), taken with the plates, or NULL
+    bool holds_sample_table = false;
     const void* skin_tables = nullptr;  // a repaintable handle's share of the device's repaint tables (kernels.h: SkinPaintShape)
     DeviceBuffer skin;                  // mcrt_scene_set_skin: the uploaded image
     // plates this shell holds a `users` count of, by kind, least recently used first: its recorded launch graphs and its
@@ -362,8 +364,12 @@ void ensure_full_seed_table(mcrt_scene* s, hipStream_t stream);
 // plane: it never builds the table); no launch, no wait
 void share_full_seed_table(mcrt_scene* s);
 // the device's background plate and draw plate for the frame prepared as p[0] — each or nullptr, both kinds under one sighting
-// rule in this one call — into bg_plate and draw_plate of p[0..n) (the lanes of one render read the same plates)
+// rule in this one call — into bg_plate and draw_plate of p[0..n) (the lanes of one render read the same plates); and, by the
+// same rule in the same call, the device's sample table into sample_table
 void acquire_plates(mcrt_scene* s, mcrt::RenderParams* p, int n, bool capturing, bool count_sighting);
+// the rows of `seeds` (kSampleRow float4 each, seeds inside the window) of the device's sample table to the host, for the probe;
+// the table is built if the device has none yet (whatever the sighting count); false where it cannot be
+bool copy_sample_rows(int device, const int32_t* seeds, int n, float* out);
 // The device's repaint tables of a skin kind (64 / 32) — the 256 floats u8 / 255.0f, then per pool texel the mesh and the skin
 // pixel it is cut from (kernels.h: SkinPaintShape) — built at the kind's first repaintable handle on the device, one `users`
 // count per handle that holds them, freed by mcrt_trim() when nobody does.  nullptr: the allocation or the upload failed.

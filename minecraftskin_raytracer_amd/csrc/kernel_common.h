@@ -229,13 +229,50 @@ __device__ __forceinline__ int block_rank(bool flag, int* s_wcnt, int& total) {
     return before + __popcll(bal & ((1ull << lane) - 1ull));
 }
 
-// The S disk sample positions of one shaded point (shading.cpp:35-53), by the lane that owns it (`lit`, the ground pass): the
-// truncated engine seeded for (P, depth) — mt[397] from the device's tables where they hold the seed, else the 397-step
-// recurrence — and the light's frame at P.  dst: 3 * S floats.
-__device__ __forceinline__ void disk_sample_positions(const SceneView& scg, const uint32_t* __restrict__ seed_table, const uint32_t* __restrict__ seed_table_full,
-                                                      const V3 P, const int depth, const int S, float* __restrict__ dst) {
+// One element of a sample-table row (kernels.h): what light_sample_on_frame makes of the draws d0, d1 before the light enters.
+__device__ __forceinline__ float4 sample_row_element(const float d0, const float d1) {
+    float sn, cs;
+    mcrt_sincosf(kTwoPi * d0, &sn, &cs);
+    return make_float4(cs, sn, sqrt_pos(d1), 0.0f);
+}
+// The S disk sample positions of the point P whose shadow seed is `seed`, from the seed's row of the device's sample table:
+// light_sample_on_frame's expressions on the row's {cs, sn, sq}.  False, and nothing written, where the table does not
+// serve: no table, more samples than a row holds, a seed outside the window.
+__device__ __forceinline__ bool sample_row_positions(const SceneView& scg, const float4* __restrict__ sample_table, const uint32_t seed, const V3 P, const int S,
+                                                     float* __restrict__ dst) {
+    const uint32_t row = seed + kSampleWindowHalf;  // wraps: the window is centred on seed 0
+    if (!sample_table || S > kSampleRow || row >= kSampleWindow) return false;
+    const float4* __restrict__ src = sample_table + static_cast<size_t>(row) * kSampleRow;
+    float4 e[kSampleRow];
+#pragma unroll
+    for (int i = 0; i < kSampleRow; ++i) e[i] = src[i];  // the whole line, whatever S is: the loads leave together
+    const LightFrame frame = light_frame(scg, P);
+    const float radius = scg.hdr->light_radius;
+    const V3 lpos = ld3(scg.hdr->light_pos);
+#pragma unroll
+    for (int i = 0; i < kSampleRow; ++i) {
+        if (i < S) {
+            const float rr = radius * e[i].z;
+            const V3 off = frame.tangent * (rr * e[i].x) + frame.bitangent * (rr * e[i].y);
+            const V3 t = lpos + off;
+            dst[3 * i + 0] = t.x;
+            dst[3 * i + 1] = t.y;
+            dst[3 * i + 2] = t.z;
+        }
+    }
+    return true;
+}
+
+// The S disk sample positions of one shaded point (shading.cpp:35-53), by the lane that owns it (`lit`, the ground pass): from
+// the seed's row of the device's sample table where that serves (sample_row_positions); else the truncated engine seeded for
+// (P, depth) — mt[397] from the device's tables where they hold the seed, else the 397-step recurrence — and the light's
+// frame at P.  dst: 3 * S floats.
+__device__ __forceinline__ void disk_sample_positions(const SceneView& scg, const float4* __restrict__ sample_table, const uint32_t* __restrict__ seed_table,
+                                                      const uint32_t* __restrict__ seed_table_full, const V3 P, const int depth, const int S,
+                                                      float* __restrict__ dst) {
     MtShort rng;
     const uint32_t seed = shadow_seed(P, depth);
+    if (sample_row_positions(scg, sample_table, seed, P, S, dst)) return;
     const uint32_t slot = seed + kSeedWindowHalf;  // wraps: the window is centred on seed 0
     if (seed_table && slot < kSeedWindow)
         rng.seed_known(seed, seed_table[slot]);  // mt[397] of this seed, from the device's table
@@ -355,7 +392,7 @@ __device__ __forceinline__ bool resolve_shadow_bundles(const SceneView& scg, con
         if (b.soft && tid < nu) {
             V3 P, N;  // (N goes unused here: the accessor is inlined and its fetch of the normal falls away)
             point_of(b.und[u0 + tid], P, N);
-            disk_sample_positions(scg, b.seed_table, nullptr, P, depth, b.S, b.pos + static_cast<size_t>(tid) * 3 * b.S);
+            disk_sample_positions(scg, nullptr, b.seed_table, nullptr, P, depth, b.S, b.pos + static_cast<size_t>(tid) * 3 * b.S);
         }
         __syncthreads();
         // ---- a lane per (undecided item, light sample)

@@ -92,6 +92,16 @@ constexpr int kDivFrameMax = 16384;
 constexpr uint32_t kSeedWindowHalf = 1u << 24;
 constexpr uint32_t kSeedWindow = 1u << 25;  // table entries: seed s at index s + kSeedWindowHalf (mod 2^32)
 
+// The device's sample table (DESIGN.md §4 "Sample table"): what a hit's light-disk samples are before the light enters — a pure
+// function of (shadow seed, sample index).  Row r serves seed r - kSampleWindowHalf (wrapping, like the seed table) and is
+// kSampleRow float4 {cs, sn, sq, 0}, one 128-byte line: d0, d1 = draws 2i, 2i+1 of std::mt19937(seed), (sn, cs) =
+// mcrt_sincosf(kTwoPi * d0), sq = sqrt_pos(d1) — filled by launch_build_sample_table with the routines
+// disk_sample_positions runs.  2^23 rows, 1 GiB: the seeds -2^22 .. 2^22 - 1; the built-in character's hits at the
+// reference's scale stay below 3.3 M in magnitude.  Seeds outside, more than kSampleRow samples, no table: the engine.
+constexpr uint32_t kSampleWindowHalf = 1u << 22;
+constexpr uint32_t kSampleWindow = 1u << 23;
+constexpr int kSampleRow = 8;
+
 struct RenderParams {
     const uint8_t* scene;  // flat blob in HBM
     const uint32_t* seed_table;  // kSeedWindow words, or NULL: every hit seeds by the recurrence
@@ -107,6 +117,7 @@ struct RenderParams {
                            //    the gradient background tiles itself
     const float* draw_plate;  // the device's draw plate of this frame configuration (below), or NULL: `plan_tiles` makes the touched
                            //    tiles' draws itself, into ws.tile_draws
+    const float4* sample_table;  // the device's sample table (kSampleWindow rows, above), or NULL: every traced hit runs its engine
     WaveSpace ws;
     int draws_per_sample;  // 0, 2 or 4
     int stream_waves;      // waves per tile in `plan_tiles` (1, 2 or 4, <= stream_parts; choose_grids)
@@ -600,6 +611,8 @@ hipError_t launch_quantize(const float* rgba, uint8_t* out, size_t n_pixels, hip
 hipError_t launch_build_seed_table(uint32_t* table, hipStream_t stream);
 // fills table[s] = mt[397] of std::mt19937(s) for the seeds first .. first + count - 1 (count a multiple of 256)
 hipError_t launch_build_seed_table_range(uint32_t* table, uint32_t first, uint32_t count, hipStream_t stream);
+// fills the kSampleWindow rows of the device's sample table (above RenderParams)
+hipError_t launch_build_sample_table(float4* table, hipStream_t stream);
 
 // probes
 // host_reciprocals: d_count floats in device memory, 1.0f / d as the host rounds it (what the render kernels get)

@@ -851,7 +851,7 @@ __device__ __forceinline__ void reflection_body(const ReflectionFrame& __restric
                     // ---- a lane per undecided hit: its mt19937 stream at depth 1 and the S disk sample positions
                     if (soft && static_cast<uint32_t>(tid) < nu) {
                         const float4 a = s_rec[s_und[u0 + tid]];
-                        disk_sample_positions(scg, f.seed_table, nullptr, mk(a.x, a.y, a.z), 1, S, s_pos + static_cast<size_t>(tid) * 3 * S);
+                        disk_sample_positions(scg, nullptr, f.seed_table, nullptr, mk(a.x, a.y, a.z), 1, S, s_pos + static_cast<size_t>(tid) * 3 * S);
                     }
                     __syncthreads();
                     // ---- a lane per (undecided hit, light sample): count_item_rays

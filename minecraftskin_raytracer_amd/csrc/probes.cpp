@@ -91,6 +91,17 @@ int mcrt_probe_mt_uniform(int device, const uint32_t* seeds, int n_seeds, int n_
     return finish_probe(e, out, d_out, static_cast<size_t>(n_seeds) * n_draws * 4, "probe_mt");
 }
 
+int mcrt_probe_sample_rows(int device, const int32_t* seeds, int n, float* out) {
+    if (!seeds || !out || n < 0) return fail(MCRT_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; ++i)
+        if (static_cast<uint32_t>(seeds[i]) + kSampleWindowHalf >= kSampleWindow) return fail(MCRT_ERR_INVALID, "seed outside the sample table's window");
+    if (n == 0) return MCRT_OK;
+    if (mcrt_device_count() <= 0) return fail(MCRT_ERR_NO_DEVICE, "no HIP device");
+    HIP_TRY(hipSetDevice(device));
+    if (!copy_sample_rows(device, seeds, n, out)) return fail(MCRT_ERR_HIP, "the device has no sample table");
+    return MCRT_OK;
+}
+
 int mcrt_probe_detmath(int device, int op, const float* x, const float* y, size_t n, float* out) {
     if (!x || !out || op < 0 || op > 5 || (op == 2 && !y)) return fail(MCRT_ERR_INVALID, "bad argument");
     if (n == 0) return MCRT_OK;

@@ -1154,8 +1154,12 @@ __device__ __forceinline__ void write_light_samples(const SceneView& sc, const W
 }
 
 template <bool kGeneral, bool kPosed>
-__device__ __forceinline__ void emit_light_samples(const SceneView& sc, const WaveSpace& ws, uint32_t e, V3 P, V3 N, int depth, int S,
-                                                   uint32_t* my_rng) {
+__device__ __forceinline__ void emit_light_samples(const SceneView& sc, const float4* __restrict__ sample_table, const WaveSpace& ws, uint32_t e, V3 P, V3 N,
+                                                   int depth, int S, uint32_t* my_rng) {
+    if (sample_row_positions(sc, sample_table, shadow_seed(P, depth), P, S, ws.targets + static_cast<size_t>(e) * 3 * S)) {  // the seed's row of the device's table
+        ws.cand[e] = bundle_candidates<kPosed>(sc, P + N * 1e-3f, ld3(sc.hdr->light_pos), sc.hdr->light_radius);
+        return;
+    }
     typename SampleRng<kGeneral>::type rng;
     seed_light_rng<kGeneral>(rng, P, depth, S, my_rng);
     write_light_samples<kPosed>(sc, ws, e, P, N, S, rng);
@@ -1179,7 +1183,7 @@ __global__ __launch_bounds__(kBlock) void light_samples_kernel(const uint8_t* __
         if (threadIdx.x >= n) return;
         const uint32_t e = first + threadIdx.x;
         const float4 hp = ws.q_p[par][e], hn = ws.q_n[par][e];
-        emit_light_samples<kGeneral, kPosed>(sc, ws, e, mk(hp.x, hp.y, hp.z), mk(hn.x, hn.y, hn.z), __float_as_int(ws.q_d[par][e].w), S,
+        emit_light_samples<kGeneral, kPosed>(sc, p.sample_table, ws, e, mk(hp.x, hp.y, hp.z), mk(hn.x, hn.y, hn.z), __float_as_int(ws.q_d[par][e].w), S,
                                              my_rng);
     });
 }
@@ -1471,7 +1475,7 @@ __device__ __forceinline__ void lit_body(const uint8_t* __restrict__ scene_blob,
                     const LitShape ls(knobs, s_dyn);
                     if (ls.mode == SHADOW_SOFT && threadIdx.x < nu) {
                         const RecordGeom g = load_geom(p.ws, kView != kViewLdsUnposed && p.scene_posed != 0, base + ls.s_und[u0 + threadIdx.x]);
-                        disk_sample_positions(scg, p.seed_table, p.seed_table_full, g.p, g.depth, ls.S, ls.s_pos + static_cast<size_t>(threadIdx.x) * 3 * ls.S);
+                        disk_sample_positions(scg, p.sample_table, p.seed_table, p.seed_table_full, g.p, g.depth, ls.S, ls.s_pos + static_cast<size_t>(threadIdx.x) * 3 * ls.S);
                     }
                 }
                 __syncthreads();
@@ -1721,10 +1725,8 @@ __global__ __launch_bounds__(kBlock, 2) void level_shade_kernel(const uint8_t* _
             // per wave survive; threads 0 .. total-1 do it instead, so the chain runs in ceil(total / 64) waves.
             if (soft && static_cast<int>(threadIdx.x) < total) {
                 const float4 np = s_np[threadIdx.x], nn = s_nn[threadIdx.x];
-                typename SampleRng<kGeneral>::type rng;
-                const V3 P = mk(np.x, np.y, np.z);
-                seed_light_rng<kGeneral>(rng, P, __float_as_int(np.w), S, my_rng);
-                write_light_samples<kView != kViewLdsUnposed>(scg, ws, s_out_base + threadIdx.x, P, mk(nn.x, nn.y, nn.z), S, rng);
+                emit_light_samples<kGeneral, kView != kViewLdsUnposed>(scg, p.sample_table, ws, s_out_base + threadIdx.x, mk(np.x, np.y, np.z), mk(nn.x, nn.y, nn.z),
+                                                                       __float_as_int(np.w), S, my_rng);
             }
             __syncthreads();
         }

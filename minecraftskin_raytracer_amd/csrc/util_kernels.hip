@@ -47,6 +47,21 @@ __global__ __launch_bounds__(256) void seed_table_range_kernel(uint32_t* __restr
     table[s] = MtShort::word397(s);
 }
 
+// the device's sample table (kernels.h): row r = the kSampleRow elements of seed r - kSampleWindowHalf, a thread per row, by the
+// engine and the routines disk_sample_positions runs (the 397-step seeding recurrence per row: 3.3 G steps in all, well under a millisecond)
+__global__ __launch_bounds__(256) void sample_table_kernel(float4* __restrict__ table) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= kSampleWindow) return;
+    MtShort rng;
+    rng.seed(r - kSampleWindowHalf);
+    float4* __restrict__ row = table + static_cast<size_t>(r) * kSampleRow;
+    for (int i = 0; i < kSampleRow; ++i) {
+        const float d0 = rng.uniform();
+        const float d1 = rng.uniform();
+        row[i] = sample_row_element(d0, d1);
+    }
+}
+
 __global__ void quantize_kernel(const float4* rgba, uchar4* out, size_t n) {  // image_writer.cpp:18-22
     size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -192,6 +207,8 @@ hipError_t launch_build_seed_table_range(uint32_t* table, uint32_t first, uint32
     if (count == 0u || (count & 255u)) return hipErrorInvalidValue;
     return launch_flat<256>(seed_table_range_kernel, count, stream, table, first);
 }
+
+hipError_t launch_build_sample_table(float4* table, hipStream_t stream) { return launch_flat<256>(sample_table_kernel, kSampleWindow, stream, table); }
 
 hipError_t launch_probe_div_const(uint32_t d_first, uint32_t d_count, int mode, const float* host_reciprocals, unsigned long long* counts, hipStream_t stream) {
     if (d_count == 0) return hipSuccess;
