@@ -206,6 +206,18 @@ void mcrt_trim(void);
  * MCRT_SAMPLE_TABLE=0 turns it off, =2 builds it at the first such render; mcrt_trim() frees it when no scene handle is left.
  * mcrt_sample_table_info: the bytes of the device's table (0: none) and how often it was built since the process began. */
 int mcrt_sample_table_info(int device, size_t* bytes, int* builds);
+/* The three per-device tables by one index: the window seed table (above, MCRT_SEED_TABLE), the table of all seeds (2^32
+ * words, 16 GiB, built at a device's first ambient-occlusion render where three times that is free; MCRT_AO_SEED_TABLE=0 turns
+ * it off) and the sample table. */
+#define MCRT_TABLE_WINDOW 0
+#define MCRT_TABLE_FULL 1
+#define MCRT_TABLE_SAMPLE 2
+/* the bytes of table `which` on `device` (0: none) and how often it was built there since the process began (either may be
+ * NULL); which = MCRT_TABLE_SAMPLE gives what mcrt_sample_table_info gives.  MCRT_ERR_INVALID for another `which`. */
+int mcrt_device_tables_info(int device, int which, size_t* bytes, int* builds);
+/* *mask: bit `1 << which` is set where the handle holds table `which` right now, that is where its next render or pass reads
+ * that table and not the recurrence or the engine (a render that the caller captures reads no sample table all the same). */
+int mcrt_scene_tables(mcrt_scene* scene, int* mask);
 
 /* Background plates.  The gradient background tiles of a frame (three quarters of the tiles of a 1080p frame of the
  * character) do not depend on the scene: their pixels are a function of width, height, tile_size, samples_per_pixel,
@@ -1107,6 +1119,11 @@ int mcrt_probe_mt_uniform(int device, const uint32_t* seeds, int n_seeds, int n_
  * {cos, sin, sqrt, 0} per sample.  Builds the table if the device has none yet; MCRT_ERR_INVALID for a seed outside the
  * window, MCRT_ERR_HIP where there is no table (MCRT_SAMPLE_TABLE=0, no room). */
 int mcrt_probe_sample_rows(int device, const int32_t* seeds, int n, float* out);
+/* The words of a seed table for n seeds, out[i] = state word 397 of std::mt19937's seeding of seeds[i] as the table holds it.
+ * which = MCRT_TABLE_WINDOW: seeds -2^24 .. 2^24-1 in two's complement, MCRT_ERR_INVALID for one outside; MCRT_TABLE_FULL:
+ * any seed.  Builds the table if the device has none yet and lets go of it afterwards (mcrt_trim() frees a table nobody
+ * holds); MCRT_ERR_HIP where there is no table (its knob at 0, no room). */
+int mcrt_probe_seed_words(int device, int which, const uint32_t* seeds, int n, uint32_t* out);
 /* device detmath: op 0 = sinf, 1 = cosf, 2 = powf(x, y), 3 / 4 = sin / cos output of the fused
  * mcrt_sincosf, 5 = the kernels' 3-instruction reciprocal (reference: IEEE 1.0f / x), over n inputs */
 int mcrt_probe_detmath(int device, int op, const float* x, const float* y, size_t n, float* out);

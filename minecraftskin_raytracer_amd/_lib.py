@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "mcrt_skin_view_table_model", "mcrt_skin_model_of",
     "mcrt_scene_set_extra_lights", "mcrt_scene_extra_lights", "mcrt_render_lights", "mcrt_render_png_lights",
     "mcrt_probe_sample_rows", "mcrt_sample_table_info",
+    "mcrt_device_tables_info", "mcrt_scene_tables", "mcrt_probe_seed_words",
 ]
 
 

@@ -871,6 +871,15 @@ class DeviceScene:
         """Wait for the scene's device work; raises if the device flagged an internal inconsistency."""
         check(load().mcrt_scene_check(self._h))
 
+    def tables(self) -> dict:
+        """``{"window": bool, "full": bool, "sample": bool}``: the per-device tables this handle holds right now, which its next
+        render or pass reads instead of the recurrence or the engine (mcrt_scene_tables)."""
+        fn = load().mcrt_scene_tables  # bound here: a build selected with MCRT_LIB may predate it
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int)]
+        mask = C.c_int()
+        check(fn(self._h, C.byref(mask)))
+        return {name: bool(mask.value >> which & 1) for which, name in enumerate(TABLE_NAMES)}
+
     def set_lanes(self, lanes: int) -> None:
         """0 = automatic split of a render over internal streams, n >= 1 = exactly n (mcrt_scene_set_lanes)."""
         check(load().mcrt_scene_set_lanes(self._h, int(lanes)))
@@ -1491,6 +1500,40 @@ def sample_table_info(device: int = 0) -> dict:
     b, k = C.c_size_t(), C.c_int()
     check(fn(int(device), C.byref(b), C.byref(k)))
     return {"bytes": int(b.value), "builds": int(k.value)}
+
+
+TABLE_NAMES = ("window", "full", "sample")  # MCRT_TABLE_WINDOW, MCRT_TABLE_FULL, MCRT_TABLE_SAMPLE
+
+
+def device_tables_info(device: int = 0) -> dict:
+    """mcrt_device_tables_info: ``{"window": {"bytes": ..., "builds": ...}, "full": {...}, "sample": {...}}`` — per table kept on
+    ``device`` its bytes (0: none) and how often it was built there since the process began (include/mcrt.h)."""
+    fn = load().mcrt_device_tables_info  # bound here: a build selected with MCRT_LIB may predate it
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    out = {}
+    for which, name in enumerate(TABLE_NAMES):
+        b, k = C.c_size_t(), C.c_int()
+        check(fn(int(device), which, C.byref(b), C.byref(k)))
+        out[name] = {"bytes": int(b.value), "builds": int(k.value)}
+    return out
+
+
+def probe_seed_words(seeds: Sequence[int], which: str = "window", device: int = 0) -> np.ndarray:
+    """uint32[n]: the words of the device's window seed table (``which="window"``: seeds in -2^24 .. 2^24-1) or of its table
+    of all seeds (``which="full"``: any 32-bit seed) for ``seeds``; the table is built if the device has none (mcrt.h)."""
+    if which not in TABLE_NAMES[:2]:
+        raise ValueError(f"which must be one of {TABLE_NAMES[:2]}, not {which!r}")
+    s = np.asarray(seeds, np.int64).ravel()
+    lo, hi = (-(1 << 24), (1 << 24) - 1) if which == "window" else (0, (1 << 32) - 1)
+    if len(s) and (s.min() < lo or s.max() > hi):
+        raise ValueError(f"a seed outside {lo} .. {hi}")
+    s = np.ascontiguousarray((s & 0xFFFFFFFF).astype(np.uint32))
+    out = np.zeros(len(s), np.uint32)
+    fn = load().mcrt_probe_seed_words  # bound here: a build selected with MCRT_LIB may predate it
+    u32_p = C.POINTER(C.c_uint32)
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_int, u32_p, C.c_int, u32_p]
+    check(fn(int(device), TABLE_NAMES.index(which), s.ctypes.data_as(u32_p), len(s), out.ctypes.data_as(u32_p)))
+    return out
 
 
 def unpack_rows_device(config: Config, first: int, step: int, packed_ptr: int, frame_ptr: int, stream: int = 0) -> None:

@@ -207,6 +207,20 @@ bool copy_sample_rows(int device, const int32_t* seeds, int n, float* out) {
     g_sample_tables.release(device);
     return ok;
 }
+bool copy_seed_words(int device, int which, const uint32_t* seeds, int n, uint32_t* out) {
+    SeedTables& store = which == MCRT_TABLE_FULL ? g_full_tables : g_window_tables;
+    const uint32_t* table = store.acquire(device);
+    if (!table) return false;
+    const uint32_t bias = which == MCRT_TABLE_FULL ? 0u : kSeedWindowHalf;  // the window table: seed s at index s + kSeedWindowHalf
+    bool ok = true;
+    for (int i = 0; i < n && ok; ++i) {
+        const uint32_t slot = seeds[i] + bias;
+        ok = (which == MCRT_TABLE_FULL || slot < kSeedWindow) && hipMemcpy(out + i, table + slot, 4, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) (void)hipGetLastError();
+    store.release(device);
+    return ok;
+}
 void share_full_seed_table(mcrt_scene* s) {
     if (s->holds_full_table) return;
     s->seed_table_full = g_full_tables.acquire_built(s->device);
@@ -686,11 +700,19 @@ void mcrt_trim(void) {
     free_unused_plates();
 }
 
-int mcrt_sample_table_info(int device, size_t* bytes, int* builds) {
+int mcrt_device_tables_info(int device, int which, size_t* bytes, int* builds) {
+    if (which != MCRT_TABLE_WINDOW && which != MCRT_TABLE_FULL && which != MCRT_TABLE_SAMPLE) return fail(MCRT_ERR_INVALID, "no such table");
+    const SeedTables& store = which == MCRT_TABLE_WINDOW ? g_window_tables : (which == MCRT_TABLE_FULL ? g_full_tables : g_sample_tables);
     std::lock_guard<std::mutex> lock(g_seed_mutex);
-    const bool known = device >= 0 && static_cast<size_t>(device) < g_sample_tables.by_device.size();
-    if (bytes) *bytes = (known && g_sample_tables.by_device[static_cast<size_t>(device)].ptr) ? g_sample_tables.bytes : 0;
-    if (builds) *builds = known ? g_sample_tables.by_device[static_cast<size_t>(device)].builds : 0;
+    const bool known = device >= 0 && static_cast<size_t>(device) < store.by_device.size();
+    if (bytes) *bytes = (known && store.by_device[static_cast<size_t>(device)].ptr) ? store.bytes : 0;
+    if (builds) *builds = known ? store.by_device[static_cast<size_t>(device)].builds : 0;
+    return MCRT_OK;
+}
+int mcrt_sample_table_info(int device, size_t* bytes, int* builds) { return mcrt_device_tables_info(device, MCRT_TABLE_SAMPLE, bytes, builds); }
+int mcrt_scene_tables(mcrt_scene* s, int* mask) {
+    if (!s || !mask) return fail(MCRT_ERR_INVALID, "NULL argument");
+    *mask = (s->seed_table ? 1 << MCRT_TABLE_WINDOW : 0) | (s->holds_full_table ? 1 << MCRT_TABLE_FULL : 0) | (s->holds_sample_table ? 1 << MCRT_TABLE_SAMPLE : 0);
     return MCRT_OK;
 }
 int mcrt_bg_plate_info(int device, int* plates, size_t* bytes, int* builds) { return plate_info(kPlatePixels, device, plates, bytes, builds); }

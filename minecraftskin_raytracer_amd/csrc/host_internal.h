@@ -370,6 +370,10 @@ void acquire_plates(mcrt_scene* s, mcrt::RenderParams* p, int n, bool capturing,
 // the rows of `seeds` (kSampleRow float4 each, seeds inside the window) of the device's sample table to the host, for the probe;
 // the table is built if the device has none yet (whatever the sighting count); false where it cannot be
 bool copy_sample_rows(int device, const int32_t* seeds, int n, float* out);
+// the words of `seeds` of the device's window table (MCRT_TABLE_WINDOW: seeds inside the window) or its table of all seeds
+// (MCRT_TABLE_FULL) to the host, for the probe; the table is built if the device has none yet, and the call's count let go of
+// afterwards; false where there is no table (the knob, no room) or a seed lies outside the window
+bool copy_seed_words(int device, int which, const uint32_t* seeds, int n, uint32_t* out);
 // The device's repaint tables of a skin kind (64 / 32) — the 256 floats u8 / 255.0f, then per pool texel the mesh and the skin
 // pixel it is cut from (kernels.h: SkinPaintShape) — built at the kind's first repaintable handle on the device, one `users`
 // count per handle that holds them, freed by mcrt_trim() when nobody does.  nullptr: the allocation or the upload failed.

@@ -102,6 +102,18 @@ int mcrt_probe_sample_rows(int device, const int32_t* seeds, int n, float* out) 
     return MCRT_OK;
 }
 
+int mcrt_probe_seed_words(int device, int which, const uint32_t* seeds, int n, uint32_t* out) {
+    if (!seeds || !out || n < 0 || (which != MCRT_TABLE_WINDOW && which != MCRT_TABLE_FULL)) return fail(MCRT_ERR_INVALID, "bad argument");
+    if (which == MCRT_TABLE_WINDOW)
+        for (int i = 0; i < n; ++i)
+            if (seeds[i] + kSeedWindowHalf >= kSeedWindow) return fail(MCRT_ERR_INVALID, "seed outside the seed table's window");
+    if (n == 0) return MCRT_OK;
+    if (mcrt_device_count() <= 0) return fail(MCRT_ERR_NO_DEVICE, "no HIP device");
+    HIP_TRY(hipSetDevice(device));
+    if (!copy_seed_words(device, which, seeds, n, out)) return fail(MCRT_ERR_HIP, "the device has no such seed table");
+    return MCRT_OK;
+}
+
 int mcrt_probe_detmath(int device, int op, const float* x, const float* y, size_t n, float* out) {
     if (!x || !out || op < 0 || op > 5 || (op == 2 && !y)) return fail(MCRT_ERR_INVALID, "bad argument");
     if (n == 0) return MCRT_OK;
