@@ -1075,6 +1075,51 @@ int mcrt_skin_view_table_model(int skin_height, int model, const float pose[12],
  * MCRT_SKIN_CLASSIC for every other 64x64 or 64x32 image.  A classic skin with transparent arms reads as slim; a slim skin
  * whose painter filled those columns reads as classic.  -1 and the error text for NULL or another size. */
 int mcrt_skin_model_of(const uint8_t* skin_rgba8, int skin_width, int skin_height);
+/* ---- capes.  A cape is a second image, RGBA8 and exactly 64x32 (HD and animated capes: no), unwrapped as Minecraft unwraps
+ * it: the box {ox, oy, w, h, d} = {0, 0, 10, 16, 1}, 372 texels inside the image's 22x17 corner, (0,0) and (21,0) unread.
+ * The mesh is the box of size {10, 16, 1} at {0, 16, -2.5} — x -5 .. 5, y 8 .. 24, z -3 .. -2, on the body's back (the figure
+ * faces +z) — with no outer-layer offset, hinged at the pivot {0, 24, -2} by rot_x = cape_angle degrees, rot_z = 0: a positive
+ * angle moves the hem towards -z, away from the legs.  cape_angle is accepted within 0 .. 90 (10 is the usual rest angle);
+ * NaN or a value outside is MCRT_ERR_INVALID; below 0.01 degrees the box is unposed, as any part is.  The cape does NOT follow
+ * the body part's own rotation: a mesh has one pivot, and the built-in poses turn the body by 5 degrees at the most.
+ * The box is turned half a turn about y, as Minecraft's cape model is, so the face slots (0 back = -z, 1 front = +z, 2 left =
+ * +x, 3 right = -x, 4 top, 5 bottom) are cut from (x, y, w, h) = (1,1,10,16) — the outward face, seen from behind the player —
+ * (12,1,10,16), (11,1,1,16), (0,1,1,16), and (1,0,10,1) and (11,0,10,1) each read turned half a turn, texel (tx, ty) from
+ * (w-1-tx, h-1-ty).  Seen from behind (camera on the -z side, the viewer's left is +x) image column 1 lies at the +x edge and
+ * row 1 at the hinge: the picture reads as painted.
+ * The cape is the LAST mesh of its figure: index 12 of a full 64x64 table (classic or slim), 7 of a 64x32 one.  A cape whose
+ * 372 texels all have alpha 0 is dropped, as a fully transparent outer part is; cape_rgba8 NULL is the entry without a cape,
+ * byte for byte (the angle is then not read). */
+int mcrt_build_skin_scene_cape(const uint8_t* skin_rgba8, int skin_width, int skin_height, int model, const float pose[12],
+                               const uint8_t* cape_rgba8 /* 64x32, or NULL */, float cape_angle, mcrt_scene_desc** out);
+/* Host only.  The cape pixel (x, y) that texel (tx, ty) of face `face_slot` of the cape mesh is cut from; and the cape mesh's
+ * 372 texels in pool order — six faces in slot order, row-major — as pixel indices y * 64 + x (returns the count, copies
+ * min(count, capacity)).  mcrt_skin_texel[_model] keeps refusing the cape's mesh index: this is the cape's mapping. */
+int mcrt_cape_texel(int face_slot, int tx, int ty, int* cape_x, int* cape_y);
+int mcrt_cape_pool_map(int32_t* out, int capacity);
+/* A repaintable handle WITH a cape mesh: mcrt_scene_create_skin_model's figure plus the cape at cape_angle, 13 or 8 meshes, a
+ * prefix of 2688 or 1728 bytes, the skin's pool texels and then the cape's 372, whose 24 alpha-predicate words are its own.
+ * A fresh handle holds a white skin and a TRANSPARENT cape (its mesh's opaque flag clear: it is never hit).  Every entry that
+ * takes a repaintable handle takes a caped one; mcrt_scene_set_skin* leave the cape's texels, words and flag alone, and
+ * mcrt_scene_set_cape* the skin's.  The handles of one batch call (set_skins, set_views, set_capes) are all caped or all
+ * capeless. */
+int mcrt_scene_create_skin_cape(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, float cape_angle, int device, mcrt_scene** out);
+/* Repaint the cape of caped handles from 64x32 RGBA8 images: from host memory, synchronous; from device memory (4-byte
+ * aligned), asynchronous on `stream`; and n handles in one launch, cape i at d_capes + i * cape_stride_bytes (a multiple of 4,
+ * at least 8192, or 0: every handle takes the one image at d_capes).  A NULL image means a transparent cape (in the batch
+ * form: every handle's).  The handle's renders are ordered against the repaint by the library, as against a skin repaint. */
+int mcrt_scene_set_cape(mcrt_scene* scene, const uint8_t* cape_rgba8);
+int mcrt_scene_set_cape_device(mcrt_scene* scene, const uint8_t* d_cape_rgba8, void* stream);
+int mcrt_scene_set_capes_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_capes, size_t cape_stride_bytes, void* stream);
+/* The views of caped handles.  mcrt_skin_view_table_cape: mcrt_skin_view_table_model for the caped figure, 2688 or 1728
+ * bytes.  mcrt_scene_set_view_cape[_device]: mcrt_scene_set_view[_device] with another cape angle (cape_angle NULL keeps the
+ * handle's); the batch form takes one angle per scene (cape_angles NULL keeps them all).  The plain view entries on a caped
+ * handle keep its angle.  A cape angle for a capeless handle is MCRT_ERR_INVALID. */
+int mcrt_skin_view_table_cape(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, float cape_angle, void* out, size_t capacity);
+int mcrt_scene_set_view_cape(mcrt_scene* scene, const float pose[12], const mcrt_scene_desc* look, const float* cape_angle);
+int mcrt_scene_set_view_cape_device(mcrt_scene* scene, const float pose[12], const mcrt_scene_desc* look, const float* cape_angle, void* stream);
+int mcrt_scene_set_views_cape_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks,
+                                           const float* cape_angles, void* stream);
 /* MeshBuilder::buildDefaultScene (mesh_builder.cpp:204-223): white 1x1 textures, no outer layer */
 int mcrt_build_default_scene(const float pose[12], mcrt_scene_desc** out);
 /* one of the 7 built-in poses of pose.h:25-92 (index 0..6) → 12 floats; returns MCRT_ERR_INVALID

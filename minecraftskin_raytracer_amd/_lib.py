@@ -47,6 +47,9 @@ EXPORTED_SYMBOLS = [
     "mcrt_scene_set_extra_lights", "mcrt_scene_extra_lights", "mcrt_render_lights", "mcrt_render_png_lights",
     "mcrt_probe_sample_rows", "mcrt_sample_table_info",
     "mcrt_device_tables_info", "mcrt_scene_tables", "mcrt_probe_seed_words",
+    "mcrt_build_skin_scene_cape", "mcrt_cape_texel", "mcrt_cape_pool_map", "mcrt_scene_create_skin_cape",
+    "mcrt_scene_set_cape", "mcrt_scene_set_cape_device", "mcrt_scene_set_capes_batch_device",
+    "mcrt_skin_view_table_cape", "mcrt_scene_set_view_cape", "mcrt_scene_set_view_cape_device", "mcrt_scene_set_views_cape_batch_device",
 ]
 
 
@@ -139,6 +142,17 @@ def load():
         "mcrt_scene_set_view_device": (C.c_int, [vp, f_p, desc_p, vp]),
         "mcrt_scene_set_views_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.POINTER(desc_p), vp]),
         "mcrt_skin_view_table": (C.c_int, [C.c_int, f_p, desc_p, vp, C.c_size_t]),
+        "mcrt_build_skin_scene_cape": (C.c_int, [u8_p, C.c_int, C.c_int, C.c_int, f_p, u8_p, C.c_float, C.POINTER(desc_p)]),
+        "mcrt_cape_texel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mcrt_cape_pool_map": (C.c_int, [abi.c_int32_p, C.c_int]),
+        "mcrt_scene_create_skin_cape": (C.c_int, [C.c_int, C.c_int, f_p, desc_p, C.c_float, C.c_int, C.POINTER(vp)]),
+        "mcrt_scene_set_cape": (C.c_int, [vp, u8_p]),
+        "mcrt_scene_set_cape_device": (C.c_int, [vp, vp, vp]),
+        "mcrt_scene_set_capes_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_size_t, vp]),
+        "mcrt_skin_view_table_cape": (C.c_int, [C.c_int, C.c_int, f_p, desc_p, C.c_float, vp, C.c_size_t]),
+        "mcrt_scene_set_view_cape": (C.c_int, [vp, f_p, desc_p, f_p]),
+        "mcrt_scene_set_view_cape_device": (C.c_int, [vp, f_p, desc_p, f_p, vp]),
+        "mcrt_scene_set_views_cape_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, vp, C.POINTER(desc_p), vp, vp]),
         "mcrt_shot_init": (None, [shot_p]),
         "mcrt_shot_scratch_bytes": (C.c_size_t, [cfg_p, shot_p, C.c_int]),
         "mcrt_composite_shot_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, shot_p, C.POINTER(abi.McrtShotInputs), C.c_size_t, vp, vp, C.c_size_t, vp]),

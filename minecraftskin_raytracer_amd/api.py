@@ -79,9 +79,12 @@ class MeshBuilder:
     """scene/mesh_builder.h:7-34 (scene construction from skin data; native implementation)."""
 
     @staticmethod
-    def buildScene(skin_rgba8: np.ndarray, pose: Optional[Sequence[float]] = None, model: str = "classic") -> SceneDesc:
+    def buildScene(skin_rgba8: np.ndarray, pose: Optional[Sequence[float]] = None, model: str = "classic", cape: Optional[np.ndarray] = None,
+                   cape_angle: float = 10.0) -> SceneDesc:
         """SkinParser::parse (64x64 / 64x32 RGBA8) + MeshBuilder::buildScene.  ``model``: ``"classic"`` (the reference's figure),
-        ``"slim"`` (arms 3 texels wide, 64x64 skins only) or ``"auto"`` (``skin_model`` of the image)."""
+        ``"slim"`` (arms 3 texels wide, 64x64 skins only) or ``"auto"`` (``skin_model`` of the image).  ``cape``: a cape image,
+        (32, 64, 4) uint8, hung on the figure's back as its last mesh at ``cape_angle`` degrees (0 .. 90) from the body
+        (mcrt_build_skin_scene_cape); ``None``: no cape, the call as it always was."""
         skin = np.ascontiguousarray(skin_rgba8, np.uint8)
         if skin.ndim != 3 or skin.shape[2] != 4:
             raise ValueError("skin must be (H, W, 4) uint8")
@@ -94,6 +97,13 @@ class MeshBuilder:
             raise ValueError("the slim model exists for 64x64 skins only")
         p = np.asarray(pose if pose is not None else [0.0] * 12, np.float32)
         out = C.POINTER(abi.McrtSceneDesc)()
+        if cape is not None:
+            c = _cape_image(cape)
+            if w != 64 or h not in (64, 32):
+                raise ValueError(f"Invalid skin dimensions: {w}x{h} (expected 64x64 or 64x32)")
+            check(load().mcrt_build_skin_scene_cape(skin.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, abi.SKIN_SLIM if model == "slim" else abi.SKIN_CLASSIC,
+                                                    abi.fptr(p), c.ctypes.data_as(C.POINTER(C.c_uint8)), float(cape_angle), C.byref(out)))
+            return SceneDesc(_native=out)
         if model == "slim":
             rc = load().mcrt_build_skin_scene_model(skin.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, abi.SKIN_SLIM, abi.fptr(p), C.byref(out))
         else:
@@ -109,6 +119,17 @@ class MeshBuilder:
         out = C.POINTER(abi.McrtSceneDesc)()
         check(load().mcrt_build_default_scene(abi.fptr(p), C.byref(out)))
         return SceneDesc(_native=out)
+
+
+CAPE_SHAPE = (32, 64, 4)
+CAPE_TEXELS = 372
+
+
+def _cape_image(cape) -> np.ndarray:
+    a = np.ascontiguousarray(cape, np.uint8)
+    if a.shape != CAPE_SHAPE:
+        raise ValueError("a cape image is (32, 64, 4) uint8: 64x32 RGBA8")
+    return a
 
 
 def getBuiltinPoses() -> List[np.ndarray]:
@@ -678,6 +699,42 @@ def skin_pool_map(kind) -> np.ndarray:
     return out
 
 
+def cape_texel(face: int, tx: int, ty: int) -> Tuple[int, int]:
+    """The cape pixel (x, y) that texel (tx, ty) of face slot ``face`` of a cape mesh is cut from (mcrt_cape_texel)."""
+    x, y = C.c_int(), C.c_int()
+    check(load().mcrt_cape_texel(int(face), int(tx), int(ty), C.byref(x), C.byref(y)))
+    return int(x.value), int(y.value)
+
+
+def cape_pool_map() -> np.ndarray:
+    """Per texel of a cape mesh, in pool order — six faces in slot order, row-major — the cape pixel index ``y * 64 + x`` it is
+    cut from (mcrt_cape_pool_map): 372 int32.  In a caped figure's pool these are the LAST 372 texels."""
+    lib = load()
+    out = np.zeros(CAPE_TEXELS, np.int32)
+    if lib.mcrt_cape_pool_map(out.ctypes.data_as(abi.c_int32_p), len(out)) != len(out):
+        raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
+    return out
+
+
+def pool_to_cape(values, fill=0) -> np.ndarray:
+    """Scatters a pool-order plane of a cape mesh — ``values``: (372,) or (372, c), e.g. the last 372 rows of a caped figure's
+    bake — into a cape-shaped image ``(32, 64[, c])`` through ``cape_pool_map``; pixels the unwrap does not read hold ``fill``."""
+    pmap = cape_pool_map()
+    v = np.asarray(values)
+    if v.ndim not in (1, 2) or v.shape[0] != len(pmap):
+        raise ValueError(f"values must be ({len(pmap)},) or ({len(pmap)}, c)")
+    out = np.full((32 * 64,) + v.shape[1:], fill, v.dtype)
+    out[pmap] = v  # (every pixel is used once at most)
+    return out.reshape((32, 64) + v.shape[1:])
+
+
+def _cape_angle(cape_angle) -> float:
+    a = float(cape_angle)
+    if not (0.0 <= a <= 90.0):
+        raise ValueError("cape_angle must be within 0 .. 90 degrees")
+    return a
+
+
 def _view_pose(pose) -> Optional[np.ndarray]:
     if pose is None:
         return None
@@ -687,18 +744,22 @@ def _view_pose(pose) -> Optional[np.ndarray]:
     return p
 
 
-def skin_view_table(kind, pose: Optional[Sequence[float]] = None, look=None) -> bytes:
+def skin_view_table(kind, pose: Optional[Sequence[float]] = None, look=None, cape_angle: Optional[float] = None) -> bytes:
     """The view-dependent prefix ``[header][mesh table]`` of the blob of ``DeviceScene.for_skin(kind, pose, look)`` — bytes
     ``[0, texel_offset)``, 2496 for ``"S64"`` and ``"S64S"``, 1536 for ``"S32"`` — computed on the host
     (mcrt_skin_view_table_model): what a view change writes into a resident scene, but for the MESH_OPAQUE bits, which are the
-    white figure's here."""
+    white figure's here.  ``cape_angle``: the prefix of the CAPED figure at that angle instead (mcrt_skin_view_table_cape), 2688 or
+    1728 bytes."""
     h, model = _skin_kind(kind)
     p, d = _view_pose(pose), _as_desc(look) if look is not None else None
     lib = load()
     args = (h, model, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None)
-    n = lib.mcrt_skin_view_table_model(*args, None, 0)
+    fn = lib.mcrt_skin_view_table_model
+    if cape_angle is not None:
+        args, fn = args + (_cape_angle(cape_angle),), lib.mcrt_skin_view_table_cape
+    n = fn(*args, None, 0)
     buf = C.create_string_buffer(max(n, 1))
-    if n <= 0 or lib.mcrt_skin_view_table_model(*args, buf, n) != n:
+    if n <= 0 or fn(*args, buf, n) != n:
         raise McrtError(abi.MCRT_ERR_INVALID, lib.mcrt_last_error().decode("utf-8", "replace"))
     return buf.raw[:n]
 
@@ -769,6 +830,7 @@ class DeviceScene:
 
     skin_height = 0  # 64 / 32 for a repaintable scene (for_skin)
     skin_model = "classic"  # "slim" for a repaintable scene of the slim model (for_skin("S64S", ...))
+    has_cape = False  # a repaintable scene with a cape mesh (for_skin(..., cape=True))
 
     def __init__(self, scene, device: int = 0):
         self._desc = _as_desc(scene)
@@ -777,12 +839,14 @@ class DeviceScene:
         check(load().mcrt_scene_create(self._desc.ptr, device, C.byref(self._h)))
 
     @classmethod
-    def for_skin(cls, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0) -> "DeviceScene":
+    def for_skin(cls, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0, cape: bool = False, cape_angle: float = 10.0) -> "DeviceScene":
         """A REPAINTABLE scene (mcrt_scene_create_skin_model): the builder's figure for ``kind`` (``"S64"`` / ``"S32"`` or the skin's
         height, ``"S64S"`` / ``"slim"`` for a 64x64 skin on the slim model) at ``pose`` with every part present — always the full mesh table of ``skin_texel``, 12 or 7 meshes — which
         ``set_skin`` / ``set_skin_device`` / ``set_skins_batch_device`` give a new skin without rebuilding the scene.  ``look``:
         a ``Scene`` / ``SceneDesc`` whose light, camera and background are taken (its meshes are ignored); ``None``: the
-        builder's.  White and opaque until the first repaint."""
+        builder's.  White and opaque until the first repaint.  ``cape=True`` (mcrt_scene_create_skin_cape): the cape mesh behind
+        the figure as mesh 12 or 7, at ``cape_angle`` degrees, which ``set_cape`` / ``set_cape_device`` / ``set_capes_batch_device``
+        paint; transparent — never hit — until then."""
         h, model = _skin_kind(kind)
         self = object.__new__(cls)
         self._desc = _as_desc(look) if look is not None else None
@@ -791,9 +855,31 @@ class DeviceScene:
         self.skin_height = h
         self.skin_model = "slim" if model == abi.SKIN_SLIM else "classic"
         p = _view_pose(pose)
+        if cape:
+            self.has_cape = True
+            check(load().mcrt_scene_create_skin_cape(h, model, abi.fptr(p) if p is not None else None, self._desc.ptr if self._desc is not None else None,
+                                                     _cape_angle(cape_angle), int(device), C.byref(self._h)))
+            return self
         check(load().mcrt_scene_create_skin_model(h, model, abi.fptr(p) if p is not None else None, self._desc.ptr if self._desc is not None else None,
                                             int(device), C.byref(self._h)))
         return self
+
+    def _need_cape(self) -> None:
+        if not self.has_cape:
+            raise ValueError("this scene has no cape: create it with DeviceScene.for_skin(..., cape=True)")
+
+    def set_cape(self, cape: Optional[np.ndarray]) -> None:
+        """Repaint the cape from a host image, (32, 64, 4) uint8, or ``None`` for no cape (transparent); synchronous
+        (mcrt_scene_set_cape).  The skin stays as it is."""
+        self._need_cape()
+        a = _cape_image(cape) if cape is not None else None
+        check(load().mcrt_scene_set_cape(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None))
+
+    def set_cape_device(self, ptr: int, stream: int = 0) -> None:
+        """Repaint the cape from 8192 bytes of RGBA8 in device memory, 4-byte aligned (0: no cape); asynchronous on ``stream``
+        (mcrt_scene_set_cape_device).  Ordered against the handle's renders like ``set_skin_device``."""
+        self._need_cape()
+        check(load().mcrt_scene_set_cape_device(self._h, C.c_void_p(ptr or None), C.c_void_p(stream)))
 
     def _skin_bytes(self) -> int:
         if not self.skin_height:
@@ -816,19 +902,31 @@ class DeviceScene:
         self._skin_bytes()
         check(load().mcrt_scene_set_skin_device(self._h, C.c_void_p(ptr or None), C.c_void_p(stream)))
 
-    def set_view(self, pose: Optional[Sequence[float]] = None, look=None) -> None:
+    def set_view(self, pose: Optional[Sequence[float]] = None, look=None, cape_angle: Optional[float] = None) -> None:
         """Another pose and / or look for this repaintable scene, synchronously (mcrt_scene_set_view): afterwards it is what
-        ``for_skin(kind, pose, look)`` repainted with the current skin would be, bit for bit.  ``None`` keeps the scene's own."""
+        ``for_skin(kind, pose, look)`` repainted with the current skin would be, bit for bit.  ``None`` keeps the scene's own.
+        ``cape_angle`` (a caped scene): another cape angle too (mcrt_scene_set_view_cape)."""
         self._skin_bytes()
         p, d = _view_pose(pose), _as_desc(look) if look is not None else None
+        if cape_angle is not None:
+            self._need_cape()
+            a = C.c_float(_cape_angle(cape_angle))
+            check(load().mcrt_scene_set_view_cape(self._h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None, C.byref(a)))
+            return
         check(load().mcrt_scene_set_view(self._h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None))
 
-    def set_view_device(self, pose: Optional[Sequence[float]] = None, look=None, stream: int = 0) -> None:
+    def set_view_device(self, pose: Optional[Sequence[float]] = None, look=None, stream: int = 0, cape_angle: Optional[float] = None) -> None:
         """The same, asynchronous on ``stream`` (mcrt_scene_set_view_device); ``pose`` and ``look`` are read before the call
         returns.  The handle's renders are ordered against it by the library; its layers, ground, reflection, light, bake and
         pick passes by the caller."""
         self._skin_bytes()
         p, d = _view_pose(pose), _as_desc(look) if look is not None else None
+        if cape_angle is not None:
+            self._need_cape()
+            a = C.c_float(_cape_angle(cape_angle))
+            check(load().mcrt_scene_set_view_cape_device(self._h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None, C.byref(a),
+                                                         C.c_void_p(stream)))
+            return
         check(load().mcrt_scene_set_view_device(self._h, abi.fptr(p) if p is not None else None, d.ptr if d is not None else None, C.c_void_p(stream)))
 
     def blob(self) -> bytes:
@@ -1229,13 +1327,27 @@ def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, ski
     check(load().mcrt_scene_set_skins_batch_device(arr, n, C.c_void_p(ptr or None), int(skin_stride_bytes), C.c_void_p(stream)))
 
 
-def set_views_batch_device(device_scenes: Sequence["DeviceScene"], poses=None, looks=None, stream: int = 0) -> None:
+def set_capes_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, cape_stride_bytes: int = 8192, stream: int = 0) -> None:
+    """One launch repaints the capes of N caped scenes (mcrt_scene_set_capes_batch_device): cape i is the 64x32 RGBA8 image at
+    ``ptr + i * cape_stride_bytes`` in device memory; a stride of 0: one image for all; ``ptr`` 0: every cape transparent.
+    Asynchronous on ``stream``."""
+    handles = _handles(device_scenes)
+    arr = _handle_array(handles)
+    check(load().mcrt_scene_set_capes_batch_device(arr, len(handles), C.c_void_p(ptr or None), int(cape_stride_bytes), C.c_void_p(stream)))
+
+
+def set_views_batch_device(device_scenes: Sequence["DeviceScene"], poses=None, looks=None, stream: int = 0, cape_angles=None) -> None:
     """One launch gives N repaintable scenes of one image size their views (mcrt_scene_set_views_batch_device): ``poses`` — N
     poses of 12 floats, or ``None``: every scene keeps its own; ``looks`` — N entries, each a ``Scene`` / ``SceneDesc`` or
     ``None`` (that scene keeps its look), or ``None`` for all.  Asynchronous on ``stream``; the arguments are read before the
-    call returns."""
+    call returns.  ``cape_angles`` (caped scenes): N cape angles, or ``None``: every scene keeps its own."""
     handles = _handles(device_scenes)
     n = len(handles)
+    angles = None
+    if cape_angles is not None:
+        angles = np.ascontiguousarray(cape_angles, np.float32)
+        if angles.shape != (n,):
+            raise ValueError(f"cape_angles must hold {n} floats: one angle per scene")
     p = None
     if poses is not None:
         p = np.ascontiguousarray(poses, np.float32)
@@ -1252,6 +1364,10 @@ def set_views_batch_device(device_scenes: Sequence["DeviceScene"], poses=None, l
     if descs is not None:
         ptrs = [d.ptr if d is not None else None for d in descs]  # (kept alive until the call has returned)
         look_arr = (C.POINTER(abi.McrtSceneDesc) * max(n, 1))(*[C.cast(q, C.POINTER(abi.McrtSceneDesc)) if q is not None else C.POINTER(abi.McrtSceneDesc)() for q in ptrs])
+    if angles is not None:
+        check(load().mcrt_scene_set_views_cape_batch_device(arr, n, p.ctypes.data_as(C.c_void_p) if p is not None and n else None, look_arr,
+                                                            angles.ctypes.data_as(C.c_void_p) if n else None, C.c_void_p(stream)))
+        return
     check(load().mcrt_scene_set_views_batch_device(arr, n, p.ctypes.data_as(C.c_void_p) if p is not None and n else None, look_arr, C.c_void_p(stream)))
 
 
@@ -1264,27 +1380,32 @@ class SkinBatch:
     ``models`` — ``None``: all classic; ``"auto"``: ``skin_model`` of each image; or one of ``"classic"`` / ``"slim"`` per skin —
     and repaint the chosen scenes of a mixed batch in the same ONE launch."""
 
-    def __init__(self, n: int, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0, slim: bool = False):
+    def __init__(self, n: int, kind, pose: Optional[Sequence[float]] = None, look=None, device: int = 0, slim: bool = False, cape: bool = False,
+                 cape_angle: float = 10.0):
         import torch
 
         self.kind_height = _skin_height(kind)
         if slim and self.kind_height != 64:
             raise ValueError("the slim model exists for 64x64 skins only")
         self.device = int(device)
+        self.cape = bool(cape)
         self._torch = torch
         self.scenes: List[DeviceScene] = []
         self.slim_scenes: List[DeviceScene] = []  # slot i's scene of the slim model (slim=True), else empty
         try:
             for _ in range(int(n)):
-                self.scenes.append(DeviceScene.for_skin(self.kind_height, pose, look, device))
+                self.scenes.append(DeviceScene.for_skin(self.kind_height, pose, look, device, cape=self.cape, cape_angle=cape_angle))
             for _ in range(int(n) if slim else 0):
-                self.slim_scenes.append(DeviceScene.for_skin("S64S", pose, look, device))
+                self.slim_scenes.append(DeviceScene.for_skin("S64S", pose, look, device, cape=self.cape, cape_angle=cape_angle))
         except Exception:
             self.close()
             raise
         self._dev = torch.device("cuda", self.device)
         self._skins = torch.zeros((max(int(n), 1), self.kind_height, 64, 4), dtype=torch.uint8, device=self._dev)
         self._staging = torch.zeros(self._skins.shape, dtype=torch.uint8).pin_memory()
+        if self.cape:  # the cape images, beside the skins'
+            self._capes = torch.zeros((max(int(n), 1),) + CAPE_SHAPE, dtype=torch.uint8, device=self._dev)
+            self._cape_staging = torch.zeros(self._capes.shape, dtype=torch.uint8).pin_memory()
         self._out = {}  # (bytes per frame) -> device buffer, pinned host buffer
         self._mode = None
 
@@ -1305,12 +1426,21 @@ class SkinBatch:
         for s in self.scenes + self.slim_scenes:
             s.set_extra_lights(lights)
 
-    def set_views(self, poses=None, looks=None) -> None:
+    def set_views(self, poses=None, looks=None, cape_angles=None) -> None:
         """Another pose and / or look for the batch's scenes without rebuilding them (``set_views_batch_device``): ``poses`` —
         one pose of 12 floats for all scenes, or one per scene (n, 12); ``looks`` — one ``Scene`` / ``SceneDesc`` for all, or a
         sequence of n (entries may be ``None``); ``None`` keeps what the scenes have.  On the current torch stream, ahead of the
-        next ``render`` / ``layers``."""
+        next ``render`` / ``layers``.  ``cape_angles`` (a caped batch): one angle for all, or one per scene."""
         n = len(self.scenes)
+        if cape_angles is not None:
+            if not self.cape:
+                raise ValueError("this batch holds no capes: create it with cape=True")
+            c = np.asarray(cape_angles, np.float32)
+            if c.shape == ():
+                c = np.full((n,), c, np.float32)
+            elif c.shape != (n,):
+                raise ValueError(f"cape_angles must be one angle or ({n},)")
+            cape_angles = c
         if poses is not None:
             p = np.ascontiguousarray(poses, np.float32)
             if p.shape == (12,):
@@ -1322,13 +1452,14 @@ class SkinBatch:
             looks = [looks] * n if isinstance(looks, (Scene, SceneDesc)) else list(looks)
             if len(looks) != n:
                 raise ValueError(f"looks must be one look or {n} of them")
-        if n == 0 or (poses is None and looks is None):
+        if n == 0 or (poses is None and looks is None and cape_angles is None):
             return
         if self.slim_scenes:  # both scenes of every slot, in the one launch
             poses = np.concatenate([poses, poses]) if poses is not None else None
             looks = looks + looks if looks is not None else None
+            cape_angles = np.concatenate([cape_angles, cape_angles]) if cape_angles is not None else None
         with self._torch.cuda.device(self._dev):
-            set_views_batch_device(self.scenes + self.slim_scenes, poses, looks, stream=self._torch.cuda.current_stream().cuda_stream)
+            set_views_batch_device(self.scenes + self.slim_scenes, poses, looks, stream=self._torch.cuda.current_stream().cuda_stream, cape_angles=cape_angles)
 
     def _check_skins(self, skins) -> np.ndarray:
         a = np.ascontiguousarray(skins, np.uint8)
@@ -1348,13 +1479,35 @@ class SkinBatch:
             raise ValueError("this batch holds no slim scenes: create it with slim=True")
         return [self.slim_scenes[i] if k == "slim" else self.scenes[i] for i, k in enumerate(names)]
 
-    def _paint(self, skins, stream, models=None) -> List[DeviceScene]:
+    def _check_capes(self, capes, m: int) -> Optional[np.ndarray]:
+        """The cape images of the ``m`` skins as (m, 32, 64, 4), a ``None`` entry zeros (no cape); ``None`` on a capeless batch."""
+        if not self.cape:
+            if capes is not None:
+                raise ValueError("this batch holds no capes: create it with cape=True")
+            return None
+        out = np.zeros((m,) + CAPE_SHAPE, np.uint8)
+        if capes is not None:
+            capes = list(capes)
+            if len(capes) != m:
+                raise ValueError(f"capes must hold {m} entries: one image (or None) per skin")
+            for i, c in enumerate(capes):
+                if c is not None:
+                    out[i] = _cape_image(c)
+        return out
+
+    def _paint(self, skins, stream, models=None, capes=None) -> List[DeviceScene]:
         """Uploads and repaints; returns the scenes that now hold the skins.  Every caller synchronises `stream` before it
         returns (the pinned staging buffer is reused)."""
         torch = self._torch
         a = self._check_skins(skins)
         chosen = self._chosen(a, models)
         m = len(a)
+        c = self._check_capes(capes, m)
+        if m and c is not None:  # one upload and one launch beside the skins'
+            self._cape_staging[:m].numpy()[...] = c
+            with torch.cuda.stream(stream):
+                self._capes[:m].copy_(self._cape_staging[:m], non_blocking=True)
+            set_capes_batch_device(chosen, self._capes.data_ptr(), stream=stream.cuda_stream)
         if m:
             self._staging[:m].numpy()[...] = a
             with torch.cuda.stream(stream):
@@ -1370,8 +1523,10 @@ class SkinBatch:
             self._out[key] = got
         return got
 
-    def render(self, skins, config: Config, rgba8: bool = False, background: str = "reference", models=None) -> np.ndarray:
-        """``skins``: (m <= n, H, 64, 4) uint8.  Returns (m, height, width, 4) float32, or uint8 with ``rgba8``."""
+    def render(self, skins, config: Config, rgba8: bool = False, background: str = "reference", models=None, capes=None) -> np.ndarray:
+        """``skins``: (m <= n, H, 64, 4) uint8.  Returns (m, height, width, 4) float32, or uint8 with ``rgba8``.  ``capes`` (a
+        batch created with ``cape=True``): m entries, each a (32, 64, 4) uint8 cape image or ``None`` for no cape; ``None``: no
+        capes at all."""
         torch = self._torch
         mode = abi.background_mode(background)
         w, h, no_frame = _frame(config)
@@ -1379,7 +1534,7 @@ class SkinBatch:
             stream = torch.cuda.current_stream()
             if no_frame:  # nothing is painted either (the staging buffer stays idle)
                 return _default_frames(len(self._check_skins(skins)), h, w, rgba8)
-            chosen = self._paint(skins, stream, models)
+            chosen = self._paint(skins, stream, models, capes)
             m = len(chosen)
             dtype = torch.uint8 if rgba8 else torch.float32
             if m == 0:
@@ -1395,7 +1550,7 @@ class SkinBatch:
             stream.synchronize()
             return host[:m].numpy().copy()
 
-    def shots(self, skins, config: Config, shot: Optional[abi.Shot] = None, ground=0.0, rgba8: bool = True, bounds: bool = False, models=None):
+    def shots(self, skins, config: Config, shot: Optional[abi.Shot] = None, ground=0.0, rgba8: bool = True, bounds: bool = False, models=None, capes=None):
         """The studio shots of the ``m`` skins (``TileRenderer.renderShotBatch`` of the scenes built per skin, bit for bit): one
         upload, one repaint, one ``render_shot_batch_device`` call — render, ground, reflection and blend on the device — and
         one download of 4 B/pixel (16 with ``rgba8=False``).  ``ground``: one height for all (0.0: the soles of the builder's
@@ -1414,7 +1569,7 @@ class SkinBatch:
                 raise ValueError("ground heights are needed: a resident scene does not keep its description")
             heights = _ground_heights(list(range(len(a))), ground)
             need = shot_scratch_bytes(config, shot, len(self.scenes), bounds)  # (raises nothing: an invalid shot is refused by the call below)
-            chosen = self._paint(a, stream, models)
+            chosen = self._paint(a, stream, models, capes)
             m = len(chosen)
             if m == 0:
                 none = _default_frames(0, h, w, rgba8)
@@ -1436,7 +1591,7 @@ class SkinBatch:
                 stream.synchronize()  # (a refused shot too: the repaint reads the pinned staging buffer)
             return (host[:m].numpy().copy(), box_host[:m].numpy().copy()) if bounds else host[:m].numpy().copy()
 
-    def layers(self, skins, config: Config, layers=abi.LAYER_NAMES, models=None) -> dict:
+    def layers(self, skins, config: Config, layers=abi.LAYER_NAMES, models=None, capes=None) -> dict:
         """The geometry layers of the ``m`` skins' frames (``TileRenderer.renderLayersBatch``'s planes) through
         ``render_layers_batch_device``, behind the repaint on the same stream."""
         torch = self._torch
@@ -1446,7 +1601,7 @@ class SkinBatch:
             stream = torch.cuda.current_stream()
             if no_frame:  # nothing is painted either
                 return {k: abi.LAYERS.empty(k, len(self._check_skins(skins)), h, w) for k in names}
-            chosen = self._paint(skins, stream, models)
+            chosen = self._paint(skins, stream, models, capes)
             m = len(chosen)
             if m == 0:
                 return {k: abi.LAYERS.empty(k, 0, h, w) for k in names}

@@ -129,6 +129,10 @@ int create_scene_from_blob(const std::vector<uint8_t>& b, int device, mcrt_scene
     s->skin_tables = nullptr;
     s->skin_height = 0;
     s->skin_model = MCRT_SKIN_CLASSIC;
+    if (s->cape_tables) release_cape_tables(device);  // a pooled shell that was a caped handle
+    s->cape_tables = nullptr;
+    s->has_cape = 0;
+    s->cape_angle = 0.0f;
     s->has_pose = s->has_look = false;  // (mcrt_scene_create_skin notes its own)
     s->budget = 0;  // a budget halved under memory pressure is not inherited
     s->have_last = false;  // a pooled shell was synchronised when its previous owner let go of it
@@ -187,6 +191,7 @@ void remember_view(mcrt_scene* s, const float pose[12], const mcrt_scene_desc* l
 }  // namespace
 
 extern "C" mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, int model, const float pose[12]);  // scene_builder.cpp
+extern "C" mcrt_scene_desc* mcrt_detail_white_figure_cape(int skin_height, int model, const float pose[12], float cape_angle, int cape_alpha);
 
 namespace mcrt_host {
 void apply_look(mcrt_scene_desc* desc, const mcrt_scene_desc* look) {
@@ -212,6 +217,24 @@ int skin_view_table(int skin_height, int model, const float pose[12], const mcrt
     mcrt_scene_desc_free(desc);
     if (!flat) return fail(MCRT_ERR_INVALID, err);
     // the white figure's own MESH_OPAQUE bits: every texel of an all-(255,255,255,255) skin is opaque
+    const FlatHeader* h = reinterpret_cast<const FlatHeader*>(table.data());
+    FlatMesh* fm = reinterpret_cast<FlatMesh*>(table.data() + h->mesh_offset);
+    for (uint32_t i = 0; i < h->n_meshes; ++i) fm[i].flags |= MESH_OPAQUE;
+    return MCRT_OK;
+}
+
+int skin_view_table_cape(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, float cape_angle, std::vector<uint8_t>& table) {
+    if (skin_height != 64 && skin_height != 32) return fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    if (model != MCRT_SKIN_CLASSIC && !(model == MCRT_SKIN_SLIM && skin_height == 64))
+        return fail(MCRT_ERR_INVALID, "model must be MCRT_SKIN_CLASSIC, or MCRT_SKIN_SLIM with a 64x64 skin");
+    if (!cape_angle_ok(cape_angle)) return fail(MCRT_ERR_INVALID, "cape_angle must be within 0 .. 90 degrees");
+    mcrt_scene_desc* desc = mcrt_detail_white_figure_cape(skin_height, model, pose, cape_angle, 255);
+    if (look) apply_look(desc, look);
+    std::string err;
+    const bool flat = flatten_view_table(desc, table, err);
+    mcrt_scene_desc_free(desc);
+    if (!flat) return fail(MCRT_ERR_INVALID, err);
+    // the white figure's and the white cape's own MESH_OPAQUE bits
     const FlatHeader* h = reinterpret_cast<const FlatHeader*>(table.data());
     FlatMesh* fm = reinterpret_cast<FlatMesh*>(table.data() + h->mesh_offset);
     for (uint32_t i = 0; i < h->n_meshes; ++i) fm[i].flags |= MESH_OPAQUE;
@@ -264,6 +287,50 @@ int mcrt_scene_create_skin_model(int skin_height, int model, const float pose[12
     remember_view(s, pose, look);
     *out = s;
     return MCRT_OK;
+}
+
+int mcrt_scene_create_skin_cape(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, float cape_angle, int device, mcrt_scene** out) {
+    if (!out) return fail(MCRT_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (skin_height != 64 && skin_height != 32) return fail(MCRT_ERR_INVALID, "skin_height must be 64 or 32");
+    if (model != MCRT_SKIN_CLASSIC && !(model == MCRT_SKIN_SLIM && skin_height == 64))
+        return fail(MCRT_ERR_INVALID, "model must be MCRT_SKIN_CLASSIC, or MCRT_SKIN_SLIM with a 64x64 skin");
+    if (!cape_angle_ok(cape_angle)) return fail(MCRT_ERR_INVALID, "cape_angle must be within 0 .. 90 degrees");
+    // the white figure with a cape mesh that is kept although every texel of it is transparent: the full table of 13 or 8
+    // meshes, the cape's texels zero, its predicate words "alpha == 0" and its MESH_OPAQUE clear — all the flattener's own
+    mcrt_scene_desc* desc = mcrt_detail_white_figure_cape(skin_height, model, pose, cape_angle, 0);
+    if (!desc) return fail(MCRT_ERR_INVALID, "the scene builder failed");
+    if (look) apply_look(desc, look);
+    std::vector<uint8_t> b;
+    std::string err;
+    const bool flat = flatten_scene(desc, b, err);
+    mcrt_scene_desc_free(desc);
+    if (!flat) return fail(MCRT_ERR_INVALID, err);
+    mcrt_scene* s = nullptr;
+    if (const int rc = create_scene_from_blob(b, device, &s); rc != MCRT_OK) return rc;
+    s->skin_model = model;  // (before the tables: a shell's release names the store by its own height and model)
+    s->skin_tables = acquire_skin_tables(device, skin_height, model);
+    s->cape_tables = s->skin_tables ? acquire_cape_tables(device) : nullptr;
+    if (!s->skin_tables || !s->cape_tables) {
+        if (s->skin_tables) release_skin_tables(device, skin_height, model);
+        s->skin_tables = nullptr;
+        s->skin_model = MCRT_SKIN_CLASSIC;
+        mcrt_scene_destroy(s);
+        return fail(MCRT_ERR_HIP, "the device's repaint tables could not be built");
+    }
+    s->skin_height = skin_height;
+    s->has_cape = 1;
+    s->cape_angle = cape_angle;
+    remember_view(s, pose, look);
+    *out = s;
+    return MCRT_OK;
+}
+
+int mcrt_skin_view_table_cape(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, float cape_angle, void* out, size_t capacity) {
+    std::vector<uint8_t> t;
+    if (skin_view_table_cape(skin_height, model, pose, look, cape_angle, t) != MCRT_OK) return 0;
+    if (out && capacity) std::memcpy(out, t.data(), t.size() < capacity ? t.size() : capacity);
+    return static_cast<int>(t.size());
 }
 
 int mcrt_skin_view_table(int skin_height, const float pose[12], const mcrt_scene_desc* look, void* out, size_t capacity) {

@@ -527,9 +527,53 @@ void release_skin_tables(int device, int skin_height, int model) {
     std::vector<SkinTables>& by_device = g_skin_tables[skin_kind_index(skin_height, model)];
     if (static_cast<size_t>(device) < by_device.size() && by_device[static_cast<size_t>(device)].users > 0) --by_device[static_cast<size_t>(device)].users;
 }
+// ---- and the cape's (kernels.h: CapePaintShape), one per device: the same 256 floats, then per texel of the cape mesh its
+// cape pixel, from the builder's map (scene_builder.cpp).  2.5 KB.
+extern "C" int mcrt_cape_pool_map(int32_t* out, int capacity);  // scene_builder.cpp
+namespace {
+std::vector<SkinTables> g_cape_tables;  // by device (g_skin_mutex)
+}
+const void* acquire_cape_tables(int device) {
+    std::lock_guard<std::mutex> lock(g_skin_mutex);
+    if (g_cape_tables.size() <= static_cast<size_t>(device)) g_cape_tables.resize(static_cast<size_t>(device) + 1);
+    SkinTables& t = g_cape_tables[static_cast<size_t>(device)];
+    if (!t.ptr) {
+        int32_t pixel[kCapeTexels];
+        if (mcrt_cape_pool_map(pixel, kCapeTexels) != kCapeTexels) return nullptr;  // the builder's map outgrew the kernel's: no repaint
+        std::vector<uint8_t> host(cape_tables_bytes());
+        float* unit = reinterpret_cast<float*>(host.data());
+        for (int i = 0; i < 256; ++i) unit[i] = static_cast<uint8_t>(i) / 255.0f;  // as mcrt_build_skin_scene_cape
+        uint16_t* map = reinterpret_cast<uint16_t*>(unit + 256);
+        for (int i = 0; i < kCapeTexels; ++i) {
+            if (pixel[i] < 0 || pixel[i] >= kCapeImageBytes / 4) return nullptr;  // never a read outside the image
+            map[i] = static_cast<uint16_t>(pixel[i]);
+        }
+        void* p = nullptr;
+        if (hipMalloc(&p, host.size()) != hipSuccess || hipMemcpy(p, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            if (p) (void)hipFree(p);
+            return nullptr;
+        }
+        t.ptr = p;
+    }
+    ++t.users;
+    return t.ptr;
+}
+void release_cape_tables(int device) {
+    std::lock_guard<std::mutex> lock(g_skin_mutex);
+    if (static_cast<size_t>(device) < g_cape_tables.size() && g_cape_tables[static_cast<size_t>(device)].users > 0) --g_cape_tables[static_cast<size_t>(device)].users;
+}
 namespace {
 void free_unused_skin_tables() {  // mcrt_trim
     std::lock_guard<std::mutex> lock(g_skin_mutex);
+    for (size_t d = 0; d < g_cape_tables.size(); ++d) {
+        SkinTables& t = g_cape_tables[d];
+        if (t.ptr && t.users == 0) {
+            (void)hipSetDevice(static_cast<int>(d));
+            (void)hipFree(t.ptr);
+            t.ptr = nullptr;
+        }
+    }
     for (auto& by_device : g_skin_tables)
         for (size_t d = 0; d < by_device.size(); ++d) {
             SkinTables& t = by_device[d];
@@ -589,6 +633,7 @@ void destroy_scene_now(mcrt_scene* s) {
     if (s->holds_full_table) g_full_tables.release(s->device);
     if (s->holds_sample_table) g_sample_tables.release(s->device);
     if (s->skin_tables) release_skin_tables(s->device, s->skin_height, s->skin_model);
+    if (s->cape_tables) release_cape_tables(s->device);
     release_plates(s);
     s->blob.release();  // the other buffers are released by their destructors below
     for (auto& ln : s->lanes) {

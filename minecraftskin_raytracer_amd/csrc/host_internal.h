@@ -114,8 +114,12 @@ struct mcrt_scene {
     // the three words the no-device tests already own, so their zeroed blocks stay classic handles.  The batch entries' argument
     // checks do not read it (handles of both models may be mixed); what follows them does.
     int skin_model = 0;
+    // Whether a repaintable handle has a cape mesh behind its figure (mcrt.h, "capes"; mcrt_scene_create_skin_cape), the fifth
+    // word: zero is "no cape", so the zeroed blocks of the no-device tests stay capeless handles.  The batch entries read it
+    // in their argument checks: the handles of one call are all caped or all capeless.
+    int has_cape = 0;
     // The handle's extra lights (mcrt.h, "extra lights"; mcrt_scene_set_extra_lights), unused entries zero.  Directly behind the
-    // four words above: the passes that refuse a handle with extra lights read the count behind their other argument checks,
+    // five words above: the passes that refuse a handle with extra lights read the count behind their other argument checks,
     // and the zeroed blocks of the no-device tests then read 0.  Host state only — a render's launches carry a copy as a kernel
     // argument — so a change needs no ordering against renders in flight.  Reset where a pooled shell is reused.
     mcrt::LightSet extra = {};
@@ -180,6 +184,9 @@ struct mcrt_scene {
     bool holds_sample_table = false;
     const void* skin_tables = nullptr;  // a repaintable handle's share of the device's repaint tables (kernels.h: SkinPaintShape)
     DeviceBuffer skin;                  // mcrt_scene_set_skin: the uploaded image
+    const void* cape_tables = nullptr;  // a caped handle's share of the device's cape repaint tables (kernels.h: CapePaintShape)
+    DeviceBuffer cape;                  // mcrt_scene_set_cape: the uploaded image
+    float cape_angle = 0.0f;            // a caped handle's cape angle, as its creation or its last view gave it
     // plates this shell holds a `users` count of, by kind, least recently used first: its recorded launch graphs and its
     // launches in flight may read them, so one is let go of only behind a device synchronisation (acquire_plates)
     std::vector<Plate*> plates[kPlateKinds];
@@ -188,6 +195,7 @@ struct mcrt_scene {
 static_assert(offsetof(mcrt_scene, device) == 0 && offsetof(mcrt_scene, skin_height) == sizeof(int), "mcrt_scene: device, then skin_height (see the member)");
 static_assert(offsetof(mcrt_scene, n_texels) == 2 * sizeof(int), "mcrt_scene: n_texels is the third word (see the member)");
 static_assert(offsetof(mcrt_scene, skin_model) == 3 * sizeof(int), "mcrt_scene: skin_model is the fourth word (see the member)");
+static_assert(offsetof(mcrt_scene, has_cape) == 4 * sizeof(int), "mcrt_scene: has_cape is the fifth word (see the member)");
 
 namespace mcrt_host {
 
@@ -382,6 +390,9 @@ constexpr int kSkinKinds = 3;
 inline int skin_kind_index(int skin_height, int model) { return skin_height == 32 ? 1 : (model == 1 ? 2 : 0); }
 const void* acquire_skin_tables(int device, int skin_height, int model);
 void release_skin_tables(int device, int skin_height, int model);
+// and the cape's (kernels.h: CapePaintShape), one per device, held by caped handles in the same way
+const void* acquire_cape_tables(int device);
+void release_cape_tables(int device);
 size_t pool_limit(int device);
 bool pool_scene(mcrt_scene* s);             // false: not kept, the caller destroys it
 mcrt_scene* take_pooled_scene(int device);  // device < 0: any
@@ -440,6 +451,11 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
 // gives the n repaintable handles the views (poses[i], looks[i]); NULL poses, looks or looks[i]: the handle's own
 // (mcrt_scene_set_views_batch_device)
 int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, hipStream_t stream);
+// the same with one cape angle per caped handle, cape_angles NULL: kept (mcrt_scene_set_views_cape_batch_device)
+int set_views_cape_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, const float* cape_angles,
+                                hipStream_t stream);
+// repaints the capes of the n caped handles from the 64x32 images at d_capes + i * stride_bytes (mcrt_scene_set_capes_batch_device)
+int set_capes_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_capes, size_t stride_bytes, hipStream_t stream);
 
 // ---- api.cpp
 // the light, camera and background fields of `look` into `desc` (what mcrt_scene_create_skin reads of a look)
@@ -447,6 +463,9 @@ void apply_look(mcrt_scene_desc* desc, const mcrt_scene_desc* look);
 // The prefix [FlatHeader][FlatMesh x n] of the blob of the kind's white figure at pose / look (NULL: the builder's own), with
 // MESH_OPAQUE on every mesh as that figure has it.  No device work.
 int skin_view_table(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, std::vector<uint8_t>& table);
+// the same for the caped figure (mcrt.h, "capes"): one more mesh, the cape at cape_angle, also with MESH_OPAQUE
+int skin_view_table_cape(int skin_height, int model, const float pose[12], const mcrt_scene_desc* look, float cape_angle, std::vector<uint8_t>& table);
+inline bool cape_angle_ok(float a) { return a >= 0.0f && a <= 90.0f; }  // (false for NaN)
 
 }  // namespace mcrt_host
 

@@ -478,14 +478,40 @@ struct SkinPaintFrame {
 };
 size_t skin_tables_bytes(int n_texels);
 
+// ---- capes on resident scenes (mcrt_scene_set_cape_device & co): a caped handle's blob holds the cape as its LAST mesh, its
+// 372 texels behind the skin's in the pool.  The skin's texel counts are all multiples of 16, so the cape's 24 alpha-predicate
+// words are its own.  One workgroup per scene rewrites what a cape image decides of the blob: those texels, those words and the
+// cape mesh's MESH_OPAQUE bit.  Nothing else of the blob is touched — the skin kernels above, given the skin's counts and
+// n_meshes without the cape, in turn leave the cape's alone.
+constexpr int kCapeTexels = 372;       // faces 10x16, 10x16, 1x16, 1x16, 10x1, 10x1
+constexpr int kCapeImageBytes = 64 * 32 * 4;
+constexpr int kCapeAlphaWords = 24;    // the last one holds 4 texels
+constexpr int kCapedMaxMeshes = kSkinMaxMeshes + 1;
+// what the scenes of one launch share.  `tables` (device_stores.cpp, per device): 256 floats i / 255.0f, then kCapeTexels
+// uint16 cape pixel indices y * 64 + x, in pool order.
+struct CapePaintShape {
+    const void* tables;
+};
+// Where the cape lies travels with the frame, not the shape: a slim skin's pool is shorter than a classic one's, and the two
+// models mix in one launch.  Read through the frame table these are scalar loads like the pointers.
+struct CapePaintFrame {
+    uint8_t* scene;         // the resident blob
+    const uint8_t* cape;    // 64x32 RGBA8, row-major, 4-byte aligned; NULL: a transparent cape
+    uint32_t flags_offset;  // of the cape mesh's FlatMesh::flags in the blob
+    uint32_t texel_offset;  // of the cape's first texel, a multiple of 16
+    uint32_t alpha_offset;  // of the cape's first alpha-predicate word
+    uint32_t reserved;      // (32 bytes: a frame is two aligned scalar loads)
+};
+size_t cape_tables_bytes();
+
 // ---- views of resident scenes (mcrt_scene_set_view_device & co): the prefix [FlatHeader][FlatMesh x n] of a repaintable
 // handle's blob is what pose, camera and light decide, but for the MESH_OPAQUE bit of every FlatMesh::flags, which the skin
 // owns.  One wave per scene copies a table the host flattened (flatten_view_table) over that prefix in 16-byte chunks and
 // keeps those bits as the blob has them.  Nothing from texel_offset on is touched.
-constexpr int kViewMaxChunks = 192;  // 64 lanes x 3 chunks: (192 + 12 * 192) / 16 = 156 for a 64x64 skin, 96 for a 64x32 one
+constexpr int kViewMaxChunks = 192;  // 64 lanes x 3 chunks: (192 + 12 * 192) / 16 = 156 for a 64x64 skin, 96 for a 64x32 one; with a cape mesh 168 and 108
 struct SceneViewShape {
     uint32_t mesh_offset;  // of the kind's blob (FlatHeader), a multiple of 16
-    int n_meshes;          // 12 or 7
+    int n_meshes;          // 12 or 7; 13 or 8 for a caped handle (168 or 108 chunks)
     int n_chunks;          // texel_offset / 16
 };
 struct SceneViewFrame {
@@ -550,7 +576,7 @@ hipError_t launch_seed_tiles_batch(const RenderParams& p0, const RenderParams* d
 // plan → (background) → primary → (ao) → lit → resolve, one launch each for all n_frames (<= kBatchMaxFrames) frames
 hipError_t launch_render_batch(const RenderParams& p0, const BatchPlan& plan, const RenderParams* d_table, int n_frames, hipStream_t stream);
 
-// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground occlusion, ground reflection, light layers, light bake, studio shot, skin repaints, views ========
+// ======== passes (pass_kernels.hip): layers and picks, ground shadow, ground occlusion, ground reflection, light layers, light bake, studio shot, skin repaints, cape repaints, views ========
 hipError_t launch_layers(const LayersFrame& f, const LayersShape& shape, int view, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; max_dyn: the largest
 // frame's LDS tables
@@ -596,6 +622,10 @@ hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shap
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame; frame i takes
 // shapes[frame i's kind] — the two 64x64 models of one batch; a batch of one kind passes its shape twice
 hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, const SkinPaintShape shapes[kSkinBatchShapes], hipStream_t stream);
+bool cape_frame_ok(const CapePaintFrame& f);  // alignment and order of a frame's offsets: what the kernel's stores need
+hipError_t launch_cape_paint(const CapePaintFrame& f, const CapePaintShape& shape, hipStream_t stream);
+// frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
+hipError_t launch_cape_paint_batch(const CapePaintFrame* d_table, int n_frames, const CapePaintShape& shape, hipStream_t stream);
 hipError_t launch_scene_view(const SceneViewFrame& f, const SceneViewShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_scene_view_batch(const SceneViewFrame* d_table, int n_frames, const SceneViewShape& shape, hipStream_t stream);

@@ -255,6 +255,64 @@ __global__ __launch_bounds__(kSkinBlock) void skin_paint_mixed_kernel(SkinPaintT
 }
 
 // ---------------------------------------------------------------------------------------------
+// capes on resident scenes (kernels.h: CapePaintFrame): a caped handle's blob takes a new cape from a 64x32 RGBA8 image in
+// device memory (NULL: a transparent one).  One workgroup of 256 threads per scene:
+//   the host's 256 floats u8 / 255.0f go to LDS — four reads per texel at indices the image decides
+//   1 lane / pool texel (372: two strides of 256)   its cape pixel through the map, four table reads, one 16-byte store; the
+//                                                    two ballots per wave and their interleaving as in skin_paint_body;
+//                                                    lanes past texel 371 contribute zero bits, as the flattener leaves them
+//   lane 0                                           the cape mesh's MESH_OPAQUE bit, an ordinary load and store
+// The IMAGE is not staged in LDS.  The unwrap reads 88 bytes of each of 17 rows, every pixel once: 17 cache lines of 128 bytes
+// in all, seven or so per wave load (a face is 10 texels wide), each fetched once — staging would put a second barrier and an
+// LDS round trip behind the same 17 line fetches and buy no reuse.  The skin kernel stages because its image is read whole,
+// 16 bytes per lane; here a third of 17 rows is read, 4 bytes per lane.
+// Every store is a vector store; nothing of the blob but the cape's 372 texels, its 24 predicate words and that bit is written.
+// ---------------------------------------------------------------------------------------------
+constexpr int kCapeBlock = 256;
+static_assert(kCapeAlphaWords == (kCapeTexels + 15) / 16, "cape_paint_body: the cape's alpha-predicate words");
+__device__ __forceinline__ void cape_paint_body(const CapePaintFrame& __restrict__ f, const CapePaintShape& __restrict__ sh) {
+    __shared__ float s_unit[256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float* __restrict__ unit = static_cast<const float*>(sh.tables);
+    const uint16_t* __restrict__ map = reinterpret_cast<const uint16_t*>(unit + 256);
+    s_unit[tid] = unit[tid];
+    __syncthreads();
+    const uint32_t* __restrict__ cape = reinterpret_cast<const uint32_t*>(f.cape);
+    float4* __restrict__ pool = reinterpret_cast<float4*>(f.scene + f.texel_offset);
+    uint32_t* __restrict__ abits = reinterpret_cast<uint32_t*>(f.scene + f.alpha_offset);
+    bool any_zero = false;
+    for (int base = 0; base < kCapeTexels; base += kCapeBlock) {  // (uniform per workgroup: every wave reaches its ballots)
+        const int i = base + tid;
+        bool zero = false, positive = false;
+        if (i < kCapeTexels) {
+            const uint32_t px = cape ? cape[map[i]] : 0u;  // (`cape` is uniform)
+            const uint32_t a = px >> 24;
+            pool[i] = make_float4(s_unit[px & 255u], s_unit[(px >> 8) & 255u], s_unit[(px >> 16) & 255u], s_unit[a]);
+            zero = a == 0u, positive = a != 0u;
+            any_zero = any_zero || zero;
+        }
+        const unsigned long long z = __ballot(zero), p = __ballot(positive);
+        // the wave's 64 texels are words w0 .. w0 + 3 (a wave starts at a multiple of 64 texels): lane k forms word k
+        const uint32_t word = static_cast<uint32_t>(i - lane) / 16u + static_cast<uint32_t>(lane);
+        if (lane < 4 && word < static_cast<uint32_t>(kCapeAlphaWords)) {
+            const uint32_t zk = static_cast<uint32_t>(z >> (16 * lane)) & 0xffffu, pk = static_cast<uint32_t>(p >> (16 * lane)) & 0xffffu;
+            abits[word] = spread16(zk) | (spread16(pk) << 1);
+        }
+    }
+    const int clear = __syncthreads_or(any_zero ? 1 : 0);
+    if (tid == 0) {
+        uint32_t* flags = reinterpret_cast<uint32_t*>(f.scene + f.flags_offset);
+        const uint32_t current = *flags;
+        *flags = clear ? (current & ~static_cast<uint32_t>(MESH_OPAQUE)) : (current | MESH_OPAQUE);
+    }
+}
+__global__ __launch_bounds__(kCapeBlock) void cape_paint_kernel(const CapePaintFrame f, const CapePaintShape sh) { cape_paint_body(f, sh); }
+using CapePaintTable = const __attribute__((address_space(4))) CapePaintFrame*;
+__global__ __launch_bounds__(kCapeBlock) void cape_paint_batch_kernel(CapePaintTable table, const CapePaintShape sh) {
+    cape_paint_body(*(const CapePaintFrame*)(table + blockIdx.y), sh);
+}
+
+// ---------------------------------------------------------------------------------------------
 // views of resident scenes (kernels.h: SceneViewFrame): a repaintable handle's blob takes the header and the mesh table of
 // another pose, camera and light from a table the host flattened.  One wave per scene:
 //   lane i   chunks i, i + 64, i + 128 of the prefix [0, texel_offset), 16 bytes each, one load and one store per chunk;
@@ -1937,9 +1995,27 @@ hipError_t launch_skin_paint_batch(const SkinPaintFrame* d_table, int n_frames, 
         hipLaunchKernelGGL(skin_paint_mixed_kernel, grid, dim3(kSkinBlock), 0, stream, SkinPaintTable(d_table), shapes[0], shapes[1]);
     return hipGetLastError();
 }
+// ---- capes on resident scenes (kernels.h) -----------------------------------------------------------
+// 16-byte texel stores, 4-byte words; the parts in the blob's order.  (The frames of a batch are in device memory: their
+// caller, set_capes_batch_device, checks each with this before it uploads them.)
+bool cape_frame_ok(const CapePaintFrame& f) {
+    return f.scene && (reinterpret_cast<uintptr_t>(f.cape) & 3u) == 0 && f.flags_offset % 4u == 0 && f.texel_offset % 16u == 0 && f.alpha_offset % 4u == 0 &&
+           f.flags_offset + 4u <= f.texel_offset && f.texel_offset + static_cast<uint32_t>(kCapeTexels) * 16u <= f.alpha_offset;
+}
+hipError_t launch_cape_paint(const CapePaintFrame& f, const CapePaintShape& shape, hipStream_t stream) {
+    if (!shape.tables || !cape_frame_ok(f)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cape_paint_kernel, dim3(1), dim3(kCapeBlock), 0, stream, f, shape);
+    return hipGetLastError();
+}
+hipError_t launch_cape_paint_batch(const CapePaintFrame* d_table, int n_frames, const CapePaintShape& shape, hipStream_t stream) {
+    if (n_frames <= 0) return hipSuccess;
+    if (!shape.tables || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cape_paint_batch_kernel, dim3(1, static_cast<unsigned>(n_frames)), dim3(kCapeBlock), 0, stream, CapePaintTable(d_table), shape);
+    return hipGetLastError();
+}
 // ---- views of resident scenes (kernels.h) -------------------------------------------------------------
 static bool view_shape_ok(const SceneViewShape& sh) {  // three chunks per lane; the mesh table inside the prefix
-    return sh.n_chunks > 0 && sh.n_chunks <= kViewMaxChunks && sh.mesh_offset % 16u == 0 && sh.n_meshes >= 0 && sh.n_meshes <= kSkinMaxMeshes &&
+    return sh.n_chunks > 0 && sh.n_chunks <= kViewMaxChunks && sh.mesh_offset % 16u == 0 && sh.n_meshes >= 0 && sh.n_meshes <= kCapedMaxMeshes &&
            sh.mesh_offset / 16u + kMeshChunks * static_cast<uint32_t>(sh.n_meshes) <= static_cast<uint32_t>(sh.n_chunks);
 }
 hipError_t launch_scene_view(const SceneViewFrame& f, const SceneViewShape& shape, hipStream_t stream) {

@@ -957,6 +957,20 @@ int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config*
 // predicates and the MESH_OPAQUE bits of its blob.  The blob is what the handle's renders read, so a repaint sits in the
 // handle's event chain like a render (join_handle_chain / extend_handle_chain, the halves begin_ / end_handle_render use).
 // It uses no workspace and no counters: flags_checked and the lanes stay as they are.
+namespace {
+const char* const kMixedCapes = "the handles of a batch must all have a cape or all have none";
+// what of a repaintable handle's blob (header h) the skin owns: everything but the cape's mesh, its 372 texels and — the skin's
+// texel count being a multiple of 16 — its 24 alpha-predicate words
+struct SkinCounts {
+    int n_texels, n_meshes;
+    uint32_t alpha_words;
+};
+SkinCounts skin_counts(const mcrt_scene* s, const FlatHeader* h) {
+    if (!s->has_cape) return SkinCounts{static_cast<int>(h->n_texels), static_cast<int>(h->n_meshes), h->alpha_words};
+    return SkinCounts{static_cast<int>(h->n_texels) - kCapeTexels, static_cast<int>(h->n_meshes) - 1, h->alpha_words - static_cast<uint32_t>(kCapeAlphaWords)};
+}
+}  // namespace
+
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream) {
     // argument checks, before any device work (the first ones do not look inside the handles)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n must be >= 0");
@@ -972,6 +986,8 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
             return fail(MCRT_ERR_INVALID, "a handle was not created by mcrt_scene_create_skin (only those hold the full mesh table a repaint writes)");
     for (int i = 1; i < n; ++i)
         if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must take images of one size (one skin kind, but for the two 64x64 models)");
+    for (int i = 1; i < n; ++i)
+        if ((scenes[i]->has_cape != 0) != (scenes[0]->has_cape != 0)) return fail(MCRT_ERR_INVALID, kMixedCapes);
     const size_t image_bytes = static_cast<size_t>(64) * static_cast<size_t>(kind) * 4;
     if (stride_bytes < image_bytes) return fail(MCRT_ERR_INVALID, "skin_stride_bytes is smaller than the skin image");
     for (int i = 1; i < n; ++i)
@@ -996,8 +1012,11 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
         if (shape.tables) continue;
         const FlatHeader* h = reinterpret_cast<const FlatHeader*>(s->host_meshes.data());
         shape.tables = s->skin_tables;
-        shape.n_texels = static_cast<int>(h->n_texels), shape.n_meshes = static_cast<int>(h->n_meshes), shape.skin_bytes = static_cast<int>(image_bytes);
-        shape.mesh_offset = h->mesh_offset, shape.texel_offset = h->texel_offset, shape.alpha_offset = h->alpha_offset, shape.alpha_words = h->alpha_words;
+        // (a caped handle: the SKIN's texels, words and meshes — the cape's, behind them, are mcrt_scene_set_cape's, and the
+        // kernel's last step would otherwise set the cape mesh's MESH_OPAQUE from a bit no skin texel ever sets)
+        const SkinCounts c = skin_counts(s, h);
+        shape.n_texels = c.n_texels, shape.n_meshes = c.n_meshes, shape.skin_bytes = static_cast<int>(image_bytes);
+        shape.mesh_offset = h->mesh_offset, shape.texel_offset = h->texel_offset, shape.alpha_offset = h->alpha_offset, shape.alpha_words = c.alpha_words;
     }
     for (int k = 0; k < kSkinBatchShapes; ++k)
         if (!shapes[k].tables) shapes[k] = shapes[1 - k];
@@ -1010,8 +1029,9 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
         // every handle of a model has that model's layout: a frame writes n_texels texels and alpha_words words of ITS blob
         const FlatHeader* h = reinterpret_cast<const FlatHeader*>(s->host_meshes.data());
         const SkinPaintShape& shape = shapes[f.kind];
-        if (s->skin_tables != shape.tables || static_cast<int>(h->n_texels) != shape.n_texels || static_cast<int>(h->n_meshes) != shape.n_meshes ||
-            h->mesh_offset != shape.mesh_offset || h->texel_offset != shape.texel_offset || h->alpha_offset != shape.alpha_offset || h->alpha_words != shape.alpha_words)
+        const SkinCounts c = skin_counts(s, h);
+        if (s->skin_tables != shape.tables || c.n_texels != shape.n_texels || c.n_meshes != shape.n_meshes ||
+            h->mesh_offset != shape.mesh_offset || h->texel_offset != shape.texel_offset || h->alpha_offset != shape.alpha_offset || c.alpha_words != shape.alpha_words)
             return fail(MCRT_ERR_HIP, "internal error: a handle's blob does not have the layout of its skin kind");
     }
     for (int i = 0; i < n; ++i)
@@ -1028,6 +1048,73 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
     return MCRT_OK;
 }
 
+// ---- capes on resident scenes (mcrt_scene_set_cape_device & co): one workgroup per caped handle rewrites the cape's texels,
+// its alpha predicates and its mesh's MESH_OPAQUE bit.  In the handles' event chains like a skin repaint; no workspace, no
+// counters.  d_capes NULL: every cape transparent; stride 0: one image for all.
+int set_capes_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_capes, size_t stride_bytes, hipStream_t stream) {
+    // argument checks, before any device work (they read `device`, `skin_height` and `has_cape` of a handle, nothing else)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n must be >= 0");
+    if (n > 0 && !scenes) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (stride_bytes % 4 != 0) return fail(MCRT_ERR_INVALID, "cape_stride_bytes must be a multiple of 4");
+    if ((reinterpret_cast<uintptr_t>(d_capes) & 3u) != 0) return fail(MCRT_ERR_INVALID, "the cape images must be aligned to 4 bytes");
+    if (stride_bytes != 0 && stride_bytes < static_cast<size_t>(kCapeImageBytes)) return fail(MCRT_ERR_INVALID, "cape_stride_bytes is smaller than the cape image (64x32 RGBA8), and not 0");
+    if (n == 0) return MCRT_OK;
+    const int kind = scenes[0]->skin_height, device = scenes[0]->device;
+    for (int i = 0; i < n; ++i)
+        if (scenes[i]->skin_height != 64 && scenes[i]->skin_height != 32)
+            return fail(MCRT_ERR_INVALID, "a handle was not created by mcrt_scene_create_skin_cape (only those hold the cape mesh a cape repaint writes)");
+    for (int i = 1; i < n; ++i)
+        if ((scenes[i]->has_cape != 0) != (scenes[0]->has_cape != 0)) return fail(MCRT_ERR_INVALID, kMixedCapes);
+    if (!scenes[0]->has_cape) return fail(MCRT_ERR_INVALID, "a handle has no cape: create it with mcrt_scene_create_skin_cape");
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->skin_height != kind) return fail(MCRT_ERR_INVALID, "the handles of a batch must take images of one size (one skin kind, but for the two 64x64 models)");
+    for (int i = 1; i < n; ++i)
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+    {
+        std::vector<mcrt_scene*> sorted(scenes, scenes + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (two images for one blob)");
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a repaint cannot be recorded into a caller's graph (it takes the handles' events)");
+    (void)hipGetLastError();
+    // where the cape lies in each blob, from the handle's own header: behind the skin's texels and words, the last mesh
+    CapePaintShape shape{};
+    shape.tables = scenes[0]->cape_tables;
+    std::vector<CapePaintFrame> frames(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        const mcrt_scene* s = scenes[i];
+        const FlatHeader* h = reinterpret_cast<const FlatHeader*>(s->host_meshes.data());
+        CapePaintFrame& f = frames[static_cast<size_t>(i)];
+        f = CapePaintFrame{};
+        bool ok = s->host_meshes.size() >= sizeof(FlatHeader) && s->cape_tables == shape.tables && shape.tables && h->n_meshes >= 1 &&
+                  h->n_texels >= static_cast<uint32_t>(kCapeTexels) && (h->n_texels - kCapeTexels) % 16u == 0 && h->alpha_words == (h->n_texels + 15u) / 16u &&
+                  h->texel_offset == h->mesh_offset + h->n_meshes * static_cast<uint32_t>(sizeof(FlatMesh)) && h->alpha_offset == h->texel_offset + h->n_texels * 16u &&
+                  h->blob_bytes == h->alpha_offset + h->alpha_words * 4u;
+        if (ok) {
+            f.scene = static_cast<uint8_t*>(s->blob.ptr);
+            f.cape = d_capes ? d_capes + static_cast<size_t>(i) * stride_bytes : nullptr;
+            f.flags_offset = h->mesh_offset + (h->n_meshes - 1u) * static_cast<uint32_t>(sizeof(FlatMesh)) + static_cast<uint32_t>(offsetof(FlatMesh, flags));
+            f.texel_offset = h->texel_offset + (h->n_texels - static_cast<uint32_t>(kCapeTexels)) * 16u;
+            f.alpha_offset = h->alpha_offset + (h->alpha_words - static_cast<uint32_t>(kCapeAlphaWords)) * 4u;
+            ok = cape_frame_ok(f);
+        }
+        if (!ok) return fail(MCRT_ERR_HIP, "internal error: a handle's blob does not have the layout of a caped figure");
+    }
+    for (int i = 0; i < n; ++i)
+        if (const int rc = join_handle_chain(scenes[i], stream); rc != MCRT_OK) return rc;
+    const int rc = launch_pass(
+        device, frames, stream, "cape repaint launches", [&](const CapePaintFrame& f) { return launch_cape_paint(f, shape, stream); },
+        [&](const CapePaintFrame* d_table, int m) { return launch_cape_paint_batch(d_table, m, shape, stream); });
+    if (rc != MCRT_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (const int rc = extend_handle_chain(scenes[i], stream); rc != MCRT_OK) return rc;
+    return MCRT_OK;
+}
+
 // ---- views of resident scenes (mcrt_scene_set_view_device & co): the prefix [FlatHeader][FlatMesh x n] of a repaintable
 // handle's blob is flattened on the host for the new pose and look (skin_view_table: the flattener's own code, no texel read),
 // the tables of a call travel in ONE asynchronous copy through a slot of the table ring — pinned staging, a device buffer
@@ -1037,6 +1124,13 @@ int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_sk
 // remembered view — what touched_tiles_per_row, lds_fit and the passes' views plan from, so a render's RenderParams (and with
 // them the recorded launch graph it may replay: launch_or_replay compares every word) are those of a fresh handle at that view.
 int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, hipStream_t stream) {
+    return set_views_cape_batch_device(scenes, n, poses, looks, nullptr, stream);
+}
+
+// The same with a cape angle per caped handle (cape_angles NULL: every handle keeps its own): a caped handle's table is the
+// caped figure's (skin_view_table_cape) — one mesh and twelve chunks more, the same kernel.
+int set_views_cape_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, const float* cape_angles,
+                                hipStream_t stream) {
     // argument checks, before any device work (they read `device` and `skin_height` of a handle, nothing else)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n must be >= 0");
     if (n > 0 && !scenes) return fail(MCRT_ERR_INVALID, "NULL argument");
@@ -1057,6 +1151,12 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
         if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
             return fail(MCRT_ERR_INVALID, "a scene handle is listed twice (two views for one blob)");
     }
+    const bool caped = scenes[0]->has_cape != 0;
+    for (int i = 1; i < n; ++i)
+        if ((scenes[i]->has_cape != 0) != caped) return fail(MCRT_ERR_INVALID, kMixedCapes);
+    if (cape_angles && !caped) return fail(MCRT_ERR_INVALID, "a cape angle was given for a handle without a cape");
+    for (int i = 0; cape_angles && i < n; ++i)
+        if (!cape_angle_ok(cape_angles[i])) return fail(MCRT_ERR_INVALID, "cape_angle must be within 0 .. 90 degrees");
     HIP_TRY(hipSetDevice(device));
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a view change cannot be recorded into a caller's graph (it takes the handles' events)");
     (void)hipGetLastError();
@@ -1067,7 +1167,9 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
         const mcrt_scene* s = scenes[i];
         const float* pose = poses ? poses[i] : (s->has_pose ? s->view_pose : nullptr);
         const mcrt_scene_desc* look = (looks && looks[i]) ? looks[i] : (s->has_look ? &s->view_look : nullptr);
-        if (const int rc = skin_view_table(kind, s->skin_model, pose, look, table); rc != MCRT_OK) return rc;  // the handle's own model
+        const int made = caped ? skin_view_table_cape(kind, s->skin_model, pose, look, cape_angles ? cape_angles[i] : s->cape_angle, table)
+                               : skin_view_table(kind, s->skin_model, pose, look, table);  // the handle's own model
+        if (made != MCRT_OK) return made;
         bool same = table_bytes >= sizeof(FlatHeader) && table.size() == table_bytes && s->host_meshes.size() == table_bytes;
         if (same) {
             const FlatHeader* a = reinterpret_cast<const FlatHeader*>(table.data());
@@ -1124,6 +1226,7 @@ int set_views_batch_device(mcrt_scene* const* scenes, int n, const float (*poses
             s->has_look = true;
             apply_look(&s->view_look, looks[i]);
         }
+        if (cape_angles) s->cape_angle = cape_angles[i];
         if (const int chained = extend_handle_chain(s, stream); chained != MCRT_OK && rc == MCRT_OK) rc = chained;
     }
     return rc;
@@ -1304,6 +1407,52 @@ int mcrt_scene_set_skin(mcrt_scene* s, const uint8_t* skin_rgba8) {
     // (a second upload into s->skin may not overtake the repaint that reads the first: this call waits for its own)
     HIP_TRY(hipMemcpy(s->skin.ptr, skin_rgba8, bytes, hipMemcpyHostToDevice));
     const int rc = mcrt_scene_set_skin_device(s, static_cast<const uint8_t*>(s->skin.ptr), nullptr);
+    if (rc != MCRT_OK) return rc;
+    HIP_TRY(hipEventSynchronize(s->last_done));
+    return MCRT_OK;
+}
+
+int mcrt_scene_set_cape_device(mcrt_scene* s, const uint8_t* d_cape_rgba8, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    return set_capes_batch_device(one, 1, d_cape_rgba8, static_cast<size_t>(kCapeImageBytes), static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_capes_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_capes, size_t cape_stride_bytes, void* stream) {
+    return set_capes_batch_device(scenes, n, d_capes, cape_stride_bytes, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_cape(mcrt_scene* s, const uint8_t* cape_rgba8) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if ((s->skin_height != 64 && s->skin_height != 32) || !s->has_cape)
+        return fail(MCRT_ERR_INVALID, "the handle has no cape: create it with mcrt_scene_create_skin_cape");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(s->cape.reserve(static_cast<size_t>(kCapeImageBytes)));
+    // (a second upload into s->cape may not overtake the repaint that reads the first: this call waits for its own)
+    if (cape_rgba8)
+        HIP_TRY(hipMemcpy(s->cape.ptr, cape_rgba8, static_cast<size_t>(kCapeImageBytes), hipMemcpyHostToDevice));
+    else
+        HIP_TRY(hipMemset(s->cape.ptr, 0, static_cast<size_t>(kCapeImageBytes)));  // no cape: zeros
+    const int rc = mcrt_scene_set_cape_device(s, static_cast<const uint8_t*>(s->cape.ptr), nullptr);
+    if (rc != MCRT_OK) return rc;
+    HIP_TRY(hipEventSynchronize(s->last_done));
+    return MCRT_OK;
+}
+
+int mcrt_scene_set_view_cape_device(mcrt_scene* s, const float pose[12], const mcrt_scene_desc* look, const float* cape_angle, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const mcrt_scene_desc* one_look[1] = {look};
+    return set_views_cape_batch_device(one, 1, reinterpret_cast<const float(*)[12]>(pose), one_look, cape_angle, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_views_cape_batch_device(mcrt_scene* const* scenes, int n, const float (*poses)[12], const mcrt_scene_desc* const* looks, const float* cape_angles,
+                                           void* stream) {
+    return set_views_cape_batch_device(scenes, n, poses, looks, cape_angles, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_scene_set_view_cape(mcrt_scene* s, const float pose[12], const mcrt_scene_desc* look, const float* cape_angle) {
+    const int rc = mcrt_scene_set_view_cape_device(s, pose, look, cape_angle, nullptr);
     if (rc != MCRT_OK) return rc;
     HIP_TRY(hipEventSynchronize(s->last_done));
     return MCRT_OK;

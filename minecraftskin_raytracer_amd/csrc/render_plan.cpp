@@ -467,5 +467,6 @@ size_t bake_occlusion_lds_bytes(const BakeFrame& f) {
 }
 // ---- skins on resident scenes (kernels.h) -----------------------------------------------------------
 size_t skin_tables_bytes(int n_texels) { return 256 * sizeof(float) + static_cast<size_t>(n_texels) * sizeof(uint16_t); }
+size_t cape_tables_bytes() { return 256 * sizeof(float) + static_cast<size_t>(kCapeTexels) * sizeof(uint16_t); }
 
 }  // namespace mcrt

@@ -87,6 +87,25 @@ const PartBox& part_box(int model, bool outer, int part) {
     return (outer ? kOuterBox : kInnerBox)[part];
 }
 
+// The cape (mcrt.h, "capes"): a 64x32 image of its own, unwrapped as Minecraft unwraps it — the box {10, 16, 1} at the image's
+// origin.  The box hangs on the body's back turned half a turn about y, so add_box's face slots take the unwrap's faces
+// crosswise: the -z slot (outward, seen from behind the player) the unwrap's "front" rectangle (1, 1, 10, 16), the +z slot
+// (towards the body) (12, 1, 10, 16), the +x slot (11, 1, 1, 16), the -x slot (0, 1, 1, 16); top (1, 0, 10, 1) and bottom
+// (11, 0, 10, 1) keep their slots and are read turned half a turn.  The -z face puts texel column 0 at the +x edge and row 0
+// at the top (face_uv), which from behind is the viewer's left and the hinge: the picture reads as painted, nothing is mirrored.
+const PartBox kCapeBox = {0, 0, 10, 16, 1};
+constexpr int kCapeWidth = 64, kCapeHeight = 32, kCapeTexels = 372;
+struct CapeSource {
+    Rect rect;
+    bool turned;  // read turned half a turn: texel (tx, ty) <- (w - 1 - tx, h - 1 - ty)
+};
+// where face `face_slot` (add_box's order, 0..5) of the cape mesh is cut from: the one answer for the builder, mcrt_cape_texel
+// and the pool map
+CapeSource cape_source(int face_slot) {
+    static const int unwrap_face[6] = {1, 0, 3, 2, 4, 5};
+    return CapeSource{face_rect(kCapeBox, unwrap_face[face_slot]), face_slot >= 4};
+}
+
 PartTex unwrap(const SkinImage& img, const PartBox& b) {
     auto face = [&](int f) {
         const Rect r = face_rect(b, f);
@@ -112,6 +131,33 @@ Region flip_h(const Region& r) {
             std::memcpy(&m.px[4 * (static_cast<size_t>(y) * r.w + x)],
                         &r.px[4 * (static_cast<size_t>(y) * r.w + (r.w - 1 - x))], 16);
     return m;
+}
+
+Region turn_half(const Region& r) {
+    Region m;
+    m.w = r.w;
+    m.h = r.h;
+    m.px.resize(r.px.size());
+    const size_t n = r.px.size() / 4;
+    for (size_t i = 0; i < n; ++i) std::memcpy(&m.px[4 * i], &r.px[4 * (n - 1 - i)], 16);
+    return m;
+}
+
+PartTex cape_part(const uint8_t* rgba8) {  // 64x32 RGBA8
+    SkinImage img;
+    img.w = kCapeWidth;
+    img.h = kCapeHeight;
+    img.px.resize(static_cast<size_t>(kCapeWidth) * kCapeHeight * 4);
+    for (size_t i = 0; i < img.px.size(); ++i) img.px[i] = rgba8[i] / 255.0f;
+    Region* slot[6];
+    PartTex p;
+    slot[0] = &p.back, slot[1] = &p.front, slot[2] = &p.left, slot[3] = &p.right, slot[4] = &p.top, slot[5] = &p.bottom;  // add_box's order
+    for (int f = 0; f < 6; ++f) {
+        const CapeSource src = cape_source(f);
+        const Region r = cut(img, src.rect.x, src.rect.y, src.rect.w, src.rect.h);
+        *slot[f] = src.turned ? turn_half(r) : r;
+    }
+    return p;
 }
 
 PartTex mirror_part(const PartTex& p) {
@@ -240,7 +286,12 @@ void add_box(OwnedDesc& o, const PartTex& tex, const float pos[3], const float s
     o.meshes.push_back(m);
 }
 
-OwnedDesc* assemble(const Skin& skin, const float pose[12], int model = MCRT_SKIN_CLASSIC) {  // mesh_builder.cpp:145-202
+// `cape`: the cape's textures or NULL.  The cape is the LAST mesh: the box {10, 16, 1} at {0, 16, -2.5} — x -5 .. 5, y 8 .. 24,
+// z -3 .. -2, on the body's back — hinged at {0, 24, -2} by cape_angle degrees about x (positive: the hem away from the legs).
+// It does not follow the body part's own rotation: a mesh has one pivot.  A fully transparent cape is dropped like an outer
+// part unless `keep_clear_cape` (a repaintable handle's full table).
+OwnedDesc* assemble(const Skin& skin, const float pose[12], int model = MCRT_SKIN_CLASSIC, const PartTex* cape = nullptr, float cape_angle = 0.0f,
+                    bool keep_clear_cape = false) {  // mesh_builder.cpp:145-202
     auto* o = new OwnedDesc();
     static const float position[6][3] = {{0, 28, 0}, {0, 18, 0}, {-6, 18, 0}, {6, 18, 0}, {-2, 6, 0}, {2, 6, 0}};
     static const float size[6][3] = {{8, 8, 8}, {8, 12, 4}, {4, 12, 4}, {4, 12, 4}, {4, 12, 4}, {4, 12, 4}};
@@ -259,6 +310,10 @@ OwnedDesc* assemble(const Skin& skin, const float pose[12], int model = MCRT_SKI
         add_box(*o, skin.inner[p], at, sz, 0.0f, posed, pv, rx, rz);
         if (!fully_transparent(skin.outer[p]))
             add_box(*o, skin.outer[p], at, sz, 0.5f, posed, pv, rx, rz);
+    }
+    if (cape && (keep_clear_cape || !fully_transparent(*cape))) {
+        static const float cape_position[3] = {0, 16, -2.5f}, cape_size[3] = {10, 16, 1}, cape_pivot[3] = {0, 24, -2};
+        add_box(*o, *cape, cape_position, cape_size, 0.0f, std::fabs(cape_angle) > 0.01f, cape_pivot, cape_angle, 0.0f);
     }
     mcrt_scene_desc& d = o->desc;
     std::memset(&d, 0, sizeof d);
@@ -327,16 +382,30 @@ bool model_ok(int skin_height, int model) {  // slim exists for 64x64 skins only
     return model == MCRT_SKIN_CLASSIC || (model == MCRT_SKIN_SLIM && skin_height == 64);
 }
 const char* const kBadModel = "model must be MCRT_SKIN_CLASSIC, or MCRT_SKIN_SLIM with a 64x64 skin";
+const char* const kBadCapeAngle = "cape_angle must be within 0 .. 90 degrees";
+bool cape_angle_ok(float a) { return a >= 0.0f && a <= 90.0f; }  // (false for NaN)
+
+const Skin& white_skin(int skin_height, int model) {  // parsed once per kind and process
+    static const Skin white[3] = {parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64),
+                                  parse_skin(std::vector<uint8_t>(64 * 32 * 4, 255).data(), 64, 32),
+                                  parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64, MCRT_SKIN_SLIM)};
+    return white[skin_height == 32 ? 1 : (model == MCRT_SKIN_SLIM ? 2 : 0)];
+}
 }  // namespace
 
 // The figure mcrt_build_skin_scene_model builds from an all-(255,255,255,255) skin of the kind (64 / 32, classic / slim) — every
 // part present — at `pose`: what a view of a repaintable handle is flattened from (api.cpp).  The white skin is parsed once
 // per kind and process.
 extern "C" __attribute__((visibility("hidden"))) mcrt_scene_desc* mcrt_detail_white_figure(int skin_height, int model, const float pose[12]) {
-    static const Skin white[3] = {parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64),
-                                  parse_skin(std::vector<uint8_t>(64 * 32 * 4, 255).data(), 64, 32),
-                                  parse_skin(std::vector<uint8_t>(64 * 64 * 4, 255).data(), 64, 64, MCRT_SKIN_SLIM)};
-    return &assemble(white[skin_height == 32 ? 1 : (model == MCRT_SKIN_SLIM ? 2 : 0)], pose, model)->desc;
+    return &assemble(white_skin(skin_height, model), pose, model)->desc;
+}
+// The caped form (arguments checked by the callers): the white figure with the cape mesh behind it, always present — what a
+// caped handle's view is flattened from, and, with `cape_alpha` 0, its first blob: a white skin and a transparent cape.
+extern "C" __attribute__((visibility("hidden"))) mcrt_scene_desc* mcrt_detail_white_figure_cape(int skin_height, int model, const float pose[12], float cape_angle,
+                                                                                                int cape_alpha) {
+    static const PartTex cape[2] = {cape_part(std::vector<uint8_t>(kCapeWidth * kCapeHeight * 4, 0).data()),
+                                    cape_part(std::vector<uint8_t>(kCapeWidth * kCapeHeight * 4, 255).data())};
+    return &assemble(white_skin(skin_height, model), pose, model, &cape[cape_alpha ? 1 : 0], cape_angle, true)->desc;
 }
 
 extern "C" {
@@ -351,6 +420,48 @@ int mcrt_build_skin_scene_model(const uint8_t* rgba8, int w, int h, int model, c
     if (!rgba8 || !out || w != 64 || (h != 64 && h != 32) || !model_ok(h, model)) return MCRT_ERR_INVALID;
     *out = &assemble(parse_skin(rgba8, w, h, model), pose, model)->desc;
     return MCRT_OK;
+}
+
+int mcrt_build_skin_scene_cape(const uint8_t* rgba8, int w, int h, int model, const float pose[12], const uint8_t* cape_rgba8, float cape_angle,
+                               mcrt_scene_desc** out) {
+    if (!rgba8 || !out) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
+    if (w != 64 || (h != 64 && h != 32)) return mcrt_detail_fail(MCRT_ERR_INVALID, "a skin image is 64x64 or 64x32");
+    if (!model_ok(h, model)) return mcrt_detail_fail(MCRT_ERR_INVALID, kBadModel);
+    if (!cape_rgba8) {  // the capeless call, byte for byte; the angle is not read
+        *out = &assemble(parse_skin(rgba8, w, h, model), pose, model)->desc;
+        return MCRT_OK;
+    }
+    if (!cape_angle_ok(cape_angle)) return mcrt_detail_fail(MCRT_ERR_INVALID, kBadCapeAngle);
+    const PartTex cape = cape_part(cape_rgba8);
+    *out = &assemble(parse_skin(rgba8, w, h, model), pose, model, &cape, cape_angle)->desc;
+    return MCRT_OK;
+}
+
+int mcrt_cape_texel(int face_slot, int tx, int ty, int* cape_x, int* cape_y) {
+    if (!cape_x || !cape_y) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
+    if (face_slot < 0 || face_slot > 5) return mcrt_detail_fail(MCRT_ERR_INVALID, "face_slot must be 0..5");
+    const CapeSource src = cape_source(face_slot);
+    const Rect& r = src.rect;
+    if (tx < 0 || tx >= r.w || ty < 0 || ty >= r.h) return mcrt_detail_fail(MCRT_ERR_INVALID, "texel outside the face's region");
+    *cape_x = r.x + (src.turned ? r.w - 1 - tx : tx);
+    *cape_y = r.y + (src.turned ? r.h - 1 - ty : ty);
+    return MCRT_OK;
+}
+
+// The cape mesh's texels in pool order — six faces in slot order, row-major — as cape pixel indices y * 64 + x.  Returns the
+// count, 372; writes `capacity` entries at most.
+int mcrt_cape_pool_map(int32_t* out, int capacity) {
+    if (!out) return mcrt_detail_fail(MCRT_ERR_INVALID, "NULL argument");
+    int n = 0;
+    for (int face = 0; face < 6; ++face) {
+        const CapeSource src = cape_source(face);
+        const Rect& r = src.rect;
+        for (int ty = 0; ty < r.h; ++ty)
+            for (int tx = 0; tx < r.w; ++tx, ++n)
+                if (n < capacity) out[n] = (r.y + (src.turned ? r.h - 1 - ty : ty)) * kCapeWidth + r.x + (src.turned ? r.w - 1 - tx : tx);
+    }
+    static_assert(2 * 10 * 16 + 2 * 1 * 16 + 2 * 10 * 1 == kCapeTexels, "the cape box's six faces");
+    return n;
 }
 
 int mcrt_skin_model_of(const uint8_t* rgba8, int w, int h) {

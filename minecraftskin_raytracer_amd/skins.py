@@ -29,6 +29,21 @@ def slim_unused_mask() -> np.ndarray:
     return mask
 
 
+def synthetic_cape(seed: int = 54321) -> np.ndarray:
+    """A deterministic cape image, (32, 64, 4) uint8: r, g, b from the skins' LCG, one step each, row-major over the whole
+    image, alpha 255 everywhere — so every one of the 372 texels of the cape's unwrap is opaque and all differ."""
+    img = np.zeros((32, 64, 4), dtype=np.uint8)
+    s = seed & 0xFFFFFFFF
+    for y in range(32):
+        for x in range(64):
+            rgb = []
+            for _ in range(3):
+                s = (s * 1664525 + 1013904223) & 0xFFFFFFFF
+                rgb.append(s >> 24)
+            img[y, x] = (rgb[0], rgb[1], rgb[2], 255)
+    return img
+
+
 def synthetic_skin(kind: str = "S64", seed: int = 12345) -> np.ndarray:
     """Returns (H, 64, 4) uint8."""
     if kind == "S64S":
