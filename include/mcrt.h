@@ -710,6 +710,71 @@ int mcrt_bake_texel_table(const mcrt_scene_desc* scene, int32_t (*out)[4], int c
 /* the number of pool texels of a resident scene: the texels per plane of its bake */
 int mcrt_scene_texels(mcrt_scene* scene, int* n_texels);
 
+/* ---- light layers and bake under extra lights: one visibility and one direct plane PER LIGHT, and their sum -------------------
+ * What a compositor or a skin editor needs to dim, recolour or switch off one light of a key / fill / rim set without a new
+ * render.  mcrt_render_light_device, mcrt_bake_light_device & co stay as they are and go on refusing a handle with extra lights;
+ * these entries take such a handle.  The handle's lights are read BY VALUE at enqueue, as a render reads them: a pass enqueued
+ * before mcrt_scene_set_extra_lights keeps the lights it was enqueued with.
+ * Light 0 is the scene's own light, lights 1 .. K the handle's extra lights ("extra lights"), M = MCRT_MAX_LIGHTS = 4 plane slots.
+ * LIGHT LAYERS.  At the primary hit h of the pixel-centre ray of "light layers", origin o, view = normalize(o - h.point), with
+ * the ONE seed of "light layers" (depth 0, one per hit, shared by all lights), S = shadow_samples:
+ *   vis_k       per light k = 0 .. K.  soft_shadows && shadow_samples > 1: computeSoftShadow(h.point, h.normal, light_k, scene, S,
+ *               seed) — every light sees the hit's same 2 * S draws, and light k's own radius decides between its disk and the
+ *               single ray with the raw normal (a radius below 1e-4); otherwise
+ *               isInShadow(h.point, normalize(h.normal), light_k.position) ? 0 : 1
+ *   D_0         shade(h, view, light_0, scene, ShadingParams{}, vis_0)
+ *   D_k, k >= 1 shade(h, view, light_k, scene, ShadingParams{kd, ks, ambient = 0, shininess}, vis_k); each D is clamped by shade
+ *               itself, and its alpha is what shade returns: the texel's
+ *   combined    rgb = clamp(((D_0.rgb + D_1.rgb) + D_2.rgb) + D_3.rgb, 0, 1), added left to right over the lights the handle
+ *               has; a = D_0.a
+ *   occlusion   as in "light layers": it does not read a light
+ * Planes: visibility[k] = vis_k (1 float), direct[k] = D_k (4 floats), occlusion (1 float), combined (4 floats).
+ * At a miss every vis_k is 1.0f, every D_k and combined (0, 0, 0, 0), occlusion 1.0f.  A plane asked for a light the handle lacks
+ * (k > K) holds the miss constants everywhere — an absent light is a black light; nothing is refused for it, so a batch of
+ * handles with different K is one call.
+ * RECOMPOSITION (part of the contract).  For every pixel with a hit, the beauty frame of the handle with the same lights at
+ * samples_per_pixel = 1, no depth of field, max_bounces = 0 and the same shadow settings
+ *   - with ao_enabled = 0 EQUALS combined, bit for bit;
+ *   - with ao_enabled = 1 equals k = 1.0f - ao_intensity * (1.0f - occlusion); rgb = clamp(combined.rgb * k, 0, 1); a = combined.a.
+ * With K = 0, visibility[0], direct[0] and occlusion are the bytes of mcrt_render_light_device's planes, and combined is the
+ * formula on D_0 alone.
+ * LIGHT BAKE.  The same per sub-sample s of "light bake", with its P, N and view = N: vis_k,s, D_k,s and
+ * comb_s = clamp(sum over k of D_k,s) with alpha D_0,s.a.  Every plane is the "mean" of its sub-sample values; combined is the
+ * mean of comb_s, NOT the clamp of the means.  Dead texels: 1.0f / (0, 0, 0, 0); a light the handle lacks: the same.  position and
+ * normal are unchanged.
+ * Each family keeps the rules of its single-light entries: whole frames, asynchronous on `stream` and not into a graph being
+ * recorded, no workspace, no counters and none of the handle's events, one launch per kernel and 4096 frames, a handle may be
+ * listed more than once and the handles of a batch may carry different lights, the gaps between frames are not written — and the
+ * same MCRT_ERR_INVALID list before any device work, the planes untouched, with "all planes NULL" meaning every pointer of the
+ * struct.  The one-shot forms add the checks of mcrt_scene_set_extra_lights on `lights` / `n_lights`, right behind the NULL
+ * checks.  Zero-size frames, n_frames = 0 and scenes without texels: MCRT_OK, nothing written. */
+#define MCRT_MAX_LIGHTS (1 + MCRT_MAX_EXTRA_LIGHTS)
+typedef struct mcrt_light_planes_multi {
+    float* visibility[MCRT_MAX_LIGHTS]; /* 1 float / pixel each; any may be NULL, not all of the struct */
+    float* direct[MCRT_MAX_LIGHTS];     /* 4 floats / pixel each */
+    float* occlusion;
+    float* combined;                    /* 4 floats / pixel */
+} mcrt_light_planes_multi;
+int mcrt_render_light_multi_device(mcrt_scene* scene, const mcrt_config* cfg, const mcrt_light_planes_multi* d_out, void* stream);
+int mcrt_render_light_multi_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_light_planes_multi* d_out,
+                                         size_t frame_stride_pixels, void* stream);
+/* one-shot host form: host pointers; `lights` are the extra lights 1 .. n_lights of the pooled handle */
+int mcrt_render_light_multi(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights,
+                            const mcrt_light_planes_multi* out, int device);
+typedef struct mcrt_bake_planes_multi {
+    float* position; /* any may be NULL, not all of the struct */
+    float* normal;
+    float* visibility[MCRT_MAX_LIGHTS];
+    float* occlusion;
+    float* direct[MCRT_MAX_LIGHTS];
+    float* combined;
+} mcrt_bake_planes_multi;
+int mcrt_bake_light_multi_device(mcrt_scene* scene, const mcrt_config* cfg, int grid, const mcrt_bake_planes_multi* d_out, void* stream);
+int mcrt_bake_light_multi_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, int grid,
+                                       const mcrt_bake_planes_multi* d_out, size_t texel_stride, void* stream);
+int mcrt_bake_light_multi(const mcrt_scene_desc* scene, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights, int grid,
+                          const mcrt_bake_planes_multi* out, int device);
+
 /* ---- skins on resident scenes: a new skin for a scene that is already on the device -----------------------------------------
  * Everything in a flattened skin scene but its texels is a function of pose, camera and light alone.  A REPAINTABLE handle takes
  * a new skin from a 64 x skin_height RGBA8 image in device memory with one small kernel — no scene build, no flattening, no upload

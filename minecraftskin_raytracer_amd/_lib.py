@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = [
     "mcrt_build_skin_scene_cape", "mcrt_cape_texel", "mcrt_cape_pool_map", "mcrt_scene_create_skin_cape",
     "mcrt_scene_set_cape", "mcrt_scene_set_cape_device", "mcrt_scene_set_capes_batch_device",
     "mcrt_skin_view_table_cape", "mcrt_scene_set_view_cape", "mcrt_scene_set_view_cape_device", "mcrt_scene_set_views_cape_batch_device",
+    "mcrt_render_light_multi_device", "mcrt_render_light_multi_batch_device", "mcrt_render_light_multi",
+    "mcrt_bake_light_multi_device", "mcrt_bake_light_multi_batch_device", "mcrt_bake_light_multi",
 ]
 
 
@@ -74,6 +76,8 @@ def load():
     reflection_p = C.POINTER(abi.McrtReflection)
     light_p = C.POINTER(abi.McrtLightPlanes)
     bake_p = C.POINTER(abi.McrtBakePlanes)
+    light_multi_p = C.POINTER(abi.McrtLightPlanesMulti)
+    bake_multi_p = C.POINTER(abi.McrtBakePlanesMulti)
     shot_p = C.POINTER(abi.McrtShot)
     shot_ex_p = C.POINTER(abi.McrtShotEx)
     lights_p = C.POINTER(abi.McrtLightSource)
@@ -123,6 +127,12 @@ def load():
         "mcrt_bake_light_device": (C.c_int, [vp, cfg_p, C.c_int, bake_p, vp]),
         "mcrt_bake_light_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, C.c_int, bake_p, C.c_size_t, vp]),
         "mcrt_bake_light": (C.c_int, [desc_p, cfg_p, C.c_int, bake_p, C.c_int]),
+        "mcrt_render_light_multi_device": (C.c_int, [vp, cfg_p, light_multi_p, vp]),
+        "mcrt_render_light_multi_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, light_multi_p, C.c_size_t, vp]),
+        "mcrt_render_light_multi": (C.c_int, [desc_p, cfg_p, lights_p, C.c_int, light_multi_p, C.c_int]),
+        "mcrt_bake_light_multi_device": (C.c_int, [vp, cfg_p, C.c_int, bake_multi_p, vp]),
+        "mcrt_bake_light_multi_batch_device": (C.c_int, [C.POINTER(vp), C.c_int, cfg_p, C.c_int, bake_multi_p, C.c_size_t, vp]),
+        "mcrt_bake_light_multi": (C.c_int, [desc_p, cfg_p, lights_p, C.c_int, C.c_int, bake_multi_p, C.c_int]),
         "mcrt_bake_texel_table": (C.c_int, [desc_p, abi.c_int32_p, C.c_int]),
         "mcrt_scene_texels": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "mcrt_scene_pick": (C.c_int, [vp, cfg_p, abi.c_int32_p, C.c_int, vp]),

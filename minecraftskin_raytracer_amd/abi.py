@@ -405,6 +405,58 @@ def light_array(lights):
     return (McrtLightSource * len(lights))(*[l.to_c() for l in lights]), len(lights)
 
 
+MAX_LIGHTS = 1 + MAX_EXTRA_LIGHTS  # MCRT_MAX_LIGHTS: light 0 is the scene's own
+
+
+class McrtLightPlanesMulti(C.Structure):
+    """mcrt_light_planes_multi: a visibility and a direct plane per light, occlusion and the clamped sum; NULL = not wanted."""
+
+    _fields_ = [("visibility", C.c_void_p * MAX_LIGHTS), ("direct", C.c_void_p * MAX_LIGHTS), ("occlusion", C.c_void_p), ("combined", C.c_void_p)]
+
+
+class McrtBakePlanesMulti(C.Structure):
+    """mcrt_bake_planes_multi: mcrt_bake_planes with a visibility and a direct plane per light, and the mean of the clamped sums."""
+
+    _fields_ = [("position", C.c_void_p), ("normal", C.c_void_p), ("visibility", C.c_void_p * MAX_LIGHTS), ("occlusion", C.c_void_p),
+                ("direct", C.c_void_p * MAX_LIGHTS), ("combined", C.c_void_p)]
+
+
+assert C.sizeof(McrtLightPlanesMulti) == 8 * (2 * MAX_LIGHTS + 2) and C.sizeof(McrtBakePlanesMulti) == 8 * (2 * MAX_LIGHTS + 4)
+
+# The planes of the passes under extra lights (include/mcrt.h, "light layers and bake under extra lights").  A structure member
+# that holds a pointer per light is ONE name here: ``visibility`` is (M, ...) and ``direct`` (M, ..., 4) in the wrappers' results.
+# They are rows beside FAMILIES, not in it: a PlaneFamily describes a structure of one pointer per name.
+LIGHT_MULTI_FORMATS = {"visibility": (np.float32, 1), "direct": (np.float32, 4), "occlusion": (np.float32, 1), "combined": (np.float32, 4)}
+BAKE_MULTI_FORMATS = {"position": (np.float32, 4), "normal": (np.float32, 4), "visibility": (np.float32, 1), "occlusion": (np.float32, 1),
+                      "direct": (np.float32, 4), "combined": (np.float32, 4)}
+LIGHT_MULTI_NAMES, BAKE_MULTI_NAMES = tuple(LIGHT_MULTI_FORMATS), tuple(BAKE_MULTI_FORMATS)
+PER_LIGHT_NAMES = ("visibility", "direct")  # the members with a plane per light
+MULTI_MISS = {"visibility": 1, "occlusion": 1}  # what a plane holds at a miss, for a dead texel and for a light the handle lacks; else 0
+
+
+def multi_names(names: tuple, planes) -> tuple:
+    """The wanted planes of LIGHT_MULTI_NAMES / BAKE_MULTI_NAMES in canonical order, as ``PlaneFamily.select`` words it."""
+    if isinstance(planes, str):
+        planes = (planes,)
+    chosen = tuple(planes)
+    for n in chosen:
+        if not isinstance(n, str) or n not in names:
+            raise ValueError(f"planes must be taken from {names}, not {n!r}")
+    if not chosen:
+        raise ValueError("no plane selected")
+    return tuple(n for n in names if n in chosen)
+
+
+def light_indices(lights_k) -> tuple:
+    """The light indices k a per-light plane is asked for: None = all MAX_LIGHTS, else a sequence of 0 .. MAX_LIGHTS - 1, ascending."""
+    if lights_k is None:
+        return tuple(range(MAX_LIGHTS))
+    ks = tuple(sorted({int(k) for k in lights_k}))
+    if not ks or ks[0] < 0 or ks[-1] >= MAX_LIGHTS:
+        raise ValueError(f"light indices must be taken from 0 .. {MAX_LIGHTS - 1}")
+    return ks
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
 
 SURFACE_DTYPE = np.dtype(

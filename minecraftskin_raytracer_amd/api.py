@@ -474,6 +474,47 @@ class TileRenderer:
         return out
 
     @staticmethod
+    def renderLightMulti(scene, config: Config, lights=(), planes=abi.LIGHT_MULTI_NAMES, light_indices=None, device: int = 0) -> dict:
+        """``renderLight`` with planes PER LIGHT, under 0 to 3 extra ``lights`` (``abi.Light``) beside the scene's own
+        (mcrt_render_light_multi): what a compositor needs to dim, recolour or switch off one light.  A dict of the wanted planes:
+        ``visibility`` (M, H, W) and ``direct`` (M, H, W, 4), row k for light k — 0 the scene's own, 1.. the extra lights in
+        order; a light that is not there is a black light: 1 / zeros — restricted to ``light_indices`` where given (then M is
+        their number, ascending); ``occlusion`` (H, W); ``combined`` (H, W, 4) = ``clip(direct[0] + direct[1] + ..., 0, 1)`` with
+        ``direct[0]``'s alpha, which is the beauty frame under the same lights at 1 spp, 0 bounces on every hit pixel (with AO:
+        ``clip(combined.rgb * (1 - aoIntensity * (1 - occlusion)), 0, 1)``), bit for bit."""
+        names = abi.multi_names(abi.LIGHT_MULTI_NAMES, planes)
+        ks = abi.light_indices(light_indices)
+        extra, n_extra = abi.light_array(lights)
+        h, w = max(int(config.height), 0), max(int(config.width), 0)
+        out = _multi_empty(abi.LIGHT_MULTI_FORMATS, names, len(ks), (h, w))
+        if h == 0 or w == 0 or config.tileSize <= 0:
+            return out
+        frame = _multi_host_planes(abi.McrtLightPlanesMulti, out, ks)
+        c = config.to_c()
+        check(load().mcrt_render_light_multi(_as_desc(scene).ptr, C.byref(c), extra, n_extra, C.byref(frame), int(device)))
+        return out
+
+    @staticmethod
+    def bakeLightMulti(scene, config: Config, grid: int = 1, lights=(), planes=abi.BAKE_MULTI_NAMES, light_indices=None, device: int = 0) -> dict:
+        """``bakeLight`` with planes PER LIGHT, under 0 to 3 extra ``lights`` (mcrt_bake_light_multi): ``visibility`` (M, n) and
+        ``direct`` (M, n, 4) as ``renderLightMulti`` lays them out, ``position``, ``normal`` and ``occlusion`` as ``bakeLight``
+        gives them, and ``combined`` (n, 4): the mean over the sub-samples of the clamped sum of the lights' terms (not the clamp
+        of the means)."""
+        names = abi.multi_names(abi.BAKE_MULTI_NAMES, planes)
+        ks = abi.light_indices(light_indices)
+        extra, n_extra = abi.light_array(lights)
+        grid = _bake_grid(grid)
+        d = _as_desc(scene)
+        n = len(texel_table(d))
+        out = _multi_empty(abi.BAKE_MULTI_FORMATS, names, len(ks), (n,))
+        if n == 0:
+            return out
+        frame = _multi_host_planes(abi.McrtBakePlanesMulti, out, ks)
+        c = config.to_c()
+        check(load().mcrt_bake_light_multi(d.ptr, C.byref(c), extra, n_extra, grid, C.byref(frame), int(device)))
+        return out
+
+    @staticmethod
     def lastBatchInfo() -> dict:
         """How the last batch call on this thread ran (mcrt_last_batch_info): ``batched_frames`` taken by the batched
         kernels and ``launch_sequences`` enqueued (1 when the whole batch went through them at once)."""
@@ -1100,6 +1141,27 @@ class DeviceScene:
         stream.  Ordering against a repaint of the handle is the caller's job."""
         self._pass_device(abi.BAKE, config, _device_planes(abi.BAKE, position_ptr, normal_ptr, visibility_ptr, occlusion_ptr, direct_ptr), stream, _bake_grid(grid))
 
+    def render_light_multi_device(self, config: Config, visibility_ptrs: Sequence[int] = (), direct_ptrs: Sequence[int] = (), occlusion_ptr: int = 0,
+                                  combined_ptr: int = 0, stream: int = 0) -> None:
+        """The light planes PER LIGHT of the frame into device memory (mcrt_render_light_multi_device), for a handle with or without
+        extra lights: ``visibility_ptrs[k]`` (4 bytes per pixel) and ``direct_ptrs[k]`` (16) take light k's plane — light 0 is the
+        scene's own, lights 1.. the handle's extra lights, read at this call; a light the handle lacks gives the miss constants —,
+        ``occlusion_ptr`` the occlusion (4) and ``combined_ptr`` the clamped sum of the direct planes (16), which is the beauty
+        frame at 1 spp and 0 bounces on every hit pixel.  Any pointer may be 0, not all.  Asynchronous on ``stream``."""
+        planes = _multi_device_planes(abi.McrtLightPlanesMulti, visibility_ptrs, direct_ptrs, occlusion=occlusion_ptr, combined=combined_ptr)
+        c = config.to_c()
+        check(load().mcrt_render_light_multi_device(self._h, C.byref(c), C.byref(planes), C.c_void_p(stream)))
+
+    def bake_light_multi_device(self, config: Config, grid: int = 1, position_ptr: int = 0, normal_ptr: int = 0, visibility_ptrs: Sequence[int] = (),
+                                occlusion_ptr: int = 0, direct_ptrs: Sequence[int] = (), combined_ptr: int = 0, stream: int = 0) -> None:
+        """The planes of a light bake PER LIGHT into device memory (mcrt_bake_light_multi_device): ``bake_light_device`` with one
+        visibility and one direct plane per light, as ``render_light_multi_device`` takes them, and ``combined_ptr``: the mean of
+        the sub-samples' clamped sums (16 bytes per texel)."""
+        planes = _multi_device_planes(abi.McrtBakePlanesMulti, visibility_ptrs, direct_ptrs, position=position_ptr, normal=normal_ptr,
+                                      occlusion=occlusion_ptr, combined=combined_ptr)
+        c = config.to_c()
+        check(load().mcrt_bake_light_multi_device(self._h, C.byref(c), _bake_grid(grid), C.byref(planes), C.c_void_p(stream)))
+
     def pick(self, config: Config, xy) -> np.ndarray:
         """What is under the pixels ``xy`` ((n, 2) integers, x then y, inside the frame): a structured array of
         ``abi.SURFACE_DTYPE`` — mesh, face, tx, ty, t, point, normal, albedo — equal to the layers at those pixels
@@ -1203,6 +1265,31 @@ def _device_planes(family: abi.PlaneFamily, *ptrs: int):
     if not any(ptrs):
         raise ValueError("give at least one of " + ", ".join(f"{k}_ptr" for k in family.names))
     return family.struct(*[p or None for p in ptrs])
+
+
+def _multi_empty(formats: dict, names, n_lights: int, shape: tuple) -> dict:
+    """The host planes of a pass under extra lights, holding the miss values: a per-light member with a leading ``n_lights``."""
+    out = {}
+    for name in names:
+        dtype, comps = formats[name]
+        lead = (n_lights,) if name in abi.PER_LIGHT_NAMES else ()
+        a = np.zeros(lead + shape + ((comps,) if comps > 1 else ()), dtype)
+        if name in abi.MULTI_MISS:
+            a[...] = abi.MULTI_MISS[name]
+        out[name] = a
+    return out
+
+
+def _multi_host_planes(struct, out: dict, ks):
+    """``struct`` with the host addresses of ``out``: row i of a per-light member is light ks[i]'s plane."""
+    frame = struct()
+    for name, a in out.items():
+        if name in abi.PER_LIGHT_NAMES:
+            for i, k in enumerate(ks):
+                getattr(frame, name)[k] = a[i].ctypes.data
+        else:
+            setattr(frame, name, a.ctypes.data)
+    return frame
 
 
 def _finite_ground(ground) -> float:
@@ -1313,6 +1400,57 @@ def bake_light_batch_device(device_scenes: Sequence["DeviceScene"], config: Conf
         raise ValueError("texel_stride must be >= 0")
     c = config.to_c()
     check(load().mcrt_bake_light_batch_device(_handle_array(handles), len(handles), C.byref(c), g, C.byref(planes), int(texel_stride), C.c_void_p(stream)))
+
+
+def _multi_device_planes(struct, visibility_ptrs, direct_ptrs, **single):
+    """The structure of device pointers of a pass under extra lights: up to ``abi.MAX_LIGHTS`` pointers per per-light member (light
+    k's plane at index k, 0 = not wanted), one per other member; all 0 raises."""
+    planes = struct()
+    for name, ptrs in (("visibility", visibility_ptrs), ("direct", direct_ptrs)):
+        ptrs = tuple(int(p or 0) for p in ptrs)
+        if len(ptrs) > abi.MAX_LIGHTS:
+            raise ValueError(f"{name}_ptrs takes at most {abi.MAX_LIGHTS} pointers, one per light")
+        for k, p in enumerate(ptrs):
+            getattr(planes, name)[k] = p or None
+    for name, p in single.items():
+        setattr(planes, name, int(p or 0) or None)
+    if not any(visibility_ptrs) and not any(direct_ptrs) and not any(single.values()):
+        raise ValueError("give at least one of visibility_ptrs, direct_ptrs, " + ", ".join(f"{k}_ptr" for k in single))
+    return planes
+
+
+def render_light_multi_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, visibility_ptrs: Sequence[int] = (),
+                                    direct_ptrs: Sequence[int] = (), occlusion_ptr: int = 0, combined_ptr: int = 0,
+                                    frame_stride_pixels: Optional[int] = None, stream: int = 0) -> None:
+    """The per-light light planes of N resident scenes of one config in one launch per kernel
+    (mcrt_render_light_multi_batch_device): ``visibility_ptrs[k]`` / ``direct_ptrs[k]`` take light k's plane (0: the scene's own
+    light, 1..: the handle's extra lights; a light a handle lacks: the miss constants), ``combined_ptr`` the clamped sum.  Frame i
+    of each plane starts ``i * frame_stride_pixels`` pixels on.  The handles may carry different lights and may be listed more
+    than once.  Asynchronous on ``stream``."""
+    handles = _handles(device_scenes)
+    planes = _multi_device_planes(abi.McrtLightPlanesMulti, visibility_ptrs, direct_ptrs, occlusion=occlusion_ptr, combined=combined_ptr)
+    stride = _frame_stride(config, frame_stride_pixels)
+    c = config.to_c()
+    check(load().mcrt_render_light_multi_batch_device(_handle_array(handles), len(handles), C.byref(c), C.byref(planes), stride, C.c_void_p(stream)))
+
+
+def bake_light_multi_batch_device(device_scenes: Sequence["DeviceScene"], config: Config, grid: int = 1, position_ptr: int = 0, normal_ptr: int = 0,
+                                  visibility_ptrs: Sequence[int] = (), occlusion_ptr: int = 0, direct_ptrs: Sequence[int] = (), combined_ptr: int = 0,
+                                  texel_stride: Optional[int] = None, stream: int = 0) -> None:
+    """The per-light light bakes of N resident scenes in one launch per kernel (mcrt_bake_light_multi_batch_device): the planes of
+    ``bake_light_batch_device`` with one visibility and one direct plane per light and ``combined_ptr``, the mean of the
+    sub-samples' clamped sums.  Frame i starts ``i * texel_stride`` texels on (default: the largest ``texels`` of the scenes)."""
+    handles = _handles(device_scenes)
+    planes = _multi_device_planes(abi.McrtBakePlanesMulti, visibility_ptrs, direct_ptrs, position=position_ptr, normal=normal_ptr,
+                                  occlusion=occlusion_ptr, combined=combined_ptr)
+    g = _bake_grid(grid)
+    if texel_stride is None:
+        texel_stride = max([s.texels for s in device_scenes], default=0)
+    if int(texel_stride) < 0:
+        raise ValueError("texel_stride must be >= 0")
+    c = config.to_c()
+    check(load().mcrt_bake_light_multi_batch_device(_handle_array(handles), len(handles), C.byref(c), g, C.byref(planes), int(texel_stride),
+                                                    C.c_void_p(stream)))
 
 
 def set_skins_batch_device(device_scenes: Sequence["DeviceScene"], ptr: int, skin_stride_bytes: Optional[int] = None, stream: int = 0) -> None:

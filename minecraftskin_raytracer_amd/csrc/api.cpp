@@ -783,6 +783,7 @@ struct OneShotScenes {
             const int rc = create_scene_from_blob(blobs[static_cast<size_t>(i)], device, &h[static_cast<size_t>(i)]);
             if (rc != MCRT_OK) return rc;
             h[static_cast<size_t>(i)]->background = background;
+            if (t_one_shot_lights) h[static_cast<size_t>(i)]->extra = *t_one_shot_lights;  // (the multi-light pass forms: OneShotLights)
         }
         return one_shot_streams(h[0]) == MCRT_OK ? MCRT_OK : MCRT_ERR_HIP;
     }
@@ -1260,6 +1261,51 @@ int mcrt_bake_light(const mcrt_scene_desc* desc, const mcrt_config* cfg, int gri
                             {out->visibility, 4, &d.visibility}, {out->occlusion, 4, &d.occlusion}};
     return one_shot_pass(&desc, 1, device, planes, kPerTexel, "bake planes", "light bake",
                          [&](mcrt_scene* const* h, size_t n, hipStream_t stream) { return bake_light_batch_device(h, 1, cfg, grid, &d, n, stream); });
+}
+
+// ---- light layers and bake under extra lights: the one-shot host forms (render_enqueue.cpp: render_light_multi_batch_device,
+// bake_light_multi_batch_device).  The lights ride to the pooled shell like mcrt_render_lights' (OneShotLights).
+int mcrt_render_light_multi(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights,
+                            const mcrt_light_planes_multi* out, int device) {
+    if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (const int rc = check_extra_lights(lights, n_lights); rc != MCRT_OK) return rc;
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all planes are NULL");
+    {
+        const mcrt_light_planes occ = occlusion_alone(out);
+        if (const int rc = check_light_config(cfg, &occ); rc != MCRT_OK) return rc;
+    }
+    if (!valid_frame(cfg)) return MCRT_OK;  // zero tiles: nothing is written
+    const mcrt::LightSet set = light_set_of(lights, n_lights);
+    const OneShotLights carried(&set);
+    mcrt_light_planes_multi d{};
+    const Plane planes[] = {{out->direct[0], 16, &d.direct[0]}, {out->direct[1], 16, &d.direct[1]}, {out->direct[2], 16, &d.direct[2]},
+                            {out->direct[3], 16, &d.direct[3]}, {out->combined, 16, &d.combined},
+                            {out->visibility[0], 4, &d.visibility[0]}, {out->visibility[1], 4, &d.visibility[1]},
+                            {out->visibility[2], 4, &d.visibility[2]}, {out->visibility[3], 4, &d.visibility[3]}, {out->occlusion, 4, &d.occlusion}};
+    static_assert(MCRT_MAX_LIGHTS == 4, "the plane lists name every light");
+    return one_shot_pass(&desc, 1, device, planes, frame_pixels(cfg), "light planes", "light render",
+                         [&](mcrt_scene* const* h, size_t px, hipStream_t stream) { return render_light_multi_batch_device(h, 1, cfg, &d, px, stream); });
+}
+
+int mcrt_bake_light_multi(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_light_source* lights, int n_lights, int grid,
+                          const mcrt_bake_planes_multi* out, int device) {
+    if (!desc || !cfg || !out) return fail(MCRT_ERR_INVALID, "NULL argument");
+    if (const int rc = check_extra_lights(lights, n_lights); rc != MCRT_OK) return rc;
+    if (no_plane(out)) return fail(MCRT_ERR_INVALID, "all planes are NULL");
+    {
+        const mcrt_bake_planes occ = occlusion_alone(out);
+        if (const int rc = check_bake_config(cfg, grid, &occ); rc != MCRT_OK) return rc;
+    }
+    const mcrt::LightSet set = light_set_of(lights, n_lights);
+    const OneShotLights carried(&set);
+    mcrt_bake_planes_multi d{};
+    const Plane planes[] = {{out->position, 16, &d.position}, {out->normal, 16, &d.normal},
+                            {out->direct[0], 16, &d.direct[0]}, {out->direct[1], 16, &d.direct[1]}, {out->direct[2], 16, &d.direct[2]},
+                            {out->direct[3], 16, &d.direct[3]}, {out->combined, 16, &d.combined},
+                            {out->visibility[0], 4, &d.visibility[0]}, {out->visibility[1], 4, &d.visibility[1]},
+                            {out->visibility[2], 4, &d.visibility[2]}, {out->visibility[3], 4, &d.visibility[3]}, {out->occlusion, 4, &d.occlusion}};
+    return one_shot_pass(&desc, 1, device, planes, kPerTexel, "bake planes", "light bake",
+                         [&](mcrt_scene* const* h, size_t n, hipStream_t stream) { return bake_light_multi_batch_device(h, 1, cfg, grid, &d, n, stream); });
 }
 
 int mcrt_scene_floor(const mcrt_scene_desc* desc, float* y) {

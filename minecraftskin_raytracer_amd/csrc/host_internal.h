@@ -284,6 +284,24 @@ inline int check_bake_config(const mcrt_config* c, int grid, const mcrt_bake_pla
     return MCRT_OK;
 }
 
+// the multi-light planes (mcrt.h, "light layers and bake under extra lights"): nothing asked for at all; whether a plane that
+// reads the lights is asked for (the `shade_lights` / `bake_shade_lights` kernel runs); the occlusion plane as the single-light
+// struct the config checks above read
+inline bool light_plane_asked(const mcrt_light_planes_multi* l) {
+    bool any = l->combined != nullptr;
+    for (int k = 0; k < MCRT_MAX_LIGHTS; ++k) any = any || l->visibility[k] || l->direct[k];
+    return any;
+}
+inline bool light_plane_asked(const mcrt_bake_planes_multi* b) {
+    bool any = b->combined != nullptr;
+    for (int k = 0; k < MCRT_MAX_LIGHTS; ++k) any = any || b->visibility[k] || b->direct[k];
+    return any;
+}
+inline bool no_plane(const mcrt_light_planes_multi* l) { return !light_plane_asked(l) && !l->occlusion; }
+inline bool no_plane(const mcrt_bake_planes_multi* b) { return !light_plane_asked(b) && !b->occlusion && !b->position && !b->normal; }
+inline mcrt_light_planes occlusion_alone(const mcrt_light_planes_multi* l) { return mcrt_light_planes{nullptr, l->occlusion, nullptr}; }
+inline mcrt_bake_planes occlusion_alone(const mcrt_bake_planes_multi* b) { return mcrt_bake_planes{nullptr, nullptr, nullptr, b->occlusion, nullptr}; }
+
 // what every studio-shot entry point refuses of the shot itself (before any device work)
 inline int check_shot(const mcrt_shot* s) {
     if (s->page != MCRT_PAGE_COLOR && s->page != MCRT_PAGE_REFERENCE) return fail(MCRT_ERR_INVALID, "page must be MCRT_PAGE_COLOR or MCRT_PAGE_REFERENCE");
@@ -436,6 +454,11 @@ int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_
                                    size_t stride, hipStream_t stream);
 int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes* d_out, size_t stride, hipStream_t stream);
 int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream);
+// the same two passes with planes per light, for handles with extra lights too (mcrt_render_light_multi_device, mcrt_bake_light_multi_device & co)
+int render_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes_multi* d_out, size_t stride,
+                                    hipStream_t stream);
+int bake_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes_multi* d_out, size_t stride,
+                                  hipStream_t stream);
 // the studio shot's blend on the caller's planes (mcrt_composite_shot_batch_device[_occ]), and render + ground + reflection +
 // ground occlusion + blend on `stream` in order with the planes in the caller's scratch (mcrt_render_shot_batch_device[_occ]);
 // the entries without the floor-occlusion term pass floor_occlusion = 0 and no plane; ex: the _ex entries' additions (bounds:

@@ -454,6 +454,31 @@ void make_bake_shape(const mcrt_config& cfg, int grid, bool bundle_decisions, bo
 size_t bake_shade_lds_bytes(const BakeFrame& f, const BakeShape& shape);  // point records, texel records, masks, counts and sample positions
 size_t bake_occlusion_lds_bytes(const BakeFrame& f);                         // point records, texel records, masks, the traced list and the values
 
+// ---- light layers and bake under extra lights (mcrt_render_light_multi_device, mcrt_bake_light_multi_device & co; include/mcrt.h,
+// "light layers and bake under extra lights"): one visibility and one direct plane per light — light 0 the scene's own, lights
+// 1 .. n_extra the handle's, read BY VALUE at enqueue — and their clamped sum.  Kernels of their own (`shade_lights`,
+// `bake_shade_lights`) over frame records of their own, which carry the lights so that the table of a batch gives every frame
+// its own; ShadeShape / BakeShape, the LDS areas and their size functions are the single-light kernels'.  The occlusion plane
+// does not read a light: it is the `occlusion` / `bake_occlusion` kernels' over a ShadeFrame / BakeFrame with that plane alone.
+// Of the base record `visibility`, `occlusion` and `direct` stay NULL; a bake's `position` and `normal` are the base's.
+struct ShadeLightsFrame : ShadeFrame {
+    LightSet lights;
+    float* vis[kMaxLights];     // 1 float per pixel: light k's shadow factor; a light the handle lacks: the miss constant 1.0f
+    float* dir[kMaxLights];     // 4 floats per pixel: shade() for light k alone (k >= 1: ambient 0); a light the handle lacks: zero
+    float* combined;            // 4 floats per pixel: clamp(D_0 + D_1 + ..), alpha D_0's
+};
+struct BakeLightsFrame : BakeFrame {
+    LightSet lights;
+    float* vis[kMaxLights];     // the means of the sub-samples' values, per texel
+    float* dir[kMaxLights];
+    float* combined;            // the mean of the sub-samples' clamped sums
+};
+inline bool any_light_plane(float* const (&vis)[kMaxLights], float* const (&dir)[kMaxLights], const float* combined) {
+    bool any = combined != nullptr;
+    for (int k = 0; k < kMaxLights; ++k) any = any || vis[k] || dir[k];
+    return any;
+}
+
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): a repaintable handle's blob holds the full mesh table of
 // its skin kind, so texel i of its pool is cut from one fixed pixel of the skin image.  One workgroup per scene rewrites what
 // a skin decides of the blob: the float4 texel pool (u8 / 255.0f through a table the HOST formed), the 2-bit alpha predicates
@@ -609,6 +634,13 @@ hipError_t launch_bake(const BakeFrame& f, const BakeShape& shape, int view, hip
 // frames of a call share their planes) and the largest frame's bake_shade_lds_bytes / bake_occlusion_lds_bytes
 hipError_t launch_bake_batch(const BakeFrame* d_table, int n_frames, const BakeShape& shape, int view, bool shade, size_t shade_dyn, bool occlusion,
                              size_t occlusion_dyn, hipStream_t stream);
+// `shade_lights` / `bake_shade_lights` alone (the occlusion plane of the multi-light entries goes through launch_light /
+// launch_bake over a record of its own); dyn: shade_lds_bytes / bake_shade_lds_bytes of the frame, of the largest frame in a batch.
+// A bake's kernel writes position and normal too (BakeShape::geometry and ::rays are set here).
+hipError_t launch_light_multi(const ShadeLightsFrame& f, const ShadeShape& shape, int view, hipStream_t stream);
+hipError_t launch_light_multi_batch(const ShadeLightsFrame* d_table, int n_frames, const ShadeShape& shape, int view, size_t max_dyn, hipStream_t stream);
+hipError_t launch_bake_multi(const BakeLightsFrame& f, const BakeShape& shape, int view, hipStream_t stream);
+hipError_t launch_bake_multi_batch(const BakeLightsFrame* d_table, int n_frames, const BakeShape& shape, int view, size_t max_dyn, hipStream_t stream);
 hipError_t launch_shot(const ShotFrame& f, const ShotShape& shape, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
 hipError_t launch_shot_batch(const ShotFrame* d_table, int n_frames, const ShotShape& shape, hipStream_t stream);

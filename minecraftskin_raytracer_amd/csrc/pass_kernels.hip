@@ -1544,6 +1544,300 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void bake_occlusion_batch_ker
 }
 
 // ---------------------------------------------------------------------------------------------
+// light layers and bake under extra lights (kernels.h: ShadeLightsFrame, BakeLightsFrame; include/mcrt.h, "light layers and bake
+// under extra lights"): `shade` and `bake_shade` with the shadow resolution and shade() once per light of the frame's LightSet —
+// light 0 the header's, through shade(); light k >= 1 through shade_at(light k, ambient 0) — on the hit's ONE shadow seed:
+// every light's call seeds its engine from the same (point, depth), so all lights see the same draws.  Kernels of their own:
+// shade_body and bake_shade_body stay as they are.  The phases are theirs; what differs:
+//   the loop over the lights k = 0 .. K is uniform per workgroup (K from the frame record) and runs around the COLLECTIVE
+//   resolver (kernel_common.h: resolve_shadow_bundles_at), whose area it reuses from light to light: behind the resolver nothing
+//   of the area is read across lanes, and the LDS a launch takes does not grow with K;
+//   `shade_lights`: light k's visibility and colour return through LDS per light (plane 2 of the record, {r, g, b, vis}: the texel
+//   colour it held is in the hit lane's registers by then, and the next light's write lies behind its resolver's barriers) and
+//   the PIXEL lane adds the colours left to right — the additions the definition names — and clamps the sum;
+//   `bake_shade_lights`: the texel's lane keeps a sum per light and the sum of the sub-samples' clamped totals in registers
+//   (the per-light slots are addressed by unrolled selects, never by index) and hands the means back light by light;
+//   a plane of a light the frame lacks (k > K) takes the miss constants.
+// ---------------------------------------------------------------------------------------------
+// light k of a frame, k uniform: the header's, or entry k - 1 of the record's set (a scalar load, not a select)
+__device__ __forceinline__ LightAt frame_light(const FlatHeader* __restrict__ h, const LightSet& ls, const int k) {
+    LightAt l;
+    if (k == 0) {
+        l.pos = ld3(h->light_pos);
+        l.radius = h->light_radius;
+        l.col[0] = h->light_color[0], l.col[1] = h->light_color[1], l.col[2] = h->light_color[2];
+    } else {
+        const mcrt_light_source& e = ls.extra[k - 1];
+        l.pos = mk(e.position[0], e.position[1], e.position[2]);
+        l.radius = e.radius;
+        l.col[0] = e.color[0], l.col[1] = e.color[1], l.col[2] = e.color[2];
+    }
+    return l;
+}
+__device__ __forceinline__ void store_rgba(float* __restrict__ plane, const size_t idx, const float4 val) {
+    if ((reinterpret_cast<uintptr_t>(plane) & 15u) == 0) {
+        reinterpret_cast<float4*>(plane)[idx] = val;
+    } else {
+        float* o = plane + idx * 4;
+        o[0] = val.x, o[1] = val.y, o[2] = val.z, o[3] = val.w;
+    }
+}
+template <int kView>
+__device__ __forceinline__ void shade_lights_body(const ShadeLightsFrame& __restrict__ f, const ShadeShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][ShadeArea][positions: pass x S x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const SceneView scg = view_of(f.scene);
+    const mcrt_config& cfg = sh.tiles.cfg;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float aspect = static_cast<float>(cfg.width) / static_cast<float>(cfg.height);
+    const V3 cam = ld3(scg.hdr->cam_pos);
+    const int S = sh.samples;
+    const int K = min(max(f.lights.n_extra, 0), MCRT_MAX_EXTRA_LIGHTS);  // uniform
+    const bool raw_normal = S > 1;
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    ShadeArea& area = *reinterpret_cast<ShadeArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float4* s_rec = area.rec;  // plane 0: hit point; 1: normal; 2: texel colour — then, per light, the hit's {r, g, b, visibility}
+    const bool quads_ok = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    const int n_units = sh.tiles.tiles_x * sh.tiles.tiles_y * sh.tiles.parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        UnitPixel up;
+        if (!unit_pixel(sh.tiles, unit, tid, up)) continue;
+        const unsigned long long mask = layers_tile_mask(scg, cfg, up.tg, aspect, lane);  // the same in every wave of the workgroup
+        stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
+        // ---- a lane per pixel: the ray and its closest hit; a lane per hit: its record
+        bool is_hit = false, mine = false, shaded = false;  // shaded: uniform — the unit holds hits, the lights' loop resolves and shades
+        int rank = 0;
+        float alpha = 0.0f;  // shade()'s alpha of the pixel's hit: the texel's, clamped
+        Hit hit;
+        hit.hit = true;
+        V3 O = mk(0, 0, 0), view = mk(0, 0, 0);
+        if (mask != 0ull) {  // uniform
+            Hit h;
+            if (up.valid) {
+                h = pixel_hit(scg, sc, cfg, aspect, up.px, up.py, mask);
+                is_hit = h.hit;
+            }
+            int n_hits = 0;
+            rank = block_rank(is_hit, s_wcnt, n_hits);
+            if (is_hit) {
+                s_rec[rank] = make_float4(h.p.x, h.p.y, h.p.z, 0.0f);
+                s_rec[kBlock + rank] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
+                s_rec[2 * kBlock + rank] = make_float4(h.tex.r, h.tex.g, h.tex.b, h.tex.a);
+                alpha = sclamp(h.tex.a, 0.0f, 1.0f);
+            }
+            if (n_hits) {  // uniform
+                __syncthreads();
+                shaded = true;
+                mine = tid < n_hits;
+                if (mine) {
+                    const float4 a = s_rec[tid], b = s_rec[kBlock + tid], c = s_rec[2 * kBlock + tid];
+                    hit.p = mk(a.x, a.y, a.z), hit.n = mk(b.x, b.y, b.z), hit.tex = C4{c.x, c.y, c.z, c.w};
+                    O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
+                    view = normalize(cam - hit.p);
+                }
+            }
+        }
+        // ---- per light slot k: its planes.  A light the frame has (k <= K), in a unit with hits: the resolver and shade; otherwise the
+        // miss constants — ONE store site per plane, its values formed right in front of it
+        C4 comb{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < kMaxLights; ++k) {  // uniform
+            float vis = 1.0f;
+            C4 col{0.0f, 0.0f, 0.0f, 0.0f};
+            if (shaded && k <= K) {  // uniform: the resolver inside is collective
+                const LightAt l = frame_light(scg.hdr, f.lights, k);
+                const ShadowBundles sb = shadow_bundles_at(l, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins,
+                                                           area.sh.lit, area.sh.und, reinterpret_cast<float*>(&area + 1), s_wcnt);
+                // ---- resolve_shadow_bundles_at over the hits' shadow rays towards light k (depth 0)
+                uint32_t lit = 0u;
+                resolve_shadow_bundles_at<kPosed>(scg, sc, sb, l, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
+                // ---- a lane per hit: light k's visibility term and shade
+                if (mine) {
+                    const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    const C4 c = k == 0 ? shade(scg, hit, view, v) : shade_at(l, hit, view, 0.0f, v);
+                    s_rec[2 * kBlock + tid] = make_float4(c.r, c.g, c.b, v);  // (record tid is this lane's alone; its colour is in `hit`)
+                }
+                __syncthreads();
+                // ---- a lane per pixel: light k's values, and its term of the sum
+                if (is_hit) {
+                    const float4 r = s_rec[2 * kBlock + rank];
+                    vis = r.w;
+                    col = C4{r.x, r.y, r.z, alpha};
+                    comb = k == 0 ? col : C4{comb.r + col.r, comb.g + col.g, comb.b + col.b, comb.a};
+                }
+                // (the next light's record write lies behind the barriers of its resolver's block_rank, the next unit's behind its own)
+            }
+            float* const pv = f.vis[k];
+            float* const pd = f.dir[k];
+            if (pv) store_plane(pv, quads_ok && (reinterpret_cast<uintptr_t>(pv) & 15u) == 0, up.valid, lane, up.idx, vis);
+            if (pd && up.valid) store_rgba(pd, up.idx, make_float4(col.r, col.g, col.b, col.a));
+        }
+        if (f.combined && up.valid) {
+            comb = clamp4(comb);
+            store_rgba(f.combined, up.idx, make_float4(comb.r, comb.g, comb.b, comb.a));
+        }
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void shade_lights_kernel(const ShadeLightsFrame f, const ShadeShape sh) {
+    shade_lights_body<kView>(f, sh);
+}
+using ShadeLightsTable = const __attribute__((address_space(4))) ShadeLightsFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void shade_lights_batch_kernel(ShadeLightsTable table, const ShadeShape sh) {
+    shade_lights_body<kView>(*(const ShadeLightsFrame*)(table + blockIdx.y), sh);
+}
+template <int kView>
+__device__ __forceinline__ void bake_shade_lights_body(const BakeLightsFrame& __restrict__ f, const BakeShape& __restrict__ sh) {
+    extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][BakeShadeArea][positions: pass x S x 3 floats]
+    __shared__ int s_wcnt[kBlock / 64];
+    const int n_units = (f.n_texels + kBlock - 1) / kBlock;
+    if (static_cast<int>(blockIdx.x) >= n_units) return;  // (uniform; before the collective staging: the frames of a batch differ in size)
+    const SceneView scg = view_of(f.scene);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int S = sh.samples, q = sh.grid;
+    const int K = min(max(f.lights.n_extra, 0), MCRT_MAX_EXTRA_LIGHTS);  // uniform
+    const bool raw_normal = S > 1;
+    constexpr bool kPosed = kView != kViewLdsUnposed;
+    BakeShadeArea& area = *reinterpret_cast<BakeShadeArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
+    float4* s_rec = area.rec;       // plane 0: point; 1: normal
+    float4* s_tex = area.tex;       // the live texel's colour — then, plane by plane, its means
+    int4* s_own = area.own;         // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
+    uint32_t* s_lit = area.sh.lit;  // lit counts — then the texel's mean alpha, bit-cast
+    typename ViewSel<kView>::type sc;
+    bool staged = false;
+    stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, true, sc, staged);
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        // ---- a lane per texel: owner, colour, the geometry planes; the live texels are packed
+        const BakeLane b = bake_lane(f, scg, sc, unit, tid, sh.geometry != 0);
+        if (!sh.rays) continue;  // uniform: position / normal alone
+        int n_live = 0;
+        const int rank = block_rank(b.live, s_wcnt, n_live);
+        if (b.live) {
+            s_tex[rank] = b.tex;
+            s_own[rank] = make_int4(b.t.code, b.t.ty * b.t.w + b.t.tx, b.t.w, b.t.h);
+        }
+        const bool mine = tid < n_live;
+        float vsum[kMaxLights];  // (addressed by unrolled selects alone: registers)
+        C4 csum[kMaxLights];
+        C4 msum{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int j = 0; j < kMaxLights; ++j) vsum[j] = 0.0f, csum[j] = C4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (n_live) {  // uniform
+            __syncthreads();
+            BakeTexel t{-1, -1, -1, 0, 0};
+            Hit hit;
+            hit.hit = true;
+            if (mine) {
+                const int4 o = s_own[tid];
+                const float4 c = s_tex[tid];
+                t.code = o.x, t.w = o.z, t.h = o.w;
+                t.ty = o.y / o.z;
+                t.tx = o.y - t.ty * o.z;
+                hit.tex = C4{c.x, c.y, c.z, c.w};
+                hit.outer = (mesh_lane(sc, o.x >> 3).flags & MESH_OUTER) != 0;
+            }
+            for (int sub = 0; sub < q * q; ++sub) {  // uniform: j outer, i inner
+                const int sj = sub / q, si = sub - sj * q;
+                // ---- a lane per live texel: the sub-sample's point
+                V3 O = mk(0, 0, 0);
+                if (mine) {
+                    bake_point(sc, t, si, sj, q, hit.p, hit.n);
+                    s_rec[tid] = make_float4(hit.p.x, hit.p.y, hit.p.z, 0.0f);
+                    s_rec[kBlock + tid] = make_float4(hit.n.x, hit.n.y, hit.n.z, 0.0f);
+                    O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
+                }
+                // (the record of lane tid is read across lanes only behind the barriers of the resolver's block_rank, and the
+                // previous sub-sample's last resolver has left nothing to be read)
+                C4 comb{0.0f, 0.0f, 0.0f, 0.0f};
+                for (int k = 0; k <= K; ++k) {  // uniform: the resolver inside is collective
+                    const LightAt l = frame_light(scg.hdr, f.lights, k);
+                    const ShadowBundles sb = shadow_bundles_at(l, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins,
+                                                               area.sh.lit, area.sh.und, reinterpret_cast<float*>(&area + 1), s_wcnt);
+                    uint32_t lit = 0u;
+                    resolve_shadow_bundles_at<kPosed>(scg, sc, sb, l, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
+                    // ---- a lane per live texel: light k's visibility term and shade, added in the defined order
+                    if (mine) {
+                        const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                        const C4 c = k == 0 ? shade(scg, hit, hit.n, v) : shade_at(l, hit, hit.n, 0.0f, v);
+                        comb = k == 0 ? c : C4{comb.r + c.r, comb.g + c.g, comb.b + c.b, comb.a};
+#pragma unroll
+                        for (int j = 0; j < kMaxLights; ++j)
+                            if (j == k) {
+                                if (sub == 0) {
+                                    vsum[j] = v, csum[j] = c;
+                                } else {
+                                    vsum[j] = vsum[j] + v;
+                                    csum[j] = C4{csum[j].r + c.r, csum[j].g + c.g, csum[j].b + c.b, csum[j].a + c.a};
+                                }
+                            }
+                    }
+                }
+                if (mine) {
+                    comb = clamp4(comb);
+                    msum = sub == 0 ? comb : C4{msum.r + comb.r, msum.g + comb.g, msum.b + comb.b, msum.a + comb.a};
+                }
+            }
+            if (mine) {
+                if (q > 1) {
+                    const float d = static_cast<float>(q * q);
+#pragma unroll
+                    for (int j = 0; j < kMaxLights; ++j) {
+                        vsum[j] = vsum[j] / d;
+                        csum[j] = C4{csum[j].r / d, csum[j].g / d, csum[j].b / d, csum[j].a / d};
+                    }
+                    msum = C4{msum.r / d, msum.g / d, msum.b / d, msum.a / d};
+                }
+                s_lit[tid] = __float_as_uint(csum[0].a);  // (entry tid is this lane's alone by now; every light's mean alpha is light 0's)
+            }
+        }
+        // ---- the means return through LDS plane by plane — lights 0 .. K, then the sum — and a lane per texel stores them; a light
+        // the frame lacks and a dead texel take the constants
+        for (int k = 0; k <= kMaxLights; ++k) {  // uniform
+            const bool sum = k == kMaxLights;
+            float4 r = make_float4(0.0f, 0.0f, 0.0f, sum ? 0.0f : 1.0f);
+            float alpha = 0.0f;
+            if (n_live && (sum || k <= K)) {  // uniform
+                __syncthreads();  // the previous plane's values have been read (the first: the texel colours)
+                if (mine) {
+                    float pv = vsum[0];
+                    C4 pc = csum[0];
+#pragma unroll
+                    for (int j = 1; j < kMaxLights; ++j)
+                        if (j == k) pv = vsum[j], pc = csum[j];
+                    if (sum) pv = msum.a, pc = msum;
+                    s_tex[tid] = make_float4(pc.r, pc.g, pc.b, pv);
+                }
+                __syncthreads();
+                if (b.live) {
+                    r = s_tex[rank];
+                    alpha = __uint_as_float(s_lit[rank]);
+                }
+            }
+            if (sum) {
+                if (f.combined && b.valid) bake_store4(f.combined, (reinterpret_cast<uintptr_t>(f.combined) & 15u) == 0, b.texel, r);
+            } else {
+                float* const pv = f.vis[k];
+                float* const pd = f.dir[k];
+                if (pv) bake_store_plane(pv, (reinterpret_cast<uintptr_t>(pv) & 15u) == 0, b.texel, f.n_texels, lane, r.w);
+                if (pd && b.valid) bake_store4(pd, (reinterpret_cast<uintptr_t>(pd) & 15u) == 0, b.texel, make_float4(r.x, r.y, r.z, alpha));
+            }
+        }
+        // (the next unit writes its records behind the two barriers of its block_rank)
+    }
+}
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void bake_shade_lights_kernel(const BakeLightsFrame f, const BakeShape sh) {
+    bake_shade_lights_body<kView>(f, sh);
+}
+using BakeLightsTable = const __attribute__((address_space(4))) BakeLightsFrame*;
+template <int kView>
+__global__ __launch_bounds__(kBlock, kGroundWaves) void bake_shade_lights_batch_kernel(BakeLightsTable table, const BakeShape sh) {
+    bake_shade_lights_body<kView>(*(const BakeLightsFrame*)(table + blockIdx.y), sh);
+}
+
+// ---------------------------------------------------------------------------------------------
 // studio shot (kernels.h: ShotFrame): the blend of include/mcrt.h, "studio shot" — the straight-alpha figure over a page that
 // carries the ground shadow and the floor reflection — as one streaming pass.  No scene geometry, no LDS, no atomics:
 //   1 lane / pixel (grid-stride over the frame's pixels, blockIdx.y = frame)
@@ -1905,6 +2199,26 @@ hipError_t launch_bake_batch(const BakeFrame* d_table, int n_frames, const BakeS
         e = launch_bake_pass(BakeTable(d_table), n_frames, sh, view, occlusion_dyn, stream, [](auto v) { return bake_occlusion_batch_kernel<decltype(v)::value>; });
     }
     return e;
+}
+// ---- light layers and bake under extra lights (kernels.h): `shade_lights` / `bake_shade_lights` alone, with the single-light
+// kernels' LDS (the area does not grow with the lights); the occlusion plane goes through launch_light / launch_bake
+hipError_t launch_light_multi(const ShadeLightsFrame& f, const ShadeShape& shape, int view, hipStream_t stream) {
+    const size_t dyn = shade_lds_bytes(f, shape);
+    return launch_tile_pass(f, 1, shape, shape.tiles, view, dyn, dyn, stream, [](auto v) { return shade_lights_kernel<decltype(v)::value>; });
+}
+hipError_t launch_light_multi_batch(const ShadeLightsFrame* d_table, int n_frames, const ShadeShape& shape, int view, size_t max_dyn, hipStream_t stream) {
+    return launch_tile_pass(ShadeLightsTable(d_table), n_frames, shape, shape.tiles, view, max_dyn, max_dyn, stream,
+                            [](auto v) { return shade_lights_batch_kernel<decltype(v)::value>; });
+}
+hipError_t launch_bake_multi(const BakeLightsFrame& f, const BakeShape& shape, int view, hipStream_t stream) {
+    BakeShape sh = shape;
+    sh.geometry = 1, sh.rays = 1;
+    return launch_bake_pass(f, 1, sh, view, bake_shade_lds_bytes(f, sh), stream, [](auto v) { return bake_shade_lights_kernel<decltype(v)::value>; });
+}
+hipError_t launch_bake_multi_batch(const BakeLightsFrame* d_table, int n_frames, const BakeShape& shape, int view, size_t max_dyn, hipStream_t stream) {
+    BakeShape sh = shape;
+    sh.geometry = 1, sh.rays = 1;
+    return launch_bake_pass(BakeLightsTable(d_table), n_frames, sh, view, max_dyn, stream, [](auto v) { return bake_shade_lights_batch_kernel<decltype(v)::value>; });
 }
 hipError_t launch_pick(const uint8_t* scene, const LayersShape& shape, const int32_t* d_xy, int n, mcrt_surface* d_out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;

@@ -513,6 +513,43 @@ int bake_frame_of(const mcrt_scene* s, const mcrt_bake_planes& out, size_t index
     return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
 }
 
+// and for the two passes under extra lights (mcrt_render_light_multi_device, mcrt_bake_light_multi_device & co): the base record
+// without its light planes — the occlusion plane travels in a ShadeFrame / BakeFrame of its own —, the handle's lights BY VALUE
+// and the planes per light
+int shade_lights_frame_of(const mcrt_scene* s, const mcrt_light_planes_multi& out, size_t index, size_t stride, ShadeLightsFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.seed_table = s->seed_table;
+    f.seed_table_full = s->seed_table_full;
+    f.lights = s->extra;
+    for (int k = 0; k < kMaxLights; ++k) {
+        f.vis[k] = out.visibility[k] ? out.visibility[k] + off : nullptr;
+        f.dir[k] = out.direct[k] ? out.direct[k] + off * 4 : nullptr;
+    }
+    f.combined = out.combined ? out.combined + off * 4 : nullptr;
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
+}
+int bake_lights_frame_of(const mcrt_scene* s, const mcrt_bake_planes_multi& out, size_t index, size_t stride, BakeLightsFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const size_t off = index * stride;
+    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
+    f.faces = reinterpret_cast<const BakeFace*>(static_cast<const uint8_t*>(s->blob.ptr) + s->bake_faces_offset);
+    f.n_faces = s->bake_n_faces;
+    f.n_texels = s->n_texels;
+    f.position = out.position ? reinterpret_cast<float4*>(out.position + off * 4) : nullptr;
+    f.normal = out.normal ? reinterpret_cast<float4*>(out.normal + off * 4) : nullptr;
+    f.seed_table = s->seed_table;
+    f.seed_table_full = s->seed_table_full;
+    f.lights = s->extra;
+    for (int k = 0; k < kMaxLights; ++k) {
+        f.vis[k] = out.visibility[k] ? out.visibility[k] + off : nullptr;
+        f.dir[k] = out.direct[k] ? out.direct[k] + off * 4 : nullptr;
+    }
+    f.combined = out.combined ? out.combined + off * 4 : nullptr;
+    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
+}
+
 // What the layers and the ground entry points check alike, before any device work (only the last check looks inside the
 // handles, at their device index).  run = false with MCRT_OK: zero tiles, nothing is written.
 int check_pass_arguments(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const void* d_out, size_t stride, bool& run, int& device) {
@@ -951,6 +988,97 @@ int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config*
         [&](const BakeFrame* d_table, int m, int view, PassLds dyn) {
             return launch_bake_batch(d_table, m, shape, view, shade, dyn.first, occlusion, dyn.second, stream);
         });
+}
+
+// ---- light layers and bake under extra lights (mcrt_render_light_multi_device, mcrt_bake_light_multi_device & co): the host paths
+// of the two passes above with a kernel of their own for the planes that read the lights — `shade_lights` / `bake_shade_lights`
+// over records that carry the handle's lights by value — and the single-light passes' occlusion kernel, over a record of its own
+// with that plane alone, for the plane that reads none.  The checks are the single-light entries', in their order; nothing
+// refuses a handle for its lights.
+int render_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes_multi* d_out, size_t stride,
+                                    hipStream_t stream) {
+    // argument checks, before any device work
+    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all planes are NULL");
+    if (cfg && d_out) {
+        const mcrt_light_planes occ = occlusion_alone(d_out);
+        if (const int rc = check_light_config(cfg, &occ); rc != MCRT_OK) return rc;
+    }
+    bool run;
+    int device = 0;
+    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
+    ShadeShape shape;
+    if (!make_shade_shape(*cfg, decisions, inside_fast, shape)) return fail(MCRT_ERR_INVALID, "the frame holds more than 2^31 work units");
+    HIP_TRY(hipSetDevice(device));
+    if (light_plane_asked(d_out)) {
+        const int rc = enqueue_pass<ShadeLightsFrame>(
+            device, n, stream, "light launches", [&](int i, ShadeLightsFrame& f) { return shade_lights_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, f); },
+            [&](const ShadeLightsFrame& f) { return PassLds{shade_lds_bytes(f, shape), 0}; },
+            [&](const ShadeLightsFrame& f, int view) { return launch_light_multi(f, shape, view, stream); },
+            [&](const ShadeLightsFrame* d_table, int m, int view, PassLds dyn) { return launch_light_multi_batch(d_table, m, shape, view, dyn.first, stream); });
+        if (rc != MCRT_OK) return rc;
+    }
+    if (!d_out->occlusion) return MCRT_OK;
+    const mcrt_light_planes occ = occlusion_alone(d_out);
+    return enqueue_pass<ShadeFrame>(
+        device, n, stream, "light launches",
+        [&](int i, ShadeFrame& f) {
+            share_full_seed_table(scenes[i]);
+            return shade_frame_of(scenes[i], occ, static_cast<size_t>(i), stride, f);
+        },
+        [&](const ShadeFrame& f) { return PassLds{0, occlusion_lds_bytes(f)}; }, [&](const ShadeFrame& f, int view) { return launch_light(f, shape, view, stream); },
+        [&](const ShadeFrame* d_table, int m, int view, PassLds dyn) { return launch_light_batch(d_table, m, shape, view, false, 0, true, dyn.second, stream); });
+}
+
+int bake_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes_multi* d_out, size_t stride,
+                                  hipStream_t stream) {
+    // argument checks, before any device work (only the last ones look inside the handles: device index and texel count)
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all planes are NULL");
+    {
+        const mcrt_bake_planes occ = occlusion_alone(d_out);
+        if (const int rc = check_bake_config(cfg, grid, &occ); rc != MCRT_OK) return rc;
+    }
+    if (n == 0) return MCRT_OK;
+    const int device = scenes[0]->device;
+    int max_texels = 0;
+    for (int i = 0; i < n; ++i) {
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+        if (scenes[i]->n_texels > 0 && stride < static_cast<size_t>(scenes[i]->n_texels)) return fail(MCRT_ERR_INVALID, "texel_stride is smaller than a scene's texel count");
+        max_texels = std::max(max_texels, scenes[i]->n_texels);
+    }
+    if (max_texels <= 0) return MCRT_OK;  // no texel: nothing is written
+    static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
+    static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
+    BakeShape shape;
+    make_bake_shape(*cfg, grid, decisions, inside_fast, max_texels, shape);
+    HIP_TRY(hipSetDevice(device));
+    const bool lights = light_plane_asked(d_out);
+    if (lights) {  // `bake_shade_lights` writes position and normal too
+        const int rc = enqueue_pass<BakeLightsFrame>(
+            device, n, stream, "bake launches", [&](int i, BakeLightsFrame& f) { return bake_lights_frame_of(scenes[i], *d_out, static_cast<size_t>(i), stride, f); },
+            [&](const BakeLightsFrame& f) { return PassLds{bake_shade_lds_bytes(f, shape), 0}; },
+            [&](const BakeLightsFrame& f, int view) { return launch_bake_multi(f, shape, view, stream); },
+            [&](const BakeLightsFrame* d_table, int m, int view, PassLds dyn) { return launch_bake_multi_batch(d_table, m, shape, view, dyn.first, stream); });
+        if (rc != MCRT_OK || !d_out->occlusion) return rc;
+    }
+    // what is left is the single-light bake's: the occlusion plane, and position / normal where no plane that reads the lights was asked for
+    mcrt_bake_planes rest = occlusion_alone(d_out);
+    if (!lights) rest.position = d_out->position, rest.normal = d_out->normal;
+    const bool occlusion = rest.occlusion != nullptr;
+    return enqueue_pass<BakeFrame>(
+        device, n, stream, "bake launches",
+        [&](int i, BakeFrame& f) {
+            if (occlusion) share_full_seed_table(scenes[i]);
+            return bake_frame_of(scenes[i], rest, static_cast<size_t>(i), stride, f);
+        },
+        [&](const BakeFrame& f) { return PassLds{bake_shade_lds_bytes(f, shape), bake_occlusion_lds_bytes(f)}; },
+        [&](const BakeFrame& f, int view) { return launch_bake(f, shape, view, stream); },
+        [&](const BakeFrame* d_table, int m, int view, PassLds dyn) { return launch_bake_batch(d_table, m, shape, view, false, dyn.first, occlusion, dyn.second, stream); });
 }
 
 // ---- skins on resident scenes (mcrt_scene_set_skin_device & co): one workgroup per handle rewrites the texel pool, the alpha
@@ -1667,6 +1795,29 @@ int mcrt_bake_light_device(mcrt_scene* s, const mcrt_config* cfg, int grid, cons
 int mcrt_bake_light_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out,
                                  size_t texel_stride, void* stream) {
     return bake_light_batch_device(scenes, n_frames, cfg, grid, d_out, texel_stride, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_light_multi_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_light_planes_multi* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    const size_t px = cfg ? static_cast<size_t>(cfg->width > 0 ? cfg->width : 0) * static_cast<size_t>(cfg->height > 0 ? cfg->height : 0) : 0;
+    return render_light_multi_batch_device(one, 1, cfg, d_out, px, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_render_light_multi_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_light_planes_multi* d_out,
+                                         size_t frame_stride_pixels, void* stream) {
+    return render_light_multi_batch_device(scenes, n_frames, cfg, d_out, frame_stride_pixels, static_cast<hipStream_t>(stream));
+}
+
+int mcrt_bake_light_multi_device(mcrt_scene* s, const mcrt_config* cfg, int grid, const mcrt_bake_planes_multi* d_out, void* stream) {
+    if (!s) return fail(MCRT_ERR_INVALID, "NULL argument");
+    mcrt_scene* one[1] = {s};
+    return bake_light_multi_batch_device(one, 1, cfg, grid, d_out, ~static_cast<size_t>(0), static_cast<hipStream_t>(stream));  // (one frame: no stride)
+}
+
+int mcrt_bake_light_multi_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, int grid, const mcrt_bake_planes_multi* d_out,
+                                       size_t texel_stride, void* stream) {
+    return bake_light_multi_batch_device(scenes, n_frames, cfg, grid, d_out, texel_stride, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_scene_texels(mcrt_scene* s, int* n_texels) {
