@@ -1088,22 +1088,21 @@ void mcrt_shot_ex_init(mcrt_shot_ex* shot) {
 
 size_t mcrt_shot_scratch_bytes_ex(const mcrt_config* cfg, const mcrt_shot_ex* shot, int n_frames) {
     if (!cfg || !shot || n_frames <= 0 || !valid_frame(cfg) || shot_frame_too_large(cfg)) return 0;
-    ShotExtra ex;
-    std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
-    if (check_shot_ex(&shot->shot, ex) != MCRT_OK || check_floor_occlusion(shot->floor_occlusion) != MCRT_OK) return 0;
+    if (check_shot(shot_spec_ex(shot, nullptr)) != MCRT_OK || check_floor_occlusion(shot->floor_occlusion) != MCRT_OK) return 0;
     return shot_scratch(cfg, &shot->shot, n_frames, shot->floor_occlusion).bytes;
 }
 
-// the host forms with and without the floor-occlusion term (the latter: floor_occlusion = 0); ex: the _ex entries' additions
-// (bounds: n_frames entries in HOST memory, downloaded with the image), nullptr for the entries before them
-static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion,
-                                  const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device, const ShotExtra* ex = nullptr) {
+// the host form of every entry family (spec.bounds: n_frames entries in HOST memory, downloaded with the image)
+static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const ShotSpec& spec, const float* ground_y,
+                                  float* out_rgba, uint8_t* out_rgba8, int device) {
+    const mcrt_shot* shot = spec.shot;
+    const float floor_occlusion = spec.floor_occlusion;
     // the device form's checks that need no handle, before anything is created
     if (n_frames < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || (n_frames > 0 && (!descs || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n_frames; ++i)
         if (!descs[i]) return fail(MCRT_ERR_INVALID, "NULL scene description in the batch");
-    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(spec); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     for (int i = 0; i < n_frames; ++i)
         if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
@@ -1120,19 +1119,17 @@ static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_fra
     const size_t scratch_bytes = shot_scratch(cfg, shot, n_frames, floor_occlusion).bytes;
     float* d_f32 = nullptr;
     uint8_t* d_u8 = nullptr;
-    ShotExtra on_device;  // the caller's additions, with the bounds in device memory
-    if (ex) on_device = *ex;
+    ShotSpec on_device = spec;  // with the bounds in device memory
     on_device.bounds = nullptr;
     const Plane planes[] = {{out_rgba, 16, &d_f32}, {out_rgba8, 4, &d_u8}};
-    const Plane boxes[] = {{ex ? ex->bounds : nullptr, sizeof(int32_t[4]), &on_device.bounds}};
+    const Plane boxes[] = {{spec.bounds, sizeof(int32_t[4]), &on_device.bounds}};
     const size_t out_bytes = place_planes(planes, total_px, nullptr);
     hipError_t e = s0->frame.reserve(scratch_bytes + out_bytes + place_planes(boxes, static_cast<size_t>(n_frames), nullptr));
     if (e != hipSuccess) return hip_fail(e, "shot planes");
     char* base = static_cast<char*>(s0->frame.ptr);
     place_planes(planes, total_px, base + scratch_bytes);
     place_planes(boxes, static_cast<size_t>(n_frames), base + scratch_bytes + out_bytes);
-    rc = render_shot_batch_device(set.h.data(), n_frames, cfg, shot, floor_occlusion, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream,
-                                  ex ? &on_device : nullptr);
+    rc = render_shot_batch_device(set.h.data(), n_frames, cfg, on_device, ground_y, base, scratch_bytes, d_f32, d_u8, px, s0->main_stream);
     set.download(planes, total_px, rc);
     set.download(boxes, static_cast<size_t>(n_frames), rc);
     if (rc == MCRT_OK) {
@@ -1145,12 +1142,12 @@ static int render_shot_batch_host(const mcrt_scene_desc* const* descs, int n_fra
 
 int mcrt_render_shot_batch(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y,
                            float* out_rgba, uint8_t* out_rgba8, int device) {
-    return render_shot_batch_host(descs, n_frames, cfg, shot, 0.0f, ground_y, out_rgba, out_rgba8, device);
+    return render_shot_batch_host(descs, n_frames, cfg, shot_spec(shot, 0.0f), ground_y, out_rgba, out_rgba8, device);
 }
 
 int mcrt_render_shot_batch_occ(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion,
                                const float* ground_y, float* out_rgba, uint8_t* out_rgba8, int device) {
-    return render_shot_batch_host(descs, n_frames, cfg, shot, floor_occlusion, ground_y, out_rgba, out_rgba8, device);
+    return render_shot_batch_host(descs, n_frames, cfg, shot_spec(shot, floor_occlusion), ground_y, out_rgba, out_rgba8, device);
 }
 
 int mcrt_render_shot(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, float* out_rgba, uint8_t* out_rgba8,
@@ -1160,11 +1157,12 @@ int mcrt_render_shot(const mcrt_scene_desc* desc, const mcrt_config* cfg, const 
     return mcrt_render_shot_batch(one, 1, cfg, shot, &ground_y, out_rgba, out_rgba8, device);
 }
 
-// ex: mcrt_render_shot_png_ex's additions — bounds (one entry in host memory, or nullptr) and crop
-static int render_shot_png_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, float ground_y, const char* path,
-                                int device, const ShotExtra* ex = nullptr) {
+// spec.bounds: one entry in host memory, or nullptr
+static int render_shot_png_host(const mcrt_scene_desc* desc, const mcrt_config* cfg, const ShotSpec& spec, float ground_y, const char* path, int device) {
+    const mcrt_shot* shot = spec.shot;
+    const float floor_occlusion = spec.floor_occlusion;
     if (!desc || !cfg || !shot || !path) return fail(MCRT_ERR_INVALID, "NULL argument");
-    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(spec); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     if (!std::isfinite(ground_y)) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
     if (const int rc = check_shot_config(cfg, shot, floor_occlusion); rc != MCRT_OK) return rc;
@@ -1172,20 +1170,20 @@ static int render_shot_png_host(const mcrt_scene_desc* desc, const mcrt_config* 
     if (shot_frame_too_large(cfg)) return fail(MCRT_ERR_INVALID, "the frame holds 2^31 pixels or more");
     std::vector<uint8_t> host(static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) * 4);
     const mcrt_scene_desc* one[1] = {desc};
-    if (!ex) {
-        const int rc = render_shot_batch_host(one, 1, cfg, shot, floor_occlusion, &ground_y, nullptr, host.data(), device);
+    if (!spec.ex) {
+        const int rc = render_shot_batch_host(one, 1, cfg, spec, &ground_y, nullptr, host.data(), device);
         if (rc != MCRT_OK) return rc;
         return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);
     }
     // the cut-out's file: the box comes down with the image where the page is transparent and somebody wants it
     int32_t box[1][4] = {{0, 0, cfg->width, cfg->height}};
-    ShotExtra with_box = *ex;
-    with_box.bounds = shot->page == MCRT_PAGE_TRANSPARENT && (ex->bounds || ex->crop) ? box : nullptr;
-    const int rc = render_shot_batch_host(one, 1, cfg, shot, floor_occlusion, &ground_y, nullptr, host.data(), device, &with_box);
+    ShotSpec with_box = spec;
+    with_box.bounds = shot->page == MCRT_PAGE_TRANSPARENT && (spec.bounds || spec.crop) ? box : nullptr;
+    const int rc = render_shot_batch_host(one, 1, cfg, with_box, &ground_y, nullptr, host.data(), device);
     if (rc != MCRT_OK) return rc;
-    if (ex->bounds) std::memcpy(ex->bounds[0], box[0], sizeof box[0]);
+    if (spec.bounds) std::memcpy(spec.bounds[0], box[0], sizeof box[0]);
     const int x0 = box[0][0], y0 = box[0][1], x1 = box[0][2], y1 = box[0][3];
-    if (!ex->crop || x1 <= x0 || y1 <= y0) return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);  // an empty box: the whole frame
+    if (!spec.crop || x1 <= x0 || y1 <= y0) return mcrt_write_png_rgba8(path, host.data(), cfg->width, cfg->height);  // an empty box: the whole frame
     const size_t row = static_cast<size_t>(x1 - x0) * 4;
     std::vector<uint8_t> cut(row * static_cast<size_t>(y1 - y0));
     for (int y = y0; y < y1; ++y)
@@ -1195,28 +1193,21 @@ static int render_shot_png_host(const mcrt_scene_desc* desc, const mcrt_config* 
 
 int mcrt_render_shot_batch_ex(const mcrt_scene_desc* const* descs, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot, const float* ground_y,
                               float* out_rgba, uint8_t* out_rgba8, int32_t (*out_bounds)[4], int device) {
-    ShotExtra ex;
-    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
-    ex.bounds = out_bounds;
-    return render_shot_batch_host(descs, n_frames, cfg, shot ? &shot->shot : nullptr, shot ? shot->floor_occlusion : 0.0f, ground_y, out_rgba, out_rgba8, device, &ex);
+    return render_shot_batch_host(descs, n_frames, cfg, shot_spec_ex(shot, out_bounds), ground_y, out_rgba, out_rgba8, device);
 }
 
 int mcrt_render_shot_png_ex(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot_ex* shot, float ground_y, const char* path, int crop,
                             int32_t* out_bounds, int device) {
-    ShotExtra ex;
-    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
-    ex.bounds = reinterpret_cast<int32_t(*)[4]>(out_bounds);
-    ex.crop = crop != 0;
-    return render_shot_png_host(desc, cfg, shot ? &shot->shot : nullptr, shot ? shot->floor_occlusion : 0.0f, ground_y, path, device, &ex);
+    return render_shot_png_host(desc, cfg, shot_spec_ex(shot, reinterpret_cast<int32_t(*)[4]>(out_bounds), crop != 0), ground_y, path, device);
 }
 
 int mcrt_render_shot_png(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float ground_y, const char* path, int device) {
-    return render_shot_png_host(desc, cfg, shot, 0.0f, ground_y, path, device);
+    return render_shot_png_host(desc, cfg, shot_spec(shot, 0.0f), ground_y, path, device);
 }
 
 int mcrt_render_shot_png_occ(const mcrt_scene_desc* desc, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, float ground_y, const char* path,
                              int device) {
-    return render_shot_png_host(desc, cfg, shot, floor_occlusion, ground_y, path, device);
+    return render_shot_png_host(desc, cfg, shot_spec(shot, floor_occlusion), ground_y, path, device);
 }
 
 // ---- light layers: the one-shot host form (render_enqueue.cpp: render_light_batch_device) ----------------------------------------

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -299,6 +300,8 @@ inline bool light_plane_asked(const mcrt_bake_planes_multi* b) {
 }
 inline bool no_plane(const mcrt_light_planes_multi* l) { return !light_plane_asked(l) && !l->occlusion; }
 inline bool no_plane(const mcrt_bake_planes_multi* b) { return !light_plane_asked(b) && !b->occlusion && !b->position && !b->normal; }
+inline mcrt_light_planes occlusion_alone(const mcrt_light_planes* l) { return mcrt_light_planes{nullptr, l->occlusion, nullptr}; }
+inline mcrt_bake_planes occlusion_alone(const mcrt_bake_planes* b) { return mcrt_bake_planes{nullptr, nullptr, nullptr, b->occlusion, nullptr}; }
 inline mcrt_light_planes occlusion_alone(const mcrt_light_planes_multi* l) { return mcrt_light_planes{nullptr, l->occlusion, nullptr}; }
 inline mcrt_bake_planes occlusion_alone(const mcrt_bake_planes_multi* b) { return mcrt_bake_planes{nullptr, nullptr, nullptr, b->occlusion, nullptr}; }
 
@@ -317,15 +320,34 @@ inline int check_floor_occlusion(float o) {
     if (!(o >= 0.0f && o <= 1.0f)) return fail(MCRT_ERR_INVALID, "floor_occlusion must lie in [0, 1]");
     return MCRT_OK;
 }
-// What the _ex entry points add to a shot (the entries before them pass nullptr): the shadow's colour and the bounds — device
-// memory behind the device forms, host memory behind the host forms.  With it the shot's page may be MCRT_PAGE_TRANSPARENT.
-struct ShotExtra {
+// What a shot entry point asks for, as the shot's host paths pass it on: the caller's shot (NULL is refused where the entries
+// refuse it), the strength of the floor-occlusion term (0 from the plain entries) and what the _ex entries add — the shadow's
+// colour, the bounds (device memory behind the device forms, host memory behind the host forms) and the PNG's crop.  `ex`: an
+// _ex entry called; the page may then be MCRT_PAGE_TRANSPARENT, and the checks and their messages are that family's.
+struct ShotSpec {
+    const mcrt_shot* shot = nullptr;
+    float floor_occlusion = 0.0f;
     float shadow_color[3] = {0.0f, 0.0f, 0.0f};
     int32_t (*bounds)[4] = nullptr;
     bool crop = false;  // mcrt_render_shot_png_ex's: like the bounds, only with the transparent page
+    bool ex = false;
 };
-// what they refuse of the shot: check_shot's list with the third page, then the colour and what needs the transparent page
-inline int check_shot_ex(const mcrt_shot* s, const ShotExtra& ex) {
+inline ShotSpec shot_spec(const mcrt_shot* shot, float floor_occlusion) {
+    ShotSpec spec;
+    spec.shot = shot, spec.floor_occlusion = floor_occlusion;
+    return spec;
+}
+inline ShotSpec shot_spec_ex(const mcrt_shot_ex* shot, int32_t (*bounds)[4], bool crop = false) {  // (a NULL shot stays NULL)
+    ShotSpec spec;
+    if (shot) {
+        spec.shot = &shot->shot, spec.floor_occlusion = shot->floor_occlusion;
+        std::memcpy(spec.shadow_color, shot->shadow_color, sizeof spec.shadow_color);
+    }
+    spec.bounds = bounds, spec.crop = crop, spec.ex = true;
+    return spec;
+}
+// what the _ex entries refuse of the shot: check_shot's list with the third page, then the colour and what needs the transparent page
+inline int check_shot_ex(const mcrt_shot* s, const ShotSpec& ex) {
     if (s->page < MCRT_PAGE_COLOR || s->page > MCRT_PAGE_TRANSPARENT)
         return fail(MCRT_ERR_INVALID, "page must be MCRT_PAGE_COLOR, MCRT_PAGE_REFERENCE or MCRT_PAGE_TRANSPARENT");
     mcrt_shot on_a_page = *s;
@@ -336,7 +358,7 @@ inline int check_shot_ex(const mcrt_shot* s, const ShotExtra& ex) {
     if (s->page != MCRT_PAGE_TRANSPARENT && (ex.bounds || ex.crop)) return fail(MCRT_ERR_INVALID, "bounds and crop come with MCRT_PAGE_TRANSPARENT only");
     return MCRT_OK;
 }
-inline int check_shot(const mcrt_shot* s, const ShotExtra* ex) { return ex ? check_shot_ex(s, *ex) : check_shot(s); }
+inline int check_shot(const ShotSpec& spec) { return spec.ex ? check_shot_ex(spec.shot, spec) : check_shot(spec.shot); }
 // and of the config of a shot that renders: the render's limit, and the limits of the passes the shot runs
 int validate_config(const mcrt_config* cfg);
 inline int check_shot_config(const mcrt_config* c, const mcrt_shot* s, float floor_occlusion = 0.0f) {
@@ -461,14 +483,11 @@ int bake_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt_c
                                   hipStream_t stream);
 // the studio shot's blend on the caller's planes (mcrt_composite_shot_batch_device[_occ]), and render + ground + reflection +
 // ground occlusion + blend on `stream` in order with the planes in the caller's scratch (mcrt_render_shot_batch_device[_occ]);
-// the entries without the floor-occlusion term pass floor_occlusion = 0 and no plane; ex: the _ex entries' additions (bounds:
-// device memory), nullptr for the entries before them, which then launch the kernels they always launched
-int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
-                                const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride,
-                                hipStream_t stream, const ShotExtra* ex = nullptr);
-int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, const float* ground_y,
-                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream,
-                             const ShotExtra* ex = nullptr);
+// the entries without the floor-occlusion term pass a spec with floor_occlusion = 0 and no plane; spec.bounds: device memory
+int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const ShotSpec& spec, const mcrt_shot_inputs* d_in,
+                                const float* d_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream);
+int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const ShotSpec& spec, const float* ground_y, void* d_scratch,
+                             size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream);
 // repaints the n repaintable handles from the skin images at d_skins + i * stride_bytes (mcrt_scene_set_skins_batch_device)
 int set_skins_batch_device(mcrt_scene* const* scenes, int n, const uint8_t* d_skins, size_t stride_bytes, hipStream_t stream);
 // gives the n repaintable handles the views (poses[i], looks[i]); NULL poses, looks or looks[i]: the handle's own

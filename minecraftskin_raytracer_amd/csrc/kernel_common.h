@@ -291,6 +291,30 @@ __device__ __forceinline__ void disk_sample_positions(const SceneView& scg, cons
     }
 }
 
+// disk_sample_positions as the shadow resolver calls it — no sample table, no table of all seeds — for any light l (rt_core.h).
+// Every light's call seeds from the same (P, depth): all lights see the same draws.  (A core of its own beside the form above:
+// every shape that shared the two moved `lit`'s schedule — profiles/fold_twins/README.md.)
+template <class Light>
+__device__ __forceinline__ void disk_sample_positions_at(const Light& l, const uint32_t* __restrict__ seed_table, const V3 P, const int depth, const int S,
+                                                         float* __restrict__ dst) {
+    MtShort rng;
+    const uint32_t seed = shadow_seed(P, depth);
+    const uint32_t slot = seed + kSeedWindowHalf;  // wraps: the window is centred on seed 0
+    if (seed_table && slot < kSeedWindow)
+        rng.seed_known(seed, seed_table[slot]);  // mt[397] of this seed, from the device's table
+    else
+        rng.seed(seed);  // the 397-step recurrence
+    const LightFrame frame = light_frame_at(l.position(), P);
+    for (int i = 0; i < S; ++i) {
+        const float d0 = rng.uniform();
+        const float d1 = rng.uniform();
+        const V3 t = light_sample_at(l, frame, d0, d1);
+        dst[3 * i + 0] = t.x;
+        dst[3 * i + 1] = t.y;
+        dst[3 * i + 2] = t.z;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // phases the stand-alone passes share (pass_kernels.hip; DESIGN.md, "phases the passes share")
 // ---------------------------------------------------------------------------------------------
@@ -330,7 +354,7 @@ __device__ __forceinline__ void count_item_rays(const uint32_t* __restrict__ ite
 // and the four wave counts of block_rank.
 struct ShadowBundles {
     V3 lpos;
-    float R;          // the light's radius, 0 in the hard modes
+    float R;          // the light's disk radius, 0 in the hard modes
     bool soft;        // S rays per item towards disk samples; otherwise one towards the light's centre (shading.cpp:31)
     int S;
     uint32_t pairs;   // rays per item
@@ -344,15 +368,21 @@ struct ShadowBundles {
     float* pos;
     int* wcnt;
 };
-__device__ __forceinline__ ShadowBundles shadow_bundles(const SceneView& scg, const int samples, const int pass, const int decisions, const int inside_fast,
+template <class Light>
+__device__ __forceinline__ ShadowBundles shadow_bundles(const Light& l, const int samples, const int pass, const int decisions, const int inside_fast,
                                                         const uint32_t* seed_table, unsigned long long* cand, unsigned long long* ins, uint32_t* lit,
                                                         uint32_t* und, float* pos, int* wcnt) {
-    const float lradius = scg.hdr->light_radius;
+    const float lradius = l.disk_radius();
     const bool soft = samples > 1 && !(lradius < 1e-4f);
-    return ShadowBundles{ld3(scg.hdr->light_pos), soft ? lradius : 0.0f, soft, samples, soft ? static_cast<uint32_t>(samples) : 1u, static_cast<uint32_t>(pass),
+    return ShadowBundles{l.position(), soft ? lradius : 0.0f, soft, samples, soft ? static_cast<uint32_t>(samples) : 1u, static_cast<uint32_t>(pass),
                          decisions != 0, inside_fast != 0, seed_table, cand, ins, lit, und, pos, wcnt};
 }
-// The lit counts of the workgroup's items, one per lane (item = lane index; `active`: the lane holds one, with shadow origin O):
+// the visibility term of an item from its lit count: lit / S of computeSoftShadow, or the one ray of the hard modes
+__device__ __forceinline__ float bundle_visibility(const ShadowBundles& b, const uint32_t lit) {
+    return b.soft ? static_cast<float>(lit) / static_cast<float>(b.S) : (lit ? 1.0f : 0.0f);
+}
+// The lit counts of the workgroup's items towards light l, of which b was made (shadow_bundles(l, ...)): the scene's
+// header_light, or a LightAt.  One per lane (item = lane index; `active`: the lane holds one, with shadow origin O):
 // the whole-bundle decision (rt::bundle_classify, its candidates ANDed with tile_mask) and the inside masks by the item's
 // lane; the undecided packed (block_rank); then in passes of b.pass items a lane per item forms the S disk sample positions
 // of the engine seeded for (point, depth), and a lane per (item, sample) runs the exact any-hit test (count_item_rays).
@@ -361,10 +391,11 @@ __device__ __forceinline__ ShadowBundles shadow_bundles(const SceneView& scg, co
 // without an item.
 // COLLECTIVE: two barriers of block_rank, then — only where the workgroup has undecided items — one before the passes, one
 // per pass (and one between passes) and one behind the counts.  All 256 threads must reach it under uniform control flow;
-// a barrier under a divergent branch hangs the device.  Behind it nothing of the area is read across lanes any more.
-template <bool kPosed, class SV, class PointOf>
-__device__ __forceinline__ bool resolve_shadow_bundles(const SceneView& scg, const SV& sc, const ShadowBundles b, const bool active, const V3 O,
-                                                       const unsigned long long tile_mask, const int depth, PointOf point_of, uint32_t& lit) {
+// a barrier under a divergent branch hangs the device — a loop over lights around it has the same trip count in all of them.
+// Behind it nothing of the area is read across lanes any more, so the next light's call may write it at once.
+template <bool kPosed, class SV, class Light, class PointOf>
+__device__ __forceinline__ bool resolve_shadow_bundles(const SceneView& scg, const SV& sc, const ShadowBundles b, const Light& l, const bool active,
+                                                       const V3 O, const unsigned long long tile_mask, const int depth, PointOf point_of, uint32_t& lit) {
     const uint32_t tid = threadIdx.x;
     const V3 lpos = b.lpos;  // (a value of its own: selected against a load below, b.lpos would be selected by address and keep b in memory)
     bool undecided = false;
@@ -391,84 +422,6 @@ __device__ __forceinline__ bool resolve_shadow_bundles(const SceneView& scg, con
         // (outside the seed table's window — points far out, at the horizon — the 397-step recurrence)
         if (b.soft && tid < nu) {
             V3 P, N;  // (N goes unused here: the accessor is inlined and its fetch of the normal falls away)
-            point_of(b.und[u0 + tid], P, N);
-            disk_sample_positions(scg, nullptr, b.seed_table, nullptr, P, depth, b.S, b.pos + static_cast<size_t>(tid) * 3 * b.S);
-        }
-        __syncthreads();
-        // ---- a lane per (undecided item, light sample)
-        count_item_rays(b.und + u0, nu, b.pairs, b.lit, [&](const uint32_t k, const uint32_t q) __attribute__((always_inline)) {
-            V3 P, N;
-            point_of(k, P, N);
-            const V3 target = b.soft ? ld3(b.pos + static_cast<size_t>(q) * 3) : lpos;
-            return !in_shadow_masked(sc, P, N, target, b.cand[k], b.ins[k]);
-        });
-    }
-    if (n_und) __syncthreads();  // the counts are complete
-    if (undecided) lit = b.lit[tid];
-    return undecided;
-}
-
-// ---- the resolver for a light given by value (mcrt.h, "light layers and bake under extra lights"): by-value twins of
-// disk_sample_positions, shadow_bundles and resolve_shadow_bundles, which read the scene header's light and stay as they are, so
-// the code of the kernels that call them does not move.
-// disk_sample_positions as the resolver calls it — no sample table, no table of all seeds — with light l in the header's place
-__device__ __forceinline__ void disk_sample_positions_at(const LightAt& l, const uint32_t* __restrict__ seed_table, const V3 P, const int depth, const int S,
-                                                         float* __restrict__ dst) {
-    MtShort rng;
-    const uint32_t seed = shadow_seed(P, depth);
-    const uint32_t slot = seed + kSeedWindowHalf;  // wraps: the window is centred on seed 0
-    if (seed_table && slot < kSeedWindow)
-        rng.seed_known(seed, seed_table[slot]);  // mt[397] of this seed, from the device's table
-    else
-        rng.seed(seed);  // the 397-step recurrence
-    const LightFrame frame = light_frame_at(l.pos, P);
-    for (int i = 0; i < S; ++i) {
-        const float d0 = rng.uniform();
-        const float d1 = rng.uniform();
-        const V3 t = light_sample_at(l, frame, d0, d1);
-        dst[3 * i + 0] = t.x;
-        dst[3 * i + 1] = t.y;
-        dst[3 * i + 2] = t.z;
-    }
-}
-__device__ __forceinline__ ShadowBundles shadow_bundles_at(const LightAt& l, const int samples, const int pass, const int decisions, const int inside_fast,
-                                                           const uint32_t* seed_table, unsigned long long* cand, unsigned long long* ins, uint32_t* lit,
-                                                           uint32_t* und, float* pos, int* wcnt) {
-    const bool soft = samples > 1 && !(l.radius < 1e-4f);
-    return ShadowBundles{l.pos, soft ? l.radius : 0.0f, soft, samples, soft ? static_cast<uint32_t>(samples) : 1u, static_cast<uint32_t>(pass),
-                         decisions != 0, inside_fast != 0, seed_table, cand, ins, lit, und, pos, wcnt};
-}
-// resolve_shadow_bundles for the bundles `b` of light l (shadow_bundles_at).  COLLECTIVE like it, with the same barriers: a loop
-// over the lights around it must have the same trip count in all 256 threads.  Behind it nothing of the area is read across
-// lanes, so the next light's call may write it at once.
-template <bool kPosed, class SV, class PointOf>
-__device__ __forceinline__ bool resolve_shadow_bundles_at(const SceneView& scg, const SV& sc, const ShadowBundles b, const LightAt& l, const bool active,
-                                                          const V3 O, const unsigned long long tile_mask, const int depth, PointOf point_of, uint32_t& lit) {
-    const uint32_t tid = threadIdx.x;
-    const V3 lpos = b.lpos;
-    bool undecided = false;
-    // ---- a lane per item: the whole-bundle decision
-    if (active) {
-        unsigned long long cand;
-        const int known = bundle_classify<kPosed>(scg, sc, O, lpos, b.R, static_cast<int>(b.pairs), b.decisions, cand);
-        cand &= tile_mask;
-        undecided = known < 0;
-        b.cand[tid] = cand;
-        b.ins[tid] = (undecided && b.inside_fast) ? origin_inside_boxes(sc, O, cand) : 0ull;
-        if (!undecided) lit = static_cast<uint32_t>(known);
-    }
-    b.lit[tid] = 0u;
-    int total = 0;
-    const int rank = block_rank(undecided, b.wcnt, total);
-    if (undecided) b.und[rank] = tid;
-    const uint32_t n_und = static_cast<uint32_t>(total);
-    if (n_und) __syncthreads();  // uniform
-    for (uint32_t u0 = 0; u0 < n_und; u0 += b.pass) {  // uniform
-        const uint32_t nu = min(b.pass, n_und - u0);
-        if (u0) __syncthreads();  // the previous pass's rays have read the positions
-        // ---- a lane per undecided item: its mt19937 stream and the S sample positions on light l's disk
-        if (b.soft && tid < nu) {
-            V3 P, N;
             point_of(b.und[u0 + tid], P, N);
             disk_sample_positions_at(l, b.seed_table, P, depth, b.S, b.pos + static_cast<size_t>(tid) * 3 * b.S);
         }

@@ -561,16 +561,11 @@ struct ShotFrame {
 // what the frames of one launch share: the frame's size and gradient (cfg) and the shot's settings
 struct ShotShape {
     mcrt_config cfg;
-    int page;  // MCRT_PAGE_*
+    int page;  // MCRT_PAGE_*; MCRT_PAGE_TRANSPARENT from the _ex entries alone
     float page_color[3];
     float shadow_strength, reflectivity, reflection_fade;
     float floor_occlusion;  // o, 0..1: read only where a frame has an occlusion plane
-};
-// and of the _ex kernels: page may be MCRT_PAGE_TRANSPARENT, and the shadow has a colour.  (A struct of its own: a larger
-// ShotShape would move the hidden arguments of the kernels that were there before, and so change their code.)
-struct ShotShapeEx {
-    ShotShape shot;
-    float shadow_color[3];  // C
+    float shadow_color[3];  // C: (0, 0, 0) from the plain and _occ entries
 };
 
 // ======== pipeline launches (render_kernels.hip) ========
@@ -641,13 +636,12 @@ hipError_t launch_light_multi(const ShadeLightsFrame& f, const ShadeShape& shape
 hipError_t launch_light_multi_batch(const ShadeLightsFrame* d_table, int n_frames, const ShadeShape& shape, int view, size_t max_dyn, hipStream_t stream);
 hipError_t launch_bake_multi(const BakeLightsFrame& f, const BakeShape& shape, int view, hipStream_t stream);
 hipError_t launch_bake_multi_batch(const BakeLightsFrame* d_table, int n_frames, const BakeShape& shape, int view, size_t max_dyn, hipStream_t stream);
-hipError_t launch_shot(const ShotFrame& f, const ShotShape& shape, hipStream_t stream);
+// The blend of every shot entry (include/mcrt.h, "studio shot" and "cut-out").  d_bounds: NULL, or 4 int32 per frame of the launch
+// (frame blockIdx.y at d_bounds + 4 * blockIdx.y) that already hold {width, height, 0, 0} in stream order
+// (launch_shot_bounds_init) — only with the transparent page.
+hipError_t launch_shot(const ShotFrame& f, const ShotShape& shape, int32_t* d_bounds, hipStream_t stream);
 // frames d_table[0..n_frames) (device memory, n_frames <= kLayersBatchMaxFrames), blockIdx.y = frame
-hipError_t launch_shot_batch(const ShotFrame* d_table, int n_frames, const ShotShape& shape, hipStream_t stream);
-// The blend of the _ex entries (include/mcrt.h, "cut-out").  d_bounds: NULL, or 4 int32 per frame of the launch (frame blockIdx.y at d_bounds + 4 * blockIdx.y) that already hold
-// {width, height, 0, 0} in stream order (launch_shot_bounds_init) — only with the transparent page.
-hipError_t launch_shot_ex(const ShotFrame& f, const ShotShapeEx& shape, int32_t* d_bounds, hipStream_t stream);
-hipError_t launch_shot_ex_batch(const ShotFrame* d_table, int n_frames, const ShotShapeEx& shape, int32_t* d_bounds, hipStream_t stream);
+hipError_t launch_shot_batch(const ShotFrame* d_table, int n_frames, const ShotShape& shape, int32_t* d_bounds, hipStream_t stream);
 // {width, height, 0, 0} into each of the n entries of d_bounds
 hipError_t launch_shot_bounds_init(int32_t* d_bounds, int n, int width, int height, hipStream_t stream);
 hipError_t launch_skin_paint(const SkinPaintFrame& f, const SkinPaintShape& shape, hipStream_t stream);

@@ -490,7 +490,7 @@ __device__ __forceinline__ void ground_body(const GroundFrame& __restrict__ f, c
     const V3 N = mk(0.0f, 1.0f, 0.0f);
     constexpr bool kPosed = kView != kViewLdsUnposed;
     GroundArea& area = *reinterpret_cast<GroundArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
-    const ShadowBundles sb = shadow_bundles(scg, sh.samples, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.cand, area.ins, area.count,
+    const ShadowBundles sb = shadow_bundles(header_light(scg), sh.samples, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.cand, area.ins, area.count,
                                             area.list, reinterpret_cast<float*>(&area + 1), s_wcnt);
     // four neighbouring pixels of a row per store: every tile row starts and ends on a four-pixel boundary of the plane
     const bool quad_rows = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0;
@@ -513,7 +513,7 @@ __device__ __forceinline__ void ground_body(const GroundFrame& __restrict__ f, c
         if (mask != 0ull) {  // uniform
             // ---- resolve_shadow_bundles: the pixel's point goes to LDS as P.x, P.z; the normal is the plane's
             if (gp.reached) area.pxz[tid] = make_float2(gp.P.x, gp.P.z);
-            undecided = resolve_shadow_bundles<kPosed>(scg, sc, sb, gp.reached, gp.P + N * 1e-3f, mask, 0,
+            undecided = resolve_shadow_bundles<kPosed>(scg, sc, sb, header_light(scg), gp.reached, gp.P + N * 1e-3f, mask, 0,
                                                        [&](const uint32_t k, V3& P, V3& Nk) __attribute__((always_inline)) {
                                                            const float2 xz = area.pxz[k];
                                                            P = mk(xz.x, g, xz.y), Nk = N;
@@ -1024,6 +1024,34 @@ __device__ __forceinline__ Hit pixel_hit(const SceneView& scg, const SV& sc, con
     const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
     return hit_scene(sc, camera_ray(scg, u, v, aspect), mesh_mask);
 }
+// The first phase of `shade`, `occlusion` and `shade_lights`, a lane per pixel: the pixel-centre ray's closest hit among the
+// tile's meshes; the hits are packed onto the block's first lanes as records in LDS — plane 0 the point, plane 1 the normal
+// and, where kColour, plane 2 the texel colour.  COLLECTIVE (the two barriers of block_rank: the records are read behind one
+// more): all 256 threads reach it under uniform control flow.
+struct PixelHits {
+    bool is_hit;  // this lane's pixel has a hit,
+    int rank;     // whose record this is
+    int n_hits;   // the workgroup's records
+    float alpha;  // the hit's texel alpha
+};
+template <bool kColour, class SV>
+__device__ __forceinline__ PixelHits pack_pixel_hits(const SceneView& scg, const SV& sc, const mcrt_config& cfg, const float aspect, const UnitPixel& up,
+                                                     const unsigned long long mask, float4* s_rec, int* s_wcnt) {
+    PixelHits ph{false, 0, 0, 0.0f};
+    Hit h;
+    if (up.valid) {
+        h = pixel_hit(scg, sc, cfg, aspect, up.px, up.py, mask);
+        ph.is_hit = h.hit;
+    }
+    ph.rank = block_rank(ph.is_hit, s_wcnt, ph.n_hits);
+    if (ph.is_hit) {
+        s_rec[ph.rank] = make_float4(h.p.x, h.p.y, h.p.z, 0.0f);
+        s_rec[kBlock + ph.rank] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
+        if constexpr (kColour) s_rec[2 * kBlock + ph.rank] = make_float4(h.tex.r, h.tex.g, h.tex.b, h.tex.a);
+        ph.alpha = h.tex.a;
+    }
+    return ph;
+}
 // resolve_shadow_bundles' accessor over records in LDS whose plane 0 holds the point and plane 1 the normal (`shade`, `bake_shade`):
 // computeSoftShadow takes the normal as it is (raw), shade()'s own test normalises it (shading.cpp:76-80)
 struct RecordPoint {
@@ -1050,7 +1078,7 @@ __device__ __forceinline__ void shade_body(const ShadeFrame& __restrict__ f, con
     ShadeArea& area = *reinterpret_cast<ShadeArea*>(s_dyn + scene_tables_lds_span(f.lds_face_entries, f.lds_alpha_words));
     float4* s_rec = area.rec;      // plane 0: hit point; 1: normal; 2: texel colour — then the hit's colour
     uint32_t* s_lit = area.sh.lit;  // lit counts — then the hit's visibility, bit-cast
-    const ShadowBundles sb = shadow_bundles(scg, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins, area.sh.lit, area.sh.und,
+    const ShadowBundles sb = shadow_bundles(header_light(scg), S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins, area.sh.lit, area.sh.und,
                                             reinterpret_cast<float*>(&area + 1), s_wcnt);
     const bool quads_vis = (cfg.width & 3) == 0 && (cfg.tile_size & 3) == 0 && (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
     const bool vec_direct = (reinterpret_cast<uintptr_t>(f.direct) & 15u) == 0;
@@ -1065,24 +1093,12 @@ __device__ __forceinline__ void shade_body(const ShadeFrame& __restrict__ f, con
         float vis = 1.0f;
         C4 col{0.0f, 0.0f, 0.0f, 0.0f};
         if (mask != 0ull) {  // uniform
-            // ---- a lane per pixel: the ray and its closest hit
-            bool is_hit = false;
-            Hit h;
-            if (up.valid) {
-                h = pixel_hit(scg, sc, cfg, aspect, up.px, up.py, mask);
-                is_hit = h.hit;
-            }
-            int n_hits = 0;
-            const int rank = block_rank(is_hit, s_wcnt, n_hits);
-            if (is_hit) {
-                s_rec[rank] = make_float4(h.p.x, h.p.y, h.p.z, 0.0f);
-                s_rec[kBlock + rank] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
-                s_rec[2 * kBlock + rank] = make_float4(h.tex.r, h.tex.g, h.tex.b, h.tex.a);
-            }
-            if (n_hits) {  // uniform
+            // ---- a lane per pixel: the ray and its closest hit, packed
+            const PixelHits ph = pack_pixel_hits<true>(scg, sc, cfg, aspect, up, mask, s_rec, s_wcnt);
+            if (ph.n_hits) {  // uniform
                 __syncthreads();
                 // ---- a lane per hit: its record, then resolve_shadow_bundles over its shadow rays (depth 0)
-                const bool mine = tid < n_hits;
+                const bool mine = tid < ph.n_hits;
                 Hit hit;
                 hit.hit = true;
                 uint32_t lit = 0u;
@@ -1092,18 +1108,18 @@ __device__ __forceinline__ void shade_body(const ShadeFrame& __restrict__ f, con
                     hit.p = mk(a.x, a.y, a.z), hit.n = mk(b.x, b.y, b.z), hit.tex = C4{c.x, c.y, c.z, c.w};
                     O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
                 }
-                resolve_shadow_bundles<kPosed>(scg, sc, sb, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
+                resolve_shadow_bundles<kPosed>(scg, sc, sb, header_light(scg), mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
                 // ---- a lane per hit: the visibility term and shade (raytracer.cpp:107-117)
                 if (mine) {
-                    const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    const float v = bundle_visibility(sb, lit);
                     const C4 c = shade(scg, hit, normalize(cam - hit.p), v);
                     s_lit[tid] = __float_as_uint(v);  // (entry and record tid are this lane's alone by now)
                     s_rec[2 * kBlock + tid] = make_float4(c.r, c.g, c.b, c.a);
                 }
                 __syncthreads();
-                if (is_hit) {
-                    const float4 c = s_rec[2 * kBlock + rank];
-                    vis = __uint_as_float(s_lit[rank]);
+                if (ph.is_hit) {
+                    const float4 c = s_rec[2 * kBlock + ph.rank];
+                    vis = __uint_as_float(s_lit[ph.rank]);
                     col = C4{c.x, c.y, c.z, c.w};
                 }
                 // (the next unit writes its records behind the two barriers of its block_rank)
@@ -1172,24 +1188,13 @@ __device__ __forceinline__ void occlusion_body(const ShadeFrame& __restrict__ f,
         stage_view_once<kView>(scg, f.lds_face_entries, f.lds_alpha_words, s_dyn, mask != 0ull, sc, staged);
         float occ = 1.0f;
         if (mask != 0ull) {  // uniform
-            // ---- a lane per pixel: the ray and its closest hit
-            bool is_hit = false;
-            Hit h;
-            if (up.valid) {
-                h = pixel_hit(scg, sc, cfg, aspect, up.px, up.py, mask);
-                is_hit = h.hit;
-            }
-            int n_hits = 0;
-            const int rank = block_rank(is_hit, s_wcnt, n_hits);
-            if (is_hit) {
-                s_rec[rank] = make_float4(h.p.x, h.p.y, h.p.z, 0.0f);
-                s_rec[kBlock + rank] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
-            }
-            if (n_hits) {  // uniform
+            // ---- a lane per pixel: the ray and its closest hit, packed
+            const PixelHits ph = pack_pixel_hits<false>(scg, sc, cfg, aspect, up, mask, s_rec, s_wcnt);
+            if (ph.n_hits) {  // uniform
                 __syncthreads();
                 // ---- a lane per hit: the meshes a ray of its hemisphere can meet (`ao`, step 1)
                 bool traced = false;
-                if (tid < n_hits) {
+                if (tid < ph.n_hits) {
                     const float4 a = s_rec[tid], b = s_rec[kBlock + tid];
                     const V3 P = mk(a.x, a.y, a.z), N = normalize(mk(b.x, b.y, b.z));
                     const unsigned long long cand = hemisphere_candidates<kPosed>(scg, P + N * 1e-3f, N, radius);
@@ -1207,7 +1212,7 @@ __device__ __forceinline__ void occlusion_body(const ShadeFrame& __restrict__ f,
                     s_val[k] = record_occlusion(sc, f.seed_table_full, s_rec, k, s_mask[k], sh.inside_fast != 0, radius, A);
                 }
                 __syncthreads();
-                if (is_hit) occ = s_val[rank];
+                if (ph.is_hit) occ = s_val[ph.rank];
                 // (the next unit writes its records behind the two barriers of its block_rank)
             }
         }
@@ -1348,6 +1353,36 @@ __device__ __forceinline__ BakeLane bake_lane(const BakeFrame& __restrict__ f, c
     }
     return b;
 }
+// The packing phase of the bake kernels, a lane per live texel: the live texels go onto the block's first lanes as records in
+// LDS (s_own; with `hit`, their colours into s_tex), then lane tid < n_live reads record tid back — the texel on its owner face
+// into t and, with `hit`, the colour and whether the owner mesh is an outer layer into *hit (nullptr: `bake_occlusion`, which
+// shades nothing).  Returns this lane's rank: the record of its texel, where that is live.
+// COLLECTIVE: the two barriers of block_rank and, where the workgroup has live texels, one more in front of the read.
+template <class SV>
+__device__ __forceinline__ int pack_live_texels(const SV& sc, const BakeLane& b, int4* s_own, float4* s_tex, int* s_wcnt, int& n_live, BakeTexel& t, Hit* hit) {
+    const int tid = threadIdx.x;
+    const int rank = block_rank(b.live, s_wcnt, n_live);
+    if (b.live) {
+        if (hit) s_tex[rank] = b.tex;
+        s_own[rank] = make_int4(b.t.code, b.t.ty * b.t.w + b.t.tx, b.t.w, b.t.h);
+    }
+    t = BakeTexel{-1, -1, -1, 0, 0};
+    if (n_live) {  // uniform
+        __syncthreads();
+        if (tid < n_live) {
+            const int4 o = s_own[tid];
+            t.code = o.x, t.w = o.z, t.h = o.w;
+            t.ty = o.y / o.z;
+            t.tx = o.y - t.ty * o.z;
+            if (hit) {
+                const float4 c = s_tex[tid];
+                hit->tex = C4{c.x, c.y, c.z, c.w};
+                hit->outer = (mesh_lane(sc, o.x >> 3).flags & MESH_OUTER) != 0;
+            }
+        }
+    }
+    return rank;
+}
 template <int kView>
 __device__ __forceinline__ void bake_shade_body(const BakeFrame& __restrict__ f, const BakeShape& __restrict__ sh) {
     extern __shared__ __align__(16) unsigned char s_dyn[];  // [scene tables][BakeShadeArea][positions: pass x S x 3 floats]
@@ -1364,7 +1399,7 @@ __device__ __forceinline__ void bake_shade_body(const BakeFrame& __restrict__ f,
     float4* s_tex = area.tex;       // the live texel's colour — then its mean colour
     int4* s_own = area.own;         // the live texel on its owner face: {mesh * 8 + face, ty * w + tx, w, h}
     uint32_t* s_lit = area.sh.lit;  // lit counts — then the texel's mean visibility, bit-cast
-    const ShadowBundles sb = shadow_bundles(scg, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins, area.sh.lit, area.sh.und,
+    const ShadowBundles sb = shadow_bundles(header_light(scg), S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins, area.sh.lit, area.sh.und,
                                             reinterpret_cast<float*>(&area + 1), s_wcnt);
     const bool quads_vis = (reinterpret_cast<uintptr_t>(f.visibility) & 15u) == 0;
     const bool vec_direct = (reinterpret_cast<uintptr_t>(f.direct) & 15u) == 0;
@@ -1378,28 +1413,14 @@ __device__ __forceinline__ void bake_shade_body(const BakeFrame& __restrict__ f,
         float vis = 1.0f;
         C4 col{0.0f, 0.0f, 0.0f, 0.0f};
         int n_live = 0;
-        const int rank = block_rank(b.live, s_wcnt, n_live);
-        if (b.live) {
-            s_tex[rank] = b.tex;
-            s_own[rank] = make_int4(b.t.code, b.t.ty * b.t.w + b.t.tx, b.t.w, b.t.h);
-        }
+        BakeTexel t;
+        Hit hit;
+        hit.hit = true;
+        const int rank = pack_live_texels(sc, b, s_own, s_tex, s_wcnt, n_live, t, &hit);
         if (n_live) {  // uniform
-            __syncthreads();
             const bool mine = tid < n_live;
-            BakeTexel t{-1, -1, -1, 0, 0};
-            Hit hit;
-            hit.hit = true;
             float vsum = 0.0f;
             C4 csum{0.0f, 0.0f, 0.0f, 0.0f};
-            if (mine) {
-                const int4 o = s_own[tid];
-                const float4 c = s_tex[tid];
-                t.code = o.x, t.w = o.z, t.h = o.w;
-                t.ty = o.y / o.z;
-                t.tx = o.y - t.ty * o.z;
-                hit.tex = C4{c.x, c.y, c.z, c.w};
-                hit.outer = (mesh_lane(sc, o.x >> 3).flags & MESH_OUTER) != 0;
-            }
             for (int sub = 0; sub < q * q; ++sub) {  // uniform: j outer, i inner
                 const int sj = sub / q, si = sub - sj * q;
                 // ---- a lane per live texel: the sub-sample's point, then resolve_shadow_bundles over its shadow rays (depth 0)
@@ -1411,10 +1432,10 @@ __device__ __forceinline__ void bake_shade_body(const BakeFrame& __restrict__ f,
                     s_rec[kBlock + tid] = make_float4(hit.n.x, hit.n.y, hit.n.z, 0.0f);
                     O = hit.p + (raw_normal ? hit.n : normalize(hit.n)) * 1e-3f;
                 }
-                resolve_shadow_bundles<kPosed>(scg, sc, sb, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
+                resolve_shadow_bundles<kPosed>(scg, sc, sb, header_light(scg), mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
                 // ---- a lane per live texel: the visibility term and shade, added in the defined order
                 if (mine) {
-                    const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
+                    const float v = bundle_visibility(sb, lit);
                     const C4 c = shade(scg, hit, hit.n, v);
                     if (sub == 0) {
                         vsum = v, csum = c;
@@ -1481,19 +1502,11 @@ __device__ __forceinline__ void bake_occlusion_body(const BakeFrame& __restrict_
         const BakeLane b = bake_lane(f, scg, sc, unit, tid, sh.geometry != 0);
         float occ = 1.0f;
         int n_live = 0;
-        const int rank = block_rank(b.live, s_wcnt, n_live);
-        if (b.live) s_own[rank] = make_int4(b.t.code, b.t.ty * b.t.w + b.t.tx, b.t.w, b.t.h);
+        BakeTexel t;
+        const int rank = pack_live_texels(sc, b, s_own, nullptr, s_wcnt, n_live, t, nullptr);
         if (n_live) {  // uniform
-            __syncthreads();
             const bool mine = tid < n_live;
-            BakeTexel t{-1, -1, -1, 0, 0};
             float sum = 0.0f;
-            if (mine) {
-                const int4 o = s_own[tid];
-                t.code = o.x, t.w = o.z, t.h = o.w;
-                t.ty = o.y / o.z;
-                t.tx = o.y - t.ty * o.z;
-            }
             for (int sub = 0; sub < q * q; ++sub) {  // uniform: j outer, i inner
                 const int sj = sub / q, si = sub - sj * q;
                 // ---- a lane per live texel: the sub-sample's point and the meshes a ray of its hemisphere can meet (`ao`, step 1)
@@ -1545,12 +1558,13 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void bake_occlusion_batch_ker
 
 // ---------------------------------------------------------------------------------------------
 // light layers and bake under extra lights (kernels.h: ShadeLightsFrame, BakeLightsFrame; include/mcrt.h, "light layers and bake
-// under extra lights"): `shade` and `bake_shade` with the shadow resolution and shade() once per light of the frame's LightSet —
-// light 0 the header's, through shade(); light k >= 1 through shade_at(light k, ambient 0) — on the hit's ONE shadow seed:
-// every light's call seeds its engine from the same (point, depth), so all lights see the same draws.  Kernels of their own:
-// shade_body and bake_shade_body stay as they are.  The phases are theirs; what differs:
+// under extra lights"): `shade` and `bake_shade` with the shadow resolution and the shading once per light of the frame's LightSet —
+// shade_at(frame_light(k), ambient .20 for light 0, the header's, and 0 for the others) — on the hit's ONE shadow seed: every
+// light's call seeds its engine from the same (point, depth), so all lights see the same draws.  The packing phases
+// (pack_pixel_hits, pack_live_texels), the resolver and shade_at are the single-light bodies'; the bodies are kernels of their own
+// because K = 0 through them is slower than `shade` / `bake_shade` (profiles/light_multi).  What differs:
 //   the loop over the lights k = 0 .. K is uniform per workgroup (K from the frame record) and runs around the COLLECTIVE
-//   resolver (kernel_common.h: resolve_shadow_bundles_at), whose area it reuses from light to light: behind the resolver nothing
+//   resolver (kernel_common.h: resolve_shadow_bundles), whose area it reuses from light to light: behind the resolver nothing
 //   of the area is read across lanes, and the LDS a launch takes does not grow with K;
 //   `shade_lights`: light k's visibility and colour return through LDS per light (plane 2 of the record, {r, g, b, vis}: the texel
 //   colour it held is in the hit lane's registers by then, and the next light's write lies behind its resolver's barriers) and
@@ -1560,19 +1574,10 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void bake_occlusion_batch_ker
 //   a plane of a light the frame lacks (k > K) takes the miss constants.
 // ---------------------------------------------------------------------------------------------
 // light k of a frame, k uniform: the header's, or entry k - 1 of the record's set (a scalar load, not a select)
-__device__ __forceinline__ LightAt frame_light(const FlatHeader* __restrict__ h, const LightSet& ls, const int k) {
-    LightAt l;
-    if (k == 0) {
-        l.pos = ld3(h->light_pos);
-        l.radius = h->light_radius;
-        l.col[0] = h->light_color[0], l.col[1] = h->light_color[1], l.col[2] = h->light_color[2];
-    } else {
-        const mcrt_light_source& e = ls.extra[k - 1];
-        l.pos = mk(e.position[0], e.position[1], e.position[2]);
-        l.radius = e.radius;
-        l.col[0] = e.color[0], l.col[1] = e.color[1], l.col[2] = e.color[2];
-    }
-    return l;
+__device__ __forceinline__ LightAt frame_light(const SceneView& scg, const LightSet& ls, const int k) {
+    if (k == 0) return light_value(header_light(scg));
+    const mcrt_light_source& e = ls.extra[k - 1];
+    return LightAt{mk(e.position[0], e.position[1], e.position[2]), e.radius, {e.color[0], e.color[1], e.color[2]}};
 }
 __device__ __forceinline__ void store_rgba(float* __restrict__ plane, const size_t idx, const float4 val) {
     if ((reinterpret_cast<uintptr_t>(plane) & 15u) == 0) {
@@ -1614,23 +1619,13 @@ __device__ __forceinline__ void shade_lights_body(const ShadeLightsFrame& __rest
         hit.hit = true;
         V3 O = mk(0, 0, 0), view = mk(0, 0, 0);
         if (mask != 0ull) {  // uniform
-            Hit h;
-            if (up.valid) {
-                h = pixel_hit(scg, sc, cfg, aspect, up.px, up.py, mask);
-                is_hit = h.hit;
-            }
-            int n_hits = 0;
-            rank = block_rank(is_hit, s_wcnt, n_hits);
-            if (is_hit) {
-                s_rec[rank] = make_float4(h.p.x, h.p.y, h.p.z, 0.0f);
-                s_rec[kBlock + rank] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
-                s_rec[2 * kBlock + rank] = make_float4(h.tex.r, h.tex.g, h.tex.b, h.tex.a);
-                alpha = sclamp(h.tex.a, 0.0f, 1.0f);
-            }
-            if (n_hits) {  // uniform
+            const PixelHits ph = pack_pixel_hits<true>(scg, sc, cfg, aspect, up, mask, s_rec, s_wcnt);
+            is_hit = ph.is_hit, rank = ph.rank;
+            if (is_hit) alpha = sclamp(ph.alpha, 0.0f, 1.0f);
+            if (ph.n_hits) {  // uniform
                 __syncthreads();
                 shaded = true;
-                mine = tid < n_hits;
+                mine = tid < ph.n_hits;
                 if (mine) {
                     const float4 a = s_rec[tid], b = s_rec[kBlock + tid], c = s_rec[2 * kBlock + tid];
                     hit.p = mk(a.x, a.y, a.z), hit.n = mk(b.x, b.y, b.z), hit.tex = C4{c.x, c.y, c.z, c.w};
@@ -1646,16 +1641,16 @@ __device__ __forceinline__ void shade_lights_body(const ShadeLightsFrame& __rest
             float vis = 1.0f;
             C4 col{0.0f, 0.0f, 0.0f, 0.0f};
             if (shaded && k <= K) {  // uniform: the resolver inside is collective
-                const LightAt l = frame_light(scg.hdr, f.lights, k);
-                const ShadowBundles sb = shadow_bundles_at(l, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins,
+                const LightAt l = frame_light(scg, f.lights, k);
+                const ShadowBundles sb = shadow_bundles(l, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins,
                                                            area.sh.lit, area.sh.und, reinterpret_cast<float*>(&area + 1), s_wcnt);
-                // ---- resolve_shadow_bundles_at over the hits' shadow rays towards light k (depth 0)
+                // ---- resolve_shadow_bundles over the hits' shadow rays towards light k (depth 0)
                 uint32_t lit = 0u;
-                resolve_shadow_bundles_at<kPosed>(scg, sc, sb, l, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
+                resolve_shadow_bundles<kPosed>(scg, sc, sb, l, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
                 // ---- a lane per hit: light k's visibility term and shade
                 if (mine) {
-                    const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
-                    const C4 c = k == 0 ? shade(scg, hit, view, v) : shade_at(l, hit, view, 0.0f, v);
+                    const float v = bundle_visibility(sb, lit);
+                    const C4 c = shade_at(l, hit, view, k == 0 ? 0.20f : 0.0f, v);
                     s_rec[2 * kBlock + tid] = make_float4(c.r, c.g, c.b, v);  // (record tid is this lane's alone; its colour is in `hit`)
                 }
                 __syncthreads();
@@ -1713,11 +1708,10 @@ __device__ __forceinline__ void bake_shade_lights_body(const BakeLightsFrame& __
         const BakeLane b = bake_lane(f, scg, sc, unit, tid, sh.geometry != 0);
         if (!sh.rays) continue;  // uniform: position / normal alone
         int n_live = 0;
-        const int rank = block_rank(b.live, s_wcnt, n_live);
-        if (b.live) {
-            s_tex[rank] = b.tex;
-            s_own[rank] = make_int4(b.t.code, b.t.ty * b.t.w + b.t.tx, b.t.w, b.t.h);
-        }
+        BakeTexel t;
+        Hit hit;
+        hit.hit = true;
+        const int rank = pack_live_texels(sc, b, s_own, s_tex, s_wcnt, n_live, t, &hit);
         const bool mine = tid < n_live;
         float vsum[kMaxLights];  // (addressed by unrolled selects alone: registers)
         C4 csum[kMaxLights];
@@ -1725,19 +1719,6 @@ __device__ __forceinline__ void bake_shade_lights_body(const BakeLightsFrame& __
 #pragma unroll
         for (int j = 0; j < kMaxLights; ++j) vsum[j] = 0.0f, csum[j] = C4{0.0f, 0.0f, 0.0f, 0.0f};
         if (n_live) {  // uniform
-            __syncthreads();
-            BakeTexel t{-1, -1, -1, 0, 0};
-            Hit hit;
-            hit.hit = true;
-            if (mine) {
-                const int4 o = s_own[tid];
-                const float4 c = s_tex[tid];
-                t.code = o.x, t.w = o.z, t.h = o.w;
-                t.ty = o.y / o.z;
-                t.tx = o.y - t.ty * o.z;
-                hit.tex = C4{c.x, c.y, c.z, c.w};
-                hit.outer = (mesh_lane(sc, o.x >> 3).flags & MESH_OUTER) != 0;
-            }
             for (int sub = 0; sub < q * q; ++sub) {  // uniform: j outer, i inner
                 const int sj = sub / q, si = sub - sj * q;
                 // ---- a lane per live texel: the sub-sample's point
@@ -1752,15 +1733,15 @@ __device__ __forceinline__ void bake_shade_lights_body(const BakeLightsFrame& __
                 // previous sub-sample's last resolver has left nothing to be read)
                 C4 comb{0.0f, 0.0f, 0.0f, 0.0f};
                 for (int k = 0; k <= K; ++k) {  // uniform: the resolver inside is collective
-                    const LightAt l = frame_light(scg.hdr, f.lights, k);
-                    const ShadowBundles sb = shadow_bundles_at(l, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins,
+                    const LightAt l = frame_light(scg, f.lights, k);
+                    const ShadowBundles sb = shadow_bundles(l, S, sh.pass, sh.bundle_decisions, sh.inside_fast, f.seed_table, area.sh.cand, area.sh.ins,
                                                                area.sh.lit, area.sh.und, reinterpret_cast<float*>(&area + 1), s_wcnt);
                     uint32_t lit = 0u;
-                    resolve_shadow_bundles_at<kPosed>(scg, sc, sb, l, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
+                    resolve_shadow_bundles<kPosed>(scg, sc, sb, l, mine, O, ~0ull, 0, RecordPoint{s_rec, raw_normal}, lit);
                     // ---- a lane per live texel: light k's visibility term and shade, added in the defined order
                     if (mine) {
-                        const float v = sb.soft ? static_cast<float>(lit) / static_cast<float>(S) : (lit ? 1.0f : 0.0f);
-                        const C4 c = k == 0 ? shade(scg, hit, hit.n, v) : shade_at(l, hit, hit.n, 0.0f, v);
+                        const float v = bundle_visibility(sb, lit);
+                        const C4 c = shade_at(l, hit, hit.n, k == 0 ? 0.20f : 0.0f, v);
                         comb = k == 0 ? c : C4{comb.r + c.r, comb.g + c.g, comb.b + c.b, comb.a};
 #pragma unroll
                         for (int j = 0; j < kMaxLights; ++j)
@@ -1849,86 +1830,10 @@ __global__ __launch_bounds__(kBlock, kGroundWaves) void bake_shade_lights_batch_
 //                                  of RGBA8 (byte stores for a plane off a 4-byte boundary)
 // At most 44 B read and 20 B written per pixel.  The arithmetic is the header's, in its order, one rounding per operation; an
 // absent input enters with its miss constant (visibility 1, reflection (0,0,0,0)) through the same operations, which is why a
-// shot that skips a pass equals one that ran it.
-// ---------------------------------------------------------------------------------------------
-struct ShotPage {  // what rt::background reads of a scene view
-    const FlatHeader* hdr;
-};
-__device__ __forceinline__ float4 load_rgba(const float* __restrict__ plane, const size_t i, const bool aligned) {
-    if (aligned) return reinterpret_cast<const float4*>(plane)[i];
-    const float* p = plane + 4 * i;
-    return make_float4(p[0], p[1], p[2], p[3]);
-}
-__device__ __forceinline__ void shot_body(const ShotFrame& __restrict__ f, const ShotShape& __restrict__ sh) {
-    const mcrt_config& cfg = sh.cfg;
-    const unsigned width = static_cast<unsigned>(cfg.width);
-    const unsigned n_pixels = width * static_cast<unsigned>(cfg.height);  // (the host refuses frames of 2^31 pixels and more)
-    const bool fig16 = (reinterpret_cast<uintptr_t>(f.figure) & 15u) == 0;
-    const bool ref16 = (reinterpret_cast<uintptr_t>(f.reflection) & 15u) == 0;
-    const bool out16 = (reinterpret_cast<uintptr_t>(f.out) & 15u) == 0;
-    const bool out8_4 = (reinterpret_cast<uintptr_t>(f.out8) & 3u) == 0;
-    const bool page_reference = sh.page == MCRT_PAGE_REFERENCE;
-    const ShotPage scene{reinterpret_cast<const FlatHeader*>(f.scene)};
-    const UDiv by_width(width);
-    const float s = sh.shadow_strength, k = sh.reflectivity, fade = sh.reflection_fade;
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n_pixels; i += gridDim.x * kBlock) {
-        const float4 F = load_rgba(f.figure, i, fig16);
-        const float vis = f.visibility ? f.visibility[i] : 1.0f;
-        const float4 R = f.reflection ? load_rgba(f.reflection, i, ref16) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float pr = sh.page_color[0], pg = sh.page_color[1], pb = sh.page_color[2];
-        if (page_reference) {
-            const unsigned py = by_width.div(i), px = i - py * width;
-            const float u = (static_cast<float>(px) + 0.5f) / static_cast<float>(cfg.width);
-            const float v = (static_cast<float>(py) + 0.5f) / static_cast<float>(cfg.height);
-            const C4 c = background(scene, cfg, u, v);
-            pr = c.r, pg = c.g, pb = c.b;
-        }
-        const float shade = s * (1.0f - vis);
-        float fd = 1.0f;
-        if (fade > 0.0f) {
-            const float dR = (f.reflection && f.distance) ? f.distance[i] : kFltMax;
-            fd = sclamp(1.0f - dR / fade, 0.0f, 1.0f);
-        }
-        const float ar = (k * R.w) * fd;
-        float keep = 1.0f - shade;
-        if (f.occlusion) keep = keep * (1.0f - sh.floor_occlusion * (1.0f - f.occlusion[i]));  // absent: oc = +0, and x * 1.0f is x
-        keep = keep * (1.0f - ar);
-        const float under = 1.0f - F.w;
-        float4 o;
-        o.x = F.x * F.w + (pr * keep + R.x * ar) * under;
-        o.y = F.y * F.w + (pg * keep + R.y * ar) * under;
-        o.z = F.z * F.w + (pb * keep + R.z * ar) * under;
-        o.w = 1.0f;
-        if (f.out) {
-            if (out16) {
-                reinterpret_cast<float4*>(f.out)[i] = o;
-            } else {
-                float* p = f.out + 4 * static_cast<size_t>(i);
-                p[0] = o.x, p[1] = o.y, p[2] = o.z, p[3] = o.w;
-            }
-        }
-        if (f.out8) {
-            const uchar4 q = quantize_pixel(o);
-            if (out8_4) {
-                reinterpret_cast<uchar4*>(f.out8)[i] = q;
-            } else {
-                uint8_t* p = f.out8 + 4 * static_cast<size_t>(i);
-                p[0] = q.x, p[1] = q.y, p[2] = q.z, p[3] = q.w;
-            }
-        }
-    }
-}
-__global__ __launch_bounds__(kBlock) void shot_kernel(const ShotFrame f, const ShotShape sh) { shot_body(f, sh); }
-using ShotTable = const __attribute__((address_space(4))) ShotFrame*;
-__global__ __launch_bounds__(kBlock) void shot_batch_kernel(ShotTable table, const ShotShape sh) {
-    shot_body(*(const ShotFrame*)(table + blockIdx.y), sh);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The blend of the _ex entries (include/mcrt.h, "cut-out"): a body of its own beside shot_body, so that the kernels above
-// keep their code.  The same planes, accesses and grid; new are
+// shot that skips a pass equals one that ran it.  One body for every entry family (include/mcrt.h, "cut-out"); beyond the
+// opaque blend of the plain and _occ entries, which reach it with C = 0 and no bounds, it has
 //   C          the shadow's colour with the weight dk = (1 - lit) * (1 - ar).  Where all of C is 0 — uniform per launch —
-//              the term is not formed, and an opaque page then takes shot_body's operations one by one
+//              the term is not formed
 //   kCutout    the transparent page: the floor is a layer of alpha af = 1 - keep under the figure; af == 0 hands F through
 //              untouched, otherwise one division per channel un-premultiplies the sum.  The page is not evaluated
 //   bounds     (kCutout only, NULL: none of it runs) per lane the running box of its pixels with out.a > 0 over its trips,
@@ -1938,9 +1843,17 @@ __global__ __launch_bounds__(kBlock) void shot_batch_kernel(ShotTable table, con
 //              the workgroups take the frame's chunks from the outside in — 0, last, 1, last but one, ... —: the first ones
 //              that see content set the top and the bottom, and the later ones find their box inside the entry
 // ---------------------------------------------------------------------------------------------
+struct ShotPage {  // what rt::background reads of a scene view
+    const FlatHeader* hdr;
+};
+__device__ __forceinline__ float4 load_rgba(const float* __restrict__ plane, const size_t i, const bool aligned) {
+    if (aligned) return reinterpret_cast<const float4*>(plane)[i];
+    const float* p = plane + 4 * i;
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+using ShotTable = const __attribute__((address_space(4))) ShotFrame*;
 template <bool kCutout>
-__device__ __forceinline__ void shot_ex_body(const ShotFrame& __restrict__ f, const ShotShapeEx& __restrict__ ex, int32_t* __restrict__ bounds) {
-    const ShotShape& sh = ex.shot;
+__device__ __forceinline__ void shot_body(const ShotFrame& __restrict__ f, const ShotShape& __restrict__ sh, int32_t* __restrict__ bounds) {
     const mcrt_config& cfg = sh.cfg;
     const unsigned width = static_cast<unsigned>(cfg.width);
     const unsigned n_pixels = width * static_cast<unsigned>(cfg.height);  // (the host refuses frames of 2^31 pixels and more)
@@ -1952,7 +1865,7 @@ __device__ __forceinline__ void shot_ex_body(const ShotFrame& __restrict__ f, co
     const ShotPage scene{reinterpret_cast<const FlatHeader*>(f.scene)};
     const UDiv by_width(width);
     const float s = sh.shadow_strength, k = sh.reflectivity, fade = sh.reflection_fade;
-    const float cr = ex.shadow_color[0], cg = ex.shadow_color[1], cb = ex.shadow_color[2];
+    const float cr = sh.shadow_color[0], cg = sh.shadow_color[1], cb = sh.shadow_color[2];
     const bool colored = !(cr == 0.0f && cg == 0.0f && cb == 0.0f);
     int x0 = cfg.width, y0 = cfg.height, x1 = 0, y1 = 0;  // this lane's box: the identities
     unsigned chunk = blockIdx.x;
@@ -2068,12 +1981,12 @@ __device__ __forceinline__ void shot_ex_body(const ShotFrame& __restrict__ f, co
     }
 }
 template <bool kCutout>
-__global__ __launch_bounds__(kBlock) void shot_ex_kernel(const ShotFrame f, const ShotShapeEx sh, int32_t* bounds) {
-    shot_ex_body<kCutout>(f, sh, bounds);
+__global__ __launch_bounds__(kBlock) void shot_kernel(const ShotFrame f, const ShotShape sh, int32_t* bounds) {
+    shot_body<kCutout>(f, sh, bounds);
 }
 template <bool kCutout>
-__global__ __launch_bounds__(kBlock) void shot_ex_batch_kernel(ShotTable table, const ShotShapeEx sh, int32_t* bounds) {
-    shot_ex_body<kCutout>(*(const ShotFrame*)(table + blockIdx.y), sh, bounds ? bounds + 4 * blockIdx.y : nullptr);
+__global__ __launch_bounds__(kBlock) void shot_batch_kernel(ShotTable table, const ShotShape sh, int32_t* bounds) {
+    shot_body<kCutout>(*(const ShotFrame*)(table + blockIdx.y), sh, bounds ? bounds + 4 * blockIdx.y : nullptr);
 }
 __global__ __launch_bounds__(kBlock) void shot_bounds_init_kernel(int32_t* bounds, int n, int width, int height) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;  // a lane per word: the entries need 4-byte alignment only
@@ -2231,50 +2144,36 @@ static unsigned shot_grid(const ShotShape& sh) {
     const long long groups = (px + kBlock - 1) / kBlock;
     return static_cast<unsigned>(groups < kLayersGrid ? groups : kLayersGrid);
 }
-static bool shot_shape_ok(const ShotShape& sh) {
-    return sh.cfg.width > 0 && sh.cfg.height > 0 && static_cast<long long>(sh.cfg.width) * sh.cfg.height < (1ll << 31);
-}
-hipError_t launch_shot(const ShotFrame& f, const ShotShape& shape, hipStream_t stream) {
-    if (!shot_shape_ok(shape) || !f.figure || (!f.out && !f.out8)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(shot_kernel, dim3(shot_grid(shape)), dim3(kBlock), 0, stream, f, shape);
-    return hipGetLastError();
-}
-hipError_t launch_shot_batch(const ShotFrame* d_table, int n_frames, const ShotShape& shape, hipStream_t stream) {
-    if (n_frames <= 0) return hipSuccess;
-    if (!shot_shape_ok(shape) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(shot_batch_kernel, dim3(shot_grid(shape), static_cast<unsigned>(n_frames)), dim3(kBlock), 0, stream, ShotTable(d_table), shape);
-    return hipGetLastError();
-}
 // With bounds every workgroup that sees content ends on the frame's entry, and the atomics of one entry queue up.  So a launch
 // with bounds takes no more workgroups than the chip holds at once (256 CUs x 8 of these workgroups), shared among its frames:
 // fewer, longer workgroups — the lanes take more trips — and as many atomics fewer.
 constexpr unsigned kBoundsGroups = 2048;
-static unsigned shot_ex_grid(const ShotShape& sh, const int32_t* d_bounds, int n_frames) {
+static unsigned shot_bounds_grid(const ShotShape& sh, const int32_t* d_bounds, int n_frames) {
     const unsigned groups = shot_grid(sh);
     if (!d_bounds) return groups;
     const unsigned share = kBoundsGroups / static_cast<unsigned>(n_frames);
     return share < 1u ? 1u : share < groups ? share : groups;
 }
-static bool shot_ex_shape_ok(const ShotShapeEx& ex, const int32_t* d_bounds) {  // bounds come with the cut-out alone
-    const ShotShape& sh = ex.shot;
-    return shot_shape_ok(sh) && sh.page >= MCRT_PAGE_COLOR && sh.page <= MCRT_PAGE_TRANSPARENT && (!d_bounds || sh.page == MCRT_PAGE_TRANSPARENT);
+static bool shot_shape_ok(const ShotShape& sh, const int32_t* d_bounds) {  // bounds come with the cut-out alone
+    return sh.cfg.width > 0 && sh.cfg.height > 0 && static_cast<long long>(sh.cfg.width) * sh.cfg.height < (1ll << 31) && sh.page >= MCRT_PAGE_COLOR &&
+           sh.page <= MCRT_PAGE_TRANSPARENT && (!d_bounds || sh.page == MCRT_PAGE_TRANSPARENT);
 }
-hipError_t launch_shot_ex(const ShotFrame& f, const ShotShapeEx& shape, int32_t* d_bounds, hipStream_t stream) {
-    if (!shot_ex_shape_ok(shape, d_bounds) || !f.figure || (!f.out && !f.out8)) return hipErrorInvalidValue;
-    if (shape.shot.page == MCRT_PAGE_TRANSPARENT)
-        hipLaunchKernelGGL(shot_ex_kernel<true>, dim3(shot_ex_grid(shape.shot, d_bounds, 1)), dim3(kBlock), 0, stream, f, shape, d_bounds);
+hipError_t launch_shot(const ShotFrame& f, const ShotShape& shape, int32_t* d_bounds, hipStream_t stream) {
+    if (!shot_shape_ok(shape, d_bounds) || !f.figure || (!f.out && !f.out8)) return hipErrorInvalidValue;
+    if (shape.page == MCRT_PAGE_TRANSPARENT)
+        hipLaunchKernelGGL(shot_kernel<true>, dim3(shot_bounds_grid(shape, d_bounds, 1)), dim3(kBlock), 0, stream, f, shape, d_bounds);
     else
-        hipLaunchKernelGGL(shot_ex_kernel<false>, dim3(shot_grid(shape.shot)), dim3(kBlock), 0, stream, f, shape, d_bounds);
+        hipLaunchKernelGGL(shot_kernel<false>, dim3(shot_grid(shape)), dim3(kBlock), 0, stream, f, shape, d_bounds);
     return hipGetLastError();
 }
-hipError_t launch_shot_ex_batch(const ShotFrame* d_table, int n_frames, const ShotShapeEx& shape, int32_t* d_bounds, hipStream_t stream) {
+hipError_t launch_shot_batch(const ShotFrame* d_table, int n_frames, const ShotShape& shape, int32_t* d_bounds, hipStream_t stream) {
     if (n_frames <= 0) return hipSuccess;
-    if (!shot_ex_shape_ok(shape, d_bounds) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
-    const dim3 grid(shot_ex_grid(shape.shot, d_bounds, n_frames), static_cast<unsigned>(n_frames));
-    if (shape.shot.page == MCRT_PAGE_TRANSPARENT)
-        hipLaunchKernelGGL(shot_ex_batch_kernel<true>, grid, dim3(kBlock), 0, stream, ShotTable(d_table), shape, d_bounds);
+    if (!shot_shape_ok(shape, d_bounds) || n_frames > kLayersBatchMaxFrames) return hipErrorInvalidValue;
+    const dim3 grid(shot_bounds_grid(shape, d_bounds, n_frames), static_cast<unsigned>(n_frames));
+    if (shape.page == MCRT_PAGE_TRANSPARENT)
+        hipLaunchKernelGGL(shot_batch_kernel<true>, grid, dim3(kBlock), 0, stream, ShotTable(d_table), shape, d_bounds);
     else
-        hipLaunchKernelGGL(shot_ex_batch_kernel<false>, grid, dim3(kBlock), 0, stream, ShotTable(d_table), shape, d_bounds);
+        hipLaunchKernelGGL(shot_batch_kernel<false>, grid, dim3(kBlock), 0, stream, ShotTable(d_table), shape, d_bounds);
     return hipGetLastError();
 }
 hipError_t launch_shot_bounds_init(int32_t* d_bounds, int n, int width, int height, hipStream_t stream) {

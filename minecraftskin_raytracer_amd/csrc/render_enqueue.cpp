@@ -514,40 +514,28 @@ int bake_frame_of(const mcrt_scene* s, const mcrt_bake_planes& out, size_t index
 }
 
 // and for the two passes under extra lights (mcrt_render_light_multi_device, mcrt_bake_light_multi_device & co): the base record
-// without its light planes — the occlusion plane travels in a ShadeFrame / BakeFrame of its own —, the handle's lights BY VALUE
-// and the planes per light
-int shade_lights_frame_of(const mcrt_scene* s, const mcrt_light_planes_multi& out, size_t index, size_t stride, ShadeLightsFrame& f) {
-    std::memset(&f, 0, sizeof f);
-    const size_t off = index * stride;
-    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
-    f.seed_table = s->seed_table;
-    f.seed_table_full = s->seed_table_full;
+// (shade_frame_of / bake_frame_of) without its light planes — the occlusion plane travels in a ShadeFrame / BakeFrame of its
+// own —, then the handle's lights BY VALUE and the planes per light
+template <class Frame, class Planes>
+void lights_of_frame(const mcrt_scene* s, const Planes& out, size_t off, Frame& f) {
     f.lights = s->extra;
     for (int k = 0; k < kMaxLights; ++k) {
         f.vis[k] = out.visibility[k] ? out.visibility[k] + off : nullptr;
         f.dir[k] = out.direct[k] ? out.direct[k] + off * 4 : nullptr;
     }
     f.combined = out.combined ? out.combined + off * 4 : nullptr;
-    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
+}
+int shade_lights_frame_of(const mcrt_scene* s, const mcrt_light_planes_multi& out, size_t index, size_t stride, ShadeLightsFrame& f) {
+    std::memset(&f, 0, sizeof f);
+    const int view = shade_frame_of(s, mcrt_light_planes{nullptr, nullptr, nullptr}, index, stride, f);
+    lights_of_frame(s, out, index * stride, f);
+    return view;
 }
 int bake_lights_frame_of(const mcrt_scene* s, const mcrt_bake_planes_multi& out, size_t index, size_t stride, BakeLightsFrame& f) {
     std::memset(&f, 0, sizeof f);
-    const size_t off = index * stride;
-    f.scene = static_cast<const uint8_t*>(s->blob.ptr);
-    f.faces = reinterpret_cast<const BakeFace*>(static_cast<const uint8_t*>(s->blob.ptr) + s->bake_faces_offset);
-    f.n_faces = s->bake_n_faces;
-    f.n_texels = s->n_texels;
-    f.position = out.position ? reinterpret_cast<float4*>(out.position + off * 4) : nullptr;
-    f.normal = out.normal ? reinterpret_cast<float4*>(out.normal + off * 4) : nullptr;
-    f.seed_table = s->seed_table;
-    f.seed_table_full = s->seed_table_full;
-    f.lights = s->extra;
-    for (int k = 0; k < kMaxLights; ++k) {
-        f.vis[k] = out.visibility[k] ? out.visibility[k] + off : nullptr;
-        f.dir[k] = out.direct[k] ? out.direct[k] + off * 4 : nullptr;
-    }
-    f.combined = out.combined ? out.combined + off * 4 : nullptr;
-    return view_of_frame(f, s->alpha_words, s->n_meshes, s->posed);
+    const int view = bake_frame_of(s, mcrt_bake_planes{out.position, out.normal, nullptr, nullptr, nullptr}, index, stride, f);
+    lights_of_frame(s, out, index * stride, f);
+    return view;
 }
 
 // What the layers and the ground entry points check alike, before any device work (only the last check looks inside the
@@ -565,6 +553,43 @@ int check_pass_arguments(mcrt_scene* const* scenes, int n, const mcrt_config* cf
     for (int i = 1; i < n; ++i)
         if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
     run = true;
+    return MCRT_OK;
+}
+
+// ... and the two light entry points (single- and multi-light planes) ahead of it: `none` is what a call that asks for no plane
+// is told; the config checks read the occlusion plane alone
+template <class Planes>
+int check_light_arguments(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const Planes* d_out, const char* none, size_t stride, bool& run, int& device) {
+    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, none);
+    if (cfg && d_out) {
+        const mcrt_light_planes occ = occlusion_alone(d_out);
+        if (const int rc = check_light_config(cfg, &occ); rc != MCRT_OK) return rc;
+    }
+    return check_pass_arguments(scenes, n, cfg, d_out, stride, run, device);
+}
+// What the two bake entry points check alike (only the last checks look inside the handles: device index and texel count).  No
+// frame size enters: what check_pass_arguments checks of the other arguments is checked here.  run = false with MCRT_OK: no
+// frame or no texel, nothing is written.
+template <class Planes>
+int check_bake_arguments(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const Planes* d_out, const char* none, size_t stride, bool& run,
+                         int& device, int& max_texels) {
+    run = false;
+    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
+    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
+    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, none);
+    const mcrt_bake_planes occ = occlusion_alone(d_out);
+    if (const int rc = check_bake_config(cfg, grid, &occ); rc != MCRT_OK) return rc;
+    if (n == 0) return MCRT_OK;
+    device = scenes[0]->device;
+    max_texels = 0;
+    for (int i = 0; i < n; ++i) {
+        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
+        if (scenes[i]->n_texels > 0 && stride < static_cast<size_t>(scenes[i]->n_texels)) return fail(MCRT_ERR_INVALID, "texel_stride is smaller than a scene's texel count");
+        max_texels = std::max(max_texels, scenes[i]->n_texels);
+    }
+    run = max_texels > 0;
     return MCRT_OK;
 }
 
@@ -924,12 +949,9 @@ int render_reflection_batch_device(mcrt_scene* const* scenes, int n, const mcrt_
 // only where an ambient-occlusion render has built it: the pass never builds the 16 GiB table itself.
 int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes* d_out, size_t stride, hipStream_t stream) {
     // argument checks, before any device work
-    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all three planes are NULL");
-    if (cfg && d_out)
-        if (const int rc = check_light_config(cfg, d_out); rc != MCRT_OK) return rc;
     bool run;
     int device = 0;
-    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    if (const int rc = check_light_arguments(scenes, n, cfg, d_out, "all three planes are NULL", stride, run, device); rc != MCRT_OK || !run) return rc;
     if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
@@ -952,24 +974,12 @@ int render_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_confi
 
 // ---- light bake (mcrt_bake_light_device & co): the light pass's host path over the texel pool instead of a frame — two kernels
 // over one frame record, the scene blob, the handle's owner faces and the device's seed tables; no workspace, no counters and none
-// of the handle's events.  No frame size enters: what check_pass_arguments checks of the other arguments is checked here.
+// of the handle's events.
 int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes* d_out, size_t stride, hipStream_t stream) {
-    // argument checks, before any device work (only the last ones look inside the handles: device index and texel count)
-    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
-    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
-    for (int i = 0; i < n; ++i)
-        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
-    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all five planes are NULL");
-    if (const int rc = check_bake_config(cfg, grid, d_out); rc != MCRT_OK) return rc;
-    if (n == 0) return MCRT_OK;
-    const int device = scenes[0]->device;
-    int max_texels = 0;
-    for (int i = 0; i < n; ++i) {
-        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
-        if (scenes[i]->n_texels > 0 && stride < static_cast<size_t>(scenes[i]->n_texels)) return fail(MCRT_ERR_INVALID, "texel_stride is smaller than a scene's texel count");
-        max_texels = std::max(max_texels, scenes[i]->n_texels);
-    }
-    if (max_texels <= 0) return MCRT_OK;  // no texel: nothing is written
+    // argument checks, before any device work
+    bool run;
+    int device = 0, max_texels = 0;
+    if (const int rc = check_bake_arguments(scenes, n, cfg, grid, d_out, "all five planes are NULL", stride, run, device, max_texels); rc != MCRT_OK || !run) return rc;
     if (const int rc = refuse_extra_lights(scenes, n); rc != MCRT_OK) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
@@ -998,14 +1008,9 @@ int bake_light_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config*
 int render_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_light_planes_multi* d_out, size_t stride,
                                     hipStream_t stream) {
     // argument checks, before any device work
-    if (cfg && d_out && n >= 0 && no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all planes are NULL");
-    if (cfg && d_out) {
-        const mcrt_light_planes occ = occlusion_alone(d_out);
-        if (const int rc = check_light_config(cfg, &occ); rc != MCRT_OK) return rc;
-    }
     bool run;
     int device = 0;
-    if (const int rc = check_pass_arguments(scenes, n, cfg, d_out, stride, run, device); rc != MCRT_OK || !run) return rc;
+    if (const int rc = check_light_arguments(scenes, n, cfg, d_out, "all planes are NULL", stride, run, device); rc != MCRT_OK || !run) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
     ShadeShape shape;
@@ -1033,25 +1038,10 @@ int render_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt
 
 int bake_light_multi_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, int grid, const mcrt_bake_planes_multi* d_out, size_t stride,
                                   hipStream_t stream) {
-    // argument checks, before any device work (only the last ones look inside the handles: device index and texel count)
-    if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
-    if (!cfg || !d_out || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
-    for (int i = 0; i < n; ++i)
-        if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
-    if (no_plane(d_out)) return fail(MCRT_ERR_INVALID, "all planes are NULL");
-    {
-        const mcrt_bake_planes occ = occlusion_alone(d_out);
-        if (const int rc = check_bake_config(cfg, grid, &occ); rc != MCRT_OK) return rc;
-    }
-    if (n == 0) return MCRT_OK;
-    const int device = scenes[0]->device;
-    int max_texels = 0;
-    for (int i = 0; i < n; ++i) {
-        if (scenes[i]->device != device) return fail(MCRT_ERR_INVALID, "the handles of a batch must be on one device");
-        if (scenes[i]->n_texels > 0 && stride < static_cast<size_t>(scenes[i]->n_texels)) return fail(MCRT_ERR_INVALID, "texel_stride is smaller than a scene's texel count");
-        max_texels = std::max(max_texels, scenes[i]->n_texels);
-    }
-    if (max_texels <= 0) return MCRT_OK;  // no texel: nothing is written
+    // argument checks, before any device work
+    bool run;
+    int device = 0, max_texels = 0;
+    if (const int rc = check_bake_arguments(scenes, n, cfg, grid, d_out, "all planes are NULL", stride, run, device, max_texels); rc != MCRT_OK || !run) return rc;
     static const bool decisions = !env_off("MCRT_BUNDLE_DECISIONS");  // the development knobs of `lit` (prepare)
     static const bool inside_fast = !env_off("MCRT_INSIDE_FAST");
     BakeShape shape;
@@ -1365,9 +1355,10 @@ int set_views_cape_batch_device(mcrt_scene* const* scenes, int n, const float (*
 // header's background colour, read on the device) and the device index
 namespace {
 // the launches of the blend, behind every check: frame i of the inputs in_stride pixels on, of the outputs out_stride pixels on
-int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs& in,
-                       const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream,
-                       const ShotExtra* ex) {
+int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_config* cfg, const ShotSpec& spec, const mcrt_shot_inputs& in,
+                       const float* d_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
+    const mcrt_shot* shot = spec.shot;
+    const float floor_occlusion = spec.floor_occlusion;
     ShotShape shape;
     std::memset(&shape, 0, sizeof shape);
     shape.cfg = *cfg;
@@ -1375,6 +1366,7 @@ int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_
     std::memcpy(shape.page_color, shot->page_color, sizeof shape.page_color);
     shape.shadow_strength = shot->shadow_strength, shape.reflectivity = shot->reflectivity, shape.reflection_fade = shot->reflection_fade;
     shape.floor_occlusion = floor_occlusion;
+    std::memcpy(shape.shadow_color, spec.shadow_color, sizeof shape.shadow_color);
     if (!(floor_occlusion > 0.0f)) d_occlusion = nullptr;  // oc = +0 either way: the plane is not read
     std::vector<ShotFrame> frames(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
@@ -1390,37 +1382,31 @@ int launch_shot_frames(mcrt_scene* const* scenes, int n, int device, const mcrt_
         f.out = d_f32 ? d_f32 + to * 4 : nullptr;
         f.out8 = d_u8 ? d_u8 + to * 4 : nullptr;
     }
-    if (!ex)
-        return launch_pass(
-            device, frames, stream, "shot launches", [&](const ShotFrame& f) { return launch_shot(f, shape, stream); },
-            [&](const ShotFrame* d_table, int m) { return launch_shot_batch(d_table, m, shape, stream); });
-    // the _ex kernels; the bounds' identities lie ahead of them in the stream, and each launch takes the entries of its frames
-    ShotShapeEx shape_ex;
-    shape_ex.shot = shape;
-    std::memcpy(shape_ex.shadow_color, ex->shadow_color, sizeof shape_ex.shadow_color);
-    int32_t* d_bounds = ex->bounds ? &ex->bounds[0][0] : nullptr;
+    // the bounds' identities lie ahead of the blend in the stream, and each launch takes the entries of its frames
+    int32_t* d_bounds = spec.bounds ? &spec.bounds[0][0] : nullptr;
     if (d_bounds)
         if (const hipError_t e = launch_shot_bounds_init(d_bounds, n, cfg->width, cfg->height, stream); e != hipSuccess) return hip_fail(e, "shot launches");
     int done = 0;  // frames in the launches so far
     return launch_pass(
-        device, frames, stream, "shot launches", [&](const ShotFrame& f) { return launch_shot_ex(f, shape_ex, d_bounds, stream); },
+        device, frames, stream, "shot launches", [&](const ShotFrame& f) { return launch_shot(f, shape, d_bounds, stream); },
         [&](const ShotFrame* d_table, int m) {
-            const hipError_t e = launch_shot_ex_batch(d_table, m, shape_ex, d_bounds ? d_bounds + 4 * static_cast<size_t>(done) : nullptr, stream);
+            const hipError_t e = launch_shot_batch(d_table, m, shape, d_bounds ? d_bounds + 4 * static_cast<size_t>(done) : nullptr, stream);
             done += m;
             return e;
         });
 }
 }  // namespace
 
-int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
-                                const float* d_occlusion, float floor_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride,
-                                hipStream_t stream, const ShotExtra* ex) {
+int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const ShotSpec& spec, const mcrt_shot_inputs* d_in,
+                                const float* d_occlusion, size_t in_stride, float* d_f32, uint8_t* d_u8, size_t out_stride, hipStream_t stream) {
+    const mcrt_shot* shot = spec.shot;
+    const float floor_occlusion = spec.floor_occlusion;
     // argument checks, before any device work (only the last one looks inside the handles, at their device index)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || !d_in || !d_in->figure || (n > 0 && !scenes)) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n; ++i)
         if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
-    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(spec); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     if (shot->reflection_fade > 0.0f && !d_in->reflection_distance)
         return fail(MCRT_ERR_INVALID, "reflection_distance may be NULL only with reflection_fade == 0");
@@ -1437,20 +1423,22 @@ int composite_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_con
     HIP_TRY(hipSetDevice(device));
     if (stream_capturing(stream)) return fail(MCRT_ERR_INVALID, "a shot cannot be recorded into a caller's graph");
     (void)hipGetLastError();
-    return launch_shot_frames(scenes, n, device, cfg, shot, *d_in, d_occlusion, floor_occlusion, in_stride, d_f32, d_u8, out_stride, stream, ex);
+    return launch_shot_frames(scenes, n, device, cfg, spec, *d_in, d_occlusion, in_stride, d_f32, d_u8, out_stride, stream);
 }
 
 // Render + ground + reflection + ground occlusion + blend, all on `stream` in order.  The render goes through render_batch_device (the handles'
 // event chains, batched kernels where the frames fit them) under the transparent override; the passes and the blend follow it
 // in stream order and take no events.  Nothing is forked beside the render.
-int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion, const float* ground_y,
-                             void* d_scratch, size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream, const ShotExtra* ex) {
+int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config* cfg, const ShotSpec& spec, const float* ground_y, void* d_scratch,
+                             size_t scratch_bytes, float* d_f32, uint8_t* d_u8, size_t stride, hipStream_t stream) {
+    const mcrt_shot* shot = spec.shot;
+    const float floor_occlusion = spec.floor_occlusion;
     // argument checks, before any device work (only the last ones look inside the handles, at their device index)
     if (n < 0) return fail(MCRT_ERR_INVALID, "n_frames must be >= 0");
     if (!cfg || !shot || (n > 0 && (!scenes || !ground_y))) return fail(MCRT_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n; ++i)
         if (!scenes[i]) return fail(MCRT_ERR_INVALID, "NULL scene handle in the batch");
-    if (const int rc = check_shot(shot, ex); rc != MCRT_OK) return rc;
+    if (const int rc = check_shot(spec); rc != MCRT_OK) return rc;
     if (const int rc = check_floor_occlusion(floor_occlusion); rc != MCRT_OK) return rc;
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(ground_y[i])) return fail(MCRT_ERR_INVALID, "ground_y must be finite");
@@ -1470,7 +1458,7 @@ int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config
     if (!d_scratch) return fail(MCRT_ERR_INVALID, "d_scratch is NULL");
     if ((reinterpret_cast<uintptr_t>(d_scratch) & 15u) != 0) return fail(MCRT_ERR_INVALID, "d_scratch is not 16-byte aligned");
     if (scratch_bytes < at.bytes)
-        return fail(MCRT_ERR_INVALID, ex                       ? "scratch_bytes is smaller than mcrt_shot_scratch_bytes_ex"
+        return fail(MCRT_ERR_INVALID, spec.ex                  ? "scratch_bytes is smaller than mcrt_shot_scratch_bytes_ex"
                                       : floor_occlusion > 0.0f ? "scratch_bytes is smaller than mcrt_shot_scratch_bytes_occ"
                                                                : "scratch_bytes is smaller than mcrt_shot_scratch_bytes");
     const int device = scenes[0]->device;
@@ -1507,7 +1495,7 @@ int render_shot_batch_device(mcrt_scene* const* scenes, int n, const mcrt_config
         o.occlusion = plane(at.occlusion);
         if (const int rc = render_ground_occlusion_batch_device(scenes, n, cfg, ground_y, &o, px, stream); rc != MCRT_OK) return rc;
     }
-    return launch_shot_frames(scenes, n, device, cfg, shot, in, plane(at.occlusion), floor_occlusion, px, d_f32, d_u8, stride, stream, ex);
+    return launch_shot_frames(scenes, n, device, cfg, spec, in, plane(at.occlusion), px, d_f32, d_u8, stride, stream);
 }
 
 }  // namespace mcrt_host
@@ -1721,27 +1709,27 @@ int mcrt_render_reflection_batch_device(mcrt_scene* const* scenes, int n_frames,
 
 int mcrt_composite_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
                                      size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8, size_t out_stride_pixels, void* stream) {
-    return composite_shot_batch_device(scenes, n_frames, cfg, shot, d_in, nullptr, 0.0f, in_stride_pixels, d_out_f32, d_out_rgba8, out_stride_pixels,
+    return composite_shot_batch_device(scenes, n_frames, cfg, shot_spec(shot, 0.0f), d_in, nullptr, in_stride_pixels, d_out_f32, d_out_rgba8, out_stride_pixels,
                                        static_cast<hipStream_t>(stream));
 }
 
 int mcrt_composite_shot_batch_device_occ(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const mcrt_shot_inputs* d_in,
                                          const float* d_occlusion, float floor_occlusion, size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8,
                                          size_t out_stride_pixels, void* stream) {
-    return composite_shot_batch_device(scenes, n_frames, cfg, shot, d_in, d_occlusion, floor_occlusion, in_stride_pixels, d_out_f32, d_out_rgba8,
+    return composite_shot_batch_device(scenes, n_frames, cfg, shot_spec(shot, floor_occlusion), d_in, d_occlusion, in_stride_pixels, d_out_f32, d_out_rgba8,
                                        out_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_shot_batch_device(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, const float* ground_y, void* d_scratch,
                                   size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8, size_t frame_stride_pixels, void* stream) {
-    return render_shot_batch_device(scenes, n_frames, cfg, shot, 0.0f, ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, frame_stride_pixels,
+    return render_shot_batch_device(scenes, n_frames, cfg, shot_spec(shot, 0.0f), ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, frame_stride_pixels,
                                     static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_shot_batch_device_occ(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot* shot, float floor_occlusion,
                                       const float* ground_y, void* d_scratch, size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8,
                                       size_t frame_stride_pixels, void* stream) {
-    return render_shot_batch_device(scenes, n_frames, cfg, shot, floor_occlusion, ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8,
+    return render_shot_batch_device(scenes, n_frames, cfg, shot_spec(shot, floor_occlusion), ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8,
                                     frame_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
@@ -1750,28 +1738,22 @@ int mcrt_render_shot_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_sh
     if (!s || !cfg) return fail(MCRT_ERR_INVALID, "NULL argument");
     mcrt_scene* one[1] = {s};
     const size_t px = valid_frame(cfg) ? static_cast<size_t>(cfg->width) * static_cast<size_t>(cfg->height) : 0;
-    return render_shot_batch_device(one, 1, cfg, shot, 0.0f, &ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, px, static_cast<hipStream_t>(stream));
+    return render_shot_batch_device(one, 1, cfg, shot_spec(shot, 0.0f), &ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8, px, static_cast<hipStream_t>(stream));
 }
 
-// the _ex entries: the _occ entries' paths with the shot's additions beside it (a NULL shot is refused there, as theirs is)
+// the _ex entries: the same paths with the shot's additions in the spec (a NULL shot is refused there, as the others' is)
 int mcrt_composite_shot_batch_device_ex(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot, const mcrt_shot_inputs* d_in,
                                         const float* d_occlusion, size_t in_stride_pixels, float* d_out_f32, uint8_t* d_out_rgba8, size_t out_stride_pixels,
                                         int32_t (*d_bounds)[4], void* stream) {
-    ShotExtra ex;
-    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
-    ex.bounds = d_bounds;
-    return composite_shot_batch_device(scenes, n_frames, cfg, shot ? &shot->shot : nullptr, d_in, d_occlusion, shot ? shot->floor_occlusion : 0.0f,
-                                       in_stride_pixels, d_out_f32, d_out_rgba8, out_stride_pixels, static_cast<hipStream_t>(stream), &ex);
+    return composite_shot_batch_device(scenes, n_frames, cfg, shot_spec_ex(shot, d_bounds), d_in, d_occlusion, in_stride_pixels, d_out_f32, d_out_rgba8,
+                                       out_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_shot_batch_device_ex(mcrt_scene* const* scenes, int n_frames, const mcrt_config* cfg, const mcrt_shot_ex* shot, const float* ground_y,
                                      void* d_scratch, size_t scratch_bytes, float* d_out_f32, uint8_t* d_out_rgba8, size_t frame_stride_pixels,
                                      int32_t (*d_bounds)[4], void* stream) {
-    ShotExtra ex;
-    if (shot) std::memcpy(ex.shadow_color, shot->shadow_color, sizeof ex.shadow_color);
-    ex.bounds = d_bounds;
-    return render_shot_batch_device(scenes, n_frames, cfg, shot ? &shot->shot : nullptr, shot ? shot->floor_occlusion : 0.0f, ground_y, d_scratch, scratch_bytes,
-                                    d_out_f32, d_out_rgba8, frame_stride_pixels, static_cast<hipStream_t>(stream), &ex);
+    return render_shot_batch_device(scenes, n_frames, cfg, shot_spec_ex(shot, d_bounds), ground_y, d_scratch, scratch_bytes, d_out_f32, d_out_rgba8,
+                                    frame_stride_pixels, static_cast<hipStream_t>(stream));
 }
 
 int mcrt_render_light_device(mcrt_scene* s, const mcrt_config* cfg, const mcrt_light_planes* d_out, void* stream) {

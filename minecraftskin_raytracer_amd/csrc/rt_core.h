@@ -1329,27 +1329,64 @@ DEV int shadow_mode(const SV& sc, const mcrt_config& cfg) {
     return SHADOW_HARD;
 }
 
+// A light, as the light's arithmetic below takes it — stated once, for any type with position(), disk_radius() and color(i):
+// LightAt, a light by value (one of a frame's extra lights; mcrt.h, "extra lights"), and HeaderLight, the scene header's, which
+// reads each value where the arithmetic uses it.  (The header's light filled into a LightAt up front holds its seven values
+// across a kernel: that moved `lit`'s schedule and raised the scratch of the ground and `shade` kernels.)
+struct LightAt {
+    V3 pos;
+    float radius;
+    float col[3];
+    DEV V3 position() const { return pos; }
+    DEV float disk_radius() const { return radius; }
+    DEV float color(int i) const { return col[i]; }
+};
+template <class SV>
+struct HeaderLight {
+    const SV& sc;
+    DEV V3 position() const { return ld3(sc.hdr->light_pos); }
+    DEV float disk_radius() const { return sc.hdr->light_radius; }
+    DEV float color(int i) const { return sc.hdr->light_color[i]; }
+};
+template <class SV>
+DEV HeaderLight<SV> header_light(const SV& sc) {
+    return HeaderLight<SV>{sc};
+}
+template <class Light>
+DEV LightAt light_value(const Light& l) {
+    return LightAt{l.position(), l.disk_radius(), {l.color(0), l.color(1), l.color(2)}};
+}
 // the disk frame at the light, facing the shaded point (shading.cpp:35-41) — a function of the hit only
 struct LightFrame {
     V3 tangent, bitangent;
 };
-template <class SV>
-DEV LightFrame light_frame(const SV& sc, V3 point) {
-    V3 lpos = ld3(sc.hdr->light_pos);
+DEV LightFrame light_frame_at(V3 lpos, V3 point) {
     V3 toPoint = normalize(point - lpos);
     V3 tangent = (__builtin_fabsf(toPoint.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), toPoint))
                                                      : normalize(cross(mk(0, 1, 0), toPoint));
     return LightFrame{tangent, cross(toPoint, tangent)};
 }
-// one stratified-disk light sample position (shading.cpp:46-53)
 template <class SV>
-DEV V3 light_sample_on_frame(const SV& sc, const LightFrame& f, float d0, float d1) {
+DEV LightFrame light_frame(const SV& sc, V3 point) {
+    return light_frame_at(ld3(sc.hdr->light_pos), point);
+}
+// one stratified-disk light sample (shading.cpp:46-53): its offset from the centre of a light of that radius, and its position
+DEV V3 light_sample_offset(float radius, const LightFrame& f, float d0, float d1) {
     float angle = kTwoPi * d0;
-    float rr = sc.hdr->light_radius * sqrt_pos(d1);  // a draw: 0 or at least 2^-32
+    float rr = radius * sqrt_pos(d1);  // a draw: 0 or at least 2^-32
     // inlined libm kernels: calls here would serialise the independent samples of a hit
     float sn, cs;
     mcrt_sincosf(angle, &sn, &cs);
-    V3 off = f.tangent * (rr * cs) + f.bitangent * (rr * sn);
+    return f.tangent * (rr * cs) + f.bitangent * (rr * sn);
+}
+template <class Light>
+DEV V3 light_sample_at(const Light& l, const LightFrame& f, float d0, float d1) {
+    V3 off = light_sample_offset(l.disk_radius(), f, d0, d1);
+    return l.position() + off;
+}
+template <class SV>
+DEV V3 light_sample_on_frame(const SV& sc, const LightFrame& f, float d0, float d1) {  // (written out: through light_sample_at, `lit`'s schedule moves)
+    V3 off = light_sample_offset(sc.hdr->light_radius, f, d0, d1);
     return ld3(sc.hdr->light_pos) + off;
 }
 template <class SV>
@@ -1398,14 +1435,12 @@ DEV float soft_shadow(const SV& sc, V3 point, V3 normal, int samples, uint32_t s
     return static_cast<float>(lit) / static_cast<float>(samples);
 }
 
-// shade :62-96 with ShadingParams{} (kd .75, ks .15, ambient .20, shininess 16 — shading.h:9-14;
-// renderTile always passes the defaults, tile_renderer.cpp:106-107) and the visibility term given.
-template <class SV>
-DEV C4 shade(const SV& sc, const Hit& hit, V3 viewDir, float vis) {
-    const float kd = 0.75f, ks = 0.15f, ambient = 0.20f, shininess = 16.0f;
+// shade :62-96 for light l with ShadingParams{kd .75, ks .15, ambient, shininess 16} and the visibility term given
+template <class Light>
+DEV C4 shade_at(const Light& l, const Hit& hit, V3 viewDir, float ambient, float vis) {
+    const float kd = 0.75f, ks = 0.15f, shininess = 16.0f;
     C4 tex = hit.tex;
-    V3 lpos = ld3(sc.hdr->light_pos);
-    const float* lc = sc.hdr->light_color;
+    V3 lpos = l.position();
     V3 L = normalize(lpos - hit.p);
     V3 N = normalize(hit.n);
     V3 V = normalize(viewDir);
@@ -1415,52 +1450,17 @@ DEV C4 shade(const SV& sc, const Hit& hit, V3 viewDir, float vis) {
     float ndh = smax(0.0f, dot(N, H));
     float kspec = ks * dev_powf(ndh, shininess) * vis;
     C4 out;
-    out.r = tex.r * ambient + tex.r * lc[0] * kdiff + lc[0] * kspec;
-    out.g = tex.g * ambient + tex.g * lc[1] * kdiff + lc[1] * kspec;
-    out.b = tex.b * ambient + tex.b * lc[2] * kdiff + lc[2] * kspec;
+    out.r = tex.r * ambient + tex.r * l.color(0) * kdiff + l.color(0) * kspec;
+    out.g = tex.g * ambient + tex.g * l.color(1) * kdiff + l.color(1) * kspec;
+    out.b = tex.b * ambient + tex.b * l.color(2) * kdiff + l.color(2) * kspec;
     out.a = tex.a;
     return clamp4(out);
 }
-
-// ---- a light that is not the scene header's (mcrt.h, "extra lights").  light_frame, light_sample_on_frame and shade above
-// stated for a light given by value; they stay as they are, so the code of the kernels that call them does not move.
-struct LightAt {
-    V3 pos;
-    float radius;
-    float col[3];
-};
-DEV LightFrame light_frame_at(V3 lpos, V3 point) {  // shading.cpp:35-41
-    V3 toPoint = normalize(point - lpos);
-    V3 tangent = (__builtin_fabsf(toPoint.x) < 0.9f) ? normalize(cross(mk(1, 0, 0), toPoint))
-                                                     : normalize(cross(mk(0, 1, 0), toPoint));
-    return LightFrame{tangent, cross(toPoint, tangent)};
-}
-DEV V3 light_sample_at(const LightAt& l, const LightFrame& f, float d0, float d1) {  // shading.cpp:46-53
-    float angle = kTwoPi * d0;
-    float rr = l.radius * sqrt_pos(d1);
-    float sn, cs;
-    mcrt_sincosf(angle, &sn, &cs);
-    V3 off = f.tangent * (rr * cs) + f.bitangent * (rr * sn);
-    return l.pos + off;
-}
-// shade :62-96 for that light with ShadingParams{kd .75, ks .15, ambient, shininess 16} and the visibility term given
-DEV C4 shade_at(const LightAt& l, const Hit& hit, V3 viewDir, float ambient, float vis) {
-    const float kd = 0.75f, ks = 0.15f, shininess = 16.0f;
-    C4 tex = hit.tex;
-    V3 L = normalize(l.pos - hit.p);
-    V3 N = normalize(hit.n);
-    V3 V = normalize(viewDir);
-    float ndl = smax(0.0f, dot(N, L));
-    float kdiff = kd * ndl * vis;
-    V3 H = normalize(L + V);
-    float ndh = smax(0.0f, dot(N, H));
-    float kspec = ks * dev_powf(ndh, shininess) * vis;
-    C4 out;
-    out.r = tex.r * ambient + tex.r * l.col[0] * kdiff + l.col[0] * kspec;
-    out.g = tex.g * ambient + tex.g * l.col[1] * kdiff + l.col[1] * kspec;
-    out.b = tex.b * ambient + tex.b * l.col[2] * kdiff + l.col[2] * kspec;
-    out.a = tex.a;
-    return clamp4(out);
+// the header's light with ShadingParams{} (ambient .20 — shading.h:9-14; renderTile always passes the defaults,
+// tile_renderer.cpp:106-107)
+template <class SV>
+DEV C4 shade(const SV& sc, const Hit& hit, V3 viewDir, float vis) {
+    return shade_at(header_light(sc), hit, viewDir, 0.20f, vis);
 }
 
 // ---------------------------------------------------------------------------------------------
